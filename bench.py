@@ -2,6 +2,17 @@
 """bench.py — BASELINE.json's headline metric on the MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload linear|adjoint] [--scaling weak|strong]
+                    [--dump-outputs DIR] [--full [--no-extras] [--no-cpu-baseline]]
+
+A plain run sets up, warms up, times the K steps, writes the outputs (`--dump-outputs`) and prints the line — nothing
+else.  `--full` adds everything below that is not the headline figure: the full-size parity solve (rel_err,
+rel_err_vs_reference, nfe), the roofline of the dominant launch, the solver-only rate, the CPU baseline and the
+same-device references, the other configurations / regimes and the extras file.
+
+`--dump-outputs DIR`: after the timed steps, what the last one computed, as DIR/<name>.npy (< 64 MB, rank 0's shard):
+linear  `y` (the state after the last timed trial step, 65536 x 128 fp32) and `step` (fp64: t0, t1, next dt, accepted,
+rejected); adjoint  `y_end` (y(1) of the last pass) and `param_grads` (the MLP's flat parameter gradient).  The inputs are
+seeded: the same arguments give the same inputs in every run.
 
 `--gpus N` with N > 1 and no WORLD_SIZE in the environment re-launches itself as N ranks (one process per GPU,
 `python -m torch.distributed.run ... bench.py`, rendezvous on 127.0.0.1, backend nccl = RCCL); under
@@ -25,17 +36,18 @@ Workloads
            (RCCL over xGMI) at the end of backward (torchdiffeq_amd.dist.odeint_adjoint_sharded).  One "step" = one
            forward + backward pass; value = RK stages (forward + backward solves) per second.
 
-Timing: W warm-up steps, then 5 blocks of exactly K steps each, every block bracketed by a barrier +
-torch.cuda.synchronize(); per block the MAX over ranks; `value` / `ms_per_step` are the MEDIAN block (min / max in
-`blocks`).
+Timing: W warm-up steps, then K timed steps in all, as min(5, K) blocks of near-equal size (3 for adjoint), every block
+bracketed by a barrier + torch.cuda.synchronize(); per block the MAX over ranks; `value` / `ms_per_step` are the MEDIAN
+block's (min / max in `blocks`).
 
 Output: ONE stdout line — the contract line, a whitelist of scalars < 4 KB at every N (`contract_line`): metric, value,
 unit, n_gpus, steps, warmup, ms_per_step, scaling, dtype, data, config{workload, ...}, roofline{bound, kernel, achieved,
 peak, frac (= in situ), frac_hbm_cold, algorithmic_bytes_per_launch, avg_launch_ms, avg_launch_ms_cold, traffic (=
 l2_fabric_bytes per launch from the committed PMC summary)}, cpu_baseline{value, cores, kind, sample,
 reference_8core_value}, rel_err_vs_reference, nfe / reference_nfe, rccl_ranks / backend and — N > 1 — one scalar pair per
-regime (weak, strong, lockstep, adjoint.{strong, weak}).  EVERYTHING ELSE goes to `gpurun_out/bench_extras_n{N}.json`
-(TDEQ_BENCH_EXTRAS_DIR overrides the directory; the line names the file):
+regime (weak, strong, lockstep, adjoint.{strong, weak}); roofline, cpu_baseline, the parity figures and the regime pairs
+with `--full` only.  EVERYTHING ELSE goes to the extras file `bench_extras_n{N}.json` (`--full`; TDEQ_BENCH_EXTRAS_DIR
+sets the directory; the line names it):
   roofline      the launch the north star names = the step's 7-words-per-element stage combine (234.9 MB; the 8-word
                 stage_combine_err launch is marginally heavier by total time; with carried partial sums row 4 +
                 the prefix of row 5: stage_combine_multi_kernel<float, 4>, 2 outputs).  `frac` = IN SITU: its launches inside
@@ -210,11 +222,13 @@ def write_extras(out):
         return None
 
 
-def emit(out):
-    """Extras to their file (and a digest to stderr); the contract line LAST on stdout, alone."""
-    path = write_extras(out)
-    sys.stderr.write(f"bench.py: extras -> {path}\n")
-    sys.stderr.flush()
+def emit(out, full=True):
+    """Extras to their file (and a digest to stderr; `--full` only); the contract line LAST on stdout, alone."""
+    path = None
+    if full:
+        path = write_extras(out)
+        sys.stderr.write(f"bench.py: extras -> {path}\n")
+        sys.stderr.flush()
     print(contract_line(out, path), flush=True)
 
 
@@ -318,8 +332,13 @@ def main():
     ap.add_argument("--scaling", choices=("weak", "strong"), default=None,
                     help="default: strong when --gpus > 1 (BASELINE.json's metric is quoted at batch 65536 in total: the "
                          "ONE batch split over the GPUs), weak = every GPU its own 65536 rows")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="only the contract line's own measurement")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: parity vs the reference, roofline, CPU baseline, the "
+                         "other configurations and regimes (the extras file)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) no CPU baseline, no same-device reference")
+    ap.add_argument("--no-extras", action="store_true", help="(--full) no extras beyond the contract line's own objects")
     args = ap.parse_args()
     if args.scaling is None:
         args.scaling = "strong" if args.gpus > 1 else "weak"
@@ -327,6 +346,10 @@ def main():
         args.steps = 200 if args.workload == "linear" else 5
     if args.warmup is None:
         args.warmup = 20 if args.workload == "linear" else 2
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs:
+        args.dump_outputs = os.path.abspath(args.dump_outputs)     # (the ranks of a self-launch share it)
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args))
@@ -368,20 +391,22 @@ def main():
         if rank == 0:
             out["comm"] = census
             out["rccl_ranks"], out["backend"] = census["rccl_ranks"], census["backend"]
-        extras = not args.no_extras
+        extras = args.full and not args.no_extras
         # The contract line is measured; everything below only adds objects to it.  If an extra hangs (a collective
         # that never completes on some node), every rank's watchdog fires after the same delay: rank 0 prints the
         # line as far as it got — marked, with the name of the measurement that hung — and all ranks leave.
         ex = _Extras(rank, out)
-        watchdog = _Watchdog(float(os.environ.get("TDEQ_BENCH_EXTRAS_TIMEOUT", "240")), rank, out, ex.progress)
+        watchdog = _Watchdog(float(os.environ.get("TDEQ_BENCH_EXTRAS_TIMEOUT", "240")), rank, out, ex.progress) \
+            if args.full else None
         if extras and world > 1:
             # the same ranks on the other regime and on the workload that communicates (short runs)
             other = argparse.Namespace(**vars(args))
             other.scaling = "strong" if args.scaling == "weak" else "weak"
             other.steps, other.warmup = min(args.steps, 100), min(args.warmup, 20)
+            other.dump_outputs = None
 
             def other_regime():
-                o2, _, _ = run_linear(other, rank, world, device, parity=False)
+                o2, _, _ = run_linear(other, rank, world, device, parity=False, block_steps=[other.steps] * N_BLOCKS)
                 return None if o2 is None else {k: o2[k] for k in ("value", "unit", "ms_per_step", "scaling", "config",
                                                                       "blocks")}
             ex.run(other.scaling, other_regime)
@@ -462,7 +487,7 @@ def main():
                     b = kernel_breakdown(make_stepper(field, y0)._trial_step, 20)
                 return {k: b[k] for k in ("solver_kernel_us", "func_kernel_us", "floor_us", "dispatches_per_call")}
             ex.run("breakdown_default_heuristic", default_breakdown)
-        if rank == 0 and world == 1 and not args.no_cpu_baseline:
+        if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
             def eager():
                 with torch.no_grad():
                     return eager_gpu_baseline(field, y0, 0.05)
@@ -473,13 +498,14 @@ def main():
             out["cpu_baseline"] = cpu_baseline()
             if extras and os.environ.get("TDEQ_BENCH_TUNABLEOP", "1") != "0":
                 ex.run("func_lever_tunableop", lambda: tunableop_lever(args))
-        watchdog.cancel()
-        if rank == 0:
+        if watchdog is not None:
+            watchdog.cancel()
+        if rank == 0 and args.full:
             out["extras_s"] = ex.seconds
     if rank == 0:
         if os.environ.get("TDEQ_BENCH_NOTE"):
             out["note"] = os.environ["TDEQ_BENCH_NOTE"]
-        emit(out)
+        emit(out, args.full)
     if torch.distributed.is_initialized():
         torch.distributed.destroy_process_group()
 

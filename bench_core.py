@@ -59,17 +59,27 @@ def max_over_ranks(x, world, device):
     return float(v.item())
 
 
+def split_steps(steps, n_blocks=N_BLOCKS):
+    """`steps` timed calls in all, as min(n_blocks, steps) blocks of near-equal size (the larger ones first)."""
+    n = max(1, min(n_blocks, steps))
+    return [steps // n + (1 if i < steps % n else 0) for i in range(n)]
+
+
+def _block_sizes(steps, n_blocks):
+    return list(steps) if isinstance(steps, (list, tuple)) else [steps] * n_blocks
+
+
 def timed_blocks(step_fn, steps, warmup, world, device, n_blocks=N_BLOCKS):
-    """W warm-up calls, then n_blocks blocks of exactly `steps` calls; per block barrier + synchronize on both sides
-    and the max over ranks.  Returns the per-block seconds."""
+    """W warm-up calls, then n_blocks blocks of exactly `steps` calls (or, `steps` a list, one block per entry of that
+    many calls); per block barrier + synchronize on both sides and the max over ranks.  Returns the per-block seconds."""
     for _ in range(warmup):
         step_fn()
     blocks = []
     timed_blocks.local = []          # this rank's own block times, before the barrier (skew diagnosis at N > 1)
-    for _ in range(n_blocks):
+    for size in _block_sizes(steps, n_blocks):
         dist_sync(world)
         t0 = time.perf_counter()
-        for _ in range(steps):
+        for _ in range(size):
             step_fn()
         torch.cuda.synchronize()
         timed_blocks.local.append(time.perf_counter() - t0)
@@ -170,7 +180,7 @@ def time_steps(solver, steps, warmup, world, device, n_blocks=N_BLOCKS):
 
 
 def block_stats(blocks, steps):
-    ms = sorted(1e3 * b / steps for b in blocks)
+    ms = sorted(1e3 * b / n for b, n in zip(blocks, _block_sizes(steps, len(blocks))))
     return {"median": statistics.median(ms), "min": ms[0], "max": ms[-1], "n_blocks": len(ms), "steps_per_block": steps}
 
 
@@ -393,8 +403,28 @@ def strong_breakdown(step_fn, steps, wall_ms, world, rank):
     return out
 
 
-def run_linear(args, rank, world, device, parity=True):
+def dump_outputs(directory, arrays, limit_bytes=64 * 2 ** 20):
+    """`--dump-outputs DIR`: every array as DIR/<name>.npy (float32 stays float32, everything else float64)."""
+    import numpy as np
+    host = {}
+    for name, a in arrays.items():
+        a = a.detach().cpu() if isinstance(a, torch.Tensor) else torch.as_tensor(a)
+        host[name] = a.numpy().astype(np.float32 if a.dtype == torch.float32 else np.float64, copy=False)
+    total = sum(a.nbytes for a in host.values())
+    assert total <= limit_bytes, f"--dump-outputs: {total} bytes > {limit_bytes}"
+    os.makedirs(directory, exist_ok=True)
+    for name, a in host.items():
+        np.save(os.path.join(directory, name + ".npy"), a)
+
+
+def run_linear(args, rank, world, device, parity=True, block_steps=None):
+    """The headline workload: W warm-up trial steps, then `args.steps` timed ones (in blocks: `block_steps`, default
+    split_steps(args.steps)).  Without `args.full` only that; with it (the default for callers that do not say) also the
+    full-size parity solve, the dispatch-stamped roofline of the dominant launch, the HBM-cold and solver-only rates."""
     import torchdiffeq_amd as tda
+    full = getattr(args, "full", True)
+    parity = parity and full
+    sizes = block_steps or split_steps(args.steps)
     strong = args.scaling == "strong" and world > 1
     if strong:
         from torchdiffeq_amd.dist import shard_rows
@@ -435,40 +465,51 @@ def run_linear(args, rank, world, device, parity=True):
     auto_graph = strong and n <= (1 << 21) and os.environ.get("TDEQ_BENCH_GRAPH", "1") != "0"
     solver = make_stepper(field, y0, hip_graph=auto_graph)
     every = 1 if args.steps <= 50 else 4
-    timed = EventTimedKernels(solver.kernels, dominant_terms=5, n_events=N_BLOCKS * args.steps // every + 1, every=every)
-    solver.kernels = timed
-    solver.ops.k = timed        # the elementwise kernels are issued through solver.ops
+    timed = None
+    if full:        # the roofline's dispatch-stamped events (a plain run launches the kernels as a caller does)
+        timed = EventTimedKernels(solver.kernels, dominant_terms=5, n_events=sum(sizes) // every + 1, every=every)
+        solver.kernels = timed
+        solver.ops.k = timed        # the elementwise kernels are issued through solver.ops
     with torch.no_grad():
         for _ in range(args.warmup):
             solver._trial_step()
-        timed.armed = True
-        blocks = timed_blocks(solver._trial_step, args.steps, 0, world, device)
-        timed.armed = False
-    st = block_stats(blocks, args.steps)
+        if timed is not None:
+            timed.armed = True
+        blocks = timed_blocks(solver._trial_step, sizes, 0, world, device)
+        if timed is not None:
+            timed.armed = False
+    if rank == 0 and getattr(args, "dump_outputs", None):
+        # what the last timed trial step left a caller: the state and where the solve stands
+        dump_outputs(args.dump_outputs, {
+            "y": solver.y1.reshape(y0.shape),
+            "step": torch.tensor([solver.t0, solver.t1, float(solver.dt), solver.n_accepted, solver.n_rejected],
+                                 dtype=torch.float64)})
+    st = block_stats(blocks, sizes)
     ms_per_step = st["median"]
     per_rank = None
     if world > 1:       # every rank's own median block (no barrier inside): shows a straggler GPU, if any
         per_rank = [None] * world
-        torch.distributed.all_gather_object(per_rank, 1e3 * statistics.median(timed_blocks.local) / args.steps)
+        torch.distributed.all_gather_object(per_rank, statistics.median(1e3 * b / k for b, k in
+                                                                        zip(timed_blocks.local, sizes)))
     # weak: every rank did its own stages; strong: a stage of the global batch is done when every shard's is
     value = 6e3 / ms_per_step * (1 if strong else world)
 
     breakdown = None
-    if os.environ.get("TDEQ_BENCH_BREAKDOWN") and world == 1:
+    if full and os.environ.get("TDEQ_BENCH_BREAKDOWN") and world == 1:
         with torch.no_grad():
             breakdown = kernel_breakdown(solver._trial_step, min(20, args.steps))
-    if strong:
+    if full and strong:
         # launch gaps or kernel floor?  (every rank profiles its own shard's steps; collective: all ranks call this)
         with torch.no_grad():
             breakdown = strong_breakdown(solver._trial_step, min(50, args.steps), ms_per_step, world, rank)
 
     out = None
     if rank == 0:
-        kernel_ms = [a.elapsed_time(b) for a, b in timed.events]
+        kernel_ms = [a.elapsed_time(b) for a, b in timed.events] if timed is not None else []
         avg_ms = sum(kernel_ms) / max(len(kernel_ms), 1)
         bytes_per_launch = 7 * n * 4
         achieved = bytes_per_launch / (avg_ms * 1e-3) / 1e9 if kernel_ms else None
-        traffic, traffic_src = pmc_traffic(timed.kernel) if n == BATCH * DIM else (None, None)
+        traffic, traffic_src = pmc_traffic(timed.kernel) if (full and n == BATCH * DIM) else (None, None)
         out = {
             "metric": "dopri5 RK-stages/sec at batch=65536x dim=128 (end-to-end adaptive trial steps incl. func, "
                       "error norm, read-back and host controller)",
@@ -484,19 +525,21 @@ def run_linear(args, rank, world, device, parity=True):
                        "hip_graph": bool(solver.hip_graph),
                        "backend": torch.distributed.get_backend() if world > 1 else None},
             "blocks": {"ms_per_step": st, "value_is": "median block", "per_rank_ms_per_step": per_rank},
-            "rel_err_vs_reference": rel_err_ref,
-            "rel_err_vs_reference_definition": "max|y - y_ref| over the sample rows / max|y_ref| of odeint(t=[0,1]) at "
-                                               "full size, y_ref = rtqichen/torchdiffeq v0.2.5 on the same inputs "
-                                               "(tests/golden/fullsize_cfg2.npz; rank 0's shard = SURVEY cfg2)",
-            "nfe": nfe[0], "reference_nfe": ref_nfe,
-            "rel_err": rel_err,
-            "rel_err_definition": "max|y - y_exact| / max|y_exact| vs the closed form y0 @ expm(A)^T (the reference's "
-                                  "own fp32 result scores 2.2-2.8e-6 on this)",
-            "odeint_t01_wall_s": odeint_wall,
         }
+        if parity:
+            out.update({
+                "rel_err_vs_reference": rel_err_ref,
+                "rel_err_vs_reference_definition": "max|y - y_ref| over the sample rows / max|y_ref| of odeint(t=[0,1]) "
+                                                   "at full size, y_ref = rtqichen/torchdiffeq v0.2.5 on the same inputs "
+                                                   "(tests/golden/fullsize_cfg2.npz; rank 0's shard = SURVEY cfg2)",
+                "nfe": nfe[0], "reference_nfe": ref_nfe,
+                "rel_err": rel_err,
+                "rel_err_definition": "max|y - y_exact| / max|y_exact| vs the closed form y0 @ expm(A)^T (the "
+                                      "reference's own fp32 result scores 2.2-2.8e-6 on this)",
+                "odeint_t01_wall_s": odeint_wall})
         if breakdown is not None:
             out["breakdown"] = breakdown
-        if n != BATCH * DIM:
+        if full and n != BATCH * DIM:
             # a strong-scaling shard: its steps are hipGraph replays (no dispatch-stamped events), so the dominant
             # launch's duration comes from the breakdown's kernel-activity records of rank 0
             top = ((breakdown or {}).get("per_rank") or [{}])[0].get("top_kernels", {})
@@ -519,7 +562,7 @@ def run_linear(args, rank, world, device, parity=True):
                     "note": f"1/{world} shard: the launch's seven streams ({bytes_per_launch / 1e6:.1f} MB) fit the 256 MiB "
                             "Infinity Cache, so this is a cache rate measured against the HBM peak; the full-size kernel's "
                             "HBM figures are in the N = 1 line (`roofline.frac`, `roofline.frac_hbm_cold`)"}
-        if n == BATCH * DIM:
+        if full and n == BATCH * DIM:
             out["roofline"] = {
                 "bound": "hbm", "kernel": timed.kernel, "achieved": achieved,
                 "kernel_is": "the step's 7-words-per-element stage-combine launch (234.9 MB): row 5 launched row by row "
@@ -583,8 +626,11 @@ class AllReduceProbe:
         dist.all_reduce = self._orig
 
 
-def adjoint_pass(world, rank, device, rows_per_rank, steps, warmup, group_forced=False, graph=False):
+def adjoint_pass(world, rank, device, rows_per_rank, steps, warmup, group_forced=False, graph=False, full=True,
+                 dump=None):
     """cfg3 on this rank's `rows_per_rank` rows: K forward + backward passes through odeint_adjoint_sharded.
+    full=False: the timed passes alone (no profiled pass, no instrumented one); `dump` = a directory for what the last
+    timed pass computed (y(1) and the parameter gradients).
     graph=True: options={'hip_graph': 'auto'} (forward and, inherited, backward solve as captured trial steps where the
     state is small enough); the field's own Python evaluation counter does not run during replays, so the evaluation
     counts of such a pass are not reported."""
@@ -617,7 +663,17 @@ def adjoint_pass(world, rank, device, rows_per_rank, steps, warmup, group_forced
         stats["nfe_fwd"], field.nfe = field.nfe, 0
         y[-1].pow(2).sum().backward()
         stats["nfe_bwd"] = field.nfe
+        if dump:
+            stats["y_end"] = y[-1].detach()
     blocks = timed_blocks(one, steps, warmup, world, device, n_blocks=3)
+    if dump and rank == 0:
+        dump_outputs(dump, {"y_end": stats["y_end"],
+                            "param_grads": torch.cat([p.grad.detach().reshape(-1) for p in params])})
+    if not full:
+        st = block_stats(blocks, steps)
+        return {"rows_per_gpu": rows_per_rank, "ms_per_pass": st["median"], "blocks": st,
+                "nfe_fwd": stats["nfe_fwd"], "nfe_bwd": stats["nfe_bwd"],
+                "rk_stages_per_pass": (stats["nfe_fwd"] - 2) + (stats["nfe_bwd"] - 2)}
     # launch gaps or kernel floor, per rank: one more pass under the kernel-activity profiler
     breakdown = strong_breakdown(one, 1, block_stats(blocks, steps)["median"], world, rank)
     breakdown["unit_note"] = "per forward + backward pass; func = the MLP, its autograd VJPs and torch glue kernels"
@@ -655,7 +711,8 @@ def adjoint_pass(world, rank, device, rows_per_rank, steps, warmup, group_forced
 def run_adjoint(args, rank, world, device):
     strong = args.scaling == "strong"
     rows = ADJ_BATCH // world if strong else ADJ_BATCH
-    r = adjoint_pass(world, rank, device, rows, args.steps, args.warmup)
+    r = adjoint_pass(world, rank, device, rows, split_steps(args.steps, 3), args.warmup, full=getattr(args, "full", True),
+                     dump=getattr(args, "dump_outputs", None))
     if rank != 0:
         return None
     # strong: a stage of the global batch is done when every shard's is; weak: ranks' stages add up

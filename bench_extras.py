@@ -400,8 +400,8 @@ def tunableop_lever(args):
         t0 = time.perf_counter()
         try:
             r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(args.steps),
-                                "--warmup", str(max(args.warmup, 10)), "--no-extras", "--no-cpu-baseline"], env=env,
-                               capture_output=True, text=True, timeout=float(os.environ.get("TDEQ_TUNABLEOP_TIMEOUT", "150")))
+                                "--warmup", str(max(args.warmup, 10)), "--full", "--no-extras", "--no-cpu-baseline"],
+                               env=env, capture_output=True, text=True, timeout=float(os.environ.get("TDEQ_TUNABLEOP_TIMEOUT", "150")))
         except subprocess.TimeoutExpired:
             return {"error": "tuning did not finish within the time bound"}
         took = time.perf_counter() - t0

@@ -108,14 +108,54 @@ def test_error_line_is_small_and_parseable(capsys):
     assert len(text) < 4096 and json.loads(text)["value"] is None
 
 
+def test_timed_steps_are_split_into_blocks_that_add_up():
+    """`--steps K` times K steps in all: min(5, K) blocks of near-equal size, the median block's ms per step."""
+    b = _bench()
+    for k in (1, 2, 5, 7, 200, 1001):
+        sizes = b.split_steps(k)
+        assert sum(sizes) == k and len(sizes) == min(5, k) and max(sizes) - min(sizes) <= 1
+    assert b.split_steps(5, 3) == [2, 2, 1]
+    st = b.block_stats([0.002, 0.004, 0.003], [2, 2, 1])
+    assert st["median"] == pytest.approx(2.0) and st["min"] == pytest.approx(1.0) and st["max"] == pytest.approx(3.0)
+    assert b.block_stats([0.002, 0.004], 2)["median"] == pytest.approx(1.5)     # equal blocks, as the tools call it
+
+
+@pytest.mark.gpu
+def test_plain_command_is_lean_and_dumps_its_outputs(tmp_path):
+    """`python bench.py --gpus 1 --steps 3 --warmup 1 --dump-outputs DIR` without `--full`: one small line with the
+    headline fields and no extras (no roofline, no CPU baseline, no extras file); DIR holds the last timed step's state,
+    and a second run with the same arguments writes the same arrays (the step counts exactly, the state to rounding)."""
+    import numpy as np
+    lines = []
+    for run in ("a", "b"):
+        env = dict(os.environ, TDEQ_BENCH_EXTRAS_DIR=str(tmp_path / "extras"))
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                            "--dump-outputs", str(tmp_path / run)], env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+        stdout_lines = r.stdout.strip().splitlines()
+        assert stdout_lines and stdout_lines[-1].startswith("{") and len(stdout_lines[-1]) < 4096
+        lines.append(json.loads(stdout_lines[-1]))
+    line = lines[0]
+    assert CONTRACT_KEYS <= set(line) and line["steps"] == 3 and line["warmup"] == 1 and line["dtype"] == "f32"
+    assert line["value"] == pytest.approx(6e3 / line["ms_per_step"], rel=1e-5) and line["higher_is_better"] is True
+    assert not {"roofline", "cpu_baseline", "rel_err_vs_reference", "nfe"} & set(line) and line["extras_file"] is None
+    assert not os.path.exists(tmp_path / "extras")
+    y, step = np.load(tmp_path / "a" / "y.npy"), np.load(tmp_path / "a" / "step.npy")
+    assert y.shape == (65536, 128) and y.dtype == np.float32 and np.isfinite(y).all()
+    assert step.shape == (5,) and step.dtype == np.float64 and step[3] + step[4] == 4 and 0 < step[0] <= step[1]
+    # same seeded inputs, same launch sequence: the second run lands on the same state (the field's GEMM is hipBLASLt's)
+    assert np.array_equal(step[3:], np.load(tmp_path / "b" / "step.npy")[3:])
+    assert np.allclose(y, np.load(tmp_path / "b" / "y.npy"), rtol=1e-6, atol=1e-7)
+
+
 @pytest.mark.gpu
 def test_driver_command_prints_one_small_line(tmp_path):
-    """`python bench.py --gpus 1 --steps 2 --warmup 1` (the driver's command shape): exactly one stdout line that is
-    JSON, it is the LAST line, < 4 KB, with `roofline` and `cpu_baseline`; the extras file exists and holds the rest."""
+    """`python bench.py --gpus 1 --steps 2 --warmup 1 --full` (the driver's command shape): exactly one stdout line that
+    is JSON, it is the LAST line, < 4 KB, with `roofline` and `cpu_baseline`; the extras file exists and holds the rest."""
     # (the TunableOp child of the extras is a second bench process of ~1 min: not in the test suite)
     env = dict(os.environ, TDEQ_BENCH_EXTRAS_DIR=str(tmp_path), TDEQ_BENCH_TUNABLEOP="0")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1"],
-                       env=env, capture_output=True, text=True, timeout=1200)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+                        "--full"], env=env, capture_output=True, text=True, timeout=1200)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     stdout_lines = r.stdout.strip().splitlines()
     json_lines = [ln for ln in stdout_lines if ln.startswith("{")]

@@ -44,7 +44,7 @@ def test_bench_self_launches_two_ranks_gloo(tmp_path):
     env.pop("WORLD_SIZE", None)
     if torch.cuda.device_count() < 2:
         env["TDEQ_DIST_BACKEND"] = "gloo"
-    r, lines, out = _run_bench(["--gpus", "2", "--steps", "10", "--warmup", "3"], env, tmp_path, 900)
+    r, lines, out = _run_bench(["--gpus", "2", "--steps", "10", "--warmup", "3", "--full"], env, tmp_path, 900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     assert len(lines) == 1 and r.stdout.strip().splitlines()[-1] == lines[0], r.stdout[-2000:]
     assert len(lines[0]) < 4096, len(lines[0])
@@ -89,7 +89,7 @@ def test_bench_self_launches_eight_ranks_gloo(tmp_path):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", TDEQ_DIST_BACKEND="gloo")
     env.pop("WORLD_SIZE", None)
     t0 = time.time()
-    r, lines, out = _run_bench(["--gpus", "8", "--steps", "5", "--warmup", "2"], env, tmp_path, 900)
+    r, lines, out = _run_bench(["--gpus", "8", "--steps", "5", "--warmup", "2", "--full"], env, tmp_path, 900)
     elapsed = time.time() - t0
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     assert len(lines) == 1 and r.stdout.strip().splitlines()[-1] == lines[0], r.stdout[-2000:]
@@ -121,8 +121,8 @@ def test_bench_census_through_rccl_at_world_size_one(tmp_path):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", TDEQ_DIST_FORCE_INIT="1", WORLD_SIZE="1", RANK="0", LOCAL_RANK="0",
                MASTER_ADDR="127.0.0.1", MASTER_PORT="29723")
     env.pop("TDEQ_DIST_BACKEND", None)
-    r, lines, out = _run_bench(["--gpus", "1", "--steps", "5", "--warmup", "2", "--no-extras", "--no-cpu-baseline"], env,
-                               tmp_path, 600)
+    r, lines, out = _run_bench(["--gpus", "1", "--steps", "5", "--warmup", "2", "--full", "--no-extras",
+                                "--no-cpu-baseline"], env, tmp_path, 600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     line = json.loads(lines[-1])
     assert len(lines) == 1 and len(lines[0]) < 4096
