@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define TDEQ_ABI_VERSION 21
+#define TDEQ_ABI_VERSION 22
 #define TDEQ_F32 0
 #define TDEQ_F64 1
 /* interleaved (re, im) complex states — accepted by the NORM entry points only (tdeq_error_norm, tdeq_error_norm_partial[_ctrl],
@@ -536,6 +536,67 @@ int tdeq_adams_correct(void* y_out, void* dy_out, const void* f, const void* del
                        const void* y0, double c, int compute, const tdeq_segment* segs, const void* segs_dev,
                        int n_seg, int64_t chunk, int64_t n_chunks, int64_t n, double* out_count,
                        double* out_nonfinite, void* workspace, size_t workspace_bytes, int dtype, void* stream);
+
+/*
+ * ---- Per-row step control (ABI 22; torchdiffeq_amd/rowwise.py `odeint_rowwise`) ----
+ * The state is [n_rows, row_len] row-major (fp32 / fp64 only); every row is its own IVP with its own step controller.
+ * Per-row device vectors (length n_rows) carry the controller state; the entry points below read and update them.
+ *
+ * tdeq_row_partials     fp64 partials per row of the row reductions (1 for rows up to 1024 16-byte elements); the
+ *                       reduction buffer `part` holds 3 * n_rows * that many doubles.  A function of (row_len, dtype)
+ *                       only: a row is reduced the same way in a batch of any size.
+ * tdeq_row_combine      tdeq_stage_combine_multi with the step size of each element's row: coefficient
+ *                       fl_T(fl_T(coef) * dts[r]), dts = sign * T(dt_r).  Rows with active[r] == 0 read no stage:
+ *                       outputs with add_y0 get y0, the others 0.
+ * tdeq_row_reduce       mode 0: the embedded error [partial +] sum_j fl_T(fl_T(coef_j) dts[r]) k_j and per row the fp64 sum
+ *                       of (err / (atol + rtol max(|y0|, |y1|)))^2 and the count of non-finite y0 / y1 entries (inactive
+ *                       rows: 0).  mode 1 / 2: tdeq_init_norms' MODE 0 / 1 per row with a = y1, b = partial, y = y0.
+ * tdeq_row_control      per row: the sums of `part` -> mode 0: error ratio, accept / reject, next dt, output range, counters;
+ *                       mode 1: h0 of the initial-step heuristic (dts_out = sign * T(h0), times_out[0] = time of f(t0 + h0));
+ *                       mode 2: first step = min(100 h0, h1); mode 3: dt given, non-finite census only.  Then, for rows still
+ *                       active (modes 0, 2, 3), the next trial step: dt clamp, dts_out, stage times times_out[n_times, n_rows]
+ *                       and the row's error code (2 max_num_steps, 1 dt underflow, 3 non-finite y).  status[0] = active
+ *                       rows, status[1] = smallest row with a non-zero code (0x7fffffff: none).
+ * tdeq_row_dense_commit for each row whose trial step was accepted: the quartic dense output at output times
+ *                       out_lo[r] .. out_hi[r] - 1 into sol[j, r, :], then y0 <- y1, f0 <- f1.
+ */
+typedef struct tdeq_row_state {
+    double* t0;            /* [n_rows] start of the next trial step (solver time)                     */
+    double* tprev;         /* [n_rows] start of the last accepted step                                */
+    double* dt;            /* [n_rows] size of the next trial step                                    */
+    double* h0;            /* [n_rows] initial-step heuristic                                         */
+    const double* tgrid;   /* [n_out, n_rows] output times (solver time)                              */
+    int32_t* active;
+    int32_t* accepted;
+    int32_t* out_lo;
+    int32_t* out_hi;
+    int32_t* next_out;
+    int32_t* since;        /* trial steps since the row last reached an output time                   */
+    int32_t* bad_y;
+    int32_t* code;
+    int64_t* n_acc;
+    int64_t* n_rej;
+    double* ratio;         /* [n_rows] last error ratio                                               */
+    int32_t* status;       /* [2]                                                                     */
+    int64_t n_rows;
+    int64_t row_len;
+    int64_t max_num_steps;
+    int32_t n_out;
+    int32_t order;         /* the solver's order - 1 (initial-step heuristic)                         */
+} tdeq_row_state;
+
+int64_t tdeq_row_partials(int64_t row_len, int dtype);
+int tdeq_row_combine(const tdeq_multi_out* outs, int n_out, const void* y0, const void* acc_in, const void* const* k,
+                     int n_terms, const void* dts, const int32_t* active, int64_t n_rows, int64_t row_len, int dtype,
+                     void* stream);
+int tdeq_row_reduce(int mode, const void* y0, const void* y1, const void* partial, const void* const* k,
+                    const double* coef, int n_terms, const void* dts, const int32_t* active, double rtol, double atol,
+                    int64_t n_rows, int64_t row_len, double* part, size_t part_bytes, int dtype, void* stream);
+int tdeq_row_control(int mode, const double* part, const tdeq_step_ctrl* ctrl, const tdeq_row_state* st,
+                     void* dts_out, void* times_out, int dtype, void* stream);
+int tdeq_row_dense_commit(void* sol, void* y0, const void* y1, void* f0, const void* f1, const void* const* k,
+                          const double* coef, int n_terms, const void* dts, const tdeq_row_state* st, int dtype,
+                          void* stream);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,166 @@
+"""odeint_rowwise cost against odeint's eager whole-batch step, bytes of its streaming launches, and per-row step counts
+on a mixed-stiffness batch.
+
+    python tools/rowwise_bench.py [--out profiles/rowwise_bench.json] [--reps 3]
+    python tools/rowwise_bench.py --stats <rocprofv3 kernel_stats.csv> --bench <that json>   (adds in-situ bandwidth)
+
+Headline workload of bench.py: dopri5, func y @ A.T, 65536 x 128 fp32, rtol 1e-7, atol 1e-9.  A trial step of
+odeint_rowwise is one pass of its loop (S evaluations); odeint's is one call of its adaptive step; both are timed over
+the same interval, alternated in one process, `odeint` with hip_graph=False (the eager launch sequence).
+"""
+import argparse
+import csv
+import json
+import os
+import sys
+import time
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+PEAK_TBS = 8.0
+
+
+def _headline(reps: int):
+    import torchdiffeq_amd as tda
+    dev = torch.device("cuda", 0)
+    B, D = 65536, 128
+    g = torch.Generator().manual_seed(0)
+    G = torch.randn(D, D, generator=g, dtype=torch.float64) / D ** 0.5
+    A = (0.5 * (G - G.T) - 0.1 * torch.eye(D, dtype=torch.float64)).float().to(dev)
+    y0 = torch.randn(B, D, generator=g).to(dev)
+    t = torch.tensor([0.0, 0.5], device=dev)
+    calls = [0]
+
+    def f(t_, y):
+        calls[0] += 1
+        return y @ A.T
+    res = {"rowwise_ms_per_trial": [], "odeint_ms_per_trial": []}
+    with torch.no_grad():
+        for _ in range(reps + 1):
+            for which in ("rowwise", "odeint"):
+                calls[0] = 0
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                if which == "rowwise":
+                    _, st = tda.odeint_rowwise(f, y0, t, rtol=1e-7, atol=1e-9, return_stats=True)
+                else:
+                    tda.odeint(f, y0, t, rtol=1e-7, atol=1e-9, options={"hip_graph": False})
+                torch.cuda.synchronize()
+                ms = (time.perf_counter() - t0) * 1e3
+                trials = (calls[0] - 2) / 6
+                res[which + "_ms_per_trial"].append(ms / trials)
+                res[which + "_trials"] = trials
+    for k in ("rowwise_ms_per_trial", "odeint_ms_per_trial"):
+        res[k] = res[k][1:]          # the first pair warms up
+    res["ratio_rowwise_over_odeint"] = min(res["rowwise_ms_per_trial"]) / min(res["odeint_ms_per_trial"])
+    return res
+
+
+def _launch_bytes(B=65536, L=128, esize=4):
+    """Algorithmic bytes of each streaming launch of one dopri5 trial step (carried partial sums, tableaus.carry_plan)."""
+    from torchdiffeq_amd.tableaus import carry_plan
+    plan = carry_plan("dopri5")
+    n = B * L * esize
+    out = {}
+    out["row_combine[0]"] = 3 * n                          # y0, f0 -> y1
+    for i, op in enumerate(plan.ops):
+        if op is None:
+            continue
+        out[f"row_combine[{i}]"] = (len(op.idx) + 1 + (1 if op.continues else 0) + len(op.targets)) * n
+    out["row_reduce(err)"] = (1 + len(plan.err_idx) + 2) * n      # partial, remaining stages, y0, y1
+    out["row_dense_commit(no outputs)"] = 4 * n                     # y1, f1 -> y0, f0 (accepted rows)
+    return out
+
+
+def _mixed():
+    import numpy as np
+    import torchdiffeq_amd as tda
+    dev = torch.device("cuda", 0)
+    B = 1024
+    k = torch.logspace(-1, 3, B, dtype=torch.float64, device=dev)[:, None]
+    y0 = torch.linspace(0.5, 2.0, B, dtype=torch.float64, device=dev)[:, None]
+    t = torch.linspace(0, 5, 9, dtype=torch.float64, device=dev)
+
+    def f(t_, y):
+        return -k * (y - torch.sin(3.0 * (t_[:, None] if t_.dim() else t_)))
+    acc = [0]
+    rej = [0]
+
+    def f_ode(t_, y):
+        return f(t_, y)
+    f_ode.callback_accept_step = lambda *a: acc.__setitem__(0, acc[0] + 1)
+    f_ode.callback_reject_step = lambda *a: rej.__setitem__(0, rej[0] + 1)
+    with torch.no_grad():
+        _, st = tda.odeint_rowwise(f, y0, t, rtol=1e-6, atol=1e-8, return_stats=True)
+        tda.odeint(f_ode, y0, t, rtol=1e-6, atol=1e-8)
+    n = st["n_accepted"].numpy()
+    return {"B": B, "k_range": [0.1, 1000.0], "rowwise_accepted_min": int(n.min()), "rowwise_accepted_median":
+            float(np.median(n)), "rowwise_accepted_max": int(n.max()), "rowwise_rejected_total":
+            int(st["n_rejected"].sum()), "rowwise_func_calls": st["nfe"], "odeint_whole_batch_accepted": acc[0],
+            "odeint_whole_batch_rejected": rej[0]}
+
+
+# headline launches (fp32, 65536 x 128): kernel-name prefix -> (streams of N words, what it is).  The single-stage combine
+# serves two launches of the carried plan (row 0: f0, y0 -> y1, 3 streams; row 4: carried prefix + k4 + y0 -> y5, 4
+# streams), taken at their mean.  The dense-output launch is taken at its fastest call (a step without an output time:
+# y1, f1 in, y0, f0 out).
+_HEADLINE_LAUNCHES = {
+    "row_combine_kernel<float, 1, true>": (3.5, "rows 0 and 4 (mean of 3 and 4 streams)", "avg"),
+    "row_combine_kernel<float, 2, true>": (4, "row 1", "avg"),
+    "row_combine_kernel<float, 3, true>": (5, "row 2", "avg"),
+    "row_combine_kernel<float, 4, true>": (7, "row 3 + carried prefix of row 4", "avg"),
+    "row_combine_kernel<float, 5, true>": (8, "row 5 (= y1) + partial error", "avg"),
+    "row_reduce_wave_kernel<float, 1, 0, true, true>": (4, "error (partial + k6) + row sums", "avg"),
+    "row_dense_commit_kernel<float, 6, true>": (4, "commit y1 -> y0, f1 -> f0 (no output time)", "min"),
+}
+
+
+def _stats(path, bench, n_words=65536 * 128, esize=4):
+    """In-situ bandwidth of the headline's streaming launches from a rocprofv3 kernel_stats.csv."""
+    rows = list(csv.DictReader(open(path)))
+    out = {}
+    for r in rows:
+        name = r["Name"]
+        for key, (streams, what, which) in _HEADLINE_LAUNCHES.items():
+            if key in name:
+                ns = float(r["AverageNs"] if which == "avg" else r["MinNs"])
+                nbytes = streams * n_words * esize
+                out[key] = {"launch": what, "calls": int(r["Calls"]), "us": ns / 1e3, "timing": which,
+                            "bytes": nbytes, "TB_s": nbytes / ns / 1e3, "share_of_peak": nbytes / ns / 1e3 / PEAK_TBS}
+        if "row_ctrl_kernel<float" in name:
+            out["row_ctrl_kernel<float>"] = {"launch": "per-row controller (65536 rows, not streaming)",
+                                             "calls": int(r["Calls"]), "us": float(r["AverageNs"]) / 1e3}
+    bench["in_situ"] = out
+    return bench
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--stats", default=None)
+    ap.add_argument("--bench", default=None)
+    a = ap.parse_args()
+    if a.stats:
+        bench = json.load(open(a.bench))
+        bench = _stats(a.stats, bench)
+        json.dump(bench, open(a.bench, "w"), indent=1)
+        print(json.dumps(bench["in_situ"], indent=1))
+        return
+    res = {"device": torch.cuda.get_device_name(0), "headline": _headline(a.reps)}
+    lb = _launch_bytes()
+    res["launch_bytes"] = lb
+    res["launch_us_at_peak"] = {k: v / (PEAK_TBS * 1e12) * 1e6 for k, v in lb.items()}
+    res["mixed_stiffness"] = _mixed()
+    line = json.dumps(res)
+    print(line)
+    if a.out:
+        os.makedirs(os.path.dirname(a.out) or ".", exist_ok=True)
+        with open(a.out, "w") as fh:
+            json.dump(res, fh, indent=1)
+
+
+if __name__ == "__main__":
+    main()

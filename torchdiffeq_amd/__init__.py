@@ -10,7 +10,8 @@ from .odeint import SOLVERS, odeint, odeint_dense, odeint_event
 from .adjoint import odeint_adjoint
 from .solvers import clear_graph_cache
 from ._fallback import HostPathWarning
+from .rowwise import odeint_rowwise
 
 __version__ = "0.1.0"
-__all__ = ["odeint", "odeint_adjoint", "odeint_event", "odeint_dense", "SOLVERS", "clear_graph_cache",
+__all__ = ["odeint", "odeint_adjoint", "odeint_rowwise", "odeint_event", "odeint_dense", "SOLVERS", "clear_graph_cache",
            "HostPathWarning"]

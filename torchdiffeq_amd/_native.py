@@ -18,7 +18,7 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-TDEQ_ABI_VERSION = 21
+TDEQ_ABI_VERSION = 22
 TDEQ_F32, TDEQ_F64 = 0, 1
 TDEQ_C64, TDEQ_C128 = 2, 3        # interleaved complex: the norm entry points only (include/tdeq_hip.h)
 TDEQ_BF16, TDEQ_F16 = 4, 5        # reduced-precision states: the entry points of the host-driven step (LowPrecisionHipKernels)
@@ -55,6 +55,15 @@ class MultiOut(ctypes.Structure):
     """`tdeq_multi_out` of include/tdeq_hip.h: one output of tdeq_stage_combine_multi."""
     _fields_ = [("out", ctypes.c_void_p), ("coef", ctypes.c_double * TDEQ_MAX_TERMS), ("mask", ctypes.c_uint32),
                 ("add_y0", ctypes.c_int32)]
+
+
+class RowState(ctypes.Structure):
+    """`tdeq_row_state` of include/tdeq_hip.h: the per-row device vectors of an `odeint_rowwise` solve."""
+    _fields_ = [(name, ctypes.c_void_p) for name in ("t0", "tprev", "dt", "h0", "tgrid", "active", "accepted", "out_lo",
+                                                      "out_hi", "next_out", "since", "bad_y", "code", "n_acc", "n_rej",
+                                                      "ratio", "status")] + \
+               [("n_rows", ctypes.c_int64), ("row_len", ctypes.c_int64), ("max_num_steps", ctypes.c_int64),
+                ("n_out", ctypes.c_int32), ("order", ctypes.c_int32)]
 
 
 # name -> (restype, argtypes); the authoritative list of exported symbols (checked by the tests).
@@ -189,6 +198,20 @@ ABI_SIGNATURES = {
                                           ctypes.POINTER(Segment), ctypes.c_void_p, ctypes.c_int, ctypes.c_int64,
                                           ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
                                           ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_void_p]),
+    # per-row step control (ABI 22, rowwise.py)
+    "tdeq_row_partials": (ctypes.c_int64, [ctypes.c_int64, ctypes.c_int]),
+    "tdeq_row_combine": (ctypes.c_int, [ctypes.POINTER(MultiOut), ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                        _c_void_pp, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
+                                        ctypes.c_int64, ctypes.c_int, ctypes.c_void_p]),
+    "tdeq_row_reduce": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, _c_void_pp,
+                                       _c_double_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double,
+                                       ctypes.c_double, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_size_t,
+                                       ctypes.c_int, ctypes.c_void_p]),
+    "tdeq_row_control": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(StepCtrl), ctypes.POINTER(RowState),
+                                        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
+    "tdeq_row_dense_commit": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                             ctypes.c_void_p, _c_void_pp, _c_double_p, ctypes.c_int, ctypes.c_void_p,
+                                             ctypes.POINTER(RowState), ctypes.c_int, ctypes.c_void_p]),
 }
 
 
@@ -783,6 +806,44 @@ class HipKernels:
         arr = (ctypes.c_double * n)(*vals)
         _check(self.lib.tdeq_fill_scalars(dst.data_ptr(), arr, n, dtype_code(dst.dtype), self._stream()),
                "tdeq_fill_scalars")
+
+    # -- per-row step control (odeint_rowwise, rowwise.py) ---------------------------------------------------------
+    # States are [B, L] tensors; `dts` = sign * T(dt_r) per row, `active` int32 per row; `st` a RowState.
+    def row_partials(self, row_len: int, dtype) -> int:
+        """fp64 partials per row of the row reductions (a function of L and the dtype only)."""
+        return int(self.lib.tdeq_row_partials(row_len, dtype_code(dtype)))
+
+    def row_combine(self, outs, rows, y0, acc_in, ks, dts, active) -> None:
+        """tdeq_row_combine: `rows` as for `multi_spec`, one entry per output; the step size of each row from `dts`."""
+        n = len(ks)
+        ptrs = (ctypes.c_void_p * n)(*[k.data_ptr() for k in ks])
+        spec = self.multi_spec(rows)
+        for o, t in enumerate(outs):
+            spec[o].out = t.data_ptr()
+        _check(self.lib.tdeq_row_combine(spec, len(outs), y0.data_ptr(), None if acc_in is None else acc_in.data_ptr(),
+                                         ptrs, n, dts.data_ptr(), active.data_ptr(), y0.shape[0], y0.shape[1],
+                                         dtype_code(y0.dtype), self._stream()), "tdeq_row_combine")
+
+    def row_reduce(self, mode: int, part, y0, y1, partial, ks, coefs, dts, active, rtol: float, atol: float) -> None:
+        """tdeq_row_reduce into `part` (fp64, 3 * B * row_partials)."""
+        n = len(ks)
+        ptrs = (ctypes.c_void_p * max(n, 1))(*[k.data_ptr() for k in ks])
+        cf = (ctypes.c_double * max(n, 1))(*coefs)
+        _check(self.lib.tdeq_row_reduce(mode, y0.data_ptr(), y1.data_ptr(), None if partial is None else partial.data_ptr(),
+                                        ptrs, cf, n, None if dts is None else dts.data_ptr(),
+                                        None if active is None else active.data_ptr(), rtol, atol, y0.shape[0],
+                                        y0.shape[1], part.data_ptr(), part.numel() * 8, dtype_code(y0.dtype),
+                                        self._stream()), "tdeq_row_reduce")
+
+    def row_control(self, mode: int, part, ctrl: StepCtrl, st: RowState, dts_out, times_out, dtype) -> None:
+        _check(self.lib.tdeq_row_control(mode, part.data_ptr(), ctypes.byref(ctrl), ctypes.byref(st), dts_out.data_ptr(),
+                                         times_out.data_ptr(), dtype_code(dtype), self._stream()), "tdeq_row_control")
+
+    def row_dense_commit(self, sol, y0, y1, f0, f1, ks, coefs, dts, st: RowState) -> None:
+        ptrs, cf, n = self._terms(ks, coefs)
+        _check(self.lib.tdeq_row_dense_commit(sol.data_ptr(), y0.data_ptr(), y1.data_ptr(), f0.data_ptr(), f1.data_ptr(),
+                                              ptrs, cf, n, dts.data_ptr(), ctypes.byref(st), dtype_code(y0.dtype),
+                                              self._stream()), "tdeq_row_dense_commit")
 
 
 class ComplexHipKernels:

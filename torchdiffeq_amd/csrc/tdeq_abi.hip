@@ -1760,3 +1760,5 @@ int tdeq_adams_correct(void* y_out, void* dy_out, const void* f, const void* del
 }
 
 }  // extern "C"
+
+#include "tdeq_abi_rowwise.hpp"

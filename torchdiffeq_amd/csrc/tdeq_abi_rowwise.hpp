@@ -1,0 +1,328 @@
+// tdeq_abi_rowwise.hpp — extern "C" entry points of the per-row step control (tdeq_kernels_rowwise.hpp, declared in
+// include/tdeq_hip.h).  Included by tdeq_abi.hip after its anonymous namespace: host-side validation, launch geometry,
+// template dispatch.  No allocation, no synchronisation.
+#pragma once
+
+#include "tdeq_kernels_rowwise.hpp"
+
+namespace {
+using namespace tdeq;
+
+// 16-byte elements when a row is a whole number of them (an element then never straddles two rows)
+inline int row_lanes(int64_t row_len, int dtype) {
+    const int lv = dtype == TDEQ_F32 ? 4 : 2;
+    return row_len % lv == 0 ? lv : 1;
+}
+
+// Reduction geometry of a row: a function of (L, dtype) only, so that a row's sums never depend on B.
+struct RowGeom {
+    int lv;           // T elements per E element
+    int64_t nv;       // E elements per row
+    int group;        // short rows: lanes per row
+    int64_t chunk;    // long rows: E elements per workgroup
+    int64_t nch;      // partials per row
+};
+
+inline RowGeom row_geom(int64_t row_len, int dtype) {
+    RowGeom g;
+    g.lv = row_lanes(row_len, dtype);
+    g.nv = row_len / g.lv;
+    if (g.nv <= kRowWaveMax) {
+        const int64_t want = (g.nv + 3) / 4;
+        int grp = 1;
+        while (grp < want && grp < kWave) grp <<= 1;
+        g.group = grp;
+        g.chunk = g.nv;
+        g.nch = 1;
+    } else {
+        g.group = 0;
+        g.chunk = 8 * kBlock;
+        g.nch = (g.nv + g.chunk - 1) / g.chunk;
+    }
+    return g;
+}
+
+template <typename T, int NT, bool VEC>
+int launch_row_combine(const RowMultiArgs<T, NT>& a, hipStream_t s) {
+    constexpr int LV = VEC ? VecOf<T>::L : 1;
+    hipLaunchKernelGGL((row_combine_kernel<T, NT, VEC>), dim3(stream_grid(a.n / LV, kBlock)), dim3(kBlock), 0, s, a);
+    return check_launch();
+}
+
+template <typename T, int NT>
+int row_combine_n(const tdeq_multi_out* outs, int n_out, const void* y0, const void* acc_in, const void* const* k,
+                  const void* dts, const int32_t* active, int64_t n_rows, int64_t row_len, hipStream_t s) {
+    RowMultiArgs<T, NT> a;
+    a.y0 = static_cast<const T*>(y0);
+    a.acc_in = static_cast<const T*>(acc_in);
+    for (int j = 0; j < NT; ++j) a.k[j] = static_cast<const T*>(k[j]);
+    a.add_y0 = 0;
+    for (int o = 0; o < kMaxMultiOut; ++o) {
+        const bool live = o < n_out;
+        a.out[o] = live ? static_cast<T*>(outs[o].out) : nullptr;
+        a.mask[o] = live ? outs[o].mask : 0u;
+        if (live && outs[o].add_y0) a.add_y0 |= 1u << o;
+        for (int j = 0; j < NT; ++j) a.c[o][j] = live ? (T)outs[o].coef[j] : (T)0;
+    }
+    a.n_out = n_out;
+    a.dts = static_cast<const T*>(dts);
+    a.active = active;
+    a.n = n_rows * row_len;
+    const int lv = row_lanes(row_len, std::is_same<T, float>::value ? TDEQ_F32 : TDEQ_F64);
+    bool vec = lv > 1 && aligned16(y0) && (!acc_in || aligned16(acc_in));
+    for (int j = 0; j < NT; ++j) vec = vec && aligned16(k[j]);
+    for (int o = 0; o < n_out; ++o) vec = vec && aligned16(outs[o].out);
+    if (vec) {
+        a.row_len = row_len / lv;
+        return launch_row_combine<T, NT, true>(a, s);
+    }
+    a.row_len = row_len;
+    return launch_row_combine<T, NT, false>(a, s);
+}
+
+template <typename T>
+int row_combine_dispatch(const tdeq_multi_out* outs, int n_out, const void* y0, const void* acc_in,
+                         const void* const* k, int nt, const void* dts, const int32_t* active, int64_t n_rows,
+                         int64_t row_len, hipStream_t s) {
+    switch (nt) {
+#define TDEQ_CASE(N) case N: return row_combine_n<T, N>(outs, n_out, y0, acc_in, k, dts, active, n_rows, row_len, s);
+        TDEQ_CASE(1) TDEQ_CASE(2) TDEQ_CASE(3) TDEQ_CASE(4) TDEQ_CASE(5) TDEQ_CASE(6) TDEQ_CASE(7)
+        TDEQ_CASE(8) TDEQ_CASE(9) TDEQ_CASE(10) TDEQ_CASE(11) TDEQ_CASE(12) TDEQ_CASE(13) TDEQ_CASE(14)
+#undef TDEQ_CASE
+    }
+    return TDEQ_EINVAL;
+}
+
+template <typename T, int NT, int MODE, bool PARTIAL>
+int row_reduce_launch(RowRedArgs<T, NT>& a, const RowGeom& g, bool vec, hipStream_t s) {
+    if (g.nch == 1) {
+        const int64_t threads = a.n_rows * g.group;
+        const dim3 grid((unsigned)((threads + kBlock - 1) / kBlock));
+        a.group = g.group;
+        a.nch = 1;
+        if (vec) hipLaunchKernelGGL((row_reduce_wave_kernel<T, NT, MODE, PARTIAL, true>), grid, dim3(kBlock), 0, s, a);
+        else hipLaunchKernelGGL((row_reduce_wave_kernel<T, NT, MODE, PARTIAL, false>), grid, dim3(kBlock), 0, s, a);
+    } else {
+        a.chunk = g.chunk;
+        a.nch = (int)g.nch;
+        const dim3 grid((unsigned)(a.n_rows * g.nch));
+        if (vec) hipLaunchKernelGGL((row_reduce_chunk_kernel<T, NT, MODE, PARTIAL, true>), grid, dim3(kBlock), 0, s, a);
+        else hipLaunchKernelGGL((row_reduce_chunk_kernel<T, NT, MODE, PARTIAL, false>), grid, dim3(kBlock), 0, s, a);
+    }
+    return check_launch();
+}
+
+template <typename T, int NT>
+int row_reduce_n(int mode, const void* y0, const void* y1, const void* partial, const void* const* k,
+                 const double* coef, const void* dts, const int32_t* active, double rtol, double atol, int64_t n_rows,
+                 int64_t row_len, double* part, hipStream_t s) {
+    const RowGeom g = row_geom(row_len, std::is_same<T, float>::value ? TDEQ_F32 : TDEQ_F64);
+    RowRedArgs<T, NT> a;
+    a.y0 = static_cast<const T*>(y0);
+    a.y1 = static_cast<const T*>(y1);
+    a.partial = static_cast<const T*>(partial);
+    for (int j = 0; j < (NT > 0 ? NT : 1); ++j) {
+        a.k[j] = j < NT ? static_cast<const T*>(k[j]) : nullptr;
+        a.c[j] = j < NT ? (T)coef[j] : (T)0;
+    }
+    a.dts = static_cast<const T*>(dts);
+    a.active = active;
+    a.rtol = (T)rtol;
+    a.atol = (T)atol;
+    a.row_len = g.nv;
+    a.n_rows = n_rows;
+    a.chunk = g.chunk;
+    a.nch = (int)g.nch;
+    a.group = g.group;
+    a.part = part;
+    bool vec = g.lv > 1 && aligned16(y0) && aligned16(y1) && (!partial || aligned16(partial));
+    for (int j = 0; j < NT; ++j) vec = vec && aligned16(k[j]);
+    if (g.lv > 1 && !vec) return TDEQ_EINVAL;      // (the geometry, hence the sums, must not depend on alignment)
+    if constexpr (NT == 0) {
+        if (mode == 1) return row_reduce_launch<T, NT, 1, false>(a, g, vec, s);
+        if (mode == 2) return row_reduce_launch<T, NT, 2, false>(a, g, vec, s);
+        return TDEQ_EINVAL;
+    } else {
+        if (mode != 0) return TDEQ_EINVAL;
+        return partial ? row_reduce_launch<T, NT, 0, true>(a, g, vec, s) : row_reduce_launch<T, NT, 0, false>(a, g, vec, s);
+    }
+}
+
+template <typename T>
+int row_reduce_dispatch(int mode, const void* y0, const void* y1, const void* partial, const void* const* k,
+                        const double* coef, int nt, const void* dts, const int32_t* active, double rtol, double atol,
+                        int64_t n_rows, int64_t row_len, double* part, hipStream_t s) {
+    switch (nt) {
+#define TDEQ_CASE(N) case N: return row_reduce_n<T, N>(mode, y0, y1, partial, k, coef, dts, active, rtol, atol, n_rows, row_len, part, s);
+        TDEQ_CASE(0) TDEQ_CASE(1) TDEQ_CASE(2) TDEQ_CASE(3) TDEQ_CASE(4) TDEQ_CASE(5) TDEQ_CASE(6) TDEQ_CASE(7)
+        TDEQ_CASE(8) TDEQ_CASE(9) TDEQ_CASE(10) TDEQ_CASE(11) TDEQ_CASE(12) TDEQ_CASE(13) TDEQ_CASE(14)
+#undef TDEQ_CASE
+    }
+    return TDEQ_EINVAL;
+}
+
+template <typename T>
+int row_control_launch(const RowCtrlArgs& a, hipStream_t s) {
+    if (a.nch > 1) {
+        const dim3 grid((unsigned)((a.n_rows * kWave + kBlock - 1) / kBlock));
+        hipLaunchKernelGGL((row_ctrl_kernel<T, true>), grid, dim3(kBlock), 0, s, a);
+    } else {
+        const dim3 grid((unsigned)((a.n_rows + kBlock - 1) / kBlock));
+        hipLaunchKernelGGL((row_ctrl_kernel<T, false>), grid, dim3(kBlock), 0, s, a);
+    }
+    return check_launch();
+}
+
+template <typename T, int NT, bool VEC>
+int launch_row_dense(const RowDenseArgs<T, NT>& a, hipStream_t s) {
+    constexpr int LV = VEC ? VecOf<T>::L : 1;
+    hipLaunchKernelGGL((row_dense_commit_kernel<T, NT, VEC>), dim3(stream_grid(a.n / LV, kBlock)), dim3(kBlock), 0, s, a);
+    return check_launch();
+}
+
+template <typename T, int NT>
+int row_dense_n(void* sol, void* y0, const void* y1, void* f0, const void* f1, const void* const* k, const double* coef,
+                const void* dts, const tdeq_row_state* st, hipStream_t s) {
+    RowDenseArgs<T, NT> a;
+    a.sol = static_cast<T*>(sol);
+    a.y0 = static_cast<T*>(y0);
+    a.y1 = static_cast<const T*>(y1);
+    a.f0 = static_cast<T*>(f0);
+    a.f1 = static_cast<const T*>(f1);
+    for (int j = 0; j < NT; ++j) {
+        a.k[j] = static_cast<const T*>(k[j]);
+        a.c[j] = (T)coef[j];
+    }
+    a.dts = static_cast<const T*>(dts);
+    a.tgrid = st->tgrid;
+    a.tprev = st->tprev;
+    a.t1 = st->t0;
+    a.accepted = st->accepted;
+    a.out_lo = st->out_lo;
+    a.out_hi = st->out_hi;
+    a.n_rows = st->n_rows;
+    a.n = st->n_rows * st->row_len;
+    const int lv = row_lanes(st->row_len, std::is_same<T, float>::value ? TDEQ_F32 : TDEQ_F64);
+    bool vec = lv > 1 && aligned16(sol) && aligned16(y0) && aligned16(y1) && aligned16(f0) && aligned16(f1);
+    for (int j = 0; j < NT; ++j) vec = vec && aligned16(k[j]);
+    if (vec) {
+        a.row_len = st->row_len / lv;
+        return launch_row_dense<T, NT, true>(a, s);
+    }
+    a.row_len = st->row_len;
+    return launch_row_dense<T, NT, false>(a, s);
+}
+
+template <typename T>
+int row_dense_dispatch(void* sol, void* y0, const void* y1, void* f0, const void* f1, const void* const* k,
+                       const double* coef, int nt, const void* dts, const tdeq_row_state* st, hipStream_t s) {
+    switch (nt) {
+#define TDEQ_CASE(N) case N: return row_dense_n<T, N>(sol, y0, y1, f0, f1, k, coef, dts, st, s);
+        TDEQ_CASE(1) TDEQ_CASE(2) TDEQ_CASE(3) TDEQ_CASE(4) TDEQ_CASE(5) TDEQ_CASE(6) TDEQ_CASE(7)
+        TDEQ_CASE(8) TDEQ_CASE(9) TDEQ_CASE(10) TDEQ_CASE(11) TDEQ_CASE(12) TDEQ_CASE(13) TDEQ_CASE(14)
+#undef TDEQ_CASE
+    }
+    return TDEQ_EINVAL;
+}
+
+inline bool row_dtype_ok(int dtype) { return dtype == TDEQ_F32 || dtype == TDEQ_F64; }
+
+}  // namespace
+
+int64_t tdeq_row_partials(int64_t row_len, int dtype) {
+    if (row_len < 1 || !row_dtype_ok(dtype)) return TDEQ_EINVAL;
+    return row_geom(row_len, dtype).nch;
+}
+
+int tdeq_row_combine(const tdeq_multi_out* outs, int n_out, const void* y0, const void* acc_in, const void* const* k,
+                     int n_terms, const void* dts, const int32_t* active, int64_t n_rows, int64_t row_len, int dtype,
+                     void* stream) {
+    if (!outs || !y0 || !k || !dts || !active || n_rows < 0 || row_len < 1 || !row_dtype_ok(dtype)) return TDEQ_EINVAL;
+    if (n_terms < 1 || n_terms > TDEQ_MAX_TERMS || n_out < 1 || n_out > TDEQ_MAX_MULTI_OUT) return TDEQ_EINVAL;
+    for (int j = 0; j < n_terms; ++j) if (!k[j]) return TDEQ_EINVAL;
+    for (int o = 0; o < n_out; ++o) {
+        if (!outs[o].out || outs[o].mask == 0u || (n_terms < 32 && (outs[o].mask >> n_terms) != 0u)) return TDEQ_EINVAL;
+    }
+    if (n_rows == 0) return 0;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return dtype == TDEQ_F32
+               ? row_combine_dispatch<float>(outs, n_out, y0, acc_in, k, n_terms, dts, active, n_rows, row_len, s)
+               : row_combine_dispatch<double>(outs, n_out, y0, acc_in, k, n_terms, dts, active, n_rows, row_len, s);
+}
+
+int tdeq_row_reduce(int mode, const void* y0, const void* y1, const void* partial, const void* const* k,
+                    const double* coef, int n_terms, const void* dts, const int32_t* active, double rtol, double atol,
+                    int64_t n_rows, int64_t row_len, double* part, size_t part_bytes, int dtype, void* stream) {
+    if (!y0 || !y1 || !part || n_rows < 0 || row_len < 1 || !row_dtype_ok(dtype)) return TDEQ_EINVAL;
+    if (mode < 0 || mode > 2 || n_terms < 0 || n_terms > TDEQ_MAX_TERMS) return TDEQ_EINVAL;
+    if (mode == 0 && (n_terms < 1 || !k || !coef || !dts || !active)) return TDEQ_EINVAL;
+    if (mode != 0 && (n_terms != 0 || !partial)) return TDEQ_EINVAL;
+    for (int j = 0; j < n_terms; ++j) if (!k[j]) return TDEQ_EINVAL;
+    const int64_t nch = row_geom(row_len, dtype).nch;
+    if (part_bytes < (size_t)(3 * n_rows * nch) * sizeof(double)) return TDEQ_EWORKSPACE;
+    if (n_rows == 0) return 0;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return dtype == TDEQ_F32
+               ? row_reduce_dispatch<float>(mode, y0, y1, partial, k, coef, n_terms, dts, active, rtol, atol, n_rows,
+                                            row_len, part, s)
+               : row_reduce_dispatch<double>(mode, y0, y1, partial, k, coef, n_terms, dts, active, rtol, atol, n_rows,
+                                             row_len, part, s);
+}
+
+int tdeq_row_control(int mode, const double* part, const tdeq_step_ctrl* ctrl, const tdeq_row_state* st,
+                     void* dts_out, void* times_out, int dtype, void* stream) {
+    if (!part || !ctrl || !st || !row_dtype_ok(dtype) || mode < 0 || mode > 3) return TDEQ_EINVAL;
+    if (st->n_rows < 0 || st->row_len < 1 || st->n_out < 1 || !st->status) return TDEQ_EINVAL;
+    if (ctrl->n_times < 1 || ctrl->n_times > TDEQ_MAX_STAGE_TIMES) return TDEQ_EINVAL;
+    if (!dts_out || !times_out) return TDEQ_EINVAL;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    // status = {0 active rows, no row in error}
+    hipError_t e = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(st->status), 0, 1, s);
+    if (e == hipSuccess)
+        e = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(st->status + 1), 0x7fffffff, 1, s);
+    if (e != hipSuccess) return (int)e;
+    if (st->n_rows == 0) return 0;
+    RowCtrlArgs a;
+    a.part = part;
+    a.nch = (int)row_geom(st->row_len, dtype).nch;
+    a.n_rows = st->n_rows;
+    a.row_len = st->row_len;
+    a.tkind = dtype == TDEQ_F32 ? 1 : 0;
+    a.mode = mode;
+    a.order = st->order;
+    a.c = *ctrl;
+    a.max_num_steps = st->max_num_steps;
+    a.tgrid = st->tgrid;
+    a.n_out = st->n_out;
+    a.t0 = st->t0;
+    a.tprev = st->tprev;
+    a.dt = st->dt;
+    a.h0 = st->h0;
+    a.dts_out = dts_out;
+    a.times = times_out;
+    a.active = st->active;
+    a.accepted = st->accepted;
+    a.out_lo = st->out_lo;
+    a.out_hi = st->out_hi;
+    a.next_out = st->next_out;
+    a.since = st->since;
+    a.bad_y = st->bad_y;
+    a.code = st->code;
+    a.n_acc = st->n_acc;
+    a.n_rej = st->n_rej;
+    a.ratio_out = st->ratio;
+    a.status = st->status;
+    return dtype == TDEQ_F32 ? row_control_launch<float>(a, s) : row_control_launch<double>(a, s);
+}
+
+int tdeq_row_dense_commit(void* sol, void* y0, const void* y1, void* f0, const void* f1, const void* const* k,
+                          const double* coef, int n_terms, const void* dts, const tdeq_row_state* st, int dtype,
+                          void* stream) {
+    if (!sol || !y0 || !y1 || !f0 || !f1 || !k || !coef || !dts || !st || !row_dtype_ok(dtype)) return TDEQ_EINVAL;
+    if (n_terms < 1 || n_terms > TDEQ_MAX_TERMS || st->n_rows < 0 || st->row_len < 1) return TDEQ_EINVAL;
+    for (int j = 0; j < n_terms; ++j) if (!k[j]) return TDEQ_EINVAL;
+    if (st->n_rows == 0) return 0;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return dtype == TDEQ_F32 ? row_dense_dispatch<float>(sol, y0, y1, f0, f1, k, coef, n_terms, dts, st, s)
+                             : row_dense_dispatch<double>(sol, y0, y1, f0, f1, k, coef, n_terms, dts, st, s);
+}

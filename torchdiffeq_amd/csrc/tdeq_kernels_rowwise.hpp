@@ -1,0 +1,493 @@
+// tdeq_kernels_rowwise.hpp — gfx950 device code of `odeint_rowwise` (torchdiffeq_amd/rowwise.py): a batch of B
+// independent IVPs of L elements each, one step controller PER ROW.
+//
+// The state is [B, L] row-major.  Every per-row quantity lives in a device vector of length B: the time t0[B] and step
+// size dt[B] (fp64, the reference's time type W), sign * T(dt) of the running trial step (T[B]), the stage times handed
+// to func ([n_stages, B] of T), the active flag, the counters and an error code.  The host reads back two words per
+// trial step (active rows, first row in error).
+//
+// The arithmetic of every element is that of the whole-batch kernels in tdeq_kernels.hpp with the row's own step
+// size: coefficients fl_T(fl_T(a_j) * T(dt_r)), left-to-right sums, -ffp-contract=off.  Rows that have finished
+// (`active[r] == 0`) read none of their stage streams (func's output for them is ignored, NaN or not): the stage
+// combine writes their y0 unchanged, the reductions report zeros, the controller leaves them alone.
+//
+// Reductions are batch-invariant: how a row is reduced depends on L only (never on B or on the row's position), so
+// a row's error ratio has the same bits in a batch of any size.
+//   short rows (nv <= kRowWaveMax 16-byte elements):  G = power of two <= 64 lanes per row, each lane its strided
+//                                                      elements in order, then a butterfly over the G lanes
+//   long rows:                                         nch chunks of `chunk` elements per row, one workgroup per
+//                                                      (row, chunk) -> fp64 partial; the controller adds a row's
+//                                                      partials with one wave in a fixed order
+#pragma once
+
+#include "tdeq_kernels.hpp"
+
+namespace tdeq {
+
+constexpr int kRowWaveMax = 64 * 16;      // short-row limit in E elements (16 per lane at G = 64)
+
+// ------------------------------------------------------------------------------------------------
+// Row stage combine with carried partial sums (the rowwise form of stage_combine_multi_kernel):
+//   s_o = [acc_in +] sum_{j in mask_o, ascending} fl_T(c_o[j] * dts[r]) * k_j ;  out_o = add_y0_o ? y0 + s_o : s_o
+// Inactive rows: out_o = y0 (add_y0) or 0, no stage is read.
+// ------------------------------------------------------------------------------------------------
+template <typename T, int NT>
+struct RowMultiArgs {
+    const T* y0;
+    const T* acc_in;                  // nullable: prefix of output 0's sum
+    const T* k[NT];
+    T* out[kMaxMultiOut];
+    T c[kMaxMultiOut][NT];            // fl_T(coef)
+    uint32_t mask[kMaxMultiOut];
+    uint32_t add_y0;
+    int n_out;
+    const T* dts;                     // [B] sign * T(dt_r)
+    const int32_t* active;            // [B]
+    int64_t row_len;                  // L, in units of the element type E of the launch
+    int64_t n;                        // B * L elements of T
+};
+
+template <typename T, int NT, typename E>
+__device__ __forceinline__ void row_multi_elem(const RowMultiArgs<T, NT>& a, int64_t i, int64_t r) {
+    const E y = reinterpret_cast<const E*>(a.y0)[i];
+    if (!a.active[r]) {
+        E zero = y;
+        zero = zero - y;              // (0 for a finite y0; the value is never read for a finished row)
+#pragma unroll
+        for (int o = 0; o < kMaxMultiOut; ++o)
+            if (o < a.n_out) reinterpret_cast<E*>(a.out[o])[i] = ((a.add_y0 >> o) & 1u) ? y : zero;
+        return;
+    }
+    const T dtT = a.dts[r];
+    E kk[NT];
+#pragma unroll
+    for (int j = 0; j < NT; ++j) kk[j] = reinterpret_cast<const E*>(a.k[j])[i];
+    const bool has_acc = a.acc_in != nullptr;
+    E acc0 = y;
+    if (has_acc) acc0 = reinterpret_cast<const E*>(a.acc_in)[i];
+#pragma unroll
+    for (int o = 0; o < kMaxMultiOut; ++o) {
+        if (o < a.n_out) {
+            const uint32_t m = a.mask[o];
+            bool started = (o == 0) && has_acc;
+            E s = acc0;
+#pragma unroll
+            for (int j = 0; j < NT; ++j) {
+                if ((m >> j) & 1u) {
+                    const T cj = a.c[o][j] * dtT;          // fl_T(fl_T(coef) * T(dt_r))
+                    const E p = kk[j] * cj;
+                    s = started ? s + p : p;
+                    started = true;
+                }
+            }
+            reinterpret_cast<E*>(a.out[o])[i] = ((a.add_y0 >> o) & 1u) ? y + s : s;
+        }
+    }
+}
+
+// VEC: L % (16 / sizeof(T)) == 0 and every buffer 16-byte aligned, so a 16-byte element never straddles two rows.
+template <typename T, int NT, bool VEC>
+__global__ __launch_bounds__(kBlock) void row_combine_kernel(const RowMultiArgs<T, NT> a) {
+    using E = typename std::conditional<VEC, typename VecOf<T>::type, T>::type;
+    constexpr int LV = VEC ? VecOf<T>::L : 1;
+    const int64_t ne = a.n / LV;
+    const int64_t stride = (int64_t)gridDim.x * kBlock;
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < ne; i += stride)
+        row_multi_elem<T, NT, E>(a, i, i / a.row_len);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Row reductions.  MODE 0: embedded error  e = [partial +] sum_j fl_T(c_j * dts[r]) * k_j, then
+//   acc0 += (e / (atol + rtol * max(|y0|, |y1|)))^2, bad += !finite(y0) || !finite(y1)      (tol_accumulate)
+// MODE 1 / 2: the initial-step norms of init_elem (a = y0 or f1, b = f0, y = y0 for the scale).
+// Results: part[q * (B * nch) + r * nch + c], q = 0, 1 sums, q = 2 the non-finite count.
+// ------------------------------------------------------------------------------------------------
+template <typename T, int NT>
+struct RowRedArgs {
+    const T* y0;                      // MODE 0: y0; MODE 1/2: the scale state y
+    const T* y1;                      // MODE 0: y1; MODE 1/2: a
+    const T* partial;                 // MODE 0, nullable; MODE 1/2: b
+    const T* k[NT > 0 ? NT : 1];
+    T c[NT > 0 ? NT : 1];
+    const T* dts;
+    const int32_t* active;
+    T rtol, atol;
+    int64_t row_len;                  // in E units
+    int64_t n_rows;
+    int64_t chunk;                    // long rows: E units per workgroup
+    int nch;                          // chunks per row (1 for short rows)
+    int group;                        // short rows: lanes per row (power of two <= 64)
+    double* part;
+};
+
+template <typename T, int NT, int MODE, bool PARTIAL, typename E>
+__device__ __forceinline__ void row_red_elem(const RowRedArgs<T, NT>& a, const T (&cc)[NT > 0 ? NT : 1], int64_t i,
+                                             double (&acc)[3]) {
+    constexpr int LV = sizeof(E) / sizeof(T);
+    if constexpr (MODE == 0) {
+        E e;
+        if constexpr (PARTIAL) e = reinterpret_cast<const E*>(a.partial)[i];
+#pragma unroll
+        for (int j = 0; j < NT; ++j) {
+            const E p = reinterpret_cast<const E*>(a.k[j])[i] * cc[j];
+            if (PARTIAL || j > 0) e = e + p;
+            else e = p;
+        }
+        const E v0 = reinterpret_cast<const E*>(a.y0)[i], v1 = reinterpret_cast<const E*>(a.y1)[i];
+        if constexpr (LV == 1) {
+            tol_accumulate<T>(e, v0, v1, a.rtol, a.atol, acc[0], acc[2]);
+        } else {
+#pragma unroll
+            for (int q = 0; q < LV; ++q) tol_accumulate<T>(e[q], v0[q], v1[q], a.rtol, a.atol, acc[0], acc[2]);
+        }
+    } else {
+        const E yv = reinterpret_cast<const E*>(a.y0)[i];
+        const E av = reinterpret_cast<const E*>(a.y1)[i];
+        const E bv = reinterpret_cast<const E*>(a.partial)[i];
+        if constexpr (LV == 1) {
+            init_elem<T, MODE - 1>(a.rtol, a.atol, av, bv, yv, acc);
+        } else {
+#pragma unroll
+            for (int q = 0; q < LV; ++q) init_elem<T, MODE - 1>(a.rtol, a.atol, av[q], bv[q], yv[q], acc);
+        }
+    }
+}
+
+template <typename T, int NT>
+__device__ __forceinline__ void row_coefs(const RowRedArgs<T, NT>& a, int64_t r, T (&cc)[NT > 0 ? NT : 1]) {
+    const T dtT = a.dts ? a.dts[r] : (T)1;
+#pragma unroll
+    for (int j = 0; j < NT; ++j) cc[j] = a.c[j] * dtT;
+}
+
+// short rows: `group` lanes per row, 256 / group rows per workgroup
+template <typename T, int NT, int MODE, bool PARTIAL, bool VEC>
+__global__ __launch_bounds__(kBlock) void row_reduce_wave_kernel(const RowRedArgs<T, NT> a) {
+    using E = typename std::conditional<VEC, typename VecOf<T>::type, T>::type;
+    const int g = a.group;
+    const int lane = threadIdx.x & (g - 1);
+    const int64_t r = ((int64_t)blockIdx.x * kBlock + threadIdx.x) / g;
+    double acc[3] = {0.0, 0.0, 0.0};
+    const bool live = r < a.n_rows && (MODE != 0 || a.active[r]);
+    if (live) {
+        T cc[NT > 0 ? NT : 1];
+        row_coefs<T, NT>(a, r, cc);
+        const int64_t base = r * a.row_len;
+        for (int64_t e = lane; e < a.row_len; e += g) row_red_elem<T, NT, MODE, PARTIAL, E>(a, cc, base + e, acc);
+    }
+    // butterfly over the group's lanes (the same tree for every row; lanes of other groups are never mixed in)
+    for (int off = g >> 1; off > 0; off >>= 1) {
+#pragma unroll
+        for (int q = 0; q < 3; ++q) acc[q] += __shfl_xor(acc[q], off, kWave);
+    }
+    if (lane == 0 && r < a.n_rows) {
+        const int64_t nb = a.n_rows;
+        a.part[r] = acc[0];
+        a.part[nb + r] = acc[1];
+        a.part[2 * nb + r] = acc[2];
+    }
+}
+
+// long rows: one workgroup per (row, chunk)
+template <typename T, int NT, int MODE, bool PARTIAL, bool VEC>
+__global__ __launch_bounds__(kBlock) void row_reduce_chunk_kernel(const RowRedArgs<T, NT> a) {
+    using E = typename std::conditional<VEC, typename VecOf<T>::type, T>::type;
+    __shared__ double red[3 * (kBlock / kWave)];
+    const int64_t b = blockIdx.x;
+    const int64_t r = b / a.nch, c = b - r * a.nch;
+    double acc[3] = {0.0, 0.0, 0.0};
+    if (MODE != 0 || a.active[r]) {
+        T cc[NT > 0 ? NT : 1];
+        row_coefs<T, NT>(a, r, cc);
+        const int64_t lo = c * a.chunk;
+        const int64_t hi = lo + a.chunk < a.row_len ? lo + a.chunk : a.row_len;
+        const int64_t base = r * a.row_len;
+#pragma unroll 2
+        for (int64_t e = lo + threadIdx.x; e < hi; e += kBlock) row_red_elem<T, NT, MODE, PARTIAL, E>(a, cc, base + e, acc);
+    }
+    block_sum<3>(acc, red);
+    if (threadIdx.x == 0) {
+        const int64_t nb = a.n_rows * a.nch;
+        a.part[b] = acc[0];
+        a.part[nb + b] = acc[1];
+        a.part[2 * nb + b] = acc[2];
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Per-row controller.  One lane per row (short rows) or one wave per row (long rows: the wave adds the row's nch
+// partials, lane q taking q, q + 64, ... in order, then the wave's shuffle tree).  MODE:
+//   0  trial step: error ratio -> accept / reject, next dt, output range, counters      (norm_finalize_ctrl_kernel)
+//   1  initial step, first half: d0, d1 -> h0; dts = sign * T(h0), stage time of f(t0 + h0)   (_select_initial_step)
+//   2  initial step, second half: d2 -> h1 -> dt = min(100 h0, h1)
+//   3  dt given (first_step): only the non-finite census of y0 (the MODE 1 reduction) and the set-up below
+// After modes 0 (rows still active), 2 and 3: the next trial step's dt clamp, sign * T(dt) and stage times, and the
+// error checks the host raises for (code 2: max_num_steps, 1: dt underflow, 3: non-finite y).
+// ------------------------------------------------------------------------------------------------
+struct RowCtrlArgs {
+    const double* part;               // [3][B * nch]
+    int nch;
+    int64_t n_rows;
+    int64_t row_len;                  // L in elements (the norm's mean)
+    int tkind;                        // 0 = fp64, 1 = fp32
+    int mode;
+    int order;                        // initial step: the solver's order - 1 (rk_common.py:217)
+    tdeq_step_ctrl c;                 // safety, ifactor, dfactor, exponent, min_step, max_step, time_sign, alpha[], n_times
+    int64_t max_num_steps;
+    const double* tgrid;              // [n_out, B] output times (solver time, fp64)
+    int n_out;
+    double* t0;                       // [B]
+    double* tprev;                    // [B] start of the last accepted step
+    double* dt;                       // [B]
+    double* h0;                       // [B] initial step: h0 (T value in a double)
+    void* dts_out;                    // [B] of T: sign * T(dt) of the next trial step (mode 1: sign * T(h0))
+    void* times;                      // [n_times, B] of T (mode 1: row 0 = the time of f(t0 + h0))
+    int32_t* active;
+    int32_t* accepted;                // [B] this trial step was accepted (dense output + commit)
+    int32_t* out_lo;                  // [B] first output index inside the accepted step
+    int32_t* out_hi;                  // [B] one past the last
+    int32_t* next_out;                // [B]
+    int32_t* since;                   // [B] trial steps since the row last reached an output time
+    int32_t* bad_y;                   // [B] the row's current y has non-finite entries
+    int32_t* code;                    // [B]
+    int64_t* n_acc;
+    int64_t* n_rej;
+    double* ratio_out;                // [B]
+    int32_t* status;                  // [2] = {active rows, first row with a non-zero code} (reset by the host side)
+};
+
+template <typename T>
+__device__ __forceinline__ T row_stage_time(const tdeq_step_ctrl& c, double t0n, double dtn, int i) {
+    return ctl_stage_time<T>(c, t0n, dtn, i);
+}
+
+template <typename T>
+__device__ __forceinline__ void row_prepare(const RowCtrlArgs& a, int64_t r) {
+    const tdeq_step_ctrl& c = a.c;
+    double dtn = a.dt[r];
+    if (!__builtin_isfinite(dtn)) dtn = c.min_step;
+    dtn = ctl_clamp(dtn, c.min_step, c.max_step);
+    a.dt[r] = dtn;
+    const double t0 = a.t0[r];
+    static_cast<T*>(a.dts_out)[r] = (T)dtn * (T)c.time_sign;
+    for (int i = 0; i < c.n_times; ++i) static_cast<T*>(a.times)[i * a.n_rows + r] = row_stage_time<T>(c, t0, dtn, i);
+    int code = 0;
+    if (a.bad_y[r]) code = 3;
+    if (!(t0 + dtn > t0)) code = 1;
+    if (a.since[r] >= a.max_num_steps) code = 2;
+    a.code[r] = code;
+}
+
+// a finished row: func keeps being evaluated at the end of its last accepted step, on its frozen state
+template <typename T>
+__device__ __forceinline__ void row_freeze(const RowCtrlArgs& a, int64_t r) {
+    static_cast<T*>(a.dts_out)[r] = (T)0;
+    const T tt = (T)a.c.time_sign * (T)a.t0[r];
+    for (int i = 0; i < a.c.n_times; ++i) static_cast<T*>(a.times)[i * a.n_rows + r] = tt;
+}
+
+// sqrt(mean) of a row, rounded to T (misc.py:22-33 with one segment)
+__device__ __forceinline__ double row_norm(double sum, int64_t numel, int tkind) {
+    const double v = __builtin_sqrt(sum / (double)numel);
+    return tkind == 1 ? (double)(float)v : v;
+}
+
+// returns: the row is active after this launch, and (code != 0)
+template <typename T>
+__device__ __forceinline__ void row_control(const RowCtrlArgs& a, int64_t r, double s0, double s1, double sb,
+                                            bool& live, bool& err) {
+    const tdeq_step_ctrl& c = a.c;
+    live = a.active[r] != 0;
+    err = false;
+    if (a.mode == 0) {
+        if (!live) {
+            a.accepted[r] = 0;
+            row_freeze<T>(a, r);
+            return;
+        }
+        const double ratio = row_norm(s0, a.row_len, a.tkind);
+        const double step_t0 = a.t0[r], step_dt = a.dt[r];
+        bool accept = ratio <= 1.0;
+        if (step_dt > c.max_step) accept = false;
+        if (step_dt <= c.min_step) accept = true;
+        double dt_next;
+        if (ratio == 0.0) {
+            dt_next = step_dt * c.ifactor;
+        } else {
+            const double dfactor = ratio < 1.0 ? 1.0 : c.dfactor;
+            const double scaled = c.safety / pow(ratio, c.exponent);
+            dt_next = step_dt * ctl_nan_min(c.ifactor, ctl_nan_max(scaled, dfactor));
+        }
+        dt_next = ctl_clamp(dt_next, c.min_step, c.max_step);
+        a.ratio_out[r] = ratio;
+        a.since[r] += 1;
+        a.accepted[r] = accept ? 1 : 0;
+        if (accept) {
+            const double t1 = step_t0 + step_dt;
+            a.tprev[r] = step_t0;
+            a.t0[r] = t1;
+            a.n_acc[r] += 1;
+            const int lo = a.next_out[r];
+            int hi = lo;
+            while (hi < a.n_out && a.tgrid[(int64_t)hi * a.n_rows + r] <= t1) ++hi;
+            a.out_lo[r] = lo;
+            a.out_hi[r] = hi;
+            a.next_out[r] = hi;
+            if (hi > lo) a.since[r] = 0;
+            a.bad_y[r] = sb != 0.0 ? 1 : 0;
+            if (hi >= a.n_out) {
+                live = false;
+                a.active[r] = 0;
+            }
+        } else {
+            a.n_rej[r] += 1;
+        }
+        a.dt[r] = dt_next;
+    } else if (a.mode == 1) {
+        // _select_initial_step (misc.py:36-77) in T: d0 = ||y0 / scale||, d1 = ||f0 / scale||
+        const T d0 = (T)row_norm(s0, a.row_len, a.tkind), d1 = (T)row_norm(s1, a.row_len, a.tkind);
+        T h0;
+        if (d0 < (T)1e-5 || d1 < (T)1e-5) h0 = (T)1e-6;
+        else h0 = ((T)0.01 * d0) / d1;
+        h0 = h0 < (T)0 ? -h0 : h0;
+        a.h0[r] = (double)h0;
+        a.bad_y[r] = sb != 0.0 ? 1 : 0;
+        static_cast<T*>(a.dts_out)[r] = (T)((double)h0 * c.time_sign);
+        static_cast<T*>(a.times)[r] = (T)c.time_sign * (T)(a.t0[r] + (double)h0);
+        return;
+    } else if (a.mode == 2) {
+        const T h0 = (T)a.h0[r];
+        const T d1 = (T)a.dt[r];              // (mode 1 parked d1 here, see below)
+        const T d2n = (T)row_norm(s0, a.row_len, a.tkind);
+        T d2 = d2n / h0;
+        d2 = d2 < (T)0 ? -d2 : d2;
+        T h1;
+        // (Python's max / min on host scalars: max(a, b) = b if b > a else a, min(a, b) = b if b < a else a)
+        if (d1 <= (T)1e-15 && d2 <= (T)1e-15) {
+            const T lo = (T)1e-6, v = h0 * (T)1e-3;
+            h1 = v > lo ? v : lo;
+        } else {
+            const T m = d2 > d1 ? d2 : d1;
+            const T q = ((T)1 / m) * (T)0.01;           // `0.01 / x` = x.reciprocal() * 0.01 (_scalars.rdiv)
+            const double e = 1.0 / (double)(a.order + 1);
+            if (e == 0.5) h1 = sizeof(T) == 4 ? (T)__builtin_sqrtf((float)q) : (T)__builtin_sqrt((double)q);   // ATen's sqrt
+            else h1 = (T)pow((double)q, e);                                                    // raised in double (_scalars.power)
+        }
+        h1 = h1 < (T)0 ? -h1 : h1;
+        const T big = (T)100 * h0;
+        const T fs = h1 < big ? h1 : big;
+        a.dt[r] = (double)fs;
+    } else {
+        a.bad_y[r] = sb != 0.0 ? 1 : 0;
+    }
+    if (live) {
+        row_prepare<T>(a, r);
+        err = a.code[r] != 0;
+    } else {
+        row_freeze<T>(a, r);
+    }
+}
+
+template <typename T, bool WAVE>
+__global__ __launch_bounds__(kBlock) void row_ctrl_kernel(const RowCtrlArgs a) {
+    const int lane = threadIdx.x & (kWave - 1);
+    int64_t r;
+    double s0 = 0.0, s1 = 0.0, sb = 0.0;
+    const int64_t np = a.n_rows * a.nch;
+    if (WAVE) {
+        r = ((int64_t)blockIdx.x * kBlock + threadIdx.x) / kWave;
+        if (r < a.n_rows) {
+            for (int64_t q = lane; q < a.nch; q += kWave) {
+                s0 += a.part[r * a.nch + q];
+                s1 += a.part[np + r * a.nch + q];
+                sb += a.part[2 * np + r * a.nch + q];
+            }
+        }
+        s0 = wave_sum(s0);
+        s1 = wave_sum(s1);
+        sb = wave_sum(sb);
+    } else {
+        r = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+        if (r < a.n_rows) {
+            s0 = a.part[r];
+            s1 = a.part[np + r];
+            sb = a.part[2 * np + r];
+        }
+    }
+    bool live = false, err = false;
+    if (r < a.n_rows && (!WAVE || lane == 0)) {
+        if (a.mode == 1) {
+            row_control<T>(a, r, s0, s1, sb, live, err);
+            a.dt[r] = (double)(T)row_norm(s1, a.row_len, a.tkind);     // d1 for mode 2
+        } else {
+            row_control<T>(a, r, s0, s1, sb, live, err);
+        }
+        if (err) atomicMin(a.status + 1, (int32_t)r);
+    }
+    // active-row count: one atomic per wave
+    const uint64_t m = __ballot(live ? 1 : 0);
+    if (lane == 0 && m) atomicAdd(a.status, (int32_t)__popcll(m));
+}
+
+// ------------------------------------------------------------------------------------------------
+// Dense output + commit of the accepted rows (rk_common.py:243-250, 335-352, interp.py:25-48): the quartic of the step
+// at every output time in (tprev_r, t0_r] — out_lo[r] .. out_hi[r] - 1 — written to solution[j, r, :], then
+// y0 <- y1 and f0 <- f1 (FSAL) for the row.  Rows without an accepted step are not touched.
+// ------------------------------------------------------------------------------------------------
+template <typename T, int NT>
+struct RowDenseArgs {
+    T* sol;                           // [n_out, B, L]
+    T* y0;                            // updated in place
+    const T* y1;
+    T* f0;                            // updated in place
+    const T* f1;
+    const T* k[NT];
+    T c[NT];                          // fl_T(c_mid)
+    const T* dts;                     // sign * T(dt) of the step just taken
+    const double* tgrid;
+    const double* tprev;
+    const double* t1;
+    const int32_t* accepted;
+    const int32_t* out_lo;
+    const int32_t* out_hi;
+    int64_t row_len;                  // E units
+    int64_t n_rows;
+    int64_t n;                        // B * L elements of T
+};
+
+template <typename T, int NT, bool VEC>
+__global__ __launch_bounds__(kBlock) void row_dense_commit_kernel(const RowDenseArgs<T, NT> a) {
+    using E = typename std::conditional<VEC, typename VecOf<T>::type, T>::type;
+    constexpr int LV = VEC ? VecOf<T>::L : 1;
+    const int64_t ne = a.n / LV;
+    const int64_t stride = (int64_t)gridDim.x * kBlock;
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < ne; i += stride) {
+        const int64_t r = i / a.row_len;
+        if (!a.accepted[r]) continue;
+        const E y1 = reinterpret_cast<const E*>(a.y1)[i];
+        const E f1 = reinterpret_cast<const E*>(a.f1)[i];
+        const int lo = a.out_lo[r], hi = a.out_hi[r];
+        if (hi > lo) {                // (a step without an output time moves 4 words: y1, f1 in, y0, f0 out)
+            const E y0 = reinterpret_cast<const E*>(a.y0)[i];
+            DenseArgs<T, NT> d;
+            const T dtT = a.dts[r];
+#pragma unroll
+            for (int j = 0; j < NT; ++j) d.c[j] = a.c[j] * dtT;      // fl_T(fl_T(mid_j) * T(dt)) — rk_common.py:365-366
+            d.dt = dtT;
+            E kk[NT];
+#pragma unroll
+            for (int j = 0; j < NT; ++j) kk[j] = reinterpret_cast<const E*>(a.k[j])[i];
+            const E f0 = reinterpret_cast<const E*>(a.f0)[i];
+            const Quartic<T, E> q = fit_one<T, NT, E>(d, y0, y1, f0, f1, kk);
+            const double ta = a.tprev[r], tb = a.t1[r];
+            for (int j = lo; j < hi; ++j) {
+                const T x = (T)((a.tgrid[(int64_t)j * a.n_rows + r] - ta) / (tb - ta));   // interp.py:39-40 in W, then T
+                reinterpret_cast<E*>(a.sol + (int64_t)j * a.n)[i] = eval_one<T, E>(q, x);
+            }
+        }
+        reinterpret_cast<E*>(a.y0)[i] = y1;
+        reinterpret_cast<E*>(a.f0)[i] = f1;
+    }
+}
+
+}  // namespace tdeq

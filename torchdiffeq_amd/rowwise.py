@@ -1,0 +1,613 @@
+"""`odeint_rowwise`: a batch of independent IVPs, each row with its own adaptive step controller.
+
+`odeint` treats a batched state as ONE system: the error ratio is the RMS over every element of the batch, so every
+row takes the same step sizes and the same accept / reject decisions, and a row's answer depends on its batch mates.
+Here row r of `y0[B, *row_shape]` is its own IVP: its own error norm (the RMS over its L = prod(row_shape) elements),
+its own step size, accept / reject decision, counters and output times.  A row's bits do not depend on B or on the
+other rows (as long as `func` itself treats rows independently).
+
+On a ROCm device every state-sized operation is a HIP kernel of csrc/tdeq_kernels_rowwise.hpp and the per-row
+controller runs on the device (the host reads two words per trial step); CPU states run the same row operations as
+torch ops (`HostRowKernels`, one `HostPathWarning`).
+"""
+from __future__ import annotations
+
+import math
+from typing import List
+
+import numpy as np
+import torch
+
+from . import _fallback, _native
+from ._native import device_guard
+from ._scalars import nextafter, power, rdiv, scalar_type
+from .solvers._common import optimal_step_size
+from .solvers.adaptive import (AdaptiveHeunSolver, Bosh3Solver, Dopri5Solver, Dopri8Solver, Fehlberg2,
+                               Tsit5Solver)
+from .tableaus import SparseRow, carry_plan
+
+__all__ = ["odeint_rowwise"]
+
+_METHODS = {"dopri5": Dopri5Solver, "bosh3": Bosh3Solver, "tsit5": Tsit5Solver, "fehlberg2": Fehlberg2,
+            "adaptive_heun": AdaptiveHeunSolver, "dopri8": Dopri8Solver}
+_OPTIONS = ("first_step", "safety", "ifactor", "dfactor", "max_num_steps")
+_NO_ERROR_ROW = 0x7FFFFFFF
+
+
+class _Method:
+    """Host-side constants of one tableau, shared by both backends."""
+
+    def __init__(self, name: str, np_dtype):
+        cls = _METHODS[name]
+        tab = cls.tableau
+        self.name, self.order, self.tableau = name, cls.order, tab
+        self.beta = tab.beta_rows()
+        self.c_sol = SparseRow.from_dense(tab.c_sol)
+        self.c_err = SparseRow.from_dense(tab.c_error)
+        self.c_mid = SparseRow.from_dense(tab.c_mid)
+        self.fsal = tab.fsal_solution
+        self.alpha = [np_dtype(a) for a in tab.alpha]
+        self.alpha_is_one = [a == 1.0 for a in tab.alpha]
+        self.n_stages = len(self.beta)
+
+
+def _func_parameters_require_grad(func) -> bool:
+    params = getattr(func, "parameters", None)
+    if callable(params):
+        try:
+            return any(p.requires_grad for p in params())
+        except TypeError:
+            return False
+    return False
+
+
+class _Problem:
+    """Validated inputs: y [B, L] (contiguous copy), tgrid [T, B] fp64 in solver time (ascending), sign."""
+
+    def __init__(self, func, y0, t, rtol, atol, method, options, event_fn):
+        if event_fn is not None:
+            raise ValueError("odeint_rowwise: event_fn is not supported (use odeint)")
+        if not isinstance(y0, torch.Tensor):
+            raise ValueError("odeint_rowwise: tuple states are not supported; y0 must be one tensor [B, *row_shape]")
+        if y0.dtype not in (torch.float32, torch.float64):
+            raise ValueError(f"odeint_rowwise: the state dtype must be float32 or float64, got {y0.dtype} "
+                             "(16-bit, complex and integer states are not supported)")
+        if y0.dim() < 1 or y0.shape[0] < 1:
+            raise ValueError("odeint_rowwise: y0 must have a leading batch dimension B >= 1")
+        if method not in _METHODS:
+            raise ValueError('odeint_rowwise: method "{}" is not supported; one of {}'.format(
+                method, ", ".join(sorted(_METHODS))))
+        options = dict(options or {})
+        unknown = sorted(set(options) - set(_OPTIONS))
+        if unknown:
+            raise ValueError("odeint_rowwise: unsupported option(s) {}; supported: {}".format(
+                ", ".join(repr(u) for u in unknown), ", ".join(_OPTIONS)))
+        for name, tol in (("rtol", rtol), ("atol", atol)):
+            if isinstance(tol, torch.Tensor):
+                if tol.numel() != 1:
+                    raise ValueError(f"odeint_rowwise: vector tolerances are not supported ({name} has {tol.numel()} "
+                                     "elements)")
+            elif not isinstance(tol, (int, float)) or isinstance(tol, bool):
+                raise ValueError(f"odeint_rowwise: {name} must be a number (vector / tuple tolerances are not supported)")
+        for name in _native_callback_names():
+            if getattr(func, name, None) is not None:
+                raise ValueError(f"odeint_rowwise: step callbacks ({name}) are not supported")
+        if not isinstance(t, torch.Tensor) or not torch.is_floating_point(t):
+            raise ValueError("odeint_rowwise: t must be a floating point tensor [T] or [T, B]")
+        B = y0.shape[0]
+        if t.dim() == 2:
+            if t.shape[1] != B:
+                raise ValueError(f"odeint_rowwise: a 2-D t must be [T, B] = [T, {B}], got {tuple(t.shape)}")
+        elif t.dim() != 1:
+            raise ValueError(f"odeint_rowwise: t must be [T] or [T, B], got {t.dim()} dimensions")
+        if t.shape[0] < 1:
+            raise ValueError("odeint_rowwise: t needs at least one time")
+        if torch.is_grad_enabled() and (y0.requires_grad or t.requires_grad or _func_parameters_require_grad(func)):
+            raise NotImplementedError("odeint_rowwise does not propagate gradients; use odeint (backprop through the "
+                                      "solver) or odeint_adjoint, or call it under torch.no_grad()")
+
+        self.func, self.shape, self.B = func, y0.shape, B
+        self.L = int(math.prod(y0.shape[1:]))
+        self.dtype, self.device = y0.dtype, y0.device
+        self.np_dtype = scalar_type(y0.dtype)
+        tg = t.detach().to(torch.float64)
+        tg = tg[:, None].expand(-1, B) if tg.dim() == 1 else tg
+        tg = tg.to("cpu")
+        n_t = tg.shape[0]
+        sign = 1.0
+        if n_t > 1:
+            inc, dec = bool((tg[1:] > tg[:-1]).all()), bool((tg[1:] < tg[:-1]).all())
+            if not (inc or dec):
+                raise ValueError("odeint_rowwise: every row of t must be strictly monotone, all in the same direction")
+            sign = 1.0 if inc else -1.0
+        # times as the solver sees them: the grid cast to the state's type and back (odeint: t.to(y0.dtype)), negated
+        # for decreasing time (misc.py `_ReverseFunc`)
+        self.tgrid = (tg * sign).contiguous()
+        self.sign = sign
+        self.y0 = y0.detach().reshape(B, self.L).contiguous()
+        self.rtol, self.atol = float(rtol), float(atol)
+        self.method = _Method(method, self.np_dtype)
+        fs = options.get("first_step")
+        if fs is not None:
+            fs = torch.as_tensor(fs, dtype=torch.float64).detach().reshape(-1).cpu()
+            if fs.numel() == 1:
+                fs = fs.expand(B)
+            elif fs.numel() != B:
+                raise ValueError(f"odeint_rowwise: first_step must be a scalar or a [B] = [{B}] tensor")
+            fs = fs.abs()
+        self.first_step = fs
+        self.safety = float(options.get("safety", 0.9))
+        self.ifactor = float(options.get("ifactor", 10.0))
+        self.dfactor = float(options.get("dfactor", 0.2))
+        self.max_num_steps = int(options.get("max_num_steps", 2 ** 31 - 1))
+        self.nfe = 0
+
+    def call(self, t_rows: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+        """func(t_rows [B], y [B, *row_shape]) -> [B, L] contiguous in the state's dtype."""
+        self.nfe += 1
+        f = self.func(t_rows, y.view(self.shape))
+        if not isinstance(f, torch.Tensor):
+            raise TypeError("odeint_rowwise: func must return a Tensor, got {}".format(type(f).__name__))
+        if f.requires_grad and torch.is_grad_enabled():
+            raise NotImplementedError("odeint_rowwise does not propagate gradients (func's output requires grad); use "
+                                      "odeint / odeint_adjoint, or call it under torch.no_grad()")
+        if f.shape != self.shape:
+            raise RuntimeError("odeint_rowwise: func returned shape {} for a state of shape {}".format(
+                tuple(f.shape), tuple(self.shape)))
+        if f.device != self.device:
+            raise RuntimeError(f"odeint_rowwise: func returned a tensor on '{f.device}', the state lives on '{self.device}'")
+        f = f.reshape(self.B, self.L)
+        if f.dtype != self.dtype:
+            f = f.to(self.dtype)
+        return f if f.is_contiguous() and f.data_ptr() % 16 == 0 else f.contiguous(memory_format=torch.contiguous_format).clone()
+
+    def raise_row_error(self, r: int, code: int, since: int, dt: float, y_row) -> None:
+        if code == 2:
+            raise AssertionError("max_num_steps exceeded ({}>={}) in row {}".format(since, self.max_num_steps, r))
+        if code == 1:
+            raise AssertionError("underflow in dt {} in row {}".format(dt, r))
+        raise AssertionError("non-finite values in state `y`: {} in row {}".format(y_row, r))
+
+
+def _native_callback_names():
+    return ("callback_step", "callback_accept_step", "callback_reject_step")
+
+
+def _row_sum(x: torch.Tensor) -> torch.Tensor:
+    """Sum over dim 1 of an fp64 [B, L] tensor in a FIXED order (pairwise halving over a zero-padded power-of-two
+    width): each addition is an elementwise op, so a row's sum has the same bits in a batch of any size — unlike
+    `sum(dim=-1)`, whose order ATen may choose by shape and thread count."""
+    n = x.shape[1]
+    w = 1 << max(0, (n - 1).bit_length())
+    if w != n:
+        x = torch.cat([x, x.new_zeros(x.shape[0], w - n)], dim=1)
+    while x.shape[1] > 1:
+        h = x.shape[1] // 2
+        x = x[:, :h] + x[:, h:]
+    return x[:, 0]
+
+
+class HostRowKernels:
+    """The row operations of `odeint_rowwise` as torch ops (CPU states): the per-row controller runs as host scalar
+    arithmetic, row by row, with the decisions of the device controller (tdeq_kernels_rowwise.hpp)."""
+
+    name = "host"
+
+    def __init__(self, p: _Problem):
+        self.p = p
+        T = p.np_dtype
+        self.T = T
+        B = p.B
+        self.t0 = np.zeros(B)
+        self.tprev = np.zeros(B)
+        self.dt = np.zeros(B)
+        self.active = np.ones(B, dtype=bool)
+        self.since = np.zeros(B, dtype=np.int64)
+        self.next_out = np.ones(B, dtype=np.int64)
+        self.bad_y = np.zeros(B, dtype=bool)
+        self.n_acc = np.zeros(B, dtype=np.int64)
+        self.n_rej = np.zeros(B, dtype=np.int64)
+        self.code = np.zeros(B, dtype=np.int64)
+        self.tg = p.tgrid.numpy()
+
+    # -- helpers ------------------------------------------------------------------------------------------------------
+    def _coef(self, coef: float, dts: torch.Tensor) -> torch.Tensor:
+        return torch.tensor(coef, dtype=self.p.dtype) * dts
+
+    def _sum_terms(self, ks, row: SparseRow, dts):
+        acc = None
+        for j, c in zip(row.idx, row.coef):
+            term = ks[j] * self._coef(c, dts)
+            acc = term if acc is None else acc + term
+        return acc
+
+    def _dts_tensor(self, vals) -> torch.Tensor:
+        return torch.tensor(np.asarray(vals, dtype=self.T).astype(np.float64), dtype=self.p.dtype).reshape(-1, 1)
+
+    def _row_norms(self, q: torch.Tensor) -> np.ndarray:
+        qd = q.to(torch.float64)
+        return _row_sum(qd * qd).numpy()
+
+    def stage_time(self, r: int, i: int):
+        m, T = self.p.method, self.T
+        t0, dt = self.t0[r], self.dt[r]
+        if m.alpha_is_one[i]:
+            t1 = T(t0 + dt)
+            tt = nextafter(t1, t1 - 1)
+        else:
+            tt = T(t0) + m.alpha[i] * T(dt)
+        return float(self.p.sign * tt)
+
+    def times_tensor(self) -> List[torch.Tensor]:
+        p, m = self.p, self.p.method
+        out = np.empty((m.n_stages, p.B))
+        for r in range(p.B):
+            for i in range(m.n_stages):
+                out[i, r] = self.stage_time(r, i) if self.active[r] else float(p.sign * self.T(self.t0[r]))
+        return list(torch.tensor(out, dtype=p.dtype).unbind(0))
+
+    def prepare(self, r: int) -> None:
+        dt = self.dt[r]
+        if not math.isfinite(dt):
+            dt = 0.0
+        dt = max(dt, 0.0)
+        self.dt[r] = dt
+        code = 3 if self.bad_y[r] else 0
+        if not self.t0[r] + dt > self.t0[r]:
+            code = 1
+        if self.since[r] >= self.p.max_num_steps:
+            code = 2
+        self.code[r] = code
+
+    # -- initial step ---------------------------------------------------------------------------------------------------
+    def initial_step(self, y, f0) -> None:
+        p, T = self.p, self.T
+        self.t0[:] = p.tgrid[0].numpy()
+        scale = p.atol + y.abs() * p.rtol
+        bad = (~torch.isfinite(y)).sum(dim=1).numpy()
+        self.bad_y[:] = bad != 0
+        if p.first_step is not None:
+            self.dt[:] = p.first_step.numpy()
+        else:
+            s0, s1 = self._row_norms(y / scale), self._row_norms(f0 / scale)
+            h0 = np.empty(p.B, dtype=object)
+            d1s = []
+            with np.errstate(all="ignore"):
+                for r in range(p.B):
+                    d0, d1 = T(math.sqrt(s0[r] / p.L)), T(math.sqrt(s1[r] / p.L))
+                    h = T(1e-6) if (d0 < 1e-5 or d1 < 1e-5) else 0.01 * d0 / d1
+                    h0[r] = abs(h)
+                    d1s.append(d1)
+            c = torch.tensor([float(T(float(h) * p.sign)) for h in h0], dtype=p.dtype).reshape(-1, 1)
+            y1 = y + f0 * c
+            t1 = torch.tensor([float(p.sign * T(self.t0[r] + float(h0[r]))) for r in range(p.B)], dtype=p.dtype)
+            f1 = p.call(t1, y1)
+            s2 = self._row_norms((f1 - f0) / scale)
+            order = p.method.order - 1
+            with np.errstate(all="ignore"):
+                for r in range(p.B):
+                    hh, d1 = h0[r], d1s[r]
+                    d2 = abs(T(math.sqrt(s2[r] / p.L)) / hh)
+                    if d1 <= 1e-15 and d2 <= 1e-15:
+                        h1 = max(T(1e-6), hh * 1e-3)
+                    else:
+                        h1 = power(rdiv(0.01, max(d1, d2)), 1.0 / float(order + 1))
+                    h1 = abs(h1)
+                    self.dt[r] = float(min(100 * hh, h1))
+        for r in range(p.B):
+            self.prepare(r)
+
+    # -- trial step -----------------------------------------------------------------------------------------------------
+    def trial_step(self, y, f0, sol) -> None:
+        p, m, T = self.p, self.p.method, self.T
+        dts = self._dts_tensor([T(self.dt[r]) * T(p.sign) if self.active[r] else T(0) for r in range(p.B)])
+        act = torch.from_numpy(self.active.copy()).reshape(-1, 1)
+        times = self.times_tensor()
+        ks = [f0]
+        yi = None
+        for i, row in enumerate(m.beta):
+            yi = torch.where(act, y + self._sum_terms(ks, row, dts), y)
+            ks.append(p.call(times[i], yi))
+        y1 = yi if m.fsal else torch.where(act, y + self._sum_terms(ks, m.c_sol, dts), y)
+        f1 = ks[-1]
+        err = self._sum_terms(ks, m.c_err, dts)
+        tol = p.atol + p.rtol * torch.maximum(y.abs(), y1.abs())
+        sums = self._row_norms(err / tol)
+        bad = ((~torch.isfinite(y)) | (~torch.isfinite(y1))).sum(dim=1).numpy()
+        accepted = []
+        n_out = self.tg.shape[0]
+        with np.errstate(all="ignore"):
+            for r in range(p.B):
+                if not self.active[r]:
+                    continue
+                ratio = float(T(math.sqrt(sums[r] / p.L)))
+                dt = self.dt[r]
+                accept = bool(dt <= 0.0 or ratio <= 1)
+                dt_next = optimal_step_size(dt, ratio, p.safety, p.ifactor, p.dfactor, m.order)
+                if dt_next == dt_next:
+                    dt_next = max(dt_next, 0.0)          # the clamp to [min_step, max_step] = [0, inf]; NaN stays
+                self.since[r] += 1
+                if accept:
+                    t1 = self.t0[r] + dt
+                    self.tprev[r], self.t0[r] = self.t0[r], t1
+                    self.n_acc[r] += 1
+                    lo = hi = int(self.next_out[r])
+                    while hi < n_out and self.tg[hi, r] <= t1:
+                        hi += 1
+                    self.next_out[r] = hi
+                    if hi > lo:
+                        self.since[r] = 0
+                    self.bad_y[r] = bad[r] != 0
+                    accepted.append((r, lo, hi))
+                    if hi >= n_out:
+                        self.active[r] = False
+                else:
+                    self.n_rej[r] += 1
+                self.dt[r] = dt_next
+        if accepted:
+            self._dense_commit(accepted, y, y1, f0, f1, ks, dts, sol)
+        for r in range(p.B):
+            if self.active[r]:
+                self.prepare(r)
+
+    def _dense_commit(self, accepted, y, y1, f0, f1, ks, dts, sol) -> None:
+        p, m, T = self.p, self.p.method, self.T
+        rows = torch.tensor([r for r, _, _ in accepted])
+        with_out = [(i, r, lo, hi) for i, (r, lo, hi) in enumerate(accepted) if hi > lo]
+        if with_out:
+            idx = torch.tensor([r for _, r, _, _ in with_out])
+            d = dts[idx]
+            y0r, y1r, f0r, f1r = y[idx], y1[idx], f0[idx], f1[idx]
+            kr = [k[idx] if k is not None else None for k in ks]
+            ymid = y0r + self._sum_terms(kr, m.c_mid, d)
+            two_dt = torch.tensor(2.0, dtype=p.dtype) * d
+            qa = ((f1r - f0r) * two_dt - (y1r + y0r) * 8.0) + ymid * 16.0
+            qb = (((f0r * 5.0 - f1r * 3.0) * d + y0r * 18.0) + y1r * 14.0) - ymid * 32.0
+            qc = (((f1r - f0r * 4.0) * d - y0r * 11.0) - y1r * 5.0) + ymid * 16.0
+            qd = f0r * d
+            for n, (_, r, lo, hi) in enumerate(with_out):
+                ta, tb = self.tprev[r], self.t0[r]
+                for j in range(lo, hi):
+                    x = T((self.tg[j, r] - ta) / (tb - ta))
+                    xf = float(x)
+                    total = y0r[n] + qd[n] * xf
+                    xp = x * x
+                    total = total + qc[n] * float(xp)
+                    xp = xp * x
+                    total = total + qb[n] * float(xp)
+                    xp = xp * x
+                    total = total + qa[n] * float(xp)
+                    sol[j, r] = total
+        y[rows] = y1[rows]
+        f0[rows] = f1[rows]
+
+
+class HipRowKernels:
+    """The row operations of `odeint_rowwise` on the HIP kernels (csrc/tdeq_kernels_rowwise.hpp)."""
+
+    name = "hip"
+
+    def __init__(self, p: _Problem):
+        self.p = p
+        self.k = _native.get_kernels(p.device, p.dtype)
+        dev, B = p.device, p.B
+        f64 = dict(dtype=torch.float64, device=dev)
+        i32 = dict(dtype=torch.int32, device=dev)
+        self.t0 = p.tgrid[0].to(dev).clone()
+        self.tprev = torch.zeros(B, **f64)
+        self.dt = torch.zeros(B, **f64)
+        self.h0 = torch.zeros(B, **f64)
+        self.ratio = torch.zeros(B, **f64)
+        self.tg = p.tgrid.to(dev)
+        self.active = torch.ones(B, **i32)
+        self.accepted = torch.zeros(B, **i32)
+        self.out_lo = torch.zeros(B, **i32)
+        self.out_hi = torch.zeros(B, **i32)
+        self.next_out = torch.ones(B, **i32)
+        self.since = torch.zeros(B, **i32)
+        self.bad_y = torch.zeros(B, **i32)
+        self.code = torch.zeros(B, **i32)
+        self.n_acc = torch.zeros(B, dtype=torch.int64, device=dev)
+        self.n_rej = torch.zeros(B, dtype=torch.int64, device=dev)
+        self.status = torch.zeros(2, **i32)
+        self.nch = self.k.row_partials(p.L, p.dtype)
+        self.part = torch.empty(3 * B * self.nch, **f64)
+        st = _native.RowState()
+        for name in ("t0", "tprev", "dt", "h0", "active", "accepted", "out_lo", "out_hi", "next_out", "since", "bad_y",
+                     "code", "n_acc", "n_rej", "ratio", "status"):
+            setattr(st, name, getattr(self, name).data_ptr())
+        st.tgrid = self.tg.data_ptr()
+        st.n_rows, st.row_len, st.max_num_steps = B, p.L, p.max_num_steps
+        st.n_out, st.order = self.tg.shape[0], p.method.order - 1
+        self.st = st
+        m = p.method
+        c = _native.StepCtrl()
+        c.safety, c.ifactor, c.dfactor = p.safety, p.ifactor, p.dfactor
+        c.exponent = 1.0 / m.order
+        c.min_step, c.max_step = 0.0, math.inf
+        c.time_sign = p.sign
+        mask = 0
+        for i, a in enumerate(m.alpha):
+            c.alpha[i] = float(a)
+            if m.alpha_is_one[i]:
+                mask |= 1 << i
+        c.alpha_is_one = mask
+        c.n_times = m.n_stages
+        c.n_norm_seg = 1
+        self.ctrl = c
+        self.carry = carry_plan(m.name)
+        self.dts = None
+        self.times = None
+
+    def _control(self, mode: int) -> None:
+        p = self.p
+        dts = torch.empty(p.B, dtype=p.dtype, device=p.device)
+        times = torch.empty(p.method.n_stages, p.B, dtype=p.dtype, device=p.device)
+        self.k.row_control(mode, self.part, self.ctrl, self.st, dts, times, p.dtype)
+        self.dts, self.times = dts, times
+
+    def status_words(self):
+        return self.status.tolist()
+
+    def initial_step(self, y, f0) -> None:
+        p, k = self.p, self.k
+        k.row_reduce(1, self.part, y, y, f0, [], [], None, None, p.rtol, p.atol)
+        if p.first_step is not None:
+            self.dt.copy_(p.first_step.to(self.dt.device))
+            self._control(3)
+            return
+        self._control(1)
+        y1 = torch.empty_like(y)
+        k.row_combine([y1], (((1.0,), 1, True),), y, None, [f0], self.dts, self.active)
+        f1 = p.call(self.times[0], y1)
+        k.row_reduce(2, self.part, y, f1, f0, [], [], None, None, p.rtol, p.atol)
+        self._control(2)
+
+    def trial_step(self, y, f0, sol) -> None:
+        p, m, k = self.p, self.p.method, self.k
+        dts, times, act = self.dts, self.times.unbind(0), self.active
+        ks = [f0]
+        S = m.n_stages
+        err_partial, err_rem = None, None
+        y1 = None
+        if self.carry is not None:
+            carry = self.carry
+            held, R = {}, len(carry.ops)
+            yi = torch.empty_like(y)
+            k.row_combine([yi], ((m.beta[0].coef, (1 << len(m.beta[0].idx)) - 1, True),), y, None,
+                          [ks[j] for j in m.beta[0].idx], dts, act)
+            ks.append(p.call(times[0], yi))
+            for i in range(1, R):
+                op = carry.ops[i]
+                if op is None:
+                    yi = held.pop(i)
+                else:
+                    outs = [torch.empty_like(y) for _ in op.targets]
+                    k.row_combine(outs, op.spec, y, held.pop(i) if op.continues else None, [ks[j] for j in op.idx],
+                                  dts, act)
+                    yi = outs[0]
+                    for tgt, buf in zip(op.targets[1:], outs[1:]):
+                        held[tgt] = buf
+                if i < S:
+                    ks.append(p.call(times[i], yi))
+                else:
+                    y1 = yi
+            err_partial, err_rem = held.pop(R), (carry.err_idx, carry.err_coef)
+            if y1 is None:
+                y1 = yi
+        else:
+            n_lead = len((m.beta[-1] if m.fsal else m.c_sol).idx)
+            # the step's last combine also emits the error row's leading run when it is the same stage set and the norm
+            # launch keeps at least one stage of its own (adaptive_heun's error row has no stage beyond it: not fused)
+            fuse = m.c_err.idx[:n_lead] == (m.beta[-1] if m.fsal else m.c_sol).idx and len(m.c_err.idx) > n_lead
+            for i, row in enumerate(m.beta):
+                last = i == S - 1 and m.fsal and fuse
+                yi = torch.empty_like(y)
+                spec = ((row.coef, (1 << len(row.idx)) - 1, True),)
+                outs = [yi]
+                if last:
+                    err_partial = torch.empty_like(y)
+                    spec = spec + ((m.c_err.coef[:n_lead], (1 << n_lead) - 1, False),)
+                    outs.append(err_partial)
+                k.row_combine(outs, spec, y, None, [ks[j] for j in row.idx], dts, act)
+                ks.append(p.call(times[i], yi))
+            if m.fsal:
+                y1 = yi
+            else:
+                y1 = torch.empty_like(y)
+                spec = ((m.c_sol.coef, (1 << len(m.c_sol.idx)) - 1, True),)
+                outs = [y1]
+                if fuse:
+                    err_partial = torch.empty_like(y)
+                    spec = spec + ((m.c_err.coef[:n_lead], (1 << n_lead) - 1, False),)
+                    outs.append(err_partial)
+                k.row_combine(outs, spec, y, None, [ks[j] for j in m.c_sol.idx], dts, act)
+            if err_partial is not None:
+                err_rem = (m.c_err.idx[n_lead:], m.c_err.coef[n_lead:])
+        if err_partial is None:
+            k.row_reduce(0, self.part, y, y1, None, [ks[j] for j in m.c_err.idx], m.c_err.coef, dts, act,
+                         p.rtol, p.atol)
+        else:
+            k.row_reduce(0, self.part, y, y1, err_partial, [ks[j] for j in err_rem[0]], err_rem[1], dts, act,
+                         p.rtol, p.atol)
+        step_dts = dts
+        self._control(0)
+        k.row_dense_commit(sol, y, y1, f0, ks[-1], [ks[j] for j in m.c_mid.idx], m.c_mid.coef, step_dts, self.st)
+
+    def finish(self):
+        return self.n_acc.cpu(), self.n_rej.cpu()
+
+    def row_error(self, r: int):
+        return int(self.code[r]), int(self.since[r]), float(self.dt[r])
+
+
+def odeint_rowwise(func, y0, t, *, rtol=1e-7, atol=1e-9, method="dopri5", options=None, return_stats=False,
+                   event_fn=None):
+    """Integrate B independent IVPs `dy_r/dt = func(t, y)[r]`, each row with its own adaptive step controller.
+
+    `y0` is one tensor `[B, *row_shape]` (fp32 / fp64); row r is the IVP of `y0[r]`.  `t` is `[T]` (a grid shared by all
+    rows) or `[T, B]` (a grid per row); every row strictly monotone, all in the same direction.
+
+    `func(t_rows, y)` gets `t_rows`, a 1-D tensor `[B]` on y0's device in the state's dtype holding each row's stage time
+    (rows see different times: `func` must broadcast it itself, e.g. `t_rows[:, None]`), and `y [B, *row_shape]`; it
+    returns dy/dt of the same shape.  A row that has reached its last output time stays frozen at the end of its last
+    accepted step and is still evaluated there; its output is ignored (NaN or Inf included).
+
+    Methods: dopri5, bosh3, tsit5, fehlberg2, adaptive_heun, dopri8.  Options: `first_step` (scalar or `[B]`),
+    `safety`, `ifactor`, `dfactor`, `max_num_steps` (per row).  Everything else raises ValueError.  Error norm per
+    row: the RMS over the row's elements of err / (atol + rtol * max(|y0|, |y1|)) — `odeint`'s norm for a one-row
+    state — and the reference's controller per row.
+
+    Returns the solution `[T, *y0.shape]` with `solution[j, r]` = row r at `t[j]` (or `t[j, r]`); with
+    `return_stats=True`, `(solution, stats)` where `stats` holds `n_accepted` and `n_rejected` (int64 `[B]`) and
+    `nfe` (func calls for the whole batch).  No gradients: with grad mode on and `y0`, `t` or a parameter of `func`
+    requiring grad this raises NotImplementedError (use `odeint` / `odeint_adjoint`).
+    """
+    p = _Problem(func, y0, t, rtol, atol, method, options, event_fn)
+    n_t = p.tgrid.shape[0]
+    f0 = None
+    if n_t > 1:
+        # the first evaluation in the caller's grad mode: a func whose output depends on parameters that require grad
+        # (closures included) is refused here, never silently detached
+        with device_guard(p.device):
+            f0 = p.call((p.tgrid[0] * p.sign).to(p.dtype).to(p.device), p.y0).clone()
+    with torch.no_grad(), device_guard(p.device):
+        sol = torch.empty(n_t, p.B, p.L, dtype=p.dtype, device=p.device)
+        sol[0].copy_(p.y0)
+        if p.device.type == "cuda":
+            kern = HipRowKernels(p)
+        else:
+            _fallback.warn_once(f"the state lives on '{p.device}'")
+            kern = HostRowKernels(p)
+        n_acc = n_rej = None
+        if n_t > 1:
+            # private state buffers: the dense-output launch commits y <- y1, f0 <- f1 in place
+            y = p.y0.clone()
+            kern.initial_step(y, f0)
+            while True:
+                if isinstance(kern, HipRowKernels):
+                    n_active, err_row = kern.status_words()
+                    if err_row != _NO_ERROR_ROW and n_active > 0:
+                        code, since, dt = kern.row_error(err_row)
+                        p.raise_row_error(err_row, code, since, dt, y[err_row].view(p.shape[1:]))
+                else:
+                    n_active = int(kern.active.sum())
+                    bad = [r for r in range(p.B) if kern.active[r] and kern.code[r] != 0]
+                    if bad:
+                        r = bad[0]
+                        p.raise_row_error(r, int(kern.code[r]), int(kern.since[r]), float(kern.dt[r]),
+                                          y[r].view(p.shape[1:]))
+                if n_active == 0:
+                    break
+                kern.trial_step(y, f0, sol)
+            if isinstance(kern, HipRowKernels):
+                n_acc, n_rej = kern.finish()
+            else:
+                n_acc, n_rej = torch.from_numpy(kern.n_acc.copy()), torch.from_numpy(kern.n_rej.copy())
+        solution = sol.view(n_t, *p.shape)
+    if not return_stats:
+        return solution
+    if n_acc is None:
+        n_acc = torch.zeros(p.B, dtype=torch.int64)
+        n_rej = torch.zeros(p.B, dtype=torch.int64)
+    return solution, {"n_accepted": n_acc.to(torch.int64), "n_rejected": n_rej.to(torch.int64), "nfe": p.nfe}
