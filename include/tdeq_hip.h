@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define TDEQ_ABI_VERSION 22
+#define TDEQ_ABI_VERSION 23
 #define TDEQ_F32 0
 #define TDEQ_F64 1
 /* interleaved (re, im) complex states — accepted by the NORM entry points only (tdeq_error_norm, tdeq_error_norm_partial[_ctrl],
@@ -538,7 +538,7 @@ int tdeq_adams_correct(void* y_out, void* dy_out, const void* f, const void* del
                        double* out_nonfinite, void* workspace, size_t workspace_bytes, int dtype, void* stream);
 
 /*
- * ---- Per-row step control (ABI 22; torchdiffeq_amd/rowwise.py `odeint_rowwise`) ----
+ * ---- Per-row step control (since ABI 22; torchdiffeq_amd/rowwise.py `odeint_rowwise`) ----
  * The state is [n_rows, row_len] row-major (fp32 / fp64 only); every row is its own IVP with its own step controller.
  * Per-row device vectors (length n_rows) carry the controller state; the entry points below read and update them.
  *
@@ -597,6 +597,25 @@ int tdeq_row_control(int mode, const double* part, const tdeq_step_ctrl* ctrl, c
 int tdeq_row_dense_commit(void* sol, void* y0, const void* y1, void* f0, const void* f1, const void* const* k,
                           const double* coef, int n_terms, const void* dts, const tdeq_row_state* st, int dtype,
                           void* stream);
+
+/*
+ * ---- Backward of the row-linear operations (ABI 23; torchdiffeq_amd/rowwise_autodiff.py, `differentiable=True`) ----
+ * Every state-sized operation of a rowwise trial step is out[r, :] = sum_m w_m[r] X_m[r, :] with one weight per row.
+ *
+ * tdeq_row_scale_many   outs[m][r, e] = w[m * n_rows + r] * g[r, e] (one rounding), m < n_out <= TDEQ_MAX_TERMS; `w` is a
+ *                       device [n_out, n_rows] tensor of the state type; g is read once.
+ * tdeq_row_multi_dot    out[m * n_rows + r] = sum_e g[r, e] * x[m][r, e] accumulated in fp64, m < n_x <= TDEQ_MAX_TERMS,
+ *                       with the reduction geometry of tdeq_row_reduce: a row's dot has the same bits in a batch of
+ *                       any size.  Rows of more than one partial (tdeq_row_partials) need a workspace of
+ *                       tdeq_row_dots_workspace_bytes (0 for short rows: `workspace` may then be NULL); 16-byte aligned
+ *                       tensors whenever row_len is a multiple of 16 / sizeof(T).
+ * n_rows == 0: no-op.  row_len == 0: scale_many is a no-op, multi_dot writes zeros.
+ */
+int tdeq_row_scale_many(void* const* outs, int n_out, const void* g, const void* w, int64_t n_rows, int64_t row_len,
+                        int dtype, void* stream);
+size_t tdeq_row_dots_workspace_bytes(int64_t n_rows, int64_t row_len, int n_x, int dtype);
+int tdeq_row_multi_dot(const void* g, const void* const* x, int n_x, int64_t n_rows, int64_t row_len, double* out,
+                       void* workspace, size_t workspace_bytes, int dtype, void* stream);
 
 #ifdef __cplusplus
 }

@@ -3,6 +3,13 @@ on a mixed-stiffness batch.
 
     python tools/rowwise_bench.py [--out profiles/rowwise_bench.json] [--reps 3]
     python tools/rowwise_bench.py --stats <rocprofv3 kernel_stats.csv> --bench <that json>   (adds in-situ bandwidth)
+    python tools/rowwise_bench.py --grad [--out profiles/rowwise_grad_bench.json] [--parity profiles/rowwise_grad_parity.json]
+    python tools/rowwise_bench.py --grad --stats <kernel_stats.csv>[,<second>,...] --bench <that json>
+                                                                 (row_scale_many bandwidth, one csv per traced repeat)
+
+`--grad`: forward + backward of a `differentiable=True` solve per trial step at the headline, next to plain `odeint`
+backprop of the same state, and (`--parity`) the per-row deviations of the rowwise gradients from the reference's
+(tests/golden/rowwise_grad.npz) on the host path and on the device.
 
 Headline workload of bench.py: dopri5, func y @ A.T, 65536 x 128 fp32, rtol 1e-7, atol 1e-9.  A trial step of
 odeint_rowwise is one pass of its loop (S evaluations); odeint's is one call of its adaptive step; both are timed over
@@ -56,6 +63,91 @@ def _headline(reps: int):
         res[k] = res[k][1:]          # the first pair warms up
     res["ratio_rowwise_over_odeint"] = min(res["rowwise_ms_per_trial"]) / min(res["odeint_ms_per_trial"])
     return res
+
+
+def _grad_headline(reps: int):
+    """ms per trial step of forward + backward: odeint_rowwise(differentiable=True) and odeint (eager launches)."""
+    import torchdiffeq_amd as tda
+    dev = torch.device("cuda", 0)
+    B, D = 65536, 128
+    g = torch.Generator().manual_seed(0)
+    G = torch.randn(D, D, generator=g, dtype=torch.float64) / D ** 0.5
+    A = (0.5 * (G - G.T) - 0.1 * torch.eye(D, dtype=torch.float64)).float().to(dev)
+    y0 = torch.randn(B, D, generator=g).to(dev)
+    t = torch.tensor([0.0, 0.5], device=dev)
+    calls = [0]
+
+    def f(t_, y):
+        calls[0] += 1
+        return y @ A.T
+    res = {"rowwise_grad_ms_per_trial": [], "odeint_grad_ms_per_trial": []}
+    for _ in range(reps + 1):
+        for which in ("rowwise", "odeint"):
+            calls[0] = 0
+            y = y0.clone().requires_grad_(True)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            if which == "rowwise":
+                sol = tda.odeint_rowwise(f, y, t, rtol=1e-7, atol=1e-9, differentiable=True)
+            else:
+                sol = tda.odeint(f, y, t, rtol=1e-7, atol=1e-9, options={"hip_graph": False})
+            sol[-1].sum().backward()
+            torch.cuda.synchronize()
+            ms = (time.perf_counter() - t0) * 1e3
+            trials = (calls[0] - 2) / 6
+            res[which + "_grad_ms_per_trial"].append(ms / trials)
+            res[which + "_trials"] = trials
+            del sol, y
+    for k in ("rowwise_grad_ms_per_trial", "odeint_grad_ms_per_trial"):
+        res[k] = res[k][1:]          # the first pair warms up
+    res["ratio_rowwise_over_odeint"] = min(res["rowwise_grad_ms_per_trial"]) / min(res["odeint_grad_ms_per_trial"])
+    return res
+
+
+def _grad_parity():
+    """Per-row deviation of the rowwise gradients from the reference's, every fixture case, host path and device."""
+    import warnings
+    import torchdiffeq_amd as tda
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    from _rowwise_grad_cases import CASE_NAMES, row_bounds, solve_case
+    out = {}
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore", tda.HostPathWarning)
+        for name in CASE_NAMES:
+            entry = {}
+            for label, device in (("host", "cpu"), ("hip", torch.device("cuda", 0))):
+                dev, spread, _, _ = solve_case(tda, name, device=device)
+                entry[label] = {"per_row": [float(v) for v in dev], "worst": float(dev.max()),
+                                "worst_row": int(dev.argmax())}
+            entry["spread"], entry["bound"] = spread, 0.1 * spread
+            entry["row_bounds"] = [float(v) for v in row_bounds(name)]       # (what the tests hold each row to)
+            out[name] = entry
+    return out
+
+
+def _grad_stats(paths, bench, n_words=65536 * 128, esize=4):
+    """In-situ bandwidth of the backward's row_scale_many launches, (1 + n_out) words per element, from one
+    kernel_stats.csv per traced repeat: the per-run average share of the peak, so that their spread can be read."""
+    import re
+    out = {}
+    for run, path in enumerate(paths):
+        for r in csv.DictReader(open(path)):
+            m = re.search(r"row_scale_many_kernel<float, (\d+), true>", r["Name"])
+            if m:
+                n_out = int(m.group(1))
+                nbytes = (1 + n_out) * n_words * esize
+                e = out.setdefault(f"row_scale_many<{n_out}>", {"words_per_element": 1 + n_out, "bytes": nbytes,
+                                                                "calls_per_run": int(r["Calls"]), "avg_us": [],
+                                                                "avg_share_of_peak": [], "min_share_of_peak": []})
+                e["avg_us"].append(float(r["AverageNs"]) / 1e3)
+                e["avg_share_of_peak"].append(nbytes / float(r["AverageNs"]) / 1e3 / PEAK_TBS)
+                e["min_share_of_peak"].append(nbytes / float(r["MinNs"]) / 1e3 / PEAK_TBS)
+            elif "row_dot_" in r["Name"]:
+                e = out.setdefault(r["Name"].split("(")[0].replace("void tdeq::", ""),
+                                   {"calls_per_run": int(r["Calls"]), "avg_us": []})
+                e["avg_us"].append(float(r["AverageNs"]) / 1e3)
+    bench["in_situ"] = out
+    return bench
 
 
 def _launch_bytes(B=65536, L=128, esize=4):
@@ -142,7 +234,28 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--stats", default=None)
     ap.add_argument("--bench", default=None)
+    ap.add_argument("--grad", action="store_true")
+    ap.add_argument("--parity", default=None)
     a = ap.parse_args()
+    if a.grad and a.stats:
+        bench = _grad_stats(a.stats.split(","), json.load(open(a.bench)))
+        json.dump(bench, open(a.bench, "w"), indent=1)
+        print(json.dumps(bench["in_situ"], indent=1))
+        return
+    if a.grad:
+        res = {"device": torch.cuda.get_device_name(0), "arch": torch.cuda.get_device_properties(0).gcnArchName,
+               "headline_grad": _grad_headline(a.reps)}
+        print(json.dumps(res))
+        if a.out:
+            os.makedirs(os.path.dirname(a.out) or ".", exist_ok=True)
+            json.dump(res, open(a.out, "w"), indent=1)
+        if a.parity:
+            par = _grad_parity()
+            os.makedirs(os.path.dirname(a.parity) or ".", exist_ok=True)
+            json.dump(par, open(a.parity, "w"), indent=1)
+            print(json.dumps({k: {"host": v["host"]["worst"], "hip": v["hip"]["worst"], "bound": v["bound"]}
+                              for k, v in par.items()}))
+        return
     if a.stats:
         bench = json.load(open(a.bench))
         bench = _stats(a.stats, bench)

@@ -18,7 +18,7 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-TDEQ_ABI_VERSION = 22
+TDEQ_ABI_VERSION = 23
 TDEQ_F32, TDEQ_F64 = 0, 1
 TDEQ_C64, TDEQ_C128 = 2, 3        # interleaved complex: the norm entry points only (include/tdeq_hip.h)
 TDEQ_BF16, TDEQ_F16 = 4, 5        # reduced-precision states: the entry points of the host-driven step (LowPrecisionHipKernels)
@@ -212,6 +212,13 @@ ABI_SIGNATURES = {
     "tdeq_row_dense_commit": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                              ctypes.c_void_p, _c_void_pp, _c_double_p, ctypes.c_int, ctypes.c_void_p,
                                              ctypes.POINTER(RowState), ctypes.c_int, ctypes.c_void_p]),
+    # backward of the row-linear operations (ABI 23, rowwise_autodiff.py)
+    "tdeq_row_scale_many": (ctypes.c_int, [_c_void_pp, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
+                                           ctypes.c_int64, ctypes.c_int, ctypes.c_void_p]),
+    "tdeq_row_dots_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_int]),
+    "tdeq_row_multi_dot": (ctypes.c_int, [ctypes.c_void_p, _c_void_pp, ctypes.c_int, ctypes.c_int64, ctypes.c_int64,
+                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int,
+                                          ctypes.c_void_p]),
 }
 
 
@@ -844,6 +851,27 @@ class HipKernels:
         _check(self.lib.tdeq_row_dense_commit(sol.data_ptr(), y0.data_ptr(), y1.data_ptr(), f0.data_ptr(), f1.data_ptr(),
                                               ptrs, cf, n, dts.data_ptr(), ctypes.byref(st), dtype_code(y0.dtype),
                                               self._stream()), "tdeq_row_dense_commit")
+
+    def row_scale_many(self, outs, g, w) -> None:
+        """tdeq_row_scale_many: outs[m][r, :] = w[m, r] * g[r, :]; `w` a contiguous [len(outs), B] tensor of g's dtype."""
+        n = len(outs)
+        if w.shape != (n, g.shape[0]) or w.dtype != g.dtype or not w.is_contiguous():
+            raise ValueError("row_scale_many: w must be a contiguous [n_out, B] tensor of g's dtype")
+        ptrs = (ctypes.c_void_p * n)(*[o.data_ptr() for o in outs])
+        _check(self.lib.tdeq_row_scale_many(ptrs, n, g.data_ptr(), w.data_ptr(), g.shape[0], g.shape[1],
+                                            dtype_code(g.dtype), self._stream()), "tdeq_row_scale_many")
+
+    def row_multi_dot(self, g, xs) -> torch.Tensor:
+        """tdeq_row_multi_dot: fp64 device tensor [len(xs), B] of the row dots <g[r], x_m[r]>."""
+        n, (B, L) = len(xs), g.shape
+        ptrs = (ctypes.c_void_p * n)(*[x.data_ptr() for x in xs])
+        out = torch.empty(n, B, dtype=torch.float64, device=g.device)
+        nbytes = self.lib.tdeq_row_dots_workspace_bytes(B, L, n, dtype_code(g.dtype))
+        ws = torch.empty(nbytes // 8, dtype=torch.float64, device=g.device) if nbytes else None
+        _check(self.lib.tdeq_row_multi_dot(g.data_ptr(), ptrs, n, B, L, out.data_ptr(),
+                                           None if ws is None else ws.data_ptr(), nbytes, dtype_code(g.dtype),
+                                           self._stream()), "tdeq_row_multi_dot")
+        return out
 
 
 class ComplexHipKernels:

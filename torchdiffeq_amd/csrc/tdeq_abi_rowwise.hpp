@@ -326,3 +326,130 @@ int tdeq_row_dense_commit(void* sol, void* y0, const void* y1, void* f0, const v
     return dtype == TDEQ_F32 ? row_dense_dispatch<float>(sol, y0, y1, f0, f1, k, coef, n_terms, dts, st, s)
                              : row_dense_dispatch<double>(sol, y0, y1, f0, f1, k, coef, n_terms, dts, st, s);
 }
+
+// ---- backward of the row-linear operations: tdeq_row_scale_many / tdeq_row_multi_dot ---------------------------------
+namespace {
+
+template <typename T, int NT>
+int row_scale_n(void* const* outs, const void* g, const void* w, int64_t n_rows, int64_t row_len, hipStream_t s) {
+    RowScaleArgs<T, NT> a;
+    a.g = static_cast<const T*>(g);
+    a.w = static_cast<const T*>(w);
+    a.n_rows = n_rows;
+    a.n = n_rows * row_len;
+    const int lv = row_lanes(row_len, std::is_same<T, float>::value ? TDEQ_F32 : TDEQ_F64);
+    bool vec = lv > 1 && aligned16(g);
+    for (int j = 0; j < NT; ++j) {
+        a.out[j] = static_cast<T*>(outs[j]);
+        vec = vec && aligned16(outs[j]);
+    }
+    if (vec) {
+        a.row_len = row_len / lv;
+        hipLaunchKernelGGL((row_scale_many_kernel<T, NT, true>), dim3(stream_grid(a.n / lv, kBlock)), dim3(kBlock), 0, s, a);
+    } else {
+        a.row_len = row_len;
+        hipLaunchKernelGGL((row_scale_many_kernel<T, NT, false>), dim3(stream_grid(a.n, kBlock)), dim3(kBlock), 0, s, a);
+    }
+    return check_launch();
+}
+
+template <typename T>
+int row_scale_dispatch(void* const* outs, int nt, const void* g, const void* w, int64_t n_rows, int64_t row_len,
+                       hipStream_t s) {
+    switch (nt) {
+#define TDEQ_CASE(N) case N: return row_scale_n<T, N>(outs, g, w, n_rows, row_len, s);
+        TDEQ_CASE(1) TDEQ_CASE(2) TDEQ_CASE(3) TDEQ_CASE(4) TDEQ_CASE(5) TDEQ_CASE(6) TDEQ_CASE(7)
+        TDEQ_CASE(8) TDEQ_CASE(9) TDEQ_CASE(10) TDEQ_CASE(11) TDEQ_CASE(12) TDEQ_CASE(13) TDEQ_CASE(14)
+#undef TDEQ_CASE
+    }
+    return TDEQ_EINVAL;
+}
+
+template <typename T, int NT>
+int row_dot_n(const void* g, const void* const* x, int64_t n_rows, int64_t row_len, double* out, double* ws,
+              hipStream_t s) {
+    const RowGeom geo = row_geom(row_len, std::is_same<T, float>::value ? TDEQ_F32 : TDEQ_F64);
+    RowDotArgs<T, NT> a;
+    a.g = static_cast<const T*>(g);
+    bool vec = geo.lv > 1 && aligned16(g);
+    for (int j = 0; j < NT; ++j) {
+        a.x[j] = static_cast<const T*>(x[j]);
+        vec = vec && aligned16(x[j]);
+    }
+    if (geo.lv > 1 && !vec) return TDEQ_EINVAL;      // (the geometry, hence the sums, must not depend on alignment)
+    a.row_len = geo.nv;
+    a.n_rows = n_rows;
+    a.chunk = geo.chunk;
+    a.nch = (int)geo.nch;
+    a.group = geo.group;
+    if (geo.nch == 1) {
+        a.out = out;
+        const int64_t threads = n_rows * geo.group;
+        const dim3 grid((unsigned)((threads + kBlock - 1) / kBlock));
+        if (vec) hipLaunchKernelGGL((row_dot_wave_kernel<T, NT, true>), grid, dim3(kBlock), 0, s, a);
+        else hipLaunchKernelGGL((row_dot_wave_kernel<T, NT, false>), grid, dim3(kBlock), 0, s, a);
+        return check_launch();
+    }
+    a.out = ws;
+    const dim3 grid((unsigned)(n_rows * geo.nch));
+    if (vec) hipLaunchKernelGGL((row_dot_chunk_kernel<T, NT, true>), grid, dim3(kBlock), 0, s, a);
+    else hipLaunchKernelGGL((row_dot_chunk_kernel<T, NT, false>), grid, dim3(kBlock), 0, s, a);
+    const int e = check_launch();
+    if (e) return e;
+    RowDotFinalizeArgs f;
+    f.part = ws;
+    f.nch = (int)geo.nch;
+    f.n_x = NT;
+    f.n_rows = n_rows;
+    f.out = out;
+    hipLaunchKernelGGL(row_dot_finalize_kernel, dim3((unsigned)((n_rows * kWave + kBlock - 1) / kBlock)), dim3(kBlock), 0,
+                       s, f);
+    return check_launch();
+}
+
+template <typename T>
+int row_dot_dispatch(const void* g, const void* const* x, int nt, int64_t n_rows, int64_t row_len, double* out,
+                     double* ws, hipStream_t s) {
+    switch (nt) {
+#define TDEQ_CASE(N) case N: return row_dot_n<T, N>(g, x, n_rows, row_len, out, ws, s);
+        TDEQ_CASE(1) TDEQ_CASE(2) TDEQ_CASE(3) TDEQ_CASE(4) TDEQ_CASE(5) TDEQ_CASE(6) TDEQ_CASE(7)
+        TDEQ_CASE(8) TDEQ_CASE(9) TDEQ_CASE(10) TDEQ_CASE(11) TDEQ_CASE(12) TDEQ_CASE(13) TDEQ_CASE(14)
+#undef TDEQ_CASE
+    }
+    return TDEQ_EINVAL;
+}
+
+}  // namespace
+
+int tdeq_row_scale_many(void* const* outs, int n_out, const void* g, const void* w, int64_t n_rows, int64_t row_len,
+                        int dtype, void* stream) {
+    if (!outs || !g || !w || n_rows < 0 || row_len < 0 || !row_dtype_ok(dtype)) return TDEQ_EINVAL;
+    if (n_out < 1 || n_out > TDEQ_MAX_TERMS) return TDEQ_EINVAL;
+    for (int j = 0; j < n_out; ++j) if (!outs[j]) return TDEQ_EINVAL;
+    if (n_rows == 0 || row_len == 0) return 0;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return dtype == TDEQ_F32 ? row_scale_dispatch<float>(outs, n_out, g, w, n_rows, row_len, s)
+                             : row_scale_dispatch<double>(outs, n_out, g, w, n_rows, row_len, s);
+}
+
+size_t tdeq_row_dots_workspace_bytes(int64_t n_rows, int64_t row_len, int n_x, int dtype) {
+    if (n_rows < 1 || row_len < 1 || n_x < 1 || !row_dtype_ok(dtype)) return 0;
+    const int64_t nch = row_geom(row_len, dtype).nch;
+    return nch == 1 ? 0 : (size_t)n_x * (size_t)n_rows * (size_t)nch * sizeof(double);
+}
+
+int tdeq_row_multi_dot(const void* g, const void* const* x, int n_x, int64_t n_rows, int64_t row_len, double* out,
+                       void* workspace, size_t workspace_bytes, int dtype, void* stream) {
+    if (!g || !x || !out || n_rows < 0 || row_len < 0 || !row_dtype_ok(dtype)) return TDEQ_EINVAL;
+    if (n_x < 1 || n_x > TDEQ_MAX_TERMS) return TDEQ_EINVAL;
+    for (int j = 0; j < n_x; ++j) if (!x[j]) return TDEQ_EINVAL;
+    if (n_rows == 0) return 0;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (row_len == 0) return (int)hipMemsetAsync(out, 0, (size_t)n_x * (size_t)n_rows * sizeof(double), s);
+    const size_t need = tdeq_row_dots_workspace_bytes(n_rows, row_len, n_x, dtype);
+    if (need > 0 && (!workspace || workspace_bytes < need)) return TDEQ_EWORKSPACE;
+    if (n_rows * row_geom(row_len, dtype).nch > 0x7fffffffLL) return TDEQ_EINVAL;
+    double* ws = static_cast<double*>(workspace);
+    return dtype == TDEQ_F32 ? row_dot_dispatch<float>(g, x, n_x, n_rows, row_len, out, ws, s)
+                             : row_dot_dispatch<double>(g, x, n_x, n_rows, row_len, out, ws, s);
+}

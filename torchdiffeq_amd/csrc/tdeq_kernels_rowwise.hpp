@@ -490,4 +490,142 @@ __global__ __launch_bounds__(kBlock) void row_dense_commit_kernel(const RowDense
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// Backward of the row-linear operations (differentiable odeint_rowwise, rowwise_autodiff.py).  Every state-sized
+// operation of a rowwise trial step is out[r, :] = sum_m w_m[r] X_m[r, :], so its VJP is
+//   grad X_m[r, :] = w_m[r] * g[r, :]                       row_scale_many_kernel: g read once, NT tensors written
+//   grad s_r = sum_m dw_m/ds[r] * <g[r, :], X_m[r, :]>      row_dot_*_kernel: fp64 dots per row, g read once
+// for a per-row scalar s (the first step size).
+// ------------------------------------------------------------------------------------------------
+template <typename T, int NT>
+struct RowScaleArgs {
+    T* out[NT];
+    const T* g;
+    const T* w;                       // [NT, B]
+    int64_t n_rows;
+    int64_t row_len;                  // in E units
+    int64_t n;                        // B * L elements of T
+};
+
+// Pure streaming: 1 word read + NT written per element.  A lane keeps its row's NT weights in registers and fetches
+// them again only when its grid-stride walk enters another row.
+template <typename T, int NT, bool VEC>
+__global__ __launch_bounds__(kBlock) void row_scale_many_kernel(const RowScaleArgs<T, NT> a) {
+    using E = typename std::conditional<VEC, typename VecOf<T>::type, T>::type;
+    constexpr int LV = VEC ? VecOf<T>::L : 1;
+    const int64_t ne = a.n / LV;
+    const int64_t stride = (int64_t)gridDim.x * kBlock;
+    int64_t r_held = -1;
+    T w[NT];
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < ne; i += stride) {
+        const E g = reinterpret_cast<const E*>(a.g)[i];
+        const int64_t r = i / a.row_len;
+        if (r != r_held) {
+#pragma unroll
+            for (int j = 0; j < NT; ++j) w[j] = a.w[(int64_t)j * a.n_rows + r];
+            r_held = r;
+        }
+#pragma unroll
+        for (int j = 0; j < NT; ++j) reinterpret_cast<E*>(a.out[j])[i] = g * w[j];
+    }
+}
+
+template <typename T, int NT>
+struct RowDotArgs {
+    const T* g;
+    const T* x[NT];
+    int64_t row_len;                  // in E units
+    int64_t n_rows;
+    int64_t chunk;                    // long rows: E units per workgroup
+    int nch;                          // chunks per row (1 for short rows)
+    int group;                        // short rows: lanes per row (power of two <= 64)
+    double* out;                      // short rows: [NT, B] results; long rows: [NT, B * nch] partials
+};
+
+template <typename T, int NT, typename E>
+__device__ __forceinline__ void row_dot_elem(const RowDotArgs<T, NT>& a, int64_t i, double (&acc)[NT]) {
+    constexpr int LV = sizeof(E) / sizeof(T);
+    const E gv = reinterpret_cast<const E*>(a.g)[i];
+    E xv[NT];
+#pragma unroll
+    for (int j = 0; j < NT; ++j) xv[j] = reinterpret_cast<const E*>(a.x[j])[i];
+#pragma unroll
+    for (int j = 0; j < NT; ++j) {
+        if constexpr (LV == 1) {
+            acc[j] += (double)gv * (double)xv[j];
+        } else {
+#pragma unroll
+            for (int q = 0; q < LV; ++q) acc[j] += (double)gv[q] * (double)xv[j][q];
+        }
+    }
+}
+
+// short rows: the geometry of row_reduce_wave_kernel
+template <typename T, int NT, bool VEC>
+__global__ __launch_bounds__(kBlock) void row_dot_wave_kernel(const RowDotArgs<T, NT> a) {
+    using E = typename std::conditional<VEC, typename VecOf<T>::type, T>::type;
+    const int g = a.group;
+    const int lane = threadIdx.x & (g - 1);
+    const int64_t r = ((int64_t)blockIdx.x * kBlock + threadIdx.x) / g;
+    double acc[NT];
+#pragma unroll
+    for (int j = 0; j < NT; ++j) acc[j] = 0.0;
+    if (r < a.n_rows) {
+        const int64_t base = r * a.row_len;
+        for (int64_t e = lane; e < a.row_len; e += g) row_dot_elem<T, NT, E>(a, base + e, acc);
+    }
+    for (int off = g >> 1; off > 0; off >>= 1) {
+#pragma unroll
+        for (int j = 0; j < NT; ++j) acc[j] += __shfl_xor(acc[j], off, kWave);
+    }
+    if (lane == 0 && r < a.n_rows) {
+#pragma unroll
+        for (int j = 0; j < NT; ++j) a.out[(int64_t)j * a.n_rows + r] = acc[j];
+    }
+}
+
+// long rows: one workgroup per (row, chunk), the geometry of row_reduce_chunk_kernel
+template <typename T, int NT, bool VEC>
+__global__ __launch_bounds__(kBlock) void row_dot_chunk_kernel(const RowDotArgs<T, NT> a) {
+    using E = typename std::conditional<VEC, typename VecOf<T>::type, T>::type;
+    __shared__ double red[NT * (kBlock / kWave)];
+    const int64_t b = blockIdx.x;
+    const int64_t r = b / a.nch, c = b - r * a.nch;
+    double acc[NT];
+#pragma unroll
+    for (int j = 0; j < NT; ++j) acc[j] = 0.0;
+    const int64_t lo = c * a.chunk;
+    const int64_t hi = lo + a.chunk < a.row_len ? lo + a.chunk : a.row_len;
+    const int64_t base = r * a.row_len;
+    for (int64_t e = lo + threadIdx.x; e < hi; e += kBlock) row_dot_elem<T, NT, E>(a, base + e, acc);
+    block_sum<NT>(acc, red);
+    if (threadIdx.x == 0) {
+        const int64_t nb = a.n_rows * a.nch;
+#pragma unroll
+        for (int j = 0; j < NT; ++j) a.out[(int64_t)j * nb + b] = acc[j];
+    }
+}
+
+// out[j, r] = the row's nch partials added by one wave in a fixed order (as row_ctrl_kernel adds a long row's norms)
+struct RowDotFinalizeArgs {
+    const double* part;               // [n_x, B * nch]
+    int nch;
+    int n_x;
+    int64_t n_rows;
+    double* out;                      // [n_x, B]
+};
+
+__global__ __launch_bounds__(kBlock) void row_dot_finalize_kernel(const RowDotFinalizeArgs a) {
+    const int lane = threadIdx.x & (kWave - 1);
+    const int64_t r = ((int64_t)blockIdx.x * kBlock + threadIdx.x) / kWave;
+    const int64_t np = a.n_rows * a.nch;
+    for (int j = 0; j < a.n_x; ++j) {
+        double s = 0.0;
+        if (r < a.n_rows)
+            for (int64_t q = lane; q < a.nch; q += kWave) s += a.part[(int64_t)j * np + r * a.nch + q];
+        s = wave_sum(s);
+        if (lane == 0 && r < a.n_rows) a.out[(int64_t)j * a.n_rows + r] = s;
+    }
+}
+
 }  // namespace tdeq

@@ -12,6 +12,7 @@ torch ops (`HostRowKernels`, one `HostPathWarning`).
 """
 from __future__ import annotations
 
+import contextlib
 import math
 from typing import List
 
@@ -19,6 +20,7 @@ import numpy as np
 import torch
 
 from . import _fallback, _native
+from . import rowwise_autodiff as rad
 from ._native import device_guard
 from ._scalars import nextafter, power, rdiv, scalar_type
 from .solvers._common import optimal_step_size
@@ -64,7 +66,7 @@ def _func_parameters_require_grad(func) -> bool:
 class _Problem:
     """Validated inputs: y [B, L] (contiguous copy), tgrid [T, B] fp64 in solver time (ascending), sign."""
 
-    def __init__(self, func, y0, t, rtol, atol, method, options, event_fn):
+    def __init__(self, func, y0, t, rtol, atol, method, options, event_fn, differentiable=False):
         if event_fn is not None:
             raise ValueError("odeint_rowwise: event_fn is not supported (use odeint)")
         if not isinstance(y0, torch.Tensor):
@@ -102,9 +104,16 @@ class _Problem:
             raise ValueError(f"odeint_rowwise: t must be [T] or [T, B], got {t.dim()} dimensions")
         if t.shape[0] < 1:
             raise ValueError("odeint_rowwise: t needs at least one time")
-        if torch.is_grad_enabled() and (y0.requires_grad or t.requires_grad or _func_parameters_require_grad(func)):
-            raise NotImplementedError("odeint_rowwise does not propagate gradients; use odeint (backprop through the "
-                                      "solver) or odeint_adjoint, or call it under torch.no_grad()")
+        # record: the solve builds an autograd graph (rowwise_autodiff.py); under no_grad `differentiable` has no effect
+        self.record = bool(differentiable) and torch.is_grad_enabled()
+        if self.record and t.requires_grad:
+            raise NotImplementedError("odeint_rowwise(differentiable=True): time gradients (t.requires_grad) are not "
+                                      "supported; detach t, or use odeint")
+        if not self.record and torch.is_grad_enabled() and (y0.requires_grad or t.requires_grad or
+                                                            _func_parameters_require_grad(func)):
+            raise NotImplementedError("odeint_rowwise does not propagate gradients unless differentiable=True is "
+                                      "passed; use that, odeint (backprop through the solver) or odeint_adjoint, or "
+                                      "call it under torch.no_grad()")
 
         self.func, self.shape, self.B = func, y0.shape, B
         self.L = int(math.prod(y0.shape[1:]))
@@ -125,6 +134,7 @@ class _Problem:
         self.tgrid = (tg * sign).contiguous()
         self.sign = sign
         self.y0 = y0.detach().reshape(B, self.L).contiguous()
+        self.y0_graph = y0.reshape(B, self.L) if self.record else None
         self.rtol, self.atol = float(rtol), float(atol)
         self.method = _Method(method, self.np_dtype)
         fs = options.get("first_step")
@@ -144,13 +154,18 @@ class _Problem:
 
     def call(self, t_rows: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
         """func(t_rows [B], y [B, *row_shape]) -> [B, L] contiguous in the state's dtype."""
+        with torch.enable_grad() if self.record else contextlib.nullcontext():
+            return self._call(t_rows, y)
+
+    def _call(self, t_rows: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
         self.nfe += 1
         f = self.func(t_rows, y.view(self.shape))
         if not isinstance(f, torch.Tensor):
             raise TypeError("odeint_rowwise: func must return a Tensor, got {}".format(type(f).__name__))
-        if f.requires_grad and torch.is_grad_enabled():
-            raise NotImplementedError("odeint_rowwise does not propagate gradients (func's output requires grad); use "
-                                      "odeint / odeint_adjoint, or call it under torch.no_grad()")
+        if f.requires_grad and torch.is_grad_enabled() and not self.record:
+            raise NotImplementedError("odeint_rowwise does not propagate gradients (func's output requires grad) unless "
+                                      "differentiable=True is passed; use that, odeint / odeint_adjoint, or call it "
+                                      "under torch.no_grad()")
         if f.shape != self.shape:
             raise RuntimeError("odeint_rowwise: func returned shape {} for a state of shape {}".format(
                 tuple(f.shape), tuple(self.shape)))
@@ -209,6 +224,10 @@ class HostRowKernels:
         self.n_rej = np.zeros(B, dtype=np.int64)
         self.code = np.zeros(B, dtype=np.int64)
         self.tg = p.tgrid.numpy()
+        # record mode: [B] fp64 graphs of the first step sizes (initial-step heuristic) and, from the second trial step
+        # on, of the time every later step of the row is anchored to (t0 + dt_first for a row whose first step was accepted)
+        self.s_shadow = None
+        self.anchor = None
 
     # -- helpers ------------------------------------------------------------------------------------------------------
     def _coef(self, coef: float, dts: torch.Tensor) -> torch.Tensor:
@@ -225,7 +244,7 @@ class HostRowKernels:
         return torch.tensor(np.asarray(vals, dtype=self.T).astype(np.float64), dtype=self.p.dtype).reshape(-1, 1)
 
     def _row_norms(self, q: torch.Tensor) -> np.ndarray:
-        qd = q.to(torch.float64)
+        qd = q.detach().to(torch.float64)
         return _row_sum(qd * qd).numpy()
 
     def stage_time(self, r: int, i: int):
@@ -261,15 +280,19 @@ class HostRowKernels:
 
     # -- initial step ---------------------------------------------------------------------------------------------------
     def initial_step(self, y, f0) -> None:
+        with torch.enable_grad() if self.p.record else contextlib.nullcontext():
+            self._initial_step(y, f0)
+
+    def _initial_step(self, y, f0) -> None:
         p, T = self.p, self.T
         self.t0[:] = p.tgrid[0].numpy()
-        scale = p.atol + y.abs() * p.rtol
+        scale = p.atol + y.detach().abs() * p.rtol
         bad = (~torch.isfinite(y)).sum(dim=1).numpy()
         self.bad_y[:] = bad != 0
         if p.first_step is not None:
             self.dt[:] = p.first_step.numpy()
         else:
-            s0, s1 = self._row_norms(y / scale), self._row_norms(f0 / scale)
+            s0, s1 = self._row_norms(y.detach() / scale), self._row_norms(f0.detach() / scale)
             h0 = np.empty(p.B, dtype=object)
             d1s = []
             with np.errstate(all="ignore"):
@@ -279,10 +302,18 @@ class HostRowKernels:
                     h0[r] = abs(h)
                     d1s.append(d1)
             c = torch.tensor([float(T(float(h) * p.sign)) for h in h0], dtype=p.dtype).reshape(-1, 1)
+            shadow = None
+            if p.record:
+                shadow = rad.FirstStepShadow(_row_sum, y, f0, p.rtol, p.atol, p.sign)
+                c = rad.stitch_rows(c, shadow.h0, p.sign)
             y1 = y + f0 * c
             t1 = torch.tensor([float(p.sign * T(self.t0[r] + float(h0[r]))) for r in range(p.B)], dtype=p.dtype)
+            if shadow is not None:
+                t1 = rad.stitch_rows(t1, shadow.h0, p.sign)
             f1 = p.call(t1, y1)
-            s2 = self._row_norms((f1 - f0) / scale)
+            s2 = self._row_norms((f1.detach() - f0.detach()) / scale)
+            if shadow is not None:
+                self.s_shadow = shadow.finish(f1, p.method.order - 1)
             order = p.method.order - 1
             with np.errstate(all="ignore"):
                 for r in range(p.B):
@@ -298,11 +329,25 @@ class HostRowKernels:
             self.prepare(r)
 
     # -- trial step -----------------------------------------------------------------------------------------------------
-    def trial_step(self, y, f0, sol) -> None:
+    def trial_step(self, y, f0, sol):
+        """One trial step of every active row; returns the (y, f0) of the next one (the same tensors, committed in
+        place, unless the solve is recorded)."""
+        with torch.enable_grad() if self.p.record else contextlib.nullcontext():
+            return self._trial_step(y, f0, sol)
+
+    def _trial_step(self, y, f0, sol):
         p, m, T = self.p, self.p.method, self.T
         dts = self._dts_tensor([T(self.dt[r]) * T(p.sign) if self.active[r] else T(0) for r in range(p.B)])
+        shadow, self.s_shadow = self.s_shadow, None          # only the first trial step's size carries a graph
+        anchor = self.anchor
+        if shadow is not None:
+            dts = rad.stitch_rows(dts, shadow, p.sign)
         act = torch.from_numpy(self.active.copy()).reshape(-1, 1)
         times = self.times_tensor()
+        if shadow is not None:
+            times = [rad.stitch_rows(tt, shadow, p.sign * float(a)) for tt, a in zip(times, m.alpha)]
+        elif anchor is not None:
+            times = [rad.stitch_rows(tt, anchor, p.sign) for tt in times]
         ks = [f0]
         yi = None
         for i, row in enumerate(m.beta):
@@ -310,10 +355,11 @@ class HostRowKernels:
             ks.append(p.call(times[i], yi))
         y1 = yi if m.fsal else torch.where(act, y + self._sum_terms(ks, m.c_sol, dts), y)
         f1 = ks[-1]
-        err = self._sum_terms(ks, m.c_err, dts)
-        tol = p.atol + p.rtol * torch.maximum(y.abs(), y1.abs())
-        sums = self._row_norms(err / tol)
-        bad = ((~torch.isfinite(y)) | (~torch.isfinite(y1))).sum(dim=1).numpy()
+        with torch.no_grad():                                # the controller is outside the graph
+            err = self._sum_terms(ks, m.c_err, dts)
+            tol = p.atol + p.rtol * torch.maximum(y.abs(), y1.abs())
+            sums = self._row_norms(err / tol)
+            bad = ((~torch.isfinite(y)) | (~torch.isfinite(y1))).sum(dim=1).numpy()
         accepted = []
         n_out = self.tg.shape[0]
         with np.errstate(all="ignore"):
@@ -345,12 +391,17 @@ class HostRowKernels:
                     self.n_rej[r] += 1
                 self.dt[r] = dt_next
         if accepted:
-            self._dense_commit(accepted, y, y1, f0, f1, ks, dts, sol)
+            y, f0 = self._dense_commit(accepted, y, y1, f0, f1, ks, dts, sol, shadow, anchor)
+        if shadow is not None and shadow.requires_grad:
+            took = torch.zeros(p.B, dtype=torch.float64)
+            took[[r for r, _, _ in accepted]] = 1.0
+            self.anchor = shadow * took
         for r in range(p.B):
             if self.active[r]:
                 self.prepare(r)
+        return y, f0
 
-    def _dense_commit(self, accepted, y, y1, f0, f1, ks, dts, sol) -> None:
+    def _dense_commit(self, accepted, y, y1, f0, f1, ks, dts, sol, shadow=None, anchor=None):
         p, m, T = self.p, self.p.method, self.T
         rows = torch.tensor([r for r, _, _ in accepted])
         with_out = [(i, r, lo, hi) for i, (r, lo, hi) in enumerate(accepted) if hi > lo]
@@ -369,17 +420,32 @@ class HostRowKernels:
                 ta, tb = self.tprev[r], self.t0[r]
                 for j in range(lo, hi):
                     x = T((self.tg[j, r] - ta) / (tb - ta))
-                    xf = float(x)
-                    total = y0r[n] + qd[n] * xf
-                    xp = x * x
-                    total = total + qc[n] * float(xp)
-                    xp = xp * x
-                    total = total + qb[n] * float(xp)
-                    xp = xp * x
-                    total = total + qa[n] * float(xp)
+                    x2 = x * x
+                    x3 = x2 * x
+                    x4 = x3 * x
+                    if shadow is None and anchor is None:
+                        xs = (float(x), float(x2), float(x3), float(x4))
+                    else:
+                        # the step's ends carry the heuristic's graph, and with them theta = x (interp.py:39-40): the
+                        # first step ends at t0 + dt_r (d x / d dt_r = -x / dt_r), a later one is shifted as a whole
+                        # (d x / d anchor = -1 / width); the powers keep their T-rounded values
+                        val = lambda v: torch.tensor(float(v), dtype=p.dtype)   # noqa: E731
+                        moved = shadow[r] * float(x) if shadow is not None else anchor[r]
+                        xt = rad.stitch_rows(val(x), moved * (-1.0 / (tb - ta)))
+                        xs = (xt, rad.stitch_rows(val(x2), xt * xt), rad.stitch_rows(val(x3), xt * xt * xt),
+                              rad.stitch_rows(val(x4), xt * xt * xt * xt))
+                    total = y0r[n] + qd[n] * xs[0]
+                    total = total + qc[n] * xs[1]
+                    total = total + qb[n] * xs[2]
+                    total = total + qa[n] * xs[3]
                     sol[j, r] = total
+        if p.record:
+            mask = torch.zeros(p.B, 1, dtype=torch.bool)
+            mask[rows] = True
+            return torch.where(mask, y1, y), torch.where(mask, f1, f0)
         y[rows] = y1[rows]
         f0[rows] = f1[rows]
+        return y, f0
 
 
 class HipRowKernels:
@@ -438,6 +504,94 @@ class HipRowKernels:
         self.carry = carry_plan(m.name)
         self.dts = None
         self.times = None
+        # record mode (differentiable=True): every launch below becomes one rowwise_autodiff._RowLinearOp node
+        self.rec = p.record
+        self.s_shadow = None          # [B] fp64 graph of the first step sizes (initial-step heuristic)
+        self.anchor = None            # [B] fp64 graph of the time the later steps of a row are anchored to
+        self.sol_rows = None          # graph tensors of the solution rows (each the raw row's storage)
+        self._coef_t = {}
+
+    # -- record mode ----------------------------------------------------------------------------------------------------
+    def _coefs(self, row: SparseRow) -> torch.Tensor:
+        c = self._coef_t.get(id(row))
+        if c is None:
+            c = self._coef_t[id(row)] = torch.tensor(row.coef, dtype=self.p.dtype, device=self.p.device)[:, None]
+        return c
+
+    def _node(self, raw, y, ks, row: SparseRow, dts, shadow):
+        """`raw` = y + sum_j fl_T(fl_T(a_j) dts[r]) k_j over the whole tableau row, as one graph node (the carried
+        partial sums of the launch are an implementation detail of the forward)."""
+        if not self.rec:
+            return raw
+        w = (self._coefs(row) * dts[None, :]).unbind(0)          # T products: the kernel's own coefficients
+        xs = [y] + [ks[j] for j in row.idx]
+        if shadow is None:
+            return rad.row_linear(self.k, raw, xs, [1.0, *w])
+        dw = [0.0] + [float(c) * self.p.sign for c in self._coefs(row)[:, 0].tolist()]
+        return rad.row_linear(self.k, raw, xs, [1.0, *w], s=shadow, dw=dw)
+
+    def _record_commit(self, sol, y, y1, f0, ks, step_dts, t_start, shadow, anchor):
+        """Graph of the dense output + commit launch that just ran on the fresh (y_new, f0_new)."""
+        p, m = self.p, self.p.method
+        y_new, f0_new = self._fresh
+        acc, lo, hi = self.accepted != 0, self.out_lo, self.out_hi
+        hit = acc & (hi > lo)
+        n_acc, j_lo, j_hi = torch.stack([acc.sum(), torch.where(hit, lo, _NO_ERROR_ROW).min().long(),
+                                         torch.where(hit, hi, 0).max().long()]).tolist()
+        S = m.n_stages
+        if j_hi > j_lo:
+            d = step_dts.double()
+            width = torch.where(hit, self.t0 - t_start, torch.ones_like(self.t0))
+            cmid = self._coefs(m.c_mid)[:, 0].double().tolist()
+            for j in range(j_lo, j_hi):
+                mask = hit & (lo <= j) & (hi > j)
+                # theta as the kernel forms it: in the time type, then rounded to T (interp.py:39-40)
+                x = torch.where(mask, ((self.tg[j] - t_start) / width).to(p.dtype).double(), torch.zeros_like(width))
+                w, dwx, dwd = rad.dense_weights(x, d, cmid)
+                md = mask.double()
+                slots = {0: 2, S: 3}                           # f0 = k_0 and f1 = k_S usually carry a mid weight too
+                merged = [list(v[:4]) for v in (w, dwx, dwd)]
+                order = [0, S]
+                for q, jj in enumerate(m.c_mid.idx):
+                    if jj in slots:
+                        for lst, src in zip(merged, (w, dwx, dwd)):
+                            lst[slots[jj]] = lst[slots[jj]] + src[4 + q]
+                    else:
+                        slots[jj] = len(merged[0])
+                        order.append(jj)
+                        for lst, src in zip(merged, (w, dwx, dwd)):
+                            lst.append(src[4 + q])
+                xs = [y, y1] + [ks[jj] for jj in order]
+                ws = [(v * md).to(p.dtype) for v in merged[0]]
+                prev = self.sol_rows[j]
+                if prev is not None:
+                    # `prev` and the new node's value are both the storage of sol[j], which later launches rewrite
+                    # behind autograd's back: safe only because the chained input has weight 1 and dw = 0, so its
+                    # VALUE is never read in a backward (g passes through, no dot is taken with it)
+                    xs, ws = [prev] + xs, [1.0] + ws
+                if shadow is None and anchor is None:
+                    self.sol_rows[j] = rad.row_linear(self.k, sol[j], xs, ws)
+                    continue
+                if shadow is not None:
+                    # the first step: weights depend on dt_r directly (d = sign dt_r) and through theta (-x / dt_r)
+                    dw = [(dd * p.sign - dx * x / width) * md for dx, dd in zip(merged[1], merged[2])]
+                else:
+                    # a later step is shifted as a whole with the row's anchor: d theta / d anchor = -1 / width
+                    dw = [-dx / width * md for dx in merged[1]]
+                if prev is not None:
+                    dw = [0.0] + dw
+                self.sol_rows[j] = rad.row_linear(self.k, sol[j], xs, ws, s=shadow if shadow is not None else anchor,
+                                                  dw=dw)
+        if shadow is not None:
+            self.anchor = shadow * acc.double()
+        if n_acc == 0:
+            return y, f0
+        if n_acc == p.B:
+            wm = [1.0, 0.0]
+        else:
+            mt = acc.to(p.dtype)
+            wm = [mt, 1 - mt]
+        return rad.row_linear(self.k, y_new, [y1, y], wm), rad.row_linear(self.k, f0_new, [ks[-1], f0], wm)
 
     def _control(self, mode: int) -> None:
         p = self.p
@@ -459,13 +613,32 @@ class HipRowKernels:
         self._control(1)
         y1 = torch.empty_like(y)
         k.row_combine([y1], (((1.0,), 1, True),), y, None, [f0], self.dts, self.active)
-        f1 = p.call(self.times[0], y1)
+        shadow = None
+        if self.rec:
+            with torch.enable_grad():
+                shadow = rad.FirstStepShadow(_row_sum, y, f0, p.rtol, p.atol, p.sign)
+            y1 = rad.row_linear(k, y1, [y, f0], [1.0, self.dts], s=shadow.h0, dw=[0.0, p.sign])
+        f1 = p.call(self.times[0] if shadow is None else rad.stitch_rows(self.times[0], shadow.h0, p.sign), y1)
         k.row_reduce(2, self.part, y, f1, f0, [], [], None, None, p.rtol, p.atol)
         self._control(2)
+        if shadow is not None:
+            with torch.enable_grad():
+                self.s_shadow = shadow.finish(f1, p.method.order - 1)
 
-    def trial_step(self, y, f0, sol) -> None:
+    def trial_step(self, y, f0, sol):
+        """One trial step of every active row; returns the (y, f0) of the next one (the same tensors, committed in
+        place, unless the solve is recorded: then fresh graph tensors)."""
         p, m, k = self.p, self.p.method, self.k
         dts, times, act = self.dts, self.times.unbind(0), self.active
+        shadow, self.s_shadow = self.s_shadow, None          # only the first trial step's size carries a graph
+        if shadow is not None and not shadow.requires_grad:
+            shadow = None
+        anchor = self.anchor
+        if shadow is not None:
+            times = [rad.stitch_rows(tt, shadow, p.sign * float(a)) for tt, a in zip(times, m.alpha)]
+        elif anchor is not None:
+            times = [rad.stitch_rows(tt, anchor, p.sign) for tt in times]
+        node = lambda raw, row: self._node(raw, y, ks, row, dts, shadow)      # noqa: E731
         ks = [f0]
         S = m.n_stages
         err_partial, err_rem = None, None
@@ -476,6 +649,7 @@ class HipRowKernels:
             yi = torch.empty_like(y)
             k.row_combine([yi], ((m.beta[0].coef, (1 << len(m.beta[0].idx)) - 1, True),), y, None,
                           [ks[j] for j in m.beta[0].idx], dts, act)
+            yi = node(yi, m.beta[0])
             ks.append(p.call(times[0], yi))
             for i in range(1, R):
                 op = carry.ops[i]
@@ -488,6 +662,7 @@ class HipRowKernels:
                     yi = outs[0]
                     for tgt, buf in zip(op.targets[1:], outs[1:]):
                         held[tgt] = buf
+                yi = node(yi, m.beta[i] if i < S else m.c_sol)
                 if i < S:
                     ks.append(p.call(times[i], yi))
                 else:
@@ -510,6 +685,7 @@ class HipRowKernels:
                     spec = spec + ((m.c_err.coef[:n_lead], (1 << n_lead) - 1, False),)
                     outs.append(err_partial)
                 k.row_combine(outs, spec, y, None, [ks[j] for j in row.idx], dts, act)
+                yi = node(yi, row)
                 ks.append(p.call(times[i], yi))
             if m.fsal:
                 y1 = yi
@@ -522,6 +698,7 @@ class HipRowKernels:
                     spec = spec + ((m.c_err.coef[:n_lead], (1 << n_lead) - 1, False),)
                     outs.append(err_partial)
                 k.row_combine(outs, spec, y, None, [ks[j] for j in m.c_sol.idx], dts, act)
+                y1 = node(y1, m.c_sol)
             if err_partial is not None:
                 err_rem = (m.c_err.idx[n_lead:], m.c_err.coef[n_lead:])
         if err_partial is None:
@@ -531,8 +708,20 @@ class HipRowKernels:
             k.row_reduce(0, self.part, y, y1, err_partial, [ks[j] for j in err_rem[0]], err_rem[1], dts, act,
                          p.rtol, p.atol)
         step_dts = dts
+        if not self.rec:
+            self._control(0)
+            k.row_dense_commit(sol, y, y1, f0, ks[-1], [ks[j] for j in m.c_mid.idx], m.c_mid.coef, step_dts, self.st)
+            return y, f0
+        # recorded: the same launch commits into fresh tensors, the inputs stay alive for the backward
+        t_start = self.t0.clone()
         self._control(0)
-        k.row_dense_commit(sol, y, y1, f0, ks[-1], [ks[j] for j in m.c_mid.idx], m.c_mid.coef, step_dts, self.st)
+        self._fresh = (y.detach().clone(), f0.detach().clone())
+        k.row_dense_commit(sol, self._fresh[0], y1, self._fresh[1], ks[-1], [ks[j] for j in m.c_mid.idx], m.c_mid.coef,
+                           step_dts, self.st)
+        with torch.enable_grad():
+            out = self._record_commit(sol, y, y1, f0, ks, step_dts, t_start, shadow, anchor)
+        self._fresh = None
+        return out
 
     def finish(self):
         return self.n_acc.cpu(), self.n_rej.cpu()
@@ -542,7 +731,7 @@ class HipRowKernels:
 
 
 def odeint_rowwise(func, y0, t, *, rtol=1e-7, atol=1e-9, method="dopri5", options=None, return_stats=False,
-                   event_fn=None):
+                   event_fn=None, differentiable=False):
     """Integrate B independent IVPs `dy_r/dt = func(t, y)[r]`, each row with its own adaptive step controller.
 
     `y0` is one tensor `[B, *row_shape]` (fp32 / fp64); row r is the IVP of `y0[r]`.  `t` is `[T]` (a grid shared by all
@@ -560,17 +749,31 @@ def odeint_rowwise(func, y0, t, *, rtol=1e-7, atol=1e-9, method="dopri5", option
 
     Returns the solution `[T, *y0.shape]` with `solution[j, r]` = row r at `t[j]` (or `t[j, r]`); with
     `return_stats=True`, `(solution, stats)` where `stats` holds `n_accepted` and `n_rejected` (int64 `[B]`) and
-    `nfe` (func calls for the whole batch).  No gradients: with grad mode on and `y0`, `t` or a parameter of `func`
-    requiring grad this raises NotImplementedError (use `odeint` / `odeint_adjoint`).
+    `nfe` (func calls for the whole batch).
+
+    Gradients: by default none — with grad mode on and `y0`, `t` or a parameter of `func` requiring grad this raises
+    NotImplementedError.  `differentiable=True` (with grad mode on) records the solve: the solution carries an autograd
+    graph to `y0` and to every tensor `func` uses that requires grad, with the same forward bits, step counts and `nfe`
+    as the default.  The controller (error norm, accept / reject, next dt_r) is outside the graph; a row's FIRST step
+    size is inside it when it comes from the initial-step heuristic and outside it when `first_step` is given; `t_rows`
+    is detached from `t` and carries only that first-step graph (as the reference's stage times do; none with
+    `first_step`); a finished or rejected row sends an exactly-zero cotangent into `func`'s backward for that evaluation.
+    Every trial step's stage tensors stay alive until the backward, so memory grows with the number of trial
+    iterations.  Time gradients (`t.requires_grad`) and second-order gradients (`create_graph=True`) raise
+    NotImplementedError; under `torch.no_grad()` the argument has no effect.
     """
-    p = _Problem(func, y0, t, rtol, atol, method, options, event_fn)
+    p = _Problem(func, y0, t, rtol, atol, method, options, event_fn, differentiable)
     n_t = p.tgrid.shape[0]
     f0 = None
+    y_start = p.y0
+    if p.record:
+        # a private, aligned copy that carries y0's graph (the recorded solve never writes into a state tensor)
+        y_start = p.y0_graph.clone(memory_format=torch.contiguous_format)
     if n_t > 1:
         # the first evaluation in the caller's grad mode: a func whose output depends on parameters that require grad
-        # (closures included) is refused here, never silently detached
+        # (closures included) is refused here, never silently detached (unless the solve is recorded)
         with device_guard(p.device):
-            f0 = p.call((p.tgrid[0] * p.sign).to(p.dtype).to(p.device), p.y0).clone()
+            f0 = p.call((p.tgrid[0] * p.sign).to(p.dtype).to(p.device), y_start).clone()
     with torch.no_grad(), device_guard(p.device):
         sol = torch.empty(n_t, p.B, p.L, dtype=p.dtype, device=p.device)
         sol[0].copy_(p.y0)
@@ -582,7 +785,13 @@ def odeint_rowwise(func, y0, t, *, rtol=1e-7, atol=1e-9, method="dopri5", option
         n_acc = n_rej = None
         if n_t > 1:
             # private state buffers: the dense-output launch commits y <- y1, f0 <- f1 in place
-            y = p.y0.clone()
+            y = y_start if p.record else p.y0.clone()
+            if p.record:
+                if isinstance(kern, HipRowKernels):
+                    kern.sol_rows = [y] + [None] * (n_t - 1)
+                else:
+                    with torch.enable_grad():
+                        sol[0] = y                   # the host path records the solution rows as in-place writes
             kern.initial_step(y, f0)
             while True:
                 if isinstance(kern, HipRowKernels):
@@ -599,12 +808,20 @@ def odeint_rowwise(func, y0, t, *, rtol=1e-7, atol=1e-9, method="dopri5", option
                                           y[r].view(p.shape[1:]))
                 if n_active == 0:
                     break
-                kern.trial_step(y, f0, sol)
+                y, f0 = kern.trial_step(y, f0, sol)
             if isinstance(kern, HipRowKernels):
                 n_acc, n_rej = kern.finish()
             else:
                 n_acc, n_rej = torch.from_numpy(kern.n_acc.copy()), torch.from_numpy(kern.n_rej.copy())
-        solution = sol.view(n_t, *p.shape)
+        if p.record:
+            with torch.enable_grad():
+                if isinstance(kern, HipRowKernels) and n_t > 1:
+                    sol = torch.stack(kern.sol_rows)          # (each row is the raw solution row's storage: same bits)
+                elif n_t == 1:
+                    sol = y_start[None]
+                solution = rad.first_order_only(sol.view(n_t, *p.shape))
+        else:
+            solution = sol.view(n_t, *p.shape)
     if not return_stats:
         return solution
     if n_acc is None:
