@@ -234,3 +234,146 @@ def test_multi_with_the_step_size_on_the_device_equals_host_dt(hip_kernels, name
             assert torch.equal(_bits(x), _bits(y)), (name, op.row)
         checked += 1
     assert checked >= 5
+
+
+# ---- one launch plan for every tableau (tableaus.launch_plan / tableau_row_plan) ---------------------------------------
+_FUSED = {tb.FUSE_ROWWISE: {"dopri5": True, "bosh3": True, "dopri8": False, "tsit5": False, "fehlberg2": False,
+                            "adaptive_heun": False},
+          tb.FUSE_ODEINT: {"dopri5": True, "bosh3": True, "dopri8": True, "tsit5": True, "fehlberg2": False,
+                           "adaptive_heun": True}}
+
+
+def _hand_written_launches(tab, left):
+    """The row-by-row launches as the loops of rowwise.py / _graph.py built them before there was a plan for them,
+    straight from the tableau: (launches after row 0 as (idx, spec, continues, targets), err_idx, err_coef, fused)."""
+    rows = tab.beta_rows()
+    if not tab.fsal_solution:
+        rows = rows + [tb.SparseRow.from_dense(tab.c_sol)]
+    err = tb.SparseRow.from_dense(tab.c_error)
+    R, n_lead = len(rows), len(rows[-1].idx)
+    fused = err.idx[:n_lead] == rows[-1].idx and left[0] <= len(err.idx) - n_lead <= left[1]
+    launches = []
+    for i in range(1, R):
+        row = rows[i]
+        spec, targets = [(tuple(row.coef), (1 << len(row.idx)) - 1, True)], [i]
+        if fused and i == R - 1:
+            spec.append((tuple(err.coef[:n_lead]), (1 << n_lead) - 1, False))
+            targets.append(R)
+        launches.append((tuple(row.idx), tuple(spec), False, tuple(targets)))
+    n_lead = n_lead if fused else 0
+    return launches, tuple(err.idx[n_lead:]), tuple(err.coef[n_lead:]), fused
+
+
+@pytest.mark.parametrize("left", [tb.FUSE_ROWWISE, tb.FUSE_ODEINT], ids=["rowwise", "odeint"])
+@pytest.mark.parametrize("name", ["dopri5", "bosh3", "tsit5", "fehlberg2", "adaptive_heun", "dopri8"])
+def test_row_by_row_plan_is_the_hand_written_loop(name, left):
+    tab = tb.ADAPTIVE_TABLEAUS[name]
+    launches, err_idx, err_coef, fused = _hand_written_launches(tab, left)
+    assert fused == _FUSED[left][name]
+    plan = tb.tableau_row_plan(name, left)
+    assert plan.ops[0] is None and len(plan.ops) == len(launches) + 1
+    got = [(op.idx, tuple((tuple(c), m, a) for c, m, a in op.spec), op.continues, op.targets) for op in plan.ops[1:]]
+    assert got == launches and [op.row for op in plan.ops[1:]] == list(range(1, len(plan.ops)))
+    assert (plan.err_idx, tuple(plan.err_coef)) == (err_idx, err_coef)
+    assert plan.launches == len(plan.ops) + 1
+    if fused:
+        assert plan.words == tb.row_by_row_words(tab)
+    # what odeint_rowwise launches: the carry plan where there is one, else this plan under the rowwise rule
+    if tb.carry_plan(name) is not None:
+        assert tb.launch_plan(name) is tb.carry_plan(name)
+    elif left == tb.FUSE_ROWWISE:
+        assert tb.launch_plan(name) is plan
+
+
+def test_solver_row_plan_is_built_from_its_own_rows(cpu_backend, monkeypatch):
+    """The plan a captured step interprets where there is no carry plan comes from the solver's own rows and `_fuse`
+    (the solver classes take any Tableau), and equals the by-name plan for the shipped ones."""
+    import torchdiffeq_amd as tda
+    from torchdiffeq_amd.solvers.adaptive import RKAdaptiveStepsizeODESolver
+    seen = []
+    orig = RKAdaptiveStepsizeODESolver.integrate
+    monkeypatch.setattr(RKAdaptiveStepsizeODESolver, "integrate", lambda self, t: (seen.append(self), orig(self, t))[1])
+    for name in ["dopri5", "bosh3", "tsit5", "fehlberg2", "adaptive_heun", "dopri8"]:
+        with torch.no_grad():
+            tda.odeint(lambda t_, y: -y, torch.ones(8, dtype=torch.float64), torch.tensor([0.0, 1.0], dtype=torch.float64),
+                       method=name)
+        s = seen.pop()
+        assert not seen and s.tableau.name == name
+        if name == "fehlberg2":
+            assert s._fuse is None and s._row_plan is None
+            continue
+        plan, want = s._row_plan, tb.tableau_row_plan(name, tb.FUSE_ODEINT)
+        assert (plan.ops, plan.err_idx, tuple(plan.err_coef)) == (want.ops, want.err_idx, tuple(want.err_coef))
+        assert plan.ops[-1].spec[1][0] == s._fuse[0] and (plan.err_idx, plan.err_coef) == s._fuse[1:]
+
+
+# ---- odeint_rowwise: the launches of one trial step on the HIP kernels ------------------------------------------------
+class _LaunchLog:
+    """Stand-in for the kernels object: logs every launch (no arithmetic), so it runs without the native library."""
+
+    def __init__(self):
+        self.log = []
+
+    def row_partials(self, L, dtype):
+        return 1
+
+    def row_combine(self, outs, rows, y0, acc_in, ks, dts, active):
+        self.log.append(["combine", len(outs), [[list(c), m, a] for c, m, a in rows], acc_in is not None, len(ks)])
+
+    def row_reduce(self, mode, part, y0, y1, partial, ks, coefs, dts, active, rtol, atol):
+        self.log.append(["reduce", mode, partial is not None, len(ks), list(coefs)])
+
+    def row_control(self, mode, *a):
+        self.log.append(["control", mode])
+
+    def row_dense_commit(self, sol, y0, y1, f0, f1, ks, coefs, dts, st):
+        self.log.append(["commit", len(ks), list(coefs)])
+
+
+@pytest.mark.parametrize("method,n_launches", [("dopri5", 9), ("bosh3", 6), ("tsit5", 10), ("fehlberg2", 6),
+                                               ("adaptive_heun", 5), ("dopri8", 15)])
+def test_rowwise_trial_step_launches(monkeypatch, method, n_launches):
+    """`HipRowKernels.trial_step` issues, launch for launch and argument for argument, what it issued when the fixture
+    was recorded (golden/rowwise_launch_log.json: the log of this stand-in before the two hand-written schedules became
+    one plan interpreter)."""
+    import json
+    from torchdiffeq_amd import _native, rowwise
+    fake = _LaunchLog()
+    monkeypatch.setattr(_native, "get_kernels", lambda dev, dt: fake)
+    y0 = torch.ones(3, 4, dtype=torch.float64)
+    t = torch.tensor([0.0, 1.0], dtype=torch.float64)
+    with torch.no_grad():
+        p = rowwise._Problem(lambda t_, y: -y, y0, t, 1e-6, 1e-8, method, None, None)
+        k = rowwise.HipRowKernels(p)
+        k.dts = torch.zeros(3, dtype=torch.float64)
+        k.times = torch.zeros(p.method.n_stages, 3, dtype=torch.float64)
+        y = p.y0.clone()
+        k.trial_step(y, -y, torch.empty(2, 3, 4, dtype=torch.float64))
+    with open(os.path.join(os.path.dirname(__file__), "golden", "rowwise_launch_log.json")) as f:
+        want = json.load(f)[method]
+    assert len(fake.log) == n_launches == len(want)
+    for got, exp in zip(fake.log, want):
+        assert got == exp
+
+
+def test_recorded_rowwise_backend_is_freed_by_reference_count(monkeypatch):
+    """A recorded solve's backend owns the heads of the whole autograd graph (solution rows, first-step and anchor
+    graphs): it must die with its last reference, not wait for the cyclic collector."""
+    import gc
+    import weakref
+    from torchdiffeq_amd import _native, rowwise
+    monkeypatch.setattr(_native, "get_kernels", lambda dev, dt: _LaunchLog())
+    y0 = torch.ones(3, 4, dtype=torch.float64, requires_grad=True)
+    p = rowwise._Problem(lambda t_, y: -y, y0, torch.tensor([0.0, 1.0], dtype=torch.float64), 1e-6, 1e-8, "dopri5",
+                         None, None, True)
+    assert p.record
+    gc.collect()
+    gc.disable()
+    try:
+        k = rowwise.HipRowKernels(p)
+        assert k.rec is not None
+        ref = weakref.ref(k)
+        del k
+        assert ref() is None
+    finally:
+        gc.enable()

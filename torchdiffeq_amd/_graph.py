@@ -820,16 +820,16 @@ class _GraphStep:
     def body(self, s, side: int) -> None:
         func, kern, plan = s.func, s.kernels, s.plan
         beta, fuse, fsal = s._beta, s._fuse, s.tableau.fsal_solution
+        # the launches of the step: the carry plan (tableaus.carry_plan; needs the multi-output launch that reads the step
+        # size on the device), else row by row with the end-of-step fusion, as a plan too (RKAdaptive..._row_plan)
+        carry = s._carry if s._carry is not None and hasattr(kern, "stage_combine_multi_dev") else s._row_plan
         y_cur, f_cur, y1, epart = self.y[side], self.f_in(side), self.y[1 - side], self.epart[side]
         k = [f_cur]
         yi = torch.empty_like(y_cur)
         kern.stage_combine_dev(yi, None, y_cur, [f_cur], beta[0].coef, None, plan)
         k.append(func.eval_at(self.ts[0], yi))
         n_rows = len(beta)
-        carry = s._carry if hasattr(kern, "stage_combine_multi_dev") else None
         if carry is not None:
-            # planned launches (tableaus.carry_plan) with the step size read on the device: same stage inputs, fewer
-            # bytes and — dopri8 — one node fewer per captured step
             held, R = {}, len(carry.ops)
             for i in range(1, R):
                 op = carry.ops[i]
@@ -853,46 +853,27 @@ class _GraphStep:
                 if i < n_rows:
                     k.append(func.eval_at(self.ts[i], yi))
             assert held.pop(R) is epart and not held
+            # side 0 reads its derivative from a buffer of its own (see the class text): side 1's last evaluation goes there —
+            # written by the norm launch itself where that launch reads the stream anyway (r06), else by a copy node
             if not self._norm_ctrl(s, epart, y_cur, y1, [k[j] for j in carry.err_idx], carry.err_coef,
                                    self.f0 if side == 1 and carry.err_idx and carry.err_idx[-1] == len(k) - 1 else None) \
                     and side == 1:
                 self.f0.copy_(k[-1])
             self.k[side] = k
             return
-        if fuse is None:
-            # 16-bit states (csrc/tdeq_kernels_lp.hpp): every row whole and the error row whole — a reduced-precision row sum
-            # is rounded once, so there is no partial error to hand from the last combine to the norm launch
-            for i in range(1, n_rows):
-                row = beta[i]
-                yi = y1 if (i == n_rows - 1 and fsal) else torch.empty_like(y_cur)
-                kern.stage_combine_dev(yi, None, y_cur, [k[j] for j in row.idx], row.coef, None, plan)
-                k.append(func.eval_at(self.ts[i], yi))
-            if not fsal:
-                kern.stage_combine_dev(y1, None, y_cur, [k[j] for j in s._c_sol.idx], s._c_sol.coef, None, plan)
-            err = s._c_err
-            kern.error_norm_ctrl(plan, y_cur, y1, [k[j] for j in err.idx], err.coef, 0.0, s._ctrl, self.tbuf,
-                                 state_in_dev=True)
-            if side == 1:
-                self.f0.copy_(k[-1])
-            self.k[side] = k
-            return
+        # no partial error: 16-bit states (csrc/tdeq_kernels_lp.hpp) — every row whole and the error row whole: a reduced-
+        # precision row sum is rounded once, so there is nothing to hand from the last combine to the norm launch
         for i in range(1, n_rows):
             row = beta[i]
-            ks = [k[j] for j in row.idx]
-            if i == n_rows - 1 and fsal:
-                yi = y1
-                kern.stage_combine_dev(yi, epart, y_cur, ks, row.coef, fuse[0], plan)
-            else:
-                yi = torch.empty_like(y_cur)
-                kern.stage_combine_dev(yi, None, y_cur, ks, row.coef, None, plan)
+            yi = y1 if (i == n_rows - 1 and fsal) else torch.empty_like(y_cur)
+            kern.stage_combine_dev(yi, None, y_cur, [k[j] for j in row.idx], row.coef, None, plan)
             k.append(func.eval_at(self.ts[i], yi))
         if not fsal:
-            sol = s._c_sol
-            kern.stage_combine_dev(y1, epart, y_cur, [k[j] for j in sol.idx], sol.coef, fuse[0], plan)
-        # side 0 reads its derivative from a buffer of its own (see the class text): side 1's last evaluation goes there —
-        # written by the norm launch itself where that launch reads the stream anyway (r06), else by a copy node
-        if not self._norm_ctrl(s, epart, y_cur, y1, [k[j] for j in fuse[1]], fuse[2],
-                               self.f0 if side == 1 and fuse[1] and fuse[1][-1] == len(k) - 1 else None) and side == 1:
+            kern.stage_combine_dev(y1, None, y_cur, [k[j] for j in s._c_sol.idx], s._c_sol.coef, None, plan)
+        err = s._c_err
+        kern.error_norm_ctrl(plan, y_cur, y1, [k[j] for j in err.idx], err.coef, 0.0, s._ctrl, self.tbuf,
+                             state_in_dev=True)
+        if side == 1:
             self.f0.copy_(k[-1])
         self.k[side] = k
 

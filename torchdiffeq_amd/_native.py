@@ -51,6 +51,20 @@ class StepCtrl(ctypes.Structure):
                 ("n_times", ctypes.c_int32), ("n_norm_seg", ctypes.c_int32), ("leading_abs", ctypes.c_int32)]
 
 
+def step_ctrl(alpha, alpha_is_one, order, safety, ifactor, dfactor, min_step, max_step, time_sign, n_norm_seg) -> StepCtrl:
+    """A `StepCtrl` from the stage abscissae (`alpha_is_one`: which of them are exactly 1), the method's order, the
+    controller's constants, the step bounds and the direction of time; t0 / dt are per step, `leading_abs` stays 0."""
+    c = StepCtrl()
+    c.safety, c.ifactor, c.dfactor = safety, ifactor, dfactor
+    c.exponent = 1.0 / order
+    c.min_step, c.max_step, c.time_sign = min_step, max_step, time_sign
+    for i, a in enumerate(alpha):
+        c.alpha[i] = float(a)
+    c.alpha_is_one = sum(1 << i for i, one in enumerate(alpha_is_one) if one)
+    c.n_times, c.n_norm_seg = len(alpha), n_norm_seg
+    return c
+
+
 class MultiOut(ctypes.Structure):
     """`tdeq_multi_out` of include/tdeq_hip.h: one output of tdeq_stage_combine_multi."""
     _fields_ = [("out", ctypes.c_void_p), ("coef", ctypes.c_double * TDEQ_MAX_TERMS), ("mask", ctypes.c_uint32),

@@ -9,6 +9,14 @@ other rows (as long as `func` itself treats rows independently).
 On a ROCm device every state-sized operation is a HIP kernel of csrc/tdeq_kernels_rowwise.hpp and the per-row
 controller runs on the device (the host reads two words per trial step); CPU states run the same row operations as
 torch ops (`HostRowKernels`, one `HostPathWarning`).
+
+Three things are kept apart.  WHAT IS LAUNCHED in a trial step is `HipRowKernels.trial_step`: one interpreter of the
+tableau's launch plan (`tableaus.launch_plan`: the carry plan of dopri5 / dopri8 / tsit5, row by row for the others),
+then the error norm, the controller and the dense-output commit.  The TWO BACKENDS offer the driver the same methods —
+`initial_step`, `trial_step`, `poll`, `counts` and, for a recorded solve, `begin_recording` / `recorded_solution` —
+and `odeint_rowwise` calls nothing else.  WHAT IS RECORDED for `differentiable=True` lives in rowwise_autodiff.py: the
+device backend hands its finished launches to a `RowRecorder` (None in a plain solve), the host backend records plain
+torch ops; `_Problem.grad_mode` is the one place that turns grad mode on for a recorded solve.
 """
 from __future__ import annotations
 
@@ -24,9 +32,9 @@ from . import rowwise_autodiff as rad
 from ._native import device_guard
 from ._scalars import nextafter, power, rdiv, scalar_type
 from .solvers._common import optimal_step_size
-from .solvers.adaptive import (AdaptiveHeunSolver, Bosh3Solver, Dopri5Solver, Dopri8Solver, Fehlberg2,
+from .solvers.adaptive import (STEP_CALLBACKS, AdaptiveHeunSolver, Bosh3Solver, Dopri5Solver, Dopri8Solver, Fehlberg2,
                                Tsit5Solver)
-from .tableaus import SparseRow, carry_plan
+from .tableaus import SparseRow, launch_plan
 
 __all__ = ["odeint_rowwise"]
 
@@ -91,7 +99,7 @@ class _Problem:
                                      "elements)")
             elif not isinstance(tol, (int, float)) or isinstance(tol, bool):
                 raise ValueError(f"odeint_rowwise: {name} must be a number (vector / tuple tolerances are not supported)")
-        for name in _native_callback_names():
+        for name in STEP_CALLBACKS:
             if getattr(func, name, None) is not None:
                 raise ValueError(f"odeint_rowwise: step callbacks ({name}) are not supported")
         if not isinstance(t, torch.Tensor) or not torch.is_floating_point(t):
@@ -152,12 +160,13 @@ class _Problem:
         self.max_num_steps = int(options.get("max_num_steps", 2 ** 31 - 1))
         self.nfe = 0
 
+    def grad_mode(self):
+        """The grad mode the backends step in (inside the driver's no_grad): on for a recorded solve.  The controller is
+        outside the graph either way: it works on detached values or under a no_grad of its own."""
+        return torch.enable_grad() if self.record else contextlib.nullcontext()
+
     def call(self, t_rows: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
         """func(t_rows [B], y [B, *row_shape]) -> [B, L] contiguous in the state's dtype."""
-        with torch.enable_grad() if self.record else contextlib.nullcontext():
-            return self._call(t_rows, y)
-
-    def _call(self, t_rows: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
         self.nfe += 1
         f = self.func(t_rows, y.view(self.shape))
         if not isinstance(f, torch.Tensor):
@@ -176,16 +185,13 @@ class _Problem:
             f = f.to(self.dtype)
         return f if f.is_contiguous() and f.data_ptr() % 16 == 0 else f.contiguous(memory_format=torch.contiguous_format).clone()
 
-    def raise_row_error(self, r: int, code: int, since: int, dt: float, y_row) -> None:
+    def raise_row_error(self, failure, y) -> None:
+        r, code, since, dt = failure
         if code == 2:
             raise AssertionError("max_num_steps exceeded ({}>={}) in row {}".format(since, self.max_num_steps, r))
         if code == 1:
             raise AssertionError("underflow in dt {} in row {}".format(dt, r))
-        raise AssertionError("non-finite values in state `y`: {} in row {}".format(y_row, r))
-
-
-def _native_callback_names():
-    return ("callback_step", "callback_accept_step", "callback_reject_step")
+        raise AssertionError("non-finite values in state `y`: {} in row {}".format(y[r].view(self.shape[1:]), r))
 
 
 def _row_sum(x: torch.Tensor) -> torch.Tensor:
@@ -278,12 +284,22 @@ class HostRowKernels:
             code = 2
         self.code[r] = code
 
+    # -- what the driver calls besides the two steps -------------------------------------------------------------------
+    def begin_recording(self, sol, y) -> None:
+        sol[0] = y                                           # the host path records the solution rows as in-place writes
+
+    def recorded_solution(self, sol) -> torch.Tensor:
+        return sol
+
+    def poll(self):
+        r = next((r for r in range(self.p.B) if self.active[r] and self.code[r] != 0), None)
+        return int(self.active.sum()), None if r is None else (r, int(self.code[r]), int(self.since[r]), float(self.dt[r]))
+
+    def counts(self):
+        return torch.from_numpy(self.n_acc.copy()), torch.from_numpy(self.n_rej.copy())
+
     # -- initial step ---------------------------------------------------------------------------------------------------
     def initial_step(self, y, f0) -> None:
-        with torch.enable_grad() if self.p.record else contextlib.nullcontext():
-            self._initial_step(y, f0)
-
-    def _initial_step(self, y, f0) -> None:
         p, T = self.p, self.T
         self.t0[:] = p.tgrid[0].numpy()
         scale = p.atol + y.detach().abs() * p.rtol
@@ -332,10 +348,6 @@ class HostRowKernels:
     def trial_step(self, y, f0, sol):
         """One trial step of every active row; returns the (y, f0) of the next one (the same tensors, committed in
         place, unless the solve is recorded)."""
-        with torch.enable_grad() if self.p.record else contextlib.nullcontext():
-            return self._trial_step(y, f0, sol)
-
-    def _trial_step(self, y, f0, sol):
         p, m, T = self.p, self.p.method, self.T
         dts = self._dts_tensor([T(self.dt[r]) * T(p.sign) if self.active[r] else T(0) for r in range(p.B)])
         shadow, self.s_shadow = self.s_shadow, None          # only the first trial step's size carries a graph
@@ -343,11 +355,7 @@ class HostRowKernels:
         if shadow is not None:
             dts = rad.stitch_rows(dts, shadow, p.sign)
         act = torch.from_numpy(self.active.copy()).reshape(-1, 1)
-        times = self.times_tensor()
-        if shadow is not None:
-            times = [rad.stitch_rows(tt, shadow, p.sign * float(a)) for tt, a in zip(times, m.alpha)]
-        elif anchor is not None:
-            times = [rad.stitch_rows(tt, anchor, p.sign) for tt in times]
+        times = rad.stage_times(self.times_tensor(), m.alpha, p.sign, shadow, anchor)
         ks = [f0]
         yi = None
         for i, row in enumerate(m.beta):
@@ -487,111 +495,28 @@ class HipRowKernels:
         st.n_out, st.order = self.tg.shape[0], p.method.order - 1
         self.st = st
         m = p.method
-        c = _native.StepCtrl()
-        c.safety, c.ifactor, c.dfactor = p.safety, p.ifactor, p.dfactor
-        c.exponent = 1.0 / m.order
-        c.min_step, c.max_step = 0.0, math.inf
-        c.time_sign = p.sign
-        mask = 0
-        for i, a in enumerate(m.alpha):
-            c.alpha[i] = float(a)
-            if m.alpha_is_one[i]:
-                mask |= 1 << i
-        c.alpha_is_one = mask
-        c.n_times = m.n_stages
-        c.n_norm_seg = 1
-        self.ctrl = c
-        self.carry = carry_plan(m.name)
+        self.ctrl = _native.step_ctrl(m.alpha, m.alpha_is_one, m.order, p.safety, p.ifactor, p.dfactor, 0.0, math.inf,
+                                      p.sign, n_norm_seg=1)
+        self.plan = launch_plan(m.name)
         self.dts = None
         self.times = None
-        # record mode (differentiable=True): every launch below becomes one rowwise_autodiff._RowLinearOp node
-        self.rec = p.record
-        self.s_shadow = None          # [B] fp64 graph of the first step sizes (initial-step heuristic)
-        self.anchor = None            # [B] fp64 graph of the time the later steps of a row are anchored to
-        self.sol_rows = None          # graph tensors of the solution rows (each the raw row's storage)
-        self._coef_t = {}
+        # a recorded solve (differentiable=True): every launch below is handed to the recorder and becomes a graph node
+        self.rec = rad.RowRecorder(self.k, p, _row_sum) if p.record else None
 
-    # -- record mode ----------------------------------------------------------------------------------------------------
-    def _coefs(self, row: SparseRow) -> torch.Tensor:
-        c = self._coef_t.get(id(row))
-        if c is None:
-            c = self._coef_t[id(row)] = torch.tensor(row.coef, dtype=self.p.dtype, device=self.p.device)[:, None]
-        return c
+    def begin_recording(self, sol, y) -> None:
+        self.rec.sol_rows = [y] + [None] * (sol.shape[0] - 1)
 
-    def _node(self, raw, y, ks, row: SparseRow, dts, shadow):
-        """`raw` = y + sum_j fl_T(fl_T(a_j) dts[r]) k_j over the whole tableau row, as one graph node (the carried
-        partial sums of the launch are an implementation detail of the forward)."""
-        if not self.rec:
-            return raw
-        w = (self._coefs(row) * dts[None, :]).unbind(0)          # T products: the kernel's own coefficients
-        xs = [y] + [ks[j] for j in row.idx]
-        if shadow is None:
-            return rad.row_linear(self.k, raw, xs, [1.0, *w])
-        dw = [0.0] + [float(c) * self.p.sign for c in self._coefs(row)[:, 0].tolist()]
-        return rad.row_linear(self.k, raw, xs, [1.0, *w], s=shadow, dw=dw)
+    def recorded_solution(self, sol) -> torch.Tensor:
+        return torch.stack(self.rec.sol_rows)          # (each row is the raw solution row's storage: same bits)
 
-    def _record_commit(self, sol, y, y1, f0, ks, step_dts, t_start, shadow, anchor):
-        """Graph of the dense output + commit launch that just ran on the fresh (y_new, f0_new)."""
-        p, m = self.p, self.p.method
-        y_new, f0_new = self._fresh
-        acc, lo, hi = self.accepted != 0, self.out_lo, self.out_hi
-        hit = acc & (hi > lo)
-        n_acc, j_lo, j_hi = torch.stack([acc.sum(), torch.where(hit, lo, _NO_ERROR_ROW).min().long(),
-                                         torch.where(hit, hi, 0).max().long()]).tolist()
-        S = m.n_stages
-        if j_hi > j_lo:
-            d = step_dts.double()
-            width = torch.where(hit, self.t0 - t_start, torch.ones_like(self.t0))
-            cmid = self._coefs(m.c_mid)[:, 0].double().tolist()
-            for j in range(j_lo, j_hi):
-                mask = hit & (lo <= j) & (hi > j)
-                # theta as the kernel forms it: in the time type, then rounded to T (interp.py:39-40)
-                x = torch.where(mask, ((self.tg[j] - t_start) / width).to(p.dtype).double(), torch.zeros_like(width))
-                w, dwx, dwd = rad.dense_weights(x, d, cmid)
-                md = mask.double()
-                slots = {0: 2, S: 3}                           # f0 = k_0 and f1 = k_S usually carry a mid weight too
-                merged = [list(v[:4]) for v in (w, dwx, dwd)]
-                order = [0, S]
-                for q, jj in enumerate(m.c_mid.idx):
-                    if jj in slots:
-                        for lst, src in zip(merged, (w, dwx, dwd)):
-                            lst[slots[jj]] = lst[slots[jj]] + src[4 + q]
-                    else:
-                        slots[jj] = len(merged[0])
-                        order.append(jj)
-                        for lst, src in zip(merged, (w, dwx, dwd)):
-                            lst.append(src[4 + q])
-                xs = [y, y1] + [ks[jj] for jj in order]
-                ws = [(v * md).to(p.dtype) for v in merged[0]]
-                prev = self.sol_rows[j]
-                if prev is not None:
-                    # `prev` and the new node's value are both the storage of sol[j], which later launches rewrite
-                    # behind autograd's back: safe only because the chained input has weight 1 and dw = 0, so its
-                    # VALUE is never read in a backward (g passes through, no dot is taken with it)
-                    xs, ws = [prev] + xs, [1.0] + ws
-                if shadow is None and anchor is None:
-                    self.sol_rows[j] = rad.row_linear(self.k, sol[j], xs, ws)
-                    continue
-                if shadow is not None:
-                    # the first step: weights depend on dt_r directly (d = sign dt_r) and through theta (-x / dt_r)
-                    dw = [(dd * p.sign - dx * x / width) * md for dx, dd in zip(merged[1], merged[2])]
-                else:
-                    # a later step is shifted as a whole with the row's anchor: d theta / d anchor = -1 / width
-                    dw = [-dx / width * md for dx in merged[1]]
-                if prev is not None:
-                    dw = [0.0] + dw
-                self.sol_rows[j] = rad.row_linear(self.k, sol[j], xs, ws, s=shadow if shadow is not None else anchor,
-                                                  dw=dw)
-        if shadow is not None:
-            self.anchor = shadow * acc.double()
-        if n_acc == 0:
-            return y, f0
-        if n_acc == p.B:
-            wm = [1.0, 0.0]
-        else:
-            mt = acc.to(p.dtype)
-            wm = [mt, 1 - mt]
-        return rad.row_linear(self.k, y_new, [y1, y], wm), rad.row_linear(self.k, f0_new, [ks[-1], f0], wm)
+    def poll(self):
+        n_active, r = self.status.tolist()                   # the two words the host reads per trial step
+        if r == _NO_ERROR_ROW or n_active == 0:
+            return n_active, None
+        return n_active, (r, int(self.code[r]), int(self.since[r]), float(self.dt[r]))
+
+    def counts(self):
+        return self.n_acc.cpu(), self.n_rej.cpu()
 
     def _control(self, mode: int) -> None:
         p = self.p
@@ -600,134 +525,64 @@ class HipRowKernels:
         self.k.row_control(mode, self.part, self.ctrl, self.st, dts, times, p.dtype)
         self.dts, self.times = dts, times
 
-    def status_words(self):
-        return self.status.tolist()
-
     def initial_step(self, y, f0) -> None:
-        p, k = self.p, self.k
+        p, k, rec = self.p, self.k, self.rec
         k.row_reduce(1, self.part, y, y, f0, [], [], None, None, p.rtol, p.atol)
         if p.first_step is not None:
             self.dt.copy_(p.first_step.to(self.dt.device))
             self._control(3)
             return
         self._control(1)
-        y1 = torch.empty_like(y)
+        y1, t1 = torch.empty_like(y), self.times[0]
         k.row_combine([y1], (((1.0,), 1, True),), y, None, [f0], self.dts, self.active)
-        shadow = None
-        if self.rec:
-            with torch.enable_grad():
-                shadow = rad.FirstStepShadow(_row_sum, y, f0, p.rtol, p.atol, p.sign)
-            y1 = rad.row_linear(k, y1, [y, f0], [1.0, self.dts], s=shadow.h0, dw=[0.0, p.sign])
-        f1 = p.call(self.times[0] if shadow is None else rad.stitch_rows(self.times[0], shadow.h0, p.sign), y1)
+        if rec is not None:
+            y1, t1 = rec.first_probe(y, f0, y1, self.dts, t1)
+        f1 = p.call(t1, y1)
         k.row_reduce(2, self.part, y, f1, f0, [], [], None, None, p.rtol, p.atol)
         self._control(2)
-        if shadow is not None:
-            with torch.enable_grad():
-                self.s_shadow = shadow.finish(f1, p.method.order - 1)
+        if rec is not None:
+            rec.first_step_size(f1)
 
     def trial_step(self, y, f0, sol):
         """One trial step of every active row; returns the (y, f0) of the next one (the same tensors, committed in
         place, unless the solve is recorded: then fresh graph tensors)."""
-        p, m, k = self.p, self.p.method, self.k
+        p, m, k, plan, rec = self.p, self.p.method, self.k, self.plan, self.rec
         dts, times, act = self.dts, self.times.unbind(0), self.active
-        shadow, self.s_shadow = self.s_shadow, None          # only the first trial step's size carries a graph
-        if shadow is not None and not shadow.requires_grad:
-            shadow = None
-        anchor = self.anchor
-        if shadow is not None:
-            times = [rad.stitch_rows(tt, shadow, p.sign * float(a)) for tt, a in zip(times, m.alpha)]
-        elif anchor is not None:
-            times = [rad.stitch_rows(tt, anchor, p.sign) for tt in times]
-        node = lambda raw, row: self._node(raw, y, ks, row, dts, shadow)      # noqa: E731
+        if rec is not None:
+            times = rec.begin_step(times)
         ks = [f0]
-        S = m.n_stages
-        err_partial, err_rem = None, None
-        y1 = None
-        if self.carry is not None:
-            carry = self.carry
-            held, R = {}, len(carry.ops)
-            yi = torch.empty_like(y)
-            k.row_combine([yi], ((m.beta[0].coef, (1 << len(m.beta[0].idx)) - 1, True),), y, None,
-                          [ks[j] for j in m.beta[0].idx], dts, act)
-            yi = node(yi, m.beta[0])
-            ks.append(p.call(times[0], yi))
-            for i in range(1, R):
-                op = carry.ops[i]
-                if op is None:
-                    yi = held.pop(i)
-                else:
-                    outs = [torch.empty_like(y) for _ in op.targets]
-                    k.row_combine(outs, op.spec, y, held.pop(i) if op.continues else None, [ks[j] for j in op.idx],
-                                  dts, act)
-                    yi = outs[0]
-                    for tgt, buf in zip(op.targets[1:], outs[1:]):
-                        held[tgt] = buf
-                yi = node(yi, m.beta[i] if i < S else m.c_sol)
-                if i < S:
-                    ks.append(p.call(times[i], yi))
-                else:
-                    y1 = yi
-            err_partial, err_rem = held.pop(R), (carry.err_idx, carry.err_coef)
-            if y1 is None:
-                y1 = yi
-        else:
-            n_lead = len((m.beta[-1] if m.fsal else m.c_sol).idx)
-            # the step's last combine also emits the error row's leading run when it is the same stage set and the norm
-            # launch keeps at least one stage of its own (adaptive_heun's error row has no stage beyond it: not fused)
-            fuse = m.c_err.idx[:n_lead] == (m.beta[-1] if m.fsal else m.c_sol).idx and len(m.c_err.idx) > n_lead
-            for i, row in enumerate(m.beta):
-                last = i == S - 1 and m.fsal and fuse
+        held, R, S = {}, len(plan.ops), m.n_stages
+        for i in range(R):
+            op, row = plan.ops[i], m.beta[i] if i < S else m.c_sol
+            if i == 0:                                       # row 0 is no part of a plan: one whole output
                 yi = torch.empty_like(y)
-                spec = ((row.coef, (1 << len(row.idx)) - 1, True),)
-                outs = [yi]
-                if last:
-                    err_partial = torch.empty_like(y)
-                    spec = spec + ((m.c_err.coef[:n_lead], (1 << n_lead) - 1, False),)
-                    outs.append(err_partial)
-                k.row_combine(outs, spec, y, None, [ks[j] for j in row.idx], dts, act)
-                yi = node(yi, row)
-                ks.append(p.call(times[i], yi))
-            if m.fsal:
-                y1 = yi
+                k.row_combine([yi], ((row.coef, (1 << len(row.idx)) - 1, True),), y, None, [ks[j] for j in row.idx],
+                              dts, act)
+            elif op is None:
+                yi = held.pop(i)                             # finished by an earlier launch
             else:
-                y1 = torch.empty_like(y)
-                spec = ((m.c_sol.coef, (1 << len(m.c_sol.idx)) - 1, True),)
-                outs = [y1]
-                if fuse:
-                    err_partial = torch.empty_like(y)
-                    spec = spec + ((m.c_err.coef[:n_lead], (1 << n_lead) - 1, False),)
-                    outs.append(err_partial)
-                k.row_combine(outs, spec, y, None, [ks[j] for j in m.c_sol.idx], dts, act)
-                y1 = node(y1, m.c_sol)
-            if err_partial is not None:
-                err_rem = (m.c_err.idx[n_lead:], m.c_err.coef[n_lead:])
-        if err_partial is None:
-            k.row_reduce(0, self.part, y, y1, None, [ks[j] for j in m.c_err.idx], m.c_err.coef, dts, act,
-                         p.rtol, p.atol)
-        else:
-            k.row_reduce(0, self.part, y, y1, err_partial, [ks[j] for j in err_rem[0]], err_rem[1], dts, act,
-                         p.rtol, p.atol)
-        step_dts = dts
-        if not self.rec:
-            self._control(0)
-            k.row_dense_commit(sol, y, y1, f0, ks[-1], [ks[j] for j in m.c_mid.idx], m.c_mid.coef, step_dts, self.st)
-            return y, f0
-        # recorded: the same launch commits into fresh tensors, the inputs stay alive for the backward
-        t_start = self.t0.clone()
+                outs = [torch.empty_like(y) for _ in op.targets]
+                k.row_combine(outs, op.spec, y, held.pop(i) if op.continues else None, [ks[j] for j in op.idx], dts, act)
+                yi = outs[0]
+                for tgt, buf in zip(op.targets[1:], outs[1:]):
+                    held[tgt] = buf
+            if rec is not None:
+                yi = rec.stage(yi, y, ks, row, dts)
+            if i < S:
+                ks.append(p.call(times[i], yi))
+        y1, f1, mid = yi, ks[-1], [ks[j] for j in m.c_mid.idx]
+        # the error norm continues the partial error row of the last combine (none: the whole row), then the controller
+        k.row_reduce(0, self.part, y, y1, held.pop(R, None), [ks[j] for j in plan.err_idx], plan.err_coef, dts, act,
+                     p.rtol, p.atol)
+        # dense output + commit y <- y1, f0 <- f1 of the accepted rows: in place, or, recorded, into fresh tensors (the
+        # inputs stay alive for the backward)
+        t_start = None if rec is None else self.t0.clone()
         self._control(0)
-        self._fresh = (y.detach().clone(), f0.detach().clone())
-        k.row_dense_commit(sol, self._fresh[0], y1, self._fresh[1], ks[-1], [ks[j] for j in m.c_mid.idx], m.c_mid.coef,
-                           step_dts, self.st)
-        with torch.enable_grad():
-            out = self._record_commit(sol, y, y1, f0, ks, step_dts, t_start, shadow, anchor)
-        self._fresh = None
-        return out
-
-    def finish(self):
-        return self.n_acc.cpu(), self.n_rej.cpu()
-
-    def row_error(self, r: int):
-        return int(self.code[r]), int(self.since[r]), float(self.dt[r])
+        y_to, f0_to = (y, f0) if rec is None else (y.detach().clone(), f0.detach().clone())
+        k.row_dense_commit(sol, y_to, y1, f0_to, f1, mid, m.c_mid.coef, dts, self.st)
+        if rec is None:
+            return y, f0
+        return rec.commit(self, sol, y, y1, f0, ks, dts, t_start, y_to, f0_to)
 
 
 def odeint_rowwise(func, y0, t, *, rtol=1e-7, atol=1e-9, method="dopri5", options=None, return_stats=False,
@@ -786,39 +641,21 @@ def odeint_rowwise(func, y0, t, *, rtol=1e-7, atol=1e-9, method="dopri5", option
         if n_t > 1:
             # private state buffers: the dense-output launch commits y <- y1, f0 <- f1 in place
             y = y_start if p.record else p.y0.clone()
-            if p.record:
-                if isinstance(kern, HipRowKernels):
-                    kern.sol_rows = [y] + [None] * (n_t - 1)
-                else:
-                    with torch.enable_grad():
-                        sol[0] = y                   # the host path records the solution rows as in-place writes
-            kern.initial_step(y, f0)
-            while True:
-                if isinstance(kern, HipRowKernels):
-                    n_active, err_row = kern.status_words()
-                    if err_row != _NO_ERROR_ROW and n_active > 0:
-                        code, since, dt = kern.row_error(err_row)
-                        p.raise_row_error(err_row, code, since, dt, y[err_row].view(p.shape[1:]))
-                else:
-                    n_active = int(kern.active.sum())
-                    bad = [r for r in range(p.B) if kern.active[r] and kern.code[r] != 0]
-                    if bad:
-                        r = bad[0]
-                        p.raise_row_error(r, int(kern.code[r]), int(kern.since[r]), float(kern.dt[r]),
-                                          y[r].view(p.shape[1:]))
-                if n_active == 0:
-                    break
-                y, f0 = kern.trial_step(y, f0, sol)
-            if isinstance(kern, HipRowKernels):
-                n_acc, n_rej = kern.finish()
-            else:
-                n_acc, n_rej = torch.from_numpy(kern.n_acc.copy()), torch.from_numpy(kern.n_rej.copy())
+            with p.grad_mode():
+                if p.record:
+                    kern.begin_recording(sol, y)
+                kern.initial_step(y, f0)
+                while True:
+                    n_active, failure = kern.poll()
+                    if failure is not None:
+                        p.raise_row_error(failure, y)
+                    if n_active == 0:
+                        break
+                    y, f0 = kern.trial_step(y, f0, sol)
+            n_acc, n_rej = kern.counts()
         if p.record:
             with torch.enable_grad():
-                if isinstance(kern, HipRowKernels) and n_t > 1:
-                    sol = torch.stack(kern.sol_rows)          # (each row is the raw solution row's storage: same bits)
-                elif n_t == 1:
-                    sol = y_start[None]
+                sol = kern.recorded_solution(sol) if n_t > 1 else y_start[None]
                 solution = rad.first_order_only(sol.view(n_t, *p.shape))
         else:
             solution = sol.view(n_t, *p.shape)

@@ -25,6 +25,10 @@ Node types and their weights (dts[r] = sign * T(dt_r), 0 for a finished row):
   dense output       sol[j] = the quartic of the row's accepted step at theta_jr, linear in (y0, y1, f0, f1, k_mid);
                      weights zero for the rows whose step does not contain output time j
 A rejected or finished row gets an exactly-zero cotangent through the commit mask.
+
+`RowRecorder` holds everything only a recorded device solve needs (the first-step and anchor graphs, the solution rows'
+graph tensors, the tableau-only slot map of the dense-output node) and turns the launches `rowwise.HipRowKernels` hands
+it into these nodes; `stage_times` is the one rule, shared with the host backend, for the graph the stage times carry.
 """
 from __future__ import annotations
 
@@ -192,3 +196,127 @@ class FirstStepShadow:
         h1 = torch.where(floor, self.h0 * 1e-3, (0.01 / m) ** (1.0 / float(order + 1))).abs()
         big = 100 * self.h0
         return torch.where(h1.detach() < big.detach(), h1, big)
+
+
+def stage_times(times, alpha, sign: float, shadow, anchor):
+    """The stage times handed to func with the graph they carry: the first trial step's t0 + alpha_i dt_r (`shadow`,
+    the row's first step size), a later step's anchor (it is shifted as a whole); plain values without either."""
+    if shadow is not None:
+        return [stitch_rows(tt, shadow, sign * float(a)) for tt, a in zip(times, alpha)]
+    if anchor is not None:
+        return [stitch_rows(tt, anchor, sign) for tt in times]
+    return times
+
+
+class RowRecorder:
+    """What only a recorded solve on the HIP kernels needs: every launch of `rowwise.HipRowKernels` handed to it becomes
+    one `_RowLinearOp` node over the launch's finished output.  It holds the kernels object and the problem, never the
+    backend: that owns the recorder, and a cycle would keep the whole recorded graph alive until the cyclic collector
+    runs; `commit` is handed the backend (`rows`: its per-row device vectors are read, never written) per call.  The
+    solve runs in grad mode (`rowwise._Problem.grad_mode`)."""
+
+    def __init__(self, kernels, problem, row_sum):
+        self.k, self.p, self.row_sum = kernels, problem, row_sum
+        self.first = None             # FirstStepShadow between the two halves of the initial-step heuristic
+        self.s_shadow = None          # [B] fp64 graph of the first step sizes (initial-step heuristic)
+        self.shadow = None            # ... while the first trial step runs (only that step's size carries a graph)
+        self.anchor = None            # [B] fp64 graph of the time the later steps of a row are anchored to
+        self.sol_rows = None          # graph tensors of the solution rows (each the raw row's storage)
+        self._coef_t = {}
+        # which of (y0, y1, f0 = k_0, f1 = k_S, k_mid...) share an input of the dense-output node: f0 and f1 usually
+        # carry a mid weight too.  slot of every c_mid term, and the stages behind the slots from 2 on
+        m = self.p.method
+        slots = {0: 2, m.n_stages: 3}
+        for j in m.c_mid.idx:
+            slots.setdefault(j, len(slots) + 2)
+        self.mid_slot, self.dense_stages = [slots[j] for j in m.c_mid.idx], list(slots)
+
+    def _coefs(self, row) -> torch.Tensor:
+        c = self._coef_t.get(id(row))
+        if c is None:
+            c = self._coef_t[id(row)] = torch.tensor(row.coef, dtype=self.p.dtype, device=self.p.device)[:, None]
+        return c
+
+    def first_probe(self, y, f0, y1, dts, t1):
+        """(y1, t1) of the initial-step heuristic's probe y1 = y + h0 f0 at t1 = t0 + h0, as graph tensors."""
+        p = self.p
+        self.first = FirstStepShadow(self.row_sum, y, f0, p.rtol, p.atol, p.sign)
+        return (row_linear(self.k, y1, [y, f0], [1.0, dts], s=self.first.h0, dw=[0.0, p.sign]),
+                stitch_rows(t1, self.first.h0, p.sign))
+
+    def first_step_size(self, f1) -> None:
+        self.s_shadow, self.first = self.first.finish(f1, self.p.method.order - 1), None
+
+    def begin_step(self, times):
+        """The stage times of this trial step as func gets them."""
+        self.shadow, self.s_shadow = self.s_shadow, None
+        if self.shadow is not None and not self.shadow.requires_grad:
+            self.shadow = None
+        return stage_times(times, self.p.method.alpha, self.p.sign, self.shadow, self.anchor)
+
+    def stage(self, raw, y, ks, row, dts):
+        """`raw` = y + sum_j fl_T(fl_T(a_j) dts[r]) k_j over the whole tableau row, as one graph node (the carried
+        partial sums of the launch are an implementation detail of the forward)."""
+        w = (self._coefs(row) * dts[None, :]).unbind(0)          # T products: the kernel's own coefficients
+        xs = [y] + [ks[j] for j in row.idx]
+        if self.shadow is None:
+            return row_linear(self.k, raw, xs, [1.0, *w])
+        dw = [0.0] + [float(c) * self.p.sign for c in self._coefs(row)[:, 0].tolist()]
+        return row_linear(self.k, raw, xs, [1.0, *w], s=self.shadow, dw=dw)
+
+    def commit(self, rows, sol, y, y1, f0, ks, step_dts, t_start, y_new, f0_new):
+        """Graph of the dense output + commit launch that just ran on the fresh (y_new, f0_new); returns them as the
+        graph tensors of the next trial step's (y, f0)."""
+        p, m = self.p, self.p.method
+        shadow, anchor = self.shadow, self.anchor
+        acc, lo, hi = rows.accepted != 0, rows.out_lo, rows.out_hi
+        hit = acc & (hi > lo)
+        n_acc, j_lo, j_hi = torch.stack([acc.sum(), torch.where(hit, lo, torch.iinfo(torch.int32).max).min().long(),
+                                         torch.where(hit, hi, 0).max().long()]).tolist()
+        if j_hi > j_lo:
+            d = step_dts.double()
+            width = torch.where(hit, rows.t0 - t_start, torch.ones_like(rows.t0))
+            cmid = self._coefs(m.c_mid)[:, 0].double().tolist()
+            for j in range(j_lo, j_hi):
+                mask = hit & (lo <= j) & (hi > j)
+                # theta as the kernel forms it: in the time type, then rounded to T (interp.py:39-40)
+                x = torch.where(mask, ((rows.tg[j] - t_start) / width).to(p.dtype).double(), torch.zeros_like(width))
+                parts = dense_weights(x, d, cmid)                   # (w, dw/dx, dw/dd) per input
+                merged = [list(v[:4]) for v in parts]
+                for q, slot in enumerate(self.mid_slot):
+                    for lst, src in zip(merged, parts):
+                        if slot < 4:
+                            lst[slot] = lst[slot] + src[4 + q]
+                        else:
+                            lst.append(src[4 + q])
+                md = mask.double()
+                xs = [y, y1] + [ks[jj] for jj in self.dense_stages]
+                ws = [(v * md).to(p.dtype) for v in merged[0]]
+                prev = self.sol_rows[j]
+                if prev is not None:
+                    # `prev` and the new node's value are both the storage of sol[j], which later launches rewrite
+                    # behind autograd's back: safe only because the chained input has weight 1 and dw = 0, so its
+                    # VALUE is never read in a backward (g passes through, no dot is taken with it)
+                    xs, ws = [prev] + xs, [1.0] + ws
+                if shadow is None and anchor is None:
+                    self.sol_rows[j] = row_linear(self.k, sol[j], xs, ws)
+                    continue
+                if shadow is not None:
+                    # the first step: weights depend on dt_r directly (d = sign dt_r) and through theta (-x / dt_r)
+                    dw = [(dd * p.sign - dx * x / width) * md for dx, dd in zip(merged[1], merged[2])]
+                else:
+                    # a later step is shifted as a whole with the row's anchor: d theta / d anchor = -1 / width
+                    dw = [-dx / width * md for dx in merged[1]]
+                if prev is not None:
+                    dw = [0.0] + dw
+                self.sol_rows[j] = row_linear(self.k, sol[j], xs, ws, s=shadow if shadow is not None else anchor, dw=dw)
+        if shadow is not None:
+            self.anchor = shadow * acc.double()
+        if n_acc == 0:
+            return y, f0
+        if n_acc == p.B:
+            wm = [1.0, 0.0]
+        else:
+            mt = acc.to(p.dtype)
+            wm = [mt, 1 - mt]
+        return row_linear(self.k, y_new, [y1, y], wm), row_linear(self.k, f0_new, [ks[-1], f0], wm)

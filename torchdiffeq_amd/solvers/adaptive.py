@@ -24,10 +24,13 @@ from ..autodiff import Ops, stitch  # noqa: F401
 from ..misc import (BuiltinNorm, OdeFunc, Perturb, StateLayout, component_norm, find_event, handle_unused_kwargs, rms_norm,  # noqa: F401
                    vector_tolerances)
 from ..misc import _null_callback as _null
-from ..tableaus import (ADAPTIVE_HEUN, ADAPTIVE_TABLEAUS, BOSH3, CARRY_DEFAULT_ON, DOPRI5, DOPRI8, FEHLBERG2, TSIT5, SparseRow, Tableau,  # noqa: F401
-                       adams_coefficients, carry_plan)
+from ..tableaus import (ADAPTIVE_HEUN, ADAPTIVE_TABLEAUS, BOSH3, CARRY_DEFAULT_ON, DOPRI5, DOPRI8, FEHLBERG2, FUSE_ODEINT, TSIT5, SparseRow,  # noqa: F401
+                       Tableau, adams_coefficients, carry_plan, fused_lead, row_by_row_plan)
 from ._common import _nan_max, _nan_min, _clamp, _norm_value, _as_float, optimal_step_size, optimal_step_size_in, _StepShadow, _NoShadow, _NO_SHADOW  # noqa: F401
 from .events import AdaptiveEvents
+
+# the step callbacks an adaptive solver offers, in the order they are named in messages
+STEP_CALLBACKS = ("callback_step", "callback_accept_step", "callback_reject_step")
 
 
 class _LockStep:
@@ -238,14 +241,12 @@ class RKAdaptiveStepsizeODESolver(AdaptiveEvents):
         # End-of-step fusion (tdeq_stage_combine_err + tdeq_error_norm_partial): the step's last combine — the last
         # stage row of an FSAL pair, else the c_sol combine — also emits the partial embedded error over its own
         # stages.  Bit-identical only if those stages are a leading run of the error row's non-zeros.
-        last = self._beta[-1] if tab.fsal_solution else self._c_sol
-        n_lead = len(last.idx)
+        n_lead = fused_lead(self._beta[-1] if tab.fsal_solution else self._c_sol, self._c_err, FUSE_ODEINT)
         self._fuse = None
         # (not on the torch-op host path, which hands every row to ATen's `torch.sum` whole — `literal_row_sums`,
         # _fallback.py: splitting a row re-associates it, and for bf16 / fp16 states would round it twice)
         # (nor for reduced-precision states on the HIP kernels — `split_row_sums` False: a row is rounded ONCE)
-        if self._c_err.idx[:n_lead] == last.idx and len(self._c_err.idx) - n_lead <= 2 \
-                and not getattr(self.kernels, "literal_row_sums", False) \
+        if n_lead and not getattr(self.kernels, "literal_row_sums", False) \
                 and getattr(self.kernels, "split_row_sums", True):
             self._fuse = (self._c_err.coef[:n_lead], self._c_err.idx[n_lead:], self._c_err.coef[n_lead:])
         # Carried partial sums (tableaus.carry_plan / tdeq_stage_combine_multi): fewer bytes per step for the same bits.
@@ -257,6 +258,14 @@ class RKAdaptiveStepsizeODESolver(AdaptiveEvents):
                 and (carry_env == "1" or self.layout.total >= CARRY_DEFAULT_ON.get(tab.name, float("inf"))) \
                 and hasattr(self.kernels, "stage_combine_multi") and ADAPTIVE_TABLEAUS.get(tab.name) is tab:
             self._carry = carry_plan(tab.name)
+        # The row-by-row launches with the end-of-step fusion as a plan too (tableaus.row_by_row_plan), from this solver's
+        # own rows (any `Tableau`, not only the shipped ones): what a captured step interprets where it has no carry plan.
+        # None without the fusion, and for a one-launch step, which has no combine to host the partial error.
+        self._row_plan = None
+        launch_rows = self._beta + ([] if tab.fsal_solution else [self._c_sol])
+        if self._fuse is not None and len(launch_rows) > 1:
+            self._row_plan = row_by_row_plan(launch_rows, self._c_err, n_lead)
+            assert (self._row_plan.err_idx, self._row_plan.err_coef) == self._fuse[1:]
         self.n_accepted = 0
         self.n_rejected = 0
         # Device-resident controller + look-ahead first stage (tdeq_error_norm_partial_ctrl / tdeq_stage_combine_sel):
@@ -324,19 +333,8 @@ class RKAdaptiveStepsizeODESolver(AdaptiveEvents):
         self._g = None
         self._dt_shadow = None      # autograd graph of the current step size (the first, heuristic one only)
         if device_ctrl:
-            c = _native.StepCtrl()
-            c.safety, c.ifactor, c.dfactor = self.safety, self.ifactor, self.dfactor
-            c.exponent = 1.0 / self.order
-            c.min_step, c.max_step = self.min_step, self.max_step
-            c.time_sign = func.sign
-            mask = 0
-            for i, a in enumerate(self._alpha):
-                c.alpha[i] = float(a)
-                if self._alpha_is_one[i]:
-                    mask |= 1 << i
-            c.alpha_is_one = mask
-            c.n_times = len(self._alpha)
-            c.n_norm_seg = n_norm_seg
+            c = _native.step_ctrl(self._alpha, self._alpha_is_one, self.order, self.safety, self.ifactor, self.dfactor,
+                                  self.min_step, self.max_step, func.sign, n_norm_seg)
             # the adjoint norms take their one-element time component as |t|, not as an rms (adjoint.py:250, 273): the
             # same number for fp32 / fp64, one rounding apart for 16-bit states (include/tdeq_hip.h `leading_abs`)
             c.leading_abs = 1 if (getattr(self.norm, "leading_scalar", False) and self.plan.numels[0] == 1) else 0
@@ -348,7 +346,7 @@ class RKAdaptiveStepsizeODESolver(AdaptiveEvents):
 
     @classmethod
     def valid_callbacks(cls):
-        return {"callback_step", "callback_accept_step", "callback_reject_step"}
+        return set(STEP_CALLBACKS)
 
     # -- norms -------------------------------------------------------------------------------------
     @np.errstate(all="ignore")     # host scalars follow IEEE silently, as 0-dim tensors do

@@ -403,6 +403,52 @@ def carry_plan(name: str):
     return None if hosts is None else _plan_from_hosts(ADAPTIVE_TABLEAUS[name], dict(hosts))
 
 
+def row_by_row_plan(rows: Sequence[SparseRow], err: SparseRow, n_lead: int) -> CarryPlan:
+    """The launches without carried sums as a plan.  `rows`: the launch rows (the stage rows, then the c_sol combine of
+    a pair whose solution is not its last stage input), each with one whole output; with `n_lead` > 0 the last launch
+    also emits the error row's first `n_lead` terms (the end-of-step fusion) and the rest is left to the norm launch,
+    else the plan carries no partial error and the norm launch takes the whole error row."""
+    R = len(rows)
+    assert n_lead == 0 or (R > 1 and err.idx[:n_lead] == rows[-1].idx), "the fused terms are the last launch's own stages"
+    ops = [None]
+    for i in range(1, R):
+        row, fused = rows[i], n_lead > 0 and i == R - 1
+        full = (1 << len(row.idx)) - 1
+        spec = ((row.coef, full, True),) + (((err.coef[:n_lead], full, False),) if fused else ())
+        ops.append(CarryOp(i, row.idx, False, (i, R) if fused else (i,), spec))
+    rem = err.idx[n_lead:]
+    p = 1 if n_lead else 0
+    return CarryPlan(tuple(ops), rem, err.coef[n_lead:], sum(len(r.idx) + 2 for r in rows) + 2 * p + len(rem) + 2, R + 1)
+
+
+# The end-of-step fusion needs the last launch's stages to be a leading run of the error row's; the two users differ in
+# how many error terms may be left to the norm launch (min, max): the rowwise norm launch keeps at least one stage of
+# its own, tdeq_error_norm_partial continues over at most two (and over none).
+FUSE_ROWWISE, FUSE_ODEINT = (1, math.inf), (0, 2)
+
+
+def fused_lead(last: SparseRow, err: SparseRow, left) -> int:
+    """How many leading error terms the step's last combine `last` emits under the rule `left`; 0 = not fused."""
+    n_lead = len(last.idx)
+    return n_lead if err.idx[:n_lead] == last.idx and left[0] <= len(err.idx) - n_lead <= left[1] else 0
+
+
+@functools.lru_cache(maxsize=None)
+def tableau_row_plan(name: str, left=FUSE_ODEINT) -> CarryPlan:
+    """`row_by_row_plan` of the shipped tableau `name` under the fusion rule `left`."""
+    tab = ADAPTIVE_TABLEAUS[name]
+    rows = tab.beta_rows() + ([] if tab.fsal_solution else [SparseRow.from_dense(tab.c_sol)])
+    err = SparseRow.from_dense(tab.c_error)
+    n_lead = fused_lead(rows[-1], err, left)
+    return row_by_row_plan(rows, err, n_lead if len(rows) > 1 else 0)
+
+
+def launch_plan(name: str) -> CarryPlan:
+    """The launches of one `odeint_rowwise` trial step of the tableau `name`: its carry plan where it has one, else
+    row by row under the rowwise fusion rule."""
+    return carry_plan(name) or tableau_row_plan(name, FUSE_ROWWISE)
+
+
 def row_by_row_words(tab: Tableau) -> int:
     """Words per element and step of the row-by-row launches with the end-of-step fusion (docs/LAB_NOTEBOOK.md §3)."""
     rows = tab.beta_rows()
