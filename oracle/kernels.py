@@ -16,6 +16,7 @@ import os
 import subprocess
 from typing import List, Sequence, Tuple
 
+import numpy as np
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -295,3 +296,248 @@ class OracleKernels:
         """Host twin of tdeq_fill_scalars: vals converted to dst's dtype."""
         import torch as _torch
         dst.copy_(_torch.tensor(list(vals), dtype=_torch.float64).to(dst.dtype))
+
+    # -- per-row step control: the row interface of HipKernels, row by row ------------------------------------------------
+    # The contract (csrc/tdeq_kernels_rowwise.hpp): every element of row r is what the whole-batch operation gives for
+    # that row alone with dt = float(dts[r]).  So each method below loops over the rows and calls the whole-batch oracle
+    # on the row's slice; what has no whole-batch twin is restated in numpy scalars of T, one rounded operation at a
+    # time.  Row sums are `math.fsum` of the fp64 squares of the per-element T ratios: the correctly rounded sum, which
+    # any summation order of the device must be close to.  A row's sum is stored in its first partial (the others are
+    # zero): the layout of `part` is [3][B * nch] as on the device, how a sum is split over the partials is not.
+    @staticmethod
+    def row_partials(row_len: int, dtype) -> int:
+        """Partials per row, restated from the geometry rule: 16-byte elements when the row is a whole number of them,
+        one partial up to 1024 elements, else one per 2048."""
+        lv = {torch.float32: 4, torch.float64: 2}[dtype]
+        nv = row_len // lv if row_len % lv == 0 else row_len
+        return 1 if nv <= 1024 else -(-nv // 2048)
+
+    @staticmethod
+    def _np_type(dtype):
+        return {torch.float32: np.float32, torch.float64: np.float64}[dtype]
+
+    @staticmethod
+    def _fsum_sq(x) -> float:
+        sq = np.asarray(x, dtype=np.float64) ** 2
+        return math.fsum(sq) if np.isfinite(sq).all() else float(sq.sum())
+
+    def row_combine(self, outs, rows, y0, acc_in, ks, dts, active) -> None:
+        for r in range(y0.shape[0]):
+            if not int(active[r]):
+                for out, (_, _, add_y0) in zip(outs, rows):
+                    if add_y0:
+                        out[r].copy_(y0[r])
+                    else:
+                        out[r].zero_()
+                continue
+            self.stage_combine_multi([o[r] for o in outs], rows, y0[r], None if acc_in is None else acc_in[r],
+                                     [k[r] for k in ks], float(dts[r]))
+
+    def row_reduce(self, mode: int, part, y0, y1, partial, ks, coefs, dts, active, rtol: float, atol: float) -> None:
+        B, L = y0.shape
+        nch = self.row_partials(L, y0.dtype)
+        assert part.numel() >= 3 * B * nch and part.dtype == torch.float64
+        T = self._np_type(y0.dtype)
+        plan = OraclePlan([(0, L, rtol, atol)], L, L)
+        out = part.view(-1)[:3 * B * nch].view(3, B, nch)
+        out.zero_()
+        for r in range(B):
+            if mode == 0:
+                if not int(active[r]):
+                    continue
+                dt = float(dts[r])
+                if partial is None:
+                    scaled = torch.empty_like(y0[r])
+                    self.error_scaled(plan, scaled, y0[r], y1[r], [k[r] for k in ks], coefs, dt)
+                    scaled = scaled.numpy()
+                else:
+                    # e = partial + sum_j fl(fl(c_j) * T(dt)) * k_j, left to right; e / (atol + rtol * max(|y0|, |y1|))
+                    with np.errstate(all="ignore"):
+                        e = partial[r].numpy().copy()
+                        for k, c in zip(ks, coefs):
+                            e = e + k[r].numpy() * (T(c) * T(dt))
+                        tol = T(atol) + T(rtol) * np.fmax(np.abs(y0[r].numpy()), np.abs(y1[r].numpy()))
+                        scaled = e / tol
+                out[0, r, 0] = self._fsum_sq(scaled)
+                out[2, r, 0] = float((~(torch.isfinite(y0[r]) & torch.isfinite(y1[r]))).sum())
+            else:
+                # y0 = the scale state, y1 = a, partial = b: (a / scale, b / scale) or (a - b) / scale
+                s0, s1 = torch.empty_like(y0[r]), torch.empty_like(y0[r])
+                self.init_scaled(plan, mode - 1, y1[r], partial[r], y0[r], s0, s1 if mode == 1 else None)
+                out[0, r, 0] = self._fsum_sq(s0.numpy())
+                if mode == 1:
+                    out[1, r, 0] = self._fsum_sq(s1.numpy())
+                out[2, r, 0] = float((~torch.isfinite(y0[r])).sum())
+
+    @staticmethod
+    def _state_views(st):
+        """numpy views of the vectors a RowState points to (CPU addresses)."""
+        B, n_out = int(st.n_rows), int(st.n_out)
+
+        def view(name, ctype, shape):
+            return np.ctypeslib.as_array(ctypes.cast(getattr(st, name), ctypes.POINTER(ctype)), shape=shape)
+        v = {name: view(name, ctypes.c_double, (B,)) for name in ("t0", "tprev", "dt", "h0", "ratio")}
+        v.update({name: view(name, ctypes.c_int32, (B,)) for name in ("active", "accepted", "out_lo", "out_hi", "next_out",
+                                                                        "since", "bad_y", "code")})
+        v.update({name: view(name, ctypes.c_int64, (B,)) for name in ("n_acc", "n_rej")})
+        v["tgrid"] = view("tgrid", ctypes.c_double, (n_out, B))
+        v["status"] = view("status", ctypes.c_int32, (2,))
+        return v
+
+    @staticmethod
+    def _row_stage_times(ctrl, T, t0: float, dt: float):
+        """Stage times of the trial step (t0, dt) in T: nextafter(T(t0 + dt), -inf side) where alpha_i == 1, else
+        T(t0) + T(alpha_i) * T(dt); times the direction of time."""
+        t0T, dtT, t1T = T(t0), T(dt), T(t0 + dt)
+        out = []
+        with np.errstate(all="ignore"):
+            for i in range(ctrl.n_times):
+                if (ctrl.alpha_is_one >> i) & 1:
+                    tt = np.nextafter(t1T, t1T - T(1))
+                else:
+                    tt = t0T + T(ctrl.alpha[i]) * dtT
+                out.append(T(ctrl.time_sign) * tt)
+        return out
+
+    def row_control(self, mode: int, part, ctrl, st, dts_out, times_out, dtype) -> None:
+        B, L = int(st.n_rows), int(st.row_len)
+        T = self._np_type(dtype)
+        nch = self.row_partials(L, dtype)
+        v = self._state_views(st)
+        sums = part.view(-1)[:3 * B * nch].view(3, B, nch).numpy()
+        dts, times = dts_out.numpy(), times_out.numpy().reshape(-1, B)
+        n_times, sign = int(ctrl.n_times), float(ctrl.time_sign)
+        plan = OraclePlan([(0, L, 0.0, 0.0)], L, L)
+        n_live, first_err = 0, 0x7FFFFFFF
+
+        def total(q, r):
+            x = sums[q, r]
+            return math.fsum(x) if np.isfinite(x).all() else float(x.sum())
+
+        def norm(s):                                        # sqrt(mean) rounded to T
+            with np.errstate(all="ignore"):
+                return T(np.sqrt(np.float64(s) / np.float64(L)))
+
+        def freeze(r):
+            dts[r] = T(0)
+            times[:n_times, r] = T(sign) * T(v["t0"][r])
+
+        def prepare(r, expect=None):
+            dtn = float(v["dt"][r])
+            if not math.isfinite(dtn):
+                dtn = float(ctrl.min_step)
+            dtn = min(max(dtn, float(ctrl.min_step)), float(ctrl.max_step))
+            v["dt"][r] = dtn
+            t0 = float(v["t0"][r])
+            dts[r] = T(dtn) * T(sign)
+            tt = self._row_stage_times(ctrl, T, t0, dtn)
+            if expect is not None:          # the next trial step of the whole-batch controller: the same step, the same bits
+                assert dts[r] == T(expect[0]) and [float(x) for x in tt] == expect[1], (r, tt, expect)
+            times[:n_times, r] = tt
+            code = 3 if v["bad_y"][r] else 0
+            if not t0 + dtn > t0:
+                code = 1
+            if v["since"][r] >= st.max_num_steps:
+                code = 2
+            v["code"][r] = code
+            return code != 0
+
+        for r in range(B):
+            live = bool(v["active"][r])
+            s0, s1, sb = total(0, r), total(1, r), total(2, r)
+            expect = None
+            if mode == 0:
+                if not live:
+                    v["accepted"][r] = 0
+                    freeze(r)
+                    continue
+                c = type(ctrl).from_buffer_copy(ctrl)
+                c.t0, c.dt, c.n_norm_seg = float(v["t0"][r]), float(v["dt"][r]), 1
+                nxt = torch.empty(n_times, dtype=dtype)
+                (accept, dt_next, ratio, t_next), (_, dts_next) = self.step_controller(plan, [s0], c, nxt, dtype)
+                v["ratio"][r] = ratio
+                v["since"][r] += 1
+                v["accepted"][r] = 1 if accept else 0
+                if accept:
+                    v["tprev"][r] = v["t0"][r]
+                    v["t0"][r] = t_next
+                    v["n_acc"][r] += 1
+                    lo = hi = int(v["next_out"][r])
+                    while hi < st.n_out and v["tgrid"][hi, r] <= t_next:
+                        hi += 1
+                    v["out_lo"][r], v["out_hi"][r], v["next_out"][r] = lo, hi, hi
+                    if hi > lo:
+                        v["since"][r] = 0
+                    v["bad_y"][r] = 1 if sb != 0.0 else 0
+                    if hi >= st.n_out:
+                        live = False
+                        v["active"][r] = 0
+                else:
+                    v["n_rej"][r] += 1
+                v["dt"][r] = dt_next
+                expect = (dts_next, nxt.double().tolist())
+            elif mode == 1:
+                with np.errstate(all="ignore"):
+                    d0, d1 = norm(s0), norm(s1)
+                    h0 = T(1e-6) if (d0 < T(1e-5) or d1 < T(1e-5)) else (T(0.01) * d0) / d1
+                    h0 = -h0 if h0 < T(0) else h0
+                    v["h0"][r] = float(h0)
+                    v["bad_y"][r] = 1 if sb != 0.0 else 0
+                    dts[r] = T(float(h0) * sign)
+                    times[0, r] = T(sign) * T(float(v["t0"][r]) + float(h0))
+                    v["dt"][r] = float(d1)                  # parked for mode 2
+                n_live += live
+                continue
+            elif mode == 2:
+                with np.errstate(all="ignore"):
+                    h0, d1 = T(v["h0"][r]), T(v["dt"][r])
+                    d2 = norm(s0) / h0
+                    d2 = -d2 if d2 < T(0) else d2
+                    if d1 <= T(1e-15) and d2 <= T(1e-15):
+                        lo_, val = T(1e-6), h0 * T(1e-3)
+                        h1 = val if val > lo_ else lo_
+                    else:
+                        m = d2 if d2 > d1 else d1
+                        q = (T(1) / m) * T(0.01)
+                        e = 1.0 / float(st.order + 1)
+                        h1 = np.sqrt(q) if e == 0.5 else T(math.pow(float(q), e)) if float(q) >= 0 else T(np.nan)
+                    h1 = -h1 if h1 < T(0) else h1
+                    big = T(100) * h0
+                    v["dt"][r] = float(h1 if h1 < big else big)
+            else:
+                v["bad_y"][r] = 1 if sb != 0.0 else 0
+            if live:
+                if prepare(r, expect):
+                    first_err = min(first_err, r)
+            else:
+                freeze(r)
+            n_live += live
+        v["status"][0], v["status"][1] = n_live, first_err
+
+    def row_dense_commit(self, sol, y0, y1, f0, f1, ks, coefs, dts, st) -> None:
+        v = self._state_views(st)
+        T = self._np_type(y0.dtype)
+        for r in range(int(st.n_rows)):
+            if not v["accepted"][r]:
+                continue
+            ta, tb = v["tprev"][r], v["t0"][r]
+            for j in range(int(v["out_lo"][r]), int(v["out_hi"][r])):
+                x = T((v["tgrid"][j, r] - ta) / (tb - ta))      # the fraction in fp64, rounded to T once
+                self.dense_eval(sol[j, r], y0[r], y1[r], f0[r], f1[r], [k[r] for k in ks], coefs, float(dts[r]), float(x))
+            y0[r].copy_(y1[r])
+            f0[r].copy_(f1[r])
+
+    def row_scale_many(self, outs, g, w) -> None:
+        for r in range(g.shape[0]):
+            self.scale_many([o[r] for o in outs], g[r], [float(x) for x in w[:, r]])
+
+    @staticmethod
+    def row_multi_dot(g, xs) -> torch.Tensor:
+        """fp64 [len(xs), B]: the correctly rounded sum of the fp64 products of each row."""
+        out = torch.empty(len(xs), g.shape[0], dtype=torch.float64)
+        g64 = g.double().numpy()
+        for m, x in enumerate(xs):
+            prod = g64 * x.double().numpy()
+            for r in range(g.shape[0]):
+                out[m, r] = math.fsum(prod[r]) if np.isfinite(prod[r]).all() else float(prod[r].sum())
+        return out

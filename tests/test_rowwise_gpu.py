@@ -99,11 +99,13 @@ def test_hip_batch_invariance(B):
     assert torch.equal(part, full[:, idx.to(DEV)])
 
 
-@pytest.mark.parametrize("B,L", [(65536, 1), (64, 3), (64, 128), (64, 129), (2, 1 << 20), (1, 1 << 22)])
+@pytest.mark.parametrize("B,L", [(65536, 1), (64, 3), (64, 128), (64, 129), (2, 1 << 20), (1, 1 << 22),
+                                 (64, 1500), (64, 4100), (16, 8192), (64, 4096), (16, 8196)])
 def test_hip_shapes(B, L):
     """Every row reduction shape: several rows per wave (L = 1, 3), a group of lanes per row (128, 129: 16-byte and
-    scalar elements), chunked long rows (2^20, 2^22) — checked against the same rows solved alone (batch invariance)
-    and against the host path on a few rows."""
+    scalar elements), chunked long rows (2^20, 2^22), long rows of ONE chunk (1500 scalar, 4100 and 8192 16-byte
+    elements) with the last short length (4096) and the first two-chunk one (8196) on either side — checked against
+    the same rows solved alone (batch invariance) and against the host path on a few rows."""
     g = torch.Generator().manual_seed(L)
     k = torch.logspace(-1, 1, B, dtype=torch.float64)[:, None]
     y0 = torch.randn(B, L, generator=g, dtype=torch.float32)

@@ -52,7 +52,7 @@ def test_row_scale_many(L, dtype):
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.float64])
-@pytest.mark.parametrize("L", [1, 3, 4, 127, 128, 2048, 2049, (1 << 15) + 5])
+@pytest.mark.parametrize("L", [1, 3, 4, 127, 128, 2048, 2049, (1 << 15) + 5, 1025, 1500, 2047, 4096, 4100, 8192])
 def test_row_multi_dot(L, dtype):
     """out[m, r] = <g[r], x_m[r]> in fp64: within the bound of an fp64 accumulation of L terms (L * 2^-53 * sum|g x|),
     and the same bits for a row at B = 1 and inside a large batch."""
@@ -243,6 +243,32 @@ def test_hip_long_rows():
     for r in range(B):
         one, _ = _grad_y0(make, y0, t, W, idx=torch.tensor([r]), rtol=1e-5, atol=1e-7)
         assert torch.equal(one[0], full[r])
+
+
+@pytest.mark.parametrize("L", [4100, 1501])
+def test_hip_one_chunk_long_rows(L):
+    """`test_hip_long_rows` at long rows of ONE chunk (1024 < 16-byte or scalar elements <= 2048: the chunk kernels
+    writing the row dots directly, no finalize pass), against the same rows solved alone and against the host path."""
+    B = 3
+    g = torch.Generator().manual_seed(L)
+    k = torch.tensor([[0.5], [4.0], [1.5]])
+    y0 = torch.randn(B, L, generator=g, dtype=torch.float32)
+    t = torch.tensor([0.0, 0.5, 1.0])
+    W = torch.cos(torch.arange(L, dtype=torch.float32) * 1e-3).expand(3, B, L)
+
+    def make(device, idx=None):
+        kk = (k if idx is None else k[idx]).to(device)
+        return lambda t_, y: -kk * y + 0.25 * torch.roll(y, 1, dims=1)
+    full, sg = _grad_y0(make, y0, t, W, rtol=1e-5, atol=1e-7)
+    assert torch.isfinite(full).all() and float(full.abs().max()) > 0
+    for r in range(B):
+        one, _ = _grad_y0(make, y0, t, W, idx=torch.tensor([r]), rtol=1e-5, atol=1e-7)
+        assert torch.equal(one[0], full[r])
+    cpu, sc = _grad_y0(make, y0, t, W, device="cpu", rtol=1e-5, atol=1e-7)
+    rel = _row_rel(full, cpu)
+    for r in range(B):                     # (the fp32 bound of test_hip_gradient_matches_host_path_fp32, rows with equal counts)
+        if int(sg["n_accepted"][r]) == int(sc["n_accepted"][r]) and int(sg["n_rejected"][r]) == int(sc["n_rejected"][r]):
+            assert float(rel[r]) < 1e-5, (r, float(rel[r]))
 
 
 def test_hip_second_order_is_refused():

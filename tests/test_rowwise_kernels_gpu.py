@@ -1,0 +1,584 @@
+"""Kernel parity of the four forward row entry points (tdeq_row_combine, tdeq_row_reduce, tdeq_row_control,
+tdeq_row_dense_commit) against the CPU row oracle on the same seeded inputs, at the row lengths that name every
+reduction geometry (tests/_rowwise_kernels.py).
+
+Tolerances, the project's own: elementwise outputs are the same sequence of individually rounded T operations on both
+sides and must agree BIT FOR BIT (tests/test_kernels_gpu.py); a row sum is an fp64 accumulation of n = L terms in some
+order against the correctly rounded sum, |got - ref| <= (n + 1) * 2^-53 * sum|terms| (test_row_multi_dot); the
+non-finite census is exact; a dt that went through `pow` is within 4 ulp of fp64 (the GPU's pow against libm's), and
+where it agrees bit for bit so do sign * T(dt) and the stage times (tests/test_lookahead.py)."""
+import math
+
+import numpy as np
+import pytest
+import torch
+
+from _rowwise_kernels import (BAND_NV, F64_VECTORS, I32_VECTORS, I64_VECTORS, LONG_NV, MANY_PARTIALS_NV, SENTINEL,
+                              SHORT_NV, RowVectors, ctrl_for, lane_elems, np_type, row_lengths, seeded)
+
+from oracle.kernels import OracleKernels
+
+from torchdiffeq_amd.rowwise import _METHODS
+from torchdiffeq_amd.tableaus import SparseRow, launch_plan
+
+pytestmark = pytest.mark.gpu
+
+DTYPES = [torch.float32, torch.float64]
+IDS = ["f32", "f64"]
+METHODS = sorted(_METHODS)
+NO_ERROR_ROW = 0x7FFFFFFF
+_partials = OracleKernels.row_partials         # pinned against literal numbers in tests/test_rowwise_oracle.py
+
+
+def _batches(L, dtype):
+    """Batch sizes that leave tail lanes and straddle workgroups; 3 rows where a row has several partials."""
+    return (3,) if _partials(L, dtype) > 1 else (1, 7, 300)
+
+
+def _all_lengths(dtype, many=True):
+    return row_lengths(dtype, SHORT_NV + BAND_NV + LONG_NV + (MANY_PARTIALS_NV if many else ()))
+
+
+class _Placed:
+    """CPU tensors copied into views of sentinel-filled device buffers, `offset` elements in (0: 16-byte aligned; 1: the
+    scalar fallback) and with a guard behind: `intact()` tells that nothing outside the views was written."""
+
+    def __init__(self, offset=0, guard=8):
+        self.offset, self.guard, self.bufs = offset, guard, []
+
+    def __call__(self, t):
+        n = t.numel()
+        buf = torch.full((self.offset + n + self.guard,), SENTINEL, dtype=t.dtype, device="cuda")
+        view = buf[self.offset:self.offset + n].view(t.shape)
+        view.copy_(t)
+        self.bufs.append((buf, n))
+        return view
+
+    def intact(self):
+        torch.cuda.synchronize()
+        return all(bool((b[:self.offset] == SENTINEL).all()) and bool((b[self.offset + n:] == SENTINEL).all())
+                   for b, n in self.bufs)
+
+
+def _bits_equal(a, b):
+    """Bit equality of two tensors (NaN payloads aside: NaN matches NaN)."""
+    a, b = a.cpu(), b.cpu()
+    return a.shape == b.shape and bool(((a == b) | (a.isnan() & b.isnan())).all())
+
+
+def _row_inputs(B, L, dtype, seed, n_streams):
+    """y0, the stage streams, per-row dts of both signs with an exact 0, an active mix; the stage streams of the inactive
+    rows are NaN (a finished row's func output is never read)."""
+    y0 = seeded((B, L), dtype, seed)
+    ks = [seeded((B, L), dtype, seed + 1 + j) for j in range(n_streams)]
+    g = torch.Generator().manual_seed(seed + 99)
+    dts = ((torch.rand(B, generator=g, dtype=torch.float64) - 0.4) * 0.2).to(dtype)
+    if B > 2:
+        dts[B // 2] = 0.0                   # (never row 0, and not the only row of a B = 1 batch)
+    active = (torch.rand(B, generator=g) < 0.7).to(torch.int32)
+    active[0] = 1
+    if B > 1:
+        active[B - 1] = 0
+    for k in ks:
+        k[active == 0] = float("nan")
+    return y0, ks, dts, active
+
+
+def _method_launches(name):
+    """(rows spec, stage slots, continues) of every row_combine launch of one trial step of the method."""
+    m = _METHODS[name].tableau
+    beta = m.beta_rows()
+    plan = launch_plan(name)
+    row0 = beta[0]
+    out = [(((tuple(row0.coef), (1 << len(row0.idx)) - 1, True),), tuple(row0.idx), False)]
+    out += [(op.spec, tuple(op.idx), op.continues) for op in plan.ops[1:] if op is not None]
+    return out
+
+
+def _run_combine(kern, oracle, spec, idx, continues, y0, ks, dts, active, offset=0):
+    """Both sides of one launch -> (device outputs on the CPU, oracle outputs, the guards are intact)."""
+    B, L = y0.shape
+    acc = seeded((B, L), y0.dtype, 4242) if continues else None
+    ref = [torch.full((B, L), SENTINEL, dtype=y0.dtype) for _ in spec]
+    oracle.row_combine(ref, spec, y0, acc, [ks[j] for j in idx], dts, active)
+    put = _Placed(offset)
+    outs = [put(torch.full((B, L), SENTINEL, dtype=y0.dtype)) for _ in spec]
+    kern.row_combine(outs, spec, put(y0), None if acc is None else put(acc), [put(ks[j]) for j in idx], dts.cuda(),
+                     active.cuda())
+    ok = put.intact()
+    return [o.cpu() for o in outs], ref, ok
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# tdeq_row_combine
+# ------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("dtype", DTYPES, ids=IDS)
+@pytest.mark.parametrize("method", METHODS)
+def test_row_combine_plan_ops(hip_kernels, oracle_kernels, method, dtype):
+    """Every launch of the method's plan (1-14 terms, several outputs, a carried acc_in, add_y0 set and clear) at a
+    one-lane, a grouped and a one-chunk long row length: bit for bit, inactive rows y0 / 0 whatever their streams hold."""
+    lv = lane_elems(dtype)
+    n_streams = len(_METHODS[method].tableau.beta_rows()) + 1
+    seen_terms = set()
+    for L in (5, 8 * lv, 1100 * lv):
+        y0, ks, dts, active = _row_inputs(7, L, dtype, L, n_streams)
+        for spec, idx, continues in _method_launches(method):
+            seen_terms.add(len(idx))
+            got, ref, intact = _run_combine(hip_kernels, oracle_kernels, spec, idx, continues, y0, ks, dts, active)
+            assert intact, (method, L, idx)
+            for o, (g, r) in enumerate(zip(got, ref)):
+                assert torch.equal(g, r), (method, L, idx, o)
+                inactive = active == 0
+                expect = y0[inactive] if spec[o][2] else torch.zeros_like(y0[inactive])
+                assert torch.equal(g[inactive], expect)
+    assert seen_terms
+
+
+def _synthetic_launch(nt, n_out, seed):
+    """A launch the plans do not contain: `nt` stage streams, `n_out` outputs with different masks, output 0 continuing a
+    carried acc_in, add_y0 alternating."""
+    g = np.random.default_rng(seed)
+    spec = []
+    for o in range(n_out):
+        mask = int(g.integers(1, 1 << nt)) if o else (1 << nt) - 1 - (int(g.integers(0, 1 << nt)) & ~1)
+        spec.append((tuple(float(c) for c in g.standard_normal(nt)), mask, o % 2 == 0))
+    return tuple(spec), tuple(range(nt)), True
+
+
+@pytest.mark.parametrize("dtype", DTYPES, ids=IDS)
+def test_row_combine_term_counts(hip_kernels, oracle_kernels, dtype):
+    """1 to 14 stage streams (the plans stop at 9) with 1 to 4 outputs, a carried acc_in and both add_y0 settings."""
+    plans = [x for m in METHODS for x in _method_launches(m)]
+    assert {len(idx) for _, idx, _ in plans} >= {1, 2, 3, 4, 5, 9} and max(len(spec) for spec, _, _ in plans) == 4
+    assert any(c for _, _, c in plans)
+    lv = lane_elems(dtype)
+    for nt in range(1, 15):
+        spec, idx, continues = _synthetic_launch(nt, 1 + nt % 4, nt)
+        for L in (3, 8 * lv):
+            y0, ks, dts, active = _row_inputs(7, L, dtype, nt + L, nt)
+            got, ref, intact = _run_combine(hip_kernels, oracle_kernels, spec, idx, continues, y0, ks, dts, active)
+            assert intact
+            for o in range(len(spec)):
+                assert torch.equal(got[o], ref[o]), (nt, L, o)
+
+
+@pytest.mark.parametrize("dtype", DTYPES, ids=IDS)
+def test_row_combine_lengths(hip_kernels, oracle_kernels, dtype):
+    """One launch with a carried acc_in and several outputs at every geometry class and batch size; the same launch on
+    buffers one element off 16-byte alignment (the scalar fallback) gives the bits of the aligned run."""
+    spec, idx, continues = _synthetic_launch(6, 3, 0)
+    for L in _all_lengths(dtype):
+        for B in _batches(L, dtype):
+            y0, ks, dts, active = _row_inputs(B, L, dtype, L + B, 7)
+            got, ref, intact = _run_combine(hip_kernels, oracle_kernels, spec, idx, continues, y0, ks, dts, active)
+            off, _, intact1 = _run_combine(hip_kernels, oracle_kernels, spec, idx, continues, y0, ks, dts, active,
+                                           offset=1)
+            assert intact and intact1, (L, B)
+            for o in range(len(spec)):
+                assert torch.equal(got[o], ref[o]), (L, B, o)
+                assert torch.equal(off[o], got[o]), (L, B, o)
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# tdeq_row_reduce
+# ------------------------------------------------------------------------------------------------------------------------
+RTOL_, ATOL_ = 1e-3, 1e-4
+
+
+def _reduce_case(mode, with_partial, B, L, dtype, seed):
+    """Arguments of row_reduce after `part`, on the CPU."""
+    y0, ks, dts, active = _row_inputs(B, L, dtype, seed, 3)
+    y1 = y0 + seeded((B, L), dtype, seed + 50, 0.01)
+    partial = seeded((B, L), dtype, seed + 51, 1e-3)
+    if mode == 0:
+        n = 2 if with_partial else 3
+        return [y0, y1, partial if with_partial else None, ks[:n], [0.37, -1.25, 0.0625][:n], dts, active]
+    return [y0, y1, partial, [], [], None, None]
+
+
+def _to_dev(args, put):
+    return [put(a) if isinstance(a, torch.Tensor) and a.dtype.is_floating_point else
+            a.cuda() if isinstance(a, torch.Tensor) else
+            [put(k) for k in a] if isinstance(a, list) and a and isinstance(a[0], torch.Tensor) else a for a in args]
+
+
+def _device_reduce(kern, mode, args, B, nch, offset=0):
+    put = _Placed(offset)
+    dev = _to_dev(args, put)
+    dev[5] = None if args[5] is None else args[5].cuda()        # dts, active: plain device vectors
+    dev[6] = None if args[6] is None else args[6].cuda()
+    words = 3 * B * nch
+    part = torch.full((words + 16,), SENTINEL, dtype=torch.float64, device="cuda")
+    kern.row_reduce(mode, part[:words], *dev, RTOL_, ATOL_)
+    assert put.intact()
+    part = part.cpu()
+    assert bool((part[words:] == SENTINEL).all()), "written behind 3 * B * nch words"
+    return part[:words].view(3, B, nch)
+
+
+def _check_sums(got, ref, L, what):
+    """got, ref: [3, B, nch].  Row sums within the fp64 accumulation bound of L non-negative terms, census exact."""
+    for q in (0, 1):
+        for r in range(got.shape[1]):
+            g, e = math.fsum(got[q, r].tolist()) if bool(got[q, r].isfinite().all()) else float(got[q, r].sum()), \
+                float(ref[q, r].sum())
+            if math.isfinite(e):
+                assert abs(g - e) <= (L + 1) * 2.0 ** -53 * abs(e), (what, q, r, g, e)
+            else:
+                assert (math.isnan(g) and math.isnan(e)) or g == e, (what, q, r, g, e)
+    assert torch.equal(got[2].sum(dim=1), ref[2].sum(dim=1)), what
+
+
+MODES = [(0, False), (0, True), (1, False), (2, False)]
+
+
+@pytest.mark.parametrize("dtype", DTYPES, ids=IDS)
+@pytest.mark.parametrize("mode,with_partial", MODES, ids=["err", "err_partial", "init01", "init2"])
+def test_row_reduce_sums_and_census(hip_kernels, oracle_kernels, mode, with_partial, dtype):
+    """Per row against the oracle at every geometry class and batch size, nothing written behind `part`; every row's
+    partials are those of the same row reduced alone."""
+    for L in _all_lengths(dtype):
+        nch = _partials(L, dtype)
+        assert hip_kernels.row_partials(L, dtype) == nch
+        for B in _batches(L, dtype):
+            args = _reduce_case(mode, with_partial, B, L, dtype, 7 * L + B)
+            ref = torch.zeros(3 * B * nch, dtype=torch.float64)
+            oracle_kernels.row_reduce(mode, ref, *args, RTOL_, ATOL_)
+            got = _device_reduce(hip_kernels, mode, args, B, nch)
+            _check_sums(got, ref.view(3, B, nch), L, (mode, with_partial, L, B))
+            if mode == 0:
+                inactive = args[6] == 0
+                assert bool((got[:, inactive] == 0).all()), "an inactive row reports zeros"
+            for r in sorted({0, B // 2, B - 1}):
+                alone = [a[r:r + 1].clone() if isinstance(a, torch.Tensor) else
+                         [k[r:r + 1].clone() for k in a] if isinstance(a, list) and a and isinstance(a[0], torch.Tensor)
+                         else a for a in args]
+                one = _device_reduce(hip_kernels, mode, alone, 1, nch)
+                assert _bits_equal(one[:, 0], got[:, r]), (mode, L, B, r)
+
+
+@pytest.mark.parametrize("dtype", DTYPES, ids=IDS)
+@pytest.mark.parametrize("mode,with_partial", MODES, ids=["err", "err_partial", "init01", "init2"])
+def test_row_reduce_nonfinite_rows_and_elements(hip_kernels, oracle_kernels, mode, with_partial, dtype):
+    """A row full of NaN / Inf between finite rows leaves its neighbours' words unchanged by a bit (lanes of one wave serve
+    several rows); non-finite state values planted at a row's first and last element and at the chunk edges are counted
+    exactly."""
+    lv = lane_elems(dtype)
+    for L in row_lengths(dtype, (1, 3, 5, 17, 257, 1024, 1500, 2049, 3 * 2048 + 1)):
+        B = 3 if _partials(L, dtype) > 1 else 9
+        nch = _partials(L, dtype)
+        args = _reduce_case(mode, with_partial, B, L, dtype, 11 * L)
+        if mode == 0:
+            args[6][:] = 1
+        clean = _device_reduce(hip_kernels, mode, args, B, nch)
+        mid = B // 2
+        poisoned = [a.clone() if isinstance(a, torch.Tensor) else [k.clone() for k in a] if isinstance(a, list) and a
+                    and isinstance(a[0], torch.Tensor) else a for a in args]
+        poisoned[0][mid] = float("nan")
+        poisoned[1][mid, ::2] = float("inf")
+        got = _device_reduce(hip_kernels, mode, poisoned, B, nch)
+        keep = [r for r in range(B) if r != mid]
+        assert _bits_equal(got[:, keep], clean[:, keep]), (mode, L)
+        assert float(got[2, mid].sum()) == L, (mode, L)
+        # planted values: the first and last element of a row, and both sides of every chunk edge
+        chunk = 2048 * (lv if L % lv == 0 else 1)
+        spots = sorted({0, L - 1} | {e for c in range(1, nch) for e in (c * chunk - 1, c * chunk) if e < L})
+        planted = [a.clone() if isinstance(a, torch.Tensor) else a for a in args]
+        row = B - 1
+        for n, e in enumerate(spots):
+            planted[0][row, e] = (float("nan"), float("inf"), float("-inf"))[n % 3]
+        ref = torch.zeros(3 * B * nch, dtype=torch.float64)
+        oracle_kernels.row_reduce(mode, ref, *planted, RTOL_, ATOL_)
+        got = _device_reduce(hip_kernels, mode, planted, B, nch)
+        assert float(got[2, row].sum()) == len(spots) == float(ref.view(3, B, nch)[2, row].sum()), (mode, L, spots)
+        assert _bits_equal(got[:, :row], clean[:, :row]), (mode, L)
+        assert bool((got[2, :row] == 0).all())
+
+
+@pytest.mark.parametrize("dtype", DTYPES, ids=IDS)
+def test_row_reduce_misaligned(hip_kernels, dtype):
+    """The geometry (hence the sums) must not depend on alignment: a misaligned buffer is refused when the row takes
+    16-byte elements, and a scalar-element row gives the bits of the aligned run."""
+    lv = lane_elems(dtype)
+    args = _reduce_case(0, True, 5, 4 * lv, dtype, 3)
+    with pytest.raises(RuntimeError, match="code -1"):
+        _device_reduce(hip_kernels, 0, args, 5, 1, offset=1)
+    for L in (4 * lv + 1, 1500 + (1 if 1500 % lv == 0 else 0), 2049 * lv + 1):
+        nch = _partials(L, dtype)
+        args = _reduce_case(0, True, 3, L, dtype, L)
+        assert _bits_equal(_device_reduce(hip_kernels, 0, args, 3, nch, offset=1), _device_reduce(hip_kernels, 0, args, 3, nch))
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# tdeq_row_control
+# ------------------------------------------------------------------------------------------------------------------------
+def _dyadic_part(B, nch, s0, s1, sb, seed):
+    """part[3][B * nch] whose row sums are exactly s0, s1, sb in ANY order of addition: every partial but a row's first is
+    a small multiple of 2^-10, the first holds the rest (values of at most ~2^30 that are multiples of 2^-20; a huge,
+    infinite or NaN target swallows the small ones whatever the order)."""
+    g = torch.Generator().manual_seed(seed)
+    part = torch.zeros(3, B, nch, dtype=torch.float64)
+    for q, target in enumerate((s0, s1, sb)):
+        target = torch.as_tensor(target, dtype=torch.float64)
+        if nch > 1 and q < 2:
+            small = torch.randint(0, 8, (B, nch - 1), generator=g).double() * 2.0 ** -10
+            small[target < 16] = 0.0                      # (a small target keeps all its mass in the first partial)
+            part[q, :, 1:] = small
+        if nch > 1 and q == 2:
+            part[q, :, 0] = 0.0
+            part[q, :, nch - 1] = target                  # the census arrives through the last partial
+            continue
+        part[q, :, 0] = target - part[q, :, 1:].sum(dim=1)
+    return part
+
+
+def _control_both(kern, oracle, mode, part, ctrl, dtype, B, L, tgrid, n_times, **state):
+    """Run one launch on both sides from the same state -> (device state, oracle state), each a dict of CPU tensors with
+    `dts_out` and `times_out` added."""
+    out = []
+    for dev, k in (("cuda", kern), ("cpu", oracle)):
+        rows = RowVectors(dev, B, L, tgrid, **state)
+        dts = torch.full((B,), SENTINEL, dtype=dtype, device=dev)
+        times = torch.full((n_times, B), SENTINEL, dtype=dtype, device=dev)
+        k.row_control(mode, part.reshape(-1).to(dev), ctrl, rows.st, dts, times, dtype)
+        if dev == "cuda":
+            torch.cuda.synchronize()
+        res = rows.cpu()
+        res["dts_out"], res["times_out"] = dts.cpu(), times.cpu()
+        out.append(res)
+    return out
+
+
+def _same(a, b):
+    return bool(((a == b) | (a.isnan() & b.isnan())).all()) if a.dtype.is_floating_point else torch.equal(a, b)
+
+
+def _compare_control(dev, ref, dtype, pow_rows, what, pow_rounded_to_T=False):
+    """Every RowState vector, dts_out and times_out.  `pow_rows`: rows whose new dt went through pow: within 4 ulp of
+    fp64 (a trial step's dt_next is an fp64 quantity whatever T is).  `pow_rounded_to_T` (mode 2 only, where the device
+    stores h1 = T(pow(...))): two fp64 values 4 ulp apart round to T values at most one T ulp apart."""
+    T = np_type(dtype)
+    for name in I32_VECTORS + I64_VECTORS + ("status", "t0", "tprev", "ratio", "h0", "tgrid"):
+        assert _same(dev[name], ref[name]), (what, name, dev[name].tolist(), ref[name].tolist())
+    dt_d, dt_r = dev["dt"].numpy(), ref["dt"].numpy()
+    for r in range(len(dt_r)):
+        if r in pow_rows and math.isfinite(dt_r[r]):
+            bound = 4 * np.spacing(abs(dt_r[r]))
+            if pow_rounded_to_T and T is np.float32:
+                bound = float(np.spacing(T(abs(dt_r[r]))))
+            assert abs(dt_d[r] - dt_r[r]) <= bound, (what, r, dt_d[r], dt_r[r])
+        else:
+            assert dt_d[r] == dt_r[r] or (math.isnan(dt_d[r]) and math.isnan(dt_r[r])), (what, r, dt_d[r], dt_r[r])
+        got = torch.cat([dev["dts_out"][r:r + 1], dev["times_out"][:, r]]).double().numpy()
+        exp = torch.cat([ref["dts_out"][r:r + 1], ref["times_out"][:, r]]).double().numpy()
+        if dt_d[r] == dt_r[r] or r not in pow_rows:
+            assert np.array_equal(got, exp), (what, r, got, exp)       # identical dt => identical step and stage times
+        else:
+            ulp = float(np.spacing(T(np.abs(exp).max())))
+            assert np.abs(got - exp).max() <= 2 * ulp, (what, r, got, exp)
+
+
+_RATIOS = ("zero", "under", "one", "over", "huge", "inf", "nan")
+_OUTPUTS = ("none", "one_at_t1", "three", "last")
+
+
+def _trial_rows(B, L, seed, with_errors):
+    """Per-row scenarios of a mode 0 launch, drawn per row: the error ratio, the output times the step crosses, rows that
+    are already finished, and the three error conditions alone and together."""
+    g = np.random.default_rng(seed)
+    n_out = 6
+    rows = dict(ratio=g.integers(0, len(_RATIOS), B), outs=g.integers(0, len(_OUTPUTS), B), inactive=g.random(B) < 0.15)
+    for name in ("many_steps", "no_progress", "bad"):
+        rows[name] = (g.random(B) < 0.2) if with_errors else np.zeros(B, dtype=bool)
+    s0 = np.zeros(B)
+    sb = np.zeros(B)
+    t0 = np.full(B, 0.5)
+    dt = np.full(B, 0.25)
+    tgrid = np.zeros((n_out, B))
+    next_out = np.ones(B, dtype=np.int32)
+    for r in range(B):
+        s0[r] = {"zero": 0.0, "under": L * (1 - 2.0 ** -20), "one": float(L), "over": L * (1 + 2.0 ** -20),
+                 "huge": 2.0 ** 100, "inf": math.inf, "nan": math.nan}[_RATIOS[rows["ratio"][r]]]
+        if rows["no_progress"][r]:
+            t0[r] = 2.0 ** 60                      # t0 + dt == t0 for every dt the controller can choose
+        t1 = t0[r] + dt[r]
+        kind = _OUTPUTS[rows["outs"][r]]
+        inside = {"none": 0, "one_at_t1": 1, "three": 3, "last": 2}[kind]
+        first = n_out - 2 if kind == "last" else 1
+        next_out[r] = first
+        tgrid[:first, r] = t0[r] - 1 - np.arange(first)[::-1]
+        for j in range(first, n_out):
+            n = j - first
+            if n < inside:
+                tgrid[j, r] = t1 if n == inside - 1 and kind != "three" else t0[r] + dt[r] * (n + 1) / 4
+            else:
+                tgrid[j, r] = t1 * 2 + n
+        sb[r] = 2.0 if rows["bad"][r] else 0.0
+    state = dict(t0=t0, dt=dt, tprev=np.full(B, 0.25), next_out=next_out, active=(~rows["inactive"]).astype(np.int32),
+                 since=np.where(rows["many_steps"], 9, 3), bad_y=np.zeros(B), code=np.zeros(B), n_acc=np.full(B, 4),
+                 n_rej=np.full(B, 1))
+    return s0, sb, tgrid, state, rows
+
+
+@pytest.mark.parametrize("dtype", DTYPES, ids=IDS)
+@pytest.mark.parametrize("sign", [1.0, -1.0], ids=["fwd", "bwd"])
+@pytest.mark.parametrize("L", [8, 1500, 64 * 2048 + 1, 127 * 2048 + 5],
+                         ids=["short", "one_chunk", "65_partials", "128_partials"])
+def test_row_control_trial_step(hip_kernels, oracle_kernels, L, sign, dtype):
+    """Mode 0: the ratio at and around 1, steps that cross 0, 1 and 3 output times (one equal to t1) and the last one,
+    finished rows, max_num_steps / dt underflow / non-finite y and their precedence, the two status words with errors in
+    several rows and in none — every vector of the state, bit for bit except what went through pow."""
+    tab = _METHODS["dopri5"].tableau
+    ctrl = ctrl_for(tab.alpha, 5, sign, np_type(dtype))
+    nch = _partials(L, dtype)
+    seen = dict(codes=set(), crossed=set(), finished=False, rejected=False, none_in_error=False)
+    for B in (1, 63, 64, 65, 257):
+        for with_errors in (True, False):
+            s0, sb, tgrid, state, rows = _trial_rows(B, L, 1000 * B + L, with_errors)
+            part = _dyadic_part(B, nch, s0, np.zeros(B), sb, B)
+            dev, ref = _control_both(hip_kernels, oracle_kernels, 0, part, ctrl, dtype, B, L, tgrid, ctrl.n_times,
+                                     max_num_steps=10, **state)
+            live = state["active"] != 0
+            pow_rows = {r for r in range(B) if live[r] and s0[r] != 0.0}
+            _compare_control(dev, ref, dtype, pow_rows, (L, sign, B, with_errors))
+            # what the oracle itself must have seen, so that the comparison above covers the named cases
+            acc = ref["accepted"].numpy() != 0
+            seen["codes"] |= set(ref["code"][torch.as_tensor(live) & (ref["active"] != 0)].tolist())
+            seen["crossed"] |= set((ref["out_hi"] - ref["out_lo"])[torch.as_tensor(acc)].tolist())
+            seen["finished"] |= bool((torch.as_tensor(live) & (ref["active"] == 0)).any())
+            seen["rejected"] |= bool((live & ~acc).any())
+            frozen = ref["active"] == 0
+            assert bool((ref["dts_out"][frozen] == 0).all())
+            assert torch.equal(ref["times_out"][:, frozen], (sign * ref["t0"][frozen]).to(dtype).expand(ctrl.n_times, -1))
+            first_err = [r for r in range(B) if ref["active"][r] and ref["code"][r]]
+            assert ref["status"].tolist() == [int((ref["active"] != 0).sum()), first_err[0] if first_err else NO_ERROR_ROW]
+            seen["none_in_error"] |= not first_err and not with_errors
+    assert seen["codes"] >= {0, 1, 2, 3} and seen["crossed"] >= {0, 1, 2, 3}, seen
+    assert seen["finished"] and seen["rejected"] and seen["none_in_error"], seen
+
+
+def test_row_control_error_precedence(hip_kernels, oracle_kernels):
+    """max_num_steps (2) over dt underflow (1) over non-finite y (3), one row each and every combination."""
+    dtype, L, B = torch.float64, 8, 8
+    ctrl = ctrl_for(_METHODS["dopri5"].tableau.alpha, 5, 1.0, np.float64)
+    many = np.array([r & 1 for r in range(B)], dtype=bool)
+    stuck = np.array([r & 2 for r in range(B)], dtype=bool)
+    bad = np.array([r & 4 for r in range(B)], dtype=bool)
+    part = _dyadic_part(B, 1, np.full(B, L / 4.0), np.zeros(B), np.where(bad, 1.0, 0.0), 1)
+    state = dict(t0=np.where(stuck, 2.0 ** 60, 0.5), dt=np.full(B, 0.25), tprev=np.zeros(B), next_out=np.ones(B),
+                 active=np.ones(B), since=np.where(many, 9, 0), bad_y=np.zeros(B), code=np.zeros(B), n_acc=np.zeros(B),
+                 n_rej=np.zeros(B))
+    tgrid = np.stack([np.zeros(B), np.full(B, 2.0 ** 70)])
+    dev, ref = _control_both(hip_kernels, oracle_kernels, 0, part, ctrl, dtype, B, L, tgrid, ctrl.n_times,
+                             max_num_steps=10, **state)
+    expect = [2 if many[r] else 1 if stuck[r] else 3 if bad[r] else 0 for r in range(B)]
+    assert ref["code"].tolist() == expect and dev["code"].tolist() == expect
+    assert dev["status"].tolist() == [B, 1]
+
+
+@pytest.mark.parametrize("dtype", DTYPES, ids=IDS)
+@pytest.mark.parametrize("sign", [1.0, -1.0], ids=["fwd", "bwd"])
+@pytest.mark.parametrize("order", [1, 4], ids=["sqrt", "pow"])
+@pytest.mark.parametrize("L", [8, 64 * 2048 + 1, 127 * 2048 + 5], ids=["short", "65_partials", "128_partials"])
+def test_row_control_initial_step(hip_kernels, oracle_kernels, L, order, sign, dtype):
+    """Modes 1, 2 and 3: the d0 / d1 < 1e-5 and the d1, d2 <= 1e-15 branches next to the ordinary ones, the square-root
+    path of an order-2 pair (exact) and pow (4 ulp), then the first trial step's set-up."""
+    tab = _METHODS["adaptive_heun" if order == 1 else "dopri5"].tableau
+    ctrl = ctrl_for(tab.alpha, order + 1, sign, np_type(dtype))
+    nch = _partials(L, dtype)
+    B = 65
+    r = np.arange(B)
+    # mode 1: rows cycle through d0 tiny, d1 tiny (exactly 0), both ordinary; every fourth row has non-finite y
+    s0 = np.where(r % 3 == 0, 0.0, L * 4.0 ** (r % 5))
+    s1 = np.where(r % 3 == 1, 0.0, L * 16.0 * 4.0 ** (r % 7))
+    sb = np.where(r % 4 == 3, 1.0, 0.0)
+    tgrid = np.stack([np.full(B, 0.25), np.full(B, 4.0)])
+    state = dict(t0=np.full(B, 0.25), active=np.ones(B), since=np.zeros(B), next_out=np.ones(B))
+    dev1, ref1 = _control_both(hip_kernels, oracle_kernels, 1, _dyadic_part(B, nch, s0, s1, sb, 1), ctrl, dtype, B, L,
+                               tgrid, ctrl.n_times, order=order, **state)
+    # (mode 1 writes dts_out and row 0 of times_out only; the rest keeps the filler on both sides)
+    _compare_control(dev1, ref1, dtype, set(), ("mode 1", L, order, sign))
+    assert dev1["status"].tolist() == [B, NO_ERROR_ROW]
+    # mode 2 from the oracle's mode 1 state: d2 exactly 0 on the rows whose d1 is 0 (both <= 1e-15), ordinary elsewhere
+    carried = {n: ref1[n] for n in F64_VECTORS + I32_VECTORS + I64_VECTORS}
+    s2 = np.where(r % 3 == 1, 0.0, L * 4.0 ** (r % 4) * 2.0 ** -20)
+    dev2, ref2 = _control_both(hip_kernels, oracle_kernels, 2, _dyadic_part(B, nch, s2, np.zeros(B), np.zeros(B), 2), ctrl,
+                               dtype, B, L, tgrid, ctrl.n_times, order=order, **carried)
+    pow_rows = set() if order == 1 else {int(i) for i in r if i % 3 != 1}
+    _compare_control(dev2, ref2, dtype, pow_rows, ("mode 2", L, order, sign), pow_rounded_to_T=True)
+    assert set(ref2["code"].tolist()) == {0, 3}
+    # mode 3: dt given
+    given = dict(state, dt=2.0 ** -(r % 9 + 1.0), bad_y=np.zeros(B), code=np.zeros(B))
+    dev3, ref3 = _control_both(hip_kernels, oracle_kernels, 3, _dyadic_part(B, nch, s0, s1, sb, 3), ctrl, dtype, B, L,
+                               tgrid, ctrl.n_times, order=order, **given)
+    _compare_control(dev3, ref3, dtype, set(), ("mode 3", L, order, sign))
+    assert ref3["bad_y"].tolist() == [int(x) for x in sb]
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# tdeq_row_dense_commit
+# ------------------------------------------------------------------------------------------------------------------------
+def _dense_rows(B, seed):
+    """Per row: not accepted, or accepted with 0, 1 (x = 1: the output time is the step's end) or 3 output times."""
+    g = np.random.default_rng(seed)
+    kind = g.integers(0, 4, B)
+    if B >= 4:
+        kind[:4] = (0, 1, 2, 3)
+    n_out = 6
+    tprev, t1 = 0.25 + 0.125 * g.random(B), 0.75 + 0.125 * g.random(B)
+    tgrid = np.zeros((n_out, B))
+    lo = g.integers(1, 3, B)
+    hi = lo + np.array([0, 0, 1, 3])[kind]
+    for r in range(B):
+        tgrid[:, r] = t1[r] + 1 + np.arange(n_out)
+        tgrid[:lo[r], r] = tprev[r] - 1
+        for j in range(lo[r], hi[r]):
+            tgrid[j, r] = t1[r] if j == hi[r] - 1 and kind[r] == 2 else tprev[r] + (t1[r] - tprev[r]) * (j - lo[r] + 1) / 4
+    state = dict(tprev=tprev, t0=t1, accepted=(kind > 0).astype(np.int32), out_lo=lo, out_hi=hi)
+    return tgrid, state, n_out
+
+
+def _run_dense(kern, oracle, B, L, dtype, mid, seed, offset=0):
+    tgrid, state, n_out = _dense_rows(B, seed)
+    n_streams = max(mid.idx) + 1
+    y0, y1, f0, f1 = (seeded((B, L), dtype, seed + j) for j in range(4))
+    ks = [seeded((B, L), dtype, seed + 10 + j) for j in range(n_streams)]
+    dts = seeded((B,), dtype, seed + 30, 0.1)
+    sol = torch.full((n_out, B, L), SENTINEL, dtype=dtype)
+    res = []
+    for dev, k in (("cuda", kern), ("cpu", oracle)):
+        rows = RowVectors(dev, B, L, tgrid, **state)
+        put = _Placed(offset) if dev == "cuda" else (lambda t: t.clone())
+        s, a, b = put(sol), put(y0), put(f0)
+        k.row_dense_commit(s, a, put(y1), b, put(f1), [put(ks[j]) for j in mid.idx], mid.coef, dts.to(dev), rows.st)
+        if dev == "cuda":
+            assert put.intact()
+        res.append((s.cpu(), a.cpu(), b.cpu()))
+    return res, (y0, y1, f0, f1), state
+
+
+@pytest.mark.parametrize("dtype", DTYPES, ids=IDS)
+def test_row_dense_commit(hip_kernels, oracle_kernels, dtype):
+    """Rows accepted with 0, 1 and 3 output times and rows not accepted: the oracle's quartic bit for bit, y0 <- y1 and
+    f0 <- f1 exactly for the accepted rows, every other word (rows, solution slots, the guards) untouched; c_mid of all
+    six methods; 16-byte and scalar L; buffers one element off alignment equal to the aligned run."""
+    lv = lane_elems(dtype)
+    cases = [(m, L, B) for m in METHODS for L, B in ((5, 7), (8 * lv, 7))]
+    cases += [("dopri5", L, B) for L in row_lengths(dtype, (1, 3, 17, 257, 1024, 1500, 2049)) for B in _batches(L, dtype)]
+    for method, L, B in cases:
+        mid = SparseRow.from_dense(_METHODS[method].tableau.c_mid)
+        (dev, ref), (y0, y1, f0, f1), state = _run_dense(hip_kernels, oracle_kernels, B, L, dtype, mid, L + B)
+        for name, g, e in zip(("sol", "y0", "f0"), dev, ref):
+            assert torch.equal(g, e), (method, L, B, name)
+        acc = torch.as_tensor(state["accepted"] != 0)
+        sol, ny0, nf0 = dev
+        assert torch.equal(ny0[acc], y1[acc]) and torch.equal(nf0[acc], f1[acc])
+        assert torch.equal(ny0[~acc], y0[~acc]) and torch.equal(nf0[~acc], f0[~acc])
+        for r in range(B):
+            lo, hi = (int(state["out_lo"][r]), int(state["out_hi"][r])) if acc[r] else (0, 0)
+            outside = [j for j in range(sol.shape[0]) if not lo <= j < hi]
+            assert bool((sol[outside, r] == SENTINEL).all()), (method, L, B, r)
+            assert bool((sol[lo:hi, r] != SENTINEL).all())
+        (off, _), _, _ = _run_dense(hip_kernels, oracle_kernels, B, L, dtype, mid, L + B, offset=1)
+        for g, e in zip(off, dev):
+            assert torch.equal(g, e), (method, L, B, "one element off")

@@ -18,7 +18,7 @@ inline int row_lanes(int64_t row_len, int dtype) {
 struct RowGeom {
     int lv;           // T elements per E element
     int64_t nv;       // E elements per row
-    int group;        // short rows: lanes per row
+    int group;        // short rows: lanes per row; 0 = long row (one workgroup per chunk, also when nch == 1)
     int64_t chunk;    // long rows: E elements per workgroup
     int64_t nch;      // partials per row
 };
@@ -95,8 +95,8 @@ int row_combine_dispatch(const tdeq_multi_out* outs, int n_out, const void* y0, 
 
 template <typename T, int NT, int MODE, bool PARTIAL>
 int row_reduce_launch(RowRedArgs<T, NT>& a, const RowGeom& g, bool vec, hipStream_t s) {
-    if (g.nch == 1) {
-        const int64_t threads = a.n_rows * g.group;
+    if (g.group > 0) {                // short row; a long row of one chunk (1024 < nv <= 2048) takes the chunk kernel,
+        const int64_t threads = a.n_rows * g.group;      // whose part[q * B + r] is what the lane-per-row controller reads
         const dim3 grid((unsigned)((threads + kBlock - 1) / kBlock));
         a.group = g.group;
         a.nch = 1;
@@ -382,7 +382,7 @@ int row_dot_n(const void* g, const void* const* x, int64_t n_rows, int64_t row_l
     a.chunk = geo.chunk;
     a.nch = (int)geo.nch;
     a.group = geo.group;
-    if (geo.nch == 1) {
+    if (geo.group > 0) {
         a.out = out;
         const int64_t threads = n_rows * geo.group;
         const dim3 grid((unsigned)((threads + kBlock - 1) / kBlock));
@@ -390,12 +390,12 @@ int row_dot_n(const void* g, const void* const* x, int64_t n_rows, int64_t row_l
         else hipLaunchKernelGGL((row_dot_wave_kernel<T, NT, false>), grid, dim3(kBlock), 0, s, a);
         return check_launch();
     }
-    a.out = ws;
+    a.out = geo.nch == 1 ? out : ws;                 // one chunk per row: the chunk sums are the results, [NT, B]
     const dim3 grid((unsigned)(n_rows * geo.nch));
     if (vec) hipLaunchKernelGGL((row_dot_chunk_kernel<T, NT, true>), grid, dim3(kBlock), 0, s, a);
     else hipLaunchKernelGGL((row_dot_chunk_kernel<T, NT, false>), grid, dim3(kBlock), 0, s, a);
     const int e = check_launch();
-    if (e) return e;
+    if (e || geo.nch == 1) return e;
     RowDotFinalizeArgs f;
     f.part = ws;
     f.nch = (int)geo.nch;

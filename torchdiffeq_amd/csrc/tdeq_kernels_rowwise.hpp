@@ -17,7 +17,9 @@
 //                                                      elements in order, then a butterfly over the G lanes
 //   long rows:                                         nch chunks of `chunk` elements per row, one workgroup per
 //                                                      (row, chunk) -> fp64 partial; the controller adds a row's
-//                                                      partials with one wave in a fixed order
+//                                                      partials with one wave in a fixed order.  A long row of ONE
+//                                                      chunk (kRowWaveMax < nv <= chunk) takes the same chunk kernels;
+//                                                      its single partial sits where a short row's does
 #pragma once
 
 #include "tdeq_kernels.hpp"
@@ -115,7 +117,7 @@ struct RowRedArgs {
     int64_t row_len;                  // in E units
     int64_t n_rows;
     int64_t chunk;                    // long rows: E units per workgroup
-    int nch;                          // chunks per row (1 for short rows)
+    int nch;                          // chunks per row (1 for short rows and for long rows of one chunk)
     int group;                        // short rows: lanes per row (power of two <= 64)
     double* part;
 };
@@ -537,9 +539,9 @@ struct RowDotArgs {
     int64_t row_len;                  // in E units
     int64_t n_rows;
     int64_t chunk;                    // long rows: E units per workgroup
-    int nch;                          // chunks per row (1 for short rows)
+    int nch;                          // chunks per row (1 for short rows and for long rows of one chunk)
     int group;                        // short rows: lanes per row (power of two <= 64)
-    double* out;                      // short rows: [NT, B] results; long rows: [NT, B * nch] partials
+    double* out;                      // nch == 1: [NT, B] results; else [NT, B * nch] partials
 };
 
 template <typename T, int NT, typename E>
