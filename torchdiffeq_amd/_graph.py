@@ -818,62 +818,53 @@ class _GraphStep:
         return total + need <= budget
 
     def body(self, s, side: int) -> None:
+        """The launches of one trial step from side `side`'s pair, captured or run eagerly: ONE loop over the step's launch
+        plan, step size and stage times read from device memory; y1 and the partial error go to the static buffers."""
         func, kern, plan = s.func, s.kernels, s.plan
-        beta, fuse, fsal = s._beta, s._fuse, s.tableau.fsal_solution
-        # the launches of the step: the carry plan (tableaus.carry_plan; needs the multi-output launch that reads the step
-        # size on the device), else row by row with the end-of-step fusion, as a plan too (RKAdaptive..._row_plan)
-        carry = s._carry if s._carry is not None and hasattr(kern, "stage_combine_multi_dev") else s._row_plan
+        # the plan: carried sums (tableaus.carry_plan; needs the multi-output launch that reads the step size on the
+        # device), else row by row with the end-of-step fusion, else — 16-bit states (csrc/tdeq_kernels_lp.hpp), fehlberg2 —
+        # every row and the error row whole: a reduced-precision row sum is rounded once, so there is nothing to hand from
+        # the last combine to the norm launch
+        launches = s._carry if s._carry is not None and hasattr(kern, "stage_combine_multi_dev") else s._row_plan
+        launches = launches or s._whole_plan
         y_cur, f_cur, y1, epart = self.y[side], self.f_in(side), self.y[1 - side], self.epart[side]
         k = [f_cur]
         yi = torch.empty_like(y_cur)
-        kern.stage_combine_dev(yi, None, y_cur, [f_cur], beta[0].coef, None, plan)
+        kern.stage_combine_dev(yi, None, y_cur, [f_cur], s._beta[0].coef, None, plan)
         k.append(func.eval_at(self.ts[0], yi))
-        n_rows = len(beta)
-        if carry is not None:
-            held, R = {}, len(carry.ops)
-            for i in range(1, R):
-                op = carry.ops[i]
-                row = beta[i] if i < n_rows else s._c_sol
-                if op is None:
-                    yi = held.pop(i)
-                elif len(op.targets) == 1 and not op.continues:
-                    yi = y1 if i == R - 1 else torch.empty_like(y_cur)
-                    kern.stage_combine_dev(yi, None, y_cur, [k[j] for j in row.idx], row.coef, None, plan)
-                elif op.targets == (i, R) and i == R - 1 and not op.continues and op.idx == row.idx:
-                    yi, held[R] = y1, epart
-                    kern.stage_combine_dev(yi, epart, y_cur, [k[j] for j in row.idx], row.coef, fuse[0], plan)
-                else:
-                    # the step's solution (launch row R - 1) and the partial error go to the static buffers
-                    outs = [y1 if t == R - 1 else (epart if t == R else torch.empty_like(y_cur)) for t in op.targets]
-                    kern.stage_combine_multi_dev(outs, op.spec, y_cur, held.pop(i) if op.continues else None,
-                                                 [k[j] for j in op.idx], plan)
-                    yi = outs[0]
-                    for tgt, buf in zip(op.targets[1:], outs[1:]):
-                        held[tgt] = buf
-                if i < n_rows:
-                    k.append(func.eval_at(self.ts[i], yi))
+        rows, n_rows, R, held = s._launch_rows, len(s._beta), len(launches.ops), {}
+        for i in range(1, R):
+            op, row = launches.ops[i], rows[i]
+            if op is None:
+                yi = held.pop(i)
+            elif op.form == "whole":
+                yi = y1 if i == R - 1 else torch.empty_like(y_cur)
+                kern.stage_combine_dev(yi, None, y_cur, [k[j] for j in row.idx], row.coef, None, plan)
+            elif op.form == "pair":
+                yi, held[R] = y1, epart
+                kern.stage_combine_dev(yi, epart, y_cur, [k[j] for j in row.idx], row.coef, s._fuse[0], plan)
+            else:
+                # the step's solution (launch row R - 1) and the partial error go to the static buffers
+                outs = [y1 if t == R - 1 else (epart if t == R else torch.empty_like(y_cur)) for t in op.targets]
+                kern.stage_combine_multi_dev(outs, op.spec, y_cur, held.pop(i) if op.continues else None,
+                                             [k[j] for j in op.idx], plan)
+                yi = outs[0]
+                for tgt, buf in zip(op.targets[1:], outs[1:]):
+                    held[tgt] = buf
+            if i < n_rows:
+                k.append(func.eval_at(self.ts[i], yi))
+        ks = [k[j] for j in launches.err_idx]
+        if R in held:
             assert held.pop(R) is epart and not held
             # side 0 reads its derivative from a buffer of its own (see the class text): side 1's last evaluation goes there —
             # written by the norm launch itself where that launch reads the stream anyway (r06), else by a copy node
-            if not self._norm_ctrl(s, epart, y_cur, y1, [k[j] for j in carry.err_idx], carry.err_coef,
-                                   self.f0 if side == 1 and carry.err_idx and carry.err_idx[-1] == len(k) - 1 else None) \
-                    and side == 1:
-                self.f0.copy_(k[-1])
-            self.k[side] = k
-            return
-        # no partial error: 16-bit states (csrc/tdeq_kernels_lp.hpp) — every row whole and the error row whole: a reduced-
-        # precision row sum is rounded once, so there is nothing to hand from the last combine to the norm launch
-        for i in range(1, n_rows):
-            row = beta[i]
-            yi = y1 if (i == n_rows - 1 and fsal) else torch.empty_like(y_cur)
-            kern.stage_combine_dev(yi, None, y_cur, [k[j] for j in row.idx], row.coef, None, plan)
-            k.append(func.eval_at(self.ts[i], yi))
-        if not fsal:
-            kern.stage_combine_dev(y1, None, y_cur, [k[j] for j in s._c_sol.idx], s._c_sol.coef, None, plan)
-        err = s._c_err
-        kern.error_norm_ctrl(plan, y_cur, y1, [k[j] for j in err.idx], err.coef, 0.0, s._ctrl, self.tbuf,
-                             state_in_dev=True)
-        if side == 1:
+            last_too = side == 1 and launches.err_idx and launches.err_idx[-1] == len(k) - 1
+            copied = self._norm_ctrl(s, epart, y_cur, y1, ks, launches.err_coef, self.f0 if last_too else None)
+        else:
+            assert not held
+            kern.error_norm_ctrl(plan, y_cur, y1, ks, launches.err_coef, 0.0, s._ctrl, self.tbuf, state_in_dev=True)
+            copied = False
+        if side == 1 and not copied:
             self.f0.copy_(k[-1])
         self.k[side] = k
 

@@ -141,9 +141,10 @@ class _DenseRecord:
     """Data of the last accepted step, kept for lazy dense output (rk_common.py:363-369)."""
     __slots__ = ("y0", "y1", "k", "dt_signed", "t0", "t1", "dt_shadow", "anchor")
 
-    def __init__(self):
-        self.dt_shadow = None     # graph of the step size (only the first step's, see _initial_step_shadow)
-        self.anchor = None        # time anchor (graph of the step's start time) when the step was taken
+    def __init__(self, y0, y1, k, dt_signed, t0, t1, dt_shadow=None, anchor=None):
+        self.y0, self.y1, self.k, self.dt_signed, self.t0, self.t1 = y0, y1, k, dt_signed, t0, t1
+        self.dt_shadow = dt_shadow     # graph of the step size (only the first step's, see _initial_step_shadow)
+        self.anchor = anchor           # time anchor (graph of the step's start time) when the step was taken
 
 
 class RKAdaptiveStepsizeODESolver(AdaptiveEvents):
@@ -258,13 +259,16 @@ class RKAdaptiveStepsizeODESolver(AdaptiveEvents):
                 and (carry_env == "1" or self.layout.total >= CARRY_DEFAULT_ON.get(tab.name, float("inf"))) \
                 and hasattr(self.kernels, "stage_combine_multi") and ADAPTIVE_TABLEAUS.get(tab.name) is tab:
             self._carry = carry_plan(tab.name)
-        # The row-by-row launches with the end-of-step fusion as a plan too (tableaus.row_by_row_plan), from this solver's
-        # own rows (any `Tableau`, not only the shipped ones): what a captured step interprets where it has no carry plan.
-        # None without the fusion, and for a one-launch step, which has no combine to host the partial error.
+        # The row-by-row launches as plans too (tableaus.row_by_row_plan), from this solver's own rows (any `Tableau`, not
+        # only the shipped ones), so that a trial step — eager or captured — always interprets ONE plan: `_row_plan` with
+        # the end-of-step fusion (None without it, and for a one-launch step, which has no combine to host the partial
+        # error), `_whole_plan` with every row and the error row whole (no `_fuse`, the torch-op host path, 16-bit
+        # states, and any step that is recorded for autograd or goes to a user norm).
         self._row_plan = None
-        launch_rows = self._beta + ([] if tab.fsal_solution else [self._c_sol])
-        if self._fuse is not None and len(launch_rows) > 1:
-            self._row_plan = row_by_row_plan(launch_rows, self._c_err, n_lead)
+        self._launch_rows = self._beta + ([] if tab.fsal_solution else [self._c_sol])
+        self._whole_plan = row_by_row_plan(self._launch_rows, self._c_err, 0)
+        if self._fuse is not None and len(self._launch_rows) > 1:
+            self._row_plan = row_by_row_plan(self._launch_rows, self._c_err, n_lead)
             assert (self._row_plan.err_idx, self._row_plan.err_coef) == self._fuse[1:]
         self.n_accepted = 0
         self.n_rejected = 0
@@ -719,30 +723,63 @@ class RKAdaptiveStepsizeODESolver(AdaptiveEvents):
         return self.ops.dense_eval(rec.y0, rec.y1, rec.k, mid.idx, mid.coef, rec.dt_signed, x,
                                    dt_shadow=rec.dt_shadow, x_shadow=x_shadow, out=out)
 
+    # -- one trial step: begin, stages, error ratio, commit ------------------------------------------------
     def _adaptive_step(self) -> None:
         """One trial step (rk_common.py:266-361)."""
-        func, kern, T = self.func, self.kernels, self.np_dtype
-        y0, f0, t0, dt = self.y1, self.f1, self.t1, self.dt
+        func = self.func
+        y0, f0 = self.y1, self.f1
+        t0, dt, t1 = self._begin_step()
+        dt, t1, on_step_t, on_jump_t = self._clip_step(t0, dt, t1)
+        plain = not (torch.is_grad_enabled() and (y0.requires_grad or f0.requires_grad or self._anchor is not None))
+        dsh, dsh_signed = self._step_shadow(plain, on_step_t or on_jump_t)
+        dt_signed = float(self.np_dtype(dt)) * func.sign      # the stages' step size: in the state precision T
+        lookahead = (self._lookahead and plain and func.callback_step is _null
+                     and func.callback_accept_step is _null and func.callback_reject_step is _null)
+        y1, k, err_partial, err_rem = self._stages(y0, f0, t0, dt, t1, dt_signed, dsh, dsh_signed, plain, lookahead)
+        error_ratio, y1_nonfinite, decided = self._error_ratio(y0, f0, y1, k, err_partial, err_rem, t0, dt, t1,
+                                                               dt_signed, lookahead)
+        if decided is not None:
+            # the device's decision is the one its look-ahead stage was built on; its step size is already clamped
+            accept_step, dt_next = decided
+        else:
+            # rk_common.py:324-332: a step at the floor is always taken, one above the ceiling never, else the error decides
+            accept_step = bool(dt <= self.min_step or (error_ratio <= 1 and not dt > self.max_step))
+            if self._wide:
+                dt_next = optimal_step_size(dt, error_ratio, self.safety, self.ifactor, self.dfactor, self.order)
+            else:
+                dt_next = optimal_step_size_in(self._W, dt, error_ratio, self.safety, self.ifactor, self.dfactor,
+                                               self.order)
+            dt_next = _clamp(dt_next, self.min_step, self.max_step)
+        self._commit(accept_step, dt_next, y0, y1, k, t0, dt, t1, dt_signed, dsh, dsh_signed, on_step_t, on_jump_t,
+                     y1_nonfinite)
+
+    def _begin_step(self):
+        """(t0, dt, t1) of the trial step about to be taken from (self.t1, self.dt): the step size clamped, the step
+        callback, the underflow and non-finite assertions (rk_common.py:266-287)."""
+        t0, dt = self.t1, self.dt
         if not math.isfinite(dt):
             dt = self.min_step
         if self._dt_shadow is not None and not self.min_step <= dt <= self.max_step:
             self._dt_shadow = None          # `dt.clamp(min_step, max_step)` (rk_common.py:271): a constant outside the range
         dt = _clamp(dt, self.min_step, self.max_step)
-        if func.callback_step is not _null:
-            func.callback_step(self._time_tensor(t0), y0, self._time_tensor(dt))
-        w = self._w
-        t1 = w(t0 + dt)
+        if self.func.callback_step is not _null:
+            self.func.callback_step(self._time_tensor(t0), self.y1, self._time_tensor(dt))
+        t1 = self._w(t0 + dt)
         assert t1 > t0, "underflow in dt {}".format(dt)
-        assert not self._y_nonfinite, "non-finite values in state `y`: {}".format(self._unpadded(y0))
+        assert not self._y_nonfinite, "non-finite values in state `y`: {}".format(self._unpadded(self.y1))
+        return t0, dt, t1
 
-        on_step_t = False
+    def _clip_step(self, t0: float, dt: float, t1: float):
+        """The step cut short at the next `step_t` / `jump_t` point inside it (rk_common.py:289-309):
+        (dt, t1, on_step_t, on_jump_t)."""
+        w = self._w
+        on_step_t = on_jump_t = False
         if len(self._step_t):
             next_step_t = self._step_t[self.next_step_index]
             on_step_t = t0 < next_step_t < w(t0 + dt)
             if on_step_t:
                 t1 = next_step_t
                 dt = w(t1 - t0)
-        on_jump_t = False
         if len(self._jump_t):
             next_jump_t = self._jump_t[self.next_jump_index]
             on_jump_t = t0 < next_jump_t < w(t0 + dt)
@@ -750,17 +787,13 @@ class RKAdaptiveStepsizeODESolver(AdaptiveEvents):
                 on_step_t = False
                 t1 = next_jump_t
                 dt = w(t1 - t0)
+        return dt, t1, on_step_t, on_jump_t
 
-        # ---- Runge–Kutta stages (rk_common.py:43-90); times in the state precision T ----
-        t0_T, dt_T, t1_T = T(t0), T(dt), T(t1)
-        dt_signed = float(dt_T) * func.sign
-        ops = self.ops
-        row0 = self._beta[0]
-        plain = not (torch.is_grad_enabled() and (y0.requires_grad or f0.requires_grad or self._anchor is not None))
-        # graph of this trial's step size: the first, heuristic one has one (the controller is under no_grad) — and a
-        # step cut short at a `step_t` / `jump_t` point: dt = t_point - t0 (rk_common.py:296-309) moves AGAINST whatever t0
-        # moves with (the first step size, t[0] when `t` requires grad), and t1 = t_point with nothing any more
-        clipped = on_step_t or on_jump_t
+    def _step_shadow(self, plain: bool, clipped: bool):
+        """(dsh, dsh * sign): the autograd graph of this trial's step size, or None.  The first, heuristic one has one (the
+        controller is under no_grad) — and a step cut short at a `step_t` / `jump_t` point: dt = t_point - t0
+        (rk_common.py:296-309) moves AGAINST whatever t0 moves with (the first step size, t[0] when `t` requires grad),
+        and t1 = t_point with nothing any more."""
         if plain:
             dsh = None
         elif clipped:
@@ -768,194 +801,178 @@ class RKAdaptiveStepsizeODESolver(AdaptiveEvents):
         else:
             dsh = self._dt_shadow
         self._dt_shadow = None
-        dsh_signed = None if dsh is None else dsh * func.sign
-        lookahead = (self._lookahead and plain and func.callback_step is _null
-                     and func.callback_accept_step is _null and func.callback_reject_step is _null)
+        return dsh, (None if dsh is None else dsh * self.func.sign)
+
+    def _partial_norm(self):
+        """(the norm is the built-in one, per-element tolerances on the fused vector-tolerance kernel).  Either is a norm
+        LAUNCH that can continue the partial error row of the step's last combine (tdeq_error_norm_vec's `err_partial`:
+        the same launch sequence, the tolerance vectors are the only extra streams)."""
+        builtin_norm = isinstance(self.norm, BuiltinNorm)
+        return builtin_norm, (self._vec_fused is not None and not builtin_norm
+                              and getattr(self.kernels, "vec_partial", False))
+
+    def _first_stage(self, y0, f0, t0, dt, t1, dt_signed, dsh, dsh_signed, plain):
+        """(first stage input, the step's stage times, k_1) of a step whose first stage was not enqueued ahead; times in
+        the state precision T (rk_common.py:43-90)."""
+        func, kern, T = self.func, self.kernels, self.np_dtype
+        t0_T, dt_T, t1_T = T(t0), T(dt), T(t1)
+        row0 = self._beta[0]
+        times = [(t1_T, Perturb.PREV) if self._alpha_is_one[i] else (t0_T + self._alpha[i] * dt_T, Perturb.NONE)
+                 for i in range(len(self._beta))]
+        if len(times) <= 16 and plain:
+            # one launch: first stage input + the step's stage times (tdeq_stage_combine_fill)
+            yi = torch.empty_like(y0)
+            tbuf = torch.empty(len(times), dtype=func.time_dtype, device=y0.device)
+            kern.stage_combine_fill(yi, y0, [f0], row0.coef, dt_signed, tbuf, [func.user_time(t, p) for t, p in times])
+            stage_times = tbuf.unbind(0)
+        else:
+            yi = self.ops.combine(y0, [f0], row0.coef, dt_signed, dsh_signed)
+            shadows = None
+            if dsh is not None:
+                # t_i = t0 + alpha_i dt0 (t1 = t0 + dt0 for alpha_i = 1), in user time
+                base = self._anchor
+                shadows = []
+                for i in range(len(self._beta)):
+                    inc = dsh if self._alpha_is_one[i] else float(self._alpha[i]) * dsh
+                    shadows.append((inc if base is None else base + inc) * func.sign)
+            stage_times = func.time_tensors(kern, times, shadows=shadows)
+        return yi, stage_times, func.eval_at(stage_times[0], yi)
+
+    def _stages(self, y0, f0, t0, dt, t1, dt_signed, dsh, dsh_signed, plain, lookahead):
+        """The Runge–Kutta stages (rk_common.py:43-90) as ONE loop over the launch plan of this step: (y1, k, err_partial,
+        err_rem) with `err_partial` the part of the embedded error the plan's launches already summed (None: nothing) and
+        `err_rem` = (stages, weights) left to the norm launch.  Every stage input is bit-identical under every plan."""
+        func, kern = self.func, self.kernels
         pre, self._pre = self._pre, None
         if lookahead and pre is not None:
             # this trial step's first stage was enqueued by the previous one (tdeq_stage_combine_sel on the pair and
             # the step size the device controller chose) together with its func evaluation
             yi, stage_times, k1 = pre
         else:
-            times = [(t1_T, Perturb.PREV) if self._alpha_is_one[i] else (t0_T + self._alpha[i] * dt_T, Perturb.NONE)
-                     for i in range(len(self._beta))]
-            if len(times) <= 16 and plain:
-                # one launch: first stage input + the step's stage times (tdeq_stage_combine_fill)
-                yi = torch.empty_like(y0)
-                tbuf = torch.empty(len(times), dtype=func.time_dtype, device=y0.device)
-                kern.stage_combine_fill(yi, y0, [f0], row0.coef, dt_signed, tbuf,
-                                        [func.user_time(t, p) for t, p in times])
-                stage_times = tbuf.unbind(0)
-            else:
-                yi = ops.combine(y0, [f0], row0.coef, dt_signed, dsh_signed)
-                shadows = None
-                if dsh is not None:
-                    # t_i = t0 + alpha_i dt0 (t1 = t0 + dt0 for alpha_i = 1), in user time
-                    base = self._anchor
-                    shadows = []
-                    for i in range(len(self._beta)):
-                        inc = dsh if self._alpha_is_one[i] else float(self._alpha[i]) * dsh
-                        shadows.append((inc if base is None else base + inc) * func.sign)
-                stage_times = func.time_tensors(kern, times, shadows=shadows)
-            k1 = func.eval_at(stage_times[0], yi)
-        k: List[torch.Tensor] = [f0, k1]
-        n_rows = len(self._beta)
-        fsal = self.tableau.fsal_solution
-        builtin_norm = isinstance(self.norm, BuiltinNorm)
-        # a norm LAUNCH that can continue the partial error row of the step's last combine: the built-in norm, and per-element
-        # tolerances on the fused vector-tolerance kernel (tdeq_error_norm_vec's `err_partial`) — same launch sequence, the
-        # tolerance vectors are the only extra streams
-        vec_fused = self._vec_fused is not None and not builtin_norm and getattr(kern, "vec_partial", False)
-        fused_norm = builtin_norm or vec_fused
-        err_partial = None
-        err_rem = self._fuse[1:] if self._fuse is not None else None     # (stages, weights) left to the norm kernel
+            yi, stage_times, k1 = self._first_stage(y0, f0, t0, dt, t1, dt_signed, dsh, dsh_signed, plain)
+        fused_norm = any(self._partial_norm())
         nograd = not torch.is_grad_enabled()      # no-grad solves (the adjoint's two solves, inference): no graph checks
-        carry = self._carry if (fused_norm and (nograd or (plain and not k1.requires_grad))) else None
-        y1_planned = None
-        if carry is not None:
-            # planned launches (tableaus.carry_plan): a launch may also emit the left-to-right prefixes of later rows'
-            # sums (continued by those rows: fewer bytes) or a later stage input that needs no newer stage; launch row
-            # n_rows of a pair whose solution is not its last stage input is the c_sol combine (no evaluation follows).
-            # Every stage input is bit-identical to the row-by-row launches below.
-            held, R = {}, len(carry.ops)
-            for i in range(1, R):
-                op = carry.ops[i]
-                row = self._beta[i] if i < n_rows else self._c_sol
-                if op is None:
-                    yi = held.pop(i)                      # finished by an earlier launch
-                elif len(op.targets) == 1 and not op.continues:
-                    yi = torch.empty_like(y0)
-                    kern.stage_combine(yi, y0, [k[j] for j in row.idx], row.coef, dt_signed)
-                elif op.targets == (i, R) and i == R - 1 and not op.continues and op.idx == row.idx:
-                    yi, held[R] = torch.empty_like(y0), torch.empty_like(y0)      # the end-of-step pair as before
-                    kern.stage_combine_err(yi, held[R], y0, [k[j] for j in row.idx], row.coef, self._fuse[0], dt_signed)
-                else:
-                    outs = [torch.empty_like(y0) for _ in op.targets]
-                    kern.stage_combine_multi(outs, op.spec, y0, held.pop(i) if op.continues else None,
-                                             [k[j] for j in op.idx], dt_signed)
-                    yi = outs[0]
-                    for tgt, buf in zip(op.targets[1:], outs[1:]):
-                        held[tgt] = buf
-                if i < n_rows:
-                    k.append(func.eval_at(stage_times[i], yi))
-                else:
-                    y1_planned = yi
-            err_partial, err_rem = held.pop(R), (carry.err_idx, carry.err_coef)
-        for i in range(1, n_rows if carry is None else 0):
-            row = self._beta[i]
-            if i == n_rows - 1 and fsal and self._fuse is not None and fused_norm and \
-                    (nograd or not (y0.requires_grad or k[-1].requires_grad)):
-                yi, err_partial = torch.empty_like(y0), torch.empty_like(y0)
-                kern.stage_combine_err(yi, err_partial, y0, [k[j] for j in row.idx], row.coef, self._fuse[0], dt_signed)
-            elif nograd:
+        if self._carry is not None and fused_norm and (nograd or (plain and not k1.requires_grad)):
+            # carried partial sums (tableaus.carry_plan): a launch may also emit the left-to-right prefixes of later rows'
+            # sums (continued by those rows: fewer bytes) or a later stage input that needs no newer stage
+            plan, direct = self._carry, True
+        else:
+            # row by row: with the end-of-step fusion where the norm launch can continue it, else every row whole.
+            # `direct`: kern.stage_combine without Ops.combine's look at the inputs (host time on the headline path)
+            plan = self._row_plan if (fused_norm and self._row_plan is not None) else self._whole_plan
+            direct = nograd
+        k: List[torch.Tensor] = [f0, k1]
+        rows, n_rows, R, held = self._launch_rows, len(self._beta), len(plan.ops), {}
+        for i in range(1, R):
+            op, row = plan.ops[i], rows[i]
+            form = None if op is None else op.form
+            if form == "pair" and not direct and (y0.requires_grad or k[-1].requires_grad):
+                form = "whole"      # decided at the last launch: a recorded combine emits no partial error
+            if form is None:
+                yi = held.pop(i)                      # finished by an earlier launch
+            elif form == "whole" and direct:
                 yi = torch.empty_like(y0)
                 kern.stage_combine(yi, y0, [k[j] for j in row.idx], row.coef, dt_signed)
+            elif form == "whole":
+                yi = self.ops.combine(y0, [k[j] for j in row.idx], row.coef, dt_signed, dsh_signed)
+            elif form == "pair":
+                yi, held[R] = torch.empty_like(y0), torch.empty_like(y0)
+                kern.stage_combine_err(yi, held[R], y0, [k[j] for j in row.idx], row.coef, self._fuse[0], dt_signed)
             else:
-                yi = ops.combine(y0, [k[j] for j in row.idx], row.coef, dt_signed, dsh_signed)
-            k.append(func.eval_at(stage_times[i], yi))
-        if fsal:
-            y1 = yi
-        elif y1_planned is not None:
-            y1 = y1_planned
-        elif self._fuse is not None and fused_norm and \
-                not (torch.is_grad_enabled() and (y0.requires_grad or k[-1].requires_grad)):
-            sol = self._c_sol
-            y1, err_partial = torch.empty_like(y0), torch.empty_like(y0)
-            kern.stage_combine_err(y1, err_partial, y0, [k[j] for j in sol.idx], sol.coef, self._fuse[0], dt_signed)
-        else:
-            y1 = ops.combine(y0, [k[j] for j in self._c_sol.idx], self._c_sol.coef, dt_signed, dsh_signed)
-        f1 = k[-1]
-
-        # ---- error ratio (misc.py:80-82) ----
+                outs = [torch.empty_like(y0) for _ in op.targets]
+                kern.stage_combine_multi(outs, op.spec, y0, held.pop(i) if op.continues else None,
+                                         [k[j] for j in op.idx], dt_signed)
+                yi = outs[0]
+                for tgt, buf in zip(op.targets[1:], outs[1:]):
+                    held[tgt] = buf
+            if i < n_rows:      # (launch row n_rows of a pair whose solution is not its last stage input: the c_sol combine)
+                k.append(func.eval_at(stage_times[i], yi))
+        err_partial = held.pop(R, None)
+        assert not held
         err = self._c_err
+        return yi, k, err_partial, ((plan.err_idx, plan.err_coef) if err_partial is not None else (err.idx, err.coef))
+
+    def _error_ratio(self, y0, f0, y1, k, err_partial, err_rem, t0, dt, t1, dt_signed, lookahead):
+        """The error ratio of the trial step (misc.py:80-82): (error_ratio, y1 has non-finite values, decided).  With the
+        device-resident controller `decided` = (accept, next step size) as the device took them — the next trial step's
+        first stage and evaluation are enqueued on them before they are read back —, else None: the host decides."""
+        func, kern = self.func, self.kernels
+        builtin_norm, vec_fused = self._partial_norm()
+        ks, coefs = [k[j] for j in err_rem[0]], err_rem[1]
         vec_ctrl = self._vec_ctrl and not builtin_norm and (err_partial is None or vec_fused)
-        use_ctrl = lookahead and ((err_partial is not None and (builtin_norm or vec_ctrl))
-                                  or (self._whole_row_ctrl and builtin_norm) or vec_ctrl)
-        if use_ctrl:
+        if lookahead and ((err_partial is not None and (builtin_norm or vec_ctrl))
+                          or (self._whole_row_ctrl and builtin_norm) or vec_ctrl):
             ctrl = self._ctrl
             ctrl.t0, ctrl.dt = t0, dt
             tnext = torch.empty(ctrl.n_times, dtype=func.time_dtype, device=y0.device)
-            if vec_ctrl and err_partial is not None:
-                kern.error_norm_vec_ctrl(self.plan, y0, y1, [k[j] for j in err_rem[0]], err_rem[1], dt_signed,
-                                         self._vec_fused[0], self._vec_fused[1], ctrl, tnext, partial=err_partial)
-            elif vec_ctrl:
-                kern.error_norm_vec_ctrl(self.plan, y0, y1, [k[j] for j in err.idx], err.coef, dt_signed,
-                                         self._vec_fused[0], self._vec_fused[1], ctrl, tnext)
+            if vec_ctrl:
+                kern.error_norm_vec_ctrl(self.plan, y0, y1, ks, coefs, dt_signed, self._vec_fused[0], self._vec_fused[1],
+                                         ctrl, tnext, **({} if err_partial is None else {"partial": err_partial}))
             elif err_partial is None:
-                kern.error_norm_ctrl(self.plan, y0, y1, [k[j] for j in err.idx], err.coef, dt_signed, ctrl, tnext)
+                kern.error_norm_ctrl(self.plan, y0, y1, ks, coefs, dt_signed, ctrl, tnext)
             elif self._sync is None:
-                kern.error_norm_partial_ctrl(self.plan, err_partial, y0, y1, [k[j] for j in err_rem[0]],
-                                             err_rem[1], dt_signed, ctrl, tnext)
+                kern.error_norm_partial_ctrl(self.plan, err_partial, y0, y1, ks, coefs, dt_signed, ctrl, tnext)
             else:
                 # lock step: this rank's sums -> device buffer, all-reduce over the ranks on the device, the
                 # controller on the global sums (global element counts): every rank takes the whole-batch decision
-                kern.error_norm_partial(self._plan_dev, err_partial, y0, y1, [k[j] for j in err_rem[0]],
-                                        err_rem[1], dt_signed)
+                kern.error_norm_partial(self._plan_dev, err_partial, y0, y1, ks, coefs, dt_signed)
                 self._sync.reduce_device(self._plan_dev.out, self.plan.n_seg)
                 kern.step_controller(self.plan, self._plan_dev, self._plan_glob, ctrl, tnext, y0.dtype)
             if t1 < self._t_end and not self._hold_pre and not self._last_trial:
                 # accepted or rejected, another trial step follows: enqueue its first stage and func evaluation now
                 yi_n = torch.empty_like(y0)
-                kern.stage_combine_sel(yi_n, y1, f1, y0, f0, row0.coef[0], self.plan)
+                kern.stage_combine_sel(yi_n, y1, k[-1], y0, f0, self._beta[0].coef[0], self.plan)
                 tn = tnext.unbind(0)
                 self._pre = (yi_n, tn, func.eval_at(tn[0], yi_n))
             accept_dev, dt_next_dev, error_ratio, bad = kern.read_ctrl(self.plan)
-            y1_nonfinite = any(b != 0 for b in bad)
-        elif err_partial is not None and builtin_norm:
-            kern.error_norm_partial(self.plan, err_partial, y0, y1, [k[j] for j in err_rem[0]], err_rem[1],
-                                    dt_signed)
-            sumsq, _, bad = self._read_norms()
-            error_ratio = self._segment_norm(sumsq, bad)
-            y1_nonfinite = any(b != 0 for b in bad)
-        elif builtin_norm:
-            kern.error_norm(self.plan, y0, y1, [k[j] for j in err.idx], err.coef, dt_signed)
-            sumsq, _, bad = self._read_norms()
-            error_ratio = self._segment_norm(sumsq, bad)
-            y1_nonfinite = any(b != 0 for b in bad)
+            return error_ratio, any(b != 0 for b in bad), (accept_dev, dt_next_dev)
+        if not builtin_norm:
+            return self._user_norm_ratio(y0, y1, k, dt_signed, err_partial, err_rem) + (None,)
+        if err_partial is not None:
+            kern.error_norm_partial(self.plan, err_partial, y0, y1, ks, coefs, dt_signed)
         else:
-            error_ratio, y1_nonfinite = self._user_norm_ratio(y0, y1, k, dt_signed, err_partial, err_rem)
-        if use_ctrl:
-            accept_step = accept_dev      # the device's decision is the one its look-ahead stage was built on
-        else:
-            # rk_common.py:324-332: a step at the floor is always taken, one above the ceiling never, else the error decides
-            accept_step = bool(dt <= self.min_step or (error_ratio <= 1 and not dt > self.max_step))
+            kern.error_norm(self.plan, y0, y1, ks, coefs, dt_signed)
+        sumsq, _, bad = self._read_norms()
+        return self._segment_norm(sumsq, bad), any(b != 0 for b in bad), None
 
-        # ---- update state (rk_common.py:335-361) ----
+    def _commit(self, accept_step, dt_next, y0, y1, k, t0, dt, t1, dt_signed, dsh, dsh_signed, on_step_t, on_jump_t,
+                y1_nonfinite) -> None:
+        """Accept or reject the trial step and set the next step size (rk_common.py:335-361)."""
+        func = self.func
         if accept_step:
             if func.callback_accept_step is not _null:
                 func.callback_accept_step(self._time_tensor(t0), y0, self._time_tensor(dt))
-            rec = _DenseRecord()
-            rec.y0, rec.y1, rec.k, rec.dt_signed, rec.t0, rec.t1 = y0, y1, k, dt_signed, t0, t1
-            rec.dt_shadow, rec.anchor = dsh_signed, self._anchor
-            self._dense = rec
+            rec = _DenseRecord(y0, y1, k, dt_signed, t0, t1, dsh_signed, self._anchor)
             if dsh is not None:
                 # every later time of the solve is t0 + dt0 + constants: it moves with the first step size — until a
                 # step ends on a prescribed point, a constant
+                clipped = on_step_t or on_jump_t
                 self._anchor = None if clipped else (dsh if self._anchor is None else self._anchor + dsh)
                 func.set_time_anchor(self._anchor)
             if on_step_t and self.next_step_index != len(self._step_t) - 1:
                 self.next_step_index += 1
+            f1 = k[-1]
             if on_jump_t:
                 if self.next_jump_index != len(self._jump_t) - 1:
                     self.next_jump_index += 1
                 f1 = func.eval(t1, y1, Perturb.NEXT)
-            self.y1, self.f1, self.t0, self.t1 = y1, f1, t0, t1
-            self._y_nonfinite = y1_nonfinite
-            self.n_accepted += 1
+            self._accept(rec, y1, f1, y1_nonfinite)
         else:
             if func.callback_reject_step is not _null:
                 func.callback_reject_step(self._time_tensor(t0), y0, self._time_tensor(dt))
-            self.t0 = t0   # (y, f, t1) unchanged: the step is retried from t0 with a smaller dt
-            self.n_rejected += 1
-        if use_ctrl:
-            self.dt = dt_next_dev         # already clamped (tdeq_error_norm_partial_ctrl)
-        else:
-            if self._wide:
-                dt_next = optimal_step_size(dt, error_ratio, self.safety, self.ifactor, self.dfactor, self.order)
-            else:
-                dt_next = optimal_step_size_in(self._W, dt, error_ratio, self.safety, self.ifactor, self.dfactor,
-                                               self.order)
-            self.dt = _clamp(dt_next, self.min_step, self.max_step)
+            self._reject(t0)
+        self.dt = dt_next
+
+    def _accept(self, rec: _DenseRecord, y, f, y_nonfinite: bool) -> None:
+        """The step recorded in `rec` was accepted: the next one starts from (rec.t1, y, f)."""
+        self._dense = rec
+        self.y1, self.f1, self.t0, self.t1 = y, f, rec.t0, rec.t1
+        self._y_nonfinite = y_nonfinite
+        self.n_accepted += 1
+
+    def _reject(self, t0: float) -> None:
+        self.t0 = t0   # (y, f, t1) unchanged: the step is retried from t0 with a smaller dt
+        self.n_rejected += 1
 
     # -- hipGraph mode -----------------------------------------------------------------------------------
     def _graph_step_ok(self) -> bool:
@@ -971,43 +988,30 @@ class RKAdaptiveStepsizeODESolver(AdaptiveEvents):
         from device memory (tdeq_stage_combine_dev) and the error norm + device controller (state_in_dev); the host
         replays the graph of the current side (see _GraphStep: two graphs over ping-pong state buffers), reads the
         controller's words, flips the side when the step was accepted and keeps its own mirror of (t0, dt) — identical
-        doubles — for the output loop.  Same kernels' arithmetic and decisions as the eager path."""
-        func, kern, T = self.func, self.kernels, self.np_dtype
-        t0, dt = self.t1, self.dt
-        if not math.isfinite(dt):
-            dt = self.min_step
-        dt = _clamp(dt, self.min_step, self.max_step)
-        t1 = t0 + dt
-        assert t0 + dt > t0, "underflow in dt {}".format(dt)
-        assert not self._y_nonfinite, "non-finite values in state `y`: {}".format(self._unpadded(self.y1))
+        doubles — for the output loop.  Same kernels' arithmetic and decisions as the eager path, begun and committed by
+        the same code (no callbacks, no clipping, no shadows: `_graph_step_ok`)."""
+        t0, dt, t1 = self._begin_step()
         g = self._g
         if g is None:
             g = self._g = _GraphStep.acquire(self, t0, dt)
         side = g.side
         g.run(self)
-        accept_step, dt_next, _ratio, bad = g.take_words(kern, self.plan)
-        dt_signed = float(T(dt)) * func.sign
+        accept_step, dt_next, _ratio, bad = g.take_words(self.kernels, self.plan)
         if accept_step:
+            dt_signed = float(self.np_dtype(dt)) * self.func.sign
             k = g.k[side]
-            rec = _DenseRecord()
             if g.eager:
                 # warm-up step on transient buffers: keep private copies of the pair it started from (the static pair
                 # is about to receive its end state)
-                rec.y0, rec.k = g.y[0].clone(), [g.f0.clone()] + k[1:]
-                rec.y1 = g.y[1].clone()
-                self.y1, self.f1 = g.y[0], g.f0
+                rec = _DenseRecord(g.y[0].clone(), g.y[1].clone(), [g.f0.clone()] + k[1:], dt_signed, t0, t1)
+                y_next, f_next = g.y[0], g.f0
             else:
-                rec.y0, rec.y1, rec.k = g.y[side], g.y[1 - side], k
-                self.y1, self.f1 = g.y[1 - side], (k[-1] if side == 0 else g.f0)
-            rec.dt_signed, rec.t0, rec.t1 = dt_signed, t0, t1
-            self._dense = rec
+                rec = _DenseRecord(g.y[side], g.y[1 - side], k, dt_signed, t0, t1)
+                y_next, f_next = g.y[1 - side], (k[-1] if side == 0 else g.f0)
             g.accepted(self)
-            self.t0, self.t1 = t0, t1
-            self._y_nonfinite = any(b != 0 for b in bad)
-            self.n_accepted += 1
+            self._accept(rec, y_next, f_next, any(b != 0 for b in bad))
         else:
-            self.t0 = t0
-            self.n_rejected += 1
+            self._reject(t0)
         self.dt = dt_next
         if g.refused is not None:
             # auto mode: the step just taken stands (it was evaluated eagerly), the rest of the solve runs on the eager
@@ -1016,36 +1020,32 @@ class RKAdaptiveStepsizeODESolver(AdaptiveEvents):
             self._g = None
             self._hold_pre = False
 
-    def _user_norm_ratio(self, y0, y1, k, dt_signed, err_partial=None, err_rem=None):
-        """User-supplied `norm` callable (misc.py:80-82 with a custom norm): the kernel materialises
-        err/tol (padding zero-filled) and the user's own function reduces it."""
-        err = self._c_err
+    def _user_norm_ratio(self, y0, y1, k, dt_signed, err_partial, err_rem):
+        """(error ratio, y1 has non-finite values) under a user-supplied `norm` callable (misc.py:80-82 with a custom
+        norm): the kernel materialises err/tol (padding zero-filled) and the user's own function reduces it."""
         y0, y1 = y0.detach(), y1.detach()
+        ks = [k[j].detach() for j in err_rem[0]]
         if self._vec_fused is not None:
             # per-element tolerances under the built-in norm: err / tol and the per-segment sums in one launch, in the
             # reference's promoted precision (fp64); max over the components of sqrt(mean) as misc.py:22-33
             rtol_v, atol_v, n_skip = self._vec_fused
-            if err_partial is not None:       # (the step's last combine already summed the row's leading run)
-                self.kernels.error_norm_vec(self.plan, y0, y1, [k[j].detach() for j in err_rem[0]], err_rem[1], dt_signed,
-                                            rtol_v, atol_v, partial=err_partial)
-            else:
-                self.kernels.error_norm_vec(self.plan, y0, y1, [k[j].detach() for j in err.idx], err.coef, dt_signed,
-                                            rtol_v, atol_v)
+            # (`partial`: the step's last combine already summed the row's leading run)
+            self.kernels.error_norm_vec(self.plan, y0, y1, ks, err_rem[1], dt_signed, rtol_v, atol_v,
+                                        **({} if err_partial is None else {"partial": err_partial}))
             sumsq, _, bad = self.kernels.read_norms(self.plan)
             ratio = 0.0
             for s_, n_ in list(zip(sumsq, self._numels))[:len(self._numels) - n_skip]:
                 if n_:
                     ratio = _nan_max(ratio, math.sqrt(s_ / n_))
             return ratio, any(b != 0 for b in bad)
-        scaled = torch.empty_like(y0)
-        self.kernels.error_scaled(self.plan, scaled, y0, y1, [k[j].detach() for j in err.idx], err.coef, dt_signed)
+        scaled = torch.empty_like(y0)       # (no partial error here: only a norm LAUNCH continues one, `_partial_norm`)
+        self.kernels.error_scaled(self.plan, scaled, y0, y1, ks, err_rem[1], dt_signed)
         _, _, bad = self.kernels.read_norms(self.plan)
         with torch.no_grad():
             if self._vec_tol is not None:       # `scaled` is the raw error estimate here (segment tolerances 0 / 1)
                 scaled = scaled / (self._vec_tol[1] + self._vec_tol[0] * torch.maximum(y0.abs(), y1.abs()))
             ratio = self.norm(scaled)
-        ratio = _norm_value(ratio)
-        return ratio, any(b != 0 for b in bad)
+        return _norm_value(ratio), any(b != 0 for b in bad)
 
 
 class Dopri5Solver(RKAdaptiveStepsizeODESolver):

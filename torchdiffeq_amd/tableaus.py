@@ -333,6 +333,21 @@ class CarryOp:
     continues: bool                         # output 0 continues the partial sum carried for `row`
     targets: Tuple[int, ...]                # tableau row of every output (targets[0] == row; n_rows = the error)
     spec: Tuple[Tuple[Tuple[float, ...], int, bool], ...]   # per output: (weights over idx, mask, add_y0)
+    form: str = "multi"                     # the launch `odeint` makes of it, see `_launch_form` (odeint_rowwise has one form)
+
+
+# Which of the three stage-combine launches an op of `odeint`'s trial step is — decided HERE, where ops are made; the
+# interpreters (solvers/adaptive.py `_stages`, _graph.py `body`) only look it up:
+#   "whole"  one output that continues nothing                                                  tdeq_stage_combine
+#   "pair"   the step's last launch emitting exactly (its own row, the error's leading run) over the row's own stages:
+#            the end-of-step fusion                                                             tdeq_stage_combine_err
+#   "multi"  everything else                                                                    tdeq_stage_combine_multi
+def _launch_form(row: int, n_launch_rows: int, row_idx, idx, continues: bool, targets) -> str:
+    if len(targets) == 1 and not continues:
+        return "whole"
+    if tuple(targets) == (row, n_launch_rows) and row == n_launch_rows - 1 and not continues and tuple(idx) == tuple(row_idx):
+        return "pair"
+    return "multi"
 
 
 @dataclasses.dataclass(frozen=True)
@@ -385,7 +400,8 @@ def _plan_from_hosts(tab: Tableau, hosts) -> CarryPlan:
         words += len(idx) + 1 + (1 if h is not None else 0) + len(targets)
         launches += 1
         if i > 0:
-            ops[i] = CarryOp(i, tuple(idx), h is not None, tuple(targets), tuple(spec))
+            ops[i] = CarryOp(i, tuple(idx), h is not None, tuple(targets), tuple(spec),
+                             _launch_form(i, R, sorted(nz[i]), idx, h is not None, targets))
         else:
             assert targets == [0]
     rem = sorted(j for j in nz[R] if j > hosts[R])
@@ -415,10 +431,13 @@ def row_by_row_plan(rows: Sequence[SparseRow], err: SparseRow, n_lead: int) -> C
         row, fused = rows[i], n_lead > 0 and i == R - 1
         full = (1 << len(row.idx)) - 1
         spec = ((row.coef, full, True),) + (((err.coef[:n_lead], full, False),) if fused else ())
-        ops.append(CarryOp(i, row.idx, False, (i, R) if fused else (i,), spec))
+        targets = (i, R) if fused else (i,)
+        ops.append(CarryOp(i, row.idx, False, targets, spec, _launch_form(i, R, row.idx, row.idx, False, targets)))
     rem = err.idx[n_lead:]
     p = 1 if n_lead else 0
-    return CarryPlan(tuple(ops), rem, err.coef[n_lead:], sum(len(r.idx) + 2 for r in rows) + 2 * p + len(rem) + 2, R + 1)
+    # (the whole error row keeps its own weights object: the torch-op host path reads where in the dense row they sit)
+    return CarryPlan(tuple(ops), rem, err.coef[n_lead:] if n_lead else err.coef,
+                     sum(len(r.idx) + 2 for r in rows) + 2 * p + len(rem) + 2, R + 1)
 
 
 # The end-of-step fusion needs the last launch's stages to be a leading run of the error row's; the two users differ in
