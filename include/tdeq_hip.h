@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define TDEQ_ABI_VERSION 23
+#define TDEQ_ABI_VERSION 24
 #define TDEQ_F32 0
 #define TDEQ_F64 1
 /* interleaved (re, im) complex states — accepted by the NORM entry points only (tdeq_error_norm, tdeq_error_norm_partial[_ctrl],
@@ -616,6 +616,22 @@ int tdeq_row_scale_many(void* const* outs, int n_out, const void* g, const void*
 size_t tdeq_row_dots_workspace_bytes(int64_t n_rows, int64_t row_len, int n_x, int dtype);
 int tdeq_row_multi_dot(const void* g, const void* const* x, int n_x, int64_t n_rows, int64_t row_len, double* out,
                        void* workspace, size_t workspace_bytes, int dtype, void* stream);
+
+/*
+ * ---- Compaction of a rowwise batch (ABI 24; `odeint_rowwise(compact=...)`) ----
+ * tdeq_row_gather               dst[m][q, e] = src[m][idx[q], e] for q < n_idx, e < row_len, m < n_src (1 .. 4), all in one
+ *                               launch; a copy of bits.  16-byte elements when row_len is a multiple of 16 / sizeof(T) and
+ *                               every pointer is 16-byte aligned, scalar elements otherwise.  Every idx[q] must be a row of
+ *                               every src[m]; dst[m] holds n_idx rows and must not overlap any src.  n_idx == 0: no-op.
+ * tdeq_row_dense_commit_mapped  tdeq_row_dense_commit for a compacted batch: the state tensors and `st` hold st->n_rows
+ *                               compact rows, `sol` is [n_out, sol_rows, row_len], and the outputs of compact row r go to
+ *                               sol[j, row_map[r], :] (0 <= row_map[r] < sol_rows); y0 <- y1, f0 <- f1 at the compact index.
+ */
+int tdeq_row_gather(void* const* dst, const void* const* src, int n_src, const int32_t* idx, int64_t n_idx,
+                    int64_t row_len, int dtype, void* stream);
+int tdeq_row_dense_commit_mapped(void* sol, const int32_t* row_map, int64_t sol_rows, void* y0, const void* y1, void* f0,
+                                 const void* f1, const void* const* k, const double* coef, int n_terms, const void* dts,
+                                 const tdeq_row_state* st, int dtype, void* stream);
 
 #ifdef __cplusplus
 }

@@ -6,6 +6,11 @@ on a mixed-stiffness batch.
     python tools/rowwise_bench.py --grad [--out profiles/rowwise_grad_bench.json] [--parity profiles/rowwise_grad_parity.json]
     python tools/rowwise_bench.py --grad --stats <kernel_stats.csv>[,<second>,...] --bench <that json>
                                                                  (row_scale_many bandwidth, one csv per traced repeat)
+    python tools/rowwise_bench.py --compact [--out profiles/rowwise_compact_bench.json] [--reps 5]
+
+`--compact`: wall time of one solve at the headline shape with a per-row rate spread over logspace(-1, 1.5) (so that the
+rows' trial counts differ), plain against `compact=0.5` and `compact=1.0`: `row_evals` against `nfe x B` (the bound on
+any speed-up), the number of repacks and the time spent inside `repack`.
 
 `--grad`: forward + backward of a `differentiable=True` solve per trial step at the headline, next to plain `odeint`
 backprop of the same state, and (`--parity`) the per-row deviations of the rowwise gradients from the reference's
@@ -63,6 +68,72 @@ def _headline(reps: int):
         res[k] = res[k][1:]          # the first pair warms up
     res["ratio_rowwise_over_odeint"] = min(res["rowwise_ms_per_trial"]) / min(res["odeint_ms_per_trial"])
     return res
+
+
+def _compact(reps: int):
+    """Headline shape, dopri5, func k_r * (y @ A.T) with k_r over logspace(-1, 1.5): ms per solve, plain / compact=0.5 /
+    compact=1.0 alternated in one process after a warm-up round, then one more solve per setting with `repack` timed
+    (synchronised on both sides, so that solve is not among the timed ones)."""
+    import torchdiffeq_amd as tda
+    from torchdiffeq_amd import rowwise
+    dev = torch.device("cuda", 0)
+    B, D = 65536, 128
+    g = torch.Generator().manual_seed(0)
+    G = torch.randn(D, D, generator=g, dtype=torch.float64) / D ** 0.5
+    A = (0.5 * (G - G.T) - 0.1 * torch.eye(D, dtype=torch.float64)).float().to(dev)
+    k = torch.logspace(-1, 1.5, B, dtype=torch.float64)[torch.randperm(B, generator=g)][:, None].float().to(dev)
+    y0 = torch.randn(B, D, generator=g).to(dev)
+    t = torch.tensor([0.0, 0.5], device=dev)
+    settings = (("plain", None), ("compact_0.5", 0.5), ("compact_1.0", 1.0))
+
+    def solve(c):
+        if c is None:
+            return tda.odeint_rowwise(lambda t_, y: k * (y @ A.T), y0, t, rtol=1e-7, atol=1e-9, return_stats=True)
+        return tda.odeint_rowwise(lambda t_, y, rows: k[rows] * (y @ A.T), y0, t, rtol=1e-7, atol=1e-9,
+                                  return_stats=True, compact=c)
+    res = {name: {"ms_per_solve": []} for name, _ in settings}
+    sols = {}
+    with torch.no_grad():
+        for rep in range(reps + 1):
+            for name, c in settings:
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                sol, st = solve(c)
+                torch.cuda.synchronize()
+                if rep:                       # the first round warms up
+                    res[name]["ms_per_solve"].append((time.perf_counter() - t0) * 1e3)
+                sols[name] = sol
+                trials = st["n_accepted"] + st["n_rejected"]
+                res[name].update(nfe=st["nfe"], nfe_times_B=st["nfe"] * B, row_evals=st.get("row_evals", st["nfe"] * B),
+                                 n_repacks=st.get("n_repacks", 0), trials_min=int(trials.min()),
+                                 trials_median=float(trials.median()), trials_max=int(trials.max()))
+        inside = [0.0]
+        plain_repack = rowwise.HipRowKernels.repack
+
+        def timed_repack(self, y, f0, n_keep):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            out = plain_repack(self, y, f0, n_keep)
+            torch.cuda.synchronize()
+            inside[0] += (time.perf_counter() - t0) * 1e3
+            return out
+        rowwise.HipRowKernels.repack = timed_repack
+        try:
+            for name, c in settings[1:]:
+                inside[0] = 0.0
+                solve(c)
+                res[name]["ms_inside_repack"] = inside[0]
+        finally:
+            rowwise.HipRowKernels.repack = plain_repack
+    med = lambda v: sorted(v)[len(v) // 2]       # noqa: E731
+    for name, _ in settings:
+        r = res[name]
+        r["ms_per_solve_median"] = med(r["ms_per_solve"])
+        r["bit_identical_to_plain"] = bool(torch.equal(sols[name], sols["plain"]))
+        r["speedup_bound"] = r["nfe_times_B"] / r["row_evals"]
+        r["speedup"] = med(res["plain"]["ms_per_solve"]) / r["ms_per_solve_median"]
+    return {"B": B, "L": D, "dtype": "float32", "method": "dopri5", "rtol": 1e-7, "atol": 1e-9,
+            "rate_spread": "k_r in logspace(-1, 1.5), shuffled; func k_r * (y @ A.T)", **res}
 
 
 def _grad_headline(reps: int):
@@ -236,7 +307,16 @@ def main():
     ap.add_argument("--bench", default=None)
     ap.add_argument("--grad", action="store_true")
     ap.add_argument("--parity", default=None)
+    ap.add_argument("--compact", action="store_true")
     a = ap.parse_args()
+    if a.compact:
+        res = {"device": torch.cuda.get_device_name(0), "arch": torch.cuda.get_device_properties(0).gcnArchName,
+               "compact": _compact(a.reps)}
+        print(json.dumps(res))
+        if a.out:
+            os.makedirs(os.path.dirname(a.out) or ".", exist_ok=True)
+            json.dump(res, open(a.out, "w"), indent=1)
+        return
     if a.grad and a.stats:
         bench = _grad_stats(a.stats.split(","), json.load(open(a.bench)))
         json.dump(bench, open(a.bench, "w"), indent=1)

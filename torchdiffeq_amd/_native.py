@@ -18,7 +18,7 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-TDEQ_ABI_VERSION = 23
+TDEQ_ABI_VERSION = 24
 TDEQ_F32, TDEQ_F64 = 0, 1
 TDEQ_C64, TDEQ_C128 = 2, 3        # interleaved complex: the norm entry points only (include/tdeq_hip.h)
 TDEQ_BF16, TDEQ_F16 = 4, 5        # reduced-precision states: the entry points of the host-driven step (LowPrecisionHipKernels)
@@ -28,6 +28,7 @@ TDEQ_CHUNK_QUANTUM = 1024
 TDEQ_MAX_STAGE_TIMES = 16
 TDEQ_MAX_DENSE_OUTPUTS = 16
 TDEQ_MAX_MULTI_OUT = 4
+TDEQ_MAX_GATHER = 4
 
 _LIB_NAME = "libtdeq_hip.so"
 _LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), _LIB_NAME)
@@ -233,6 +234,13 @@ ABI_SIGNATURES = {
     "tdeq_row_multi_dot": (ctypes.c_int, [ctypes.c_void_p, _c_void_pp, ctypes.c_int, ctypes.c_int64, ctypes.c_int64,
                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int,
                                           ctypes.c_void_p]),
+    # compaction of a rowwise batch (ABI 24, odeint_rowwise(compact=...))
+    "tdeq_row_gather": (ctypes.c_int, [_c_void_pp, _c_void_pp, ctypes.c_int, ctypes.c_void_p, ctypes.c_int64,
+                                       ctypes.c_int64, ctypes.c_int, ctypes.c_void_p]),
+    "tdeq_row_dense_commit_mapped": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
+                                                    ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, _c_void_pp,
+                                                    _c_double_p, ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(RowState),
+                                                    ctypes.c_int, ctypes.c_void_p]),
 }
 
 
@@ -865,6 +873,26 @@ class HipKernels:
         _check(self.lib.tdeq_row_dense_commit(sol.data_ptr(), y0.data_ptr(), y1.data_ptr(), f0.data_ptr(), f1.data_ptr(),
                                               ptrs, cf, n, dts.data_ptr(), ctypes.byref(st), dtype_code(y0.dtype),
                                               self._stream()), "tdeq_row_dense_commit")
+
+    def row_dense_commit_mapped(self, sol, row_map, y0, y1, f0, f1, ks, coefs, dts, st: RowState) -> None:
+        """tdeq_row_dense_commit_mapped: `sol` [n_out, sol_rows, L], the state tensors [st.n_rows, L], `row_map` int32
+        [st.n_rows] = the solution row of each state row."""
+        ptrs, cf, n = self._terms(ks, coefs)
+        _check(self.lib.tdeq_row_dense_commit_mapped(sol.data_ptr(), row_map.data_ptr(), sol.shape[1], y0.data_ptr(),
+                                                     y1.data_ptr(), f0.data_ptr(), f1.data_ptr(), ptrs, cf, n,
+                                                     dts.data_ptr(), ctypes.byref(st), dtype_code(y0.dtype),
+                                                     self._stream()), "tdeq_row_dense_commit_mapped")
+
+    def row_gather(self, outs, srcs, idx) -> None:
+        """tdeq_row_gather: outs[m][q, :] = srcs[m][idx[q], :] for up to 4 [*, L] tensors of one dtype in one launch;
+        `idx` int32 on the device, `outs[m]` contiguous [len(idx), L]."""
+        n = len(srcs)
+        if idx.numel() == 0:                  # (nothing to gather; empty tensors have null pointers, which the ABI refuses)
+            return
+        dst = (ctypes.c_void_p * n)(*[o.data_ptr() for o in outs])
+        src = (ctypes.c_void_p * n)(*[x.data_ptr() for x in srcs])
+        _check(self.lib.tdeq_row_gather(dst, src, n, idx.data_ptr(), idx.numel(), srcs[0].shape[1],
+                                        dtype_code(srcs[0].dtype), self._stream()), "tdeq_row_gather")
 
     def row_scale_many(self, outs, g, w) -> None:
         """tdeq_row_scale_many: outs[m][r, :] = w[m, r] * g[r, :]; `w` a contiguous [len(outs), B] tensor of g's dtype."""

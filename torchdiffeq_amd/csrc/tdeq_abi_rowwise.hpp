@@ -225,6 +225,86 @@ int row_dense_dispatch(void* sol, void* y0, const void* y1, void* f0, const void
     return TDEQ_EINVAL;
 }
 
+template <typename T, int NT>
+int row_dense_mapped_n(void* sol, const int32_t* row_map, int64_t sol_rows, void* y0, const void* y1, void* f0,
+                       const void* f1, const void* const* k, const double* coef, const void* dts,
+                       const tdeq_row_state* st, hipStream_t s) {
+    RowDenseMappedArgs<T, NT> a;
+    a.sol = static_cast<T*>(sol);
+    a.y0 = static_cast<T*>(y0);
+    a.y1 = static_cast<const T*>(y1);
+    a.f0 = static_cast<T*>(f0);
+    a.f1 = static_cast<const T*>(f1);
+    for (int j = 0; j < NT; ++j) {
+        a.k[j] = static_cast<const T*>(k[j]);
+        a.c[j] = (T)coef[j];
+    }
+    a.dts = static_cast<const T*>(dts);
+    a.tgrid = st->tgrid;
+    a.tprev = st->tprev;
+    a.t1 = st->t0;
+    a.accepted = st->accepted;
+    a.out_lo = st->out_lo;
+    a.out_hi = st->out_hi;
+    a.n_rows = st->n_rows;
+    a.n = st->n_rows * st->row_len;
+    a.row_map = row_map;
+    a.sol_rows = sol_rows;
+    const int lv = row_lanes(st->row_len, std::is_same<T, float>::value ? TDEQ_F32 : TDEQ_F64);
+    bool vec = lv > 1 && aligned16(sol) && aligned16(y0) && aligned16(y1) && aligned16(f0) && aligned16(f1);
+    for (int j = 0; j < NT; ++j) vec = vec && aligned16(k[j]);
+    if (vec) {
+        a.row_len = st->row_len / lv;
+        hipLaunchKernelGGL((row_dense_commit_mapped_kernel<T, NT, true>), dim3(stream_grid(a.n / lv, kBlock)), dim3(kBlock),
+                           0, s, a);
+    } else {
+        a.row_len = st->row_len;
+        hipLaunchKernelGGL((row_dense_commit_mapped_kernel<T, NT, false>), dim3(stream_grid(a.n, kBlock)), dim3(kBlock), 0,
+                           s, a);
+    }
+    return check_launch();
+}
+
+template <typename T>
+int row_dense_mapped_dispatch(void* sol, const int32_t* row_map, int64_t sol_rows, void* y0, const void* y1, void* f0,
+                              const void* f1, const void* const* k, const double* coef, int nt, const void* dts,
+                              const tdeq_row_state* st, hipStream_t s) {
+    switch (nt) {
+#define TDEQ_CASE(N) case N: return row_dense_mapped_n<T, N>(sol, row_map, sol_rows, y0, y1, f0, f1, k, coef, dts, st, s);
+        TDEQ_CASE(1) TDEQ_CASE(2) TDEQ_CASE(3) TDEQ_CASE(4) TDEQ_CASE(5) TDEQ_CASE(6) TDEQ_CASE(7)
+        TDEQ_CASE(8) TDEQ_CASE(9) TDEQ_CASE(10) TDEQ_CASE(11) TDEQ_CASE(12) TDEQ_CASE(13) TDEQ_CASE(14)
+#undef TDEQ_CASE
+    }
+    return TDEQ_EINVAL;
+}
+
+template <typename E, int NS>
+int row_gather_n(void* const* dst, const void* const* src, const int32_t* idx, int64_t n_idx, int64_t row_len_e,
+                 hipStream_t s) {
+    RowGatherArgs<NS> a;
+    for (int m = 0; m < NS; ++m) {
+        a.dst[m] = dst[m];
+        a.src[m] = src[m];
+    }
+    a.idx = idx;
+    a.row_len = row_len_e;
+    a.ne = n_idx * row_len_e;
+    hipLaunchKernelGGL((row_gather_kernel<E, NS>), dim3(stream_grid(a.ne, kBlock)), dim3(kBlock), 0, s, a);
+    return check_launch();
+}
+
+template <typename E>
+int row_gather_dispatch(void* const* dst, const void* const* src, int n_src, const int32_t* idx, int64_t n_idx,
+                        int64_t row_len_e, hipStream_t s) {
+    switch (n_src) {
+        case 1: return row_gather_n<E, 1>(dst, src, idx, n_idx, row_len_e, s);
+        case 2: return row_gather_n<E, 2>(dst, src, idx, n_idx, row_len_e, s);
+        case 3: return row_gather_n<E, 3>(dst, src, idx, n_idx, row_len_e, s);
+        case 4: return row_gather_n<E, 4>(dst, src, idx, n_idx, row_len_e, s);
+    }
+    return TDEQ_EINVAL;
+}
+
 inline bool row_dtype_ok(int dtype) { return dtype == TDEQ_F32 || dtype == TDEQ_F64; }
 
 }  // namespace
@@ -325,6 +405,39 @@ int tdeq_row_dense_commit(void* sol, void* y0, const void* y1, void* f0, const v
     hipStream_t s = static_cast<hipStream_t>(stream);
     return dtype == TDEQ_F32 ? row_dense_dispatch<float>(sol, y0, y1, f0, f1, k, coef, n_terms, dts, st, s)
                              : row_dense_dispatch<double>(sol, y0, y1, f0, f1, k, coef, n_terms, dts, st, s);
+}
+
+// ---- compaction of a rowwise batch: tdeq_row_gather / tdeq_row_dense_commit_mapped ------------------------------------
+int tdeq_row_gather(void* const* dst, const void* const* src, int n_src, const int32_t* idx, int64_t n_idx,
+                    int64_t row_len, int dtype, void* stream) {
+    if (!dst || !src || !idx || n_src < 1 || n_src > kMaxGather || n_idx < 0 || row_len < 1 || !row_dtype_ok(dtype))
+        return TDEQ_EINVAL;
+    for (int m = 0; m < n_src; ++m) if (!dst[m] || !src[m]) return TDEQ_EINVAL;
+    if (n_idx == 0) return 0;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int lv = row_lanes(row_len, dtype);
+    bool vec = lv > 1;
+    for (int m = 0; m < n_src; ++m) vec = vec && aligned16(dst[m]) && aligned16(src[m]);
+    if (vec) {
+        return dtype == TDEQ_F32 ? row_gather_dispatch<VecOf<float>::type>(dst, src, n_src, idx, n_idx, row_len / lv, s)
+                                 : row_gather_dispatch<VecOf<double>::type>(dst, src, n_src, idx, n_idx, row_len / lv, s);
+    }
+    return dtype == TDEQ_F32 ? row_gather_dispatch<float>(dst, src, n_src, idx, n_idx, row_len, s)
+                             : row_gather_dispatch<double>(dst, src, n_src, idx, n_idx, row_len, s);
+}
+
+int tdeq_row_dense_commit_mapped(void* sol, const int32_t* row_map, int64_t sol_rows, void* y0, const void* y1, void* f0,
+                                 const void* f1, const void* const* k, const double* coef, int n_terms, const void* dts,
+                                 const tdeq_row_state* st, int dtype, void* stream) {
+    if (!sol || !row_map || !y0 || !y1 || !f0 || !f1 || !k || !coef || !dts || !st || !row_dtype_ok(dtype)) return TDEQ_EINVAL;
+    if (n_terms < 1 || n_terms > TDEQ_MAX_TERMS || st->n_rows < 0 || st->row_len < 1) return TDEQ_EINVAL;
+    if (sol_rows < 1 || sol_rows < st->n_rows) return TDEQ_EINVAL;
+    for (int j = 0; j < n_terms; ++j) if (!k[j]) return TDEQ_EINVAL;
+    if (st->n_rows == 0) return 0;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return dtype == TDEQ_F32
+               ? row_dense_mapped_dispatch<float>(sol, row_map, sol_rows, y0, y1, f0, f1, k, coef, n_terms, dts, st, s)
+               : row_dense_mapped_dispatch<double>(sol, row_map, sol_rows, y0, y1, f0, f1, k, coef, n_terms, dts, st, s);
 }
 
 // ---- backward of the row-linear operations: tdeq_row_scale_many / tdeq_row_multi_dot ---------------------------------

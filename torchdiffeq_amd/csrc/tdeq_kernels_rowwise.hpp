@@ -457,8 +457,17 @@ struct RowDenseArgs {
     int64_t n;                        // B * L elements of T
 };
 
-template <typename T, int NT, bool VEC>
-__global__ __launch_bounds__(kBlock) void row_dense_commit_kernel(const RowDenseArgs<T, NT> a) {
+// The mapped form (MAPPED) serves a compacted batch (`odeint_rowwise(compact=...)`): the state holds n_rows compact rows,
+// the solution keeps all sol_rows original ones, and output j of compact row r goes to sol[j, row_map[r], :]; y0 and f0
+// are committed at the compact index.  The plain form is the arithmetic and the addressing it always was.
+template <typename T, int NT>
+struct RowDenseMappedArgs : RowDenseArgs<T, NT> {
+    const int32_t* row_map;           // [n_rows] solution row of each compact row
+    int64_t sol_rows;                 // rows of sol: [n_out, sol_rows, L]
+};
+
+template <typename T, int NT, bool VEC, bool MAPPED, typename Args>
+__device__ __forceinline__ void row_dense_commit_body(const Args& a) {
     using E = typename std::conditional<VEC, typename VecOf<T>::type, T>::type;
     constexpr int LV = VEC ? VecOf<T>::L : 1;
     const int64_t ne = a.n / LV;
@@ -484,11 +493,53 @@ __global__ __launch_bounds__(kBlock) void row_dense_commit_kernel(const RowDense
             const double ta = a.tprev[r], tb = a.t1[r];
             for (int j = lo; j < hi; ++j) {
                 const T x = (T)((a.tgrid[(int64_t)j * a.n_rows + r] - ta) / (tb - ta));   // interp.py:39-40 in W, then T
-                reinterpret_cast<E*>(a.sol + (int64_t)j * a.n)[i] = eval_one<T, E>(q, x);
+                if constexpr (MAPPED) {
+                    const int64_t at = ((int64_t)j * a.sol_rows + (int64_t)a.row_map[r]) * a.row_len + (i - r * a.row_len);
+                    reinterpret_cast<E*>(a.sol)[at] = eval_one<T, E>(q, x);
+                } else {
+                    reinterpret_cast<E*>(a.sol + (int64_t)j * a.n)[i] = eval_one<T, E>(q, x);
+                }
             }
         }
         reinterpret_cast<E*>(a.y0)[i] = y1;
         reinterpret_cast<E*>(a.f0)[i] = f1;
+    }
+}
+
+template <typename T, int NT, bool VEC>
+__global__ __launch_bounds__(kBlock) void row_dense_commit_kernel(const RowDenseArgs<T, NT> a) {
+    row_dense_commit_body<T, NT, VEC, false>(a);
+}
+
+template <typename T, int NT, bool VEC>
+__global__ __launch_bounds__(kBlock) void row_dense_commit_mapped_kernel(const RowDenseMappedArgs<T, NT> a) {
+    row_dense_commit_body<T, NT, VEC, true>(a);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Row gather (the repack of `odeint_rowwise(compact=...)`): dst[m][q, :] = src[m][idx[q], :] for m < NS, one launch
+// for up to kMaxGather tensors.  A copy of bits: no arithmetic touches a value.  NS is a template parameter so that the
+// pointer arrays of the argument block are indexed by constants (a runtime index would put the block into scratch).
+// ------------------------------------------------------------------------------------------------
+constexpr int kMaxGather = 4;
+
+template <int NS>
+struct RowGatherArgs {
+    void* dst[NS];
+    const void* src[NS];
+    const int32_t* idx;               // [n_idx] source row of each output row
+    int64_t row_len;                  // E units
+    int64_t ne;                       // n_idx * row_len
+};
+
+template <typename E, int NS>
+__global__ __launch_bounds__(kBlock) void row_gather_kernel(const RowGatherArgs<NS> a) {
+    const int64_t stride = (int64_t)gridDim.x * kBlock;
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < a.ne; i += stride) {
+        const int64_t q = i / a.row_len;
+        const int64_t from = (int64_t)a.idx[q] * a.row_len + (i - q * a.row_len);
+#pragma unroll
+        for (int m = 0; m < NS; ++m) static_cast<E*>(a.dst[m])[i] = static_cast<const E*>(a.src[m])[from];
     }
 }
 

@@ -13,8 +13,9 @@ torch ops (`HostRowKernels`, one `HostPathWarning`).
 Three things are kept apart.  WHAT IS LAUNCHED in a trial step is `HipRowKernels.trial_step`: one interpreter of the
 tableau's launch plan (`tableaus.launch_plan`: the carry plan of dopri5 / dopri8 / tsit5, row by row for the others),
 then the error norm, the controller and the dense-output commit.  The TWO BACKENDS offer the driver the same methods —
-`initial_step`, `trial_step`, `poll`, `counts` and, for a recorded solve, `begin_recording` / `recorded_solution` —
-and `odeint_rowwise` calls nothing else.  WHAT IS RECORDED for `differentiable=True` lives in rowwise_autodiff.py: the
+`initial_step`, `trial_step`, `poll`, `counts`, for a recorded solve `begin_recording` / `recorded_solution`, and with
+`compact=` set `repack` (the finished rows leave the batch and the solve carries on with the rest, `_compact_fraction`)
+— and `odeint_rowwise` calls nothing else.  WHAT IS RECORDED for `differentiable=True` lives in rowwise_autodiff.py: the
 device backend hands its finished launches to a `RowRecorder` (None in a plain solve), the host backend records plain
 torch ops; `_Problem.grad_mode` is the one place that turns grad mode on for a recorded solve.
 """
@@ -61,6 +62,18 @@ class _Method:
         self.n_stages = len(self.beta)
 
 
+def _compact_fraction(compact):
+    """`compact=` of odeint_rowwise -> None (off) or the fraction c in (0, 1]: after a poll that finds n_active of the
+    `cur` carried rows still active, 0 < n_active < cur and n_active <= c * cur, the batch is repacked to those rows."""
+    if compact is None or compact is False:
+        return None
+    if compact is True:
+        return 0.5
+    if isinstance(compact, (int, float)) and 0.0 < compact <= 1.0:
+        return float(compact)
+    raise ValueError(f"odeint_rowwise: compact must be None, a bool or a fraction in (0, 1], got {compact!r}")
+
+
 def _func_parameters_require_grad(func) -> bool:
     params = getattr(func, "parameters", None)
     if callable(params):
@@ -74,7 +87,8 @@ def _func_parameters_require_grad(func) -> bool:
 class _Problem:
     """Validated inputs: y [B, L] (contiguous copy), tgrid [T, B] fp64 in solver time (ascending), sign."""
 
-    def __init__(self, func, y0, t, rtol, atol, method, options, event_fn, differentiable=False):
+    def __init__(self, func, y0, t, rtol, atol, method, options, event_fn, differentiable=False, compact=None):
+        self.compact = _compact_fraction(compact)
         if event_fn is not None:
             raise ValueError("odeint_rowwise: event_fn is not supported (use odeint)")
         if not isinstance(y0, torch.Tensor):
@@ -117,6 +131,9 @@ class _Problem:
         if self.record and t.requires_grad:
             raise NotImplementedError("odeint_rowwise(differentiable=True): time gradients (t.requires_grad) are not "
                                       "supported; detach t, or use odeint")
+        if self.record and self.compact is not None:
+            raise NotImplementedError("odeint_rowwise: compact is not supported for a recorded solve "
+                                      "(differentiable=True with grad mode on)")
         if not self.record and torch.is_grad_enabled() and (y0.requires_grad or t.requires_grad or
                                                             _func_parameters_require_grad(func)):
             raise NotImplementedError("odeint_rowwise does not propagate gradients unless differentiable=True is "
@@ -159,6 +176,16 @@ class _Problem:
         self.dfactor = float(options.get("dfactor", 0.2))
         self.max_num_steps = int(options.get("max_num_steps", 2 ** 31 - 1))
         self.nfe = 0
+        # compact: the original indices of the rows now carried (int64, ascending, on the state's device) — func's third
+        # argument — and what the two extra stats count
+        self.rows = torch.arange(B, device=self.device) if self.compact is not None else None
+        self.row_evals = 0
+        self.n_repacks = 0
+
+    def keep_rows(self, idx: torch.Tensor) -> None:
+        """A repack: the carried rows `idx` (int64 positions in the current batch, ascending) stay."""
+        self.rows = self.rows.index_select(0, idx.to(self.rows.device))
+        self.n_repacks += 1
 
     def grad_mode(self):
         """The grad mode the backends step in (inside the driver's no_grad): on for a recorded solve.  The controller is
@@ -166,32 +193,36 @@ class _Problem:
         return torch.enable_grad() if self.record else contextlib.nullcontext()
 
     def call(self, t_rows: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
-        """func(t_rows [B], y [B, *row_shape]) -> [B, L] contiguous in the state's dtype."""
+        """func(t_rows [b], y [b, *row_shape]) -> [b, L] contiguous in the state's dtype, b the rows now carried (B
+        unless the batch was compacted); with `compact` set func also gets their original indices."""
         self.nfe += 1
-        f = self.func(t_rows, y.view(self.shape))
+        self.row_evals += y.shape[0]
+        y = y.view(y.shape[0], *self.shape[1:])
+        shape = y.shape
+        f = self.func(t_rows, y) if self.rows is None else self.func(t_rows, y, self.rows)
         if not isinstance(f, torch.Tensor):
             raise TypeError("odeint_rowwise: func must return a Tensor, got {}".format(type(f).__name__))
         if f.requires_grad and torch.is_grad_enabled() and not self.record:
             raise NotImplementedError("odeint_rowwise does not propagate gradients (func's output requires grad) unless "
                                       "differentiable=True is passed; use that, odeint / odeint_adjoint, or call it "
                                       "under torch.no_grad()")
-        if f.shape != self.shape:
+        if f.shape != shape:
             raise RuntimeError("odeint_rowwise: func returned shape {} for a state of shape {}".format(
-                tuple(f.shape), tuple(self.shape)))
+                tuple(f.shape), tuple(shape)))
         if f.device != self.device:
             raise RuntimeError(f"odeint_rowwise: func returned a tensor on '{f.device}', the state lives on '{self.device}'")
-        f = f.reshape(self.B, self.L)
+        f = f.reshape(shape[0], self.L)
         if f.dtype != self.dtype:
             f = f.to(self.dtype)
         return f if f.is_contiguous() and f.data_ptr() % 16 == 0 else f.contiguous(memory_format=torch.contiguous_format).clone()
 
     def raise_row_error(self, failure, y) -> None:
-        r, code, since, dt = failure
+        r, code, since, dt, at = failure                     # r: the original row; at: where it sits in y
         if code == 2:
             raise AssertionError("max_num_steps exceeded ({}>={}) in row {}".format(since, self.max_num_steps, r))
         if code == 1:
             raise AssertionError("underflow in dt {} in row {}".format(dt, r))
-        raise AssertionError("non-finite values in state `y`: {} in row {}".format(y[r].view(self.shape[1:]), r))
+        raise AssertionError("non-finite values in state `y`: {} in row {}".format(y[at].view(self.shape[1:]), r))
 
 
 def _row_sum(x: torch.Tensor) -> torch.Tensor:
@@ -219,6 +250,8 @@ class HostRowKernels:
         T = p.np_dtype
         self.T = T
         B = p.B
+        self.n = B                                           # rows now carried (fewer than p.B after a repack)
+        self.row_map = None                                  # after a repack: their original indices
         self.t0 = np.zeros(B)
         self.tprev = np.zeros(B)
         self.dt = np.zeros(B)
@@ -265,8 +298,8 @@ class HostRowKernels:
 
     def times_tensor(self) -> List[torch.Tensor]:
         p, m = self.p, self.p.method
-        out = np.empty((m.n_stages, p.B))
-        for r in range(p.B):
+        out = np.empty((m.n_stages, self.n))
+        for r in range(self.n):
             for i in range(m.n_stages):
                 out[i, r] = self.stage_time(r, i) if self.active[r] else float(p.sign * self.T(self.t0[r]))
         return list(torch.tensor(out, dtype=p.dtype).unbind(0))
@@ -292,11 +325,41 @@ class HostRowKernels:
         return sol
 
     def poll(self):
-        r = next((r for r in range(self.p.B) if self.active[r] and self.code[r] != 0), None)
-        return int(self.active.sum()), None if r is None else (r, int(self.code[r]), int(self.since[r]), float(self.dt[r]))
+        r = next((r for r in range(self.n) if self.active[r] and self.code[r] != 0), None)
+        if r is None:
+            return int(self.active.sum()), None
+        row = r if self.row_map is None else int(self.row_map[r])
+        return int(self.active.sum()), (row, int(self.code[r]), int(self.since[r]), float(self.dt[r]), r)
 
     def counts(self):
-        return torch.from_numpy(self.n_acc.copy()), torch.from_numpy(self.n_rej.copy())
+        if self.row_map is None:
+            return torch.from_numpy(self.n_acc.copy()), torch.from_numpy(self.n_rej.copy())
+        self.all_acc[self.row_map], self.all_rej[self.row_map] = self.n_acc, self.n_rej
+        return torch.from_numpy(self.all_acc.copy()), torch.from_numpy(self.all_rej.copy())
+
+    _ROW_VECTORS = ("t0", "tprev", "dt", "active", "since", "next_out", "bad_y", "n_acc", "n_rej", "code")
+
+    def repack(self, y, f0, n_keep: int):
+        """Carry on with the `n_keep` active rows only, in their order: (y, f0) of those rows."""
+        if self.row_map is None:
+            self.row_map = np.arange(self.p.B)
+            self.all_acc = np.zeros(self.p.B, dtype=np.int64)
+            self.all_rej = np.zeros(self.p.B, dtype=np.int64)
+        self.all_acc[self.row_map], self.all_rej[self.row_map] = self.n_acc, self.n_rej     # the rows that leave keep theirs
+        keep = np.flatnonzero(self.active)
+        assert len(keep) == n_keep
+        for name in self._ROW_VECTORS:
+            setattr(self, name, getattr(self, name)[keep])
+        self.tg = self.tg[:, keep]
+        self.row_map = self.row_map[keep]
+        idx = torch.from_numpy(keep)
+        if self.s_shadow is not None:
+            self.s_shadow = self.s_shadow[idx]
+        if self.anchor is not None:
+            self.anchor = self.anchor[idx]
+        self.n = n_keep
+        self.p.keep_rows(idx)
+        return y[idx], f0[idx]
 
     # -- initial step ---------------------------------------------------------------------------------------------------
     def initial_step(self, y, f0) -> None:
@@ -309,10 +372,10 @@ class HostRowKernels:
             self.dt[:] = p.first_step.numpy()
         else:
             s0, s1 = self._row_norms(y.detach() / scale), self._row_norms(f0.detach() / scale)
-            h0 = np.empty(p.B, dtype=object)
+            h0 = np.empty(self.n, dtype=object)
             d1s = []
             with np.errstate(all="ignore"):
-                for r in range(p.B):
+                for r in range(self.n):
                     d0, d1 = T(math.sqrt(s0[r] / p.L)), T(math.sqrt(s1[r] / p.L))
                     h = T(1e-6) if (d0 < 1e-5 or d1 < 1e-5) else 0.01 * d0 / d1
                     h0[r] = abs(h)
@@ -323,7 +386,7 @@ class HostRowKernels:
                 shadow = rad.FirstStepShadow(_row_sum, y, f0, p.rtol, p.atol, p.sign)
                 c = rad.stitch_rows(c, shadow.h0, p.sign)
             y1 = y + f0 * c
-            t1 = torch.tensor([float(p.sign * T(self.t0[r] + float(h0[r]))) for r in range(p.B)], dtype=p.dtype)
+            t1 = torch.tensor([float(p.sign * T(self.t0[r] + float(h0[r]))) for r in range(self.n)], dtype=p.dtype)
             if shadow is not None:
                 t1 = rad.stitch_rows(t1, shadow.h0, p.sign)
             f1 = p.call(t1, y1)
@@ -332,7 +395,7 @@ class HostRowKernels:
                 self.s_shadow = shadow.finish(f1, p.method.order - 1)
             order = p.method.order - 1
             with np.errstate(all="ignore"):
-                for r in range(p.B):
+                for r in range(self.n):
                     hh, d1 = h0[r], d1s[r]
                     d2 = abs(T(math.sqrt(s2[r] / p.L)) / hh)
                     if d1 <= 1e-15 and d2 <= 1e-15:
@@ -341,7 +404,7 @@ class HostRowKernels:
                         h1 = power(rdiv(0.01, max(d1, d2)), 1.0 / float(order + 1))
                     h1 = abs(h1)
                     self.dt[r] = float(min(100 * hh, h1))
-        for r in range(p.B):
+        for r in range(self.n):
             self.prepare(r)
 
     # -- trial step -----------------------------------------------------------------------------------------------------
@@ -349,7 +412,7 @@ class HostRowKernels:
         """One trial step of every active row; returns the (y, f0) of the next one (the same tensors, committed in
         place, unless the solve is recorded)."""
         p, m, T = self.p, self.p.method, self.T
-        dts = self._dts_tensor([T(self.dt[r]) * T(p.sign) if self.active[r] else T(0) for r in range(p.B)])
+        dts = self._dts_tensor([T(self.dt[r]) * T(p.sign) if self.active[r] else T(0) for r in range(self.n)])
         shadow, self.s_shadow = self.s_shadow, None          # only the first trial step's size carries a graph
         anchor = self.anchor
         if shadow is not None:
@@ -371,7 +434,7 @@ class HostRowKernels:
         accepted = []
         n_out = self.tg.shape[0]
         with np.errstate(all="ignore"):
-            for r in range(p.B):
+            for r in range(self.n):
                 if not self.active[r]:
                     continue
                 ratio = float(T(math.sqrt(sums[r] / p.L)))
@@ -401,10 +464,10 @@ class HostRowKernels:
         if accepted:
             y, f0 = self._dense_commit(accepted, y, y1, f0, f1, ks, dts, sol, shadow, anchor)
         if shadow is not None and shadow.requires_grad:
-            took = torch.zeros(p.B, dtype=torch.float64)
+            took = torch.zeros(self.n, dtype=torch.float64)
             took[[r for r, _, _ in accepted]] = 1.0
             self.anchor = shadow * took
-        for r in range(p.B):
+        for r in range(self.n):
             if self.active[r]:
                 self.prepare(r)
         return y, f0
@@ -446,9 +509,9 @@ class HostRowKernels:
                     total = total + qc[n] * xs[1]
                     total = total + qb[n] * xs[2]
                     total = total + qa[n] * xs[3]
-                    sol[j, r] = total
+                    sol[j, r if self.row_map is None else self.row_map[r]] = total
         if p.record:
-            mask = torch.zeros(p.B, 1, dtype=torch.bool)
+            mask = torch.zeros(self.n, 1, dtype=torch.bool)
             mask[rows] = True
             return torch.where(mask, y1, y), torch.where(mask, f1, f0)
         y[rows] = y1[rows]
@@ -500,6 +563,8 @@ class HipRowKernels:
         self.plan = launch_plan(m.name)
         self.dts = None
         self.times = None
+        self.n = B                                           # rows now carried (fewer than p.B after a repack)
+        self.row_map = None                                  # after a repack: their original indices, int32 on the device
         # a recorded solve (differentiable=True): every launch below is handed to the recorder and becomes a graph node
         self.rec = rad.RowRecorder(self.k, p, _row_sum) if p.record else None
 
@@ -513,15 +578,52 @@ class HipRowKernels:
         n_active, r = self.status.tolist()                   # the two words the host reads per trial step
         if r == _NO_ERROR_ROW or n_active == 0:
             return n_active, None
-        return n_active, (r, int(self.code[r]), int(self.since[r]), float(self.dt[r]))
+        row = r if self.row_map is None else int(self.row_map[r])
+        return n_active, (row, int(self.code[r]), int(self.since[r]), float(self.dt[r]), r)
 
     def counts(self):
-        return self.n_acc.cpu(), self.n_rej.cpu()
+        if self.row_map is None:
+            return self.n_acc.cpu(), self.n_rej.cpu()
+        self._park_counts()
+        return self.all_acc.cpu(), self.all_rej.cpu()
+
+    def _park_counts(self) -> None:
+        rows = self.p.rows.to(self.all_acc.device)
+        self.all_acc.index_copy_(0, rows, self.n_acc)
+        self.all_rej.index_copy_(0, rows, self.n_rej)
+
+    _ROW_VECTORS = ("t0", "tprev", "dt", "h0", "ratio", "active", "accepted", "out_lo", "out_hi", "next_out", "since",
+                    "bad_y", "code", "n_acc", "n_rej")
+
+    def repack(self, y, f0, n_keep: int):
+        """Carry on with the `n_keep` active rows only, in their order: (y, f0) of those rows in fresh tensors (one
+        gather launch), every per-row vector of the state, the running step sizes, stage times and output grid
+        re-selected.  The workspace `part` and `status` keep their size; from here on the dense output goes through
+        `row_map` (`tdeq_row_dense_commit_mapped`)."""
+        p, st = self.p, self.st
+        if self.row_map is None:
+            self.all_acc, self.all_rej = torch.zeros_like(self.n_acc), torch.zeros_like(self.n_rej)
+        self._park_counts()                                  # the rows that leave keep their counters
+        keep = torch.nonzero(self.active).view(-1)           # ascending
+        assert keep.numel() == n_keep
+        y_new, f_new = y.new_empty(n_keep, p.L), f0.new_empty(n_keep, p.L)
+        self.k.row_gather([y_new, f_new], [y, f0], keep.to(torch.int32))
+        for name in self._ROW_VECTORS:
+            vec = getattr(self, name).index_select(0, keep)
+            setattr(self, name, vec)
+            setattr(st, name, vec.data_ptr())
+        self.tg = self.tg.index_select(1, keep)
+        st.tgrid = self.tg.data_ptr()
+        self.dts, self.times = self.dts.index_select(0, keep), self.times.index_select(1, keep)
+        st.n_rows = self.n = n_keep
+        p.keep_rows(keep)
+        self.row_map = p.rows.to(device=self.active.device, dtype=torch.int32)
+        return y_new, f_new
 
     def _control(self, mode: int) -> None:
         p = self.p
-        dts = torch.empty(p.B, dtype=p.dtype, device=p.device)
-        times = torch.empty(p.method.n_stages, p.B, dtype=p.dtype, device=p.device)
+        dts = torch.empty(self.n, dtype=p.dtype, device=p.device)
+        times = torch.empty(p.method.n_stages, self.n, dtype=p.dtype, device=p.device)
         self.k.row_control(mode, self.part, self.ctrl, self.st, dts, times, p.dtype)
         self.dts, self.times = dts, times
 
@@ -579,14 +681,17 @@ class HipRowKernels:
         t_start = None if rec is None else self.t0.clone()
         self._control(0)
         y_to, f0_to = (y, f0) if rec is None else (y.detach().clone(), f0.detach().clone())
-        k.row_dense_commit(sol, y_to, y1, f0_to, f1, mid, m.c_mid.coef, dts, self.st)
+        if self.row_map is None:
+            k.row_dense_commit(sol, y_to, y1, f0_to, f1, mid, m.c_mid.coef, dts, self.st)
+        else:                                                # a compacted batch: y, f0 at the compact index, sol at the original
+            k.row_dense_commit_mapped(sol, self.row_map, y_to, y1, f0_to, f1, mid, m.c_mid.coef, dts, self.st)
         if rec is None:
             return y, f0
         return rec.commit(self, sol, y, y1, f0, ks, dts, t_start, y_to, f0_to)
 
 
 def odeint_rowwise(func, y0, t, *, rtol=1e-7, atol=1e-9, method="dopri5", options=None, return_stats=False,
-                   event_fn=None, differentiable=False):
+                   event_fn=None, differentiable=False, compact=None):
     """Integrate B independent IVPs `dy_r/dt = func(t, y)[r]`, each row with its own adaptive step controller.
 
     `y0` is one tensor `[B, *row_shape]` (fp32 / fp64); row r is the IVP of `y0[r]`.  `t` is `[T]` (a grid shared by all
@@ -616,8 +721,22 @@ def odeint_rowwise(func, y0, t, *, rtol=1e-7, atol=1e-9, method="dopri5", option
     Every trial step's stage tensors stay alive until the backward, so memory grows with the number of trial
     iterations.  Time gradients (`t.requires_grad`) and second-order gradients (`create_graph=True`) raise
     NotImplementedError; under `torch.no_grad()` the argument has no effect.
+
+    `compact` (default None / False: off) takes the finished rows out of the batch instead of freezing them.  `True`
+    means 0.5; a float c in (0, 1] is the threshold: after the initial step and after every trial step, with `cur` rows
+    carried and `n_active` of them still active, `0 < n_active < cur` and `n_active <= c * cur` repacks the batch to the
+    active rows, in ascending original order (c = 1.0: whenever a row finishes; c = 0.5: at most log2(B) times).  The
+    solution, the per-row counters and the row named by an error message stay indexed by ORIGINAL row, and every bit of
+    them is what the plain solve gives (as long as `func` treats rows independently).  With `compact` set `func` is
+    called with a THIRD argument, `func(t_rows, y, rows)`: `rows` is an int64 `[b]` tensor on y0's device with the
+    original indices of the rows of this call, ascending; `t_rows` is `[b]`, `y` and the return value `[b, *row_shape]`.
+    Per-row parameters of `func` must be indexed with it (`k[rows]`).  Before the first repack `rows` is `arange(B)`;
+    between repacks a finished row is still evaluated and ignored, after the next repack it is gone.  `nfe` stays the
+    number of calls of `func`; `stats` gains `row_evals`, the sum of `y.shape[0]` over those calls, and `n_repacks`.
+    Anything else for `compact` raises ValueError; with `differentiable=True` and grad mode on it raises
+    NotImplementedError.
     """
-    p = _Problem(func, y0, t, rtol, atol, method, options, event_fn, differentiable)
+    p = _Problem(func, y0, t, rtol, atol, method, options, event_fn, differentiable, compact)
     n_t = p.tgrid.shape[0]
     f0 = None
     y_start = p.y0
@@ -651,6 +770,8 @@ def odeint_rowwise(func, y0, t, *, rtol=1e-7, atol=1e-9, method="dopri5", option
                         p.raise_row_error(failure, y)
                     if n_active == 0:
                         break
+                    if p.compact is not None and n_active < y.shape[0] and n_active <= p.compact * y.shape[0]:
+                        y, f0 = kern.repack(y, f0, n_active)
                     y, f0 = kern.trial_step(y, f0, sol)
             n_acc, n_rej = kern.counts()
         if p.record:
@@ -664,4 +785,7 @@ def odeint_rowwise(func, y0, t, *, rtol=1e-7, atol=1e-9, method="dopri5", option
     if n_acc is None:
         n_acc = torch.zeros(p.B, dtype=torch.int64)
         n_rej = torch.zeros(p.B, dtype=torch.int64)
-    return solution, {"n_accepted": n_acc.to(torch.int64), "n_rejected": n_rej.to(torch.int64), "nfe": p.nfe}
+    stats = {"n_accepted": n_acc.to(torch.int64), "n_rejected": n_rej.to(torch.int64), "nfe": p.nfe}
+    if p.compact is not None:
+        stats["row_evals"], stats["n_repacks"] = p.row_evals, p.n_repacks
+    return solution, stats
