@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define TDEQ_ABI_VERSION 24
+#define TDEQ_ABI_VERSION 25
 #define TDEQ_F32 0
 #define TDEQ_F64 1
 /* interleaved (re, im) complex states — accepted by the NORM entry points only (tdeq_error_norm, tdeq_error_norm_partial[_ctrl],
@@ -632,6 +632,21 @@ int tdeq_row_gather(void* const* dst, const void* const* src, int n_src, const i
 int tdeq_row_dense_commit_mapped(void* sol, const int32_t* row_map, int64_t sol_rows, void* y0, const void* y1, void* f0,
                                  const void* f1, const void* const* k, const double* coef, int n_terms, const void* dts,
                                  const tdeq_row_state* st, int dtype, void* stream);
+
+/*
+ * ---- Per-row tolerances of the row reductions (ABI 25; `odeint_rowwise(rtol=[B], atol=[B])`) ----
+ * tdeq_row_reduce_tol   tdeq_row_reduce with a tolerance pair per row: `rtol_rows`, `atol_rows` are device vectors
+ *                       [n_rows] of the state type (already rounded to it), and row r is reduced with rtol_rows[r],
+ *                       atol_rows[r] in every mode.  Same argument checks (a NULL tolerance pointer: TDEQ_EINVAL), same
+ *                       geometry, same layout of `part`, same element arithmetic: with rtol_rows[r] = T(rtol) and
+ *                       atol_rows[r] = T(atol) for every r it writes the bits of tdeq_row_reduce(rtol, atol), and a row's
+ *                       words do not depend on the tolerances of the other rows.  Per-element tolerances inside a row are
+ *                       not offered.
+ */
+int tdeq_row_reduce_tol(int mode, const void* y0, const void* y1, const void* partial, const void* const* k,
+                        const double* coef, int n_terms, const void* dts, const int32_t* active, const void* rtol_rows,
+                        const void* atol_rows, int64_t n_rows, int64_t row_len, double* part, size_t part_bytes, int dtype,
+                        void* stream);
 
 #ifdef __cplusplus
 }

@@ -1,7 +1,7 @@
 """odeint_rowwise cost against odeint's eager whole-batch step, bytes of its streaming launches, and per-row step counts
 on a mixed-stiffness batch.
 
-    python tools/rowwise_bench.py [--out profiles/rowwise_bench.json] [--reps 3]
+    python tools/rowwise_bench.py [--out profiles/rowwise_bench.json] [--reps 3] [--rowtol]
     python tools/rowwise_bench.py --stats <rocprofv3 kernel_stats.csv> --bench <that json>   (adds in-situ bandwidth)
     python tools/rowwise_bench.py --grad [--out profiles/rowwise_grad_bench.json] [--parity profiles/rowwise_grad_parity.json]
     python tools/rowwise_bench.py --grad --stats <kernel_stats.csv>[,<second>,...] --bench <that json>
@@ -15,6 +15,9 @@ any speed-up), the number of repacks and the time spent inside `repack`.
 `--grad`: forward + backward of a `differentiable=True` solve per trial step at the headline, next to plain `odeint`
 backprop of the same state, and (`--parity`) the per-row deviations of the rowwise gradients from the reference's
 (tests/golden/rowwise_grad.npz) on the host path and on the device.
+
+`--rowtol`: the headline's rowwise solve with `rtol` / `atol` as constant `[B]` vectors (tdeq_row_reduce_tol): the step
+sequence of the scalar solve, so the two figures compare launch for launch.
 
 Headline workload of bench.py: dopri5, func y @ A.T, 65536 x 128 fp32, rtol 1e-7, atol 1e-9.  A trial step of
 odeint_rowwise is one pass of its loop (S evaluations); odeint's is one call of its adaptive step; both are timed over
@@ -34,7 +37,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 PEAK_TBS = 8.0
 
 
-def _headline(reps: int):
+def _headline(reps: int, rowtol: bool = False):
     import torchdiffeq_amd as tda
     dev = torch.device("cuda", 0)
     B, D = 65536, 128
@@ -44,11 +47,14 @@ def _headline(reps: int):
     y0 = torch.randn(B, D, generator=g).to(dev)
     t = torch.tensor([0.0, 0.5], device=dev)
     calls = [0]
+    tol = dict(rtol=1e-7, atol=1e-9)
+    if rowtol:
+        tol = {k: torch.full((B,), v, dtype=torch.float64) for k, v in tol.items()}
 
     def f(t_, y):
         calls[0] += 1
         return y @ A.T
-    res = {"rowwise_ms_per_trial": [], "odeint_ms_per_trial": []}
+    res = {"rowwise_ms_per_trial": [], "odeint_ms_per_trial": [], "rowwise_tolerances": "[B] vectors" if rowtol else "scalars"}
     with torch.no_grad():
         for _ in range(reps + 1):
             for which in ("rowwise", "odeint"):
@@ -56,7 +62,7 @@ def _headline(reps: int):
                 torch.cuda.synchronize()
                 t0 = time.perf_counter()
                 if which == "rowwise":
-                    _, st = tda.odeint_rowwise(f, y0, t, rtol=1e-7, atol=1e-9, return_stats=True)
+                    _, st = tda.odeint_rowwise(f, y0, t, return_stats=True, **tol)
                 else:
                     tda.odeint(f, y0, t, rtol=1e-7, atol=1e-9, options={"hip_graph": False})
                 torch.cuda.synchronize()
@@ -275,7 +281,7 @@ _HEADLINE_LAUNCHES = {
     "row_combine_kernel<float, 3, true>": (5, "row 2", "avg"),
     "row_combine_kernel<float, 4, true>": (7, "row 3 + carried prefix of row 4", "avg"),
     "row_combine_kernel<float, 5, true>": (8, "row 5 (= y1) + partial error", "avg"),
-    "row_reduce_wave_kernel<float, 1, 0, true, true>": (4, "error (partial + k6) + row sums", "avg"),
+    "row_reduce_wave_kernel<float, 1, 0, true, true, false>": (4, "error (partial + k6) + row sums", "avg"),
     "row_dense_commit_kernel<float, 6, true>": (4, "commit y1 -> y0, f1 -> f0 (no output time)", "min"),
 }
 
@@ -308,6 +314,7 @@ def main():
     ap.add_argument("--grad", action="store_true")
     ap.add_argument("--parity", default=None)
     ap.add_argument("--compact", action="store_true")
+    ap.add_argument("--rowtol", action="store_true")
     a = ap.parse_args()
     if a.compact:
         res = {"device": torch.cuda.get_device_name(0), "arch": torch.cuda.get_device_properties(0).gcnArchName,
@@ -342,7 +349,7 @@ def main():
         json.dump(bench, open(a.bench, "w"), indent=1)
         print(json.dumps(bench["in_situ"], indent=1))
         return
-    res = {"device": torch.cuda.get_device_name(0), "headline": _headline(a.reps)}
+    res = {"device": torch.cuda.get_device_name(0), "headline": _headline(a.reps, a.rowtol)}
     lb = _launch_bytes()
     res["launch_bytes"] = lb
     res["launch_us_at_peak"] = {k: v / (PEAK_TBS * 1e12) * 1e6 for k, v in lb.items()}

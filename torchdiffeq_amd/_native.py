@@ -18,7 +18,7 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-TDEQ_ABI_VERSION = 24
+TDEQ_ABI_VERSION = 25
 TDEQ_F32, TDEQ_F64 = 0, 1
 TDEQ_C64, TDEQ_C128 = 2, 3        # interleaved complex: the norm entry points only (include/tdeq_hip.h)
 TDEQ_BF16, TDEQ_F16 = 4, 5        # reduced-precision states: the entry points of the host-driven step (LowPrecisionHipKernels)
@@ -241,6 +241,11 @@ ABI_SIGNATURES = {
                                                     ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, _c_void_pp,
                                                     _c_double_p, ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(RowState),
                                                     ctypes.c_int, ctypes.c_void_p]),
+    # per-row tolerances of the row reductions (ABI 25, odeint_rowwise(rtol=[B], atol=[B]))
+    "tdeq_row_reduce_tol": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, _c_void_pp,
+                                           _c_double_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                           ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p,
+                                           ctypes.c_size_t, ctypes.c_int, ctypes.c_void_p]),
 }
 
 
@@ -863,6 +868,23 @@ class HipKernels:
                                         None if active is None else active.data_ptr(), rtol, atol, y0.shape[0],
                                         y0.shape[1], part.data_ptr(), part.numel() * 8, dtype_code(y0.dtype),
                                         self._stream()), "tdeq_row_reduce")
+
+    def row_reduce_tol(self, mode: int, part, y0, y1, partial, ks, coefs, dts, active, rtol_rows, atol_rows) -> None:
+        """tdeq_row_reduce_tol: `row_reduce` with the tolerances of each row from two contiguous [B] tensors of the
+        state's dtype on its device."""
+        n = len(ks)
+        for v in (rtol_rows, atol_rows):
+            if v.shape != (y0.shape[0],) or v.dtype != y0.dtype or v.device != y0.device or not v.is_contiguous():
+                raise ValueError("row_reduce_tol: the tolerances must be contiguous [B] tensors of the state's dtype on "
+                                 "its device")
+        ptrs = (ctypes.c_void_p * max(n, 1))(*[k.data_ptr() for k in ks])
+        cf = (ctypes.c_double * max(n, 1))(*coefs)
+        _check(self.lib.tdeq_row_reduce_tol(mode, y0.data_ptr(), y1.data_ptr(),
+                                            None if partial is None else partial.data_ptr(), ptrs, cf, n,
+                                            None if dts is None else dts.data_ptr(),
+                                            None if active is None else active.data_ptr(), rtol_rows.data_ptr(),
+                                            atol_rows.data_ptr(), y0.shape[0], y0.shape[1], part.data_ptr(),
+                                            part.numel() * 8, dtype_code(y0.dtype), self._stream()), "tdeq_row_reduce_tol")
 
     def row_control(self, mode: int, part, ctrl: StepCtrl, st: RowState, dts_out, times_out, dtype) -> None:
         _check(self.lib.tdeq_row_control(mode, part.data_ptr(), ctypes.byref(ctrl), ctypes.byref(st), dts_out.data_ptr(),

@@ -93,31 +93,39 @@ int row_combine_dispatch(const tdeq_multi_out* outs, int n_out, const void* y0, 
     return TDEQ_EINVAL;
 }
 
-template <typename T, int NT, int MODE, bool PARTIAL>
-int row_reduce_launch(RowRedArgs<T, NT>& a, const RowGeom& g, bool vec, hipStream_t s) {
+template <typename T, int NT, int MODE, bool PARTIAL, bool ROWTOL>
+int row_reduce_launch(RowRedArgsOf<T, NT, ROWTOL>& a, const RowGeom& g, bool vec, hipStream_t s) {
     if (g.group > 0) {                // short row; a long row of one chunk (1024 < nv <= 2048) takes the chunk kernel,
         const int64_t threads = a.n_rows * g.group;      // whose part[q * B + r] is what the lane-per-row controller reads
         const dim3 grid((unsigned)((threads + kBlock - 1) / kBlock));
         a.group = g.group;
         a.nch = 1;
-        if (vec) hipLaunchKernelGGL((row_reduce_wave_kernel<T, NT, MODE, PARTIAL, true>), grid, dim3(kBlock), 0, s, a);
-        else hipLaunchKernelGGL((row_reduce_wave_kernel<T, NT, MODE, PARTIAL, false>), grid, dim3(kBlock), 0, s, a);
+        if (vec) hipLaunchKernelGGL((row_reduce_wave_kernel<T, NT, MODE, PARTIAL, true, ROWTOL>), grid, dim3(kBlock), 0, s, a);
+        else hipLaunchKernelGGL((row_reduce_wave_kernel<T, NT, MODE, PARTIAL, false, ROWTOL>), grid, dim3(kBlock), 0, s, a);
     } else {
         a.chunk = g.chunk;
         a.nch = (int)g.nch;
         const dim3 grid((unsigned)(a.n_rows * g.nch));
-        if (vec) hipLaunchKernelGGL((row_reduce_chunk_kernel<T, NT, MODE, PARTIAL, true>), grid, dim3(kBlock), 0, s, a);
-        else hipLaunchKernelGGL((row_reduce_chunk_kernel<T, NT, MODE, PARTIAL, false>), grid, dim3(kBlock), 0, s, a);
+        if (vec) hipLaunchKernelGGL((row_reduce_chunk_kernel<T, NT, MODE, PARTIAL, true, ROWTOL>), grid, dim3(kBlock), 0, s, a);
+        else hipLaunchKernelGGL((row_reduce_chunk_kernel<T, NT, MODE, PARTIAL, false, ROWTOL>), grid, dim3(kBlock), 0, s, a);
     }
     return check_launch();
 }
 
-template <typename T, int NT>
+// The tolerances of one reduce launch: the two scalars of tdeq_row_reduce, or the two [n_rows] device vectors of
+// tdeq_row_reduce_tol.
+struct RowTols {
+    double rtol, atol;
+    const void* rtol_rows;
+    const void* atol_rows;
+};
+
+template <typename T, int NT, bool ROWTOL>
 int row_reduce_n(int mode, const void* y0, const void* y1, const void* partial, const void* const* k,
-                 const double* coef, const void* dts, const int32_t* active, double rtol, double atol, int64_t n_rows,
+                 const double* coef, const void* dts, const int32_t* active, const RowTols& tol, int64_t n_rows,
                  int64_t row_len, double* part, hipStream_t s) {
     const RowGeom g = row_geom(row_len, std::is_same<T, float>::value ? TDEQ_F32 : TDEQ_F64);
-    RowRedArgs<T, NT> a;
+    RowRedArgsOf<T, NT, ROWTOL> a;
     a.y0 = static_cast<const T*>(y0);
     a.y1 = static_cast<const T*>(y1);
     a.partial = static_cast<const T*>(partial);
@@ -127,8 +135,15 @@ int row_reduce_n(int mode, const void* y0, const void* y1, const void* partial, 
     }
     a.dts = static_cast<const T*>(dts);
     a.active = active;
-    a.rtol = (T)rtol;
-    a.atol = (T)atol;
+    if constexpr (ROWTOL) {
+        a.rtol = (T)0;                // (not read)
+        a.atol = (T)0;
+        a.rtol_rows = static_cast<const T*>(tol.rtol_rows);
+        a.atol_rows = static_cast<const T*>(tol.atol_rows);
+    } else {
+        a.rtol = (T)tol.rtol;
+        a.atol = (T)tol.atol;
+    }
     a.row_len = g.nv;
     a.n_rows = n_rows;
     a.chunk = g.chunk;
@@ -139,26 +154,41 @@ int row_reduce_n(int mode, const void* y0, const void* y1, const void* partial, 
     for (int j = 0; j < NT; ++j) vec = vec && aligned16(k[j]);
     if (g.lv > 1 && !vec) return TDEQ_EINVAL;      // (the geometry, hence the sums, must not depend on alignment)
     if constexpr (NT == 0) {
-        if (mode == 1) return row_reduce_launch<T, NT, 1, false>(a, g, vec, s);
-        if (mode == 2) return row_reduce_launch<T, NT, 2, false>(a, g, vec, s);
+        if (mode == 1) return row_reduce_launch<T, NT, 1, false, ROWTOL>(a, g, vec, s);
+        if (mode == 2) return row_reduce_launch<T, NT, 2, false, ROWTOL>(a, g, vec, s);
         return TDEQ_EINVAL;
     } else {
         if (mode != 0) return TDEQ_EINVAL;
-        return partial ? row_reduce_launch<T, NT, 0, true>(a, g, vec, s) : row_reduce_launch<T, NT, 0, false>(a, g, vec, s);
+        return partial ? row_reduce_launch<T, NT, 0, true, ROWTOL>(a, g, vec, s)
+                       : row_reduce_launch<T, NT, 0, false, ROWTOL>(a, g, vec, s);
     }
 }
 
-template <typename T>
+template <typename T, bool ROWTOL>
 int row_reduce_dispatch(int mode, const void* y0, const void* y1, const void* partial, const void* const* k,
-                        const double* coef, int nt, const void* dts, const int32_t* active, double rtol, double atol,
+                        const double* coef, int nt, const void* dts, const int32_t* active, const RowTols& tol,
                         int64_t n_rows, int64_t row_len, double* part, hipStream_t s) {
     switch (nt) {
-#define TDEQ_CASE(N) case N: return row_reduce_n<T, N>(mode, y0, y1, partial, k, coef, dts, active, rtol, atol, n_rows, row_len, part, s);
+#define TDEQ_CASE(N) case N: return row_reduce_n<T, N, ROWTOL>(mode, y0, y1, partial, k, coef, dts, active, tol, n_rows, row_len, part, s);
         TDEQ_CASE(0) TDEQ_CASE(1) TDEQ_CASE(2) TDEQ_CASE(3) TDEQ_CASE(4) TDEQ_CASE(5) TDEQ_CASE(6) TDEQ_CASE(7)
         TDEQ_CASE(8) TDEQ_CASE(9) TDEQ_CASE(10) TDEQ_CASE(11) TDEQ_CASE(12) TDEQ_CASE(13) TDEQ_CASE(14)
 #undef TDEQ_CASE
     }
     return TDEQ_EINVAL;
+}
+
+// the argument checks the two reduce entry points share; > 0: nothing to do (no row)
+inline int row_reduce_check(int mode, const void* y0, const void* y1, const void* partial, const void* const* k,
+                            const double* coef, int n_terms, const void* dts, const int32_t* active, int64_t n_rows,
+                            int64_t row_len, const double* part, size_t part_bytes, int dtype) {
+    if (!y0 || !y1 || !part || n_rows < 0 || row_len < 1 || !(dtype == TDEQ_F32 || dtype == TDEQ_F64)) return TDEQ_EINVAL;
+    if (mode < 0 || mode > 2 || n_terms < 0 || n_terms > TDEQ_MAX_TERMS) return TDEQ_EINVAL;
+    if (mode == 0 && (n_terms < 1 || !k || !coef || !dts || !active)) return TDEQ_EINVAL;
+    if (mode != 0 && (n_terms != 0 || !partial)) return TDEQ_EINVAL;
+    for (int j = 0; j < n_terms; ++j) if (!k[j]) return TDEQ_EINVAL;
+    const int64_t nch = row_geom(row_len, dtype).nch;
+    if (part_bytes < (size_t)(3 * n_rows * nch) * sizeof(double)) return TDEQ_EWORKSPACE;
+    return n_rows == 0 ? 1 : 0;
 }
 
 template <typename T>
@@ -333,20 +363,33 @@ int tdeq_row_combine(const tdeq_multi_out* outs, int n_out, const void* y0, cons
 int tdeq_row_reduce(int mode, const void* y0, const void* y1, const void* partial, const void* const* k,
                     const double* coef, int n_terms, const void* dts, const int32_t* active, double rtol, double atol,
                     int64_t n_rows, int64_t row_len, double* part, size_t part_bytes, int dtype, void* stream) {
-    if (!y0 || !y1 || !part || n_rows < 0 || row_len < 1 || !row_dtype_ok(dtype)) return TDEQ_EINVAL;
-    if (mode < 0 || mode > 2 || n_terms < 0 || n_terms > TDEQ_MAX_TERMS) return TDEQ_EINVAL;
-    if (mode == 0 && (n_terms < 1 || !k || !coef || !dts || !active)) return TDEQ_EINVAL;
-    if (mode != 0 && (n_terms != 0 || !partial)) return TDEQ_EINVAL;
-    for (int j = 0; j < n_terms; ++j) if (!k[j]) return TDEQ_EINVAL;
-    const int64_t nch = row_geom(row_len, dtype).nch;
-    if (part_bytes < (size_t)(3 * n_rows * nch) * sizeof(double)) return TDEQ_EWORKSPACE;
-    if (n_rows == 0) return 0;
+    const int e = row_reduce_check(mode, y0, y1, partial, k, coef, n_terms, dts, active, n_rows, row_len, part, part_bytes,
+                                   dtype);
+    if (e) return e < 0 ? e : 0;
     hipStream_t s = static_cast<hipStream_t>(stream);
+    const RowTols tol = {rtol, atol, nullptr, nullptr};
     return dtype == TDEQ_F32
-               ? row_reduce_dispatch<float>(mode, y0, y1, partial, k, coef, n_terms, dts, active, rtol, atol, n_rows,
-                                            row_len, part, s)
-               : row_reduce_dispatch<double>(mode, y0, y1, partial, k, coef, n_terms, dts, active, rtol, atol, n_rows,
-                                             row_len, part, s);
+               ? row_reduce_dispatch<float, false>(mode, y0, y1, partial, k, coef, n_terms, dts, active, tol, n_rows,
+                                                   row_len, part, s)
+               : row_reduce_dispatch<double, false>(mode, y0, y1, partial, k, coef, n_terms, dts, active, tol, n_rows,
+                                                    row_len, part, s);
+}
+
+int tdeq_row_reduce_tol(int mode, const void* y0, const void* y1, const void* partial, const void* const* k,
+                        const double* coef, int n_terms, const void* dts, const int32_t* active, const void* rtol_rows,
+                        const void* atol_rows, int64_t n_rows, int64_t row_len, double* part, size_t part_bytes, int dtype,
+                        void* stream) {
+    if (!rtol_rows || !atol_rows) return TDEQ_EINVAL;
+    const int e = row_reduce_check(mode, y0, y1, partial, k, coef, n_terms, dts, active, n_rows, row_len, part, part_bytes,
+                                   dtype);
+    if (e) return e < 0 ? e : 0;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const RowTols tol = {0.0, 0.0, rtol_rows, atol_rows};
+    return dtype == TDEQ_F32
+               ? row_reduce_dispatch<float, true>(mode, y0, y1, partial, k, coef, n_terms, dts, active, tol, n_rows,
+                                                  row_len, part, s)
+               : row_reduce_dispatch<double, true>(mode, y0, y1, partial, k, coef, n_terms, dts, active, tol, n_rows,
+                                                   row_len, part, s);
 }
 
 int tdeq_row_control(int mode, const double* part, const tdeq_step_ctrl* ctrl, const tdeq_row_state* st,

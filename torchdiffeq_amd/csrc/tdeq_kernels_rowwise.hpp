@@ -102,6 +102,7 @@ __global__ __launch_bounds__(kBlock) void row_combine_kernel(const RowMultiArgs<
 // Row reductions.  MODE 0: embedded error  e = [partial +] sum_j fl_T(c_j * dts[r]) * k_j, then
 //   acc0 += (e / (atol + rtol * max(|y0|, |y1|)))^2, bad += !finite(y0) || !finite(y1)      (tol_accumulate)
 // MODE 1 / 2: the initial-step norms of init_elem (a = y0 or f1, b = f0, y = y0 for the scale).
+// rtol, atol: the two scalars of the argument block, or with ROWTOL the row's own (RowRedTolArgs) — in every mode.
 // Results: part[q * (B * nch) + r * nch + c], q = 0, 1 sums, q = 2 the non-finite count.
 // ------------------------------------------------------------------------------------------------
 template <typename T, int NT>
@@ -122,9 +123,21 @@ struct RowRedArgs {
     double* part;
 };
 
+// The per-row form (ROWTOL) serves `odeint_rowwise` with [B] tolerance vectors: row r is reduced with rtol_rows[r],
+// atol_rows[r] (already rounded to T by the caller) in place of the two scalars of the block, which it does not read.
+// The element arithmetic, the geometry and the layout of `part` are those of the plain form.
+template <typename T, int NT>
+struct RowRedTolArgs : RowRedArgs<T, NT> {
+    const T* rtol_rows;               // [n_rows]
+    const T* atol_rows;               // [n_rows]
+};
+
+template <typename T, int NT, bool ROWTOL>
+using RowRedArgsOf = typename std::conditional<ROWTOL, RowRedTolArgs<T, NT>, RowRedArgs<T, NT>>::type;
+
 template <typename T, int NT, int MODE, bool PARTIAL, typename E>
-__device__ __forceinline__ void row_red_elem(const RowRedArgs<T, NT>& a, const T (&cc)[NT > 0 ? NT : 1], int64_t i,
-                                             double (&acc)[3]) {
+__device__ __forceinline__ void row_red_elem(const RowRedArgs<T, NT>& a, const T (&cc)[NT > 0 ? NT : 1], T rtol, T atol,
+                                             int64_t i, double (&acc)[3]) {
     constexpr int LV = sizeof(E) / sizeof(T);
     if constexpr (MODE == 0) {
         E e;
@@ -137,20 +150,20 @@ __device__ __forceinline__ void row_red_elem(const RowRedArgs<T, NT>& a, const T
         }
         const E v0 = reinterpret_cast<const E*>(a.y0)[i], v1 = reinterpret_cast<const E*>(a.y1)[i];
         if constexpr (LV == 1) {
-            tol_accumulate<T>(e, v0, v1, a.rtol, a.atol, acc[0], acc[2]);
+            tol_accumulate<T>(e, v0, v1, rtol, atol, acc[0], acc[2]);
         } else {
 #pragma unroll
-            for (int q = 0; q < LV; ++q) tol_accumulate<T>(e[q], v0[q], v1[q], a.rtol, a.atol, acc[0], acc[2]);
+            for (int q = 0; q < LV; ++q) tol_accumulate<T>(e[q], v0[q], v1[q], rtol, atol, acc[0], acc[2]);
         }
     } else {
         const E yv = reinterpret_cast<const E*>(a.y0)[i];
         const E av = reinterpret_cast<const E*>(a.y1)[i];
         const E bv = reinterpret_cast<const E*>(a.partial)[i];
         if constexpr (LV == 1) {
-            init_elem<T, MODE - 1>(a.rtol, a.atol, av, bv, yv, acc);
+            init_elem<T, MODE - 1>(rtol, atol, av, bv, yv, acc);
         } else {
 #pragma unroll
-            for (int q = 0; q < LV; ++q) init_elem<T, MODE - 1>(a.rtol, a.atol, av[q], bv[q], yv[q], acc);
+            for (int q = 0; q < LV; ++q) init_elem<T, MODE - 1>(rtol, atol, av[q], bv[q], yv[q], acc);
         }
     }
 }
@@ -162,9 +175,22 @@ __device__ __forceinline__ void row_coefs(const RowRedArgs<T, NT>& a, int64_t r,
     for (int j = 0; j < NT; ++j) cc[j] = a.c[j] * dtT;
 }
 
+// the row's two tolerances: the block's scalars, or (ROWTOL) one load each per row, the same address for every lane that
+// serves the row
+template <typename T, int NT, bool ROWTOL>
+__device__ __forceinline__ void row_tols(const RowRedArgsOf<T, NT, ROWTOL>& a, int64_t r, T& rtol, T& atol) {
+    if constexpr (ROWTOL) {
+        rtol = a.rtol_rows[r];
+        atol = a.atol_rows[r];
+    } else {
+        rtol = a.rtol;
+        atol = a.atol;
+    }
+}
+
 // short rows: `group` lanes per row, 256 / group rows per workgroup
-template <typename T, int NT, int MODE, bool PARTIAL, bool VEC>
-__global__ __launch_bounds__(kBlock) void row_reduce_wave_kernel(const RowRedArgs<T, NT> a) {
+template <typename T, int NT, int MODE, bool PARTIAL, bool VEC, bool ROWTOL>
+__global__ __launch_bounds__(kBlock) void row_reduce_wave_kernel(const RowRedArgsOf<T, NT, ROWTOL> a) {
     using E = typename std::conditional<VEC, typename VecOf<T>::type, T>::type;
     const int g = a.group;
     const int lane = threadIdx.x & (g - 1);
@@ -174,8 +200,10 @@ __global__ __launch_bounds__(kBlock) void row_reduce_wave_kernel(const RowRedArg
     if (live) {
         T cc[NT > 0 ? NT : 1];
         row_coefs<T, NT>(a, r, cc);
+        T rtol, atol;
+        row_tols<T, NT, ROWTOL>(a, r, rtol, atol);
         const int64_t base = r * a.row_len;
-        for (int64_t e = lane; e < a.row_len; e += g) row_red_elem<T, NT, MODE, PARTIAL, E>(a, cc, base + e, acc);
+        for (int64_t e = lane; e < a.row_len; e += g) row_red_elem<T, NT, MODE, PARTIAL, E>(a, cc, rtol, atol, base + e, acc);
     }
     // butterfly over the group's lanes (the same tree for every row; lanes of other groups are never mixed in)
     for (int off = g >> 1; off > 0; off >>= 1) {
@@ -191,8 +219,8 @@ __global__ __launch_bounds__(kBlock) void row_reduce_wave_kernel(const RowRedArg
 }
 
 // long rows: one workgroup per (row, chunk)
-template <typename T, int NT, int MODE, bool PARTIAL, bool VEC>
-__global__ __launch_bounds__(kBlock) void row_reduce_chunk_kernel(const RowRedArgs<T, NT> a) {
+template <typename T, int NT, int MODE, bool PARTIAL, bool VEC, bool ROWTOL>
+__global__ __launch_bounds__(kBlock) void row_reduce_chunk_kernel(const RowRedArgsOf<T, NT, ROWTOL> a) {
     using E = typename std::conditional<VEC, typename VecOf<T>::type, T>::type;
     __shared__ double red[3 * (kBlock / kWave)];
     const int64_t b = blockIdx.x;
@@ -201,11 +229,14 @@ __global__ __launch_bounds__(kBlock) void row_reduce_chunk_kernel(const RowRedAr
     if (MODE != 0 || a.active[r]) {
         T cc[NT > 0 ? NT : 1];
         row_coefs<T, NT>(a, r, cc);
+        T rtol, atol;
+        row_tols<T, NT, ROWTOL>(a, r, rtol, atol);
         const int64_t lo = c * a.chunk;
         const int64_t hi = lo + a.chunk < a.row_len ? lo + a.chunk : a.row_len;
         const int64_t base = r * a.row_len;
 #pragma unroll 2
-        for (int64_t e = lo + threadIdx.x; e < hi; e += kBlock) row_red_elem<T, NT, MODE, PARTIAL, E>(a, cc, base + e, acc);
+        for (int64_t e = lo + threadIdx.x; e < hi; e += kBlock)
+            row_red_elem<T, NT, MODE, PARTIAL, E>(a, cc, rtol, atol, base + e, acc);
     }
     block_sum<3>(acc, red);
     if (threadIdx.x == 0) {

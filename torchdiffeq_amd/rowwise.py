@@ -3,8 +3,9 @@
 `odeint` treats a batched state as ONE system: the error ratio is the RMS over every element of the batch, so every
 row takes the same step sizes and the same accept / reject decisions, and a row's answer depends on its batch mates.
 Here row r of `y0[B, *row_shape]` is its own IVP: its own error norm (the RMS over its L = prod(row_shape) elements),
-its own step size, accept / reject decision, counters and output times.  A row's bits do not depend on B or on the
-other rows (as long as `func` itself treats rows independently).
+its own step size, accept / reject decision, counters and output times, and — with `rtol` / `atol` given as [B] vectors —
+its own tolerances.  A row's bits do not depend on B or on the other rows (as long as `func` itself treats rows
+independently).
 
 On a ROCm device every state-sized operation is a HIP kernel of csrc/tdeq_kernels_rowwise.hpp and the per-row
 controller runs on the device (the host reads two words per trial step); CPU states run the same row operations as
@@ -74,6 +75,34 @@ def _compact_fraction(compact):
     raise ValueError(f"odeint_rowwise: compact must be None, a bool or a fraction in (0, 1], got {compact!r}")
 
 
+def _tolerance(name: str, tol, B: int):
+    """`rtol` / `atol` of odeint_rowwise -> (float, None) for a number or a one-element tensor, (None, fp64 CPU tensor
+    [B]) for a per-row vector (a 1-D real tensor, a 1-D numpy array, a list or a tuple of numbers with B entries).  A
+    tensor is detached: no gradient flows to a tolerance.  The values are not looked at."""
+    if isinstance(tol, torch.Tensor) and tol.numel() == 1 and not tol.is_complex():
+        return float(tol), None
+    if isinstance(tol, (int, float)) and not isinstance(tol, bool):
+        return float(tol), None
+    if isinstance(tol, torch.Tensor):
+        shape, ok = tuple(tol.shape), tol.dim() == 1 and not tol.is_complex()
+        vec = tol.detach().to("cpu", torch.float64) if ok else None
+    elif isinstance(tol, np.ndarray):
+        shape, ok = tol.shape, tol.ndim == 1 and tol.dtype.kind in "fiu"
+        vec = torch.as_tensor(np.ascontiguousarray(tol), dtype=torch.float64) if ok else None
+    elif isinstance(tol, (list, tuple)):
+        shape = (len(tol),)
+        ok = all(isinstance(x, (int, float)) and not isinstance(x, bool) for x in tol)
+        vec = torch.as_tensor([float(x) for x in tol], dtype=torch.float64) if ok else None
+    else:
+        raise ValueError(f"odeint_rowwise: {name} must be a number or a per-row vector [B] = [{B}] (a 1-D tensor, numpy "
+                         f"array, list or tuple of numbers), got {type(tol).__name__}")
+    if not ok or shape != (B,):
+        raise ValueError(f"odeint_rowwise: {name} must be a number or a per-row vector of exactly B = {B} real entries, "
+                         f"got shape {tuple(shape)}; a vector of another length and tolerances per element of a row "
+                         "([B, *row_shape], [*row_shape]) are not supported")
+    return None, vec
+
+
 def _func_parameters_require_grad(func) -> bool:
     params = getattr(func, "parameters", None)
     if callable(params):
@@ -98,6 +127,7 @@ class _Problem:
                              "(16-bit, complex and integer states are not supported)")
         if y0.dim() < 1 or y0.shape[0] < 1:
             raise ValueError("odeint_rowwise: y0 must have a leading batch dimension B >= 1")
+        (rtol, rtol_rows), (atol, atol_rows) = _tolerance("rtol", rtol, y0.shape[0]), _tolerance("atol", atol, y0.shape[0])
         if method not in _METHODS:
             raise ValueError('odeint_rowwise: method "{}" is not supported; one of {}'.format(
                 method, ", ".join(sorted(_METHODS))))
@@ -106,13 +136,6 @@ class _Problem:
         if unknown:
             raise ValueError("odeint_rowwise: unsupported option(s) {}; supported: {}".format(
                 ", ".join(repr(u) for u in unknown), ", ".join(_OPTIONS)))
-        for name, tol in (("rtol", rtol), ("atol", atol)):
-            if isinstance(tol, torch.Tensor):
-                if tol.numel() != 1:
-                    raise ValueError(f"odeint_rowwise: vector tolerances are not supported ({name} has {tol.numel()} "
-                                     "elements)")
-            elif not isinstance(tol, (int, float)) or isinstance(tol, bool):
-                raise ValueError(f"odeint_rowwise: {name} must be a number (vector / tuple tolerances are not supported)")
         for name in STEP_CALLBACKS:
             if getattr(func, name, None) is not None:
                 raise ValueError(f"odeint_rowwise: step callbacks ({name}) are not supported")
@@ -160,7 +183,15 @@ class _Problem:
         self.sign = sign
         self.y0 = y0.detach().reshape(B, self.L).contiguous()
         self.y0_graph = y0.reshape(B, self.L) if self.record else None
-        self.rtol, self.atol = float(rtol), float(atol)
+        # the tolerances: two floats, or — as soon as one of them is a per-row vector — two [B] tensors in the state's
+        # dtype on its device (the other filled to [B]), rounded as the kernels round a scalar: T(x) of the fp64 value
+        self.rtol, self.atol = rtol, atol
+        self.rtol_rows = self.atol_rows = None
+        if rtol_rows is not None or atol_rows is not None:
+            rows = [torch.full((B,), x, dtype=torch.float64) if v is None else v
+                    for x, v in ((rtol, rtol_rows), (atol, atol_rows))]
+            self.rtol_rows, self.atol_rows = (v.to(self.dtype).to(self.device).contiguous() for v in rows)
+            self.rtol = self.atol = None
         self.method = _Method(method, self.np_dtype)
         fs = options.get("first_step")
         if fs is not None:
@@ -185,7 +216,17 @@ class _Problem:
     def keep_rows(self, idx: torch.Tensor) -> None:
         """A repack: the carried rows `idx` (int64 positions in the current batch, ascending) stay."""
         self.rows = self.rows.index_select(0, idx.to(self.rows.device))
+        if self.rtol_rows is not None:
+            at = idx.to(self.rtol_rows.device)
+            self.rtol_rows, self.atol_rows = self.rtol_rows.index_select(0, at), self.atol_rows.index_select(0, at)
         self.n_repacks += 1
+
+    def tolerances(self):
+        """(rtol, atol) as a torch expression over a [b, L] state takes them: the two floats, or the [b, 1] columns of the
+        per-row vectors of the rows now carried."""
+        if self.rtol_rows is None:
+            return self.rtol, self.atol
+        return self.rtol_rows[:, None], self.atol_rows[:, None]
 
     def grad_mode(self):
         """The grad mode the backends step in (inside the driver's no_grad): on for a recorded solve.  The controller is
@@ -365,7 +406,8 @@ class HostRowKernels:
     def initial_step(self, y, f0) -> None:
         p, T = self.p, self.T
         self.t0[:] = p.tgrid[0].numpy()
-        scale = p.atol + y.detach().abs() * p.rtol
+        rtol, atol = p.tolerances()
+        scale = atol + y.detach().abs() * rtol
         bad = (~torch.isfinite(y)).sum(dim=1).numpy()
         self.bad_y[:] = bad != 0
         if p.first_step is not None:
@@ -383,7 +425,7 @@ class HostRowKernels:
             c = torch.tensor([float(T(float(h) * p.sign)) for h in h0], dtype=p.dtype).reshape(-1, 1)
             shadow = None
             if p.record:
-                shadow = rad.FirstStepShadow(_row_sum, y, f0, p.rtol, p.atol, p.sign)
+                shadow = rad.FirstStepShadow(_row_sum, y, f0, rtol, atol, p.sign)
                 c = rad.stitch_rows(c, shadow.h0, p.sign)
             y1 = y + f0 * c
             t1 = torch.tensor([float(p.sign * T(self.t0[r] + float(h0[r]))) for r in range(self.n)], dtype=p.dtype)
@@ -428,7 +470,8 @@ class HostRowKernels:
         f1 = ks[-1]
         with torch.no_grad():                                # the controller is outside the graph
             err = self._sum_terms(ks, m.c_err, dts)
-            tol = p.atol + p.rtol * torch.maximum(y.abs(), y1.abs())
+            rtol, atol = p.tolerances()
+            tol = atol + rtol * torch.maximum(y.abs(), y1.abs())
             sums = self._row_norms(err / tol)
             bad = ((~torch.isfinite(y)) | (~torch.isfinite(y1))).sum(dim=1).numpy()
         accepted = []
@@ -627,9 +670,18 @@ class HipRowKernels:
         self.k.row_control(mode, self.part, self.ctrl, self.st, dts, times, p.dtype)
         self.dts, self.times = dts, times
 
+    def _reduce(self, mode: int, y0, y1, partial, ks, coefs, dts, active) -> None:
+        """The row reduction into `part`: with the two scalar tolerances, or with the [n] vectors of the rows now carried
+        (`_Problem.keep_rows` re-selects them at a repack)."""
+        p = self.p
+        if p.rtol_rows is None:
+            self.k.row_reduce(mode, self.part, y0, y1, partial, ks, coefs, dts, active, p.rtol, p.atol)
+        else:
+            self.k.row_reduce_tol(mode, self.part, y0, y1, partial, ks, coefs, dts, active, p.rtol_rows, p.atol_rows)
+
     def initial_step(self, y, f0) -> None:
         p, k, rec = self.p, self.k, self.rec
-        k.row_reduce(1, self.part, y, y, f0, [], [], None, None, p.rtol, p.atol)
+        self._reduce(1, y, y, f0, [], [], None, None)
         if p.first_step is not None:
             self.dt.copy_(p.first_step.to(self.dt.device))
             self._control(3)
@@ -640,7 +692,7 @@ class HipRowKernels:
         if rec is not None:
             y1, t1 = rec.first_probe(y, f0, y1, self.dts, t1)
         f1 = p.call(t1, y1)
-        k.row_reduce(2, self.part, y, f1, f0, [], [], None, None, p.rtol, p.atol)
+        self._reduce(2, y, f1, f0, [], [], None, None)
         self._control(2)
         if rec is not None:
             rec.first_step_size(f1)
@@ -674,8 +726,7 @@ class HipRowKernels:
                 ks.append(p.call(times[i], yi))
         y1, f1, mid = yi, ks[-1], [ks[j] for j in m.c_mid.idx]
         # the error norm continues the partial error row of the last combine (none: the whole row), then the controller
-        k.row_reduce(0, self.part, y, y1, held.pop(R, None), [ks[j] for j in plan.err_idx], plan.err_coef, dts, act,
-                     p.rtol, p.atol)
+        self._reduce(0, y, y1, held.pop(R, None), [ks[j] for j in plan.err_idx], plan.err_coef, dts, act)
         # dense output + commit y <- y1, f0 <- f1 of the accepted rows: in place, or, recorded, into fresh tensors (the
         # inputs stay alive for the backward)
         t_start = None if rec is None else self.t0.clone()
@@ -706,6 +757,15 @@ def odeint_rowwise(func, y0, t, *, rtol=1e-7, atol=1e-9, method="dopri5", option
     `safety`, `ifactor`, `dfactor`, `max_num_steps` (per row).  Everything else raises ValueError.  Error norm per
     row: the RMS over the row's elements of err / (atol + rtol * max(|y0|, |y1|)) — `odeint`'s norm for a one-row
     state — and the reference's controller per row.
+
+    `rtol` and `atol` are each a number (or a one-element tensor), or a per-row vector with exactly `B = y0.shape[0]`
+    entries: a 1-D tensor of any real dtype on any device, a 1-D numpy array, a list or a tuple of numbers.  Row r is then
+    integrated with `rtol[r]`, `atol[r]`; if only one of the two is a vector the other is filled to `[B]`.  Row r of such a
+    solve has the bits, the counts and the error behaviour of the one-row solve with the scalars `float(rtol[r])`,
+    `float(atol[r])`, and constant vectors give the bits of the scalar solve (both backends, with `compact` and with
+    `differentiable=True`).  A tolerance tensor is detached: no gradient flows to a tolerance.  Values are not validated,
+    as scalars are not.  A vector of another length and a tensor of two or more dimensions raise ValueError: tolerances
+    per element of a row (`[B, *row_shape]`, `[*row_shape]`) are not supported.
 
     Returns the solution `[T, *y0.shape]` with `solution[j, r]` = row r at `t[j]` (or `t[j, r]`); with
     `return_stats=True`, `(solution, stats)` where `stats` holds `n_accepted` and `n_rejected` (int64 `[B]`) and

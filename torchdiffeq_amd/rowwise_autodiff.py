@@ -166,7 +166,8 @@ class FirstStepShadow:
     ops on per-row quantities, beside the values the backend computed.  The branches are taken from the shadow's own
     norms.  `row_sum` is the backend-independent fixed-order row sum, so that a row's graph does not depend on B."""
 
-    def __init__(self, row_sum, y, f0, rtol: float, atol: float, sign: float):
+    def __init__(self, row_sum, y, f0, rtol, atol, sign: float):
+        # rtol, atol: two floats, or the [B, 1] columns of per-row tolerances (`rowwise._Problem.tolerances`)
         self.row_sum, self.sign = row_sum, sign
         self.f0 = f0
         self.L = y.shape[1]
@@ -240,7 +241,7 @@ class RowRecorder:
     def first_probe(self, y, f0, y1, dts, t1):
         """(y1, t1) of the initial-step heuristic's probe y1 = y + h0 f0 at t1 = t0 + h0, as graph tensors."""
         p = self.p
-        self.first = FirstStepShadow(self.row_sum, y, f0, p.rtol, p.atol, p.sign)
+        self.first = FirstStepShadow(self.row_sum, y, f0, *p.tolerances(), p.sign)
         return (row_linear(self.k, y1, [y, f0], [1.0, dts], s=self.first.h0, dw=[0.0, p.sign]),
                 stitch_rows(t1, self.first.h0, p.sign))
 
