@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define TDEQ_ABI_VERSION 25
+#define TDEQ_ABI_VERSION 26
 #define TDEQ_F32 0
 #define TDEQ_F64 1
 /* interleaved (re, im) complex states — accepted by the NORM entry points only (tdeq_error_norm, tdeq_error_norm_partial[_ctrl],
@@ -647,6 +647,34 @@ int tdeq_row_reduce_tol(int mode, const void* y0, const void* y1, const void* pa
                         const double* coef, int n_terms, const void* dts, const int32_t* active, const void* rtol_rows,
                         const void* atol_rows, int64_t n_rows, int64_t row_len, double* part, size_t part_bytes, int dtype,
                         void* stream);
+
+/*
+ * ---- Per-row terminal events (ABI 26; torchdiffeq_amd/rowwise_event.py `odeint_rowwise_event`) ----
+ * tdeq_row_event_detect  after tdeq_row_control(mode 0), one lane per row.  `g1` [n_rows] of the state type holds the event
+ *                        value at the end of each row's trial step, `sign0` [n_rows] the row's starting sign, sign(g) =
+ *                        (g > 0) - (g < 0) (0 for a NaN).  A row with accepted[r] && !fired[r] && sign(g1[r]) != sign0[r]
+ *                        fires: fired[r] = fired_now[r] = 1, lo[r] = tprev[r], hi[r] = t0[r]; if it is still active,
+ *                        active[r] = 0, status[0] -= 1 and `dts` [n_rows] / `times` [n_times, n_rows] — the buffers the
+ *                        controller just wrote for the next trial step — are frozen as for a finished row (0 and
+ *                        time_sign * T(t0[r])).  Every other row gets fired_now[r] = 0 and nothing else.  `ctrl` gives
+ *                        n_times and time_sign.
+ * tdeq_row_event_fit     for the rows with fired_now[r]: the quartic of the step (y0, y1, f0, f1, the mid-point stages `k`
+ *                        with fl_T(fl_T(coef_j) * dts[r])) as tdeq_row_dense_commit forms it, its coefficients e, d, c, b, a
+ *                        stored at q[j, r, :] of a [5, n_rows, row_len] buffer.  Other rows are neither read nor written.
+ *                        Runs before the commit, which overwrites y0 and f0.
+ * tdeq_row_event_eval    out[r, :] = the quartic q[:, r, :] at x[r] (`x` [n_rows] of the state type) for the rows with
+ *                        mask[r]; other rows of `out` are untouched.
+ * 16-byte elements when row_len is a multiple of 16 / sizeof(T) and every state-sized pointer is 16-byte aligned, scalar
+ * elements otherwise.  n_rows == 0: no-op.
+ */
+int tdeq_row_event_detect(const void* g1, const int32_t* sign0, const tdeq_step_ctrl* ctrl, const tdeq_row_state* st,
+                          void* dts, void* times, int32_t* fired, int32_t* fired_now, double* lo, double* hi, int dtype,
+                          void* stream);
+int tdeq_row_event_fit(void* q, const int32_t* fired_now, const void* y0, const void* y1, const void* f0, const void* f1,
+                       const void* const* k, const double* coef, int n_terms, const void* dts, int64_t n_rows,
+                       int64_t row_len, int dtype, void* stream);
+int tdeq_row_event_eval(void* out, const void* q, const void* x, const int32_t* mask, int64_t n_rows, int64_t row_len,
+                        int dtype, void* stream);
 
 #ifdef __cplusplus
 }

@@ -7,10 +7,20 @@ on a mixed-stiffness batch.
     python tools/rowwise_bench.py --grad --stats <kernel_stats.csv>[,<second>,...] --bench <that json>
                                                                  (row_scale_many bandwidth, one csv per traced repeat)
     python tools/rowwise_bench.py --compact [--out profiles/rowwise_compact_bench.json] [--reps 5]
+    python tools/rowwise_bench.py --event [--reps 5]          (one JSON line: plain and event solve of one fresh process)
+    python tools/rowwise_bench.py --event --plain-only        (the plain solve alone: also runs on a tree without events)
+    python tools/rowwise_bench.py --event-summary parent.jsonl,new_plain.jsonl,new_event.jsonl --out profiles/rowwise_event_bench.json
 
 `--compact`: wall time of one solve at the headline shape with a per-row rate spread over logspace(-1, 1.5) (so that the
 rows' trial counts differ), plain against `compact=0.5` and `compact=1.0`: `row_evals` against `nfe x B` (the bound on
 any speed-up), the number of repacks and the time spent inside `repack`.
+
+`--event`: the headline's plain rowwise solve and `odeint_rowwise_event` of the same func (event: y[:, 0] falls 0.25 below
+its start, t_end = 0.5, so that some rows fire and the others reach t_end), each the median of `--reps` solves after a
+warm-up, then one instrumented event solve with the time inside `event_fn` during the trial steps and inside the final
+bisection measured between synchronisations.  One fresh process per figure; `--event-summary` folds the lines of
+alternated processes (parent tree plain, this tree plain, this tree event) into the medians and spreads of
+profiles/rowwise_event_bench.json.
 
 `--grad`: forward + backward of a `differentiable=True` solve per trial step at the headline, next to plain `odeint`
 backprop of the same state, and (`--parity`) the per-row deviations of the rowwise gradients from the reference's
@@ -140,6 +150,113 @@ def _compact(reps: int):
         r["speedup"] = med(res["plain"]["ms_per_solve"]) / r["ms_per_solve_median"]
     return {"B": B, "L": D, "dtype": "float32", "method": "dopri5", "rtol": 1e-7, "atol": 1e-9,
             "rate_spread": "k_r in logspace(-1, 1.5), shuffled; func k_r * (y @ A.T)", **res}
+
+
+def _event(reps: int, plain_only: bool):
+    """One process's figures: ms per trial step of the plain headline solve and (unless `plain_only`) of the event solve."""
+    import torchdiffeq_amd as tda
+    dev = torch.device("cuda", 0)
+    B, D = 65536, 128
+    g = torch.Generator().manual_seed(0)
+    G = torch.randn(D, D, generator=g, dtype=torch.float64) / D ** 0.5
+    A = (0.5 * (G - G.T) - 0.1 * torch.eye(D, dtype=torch.float64)).float().to(dev)
+    y0 = torch.randn(B, D, generator=g).to(dev)
+    t = torch.tensor([0.0, 0.5], device=dev)
+    level = y0[:, 0] - 0.25
+    med = lambda v: sorted(v)[len(v) // 2]       # noqa: E731
+
+    def f(t_, y):
+        return y @ A.T
+
+    def ev(t_, y):
+        return y[:, 0] - level
+
+    def timed(solve):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = solve()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3, out
+    res = {}
+    with torch.no_grad():
+        ms = []
+        for rep in range(reps + 1):
+            took, (_, st) = timed(lambda: tda.odeint_rowwise(f, y0, t, rtol=1e-7, atol=1e-9, return_stats=True))
+            trials = (st["nfe"] - 2) / 6
+            if rep:                           # the first solve warms up
+                ms.append(took / trials)
+        res["plain"] = {"ms_per_trial": ms, "median_ms_per_trial": med(ms), "trials_per_solve": trials}
+        if plain_only:
+            return res
+        from torchdiffeq_amd import rowwise_event
+        solve = lambda fn=ev: tda.odeint_rowwise_event(f, y0, 0.0, event_fn=fn, t_end=0.5, rtol=1e-7, atol=1e-9,      # noqa: E731
+                                                        return_stats=True)
+        ms = []
+        for rep in range(reps + 1):
+            took, (_, _, st) = timed(solve)
+            if rep:
+                ms.append(took)
+        trials = (st["nfe"] - 2) / 6
+        # one more solve, instrumented: event_fn during the trial steps and the whole final bisection between synchronisations
+        inside = {"event_fn": 0.0, "bisection": 0.0, "in_bisection": False}
+
+        def timed_ev(t_, y):
+            if inside["in_bisection"]:
+                return ev(t_, y)
+            took, out = timed(lambda: ev(t_, y))
+            inside["event_fn"] += took
+            return out
+        plain_locate = rowwise_event._locate
+
+        def timed_locate(*a):
+            inside["in_bisection"] = True
+            took, out = timed(lambda: plain_locate(*a))
+            inside["bisection"] += took
+            return out
+        rowwise_event._locate = timed_locate
+        try:
+            solve(timed_ev)
+        finally:
+            rowwise_event._locate = plain_locate
+        n_steps_calls = 1 + int(trials)                       # event_fn at t0 and once per trial step
+        res["event"] = {"ms_per_solve": ms, "median_ms_per_solve": med(ms), "trials_per_solve": trials,
+                        "rows_fired": int(st["fired"].sum()), "n_event_evals": st["n_event_evals"],
+                        "bisection_rounds": st["n_event_evals"] - n_steps_calls,
+                        "ms_inside_bisection": inside["bisection"], "ms_inside_event_fn_while_stepping": inside["event_fn"],
+                        "median_ms_per_trial_without_bisection": (med(ms) - inside["bisection"]) / trials,
+                        "event_fn_ms_per_trial": inside["event_fn"] / n_steps_calls}
+    return res
+
+
+def _event_summary(paths, out):
+    """Fold the JSON lines of the alternated fresh processes (parent plain, this tree plain, this tree event; the first
+    line of each file is the warm-up round) into medians and spreads."""
+    med = lambda v: sorted(v)[len(v) // 2]       # noqa: E731
+    lines = [[json.loads(x) for x in open(p) if x.strip().startswith("{")][1:] for p in paths]
+    parent, new_plain, new_event = lines
+
+    def fold(vals):
+        return {"per_process": [round(v, 4) for v in vals], "median": round(med(vals), 4), "min": round(min(vals), 4),
+                "max": round(max(vals), 4)}
+    res = {"what": "tools/rowwise_bench.py --event: 65536 x 128 fp32 dopri5, func y @ A.T, rtol 1e-7, atol 1e-9; every figure "
+                   "the median of 5 solves of one fresh process; parent tree (plain), this tree (plain) and this tree (event "
+                   "solve: y[:, 0] falls 0.25 below its start, t_end 0.5) alternated, %d rounds after a warm-up round" % len(parent),
+           "parent_plain_ms_per_trial": fold([r["plain"]["median_ms_per_trial"] for r in parent]),
+           "new_plain_ms_per_trial": fold([r["plain"]["median_ms_per_trial"] for r in new_plain]),
+           "event_ms_per_trial_without_bisection": fold([r["event"]["median_ms_per_trial_without_bisection"] for r in new_event]),
+           "event_fn_ms_per_trial": fold([r["event"]["event_fn_ms_per_trial"] for r in new_event]),
+           "bisection_ms_per_solve": fold([r["event"]["ms_inside_bisection"] for r in new_event]),
+           "event_ms_per_solve": fold([r["event"]["median_ms_per_solve"] for r in new_event]),
+           "event_solve": {k: new_event[-1]["event"][k] for k in ("trials_per_solve", "rows_fired", "n_event_evals",
+                                                                   "bisection_rounds")},
+           "plain_trials_per_solve": new_plain[-1]["plain"]["trials_per_solve"]}
+    pp, npl = res["parent_plain_ms_per_trial"], res["new_plain_ms_per_trial"]
+    res["new_plain_median_inside_parent_min_max"] = pp["min"] <= npl["median"] <= pp["max"]
+    extra = res["event_ms_per_trial_without_bisection"]["median"] - pp["median"]
+    res["event_extra_ms_per_trial_over_parent_plain"] = round(extra, 4)
+    res["event_fn_share_of_extra"] = round(res["event_fn_ms_per_trial"]["median"] / extra, 3) if extra > 0 else None
+    json.dump(res, open(out, "w"), indent=1)
+    print(json.dumps(res))
 
 
 def _grad_headline(reps: int):
@@ -315,7 +432,18 @@ def main():
     ap.add_argument("--parity", default=None)
     ap.add_argument("--compact", action="store_true")
     ap.add_argument("--rowtol", action="store_true")
+    ap.add_argument("--event", action="store_true")
+    ap.add_argument("--plain-only", action="store_true")
+    ap.add_argument("--event-summary", default=None)
     a = ap.parse_args()
+    if a.event_summary:
+        _event_summary(a.event_summary.split(","), a.out)
+        return
+    if a.event:
+        res = {"device": torch.cuda.get_device_name(0), "arch": torch.cuda.get_device_properties(0).gcnArchName,
+               **_event(a.reps, a.plain_only)}
+        print(json.dumps(res))
+        return
     if a.compact:
         res = {"device": torch.cuda.get_device_name(0), "arch": torch.cuda.get_device_properties(0).gcnArchName,
                "compact": _compact(a.reps)}

@@ -11,7 +11,8 @@ from .adjoint import odeint_adjoint
 from .solvers import clear_graph_cache
 from ._fallback import HostPathWarning
 from .rowwise import odeint_rowwise
+from .rowwise_event import odeint_rowwise_event
 
 __version__ = "0.1.0"
-__all__ = ["odeint", "odeint_adjoint", "odeint_rowwise", "odeint_event", "odeint_dense", "SOLVERS", "clear_graph_cache",
+__all__ = ["odeint", "odeint_adjoint", "odeint_rowwise", "odeint_rowwise_event", "odeint_event", "odeint_dense", "SOLVERS", "clear_graph_cache",
            "HostPathWarning"]

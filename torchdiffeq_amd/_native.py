@@ -18,7 +18,7 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-TDEQ_ABI_VERSION = 25
+TDEQ_ABI_VERSION = 26
 TDEQ_F32, TDEQ_F64 = 0, 1
 TDEQ_C64, TDEQ_C128 = 2, 3        # interleaved complex: the norm entry points only (include/tdeq_hip.h)
 TDEQ_BF16, TDEQ_F16 = 4, 5        # reduced-precision states: the entry points of the host-driven step (LowPrecisionHipKernels)
@@ -246,6 +246,16 @@ ABI_SIGNATURES = {
                                            _c_double_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                            ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p,
                                            ctypes.c_size_t, ctypes.c_int, ctypes.c_void_p]),
+    # per-row terminal events (ABI 26, rowwise_event.py)
+    "tdeq_row_event_detect": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(StepCtrl),
+                                             ctypes.POINTER(RowState), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                             ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+                                             ctypes.c_void_p]),
+    "tdeq_row_event_fit": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                          ctypes.c_void_p, ctypes.c_void_p, _c_void_pp, _c_double_p, ctypes.c_int,
+                                          ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p]),
+    "tdeq_row_event_eval": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                           ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p]),
 }
 
 
@@ -936,6 +946,36 @@ class HipKernels:
                                            None if ws is None else ws.data_ptr(), nbytes, dtype_code(g.dtype),
                                            self._stream()), "tdeq_row_multi_dot")
         return out
+
+    # -- per-row terminal events (odeint_rowwise_event, rowwise_event.py) ----------------------------------------------
+    def row_event_detect(self, g1, sign0, ctrl: StepCtrl, st: RowState, dts, times, fired, fired_now, lo, hi) -> None:
+        """tdeq_row_event_detect: `g1` [n] of the state dtype, `sign0` / `fired` / `fired_now` int32 [n], `lo` / `hi` fp64
+        [n]; `dts` [n] and `times` [n_times, n] are the buffers the controller just wrote."""
+        n = int(st.n_rows)
+        if g1.shape != (n,) or g1.dtype != dts.dtype or not g1.is_contiguous():
+            raise ValueError("row_event_detect: g1 must be a contiguous [n_rows] tensor of the state's dtype")
+        _check(self.lib.tdeq_row_event_detect(g1.data_ptr(), sign0.data_ptr(), ctypes.byref(ctrl), ctypes.byref(st),
+                                              dts.data_ptr(), times.data_ptr(), fired.data_ptr(), fired_now.data_ptr(),
+                                              lo.data_ptr(), hi.data_ptr(), dtype_code(g1.dtype), self._stream()),
+               "tdeq_row_event_detect")
+
+    def row_event_fit(self, q, fired_now, y0, y1, f0, f1, ks, coefs, dts) -> None:
+        """tdeq_row_event_fit: `q` a contiguous [5, n, L] tensor of the state's dtype."""
+        if q.shape != (5,) + tuple(y0.shape) or q.dtype != y0.dtype or not q.is_contiguous():
+            raise ValueError("row_event_fit: q must be a contiguous [5, n_rows, L] tensor of the state's dtype")
+        ptrs, cf, n = self._terms(ks, coefs)
+        _check(self.lib.tdeq_row_event_fit(q.data_ptr(), fired_now.data_ptr(), y0.data_ptr(), y1.data_ptr(), f0.data_ptr(),
+                                           f1.data_ptr(), ptrs, cf, n, dts.data_ptr(), y0.shape[0], y0.shape[1],
+                                           dtype_code(y0.dtype), self._stream()), "tdeq_row_event_fit")
+
+    def row_event_eval(self, out, q, x, mask) -> None:
+        """tdeq_row_event_eval: out[r, :] = q[:, r, :] at x[r] for the rows with mask[r] (int32 [n])."""
+        if q.shape != (5,) + tuple(out.shape) or q.dtype != out.dtype or not q.is_contiguous() or not out.is_contiguous():
+            raise ValueError("row_event_eval: q must be a contiguous [5, n_rows, L] tensor of out's dtype")
+        if x.shape != (out.shape[0],) or x.dtype != out.dtype or not x.is_contiguous():
+            raise ValueError("row_event_eval: x must be a contiguous [n_rows] tensor of out's dtype")
+        _check(self.lib.tdeq_row_event_eval(out.data_ptr(), q.data_ptr(), x.data_ptr(), mask.data_ptr(), out.shape[0],
+                                            out.shape[1], dtype_code(out.dtype), self._stream()), "tdeq_row_event_eval")
 
 
 class ComplexHipKernels:

@@ -4,6 +4,7 @@
 #pragma once
 
 #include "tdeq_kernels_rowwise.hpp"
+#include "tdeq_kernels_rowwise_event.hpp"
 
 namespace {
 using namespace tdeq;
@@ -608,4 +609,126 @@ int tdeq_row_multi_dot(const void* g, const void* const* x, int n_x, int64_t n_r
     double* ws = static_cast<double*>(workspace);
     return dtype == TDEQ_F32 ? row_dot_dispatch<float>(g, x, n_x, n_rows, row_len, out, ws, s)
                              : row_dot_dispatch<double>(g, x, n_x, n_rows, row_len, out, ws, s);
+}
+
+// ---- per-row terminal events: tdeq_row_event_detect / tdeq_row_event_fit / tdeq_row_event_eval ------------------------
+namespace {
+
+template <typename T, int NT>
+int row_event_fit_n(void* q, const int32_t* fired_now, const void* y0, const void* y1, const void* f0, const void* f1,
+                    const void* const* k, const double* coef, const void* dts, int64_t n_rows, int64_t row_len,
+                    hipStream_t s) {
+    RowEventFitArgs<T, NT> a;
+    a.q = static_cast<T*>(q);
+    a.y0 = static_cast<const T*>(y0);
+    a.y1 = static_cast<const T*>(y1);
+    a.f0 = static_cast<const T*>(f0);
+    a.f1 = static_cast<const T*>(f1);
+    for (int j = 0; j < NT; ++j) {
+        a.k[j] = static_cast<const T*>(k[j]);
+        a.c[j] = (T)coef[j];
+    }
+    a.dts = static_cast<const T*>(dts);
+    a.fired_now = fired_now;
+    a.n = n_rows * row_len;
+    const int lv = row_lanes(row_len, std::is_same<T, float>::value ? TDEQ_F32 : TDEQ_F64);
+    bool vec = lv > 1 && aligned16(q) && aligned16(y0) && aligned16(y1) && aligned16(f0) && aligned16(f1);
+    for (int j = 0; j < NT; ++j) vec = vec && aligned16(k[j]);
+    if (vec) {
+        a.row_len = row_len / lv;
+        hipLaunchKernelGGL((row_event_fit_kernel<T, NT, true>), dim3(stream_grid(a.n / lv, kBlock)), dim3(kBlock), 0, s, a);
+    } else {
+        a.row_len = row_len;
+        hipLaunchKernelGGL((row_event_fit_kernel<T, NT, false>), dim3(stream_grid(a.n, kBlock)), dim3(kBlock), 0, s, a);
+    }
+    return check_launch();
+}
+
+template <typename T>
+int row_event_fit_dispatch(void* q, const int32_t* fired_now, const void* y0, const void* y1, const void* f0,
+                           const void* f1, const void* const* k, const double* coef, int nt, const void* dts,
+                           int64_t n_rows, int64_t row_len, hipStream_t s) {
+    switch (nt) {
+#define TDEQ_CASE(N) case N: return row_event_fit_n<T, N>(q, fired_now, y0, y1, f0, f1, k, coef, dts, n_rows, row_len, s);
+        TDEQ_CASE(1) TDEQ_CASE(2) TDEQ_CASE(3) TDEQ_CASE(4) TDEQ_CASE(5) TDEQ_CASE(6) TDEQ_CASE(7)
+        TDEQ_CASE(8) TDEQ_CASE(9) TDEQ_CASE(10) TDEQ_CASE(11) TDEQ_CASE(12) TDEQ_CASE(13) TDEQ_CASE(14)
+#undef TDEQ_CASE
+    }
+    return TDEQ_EINVAL;
+}
+
+template <typename T>
+int row_event_eval_launch(void* out, const void* q, const void* x, const int32_t* mask, int64_t n_rows, int64_t row_len,
+                          hipStream_t s) {
+    RowEventEvalArgs<T> a;
+    a.out = static_cast<T*>(out);
+    a.q = static_cast<const T*>(q);
+    a.x = static_cast<const T*>(x);
+    a.mask = mask;
+    a.n = n_rows * row_len;
+    const int lv = row_lanes(row_len, std::is_same<T, float>::value ? TDEQ_F32 : TDEQ_F64);
+    if (lv > 1 && aligned16(out) && aligned16(q)) {
+        a.row_len = row_len / lv;
+        hipLaunchKernelGGL((row_event_eval_kernel<T, true>), dim3(stream_grid(a.n / lv, kBlock)), dim3(kBlock), 0, s, a);
+    } else {
+        a.row_len = row_len;
+        hipLaunchKernelGGL((row_event_eval_kernel<T, false>), dim3(stream_grid(a.n, kBlock)), dim3(kBlock), 0, s, a);
+    }
+    return check_launch();
+}
+
+}  // namespace
+
+int tdeq_row_event_detect(const void* g1, const int32_t* sign0, const tdeq_step_ctrl* ctrl, const tdeq_row_state* st,
+                          void* dts, void* times, int32_t* fired, int32_t* fired_now, double* lo, double* hi, int dtype,
+                          void* stream) {
+    if (!g1 || !sign0 || !ctrl || !st || !dts || !times || !fired || !fired_now || !lo || !hi || !row_dtype_ok(dtype))
+        return TDEQ_EINVAL;
+    if (st->n_rows < 0 || !st->accepted || !st->tprev || !st->t0 || !st->active || !st->status) return TDEQ_EINVAL;
+    if (ctrl->n_times < 1 || ctrl->n_times > TDEQ_MAX_STAGE_TIMES) return TDEQ_EINVAL;
+    if (st->n_rows == 0) return 0;
+    RowEventDetectArgs a;
+    a.g1 = g1;
+    a.sign0 = sign0;
+    a.accepted = st->accepted;
+    a.tprev = st->tprev;
+    a.t0 = st->t0;
+    a.active = st->active;
+    a.status = st->status;
+    a.dts = dts;
+    a.times = times;
+    a.n_times = ctrl->n_times;
+    a.time_sign = ctrl->time_sign;
+    a.n_rows = st->n_rows;
+    a.fired = fired;
+    a.fired_now = fired_now;
+    a.lo = lo;
+    a.hi = hi;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const dim3 grid((unsigned)((a.n_rows + kBlock - 1) / kBlock));
+    if (dtype == TDEQ_F32) hipLaunchKernelGGL((row_event_detect_kernel<float>), grid, dim3(kBlock), 0, s, a);
+    else hipLaunchKernelGGL((row_event_detect_kernel<double>), grid, dim3(kBlock), 0, s, a);
+    return check_launch();
+}
+
+int tdeq_row_event_fit(void* q, const int32_t* fired_now, const void* y0, const void* y1, const void* f0, const void* f1,
+                       const void* const* k, const double* coef, int n_terms, const void* dts, int64_t n_rows,
+                       int64_t row_len, int dtype, void* stream) {
+    if (!q || !fired_now || !y0 || !y1 || !f0 || !f1 || !k || !coef || !dts || !row_dtype_ok(dtype)) return TDEQ_EINVAL;
+    if (n_terms < 1 || n_terms > TDEQ_MAX_TERMS || n_rows < 0 || row_len < 1) return TDEQ_EINVAL;
+    for (int j = 0; j < n_terms; ++j) if (!k[j]) return TDEQ_EINVAL;
+    if (n_rows == 0) return 0;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return dtype == TDEQ_F32
+               ? row_event_fit_dispatch<float>(q, fired_now, y0, y1, f0, f1, k, coef, n_terms, dts, n_rows, row_len, s)
+               : row_event_fit_dispatch<double>(q, fired_now, y0, y1, f0, f1, k, coef, n_terms, dts, n_rows, row_len, s);
+}
+
+int tdeq_row_event_eval(void* out, const void* q, const void* x, const int32_t* mask, int64_t n_rows, int64_t row_len,
+                        int dtype, void* stream) {
+    if (!out || !q || !x || !mask || n_rows < 0 || row_len < 1 || !row_dtype_ok(dtype)) return TDEQ_EINVAL;
+    if (n_rows == 0) return 0;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return dtype == TDEQ_F32 ? row_event_eval_launch<float>(out, q, x, mask, n_rows, row_len, s)
+                             : row_event_eval_launch<double>(out, q, x, mask, n_rows, row_len, s);
 }

@@ -16,7 +16,9 @@ tableau's launch plan (`tableaus.launch_plan`: the carry plan of dopri5 / dopri8
 then the error norm, the controller and the dense-output commit.  The TWO BACKENDS offer the driver the same methods —
 `initial_step`, `trial_step`, `poll`, `counts`, for a recorded solve `begin_recording` / `recorded_solution`, and with
 `compact=` set `repack` (the finished rows leave the batch and the solve carries on with the rest, `_compact_fraction`)
-— and `odeint_rowwise` calls nothing else.  WHAT IS RECORDED for `differentiable=True` lives in rowwise_autodiff.py: the
+— and `odeint_rowwise` calls nothing else; an event solve (`odeint_rowwise_event`, rowwise_event.py) hands both
+backends a `RowEvents` object, whose hook runs between the controller and the commit of `trial_step`, and adds
+`deactivate_rows` / `event_eval`.  WHAT IS RECORDED for `differentiable=True` lives in rowwise_autodiff.py: the
 device backend hands its finished launches to a `RowRecorder` (None in a plain solve), the host backend records plain
 torch ops; `_Problem.grad_mode` is the one place that turns grad mode on for a recorded solve.
 """
@@ -286,8 +288,9 @@ class HostRowKernels:
 
     name = "host"
 
-    def __init__(self, p: _Problem):
+    def __init__(self, p: _Problem, ev=None):
         self.p = p
+        self.ev = ev                                         # rowwise_event.RowEvents of an event solve, else None
         T = p.np_dtype
         self.T = T
         B = p.B
@@ -366,7 +369,9 @@ class HostRowKernels:
         return sol
 
     def poll(self):
-        r = next((r for r in range(self.n) if self.active[r] and self.code[r] != 0), None)
+        # (an event solve: a row that fired in this trial step was prepared before it left, and its error wins)
+        live = self.active if self.ev is None else self.active | self.ev.fired_now.numpy().astype(bool)
+        r = next((r for r in range(self.n) if live[r] and self.code[r] != 0), None)
         if r is None:
             return int(self.active.sum()), None
         row = r if self.row_map is None else int(self.row_map[r])
@@ -504,6 +509,8 @@ class HostRowKernels:
                 else:
                     self.n_rej[r] += 1
                 self.dt[r] = dt_next
+        if self.ev is not None:                              # between controller and commit: the commit overwrites y, f0
+            self.ev.host_step(self, accepted, y, y1, f0, f1, ks, dts)
         if accepted:
             y, f0 = self._dense_commit(accepted, y, y1, f0, f1, ks, dts, sol, shadow, anchor)
         if shadow is not None and shadow.requires_grad:
@@ -513,7 +520,29 @@ class HostRowKernels:
         for r in range(self.n):
             if self.active[r]:
                 self.prepare(r)
+        if self.ev is not None:
+            self.active[self.ev.fired_now.numpy().astype(bool)] = False
         return y, f0
+
+    def deactivate_rows(self, mask: torch.Tensor) -> None:
+        """Before the initial step: the rows of `mask` (bool [B]) never start."""
+        self.active[mask.numpy()] = False
+
+    def event_eval(self, out, x, mask) -> None:
+        """out[r, :] = the kept quartic of row r at x[r] for the rows with mask[r] (the arithmetic of `_dense_commit`)."""
+        idx = torch.nonzero(mask).view(-1)
+        if idx.numel() == 0:
+            return
+        e, d, c, b, a = self.ev.coef[:, idx].unbind(0)
+        x1 = x[idx][:, None]
+        x2 = x1 * x1
+        x3 = x2 * x1
+        x4 = x3 * x1
+        total = e + d * x1
+        total = total + c * x2
+        total = total + b * x3
+        total = total + a * x4
+        out[idx] = total
 
     def _dense_commit(self, accepted, y, y1, f0, f1, ks, dts, sol, shadow=None, anchor=None):
         p, m, T = self.p, self.p.method, self.T
@@ -567,8 +596,9 @@ class HipRowKernels:
 
     name = "hip"
 
-    def __init__(self, p: _Problem):
+    def __init__(self, p: _Problem, ev=None):
         self.p = p
+        self.ev = ev                                         # rowwise_event.RowEvents of an event solve, else None
         self.k = _native.get_kernels(p.device, p.dtype)
         dev, B = p.device, p.B
         f64 = dict(dtype=torch.float64, device=dev)
@@ -619,7 +649,11 @@ class HipRowKernels:
 
     def poll(self):
         n_active, r = self.status.tolist()                   # the two words the host reads per trial step
-        if r == _NO_ERROR_ROW or n_active == 0:
+        # (an event solve: a row the controller found in error may have fired and left in the same trial step — its error
+        #  wins.  Safe because every control launch (`tdeq_row_control`) first resets both words to {0, no error row}, so
+        #  status[1] can only name a row of THIS launch, never a stale one; pinned by
+        #  tests/test_rowwise_event.py::test_max_num_steps_names_the_original_row)
+        if r == _NO_ERROR_ROW or (n_active == 0 and self.ev is None):
             return n_active, None
         row = r if self.row_map is None else int(self.row_map[r])
         return n_active, (row, int(self.code[r]), int(self.since[r]), float(self.dt[r]), r)
@@ -731,6 +765,8 @@ class HipRowKernels:
         # inputs stay alive for the backward)
         t_start = None if rec is None else self.t0.clone()
         self._control(0)
+        if self.ev is not None:                              # between controller and commit: the commit overwrites y, f0
+            self.ev.device_step(self, y, y1, f0, f1, mid, m.c_mid.coef, dts)
         y_to, f0_to = (y, f0) if rec is None else (y.detach().clone(), f0.detach().clone())
         if self.row_map is None:
             k.row_dense_commit(sol, y_to, y1, f0_to, f1, mid, m.c_mid.coef, dts, self.st)
@@ -739,6 +775,14 @@ class HipRowKernels:
         if rec is None:
             return y, f0
         return rec.commit(self, sol, y, y1, f0, ks, dts, t_start, y_to, f0_to)
+
+    def deactivate_rows(self, mask: torch.Tensor) -> None:
+        """Before the initial step: the rows of `mask` (bool [B]) never start."""
+        self.active.masked_fill_(mask, 0)
+
+    def event_eval(self, out, x, mask) -> None:
+        """out[r, :] = the kept quartic of row r at x[r] for the rows with mask[r] (int32 [B])."""
+        self.k.row_event_eval(out, self.ev.coef, x, mask)
 
 
 def odeint_rowwise(func, y0, t, *, rtol=1e-7, atol=1e-9, method="dopri5", options=None, return_stats=False,

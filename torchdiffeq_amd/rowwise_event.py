@@ -1,0 +1,277 @@
+"""`odeint_rowwise_event`: a batch of independent IVPs, each row stopped by its own terminal event.
+
+`odeint_event` treats a batched state as one system with one scalar event; here row r of `y0[B, *row_shape]` is
+integrated by the per-row controller of `odeint_rowwise` until `event_fn(t, y)[r]` changes sign (or the row reaches
+`t_end[r]`), and the event time of every row is then located by ONE bisection over the quartics of the rows' last steps.
+
+What an event solve adds to a rowwise trial step sits between the controller and the dense-output commit
+(`HipRowKernels.trial_step` / `HostRowKernels.trial_step` with a `RowEvents` object): one call of `event_fn`, the
+detection (`tdeq_row_event_detect`: a row that fires leaves the active rows like a finished one) and the quartic of the
+rows that fired in this step (`tdeq_row_event_fit`), kept in a [5, B, L] buffer because the commit overwrites y0 and f0.
+The bisection evaluates the kept quartics (`tdeq_row_event_eval`); its [B] bracket arithmetic is a handful of fp64 torch
+ops, the same expressions on both backends.
+"""
+from __future__ import annotations
+
+import math
+
+import numpy as np
+import torch
+
+from . import _fallback, rowwise
+from ._native import device_guard
+from .rowwise import _Problem
+
+__all__ = ["odeint_rowwise_event"]
+
+
+def _sign(g: torch.Tensor) -> torch.Tensor:
+    """(g > 0) - (g < 0) as int32: 0 for a zero and for a NaN (the expression of tdeq_row_event_detect)."""
+    return (g > 0).to(torch.int32) - (g < 0).to(torch.int32)
+
+
+def _row_times(name: str, v, B: int) -> torch.Tensor:
+    """`t0` / `t_end` -> fp64 CPU tensor [B]: a number, a 0-dim tensor or a [B] tensor."""
+    if isinstance(v, torch.Tensor):
+        if v.is_complex() or v.dtype == torch.bool or v.dim() > 1 or (v.dim() == 1 and v.shape[0] != B):
+            raise ValueError(f"odeint_rowwise_event: {name} must be a number, a 0-dim tensor or a real [B] = [{B}] tensor, "
+                             f"got a {v.dtype} tensor of shape {tuple(v.shape)}")
+        v = v.detach().to("cpu", torch.float64)
+        return v.expand(B).clone() if v.dim() == 0 else v.clone()
+    if isinstance(v, (int, float)) and not isinstance(v, bool):
+        return torch.full((B,), float(v), dtype=torch.float64)
+    raise ValueError(f"odeint_rowwise_event: {name} must be a number, a 0-dim tensor or a [B] = [{B}] tensor, got "
+                     f"{type(v).__name__}")
+
+
+def _event_grid(t0, t_end, B: int) -> torch.Tensor:
+    """The [2, B] fp64 grid [t0, t_end] of the solve (+inf for `t_end=None`)."""
+    for v in (t0, t_end):
+        if isinstance(v, torch.Tensor) and v.requires_grad and torch.is_grad_enabled():
+            raise NotImplementedError("odeint_rowwise_event does not propagate gradients (t0 / t_end requires grad); "
+                                      "detach them or call it under torch.no_grad()")
+    start = _row_times("t0", t0, B)
+    if not bool(torch.isfinite(start).all()):
+        raise ValueError("odeint_rowwise_event: t0 must be finite")
+    if t_end is None:
+        return torch.stack([start, torch.full((B,), math.inf, dtype=torch.float64)])
+    end = _row_times("t_end", t_end, B)
+    if not (bool((end > start).all()) or bool((end < start).all())):
+        raise ValueError("odeint_rowwise_event: t_end must differ from t0 in every row, in the same direction for all rows")
+    return torch.stack([start, end])
+
+
+class RowEvents:
+    """The event state of one solve, shared by both backends: the starting signs, which rows fired (ever / in the last
+    trial step), their brackets in solver time and the quartic of the step each row fired in.
+
+    `coef` is a [5, B, L] tensor of the state's dtype on its device — FIVE TIMES THE STATE, held for the whole solve."""
+
+    def __init__(self, p: _Problem, event_fn):
+        dev, B = p.device, p.B
+        self.p, self.event_fn = p, event_fn
+        self.n_evals = 0
+        self.sign0 = torch.zeros(B, dtype=torch.int32, device=dev)
+        self.fired = torch.zeros(B, dtype=torch.int32, device=dev)
+        self.fired_now = torch.zeros(B, dtype=torch.int32, device=dev)
+        self.lo = torch.zeros(B, dtype=torch.float64, device=dev)
+        self.hi = torch.zeros(B, dtype=torch.float64, device=dev)
+        self.coef = torch.empty(5, B, p.L, dtype=p.dtype, device=dev)
+
+    def call(self, t_rows: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+        """event_fn(t_rows [b] true time, y [b, *row_shape]) -> [b] contiguous in the state's dtype."""
+        self.n_evals += 1
+        p = self.p
+        g = self.event_fn(t_rows, y.view(y.shape[0], *p.shape[1:]))
+        if not isinstance(g, torch.Tensor):
+            raise TypeError("odeint_rowwise_event: event_fn must return a Tensor, got {}".format(type(g).__name__))
+        if g.shape != (y.shape[0],):
+            raise RuntimeError("odeint_rowwise_event: event_fn returned shape {} for {} rows (one value per row: [{}])".format(
+                tuple(g.shape), y.shape[0], y.shape[0]))
+        if g.device != p.device:
+            raise RuntimeError(f"odeint_rowwise_event: event_fn returned a tensor on '{g.device}', the state lives on "
+                               f"'{p.device}'")
+        if g.is_complex():
+            raise RuntimeError("odeint_rowwise_event: event_fn must return a real tensor")
+        return g.detach().to(p.dtype).contiguous()
+
+    def step_times(self, t0: torch.Tensor) -> torch.Tensor:
+        """The end of each row's trial step in true time, in the state's dtype (t0: the fp64 solver times after the
+        controller — the end of an accepted step; the value of any other row is ignored)."""
+        return (t0 * self.p.sign).to(self.p.dtype)
+
+    # -- the hook of HipRowKernels.trial_step ----------------------------------------------------------------------------
+    def device_step(self, kern, y, y1, f0, f1, mid, coefs, dts) -> None:
+        g1 = self.call(self.step_times(kern.t0), y1)
+        kern.k.row_event_detect(g1, self.sign0, kern.ctrl, kern.st, kern.dts, kern.times, self.fired, self.fired_now,
+                                self.lo, self.hi)
+        kern.k.row_event_fit(self.coef, self.fired_now, y, y1, f0, f1, mid, coefs, dts)
+
+    # -- the hook of HostRowKernels.trial_step ---------------------------------------------------------------------------
+    def host_step(self, kern, accepted, y, y1, f0, f1, ks, dts) -> None:
+        """The same decisions as torch / numpy ops; the row leaves the active ones after the controller's `prepare`."""
+        p, m = self.p, self.p.method
+        g1 = self.call(self.step_times(torch.from_numpy(kern.t0.copy())), y1)
+        s1, s0 = _sign(g1).numpy(), self.sign0.numpy()
+        fired, now, lo, hi = self.fired.numpy(), self.fired_now.numpy(), self.lo.numpy(), self.hi.numpy()
+        now[:] = 0
+        rows = [r for r, _, _ in accepted if not fired[r] and s1[r] != s0[r]]
+        if not rows:
+            return
+        now[rows] = 1
+        fired[rows] = 1
+        lo[rows], hi[rows] = kern.tprev[rows], kern.t0[rows]
+        # the quartic of the step: the expressions of HostRowKernels._dense_commit
+        idx = torch.tensor(rows)
+        d = dts[idx]
+        y0r, y1r, f0r, f1r = y[idx], y1[idx], f0[idx], f1[idx]
+        kr = [k[idx] if k is not None else None for k in ks]
+        ymid = y0r + kern._sum_terms(kr, m.c_mid, d)
+        two_dt = torch.tensor(2.0, dtype=p.dtype) * d
+        qa = ((f1r - f0r) * two_dt - (y1r + y0r) * 8.0) + ymid * 16.0
+        qb = (((f0r * 5.0 - f1r * 3.0) * d + y0r * 18.0) + y1r * 14.0) - ymid * 32.0
+        qc = (((f1r - f0r * 4.0) * d - y0r * 11.0) - y1r * 5.0) + ymid * 16.0
+        qd = f0r * d
+        self.coef[:, idx] = torch.stack([y0r, qd, qc, qb, qa])
+
+
+def _bisection_rounds(width: torch.Tensor, has_q: torch.Tensor) -> np.ndarray:
+    """nitrs_r = max(0, ceil(log(width_r) / log 2)) of the rows with a quartic, 0 elsewhere (a NaN counts as 0), formed
+    on the host in fp64 so that both backends get the same integers (event_handling.py:8)."""
+    with np.errstate(all="ignore"):
+        n = np.ceil(np.log(width.cpu().numpy()) / math.log(2.0))
+    n = np.where(np.isnan(n), 0.0, np.maximum(n, 0.0))
+    return np.where(has_q.cpu().numpy(), n, 0.0)
+
+
+def _locate(p: _Problem, ev: RowEvents, kern, sol, at_start):
+    """The one bisection after every row has stopped -> (event time [B] fp64 in solver time, fired [B] bool);
+    solution row 1 of the rows that fired is overwritten with the quartic at the event time."""
+    dev = p.device
+    fired = ev.fired.bool()
+    has_q = fired & ~at_start                                # (a row that fired at t0 took no step: it keeps y0)
+    ta, tb = ev.lo.clone(), ev.hi.clone()                    # the step the row fired in: the quartic's interval
+    if p.atol_rows is not None:
+        atol = p.atol_rows.to(torch.float64)
+    else:
+        atol = torch.full((p.B,), float(p.np_dtype(p.atol)), dtype=torch.float64, device=dev)
+    n = _bisection_rounds((tb - ta) / atol, has_q)
+    if np.isinf(n).any():
+        raise OverflowError("odeint_rowwise_event: cannot bisect to a tolerance of 0 (atol must be positive) in row {}".format(
+            int(np.flatnonzero(np.isinf(n))[0])))
+    nitrs = torch.from_numpy(n.astype(np.int64)).to(dev)
+    mask = has_q.to(torch.int32)
+    width = tb - ta
+    lo, hi = ev.lo, ev.hi
+    y_mid = p.y0.clone()                                     # (rows without a quartic keep y0; their values are ignored)
+    for i in range(int(n.max()) if n.size else 0):
+        t_mid = (lo + hi) / 2
+        kern.event_eval(y_mid, ((t_mid - ta) / width).to(p.dtype), mask)
+        same = _sign(ev.call((t_mid * p.sign).to(p.dtype), y_mid)) == ev.sign0
+        update = has_q & (nitrs > i)
+        lo, hi = torch.where(update & same, t_mid, lo), torch.where(update & ~same, t_mid, hi)
+    event_s = (lo + hi) / 2
+    t_end = p.tgrid[1].to(dev)
+    fired = fired & (event_s <= t_end)                       # a final step that crossed both: the event must come first
+    kern.event_eval(sol[1], ((event_s - ta) / width).to(p.dtype), (has_q & fired).to(torch.int32))
+    return torch.where(fired, event_s, t_end), fired
+
+
+def odeint_rowwise_event(func, y0, t0, *, event_fn, t_end=None, rtol=1e-7, atol=1e-9, method="dopri5", options=None,
+                         return_stats=False):
+    """Integrate B independent IVPs `dy_r/dt = func(t, y)[r]` from `t0`, each row until ITS terminal event: the first
+    sign change of `event_fn(t, y)[r]` — or until `t_end[r]`, whichever comes first.  Returns `(event_t, solution)`.
+
+    `y0` is `[B, *row_shape]` (fp32 / fp64); `func(t_rows, y)` is the func of `odeint_rowwise` (`t_rows` a `[b]` tensor of
+    stage times in the state's dtype).  `t0` is a number, a 0-dim tensor or a `[B]` tensor.  `t_end` is None (increasing
+    time, no end), a number or a `[B]` tensor; it must differ from `t0` in every row, in the same direction for all rows
+    (`t_end < t0`: decreasing time), else ValueError.  `rtol`, `atol` (numbers or `[B]` vectors), `method` and `options`
+    (`first_step`, `safety`, `ifactor`, `dfactor`, `max_num_steps`) are those of `odeint_rowwise`.
+
+    `event_fn(t_rows [b], y [b, *row_shape]) -> [b]` returns one real value per row on the state's device; it always gets
+    TRUE time (also for decreasing time), in the state's dtype, and is called under `torch.no_grad()`; its value is cast
+    to the state's dtype.  A wrong type, shape or device raises as it does for `func`.
+
+    Per row r (the reference's `_advance_until_event` + `find_event`, row by row):
+      * `s0 = sign(event_fn(t0, y0))[r]` with `sign(g) = (g > 0) - (g < 0)` (a NaN gives 0).  `s0 == 0`: the row has fired
+        at `t0` — it takes no step and keeps `y0`.
+      * after every trial step `event_fn` is called once for all rows with the end of each row's step and the state
+        there.  A row whose step was accepted and whose sign is `!= s0` fires: it stops, frozen like a row that reached
+        its last output time (`func` and `event_fn` keep being called for it, the values are ignored).
+      * a row that reaches `t_end[r]` first stops there: `event_t[r] = t_end[r]`, `solution[1, r] = y(t_end[r])`,
+        `fired[r] = False`.
+      * once every row has stopped, ONE bisection locates all events: row r takes
+        `nitrs_r = max(0, ceil(log2((hi - lo) / atol_r)))` halvings of the step `[lo, hi]` it fired in (`atol_r` the row's
+        atol rounded to the state's dtype), each on the quartic dense output of that step, and `max_r nitrs_r` rounds are
+        run with one `event_fn` call each; `event_t[r] = (lo + hi) / 2` and `solution[1, r]` is the quartic there.
+      * a final step that crosses `t_end[r]` AND changes sign is bisected like any other; the row counts as fired only if
+        the located time is not beyond `t_end[r]`, else it is a row that reached `t_end[r]`.
+    A row's bits do not depend on B or on the other rows (as long as `func` and `event_fn` treat rows independently).
+
+    Errors are those of `odeint_rowwise`, per row.  `max_num_steps` counts ALL trial steps of a row (there are no output
+    times in between to start the count again).  The one deviation from the reference: an error the controller reports
+    for a row (max_num_steps, dt underflow, a non-finite state) wins even if that row fires in the same trial step.
+    With `t_end=None` a row that never fires ends in one of those errors, or never.
+
+    Returns `event_t` (`[B]` fp64, true time, on the state's device) and `solution` (`[2, *y0.shape]`: `solution[0] = y0`,
+    `solution[1, r]` = row r at `event_t[r]`); with `return_stats=True` also `stats`: `n_accepted`, `n_rejected` (int64
+    `[B]`), `nfe`, `fired` (bool `[B]`, on the CPU like the counters) and `n_event_evals` (calls of `event_fn`: one at `t0`,
+    one per trial step, one per bisection round).
+
+    Memory: besides the buffers of `odeint_rowwise` the solve holds the quartic coefficients of every row, a `[5, B, L]`
+    tensor of the state's dtype — five times the state.
+
+    Out of scope (raises or is not offered): gradients (with grad mode on and anything requiring grad this raises
+    NotImplementedError; there is no `differentiable` argument), `compact`, several event functions, non-terminal events,
+    16-bit or complex states, captured (hipGraph) steps.
+    """
+    if not callable(event_fn):
+        raise ValueError("odeint_rowwise_event: event_fn must be callable: event_fn(t_rows [b], y [b, *row_shape]) -> [b]")
+    if isinstance(y0, torch.Tensor) and y0.dim() >= 1 and y0.shape[0] >= 1:
+        t = _event_grid(t0, t_end, y0.shape[0])
+    else:
+        t = torch.zeros(2, dtype=torch.float64)              # (_Problem refuses this y0)
+    p = _Problem(func, y0, t, rtol, atol, method, options, None)
+    ev = RowEvents(p, event_fn)
+    start = (p.tgrid[0] * p.sign).to(p.dtype).to(p.device)   # t0 in true time, as func and event_fn see it
+    with torch.no_grad(), device_guard(p.device):
+        ev.sign0 = _sign(ev.call(start, p.y0))
+        at_start = ev.sign0 == 0
+        ev.fired.copy_(at_start)
+        ev.lo.copy_(p.tgrid[0])
+        ev.hi.copy_(p.tgrid[0])
+        sol = torch.empty(2, p.B, p.L, dtype=p.dtype, device=p.device)
+        sol[0].copy_(p.y0)
+        sol[1].copy_(p.y0)
+        stepping = not bool(at_start.all())                  # every row fired at t0: no step, no func call
+    n_acc = n_rej = torch.zeros(p.B, dtype=torch.int64)
+    event_s, fired = p.tgrid[0].to(p.device), at_start
+    if stepping:
+        # the first evaluation in the caller's grad mode, as in odeint_rowwise: a func whose output requires grad is refused
+        with device_guard(p.device):
+            f0 = p.call(start, p.y0).clone()
+        with torch.no_grad(), device_guard(p.device):
+            if p.device.type == "cuda":
+                kern = rowwise.HipRowKernels(p, ev)
+            else:
+                _fallback.warn_once(f"the state lives on '{p.device}'")
+                kern = rowwise.HostRowKernels(p, ev)
+            kern.deactivate_rows(at_start)
+            y = p.y0.clone()                                 # private: the commit writes y <- y1, f0 <- f1 in place
+            kern.initial_step(y, f0)
+            while True:
+                n_active, failure = kern.poll()
+                if failure is not None:
+                    p.raise_row_error(failure, y)
+                if n_active == 0:
+                    break
+                y, f0 = kern.trial_step(y, f0, sol)
+            n_acc, n_rej = kern.counts()
+            event_s, fired = _locate(p, ev, kern, sol, at_start)
+    event_t = event_s * p.sign
+    solution = sol.view(2, *p.shape)
+    if not return_stats:
+        return event_t, solution
+    stats = {"n_accepted": n_acc.to(torch.int64), "n_rejected": n_rej.to(torch.int64), "nfe": p.nfe,
+             "fired": fired.cpu(), "n_event_evals": ev.n_evals}
+    return event_t, solution, stats
