@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define TDEQ_ABI_VERSION 26
+#define TDEQ_ABI_VERSION 27
 #define TDEQ_F32 0
 #define TDEQ_F64 1
 /* interleaved (re, im) complex states — accepted by the NORM entry points only (tdeq_error_norm, tdeq_error_norm_partial[_ctrl],
@@ -675,6 +675,30 @@ int tdeq_row_event_fit(void* q, const int32_t* fired_now, const void* y0, const 
                        int64_t row_len, int dtype, void* stream);
 int tdeq_row_event_eval(void* out, const void* q, const void* x, const int32_t* mask, int64_t n_rows, int64_t row_len,
                         int dtype, void* stream);
+
+/*
+ * ---- Compaction of an event solve (ABI 27; `odeint_rowwise_event(compact=...)`) ----
+ * The stopped rows leave the batch; the quartics stay in a buffer of all the original rows, read by the bisection after
+ * their rows have left.
+ * tdeq_row_event_fit_mapped   tdeq_row_event_fit for a compacted batch: the state tensors, `dts` and `fired_now` hold n_rows
+ *                             compact rows, `q` is [5, q_rows, row_len], and the quartic of compact row r with fired_now[r]
+ *                             goes to q[j, row_map[r], :] (0 <= row_map[r] < q_rows, no row named twice; q_rows >= n_rows).
+ *                             The same arithmetic; other rows of q are neither read nor written.
+ * tdeq_row_event_eval_mapped  the quartics of an index list, no mask: for i < n_idx, out[dst_map ? dst_map[i] : i, :] = the
+ *                             quartic q[:, src_map[i], :] at x[i] (`x` [n_idx] of the state type).  `q` is [5, q_rows,
+ *                             row_len], `out` [out_rows, row_len]; 0 <= src_map[i] < q_rows, 0 <= dst_map[i] < out_rows (no
+ *                             row named twice), and with dst_map == NULL out_rows >= n_idx.  Other rows of `out` are
+ *                             untouched.
+ * 64-bit offsets; the stride of q's leading dimension is q_rows * row_len.  16-byte elements when row_len is a multiple of
+ * 16 / sizeof(T) and every state-sized pointer is 16-byte aligned (every row start of q and out is then aligned too),
+ * scalar elements otherwise.  A NULL pointer (dst_map excepted), a negative size, no row of q or out with work to do, or a
+ * dtype other than TDEQ_F32 / TDEQ_F64: TDEQ_EINVAL before any launch.  n_rows == 0 / n_idx == 0: no-op.
+ */
+int tdeq_row_event_fit_mapped(void* q, const int32_t* row_map, int64_t q_rows, const int32_t* fired_now, const void* y0,
+                              const void* y1, const void* f0, const void* f1, const void* const* k, const double* coef,
+                              int n_terms, const void* dts, int64_t n_rows, int64_t row_len, int dtype, void* stream);
+int tdeq_row_event_eval_mapped(void* out, const int32_t* dst_map, int64_t out_rows, const void* q, const int32_t* src_map,
+                               int64_t q_rows, const void* x, int64_t n_idx, int64_t row_len, int dtype, void* stream);
 
 #ifdef __cplusplus
 }

@@ -10,6 +10,9 @@ on a mixed-stiffness batch.
     python tools/rowwise_bench.py --event [--reps 5]          (one JSON line: plain and event solve of one fresh process)
     python tools/rowwise_bench.py --event --plain-only        (the plain solve alone: also runs on a tree without events)
     python tools/rowwise_bench.py --event-summary parent.jsonl,new_plain.jsonl,new_event.jsonl --out profiles/rowwise_event_bench.json
+    python tools/rowwise_bench.py --event --compact [--setting plain|0.5|1.0] [--reps 5]    (one JSON line of one fresh process)
+    python tools/rowwise_bench.py --event-compact-summary lines.jsonl[,parent_event.jsonl,new_event.jsonl]
+                                  --out profiles/rowwise_event_compact_bench.json
 
 `--compact`: wall time of one solve at the headline shape with a per-row rate spread over logspace(-1, 1.5) (so that the
 rows' trial counts differ), plain against `compact=0.5` and `compact=1.0`: `row_evals` against `nfe x B` (the bound on
@@ -21,6 +24,14 @@ warm-up, then one instrumented event solve with the time inside `event_fn` durin
 bisection measured between synchronisations.  One fresh process per figure; `--event-summary` folds the lines of
 alternated processes (parent tree plain, this tree plain, this tree event) into the medians and spreads of
 profiles/rowwise_event_bench.json.
+
+`--event --compact`: the event solve with the rate-spread func of `--compact` (k_r * (y @ A.T), k_r over logspace(-1, 1.5),
+so that the rows stop after different numbers of trial steps; the same event and t_end), one setting per fresh process —
+plain, `compact=0.5` or `compact=1.0`: the median of `--reps` solves after a warm-up, `row_evals`, `event_row_evals`,
+`n_repacks`, the bound nfe x B / row_evals, whether every output is bit for bit the plain solve's of the same process, and
+one instrumented solve with the final bisection timed between synchronisations.  `--event-compact-summary` folds the lines
+of alternated processes (the first round warms up) and, given the `--event` lines of the parent tree and of this tree,
+whether the plain event solve (func y @ A.T) stayed inside the parent's spread.
 
 `--grad`: forward + backward of a `differentiable=True` solve per trial step at the headline, next to plain `odeint`
 backprop of the same state, and (`--parity`) the per-row deviations of the rowwise gradients from the reference's
@@ -226,6 +237,112 @@ def _event(reps: int, plain_only: bool):
                         "median_ms_per_trial_without_bisection": (med(ms) - inside["bisection"]) / trials,
                         "event_fn_ms_per_trial": inside["event_fn"] / n_steps_calls}
     return res
+
+
+def _event_compact(reps: int, setting: str):
+    """One process's figures for one setting ("plain", "0.5", "1.0") of the rate-spread event solve."""
+    import torchdiffeq_amd as tda
+    from torchdiffeq_amd import rowwise_event
+    dev = torch.device("cuda", 0)
+    B, D = 65536, 128
+    g = torch.Generator().manual_seed(0)
+    G = torch.randn(D, D, generator=g, dtype=torch.float64) / D ** 0.5
+    A = (0.5 * (G - G.T) - 0.1 * torch.eye(D, dtype=torch.float64)).float().to(dev)
+    k = torch.logspace(-1, 1.5, B, dtype=torch.float64)[torch.randperm(B, generator=g)][:, None].float().to(dev)
+    y0 = torch.randn(B, D, generator=g).to(dev)
+    level = y0[:, 0] - 0.25
+    med = lambda v: sorted(v)[len(v) // 2]       # noqa: E731
+    kw = dict(t_end=0.5, rtol=1e-7, atol=1e-9, return_stats=True)
+
+    def solve(c, field=lambda y: y @ A.T):
+        if c is None:
+            return tda.odeint_rowwise_event(lambda t_, y: k * field(y), y0, 0.0, event_fn=lambda t_, y: y[:, 0] - level, **kw)
+        return tda.odeint_rowwise_event(lambda t_, y, rows: k[rows] * field(y), y0, 0.0,
+                                        event_fn=lambda t_, y, rows: y[:, 0] - level[rows], compact=c, **kw)
+
+    def same_outputs(a, b):
+        return bool(torch.equal(a[0], b[0]) and torch.equal(a[1], b[1]) and all(
+            torch.equal(a[2][n], b[2][n]) for n in ("n_accepted", "n_rejected", "fired")) and all(
+            a[2][n] == b[2][n] for n in ("nfe", "n_event_evals")))
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3, out
+    c = None if setting == "plain" else float(setting)
+    with torch.no_grad():
+        plain = solve(None)                                   # warms up, and is what the setting's outputs are compared to
+        ms = []
+        for rep in range(reps + 1):
+            took, (event_t, sol, st) = timed(lambda: solve(c))
+            if rep:                                           # the first solve warms up
+                ms.append(took)
+        same = same_outputs((event_t, sol, st), plain)
+        # the GEMM picks its algorithm by batch size, so this func is not batch-invariant; the same comparison with an
+        # elementwise field (k_r * -y: rows independent to the bit) is the feature's contract at this shape
+        decay = lambda y: -y      # noqa: E731
+        same_elementwise = same_outputs(solve(c, decay), solve(None, decay))
+        inside = [0.0]
+        plain_locate = rowwise_event._locate
+
+        def timed_locate(*a):
+            took, out = timed(lambda: plain_locate(*a))
+            inside[0] += took
+            return out
+        rowwise_event._locate = timed_locate
+        try:
+            solve(c)
+        finally:
+            rowwise_event._locate = plain_locate
+    trials = st["n_accepted"] + st["n_rejected"]
+    row_evals = st.get("row_evals", st["nfe"] * B)
+    return {"setting": setting, "ms_per_solve": ms, "median_ms_per_solve": med(ms), "ms_inside_bisection": inside[0],
+            "median_ms_per_solve_without_bisection": med(ms) - inside[0], "nfe": st["nfe"], "nfe_times_B": st["nfe"] * B,
+            "row_evals": row_evals, "n_event_evals": st["n_event_evals"],
+            "event_row_evals": st.get("event_row_evals", st["n_event_evals"] * B), "n_repacks": st.get("n_repacks", 0),
+            "speedup_bound": st["nfe"] * B / row_evals, "bit_identical_to_plain": bool(same),
+            "bit_identical_to_plain_elementwise_func": same_elementwise,
+            "rows_fired": int(st["fired"].sum()), "trials_min": int(trials.min()), "trials_median": float(trials.median()),
+            "trials_max": int(trials.max())}
+
+
+def _event_compact_summary(paths, out):
+    """Fold the JSON lines of the alternated fresh processes (one file, every setting; the first line of each setting is
+    the warm-up round).  With two more files — `--event` lines of the parent tree and of this tree, alternated — also the
+    plain event solve of the two trees."""
+    med = lambda v: sorted(v)[len(v) // 2]       # noqa: E731
+
+    def fold(vals):
+        return {"per_process": [round(v, 4) for v in vals], "median": round(med(vals), 4), "min": round(min(vals), 4),
+                "max": round(max(vals), 4)}
+    lines = [json.loads(x) for x in open(paths[0]) if x.strip().startswith("{")]
+    res = {"what": "tools/rowwise_bench.py --event --compact: 65536 x 128 fp32 dopri5, func k_r * (y @ A.T) with k_r in "
+                   "logspace(-1, 1.5) shuffled, event: y[:, 0] falls 0.25 below its start, t_end 0.5, rtol 1e-7, atol 1e-9; "
+                   "every figure the median of 5 solves of one fresh process, the settings alternated, the first round "
+                   "a warm-up"}
+    for setting in ("plain", "0.5", "1.0"):
+        mine = [r["event_compact"] for r in lines if r["event_compact"]["setting"] == setting][1:]
+        last = mine[-1]
+        res["plain" if setting == "plain" else "compact_" + setting] = {
+            "ms_per_solve": fold([r["median_ms_per_solve"] for r in mine]),
+            "bisection_ms_per_solve": fold([r["ms_inside_bisection"] for r in mine]),
+            "ms_per_solve_without_bisection": fold([r["median_ms_per_solve_without_bisection"] for r in mine]),
+            "bit_identical_to_plain": all(r["bit_identical_to_plain"] for r in mine),
+            "bit_identical_to_plain_elementwise_func": all(r["bit_identical_to_plain_elementwise_func"] for r in mine),
+            **{key: last[key] for key in ("nfe", "nfe_times_B", "row_evals", "n_event_evals", "event_row_evals", "n_repacks",
+                                          "speedup_bound", "rows_fired", "trials_min", "trials_median", "trials_max")}}
+    for name in ("compact_0.5", "compact_1.0"):
+        res[name]["speedup"] = round(res["plain"]["ms_per_solve"]["median"] / res[name]["ms_per_solve"]["median"], 4)
+    if len(paths) == 3:
+        parent, new = ([json.loads(x) for x in open(p) if x.strip().startswith("{")][1:] for p in paths[1:])
+        pe = fold([r["event"]["median_ms_per_solve"] for r in parent])
+        ne = fold([r["event"]["median_ms_per_solve"] for r in new])
+        res["plain_event_solve_func_y_At"] = {"parent_ms_per_solve": pe, "new_ms_per_solve": ne,
+                                              "new_median_inside_parent_min_max": pe["min"] <= ne["median"] <= pe["max"]}
+    json.dump(res, open(out, "w"), indent=1)
+    print(json.dumps(res))
 
 
 def _event_summary(paths, out):
@@ -435,9 +552,19 @@ def main():
     ap.add_argument("--event", action="store_true")
     ap.add_argument("--plain-only", action="store_true")
     ap.add_argument("--event-summary", default=None)
+    ap.add_argument("--setting", default="plain", choices=("plain", "0.5", "1.0"))
+    ap.add_argument("--event-compact-summary", default=None)
     a = ap.parse_args()
     if a.event_summary:
         _event_summary(a.event_summary.split(","), a.out)
+        return
+    if a.event_compact_summary:
+        _event_compact_summary(a.event_compact_summary.split(","), a.out)
+        return
+    if a.event and a.compact:
+        res = {"device": torch.cuda.get_device_name(0), "arch": torch.cuda.get_device_properties(0).gcnArchName,
+               "event_compact": _event_compact(a.reps, a.setting)}
+        print(json.dumps(res))
         return
     if a.event:
         res = {"device": torch.cuda.get_device_name(0), "arch": torch.cuda.get_device_properties(0).gcnArchName,

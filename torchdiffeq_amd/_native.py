@@ -18,7 +18,7 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-TDEQ_ABI_VERSION = 26
+TDEQ_ABI_VERSION = 27
 TDEQ_F32, TDEQ_F64 = 0, 1
 TDEQ_C64, TDEQ_C128 = 2, 3        # interleaved complex: the norm entry points only (include/tdeq_hip.h)
 TDEQ_BF16, TDEQ_F16 = 4, 5        # reduced-precision states: the entry points of the host-driven step (LowPrecisionHipKernels)
@@ -256,6 +256,14 @@ ABI_SIGNATURES = {
                                           ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p]),
     "tdeq_row_event_eval": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                            ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p]),
+    # compaction of an event solve (ABI 27, odeint_rowwise_event(compact=...))
+    "tdeq_row_event_fit_mapped": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
+                                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                 _c_void_pp, _c_double_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int64,
+                                                 ctypes.c_int64, ctypes.c_int, ctypes.c_void_p]),
+    "tdeq_row_event_eval_mapped": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
+                                                  ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64,
+                                                  ctypes.c_int64, ctypes.c_int, ctypes.c_void_p]),
 }
 
 
@@ -976,6 +984,38 @@ class HipKernels:
             raise ValueError("row_event_eval: x must be a contiguous [n_rows] tensor of out's dtype")
         _check(self.lib.tdeq_row_event_eval(out.data_ptr(), q.data_ptr(), x.data_ptr(), mask.data_ptr(), out.shape[0],
                                             out.shape[1], dtype_code(out.dtype), self._stream()), "tdeq_row_event_eval")
+
+    def row_event_fit_mapped(self, q, row_map, fired_now, y0, y1, f0, f1, ks, coefs, dts) -> None:
+        """tdeq_row_event_fit_mapped: `q` a contiguous [5, q_rows, L] tensor of the state's dtype, the state tensors [n, L],
+        `row_map` int32 [n] = the row of `q` of each state row."""
+        if q.dim() != 3 or q.shape[0] != 5 or q.shape[2] != y0.shape[1] or q.dtype != y0.dtype or not q.is_contiguous():
+            raise ValueError("row_event_fit_mapped: q must be a contiguous [5, q_rows, L] tensor of the state's dtype")
+        if row_map.shape != (y0.shape[0],) or row_map.dtype != torch.int32 or not row_map.is_contiguous():
+            raise ValueError("row_event_fit_mapped: row_map must be a contiguous int32 [n_rows] tensor")
+        ptrs, cf, n = self._terms(ks, coefs)
+        _check(self.lib.tdeq_row_event_fit_mapped(q.data_ptr(), row_map.data_ptr(), q.shape[1], fired_now.data_ptr(),
+                                                  y0.data_ptr(), y1.data_ptr(), f0.data_ptr(), f1.data_ptr(), ptrs, cf, n,
+                                                  dts.data_ptr(), y0.shape[0], y0.shape[1], dtype_code(y0.dtype),
+                                                  self._stream()), "tdeq_row_event_fit_mapped")
+
+    def row_event_eval_mapped(self, out, dst_map, q, src_map, x) -> None:
+        """tdeq_row_event_eval_mapped: out[dst_map[i] (None: i), :] = q[:, src_map[i], :] at x[i]; the maps int32 [n_idx] on
+        the device, `x` [n_idx] of out's dtype, `q` a contiguous [5, q_rows, L] tensor, `out` [out_rows, L]."""
+        n_idx = src_map.numel()
+        if n_idx == 0:                        # (nothing to evaluate; empty tensors have null pointers, which the ABI refuses)
+            return
+        if q.dim() != 3 or q.shape[0] != 5 or q.shape[2] != out.shape[1] or q.dtype != out.dtype or not q.is_contiguous() \
+                or not out.is_contiguous():
+            raise ValueError("row_event_eval_mapped: q must be a contiguous [5, q_rows, L] tensor of out's dtype")
+        if x.shape != (n_idx,) or x.dtype != out.dtype or not x.is_contiguous():
+            raise ValueError("row_event_eval_mapped: x must be a contiguous [n_idx] tensor of out's dtype")
+        for m in (src_map, dst_map):
+            if m is not None and (m.shape != (n_idx,) or m.dtype != torch.int32 or not m.is_contiguous()):
+                raise ValueError("row_event_eval_mapped: the maps must be contiguous int32 [n_idx] tensors")
+        _check(self.lib.tdeq_row_event_eval_mapped(out.data_ptr(), None if dst_map is None else dst_map.data_ptr(),
+                                                   out.shape[0], q.data_ptr(), src_map.data_ptr(), q.shape[1], x.data_ptr(),
+                                                   n_idx, out.shape[1], dtype_code(out.dtype), self._stream()),
+               "tdeq_row_event_eval_mapped")
 
 
 class ComplexHipKernels:

@@ -611,7 +611,8 @@ int tdeq_row_multi_dot(const void* g, const void* const* x, int n_x, int64_t n_r
                              : row_dot_dispatch<double>(g, x, n_x, n_rows, row_len, out, ws, s);
 }
 
-// ---- per-row terminal events: tdeq_row_event_detect / tdeq_row_event_fit / tdeq_row_event_eval ------------------------
+// ---- per-row terminal events: tdeq_row_event_detect / tdeq_row_event_fit / tdeq_row_event_eval, and the two of a
+// ---- compacted event solve: tdeq_row_event_fit_mapped / tdeq_row_event_eval_mapped -----------------------------------
 namespace {
 
 template <typename T, int NT>
@@ -657,6 +658,55 @@ int row_event_fit_dispatch(void* q, const int32_t* fired_now, const void* y0, co
     return TDEQ_EINVAL;
 }
 
+template <typename T, int NT>
+int row_event_fit_mapped_n(void* q, const int32_t* row_map, int64_t q_rows, const int32_t* fired_now, const void* y0,
+                           const void* y1, const void* f0, const void* f1, const void* const* k, const double* coef,
+                           const void* dts, int64_t n_rows, int64_t row_len, hipStream_t s) {
+    RowEventFitMappedArgs<T, NT> a;
+    a.q = static_cast<T*>(q);
+    a.y0 = static_cast<const T*>(y0);
+    a.y1 = static_cast<const T*>(y1);
+    a.f0 = static_cast<const T*>(f0);
+    a.f1 = static_cast<const T*>(f1);
+    for (int j = 0; j < NT; ++j) {
+        a.k[j] = static_cast<const T*>(k[j]);
+        a.c[j] = (T)coef[j];
+    }
+    a.dts = static_cast<const T*>(dts);
+    a.fired_now = fired_now;
+    a.n = n_rows * row_len;
+    a.row_map = row_map;
+    a.q_plane = q_rows * row_len;
+    // (16-byte elements: row_len is a whole number of them, so every row start and every plane of q is aligned as q is)
+    const int lv = row_lanes(row_len, std::is_same<T, float>::value ? TDEQ_F32 : TDEQ_F64);
+    bool vec = lv > 1 && aligned16(q) && aligned16(y0) && aligned16(y1) && aligned16(f0) && aligned16(f1);
+    for (int j = 0; j < NT; ++j) vec = vec && aligned16(k[j]);
+    if (vec) {
+        a.row_len = row_len / lv;
+        hipLaunchKernelGGL((row_event_fit_mapped_kernel<T, NT, true>), dim3(stream_grid(a.n / lv, kBlock)), dim3(kBlock), 0,
+                           s, a);
+    } else {
+        a.row_len = row_len;
+        hipLaunchKernelGGL((row_event_fit_mapped_kernel<T, NT, false>), dim3(stream_grid(a.n, kBlock)), dim3(kBlock), 0, s,
+                           a);
+    }
+    return check_launch();
+}
+
+template <typename T>
+int row_event_fit_mapped_dispatch(void* q, const int32_t* row_map, int64_t q_rows, const int32_t* fired_now,
+                                  const void* y0, const void* y1, const void* f0, const void* f1, const void* const* k,
+                                  const double* coef, int nt, const void* dts, int64_t n_rows, int64_t row_len,
+                                  hipStream_t s) {
+    switch (nt) {
+#define TDEQ_CASE(N) case N: return row_event_fit_mapped_n<T, N>(q, row_map, q_rows, fired_now, y0, y1, f0, f1, k, coef, dts, n_rows, row_len, s);
+        TDEQ_CASE(1) TDEQ_CASE(2) TDEQ_CASE(3) TDEQ_CASE(4) TDEQ_CASE(5) TDEQ_CASE(6) TDEQ_CASE(7)
+        TDEQ_CASE(8) TDEQ_CASE(9) TDEQ_CASE(10) TDEQ_CASE(11) TDEQ_CASE(12) TDEQ_CASE(13) TDEQ_CASE(14)
+#undef TDEQ_CASE
+    }
+    return TDEQ_EINVAL;
+}
+
 template <typename T>
 int row_event_eval_launch(void* out, const void* q, const void* x, const int32_t* mask, int64_t n_rows, int64_t row_len,
                           hipStream_t s) {
@@ -675,6 +725,33 @@ int row_event_eval_launch(void* out, const void* q, const void* x, const int32_t
         hipLaunchKernelGGL((row_event_eval_kernel<T, false>), dim3(stream_grid(a.n, kBlock)), dim3(kBlock), 0, s, a);
     }
     return check_launch();
+}
+
+template <typename T, bool VEC, bool DST>
+int row_event_eval_mapped_go(const RowEventEvalMappedArgs<T>& a, hipStream_t s) {
+    hipLaunchKernelGGL((row_event_eval_mapped_kernel<T, VEC, DST>), dim3(stream_grid(a.ne, kBlock)), dim3(kBlock), 0, s, a);
+    return check_launch();
+}
+
+template <typename T>
+int row_event_eval_mapped_launch(void* out, const int32_t* dst_map, const void* q, const int32_t* src_map, int64_t q_rows,
+                                 const void* x, int64_t n_idx, int64_t row_len, hipStream_t s) {
+    RowEventEvalMappedArgs<T> a;
+    a.out = static_cast<T*>(out);
+    a.q = static_cast<const T*>(q);
+    a.x = static_cast<const T*>(x);
+    a.src_map = src_map;
+    a.dst_map = dst_map;
+    a.q_plane = q_rows * row_len;
+    const int lv = row_lanes(row_len, std::is_same<T, float>::value ? TDEQ_F32 : TDEQ_F64);
+    if (lv > 1 && aligned16(out) && aligned16(q)) {
+        a.row_len = row_len / lv;
+        a.ne = n_idx * a.row_len;
+        return dst_map ? row_event_eval_mapped_go<T, true, true>(a, s) : row_event_eval_mapped_go<T, true, false>(a, s);
+    }
+    a.row_len = row_len;
+    a.ne = n_idx * row_len;
+    return dst_map ? row_event_eval_mapped_go<T, false, true>(a, s) : row_event_eval_mapped_go<T, false, false>(a, s);
 }
 
 }  // namespace
@@ -731,4 +808,33 @@ int tdeq_row_event_eval(void* out, const void* q, const void* x, const int32_t* 
     hipStream_t s = static_cast<hipStream_t>(stream);
     return dtype == TDEQ_F32 ? row_event_eval_launch<float>(out, q, x, mask, n_rows, row_len, s)
                              : row_event_eval_launch<double>(out, q, x, mask, n_rows, row_len, s);
+}
+
+int tdeq_row_event_fit_mapped(void* q, const int32_t* row_map, int64_t q_rows, const int32_t* fired_now, const void* y0,
+                              const void* y1, const void* f0, const void* f1, const void* const* k, const double* coef,
+                              int n_terms, const void* dts, int64_t n_rows, int64_t row_len, int dtype, void* stream) {
+    if (!q || !row_map || !fired_now || !y0 || !y1 || !f0 || !f1 || !k || !coef || !dts || !row_dtype_ok(dtype))
+        return TDEQ_EINVAL;
+    if (n_terms < 1 || n_terms > TDEQ_MAX_TERMS || n_rows < 0 || q_rows < 0 || row_len < 1) return TDEQ_EINVAL;
+    for (int j = 0; j < n_terms; ++j) if (!k[j]) return TDEQ_EINVAL;
+    if (n_rows == 0) return 0;
+    if (q_rows < n_rows) return TDEQ_EINVAL;          // (row_map names n_rows different rows of q)
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return dtype == TDEQ_F32
+               ? row_event_fit_mapped_dispatch<float>(q, row_map, q_rows, fired_now, y0, y1, f0, f1, k, coef, n_terms, dts,
+                                                      n_rows, row_len, s)
+               : row_event_fit_mapped_dispatch<double>(q, row_map, q_rows, fired_now, y0, y1, f0, f1, k, coef, n_terms, dts,
+                                                       n_rows, row_len, s);
+}
+
+int tdeq_row_event_eval_mapped(void* out, const int32_t* dst_map, int64_t out_rows, const void* q, const int32_t* src_map,
+                               int64_t q_rows, const void* x, int64_t n_idx, int64_t row_len, int dtype, void* stream) {
+    if (!out || !q || !src_map || !x || !row_dtype_ok(dtype)) return TDEQ_EINVAL;
+    if (n_idx < 0 || out_rows < 0 || q_rows < 0 || row_len < 1) return TDEQ_EINVAL;
+    if (n_idx == 0) return 0;
+    if (q_rows < 1 || out_rows < 1 || (!dst_map && out_rows < n_idx)) return TDEQ_EINVAL;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return dtype == TDEQ_F32
+               ? row_event_eval_mapped_launch<float>(out, dst_map, q, src_map, q_rows, x, n_idx, row_len, s)
+               : row_event_eval_mapped_launch<double>(out, dst_map, q, src_map, q_rows, x, n_idx, row_len, s);
 }

@@ -10,6 +10,9 @@
 //                      own step size), kept in a [5, n_rows, L] buffer: the commit that follows overwrites y0 and f0
 // and, once every row has stopped, one bisection over the kept quartics:
 //   row_event_eval     out[r, :] = the row's quartic at x[r] (interp.py:42-47), for the rows of a mask
+// With `compact=` the stopped rows leave the batch, and the quartics stay in a buffer indexed by ORIGINAL row:
+//   row_event_fit_mapped    row_event_fit of a compacted batch: the quartic of compact row r goes to q[:, row_map[r], :]
+//   row_event_eval_mapped   the quartics of an index list: out[dst_map[i] or i, :] = q[:, src_map[i], :] at x[i]
 // The arithmetic of an element is that of row_dense_commit_kernel (fit_one / eval_one of tdeq_kernels.hpp).
 #pragma once
 
@@ -127,6 +130,42 @@ __global__ __launch_bounds__(kBlock) void row_event_fit_kernel(const RowEventFit
     }
 }
 
+// The mapped form serves a compacted batch (`odeint_rowwise_event(compact=...)`): the state tensors, `dts` and
+// `fired_now` hold the compact rows, `q` keeps all q_rows original ones (a row's quartic is read by the bisection after
+// the row has left), and the quartic of compact row r goes to q[j, row_map[r], :].  A second kernel on the shared
+// arithmetic (`row_event_fit_one`), not a flag on the first: a body shared through a reference to the argument block
+// changes the register allocation of the plain instantiations, whose figures are to stay what they were.
+template <typename T, int NT>
+struct RowEventFitMappedArgs : RowEventFitArgs<T, NT> {
+    const int32_t* row_map;           // [n_rows] row of q of each compact row
+    int64_t q_plane;                  // q_rows * L elements of T: the stride of q's leading dimension
+};
+
+template <typename T, int NT, bool VEC>
+__global__ __launch_bounds__(kBlock) void row_event_fit_mapped_kernel(const RowEventFitMappedArgs<T, NT> a) {
+    using E = typename std::conditional<VEC, typename VecOf<T>::type, T>::type;
+    constexpr int LV = VEC ? VecOf<T>::L : 1;
+    const int64_t ne = a.n / LV;
+    const int64_t stride = (int64_t)gridDim.x * kBlock;
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < ne; i += stride) {
+        const int64_t r = i / a.row_len;
+        if (!a.fired_now[r]) continue;
+        const T dtT = a.dts[r];
+        E kk[NT];
+#pragma unroll
+        for (int j = 0; j < NT; ++j) kk[j] = reinterpret_cast<const E*>(a.k[j])[i];
+        const Quartic<T, E> q = row_event_fit_one<T, NT, E>(
+            a.c, dtT, reinterpret_cast<const E*>(a.y0)[i], reinterpret_cast<const E*>(a.y1)[i],
+            reinterpret_cast<const E*>(a.f0)[i], reinterpret_cast<const E*>(a.f1)[i], kk);
+        const int64_t at = (int64_t)a.row_map[r] * a.row_len + (i - r * a.row_len);
+        reinterpret_cast<E*>(a.q)[at] = q.e;
+        reinterpret_cast<E*>(a.q + a.q_plane)[at] = q.d;
+        reinterpret_cast<E*>(a.q + 2 * a.q_plane)[at] = q.c;
+        reinterpret_cast<E*>(a.q + 3 * a.q_plane)[at] = q.b;
+        reinterpret_cast<E*>(a.q + 4 * a.q_plane)[at] = q.a;
+    }
+}
+
 template <typename T>
 struct RowEventEvalArgs {
     T* out;                           // [n_rows, L]
@@ -153,6 +192,39 @@ __global__ __launch_bounds__(kBlock) void row_event_eval_kernel(const RowEventEv
         q.b = reinterpret_cast<const E*>(a.q + 3 * a.n)[i];
         q.a = reinterpret_cast<const E*>(a.q + 4 * a.n)[i];
         reinterpret_cast<E*>(a.out)[i] = eval_one<T, E>(q, a.x[r]);
+    }
+}
+
+// The quartics of an index list (the bisection of a compacted event solve): for i < n_idx,
+// out[DST ? dst_map[i] : i, :] = the quartic q[:, src_map[i], :] at x[i].  No mask: the list is the mask.
+template <typename T>
+struct RowEventEvalMappedArgs {
+    T* out;                           // [out_rows, L]
+    const T* q;                       // [5, q_rows, L]
+    const T* x;                       // [n_idx] the fraction of each listed row's step
+    const int32_t* src_map;           // [n_idx] row of q
+    const int32_t* dst_map;           // [n_idx] row of out (DST), else not read
+    int64_t row_len;                  // E units
+    int64_t ne;                       // n_idx * row_len
+    int64_t q_plane;                  // q_rows * L elements of T
+};
+
+template <typename T, bool VEC, bool DST>
+__global__ __launch_bounds__(kBlock) void row_event_eval_mapped_kernel(const RowEventEvalMappedArgs<T> a) {
+    using E = typename std::conditional<VEC, typename VecOf<T>::type, T>::type;
+    const int64_t stride = (int64_t)gridDim.x * kBlock;
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < a.ne; i += stride) {
+        const int64_t r = i / a.row_len;
+        const int64_t e = i - r * a.row_len;
+        const int64_t from = (int64_t)a.src_map[r] * a.row_len + e;
+        Quartic<T, E> q;
+        q.e = reinterpret_cast<const E*>(a.q)[from];
+        q.d = reinterpret_cast<const E*>(a.q + a.q_plane)[from];
+        q.c = reinterpret_cast<const E*>(a.q + 2 * a.q_plane)[from];
+        q.b = reinterpret_cast<const E*>(a.q + 3 * a.q_plane)[from];
+        q.a = reinterpret_cast<const E*>(a.q + 4 * a.q_plane)[from];
+        const int64_t to = DST ? (int64_t)a.dst_map[r] * a.row_len + e : i;
+        reinterpret_cast<E*>(a.out)[to] = eval_one<T, E>(q, a.x[r]);
     }
 }
 

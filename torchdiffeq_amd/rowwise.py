@@ -18,9 +18,9 @@ then the error norm, the controller and the dense-output commit.  The TWO BACKEN
 `compact=` set `repack` (the finished rows leave the batch and the solve carries on with the rest, `_compact_fraction`)
 — and `odeint_rowwise` calls nothing else; an event solve (`odeint_rowwise_event`, rowwise_event.py) hands both
 backends a `RowEvents` object, whose hook runs between the controller and the commit of `trial_step`, and adds
-`deactivate_rows` / `event_eval`.  WHAT IS RECORDED for `differentiable=True` lives in rowwise_autodiff.py: the
-device backend hands its finished launches to a `RowRecorder` (None in a plain solve), the host backend records plain
-torch ops; `_Problem.grad_mode` is the one place that turns grad mode on for a recorded solve.
+`deactivate_rows` / `event_eval` / `event_eval_mapped`.  WHAT IS RECORDED for `differentiable=True` lives in
+rowwise_autodiff.py: the device backend hands its finished launches to a `RowRecorder` (None in a plain solve), the
+host backend records plain torch ops; `_Problem.grad_mode` is the one place that turns grad mode on for a recorded solve.
 """
 from __future__ import annotations
 
@@ -399,6 +399,8 @@ class HostRowKernels:
         self.tg = self.tg[:, keep]
         self.row_map = self.row_map[keep]
         idx = torch.from_numpy(keep)
+        if self.ev is not None:
+            self.ev.keep_rows(idx)
         if self.s_shadow is not None:
             self.s_shadow = self.s_shadow[idx]
         if self.anchor is not None:
@@ -531,10 +533,14 @@ class HostRowKernels:
     def event_eval(self, out, x, mask) -> None:
         """out[r, :] = the kept quartic of row r at x[r] for the rows with mask[r] (the arithmetic of `_dense_commit`)."""
         idx = torch.nonzero(mask).view(-1)
-        if idx.numel() == 0:
+        self.event_eval_mapped(out, idx, idx, x[idx])
+
+    def event_eval_mapped(self, out, dst, src, x) -> None:
+        """out[dst[i] (None: i), :] = the kept quartic of ORIGINAL row src[i] at x[i], for the index lists `dst`, `src`."""
+        if src.numel() == 0:
             return
-        e, d, c, b, a = self.ev.coef[:, idx].unbind(0)
-        x1 = x[idx][:, None]
+        e, d, c, b, a = self.ev.coef[:, src.to(torch.int64)].unbind(0)
+        x1 = x[:, None]
         x2 = x1 * x1
         x3 = x2 * x1
         x4 = x3 * x1
@@ -542,7 +548,10 @@ class HostRowKernels:
         total = total + c * x2
         total = total + b * x3
         total = total + a * x4
-        out[idx] = total
+        if dst is None:
+            out.copy_(total)
+        else:
+            out[dst.to(torch.int64)] = total
 
     def _dense_commit(self, accepted, y, y1, f0, f1, ks, dts, sol, shadow=None, anchor=None):
         p, m, T = self.p, self.p.method, self.T
@@ -693,6 +702,8 @@ class HipRowKernels:
         st.tgrid = self.tg.data_ptr()
         self.dts, self.times = self.dts.index_select(0, keep), self.times.index_select(1, keep)
         st.n_rows = self.n = n_keep
+        if self.ev is not None:
+            self.ev.keep_rows(keep)
         p.keep_rows(keep)
         self.row_map = p.rows.to(device=self.active.device, dtype=torch.int32)
         return y_new, f_new
@@ -783,6 +794,10 @@ class HipRowKernels:
     def event_eval(self, out, x, mask) -> None:
         """out[r, :] = the kept quartic of row r at x[r] for the rows with mask[r] (int32 [B])."""
         self.k.row_event_eval(out, self.ev.coef, x, mask)
+
+    def event_eval_mapped(self, out, dst, src, x) -> None:
+        """out[dst[i] (None: i), :] = the kept quartic of ORIGINAL row src[i] at x[i]; `dst`, `src` int32 [n] index lists."""
+        self.k.row_event_eval_mapped(out, dst, self.ev.coef, src, x)
 
 
 def odeint_rowwise(func, y0, t, *, rtol=1e-7, atol=1e-9, method="dopri5", options=None, return_stats=False,

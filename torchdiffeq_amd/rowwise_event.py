@@ -10,6 +10,11 @@ detection (`tdeq_row_event_detect`: a row that fires leaves the active rows like
 rows that fired in this step (`tdeq_row_event_fit`), kept in a [5, B, L] buffer because the commit overwrites y0 and f0.
 The bisection evaluates the kept quartics (`tdeq_row_event_eval`); its [B] bracket arithmetic is a handful of fp64 torch
 ops, the same expressions on both backends.
+
+With `compact=` a row that has stopped — fired, reached `t_end`, or fired at `t0` — leaves the batch at the next repack
+(`odeint_rowwise`'s rule).  The quartics stay in the [5, B, L] buffer at their ORIGINAL row (`tdeq_row_event_fit_mapped`),
+`RowEvents.keep_rows` parks the event state of the rows that leave, and the bisection runs on the rows that have a quartic
+only (`tdeq_row_event_eval_mapped`).
 """
 from __future__ import annotations
 
@@ -65,12 +70,17 @@ class RowEvents:
     """The event state of one solve, shared by both backends: the starting signs, which rows fired (ever / in the last
     trial step), their brackets in solver time and the quartic of the step each row fired in.
 
-    `coef` is a [5, B, L] tensor of the state's dtype on its device — FIVE TIMES THE STATE, held for the whole solve."""
+    `coef` is a [5, B, L] tensor of the state's dtype on its device — FIVE TIMES THE STATE, held for the whole solve,
+    and indexed by ORIGINAL row also after a repack (`compact=`); the [B] vectors are then those of the rows carried,
+    and `all_fired` / `all_lo` / `all_hi` hold what the rows that left had (`keep_rows`, `full`)."""
 
     def __init__(self, p: _Problem, event_fn):
         dev, B = p.device, p.B
         self.p, self.event_fn = p, event_fn
         self.n_evals = 0
+        self.row_evals = 0                                   # the sum of y.shape[0] over the calls of event_fn
+        self.atol_rows = p.atol_rows                         # all B rows' (`_Problem.keep_rows` re-selects its own at a repack)
+        self.all_sign0 = self.all_fired = self.all_lo = self.all_hi = None      # [B], from the first repack on
         self.sign0 = torch.zeros(B, dtype=torch.int32, device=dev)
         self.fired = torch.zeros(B, dtype=torch.int32, device=dev)
         self.fired_now = torch.zeros(B, dtype=torch.int32, device=dev)
@@ -78,11 +88,16 @@ class RowEvents:
         self.hi = torch.zeros(B, dtype=torch.float64, device=dev)
         self.coef = torch.empty(5, B, p.L, dtype=p.dtype, device=dev)
 
-    def call(self, t_rows: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
-        """event_fn(t_rows [b] true time, y [b, *row_shape]) -> [b] contiguous in the state's dtype."""
+    def call(self, t_rows: torch.Tensor, y: torch.Tensor, rows=None) -> torch.Tensor:
+        """event_fn(t_rows [b] true time, y [b, *row_shape]) -> [b] contiguous in the state's dtype; with `compact` set
+        event_fn also gets the original indices of the rows of this call: those now carried, or `rows` (the bisection)."""
         self.n_evals += 1
+        self.row_evals += y.shape[0]
         p = self.p
-        g = self.event_fn(t_rows, y.view(y.shape[0], *p.shape[1:]))
+        if p.rows is None:
+            g = self.event_fn(t_rows, y.view(y.shape[0], *p.shape[1:]))
+        else:
+            g = self.event_fn(t_rows, y.view(y.shape[0], *p.shape[1:]), p.rows if rows is None else rows)
         if not isinstance(g, torch.Tensor):
             raise TypeError("odeint_rowwise_event: event_fn must return a Tensor, got {}".format(type(g).__name__))
         if g.shape != (y.shape[0],):
@@ -100,12 +115,41 @@ class RowEvents:
         controller — the end of an accepted step; the value of any other row is ignored)."""
         return (t0 * self.p.sign).to(self.p.dtype)
 
+    # -- compact=: what a repack does to the event state ------------------------------------------------------------------
+    def _park(self) -> None:
+        """`fired`, `lo`, `hi` of the rows now carried -> the [B] vectors, at their original indices (as
+        `HipRowKernels._park_counts` keeps the counters of the rows that leave)."""
+        rows = self.p.rows
+        self.all_fired.index_copy_(0, rows, self.fired)
+        self.all_lo.index_copy_(0, rows, self.lo)
+        self.all_hi.index_copy_(0, rows, self.hi)
+
+    def keep_rows(self, keep: torch.Tensor) -> None:
+        """A repack, before `_Problem.keep_rows`: the carried rows `keep` (int64 positions in the current batch,
+        ascending, on the state's device) stay.  Tiny [B] torch ops, like the other vectors of `repack`."""
+        if self.all_fired is None:
+            self.all_sign0 = self.sign0                      # (never written after t0: the first batch's vector is the full one)
+            self.all_fired, self.all_lo, self.all_hi = (torch.zeros_like(v) for v in (self.fired, self.lo, self.hi))
+        self._park()
+        for name in ("sign0", "fired", "fired_now", "lo", "hi"):
+            setattr(self, name, getattr(self, name).index_select(0, keep))
+
+    def full(self):
+        """(sign0, fired, lo, hi) as [B] vectors indexed by original row, for `_locate`."""
+        if self.all_fired is None:
+            return self.sign0, self.fired, self.lo, self.hi
+        self._park()
+        return self.all_sign0, self.all_fired, self.all_lo, self.all_hi
+
     # -- the hook of HipRowKernels.trial_step ----------------------------------------------------------------------------
     def device_step(self, kern, y, y1, f0, f1, mid, coefs, dts) -> None:
         g1 = self.call(self.step_times(kern.t0), y1)
         kern.k.row_event_detect(g1, self.sign0, kern.ctrl, kern.st, kern.dts, kern.times, self.fired, self.fired_now,
                                 self.lo, self.hi)
-        kern.k.row_event_fit(self.coef, self.fired_now, y, y1, f0, f1, mid, coefs, dts)
+        if kern.row_map is None:
+            kern.k.row_event_fit(self.coef, self.fired_now, y, y1, f0, f1, mid, coefs, dts)
+        else:                                                # a compacted batch: the quartic goes to the row's original index
+            kern.k.row_event_fit_mapped(self.coef, kern.row_map, self.fired_now, y, y1, f0, f1, mid, coefs, dts)
 
     # -- the hook of HostRowKernels.trial_step ---------------------------------------------------------------------------
     def host_step(self, kern, accepted, y, y1, f0, f1, ks, dts) -> None:
@@ -132,7 +176,8 @@ class RowEvents:
         qb = (((f0r * 5.0 - f1r * 3.0) * d + y0r * 18.0) + y1r * 14.0) - ymid * 32.0
         qc = (((f1r - f0r * 4.0) * d - y0r * 11.0) - y1r * 5.0) + ymid * 16.0
         qd = f0r * d
-        self.coef[:, idx] = torch.stack([y0r, qd, qc, qb, qa])
+        at = idx if kern.row_map is None else torch.from_numpy(kern.row_map[rows])
+        self.coef[:, at] = torch.stack([y0r, qd, qc, qb, qa])
 
 
 def _bisection_rounds(width: torch.Tensor, has_q: torch.Tensor) -> np.ndarray:
@@ -144,17 +189,24 @@ def _bisection_rounds(width: torch.Tensor, has_q: torch.Tensor) -> np.ndarray:
     return np.where(has_q.cpu().numpy(), n, 0.0)
 
 
+def _atol_rows(p: _Problem, atol_rows) -> torch.Tensor:
+    """Each row's atol rounded to the state's dtype, as fp64 [B] on the state's device (`atol_rows`: the [B] vector of a
+    solve with per-row tolerances, else None)."""
+    if atol_rows is not None:
+        return atol_rows.to(torch.float64)
+    return torch.full((p.B,), float(p.np_dtype(p.atol)), dtype=torch.float64, device=p.device)
+
+
 def _locate(p: _Problem, ev: RowEvents, kern, sol, at_start):
     """The one bisection after every row has stopped -> (event time [B] fp64 in solver time, fired [B] bool);
     solution row 1 of the rows that fired is overwritten with the quartic at the event time."""
+    if p.compact is not None:
+        return _locate_compact(p, ev, kern, sol, at_start)
     dev = p.device
     fired = ev.fired.bool()
     has_q = fired & ~at_start                                # (a row that fired at t0 took no step: it keeps y0)
     ta, tb = ev.lo.clone(), ev.hi.clone()                    # the step the row fired in: the quartic's interval
-    if p.atol_rows is not None:
-        atol = p.atol_rows.to(torch.float64)
-    else:
-        atol = torch.full((p.B,), float(p.np_dtype(p.atol)), dtype=torch.float64, device=dev)
+    atol = _atol_rows(p, p.atol_rows)
     n = _bisection_rounds((tb - ta) / atol, has_q)
     if np.isinf(n).any():
         raise OverflowError("odeint_rowwise_event: cannot bisect to a tolerance of 0 (atol must be positive) in row {}".format(
@@ -177,8 +229,41 @@ def _locate(p: _Problem, ev: RowEvents, kern, sol, at_start):
     return torch.where(fired, event_s, t_end), fired
 
 
+def _locate_compact(p: _Problem, ev: RowEvents, kern, sol, at_start):
+    """`_locate` of a solve with `compact` set: the same expressions on the rows that have a quartic only, gathered in
+    ascending original order — [n_q] vectors, a [n_q, L] `y_mid`, `event_fn` called with `rows = idx`."""
+    sign0, fired, lo_all, hi_all = ev.full()
+    fired = fired.bool()
+    has_q = fired & ~at_start
+    idx = torch.nonzero(has_q).view(-1)
+    ta, tb = lo_all.index_select(0, idx), hi_all.index_select(0, idx)
+    n = _bisection_rounds((tb - ta) / _atol_rows(p, ev.atol_rows).index_select(0, idx), torch.ones_like(idx, dtype=torch.bool))
+    if np.isinf(n).any():
+        raise OverflowError("odeint_rowwise_event: cannot bisect to a tolerance of 0 (atol must be positive) in row {}".format(
+            int(idx[int(np.flatnonzero(np.isinf(n))[0])])))
+    nitrs = torch.from_numpy(n.astype(np.int64)).to(p.device)
+    width = tb - ta
+    lo, hi, s0 = ta, tb, sign0.index_select(0, idx)
+    src = idx.to(torch.int32)
+    y_mid = torch.empty(idx.numel(), p.L, dtype=p.dtype, device=p.device)
+    for i in range(int(n.max()) if n.size else 0):
+        t_mid = (lo + hi) / 2
+        kern.event_eval_mapped(y_mid, None, src, ((t_mid - ta) / width).to(p.dtype))
+        same = _sign(ev.call((t_mid * p.sign).to(p.dtype), y_mid, idx)) == s0
+        update = nitrs > i
+        lo, hi = torch.where(update & same, t_mid, lo), torch.where(update & ~same, t_mid, hi)
+    event_s = ((lo_all + hi_all) / 2).index_copy_(0, idx, (lo + hi) / 2)
+    t_end = p.tgrid[1].to(p.device)
+    fired = fired & (event_s <= t_end)
+    x = ((event_s.index_select(0, idx) - ta) / width).to(p.dtype)
+    sel = fired.index_select(0, idx)
+    at = src[sel]
+    kern.event_eval_mapped(sol[1], at, at, x[sel])
+    return torch.where(fired, event_s, t_end), fired
+
+
 def odeint_rowwise_event(func, y0, t0, *, event_fn, t_end=None, rtol=1e-7, atol=1e-9, method="dopri5", options=None,
-                         return_stats=False):
+                         return_stats=False, compact=None):
     """Integrate B independent IVPs `dy_r/dt = func(t, y)[r]` from `t0`, each row until ITS terminal event: the first
     sign change of `event_fn(t, y)[r]` — or until `t_end[r]`, whichever comes first.  Returns `(event_t, solution)`.
 
@@ -218,12 +303,26 @@ def odeint_rowwise_event(func, y0, t0, *, event_fn, t_end=None, rtol=1e-7, atol=
     `[B]`), `nfe`, `fired` (bool `[B]`, on the CPU like the counters) and `n_event_evals` (calls of `event_fn`: one at `t0`,
     one per trial step, one per bisection round).
 
+    `compact` (default None / False: off; `True` = 0.5; a float c in (0, 1]; anything else ValueError) takes the rows that
+    have stopped out of the batch by `odeint_rowwise`'s rule: after every poll, the one after the initial step included,
+    with `cur` rows carried and `n_active` of them still active, `0 < n_active < cur` and `n_active <= c * cur` repacks the
+    batch to the active rows.  A row that fired, a row that reached `t_end` and a row that fired at `t0` are all simply
+    not active (the rows fired at `t0` leave at the first poll).  With `compact` set `func` is called as
+    `func(t_rows, y, rows)` and `event_fn` as `event_fn(t_rows, y, rows)` — every call, the ones at `t0` and those of the
+    bisection included: `rows` is an int64 `[b]` tensor on the state's device with the original indices of the rows of
+    the call, ascending (`arange(B)` before the first repack); per-row parameters must be indexed with it.  The final
+    bisection then runs on the rows that have a quartic only (those that fired after `t0`), with the same number of
+    rounds.  `event_t`, `solution`, `n_accepted`, `n_rejected`, `fired`, `nfe` and `n_event_evals` are bit for bit those of
+    the same call without `compact` (as long as `func` and `event_fn` treat rows independently), errors name the
+    original row, and `stats` gains `row_evals` (the sum of `y.shape[0]` over the calls of `func`), `n_repacks` and
+    `event_row_evals` (that sum over the calls of `event_fn`).
+
     Memory: besides the buffers of `odeint_rowwise` the solve holds the quartic coefficients of every row, a `[5, B, L]`
     tensor of the state's dtype — five times the state.
 
     Out of scope (raises or is not offered): gradients (with grad mode on and anything requiring grad this raises
-    NotImplementedError; there is no `differentiable` argument), `compact`, several event functions, non-terminal events,
-    16-bit or complex states, captured (hipGraph) steps.
+    NotImplementedError; there is no `differentiable` argument), several event functions, non-terminal events, 16-bit or
+    complex states, captured (hipGraph) steps.
     """
     if not callable(event_fn):
         raise ValueError("odeint_rowwise_event: event_fn must be callable: event_fn(t_rows [b], y [b, *row_shape]) -> [b]")
@@ -231,7 +330,7 @@ def odeint_rowwise_event(func, y0, t0, *, event_fn, t_end=None, rtol=1e-7, atol=
         t = _event_grid(t0, t_end, y0.shape[0])
     else:
         t = torch.zeros(2, dtype=torch.float64)              # (_Problem refuses this y0)
-    p = _Problem(func, y0, t, rtol, atol, method, options, None)
+    p = _Problem(func, y0, t, rtol, atol, method, options, None, False, compact)
     ev = RowEvents(p, event_fn)
     start = (p.tgrid[0] * p.sign).to(p.dtype).to(p.device)   # t0 in true time, as func and event_fn see it
     with torch.no_grad(), device_guard(p.device):
@@ -265,6 +364,8 @@ def odeint_rowwise_event(func, y0, t0, *, event_fn, t_end=None, rtol=1e-7, atol=
                     p.raise_row_error(failure, y)
                 if n_active == 0:
                     break
+                if p.compact is not None and n_active < y.shape[0] and n_active <= p.compact * y.shape[0]:
+                    y, f0 = kern.repack(y, f0, n_active)
                 y, f0 = kern.trial_step(y, f0, sol)
             n_acc, n_rej = kern.counts()
             event_s, fired = _locate(p, ev, kern, sol, at_start)
@@ -274,4 +375,6 @@ def odeint_rowwise_event(func, y0, t0, *, event_fn, t_end=None, rtol=1e-7, atol=
         return event_t, solution
     stats = {"n_accepted": n_acc.to(torch.int64), "n_rejected": n_rej.to(torch.int64), "nfe": p.nfe,
              "fired": fired.cpu(), "n_event_evals": ev.n_evals}
+    if p.compact is not None:
+        stats["row_evals"], stats["n_repacks"], stats["event_row_evals"] = p.row_evals, p.n_repacks, ev.row_evals
     return event_t, solution, stats
