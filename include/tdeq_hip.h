@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define TDEQ_ABI_VERSION 27
+#define TDEQ_ABI_VERSION 28
 #define TDEQ_F32 0
 #define TDEQ_F64 1
 /* interleaved (re, im) complex states — accepted by the NORM entry points only (tdeq_error_norm, tdeq_error_norm_partial[_ctrl],
@@ -699,6 +699,48 @@ int tdeq_row_event_fit_mapped(void* q, const int32_t* row_map, int64_t q_rows, c
                               int n_terms, const void* dts, int64_t n_rows, int64_t row_len, int dtype, void* stream);
 int tdeq_row_event_eval_mapped(void* out, const int32_t* dst_map, int64_t out_rows, const void* q, const int32_t* src_map,
                                int64_t q_rows, const void* x, int64_t n_idx, int64_t row_len, int dtype, void* stream);
+
+/*
+ * ---- Per-row dense output (ABI 28; torchdiffeq_amd/rowwise_dense.py `odeint_rowwise_dense`) ----
+ * The piecewise quartic of a whole rowwise solve: one segment per accepted step of each row.  During the solve the
+ * quartics go to CHUNKS — `q` [5, cap, row_len] of the state type, per-slot metadata `slot_row` / `slot_ord` (int32 [cap]),
+ * `slot_ta` / `slot_tb` (double [cap], solver time) and a device `counter` (int32 [2] = {slots taken, a row found no slot});
+ * after it every chunk is packed into `coeffs` [5, n_seg, row_len], row r's segments contiguous and in step order at
+ * offsets[r] .. offsets[r + 1] - 1.
+ * tdeq_row_dense_slots   after tdeq_row_control(mode 0), one lane per row of `st`.  A row with accepted[r] takes the slot
+ *                        s = (old counter[0]) + (its rank among the accepted rows of the launch): a ballot prefix inside a
+ *                        wave, one atomicAdd per wave — unique, inside [old counter[0], old counter[0] + accepted rows), in
+ *                        arrival order (no contract).  With s < cap: slot_row[s] = row_map ? row_map[r] : r, slot_ord[s] =
+ *                        n_acc[r] - 1 (the controller has counted the step), slot_ta[s] = tprev[r], slot_tb[s] = t0[r],
+ *                        slot[r] = s, mask[r] = 1.  With s >= cap nothing is written at s, counter[1] = 1, slot[r] = -1,
+ *                        mask[r] = 0.  Every other row: slot[r] = -1, mask[r] = 0.  The quartic then goes to the chunk by
+ *                        tdeq_row_event_fit_mapped(q = chunk, row_map = slot, fired_now = mask), which reads row_map[r] of
+ *                        the rows with fired_now[r] only and needs cap >= n_rows.  cap + n_rows must fit an int32.
+ * tdeq_row_dense_pack    dst[p, dest[s], :] = src[p, s, :] for s < n_used and the 5 planes p: a copy of bits.  `dst` is
+ *                        [5, dst_rows, row_len], `src` [5, src_rows, row_len], `dest` a device int64 [n_used] with
+ *                        0 <= dest[s] < dst_rows and no row named twice (not checked: it lives on the device); n_used <=
+ *                        src_rows.  16-byte elements when row_len is a multiple of 16 / sizeof(T) and both bases are 16-byte
+ *                        aligned, scalar elements otherwise.  Other rows of dst are untouched.
+ * tdeq_row_dense_search  one lane per query i = j * n_rows + r of `tq` [n_q, n_rows] (double, solver time).  With t0[r] <=
+ *                        tq <= t1[r] (and a row that has a segment): seg[i] = the first s in offsets[r] .. offsets[r + 1] - 1
+ *                        with tq <= seg_tb[s], the row's last segment if there is none (it may end beyond t1[r]), found by
+ *                        bisection; x[i] = T((tq - seg_ta[s]) / (seg_tb[s] - seg_ta[s])), the quotient formed in fp64.  A
+ *                        breakpoint belongs to the earlier step (x = 1), tq = t0[r] to the first (x = 0).  Any other query,
+ *                        a NaN included: seg[i] = offsets[r], x[i] = NaN, and status[0] (int32, preset to INT32_MAX by the
+ *                        caller) is lowered to i — a minimum inside the wave, one atomicMin per wave that has one.
+ *                        0 <= offsets[r] <= offsets[r + 1] <= n_seg; 1 <= n_seg <= INT32_MAX, n_q * n_rows < INT32_MAX.
+ *                        The values are then tdeq_row_event_eval_mapped(out [n_q * n_rows, row_len], dst_map = NULL,
+ *                        q = coeffs, src_map = seg, x).
+ * 64-bit offsets.  A NULL pointer (row_map excepted), a negative size, a size beyond the stated limits or a dtype other than
+ * TDEQ_F32 / TDEQ_F64: TDEQ_EINVAL before any launch.  n_rows == 0 / n_used == 0 / n_q == 0: no-op.
+ */
+int tdeq_row_dense_slots(const tdeq_row_state* st, const int32_t* row_map, int64_t cap, int32_t* counter, int32_t* slot_row,
+                         int32_t* slot_ord, double* slot_ta, double* slot_tb, int32_t* slot, int32_t* mask, void* stream);
+int tdeq_row_dense_pack(void* dst, int64_t dst_rows, const void* src, int64_t src_rows, const int64_t* dest, int64_t n_used,
+                        int64_t row_len, int dtype, void* stream);
+int tdeq_row_dense_search(const double* tq, int64_t n_q, const int64_t* offsets, const double* seg_ta, const double* seg_tb,
+                          int64_t n_seg, const double* t0, const double* t1, int64_t n_rows, int32_t* seg, void* x,
+                          int32_t* status, int dtype, void* stream);
 
 #ifdef __cplusplus
 }

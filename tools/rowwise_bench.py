@@ -13,6 +13,9 @@ on a mixed-stiffness batch.
     python tools/rowwise_bench.py --event --compact [--setting plain|0.5|1.0] [--reps 5]    (one JSON line of one fresh process)
     python tools/rowwise_bench.py --event-compact-summary lines.jsonl[,parent_event.jsonl,new_event.jsonl]
                                   --out profiles/rowwise_event_compact_bench.json
+    python tools/rowwise_bench.py --dense [--reps 5] [--out dense.json]
+    python tools/rowwise_bench.py --dense-summary dense.json,parent_event.jsonl,new_event.jsonl,parent_bench.jsonl,new_bench.jsonl
+                                  --out profiles/rowwise_dense_bench.json
 
 `--compact`: wall time of one solve at the headline shape with a per-row rate spread over logspace(-1, 1.5) (so that the
 rows' trial counts differ), plain against `compact=0.5` and `compact=1.0`: `row_evals` against `nfe x B` (the bound on
@@ -32,6 +35,16 @@ plain, `compact=0.5` or `compact=1.0`: the median of `--reps` solves after a war
 one instrumented solve with the final bisection timed between synchronisations.  `--event-compact-summary` folds the lines
 of alternated processes (the first round warms up) and, given the `--event` lines of the parent tree and of this tree,
 whether the plain event solve (func y @ A.T) stayed inside the parent's spread.
+
+`--dense`: `odeint_rowwise_dense` at the rate-spread shape of `--compact` (k_r * (y @ A.T), k_r over logspace(-1, 1.5),
+t1 = 0.5) against `odeint_rowwise` on [t0, t1] in the same process — the median of `--reps` solves each after a warm-up,
+`n_segments`, `n_chunks`, the bytes the result holds — and the evaluation `dense(t)` for Q = 16 random times per row:
+ms per call without the host read (`check=False`), the achieved bytes/s counting 5 coefficient reads and 1 write per output
+element, and the search launch alone.
+
+`--dense-summary` folds that file with the lines of alternated fresh processes of the parent tree and of this tree — `--event`
+(the plain rowwise solve and the plain event solve; the first line of each file is the warm-up round) and `bench.py --gpus 1
+--steps 200 --warmup 20` — and says whether this tree's medians lie inside the parent's observed spread.
 
 `--grad`: forward + backward of a `differentiable=True` solve per trial step at the headline, next to plain `odeint`
 backprop of the same state, and (`--parity`) the per-row deviations of the rowwise gradients from the reference's
@@ -308,6 +321,85 @@ def _event_compact(reps: int, setting: str):
             "trials_max": int(trials.max())}
 
 
+def _dense(reps: int, Q: int = 16):
+    """Solve with and without the store, and the evaluation of the dense object, in one process."""
+    import torchdiffeq_amd as tda
+    dev = torch.device("cuda", 0)
+    B, D = 65536, 128
+    g = torch.Generator().manual_seed(0)
+    G = torch.randn(D, D, generator=g, dtype=torch.float64) / D ** 0.5
+    A = (0.5 * (G - G.T) - 0.1 * torch.eye(D, dtype=torch.float64)).float().to(dev)
+    k = torch.logspace(-1, 1.5, B, dtype=torch.float64)[torch.randperm(B, generator=g)][:, None].float().to(dev)
+    y0 = torch.randn(B, D, generator=g).to(dev)
+    t = torch.tensor([0.0, 0.5], device=dev)
+    med = lambda v: sorted(v)[len(v) // 2]       # noqa: E731
+    func = lambda t_, y: k * (y @ A.T)           # noqa: E731
+    kw = dict(rtol=1e-7, atol=1e-9, return_stats=True)
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3, out
+    plain_ms, dense_ms = [], []
+    with torch.no_grad():
+        for rep in range(reps + 1):                           # the first pair warms up; the two alternate
+            a, (_, st_p) = timed(lambda: tda.odeint_rowwise(func, y0, t, **kw))
+            b, (dense, st) = timed(lambda: tda.odeint_rowwise_dense(func, y0, 0.0, 0.5, **kw))
+            if rep:
+                plain_ms.append(a)
+                dense_ms.append(b)
+        tq = torch.rand(Q, B, generator=g, dtype=torch.float64).to(dev) * 0.5
+        eval_ms, search_ms = [], []
+        for rep in range(reps + 1):
+            a, out = timed(lambda: dense(tq, check=False))
+            b, (_, _, status) = timed(lambda: dense.search(tq))          # (increasing time: solver time is true time)
+            if rep:
+                eval_ms.append(a)
+                search_ms.append(b)
+        finite = bool(torch.isfinite(out).all()) and int(status) == 0x7FFFFFFF
+    trials = st["n_accepted"] + st["n_rejected"]
+    moved = 6 * Q * B * D * 4
+    held = dense.coeffs.numel() * 4 + 2 * 8 * dense.n_segments + 8 * (B + 1)
+    return {"plain_ms_per_solve": plain_ms, "dense_ms_per_solve": dense_ms, "plain_median_ms": med(plain_ms),
+            "dense_median_ms": med(dense_ms), "extra_ms": med(dense_ms) - med(plain_ms),
+            "same_counters_as_plain": bool(torch.equal(st["n_accepted"], st_p["n_accepted"])) and st["nfe"] == st_p["nfe"],
+            "trial_steps": (st["nfe"] - 2) // 6, "n_segments": st["n_segments"], "n_chunks": st["n_chunks"],
+            "bytes_held": held, "accepted_min": int(st["n_accepted"].min()), "accepted_median": float(st["n_accepted"].median()),
+            "accepted_max": int(st["n_accepted"].max()), "trials_max": int(trials.max()),
+            "eval": {"Q": Q, "ms_per_call": eval_ms, "median_ms": med(eval_ms), "bytes_moved": moved,
+                     "achieved_TBs": moved / (med(eval_ms) * 1e-3) / 1e12, "hbm_peak_TBs": PEAK_TBS,
+                     "search_alone_ms": search_ms, "search_alone_median_ms": med(search_ms), "all_finite": finite}}
+
+
+def _dense_summary(paths, out):
+    med = lambda v: sorted(v)[len(v) // 2]       # noqa: E731
+
+    def fold(vals):
+        return {"per_process": [round(v, 4) for v in vals], "median": round(med(vals), 4), "min": round(min(vals), 4),
+                "max": round(max(vals), 4)}
+
+    def pair(parent, new):
+        p, n = fold(parent), fold(new)
+        return {"parent": p, "new": n, "new_median_inside_parent_min_max": p["min"] <= n["median"] <= p["max"]}
+    lines = lambda path: [json.loads(x) for x in open(path) if x.strip().startswith("{")]      # noqa: E731
+    res = json.load(open(paths[0]))
+    pe, ne = lines(paths[1])[1:], lines(paths[2])[1:]                         # the first round warms up
+    pb, nb = lines(paths[3]), lines(paths[4])
+    res["plain_paths_against_parent"] = {
+        "what": "parent tree and this tree alternated in fresh processes in one session; tools/rowwise_bench.py --event "
+                "--reps 3 (func y @ A.T; the median of 3 solves per process after a warm-up solve, the first round of "
+                "processes dropped) and bench.py --gpus 1 --steps 200 --warmup 20 (every process kept)",
+        "plain_rowwise_ms_per_trial": pair([r["plain"]["median_ms_per_trial"] for r in pe],
+                                           [r["plain"]["median_ms_per_trial"] for r in ne]),
+        "plain_event_ms_per_solve": pair([r["event"]["median_ms_per_solve"] for r in pe],
+                                         [r["event"]["median_ms_per_solve"] for r in ne]),
+        "bench_rk_stages_per_s": pair([r["value"] for r in pb], [r["value"] for r in nb])}
+    json.dump(res, open(out, "w"), indent=1)
+    print(json.dumps(res["plain_paths_against_parent"]))
+
+
 def _event_compact_summary(paths, out):
     """Fold the JSON lines of the alternated fresh processes (one file, every setting; the first line of each setting is
     the warm-up round).  With two more files — `--event` lines of the parent tree and of this tree, alternated — also the
@@ -554,7 +646,23 @@ def main():
     ap.add_argument("--event-summary", default=None)
     ap.add_argument("--setting", default="plain", choices=("plain", "0.5", "1.0"))
     ap.add_argument("--event-compact-summary", default=None)
+    ap.add_argument("--dense", action="store_true")
+    ap.add_argument("--dense-summary", default=None)
     a = ap.parse_args()
+    if a.dense_summary:
+        _dense_summary(a.dense_summary.split(","), a.out)
+        return
+    if a.dense:
+        res = {"device": torch.cuda.get_device_name(0), "arch": torch.cuda.get_device_properties(0).gcnArchName,
+               "what": "tools/rowwise_bench.py --dense: 65536 x 128 fp32 dopri5, func k_r * (y @ A.T) with k_r in "
+                       "logspace(-1, 1.5) shuffled, t0 = 0, t1 = 0.5, rtol 1e-7, atol 1e-9; one process, the plain and the "
+                       "dense solve alternated, the first pair a warm-up",
+               "dense": _dense(a.reps)}
+        print(json.dumps(res))
+        if a.out:
+            os.makedirs(os.path.dirname(a.out) or ".", exist_ok=True)
+            json.dump(res, open(a.out, "w"), indent=1)
+        return
     if a.event_summary:
         _event_summary(a.event_summary.split(","), a.out)
         return

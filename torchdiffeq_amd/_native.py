@@ -18,7 +18,7 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-TDEQ_ABI_VERSION = 27
+TDEQ_ABI_VERSION = 28
 TDEQ_F32, TDEQ_F64 = 0, 1
 TDEQ_C64, TDEQ_C128 = 2, 3        # interleaved complex: the norm entry points only (include/tdeq_hip.h)
 TDEQ_BF16, TDEQ_F16 = 4, 5        # reduced-precision states: the entry points of the host-driven step (LowPrecisionHipKernels)
@@ -264,6 +264,16 @@ ABI_SIGNATURES = {
     "tdeq_row_event_eval_mapped": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
                                                   ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64,
                                                   ctypes.c_int64, ctypes.c_int, ctypes.c_void_p]),
+    # per-row dense output (ABI 28, rowwise_dense.py)
+    "tdeq_row_dense_slots": (ctypes.c_int, [ctypes.POINTER(RowState), ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
+                                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "tdeq_row_dense_pack": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64,
+                                           ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p]),
+    "tdeq_row_dense_search": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
+                                             ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
+                                             ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                             ctypes.c_int, ctypes.c_void_p]),
 }
 
 
@@ -1016,6 +1026,62 @@ class HipKernels:
                                                    out.shape[0], q.data_ptr(), src_map.data_ptr(), q.shape[1], x.data_ptr(),
                                                    n_idx, out.shape[1], dtype_code(out.dtype), self._stream()),
                "tdeq_row_event_eval_mapped")
+
+    # -- per-row dense output (odeint_rowwise_dense, rowwise_dense.py) -------------------------------------------------
+    def row_dense_slots(self, st: RowState, row_map, cap: int, counter, slot_row, slot_ord, slot_ta, slot_tb, slot,
+                        mask) -> None:
+        """tdeq_row_dense_slots: every accepted row of `st` takes a slot of a chunk of `cap` slots.  `counter` int32 [2],
+        `slot_row` / `slot_ord` int32 [cap], `slot_ta` / `slot_tb` fp64 [cap], `slot` / `mask` int32 [n_rows], `row_map`
+        int32 [n_rows] or None (identity)."""
+        n = int(st.n_rows)
+        for name, t, dtype, size in (("counter", counter, torch.int32, 2), ("slot_row", slot_row, torch.int32, cap),
+                                     ("slot_ord", slot_ord, torch.int32, cap), ("slot_ta", slot_ta, torch.float64, cap),
+                                     ("slot_tb", slot_tb, torch.float64, cap), ("slot", slot, torch.int32, n),
+                                     ("mask", mask, torch.int32, n)):
+            if t.shape != (size,) or t.dtype != dtype or not t.is_contiguous():
+                raise ValueError(f"row_dense_slots: {name} must be a contiguous {dtype} [{size}] tensor")
+        if row_map is not None and (row_map.shape != (n,) or row_map.dtype != torch.int32 or not row_map.is_contiguous()):
+            raise ValueError("row_dense_slots: row_map must be a contiguous int32 [n_rows] tensor")
+        _check(self.lib.tdeq_row_dense_slots(ctypes.byref(st), None if row_map is None else row_map.data_ptr(), cap,
+                                             counter.data_ptr(), slot_row.data_ptr(), slot_ord.data_ptr(),
+                                             slot_ta.data_ptr(), slot_tb.data_ptr(), slot.data_ptr(), mask.data_ptr(),
+                                             self._stream()), "tdeq_row_dense_slots")
+
+    def row_dense_pack(self, dst, src, dest, n_used: int) -> None:
+        """tdeq_row_dense_pack: dst[:, dest[s]] = src[:, s] for s < n_used; `dst` [5, dst_rows, L] and `src` [5, src_rows, L]
+        contiguous in one dtype, `dest` int64 [n_used] on the device, its values rows of `dst`."""
+        if n_used == 0:                       # (nothing to move; empty tensors have null pointers, which the ABI refuses)
+            return
+        for name, t in (("dst", dst), ("src", src)):
+            if t.dim() != 3 or t.shape[0] != 5 or t.shape[2] != dst.shape[2] or t.dtype != dst.dtype or not t.is_contiguous():
+                raise ValueError(f"row_dense_pack: {name} must be a contiguous [5, rows, L] tensor of one dtype")
+        if dest.shape != (n_used,) or dest.dtype != torch.int64 or not dest.is_contiguous():
+            raise ValueError("row_dense_pack: dest must be a contiguous int64 [n_used] tensor")
+        _check(self.lib.tdeq_row_dense_pack(dst.data_ptr(), dst.shape[1], src.data_ptr(), src.shape[1], dest.data_ptr(),
+                                            n_used, dst.shape[2], dtype_code(dst.dtype), self._stream()),
+               "tdeq_row_dense_pack")
+
+    def row_dense_search(self, tq, offsets, seg_ta, seg_tb, t0, t1, seg, x, status) -> None:
+        """tdeq_row_dense_search: `tq` fp64 [Q, B] in solver time, `offsets` int64 [B + 1], `seg_ta` / `seg_tb` fp64 [n_seg],
+        `t0` / `t1` fp64 [B]; writes `seg` int32 [Q * B] and `x` [Q * B] of the state's dtype and lowers `status` (int32
+        [1], preset to INT32_MAX) to the smallest out-of-range query index."""
+        if tq.numel() == 0:
+            return
+        Q, B = tq.shape
+        n_seg = seg_ta.numel()
+        for name, t, dtype, size in (("tq", tq.view(-1), torch.float64, Q * B), ("offsets", offsets, torch.int64, B + 1),
+                                     ("seg_ta", seg_ta, torch.float64, n_seg), ("seg_tb", seg_tb, torch.float64, n_seg),
+                                     ("t0", t0, torch.float64, B), ("t1", t1, torch.float64, B),
+                                     ("seg", seg, torch.int32, Q * B), ("x", x, x.dtype, Q * B),
+                                     ("status", status, torch.int32, 1)):
+            if t.shape != (size,) or t.dtype != dtype or not t.is_contiguous():
+                raise ValueError(f"row_dense_search: {name} must be a contiguous {dtype} [{size}] tensor")
+        if not tq.is_contiguous():
+            raise ValueError("row_dense_search: tq must be contiguous")
+        _check(self.lib.tdeq_row_dense_search(tq.data_ptr(), Q, offsets.data_ptr(), seg_ta.data_ptr(), seg_tb.data_ptr(),
+                                              n_seg, t0.data_ptr(), t1.data_ptr(), B, seg.data_ptr(), x.data_ptr(),
+                                              status.data_ptr(), dtype_code(x.dtype), self._stream()),
+               "tdeq_row_dense_search")
 
 
 class ComplexHipKernels:

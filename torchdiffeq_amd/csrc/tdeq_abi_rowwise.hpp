@@ -5,6 +5,7 @@
 
 #include "tdeq_kernels_rowwise.hpp"
 #include "tdeq_kernels_rowwise_event.hpp"
+#include "tdeq_kernels_rowwise_dense.hpp"
 
 namespace {
 using namespace tdeq;
@@ -837,4 +838,97 @@ int tdeq_row_event_eval_mapped(void* out, const int32_t* dst_map, int64_t out_ro
     return dtype == TDEQ_F32
                ? row_event_eval_mapped_launch<float>(out, dst_map, q, src_map, q_rows, x, n_idx, row_len, s)
                : row_event_eval_mapped_launch<double>(out, dst_map, q, src_map, q_rows, x, n_idx, row_len, s);
+}
+
+// ---- per-row dense output: tdeq_row_dense_slots / tdeq_row_dense_pack / tdeq_row_dense_search -------------------------
+namespace {
+
+template <typename E>
+int row_dense_pack_launch(const RowDensePackArgs& a, hipStream_t s) {
+    hipLaunchKernelGGL((row_dense_pack_kernel<E>), dim3(stream_grid(a.ne, kBlock)), dim3(kBlock), 0, s, a);
+    return check_launch();
+}
+
+}  // namespace
+
+int tdeq_row_dense_slots(const tdeq_row_state* st, const int32_t* row_map, int64_t cap, int32_t* counter, int32_t* slot_row,
+                         int32_t* slot_ord, double* slot_ta, double* slot_tb, int32_t* slot, int32_t* mask, void* stream) {
+    if (!st || !counter || !slot_row || !slot_ord || !slot_ta || !slot_tb || !slot || !mask) return TDEQ_EINVAL;
+    if (st->n_rows < 0 || !st->accepted || !st->tprev || !st->t0 || !st->n_acc) return TDEQ_EINVAL;
+    // (a slot is an int32, and the counter may run n_rows past cap before the host looks at it)
+    if (cap < 0 || st->n_rows > 0x7fffffffLL || cap > 0x7fffffffLL - st->n_rows) return TDEQ_EINVAL;
+    if (st->n_rows == 0) return 0;
+    RowDenseSlotsArgs a;
+    a.accepted = st->accepted;
+    a.tprev = st->tprev;
+    a.t0 = st->t0;
+    a.n_acc = st->n_acc;
+    a.row_map = row_map;
+    a.n_rows = st->n_rows;
+    a.cap = (int32_t)cap;
+    a.counter = counter;
+    a.slot_row = slot_row;
+    a.slot_ord = slot_ord;
+    a.slot_ta = slot_ta;
+    a.slot_tb = slot_tb;
+    a.slot = slot;
+    a.mask = mask;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const dim3 grid((unsigned)((a.n_rows + kBlock - 1) / kBlock));
+    hipLaunchKernelGGL(row_dense_slots_kernel, grid, dim3(kBlock), 0, s, a);
+    return check_launch();
+}
+
+int tdeq_row_dense_pack(void* dst, int64_t dst_rows, const void* src, int64_t src_rows, const int64_t* dest, int64_t n_used,
+                        int64_t row_len, int dtype, void* stream) {
+    if (!dst || !src || !dest || !row_dtype_ok(dtype)) return TDEQ_EINVAL;
+    if (dst_rows < 0 || src_rows < 0 || n_used < 0 || row_len < 1 || n_used > src_rows) return TDEQ_EINVAL;
+    if (n_used == 0) return 0;
+    if (dst_rows < 1) return TDEQ_EINVAL;
+    RowDensePackArgs a;
+    a.dst = dst;
+    a.src = src;
+    a.dest = dest;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    // (16-byte elements: row_len is a whole number of them, so every row start and every plane is aligned as its base is)
+    const int lv = row_lanes(row_len, dtype);
+    const bool vec = lv > 1 && aligned16(dst) && aligned16(src);
+    a.row_len = vec ? row_len / lv : row_len;
+    a.ne = n_used * a.row_len;
+    a.dst_plane = dst_rows * a.row_len;
+    a.src_plane = src_rows * a.row_len;
+    if (vec) {
+        return dtype == TDEQ_F32 ? row_dense_pack_launch<VecOf<float>::type>(a, s)
+                                 : row_dense_pack_launch<VecOf<double>::type>(a, s);
+    }
+    return dtype == TDEQ_F32 ? row_dense_pack_launch<float>(a, s) : row_dense_pack_launch<double>(a, s);
+}
+
+int tdeq_row_dense_search(const double* tq, int64_t n_q, const int64_t* offsets, const double* seg_ta, const double* seg_tb,
+                          int64_t n_seg, const double* t0, const double* t1, int64_t n_rows, int32_t* seg, void* x,
+                          int32_t* status, int dtype, void* stream) {
+    if (!tq || !offsets || !seg_ta || !seg_tb || !t0 || !t1 || !seg || !x || !status || !row_dtype_ok(dtype))
+        return TDEQ_EINVAL;
+    if (n_q < 0 || n_rows < 0 || n_seg < 0) return TDEQ_EINVAL;
+    if (n_q == 0 || n_rows == 0) return 0;
+    // (a segment and a query index are int32 words; INT32_MAX itself is the status word's "none")
+    if (n_seg < 1 || n_seg > 0x7fffffffLL || n_q > 0x7ffffffeLL / n_rows) return TDEQ_EINVAL;
+    RowDenseSearchArgs a;
+    a.tq = tq;
+    a.offsets = offsets;
+    a.seg_ta = seg_ta;
+    a.seg_tb = seg_tb;
+    a.t0 = t0;
+    a.t1 = t1;
+    a.n_rows = n_rows;
+    a.n_seg = n_seg;
+    a.n = n_q * n_rows;
+    a.seg = seg;
+    a.x = x;
+    a.status = status;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const dim3 grid((unsigned)((a.n + kBlock - 1) / kBlock));
+    if (dtype == TDEQ_F32) hipLaunchKernelGGL((row_dense_search_kernel<float>), grid, dim3(kBlock), 0, s, a);
+    else hipLaunchKernelGGL((row_dense_search_kernel<double>), grid, dim3(kBlock), 0, s, a);
+    return check_launch();
 }

@@ -18,7 +18,8 @@ then the error norm, the controller and the dense-output commit.  The TWO BACKEN
 `compact=` set `repack` (the finished rows leave the batch and the solve carries on with the rest, `_compact_fraction`)
 — and `odeint_rowwise` calls nothing else; an event solve (`odeint_rowwise_event`, rowwise_event.py) hands both
 backends a `RowEvents` object, whose hook runs between the controller and the commit of `trial_step`, and adds
-`deactivate_rows` / `event_eval` / `event_eval_mapped`.  WHAT IS RECORDED for `differentiable=True` lives in
+`deactivate_rows` / `event_eval` / `event_eval_mapped`; a dense solve (`odeint_rowwise_dense`, rowwise_dense.py) hands them
+a `RowDenseStore`, whose hook runs in the same place.  WHAT IS RECORDED for `differentiable=True` lives in
 rowwise_autodiff.py: the device backend hands its finished launches to a `RowRecorder` (None in a plain solve), the
 host backend records plain torch ops; `_Problem.grad_mode` is the one place that turns grad mode on for a recorded solve.
 """
@@ -288,9 +289,10 @@ class HostRowKernels:
 
     name = "host"
 
-    def __init__(self, p: _Problem, ev=None):
+    def __init__(self, p: _Problem, ev=None, dense=None):
         self.p = p
         self.ev = ev                                         # rowwise_event.RowEvents of an event solve, else None
+        self.dense = dense                                   # rowwise_dense.RowDenseStore of a dense solve, else None
         T = p.np_dtype
         self.T = T
         B = p.B
@@ -513,6 +515,8 @@ class HostRowKernels:
                 self.dt[r] = dt_next
         if self.ev is not None:                              # between controller and commit: the commit overwrites y, f0
             self.ev.host_step(self, accepted, y, y1, f0, f1, ks, dts)
+        if self.dense is not None:                           # (the same place: the quartic of every accepted step is kept)
+            self.dense.host_step(self, accepted, y, y1, f0, f1, ks, dts)
         if accepted:
             y, f0 = self._dense_commit(accepted, y, y1, f0, f1, ks, dts, sol, shadow, anchor)
         if shadow is not None and shadow.requires_grad:
@@ -535,11 +539,25 @@ class HostRowKernels:
         idx = torch.nonzero(mask).view(-1)
         self.event_eval_mapped(out, idx, idx, x[idx])
 
-    def event_eval_mapped(self, out, dst, src, x) -> None:
-        """out[dst[i] (None: i), :] = the kept quartic of ORIGINAL row src[i] at x[i], for the index lists `dst`, `src`."""
-        if src.numel() == 0:
-            return
-        e, d, c, b, a = self.ev.coef[:, src.to(torch.int64)].unbind(0)
+    def step_quartic(self, idx, y, y1, f0, f1, ks, dts) -> torch.Tensor:
+        """The quartic of the trial step just taken for the rows `idx` (int64 positions in the batch) -> [5, n, L], planes
+        e, d, c, b, a: the expressions of `_dense_commit`."""
+        p, m = self.p, self.p.method
+        d = dts[idx]
+        y0r, y1r, f0r, f1r = y[idx], y1[idx], f0[idx], f1[idx]
+        kr = [k[idx] if k is not None else None for k in ks]
+        ymid = y0r + self._sum_terms(kr, m.c_mid, d)
+        two_dt = torch.tensor(2.0, dtype=p.dtype) * d
+        qa = ((f1r - f0r) * two_dt - (y1r + y0r) * 8.0) + ymid * 16.0
+        qb = (((f0r * 5.0 - f1r * 3.0) * d + y0r * 18.0) + y1r * 14.0) - ymid * 32.0
+        qc = (((f1r - f0r * 4.0) * d - y0r * 11.0) - y1r * 5.0) + ymid * 16.0
+        qd = f0r * d
+        return torch.stack([y0r, qd, qc, qb, qa])
+
+    @staticmethod
+    def eval_quartics(q, src, x) -> torch.Tensor:
+        """The quartics q[:, src[i], :] of a [5, rows, L] tensor at x[i] -> [n, L] (the arithmetic of `_dense_commit`)."""
+        e, d, c, b, a = q[:, src.to(torch.int64)].unbind(0)
         x1 = x[:, None]
         x2 = x1 * x1
         x3 = x2 * x1
@@ -548,6 +566,13 @@ class HostRowKernels:
         total = total + c * x2
         total = total + b * x3
         total = total + a * x4
+        return total
+
+    def event_eval_mapped(self, out, dst, src, x) -> None:
+        """out[dst[i] (None: i), :] = the kept quartic of ORIGINAL row src[i] at x[i], for the index lists `dst`, `src`."""
+        if src.numel() == 0:
+            return
+        total = self.eval_quartics(self.ev.coef, src, x)
         if dst is None:
             out.copy_(total)
         else:
@@ -605,9 +630,10 @@ class HipRowKernels:
 
     name = "hip"
 
-    def __init__(self, p: _Problem, ev=None):
+    def __init__(self, p: _Problem, ev=None, dense=None):
         self.p = p
         self.ev = ev                                         # rowwise_event.RowEvents of an event solve, else None
+        self.dense = dense                                   # rowwise_dense.RowDenseStore of a dense solve, else None
         self.k = _native.get_kernels(p.device, p.dtype)
         dev, B = p.device, p.B
         f64 = dict(dtype=torch.float64, device=dev)
@@ -778,6 +804,8 @@ class HipRowKernels:
         self._control(0)
         if self.ev is not None:                              # between controller and commit: the commit overwrites y, f0
             self.ev.device_step(self, y, y1, f0, f1, mid, m.c_mid.coef, dts)
+        if self.dense is not None:                           # (the same place: the quartic of every accepted step is kept)
+            self.dense.device_step(self, y, y1, f0, f1, mid, m.c_mid.coef, dts)
         y_to, f0_to = (y, f0) if rec is None else (y.detach().clone(), f0.detach().clone())
         if self.row_map is None:
             k.row_dense_commit(sol, y_to, y1, f0_to, f1, mid, m.c_mid.coef, dts, self.st)

@@ -1,0 +1,359 @@
+"""`odeint_rowwise_dense`: a batch of independent IVPs whose solution can be evaluated AFTER the solve, per row.
+
+`odeint_rowwise` needs every output time up front; `odeint_dense` treats the batch as one system.  Here row r of
+`y0[B, *row_shape]` is integrated from `t0[r]` to `t1[r]` by the per-row controller of `odeint_rowwise` — the solve on the
+grid `[t0, t1]`: the same driver loop, launches and controller — and the quartic of EVERY accepted step of every row is
+kept.  The result evaluates `y_r(t)` at any time inside the row's interval with the bits `odeint_rowwise` gives for that
+time as an output time (an interior output time does not change a row's step sequence).
+
+Rows accept very different numbers of steps, so the store is ragged (`RowDenseStore`): during the solve the quartics go to
+CHUNKS of `cap` slots (`[5, cap, L]` plus per-slot metadata: original row, index of the step within its row, the step's
+ends), filled in arrival order; after it the chunks are packed once into `coeffs [5, n_seg, L]`, row r's segments
+contiguous and in step order at `offsets[r] : offsets[r + 1]`.  What a dense solve adds to a rowwise trial step sits
+between the controller and the commit, where the event hook sits and for the same reason (the commit overwrites y and
+f0): `tdeq_row_dense_slots` gives every accepted row a slot, `tdeq_row_event_fit_mapped` writes its quartic there.  The
+host keeps an upper bound of the slots taken (a step accepts at most `n_active` rows) and reads the chunk's true counter —
+one word — only when that bound leaves no room.  An evaluation is `tdeq_row_dense_search` (per query: the row's segment
+and the fraction of the step) followed by `tdeq_row_event_eval_mapped`.  CPU states run the same steps as torch / numpy
+ops.
+"""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+from . import _fallback, rowwise
+from ._native import device_guard
+from .rowwise import _Problem
+
+__all__ = ["odeint_rowwise_dense", "RowDenseOutput"]
+
+# the default chunk: CHUNK_ROWS_PER_ROW slots per row of the batch, at most CHUNK_BYTES of coefficients, never fewer than B
+CHUNK_ROWS_PER_ROW = 4
+CHUNK_BYTES = 256 << 20
+_NONE = 0x7FFFFFFF                                           # the search's status word: no query out of range
+
+
+def _row_times(name: str, v, B: int) -> torch.Tensor:
+    """`t0` / `t1` -> fp64 CPU tensor [B]: a number, a 0-dim tensor or a [B] tensor."""
+    if isinstance(v, torch.Tensor):
+        if v.requires_grad and torch.is_grad_enabled():
+            raise NotImplementedError(f"odeint_rowwise_dense does not propagate gradients ({name} requires grad); detach "
+                                      "it or call it under torch.no_grad()")
+        if v.is_complex() or v.dtype == torch.bool or v.dim() > 1 or (v.dim() == 1 and v.shape[0] != B):
+            raise ValueError(f"odeint_rowwise_dense: {name} must be a number, a 0-dim tensor or a real [B] = [{B}] tensor, "
+                             f"got a {v.dtype} tensor of shape {tuple(v.shape)}")
+        v = v.detach().to("cpu", torch.float64)
+        return v.expand(B).clone() if v.dim() == 0 else v.clone()
+    if isinstance(v, (int, float)) and not isinstance(v, bool):
+        return torch.full((B,), float(v), dtype=torch.float64)
+    raise ValueError(f"odeint_rowwise_dense: {name} must be a number, a 0-dim tensor or a [B] = [{B}] tensor, got "
+                     f"{type(v).__name__}")
+
+
+def _dense_grid(t0, t1, B: int) -> torch.Tensor:
+    """The [2, B] fp64 grid [t0, t1] of the solve."""
+    start, end = _row_times("t0", t0, B), _row_times("t1", t1, B)
+    if not (bool(torch.isfinite(start).all()) and bool(torch.isfinite(end).all())):
+        raise ValueError("odeint_rowwise_dense: t0 and t1 must be finite")
+    if not (bool((end > start).all()) or bool((end < start).all())):
+        raise ValueError("odeint_rowwise_dense: t1 must differ from t0 in every row, in the same direction for all rows")
+    return torch.stack([start, end])
+
+
+def _chunk_rows(options: dict, p_B: int, L: int, itemsize: int) -> int:
+    """The slots of a chunk: `options['dense_chunk_rows']` (>= 1) or the default policy, raised to at least B — a trial
+    step can accept every row, and `tdeq_row_event_fit_mapped` wants no fewer rows in `q` than in the batch."""
+    rows = options.pop("dense_chunk_rows", None)
+    if rows is None:
+        rows = min(CHUNK_ROWS_PER_ROW * p_B, CHUNK_BYTES // (5 * max(L, 1) * itemsize))
+    elif isinstance(rows, bool) or not isinstance(rows, int) or rows < 1:
+        raise ValueError(f"odeint_rowwise_dense: dense_chunk_rows must be an integer >= 1, got {rows!r}")
+    return max(int(rows), p_B)
+
+
+class _Chunk:
+    def __init__(self, cap: int, L: int, dtype, device):
+        self.q = torch.empty(5, cap, L, dtype=dtype, device=device)
+        self.row = torch.empty(cap, dtype=torch.int32, device=device)
+        self.ord = torch.empty(cap, dtype=torch.int32, device=device)
+        self.ta = torch.empty(cap, dtype=torch.float64, device=device)
+        self.tb = torch.empty(cap, dtype=torch.float64, device=device)
+        self.counter = torch.zeros(2, dtype=torch.int32, device=device)     # {used, overflow}
+
+
+class RowDenseStore:
+    """The quartics of one dense solve while it runs: chunks of `cap` slots, the hooks of both backends' `trial_step`
+    and the pack into the result."""
+
+    def __init__(self, p: _Problem, cap: int):
+        self.p, self.cap = p, cap
+        self.chunks = []                                     # in the order they were opened; the last one is being filled
+        self.bound = 0                                       # an upper bound of the slots taken in it
+        self.n_chunks = 0
+        self.slot = torch.empty(p.B, dtype=torch.int32, device=p.device)
+        self.mask = torch.empty(p.B, dtype=torch.int32, device=p.device)
+
+    def reserve(self, n_active: int) -> None:
+        """Before a trial step with `n_active` active rows (it accepts at most that many): make sure the current chunk has
+        room for them.  The chunk's counter is read only when the bound leaves none."""
+        if self.chunks and self.cap - self.bound < n_active:
+            self.bound = int(self.chunks[-1].counter[0])     # the one word
+        if not self.chunks or self.cap - self.bound < n_active:
+            p = self.p
+            self.chunks.append(_Chunk(self.cap, p.L, p.dtype, p.device))
+            self.n_chunks += 1
+            self.bound = 0
+        self.bound += n_active
+
+    # -- the hook of HipRowKernels.trial_step ----------------------------------------------------------------------------
+    def device_step(self, kern, y, y1, f0, f1, mid, coefs, dts) -> None:
+        ch, n = self.chunks[-1], kern.n
+        slot, mask = self.slot[:n], self.mask[:n]
+        kern.k.row_dense_slots(kern.st, kern.row_map, self.cap, ch.counter, ch.row, ch.ord, ch.ta, ch.tb, slot, mask)
+        kern.k.row_event_fit_mapped(ch.q, slot, mask, y, y1, f0, f1, mid, coefs, dts)
+
+    # -- the hook of HostRowKernels.trial_step ---------------------------------------------------------------------------
+    def host_step(self, kern, accepted, y, y1, f0, f1, ks, dts) -> None:
+        """The same as torch / numpy ops: slots in row order."""
+        rows = [r for r, _, _ in accepted]
+        if not rows:
+            return
+        ch = self.chunks[-1]
+        used = int(ch.counter[0])
+        ch.counter[0] = used + len(rows)
+        if used + len(rows) > self.cap:
+            ch.counter[1] = 1
+            return
+        at = slice(used, used + len(rows))
+        ch.q[:, at] = kern.step_quartic(torch.tensor(rows), y, y1, f0, f1, ks, dts)
+        ch.row[at] = torch.from_numpy((np.asarray(rows) if kern.row_map is None else kern.row_map[rows]).astype(np.int32))
+        ch.ord[at] = torch.from_numpy((kern.n_acc[rows] - 1).astype(np.int32))
+        ch.ta[at] = torch.from_numpy(kern.tprev[rows])
+        ch.tb[at] = torch.from_numpy(kern.t0[rows])
+
+    # -- after the loop --------------------------------------------------------------------------------------------------
+    def finalize(self, kern, n_acc: torch.Tensor):
+        """Pack the chunks: -> (offsets [B + 1] int64, seg_ta, seg_tb [n_seg] fp64 in solver time, coeffs [5, n_seg, L]),
+        all on the state's device.  `n_acc`: the accepted steps by original row (int64, CPU).  Every chunk is released
+        before the next one is packed."""
+        p, dev = self.p, self.p.device
+        offsets = torch.zeros(p.B + 1, dtype=torch.int64)
+        torch.cumsum(n_acc, 0, out=offsets[1:])
+        n_seg = int(offsets[-1])
+        if n_seg > _NONE:
+            raise RuntimeError(f"odeint_rowwise_dense: {n_seg} segments; the segment index is a 32-bit word")
+        offsets = offsets.to(dev)
+        coeffs = torch.empty(5, n_seg, p.L, dtype=p.dtype, device=dev)
+        seg_ta = torch.empty(n_seg, dtype=torch.float64, device=dev)
+        seg_tb = torch.empty(n_seg, dtype=torch.float64, device=dev)
+        packed = 0
+        self.chunks.reverse()
+        while self.chunks:
+            ch = self.chunks.pop()
+            used, overflow = ch.counter.tolist()
+            if overflow or used > self.cap:
+                raise RuntimeError(f"odeint_rowwise_dense: internal error: a chunk of {self.cap} slots overflowed ({used} taken)")
+            dest = offsets[ch.row[:used].to(torch.int64)] + ch.ord[:used].to(torch.int64)
+            if kern.name == "hip":
+                kern.k.row_dense_pack(coeffs, ch.q, dest, used)
+            else:
+                coeffs[:, dest] = ch.q[:, :used]
+            seg_ta[dest] = ch.ta[:used]
+            seg_tb[dest] = ch.tb[:used]
+            packed += used
+            del ch
+        if packed != n_seg:
+            raise RuntimeError(f"odeint_rowwise_dense: internal error: {packed} quartics kept for {n_seg} accepted steps")
+        return offsets, seg_ta, seg_tb, coeffs
+
+
+class RowDenseOutput:
+    """The piecewise quartic of a rowwise solve; `dense(t)` evaluates it.
+
+    Attributes (the wire format, all on the state's device): `t0`, `t1` `[B]` fp64 in true time; `offsets` `[B + 1]` int64;
+    `seg_start`, `seg_end` `[n_seg]` fp64 in true time, row r's segments — its accepted steps — contiguous and in step
+    order at `offsets[r] : offsets[r + 1]`; `coeffs` `[5, n_seg, L]` in the state's dtype, planes e, d, c, b, a of
+    `y(x) = e + d x + c x^2 + b x^3 + a x^4` with x the fraction of the step; `n_segments` = `n_seg` =
+    `n_accepted.sum()`.  Within a row `seg_start[s + 1] == seg_end[s]`, the first start is `t0[r]`, and the last end may lie
+    beyond `t1[r]`."""
+
+    def __init__(self, p: _Problem, kernels, offsets, seg_ta, seg_tb, coeffs):
+        self._sign, self._shape, self._k = p.sign, tuple(p.shape), kernels
+        self._t0, self._t1 = p.tgrid[0].to(p.device), p.tgrid[1].to(p.device)      # solver time, as the search takes them
+        self._ta, self._tb = seg_ta, seg_tb
+        self.offsets, self.coeffs = offsets, coeffs
+        self.n_segments = int(seg_ta.numel())
+        if p.sign == 1.0:
+            self.t0, self.t1, self.seg_start, self.seg_end = self._t0, self._t1, seg_ta, seg_tb
+        else:
+            self.t0, self.t1, self.seg_start, self.seg_end = (v * p.sign for v in (self._t0, self._t1, seg_ta, seg_tb))
+
+    def _queries(self, t):
+        """t -> (fp64 [Q, B] in solver time on the state's device, t was a single time)."""
+        B, dev = self._shape[0], self.coeffs.device
+        if isinstance(t, torch.Tensor):
+            if t.requires_grad and torch.is_grad_enabled():
+                raise NotImplementedError("odeint_rowwise_dense: the dense output does not propagate gradients (t requires "
+                                          "grad); detach it or evaluate under torch.no_grad()")
+            if t.is_complex() or t.dtype == torch.bool or t.dim() > 2 or (t.dim() == 2 and t.shape[1] != B):
+                raise ValueError(f"dense(t): t must be a number, a 0-dim tensor, [Q] or [Q, B] = [Q, {B}], got a {t.dtype} "
+                                 f"tensor of shape {tuple(t.shape)}")
+            tq = t.detach().to(device=dev, dtype=torch.float64)
+        elif isinstance(t, (int, float)) and not isinstance(t, bool):
+            tq = torch.tensor(float(t), dtype=torch.float64, device=dev)
+        else:
+            raise ValueError(f"dense(t): t must be a number or a tensor, got {type(t).__name__}")
+        single = tq.dim() == 0
+        if tq.dim() < 2:
+            tq = tq.reshape(-1, 1).expand(-1, B)
+        return (tq * self._sign).contiguous(), single
+
+    def _search_host(self, tq):
+        """The search as numpy ops -> (seg int32 [Q * B], x [Q * B] in the state's dtype, first out-of-range index)."""
+        Q, B = tq.shape
+        T = np.float32 if self.coeffs.dtype == torch.float32 else np.float64
+        q, off = tq.numpy(), self.offsets.numpy()
+        ta, tb, t0, t1 = self._ta.numpy(), self._tb.numpy(), self._t0.numpy(), self._t1.numpy()
+        ok = (q >= t0) & (q <= t1)                           # (a NaN fails both)
+        seg = np.empty((Q, B), dtype=np.int64)
+        for r in range(B):
+            ends = tb[off[r]:off[r + 1]]
+            # the first s with tq <= seg_tb[s]; the last segment ends at or beyond t1, so it is the answer if none before is
+            seg[:, r] = off[r] + np.minimum(np.searchsorted(ends, np.where(ok[:, r], q[:, r], t0[r]), side="left"),
+                                            len(ends) - 1)
+        seg = np.where(ok, seg, off[:-1][None, :])
+        with np.errstate(all="ignore"):
+            x = np.where(ok, ((q - ta[seg]) / (tb[seg] - ta[seg])).astype(T), T(np.nan))
+        bad = np.flatnonzero(~ok.reshape(-1))
+        first = int(bad[0]) if bad.size else _NONE
+        return torch.from_numpy(seg.reshape(-1).astype(np.int32)), torch.from_numpy(x.reshape(-1).astype(T)), first
+
+    def search(self, tq: torch.Tensor):
+        """The segment lookup alone, on the device kernels: `tq` fp64 `[Q, B]` in SOLVER time, contiguous, on the state's
+        device -> (seg int32 [Q * B], x [Q * B] in the state's dtype, status int32 [1]: the smallest out-of-range query
+        index, 0x7FFFFFFF for none — still on the device, not read)."""
+        dev = self.coeffs.device
+        n = tq.numel()
+        seg = torch.empty(n, dtype=torch.int32, device=dev)
+        x = torch.empty(n, dtype=self.coeffs.dtype, device=dev)
+        status = torch.full((1,), _NONE, dtype=torch.int32, device=dev)
+        self._k.row_dense_search(tq, self.offsets, self._ta, self._tb, self._t0, self._t1, seg, x, status)
+        return seg, x, status
+
+    def __call__(self, t, check: bool = True) -> torch.Tensor:
+        """Row r at `t`: a number or 0-dim tensor -> `[B, *row_shape]`; `[Q]` (the same times for every row) or `[Q, B]` (times
+        per row) -> `[Q, B, *row_shape]`.  A query outside `[t0[r], t1[r]]` (a NaN included) raises ValueError naming the
+        first such query — or, with `check=False`, gives an all-NaN row without any host read."""
+        tq, single = self._queries(t)
+        Q, B = tq.shape
+        L, dev = self.coeffs.shape[2], self.coeffs.device
+        out = torch.empty(Q * B, L, dtype=self.coeffs.dtype, device=dev)
+        first = _NONE
+        if Q > 0:
+            with torch.no_grad(), device_guard(dev):
+                if self._k is None:
+                    seg, x, first = self._search_host(tq)
+                    out.copy_(rowwise.HostRowKernels.eval_quartics(self.coeffs, seg, x))
+                else:
+                    if Q * B >= _NONE:
+                        raise ValueError(f"dense(t): {Q * B} queries in one call; the query index is a 32-bit word")
+                    seg, x, status = self.search(tq)
+                    self._k.row_event_eval_mapped(out, None, self.coeffs, seg, x)
+                    if check:
+                        first = int(status)
+        if check and first != _NONE:
+            j, r = divmod(first, B)
+            raise ValueError("dense(t): query {} of row {} (t = {}) is outside the row's interval [t0, t1] = [{}, {}]".format(
+                j, r, float(tq[j, r]) * self._sign, float(self.t0[r]), float(self.t1[r])))
+        out = out.view(Q, *self._shape)
+        return out[0] if single else out
+
+
+def odeint_rowwise_dense(func, y0, t0, t1, *, rtol=1e-7, atol=1e-9, method="dopri5", options=None, compact=None,
+                         return_stats=False):
+    """Integrate B independent IVPs `dy_r/dt = func(t, y)[r]` from `t0[r]` to `t1[r]` and return the solution as a function:
+    `dense = odeint_rowwise_dense(...)`, then `dense(t)` for times that need not be known before the solve.
+
+    `y0`, `func`, `rtol`, `atol` (numbers or `[B]` vectors), `method` (dopri5, bosh3, tsit5, fehlberg2, adaptive_heun,
+    dopri8), `options` and `compact` are those of `odeint_rowwise`; with `compact` set `func` is called as
+    `func(t_rows, y, rows)`.  `t0` and `t1` are each a number, a 0-dim tensor or a `[B]` tensor: finite, `t1 != t0` in every
+    row, in the same direction for all rows (`t1 < t0`: decreasing time), else ValueError.  One more option,
+    `dense_chunk_rows` (an integer >= 1, raised to at least B), sets the slots of a chunk of the store.
+
+    The solve is the `odeint_rowwise` solve on the grid `[t0, t1]`: the same step sequence, counters and errors per row (a
+    failing row — max_num_steps, dt underflow, a non-finite state — raises and names the original row).  The quartic of
+    every accepted step is kept (see `RowDenseOutput` for the layout).
+
+    `dense(t)`: `t` a number or 0-dim tensor -> `[B, *row_shape]`; `[Q]` (shared) or `[Q, B]` (per row) -> `[Q, B,
+    *row_shape]`, in any order, repeats allowed.  Row r's segments are its accepted steps `[ta_s, tb_s]` in solver time; a
+    query `tq` belongs to the FIRST segment with `tq <= tb_s` (a breakpoint belongs to the earlier step, x = 1; `tq == t0[r]`
+    to the first, x = 0), and the value is that segment's quartic at `x = T((tq - ta) / (tb - ta))`, the quotient formed in
+    fp64.  For a query inside `[t0[r], t1[r]]` that is bit for bit row r of `odeint_rowwise(func, y0, grid)` at that time,
+    for the per-row grid `[t0, the queries sorted, t1]`.  The valid interval is `[t0[r], t1[r]]` in the direction of the
+    solve, `t1[r]` included (the reference's `odeint_dense` closure raises IndexError at `t == t1`); anything else, a NaN
+    included, is out of range, also where the row's last step reaches beyond `t1[r]`: with `check=True` (default) a
+    ValueError that names the smallest flat query index `(j, r)` (one word read from the device), with `check=False` an
+    all-NaN row and no host read.
+
+    Returns `dense`; with `return_stats=True`, `(dense, stats)`: the stats of `odeint_rowwise` (`n_accepted`,
+    `n_rejected`, `nfe`; with `compact` also `row_evals`, `n_repacks`) plus `n_segments` and `n_chunks`.
+
+    Memory: the result holds `5 * L * n_seg` elements of the state's dtype (`n_seg = n_accepted.sum()`) and two fp64 words
+    per segment.  During the solve the quartics sit in chunks of `cap` slots (`5 * L * cap` elements each, by default
+    `cap = max(B, min(4 B, 256 MiB of coefficients))`): every chunk but the last is full to within one trial step's accepted
+    rows.  Every chunk lives until the solve ends; the pack then allocates the result and releases the chunks one by one, so
+    the PEAK is the result plus all chunks — about twice the result.
+
+    Out of scope (raises or is not offered): gradients through the solve or through `dense(t)` (with grad mode on and
+    `y0`, `t0`, `t1`, a query tensor or a parameter of `func` requiring grad: NotImplementedError; there is no
+    `differentiable` argument), events combined with dense output, 16-bit / complex / tuple states (ValueError), captured
+    (hipGraph) steps, extrapolation outside `[t0[r], t1[r]]`, and the per-row adjoint this record is meant to serve.
+    `odeint_dense` is unchanged.
+    """
+    options = dict(options or {})
+    is_batch = isinstance(y0, torch.Tensor) and y0.dim() >= 1 and y0.shape[0] >= 1
+    if is_batch:
+        t = _dense_grid(t0, t1, y0.shape[0])
+        cap = _chunk_rows(options, y0.shape[0], int(np.prod(y0.shape[1:])), y0.element_size())
+        if torch.is_grad_enabled() and (y0.requires_grad or rowwise._func_parameters_require_grad(func)):
+            raise NotImplementedError("odeint_rowwise_dense does not propagate gradients (y0 or a parameter of func requires "
+                                      "grad); call it under torch.no_grad()")
+    else:
+        t, cap = torch.zeros(2, dtype=torch.float64), 1      # (_Problem refuses this y0)
+        options.pop("dense_chunk_rows", None)
+    p = _Problem(func, y0, t, rtol, atol, method, options, None, False, compact)
+    # the first evaluation in the caller's grad mode, as in odeint_rowwise: a func whose output requires grad is refused
+    with device_guard(p.device):
+        f0 = p.call((p.tgrid[0] * p.sign).to(p.dtype).to(p.device), p.y0).clone()
+    with torch.no_grad(), device_guard(p.device):
+        store = RowDenseStore(p, cap)
+        if p.device.type == "cuda":
+            kern = rowwise.HipRowKernels(p, None, store)
+        else:
+            _fallback.warn_once(f"the state lives on '{p.device}'")
+            kern = rowwise.HostRowKernels(p, None, store)
+        sol = torch.empty(2, p.B, p.L, dtype=p.dtype, device=p.device)      # (the commit writes y(t1) here; not returned)
+        sol[0].copy_(p.y0)
+        y = p.y0.clone()                                     # private: the commit writes y <- y1, f0 <- f1 in place
+        kern.initial_step(y, f0)
+        while True:
+            n_active, failure = kern.poll()
+            if failure is not None:
+                p.raise_row_error(failure, y)
+            if n_active == 0:
+                break
+            if p.compact is not None and n_active < y.shape[0] and n_active <= p.compact * y.shape[0]:
+                y, f0 = kern.repack(y, f0, n_active)
+            store.reserve(n_active)
+            y, f0 = kern.trial_step(y, f0, sol)
+        n_acc, n_rej = kern.counts()
+        n_acc = n_acc.to(torch.int64)
+        dense = RowDenseOutput(p, kern.k if kern.name == "hip" else None, *store.finalize(kern, n_acc))
+    if not return_stats:
+        return dense
+    stats = {"n_accepted": n_acc, "n_rejected": n_rej.to(torch.int64), "nfe": p.nfe}
+    if p.compact is not None:
+        stats["row_evals"], stats["n_repacks"] = p.row_evals, p.n_repacks
+    stats["n_segments"], stats["n_chunks"] = dense.n_segments, store.n_chunks
+    return dense, stats

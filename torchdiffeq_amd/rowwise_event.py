@@ -154,7 +154,6 @@ class RowEvents:
     # -- the hook of HostRowKernels.trial_step ---------------------------------------------------------------------------
     def host_step(self, kern, accepted, y, y1, f0, f1, ks, dts) -> None:
         """The same decisions as torch / numpy ops; the row leaves the active ones after the controller's `prepare`."""
-        p, m = self.p, self.p.method
         g1 = self.call(self.step_times(torch.from_numpy(kern.t0.copy())), y1)
         s1, s0 = _sign(g1).numpy(), self.sign0.numpy()
         fired, now, lo, hi = self.fired.numpy(), self.fired_now.numpy(), self.lo.numpy(), self.hi.numpy()
@@ -165,19 +164,9 @@ class RowEvents:
         now[rows] = 1
         fired[rows] = 1
         lo[rows], hi[rows] = kern.tprev[rows], kern.t0[rows]
-        # the quartic of the step: the expressions of HostRowKernels._dense_commit
         idx = torch.tensor(rows)
-        d = dts[idx]
-        y0r, y1r, f0r, f1r = y[idx], y1[idx], f0[idx], f1[idx]
-        kr = [k[idx] if k is not None else None for k in ks]
-        ymid = y0r + kern._sum_terms(kr, m.c_mid, d)
-        two_dt = torch.tensor(2.0, dtype=p.dtype) * d
-        qa = ((f1r - f0r) * two_dt - (y1r + y0r) * 8.0) + ymid * 16.0
-        qb = (((f0r * 5.0 - f1r * 3.0) * d + y0r * 18.0) + y1r * 14.0) - ymid * 32.0
-        qc = (((f1r - f0r * 4.0) * d - y0r * 11.0) - y1r * 5.0) + ymid * 16.0
-        qd = f0r * d
         at = idx if kern.row_map is None else torch.from_numpy(kern.row_map[rows])
-        self.coef[:, at] = torch.stack([y0r, qd, qc, qb, qa])
+        self.coef[:, at] = kern.step_quartic(idx, y, y1, f0, f1, ks, dts)
 
 
 def _bisection_rounds(width: torch.Tensor, has_q: torch.Tensor) -> np.ndarray:
