@@ -11,17 +11,32 @@ On a ROCm device every state-sized operation is a HIP kernel of csrc/tdeq_kernel
 controller runs on the device (the host reads two words per trial step); CPU states run the same row operations as
 torch ops (`HostRowKernels`, one `HostPathWarning`).
 
-Three things are kept apart.  WHAT IS LAUNCHED in a trial step is `HipRowKernels.trial_step`: one interpreter of the
-tableau's launch plan (`tableaus.launch_plan`: the carry plan of dopri5 / dopri8 / tsit5, row by row for the others),
-then the error norm, the controller and the dense-output commit.  The TWO BACKENDS offer the driver the same methods —
-`initial_step`, `trial_step`, `poll`, `counts`, for a recorded solve `begin_recording` / `recorded_solution`, and with
-`compact=` set `repack` (the finished rows leave the batch and the solve carries on with the rest, `_compact_fraction`)
-— and `odeint_rowwise` calls nothing else; an event solve (`odeint_rowwise_event`, rowwise_event.py) hands both
-backends a `RowEvents` object, whose hook runs between the controller and the commit of `trial_step`, and adds
-`deactivate_rows` / `event_eval` / `event_eval_mapped`; a dense solve (`odeint_rowwise_dense`, rowwise_dense.py) hands them
-a `RowDenseStore`, whose hook runs in the same place.  WHAT IS RECORDED for `differentiable=True` lives in
-rowwise_autodiff.py: the device backend hands its finished launches to a `RowRecorder` (None in a plain solve), the
-host backend records plain torch ops; `_Problem.grad_mode` is the one place that turns grad mode on for a recorded solve.
+The structure.  ONE DRIVER, `_solve`, serves the three entry points (`odeint_rowwise` here, `odeint_rowwise_event` in
+rowwise_event.py, `odeint_rowwise_dense` in rowwise_dense.py): it chooses the backend, runs the initial step and then the
+loop poll -> row error -> repack rule (`compact=`, `_compact_fraction`) -> trial step, and reads the counters; `_stats`
+assembles what all three report.  An entry point validates its arguments (`_Problem`; `_row_times` / `_row_grid` for a
+solve between two times per row), evaluates `func` once in the caller's grad mode (`_Problem.first_call`) and turns what
+the driver leaves behind into its result.
+
+The TWO BACKENDS, `HipRowKernels` and `HostRowKernels`, offer the driver the same methods — `initial_step`, `trial_step`,
+`poll`, `counts`, `repack`, `deactivate_rows`, for a recorded solve `begin_recording` / `recorded_solution` — and the
+entry points the operations on kept quartics, `event_eval` / `event_eval_mapped` / `pack_quartics`.  WHAT IS LAUNCHED in a
+trial step is `HipRowKernels.trial_step`: one interpreter of the tableau's launch plan (`tableaus.launch_plan`: the carry
+plan of dopri5 / dopri8 / tsit5, row by row for the others), then the error norm, the controller, the hook and the
+dense-output commit.
+
+ONE STEP HOOK (None in a plain solve; one slot, hooks do not combine) is what an event or a dense solve adds to a step.  The
+backends and the driver use exactly these members of it:
+  * `before_step(n_active)`: the driver, before every trial step;
+  * `device_step(kern, y, y1, f0, f1, mid, coefs, dts)` / `host_step(kern, accepted, y, y1, f0, f1, ks, dts)`: the backend,
+    between the controller and the commit (the commit overwrites y and f0);
+  * `keep_rows(keep)`: the backend, at a repack, before `_Problem.keep_rows`;
+  * `stopped_now`: the rows the hook took out of the active ones in this trial step (int32 [n]), or None for a hook that
+    stops none — `poll` and the end of the host trial step read it.
+
+WHAT IS RECORDED for `differentiable=True` lives in rowwise_autodiff.py: the device backend hands its finished launches
+to a `RowRecorder` (None in a plain solve), the host backend records plain torch ops; `_Problem.grad_mode` is the one
+place that turns grad mode on for a recorded solve.
 """
 from __future__ import annotations
 
@@ -104,6 +119,33 @@ def _tolerance(name: str, tol, B: int):
                          f"got shape {tuple(shape)}; a vector of another length and tolerances per element of a row "
                          "([B, *row_shape], [*row_shape]) are not supported")
     return None, vec
+
+
+def _batch_rows(y0):
+    """B of a y0 that has a batch, else None: the entry points that build their grid from B pass `t=None` then, and
+    `_Problem` refuses that y0 with its own message before it looks at t."""
+    return y0.shape[0] if isinstance(y0, torch.Tensor) and y0.dim() >= 1 and y0.shape[0] >= 1 else None
+
+
+def _row_times(fn: str, name: str, v, B: int) -> torch.Tensor:
+    """A start or end time of `fn` -> fp64 CPU tensor [B]: a number, a 0-dim tensor or a [B] tensor."""
+    if isinstance(v, torch.Tensor):
+        if v.is_complex() or v.dtype == torch.bool or v.dim() > 1 or (v.dim() == 1 and v.shape[0] != B):
+            raise ValueError(f"{fn}: {name} must be a number, a 0-dim tensor or a real [B] = [{B}] tensor, "
+                             f"got a {v.dtype} tensor of shape {tuple(v.shape)}")
+        v = v.detach().to("cpu", torch.float64)
+        return v.expand(B).clone() if v.dim() == 0 else v.clone()
+    if isinstance(v, (int, float)) and not isinstance(v, bool):
+        return torch.full((B,), float(v), dtype=torch.float64)
+    raise ValueError(f"{fn}: {name} must be a number, a 0-dim tensor or a [B] = [{B}] tensor, got "
+                     f"{type(v).__name__}")
+
+
+def _row_grid(fn: str, start: torch.Tensor, name: str, end: torch.Tensor) -> torch.Tensor:
+    """The [2, B] fp64 grid [t0, end] of a solve between two times per row (`name`: what `fn` calls the end)."""
+    if not (bool((end > start).all()) or bool((end < start).all())):
+        raise ValueError(f"{fn}: {name} must differ from t0 in every row, in the same direction for all rows")
+    return torch.stack([start, end])
 
 
 def _func_parameters_require_grad(func) -> bool:
@@ -260,6 +302,12 @@ class _Problem:
             f = f.to(self.dtype)
         return f if f.is_contiguous() and f.data_ptr() % 16 == 0 else f.contiguous(memory_format=torch.contiguous_format).clone()
 
+    def first_call(self, y: torch.Tensor) -> torch.Tensor:
+        """func at t0, for the entry points to call in the CALLER's grad mode: a func whose output depends on parameters
+        that require grad (closures included) is refused here, never silently detached (unless the solve is recorded)."""
+        with device_guard(self.device):
+            return self.call((self.tgrid[0] * self.sign).to(self.dtype).to(self.device), y).clone()
+
     def raise_row_error(self, failure, y) -> None:
         r, code, since, dt, at = failure                     # r: the original row; at: where it sits in y
         if code == 2:
@@ -283,16 +331,20 @@ def _row_sum(x: torch.Tensor) -> torch.Tensor:
     return x[:, 0]
 
 
+def _stopped_now(hook):
+    """The rows the hook took out of the active ones in the last trial step (int32 [n], nonzero: stopped), or None."""
+    return None if hook is None else hook.stopped_now
+
+
 class HostRowKernels:
     """The row operations of `odeint_rowwise` as torch ops (CPU states): the per-row controller runs as host scalar
     arithmetic, row by row, with the decisions of the device controller (tdeq_kernels_rowwise.hpp)."""
 
-    name = "host"
+    k = None                                                 # no kernels object: every operation is a torch expression
 
-    def __init__(self, p: _Problem, ev=None, dense=None):
+    def __init__(self, p: _Problem, hook=None):
         self.p = p
-        self.ev = ev                                         # rowwise_event.RowEvents of an event solve, else None
-        self.dense = dense                                   # rowwise_dense.RowDenseStore of a dense solve, else None
+        self.hook = hook                                     # the step hook of an event or dense solve, else None
         T = p.np_dtype
         self.T = T
         B = p.B
@@ -371,8 +423,9 @@ class HostRowKernels:
         return sol
 
     def poll(self):
-        # (an event solve: a row that fired in this trial step was prepared before it left, and its error wins)
-        live = self.active if self.ev is None else self.active | self.ev.fired_now.numpy().astype(bool)
+        # (a row the hook stopped in this trial step was prepared before it left, and its error wins)
+        stopped = _stopped_now(self.hook)
+        live = self.active if stopped is None else self.active | stopped.numpy().astype(bool)
         r = next((r for r in range(self.n) if live[r] and self.code[r] != 0), None)
         if r is None:
             return int(self.active.sum()), None
@@ -401,8 +454,8 @@ class HostRowKernels:
         self.tg = self.tg[:, keep]
         self.row_map = self.row_map[keep]
         idx = torch.from_numpy(keep)
-        if self.ev is not None:
-            self.ev.keep_rows(idx)
+        if self.hook is not None:
+            self.hook.keep_rows(idx)
         if self.s_shadow is not None:
             self.s_shadow = self.s_shadow[idx]
         if self.anchor is not None:
@@ -513,10 +566,8 @@ class HostRowKernels:
                 else:
                     self.n_rej[r] += 1
                 self.dt[r] = dt_next
-        if self.ev is not None:                              # between controller and commit: the commit overwrites y, f0
-            self.ev.host_step(self, accepted, y, y1, f0, f1, ks, dts)
-        if self.dense is not None:                           # (the same place: the quartic of every accepted step is kept)
-            self.dense.host_step(self, accepted, y, y1, f0, f1, ks, dts)
+        if self.hook is not None:                            # between controller and commit: the commit overwrites y, f0
+            self.hook.host_step(self, accepted, y, y1, f0, f1, ks, dts)
         if accepted:
             y, f0 = self._dense_commit(accepted, y, y1, f0, f1, ks, dts, sol, shadow, anchor)
         if shadow is not None and shadow.requires_grad:
@@ -526,22 +577,23 @@ class HostRowKernels:
         for r in range(self.n):
             if self.active[r]:
                 self.prepare(r)
-        if self.ev is not None:
-            self.active[self.ev.fired_now.numpy().astype(bool)] = False
+        stopped = _stopped_now(self.hook)
+        if stopped is not None:
+            self.active[stopped.numpy().astype(bool)] = False
         return y, f0
 
     def deactivate_rows(self, mask: torch.Tensor) -> None:
         """Before the initial step: the rows of `mask` (bool [B]) never start."""
         self.active[mask.numpy()] = False
 
-    def event_eval(self, out, x, mask) -> None:
-        """out[r, :] = the kept quartic of row r at x[r] for the rows with mask[r] (the arithmetic of `_dense_commit`)."""
+    def event_eval(self, out, q, x, mask) -> None:
+        """out[r, :] = the quartic q[:, r] of a [5, B, L] tensor at x[r] for the rows with mask[r]."""
         idx = torch.nonzero(mask).view(-1)
-        self.event_eval_mapped(out, idx, idx, x[idx])
+        self.event_eval_mapped(out, idx, q, idx, x[idx])
 
-    def step_quartic(self, idx, y, y1, f0, f1, ks, dts) -> torch.Tensor:
-        """The quartic of the trial step just taken for the rows `idx` (int64 positions in the batch) -> [5, n, L], planes
-        e, d, c, b, a: the expressions of `_dense_commit`."""
+    def _quartic_planes(self, idx, y, y1, f0, f1, ks, dts):
+        """The quartic of the trial step just taken for the rows `idx` (int64 positions in the batch): its planes
+        (e, d, c, b, a), [n, L] each — the one place the host states the coefficients (`tdeq_row_event_fit` on the device)."""
         p, m = self.p, self.p.method
         d = dts[idx]
         y0r, y1r, f0r, f1r = y[idx], y1[idx], f0[idx], f1[idx]
@@ -552,11 +604,15 @@ class HostRowKernels:
         qb = (((f0r * 5.0 - f1r * 3.0) * d + y0r * 18.0) + y1r * 14.0) - ymid * 32.0
         qc = (((f1r - f0r * 4.0) * d - y0r * 11.0) - y1r * 5.0) + ymid * 16.0
         qd = f0r * d
-        return torch.stack([y0r, qd, qc, qb, qa])
+        return y0r, qd, qc, qb, qa
+
+    def step_quartic(self, idx, y, y1, f0, f1, ks, dts) -> torch.Tensor:
+        """`_quartic_planes` as one tensor [5, n, L], as the hooks keep it."""
+        return torch.stack(self._quartic_planes(idx, y, y1, f0, f1, ks, dts))
 
     @staticmethod
     def eval_quartics(q, src, x) -> torch.Tensor:
-        """The quartics q[:, src[i], :] of a [5, rows, L] tensor at x[i] -> [n, L] (the arithmetic of `_dense_commit`)."""
+        """The quartics q[:, src[i], :] of a [5, rows, L] tensor at x[i] -> [n, L]."""
         e, d, c, b, a = q[:, src.to(torch.int64)].unbind(0)
         x1 = x[:, None]
         x2 = x1 * x1
@@ -568,31 +624,27 @@ class HostRowKernels:
         total = total + a * x4
         return total
 
-    def event_eval_mapped(self, out, dst, src, x) -> None:
-        """out[dst[i] (None: i), :] = the kept quartic of ORIGINAL row src[i] at x[i], for the index lists `dst`, `src`."""
+    def event_eval_mapped(self, out, dst, q, src, x) -> None:
+        """out[dst[i] (None: i), :] = the quartic q[:, src[i]] at x[i], for the index lists `dst`, `src`."""
         if src.numel() == 0:
             return
-        total = self.eval_quartics(self.ev.coef, src, x)
+        total = self.eval_quartics(q, src, x)
         if dst is None:
             out.copy_(total)
         else:
             out[dst.to(torch.int64)] = total
 
+    def pack_quartics(self, coeffs, q, dest, used: int) -> None:
+        """coeffs[:, dest[i]] = q[:, i] for the first `used` slots of a chunk of a dense solve."""
+        coeffs[:, dest] = q[:, :used]
+
     def _dense_commit(self, accepted, y, y1, f0, f1, ks, dts, sol, shadow=None, anchor=None):
-        p, m, T = self.p, self.p.method, self.T
+        p, T = self.p, self.T
         rows = torch.tensor([r for r, _, _ in accepted])
         with_out = [(i, r, lo, hi) for i, (r, lo, hi) in enumerate(accepted) if hi > lo]
         if with_out:
             idx = torch.tensor([r for _, r, _, _ in with_out])
-            d = dts[idx]
-            y0r, y1r, f0r, f1r = y[idx], y1[idx], f0[idx], f1[idx]
-            kr = [k[idx] if k is not None else None for k in ks]
-            ymid = y0r + self._sum_terms(kr, m.c_mid, d)
-            two_dt = torch.tensor(2.0, dtype=p.dtype) * d
-            qa = ((f1r - f0r) * two_dt - (y1r + y0r) * 8.0) + ymid * 16.0
-            qb = (((f0r * 5.0 - f1r * 3.0) * d + y0r * 18.0) + y1r * 14.0) - ymid * 32.0
-            qc = (((f1r - f0r * 4.0) * d - y0r * 11.0) - y1r * 5.0) + ymid * 16.0
-            qd = f0r * d
+            y0r, qd, qc, qb, qa = self._quartic_planes(idx, y, y1, f0, f1, ks, dts)
             for n, (_, r, lo, hi) in enumerate(with_out):
                 ta, tb = self.tprev[r], self.t0[r]
                 for j in range(lo, hi):
@@ -611,6 +663,7 @@ class HostRowKernels:
                         xt = rad.stitch_rows(val(x), moved * (-1.0 / (tb - ta)))
                         xs = (xt, rad.stitch_rows(val(x2), xt * xt), rad.stitch_rows(val(x3), xt * xt * xt),
                               rad.stitch_rows(val(x4), xt * xt * xt * xt))
+                    # (not `eval_quartics`: the powers of x are host scalars here, graph scalars in a recorded solve)
                     total = y0r[n] + qd[n] * xs[0]
                     total = total + qc[n] * xs[1]
                     total = total + qb[n] * xs[2]
@@ -628,12 +681,9 @@ class HostRowKernels:
 class HipRowKernels:
     """The row operations of `odeint_rowwise` on the HIP kernels (csrc/tdeq_kernels_rowwise.hpp)."""
 
-    name = "hip"
-
-    def __init__(self, p: _Problem, ev=None, dense=None):
+    def __init__(self, p: _Problem, hook=None):
         self.p = p
-        self.ev = ev                                         # rowwise_event.RowEvents of an event solve, else None
-        self.dense = dense                                   # rowwise_dense.RowDenseStore of a dense solve, else None
+        self.hook = hook                                     # the step hook of an event or dense solve, else None
         self.k = _native.get_kernels(p.device, p.dtype)
         dev, B = p.device, p.B
         f64 = dict(dtype=torch.float64, device=dev)
@@ -684,11 +734,11 @@ class HipRowKernels:
 
     def poll(self):
         n_active, r = self.status.tolist()                   # the two words the host reads per trial step
-        # (an event solve: a row the controller found in error may have fired and left in the same trial step — its error
-        #  wins.  Safe because every control launch (`tdeq_row_control`) first resets both words to {0, no error row}, so
-        #  status[1] can only name a row of THIS launch, never a stale one; pinned by
+        # (a hook that stops rows: a row the controller found in error may have fired and left in the same trial step — its
+        #  error wins.  Safe because every control launch (`tdeq_row_control`) first resets both words to {0, no error row},
+        #  so status[1] can only name a row of THIS launch, never a stale one; pinned by
         #  tests/test_rowwise_event.py::test_max_num_steps_names_the_original_row)
-        if r == _NO_ERROR_ROW or (n_active == 0 and self.ev is None):
+        if r == _NO_ERROR_ROW or (n_active == 0 and _stopped_now(self.hook) is None):
             return n_active, None
         row = r if self.row_map is None else int(self.row_map[r])
         return n_active, (row, int(self.code[r]), int(self.since[r]), float(self.dt[r]), r)
@@ -728,8 +778,8 @@ class HipRowKernels:
         st.tgrid = self.tg.data_ptr()
         self.dts, self.times = self.dts.index_select(0, keep), self.times.index_select(1, keep)
         st.n_rows = self.n = n_keep
-        if self.ev is not None:
-            self.ev.keep_rows(keep)
+        if self.hook is not None:
+            self.hook.keep_rows(keep)
         p.keep_rows(keep)
         self.row_map = p.rows.to(device=self.active.device, dtype=torch.int32)
         return y_new, f_new
@@ -802,10 +852,8 @@ class HipRowKernels:
         # inputs stay alive for the backward)
         t_start = None if rec is None else self.t0.clone()
         self._control(0)
-        if self.ev is not None:                              # between controller and commit: the commit overwrites y, f0
-            self.ev.device_step(self, y, y1, f0, f1, mid, m.c_mid.coef, dts)
-        if self.dense is not None:                           # (the same place: the quartic of every accepted step is kept)
-            self.dense.device_step(self, y, y1, f0, f1, mid, m.c_mid.coef, dts)
+        if self.hook is not None:                            # between controller and commit: the commit overwrites y, f0
+            self.hook.device_step(self, y, y1, f0, f1, mid, m.c_mid.coef, dts)
         y_to, f0_to = (y, f0) if rec is None else (y.detach().clone(), f0.detach().clone())
         if self.row_map is None:
             k.row_dense_commit(sol, y_to, y1, f0_to, f1, mid, m.c_mid.coef, dts, self.st)
@@ -819,13 +867,63 @@ class HipRowKernels:
         """Before the initial step: the rows of `mask` (bool [B]) never start."""
         self.active.masked_fill_(mask, 0)
 
-    def event_eval(self, out, x, mask) -> None:
-        """out[r, :] = the kept quartic of row r at x[r] for the rows with mask[r] (int32 [B])."""
-        self.k.row_event_eval(out, self.ev.coef, x, mask)
+    def event_eval(self, out, q, x, mask) -> None:
+        """out[r, :] = the quartic q[:, r] of a [5, B, L] tensor at x[r] for the rows with mask[r] (int32 [B])."""
+        self.k.row_event_eval(out, q, x, mask)
 
-    def event_eval_mapped(self, out, dst, src, x) -> None:
-        """out[dst[i] (None: i), :] = the kept quartic of ORIGINAL row src[i] at x[i]; `dst`, `src` int32 [n] index lists."""
-        self.k.row_event_eval_mapped(out, dst, self.ev.coef, src, x)
+    def event_eval_mapped(self, out, dst, q, src, x) -> None:
+        """out[dst[i] (None: i), :] = the quartic q[:, src[i]] at x[i]; `dst`, `src` int32 [n] index lists."""
+        self.k.row_event_eval_mapped(out, dst, q, src, x)
+
+    def pack_quartics(self, coeffs, q, dest, used: int) -> None:
+        """coeffs[:, dest[i]] = q[:, i] for the first `used` slots of a chunk of a dense solve."""
+        self.k.row_dense_pack(coeffs, q, dest, used)
+
+
+def _solve(p: _Problem, y_start, f0, sol, hook=None, never_start=None):
+    """The one driver of the rowwise family, called under no_grad: chooses the backend, integrates every row to its last
+    output time — or until `hook` stops it — and returns (the backend, n_accepted, n_rejected by original row).
+
+    `y_start` [B, L]: the state at t0 (copied, unless the solve is recorded); `f0`: func there (`_Problem.first_call`), or
+    None for a grid of one time — the backend is still chosen then, nothing is integrated and the counters are None.
+    `never_start`: a bool [B] mask of rows that are not integrated at all."""
+    if p.device.type == "cuda":
+        kern = HipRowKernels(p, hook)
+    else:
+        _fallback.warn_once(f"the state lives on '{p.device}'")
+        kern = HostRowKernels(p, hook)
+    if f0 is None:
+        return kern, None, None
+    if never_start is not None:
+        kern.deactivate_rows(never_start)
+    # private state buffers: the dense-output launch commits y <- y1, f0 <- f1 in place
+    y = y_start if p.record else y_start.clone()
+    with p.grad_mode():
+        if p.record:
+            kern.begin_recording(sol, y)
+        kern.initial_step(y, f0)
+        while True:
+            n_active, failure = kern.poll()
+            if failure is not None:
+                p.raise_row_error(failure, y)
+            if n_active == 0:
+                break
+            if p.compact is not None and n_active < y.shape[0] and n_active <= p.compact * y.shape[0]:
+                y, f0 = kern.repack(y, f0, n_active)
+            if hook is not None:
+                hook.before_step(n_active)
+            y, f0 = kern.trial_step(y, f0, sol)
+    return (kern, *kern.counts())
+
+
+def _stats(p: _Problem, n_acc, n_rej) -> dict:
+    """What every rowwise solve reports (`n_acc`, `n_rej` None: no step was taken)."""
+    if n_acc is None:
+        n_acc, n_rej = torch.zeros(p.B, dtype=torch.int64), torch.zeros(p.B, dtype=torch.int64)
+    stats = {"n_accepted": n_acc.to(torch.int64), "n_rejected": n_rej.to(torch.int64), "nfe": p.nfe}
+    if p.compact is not None:
+        stats["row_evals"], stats["n_repacks"] = p.row_evals, p.n_repacks
+    return stats
 
 
 def odeint_rowwise(func, y0, t, *, rtol=1e-7, atol=1e-9, method="dopri5", options=None, return_stats=False,
@@ -885,54 +983,19 @@ def odeint_rowwise(func, y0, t, *, rtol=1e-7, atol=1e-9, method="dopri5", option
     """
     p = _Problem(func, y0, t, rtol, atol, method, options, event_fn, differentiable, compact)
     n_t = p.tgrid.shape[0]
-    f0 = None
     y_start = p.y0
     if p.record:
         # a private, aligned copy that carries y0's graph (the recorded solve never writes into a state tensor)
         y_start = p.y0_graph.clone(memory_format=torch.contiguous_format)
-    if n_t > 1:
-        # the first evaluation in the caller's grad mode: a func whose output depends on parameters that require grad
-        # (closures included) is refused here, never silently detached (unless the solve is recorded)
-        with device_guard(p.device):
-            f0 = p.call((p.tgrid[0] * p.sign).to(p.dtype).to(p.device), y_start).clone()
+    f0 = p.first_call(y_start) if n_t > 1 else None
     with torch.no_grad(), device_guard(p.device):
         sol = torch.empty(n_t, p.B, p.L, dtype=p.dtype, device=p.device)
         sol[0].copy_(p.y0)
-        if p.device.type == "cuda":
-            kern = HipRowKernels(p)
-        else:
-            _fallback.warn_once(f"the state lives on '{p.device}'")
-            kern = HostRowKernels(p)
-        n_acc = n_rej = None
-        if n_t > 1:
-            # private state buffers: the dense-output launch commits y <- y1, f0 <- f1 in place
-            y = y_start if p.record else p.y0.clone()
-            with p.grad_mode():
-                if p.record:
-                    kern.begin_recording(sol, y)
-                kern.initial_step(y, f0)
-                while True:
-                    n_active, failure = kern.poll()
-                    if failure is not None:
-                        p.raise_row_error(failure, y)
-                    if n_active == 0:
-                        break
-                    if p.compact is not None and n_active < y.shape[0] and n_active <= p.compact * y.shape[0]:
-                        y, f0 = kern.repack(y, f0, n_active)
-                    y, f0 = kern.trial_step(y, f0, sol)
-            n_acc, n_rej = kern.counts()
+        kern, n_acc, n_rej = _solve(p, y_start, f0, sol)
         if p.record:
             with torch.enable_grad():
                 sol = kern.recorded_solution(sol) if n_t > 1 else y_start[None]
                 solution = rad.first_order_only(sol.view(n_t, *p.shape))
         else:
             solution = sol.view(n_t, *p.shape)
-    if not return_stats:
-        return solution
-    if n_acc is None:
-        n_acc = torch.zeros(p.B, dtype=torch.int64)
-        n_rej = torch.zeros(p.B, dtype=torch.int64)
-    stats = {"n_accepted": n_acc.to(torch.int64), "n_rejected": n_rej.to(torch.int64), "nfe": p.nfe}
-    if p.compact is not None:
-        stats["row_evals"], stats["n_repacks"] = p.row_evals, p.n_repacks
-    return solution, stats
+    return (solution, _stats(p, n_acc, n_rej)) if return_stats else solution

@@ -2,16 +2,16 @@
 
 `odeint_rowwise` needs every output time up front; `odeint_dense` treats the batch as one system.  Here row r of
 `y0[B, *row_shape]` is integrated from `t0[r]` to `t1[r]` by the per-row controller of `odeint_rowwise` — the solve on the
-grid `[t0, t1]`: the same driver loop, launches and controller — and the quartic of EVERY accepted step of every row is
-kept.  The result evaluates `y_r(t)` at any time inside the row's interval with the bits `odeint_rowwise` gives for that
-time as an output time (an interior output time does not change a row's step sequence).
+grid `[t0, t1]`: the same driver (`rowwise._solve`), launches and controller — and the quartic of EVERY accepted step of
+every row is kept.  The result evaluates `y_r(t)` at any time inside the row's interval with the bits `odeint_rowwise`
+gives for that time as an output time (an interior output time does not change a row's step sequence).
 
 Rows accept very different numbers of steps, so the store is ragged (`RowDenseStore`): during the solve the quartics go to
 CHUNKS of `cap` slots (`[5, cap, L]` plus per-slot metadata: original row, index of the step within its row, the step's
 ends), filled in arrival order; after it the chunks are packed once into `coeffs [5, n_seg, L]`, row r's segments
-contiguous and in step order at `offsets[r] : offsets[r + 1]`.  What a dense solve adds to a rowwise trial step sits
-between the controller and the commit, where the event hook sits and for the same reason (the commit overwrites y and
-f0): `tdeq_row_dense_slots` gives every accepted row a slot, `tdeq_row_event_fit_mapped` writes its quartic there.  The
+contiguous and in step order at `offsets[r] : offsets[r + 1]`.  The store is the solve's step hook (rowwise.py): what it
+adds to a trial step sits between the controller and the commit, because the commit overwrites y and f0:
+`tdeq_row_dense_slots` gives every accepted row a slot, `tdeq_row_event_fit_mapped` writes its quartic there.  The
 host keeps an upper bound of the slots taken (a step accepts at most `n_active` rows) and reads the chunk's true counter —
 one word — only when that bound leaves no room.  An evaluation is `tdeq_row_dense_search` (per query: the row's segment
 and the fraction of the step) followed by `tdeq_row_event_eval_mapped`.  CPU states run the same steps as torch / numpy
@@ -22,7 +22,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from . import _fallback, rowwise
+from . import rowwise
 from ._native import device_guard
 from .rowwise import _Problem
 
@@ -34,31 +34,20 @@ CHUNK_BYTES = 256 << 20
 _NONE = 0x7FFFFFFF                                           # the search's status word: no query out of range
 
 
-def _row_times(name: str, v, B: int) -> torch.Tensor:
-    """`t0` / `t1` -> fp64 CPU tensor [B]: a number, a 0-dim tensor or a [B] tensor."""
-    if isinstance(v, torch.Tensor):
-        if v.requires_grad and torch.is_grad_enabled():
-            raise NotImplementedError(f"odeint_rowwise_dense does not propagate gradients ({name} requires grad); detach "
-                                      "it or call it under torch.no_grad()")
-        if v.is_complex() or v.dtype == torch.bool or v.dim() > 1 or (v.dim() == 1 and v.shape[0] != B):
-            raise ValueError(f"odeint_rowwise_dense: {name} must be a number, a 0-dim tensor or a real [B] = [{B}] tensor, "
-                             f"got a {v.dtype} tensor of shape {tuple(v.shape)}")
-        v = v.detach().to("cpu", torch.float64)
-        return v.expand(B).clone() if v.dim() == 0 else v.clone()
-    if isinstance(v, (int, float)) and not isinstance(v, bool):
-        return torch.full((B,), float(v), dtype=torch.float64)
-    raise ValueError(f"odeint_rowwise_dense: {name} must be a number, a 0-dim tensor or a [B] = [{B}] tensor, got "
-                     f"{type(v).__name__}")
+def _dense_time(name: str, v, B: int) -> torch.Tensor:
+    """`t0` / `t1` -> fp64 CPU tensor [B]."""
+    if isinstance(v, torch.Tensor) and v.requires_grad and torch.is_grad_enabled():
+        raise NotImplementedError(f"odeint_rowwise_dense does not propagate gradients ({name} requires grad); detach "
+                                  "it or call it under torch.no_grad()")
+    return rowwise._row_times("odeint_rowwise_dense", name, v, B)
 
 
 def _dense_grid(t0, t1, B: int) -> torch.Tensor:
     """The [2, B] fp64 grid [t0, t1] of the solve."""
-    start, end = _row_times("t0", t0, B), _row_times("t1", t1, B)
+    start, end = _dense_time("t0", t0, B), _dense_time("t1", t1, B)
     if not (bool(torch.isfinite(start).all()) and bool(torch.isfinite(end).all())):
         raise ValueError("odeint_rowwise_dense: t0 and t1 must be finite")
-    if not (bool((end > start).all()) or bool((end < start).all())):
-        raise ValueError("odeint_rowwise_dense: t1 must differ from t0 in every row, in the same direction for all rows")
-    return torch.stack([start, end])
+    return rowwise._row_grid("odeint_rowwise_dense", start, "t1", end)
 
 
 def _chunk_rows(options: dict, p_B: int, L: int, itemsize: int) -> int:
@@ -83,8 +72,10 @@ class _Chunk:
 
 
 class RowDenseStore:
-    """The quartics of one dense solve while it runs: chunks of `cap` slots, the hooks of both backends' `trial_step`
-    and the pack into the result."""
+    """The quartics of one dense solve while it runs: chunks of `cap` slots, the step hook (rowwise.py) and the pack into
+    the result."""
+
+    stopped_now = None                                       # a dense solve stops no row
 
     def __init__(self, p: _Problem, cap: int):
         self.p, self.cap = p, cap
@@ -94,7 +85,10 @@ class RowDenseStore:
         self.slot = torch.empty(p.B, dtype=torch.int32, device=p.device)
         self.mask = torch.empty(p.B, dtype=torch.int32, device=p.device)
 
-    def reserve(self, n_active: int) -> None:
+    def keep_rows(self, keep: torch.Tensor) -> None:
+        pass                                                 # (a slot names its row by original index: a repack moves nothing)
+
+    def before_step(self, n_active: int) -> None:
         """Before a trial step with `n_active` active rows (it accepts at most that many): make sure the current chunk has
         room for them.  The chunk's counter is read only when the bound leaves none."""
         if self.chunks and self.cap - self.bound < n_active:
@@ -106,14 +100,12 @@ class RowDenseStore:
             self.bound = 0
         self.bound += n_active
 
-    # -- the hook of HipRowKernels.trial_step ----------------------------------------------------------------------------
     def device_step(self, kern, y, y1, f0, f1, mid, coefs, dts) -> None:
         ch, n = self.chunks[-1], kern.n
         slot, mask = self.slot[:n], self.mask[:n]
         kern.k.row_dense_slots(kern.st, kern.row_map, self.cap, ch.counter, ch.row, ch.ord, ch.ta, ch.tb, slot, mask)
         kern.k.row_event_fit_mapped(ch.q, slot, mask, y, y1, f0, f1, mid, coefs, dts)
 
-    # -- the hook of HostRowKernels.trial_step ---------------------------------------------------------------------------
     def host_step(self, kern, accepted, y, y1, f0, f1, ks, dts) -> None:
         """The same as torch / numpy ops: slots in row order."""
         rows = [r for r, _, _ in accepted]
@@ -155,10 +147,7 @@ class RowDenseStore:
             if overflow or used > self.cap:
                 raise RuntimeError(f"odeint_rowwise_dense: internal error: a chunk of {self.cap} slots overflowed ({used} taken)")
             dest = offsets[ch.row[:used].to(torch.int64)] + ch.ord[:used].to(torch.int64)
-            if kern.name == "hip":
-                kern.k.row_dense_pack(coeffs, ch.q, dest, used)
-            else:
-                coeffs[:, dest] = ch.q[:, :used]
+            kern.pack_quartics(coeffs, ch.q, dest, used)
             seg_ta[dest] = ch.ta[:used]
             seg_tb[dest] = ch.tb[:used]
             packed += used
@@ -312,48 +301,25 @@ def odeint_rowwise_dense(func, y0, t0, t1, *, rtol=1e-7, atol=1e-9, method="dopr
     `odeint_dense` is unchanged.
     """
     options = dict(options or {})
-    is_batch = isinstance(y0, torch.Tensor) and y0.dim() >= 1 and y0.shape[0] >= 1
-    if is_batch:
-        t = _dense_grid(t0, t1, y0.shape[0])
-        cap = _chunk_rows(options, y0.shape[0], int(np.prod(y0.shape[1:])), y0.element_size())
+    B = rowwise._batch_rows(y0)
+    t, cap = None, 1
+    if B is not None:
+        t = _dense_grid(t0, t1, B)
+        cap = _chunk_rows(options, B, int(np.prod(y0.shape[1:])), y0.element_size())
         if torch.is_grad_enabled() and (y0.requires_grad or rowwise._func_parameters_require_grad(func)):
             raise NotImplementedError("odeint_rowwise_dense does not propagate gradients (y0 or a parameter of func requires "
                                       "grad); call it under torch.no_grad()")
-    else:
-        t, cap = torch.zeros(2, dtype=torch.float64), 1      # (_Problem refuses this y0)
-        options.pop("dense_chunk_rows", None)
+    options.pop("dense_chunk_rows", None)
     p = _Problem(func, y0, t, rtol, atol, method, options, None, False, compact)
-    # the first evaluation in the caller's grad mode, as in odeint_rowwise: a func whose output requires grad is refused
-    with device_guard(p.device):
-        f0 = p.call((p.tgrid[0] * p.sign).to(p.dtype).to(p.device), p.y0).clone()
+    f0 = p.first_call(p.y0)
     with torch.no_grad(), device_guard(p.device):
         store = RowDenseStore(p, cap)
-        if p.device.type == "cuda":
-            kern = rowwise.HipRowKernels(p, None, store)
-        else:
-            _fallback.warn_once(f"the state lives on '{p.device}'")
-            kern = rowwise.HostRowKernels(p, None, store)
         sol = torch.empty(2, p.B, p.L, dtype=p.dtype, device=p.device)      # (the commit writes y(t1) here; not returned)
         sol[0].copy_(p.y0)
-        y = p.y0.clone()                                     # private: the commit writes y <- y1, f0 <- f1 in place
-        kern.initial_step(y, f0)
-        while True:
-            n_active, failure = kern.poll()
-            if failure is not None:
-                p.raise_row_error(failure, y)
-            if n_active == 0:
-                break
-            if p.compact is not None and n_active < y.shape[0] and n_active <= p.compact * y.shape[0]:
-                y, f0 = kern.repack(y, f0, n_active)
-            store.reserve(n_active)
-            y, f0 = kern.trial_step(y, f0, sol)
-        n_acc, n_rej = kern.counts()
-        n_acc = n_acc.to(torch.int64)
-        dense = RowDenseOutput(p, kern.k if kern.name == "hip" else None, *store.finalize(kern, n_acc))
+        kern, n_acc, n_rej = rowwise._solve(p, p.y0, f0, sol, store)
+        stats = rowwise._stats(p, n_acc, n_rej)
+        dense = RowDenseOutput(p, kern.k, *store.finalize(kern, stats["n_accepted"]))
     if not return_stats:
         return dense
-    stats = {"n_accepted": n_acc, "n_rejected": n_rej.to(torch.int64), "nfe": p.nfe}
-    if p.compact is not None:
-        stats["row_evals"], stats["n_repacks"] = p.row_evals, p.n_repacks
     stats["n_segments"], stats["n_chunks"] = dense.n_segments, store.n_chunks
     return dense, stats

@@ -4,15 +4,15 @@
 integrated by the per-row controller of `odeint_rowwise` until `event_fn(t, y)[r]` changes sign (or the row reaches
 `t_end[r]`), and the event time of every row is then located by ONE bisection over the quartics of the rows' last steps.
 
-What an event solve adds to a rowwise trial step sits between the controller and the dense-output commit
-(`HipRowKernels.trial_step` / `HostRowKernels.trial_step` with a `RowEvents` object): one call of `event_fn`, the
+What an event solve adds to a rowwise trial step is the step hook `RowEvents` (rowwise.py: the driver and both backends
+take one), which runs between the controller and the dense-output commit: one call of `event_fn`, the
 detection (`tdeq_row_event_detect`: a row that fires leaves the active rows like a finished one) and the quartic of the
 rows that fired in this step (`tdeq_row_event_fit`), kept in a [5, B, L] buffer because the commit overwrites y0 and f0.
 The bisection evaluates the kept quartics (`tdeq_row_event_eval`); its [B] bracket arithmetic is a handful of fp64 torch
 ops, the same expressions on both backends.
 
 With `compact=` a row that has stopped — fired, reached `t_end`, or fired at `t0` — leaves the batch at the next repack
-(`odeint_rowwise`'s rule).  The quartics stay in the [5, B, L] buffer at their ORIGINAL row (`tdeq_row_event_fit_mapped`),
+(the driver's rule).  The quartics stay in the [5, B, L] buffer at their ORIGINAL row (`tdeq_row_event_fit_mapped`),
 `RowEvents.keep_rows` parks the event state of the rows that leave, and the bisection runs on the rows that have a quartic
 only (`tdeq_row_event_eval_mapped`).
 """
@@ -23,30 +23,19 @@ import math
 import numpy as np
 import torch
 
-from . import _fallback, rowwise
+from . import rowwise
 from ._native import device_guard
 from .rowwise import _Problem
 
 __all__ = ["odeint_rowwise_event"]
 
 
+_NAME = "odeint_rowwise_event"
+
+
 def _sign(g: torch.Tensor) -> torch.Tensor:
     """(g > 0) - (g < 0) as int32: 0 for a zero and for a NaN (the expression of tdeq_row_event_detect)."""
     return (g > 0).to(torch.int32) - (g < 0).to(torch.int32)
-
-
-def _row_times(name: str, v, B: int) -> torch.Tensor:
-    """`t0` / `t_end` -> fp64 CPU tensor [B]: a number, a 0-dim tensor or a [B] tensor."""
-    if isinstance(v, torch.Tensor):
-        if v.is_complex() or v.dtype == torch.bool or v.dim() > 1 or (v.dim() == 1 and v.shape[0] != B):
-            raise ValueError(f"odeint_rowwise_event: {name} must be a number, a 0-dim tensor or a real [B] = [{B}] tensor, "
-                             f"got a {v.dtype} tensor of shape {tuple(v.shape)}")
-        v = v.detach().to("cpu", torch.float64)
-        return v.expand(B).clone() if v.dim() == 0 else v.clone()
-    if isinstance(v, (int, float)) and not isinstance(v, bool):
-        return torch.full((B,), float(v), dtype=torch.float64)
-    raise ValueError(f"odeint_rowwise_event: {name} must be a number, a 0-dim tensor or a [B] = [{B}] tensor, got "
-                     f"{type(v).__name__}")
 
 
 def _event_grid(t0, t_end, B: int) -> torch.Tensor:
@@ -55,15 +44,12 @@ def _event_grid(t0, t_end, B: int) -> torch.Tensor:
         if isinstance(v, torch.Tensor) and v.requires_grad and torch.is_grad_enabled():
             raise NotImplementedError("odeint_rowwise_event does not propagate gradients (t0 / t_end requires grad); "
                                       "detach them or call it under torch.no_grad()")
-    start = _row_times("t0", t0, B)
+    start = rowwise._row_times(_NAME, "t0", t0, B)
     if not bool(torch.isfinite(start).all()):
         raise ValueError("odeint_rowwise_event: t0 must be finite")
     if t_end is None:
         return torch.stack([start, torch.full((B,), math.inf, dtype=torch.float64)])
-    end = _row_times("t_end", t_end, B)
-    if not (bool((end > start).all()) or bool((end < start).all())):
-        raise ValueError("odeint_rowwise_event: t_end must differ from t0 in every row, in the same direction for all rows")
-    return torch.stack([start, end])
+    return rowwise._row_grid(_NAME, start, "t_end", rowwise._row_times(_NAME, "t_end", t_end, B))
 
 
 class RowEvents:
@@ -141,7 +127,14 @@ class RowEvents:
         self._park()
         return self.all_sign0, self.all_fired, self.all_lo, self.all_hi
 
-    # -- the hook of HipRowKernels.trial_step ----------------------------------------------------------------------------
+    # -- the step hook (rowwise.py) ---------------------------------------------------------------------------------------
+    @property
+    def stopped_now(self) -> torch.Tensor:
+        return self.fired_now
+
+    def before_step(self, n_active: int) -> None:
+        pass
+
     def device_step(self, kern, y, y1, f0, f1, mid, coefs, dts) -> None:
         g1 = self.call(self.step_times(kern.t0), y1)
         kern.k.row_event_detect(g1, self.sign0, kern.ctrl, kern.st, kern.dts, kern.times, self.fired, self.fired_now,
@@ -151,7 +144,6 @@ class RowEvents:
         else:                                                # a compacted batch: the quartic goes to the row's original index
             kern.k.row_event_fit_mapped(self.coef, kern.row_map, self.fired_now, y, y1, f0, f1, mid, coefs, dts)
 
-    # -- the hook of HostRowKernels.trial_step ---------------------------------------------------------------------------
     def host_step(self, kern, accepted, y, y1, f0, f1, ks, dts) -> None:
         """The same decisions as torch / numpy ops; the row leaves the active ones after the controller's `prepare`."""
         g1 = self.call(self.step_times(torch.from_numpy(kern.t0.copy())), y1)
@@ -188,66 +180,59 @@ def _atol_rows(p: _Problem, atol_rows) -> torch.Tensor:
 
 def _locate(p: _Problem, ev: RowEvents, kern, sol, at_start):
     """The one bisection after every row has stopped -> (event time [B] fp64 in solver time, fired [B] bool);
-    solution row 1 of the rows that fired is overwritten with the quartic at the event time."""
-    if p.compact is not None:
-        return _locate_compact(p, ev, kern, sol, at_start)
+    solution row 1 of the rows that fired is overwritten with the quartic at the event time.
+
+    It runs over a SELECTION of the rows.  Without `compact`: all B rows, those without a quartic masked out ([B] vectors,
+    a [B, L] `y_mid`, `event_fn` called without `rows`).  With `compact`: the rows that have a quartic only, gathered in
+    ascending original order ([n_q] vectors, a [n_q, L] `y_mid`, `event_fn` called with `rows = idx`)."""
     dev = p.device
-    fired = ev.fired.bool()
-    has_q = fired & ~at_start                                # (a row that fired at t0 took no step: it keeps y0)
-    ta, tb = ev.lo.clone(), ev.hi.clone()                    # the step the row fired in: the quartic's interval
-    atol = _atol_rows(p, p.atol_rows)
-    n = _bisection_rounds((tb - ta) / atol, has_q)
-    if np.isinf(n).any():
-        raise OverflowError("odeint_rowwise_event: cannot bisect to a tolerance of 0 (atol must be positive) in row {}".format(
-            int(np.flatnonzero(np.isinf(n))[0])))
-    nitrs = torch.from_numpy(n.astype(np.int64)).to(dev)
-    mask = has_q.to(torch.int32)
-    width = tb - ta
-    lo, hi = ev.lo, ev.hi
-    y_mid = p.y0.clone()                                     # (rows without a quartic keep y0; their values are ignored)
-    for i in range(int(n.max()) if n.size else 0):
-        t_mid = (lo + hi) / 2
-        kern.event_eval(y_mid, ((t_mid - ta) / width).to(p.dtype), mask)
-        same = _sign(ev.call((t_mid * p.sign).to(p.dtype), y_mid)) == ev.sign0
-        update = has_q & (nitrs > i)
-        lo, hi = torch.where(update & same, t_mid, lo), torch.where(update & ~same, t_mid, hi)
-    event_s = (lo + hi) / 2
-    t_end = p.tgrid[1].to(dev)
-    fired = fired & (event_s <= t_end)                       # a final step that crossed both: the event must come first
-    kern.event_eval(sol[1], ((event_s - ta) / width).to(p.dtype), (has_q & fired).to(torch.int32))
-    return torch.where(fired, event_s, t_end), fired
-
-
-def _locate_compact(p: _Problem, ev: RowEvents, kern, sol, at_start):
-    """`_locate` of a solve with `compact` set: the same expressions on the rows that have a quartic only, gathered in
-    ascending original order — [n_q] vectors, a [n_q, L] `y_mid`, `event_fn` called with `rows = idx`."""
     sign0, fired, lo_all, hi_all = ev.full()
     fired = fired.bool()
-    has_q = fired & ~at_start
-    idx = torch.nonzero(has_q).view(-1)
-    ta, tb = lo_all.index_select(0, idx), hi_all.index_select(0, idx)
-    n = _bisection_rounds((tb - ta) / _atol_rows(p, ev.atol_rows).index_select(0, idx), torch.ones_like(idx, dtype=torch.bool))
+    has_q = fired & ~at_start                                # (a row that fired at t0 took no step: it keeps y0)
+    atol = _atol_rows(p, ev.atol_rows)
+    if p.compact is None:
+        idx, live, s0 = None, has_q, sign0
+        ta, tb = lo_all.clone(), hi_all.clone()              # the step the row fired in: the quartic's interval
+        lo, hi = lo_all, hi_all
+        mask = has_q.to(torch.int32)
+        y_mid = p.y0.clone()                                 # (rows without a quartic keep y0; their values are ignored)
+    else:
+        idx = torch.nonzero(has_q).view(-1)
+        ta, tb = lo_all.index_select(0, idx), hi_all.index_select(0, idx)
+        atol, live = atol.index_select(0, idx), torch.ones_like(idx, dtype=torch.bool)
+        lo, hi, s0 = ta, tb, sign0.index_select(0, idx)
+        src = idx.to(torch.int32)
+        y_mid = torch.empty(idx.numel(), p.L, dtype=p.dtype, device=dev)
+
+    def quartics_at(out, x, fired=None):
+        """out <- the selected rows' quartics at x; `fired` ([B] bool): only those rows, written at their original row."""
+        if idx is None:
+            kern.event_eval(out, ev.coef, x, mask if fired is None else (has_q & fired).to(torch.int32))
+        elif fired is None:
+            kern.event_eval_mapped(out, None, ev.coef, src, x)
+        else:
+            sel = fired.index_select(0, idx)
+            at = src[sel]
+            kern.event_eval_mapped(out, at, ev.coef, at, x[sel])
+
+    n = _bisection_rounds((tb - ta) / atol, live)            # (0 for a row without a quartic)
     if np.isinf(n).any():
+        r = int(np.flatnonzero(np.isinf(n))[0])
         raise OverflowError("odeint_rowwise_event: cannot bisect to a tolerance of 0 (atol must be positive) in row {}".format(
-            int(idx[int(np.flatnonzero(np.isinf(n))[0])])))
-    nitrs = torch.from_numpy(n.astype(np.int64)).to(p.device)
+            r if idx is None else int(idx[r])))
+    nitrs = torch.from_numpy(n.astype(np.int64)).to(dev)
     width = tb - ta
-    lo, hi, s0 = ta, tb, sign0.index_select(0, idx)
-    src = idx.to(torch.int32)
-    y_mid = torch.empty(idx.numel(), p.L, dtype=p.dtype, device=p.device)
     for i in range(int(n.max()) if n.size else 0):
         t_mid = (lo + hi) / 2
-        kern.event_eval_mapped(y_mid, None, src, ((t_mid - ta) / width).to(p.dtype))
+        quartics_at(y_mid, ((t_mid - ta) / width).to(p.dtype))
         same = _sign(ev.call((t_mid * p.sign).to(p.dtype), y_mid, idx)) == s0
         update = nitrs > i
         lo, hi = torch.where(update & same, t_mid, lo), torch.where(update & ~same, t_mid, hi)
-    event_s = ((lo_all + hi_all) / 2).index_copy_(0, idx, (lo + hi) / 2)
-    t_end = p.tgrid[1].to(p.device)
-    fired = fired & (event_s <= t_end)
-    x = ((event_s.index_select(0, idx) - ta) / width).to(p.dtype)
-    sel = fired.index_select(0, idx)
-    at = src[sel]
-    kern.event_eval_mapped(sol[1], at, at, x[sel])
+    mid = (lo + hi) / 2
+    event_s = mid if idx is None else ((lo_all + hi_all) / 2).index_copy_(0, idx, mid)
+    t_end = p.tgrid[1].to(dev)
+    fired = fired & (event_s <= t_end)                       # a final step that crossed both: the event must come first
+    quartics_at(sol[1], ((mid - ta) / width).to(p.dtype), fired)
     return torch.where(fired, event_s, t_end), fired
 
 
@@ -315,15 +300,11 @@ def odeint_rowwise_event(func, y0, t0, *, event_fn, t_end=None, rtol=1e-7, atol=
     """
     if not callable(event_fn):
         raise ValueError("odeint_rowwise_event: event_fn must be callable: event_fn(t_rows [b], y [b, *row_shape]) -> [b]")
-    if isinstance(y0, torch.Tensor) and y0.dim() >= 1 and y0.shape[0] >= 1:
-        t = _event_grid(t0, t_end, y0.shape[0])
-    else:
-        t = torch.zeros(2, dtype=torch.float64)              # (_Problem refuses this y0)
-    p = _Problem(func, y0, t, rtol, atol, method, options, None, False, compact)
+    B = rowwise._batch_rows(y0)
+    p = _Problem(func, y0, None if B is None else _event_grid(t0, t_end, B), rtol, atol, method, options, None, False, compact)
     ev = RowEvents(p, event_fn)
-    start = (p.tgrid[0] * p.sign).to(p.dtype).to(p.device)   # t0 in true time, as func and event_fn see it
     with torch.no_grad(), device_guard(p.device):
-        ev.sign0 = _sign(ev.call(start, p.y0))
+        ev.sign0 = _sign(ev.call((p.tgrid[0] * p.sign).to(p.dtype).to(p.device), p.y0))      # at t0 in true time
         at_start = ev.sign0 == 0
         ev.fired.copy_(at_start)
         ev.lo.copy_(p.tgrid[0])
@@ -332,38 +313,18 @@ def odeint_rowwise_event(func, y0, t0, *, event_fn, t_end=None, rtol=1e-7, atol=
         sol[0].copy_(p.y0)
         sol[1].copy_(p.y0)
         stepping = not bool(at_start.all())                  # every row fired at t0: no step, no func call
-    n_acc = n_rej = torch.zeros(p.B, dtype=torch.int64)
+    n_acc = n_rej = None
     event_s, fired = p.tgrid[0].to(p.device), at_start
     if stepping:
-        # the first evaluation in the caller's grad mode, as in odeint_rowwise: a func whose output requires grad is refused
-        with device_guard(p.device):
-            f0 = p.call(start, p.y0).clone()
+        f0 = p.first_call(p.y0)
         with torch.no_grad(), device_guard(p.device):
-            if p.device.type == "cuda":
-                kern = rowwise.HipRowKernels(p, ev)
-            else:
-                _fallback.warn_once(f"the state lives on '{p.device}'")
-                kern = rowwise.HostRowKernels(p, ev)
-            kern.deactivate_rows(at_start)
-            y = p.y0.clone()                                 # private: the commit writes y <- y1, f0 <- f1 in place
-            kern.initial_step(y, f0)
-            while True:
-                n_active, failure = kern.poll()
-                if failure is not None:
-                    p.raise_row_error(failure, y)
-                if n_active == 0:
-                    break
-                if p.compact is not None and n_active < y.shape[0] and n_active <= p.compact * y.shape[0]:
-                    y, f0 = kern.repack(y, f0, n_active)
-                y, f0 = kern.trial_step(y, f0, sol)
-            n_acc, n_rej = kern.counts()
+            kern, n_acc, n_rej = rowwise._solve(p, p.y0, f0, sol, ev, at_start)
             event_s, fired = _locate(p, ev, kern, sol, at_start)
     event_t = event_s * p.sign
     solution = sol.view(2, *p.shape)
     if not return_stats:
         return event_t, solution
-    stats = {"n_accepted": n_acc.to(torch.int64), "n_rejected": n_rej.to(torch.int64), "nfe": p.nfe,
-             "fired": fired.cpu(), "n_event_evals": ev.n_evals}
+    stats = dict(rowwise._stats(p, n_acc, n_rej), fired=fired.cpu(), n_event_evals=ev.n_evals)
     if p.compact is not None:
-        stats["row_evals"], stats["n_repacks"], stats["event_row_evals"] = p.row_evals, p.n_repacks, ev.row_evals
+        stats["event_row_evals"] = ev.row_evals
     return event_t, solution, stats
