@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define TDEQ_ABI_VERSION 28
+#define TDEQ_ABI_VERSION 29
 #define TDEQ_F32 0
 #define TDEQ_F64 1
 /* interleaved (re, im) complex states — accepted by the NORM entry points only (tdeq_error_norm, tdeq_error_norm_partial[_ctrl],
@@ -577,7 +577,7 @@ typedef struct tdeq_row_state {
     int64_t* n_acc;
     int64_t* n_rej;
     double* ratio;         /* [n_rows] last error ratio                                               */
-    int32_t* status;       /* [2]                                                                     */
+    int32_t* status;       /* [2]; [3] for tdeq_row_control_points                                    */
     int64_t n_rows;
     int64_t row_len;
     int64_t max_num_steps;
@@ -741,6 +741,56 @@ int tdeq_row_dense_pack(void* dst, int64_t dst_rows, const void* src, int64_t sr
 int tdeq_row_dense_search(const double* tq, int64_t n_q, const int64_t* offsets, const double* seg_ta, const double* seg_tb,
                           int64_t n_seg, const double* t0, const double* t1, int64_t n_rows, int32_t* seg, void* x,
                           int32_t* status, int dtype, void* stream);
+
+/*
+ * ---- Per-row step options (ABI 29; `min_step`, `max_step`, `step_t`, `jump_t` of the rowwise family) ----
+ * tdeq_row_control_points  tdeq_row_control with step bounds per row and with points per row: `step_t` (times a step of
+ *                          the row must end on) and `jump_t` (times where func is discontinuous), rk_common.py:223-241,
+ *                          289-309, 343-352 row by row.  Every mode clamps with the row's min_step[r] / max_step[r] (NULL:
+ *                          the scalar of `ctrl`), and mode 0 accepts with them.  After the clamp and the error checks of a
+ *                          prepared step (modes 0, 2, 3, rows still active), with p = step_t[next_step[r], r] for a row with
+ *                          step_count[r] >= 1: t0 < p < t0 + dt cuts the step, dt = p - t0 and the step ends at p; then the
+ *                          same test with jump_t on the step so far, and a jump point wins.  on_point[r] = 0 / 1 / 2 (not
+ *                          cut / step point / jump point, 0 for a row not active), and for a cut step clip_t[r] = p,
+ *                          dt[r] = p - t0, dts_out[r] = sign * T(dt), the stage of abscissa 1 at sign * prev_T(T(p)), the
+ *                          others at sign * (T(t0) + alpha_T T(dt)).  Mode 0 ends an accepted step with on_point[r] != 0 at
+ *                          t0[r] = clip_t[r] (the point's bits, not t0 + dt), then moves next_step[r] (on_point 1) or
+ *                          next_jump[r] (on_point 2) on by one unless it is the row's last index, and writes for EVERY row
+ *                          jumped[r] = the accepted step ended on a jump point, jump_times[r] (state type) = sign *
+ *                          next_T(T(t0[r])) where jumped, sign * T(t0[r]) elsewhere: the times of the one evaluation of
+ *                          func that refreshes f0 of the rows that jumped.  st->status holds THREE words: the two of
+ *                          tdeq_row_control and status[2] = rows with jumped[r] in this launch (0 in the other modes).
+ *                          Tables are [n_points, n_rows] doubles in solver time, each column sorted ascending and padded
+ *                          with +inf; a NULL table is absent (its count / index vectors are then not read).  0 <=
+ *                          next[r] < count[r] <= n_points for a row with points.  With both tables and both bound
+ *                          vectors NULL every vector of `st`, dts_out and times_out get the bits of tdeq_row_control.
+ * tdeq_row_select          dst[r, e] = src[r, e] for the rows with mask[r] != 0 (int32 [n_rows]), e < row_len: a copy of
+ *                          bits; no other row is read or written.  16-byte elements when row_len is a multiple of
+ *                          16 / sizeof(T) and both bases are 16-byte aligned, scalar elements otherwise.
+ * 64-bit offsets.  A NULL pointer other than those named, a negative size or a dtype other than TDEQ_F32 / TDEQ_F64:
+ * TDEQ_EINVAL before any launch.  n_rows == 0: no-op (the status words are still reset).
+ */
+typedef struct tdeq_row_points {
+    const double* step_t;       /* [n_step, n_rows] or NULL                                             */
+    const double* jump_t;       /* [n_jump, n_rows] or NULL                                             */
+    const int32_t* step_count;  /* [n_rows] points of each row                                          */
+    const int32_t* jump_count;
+    int32_t* next_step;         /* [n_rows] index of the row's next point                               */
+    int32_t* next_jump;
+    double* clip_t;             /* [n_rows] end of a prepared step that was cut                         */
+    int32_t* on_point;          /* [n_rows] 0 not cut, 1 at a step point, 2 at a jump point             */
+    const double* min_step;     /* [n_rows] or NULL                                                     */
+    const double* max_step;     /* [n_rows] or NULL                                                     */
+    int32_t* jumped;            /* [n_rows] mode 0                                                      */
+    void* jump_times;           /* [n_rows] of the state type, mode 0                                   */
+    int32_t n_step;             /* rows of the step_t table                                             */
+    int32_t n_jump;
+} tdeq_row_points;
+
+int tdeq_row_control_points(int mode, const double* part, const tdeq_step_ctrl* ctrl, const tdeq_row_state* st,
+                            const tdeq_row_points* pts, void* dts_out, void* times_out, int dtype, void* stream);
+int tdeq_row_select(void* dst, const void* src, const int32_t* mask, int64_t n_rows, int64_t row_len, int dtype,
+                    void* stream);
 
 #ifdef __cplusplus
 }

@@ -46,6 +46,12 @@ element, and the search launch alone.
 (the plain rowwise solve and the plain event solve; the first line of each file is the warm-up round) and `bench.py --gpus 1
 --steps 200 --warmup 20` — and says whether this tree's medians lie inside the parent's observed spread.
 
+`--steps`: the headline shape with one jump point per row at a per-row time (func y @ A.T plus a forcing that changes sign
+at the row's point): the solve with `jump_t` against the same func without it (whose controller grinds through the kink),
+ms per trial step, the refresh calls and — from one instrumented solve, synchronised on both sides — ms per refresh; and the
+achieved rate of `tdeq_row_select` on the whole state (every row selected: 1 read + 1 write per element) against the HBM
+peak.
+
 `--grad`: forward + backward of a `differentiable=True` solve per trial step at the headline, next to plain `odeint`
 backprop of the same state, and (`--parity`) the per-row deviations of the rowwise gradients from the reference's
 (tests/golden/rowwise_grad.npz) on the host path and on the device.
@@ -107,6 +113,78 @@ def _headline(reps: int, rowtol: bool = False):
     for k in ("rowwise_ms_per_trial", "odeint_ms_per_trial"):
         res[k] = res[k][1:]          # the first pair warms up
     res["ratio_rowwise_over_odeint"] = min(res["rowwise_ms_per_trial"]) / min(res["odeint_ms_per_trial"])
+    return res
+
+
+def _steps(reps: int):
+    import torchdiffeq_amd as tda
+    from torchdiffeq_amd import _native, rowwise
+    dev = torch.device("cuda", 0)
+    B, D = 65536, 128
+    g = torch.Generator().manual_seed(0)
+    G = torch.randn(D, D, generator=g, dtype=torch.float64) / D ** 0.5
+    A = (0.5 * (G - G.T) - 0.1 * torch.eye(D, dtype=torch.float64)).float().to(dev)
+    y0 = torch.randn(B, D, generator=g).to(dev)
+    tj = (0.1 + 0.3 * torch.rand(B, generator=g, dtype=torch.float64))
+    tj_dev = tj.float().to(dev)
+    t = torch.tensor([0.0, 0.5], device=dev)
+
+    def f(t_, y):
+        return y @ A.T + torch.where(t_ >= tj_dev, 0.5, -0.5)[:, None]
+    settings = (("without_jump_t", None), ("with_jump_t", {"jump_t": tj[None, :]}))
+    res = {name: {"ms_per_solve": []} for name, _ in settings}
+    with torch.no_grad():
+        for rep in range(reps + 1):
+            for name, options in settings:
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                _, st = tda.odeint_rowwise(f, y0, t, rtol=1e-7, atol=1e-9, options=options, return_stats=True)
+                torch.cuda.synchronize()
+                if rep:                       # the first round warms up
+                    res[name]["ms_per_solve"].append((time.perf_counter() - t0) * 1e3)
+                trials = st["n_accepted"] + st["n_rejected"]
+                res[name].update(nfe=st["nfe"], trial_steps=int(trials.max()), trials_median=float(trials.median()),
+                                 refresh_calls=st["nfe"] - 2 - 6 * int(trials.max()))
+        for name, _ in settings:
+            res[name]["ms_per_trial_step"] = sorted(res[name]["ms_per_solve"])[len(res[name]["ms_per_solve"]) // 2] \
+                / res[name]["trial_steps"]
+        # one instrumented solve: the refresh (one func call + tdeq_row_select) between synchronisations
+        spent = []
+        orig = rowwise.HipRowKernels.refresh_after_jump
+
+        def timed(self, y, f0):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            out = orig(self, y, f0)
+            torch.cuda.synchronize()
+            spent.append((time.perf_counter() - t0) * 1e3)
+            return out
+        rowwise.HipRowKernels.refresh_after_jump = timed
+        try:
+            tda.odeint_rowwise(f, y0, t, rtol=1e-7, atol=1e-9, options=settings[1][1])
+        finally:
+            rowwise.HipRowKernels.refresh_after_jump = orig
+        res["refresh"] = {"calls": len(spent), "ms_per_refresh_median": sorted(spent)[len(spent) // 2] if spent else None,
+                          "ms_total": sum(spent)}
+        # tdeq_row_select on the whole state, every row selected
+        kern = _native.get_kernels(dev, torch.float32)
+        dst, src = torch.zeros_like(y0), y0.clone()
+        mask = torch.ones(B, dtype=torch.int32, device=dev)
+        for _ in range(3):
+            kern.row_select(dst, src, mask)
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+        n = 20
+        ev[0].record()
+        for _ in range(n):
+            kern.row_select(dst, src, mask)
+        ev[1].record()
+        torch.cuda.synchronize()
+        ms = ev[0].elapsed_time(ev[1]) / n
+        tbs = 2 * B * D * 4 / (ms * 1e-3) / 1e12
+        res["row_select"] = {"shape": [B, D], "ms": ms, "TB_per_s": tbs, "fraction_of_peak": tbs / PEAK_TBS,
+                             "note": "2 x 33.5 MB per launch: the state fits the 256 MB last-level cache, so the rate is not "
+                                     "bounded by HBM alone"}
+    res["shape"] = [B, D]
     return res
 
 
@@ -647,6 +725,7 @@ def main():
     ap.add_argument("--setting", default="plain", choices=("plain", "0.5", "1.0"))
     ap.add_argument("--event-compact-summary", default=None)
     ap.add_argument("--dense", action="store_true")
+    ap.add_argument("--steps", action="store_true")
     ap.add_argument("--dense-summary", default=None)
     a = ap.parse_args()
     if a.dense_summary:
@@ -658,6 +737,17 @@ def main():
                        "logspace(-1, 1.5) shuffled, t0 = 0, t1 = 0.5, rtol 1e-7, atol 1e-9; one process, the plain and the "
                        "dense solve alternated, the first pair a warm-up",
                "dense": _dense(a.reps)}
+        print(json.dumps(res))
+        if a.out:
+            os.makedirs(os.path.dirname(a.out) or ".", exist_ok=True)
+            json.dump(res, open(a.out, "w"), indent=1)
+        return
+    if a.steps:
+        res = {"device": torch.cuda.get_device_name(0), "arch": torch.cuda.get_device_properties(0).gcnArchName,
+               "what": "tools/rowwise_bench.py --steps: 65536 x 128 fp32 dopri5, func y @ A.T + 0.5 sign(t - tj_r), one jump "
+                       "point per row at tj_r in (0.1, 0.4), t = [0, 0.5], rtol 1e-7, atol 1e-9; one process, the two solves "
+                       "alternated, the first pair a warm-up",
+               "steps": _steps(a.reps)}
         print(json.dumps(res))
         if a.out:
             os.makedirs(os.path.dirname(a.out) or ".", exist_ok=True)

@@ -18,7 +18,7 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-TDEQ_ABI_VERSION = 28
+TDEQ_ABI_VERSION = 29
 TDEQ_F32, TDEQ_F64 = 0, 1
 TDEQ_C64, TDEQ_C128 = 2, 3        # interleaved complex: the norm entry points only (include/tdeq_hip.h)
 TDEQ_BF16, TDEQ_F16 = 4, 5        # reduced-precision states: the entry points of the host-driven step (LowPrecisionHipKernels)
@@ -79,6 +79,15 @@ class RowState(ctypes.Structure):
                                                       "ratio", "status")] + \
                [("n_rows", ctypes.c_int64), ("row_len", ctypes.c_int64), ("max_num_steps", ctypes.c_int64),
                 ("n_out", ctypes.c_int32), ("order", ctypes.c_int32)]
+
+
+class RowPoints(ctypes.Structure):
+    """`tdeq_row_points` of include/tdeq_hip.h: the per-row step bounds and the per-row `step_t` / `jump_t` tables of a
+    rowwise solve, with the vectors `tdeq_row_control_points` keeps for them (a null pointer: absent)."""
+    _fields_ = [(name, ctypes.c_void_p) for name in ("step_t", "jump_t", "step_count", "jump_count", "next_step",
+                                                      "next_jump", "clip_t", "on_point", "min_step", "max_step", "jumped",
+                                                      "jump_times")] + \
+               [("n_step", ctypes.c_int32), ("n_jump", ctypes.c_int32)]
 
 
 # name -> (restype, argtypes); the authoritative list of exported symbols (checked by the tests).
@@ -274,6 +283,12 @@ ABI_SIGNATURES = {
                                              ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
                                              ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                              ctypes.c_int, ctypes.c_void_p]),
+    # per-row step options (ABI 29, `min_step` / `max_step` / `step_t` / `jump_t` of the rowwise family)
+    "tdeq_row_control_points": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(StepCtrl),
+                                               ctypes.POINTER(RowState), ctypes.POINTER(RowPoints), ctypes.c_void_p,
+                                               ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
+    "tdeq_row_select": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
+                                       ctypes.c_int, ctypes.c_void_p]),
 }
 
 
@@ -917,6 +932,20 @@ class HipKernels:
     def row_control(self, mode: int, part, ctrl: StepCtrl, st: RowState, dts_out, times_out, dtype) -> None:
         _check(self.lib.tdeq_row_control(mode, part.data_ptr(), ctypes.byref(ctrl), ctypes.byref(st), dts_out.data_ptr(),
                                          times_out.data_ptr(), dtype_code(dtype), self._stream()), "tdeq_row_control")
+
+    def row_control_points(self, mode: int, part, ctrl: StepCtrl, st: RowState, pts: RowPoints, dts_out, times_out,
+                           dtype) -> None:
+        """tdeq_row_control_points: `row_control` with the per-row bounds and points of `pts`; `st.status` has 3 words."""
+        _check(self.lib.tdeq_row_control_points(mode, part.data_ptr(), ctypes.byref(ctrl), ctypes.byref(st),
+                                                ctypes.byref(pts), dts_out.data_ptr(), times_out.data_ptr(),
+                                                dtype_code(dtype), self._stream()), "tdeq_row_control_points")
+
+    def row_select(self, dst, src, mask) -> None:
+        """tdeq_row_select: dst[r, :] = src[r, :] for the rows with mask[r] != 0 (`mask` int32 [B] on the device)."""
+        if dst.shape[0] == 0:
+            return
+        _check(self.lib.tdeq_row_select(dst.data_ptr(), src.data_ptr(), mask.data_ptr(), dst.shape[0], dst.shape[1],
+                                        dtype_code(dst.dtype), self._stream()), "tdeq_row_select")
 
     def row_dense_commit(self, sol, y0, y1, f0, f1, ks, coefs, dts, st: RowState) -> None:
         ptrs, cf, n = self._terms(ks, coefs)

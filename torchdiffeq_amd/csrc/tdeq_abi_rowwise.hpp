@@ -6,6 +6,7 @@
 #include "tdeq_kernels_rowwise.hpp"
 #include "tdeq_kernels_rowwise_event.hpp"
 #include "tdeq_kernels_rowwise_dense.hpp"
+#include "tdeq_kernels_rowwise_steps.hpp"
 
 namespace {
 using namespace tdeq;
@@ -394,20 +395,25 @@ int tdeq_row_reduce_tol(int mode, const void* y0, const void* y1, const void* pa
                                                    row_len, part, s);
 }
 
-int tdeq_row_control(int mode, const double* part, const tdeq_step_ctrl* ctrl, const tdeq_row_state* st,
-                     void* dts_out, void* times_out, int dtype, void* stream) {
+namespace {
+// what tdeq_row_control and tdeq_row_control_points check and fill alike: the status words are reset, and with at least
+// one row (`launch`) the argument block is filled
+int row_control_args(RowCtrlArgs& a, int mode, const double* part, const tdeq_step_ctrl* ctrl, const tdeq_row_state* st,
+                     void* dts_out, void* times_out, int dtype, int n_status, hipStream_t s, bool& launch) {
+    launch = false;
     if (!part || !ctrl || !st || !row_dtype_ok(dtype) || mode < 0 || mode > 3) return TDEQ_EINVAL;
     if (st->n_rows < 0 || st->row_len < 1 || st->n_out < 1 || !st->status) return TDEQ_EINVAL;
     if (ctrl->n_times < 1 || ctrl->n_times > TDEQ_MAX_STAGE_TIMES) return TDEQ_EINVAL;
     if (!dts_out || !times_out) return TDEQ_EINVAL;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    // status = {0 active rows, no row in error}
+    // status = {0 active rows, no row in error[, 0 rows that jumped]}
     hipError_t e = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(st->status), 0, 1, s);
     if (e == hipSuccess)
         e = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(st->status + 1), 0x7fffffff, 1, s);
+    if (e == hipSuccess && n_status > 2)
+        e = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(st->status + 2), 0, 1, s);
     if (e != hipSuccess) return (int)e;
     if (st->n_rows == 0) return 0;
-    RowCtrlArgs a;
+    launch = true;
     a.part = part;
     a.nch = (int)row_geom(st->row_len, dtype).nch;
     a.n_rows = st->n_rows;
@@ -437,7 +443,87 @@ int tdeq_row_control(int mode, const double* part, const tdeq_step_ctrl* ctrl, c
     a.n_rej = st->n_rej;
     a.ratio_out = st->ratio;
     a.status = st->status;
+    return 0;
+}
+
+template <typename T>
+int row_control_points_launch(const RowCtrlPointsArgs& a, hipStream_t s) {
+    if (a.base.nch > 1) {
+        const dim3 grid((unsigned)((a.base.n_rows * kWave + kBlock - 1) / kBlock));
+        hipLaunchKernelGGL((row_ctrl_points_kernel<T, true>), grid, dim3(kBlock), 0, s, a);
+    } else {
+        const dim3 grid((unsigned)((a.base.n_rows + kBlock - 1) / kBlock));
+        hipLaunchKernelGGL((row_ctrl_points_kernel<T, false>), grid, dim3(kBlock), 0, s, a);
+    }
+    return check_launch();
+}
+
+template <typename E>
+int row_select_launch(void* dst, const void* src, const int32_t* mask, int64_t n_rows, int64_t row_len_e, hipStream_t s) {
+    RowSelectArgs a;
+    a.dst = dst;
+    a.src = src;
+    a.mask = mask;
+    a.row_len = row_len_e;
+    a.ne = n_rows * row_len_e;
+    hipLaunchKernelGGL((row_select_kernel<E>), dim3(stream_grid(a.ne, kBlock)), dim3(kBlock), 0, s, a);
+    return check_launch();
+}
+}  // namespace
+
+int tdeq_row_control(int mode, const double* part, const tdeq_step_ctrl* ctrl, const tdeq_row_state* st,
+                     void* dts_out, void* times_out, int dtype, void* stream) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    RowCtrlArgs a;
+    bool launch;
+    const int e = row_control_args(a, mode, part, ctrl, st, dts_out, times_out, dtype, 2, s, launch);
+    if (e || !launch) return e;
     return dtype == TDEQ_F32 ? row_control_launch<float>(a, s) : row_control_launch<double>(a, s);
+}
+
+// ---- per-row step options: tdeq_row_control_points / tdeq_row_select ---------------------------------------------------
+int tdeq_row_control_points(int mode, const double* part, const tdeq_step_ctrl* ctrl, const tdeq_row_state* st,
+                            const tdeq_row_points* pts, void* dts_out, void* times_out, int dtype, void* stream) {
+    if (!pts || !pts->clip_t || !pts->on_point || !pts->jumped || !pts->jump_times) return TDEQ_EINVAL;
+    if (pts->step_t && (pts->n_step < 1 || !pts->step_count || !pts->next_step)) return TDEQ_EINVAL;
+    if (pts->jump_t && (pts->n_jump < 1 || !pts->jump_count || !pts->next_jump)) return TDEQ_EINVAL;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    RowCtrlPointsArgs a;
+    bool launch;
+    const int e = row_control_args(a.base, mode, part, ctrl, st, dts_out, times_out, dtype, 3, s, launch);
+    if (e || !launch) return e;
+    // the bounds: per row or the two scalars, never those of `base.c` (see tdeq_kernels_rowwise_steps.hpp)
+    a.lo = ctrl->min_step;
+    a.hi = ctrl->max_step;
+    a.base.c.min_step = -HUGE_VAL;
+    a.base.c.max_step = HUGE_VAL;
+    a.step_t = pts->step_t;
+    a.jump_t = pts->jump_t;
+    a.step_count = pts->step_count;
+    a.jump_count = pts->jump_count;
+    a.next_step = pts->next_step;
+    a.next_jump = pts->next_jump;
+    a.clip_t = pts->clip_t;
+    a.on_point = pts->on_point;
+    a.min_step = pts->min_step;
+    a.max_step = pts->max_step;
+    a.jumped = pts->jumped;
+    a.jump_times = pts->jump_times;
+    return dtype == TDEQ_F32 ? row_control_points_launch<float>(a, s) : row_control_points_launch<double>(a, s);
+}
+
+int tdeq_row_select(void* dst, const void* src, const int32_t* mask, int64_t n_rows, int64_t row_len, int dtype,
+                    void* stream) {
+    if (!dst || !src || !mask || n_rows < 0 || row_len < 1 || !row_dtype_ok(dtype)) return TDEQ_EINVAL;
+    if (n_rows == 0) return 0;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int lv = row_lanes(row_len, dtype);
+    if (lv > 1 && aligned16(dst) && aligned16(src)) {
+        return dtype == TDEQ_F32 ? row_select_launch<VecOf<float>::type>(dst, src, mask, n_rows, row_len / lv, s)
+                                 : row_select_launch<VecOf<double>::type>(dst, src, mask, n_rows, row_len / lv, s);
+    }
+    return dtype == TDEQ_F32 ? row_select_launch<float>(dst, src, mask, n_rows, row_len, s)
+                             : row_select_launch<double>(dst, src, mask, n_rows, row_len, s);
 }
 
 int tdeq_row_dense_commit(void* sol, void* y0, const void* y1, void* f0, const void* f1, const void* const* k,

@@ -8,8 +8,8 @@ its own tolerances.  A row's bits do not depend on B or on the other rows (as lo
 independently).
 
 On a ROCm device every state-sized operation is a HIP kernel of csrc/tdeq_kernels_rowwise.hpp and the per-row
-controller runs on the device (the host reads two words per trial step); CPU states run the same row operations as
-torch ops (`HostRowKernels`, one `HostPathWarning`).
+controller runs on the device (the host reads two words per trial step, three with per-row bounds or points); CPU
+states run the same row operations as torch ops (`HostRowKernels`, one `HostPathWarning`).
 
 The structure.  ONE DRIVER, `_solve`, serves the three entry points (`odeint_rowwise` here, `odeint_rowwise_event` in
 rowwise_event.py, `odeint_rowwise_dense` in rowwise_dense.py): it chooses the backend, runs the initial step and then the
@@ -19,8 +19,9 @@ solve between two times per row), evaluates `func` once in the caller's grad mod
 the driver leaves behind into its result.
 
 The TWO BACKENDS, `HipRowKernels` and `HostRowKernels`, offer the driver the same methods — `initial_step`, `trial_step`,
-`poll`, `counts`, `repack`, `deactivate_rows`, for a recorded solve `begin_recording` / `recorded_solution` — and the
-entry points the operations on kept quartics, `event_eval` / `event_eval_mapped` / `pack_quartics`.  WHAT IS LAUNCHED in a
+`poll`, `counts`, `repack`, `deactivate_rows`, `n_jumped` / `refresh_after_jump` (a step onto a `jump_t` point), for a
+recorded solve `begin_recording` / `recorded_solution` — and the entry points the operations on kept quartics,
+`event_eval` / `event_eval_mapped` / `pack_quartics`.  WHAT IS LAUNCHED in a
 trial step is `HipRowKernels.trial_step`: one interpreter of the tableau's launch plan (`tableaus.launch_plan`: the carry
 plan of dopri5 / dopri8 / tsit5, row by row for the others), then the error norm, the controller, the hook and the
 dense-output commit.
@@ -51,7 +52,7 @@ from . import _fallback, _native
 from . import rowwise_autodiff as rad
 from ._native import device_guard
 from ._scalars import nextafter, power, rdiv, scalar_type
-from .solvers._common import optimal_step_size
+from .solvers._common import _clamp, optimal_step_size
 from .solvers.adaptive import (STEP_CALLBACKS, AdaptiveHeunSolver, Bosh3Solver, Dopri5Solver, Dopri8Solver, Fehlberg2,
                                Tsit5Solver)
 from .tableaus import SparseRow, launch_plan
@@ -60,7 +61,8 @@ __all__ = ["odeint_rowwise"]
 
 _METHODS = {"dopri5": Dopri5Solver, "bosh3": Bosh3Solver, "tsit5": Tsit5Solver, "fehlberg2": Fehlberg2,
             "adaptive_heun": AdaptiveHeunSolver, "dopri8": Dopri8Solver}
-_OPTIONS = ("first_step", "safety", "ifactor", "dfactor", "max_num_steps")
+_OPTIONS = ("first_step", "safety", "ifactor", "dfactor", "max_num_steps", "min_step", "max_step", "step_t", "jump_t")
+_STEP_OPTIONS = ("min_step", "max_step", "step_t", "jump_t")
 _NO_ERROR_ROW = 0x7FFFFFFF
 
 
@@ -119,6 +121,91 @@ def _tolerance(name: str, tol, B: int):
                          f"got shape {tuple(shape)}; a vector of another length and tolerances per element of a row "
                          "([B, *row_shape], [*row_shape]) are not supported")
     return None, vec
+
+
+def _step_bound(name: str, v, B: int):
+    """`min_step` / `max_step` -> (float, None) or (None, fp64 CPU tensor [B]): the forms of `_tolerance`.  The values are
+    not looked at, as the reference does not validate them."""
+    if isinstance(v, torch.Tensor) and v.dtype == torch.bool:
+        v = None
+    try:
+        return _tolerance(name, v, B)
+    except ValueError:
+        raise ValueError(f"odeint_rowwise: {name} must be a number, a 0-dim tensor or a real per-row vector of exactly "
+                         f"B = {B} entries (a 1-D tensor, numpy array, list or tuple of numbers)") from None
+
+
+class _RowPoints:
+    """One of the two point tables of a rowwise solve (`step_t`, `jump_t`) as the controllers take it: `table` [K, B] fp64
+    numpy in solver time, every column sorted ascending and padded with +inf, `count` [B] the points of each row, `next`
+    [B] the index each row starts with (rk_common.py:223-241 row by row; -1 for a row without points)."""
+
+    def __init__(self, table: np.ndarray, count: np.ndarray, nxt: np.ndarray):
+        self.table, self.count, self.next = table, count, nxt
+
+
+def _points(name: str, v, B: int) -> "np.ndarray | None":
+    """`step_t` / `jump_t` -> fp64 numpy [K, B] in the caller's time (NaN: no point), or None for K = 0."""
+    bad = None
+    if isinstance(v, torch.Tensor):
+        if v.is_complex() or v.dtype == torch.bool:
+            bad = f"a {v.dtype} tensor"
+        else:
+            a = v.detach().to("cpu", torch.float64).numpy()
+    elif isinstance(v, (np.ndarray, list, tuple)):
+        try:
+            a = np.asarray(v)
+        except ValueError:
+            a = np.empty(0, dtype=object)
+        if a.size == 0 and a.ndim == 1:
+            a = a.astype(np.float64)
+        if a.dtype.kind not in "fiu":
+            bad = f"values of kind {a.dtype}"
+        else:
+            a = a.astype(np.float64)
+    else:
+        bad = type(v).__name__
+    if bad is None and not (a.ndim == 1 or (a.ndim == 2 and a.shape[1] == B)):
+        bad = f"shape {tuple(a.shape)}"
+    if bad is not None:
+        raise ValueError(f"odeint_rowwise: {name} must be real times [K] (shared by all rows) or [K, B] = [K, {B}] (a "
+                         f"column per row): a tensor, a numpy array or a list of numbers; got {bad}")
+    if a.shape[0] == 0:
+        return None
+    return np.ascontiguousarray(np.broadcast_to(a[:, None], (a.shape[0], B)) if a.ndim == 1 else a)
+
+
+def _row_points(step, jump, sign: float, t0: np.ndarray):
+    """The two tables of `_points` -> (`_RowPoints` or None) each: per row the points >= t0_r in solver time, sorted; a
+    value that occurs twice in a row's two lists together is refused (rk_common.py:229-232).  Whole-table numpy ops: the
+    set-up of B rows costs no Python loop over them."""
+    kept = []
+    for tab in (step, jump):
+        if tab is None:
+            kept.append(None)
+            continue
+        a = tab * sign
+        with np.errstate(invalid="ignore"):
+            a = np.where(a >= t0[None, :], a, np.nan)        # (a NaN entry is padding; a point before t0_r is dropped)
+        kept.append(np.sort(a, axis=0))                      # ascending, NaN last
+    both = [a for a in kept if a is not None]
+    if both:
+        merged = np.sort(np.concatenate(both, axis=0), axis=0)
+        twice = (merged[1:] == merged[:-1]).any(axis=0)      # (NaN != NaN: padding never counts)
+        if twice.any():
+            raise ValueError("`step_t` and `jump_t` must not have any repeated elements between them (row {}).".format(
+                int(np.flatnonzero(twice)[0])))
+    out = []
+    for a in kept:
+        count = None if a is None else (a == a).sum(axis=0).astype(np.int32)
+        if a is None or count.max(initial=0) == 0:
+            out.append(None)
+            continue
+        # bisect_right(points, t0_r) counts the points equal to t0_r (none is smaller); then min(., n - 1), -1 without points
+        nxt = np.minimum((a == t0[None, :]).sum(axis=0), count - 1).astype(np.int32)
+        table = np.where(a == a, a, np.inf)[:int(count.max())]
+        out.append(_RowPoints(np.ascontiguousarray(table), count, nxt))
+    return out
 
 
 def _batch_rows(y0):
@@ -251,6 +338,22 @@ class _Problem:
         self.ifactor = float(options.get("ifactor", 10.0))
         self.dfactor = float(options.get("dfactor", 0.2))
         self.max_num_steps = int(options.get("max_num_steps", 2 ** 31 - 1))
+        # the step options: two bounds (floats, or — as soon as one is a per-row vector — two fp64 [B] numpy vectors) and
+        # the two point tables; the clipped step's graph is out of scope for a recorded solve
+        (self.min_step, lo_rows), (self.max_step, hi_rows) = (_step_bound(name, options.get(name, default), B)
+                                                              for name, default in (("min_step", 0.0), ("max_step", math.inf)))
+        self.min_rows = self.max_rows = None
+        if lo_rows is not None or hi_rows is not None:
+            self.min_rows, self.max_rows = (np.full(B, x) if v is None else v.numpy().copy()
+                                            for x, v in ((self.min_step, lo_rows), (self.max_step, hi_rows)))
+            self.min_step = self.max_step = None
+        self.step_points, self.jump_points = _row_points(_points("step_t", options.get("step_t", ()), B),
+                                                         _points("jump_t", options.get("jump_t", ()), B), sign,
+                                                         self.tgrid[0].numpy())
+        given = [name for name in _STEP_OPTIONS if name in options]
+        if self.record and given:                            # (after their validation: a wrong value is a ValueError first)
+            raise NotImplementedError("odeint_rowwise: {} not supported for a recorded solve (differentiable=True with "
+                                      "grad mode on)".format(", ".join(given) + (" is" if len(given) == 1 else " are")))
         self.nfe = 0
         # compact: the original indices of the rows now carried (int64, ascending, on the state's device) — func's third
         # argument — and what the two extra stats count
@@ -361,12 +464,27 @@ class HostRowKernels:
         self.n_rej = np.zeros(B, dtype=np.int64)
         self.code = np.zeros(B, dtype=np.int64)
         self.tg = p.tgrid.numpy()
+        # the step options: the bounds per row, the two point tables with each row's index, and of the prepared step
+        # where it was cut (`on_point`: 0 not, 1 at a step point, 2 at a jump point; `clip_t`: the point)
+        self.min_r = np.full(B, p.min_step) if p.min_rows is None else p.min_rows.copy()
+        self.max_r = np.full(B, p.max_step) if p.max_rows is None else p.max_rows.copy()
+        self.step_tab, self.step_cnt, self.step_next = self._table(p.step_points)
+        self.jump_tab, self.jump_cnt, self.jump_next = self._table(p.jump_points)
+        self.clip_t = np.zeros(B)
+        self.on_point = np.zeros(B, dtype=np.int64)
+        self.jumped = np.zeros(B, dtype=bool)
         # record mode: [B] fp64 graphs of the first step sizes (initial-step heuristic) and, from the second trial step
         # on, of the time every later step of the row is anchored to (t0 + dt_first for a row whose first step was accepted)
         self.s_shadow = None
         self.anchor = None
 
     # -- helpers ------------------------------------------------------------------------------------------------------
+    @staticmethod
+    def _table(pts):
+        if pts is None:
+            return None, None, None
+        return pts.table.copy(), pts.count.astype(np.int64), pts.next.astype(np.int64)
+
     def _coef(self, coef: float, dts: torch.Tensor) -> torch.Tensor:
         return torch.tensor(coef, dtype=self.p.dtype) * dts
 
@@ -388,7 +506,7 @@ class HostRowKernels:
         m, T = self.p.method, self.T
         t0, dt = self.t0[r], self.dt[r]
         if m.alpha_is_one[i]:
-            t1 = T(t0 + dt)
+            t1 = T(self.clip_t[r] if self.on_point[r] else t0 + dt)       # a cut step: the point itself
             tt = nextafter(t1, t1 - 1)
         else:
             tt = T(t0) + m.alpha[i] * T(dt)
@@ -403,17 +521,27 @@ class HostRowKernels:
         return list(torch.tensor(out, dtype=p.dtype).unbind(0))
 
     def prepare(self, r: int) -> None:
-        dt = self.dt[r]
+        dt, t0 = self.dt[r], self.t0[r]
         if not math.isfinite(dt):
-            dt = 0.0
-        dt = max(dt, 0.0)
-        self.dt[r] = dt
+            dt = self.min_r[r]
+        dt = _clamp(dt, self.min_r[r], self.max_r[r])
         code = 3 if self.bad_y[r] else 0
-        if not self.t0[r] + dt > self.t0[r]:
+        if not t0 + dt > t0:
             code = 1
         if self.since[r] >= self.p.max_num_steps:
             code = 2
         self.code[r] = code
+        # the step cut short at the row's next step point, then at its next jump point, which wins (rk_common.py:289-309)
+        on = 0
+        for kind, tab, cnt, nxt in ((1, self.step_tab, self.step_cnt, self.step_next),
+                                    (2, self.jump_tab, self.jump_cnt, self.jump_next)):
+            if tab is not None and cnt[r] >= 1:
+                pt = tab[nxt[r], r]
+                if t0 < pt < t0 + dt:
+                    on, dt = kind, pt - t0
+                    self.clip_t[r] = pt
+        self.on_point[r] = on
+        self.dt[r] = dt
 
     # -- what the driver calls besides the two steps -------------------------------------------------------------------
     def begin_recording(self, sol, y) -> None:
@@ -438,7 +566,8 @@ class HostRowKernels:
         self.all_acc[self.row_map], self.all_rej[self.row_map] = self.n_acc, self.n_rej
         return torch.from_numpy(self.all_acc.copy()), torch.from_numpy(self.all_rej.copy())
 
-    _ROW_VECTORS = ("t0", "tprev", "dt", "active", "since", "next_out", "bad_y", "n_acc", "n_rej", "code")
+    _ROW_VECTORS = ("t0", "tprev", "dt", "active", "since", "next_out", "bad_y", "n_acc", "n_rej", "code", "min_r", "max_r",
+                    "clip_t", "on_point", "jumped", "step_cnt", "step_next", "jump_cnt", "jump_next")
 
     def repack(self, y, f0, n_keep: int):
         """Carry on with the `n_keep` active rows only, in their order: (y, f0) of those rows."""
@@ -450,8 +579,12 @@ class HostRowKernels:
         keep = np.flatnonzero(self.active)
         assert len(keep) == n_keep
         for name in self._ROW_VECTORS:
-            setattr(self, name, getattr(self, name)[keep])
+            if getattr(self, name) is not None:
+                setattr(self, name, getattr(self, name)[keep])
         self.tg = self.tg[:, keep]
+        for name in ("step_tab", "jump_tab"):
+            if getattr(self, name) is not None:
+                setattr(self, name, getattr(self, name)[:, keep])
         self.row_map = self.row_map[keep]
         idx = torch.from_numpy(keep)
         if self.hook is not None:
@@ -538,19 +671,28 @@ class HostRowKernels:
             bad = ((~torch.isfinite(y)) | (~torch.isfinite(y1))).sum(dim=1).numpy()
         accepted = []
         n_out = self.tg.shape[0]
+        self.jumped[:] = False
         with np.errstate(all="ignore"):
             for r in range(self.n):
                 if not self.active[r]:
                     continue
                 ratio = float(T(math.sqrt(sums[r] / p.L)))
                 dt = self.dt[r]
-                accept = bool(dt <= 0.0 or ratio <= 1)
-                dt_next = optimal_step_size(dt, ratio, p.safety, p.ifactor, p.dfactor, m.order)
-                if dt_next == dt_next:
-                    dt_next = max(dt_next, 0.0)          # the clamp to [min_step, max_step] = [0, inf]; NaN stays
+                # rk_common.py:324-332: the error decides, but a step above the ceiling is never taken and one at the
+                # floor always
+                accept = bool(dt <= self.min_r[r] or (ratio <= 1 and not dt > self.max_r[r]))
+                dt_next = _clamp(optimal_step_size(dt, ratio, p.safety, p.ifactor, p.dfactor, m.order), self.min_r[r],
+                                 self.max_r[r])
                 self.since[r] += 1
                 if accept:
-                    t1 = self.t0[r] + dt
+                    on = self.on_point[r]
+                    t1 = self.clip_t[r] if on else self.t0[r] + dt      # a cut step ends on the point's own bits
+                    if on == 1 and self.step_next[r] != self.step_cnt[r] - 1:
+                        self.step_next[r] += 1
+                    if on == 2:
+                        if self.jump_next[r] != self.jump_cnt[r] - 1:
+                            self.jump_next[r] += 1
+                        self.jumped[r] = True
                     self.tprev[r], self.t0[r] = self.t0[r], t1
                     self.n_acc[r] += 1
                     lo = hi = int(self.next_out[r])
@@ -581,6 +723,24 @@ class HostRowKernels:
         if stopped is not None:
             self.active[stopped.numpy().astype(bool)] = False
         return y, f0
+
+    @property
+    def n_jumped(self) -> int:
+        """The rows whose accepted step of the last trial step ended on a jump point."""
+        return int(self.jumped.sum())
+
+    def refresh_after_jump(self, y, f0):
+        """f0 of the rows that jumped <- func just after the point (rk_common.py:352, Perturb.NEXT), one call for the
+        carried batch: every other row is evaluated at its frozen time and its f0 keeps its bits."""
+        p, T = self.p, self.T
+        t_rows = np.empty(self.n)
+        for r in range(self.n):
+            t0 = T(self.t0[r])
+            t_rows[r] = float(T(p.sign) * (nextafter(t0, t0 + 1) if self.jumped[r] else t0))
+        f_new = p.call(torch.tensor(t_rows, dtype=p.dtype), y)
+        rows = torch.from_numpy(np.flatnonzero(self.jumped))
+        f0[rows] = f_new[rows]
+        return f0
 
     def deactivate_rows(self, mask: torch.Tensor) -> None:
         """Before the initial step: the rows of `mask` (bool [B]) never start."""
@@ -704,7 +864,11 @@ class HipRowKernels:
         self.code = torch.zeros(B, **i32)
         self.n_acc = torch.zeros(B, dtype=torch.int64, device=dev)
         self.n_rej = torch.zeros(B, dtype=torch.int64, device=dev)
-        self.status = torch.zeros(2, **i32)
+        # per-row bounds or points: the controller variant (`tdeq_row_control_points`), whose status has a third word
+        self.pts = self._row_points(f64, i32) if (p.min_rows is not None or p.step_points is not None
+                                                   or p.jump_points is not None) else None
+        self.n_jumped = 0
+        self.status = torch.zeros(2 if self.pts is None else 3, **i32)
         self.nch = self.k.row_partials(p.L, p.dtype)
         self.part = torch.empty(3 * B * self.nch, **f64)
         st = _native.RowState()
@@ -716,7 +880,9 @@ class HipRowKernels:
         st.n_out, st.order = self.tg.shape[0], p.method.order - 1
         self.st = st
         m = p.method
-        self.ctrl = _native.step_ctrl(m.alpha, m.alpha_is_one, m.order, p.safety, p.ifactor, p.dfactor, 0.0, math.inf,
+        # (scalar bounds ride in the block every controller launch takes; with per-row bounds these two are not read)
+        lo, hi = (0.0, math.inf) if p.min_rows is not None else (p.min_step, p.max_step)
+        self.ctrl = _native.step_ctrl(m.alpha, m.alpha_is_one, m.order, p.safety, p.ifactor, p.dfactor, lo, hi,
                                       p.sign, n_norm_seg=1)
         self.plan = launch_plan(m.name)
         self.dts = None
@@ -726,6 +892,30 @@ class HipRowKernels:
         # a recorded solve (differentiable=True): every launch below is handed to the recorder and becomes a graph node
         self.rec = rad.RowRecorder(self.k, p, _row_sum) if p.record else None
 
+    _POINT_VECTORS = ("step_count", "jump_count", "next_step", "next_jump", "clip_t", "on_point", "min_step", "max_step",
+                      "jumped")
+
+    def _row_points(self, f64, i32) -> _native.RowPoints:
+        """The vectors and tables of `tdeq_row_points` as attributes `pt_<field>` (None: absent), and the block."""
+        p, B = self.p, self.p.B
+        for kind, src in (("step", p.step_points), ("jump", p.jump_points)):
+            for field, val, kw in ((f"{kind}_t", "table", f64), (f"{kind}_count", "count", i32), (f"next_{kind}", "next", i32)):
+                setattr(self, "pt_" + field, None if src is None else torch.as_tensor(getattr(src, val), **kw).contiguous())
+        self.pt_min_step = None if p.min_rows is None else torch.as_tensor(p.min_rows, **f64)
+        self.pt_max_step = None if p.max_rows is None else torch.as_tensor(p.max_rows, **f64)
+        self.pt_clip_t = torch.zeros(B, **f64)
+        self.pt_on_point, self.pt_jumped = torch.zeros(B, **i32), torch.zeros(B, **i32)
+        pts = _native.RowPoints()
+        pts.n_step = 0 if self.pt_step_t is None else self.pt_step_t.shape[0]
+        pts.n_jump = 0 if self.pt_jump_t is None else self.pt_jump_t.shape[0]
+        self._point_pointers(pts)
+        return pts
+
+    def _point_pointers(self, pts) -> None:
+        for field in self._POINT_VECTORS + ("step_t", "jump_t"):
+            vec = getattr(self, "pt_" + field)
+            setattr(pts, field, None if vec is None else vec.data_ptr())
+
     def begin_recording(self, sol, y) -> None:
         self.rec.sol_rows = [y] + [None] * (sol.shape[0] - 1)
 
@@ -733,7 +923,8 @@ class HipRowKernels:
         return torch.stack(self.rec.sol_rows)          # (each row is the raw solution row's storage: same bits)
 
     def poll(self):
-        n_active, r = self.status.tolist()                   # the two words the host reads per trial step
+        n_active, r, *more = self.status.tolist()            # the words the host reads per trial step: two, or three
+        self.n_jumped = more[0] if more else 0               # (per-row bounds or points: the rows that jumped)
         # (a hook that stops rows: a row the controller found in error may have fired and left in the same trial step — its
         #  error wins.  Safe because every control launch (`tdeq_row_control`) first resets both words to {0, no error row},
         #  so status[1] can only name a row of THIS launch, never a stale one; pinned by
@@ -777,6 +968,14 @@ class HipRowKernels:
         self.tg = self.tg.index_select(1, keep)
         st.tgrid = self.tg.data_ptr()
         self.dts, self.times = self.dts.index_select(0, keep), self.times.index_select(1, keep)
+        if self.pts is not None:
+            for field in self._POINT_VECTORS:
+                if getattr(self, "pt_" + field) is not None:
+                    setattr(self, "pt_" + field, getattr(self, "pt_" + field).index_select(0, keep))
+            for field in ("step_t", "jump_t"):
+                if getattr(self, "pt_" + field) is not None:
+                    setattr(self, "pt_" + field, getattr(self, "pt_" + field).index_select(1, keep).contiguous())
+            self._point_pointers(self.pts)
         st.n_rows = self.n = n_keep
         if self.hook is not None:
             self.hook.keep_rows(keep)
@@ -788,8 +987,21 @@ class HipRowKernels:
         p = self.p
         dts = torch.empty(self.n, dtype=p.dtype, device=p.device)
         times = torch.empty(p.method.n_stages, self.n, dtype=p.dtype, device=p.device)
-        self.k.row_control(mode, self.part, self.ctrl, self.st, dts, times, p.dtype)
+        if self.pts is None:
+            self.k.row_control(mode, self.part, self.ctrl, self.st, dts, times, p.dtype)
+        else:
+            # (mode 0 also writes the [n] times of the evaluation that follows a step onto a jump point)
+            self.jump_times = torch.empty(self.n, dtype=p.dtype, device=p.device)
+            self.pts.jump_times = self.jump_times.data_ptr()
+            self.k.row_control_points(mode, self.part, self.ctrl, self.st, self.pts, dts, times, p.dtype)
         self.dts, self.times = dts, times
+
+    def refresh_after_jump(self, y, f0):
+        """f0 of the rows that jumped <- func just after the point, one call for the carried batch at the times the
+        controller wrote; `tdeq_row_select` takes the rows that jumped and reads nothing of the others."""
+        f_new = self.p.call(self.jump_times, y)
+        self.k.row_select(f0, f_new, self.pt_jumped)
+        return f0
 
     def _reduce(self, mode: int, y0, y1, partial, ks, coefs, dts, active) -> None:
         """The row reduction into `part`: with the two scalar tolerances, or with the [n] vectors of the rows now carried
@@ -906,6 +1118,8 @@ def _solve(p: _Problem, y_start, f0, sol, hook=None, never_start=None):
             n_active, failure = kern.poll()
             if failure is not None:
                 p.raise_row_error(failure, y)
+            if p.jump_points is not None and kern.n_jumped:
+                f0 = kern.refresh_after_jump(y, f0)          # a step ended on a jump point: f0 from its far side
             if n_active == 0:
                 break
             if p.compact is not None and n_active < y.shape[0] and n_active <= p.compact * y.shape[0]:
@@ -939,9 +1153,23 @@ def odeint_rowwise(func, y0, t, *, rtol=1e-7, atol=1e-9, method="dopri5", option
     accepted step and is still evaluated there; its output is ignored (NaN or Inf included).
 
     Methods: dopri5, bosh3, tsit5, fehlberg2, adaptive_heun, dopri8.  Options: `first_step` (scalar or `[B]`),
-    `safety`, `ifactor`, `dfactor`, `max_num_steps` (per row).  Everything else raises ValueError.  Error norm per
+    `safety`, `ifactor`, `dfactor`, `max_num_steps` (per row), and the step options below.  Everything else raises
+    ValueError.  Error norm per
     row: the RMS over the row's elements of err / (atol + rtol * max(|y0|, |y1|)) — `odeint`'s norm for a one-row
     state — and the reference's controller per row.
+
+    Step options, the reference's row by row (rk_common.py:223-241, 266-361), quirks included.  `min_step`, `max_step`: a
+    number, a 0-dim tensor or a real `[B]` vector in the forms of the tolerances (defaults 0 and inf, not validated): the
+    bounds of `dt_r`; a step at the floor is always accepted, one above the ceiling never.  `step_t`, `jump_t`: real times
+    `[K]` (shared) or `[K, B]` (a column per row) in TRUE time — a tensor on any device, a numpy array or a list; `K = 0`
+    means absent, a NaN entry is padding.  Row r must end a step on each of its points: points before `t0_r` are dropped, a
+    value that occurs twice in the row's two lists raises ValueError naming the row, a trial step that would pass the
+    row's next point `p` (`t0 < p < t0 + dt`) is cut short and, accepted, ends at `p` exactly; a point hit exactly is not
+    cut and the row's index stays on it.  After an accepted step onto a jump point `func` is called once more for the
+    carried batch — `t_rows[r]` the next representable time behind the point for the rows that jumped, the frozen time of
+    every other row — and `f0` of the rows that jumped is taken from it (the other rows' output is ignored, NaN included);
+    `nfe` counts the call.  Row r has the bits and counts of the one-row solve with column r.  With `differentiable=True`
+    and grad mode on any of the four raises NotImplementedError.
 
     `rtol` and `atol` are each a number (or a one-element tensor), or a per-row vector with exactly `B = y0.shape[0]`
     entries: a 1-D tensor of any real dtype on any device, a 1-D numpy array, a list or a tuple of numbers.  Row r is then

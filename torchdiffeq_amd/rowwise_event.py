@@ -245,7 +245,8 @@ def odeint_rowwise_event(func, y0, t0, *, event_fn, t_end=None, rtol=1e-7, atol=
     stage times in the state's dtype).  `t0` is a number, a 0-dim tensor or a `[B]` tensor.  `t_end` is None (increasing
     time, no end), a number or a `[B]` tensor; it must differ from `t0` in every row, in the same direction for all rows
     (`t_end < t0`: decreasing time), else ValueError.  `rtol`, `atol` (numbers or `[B]` vectors), `method` and `options`
-    (`first_step`, `safety`, `ifactor`, `dfactor`, `max_num_steps`) are those of `odeint_rowwise`.
+    (`first_step`, `safety`, `ifactor`, `dfactor`, `max_num_steps`, `min_step`, `max_step`, `step_t`, `jump_t`) are those of
+    `odeint_rowwise`; the event of a step onto a jump point is tested before `f0` is re-evaluated behind it.
 
     `event_fn(t_rows [b], y [b, *row_shape]) -> [b]` returns one real value per row on the state's device; it always gets
     TRUE time (also for decreasing time), in the state's dtype, and is called under `torch.no_grad()`; its value is cast
