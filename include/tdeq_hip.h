@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define TDEQ_ABI_VERSION 29
+#define TDEQ_ABI_VERSION 30
 #define TDEQ_F32 0
 #define TDEQ_F64 1
 /* interleaved (re, im) complex states — accepted by the NORM entry points only (tdeq_error_norm, tdeq_error_norm_partial[_ctrl],
@@ -767,6 +767,20 @@ int tdeq_row_dense_search(const double* tq, int64_t n_q, const int64_t* offsets,
  * tdeq_row_select          dst[r, e] = src[r, e] for the rows with mask[r] != 0 (int32 [n_rows]), e < row_len: a copy of
  *                          bits; no other row is read or written.  16-byte elements when row_len is a multiple of
  *                          16 / sizeof(T) and both bases are 16-byte aligned, scalar elements otherwise.
+ * State impulses at jump points (ABI 30; `jump_dy` of the rowwise family):
+ * tdeq_row_control_points  with pts->jump_hit != NULL the jump table is tested with t0 < p <= t0 + dt: a prepared step
+ *                          that lands on the point exactly is a step onto it: on_point 2, clip_t = p, dt[r] unchanged
+ *                          (p - t0 may round above dt and above max_step); step_t keeps the open test.  Mode 0 writes
+ *                          jump_hit[r] = next_jump[r] before it is moved on, for the rows with jumped[r] only.
+ *                          jump_hit and jump_closed = 1 go together, and both need jump_t: one without the other, or
+ *                          without the table, is TDEQ_EINVAL.  With both zero (the zeroed tail of an ABI-29 block)
+ *                          every output is that of ABI 29.
+ * tdeq_row_impulse         for the rows with jumped[r] != 0: o = row_map ? row_map[r] : r, k = dy_index[jump_hit[r] * n_orig
+ *                          + o]; k >= 0: y[r, e] += dy[(k * dy_rows + (dy_rows == 1 ? 0 : o)) * row_len + e], one addition in
+ *                          the state's type.  dy_index is int32 [K', n_orig] (sorted position of a point in the row's column
+ *                          -> the caller's k; -1: none), dy_rows is 1 or n_orig, row_map NULL for a batch that was never
+ *                          compacted.  No other row of y or dy is read or written.  16-byte elements when row_len is a
+ *                          multiple of 16 / sizeof(T) and y and dy are 16-byte aligned, scalar elements otherwise.
  * 64-bit offsets.  A NULL pointer other than those named, a negative size or a dtype other than TDEQ_F32 / TDEQ_F64:
  * TDEQ_EINVAL before any launch.  n_rows == 0: no-op (the status words are still reset).
  */
@@ -785,12 +799,17 @@ typedef struct tdeq_row_points {
     void* jump_times;           /* [n_rows] of the state type, mode 0                                   */
     int32_t n_step;             /* rows of the step_t table                                             */
     int32_t n_jump;
+    int32_t* jump_hit;          /* [n_rows] or NULL: mode 0, position of the jump point a row ended on  */
+    int32_t jump_closed;        /* 1 with jump_hit: the jump table is tested with p <= t0 + dt          */
 } tdeq_row_points;
 
 int tdeq_row_control_points(int mode, const double* part, const tdeq_step_ctrl* ctrl, const tdeq_row_state* st,
                             const tdeq_row_points* pts, void* dts_out, void* times_out, int dtype, void* stream);
 int tdeq_row_select(void* dst, const void* src, const int32_t* mask, int64_t n_rows, int64_t row_len, int dtype,
                     void* stream);
+int tdeq_row_impulse(void* y, const void* dy, int64_t dy_rows, const int32_t* dy_index, int64_t n_orig,
+                     const int32_t* jump_hit, const int32_t* jumped, const int32_t* row_map /* or NULL */, int64_t n_rows,
+                     int64_t row_len, int dtype, void* stream);
 
 #ifdef __cplusplus
 }

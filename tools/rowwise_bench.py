@@ -14,6 +14,9 @@ on a mixed-stiffness batch.
     python tools/rowwise_bench.py --event-compact-summary lines.jsonl[,parent_event.jsonl,new_event.jsonl]
                                   --out profiles/rowwise_event_compact_bench.json
     python tools/rowwise_bench.py --dense [--reps 5] [--out dense.json]
+    python tools/rowwise_bench.py --impulse [--reps 3] [--out profiles/rowwise_impulse_bench.json]
+    python tools/rowwise_bench.py --impulse-summary impulse.json,parent_event.jsonl,new_event.jsonl,parent_dense.jsonl,
+                                  new_dense.jsonl,parent_bench.jsonl,new_bench.jsonl --out profiles/rowwise_impulse_bench.json
     python tools/rowwise_bench.py --dense-summary dense.json,parent_event.jsonl,new_event.jsonl,parent_bench.jsonl,new_bench.jsonl
                                   --out profiles/rowwise_dense_bench.json
 
@@ -51,6 +54,10 @@ at the row's point): the solve with `jump_t` against the same func without it (w
 ms per trial step, the refresh calls and — from one instrumented solve, synchronised on both sides — ms per refresh; and the
 achieved rate of `tdeq_row_select` on the whole state (every row selected: 1 read + 1 write per element) against the HBM
 peak.
+
+`--impulse`: the `--steps` shape with one bolus per row (`jump_dy`, func y @ A.T): the solve against the same solve with
+`jump_t` alone, trial steps and refresh calls, and `tdeq_row_impulse` alone — every row selected and 1 row in 64 — next to
+`tdeq_row_select` on the same state (3 words per touched element against 2).
 
 `--grad`: forward + backward of a `differentiable=True` solve per trial step at the headline, next to plain `odeint`
 backprop of the same state, and (`--parity`) the per-row deviations of the rowwise gradients from the reference's
@@ -184,6 +191,85 @@ def _steps(reps: int):
         res["row_select"] = {"shape": [B, D], "ms": ms, "TB_per_s": tbs, "fraction_of_peak": tbs / PEAK_TBS,
                              "note": "2 x 33.5 MB per launch: the state fits the 256 MB last-level cache, so the rate is not "
                                      "bounded by HBM alone"}
+    res["shape"] = [B, D]
+    return res
+
+
+def _impulse(reps: int):
+    """The `--steps` problem with one bolus per row at the row's own time: ms per solve with `jump_dy` against `jump_t`
+    alone, trial steps and refresh calls, and `tdeq_row_impulse` alone (every row, and 1 row in 64) next to
+    `tdeq_row_select` on the same state."""
+    import torchdiffeq_amd as tda
+    from torchdiffeq_amd import _native
+    dev = torch.device("cuda", 0)
+    B, D = 65536, 128
+    g = torch.Generator().manual_seed(0)
+    G = torch.randn(D, D, generator=g, dtype=torch.float64) / D ** 0.5
+    A = (0.5 * (G - G.T) - 0.1 * torch.eye(D, dtype=torch.float64)).float().to(dev)
+    y0 = torch.randn(B, D, generator=g).to(dev)
+    tj = (0.1 + 0.3 * torch.rand(B, generator=g, dtype=torch.float64))
+    dose = torch.randn(1, B, D, generator=g).to(dev)
+    t = torch.tensor([0.0, 0.5], device=dev)
+
+    def f(t_, y):
+        return y @ A.T
+    settings = (("jump_t_alone", {"jump_t": tj[None, :]}), ("with_jump_dy", {"jump_t": tj[None, :], "jump_dy": dose}))
+    res = {name: {"ms_per_solve": []} for name, _ in settings}
+    med = lambda v: sorted(v)[len(v) // 2]       # noqa: E731
+    from torchdiffeq_amd import rowwise
+    refreshes = [0]
+    plain_refresh = rowwise.HipRowKernels.refresh_after_jump
+
+    def counted(self, y, f0):                     # (counts only: no synchronisation is added to the timed solves)
+        refreshes[0] += 1
+        return plain_refresh(self, y, f0)
+    rowwise.HipRowKernels.refresh_after_jump = counted
+    with torch.no_grad():
+        for rep in range(reps + 1):
+            for name, options in settings:
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                refreshes[0] = 0
+                _, st = tda.odeint_rowwise(f, y0, t, rtol=1e-7, atol=1e-9, options=options, return_stats=True)
+                torch.cuda.synchronize()
+                if rep:                       # the first round warms up
+                    res[name]["ms_per_solve"].append((time.perf_counter() - t0) * 1e3)
+                trials = st["n_accepted"] + st["n_rejected"]
+                res[name].update(nfe=st["nfe"], trial_steps=int(trials.max()), trials_median=float(trials.median()),
+                                 refresh_calls=refreshes[0])
+                if "n_impulses" in st:
+                    res[name]["n_impulses_total"] = int(st["n_impulses"].sum())
+        rowwise.HipRowKernels.refresh_after_jump = plain_refresh
+        for name, _ in settings:
+            res[name]["ms_per_solve_median"] = med(res[name]["ms_per_solve"])
+        # the two kernels alone on the whole state
+        kern = _native.get_kernels(dev, torch.float32)
+        index = torch.zeros(1, B, dtype=torch.int32, device=dev)
+        hit = torch.zeros(B, dtype=torch.int32, device=dev)
+        every = torch.ones(B, dtype=torch.int32, device=dev)
+        sparse = (torch.arange(B, device=dev) % 64 == 0).to(torch.int32)
+        y, src = y0.clone(), y0.clone()
+
+        def rate(launch, words, rows):
+            for _ in range(3):
+                launch()
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+            n = 20
+            ev[0].record()
+            for _ in range(n):
+                launch()
+            ev[1].record()
+            torch.cuda.synchronize()
+            ms = ev[0].elapsed_time(ev[1]) / n
+            tbs = words * rows * D * 4 / (ms * 1e-3) / 1e12
+            return {"ms": ms, "rows_touched": rows, "words_per_touched_element": words, "TB_per_s": tbs,
+                    "fraction_of_peak": tbs / PEAK_TBS}
+        res["row_impulse_all_rows"] = rate(lambda: kern.row_impulse(y, dose, index, hit, every), 3, B)
+        res["row_impulse_1_in_64"] = rate(lambda: kern.row_impulse(y, dose, index, hit, sparse), 3, B // 64)
+        res["row_select_all_rows"] = rate(lambda: kern.row_select(y, src, every), 2, B)
+        res["row_impulse_over_row_select_ms"] = res["row_impulse_all_rows"]["ms"] / res["row_select_all_rows"]["ms"]
+        res["note"] = ("3 x 33.5 MB per launch with every row selected: the state fits the 256 MB last-level cache, so the "
+                       "rate is not bounded by HBM alone")
     res["shape"] = [B, D]
     return res
 
@@ -449,6 +535,38 @@ def _dense(reps: int, Q: int = 16):
             "eval": {"Q": Q, "ms_per_call": eval_ms, "median_ms": med(eval_ms), "bytes_moved": moved,
                      "achieved_TBs": moved / (med(eval_ms) * 1e-3) / 1e12, "hbm_peak_TBs": PEAK_TBS,
                      "search_alone_ms": search_ms, "search_alone_median_ms": med(search_ms), "all_finite": finite}}
+
+
+def _impulse_summary(paths, out):
+    """Fold the `--impulse` file with the JSON lines of alternated fresh processes of the parent tree and of this tree —
+    `--event` (plain rowwise solve and plain event solve), `--dense` and `bench.py --gpus 1 --steps 200 --warmup 20`; the
+    first line of every file is the warm-up round — and say whether this tree's medians lie inside the parent's spread."""
+    med = lambda v: sorted(v)[len(v) // 2]       # noqa: E731
+
+    def fold(vals):
+        return {"per_process": [round(v, 4) for v in vals], "median": round(med(vals), 4), "min": round(min(vals), 4),
+                "max": round(max(vals), 4)}
+
+    def pair(parent, new):
+        p, n = fold(parent), fold(new)
+        return {"parent": p, "new": n, "new_median_inside_parent_min_max": p["min"] <= n["median"] <= p["max"],
+                "new_median_not_above_parent_max": n["median"] <= p["max"]}      # (every figure: lower is better)
+    lines = lambda path: [json.loads(x) for x in open(path) if x.strip().startswith("{")][1:]      # noqa: E731
+    res = json.load(open(paths[0]))
+    pe, ne, pd, nd, pb, nb = (lines(path) for path in paths[1:7])
+    res["paths_without_the_option_against_parent"] = {
+        "what": "parent commit and this tree alternated in fresh processes in one session, the first round of processes "
+                "dropped: tools/rowwise_bench.py --event --reps 3 (func y @ A.T), tools/rowwise_bench.py --dense --reps 3 and "
+                "bench.py --gpus 1 --steps 200 --warmup 20",
+        "plain_rowwise_ms_per_trial": pair([r["plain"]["median_ms_per_trial"] for r in pe],
+                                           [r["plain"]["median_ms_per_trial"] for r in ne]),
+        "rowwise_event_ms_per_solve": pair([r["event"]["median_ms_per_solve"] for r in pe],
+                                           [r["event"]["median_ms_per_solve"] for r in ne]),
+        "rowwise_dense_ms_per_solve": pair([r["dense"]["dense_median_ms"] for r in pd],
+                                           [r["dense"]["dense_median_ms"] for r in nd]),
+        "bench_ms_per_step": pair([r["ms_per_step"] for r in pb], [r["ms_per_step"] for r in nb])}
+    json.dump(res, open(out, "w"), indent=1)
+    print(json.dumps(res["paths_without_the_option_against_parent"]))
 
 
 def _dense_summary(paths, out):
@@ -727,7 +845,23 @@ def main():
     ap.add_argument("--dense", action="store_true")
     ap.add_argument("--steps", action="store_true")
     ap.add_argument("--dense-summary", default=None)
+    ap.add_argument("--impulse", action="store_true")
+    ap.add_argument("--impulse-summary", default=None)
     a = ap.parse_args()
+    if a.impulse_summary:
+        _impulse_summary(a.impulse_summary.split(","), a.out)
+        return
+    if a.impulse:
+        res = {"device": torch.cuda.get_device_name(0), "arch": torch.cuda.get_device_properties(0).gcnArchName,
+               "what": "tools/rowwise_bench.py --impulse: 65536 x 128 fp32 dopri5, func y @ A.T, one bolus per row at tj_r in "
+                       "(0.1, 0.4), t = [0, 0.5], rtol 1e-7, atol 1e-9; one process, the two solves alternated, the first "
+                       "pair a warm-up",
+               "impulse": _impulse(a.reps)}
+        print(json.dumps(res))
+        if a.out:
+            os.makedirs(os.path.dirname(a.out) or ".", exist_ok=True)
+            json.dump(res, open(a.out, "w"), indent=1)
+        return
     if a.dense_summary:
         _dense_summary(a.dense_summary.split(","), a.out)
         return

@@ -18,7 +18,7 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-TDEQ_ABI_VERSION = 29
+TDEQ_ABI_VERSION = 30
 TDEQ_F32, TDEQ_F64 = 0, 1
 TDEQ_C64, TDEQ_C128 = 2, 3        # interleaved complex: the norm entry points only (include/tdeq_hip.h)
 TDEQ_BF16, TDEQ_F16 = 4, 5        # reduced-precision states: the entry points of the host-driven step (LowPrecisionHipKernels)
@@ -87,7 +87,8 @@ class RowPoints(ctypes.Structure):
     _fields_ = [(name, ctypes.c_void_p) for name in ("step_t", "jump_t", "step_count", "jump_count", "next_step",
                                                       "next_jump", "clip_t", "on_point", "min_step", "max_step", "jumped",
                                                       "jump_times")] + \
-               [("n_step", ctypes.c_int32), ("n_jump", ctypes.c_int32)]
+               [("n_step", ctypes.c_int32), ("n_jump", ctypes.c_int32)] + \
+               [("jump_hit", ctypes.c_void_p), ("jump_closed", ctypes.c_int32)]     # (ABI 30, `jump_dy`; zero: absent)
 
 
 # name -> (restype, argtypes); the authoritative list of exported symbols (checked by the tests).
@@ -289,6 +290,10 @@ ABI_SIGNATURES = {
                                                ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
     "tdeq_row_select": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
                                        ctypes.c_int, ctypes.c_void_p]),
+    # state impulses at jump points (ABI 30, `jump_dy`)
+    "tdeq_row_impulse": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64,
+                                        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
+                                        ctypes.c_int, ctypes.c_void_p]),
 }
 
 
@@ -946,6 +951,17 @@ class HipKernels:
             return
         _check(self.lib.tdeq_row_select(dst.data_ptr(), src.data_ptr(), mask.data_ptr(), dst.shape[0], dst.shape[1],
                                         dtype_code(dst.dtype), self._stream()), "tdeq_row_select")
+
+    def row_impulse(self, y, dy, dy_index, jump_hit, jumped, row_map=None) -> None:
+        """tdeq_row_impulse: y[r, :] += dy[k, o or 0, :] for the rows with jumped[r] != 0, o = row_map[r] (None: r), k =
+        dy_index[jump_hit[r], o] when >= 0.  `y` [n, L], `dy` [K, B or 1, L] of y's dtype, `dy_index` int32 [K', B], the
+        three row vectors int32 [n]; all on the device."""
+        if y.shape[0] == 0:
+            return
+        _check(self.lib.tdeq_row_impulse(y.data_ptr(), dy.data_ptr(), dy.shape[1], dy_index.data_ptr(), dy_index.shape[1],
+                                         jump_hit.data_ptr(), jumped.data_ptr(),
+                                         None if row_map is None else row_map.data_ptr(), y.shape[0], y.shape[1],
+                                         dtype_code(y.dtype), self._stream()), "tdeq_row_impulse")
 
     def row_dense_commit(self, sol, y0, y1, f0, f1, ks, coefs, dts, st: RowState) -> None:
         ptrs, cf, n = self._terms(ks, coefs)

@@ -446,15 +446,23 @@ int row_control_args(RowCtrlArgs& a, int mode, const double* part, const tdeq_st
     return 0;
 }
 
-template <typename T>
+template <typename T, bool IMPULSE>
 int row_control_points_launch(const RowCtrlPointsArgs& a, hipStream_t s) {
     if (a.base.nch > 1) {
         const dim3 grid((unsigned)((a.base.n_rows * kWave + kBlock - 1) / kBlock));
-        hipLaunchKernelGGL((row_ctrl_points_kernel<T, true>), grid, dim3(kBlock), 0, s, a);
+        hipLaunchKernelGGL((row_ctrl_points_kernel<T, true, IMPULSE>), grid, dim3(kBlock), 0, s, a);
     } else {
         const dim3 grid((unsigned)((a.base.n_rows + kBlock - 1) / kBlock));
-        hipLaunchKernelGGL((row_ctrl_points_kernel<T, false>), grid, dim3(kBlock), 0, s, a);
+        hipLaunchKernelGGL((row_ctrl_points_kernel<T, false, IMPULSE>), grid, dim3(kBlock), 0, s, a);
     }
+    return check_launch();
+}
+
+template <typename E>
+int row_impulse_launch(RowImpulseArgs& a, int64_t n_rows, int64_t row_len_e, hipStream_t s) {
+    a.row_len = row_len_e;
+    a.ne = n_rows * row_len_e;
+    hipLaunchKernelGGL((row_impulse_kernel<E>), dim3(stream_grid(a.ne, kBlock)), dim3(kBlock), 0, s, a);
     return check_launch();
 }
 
@@ -481,12 +489,13 @@ int tdeq_row_control(int mode, const double* part, const tdeq_step_ctrl* ctrl, c
     return dtype == TDEQ_F32 ? row_control_launch<float>(a, s) : row_control_launch<double>(a, s);
 }
 
-// ---- per-row step options: tdeq_row_control_points / tdeq_row_select ---------------------------------------------------
+// ---- per-row step options: tdeq_row_control_points / tdeq_row_select / tdeq_row_impulse -------------------------------
 int tdeq_row_control_points(int mode, const double* part, const tdeq_step_ctrl* ctrl, const tdeq_row_state* st,
                             const tdeq_row_points* pts, void* dts_out, void* times_out, int dtype, void* stream) {
     if (!pts || !pts->clip_t || !pts->on_point || !pts->jumped || !pts->jump_times) return TDEQ_EINVAL;
     if (pts->step_t && (pts->n_step < 1 || !pts->step_count || !pts->next_step)) return TDEQ_EINVAL;
     if (pts->jump_t && (pts->n_jump < 1 || !pts->jump_count || !pts->next_jump)) return TDEQ_EINVAL;
+    if ((pts->jump_hit != nullptr) != (pts->jump_closed != 0) || (pts->jump_hit && !pts->jump_t)) return TDEQ_EINVAL;
     hipStream_t s = static_cast<hipStream_t>(stream);
     RowCtrlPointsArgs a;
     bool launch;
@@ -509,7 +518,13 @@ int tdeq_row_control_points(int mode, const double* part, const tdeq_step_ctrl* 
     a.max_step = pts->max_step;
     a.jumped = pts->jumped;
     a.jump_times = pts->jump_times;
-    return dtype == TDEQ_F32 ? row_control_points_launch<float>(a, s) : row_control_points_launch<double>(a, s);
+    a.jump_hit = pts->jump_hit;
+    if (a.jump_hit) {                 // a solve with impulses: the closed rule for the jump table
+        return dtype == TDEQ_F32 ? row_control_points_launch<float, true>(a, s)
+                                 : row_control_points_launch<double, true>(a, s);
+    }
+    return dtype == TDEQ_F32 ? row_control_points_launch<float, false>(a, s)
+                             : row_control_points_launch<double, false>(a, s);
 }
 
 int tdeq_row_select(void* dst, const void* src, const int32_t* mask, int64_t n_rows, int64_t row_len, int dtype,
@@ -524,6 +539,31 @@ int tdeq_row_select(void* dst, const void* src, const int32_t* mask, int64_t n_r
     }
     return dtype == TDEQ_F32 ? row_select_launch<float>(dst, src, mask, n_rows, row_len, s)
                              : row_select_launch<double>(dst, src, mask, n_rows, row_len, s);
+}
+
+int tdeq_row_impulse(void* y, const void* dy, int64_t dy_rows, const int32_t* dy_index, int64_t n_orig,
+                     const int32_t* jump_hit, const int32_t* jumped, const int32_t* row_map, int64_t n_rows, int64_t row_len,
+                     int dtype, void* stream) {
+    if (!y || !dy || !dy_index || !jump_hit || !jumped || n_rows < 0 || row_len < 1 || !row_dtype_ok(dtype)) return TDEQ_EINVAL;
+    if (n_orig < 1 || (dy_rows != 1 && dy_rows != n_orig)) return TDEQ_EINVAL;
+    if (n_rows == 0) return 0;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    RowImpulseArgs a;
+    a.y = y;
+    a.dy = dy;
+    a.dy_index = dy_index;
+    a.jump_hit = jump_hit;
+    a.jumped = jumped;
+    a.row_map = row_map;
+    a.dy_rows = dy_rows;
+    a.n_orig = n_orig;
+    const int lv = row_lanes(row_len, dtype);
+    if (lv > 1 && aligned16(y) && aligned16(dy)) {
+        return dtype == TDEQ_F32 ? row_impulse_launch<VecOf<float>::type>(a, n_rows, row_len / lv, s)
+                                 : row_impulse_launch<VecOf<double>::type>(a, n_rows, row_len / lv, s);
+    }
+    return dtype == TDEQ_F32 ? row_impulse_launch<float>(a, n_rows, row_len, s)
+                             : row_impulse_launch<double>(a, n_rows, row_len, s);
 }
 
 int tdeq_row_dense_commit(void* sol, void* y0, const void* y1, void* f0, const void* f1, const void* const* k,

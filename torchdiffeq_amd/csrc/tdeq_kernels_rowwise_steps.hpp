@@ -9,6 +9,14 @@
 //                            point and the time vector of the one extra evaluation of func that follows.
 //   row_select_kernel        dst[r, :] = src[r, :] for the rows of a mask: how the re-evaluated f0 of the rows that jumped
 //                            is taken, and nothing of any other row.
+//   row_impulse_kernel       y[r, :] += dy[k, row, :] for the rows of the same mask (`jump_dy`): the state impulse of the jump
+//                            point the row's step ended on, k looked up from the position the controller reported.
+//
+// IMPULSE (a solve with `jump_dy`) is a compile-time flag of the controller, as ROWTOL is of the row reductions: false is the
+// kernel without it.  true tests the jump table with `t0 < p <= t0 + dt` — a step that lands on a point exactly is a step
+// onto it, or the row's index would stick there and the dose and every later one be lost; such a step keeps its dt (it ends
+// on the point's bits already) — and an accepted step onto a jump point writes jump_hit[r], the position of the point in the
+// row's sorted column.
 //
 // Modes 1, 2 and 3 run `row_control` for their norms and heuristics; what depends on the bounds, the points or the end of
 // an accepted step — mode 0 and the prepared step — is restated here on the `ctl_*` helpers, with the row's own bounds.
@@ -34,6 +42,7 @@ struct RowCtrlPointsArgs {
     const double* max_step;           // [n_rows]; null: hi
     int32_t* jumped;                  // [n_rows] mode 0, every row: the accepted step ended on a jump point
     void* jump_times;                 // [n_rows] of T, mode 0: sign * next_T(T(t0_r)) (ctl_next) where jumped, else sign * T(t0_r)
+    int32_t* jump_hit;                // [n_rows] IMPULSE, mode 0, rows that jumped: next_jump[r] before it moved on
 };
 
 // the next step size of the I-controller (misc.py:85-95) in host doubles, before the clamp: the expressions of row_control
@@ -53,17 +62,20 @@ __device__ __forceinline__ T row_stage_time_to(const tdeq_step_ctrl& c, double t
     return (T)c.time_sign * tt;
 }
 
-// the row's next point of one table inside the prepared step (t0, t0 + dt), or no cut (rk_common.py:292-296)
+// the row's next point of one table inside the prepared step (t0, t0 + dt), or no cut (rk_common.py:292-296); CLOSED:
+// inside (t0, t0 + dt]
+template <bool CLOSED = false>
 __device__ __forceinline__ bool row_point_inside(const double* table, const int32_t* count, const int32_t* next, int64_t r,
                                                  int64_t n_rows, double t0, double dt, double& p) {
     if (!table || count[r] < 1) return false;
     p = table[(int64_t)next[r] * n_rows + r];
+    if (CLOSED) return t0 < p && p <= t0 + dt;
     return t0 < p && p < t0 + dt;
 }
 
 // row_prepare with the row's bounds [lo, hi] (rk_common.py:266-287), then the prepared step cut short at the row's next
 // step point and at its next jump point, which wins (rk_common.py:289-309); returns code != 0
-template <typename T>
+template <typename T, bool IMPULSE>
 __device__ __forceinline__ bool row_prepare_points(const RowCtrlPointsArgs& a, int64_t r, double lo, double hi) {
     const RowCtrlArgs& b = a.base;
     const tdeq_step_ctrl& c = b.c;
@@ -86,10 +98,12 @@ __device__ __forceinline__ bool row_prepare_points(const RowCtrlPointsArgs& a, i
         t1 = p;
         dt = p - t0;
     }
-    if (row_point_inside(a.jump_t, a.jump_count, a.next_jump, r, b.n_rows, t0, dt, p)) {
+    if (row_point_inside<IMPULSE>(a.jump_t, a.jump_count, a.next_jump, r, b.n_rows, t0, dt, p)) {
         on = 2;
         t1 = p;
-        dt = p - t0;
+        // (a step that lands on the point keeps its size: p - t0 may round above dt, hence above max_step, and a step above
+        //  the ceiling is never accepted)
+        if (!IMPULSE || p < t0 + dt) dt = p - t0;
     }
     a.on_point[r] = on;
     if (on) {
@@ -103,7 +117,7 @@ __device__ __forceinline__ bool row_prepare_points(const RowCtrlPointsArgs& a, i
 }
 
 // row_control with the row's bounds and points; `jump`: the row's accepted step ended on a jump point
-template <typename T>
+template <typename T, bool IMPULSE>
 __device__ __forceinline__ void row_control_points(const RowCtrlPointsArgs& a, int64_t r, double s0, double s1, double sb,
                                                    bool& live, bool& err, bool& jump) {
     const RowCtrlArgs& b = a.base;
@@ -113,7 +127,7 @@ __device__ __forceinline__ void row_control_points(const RowCtrlPointsArgs& a, i
     if (b.mode != 0) {
         row_control<T>(b, r, s0, s1, sb, live, err);      // (modes 2, 3: its prepared step is replaced below)
         if (b.mode != 1) {
-            if (live) err = row_prepare_points<T>(a, r, lo, hi);
+            if (live) err = row_prepare_points<T, IMPULSE>(a, r, lo, hi);
             else a.on_point[r] = 0;
         }
         return;
@@ -150,6 +164,7 @@ __device__ __forceinline__ void row_control_points(const RowCtrlPointsArgs& a, i
             b.bad_y[r] = sb != 0.0 ? 1 : 0;
             if (on == 1 && a.next_step[r] != a.step_count[r] - 1) a.next_step[r] += 1;
             if (on == 2) {
+                if (IMPULSE) a.jump_hit[r] = a.next_jump[r];
                 if (a.next_jump[r] != a.jump_count[r] - 1) a.next_jump[r] += 1;
                 jump = true;
             }
@@ -163,7 +178,7 @@ __device__ __forceinline__ void row_control_points(const RowCtrlPointsArgs& a, i
         }
         b.dt[r] = dt_next;
         if (live) {
-            err = row_prepare_points<T>(a, r, lo, hi);
+            err = row_prepare_points<T, IMPULSE>(a, r, lo, hi);
         } else {
             row_freeze<T>(b, r);
             a.on_point[r] = 0;
@@ -174,7 +189,7 @@ __device__ __forceinline__ void row_control_points(const RowCtrlPointsArgs& a, i
 }
 
 // The lane-per-row and wave-per-row forms, the sums and the status protocol of row_ctrl_kernel, plus status[2].
-template <typename T, bool WAVE>
+template <typename T, bool WAVE, bool IMPULSE>
 __global__ __launch_bounds__(kBlock) void row_ctrl_points_kernel(const RowCtrlPointsArgs a) {
     const RowCtrlArgs& b = a.base;
     const int lane = threadIdx.x & (kWave - 1);
@@ -203,7 +218,7 @@ __global__ __launch_bounds__(kBlock) void row_ctrl_points_kernel(const RowCtrlPo
     }
     bool live = false, err = false, jump = false;
     if (r < b.n_rows && (!WAVE || lane == 0)) {
-        row_control_points<T>(a, r, s0, s1, sb, live, err, jump);
+        row_control_points<T, IMPULSE>(a, r, s0, s1, sb, live, err, jump);
         if (b.mode == 1) b.dt[r] = (double)(T)row_norm(s1, b.row_len, b.tkind);     // d1 for mode 2
         if (err) atomicMin(b.status + 1, (int32_t)r);
     }
@@ -231,6 +246,39 @@ __global__ __launch_bounds__(kBlock) void row_select_kernel(const RowSelectArgs 
     const int64_t stride = (int64_t)gridDim.x * kBlock;
     for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < a.ne; i += stride) {
         if (a.mask[i / a.row_len]) static_cast<E*>(a.dst)[i] = static_cast<const E*>(a.src)[i];
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Row impulse: y[r, :] += dy[k, o or 0, :] where jumped[r] != 0, with o = row_map[r] (null: r) the row's original index and
+// k = dy_index[jump_hit[r], o] the user's entry of the point the step ended on (k < 0: none).  One addition in the state's
+// type.  A row outside the mask is neither read nor written, and of `dy` only the rows that are added are read: 3 words per
+// element of a row that jumped, none for any other.
+// ------------------------------------------------------------------------------------------------
+struct RowImpulseArgs {
+    void* y;                          // [n_rows, row_len]
+    const void* dy;                   // [K, dy_rows, row_len]
+    const int32_t* dy_index;          // [K', n_orig]: sorted position -> k, -1 none
+    const int32_t* jump_hit;          // [n_rows]
+    const int32_t* jumped;            // [n_rows]
+    const int32_t* row_map;           // [n_rows] or null
+    int64_t dy_rows;                  // 1 or n_orig
+    int64_t n_orig;
+    int64_t row_len;                  // E units
+    int64_t ne;                       // n_rows * row_len
+};
+
+template <typename E>
+__global__ __launch_bounds__(kBlock) void row_impulse_kernel(const RowImpulseArgs a) {
+    const int64_t stride = (int64_t)gridDim.x * kBlock;
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < a.ne; i += stride) {
+        const int64_t r = i / a.row_len;
+        if (!a.jumped[r]) continue;
+        const int64_t o = a.row_map ? a.row_map[r] : r;
+        const int64_t k = a.dy_index[(int64_t)a.jump_hit[r] * a.n_orig + o];
+        if (k < 0) continue;
+        const int64_t src = (k * a.dy_rows + (a.dy_rows == 1 ? 0 : o)) * a.row_len + (i - r * a.row_len);
+        static_cast<E*>(a.y)[i] = static_cast<E*>(a.y)[i] + static_cast<const E*>(a.dy)[src];
     }
 }
 

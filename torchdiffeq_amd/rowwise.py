@@ -61,8 +61,9 @@ __all__ = ["odeint_rowwise"]
 
 _METHODS = {"dopri5": Dopri5Solver, "bosh3": Bosh3Solver, "tsit5": Tsit5Solver, "fehlberg2": Fehlberg2,
             "adaptive_heun": AdaptiveHeunSolver, "dopri8": Dopri8Solver}
-_OPTIONS = ("first_step", "safety", "ifactor", "dfactor", "max_num_steps", "min_step", "max_step", "step_t", "jump_t")
-_STEP_OPTIONS = ("min_step", "max_step", "step_t", "jump_t")
+_OPTIONS = ("first_step", "safety", "ifactor", "dfactor", "max_num_steps", "min_step", "max_step", "step_t", "jump_t",
+            "jump_dy")
+_STEP_OPTIONS = ("min_step", "max_step", "step_t", "jump_t", "jump_dy")
 _NO_ERROR_ROW = 0x7FFFFFFF
 
 
@@ -175,10 +176,50 @@ def _points(name: str, v, B: int) -> "np.ndarray | None":
     return np.ascontiguousarray(np.broadcast_to(a[:, None], (a.shape[0], B)) if a.ndim == 1 else a)
 
 
-def _row_points(step, jump, sign: float, t0: np.ndarray):
+def _impulses(v, jump, sign: float, t0: np.ndarray, y0: torch.Tensor) -> torch.Tensor:
+    """`jump_dy` -> a contiguous [K, B or 1, L] tensor of the state's dtype on its device, entry k the impulse of the
+    caller's `jump_t[k]` (`jump`: that table as `_points` returns it, [K, B] in the caller's time, or None)."""
+    B, row_shape = y0.shape[0], tuple(y0.shape[1:])
+    if jump is None:
+        raise ValueError("odeint_rowwise: jump_dy needs jump_t: one impulse for every entry of it")
+    try:
+        dy = v if isinstance(v, torch.Tensor) else torch.as_tensor(np.asarray(v))
+    except (TypeError, ValueError, RuntimeError):
+        raise ValueError(f"odeint_rowwise: jump_dy must be a real tensor, numpy array or nested list of numbers, got "
+                         f"{type(v).__name__}") from None
+    if dy.is_complex() or dy.dtype == torch.bool:
+        raise ValueError(f"odeint_rowwise: jump_dy must be real, got a {dy.dtype} tensor")
+    K = jump.shape[0]
+    per_row, shared = (K, B) + row_shape, (K,) + row_shape
+    if dy.dim() == y0.dim() + 1 and tuple(dy.shape) == per_row:
+        rows = B
+    elif dy.dim() == y0.dim() and tuple(dy.shape) == shared:
+        rows = 1
+    else:
+        raise ValueError(f"odeint_rowwise: jump_dy must be [K, B, *row_shape] = {list(per_row)} (an impulse per row) or "
+                         f"[K, *row_shape] = {list(shared)} (shared by all rows), entry for entry the impulses of jump_t "
+                         f"(K = {K}); got shape {list(dy.shape)}")
+    dy = dy.detach().to(device=y0.device, dtype=y0.dtype).reshape(K, rows, -1).contiguous()
+    live = jump == jump                                      # (the dy of a NaN time is ignored)
+    finite = torch.isfinite(dy).all(dim=2).cpu().numpy()
+    bad = live & ~finite
+    if bad.any():
+        k, r = (int(x[0]) for x in np.nonzero(bad))
+        raise ValueError(f"odeint_rowwise: jump_dy[{k}] is not finite for row {r}, whose jump_t[{k}] is a time")
+    with np.errstate(invalid="ignore"):
+        at_start = (jump * sign == t0[None, :]) & (dy != 0).any(dim=2).cpu().numpy()
+    if at_start.any():
+        k, r = (int(x[0]) for x in np.nonzero(at_start))
+        raise ValueError(f"odeint_rowwise: jump_t[{k}] of row {r} is the row's start time and its jump_dy is not zero: no "
+                         "step ends there, so the impulse would never be applied; add it to y0")
+    return dy
+
+
+def _row_points(step, jump, sign: float, t0: np.ndarray, index: bool = False):
     """The two tables of `_points` -> (`_RowPoints` or None) each: per row the points >= t0_r in solver time, sorted; a
     value that occurs twice in a row's two lists together is refused (rk_common.py:229-232).  Whole-table numpy ops: the
-    set-up of B rows costs no Python loop over them."""
+    set-up of B rows costs no Python loop over them.  `index`: the jump table also gets `.index`, int32 [K', B]: the entry
+    of the caller's table that sits at each sorted position (-1: padding), the argsort of the sort done here."""
     kept = []
     for tab in (step, jump):
         if tab is None:
@@ -205,6 +246,12 @@ def _row_points(step, jump, sign: float, t0: np.ndarray):
         nxt = np.minimum((a == t0[None, :]).sum(axis=0), count - 1).astype(np.int32)
         table = np.where(a == a, a, np.inf)[:int(count.max())]
         out.append(_RowPoints(np.ascontiguousarray(table), count, nxt))
+    if index and out[1] is not None:
+        with np.errstate(invalid="ignore"):
+            raw = np.where(jump * sign >= t0[None, :], jump * sign, np.nan)      # the table before its sort (kept[1])
+        order = np.argsort(raw, axis=0, kind="stable")       # (NaN last, as np.sort; no two equal times in a column)
+        a = kept[1][:out[1].table.shape[0]]
+        out[1].index = np.ascontiguousarray(np.where(a == a, order[:a.shape[0]], -1).astype(np.int32))
     return out
 
 
@@ -347,13 +394,19 @@ class _Problem:
             self.min_rows, self.max_rows = (np.full(B, x) if v is None else v.numpy().copy()
                                             for x, v in ((self.min_step, lo_rows), (self.max_step, hi_rows)))
             self.min_step = self.max_step = None
-        self.step_points, self.jump_points = _row_points(_points("step_t", options.get("step_t", ()), B),
-                                                         _points("jump_t", options.get("jump_t", ()), B), sign,
-                                                         self.tgrid[0].numpy())
+        step, jump = (_points(name, options.get(name, ()), B) for name in ("step_t", "jump_t"))
+        # the impulses of the jump points (`jump_dy`): [K, B or 1, L], never permuted or gathered — `jump_points.index`
+        # leads from a position in a row's sorted column to the caller's k; None without the option
+        self.jump_dy = None
+        if options.get("jump_dy") is not None:
+            self.jump_dy = _impulses(options["jump_dy"], jump, sign, self.tgrid[0].numpy(), y0)
+        self.step_points, self.jump_points = _row_points(step, jump, sign, self.tgrid[0].numpy(),
+                                                         index=self.jump_dy is not None)
         given = [name for name in _STEP_OPTIONS if name in options]
         if self.record and given:                            # (after their validation: a wrong value is a ValueError first)
             raise NotImplementedError("odeint_rowwise: {} not supported for a recorded solve (differentiable=True with "
                                       "grad mode on)".format(", ".join(given) + (" is" if len(given) == 1 else " are")))
+        self.n_impulses = None                               # with jump_dy: int64 [B] by original row, after the solve
         self.nfe = 0
         # compact: the original indices of the rows now carried (int64, ascending, on the state's device) — func's third
         # argument — and what the two extra stats count
@@ -473,6 +526,11 @@ class HostRowKernels:
         self.clip_t = np.zeros(B)
         self.on_point = np.zeros(B, dtype=np.int64)
         self.jumped = np.zeros(B, dtype=bool)
+        # impulses (`jump_dy`): the jump table is tested with the CLOSED rule t0 < p <= t0 + dt, an accepted step onto a jump
+        # point notes the point's position in the row's sorted column, and `refresh_after_jump` adds the impulse
+        self.impulse = p.jump_dy is not None and p.jump_points is not None
+        self.jump_hit = np.zeros(B, dtype=np.int64) if self.impulse else None
+        self.n_imp = np.zeros(B, dtype=np.int64) if self.impulse else None      # by original row
         # record mode: [B] fp64 graphs of the first step sizes (initial-step heuristic) and, from the second trial step
         # on, of the time every later step of the row is anchored to (t0 + dt_first for a row whose first step was accepted)
         self.s_shadow = None
@@ -537,8 +595,9 @@ class HostRowKernels:
                                     (2, self.jump_tab, self.jump_cnt, self.jump_next)):
             if tab is not None and cnt[r] >= 1:
                 pt = tab[nxt[r], r]
-                if t0 < pt < t0 + dt:
-                    on, dt = kind, pt - t0
+                if t0 < pt and (pt <= t0 + dt if kind == 2 and self.impulse else pt < t0 + dt):
+                    # (a step that lands on the point keeps its size: pt - t0 may round above dt, hence above max_step)
+                    on, dt = kind, (pt - t0 if pt < t0 + dt else dt)
                     self.clip_t[r] = pt
         self.on_point[r] = on
         self.dt[r] = dt
@@ -567,7 +626,7 @@ class HostRowKernels:
         return torch.from_numpy(self.all_acc.copy()), torch.from_numpy(self.all_rej.copy())
 
     _ROW_VECTORS = ("t0", "tprev", "dt", "active", "since", "next_out", "bad_y", "n_acc", "n_rej", "code", "min_r", "max_r",
-                    "clip_t", "on_point", "jumped", "step_cnt", "step_next", "jump_cnt", "jump_next")
+                    "clip_t", "on_point", "jumped", "jump_hit", "step_cnt", "step_next", "jump_cnt", "jump_next")
 
     def repack(self, y, f0, n_keep: int):
         """Carry on with the `n_keep` active rows only, in their order: (y, f0) of those rows."""
@@ -690,6 +749,8 @@ class HostRowKernels:
                     if on == 1 and self.step_next[r] != self.step_cnt[r] - 1:
                         self.step_next[r] += 1
                     if on == 2:
+                        if self.impulse:
+                            self.jump_hit[r] = self.jump_next[r]
                         if self.jump_next[r] != self.jump_cnt[r] - 1:
                             self.jump_next[r] += 1
                         self.jumped[r] = True
@@ -731,8 +792,17 @@ class HostRowKernels:
 
     def refresh_after_jump(self, y, f0):
         """f0 of the rows that jumped <- func just after the point (rk_common.py:352, Perturb.NEXT), one call for the
-        carried batch: every other row is evaluated at its frozen time and its f0 keeps its bits."""
+        carried batch: every other row is evaluated at its frozen time and its f0 keeps its bits.  With `jump_dy` the
+        state of a row that jumped first takes the impulse of the point, y_r += dy[k, r] in the state's type, so that the
+        call sees the state behind the point."""
         p, T = self.p, self.T
+        if self.impulse:
+            for r in np.flatnonzero(self.jumped):
+                o = int(r if self.row_map is None else self.row_map[r])
+                k = int(p.jump_points.index[self.jump_hit[r], o])
+                if k >= 0:
+                    y[r] += p.jump_dy[k, o if p.jump_dy.shape[1] > 1 else 0]
+                self.n_imp[o] += 1
         t_rows = np.empty(self.n)
         for r in range(self.n):
             t0 = T(self.t0[r])
@@ -741,6 +811,10 @@ class HostRowKernels:
         rows = torch.from_numpy(np.flatnonzero(self.jumped))
         f0[rows] = f_new[rows]
         return f0
+
+    def impulse_counts(self) -> torch.Tensor:
+        """`n_impulses`: the steps of each original row that ended on a jump point (int64 [B])."""
+        return torch.zeros(self.p.B, dtype=torch.int64) if self.n_imp is None else torch.from_numpy(self.n_imp.copy())
 
     def deactivate_rows(self, mask: torch.Tensor) -> None:
         """Before the initial step: the rows of `mask` (bool [B]) never start."""
@@ -865,6 +939,8 @@ class HipRowKernels:
         self.n_acc = torch.zeros(B, dtype=torch.int64, device=dev)
         self.n_rej = torch.zeros(B, dtype=torch.int64, device=dev)
         # per-row bounds or points: the controller variant (`tdeq_row_control_points`), whose status has a third word
+        self.impulse = p.jump_dy is not None and p.jump_points is not None
+        self.n_imp = torch.zeros(B, dtype=torch.int64, device=dev) if self.impulse else None      # by original row
         self.pts = self._row_points(f64, i32) if (p.min_rows is not None or p.step_points is not None
                                                    or p.jump_points is not None) else None
         self.n_jumped = 0
@@ -893,7 +969,7 @@ class HipRowKernels:
         self.rec = rad.RowRecorder(self.k, p, _row_sum) if p.record else None
 
     _POINT_VECTORS = ("step_count", "jump_count", "next_step", "next_jump", "clip_t", "on_point", "min_step", "max_step",
-                      "jumped")
+                      "jumped", "jump_hit")
 
     def _row_points(self, f64, i32) -> _native.RowPoints:
         """The vectors and tables of `tdeq_row_points` as attributes `pt_<field>` (None: absent), and the block."""
@@ -905,7 +981,13 @@ class HipRowKernels:
         self.pt_max_step = None if p.max_rows is None else torch.as_tensor(p.max_rows, **f64)
         self.pt_clip_t = torch.zeros(B, **f64)
         self.pt_on_point, self.pt_jumped = torch.zeros(B, **i32), torch.zeros(B, **i32)
+        # impulses (`jump_dy`): the controller's IMPULSE variant — closed rule for the jump table, `jump_hit` — and what
+        # `tdeq_row_impulse` reads besides: the index table by ORIGINAL row (a repack re-selects nothing of it or of jump_dy)
+        self.pt_jump_hit = torch.zeros(B, **i32) if self.impulse else None
+        if self.impulse:
+            self.dy_index = torch.as_tensor(p.jump_points.index, **i32).contiguous()
         pts = _native.RowPoints()
+        pts.jump_closed = 1 if self.impulse else 0
         pts.n_step = 0 if self.pt_step_t is None else self.pt_step_t.shape[0]
         pts.n_jump = 0 if self.pt_jump_t is None else self.pt_jump_t.shape[0]
         self._point_pointers(pts)
@@ -998,10 +1080,23 @@ class HipRowKernels:
 
     def refresh_after_jump(self, y, f0):
         """f0 of the rows that jumped <- func just after the point, one call for the carried batch at the times the
-        controller wrote; `tdeq_row_select` takes the rows that jumped and reads nothing of the others."""
+        controller wrote; `tdeq_row_select` takes the rows that jumped and reads nothing of the others.  With `jump_dy`
+        `tdeq_row_impulse` first adds the impulse of the point to the state of those rows, in place."""
+        if self.impulse:
+            self.k.row_impulse(y, self.p.jump_dy, self.dy_index, self.pt_jump_hit, self.pt_jumped, self.row_map)
         f_new = self.p.call(self.jump_times, y)
         self.k.row_select(f0, f_new, self.pt_jumped)
+        if self.impulse:
+            hit = self.pt_jumped.ne(0).to(torch.int64)
+            if self.row_map is None:
+                self.n_imp.add_(hit)
+            else:
+                self.n_imp.index_add_(0, self.row_map.to(torch.int64), hit)
         return f0
+
+    def impulse_counts(self) -> torch.Tensor:
+        """`n_impulses`: the steps of each original row that ended on a jump point (int64 [B])."""
+        return torch.zeros(self.p.B, dtype=torch.int64) if self.n_imp is None else self.n_imp.cpu()
 
     def _reduce(self, mode: int, y0, y1, partial, ks, coefs, dts, active) -> None:
         """The row reduction into `part`: with the two scalar tolerances, or with the [n] vectors of the rows now carried
@@ -1127,6 +1222,8 @@ def _solve(p: _Problem, y_start, f0, sol, hook=None, never_start=None):
             if hook is not None:
                 hook.before_step(n_active)
             y, f0 = kern.trial_step(y, f0, sol)
+    if p.jump_dy is not None:
+        p.n_impulses = kern.impulse_counts()
     return (kern, *kern.counts())
 
 
@@ -1137,6 +1234,8 @@ def _stats(p: _Problem, n_acc, n_rej) -> dict:
     stats = {"n_accepted": n_acc.to(torch.int64), "n_rejected": n_rej.to(torch.int64), "nfe": p.nfe}
     if p.compact is not None:
         stats["row_evals"], stats["n_repacks"] = p.row_evals, p.n_repacks
+    if p.jump_dy is not None:
+        stats["n_impulses"] = torch.zeros(p.B, dtype=torch.int64) if p.n_impulses is None else p.n_impulses
     return stats
 
 
@@ -1170,6 +1269,22 @@ def odeint_rowwise(func, y0, t, *, rtol=1e-7, atol=1e-9, method="dopri5", option
     every other row — and `f0` of the rows that jumped is taken from it (the other rows' output is ignored, NaN included);
     `nfe` counts the call.  Row r has the bits and counts of the one-row solve with column r.  With `differentiable=True`
     and grad mode on any of the four raises NotImplementedError.
+
+    `jump_dy`: state impulses at the jump points, entry for entry those of `jump_t` as the caller wrote it (before sorting
+    and before points are dropped): `[K, B, *row_shape]` (an impulse per row) or `[K, *row_shape]` (shared; the two forms
+    are told apart by `dim()` against `y0.dim()`), a tensor on any device, a numpy array or nested lists, converted to the
+    state's dtype; real, and finite wherever the matching time is not NaN (the dy of a NaN time is ignored).  When row r's
+    accepted step ends on `p = jump_t[k, r]`, `y_r <- y_r + jump_dy[k, r]` — one addition in the state's type, applied in
+    the direction of integration (not negated for a descending grid) — and `f0_r` is then re-evaluated behind the point on
+    the new state.  Output is LEFT-continuous: an output time equal to `p` holds the state before the impulse (the step
+    that ends on `p` writes it), the first value after `p` includes it, and an impulse at a row's last output time is
+    therefore not visible in the solution.  A point before `t0_r` is dropped with its impulse; a point equal to `t0_r`
+    whose impulse is not all zero raises ValueError naming the row (no step ends there: add it to y0).  In a solve with
+    `jump_dy` a jump point is stepped onto when `t0 < p <= t0 + dt` (closed: a step that lands on `p` exactly is a step
+    onto it, or that dose and every later one of the row would be lost); `step_t`, and `jump_t` without `jump_dy`, keep
+    the reference's open rule.  `stats` gains `n_impulses`, int64 `[B]` by original row: the steps that ended on a jump
+    point.  `compact` is supported, bit for bit.  `jump_dy` without `jump_t` or with another K raises ValueError; with
+    `differentiable=True` and grad mode on it raises NotImplementedError, as it does in `odeint_rowwise_event`.
 
     `rtol` and `atol` are each a number (or a one-element tensor), or a per-row vector with exactly `B = y0.shape[0]`
     entries: a 1-D tensor of any real dtype on any device, a 1-D numpy array, a list or a tuple of numbers.  Row r is then

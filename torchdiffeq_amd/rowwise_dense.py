@@ -272,7 +272,10 @@ def odeint_rowwise_dense(func, y0, t0, t1, *, rtol=1e-7, atol=1e-9, method="dopr
 
     The solve is the `odeint_rowwise` solve on the grid `[t0, t1]`: the same step sequence, counters and errors per row (a
     failing row — max_num_steps, dt underflow, a non-finite state — raises and names the original row).  The quartic of
-    every accepted step is kept (see `RowDenseOutput` for the layout).
+    every accepted step is kept (see `RowDenseOutput` for the layout).  With `options["jump_dy"]` (state impulses at the
+    jump points, see `odeint_rowwise`) a dose time `p` is a breakpoint: `dense(p)` is the left limit, the state before the
+    impulse, because a breakpoint belongs to the earlier step, and the segment that starts at `p` starts from the state
+    with the impulse; `stats` gains `n_impulses`.
 
     `dense(t)`: `t` a number or 0-dim tensor -> `[B, *row_shape]`; `[Q]` (shared) or `[Q, B]` (per row) -> `[Q, B,
     *row_shape]`, in any order, repeats allowed.  Row r's segments are its accepted steps `[ta_s, tb_s]` in solver time; a

@@ -246,7 +246,8 @@ def odeint_rowwise_event(func, y0, t0, *, event_fn, t_end=None, rtol=1e-7, atol=
     time, no end), a number or a `[B]` tensor; it must differ from `t0` in every row, in the same direction for all rows
     (`t_end < t0`: decreasing time), else ValueError.  `rtol`, `atol` (numbers or `[B]` vectors), `method` and `options`
     (`first_step`, `safety`, `ifactor`, `dfactor`, `max_num_steps`, `min_step`, `max_step`, `step_t`, `jump_t`) are those of
-    `odeint_rowwise`; the event of a step onto a jump point is tested before `f0` is re-evaluated behind it.
+    `odeint_rowwise`; the event of a step onto a jump point is tested before `f0` is re-evaluated behind it.  `jump_dy`
+    raises NotImplementedError: an impulse can flip the sign of the event function with no root inside any step.
 
     `event_fn(t_rows [b], y [b, *row_shape]) -> [b]` returns one real value per row on the state's device; it always gets
     TRUE time (also for decreasing time), in the state's dtype, and is called under `torch.no_grad()`; its value is cast
@@ -301,6 +302,9 @@ def odeint_rowwise_event(func, y0, t0, *, event_fn, t_end=None, rtol=1e-7, atol=
     """
     if not callable(event_fn):
         raise ValueError("odeint_rowwise_event: event_fn must be callable: event_fn(t_rows [b], y [b, *row_shape]) -> [b]")
+    if options is not None and dict(options).get("jump_dy") is not None:
+        raise NotImplementedError("odeint_rowwise_event: jump_dy is not supported: an impulse can flip the sign of the "
+                                  "event function with no root inside any step")
     B = rowwise._batch_rows(y0)
     p = _Problem(func, y0, None if B is None else _event_grid(t0, t_end, B), rtol, atol, method, options, None, False, compact)
     ev = RowEvents(p, event_fn)
