@@ -1,4 +1,4 @@
-"""The two kernels of csrc/tdeq_kernels_rowwise_steps.hpp on the MI355X against the CPU oracle
+"""The per-row step options of csrc/tdeq_kernels_rowwise.hpp on the MI355X against the CPU oracle
 (tests/_rowwise_steps_oracle.py): the controller variant on hand-made states that hit every rule of the per-row bounds
 and points, bit for bit, and the row select on sentinel-bordered buffers.
 
@@ -212,9 +212,11 @@ def test_control_points_first_step(B, mode, form, dtype, sign, hip_kernels, orac
 
 @pytest.mark.parametrize("dtype", [F64, F32], ids=["f64", "f32"])
 @pytest.mark.parametrize("form", ["lane", "wave"])
-@pytest.mark.parametrize("mode", [0, 2, 3])
+@pytest.mark.parametrize("mode", [0, 1, 2, 3])
 def test_control_points_without_points_is_row_control(mode, form, dtype, hip_kernels):
-    """Null tables and null bound vectors: every output of `tdeq_row_control` on the same inputs has the same bits."""
+    """Null tables and null bound vectors: every output of `tdeq_row_control` on the same inputs has the same bits.
+    Mode 1 (d1 parked in `dt`; with s1 = 0 the heuristic takes h0 = 1e-6, so no result of `pow` reaches an output)
+    prepares no step: `on_point`, `jumped` and `jump_times` keep their fillers."""
     B = 65
     rows = [dict(sc, lo=0.0, hi=0.25, on=0) for sc in _rows(B)]
     for L, nch in _geometry(form, dtype, hip_kernels):
@@ -227,6 +229,12 @@ def test_control_points_without_points_is_row_control(mode, form, dtype, hip_ker
         assert int(got["status"][2]) == 0 and bool((got["pt_on_point"] == 0)[torch.tensor([sc["active"] for sc in rows]) != 0].all())
         for name in F64_VECTORS + I32_VECTORS + I64_VECTORS + ("dts", "times"):
             assert torch.equal(got[name].view(torch.uint8), plain[name].view(torch.uint8)), name
+        if mode == 1:
+            kept = _launch(hip_kernels, DEV, mode, B, L, nch, dtype, 1.0, [dict(sc, on=5) for sc in rows], state, sums, False,
+                           tables=False)
+            assert bool((kept["pt_on_point"] == 5).all()) and bool((kept["pt_jumped"] == 9).all())
+            assert bool((kept["pt_jump_times"] == -77.0).all())
+            assert bool((got["pt_jumped"] == 9).all()) and bool((got["pt_jump_times"] == -77.0).all())
 
 
 # -- tdeq_row_select ------------------------------------------------------------------------------------------------------------------

@@ -14,7 +14,6 @@ SOURCES = [os.path.join(_PKG, "csrc", "tdeq_abi.hip")]
 HEADERS = [os.path.join(_PKG, "csrc", h) for h in ("tdeq_kernels.hpp", "tdeq_kernels_complex.hpp", "tdeq_kernels_lp.hpp",
                                                    "tdeq_abi_lp.hpp", "tdeq_kernels_rowwise.hpp",
                                                    "tdeq_kernels_rowwise_event.hpp", "tdeq_kernels_rowwise_dense.hpp",
-                                                   "tdeq_kernels_rowwise_steps.hpp",
                                                    "tdeq_abi_rowwise.hpp")] + [
            os.path.join(_ROOT, "include", "tdeq_hip.h")]
 OUTPUT = os.path.join(_PKG, "libtdeq_hip.so")

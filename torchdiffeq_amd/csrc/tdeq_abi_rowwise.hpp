@@ -6,7 +6,6 @@
 #include "tdeq_kernels_rowwise.hpp"
 #include "tdeq_kernels_rowwise_event.hpp"
 #include "tdeq_kernels_rowwise_dense.hpp"
-#include "tdeq_kernels_rowwise_steps.hpp"
 
 namespace {
 using namespace tdeq;
@@ -194,14 +193,15 @@ inline int row_reduce_check(int mode, const void* y0, const void* y1, const void
     return n_rows == 0 ? 1 : 0;
 }
 
-template <typename T>
-int row_control_launch(const RowCtrlArgs& a, hipStream_t s) {
+// one wave per row when a row has several partials to add, one lane per row otherwise
+template <typename T, bool POINTS, bool IMPULSE>
+int row_control_launch(const RowCtrlArgsOf<POINTS>& a, hipStream_t s) {
     if (a.nch > 1) {
-        const dim3 grid((unsigned)((a.n_rows * kWave + kBlock - 1) / kBlock));
-        hipLaunchKernelGGL((row_ctrl_kernel<T, true>), grid, dim3(kBlock), 0, s, a);
+        const dim3 grid((unsigned)((a.st.n_rows * kWave + kBlock - 1) / kBlock));
+        hipLaunchKernelGGL((row_ctrl_kernel<T, true, POINTS, IMPULSE>), grid, dim3(kBlock), 0, s, a);
     } else {
-        const dim3 grid((unsigned)((a.n_rows + kBlock - 1) / kBlock));
-        hipLaunchKernelGGL((row_ctrl_kernel<T, false>), grid, dim3(kBlock), 0, s, a);
+        const dim3 grid((unsigned)((a.st.n_rows + kBlock - 1) / kBlock));
+        hipLaunchKernelGGL((row_ctrl_kernel<T, false, POINTS, IMPULSE>), grid, dim3(kBlock), 0, s, a);
     }
     return check_launch();
 }
@@ -416,46 +416,13 @@ int row_control_args(RowCtrlArgs& a, int mode, const double* part, const tdeq_st
     launch = true;
     a.part = part;
     a.nch = (int)row_geom(st->row_len, dtype).nch;
-    a.n_rows = st->n_rows;
-    a.row_len = st->row_len;
     a.tkind = dtype == TDEQ_F32 ? 1 : 0;
     a.mode = mode;
-    a.order = st->order;
     a.c = *ctrl;
-    a.max_num_steps = st->max_num_steps;
-    a.tgrid = st->tgrid;
-    a.n_out = st->n_out;
-    a.t0 = st->t0;
-    a.tprev = st->tprev;
-    a.dt = st->dt;
-    a.h0 = st->h0;
+    a.st = *st;
     a.dts_out = dts_out;
     a.times = times_out;
-    a.active = st->active;
-    a.accepted = st->accepted;
-    a.out_lo = st->out_lo;
-    a.out_hi = st->out_hi;
-    a.next_out = st->next_out;
-    a.since = st->since;
-    a.bad_y = st->bad_y;
-    a.code = st->code;
-    a.n_acc = st->n_acc;
-    a.n_rej = st->n_rej;
-    a.ratio_out = st->ratio;
-    a.status = st->status;
     return 0;
-}
-
-template <typename T, bool IMPULSE>
-int row_control_points_launch(const RowCtrlPointsArgs& a, hipStream_t s) {
-    if (a.base.nch > 1) {
-        const dim3 grid((unsigned)((a.base.n_rows * kWave + kBlock - 1) / kBlock));
-        hipLaunchKernelGGL((row_ctrl_points_kernel<T, true, IMPULSE>), grid, dim3(kBlock), 0, s, a);
-    } else {
-        const dim3 grid((unsigned)((a.base.n_rows + kBlock - 1) / kBlock));
-        hipLaunchKernelGGL((row_ctrl_points_kernel<T, false, IMPULSE>), grid, dim3(kBlock), 0, s, a);
-    }
-    return check_launch();
 }
 
 template <typename E>
@@ -486,7 +453,8 @@ int tdeq_row_control(int mode, const double* part, const tdeq_step_ctrl* ctrl, c
     bool launch;
     const int e = row_control_args(a, mode, part, ctrl, st, dts_out, times_out, dtype, 2, s, launch);
     if (e || !launch) return e;
-    return dtype == TDEQ_F32 ? row_control_launch<float>(a, s) : row_control_launch<double>(a, s);
+    return dtype == TDEQ_F32 ? row_control_launch<float, false, false>(a, s)
+                             : row_control_launch<double, false, false>(a, s);
 }
 
 // ---- per-row step options: tdeq_row_control_points / tdeq_row_select / tdeq_row_impulse -------------------------------
@@ -499,32 +467,15 @@ int tdeq_row_control_points(int mode, const double* part, const tdeq_step_ctrl* 
     hipStream_t s = static_cast<hipStream_t>(stream);
     RowCtrlPointsArgs a;
     bool launch;
-    const int e = row_control_args(a.base, mode, part, ctrl, st, dts_out, times_out, dtype, 3, s, launch);
+    const int e = row_control_args(a, mode, part, ctrl, st, dts_out, times_out, dtype, 3, s, launch);
     if (e || !launch) return e;
-    // the bounds: per row or the two scalars, never those of `base.c` (see tdeq_kernels_rowwise_steps.hpp)
-    a.lo = ctrl->min_step;
-    a.hi = ctrl->max_step;
-    a.base.c.min_step = -HUGE_VAL;
-    a.base.c.max_step = HUGE_VAL;
-    a.step_t = pts->step_t;
-    a.jump_t = pts->jump_t;
-    a.step_count = pts->step_count;
-    a.jump_count = pts->jump_count;
-    a.next_step = pts->next_step;
-    a.next_jump = pts->next_jump;
-    a.clip_t = pts->clip_t;
-    a.on_point = pts->on_point;
-    a.min_step = pts->min_step;
-    a.max_step = pts->max_step;
-    a.jumped = pts->jumped;
-    a.jump_times = pts->jump_times;
-    a.jump_hit = pts->jump_hit;
-    if (a.jump_hit) {                 // a solve with impulses: the closed rule for the jump table
-        return dtype == TDEQ_F32 ? row_control_points_launch<float, true>(a, s)
-                                 : row_control_points_launch<double, true>(a, s);
+    a.pts = *pts;
+    if (pts->jump_hit) {              // a solve with impulses: the closed rule for the jump table
+        return dtype == TDEQ_F32 ? row_control_launch<float, true, true>(a, s)
+                                 : row_control_launch<double, true, true>(a, s);
     }
-    return dtype == TDEQ_F32 ? row_control_points_launch<float, false>(a, s)
-                             : row_control_points_launch<double, false>(a, s);
+    return dtype == TDEQ_F32 ? row_control_launch<float, true, false>(a, s)
+                             : row_control_launch<double, true, false>(a, s);
 }
 
 int tdeq_row_select(void* dst, const void* src, const int32_t* mask, int64_t n_rows, int64_t row_len, int dtype,

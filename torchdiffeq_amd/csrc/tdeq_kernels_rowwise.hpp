@@ -4,7 +4,7 @@
 // The state is [B, L] row-major.  Every per-row quantity lives in a device vector of length B: the time t0[B] and step
 // size dt[B] (fp64, the reference's time type W), sign * T(dt) of the running trial step (T[B]), the stage times handed
 // to func ([n_stages, B] of T), the active flag, the counters and an error code.  The host reads back two words per
-// trial step (active rows, first row in error).
+// trial step (active rows, first row in error), three in a solve with per-row step options (rows that jumped).
 //
 // The arithmetic of every element is that of the whole-batch kernels in tdeq_kernels.hpp with the row's own step
 // size: coefficients fl_T(fl_T(a_j) * T(dt_r)), left-to-right sums, -ffp-contract=off.  Rows that have finished
@@ -20,6 +20,13 @@
 //                                                      partials with one wave in a fixed order.  A long row of ONE
 //                                                      chunk (kRowWaveMax < nv <= chunk) takes the same chunk kernels;
 //                                                      its single partial sits where a short row's does
+//
+// The per-row step options (`min_step`, `max_step` as [B] vectors, `step_t`, `jump_t`, `jump_dy`) are the controller's
+// POINTS / IMPULSE instantiations — the step rule is stated once, see "Per-row controller" — plus two streaming kernels:
+//   row_select_kernel        dst[r, :] = src[r, :] for the rows of a mask: how the re-evaluated f0 of the rows that jumped
+//                            is taken, and nothing of any other row.
+//   row_impulse_kernel       y[r, :] += dy[k, row, :] for the rows of the same mask (`jump_dy`): the state impulse of the
+//                            jump point the row's step ended on, k looked up from the position the controller reported.
 #pragma once
 
 #include "tdeq_kernels.hpp"
@@ -256,67 +263,107 @@ __global__ __launch_bounds__(kBlock) void row_reduce_chunk_kernel(const RowRedAr
 //   3  dt given (first_step): only the non-finite census of y0 (the MODE 1 reduction) and the set-up below
 // After modes 0 (rows still active), 2 and 3: the next trial step's dt clamp, sign * T(dt) and stage times, and the
 // error checks the host raises for (code 2: max_num_steps, 1: dt underflow, 3: non-finite y).
+//
+// POINTS (a solve with `min_step` / `max_step` as [B] vectors, `step_t` or `jump_t`) is a compile-time flag of the
+// controller, as ROWTOL is of the row reductions: false is the controller without them, with the two scalar bounds of
+// `c`, and its block is RowCtrlArgs.  true takes the row's own bounds and the row's own points: times a step must end on
+// (`step_t`) and times where func is discontinuous (`jump_t`).  A prepared step that would pass the row's next point is
+// cut short at it (rk_common.py:289-309); an accepted cut step ends on the point's own bits and moves the row's index
+// (rk_common.py:343-352); mode 0 also reports which rows ended on a jump point and the time vector of the one extra
+// evaluation of func that follows.
+// IMPULSE (POINTS with `jump_dy`) tests the jump table with `t0 < p <= t0 + dt` — a step that lands on a point exactly
+// is a step onto it, or the row's index would stick there and the dose and every later one be lost; such a step keeps
+// its dt (it ends on the point's bits already) — and an accepted step onto a jump point writes jump_hit[r], the
+// position of the point in the row's sorted column.
 // ------------------------------------------------------------------------------------------------
 struct RowCtrlArgs {
     const double* part;               // [3][B * nch]
     int nch;
-    int64_t n_rows;
-    int64_t row_len;                  // L in elements (the norm's mean)
     int tkind;                        // 0 = fp64, 1 = fp32
     int mode;
-    int order;                        // initial step: the solver's order - 1 (rk_common.py:217)
     tdeq_step_ctrl c;                 // safety, ifactor, dfactor, exponent, min_step, max_step, time_sign, alpha[], n_times
-    int64_t max_num_steps;
-    const double* tgrid;              // [n_out, B] output times (solver time, fp64)
-    int n_out;
-    double* t0;                       // [B]
-    double* tprev;                    // [B] start of the last accepted step
-    double* dt;                       // [B]
-    double* h0;                       // [B] initial step: h0 (T value in a double)
+    tdeq_row_state st;                // the [B] vectors of the solve; status: [2] = {active rows, first row in error}
     void* dts_out;                    // [B] of T: sign * T(dt) of the next trial step (mode 1: sign * T(h0))
     void* times;                      // [n_times, B] of T (mode 1: row 0 = the time of f(t0 + h0))
-    int32_t* active;
-    int32_t* accepted;                // [B] this trial step was accepted (dense output + commit)
-    int32_t* out_lo;                  // [B] first output index inside the accepted step
-    int32_t* out_hi;                  // [B] one past the last
-    int32_t* next_out;                // [B]
-    int32_t* since;                   // [B] trial steps since the row last reached an output time
-    int32_t* bad_y;                   // [B] the row's current y has non-finite entries
-    int32_t* code;                    // [B]
-    int64_t* n_acc;
-    int64_t* n_rej;
-    double* ratio_out;                // [B]
-    int32_t* status;                  // [2] = {active rows, first row with a non-zero code} (reset by the host side)
 };
 
+struct RowCtrlPointsArgs : RowCtrlArgs {      // st.status: [3], the third word = rows that jumped in this launch
+    tdeq_row_points pts;              // tables sorted per row and padded with +inf; a null table or bound vector: none
+};
+
+template <bool POINTS>
+using RowCtrlArgsOf = typename std::conditional<POINTS, RowCtrlPointsArgs, RowCtrlArgs>::type;
+
+// stage time i of a step from t0 of size dt that ends at t1 (rk_common.py:72-78): ctl_stage_time with the end given
 template <typename T>
-__device__ __forceinline__ T row_stage_time(const tdeq_step_ctrl& c, double t0n, double dtn, int i) {
-    return ctl_stage_time<T>(c, t0n, dtn, i);
+__device__ __forceinline__ T row_stage_time_to(const tdeq_step_ctrl& c, double t0, double dt, double t1, int i) {
+    T tt;
+    if ((c.alpha_is_one >> i) & 1u) tt = ctl_prev((T)t1);
+    else tt = (T)t0 + (T)c.alpha[i] * (T)dt;
+    return (T)c.time_sign * tt;
 }
 
-template <typename T>
-__device__ __forceinline__ void row_prepare(const RowCtrlArgs& a, int64_t r) {
+// the row's next point of one table inside the prepared step (t0, t0 + dt), or no cut (rk_common.py:292-296); CLOSED:
+// inside (t0, t0 + dt]
+template <bool CLOSED = false>
+__device__ __forceinline__ bool row_point_inside(const double* table, const int32_t* count, const int32_t* next, int64_t r,
+                                                 int64_t n_rows, double t0, double dt, double& p) {
+    if (!table || count[r] < 1) return false;
+    p = table[(int64_t)next[r] * n_rows + r];
+    if (CLOSED) return t0 < p && p <= t0 + dt;
+    return t0 < p && p < t0 + dt;
+}
+
+// The next trial step of an active row (rk_common.py:266-287) with the row's bounds [lo, hi]; with POINTS the step is
+// then cut short at the row's next step point and at its next jump point, which wins (rk_common.py:289-309).  Returns
+// code != 0.
+template <typename T, bool POINTS, bool IMPULSE>
+__device__ __forceinline__ bool row_prepare(const RowCtrlArgsOf<POINTS>& a, int64_t r, double lo, double hi) {
     const tdeq_step_ctrl& c = a.c;
-    double dtn = a.dt[r];
-    if (!__builtin_isfinite(dtn)) dtn = c.min_step;
-    dtn = ctl_clamp(dtn, c.min_step, c.max_step);
-    a.dt[r] = dtn;
-    const double t0 = a.t0[r];
-    static_cast<T*>(a.dts_out)[r] = (T)dtn * (T)c.time_sign;
-    for (int i = 0; i < c.n_times; ++i) static_cast<T*>(a.times)[i * a.n_rows + r] = row_stage_time<T>(c, t0, dtn, i);
+    const tdeq_row_state& s = a.st;
+    double dt = s.dt[r];
+    if (!__builtin_isfinite(dt)) dt = lo;
+    dt = ctl_clamp(dt, lo, hi);
+    const double t0 = s.t0[r];
     int code = 0;
-    if (a.bad_y[r]) code = 3;
-    if (!(t0 + dtn > t0)) code = 1;
-    if (a.since[r] >= a.max_num_steps) code = 2;
-    a.code[r] = code;
+    if (s.bad_y[r]) code = 3;
+    if (!(t0 + dt > t0)) code = 1;
+    if (s.since[r] >= s.max_num_steps) code = 2;
+    double t1 = 0.0;
+    int on = 0;
+    if constexpr (POINTS) {
+        const tdeq_row_points& q = a.pts;
+        double p;
+        if (row_point_inside(q.step_t, q.step_count, q.next_step, r, s.n_rows, t0, dt, p)) {
+            on = 1;
+            t1 = p;
+            dt = p - t0;
+        }
+        if (row_point_inside<IMPULSE>(q.jump_t, q.jump_count, q.next_jump, r, s.n_rows, t0, dt, p)) {
+            on = 2;
+            t1 = p;
+            // (a step that lands on the point keeps its size: p - t0 may round above dt, hence above max_step, and a step
+            //  above the ceiling is never accepted)
+            if (!IMPULSE || p < t0 + dt) dt = p - t0;
+        }
+        q.on_point[r] = on;
+        if (on) q.clip_t[r] = t1;
+    }
+    s.dt[r] = dt;
+    static_cast<T*>(a.dts_out)[r] = (T)dt * (T)c.time_sign;
+    for (int i = 0; i < c.n_times; ++i)
+        static_cast<T*>(a.times)[i * s.n_rows + r] = on ? row_stage_time_to<T>(c, t0, dt, t1, i) : ctl_stage_time<T>(c, t0, dt, i);
+    s.code[r] = code;
+    return code != 0;
 }
 
-// a finished row: func keeps being evaluated at the end of its last accepted step, on its frozen state
+// a finished row: func keeps being evaluated at the end t0 of its last accepted step, on its frozen state
 template <typename T>
-__device__ __forceinline__ void row_freeze(const RowCtrlArgs& a, int64_t r) {
-    static_cast<T*>(a.dts_out)[r] = (T)0;
-    const T tt = (T)a.c.time_sign * (T)a.t0[r];
-    for (int i = 0; i < a.c.n_times; ++i) static_cast<T*>(a.times)[i * a.n_rows + r] = tt;
+__device__ __forceinline__ void row_freeze(void* dts, void* times, int n_times, int64_t n_rows, double time_sign, double t0,
+                                           int64_t r) {
+    static_cast<T*>(dts)[r] = (T)0;
+    const T tt = (T)time_sign * (T)t0;
+    for (int i = 0; i < n_times; ++i) static_cast<T*>(times)[i * n_rows + r] = tt;
 }
 
 // sqrt(mean) of a row, rounded to T (misc.py:22-33 with one segment)
@@ -325,111 +372,141 @@ __device__ __forceinline__ double row_norm(double sum, int64_t numel, int tkind)
     return tkind == 1 ? (double)(float)v : v;
 }
 
-// returns: the row is active after this launch, and (code != 0)
-template <typename T>
-__device__ __forceinline__ void row_control(const RowCtrlArgs& a, int64_t r, double s0, double s1, double sb,
-                                            bool& live, bool& err) {
+// returns: the row is active after this launch, (code != 0), and with POINTS: its accepted step ended on a jump point
+template <typename T, bool POINTS, bool IMPULSE>
+__device__ __forceinline__ void row_control(const RowCtrlArgsOf<POINTS>& a, int64_t r, double s0, double s1, double sb,
+                                            bool& live, bool& err, bool& jump) {
     const tdeq_step_ctrl& c = a.c;
-    live = a.active[r] != 0;
+    const tdeq_row_state& s = a.st;
+    double lo = c.min_step, hi = c.max_step;          // the bounds of row r
+    if constexpr (POINTS) {
+        if (a.pts.min_step) lo = a.pts.min_step[r];
+        if (a.pts.max_step) hi = a.pts.max_step[r];
+    }
+    const bool was_live = s.active[r] != 0;
+    live = was_live;
     err = false;
+    jump = false;
     if (a.mode == 0) {
-        if (!live) {
-            a.accepted[r] = 0;
-            row_freeze<T>(a, r);
-            return;
-        }
-        const double ratio = row_norm(s0, a.row_len, a.tkind);
-        const double step_t0 = a.t0[r], step_dt = a.dt[r];
-        bool accept = ratio <= 1.0;
-        if (step_dt > c.max_step) accept = false;
-        if (step_dt <= c.min_step) accept = true;
-        double dt_next;
-        if (ratio == 0.0) {
-            dt_next = step_dt * c.ifactor;
-        } else {
-            const double dfactor = ratio < 1.0 ? 1.0 : c.dfactor;
-            const double scaled = c.safety / pow(ratio, c.exponent);
-            dt_next = step_dt * ctl_nan_min(c.ifactor, ctl_nan_max(scaled, dfactor));
-        }
-        dt_next = ctl_clamp(dt_next, c.min_step, c.max_step);
-        a.ratio_out[r] = ratio;
-        a.since[r] += 1;
-        a.accepted[r] = accept ? 1 : 0;
-        if (accept) {
-            const double t1 = step_t0 + step_dt;
-            a.tprev[r] = step_t0;
-            a.t0[r] = t1;
-            a.n_acc[r] += 1;
-            const int lo = a.next_out[r];
-            int hi = lo;
-            while (hi < a.n_out && a.tgrid[(int64_t)hi * a.n_rows + r] <= t1) ++hi;
-            a.out_lo[r] = lo;
-            a.out_hi[r] = hi;
-            a.next_out[r] = hi;
-            if (hi > lo) a.since[r] = 0;
-            a.bad_y[r] = sb != 0.0 ? 1 : 0;
-            if (hi >= a.n_out) {
-                live = false;
-                a.active[r] = 0;
+        double t_now = s.t0[r];
+        if (live) {
+            const double ratio = row_norm(s0, s.row_len, a.tkind);
+            const double step_t0 = t_now, step_dt = s.dt[r];
+            bool accept = ratio <= 1.0;
+            if (step_dt > hi) accept = false;
+            if (step_dt <= lo) accept = true;
+            double dt_next;
+            if (ratio == 0.0) {
+                dt_next = step_dt * c.ifactor;
+            } else {
+                const double dfactor = ratio < 1.0 ? 1.0 : c.dfactor;
+                const double scaled = c.safety / pow(ratio, c.exponent);
+                dt_next = step_dt * ctl_nan_min(c.ifactor, ctl_nan_max(scaled, dfactor));
             }
+            dt_next = ctl_clamp(dt_next, lo, hi);
+            s.ratio[r] = ratio;
+            s.since[r] += 1;
+            s.accepted[r] = accept ? 1 : 0;
+            if (accept) {
+                t_now = step_t0 + step_dt;
+                int on = 0;
+                if constexpr (POINTS) {
+                    on = a.pts.on_point[r];
+                    if (on) t_now = a.pts.clip_t[r];              // a cut step ends on the point's own bits
+                }
+                s.tprev[r] = step_t0;
+                s.t0[r] = t_now;
+                s.n_acc[r] += 1;
+                const int out_lo = s.next_out[r];
+                int out_hi = out_lo;
+                while (out_hi < s.n_out && s.tgrid[(int64_t)out_hi * s.n_rows + r] <= t_now) ++out_hi;
+                s.out_lo[r] = out_lo;
+                s.out_hi[r] = out_hi;
+                s.next_out[r] = out_hi;
+                if (out_hi > out_lo) s.since[r] = 0;
+                s.bad_y[r] = sb != 0.0 ? 1 : 0;
+                if constexpr (POINTS) {
+                    const tdeq_row_points& q = a.pts;
+                    if (on == 1 && q.next_step[r] != q.step_count[r] - 1) q.next_step[r] += 1;
+                    if (on == 2) {
+                        if (IMPULSE) q.jump_hit[r] = q.next_jump[r];
+                        if (q.next_jump[r] != q.jump_count[r] - 1) q.next_jump[r] += 1;
+                        jump = true;
+                    }
+                }
+                if (out_hi >= s.n_out) {
+                    live = false;
+                    s.active[r] = 0;
+                }
+            } else {
+                s.n_rej[r] += 1;
+            }
+            s.dt[r] = dt_next;
         } else {
-            a.n_rej[r] += 1;
+            s.accepted[r] = 0;
         }
-        a.dt[r] = dt_next;
+        if constexpr (POINTS) {
+            a.pts.jumped[r] = jump ? 1 : 0;
+            static_cast<T*>(a.pts.jump_times)[r] = (T)c.time_sign * (jump ? ctl_next((T)t_now) : (T)t_now);
+        }
     } else if (a.mode == 1) {
         // _select_initial_step (misc.py:36-77) in T: d0 = ||y0 / scale||, d1 = ||f0 / scale||
-        const T d0 = (T)row_norm(s0, a.row_len, a.tkind), d1 = (T)row_norm(s1, a.row_len, a.tkind);
+        const T d0 = (T)row_norm(s0, s.row_len, a.tkind), d1 = (T)row_norm(s1, s.row_len, a.tkind);
         T h0;
         if (d0 < (T)1e-5 || d1 < (T)1e-5) h0 = (T)1e-6;
         else h0 = ((T)0.01 * d0) / d1;
         h0 = h0 < (T)0 ? -h0 : h0;
-        a.h0[r] = (double)h0;
-        a.bad_y[r] = sb != 0.0 ? 1 : 0;
+        s.h0[r] = (double)h0;
+        s.dt[r] = (double)d1;                 // parked for mode 2; no step is prepared before it
+        s.bad_y[r] = sb != 0.0 ? 1 : 0;
         static_cast<T*>(a.dts_out)[r] = (T)((double)h0 * c.time_sign);
-        static_cast<T*>(a.times)[r] = (T)c.time_sign * (T)(a.t0[r] + (double)h0);
+        static_cast<T*>(a.times)[r] = (T)c.time_sign * (T)(s.t0[r] + (double)h0);
         return;
     } else if (a.mode == 2) {
-        const T h0 = (T)a.h0[r];
-        const T d1 = (T)a.dt[r];              // (mode 1 parked d1 here, see below)
-        const T d2n = (T)row_norm(s0, a.row_len, a.tkind);
+        const T h0 = (T)s.h0[r];
+        const T d1 = (T)s.dt[r];              // (parked by mode 1)
+        const T d2n = (T)row_norm(s0, s.row_len, a.tkind);
         T d2 = d2n / h0;
         d2 = d2 < (T)0 ? -d2 : d2;
         T h1;
         // (Python's max / min on host scalars: max(a, b) = b if b > a else a, min(a, b) = b if b < a else a)
         if (d1 <= (T)1e-15 && d2 <= (T)1e-15) {
-            const T lo = (T)1e-6, v = h0 * (T)1e-3;
-            h1 = v > lo ? v : lo;
+            const T small = (T)1e-6, v = h0 * (T)1e-3;
+            h1 = v > small ? v : small;
         } else {
             const T m = d2 > d1 ? d2 : d1;
             const T q = ((T)1 / m) * (T)0.01;           // `0.01 / x` = x.reciprocal() * 0.01 (_scalars.rdiv)
-            const double e = 1.0 / (double)(a.order + 1);
+            const double e = 1.0 / (double)(s.order + 1);
             if (e == 0.5) h1 = sizeof(T) == 4 ? (T)__builtin_sqrtf((float)q) : (T)__builtin_sqrt((double)q);   // ATen's sqrt
             else h1 = (T)pow((double)q, e);                                                    // raised in double (_scalars.power)
         }
         h1 = h1 < (T)0 ? -h1 : h1;
         const T big = (T)100 * h0;
         const T fs = h1 < big ? h1 : big;
-        a.dt[r] = (double)fs;
+        s.dt[r] = (double)fs;
     } else {
-        a.bad_y[r] = sb != 0.0 ? 1 : 0;
+        s.bad_y[r] = sb != 0.0 ? 1 : 0;
     }
     if (live) {
-        row_prepare<T>(a, r);
-        err = a.code[r] != 0;
+        err = row_prepare<T, POINTS, IMPULSE>(a, r, lo, hi);
     } else {
-        row_freeze<T>(a, r);
+        row_freeze<T>(a.dts_out, a.times, c.n_times, s.n_rows, c.time_sign, s.t0[r], r);
+        // (a row that had finished before a trial step is only frozen again: its on_point stays as it is)
+        if constexpr (POINTS) if (was_live || a.mode != 0) a.pts.on_point[r] = 0;
     }
 }
 
-template <typename T, bool WAVE>
-__global__ __launch_bounds__(kBlock) void row_ctrl_kernel(const RowCtrlArgs a) {
+template <typename T, bool WAVE, bool POINTS, bool IMPULSE>
+__global__ __launch_bounds__(kBlock) void row_ctrl_kernel(const RowCtrlArgsOf<POINTS> a) {
+    static_assert(POINTS || !IMPULSE, "IMPULSE is a variant of POINTS");
     const int lane = threadIdx.x & (kWave - 1);
+    const int64_t n_rows = a.st.n_rows;
     int64_t r;
     double s0 = 0.0, s1 = 0.0, sb = 0.0;
-    const int64_t np = a.n_rows * a.nch;
+    const int64_t np = n_rows * a.nch;
     if (WAVE) {
         r = ((int64_t)blockIdx.x * kBlock + threadIdx.x) / kWave;
-        if (r < a.n_rows) {
+        if (r < n_rows) {
             for (int64_t q = lane; q < a.nch; q += kWave) {
                 s0 += a.part[r * a.nch + q];
                 s1 += a.part[np + r * a.nch + q];
@@ -441,25 +518,24 @@ __global__ __launch_bounds__(kBlock) void row_ctrl_kernel(const RowCtrlArgs a) {
         sb = wave_sum(sb);
     } else {
         r = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-        if (r < a.n_rows) {
+        if (r < n_rows) {
             s0 = a.part[r];
             s1 = a.part[np + r];
             sb = a.part[2 * np + r];
         }
     }
-    bool live = false, err = false;
-    if (r < a.n_rows && (!WAVE || lane == 0)) {
-        if (a.mode == 1) {
-            row_control<T>(a, r, s0, s1, sb, live, err);
-            a.dt[r] = (double)(T)row_norm(s1, a.row_len, a.tkind);     // d1 for mode 2
-        } else {
-            row_control<T>(a, r, s0, s1, sb, live, err);
-        }
-        if (err) atomicMin(a.status + 1, (int32_t)r);
+    bool live = false, err = false, jump = false;
+    if (r < n_rows && (!WAVE || lane == 0)) {
+        row_control<T, POINTS, IMPULSE>(a, r, s0, s1, sb, live, err, jump);
+        if (err) atomicMin(a.st.status + 1, (int32_t)r);
     }
-    // active-row count: one atomic per wave
+    // the active-row count, and with POINTS the count of rows that jumped: one atomic per wave each
     const uint64_t m = __ballot(live ? 1 : 0);
-    if (lane == 0 && m) atomicAdd(a.status, (int32_t)__popcll(m));
+    if (lane == 0 && m) atomicAdd(a.st.status, (int32_t)__popcll(m));
+    if constexpr (POINTS) {
+        const uint64_t mj = __ballot(jump ? 1 : 0);
+        if (lane == 0 && mj) atomicAdd(a.st.status + 2, (int32_t)__popcll(mj));
+    }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -571,6 +647,59 @@ __global__ __launch_bounds__(kBlock) void row_gather_kernel(const RowGatherArgs<
         const int64_t from = (int64_t)a.idx[q] * a.row_len + (i - q * a.row_len);
 #pragma unroll
         for (int m = 0; m < NS; ++m) static_cast<E*>(a.dst[m])[i] = static_cast<const E*>(a.src[m])[from];
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Row select: dst[r, :] = src[r, :] where mask[r] != 0.  A copy of bits; a row outside the mask is neither read nor
+// written (its src may hold anything, NaN included).
+// ------------------------------------------------------------------------------------------------
+struct RowSelectArgs {
+    void* dst;
+    const void* src;
+    const int32_t* mask;              // [n_rows]
+    int64_t row_len;                  // E units
+    int64_t ne;                       // n_rows * row_len
+};
+
+template <typename E>
+__global__ __launch_bounds__(kBlock) void row_select_kernel(const RowSelectArgs a) {
+    const int64_t stride = (int64_t)gridDim.x * kBlock;
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < a.ne; i += stride) {
+        if (a.mask[i / a.row_len]) static_cast<E*>(a.dst)[i] = static_cast<const E*>(a.src)[i];
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Row impulse: y[r, :] += dy[k, o or 0, :] where jumped[r] != 0, with o = row_map[r] (null: r) the row's original index and
+// k = dy_index[jump_hit[r], o] the user's entry of the point the step ended on (k < 0: none).  One addition in the state's
+// type.  A row outside the mask is neither read nor written, and of `dy` only the rows that are added are read: 3 words per
+// element of a row that jumped, none for any other.
+// ------------------------------------------------------------------------------------------------
+struct RowImpulseArgs {
+    void* y;                          // [n_rows, row_len]
+    const void* dy;                   // [K, dy_rows, row_len]
+    const int32_t* dy_index;          // [K', n_orig]: sorted position -> k, -1 none
+    const int32_t* jump_hit;          // [n_rows]
+    const int32_t* jumped;            // [n_rows]
+    const int32_t* row_map;           // [n_rows] or null
+    int64_t dy_rows;                  // 1 or n_orig
+    int64_t n_orig;
+    int64_t row_len;                  // E units
+    int64_t ne;                       // n_rows * row_len
+};
+
+template <typename E>
+__global__ __launch_bounds__(kBlock) void row_impulse_kernel(const RowImpulseArgs a) {
+    const int64_t stride = (int64_t)gridDim.x * kBlock;
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < a.ne; i += stride) {
+        const int64_t r = i / a.row_len;
+        if (!a.jumped[r]) continue;
+        const int64_t o = a.row_map ? a.row_map[r] : r;
+        const int64_t k = a.dy_index[(int64_t)a.jump_hit[r] * a.n_orig + o];
+        if (k < 0) continue;
+        const int64_t src = (k * a.dy_rows + (a.dy_rows == 1 ? 0 : o)) * a.row_len + (i - r * a.row_len);
+        static_cast<E*>(a.y)[i] = static_cast<E*>(a.y)[i] + static_cast<const E*>(a.dy)[src];
     }
 }
 

@@ -60,9 +60,7 @@ __global__ __launch_bounds__(kBlock) void row_event_detect_kernel(const RowEvent
             if (a.active[r]) {        // (a row whose step also reached its last output time has left already)
                 a.active[r] = 0;
                 left = true;
-                static_cast<T*>(a.dts)[r] = (T)0;                     // row_freeze
-                const T tt = (T)a.time_sign * (T)a.t0[r];
-                for (int i = 0; i < a.n_times; ++i) static_cast<T*>(a.times)[i * a.n_rows + r] = tt;
+                row_freeze<T>(a.dts, a.times, a.n_times, a.n_rows, a.time_sign, a.t0[r], r);
             }
         }
         a.fired_now[r] = now;
