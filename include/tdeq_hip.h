@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define TDEQ_ABI_VERSION 30
+#define TDEQ_ABI_VERSION 31
 #define TDEQ_F32 0
 #define TDEQ_F64 1
 /* interleaved (re, im) complex states — accepted by the NORM entry points only (tdeq_error_norm, tdeq_error_norm_partial[_ctrl],
@@ -741,6 +741,50 @@ int tdeq_row_dense_pack(void* dst, int64_t dst_rows, const void* src, int64_t sr
 int tdeq_row_dense_search(const double* tq, int64_t n_q, const int64_t* offsets, const double* seg_ta, const double* seg_tb,
                           int64_t n_seg, const double* t0, const double* t1, int64_t n_rows, int32_t* seg, void* x,
                           int32_t* status, int dtype, void* stream);
+
+/*
+ * ---- Calculus on the per-row dense record (ABI 31; `RowDenseOutput.derivative` / `.antiderivative` / `.integral`) ----
+ * Linear functionals of the piecewise quartic y(x) = e + d x + c x^2 + b x^3 + a x^4 of `coeffs` [5, n_seg, row_len] (planes
+ * e, d, c, b, a), per element.  `seg_ta` / `seg_tb` are the segment ends in SOLVER time, `time_sign` is +1 for an ascending
+ * and -1 for a descending solve (true time = time_sign * solver time), so every result is with respect to TRUE time.  Nothing
+ * is contracted.
+ * tdeq_row_dense_prefix  `prefix` [n_seg, row_len] double: the EXCLUSIVE prefix of the whole-segment integrals of each row, in
+ *                        solver time.  With h_s = seg_tb[s] - seg_ta[s] (fp64), the coefficients converted to double and
+ *                            J_s(x) = (((((a*0.2)*x + b*0.25)*x + c*(1.0/3.0))*x + d*0.5)*x + e) * x * h_s
+ *                        every product and sum rounded once in fp64, I_s = J_s(1.0) — the same expression — and
+ *                        prefix[offsets[r]] = 0, prefix[s + 1] = prefix[s] + I_s for s + 1 < offsets[r + 1], added LEFT TO
+ *                        RIGHT: one lane per (row, element) walks the row's segments in order.  That order is the contract (a
+ *                        row's bits depend neither on n_rows nor on the backend); a row with many segments runs serially.
+ *                        0 <= offsets[r] <= offsets[r + 1] <= n_seg (the walk is clamped to the record).
+ * tdeq_row_dense_calc    for i < n_idx, out[i, :] (of the state type T) from the segment seg[i] and the fraction x[i] (T) that
+ *                        tdeq_row_dense_search wrote for query tq[i]; an out-of-range query is marked by x[i] = NaN and gives
+ *                        a row of NaN.  mode
+ *                        TDEQ_DENSE_DERIVATIVE      in T:  tot = d + (c + c) * x;  xp = x * x;  tot = tot + (T(3) * b) * xp;
+ *                                                   xp = xp * x;  tot = tot + (T(4) * a) * xp;  out = tot / w  with
+ *                                                   w = T(time_sign * (seg_tb[s] - seg_ta[s])), the difference in fp64.  At a
+ *                                                   breakpoint (x = 1 of the earlier segment) that is the LEFT derivative.
+ *                                                   `prefix`, `tq`, `seg2`, `x2`, `tq2` are not read (may be NULL).
+ *                        TDEQ_DENSE_ANTIDERIVATIVE  in fp64: x64 = (tq[i] - seg_ta[s]) / h_s, NOT rounded to T,
+ *                                                   F64 = time_sign * (prefix[s, :] + J_s(x64)),  out = T(F64): one rounding
+ *                                                   to T.  The integral from t0[r] in true time; 0 at tq = t0[r].
+ *                        TDEQ_DENSE_INTEGRAL        out = T(F64 of (seg2[i], x2[i], tq2[i]) - F64 of (seg[i], x[i], tq[i])),
+ *                                                   the difference in fp64: the integral from tq to tq2.  Either end out of
+ *                                                   range gives NaN.
+ *                        0 <= seg[i], seg2[i] < n_seg (not checked: they live on the device; the search guarantees it).
+ * 64-bit offsets; 16-byte elements when row_len is a multiple of 16 / sizeof(T) and `out`, `coeffs` and `prefix` are 16-byte
+ * aligned, scalar elements otherwise.  A NULL pointer that the mode reads, a negative size, n_seg > INT32_MAX, a mode or
+ * time_sign other than those named, or a dtype other than TDEQ_F32 / TDEQ_F64: TDEQ_EINVAL before any launch.  n_rows == 0 /
+ * n_seg == 0 (prefix) / n_idx == 0: no-op.
+ */
+#define TDEQ_DENSE_DERIVATIVE 0
+#define TDEQ_DENSE_ANTIDERIVATIVE 1
+#define TDEQ_DENSE_INTEGRAL 2
+int tdeq_row_dense_prefix(double* prefix, const void* coeffs, const int64_t* offsets, const double* seg_ta,
+                          const double* seg_tb, int64_t n_seg, int64_t n_rows, int64_t row_len, int dtype, void* stream);
+int tdeq_row_dense_calc(void* out, int mode, const void* coeffs, int64_t n_seg, const double* seg_ta, const double* seg_tb,
+                        const double* prefix, double time_sign, const int32_t* seg, const void* x, const double* tq,
+                        const int32_t* seg2, const void* x2, const double* tq2, int64_t n_idx, int64_t row_len, int dtype,
+                        void* stream);
 
 /*
  * ---- Per-row step options (ABI 29; `min_step`, `max_step`, `step_t`, `jump_t` of the rowwise family) ----

@@ -14,6 +14,9 @@ on a mixed-stiffness batch.
     python tools/rowwise_bench.py --event-compact-summary lines.jsonl[,parent_event.jsonl,new_event.jsonl]
                                   --out profiles/rowwise_event_compact_bench.json
     python tools/rowwise_bench.py --dense [--reps 5] [--out dense.json]
+    python tools/rowwise_bench.py --dense-calculus [--reps 5] [--out calculus.json]
+    python tools/rowwise_bench.py --dense-calculus-summary calculus.json,parent_dense.jsonl,new_dense.jsonl,parent_bench.jsonl,
+                                  new_bench.jsonl --out profiles/rowwise_dense_calculus_bench.json
     python tools/rowwise_bench.py --impulse [--reps 3] [--out profiles/rowwise_impulse_bench.json]
     python tools/rowwise_bench.py --impulse-summary impulse.json,parent_event.jsonl,new_event.jsonl,parent_dense.jsonl,
                                   new_dense.jsonl,parent_bench.jsonl,new_bench.jsonl --out profiles/rowwise_impulse_bench.json
@@ -569,6 +572,93 @@ def _impulse_summary(paths, out):
     print(json.dumps(res["paths_without_the_option_against_parent"]))
 
 
+def _dense_calculus(reps: int, Q: int = 16):
+    """The calculus on the record of the `--dense` solve, in one process: the prefix build (dropped and rebuilt `reps` times
+    after a warm-up) against the bytes it must move — five T words read and one fp64 word written per segment element — and
+    `derivative`, `antiderivative`, `integral` next to `dense(t)` for the same Q times per row, the four alternated."""
+    import torchdiffeq_amd as tda
+    dev = torch.device("cuda", 0)
+    B, D = 65536, 128
+    g = torch.Generator().manual_seed(0)
+    G = torch.randn(D, D, generator=g, dtype=torch.float64) / D ** 0.5
+    A = (0.5 * (G - G.T) - 0.1 * torch.eye(D, dtype=torch.float64)).float().to(dev)
+    k = torch.logspace(-1, 1.5, B, dtype=torch.float64)[torch.randperm(B, generator=g)][:, None].float().to(dev)
+    y0 = torch.randn(B, D, generator=g).to(dev)
+    med = lambda v: sorted(v)[len(v) // 2]       # noqa: E731
+    func = lambda t_, y: k * (y @ A.T)           # noqa: E731
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3, out
+    with torch.no_grad():
+        dense, st = tda.odeint_rowwise_dense(func, y0, 0.0, 0.5, rtol=1e-7, atol=1e-9, return_stats=True)
+        tq = torch.rand(Q, B, generator=g, dtype=torch.float64).to(dev) * 0.5
+        tq2 = torch.rand(Q, B, generator=g, dtype=torch.float64).to(dev) * 0.5
+        prefix_ms = []
+        for rep in range(reps + 1):                           # the first build warms up
+            dense.drop_integral_cache()
+            ms, P = timed(dense._integral_prefix)
+            if rep:
+                prefix_ms.append(ms)
+        calls = {"dense(t)": lambda: dense(tq, check=False), "derivative": lambda: dense.derivative(tq, check=False),
+                 "antiderivative": lambda: dense.antiderivative(tq, check=False),
+                 "integral": lambda: dense.integral(tq, tq2, check=False)}
+        ms_of, finite = {name: [] for name in calls}, True
+        for rep in range(reps + 1):
+            for name, fn in calls.items():
+                ms, out = timed(fn)
+                finite = finite and bool(torch.isfinite(out).all())
+                if rep:
+                    ms_of[name].append(ms)
+    n_el = dense.n_segments * D
+    prefix_bytes = n_el * (5 * 4 + 8)
+    word = Q * B * D
+    moved = {"dense(t)": 6 * 4 * word, "derivative": 5 * 4 * word, "antiderivative": (6 * 4 + 8) * word,
+             "integral": (11 * 4 + 2 * 8) * word}
+    res = {"n_segments": dense.n_segments, "accepted_median": float(st["n_accepted"].median()),
+           "accepted_max": int(st["n_accepted"].max()), "all_finite": finite, "hbm_peak_TBs": PEAK_TBS,
+           "prefix": {"bytes_held": P.numel() * 8, "bytes_moved": prefix_bytes, "ms_per_build": prefix_ms,
+                      "median_ms": med(prefix_ms), "achieved_TBs": prefix_bytes / (med(prefix_ms) * 1e-3) / 1e12},
+           "eval": {"Q": Q}}
+    for name in calls:
+        res["eval"][name] = {"ms_per_call": ms_of[name], "median_ms": med(ms_of[name]), "bytes_moved": moved[name],
+                             "achieved_TBs": moved[name] / (med(ms_of[name]) * 1e-3) / 1e12,
+                             "ratio_to_dense(t)": med(ms_of[name]) / med(ms_of["dense(t)"])}
+    return res
+
+
+def _dense_calculus_summary(paths, out):
+    """Fold the `--dense-calculus` file with the JSON lines of alternated fresh processes of the parent tree and of this tree
+    — `--dense --reps 3` (the plain dense solve and `dense(t)`) and `bench.py --gpus 1 --steps 200 --warmup 20`; the first
+    line of every file is the warm-up round — and say whether this tree's medians lie inside the parent's spread."""
+    med = lambda v: sorted(v)[len(v) // 2]       # noqa: E731
+
+    def fold(vals):
+        return {"per_process": [round(v, 4) for v in vals], "median": round(med(vals), 4), "min": round(min(vals), 4),
+                "max": round(max(vals), 4)}
+
+    def pair(parent, new):
+        p, n = fold(parent), fold(new)
+        return {"parent": p, "new": n, "new_median_inside_parent_min_max": p["min"] <= n["median"] <= p["max"],
+                "new_median_not_above_parent_max": n["median"] <= p["max"]}      # (every figure: lower is better)
+    lines = lambda path: [json.loads(x) for x in open(path) if x.strip().startswith("{")][1:]      # noqa: E731
+    res = json.load(open(paths[0]))
+    pd, nd, pb, nb = (lines(path) for path in paths[1:5])
+    res["unchanged_paths_against_parent"] = {
+        "what": "parent commit and this tree alternated in fresh processes in one session, the first round of processes "
+                "dropped: tools/rowwise_bench.py --dense --reps 3 and bench.py --gpus 1 --steps 200 --warmup 20",
+        "rowwise_dense_ms_per_solve": pair([r["dense"]["dense_median_ms"] for r in pd],
+                                           [r["dense"]["dense_median_ms"] for r in nd]),
+        "dense_eval_ms_per_call": pair([r["dense"]["eval"]["median_ms"] for r in pd],
+                                       [r["dense"]["eval"]["median_ms"] for r in nd]),
+        "bench_ms_per_step": pair([r["ms_per_step"] for r in pb], [r["ms_per_step"] for r in nb])}
+    json.dump(res, open(out, "w"), indent=1)
+    print(json.dumps(res["unchanged_paths_against_parent"]))
+
+
 def _dense_summary(paths, out):
     med = lambda v: sorted(v)[len(v) // 2]       # noqa: E731
 
@@ -844,6 +934,8 @@ def main():
     ap.add_argument("--event-compact-summary", default=None)
     ap.add_argument("--dense", action="store_true")
     ap.add_argument("--steps", action="store_true")
+    ap.add_argument("--dense-calculus", action="store_true")
+    ap.add_argument("--dense-calculus-summary", default=None)
     ap.add_argument("--dense-summary", default=None)
     ap.add_argument("--impulse", action="store_true")
     ap.add_argument("--impulse-summary", default=None)
@@ -864,6 +956,21 @@ def main():
         return
     if a.dense_summary:
         _dense_summary(a.dense_summary.split(","), a.out)
+        return
+    if a.dense_calculus_summary:
+        _dense_calculus_summary(a.dense_calculus_summary.split(","), a.out)
+        return
+    if a.dense_calculus:
+        res = {"device": torch.cuda.get_device_name(0), "arch": torch.cuda.get_device_properties(0).gcnArchName,
+               "what": "tools/rowwise_bench.py --dense-calculus: the record of the --dense solve (65536 x 128 fp32 dopri5, func "
+                       "k_r * (y @ A.T), t0 = 0, t1 = 0.5, rtol 1e-7, atol 1e-9); one process: the prefix build, then dense(t), "
+                       "derivative, antiderivative and integral alternated for 16 random times per row, check=False, the first "
+                       "round a warm-up; host clock around a device synchronise",
+               "dense_calculus": _dense_calculus(a.reps)}
+        print(json.dumps(res))
+        if a.out:
+            os.makedirs(os.path.dirname(a.out) or ".", exist_ok=True)
+            json.dump(res, open(a.out, "w"), indent=1)
         return
     if a.dense:
         res = {"device": torch.cuda.get_device_name(0), "arch": torch.cuda.get_device_properties(0).gcnArchName,

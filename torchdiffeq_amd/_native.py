@@ -18,7 +18,7 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-TDEQ_ABI_VERSION = 30
+TDEQ_ABI_VERSION = 31
 TDEQ_F32, TDEQ_F64 = 0, 1
 TDEQ_C64, TDEQ_C128 = 2, 3        # interleaved complex: the norm entry points only (include/tdeq_hip.h)
 TDEQ_BF16, TDEQ_F16 = 4, 5        # reduced-precision states: the entry points of the host-driven step (LowPrecisionHipKernels)
@@ -284,6 +284,14 @@ ABI_SIGNATURES = {
                                              ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
                                              ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                              ctypes.c_int, ctypes.c_void_p]),
+    # calculus on the per-row dense record (ABI 31, `RowDenseOutput.derivative` / `.antiderivative` / `.integral`)
+    "tdeq_row_dense_prefix": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                             ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int,
+                                             ctypes.c_void_p]),
+    "tdeq_row_dense_calc": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
+                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double, ctypes.c_void_p,
+                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                           ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p]),
     # per-row step options (ABI 29, `min_step` / `max_step` / `step_t` / `jump_t` of the rowwise family)
     "tdeq_row_control_points": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(StepCtrl),
                                                ctypes.POINTER(RowState), ctypes.POINTER(RowPoints), ctypes.c_void_p,
@@ -1127,6 +1135,62 @@ class HipKernels:
                                               n_seg, t0.data_ptr(), t1.data_ptr(), B, seg.data_ptr(), x.data_ptr(),
                                               status.data_ptr(), dtype_code(x.dtype), self._stream()),
                "tdeq_row_dense_search")
+
+    # -- calculus on the per-row dense record (RowDenseOutput.derivative / antiderivative / integral) --------------------
+    def row_dense_prefix(self, prefix, coeffs, offsets, seg_ta, seg_tb) -> None:
+        """tdeq_row_dense_prefix: `prefix` fp64 [n_seg, L] = the exclusive prefix, per row and left to right in fp64, of the
+        whole-segment integrals of `coeffs` [5, n_seg, L]; `offsets` int64 [B + 1], `seg_ta` / `seg_tb` fp64 [n_seg]."""
+        n_seg, B = seg_ta.numel(), offsets.numel() - 1
+        if n_seg == 0 or B <= 0:              # (nothing to add up; empty tensors have null pointers, which the ABI refuses)
+            return
+        if coeffs.dim() != 3 or coeffs.shape[:2] != (5, n_seg) or not coeffs.is_contiguous():
+            raise ValueError("row_dense_prefix: coeffs must be a contiguous [5, n_seg, L] tensor")
+        L = coeffs.shape[2]
+        for name, t, dtype, shape in (("prefix", prefix, torch.float64, (n_seg, L)), ("offsets", offsets, torch.int64, (B + 1,)),
+                                      ("seg_ta", seg_ta, torch.float64, (n_seg,)), ("seg_tb", seg_tb, torch.float64, (n_seg,))):
+            if tuple(t.shape) != shape or t.dtype != dtype or not t.is_contiguous():
+                raise ValueError(f"row_dense_prefix: {name} must be a contiguous {dtype} {list(shape)} tensor")
+        _check(self.lib.tdeq_row_dense_prefix(prefix.data_ptr(), coeffs.data_ptr(), offsets.data_ptr(), seg_ta.data_ptr(),
+                                              seg_tb.data_ptr(), n_seg, B, L, dtype_code(coeffs.dtype), self._stream()),
+               "tdeq_row_dense_prefix")
+
+    def row_dense_calc(self, out, mode: int, coeffs, seg_ta, seg_tb, prefix, sign: float, seg, x, tq=None, seg2=None,
+                       x2=None, tq2=None) -> None:
+        """tdeq_row_dense_calc: out[i, :] for the queries (seg[i], x[i], tq[i]) of `row_dense_search`; `mode` 0: the derivative
+        (`prefix`, `tq` and the second list may be None), 1: the antiderivative, 2: the integral from the first list to the
+        second (`seg2`, `x2`, `tq2`).  `out` [n_idx, L] and `x` [n_idx] of the dtype of `coeffs` [5, n_seg, L], `seg` int32
+        [n_idx], `tq` fp64 with n_idx elements in solver time, `prefix` fp64 [n_seg, L], `sign` +1.0 or -1.0."""
+        n_idx = seg.numel()
+        if n_idx == 0:
+            return
+        n_seg = seg_ta.numel()
+        if coeffs.dim() != 3 or coeffs.shape[:2] != (5, n_seg) or coeffs.dtype != out.dtype or not coeffs.is_contiguous():
+            raise ValueError("row_dense_calc: coeffs must be a contiguous [5, n_seg, L] tensor of out's dtype")
+        L = coeffs.shape[2]
+        if mode not in (0, 1, 2) or (mode != 0 and (prefix is None or tq is None)) \
+                or (mode == 2 and (seg2 is None or x2 is None or tq2 is None)):
+            raise ValueError("row_dense_calc: mode 0 (derivative), 1 (antiderivative: prefix, tq) or 2 (integral: also seg2, "
+                             "x2, tq2)")
+        checks = [("out", out, out.dtype, (n_idx, L)), ("seg_ta", seg_ta, torch.float64, (n_seg,)),
+                  ("seg_tb", seg_tb, torch.float64, (n_seg,)), ("seg", seg, torch.int32, (n_idx,)), ("x", x, out.dtype, (n_idx,))]
+        if mode != 0:
+            checks += [("prefix", prefix, torch.float64, (n_seg, L)), ("tq", tq.view(-1), torch.float64, (n_idx,))]
+        if mode == 2:
+            checks += [("seg2", seg2, torch.int32, (n_idx,)), ("x2", x2, out.dtype, (n_idx,)),
+                       ("tq2", tq2.view(-1), torch.float64, (n_idx,))]
+        for name, t, dtype, shape in checks:
+            if tuple(t.shape) != shape or t.dtype != dtype or not t.is_contiguous():
+                raise ValueError(f"row_dense_calc: {name} must be a contiguous {dtype} {list(shape)} tensor")
+        if (mode != 0 and not tq.is_contiguous()) or (mode == 2 and not tq2.is_contiguous()):
+            raise ValueError("row_dense_calc: tq and tq2 must be contiguous")
+
+        def ptr(t, needed):
+            return t.data_ptr() if needed and t is not None else None
+        _check(self.lib.tdeq_row_dense_calc(out.data_ptr(), mode, coeffs.data_ptr(), n_seg, seg_ta.data_ptr(),
+                                            seg_tb.data_ptr(), ptr(prefix, mode != 0), float(sign), seg.data_ptr(),
+                                            x.data_ptr(), ptr(tq, mode != 0), ptr(seg2, mode == 2), ptr(x2, mode == 2),
+                                            ptr(tq2, mode == 2), n_idx, L, dtype_code(out.dtype), self._stream()),
+               "tdeq_row_dense_calc")
 
 
 class ComplexHipKernels:

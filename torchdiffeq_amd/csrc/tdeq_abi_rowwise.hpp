@@ -1009,3 +1009,104 @@ int tdeq_row_dense_search(const double* tq, int64_t n_q, const int64_t* offsets,
     else hipLaunchKernelGGL((row_dense_search_kernel<double>), grid, dim3(kBlock), 0, s, a);
     return check_launch();
 }
+
+// ---- calculus on the record: tdeq_row_dense_prefix / tdeq_row_dense_calc ----------------------------------------------
+namespace {
+
+template <typename T>
+int row_dense_prefix_launch(double* prefix, const void* coeffs, const int64_t* offsets, const double* seg_ta,
+                            const double* seg_tb, int64_t n_seg, int64_t n_rows, int64_t row_len, hipStream_t s) {
+    RowDensePrefixArgs<T> a;
+    a.prefix = prefix;
+    a.q = static_cast<const T*>(coeffs);
+    a.offsets = offsets;
+    a.seg_ta = seg_ta;
+    a.seg_tb = seg_tb;
+    a.n_seg = n_seg;
+    a.q_plane = n_seg * row_len;
+    const int lv = row_lanes(row_len, std::is_same<T, float>::value ? TDEQ_F32 : TDEQ_F64);
+    if (lv > 1 && aligned16(prefix) && aligned16(coeffs)) {
+        a.row_len = row_len / lv;
+        a.ne = n_rows * a.row_len;
+        hipLaunchKernelGGL((row_dense_prefix_kernel<T, true>), dim3(stream_grid(a.ne, kBlock)), dim3(kBlock), 0, s, a);
+    } else {
+        a.row_len = row_len;
+        a.ne = n_rows * row_len;
+        hipLaunchKernelGGL((row_dense_prefix_kernel<T, false>), dim3(stream_grid(a.ne, kBlock)), dim3(kBlock), 0, s, a);
+    }
+    return check_launch();
+}
+
+template <typename T, bool VEC>
+int row_dense_calc_go(const RowDenseCalcArgs<T>& a, int mode, hipStream_t s) {
+    const dim3 grid(stream_grid(a.ne, kBlock)), block(kBlock);
+    if (mode == kDenseDerivative) hipLaunchKernelGGL((row_dense_calc_kernel<T, VEC, kDenseDerivative>), grid, block, 0, s, a);
+    else if (mode == kDenseAntiderivative)
+        hipLaunchKernelGGL((row_dense_calc_kernel<T, VEC, kDenseAntiderivative>), grid, block, 0, s, a);
+    else hipLaunchKernelGGL((row_dense_calc_kernel<T, VEC, kDenseIntegral>), grid, block, 0, s, a);
+    return check_launch();
+}
+
+template <typename T>
+int row_dense_calc_launch(void* out, int mode, const void* coeffs, int64_t n_seg, const double* seg_ta, const double* seg_tb,
+                          const double* prefix, double time_sign, const int32_t* seg, const void* x, const double* tq,
+                          const int32_t* seg2, const void* x2, const double* tq2, int64_t n_idx, int64_t row_len,
+                          hipStream_t s) {
+    RowDenseCalcArgs<T> a;
+    a.out = static_cast<T*>(out);
+    a.q = static_cast<const T*>(coeffs);
+    a.seg_ta = seg_ta;
+    a.seg_tb = seg_tb;
+    a.prefix = prefix;
+    a.sign = time_sign;
+    a.seg = seg;
+    a.x = static_cast<const T*>(x);
+    a.tq = tq;
+    a.seg2 = seg2;
+    a.x2 = static_cast<const T*>(x2);
+    a.tq2 = tq2;
+    a.q_plane = n_seg * row_len;
+    const int lv = row_lanes(row_len, std::is_same<T, float>::value ? TDEQ_F32 : TDEQ_F64);
+    if (lv > 1 && aligned16(out) && aligned16(coeffs) && (!prefix || aligned16(prefix))) {
+        a.row_len = row_len / lv;
+        a.ne = n_idx * a.row_len;
+        return row_dense_calc_go<T, true>(a, mode, s);
+    }
+    a.row_len = row_len;
+    a.ne = n_idx * row_len;
+    return row_dense_calc_go<T, false>(a, mode, s);
+}
+
+}  // namespace
+
+int tdeq_row_dense_prefix(double* prefix, const void* coeffs, const int64_t* offsets, const double* seg_ta,
+                          const double* seg_tb, int64_t n_seg, int64_t n_rows, int64_t row_len, int dtype, void* stream) {
+    if (!prefix || !coeffs || !offsets || !seg_ta || !seg_tb || !row_dtype_ok(dtype)) return TDEQ_EINVAL;
+    if (n_seg < 0 || n_rows < 0 || row_len < 1) return TDEQ_EINVAL;
+    if (n_rows == 0 || n_seg == 0) return 0;
+    if (n_seg > 0x7fffffffLL) return TDEQ_EINVAL;      // (a segment index is an int32 word everywhere else)
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return dtype == TDEQ_F32
+               ? row_dense_prefix_launch<float>(prefix, coeffs, offsets, seg_ta, seg_tb, n_seg, n_rows, row_len, s)
+               : row_dense_prefix_launch<double>(prefix, coeffs, offsets, seg_ta, seg_tb, n_seg, n_rows, row_len, s);
+}
+
+int tdeq_row_dense_calc(void* out, int mode, const void* coeffs, int64_t n_seg, const double* seg_ta, const double* seg_tb,
+                        const double* prefix, double time_sign, const int32_t* seg, const void* x, const double* tq,
+                        const int32_t* seg2, const void* x2, const double* tq2, int64_t n_idx, int64_t row_len, int dtype,
+                        void* stream) {
+    if (!out || !coeffs || !seg_ta || !seg_tb || !seg || !x || !row_dtype_ok(dtype)) return TDEQ_EINVAL;
+    if (mode != TDEQ_DENSE_DERIVATIVE && mode != TDEQ_DENSE_ANTIDERIVATIVE && mode != TDEQ_DENSE_INTEGRAL) return TDEQ_EINVAL;
+    if (mode != TDEQ_DENSE_DERIVATIVE && (!prefix || !tq)) return TDEQ_EINVAL;
+    if (mode == TDEQ_DENSE_INTEGRAL && (!seg2 || !x2 || !tq2)) return TDEQ_EINVAL;
+    if (!(time_sign == 1.0 || time_sign == -1.0)) return TDEQ_EINVAL;
+    if (n_idx < 0 || n_seg < 0 || row_len < 1) return TDEQ_EINVAL;
+    if (n_idx == 0) return 0;
+    if (n_seg < 1 || n_seg > 0x7fffffffLL) return TDEQ_EINVAL;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return dtype == TDEQ_F32
+               ? row_dense_calc_launch<float>(out, mode, coeffs, n_seg, seg_ta, seg_tb, prefix, time_sign, seg, x, tq, seg2,
+                                              x2, tq2, n_idx, row_len, s)
+               : row_dense_calc_launch<double>(out, mode, coeffs, n_seg, seg_ta, seg_tb, prefix, time_sign, seg, x, tq, seg2,
+                                               x2, tq2, n_idx, row_len, s);
+}

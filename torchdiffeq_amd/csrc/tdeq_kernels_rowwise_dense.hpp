@@ -14,6 +14,7 @@
 //   row_dense_search   one lane per query: the segment of the row that holds the query time (bisection over the row's
 //                      segment ends) and the fraction x of that step, in the arithmetic of row_dense_commit
 // followed by row_event_eval_mapped on (coeffs, seg, x).  No LDS; plain vector loads and stores; 64-bit element offsets.
+// The derivative, antiderivative and integral of the record (row_dense_prefix, row_dense_calc) are at the end of the file.
 #pragma once
 
 #include "tdeq_kernels_rowwise.hpp"
@@ -130,6 +131,189 @@ __global__ __launch_bounds__(kBlock) void row_dense_search_kernel(const RowDense
     // the wave's smallest offending index is that of its lowest lane: one atomic per wave that has one
     const uint64_t m = __ballot(bad ? 1 : 0);
     if (m && lane == __ffsll((unsigned long long)m) - 1) atomicMin(a.status, (int32_t)i);
+}
+
+// ---- calculus on the record (ABI 31): derivative, antiderivative and integral of the piecewise quartic -----------------
+//   row_dense_prefix   one lane per (row, element): walks the row's segments in step order and writes the EXCLUSIVE prefix
+//                      of the whole-segment integrals, P[s] = sum of I over the row's segments before s, added left to
+//                      right in fp64 (that order is the contract: a row's bits depend neither on B nor on the backend)
+//   row_dense_calc     the shape of row_event_eval_mapped with three modes: the derivative in T, the antiderivative
+//                      T(sign * (P[s] + J_s(x64))) in fp64, and the integral T(F64(b) - F64(a)) of two query lists
+// No LDS, no atomics; 64-bit element offsets.  Nothing is contracted (the library is built with -ffp-contract=off).
+
+// J_s(x) of a segment with coefficients e, d, c, b, a (as doubles), fp64 throughout; I_s = J_s(1.0), the same expression
+__device__ __forceinline__ double quartic_integral_one(double e, double d, double c, double b, double a, double x, double h) {
+    return (((((a * 0.2) * x + b * 0.25) * x + c * (1.0 / 3.0)) * x + d * 0.5) * x + e) * x * h;
+}
+
+// LV consecutive elements of T, moved as one E (E = T: LV = 1)
+template <typename T, typename E, int LV>
+__device__ __forceinline__ void load_lanes(const T* base, int64_t at, T (&v)[LV]) {
+    const E w = reinterpret_cast<const E*>(base)[at];
+    __builtin_memcpy(v, &w, sizeof(E));
+}
+
+template <int LV>
+__device__ __forceinline__ void store_doubles(double* p, const double (&v)[LV]) {
+    if constexpr (LV == 1) {
+        p[0] = v[0];
+    } else {
+#pragma unroll
+        for (int c = 0; c < LV; c += 2) {
+            f64x2 w;
+            w[0] = v[c];
+            w[1] = v[c + 1];
+            reinterpret_cast<f64x2*>(p)[c / 2] = w;
+        }
+    }
+}
+
+template <int LV>
+__device__ __forceinline__ void load_doubles(const double* p, double (&v)[LV]) {
+    if constexpr (LV == 1) {
+        v[0] = p[0];
+    } else {
+#pragma unroll
+        for (int c = 0; c < LV; c += 2) {
+            const f64x2 w = reinterpret_cast<const f64x2*>(p)[c / 2];
+            v[c] = w[0];
+            v[c + 1] = w[1];
+        }
+    }
+}
+
+template <typename T>
+struct RowDensePrefixArgs {
+    double* prefix;                   // [n_seg, L]
+    const T* q;                       // [5, n_seg, L] planes e, d, c, b, a
+    const int64_t* offsets;           // [n_rows + 1]
+    const double* seg_ta;             // [n_seg]
+    const double* seg_tb;             // [n_seg]
+    int64_t n_seg;
+    int64_t row_len;                  // E units
+    int64_t ne;                       // n_rows * row_len
+    int64_t q_plane;                  // n_seg * L elements of T
+};
+
+template <typename T, bool VEC>
+__global__ __launch_bounds__(kBlock) void row_dense_prefix_kernel(const RowDensePrefixArgs<T> a) {
+    using E = typename std::conditional<VEC, typename VecOf<T>::type, T>::type;
+    constexpr int LV = VEC ? VecOf<T>::L : 1;
+    const int64_t stride = (int64_t)gridDim.x * kBlock;
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < a.ne; i += stride) {
+        const int64_t r = i / a.row_len;
+        const int64_t el = i - r * a.row_len;
+        int64_t s = a.offsets[r], end = a.offsets[r + 1];
+        if (s < 0) s = 0;                                             // (nothing is read or written outside the record)
+        if (end > a.n_seg) end = a.n_seg;
+        double acc[LV];
+#pragma unroll
+        for (int c = 0; c < LV; ++c) acc[c] = 0.0;
+        for (; s < end; ++s) {                                        // serial by construction: the order is the contract
+            const int64_t at = s * a.row_len + el;
+            T qe[LV], qd[LV], qc[LV], qb[LV], qa[LV];
+            load_lanes<T, E, LV>(a.q, at, qe);
+            load_lanes<T, E, LV>(a.q + a.q_plane, at, qd);
+            load_lanes<T, E, LV>(a.q + 2 * a.q_plane, at, qc);
+            load_lanes<T, E, LV>(a.q + 3 * a.q_plane, at, qb);
+            load_lanes<T, E, LV>(a.q + 4 * a.q_plane, at, qa);
+            const double h = a.seg_tb[s] - a.seg_ta[s];
+            store_doubles<LV>(a.prefix + at * LV, acc);
+#pragma unroll
+            for (int c = 0; c < LV; ++c)
+                acc[c] = acc[c] + quartic_integral_one((double)qe[c], (double)qd[c], (double)qc[c], (double)qb[c],
+                                                       (double)qa[c], 1.0, h);
+        }
+    }
+}
+
+// modes of row_dense_calc (== TDEQ_DENSE_DERIVATIVE / _ANTIDERIVATIVE / _INTEGRAL of include/tdeq_hip.h)
+constexpr int kDenseDerivative = 0;
+constexpr int kDenseAntiderivative = 1;
+constexpr int kDenseIntegral = 2;
+
+template <typename T>
+struct RowDenseCalcArgs {
+    T* out;                           // [n_idx, L]
+    const T* q;                       // [5, n_seg, L]
+    const double* seg_ta;             // [n_seg]
+    const double* seg_tb;             // [n_seg]
+    const double* prefix;             // [n_seg, L] (not read by the derivative)
+    double sign;                      // +1 ascending, -1 descending solve
+    const int32_t* seg;               // [n_idx] segment of each query (row_dense_search)
+    const T* x;                       // [n_idx] its fraction in T; NaN marks an out-of-range query
+    const double* tq;                 // [n_idx] the query in solver time (not read by the derivative)
+    const int32_t* seg2;              // the integral's upper ends; not read otherwise
+    const T* x2;
+    const double* tq2;
+    int64_t row_len;                  // E units
+    int64_t ne;                       // n_idx * row_len
+    int64_t q_plane;                  // n_seg * L elements of T
+};
+
+// sign * (P[s] + J_s(x64)) of LV elements, x64 = (tq - ta) / (tb - ta) in fp64 and NOT rounded to T
+template <typename T, typename E, int LV>
+__device__ __forceinline__ void row_dense_antiderivative_one(const RowDenseCalcArgs<T>& a, int64_t s, int64_t el, T xT,
+                                                             double tq, double (&f)[LV]) {
+    const double ta = a.seg_ta[s], tb = a.seg_tb[s];
+    const double h = tb - ta;
+    const double x64 = xT != xT ? __builtin_nan("") : (tq - ta) / h;
+    const int64_t at = s * a.row_len + el;
+    T qe[LV], qd[LV], qc[LV], qb[LV], qa[LV];
+    load_lanes<T, E, LV>(a.q, at, qe);
+    load_lanes<T, E, LV>(a.q + a.q_plane, at, qd);
+    load_lanes<T, E, LV>(a.q + 2 * a.q_plane, at, qc);
+    load_lanes<T, E, LV>(a.q + 3 * a.q_plane, at, qb);
+    load_lanes<T, E, LV>(a.q + 4 * a.q_plane, at, qa);
+    double p[LV];
+    load_doubles<LV>(a.prefix + at * LV, p);
+#pragma unroll
+    for (int c = 0; c < LV; ++c)
+        f[c] = a.sign * (p[c] + quartic_integral_one((double)qe[c], (double)qd[c], (double)qc[c], (double)qb[c],
+                                                     (double)qa[c], x64, h));
+}
+
+template <typename T, bool VEC, int MODE>
+__global__ __launch_bounds__(kBlock) void row_dense_calc_kernel(const RowDenseCalcArgs<T> a) {
+    using E = typename std::conditional<VEC, typename VecOf<T>::type, T>::type;
+    constexpr int LV = VEC ? VecOf<T>::L : 1;
+    const int64_t stride = (int64_t)gridDim.x * kBlock;
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < a.ne; i += stride) {
+        const int64_t r = i / a.row_len;
+        const int64_t el = i - r * a.row_len;
+        const int64_t s = a.seg[r];
+        if constexpr (MODE == kDenseDerivative) {
+            const int64_t from = s * a.row_len + el;
+            const E d = reinterpret_cast<const E*>(a.q + a.q_plane)[from];
+            const E c = reinterpret_cast<const E*>(a.q + 2 * a.q_plane)[from];
+            const E b = reinterpret_cast<const E*>(a.q + 3 * a.q_plane)[from];
+            const E qa = reinterpret_cast<const E*>(a.q + 4 * a.q_plane)[from];
+            const T x = a.x[r];
+            const T w = (T)(a.sign * (a.seg_tb[s] - a.seg_ta[s]));
+            E tot = d + (c + c) * x;
+            T xp = x * x;
+            tot = tot + (b * (T)3) * xp;
+            xp = xp * x;
+            tot = tot + (qa * (T)4) * xp;
+            reinterpret_cast<E*>(a.out)[i] = tot / w;
+        } else {
+            double f[LV];
+            row_dense_antiderivative_one<T, E, LV>(a, s, el, a.x[r], a.tq[r], f);
+            T o[LV];
+            if constexpr (MODE == kDenseIntegral) {
+                double g[LV];
+                row_dense_antiderivative_one<T, E, LV>(a, a.seg2[r], el, a.x2[r], a.tq2[r], g);
+#pragma unroll
+                for (int c = 0; c < LV; ++c) o[c] = (T)(g[c] - f[c]);
+            } else {
+#pragma unroll
+                for (int c = 0; c < LV; ++c) o[c] = (T)f[c];
+            }
+            E w;
+            __builtin_memcpy(&w, o, sizeof(E));
+            reinterpret_cast<E*>(a.out)[i] = w;
+        }
+    }
 }
 
 }  // namespace tdeq

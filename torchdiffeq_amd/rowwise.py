@@ -858,6 +858,51 @@ class HostRowKernels:
         total = total + a * x4
         return total
 
+    # -- calculus on a dense record (rowwise_dense.py; the arithmetic of tdeq_row_dense_prefix / tdeq_row_dense_calc) -----
+    @staticmethod
+    def _quartic_integral(e, d, c, b, a, x, h):
+        """J_s(x) in fp64 (numpy float64 arrays, every product and sum rounded once); the whole segment is x = 1.0."""
+        return (((((a * 0.2) * x + b * 0.25) * x + c * (1.0 / 3.0)) * x + d * 0.5) * x + e) * x * h
+
+    @staticmethod
+    def quartic_prefix(q, offsets, ta, tb) -> torch.Tensor:
+        """The exclusive prefix of the whole-segment integrals of a record `q` [5, n_seg, L] -> fp64 [n_seg, L]: per row
+        P[offsets[r]] = 0, P[s + 1] = P[s] + I_s, added left to right (step k of every row at once)."""
+        planes = [v.numpy().astype(np.float64) for v in q.unbind(0)]
+        h = (tb.numpy() - ta.numpy())[:, None]
+        whole = HostRowKernels._quartic_integral(*planes, 1.0, h)
+        P = np.zeros_like(whole)
+        off = offsets.numpy()
+        count = np.diff(off)
+        for k in range(1, int(count.max()) if count.size else 0):
+            at = off[:-1][count > k] + k
+            P[at] = P[at - 1] + whole[at - 1]
+        return torch.from_numpy(P)
+
+    @staticmethod
+    def quartic_derivatives(q, src, x, w) -> torch.Tensor:
+        """d/dt of the quartics q[:, src[i], :] at x[i], in the state's type; `w[i]` = T(sign * (tb - ta)) -> [n, L]."""
+        _, d, c, b, a = q[:, src.to(torch.int64)].unbind(0)
+        x1 = x[:, None]
+        total = d + (c + c) * x1
+        xp = x1 * x1
+        total = total + (b * 3) * xp
+        xp = xp * x1
+        total = total + (a * 4) * xp
+        return total / w[:, None]
+
+    @staticmethod
+    def quartic_antiderivatives(q, prefix, ta, tb, sign: float, src, x, tq) -> torch.Tensor:
+        """sign * (P[s] + J_s(x64)) for s = src[i], x64 = (tq[i] - ta[s]) / (tb[s] - ta[s]) in fp64 (NaN where the search
+        marked the query out of range with x[i] = NaN) -> fp64 [n, L], not yet rounded to the state's type."""
+        s = src.numpy().astype(np.int64)
+        planes = [v.numpy().astype(np.float64) for v in q[:, torch.from_numpy(s)].unbind(0)]
+        start, h = ta.numpy()[s], tb.numpy()[s] - ta.numpy()[s]
+        with np.errstate(all="ignore"):
+            x64 = np.where(np.isnan(x.numpy()), np.nan, (tq.numpy().reshape(-1) - start) / h)[:, None]
+            total = sign * (prefix.numpy()[s] + HostRowKernels._quartic_integral(*planes, x64, h[:, None]))
+        return torch.from_numpy(total)
+
     def event_eval_mapped(self, out, dst, q, src, x) -> None:
         """out[dst[i] (None: i), :] = the quartic q[:, src[i]] at x[i], for the index lists `dst`, `src`."""
         if src.numel() == 0:

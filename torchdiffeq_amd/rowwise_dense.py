@@ -14,8 +14,9 @@ adds to a trial step sits between the controller and the commit, because the com
 `tdeq_row_dense_slots` gives every accepted row a slot, `tdeq_row_event_fit_mapped` writes its quartic there.  The
 host keeps an upper bound of the slots taken (a step accepts at most `n_active` rows) and reads the chunk's true counter —
 one word — only when that bound leaves no room.  An evaluation is `tdeq_row_dense_search` (per query: the row's segment
-and the fraction of the step) followed by `tdeq_row_event_eval_mapped`.  CPU states run the same steps as torch / numpy
-ops.
+and the fraction of the step) followed by `tdeq_row_event_eval_mapped`.  The derivative, antiderivative and integral of the
+record are the same search followed by `tdeq_row_dense_calc`; the two integrals read a per-row prefix of whole-step
+integrals that `tdeq_row_dense_prefix` builds on first use.  CPU states run the same steps as torch / numpy ops.
 """
 from __future__ import annotations
 
@@ -158,7 +159,8 @@ class RowDenseStore:
 
 
 class RowDenseOutput:
-    """The piecewise quartic of a rowwise solve; `dense(t)` evaluates it.
+    """The piecewise quartic of a rowwise solve; `dense(t)` evaluates it, `derivative(t)`, `antiderivative(t)` and
+    `integral(ta, tb)` give its time derivative and its integrals in closed form (see `odeint_rowwise_dense`).
 
     Attributes (the wire format, all on the state's device): `t0`, `t1` `[B]` fp64 in true time; `offsets` `[B + 1]` int64;
     `seg_start`, `seg_end` `[n_seg]` fp64 in true time, row r's segments — its accepted steps — contiguous and in step
@@ -173,6 +175,7 @@ class RowDenseOutput:
         self._ta, self._tb = seg_ta, seg_tb
         self.offsets, self.coeffs = offsets, coeffs
         self.n_segments = int(seg_ta.numel())
+        self._prefix = None                                  # fp64 [n_seg, L], built by the first antiderivative / integral
         if p.sign == 1.0:
             self.t0, self.t1, self.seg_start, self.seg_end = self._t0, self._t1, seg_ta, seg_tb
         else:
@@ -258,6 +261,99 @@ class RowDenseOutput:
         out = out.view(Q, *self._shape)
         return out[0] if single else out
 
+    # -- calculus on the record: closed forms of every segment's quartic ---------------------------------------------------
+    def _integral_prefix(self) -> torch.Tensor:
+        """The prefix store `P` fp64 `[n_seg, L]` (8 * L * n_seg bytes), built on first use and kept: per row the exclusive
+        prefix of the whole-segment integrals in solver time, added left to right in fp64."""
+        if self._prefix is None:
+            if self._k is None:
+                self._prefix = rowwise.HostRowKernels.quartic_prefix(self.coeffs, self.offsets, self._ta, self._tb)
+            else:
+                P = torch.empty(self.n_segments, self.coeffs.shape[2], dtype=torch.float64, device=self.coeffs.device)
+                self._k.row_dense_prefix(P, self.coeffs, self.offsets, self._ta, self._tb)
+                self._prefix = P
+        return self._prefix
+
+    def drop_integral_cache(self) -> None:
+        """Release the prefix store of `antiderivative` / `integral`; the next such call rebuilds it (the same bits)."""
+        self._prefix = None
+
+    def _calculus(self, what: str, mode: int, names, ts, check: bool) -> torch.Tensor:
+        """`derivative` (mode 0), `antiderivative` (1), `integral` (2) of the query lists `ts`, in the steps of `dense(t)`:
+        the search per list, one evaluation, one read of the status words (with `check`)."""
+        parsed = [self._queries(t) for t in ts]
+        single = all(one for _, one in parsed)
+        tqs = [tq for tq, _ in parsed]
+        B = self._shape[0]
+        if len(tqs) == 2 and tqs[0].shape[0] != tqs[1].shape[0]:
+            Qa, Qb = tqs[0].shape[0], tqs[1].shape[0]
+            if 1 not in (Qa, Qb):
+                raise ValueError(f"{what}: {names[0]} and {names[1]} hold {Qa} and {Qb} times; they do not broadcast")
+            tqs = [tq.expand(Qa * Qb, B).contiguous() for tq in tqs]      # (one of them is 1: Qa * Qb is the other)
+        Q = tqs[0].shape[0]
+        L, dev, dtype = self.coeffs.shape[2], self.coeffs.device, self.coeffs.dtype
+        out = torch.empty(Q * B, L, dtype=dtype, device=dev)
+        firsts = [_NONE] * len(tqs)
+        if Q > 0:
+            with torch.no_grad(), device_guard(dev):
+                prefix = self._integral_prefix() if mode else None
+                if self._k is None:
+                    H = rowwise.HostRowKernels
+                    found = [self._search_host(tq) for tq in tqs]
+                    firsts = [first for _, _, first in found]
+                    if mode == 0:
+                        seg, x, _ = found[0]
+                        s = seg.numpy().astype(np.int64)
+                        w = (self._sign * (self._tb.numpy()[s] - self._ta.numpy()[s])).astype(x.numpy().dtype)
+                        out.copy_(H.quartic_derivatives(self.coeffs, seg, x, torch.from_numpy(w)))
+                    else:
+                        F = [H.quartic_antiderivatives(self.coeffs, prefix, self._ta, self._tb, self._sign, seg, x, tq)
+                             for (seg, x, _), tq in zip(found, tqs)]
+                        out.copy_((F[0] if mode == 1 else F[1] - F[0]).to(dtype))
+                else:
+                    if Q * B >= _NONE:
+                        raise ValueError(f"{what}: {Q * B} queries in one call; the query index is a 32-bit word")
+                    status = torch.full((len(tqs),), _NONE, dtype=torch.int32, device=dev)
+                    lists = []
+                    for i, tq in enumerate(tqs):
+                        seg = torch.empty(Q * B, dtype=torch.int32, device=dev)
+                        x = torch.empty(Q * B, dtype=dtype, device=dev)
+                        self._k.row_dense_search(tq, self.offsets, self._ta, self._tb, self._t0, self._t1, seg, x,
+                                                 status[i:i + 1])
+                        lists += [seg, x, tq]
+                    self._k.row_dense_calc(out, mode, self.coeffs, self._ta, self._tb, prefix, self._sign, *lists)
+                    if check:
+                        firsts = status.tolist()                          # the one read
+        if check:
+            for name, tq, first in zip(names, tqs, firsts):
+                if first != _NONE:
+                    j, r = divmod(first, B)
+                    raise ValueError("{}: query {} of row {} ({} = {}) is outside the row's interval [t0, t1] = [{}, {}]".format(
+                        what, j, r, name, float(tq[j, r]) * self._sign, float(self.t0[r]), float(self.t1[r])))
+        out = out.view(Q, *self._shape)
+        return out[0] if single else out
+
+    def derivative(self, t, check: bool = True) -> torch.Tensor:
+        """`dy_r/dt` of the interpolant at `t`, with respect to TRUE time (also for a descending solve), in the query forms
+        and with the `check` of `dense(t)`.  Inside a step that is the quartic's derivative `(d + 2 c x + 3 b x^2 + 4 a x^3) /
+        (tb - ta)` in the state's type; a breakpoint belongs to the earlier step, so at a breakpoint — a dose time of
+        `jump_dy` included — the value is the LEFT derivative.  Never builds the prefix store."""
+        return self._calculus("dense.derivative(t)", 0, ("t",), (t,), check)
+
+    def antiderivative(self, t, check: bool = True) -> torch.Tensor:
+        """`F_r(t)` = the integral of `y_r` from `t0[r]` to `t` in true time (`F_r(t0[r]) == 0` exactly), computed in fp64 —
+        the prefix of the whole-step integrals before the query's step, added left to right, plus the closed-form integral
+        of its quartic up to `t` — and rounded once to the state's type.  Query forms and `check` as `dense(t)`; the first
+        call builds the prefix store (fp64 `[n_seg, L]`), see `drop_integral_cache`."""
+        return self._calculus("dense.antiderivative(t)", 1, ("t",), (t,), check)
+
+    def integral(self, ta, tb, check: bool = True) -> torch.Tensor:
+        """The integral of `y_r` from `ta` to `tb` in true time: `T(F64(tb) - F64(ta))`, the difference of the two fp64
+        antiderivatives rounded once, so `integral(a, b) == -integral(b, a)` bit for bit and `integral(a, a) == 0`.  `ta` and
+        `tb` each take the query forms of `dense(t)` and broadcast against each other; both must lie inside `[t0[r], t1[r]]`
+        (`check=True` names the offending query of `ta` first, then of `tb`; `check=False` gives NaN rows)."""
+        return self._calculus("dense.integral(ta, tb)", 2, ("ta", "tb"), (ta, tb), check)
+
 
 def odeint_rowwise_dense(func, y0, t0, t1, *, rtol=1e-7, atol=1e-9, method="dopri5", options=None, compact=None,
                          return_stats=False):
@@ -288,6 +384,18 @@ def odeint_rowwise_dense(func, y0, t0, t1, *, rtol=1e-7, atol=1e-9, method="dopr
     ValueError that names the smallest flat query index `(j, r)` (one word read from the device), with `check=False` an
     all-NaN row and no host read.
 
+    Calculus on the record: `dense.derivative(t)`, `dense.antiderivative(t)` and `dense.integral(ta, tb)` take the query
+    forms, the valid interval and `check` of `dense(t)`, with respect to TRUE time (also for `t1 < t0`).  The derivative is the
+    quartic's, in the state's dtype: `(d + (c + c) x + (3 b) x^2 + (4 a) x^3) / T(tb - ta)`; a breakpoint belongs to the
+    earlier step, so at a breakpoint — a dose time of `jump_dy` included — it is the LEFT derivative.  The antiderivative
+    `F_r(t)`, the integral of `y_r` from `t0[r]`, is formed in fp64 and rounded once: per row the whole-step integrals of
+    the steps before the query's, added left to right (that order is part of the contract: a row's bits depend neither on B
+    nor on the backend), plus the closed-form integral of the query's quartic up to `x64 = (tq - ta) / (tb - ta)`, the fraction
+    NOT rounded to the state's dtype; `F_r(t0[r]) == 0`.  `integral(ta, tb) = T(F64(tb) - F64(ta))`, the difference in fp64:
+    `integral(a, b) == -integral(b, a)` bit for bit, `integral(a, a) == 0`; `ta` and `tb` broadcast against each other, both
+    must be in range (`check=True` names the offending query of `ta` first, then of `tb`).  A ROCm state runs them on HIP
+    kernels (`tdeq_row_dense_prefix`, `tdeq_row_dense_calc`, ABI 31), a CPU state as numpy / torch ops with the same bits.
+
     Returns `dense`; with `return_stats=True`, `(dense, stats)`: the stats of `odeint_rowwise` (`n_accepted`,
     `n_rejected`, `nfe`; with `compact` also `row_evals`, `n_repacks`) plus `n_segments` and `n_chunks`.
 
@@ -295,9 +403,12 @@ def odeint_rowwise_dense(func, y0, t0, t1, *, rtol=1e-7, atol=1e-9, method="dopr
     per segment.  During the solve the quartics sit in chunks of `cap` slots (`5 * L * cap` elements each, by default
     `cap = max(B, min(4 B, 256 MiB of coefficients))`): every chunk but the last is full to within one trial step's accepted
     rows.  Every chunk lives until the solve ends; the pack then allocates the result and releases the chunks one by one, so
-    the PEAK is the result plus all chunks — about twice the result.
+    the PEAK is the result plus all chunks — about twice the result.  `antiderivative` and `integral` add a prefix store of
+    `8 * L * n_seg` bytes (fp64 `[n_seg, L]`: 40 % on top of an fp32 record), built by the first such call, kept on the object
+    and released by `dense.drop_integral_cache()`; `dense(t)` and `derivative` never build it.
 
-    Out of scope (raises or is not offered): gradients through the solve or through `dense(t)` (with grad mode on and
+    Out of scope (raises or is not offered): gradients through the solve, through `dense(t)` or through the three methods
+    above (with grad mode on and
     `y0`, `t0`, `t1`, a query tensor or a parameter of `func` requiring grad: NotImplementedError; there is no
     `differentiable` argument), events combined with dense output, 16-bit / complex / tuple states (ValueError), captured
     (hipGraph) steps, extrapolation outside `[t0[r], t1[r]]`, and the per-row adjoint this record is meant to serve.
