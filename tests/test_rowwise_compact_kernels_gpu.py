@@ -9,6 +9,7 @@ import torch
 
 from _rowwise_compact_oracle import CompactOracle
 from _rowwise_kernels import SENTINEL, RowVectors, lane_elems, row_lengths, seeded
+from test_rowwise_kernels_gpu import WIDE_MID
 
 from torchdiffeq_amd.rowwise import _METHODS
 from torchdiffeq_amd.tableaus import SparseRow
@@ -140,13 +141,13 @@ def test_row_dense_commit_mapped(hip_kernels, oracle_kernels, dtype):
     accepted rows, every other word — unmapped solution rows, other slots, the guards — untouched."""
     oracle = CompactOracle(oracle_kernels)
     lv = lane_elems(dtype)
-    cases = [(m, L) for m in METHODS for L in (5, 8 * lv)]
+    cases = [(m, L) for m in METHODS + [WIDE_MID] for L in (5, 8 * lv)]               # (WIDE_MID: 14 terms)
     cases += [("dopri5", L) for L in row_lengths(dtype, (1, 3, 17, 257, 1024, 1500, 2049))]
     seen = set()
     for n, (method, L) in enumerate(cases):
         kinds = [(n + r) % 4 for r in range(3)]
         seen |= set(kinds)
-        mid = SparseRow.from_dense(_METHODS[method].tableau.c_mid)
+        mid = SparseRow.from_dense(method if method is WIDE_MID else _METHODS[method].tableau.c_mid)
         (dev, ref), (y0, y1, f0, f1), state = _run_mapped(hip_kernels, oracle, L, dtype, mid, kinds, L + n)
         for name, g, e in zip(("sol", "y0", "f0"), dev, ref):
             assert torch.equal(g, e), (method, L, kinds, name)

@@ -38,8 +38,8 @@ def _i32(values, device):
     return torch.tensor(values, dtype=torch.int32, device=device)
 
 
-# the term counts of c_mid: bosh3 / fehlberg2 / adaptive_heun 1, dopri5 6, tsit5 7, dopri8 10
-@pytest.mark.parametrize("nt", [1, 6, 7, 10])
+# the term counts of c_mid: bosh3 / fehlberg2 / adaptive_heun 1, dopri5 6, tsit5 7, dopri8 10; 14: the most the entry point takes
+@pytest.mark.parametrize("nt", [1, 6, 7, 10, 14])
 @pytest.mark.parametrize("dtype", [F64, F32], ids=["f64", "f32"])
 @pytest.mark.parametrize("L", [3, 8, 1028])
 def test_fit_mapped_and_eval_mapped(L, dtype, nt, hip_kernels, oracle):

@@ -104,8 +104,8 @@ def _borders_intact(buf):
     return bool((buf[:BORDER] == SENTINEL).all()) and bool((buf[-BORDER:] == SENTINEL).all())
 
 
-# the term counts of c_mid: bosh3 / fehlberg2 / adaptive_heun 1, dopri5 6, tsit5 7, dopri8 10
-@pytest.mark.parametrize("nt", [1, 6, 7, 10])
+# the term counts of c_mid: bosh3 / fehlberg2 / adaptive_heun 1, dopri5 6, tsit5 7, dopri8 10; 14: the most the entry point takes
+@pytest.mark.parametrize("nt", [1, 6, 7, 10, 14])
 @pytest.mark.parametrize("dtype", [F64, F32], ids=["f64", "f32"])
 @pytest.mark.parametrize("L", [3, 8, 1028])
 def test_fit_and_eval(L, dtype, nt, hip_kernels, oracle):

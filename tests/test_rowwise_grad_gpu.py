@@ -70,13 +70,14 @@ def test_row_multi_dot(L, dtype):
     for r in (0, B // 2, B - 1):
         one = kern.row_multi_dot(g[r:r + 1].clone(), [x[r:r + 1].clone() for x in xs])
         assert torch.equal(one[:, 0], out[:, r]), (L, r)
-    # 14 inputs in one launch
+    # 14 inputs in one launch, and 1: the most and the fewest the entry point takes
     many = [_rows(5, L, dtype, 200 + m) for m in range(14)]
     g5 = _rows(5, L, dtype, 7)
-    out = kern.row_multi_dot(g5, many)
-    for m in range(14):
-        prod = g5.double() * many[m].double()
-        assert bool(((out[m] - prod.sum(dim=1)).abs() <= (L + 1) * 2.0 ** -53 * prod.abs().sum(dim=1) + 1e-300).all())
+    for xs in (many, many[:1]):
+        out = kern.row_multi_dot(g5, xs)
+        for m in range(len(xs)):
+            prod = g5.double() * xs[m].double()
+            assert bool(((out[m] - prod.sum(dim=1)).abs() <= (L + 1) * 2.0 ** -53 * prod.abs().sum(dim=1) + 1e-300).all())
 
 
 def test_row_kernels_empty_and_invalid():
@@ -88,6 +89,9 @@ def test_row_kernels_empty_and_invalid():
     assert lib.tdeq_row_scale_many(ptrs, 1, g.data_ptr(), g.data_ptr(), 0, 4, 0, None) == 0
     assert lib.tdeq_row_scale_many(ptrs, 1, g.data_ptr(), g.data_ptr(), 4, 0, 0, None) == 0
     assert lib.tdeq_row_scale_many(ptrs, 15, g.data_ptr(), g.data_ptr(), 4, 4, 0, None) == -1
+    assert lib.tdeq_row_scale_many(ptrs, 0, g.data_ptr(), g.data_ptr(), 4, 4, 0, None) == -1
+    for n_x in (0, 15):
+        assert lib.tdeq_row_multi_dot(g.data_ptr(), ptrs, n_x, 4, 4, out.data_ptr(), None, 0, 0, None) == -1
     assert lib.tdeq_row_multi_dot(g.data_ptr(), ptrs, 1, 0, 4, out.data_ptr(), None, 0, 0, None) == 0
     assert lib.tdeq_row_multi_dot(g.data_ptr(), ptrs, 1, 4, 0, out.data_ptr(), None, 0, 0, None) == 0
     torch.cuda.synchronize()

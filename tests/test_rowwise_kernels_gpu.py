@@ -185,14 +185,15 @@ def test_row_combine_lengths(hip_kernels, oracle_kernels, dtype):
 RTOL_, ATOL_ = 1e-3, 1e-4
 
 
-def _reduce_case(mode, with_partial, B, L, dtype, seed):
-    """Arguments of row_reduce after `part`, on the CPU."""
-    y0, ks, dts, active = _row_inputs(B, L, dtype, seed, 3)
+def _reduce_case(mode, with_partial, B, L, dtype, seed, nt=None):
+    """Arguments of row_reduce after `part`, on the CPU; `nt` error terms (2 after a `partial`, 3 without one)."""
+    n = nt or (2 if with_partial else 3)
+    y0, ks, dts, active = _row_inputs(B, L, dtype, seed, max(n, 3))
     y1 = y0 + seeded((B, L), dtype, seed + 50, 0.01)
     partial = seeded((B, L), dtype, seed + 51, 1e-3)
     if mode == 0:
-        n = 2 if with_partial else 3
-        return [y0, y1, partial if with_partial else None, ks[:n], [0.37, -1.25, 0.0625][:n], dts, active]
+        coefs = [0.37, -1.25, 0.0625] + [0.03125 * (j - 8) for j in range(3, 14)]
+        return [y0, y1, partial if with_partial else None, ks[:n], coefs[:n], dts, active]
     return [y0, y1, partial, [], [], None, None]
 
 
@@ -255,6 +256,20 @@ def test_row_reduce_sums_and_census(hip_kernels, oracle_kernels, mode, with_part
                          else a for a in args]
                 one = _device_reduce(hip_kernels, mode, alone, 1, nch)
                 assert _bits_equal(one[:, 0], got[:, r]), (mode, L, B, r)
+
+
+@pytest.mark.parametrize("dtype", DTYPES, ids=IDS)
+def test_row_reduce_term_counts(hip_kernels, oracle_kernels, dtype):
+    """1 and 14 error terms, the fewest and the most the entry point takes (the cases above have 2 and 3), with and
+    without `partial`, 3 rows of one 16-byte element and of 5 scalar ones: the bounds of the test above."""
+    for nt in (1, 14):
+        for L in (lane_elems(dtype), 5):
+            for with_partial in (False, True):
+                args = _reduce_case(0, with_partial, 3, L, dtype, nt + L, nt)
+                ref = torch.zeros(3 * 3, dtype=torch.float64)
+                oracle_kernels.row_reduce(0, ref, *args, RTOL_, ATOL_)
+                got = _device_reduce(hip_kernels, 0, args, 3, 1)
+                _check_sums(got, ref.view(3, 3, 1), L, (nt, L, with_partial))
 
 
 @pytest.mark.parametrize("dtype", DTYPES, ids=IDS)
@@ -538,6 +553,9 @@ def _dense_rows(B, seed):
     return tgrid, state, n_out
 
 
+WIDE_MID = tuple(0.0625 * (j - 6.5) for j in range(14))           # a c_mid row no method has: 14 non-zero terms
+
+
 def _run_dense(kern, oracle, B, L, dtype, mid, seed, offset=0):
     tgrid, state, n_out = _dense_rows(B, seed)
     n_streams = max(mid.idx) + 1
@@ -561,12 +579,13 @@ def _run_dense(kern, oracle, B, L, dtype, mid, seed, offset=0):
 def test_row_dense_commit(hip_kernels, oracle_kernels, dtype):
     """Rows accepted with 0, 1 and 3 output times and rows not accepted: the oracle's quartic bit for bit, y0 <- y1 and
     f0 <- f1 exactly for the accepted rows, every other word (rows, solution slots, the guards) untouched; c_mid of all
-    six methods; 16-byte and scalar L; buffers one element off alignment equal to the aligned run."""
+    six methods (1, 6, 7 and 10 terms) and a row of 14 terms, the most the entry point takes; 16-byte and scalar L; buffers
+    one element off alignment equal to the aligned run."""
     lv = lane_elems(dtype)
-    cases = [(m, L, B) for m in METHODS for L, B in ((5, 7), (8 * lv, 7))]
+    cases = [(m, L, B) for m in METHODS + [WIDE_MID] for L, B in ((5, 7), (8 * lv, 7))]
     cases += [("dopri5", L, B) for L in row_lengths(dtype, (1, 3, 17, 257, 1024, 1500, 2049)) for B in _batches(L, dtype)]
     for method, L, B in cases:
-        mid = SparseRow.from_dense(_METHODS[method].tableau.c_mid)
+        mid = SparseRow.from_dense(method if method is WIDE_MID else _METHODS[method].tableau.c_mid)
         (dev, ref), (y0, y1, f0, f1), state = _run_dense(hip_kernels, oracle_kernels, B, L, dtype, mid, L + B)
         for name, g, e in zip(("sol", "y0", "f0"), dev, ref):
             assert torch.equal(g, e), (method, L, B, name)

@@ -297,6 +297,16 @@ def test_row_dense_commit_argument_errors(lib):
     assert call(st=st) == 0
 
 
+def test_row_scale_many_and_multi_dot_term_counts(lib):
+    """The term counts of the two backward entry points (tests/test_rowwise_grad_gpu.py has their other answers)."""
+    buf, p, ptrs = _buffers()
+    for n in (0, 15, -1):
+        assert lib.tdeq_row_scale_many(ptrs, n, p, p, 2, 4, F64, None) == EINVAL, n
+        assert lib.tdeq_row_multi_dot(p, ptrs, n, 2, 4, p, None, 0, F64, None) == EINVAL, n
+    assert lib.tdeq_row_scale_many(ptrs, 14, p, p, 0, 4, F64, None) == 0
+    assert lib.tdeq_row_multi_dot(p, ptrs, 14, 0, 4, p, None, 0, F64, None) == 0
+
+
 # (L, dtype code) -> partials per row: short rows, the one-chunk long rows, chunked rows
 _PARTIALS = [(1, F32, 1), (1, F64, 1), (3, F32, 1), (4, F32, 1), (1024, F32, 1), (1024, F64, 1), (1023, F64, 1),
              (4096, F32, 1), (2048, F64, 1),                       # nv = 1024: the top of the short rows

@@ -91,6 +91,22 @@ def test_row_reduce_tol(hip_kernels, oracle_kernels, mode, with_partial, dtype):
 
 
 @pytest.mark.parametrize("dtype", DTYPES, ids=IDS)
+def test_row_reduce_tol_term_counts(hip_kernels, oracle_kernels, dtype):
+    """1 and 14 error terms, the fewest and the most the entry point takes (the cases above have 2 and 3), with and
+    without `partial`, 3 rows of one 16-byte element and of 5 scalar ones: (a) of the test above."""
+    oracle = TolOracle(oracle_kernels)
+    for nt in (1, 14):
+        for L in (lane_elems(dtype), 5):
+            for with_partial in (False, True):
+                args = _reduce_case(0, with_partial, 3, L, dtype, nt + L, nt)
+                rtol, atol = _row_tolerances(3, dtype, nt + L)
+                ref = torch.zeros(3 * 3, dtype=torch.float64)
+                oracle.row_reduce_tol(0, ref, *args, rtol, atol)
+                got = _device_reduce_tol(hip_kernels, 0, args, 3, 1, rtol, atol)
+                _check_sums(got, ref.view(3, 3, 1), L, (nt, L, with_partial))
+
+
+@pytest.mark.parametrize("dtype", DTYPES, ids=IDS)
 @pytest.mark.parametrize("mode,with_partial", MODES, ids=["err", "err_partial", "init01", "init2"])
 def test_row_reduce_tol_scalar_fallback(hip_kernels, mode, with_partial, dtype):
     """A scalar-element row on buffers one element off 16-byte alignment gives the bits of the aligned run; a row of

@@ -10,10 +10,82 @@
 namespace {
 using namespace tdeq;
 
+// ---- the run-time choices of a launch, each written once: every helper calls f with a tag and returns its status -----
+inline bool row_dtype_ok(int dtype) { return dtype == TDEQ_F32 || dtype == TDEQ_F64; }
+
+// f(T{}), T = float or double
+template <typename F>
+int row_dtype(int dtype, F f) {
+    return dtype == TDEQ_F32 ? f(float{}) : f(double{});
+}
+
+// f(std::true_type{}) or f(std::false_type{}): one bool template argument of a kernel
+template <typename F>
+int row_bool(bool b, F f) {
+    return b ? f(std::true_type{}) : f(std::false_type{});
+}
+
+// f(std::integral_constant<int, N>{}) for LO <= N = nt <= 14: the only switch over the term count
+template <int LO, typename F>
+int row_terms(int nt, F f) {
+    switch (nt) {
+#define TDEQ_CASE(N) case N: if constexpr (N >= LO) return f(std::integral_constant<int, N>{}); break;
+        TDEQ_CASE(0) TDEQ_CASE(1) TDEQ_CASE(2) TDEQ_CASE(3) TDEQ_CASE(4) TDEQ_CASE(5) TDEQ_CASE(6) TDEQ_CASE(7)
+        TDEQ_CASE(8) TDEQ_CASE(9) TDEQ_CASE(10) TDEQ_CASE(11) TDEQ_CASE(12) TDEQ_CASE(13) TDEQ_CASE(14)
+#undef TDEQ_CASE
+    }
+    return TDEQ_EINVAL;
+}
+
+// f(T{}, std::integral_constant<int, N>{}): what a term-templated entry point launches through
+template <int LO, typename F>
+int row_dtype_terms(int dtype, int nt, F f) {
+    return row_dtype(dtype, [&](auto t) { return row_terms<LO>(nt, [&](auto n) { return f(t, n); }); });
+}
+
+// ---- the 16-byte decision ---------------------------------------------------------------------------------------------
 // 16-byte elements when a row is a whole number of them (an element then never straddles two rows)
-inline int row_lanes(int64_t row_len, int dtype) {
-    const int lv = dtype == TDEQ_F32 ? 4 : 2;
-    return row_len % lv == 0 ? lv : 1;
+template <typename T>
+int row_lanes(int64_t row_len) {
+    return row_len % VecOf<T>::L == 0 ? VecOf<T>::L : 1;
+}
+
+struct RowPtrs {                      // an array of n pointers: k[], outs[], x[]
+    const void* const* p;
+    int n;
+};
+
+inline bool row_aligned16(const void* p) { return aligned16(p); }      // (so is a null pointer: an input that is absent)
+inline bool row_aligned16(RowPtrs a) {
+    for (int j = 0; j < a.n; ++j) if (!aligned16(a.p[j])) return false;
+    return true;
+}
+
+// are all of these pointers (and every pointer of these arrays) 16-byte aligned
+template <typename... P>
+bool row_aligned(P... p) {
+    return (row_aligned16(p) && ...);
+}
+
+// A launch takes 16-byte elements when the row is a whole number of them and every pointer is `aligned`: row_len_e
+// becomes the row length in the launch's elements, and f(std::bool_constant<VEC>{}) launches.
+template <typename T, typename F>
+int row_vec(int64_t row_len, bool aligned, int64_t& row_len_e, F f) {
+    const int lv = row_lanes<T>(row_len);
+    const bool vec = lv > 1 && aligned;
+    row_len_e = vec ? row_len / lv : row_len;
+    return row_bool(vec, f);
+}
+
+// The same decision for the copy-style kernels, which are templated on the element alone: f(E{}, row_len_e) with
+// E = T or VecOf<T>::type.
+template <typename F>
+int row_elem(int dtype, int64_t row_len, bool aligned, F f) {
+    return row_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        const int lv = row_lanes<T>(row_len);
+        return lv > 1 && aligned ? f(typename VecOf<T>::type{}, row_len / lv) : f(t, row_len);
+    });
 }
 
 // Reduction geometry of a row: a function of (L, dtype) only, so that a row's sums never depend on B.
@@ -25,9 +97,10 @@ struct RowGeom {
     int64_t nch;      // partials per row
 };
 
-inline RowGeom row_geom(int64_t row_len, int dtype) {
+template <typename T>
+RowGeom row_geom(int64_t row_len) {
     RowGeom g;
-    g.lv = row_lanes(row_len, dtype);
+    g.lv = row_lanes<T>(row_len);
     g.nv = row_len / g.lv;
     if (g.nv <= kRowWaveMax) {
         const int64_t want = (g.nv + 3) / 4;
@@ -44,11 +117,8 @@ inline RowGeom row_geom(int64_t row_len, int dtype) {
     return g;
 }
 
-template <typename T, int NT, bool VEC>
-int launch_row_combine(const RowMultiArgs<T, NT>& a, hipStream_t s) {
-    constexpr int LV = VEC ? VecOf<T>::L : 1;
-    hipLaunchKernelGGL((row_combine_kernel<T, NT, VEC>), dim3(stream_grid(a.n / LV, kBlock)), dim3(kBlock), 0, s, a);
-    return check_launch();
+inline RowGeom row_geom(int64_t row_len, int dtype) {
+    return dtype == TDEQ_F32 ? row_geom<float>(row_len) : row_geom<double>(row_len);
 }
 
 template <typename T, int NT>
@@ -59,59 +129,44 @@ int row_combine_n(const tdeq_multi_out* outs, int n_out, const void* y0, const v
     a.acc_in = static_cast<const T*>(acc_in);
     for (int j = 0; j < NT; ++j) a.k[j] = static_cast<const T*>(k[j]);
     a.add_y0 = 0;
+    bool aligned = row_aligned(y0, acc_in, RowPtrs{k, NT});
     for (int o = 0; o < kMaxMultiOut; ++o) {
         const bool live = o < n_out;
         a.out[o] = live ? static_cast<T*>(outs[o].out) : nullptr;
         a.mask[o] = live ? outs[o].mask : 0u;
         if (live && outs[o].add_y0) a.add_y0 |= 1u << o;
         for (int j = 0; j < NT; ++j) a.c[o][j] = live ? (T)outs[o].coef[j] : (T)0;
+        aligned = aligned && aligned16(a.out[o]);
     }
     a.n_out = n_out;
     a.dts = static_cast<const T*>(dts);
     a.active = active;
     a.n = n_rows * row_len;
-    const int lv = row_lanes(row_len, std::is_same<T, float>::value ? TDEQ_F32 : TDEQ_F64);
-    bool vec = lv > 1 && aligned16(y0) && (!acc_in || aligned16(acc_in));
-    for (int j = 0; j < NT; ++j) vec = vec && aligned16(k[j]);
-    for (int o = 0; o < n_out; ++o) vec = vec && aligned16(outs[o].out);
-    if (vec) {
-        a.row_len = row_len / lv;
-        return launch_row_combine<T, NT, true>(a, s);
-    }
-    a.row_len = row_len;
-    return launch_row_combine<T, NT, false>(a, s);
-}
-
-template <typename T>
-int row_combine_dispatch(const tdeq_multi_out* outs, int n_out, const void* y0, const void* acc_in,
-                         const void* const* k, int nt, const void* dts, const int32_t* active, int64_t n_rows,
-                         int64_t row_len, hipStream_t s) {
-    switch (nt) {
-#define TDEQ_CASE(N) case N: return row_combine_n<T, N>(outs, n_out, y0, acc_in, k, dts, active, n_rows, row_len, s);
-        TDEQ_CASE(1) TDEQ_CASE(2) TDEQ_CASE(3) TDEQ_CASE(4) TDEQ_CASE(5) TDEQ_CASE(6) TDEQ_CASE(7)
-        TDEQ_CASE(8) TDEQ_CASE(9) TDEQ_CASE(10) TDEQ_CASE(11) TDEQ_CASE(12) TDEQ_CASE(13) TDEQ_CASE(14)
-#undef TDEQ_CASE
-    }
-    return TDEQ_EINVAL;
+    return row_vec<T>(row_len, aligned, a.row_len, [&](auto vec) {
+        hipLaunchKernelGGL((row_combine_kernel<T, NT, decltype(vec)::value>), dim3(stream_grid(n_rows * a.row_len, kBlock)),
+                           dim3(kBlock), 0, s, a);
+        return check_launch();
+    });
 }
 
 template <typename T, int NT, int MODE, bool PARTIAL, bool ROWTOL>
 int row_reduce_launch(RowRedArgsOf<T, NT, ROWTOL>& a, const RowGeom& g, bool vec, hipStream_t s) {
-    if (g.group > 0) {                // short row; a long row of one chunk (1024 < nv <= 2048) takes the chunk kernel,
-        const int64_t threads = a.n_rows * g.group;      // whose part[q * B + r] is what the lane-per-row controller reads
-        const dim3 grid((unsigned)((threads + kBlock - 1) / kBlock));
-        a.group = g.group;
-        a.nch = 1;
-        if (vec) hipLaunchKernelGGL((row_reduce_wave_kernel<T, NT, MODE, PARTIAL, true, ROWTOL>), grid, dim3(kBlock), 0, s, a);
-        else hipLaunchKernelGGL((row_reduce_wave_kernel<T, NT, MODE, PARTIAL, false, ROWTOL>), grid, dim3(kBlock), 0, s, a);
-    } else {
-        a.chunk = g.chunk;
-        a.nch = (int)g.nch;
-        const dim3 grid((unsigned)(a.n_rows * g.nch));
-        if (vec) hipLaunchKernelGGL((row_reduce_chunk_kernel<T, NT, MODE, PARTIAL, true, ROWTOL>), grid, dim3(kBlock), 0, s, a);
-        else hipLaunchKernelGGL((row_reduce_chunk_kernel<T, NT, MODE, PARTIAL, false, ROWTOL>), grid, dim3(kBlock), 0, s, a);
-    }
-    return check_launch();
+    return row_bool(vec, [&](auto v) {
+        constexpr bool VEC = decltype(v)::value;
+        if (g.group > 0) {            // short row; a long row of one chunk (1024 < nv <= 2048) takes the chunk kernel,
+            const int64_t threads = a.n_rows * g.group;  // whose part[q * B + r] is what the lane-per-row controller reads
+            const dim3 grid((unsigned)((threads + kBlock - 1) / kBlock));
+            a.group = g.group;
+            a.nch = 1;
+            hipLaunchKernelGGL((row_reduce_wave_kernel<T, NT, MODE, PARTIAL, VEC, ROWTOL>), grid, dim3(kBlock), 0, s, a);
+        } else {
+            a.chunk = g.chunk;
+            a.nch = (int)g.nch;
+            const dim3 grid((unsigned)(a.n_rows * g.nch));
+            hipLaunchKernelGGL((row_reduce_chunk_kernel<T, NT, MODE, PARTIAL, VEC, ROWTOL>), grid, dim3(kBlock), 0, s, a);
+        }
+        return check_launch();
+    });
 }
 
 // The tolerances of one reduce launch: the two scalars of tdeq_row_reduce, or the two [n_rows] device vectors of
@@ -126,7 +181,7 @@ template <typename T, int NT, bool ROWTOL>
 int row_reduce_n(int mode, const void* y0, const void* y1, const void* partial, const void* const* k,
                  const double* coef, const void* dts, const int32_t* active, const RowTols& tol, int64_t n_rows,
                  int64_t row_len, double* part, hipStream_t s) {
-    const RowGeom g = row_geom(row_len, std::is_same<T, float>::value ? TDEQ_F32 : TDEQ_F64);
+    const RowGeom g = row_geom<T>(row_len);
     RowRedArgsOf<T, NT, ROWTOL> a;
     a.y0 = static_cast<const T*>(y0);
     a.y1 = static_cast<const T*>(y1);
@@ -152,8 +207,7 @@ int row_reduce_n(int mode, const void* y0, const void* y1, const void* partial, 
     a.nch = (int)g.nch;
     a.group = g.group;
     a.part = part;
-    bool vec = g.lv > 1 && aligned16(y0) && aligned16(y1) && (!partial || aligned16(partial));
-    for (int j = 0; j < NT; ++j) vec = vec && aligned16(k[j]);
+    const bool vec = g.lv > 1 && row_aligned(y0, y1, partial, RowPtrs{k, NT});
     if (g.lv > 1 && !vec) return TDEQ_EINVAL;      // (the geometry, hence the sums, must not depend on alignment)
     if constexpr (NT == 0) {
         if (mode == 1) return row_reduce_launch<T, NT, 1, false, ROWTOL>(a, g, vec, s);
@@ -166,31 +220,24 @@ int row_reduce_n(int mode, const void* y0, const void* y1, const void* partial, 
     }
 }
 
-template <typename T, bool ROWTOL>
-int row_reduce_dispatch(int mode, const void* y0, const void* y1, const void* partial, const void* const* k,
-                        const double* coef, int nt, const void* dts, const int32_t* active, const RowTols& tol,
-                        int64_t n_rows, int64_t row_len, double* part, hipStream_t s) {
-    switch (nt) {
-#define TDEQ_CASE(N) case N: return row_reduce_n<T, N, ROWTOL>(mode, y0, y1, partial, k, coef, dts, active, tol, n_rows, row_len, part, s);
-        TDEQ_CASE(0) TDEQ_CASE(1) TDEQ_CASE(2) TDEQ_CASE(3) TDEQ_CASE(4) TDEQ_CASE(5) TDEQ_CASE(6) TDEQ_CASE(7)
-        TDEQ_CASE(8) TDEQ_CASE(9) TDEQ_CASE(10) TDEQ_CASE(11) TDEQ_CASE(12) TDEQ_CASE(13) TDEQ_CASE(14)
-#undef TDEQ_CASE
-    }
-    return TDEQ_EINVAL;
-}
-
-// the argument checks the two reduce entry points share; > 0: nothing to do (no row)
-inline int row_reduce_check(int mode, const void* y0, const void* y1, const void* partial, const void* const* k,
-                            const double* coef, int n_terms, const void* dts, const int32_t* active, int64_t n_rows,
-                            int64_t row_len, const double* part, size_t part_bytes, int dtype) {
-    if (!y0 || !y1 || !part || n_rows < 0 || row_len < 1 || !(dtype == TDEQ_F32 || dtype == TDEQ_F64)) return TDEQ_EINVAL;
+// what the two reduce entry points share: the argument checks (> 0: nothing to do, no row), then the launch
+template <bool ROWTOL>
+int row_reduce_entry(int mode, const void* y0, const void* y1, const void* partial, const void* const* k,
+                     const double* coef, int n_terms, const void* dts, const int32_t* active, const RowTols& tol,
+                     int64_t n_rows, int64_t row_len, double* part, size_t part_bytes, int dtype, void* stream) {
+    if (!y0 || !y1 || !part || n_rows < 0 || row_len < 1 || !row_dtype_ok(dtype)) return TDEQ_EINVAL;
     if (mode < 0 || mode > 2 || n_terms < 0 || n_terms > TDEQ_MAX_TERMS) return TDEQ_EINVAL;
     if (mode == 0 && (n_terms < 1 || !k || !coef || !dts || !active)) return TDEQ_EINVAL;
     if (mode != 0 && (n_terms != 0 || !partial)) return TDEQ_EINVAL;
     for (int j = 0; j < n_terms; ++j) if (!k[j]) return TDEQ_EINVAL;
     const int64_t nch = row_geom(row_len, dtype).nch;
     if (part_bytes < (size_t)(3 * n_rows * nch) * sizeof(double)) return TDEQ_EWORKSPACE;
-    return n_rows == 0 ? 1 : 0;
+    if (n_rows == 0) return 0;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return row_dtype_terms<0>(dtype, n_terms, [&](auto t, auto n) {
+        return row_reduce_n<decltype(t), decltype(n)::value, ROWTOL>(mode, y0, y1, partial, k, coef, dts, active, tol,
+                                                                     n_rows, row_len, part, s);
+    });
 }
 
 // one wave per row when a row has several partials to add, one lane per row otherwise
@@ -206,27 +253,30 @@ int row_control_launch(const RowCtrlArgsOf<POINTS>& a, hipStream_t s) {
     return check_launch();
 }
 
-template <typename T, int NT, bool VEC>
-int launch_row_dense(const RowDenseArgs<T, NT>& a, hipStream_t s) {
-    constexpr int LV = VEC ? VecOf<T>::L : 1;
-    hipLaunchKernelGGL((row_dense_commit_kernel<T, NT, VEC>), dim3(stream_grid(a.n / LV, kBlock)), dim3(kBlock), 0, s, a);
-    return check_launch();
-}
-
-template <typename T, int NT>
-int row_dense_n(void* sol, void* y0, const void* y1, void* f0, const void* f1, const void* const* k, const double* coef,
-                const void* dts, const tdeq_row_state* st, hipStream_t s) {
-    RowDenseArgs<T, NT> a;
-    a.sol = static_cast<T*>(sol);
-    a.y0 = static_cast<T*>(y0);
+// The inputs of a step's quartic, which the dense-commit and event-fit argument blocks name alike (P = void where the
+// kernel also writes y0 and f0, const void where it only reads them); their 16-byte decision includes the output.
+template <typename T, int NT, typename A, typename P>
+bool row_quartic_args(A& a, const void* out, P* y0, const void* y1, P* f0, const void* f1, const void* const* k,
+                      const double* coef, const void* dts) {
+    a.y0 = static_cast<decltype(a.y0)>(y0);
     a.y1 = static_cast<const T*>(y1);
-    a.f0 = static_cast<T*>(f0);
+    a.f0 = static_cast<decltype(a.f0)>(f0);
     a.f1 = static_cast<const T*>(f1);
     for (int j = 0; j < NT; ++j) {
         a.k[j] = static_cast<const T*>(k[j]);
         a.c[j] = (T)coef[j];
     }
     a.dts = static_cast<const T*>(dts);
+    return row_aligned(out, y0, y1, f0, f1, RowPtrs{k, NT});
+}
+
+// tdeq_row_dense_commit and (MAPPED: row_map, sol_rows) tdeq_row_dense_commit_mapped
+template <typename T, int NT, bool MAPPED>
+int row_dense_n(void* sol, const int32_t* row_map, int64_t sol_rows, void* y0, const void* y1, void* f0, const void* f1,
+                const void* const* k, const double* coef, const void* dts, const tdeq_row_state* st, hipStream_t s) {
+    typename std::conditional<MAPPED, RowDenseMappedArgs<T, NT>, RowDenseArgs<T, NT>>::type a;
+    a.sol = static_cast<T*>(sol);
+    const bool aligned = row_quartic_args<T, NT>(a, sol, y0, y1, f0, f1, k, coef, dts);
     a.tgrid = st->tgrid;
     a.tprev = st->tprev;
     a.t1 = st->t0;
@@ -235,80 +285,17 @@ int row_dense_n(void* sol, void* y0, const void* y1, void* f0, const void* f1, c
     a.out_hi = st->out_hi;
     a.n_rows = st->n_rows;
     a.n = st->n_rows * st->row_len;
-    const int lv = row_lanes(st->row_len, std::is_same<T, float>::value ? TDEQ_F32 : TDEQ_F64);
-    bool vec = lv > 1 && aligned16(sol) && aligned16(y0) && aligned16(y1) && aligned16(f0) && aligned16(f1);
-    for (int j = 0; j < NT; ++j) vec = vec && aligned16(k[j]);
-    if (vec) {
-        a.row_len = st->row_len / lv;
-        return launch_row_dense<T, NT, true>(a, s);
+    if constexpr (MAPPED) {
+        a.row_map = row_map;
+        a.sol_rows = sol_rows;
     }
-    a.row_len = st->row_len;
-    return launch_row_dense<T, NT, false>(a, s);
-}
-
-template <typename T>
-int row_dense_dispatch(void* sol, void* y0, const void* y1, void* f0, const void* f1, const void* const* k,
-                       const double* coef, int nt, const void* dts, const tdeq_row_state* st, hipStream_t s) {
-    switch (nt) {
-#define TDEQ_CASE(N) case N: return row_dense_n<T, N>(sol, y0, y1, f0, f1, k, coef, dts, st, s);
-        TDEQ_CASE(1) TDEQ_CASE(2) TDEQ_CASE(3) TDEQ_CASE(4) TDEQ_CASE(5) TDEQ_CASE(6) TDEQ_CASE(7)
-        TDEQ_CASE(8) TDEQ_CASE(9) TDEQ_CASE(10) TDEQ_CASE(11) TDEQ_CASE(12) TDEQ_CASE(13) TDEQ_CASE(14)
-#undef TDEQ_CASE
-    }
-    return TDEQ_EINVAL;
-}
-
-template <typename T, int NT>
-int row_dense_mapped_n(void* sol, const int32_t* row_map, int64_t sol_rows, void* y0, const void* y1, void* f0,
-                       const void* f1, const void* const* k, const double* coef, const void* dts,
-                       const tdeq_row_state* st, hipStream_t s) {
-    RowDenseMappedArgs<T, NT> a;
-    a.sol = static_cast<T*>(sol);
-    a.y0 = static_cast<T*>(y0);
-    a.y1 = static_cast<const T*>(y1);
-    a.f0 = static_cast<T*>(f0);
-    a.f1 = static_cast<const T*>(f1);
-    for (int j = 0; j < NT; ++j) {
-        a.k[j] = static_cast<const T*>(k[j]);
-        a.c[j] = (T)coef[j];
-    }
-    a.dts = static_cast<const T*>(dts);
-    a.tgrid = st->tgrid;
-    a.tprev = st->tprev;
-    a.t1 = st->t0;
-    a.accepted = st->accepted;
-    a.out_lo = st->out_lo;
-    a.out_hi = st->out_hi;
-    a.n_rows = st->n_rows;
-    a.n = st->n_rows * st->row_len;
-    a.row_map = row_map;
-    a.sol_rows = sol_rows;
-    const int lv = row_lanes(st->row_len, std::is_same<T, float>::value ? TDEQ_F32 : TDEQ_F64);
-    bool vec = lv > 1 && aligned16(sol) && aligned16(y0) && aligned16(y1) && aligned16(f0) && aligned16(f1);
-    for (int j = 0; j < NT; ++j) vec = vec && aligned16(k[j]);
-    if (vec) {
-        a.row_len = st->row_len / lv;
-        hipLaunchKernelGGL((row_dense_commit_mapped_kernel<T, NT, true>), dim3(stream_grid(a.n / lv, kBlock)), dim3(kBlock),
-                           0, s, a);
-    } else {
-        a.row_len = st->row_len;
-        hipLaunchKernelGGL((row_dense_commit_mapped_kernel<T, NT, false>), dim3(stream_grid(a.n, kBlock)), dim3(kBlock), 0,
-                           s, a);
-    }
-    return check_launch();
-}
-
-template <typename T>
-int row_dense_mapped_dispatch(void* sol, const int32_t* row_map, int64_t sol_rows, void* y0, const void* y1, void* f0,
-                              const void* f1, const void* const* k, const double* coef, int nt, const void* dts,
-                              const tdeq_row_state* st, hipStream_t s) {
-    switch (nt) {
-#define TDEQ_CASE(N) case N: return row_dense_mapped_n<T, N>(sol, row_map, sol_rows, y0, y1, f0, f1, k, coef, dts, st, s);
-        TDEQ_CASE(1) TDEQ_CASE(2) TDEQ_CASE(3) TDEQ_CASE(4) TDEQ_CASE(5) TDEQ_CASE(6) TDEQ_CASE(7)
-        TDEQ_CASE(8) TDEQ_CASE(9) TDEQ_CASE(10) TDEQ_CASE(11) TDEQ_CASE(12) TDEQ_CASE(13) TDEQ_CASE(14)
-#undef TDEQ_CASE
-    }
-    return TDEQ_EINVAL;
+    return row_vec<T>(st->row_len, aligned, a.row_len, [&](auto vec) {
+        constexpr bool VEC = decltype(vec)::value;
+        const dim3 grid(stream_grid(a.n_rows * a.row_len, kBlock));
+        if constexpr (MAPPED) hipLaunchKernelGGL((row_dense_commit_mapped_kernel<T, NT, VEC>), grid, dim3(kBlock), 0, s, a);
+        else hipLaunchKernelGGL((row_dense_commit_kernel<T, NT, VEC>), grid, dim3(kBlock), 0, s, a);
+        return check_launch();
+    });
 }
 
 template <typename E, int NS>
@@ -338,8 +325,6 @@ int row_gather_dispatch(void* const* dst, const void* const* src, int n_src, con
     return TDEQ_EINVAL;
 }
 
-inline bool row_dtype_ok(int dtype) { return dtype == TDEQ_F32 || dtype == TDEQ_F64; }
-
 }  // namespace
 
 int64_t tdeq_row_partials(int64_t row_len, int dtype) {
@@ -358,24 +343,16 @@ int tdeq_row_combine(const tdeq_multi_out* outs, int n_out, const void* y0, cons
     }
     if (n_rows == 0) return 0;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    return dtype == TDEQ_F32
-               ? row_combine_dispatch<float>(outs, n_out, y0, acc_in, k, n_terms, dts, active, n_rows, row_len, s)
-               : row_combine_dispatch<double>(outs, n_out, y0, acc_in, k, n_terms, dts, active, n_rows, row_len, s);
+    return row_dtype_terms<1>(dtype, n_terms, [&](auto t, auto n) {
+        return row_combine_n<decltype(t), decltype(n)::value>(outs, n_out, y0, acc_in, k, dts, active, n_rows, row_len, s);
+    });
 }
 
 int tdeq_row_reduce(int mode, const void* y0, const void* y1, const void* partial, const void* const* k,
                     const double* coef, int n_terms, const void* dts, const int32_t* active, double rtol, double atol,
                     int64_t n_rows, int64_t row_len, double* part, size_t part_bytes, int dtype, void* stream) {
-    const int e = row_reduce_check(mode, y0, y1, partial, k, coef, n_terms, dts, active, n_rows, row_len, part, part_bytes,
-                                   dtype);
-    if (e) return e < 0 ? e : 0;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const RowTols tol = {rtol, atol, nullptr, nullptr};
-    return dtype == TDEQ_F32
-               ? row_reduce_dispatch<float, false>(mode, y0, y1, partial, k, coef, n_terms, dts, active, tol, n_rows,
-                                                   row_len, part, s)
-               : row_reduce_dispatch<double, false>(mode, y0, y1, partial, k, coef, n_terms, dts, active, tol, n_rows,
-                                                    row_len, part, s);
+    return row_reduce_entry<false>(mode, y0, y1, partial, k, coef, n_terms, dts, active, {rtol, atol, nullptr, nullptr},
+                                   n_rows, row_len, part, part_bytes, dtype, stream);
 }
 
 int tdeq_row_reduce_tol(int mode, const void* y0, const void* y1, const void* partial, const void* const* k,
@@ -383,16 +360,8 @@ int tdeq_row_reduce_tol(int mode, const void* y0, const void* y1, const void* pa
                         const void* atol_rows, int64_t n_rows, int64_t row_len, double* part, size_t part_bytes, int dtype,
                         void* stream) {
     if (!rtol_rows || !atol_rows) return TDEQ_EINVAL;
-    const int e = row_reduce_check(mode, y0, y1, partial, k, coef, n_terms, dts, active, n_rows, row_len, part, part_bytes,
-                                   dtype);
-    if (e) return e < 0 ? e : 0;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const RowTols tol = {0.0, 0.0, rtol_rows, atol_rows};
-    return dtype == TDEQ_F32
-               ? row_reduce_dispatch<float, true>(mode, y0, y1, partial, k, coef, n_terms, dts, active, tol, n_rows,
-                                                  row_len, part, s)
-               : row_reduce_dispatch<double, true>(mode, y0, y1, partial, k, coef, n_terms, dts, active, tol, n_rows,
-                                                   row_len, part, s);
+    return row_reduce_entry<true>(mode, y0, y1, partial, k, coef, n_terms, dts, active, {0.0, 0.0, rtol_rows, atol_rows},
+                                  n_rows, row_len, part, part_bytes, dtype, stream);
 }
 
 namespace {
@@ -424,26 +393,6 @@ int row_control_args(RowCtrlArgs& a, int mode, const double* part, const tdeq_st
     a.times = times_out;
     return 0;
 }
-
-template <typename E>
-int row_impulse_launch(RowImpulseArgs& a, int64_t n_rows, int64_t row_len_e, hipStream_t s) {
-    a.row_len = row_len_e;
-    a.ne = n_rows * row_len_e;
-    hipLaunchKernelGGL((row_impulse_kernel<E>), dim3(stream_grid(a.ne, kBlock)), dim3(kBlock), 0, s, a);
-    return check_launch();
-}
-
-template <typename E>
-int row_select_launch(void* dst, const void* src, const int32_t* mask, int64_t n_rows, int64_t row_len_e, hipStream_t s) {
-    RowSelectArgs a;
-    a.dst = dst;
-    a.src = src;
-    a.mask = mask;
-    a.row_len = row_len_e;
-    a.ne = n_rows * row_len_e;
-    hipLaunchKernelGGL((row_select_kernel<E>), dim3(stream_grid(a.ne, kBlock)), dim3(kBlock), 0, s, a);
-    return check_launch();
-}
 }  // namespace
 
 int tdeq_row_control(int mode, const double* part, const tdeq_step_ctrl* ctrl, const tdeq_row_state* st,
@@ -453,8 +402,7 @@ int tdeq_row_control(int mode, const double* part, const tdeq_step_ctrl* ctrl, c
     bool launch;
     const int e = row_control_args(a, mode, part, ctrl, st, dts_out, times_out, dtype, 2, s, launch);
     if (e || !launch) return e;
-    return dtype == TDEQ_F32 ? row_control_launch<float, false, false>(a, s)
-                             : row_control_launch<double, false, false>(a, s);
+    return row_dtype(dtype, [&](auto t) { return row_control_launch<decltype(t), false, false>(a, s); });
 }
 
 // ---- per-row step options: tdeq_row_control_points / tdeq_row_select / tdeq_row_impulse -------------------------------
@@ -470,12 +418,10 @@ int tdeq_row_control_points(int mode, const double* part, const tdeq_step_ctrl* 
     const int e = row_control_args(a, mode, part, ctrl, st, dts_out, times_out, dtype, 3, s, launch);
     if (e || !launch) return e;
     a.pts = *pts;
-    if (pts->jump_hit) {              // a solve with impulses: the closed rule for the jump table
-        return dtype == TDEQ_F32 ? row_control_launch<float, true, true>(a, s)
-                                 : row_control_launch<double, true, true>(a, s);
-    }
-    return dtype == TDEQ_F32 ? row_control_launch<float, true, false>(a, s)
-                             : row_control_launch<double, true, false>(a, s);
+    return row_dtype(dtype, [&](auto t) {                // a solve with impulses: the closed rule for the jump table
+        return pts->jump_hit ? row_control_launch<decltype(t), true, true>(a, s)
+                             : row_control_launch<decltype(t), true, false>(a, s);
+    });
 }
 
 int tdeq_row_select(void* dst, const void* src, const int32_t* mask, int64_t n_rows, int64_t row_len, int dtype,
@@ -483,13 +429,16 @@ int tdeq_row_select(void* dst, const void* src, const int32_t* mask, int64_t n_r
     if (!dst || !src || !mask || n_rows < 0 || row_len < 1 || !row_dtype_ok(dtype)) return TDEQ_EINVAL;
     if (n_rows == 0) return 0;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const int lv = row_lanes(row_len, dtype);
-    if (lv > 1 && aligned16(dst) && aligned16(src)) {
-        return dtype == TDEQ_F32 ? row_select_launch<VecOf<float>::type>(dst, src, mask, n_rows, row_len / lv, s)
-                                 : row_select_launch<VecOf<double>::type>(dst, src, mask, n_rows, row_len / lv, s);
-    }
-    return dtype == TDEQ_F32 ? row_select_launch<float>(dst, src, mask, n_rows, row_len, s)
-                             : row_select_launch<double>(dst, src, mask, n_rows, row_len, s);
+    RowSelectArgs a;
+    a.dst = dst;
+    a.src = src;
+    a.mask = mask;
+    return row_elem(dtype, row_len, row_aligned(dst, src), [&](auto e, int64_t row_len_e) {
+        a.row_len = row_len_e;
+        a.ne = n_rows * row_len_e;
+        hipLaunchKernelGGL((row_select_kernel<decltype(e)>), dim3(stream_grid(a.ne, kBlock)), dim3(kBlock), 0, s, a);
+        return check_launch();
+    });
 }
 
 int tdeq_row_impulse(void* y, const void* dy, int64_t dy_rows, const int32_t* dy_index, int64_t n_orig,
@@ -508,13 +457,12 @@ int tdeq_row_impulse(void* y, const void* dy, int64_t dy_rows, const int32_t* dy
     a.row_map = row_map;
     a.dy_rows = dy_rows;
     a.n_orig = n_orig;
-    const int lv = row_lanes(row_len, dtype);
-    if (lv > 1 && aligned16(y) && aligned16(dy)) {
-        return dtype == TDEQ_F32 ? row_impulse_launch<VecOf<float>::type>(a, n_rows, row_len / lv, s)
-                                 : row_impulse_launch<VecOf<double>::type>(a, n_rows, row_len / lv, s);
-    }
-    return dtype == TDEQ_F32 ? row_impulse_launch<float>(a, n_rows, row_len, s)
-                             : row_impulse_launch<double>(a, n_rows, row_len, s);
+    return row_elem(dtype, row_len, row_aligned(y, dy), [&](auto e, int64_t row_len_e) {
+        a.row_len = row_len_e;
+        a.ne = n_rows * row_len_e;
+        hipLaunchKernelGGL((row_impulse_kernel<decltype(e)>), dim3(stream_grid(a.ne, kBlock)), dim3(kBlock), 0, s, a);
+        return check_launch();
+    });
 }
 
 int tdeq_row_dense_commit(void* sol, void* y0, const void* y1, void* f0, const void* f1, const void* const* k,
@@ -525,8 +473,9 @@ int tdeq_row_dense_commit(void* sol, void* y0, const void* y1, void* f0, const v
     for (int j = 0; j < n_terms; ++j) if (!k[j]) return TDEQ_EINVAL;
     if (st->n_rows == 0) return 0;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    return dtype == TDEQ_F32 ? row_dense_dispatch<float>(sol, y0, y1, f0, f1, k, coef, n_terms, dts, st, s)
-                             : row_dense_dispatch<double>(sol, y0, y1, f0, f1, k, coef, n_terms, dts, st, s);
+    return row_dtype_terms<1>(dtype, n_terms, [&](auto t, auto n) {
+        return row_dense_n<decltype(t), decltype(n)::value, false>(sol, nullptr, 0, y0, y1, f0, f1, k, coef, dts, st, s);
+    });
 }
 
 // ---- compaction of a rowwise batch: tdeq_row_gather / tdeq_row_dense_commit_mapped ------------------------------------
@@ -537,15 +486,10 @@ int tdeq_row_gather(void* const* dst, const void* const* src, int n_src, const i
     for (int m = 0; m < n_src; ++m) if (!dst[m] || !src[m]) return TDEQ_EINVAL;
     if (n_idx == 0) return 0;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const int lv = row_lanes(row_len, dtype);
-    bool vec = lv > 1;
-    for (int m = 0; m < n_src; ++m) vec = vec && aligned16(dst[m]) && aligned16(src[m]);
-    if (vec) {
-        return dtype == TDEQ_F32 ? row_gather_dispatch<VecOf<float>::type>(dst, src, n_src, idx, n_idx, row_len / lv, s)
-                                 : row_gather_dispatch<VecOf<double>::type>(dst, src, n_src, idx, n_idx, row_len / lv, s);
-    }
-    return dtype == TDEQ_F32 ? row_gather_dispatch<float>(dst, src, n_src, idx, n_idx, row_len, s)
-                             : row_gather_dispatch<double>(dst, src, n_src, idx, n_idx, row_len, s);
+    const bool aligned = row_aligned(RowPtrs{dst, n_src}, RowPtrs{src, n_src});
+    return row_elem(dtype, row_len, aligned, [&](auto e, int64_t row_len_e) {
+        return row_gather_dispatch<decltype(e)>(dst, src, n_src, idx, n_idx, row_len_e, s);
+    });
 }
 
 int tdeq_row_dense_commit_mapped(void* sol, const int32_t* row_map, int64_t sol_rows, void* y0, const void* y1, void* f0,
@@ -557,9 +501,10 @@ int tdeq_row_dense_commit_mapped(void* sol, const int32_t* row_map, int64_t sol_
     for (int j = 0; j < n_terms; ++j) if (!k[j]) return TDEQ_EINVAL;
     if (st->n_rows == 0) return 0;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    return dtype == TDEQ_F32
-               ? row_dense_mapped_dispatch<float>(sol, row_map, sol_rows, y0, y1, f0, f1, k, coef, n_terms, dts, st, s)
-               : row_dense_mapped_dispatch<double>(sol, row_map, sol_rows, y0, y1, f0, f1, k, coef, n_terms, dts, st, s);
+    return row_dtype_terms<1>(dtype, n_terms, [&](auto t, auto n) {
+        return row_dense_n<decltype(t), decltype(n)::value, true>(sol, row_map, sol_rows, y0, y1, f0, f1, k, coef, dts, st,
+                                                                   s);
+    });
 }
 
 // ---- backward of the row-linear operations: tdeq_row_scale_many / tdeq_row_multi_dot ---------------------------------
@@ -572,64 +517,39 @@ int row_scale_n(void* const* outs, const void* g, const void* w, int64_t n_rows,
     a.w = static_cast<const T*>(w);
     a.n_rows = n_rows;
     a.n = n_rows * row_len;
-    const int lv = row_lanes(row_len, std::is_same<T, float>::value ? TDEQ_F32 : TDEQ_F64);
-    bool vec = lv > 1 && aligned16(g);
-    for (int j = 0; j < NT; ++j) {
-        a.out[j] = static_cast<T*>(outs[j]);
-        vec = vec && aligned16(outs[j]);
-    }
-    if (vec) {
-        a.row_len = row_len / lv;
-        hipLaunchKernelGGL((row_scale_many_kernel<T, NT, true>), dim3(stream_grid(a.n / lv, kBlock)), dim3(kBlock), 0, s, a);
-    } else {
-        a.row_len = row_len;
-        hipLaunchKernelGGL((row_scale_many_kernel<T, NT, false>), dim3(stream_grid(a.n, kBlock)), dim3(kBlock), 0, s, a);
-    }
-    return check_launch();
-}
-
-template <typename T>
-int row_scale_dispatch(void* const* outs, int nt, const void* g, const void* w, int64_t n_rows, int64_t row_len,
-                       hipStream_t s) {
-    switch (nt) {
-#define TDEQ_CASE(N) case N: return row_scale_n<T, N>(outs, g, w, n_rows, row_len, s);
-        TDEQ_CASE(1) TDEQ_CASE(2) TDEQ_CASE(3) TDEQ_CASE(4) TDEQ_CASE(5) TDEQ_CASE(6) TDEQ_CASE(7)
-        TDEQ_CASE(8) TDEQ_CASE(9) TDEQ_CASE(10) TDEQ_CASE(11) TDEQ_CASE(12) TDEQ_CASE(13) TDEQ_CASE(14)
-#undef TDEQ_CASE
-    }
-    return TDEQ_EINVAL;
+    for (int j = 0; j < NT; ++j) a.out[j] = static_cast<T*>(outs[j]);
+    return row_vec<T>(row_len, row_aligned(g, RowPtrs{outs, NT}), a.row_len, [&](auto vec) {
+        hipLaunchKernelGGL((row_scale_many_kernel<T, NT, decltype(vec)::value>),
+                           dim3(stream_grid(n_rows * a.row_len, kBlock)), dim3(kBlock), 0, s, a);
+        return check_launch();
+    });
 }
 
 template <typename T, int NT>
 int row_dot_n(const void* g, const void* const* x, int64_t n_rows, int64_t row_len, double* out, double* ws,
               hipStream_t s) {
-    const RowGeom geo = row_geom(row_len, std::is_same<T, float>::value ? TDEQ_F32 : TDEQ_F64);
+    const RowGeom geo = row_geom<T>(row_len);
     RowDotArgs<T, NT> a;
     a.g = static_cast<const T*>(g);
-    bool vec = geo.lv > 1 && aligned16(g);
-    for (int j = 0; j < NT; ++j) {
-        a.x[j] = static_cast<const T*>(x[j]);
-        vec = vec && aligned16(x[j]);
-    }
+    for (int j = 0; j < NT; ++j) a.x[j] = static_cast<const T*>(x[j]);
+    const bool vec = geo.lv > 1 && row_aligned(g, RowPtrs{x, NT});
     if (geo.lv > 1 && !vec) return TDEQ_EINVAL;      // (the geometry, hence the sums, must not depend on alignment)
     a.row_len = geo.nv;
     a.n_rows = n_rows;
     a.chunk = geo.chunk;
     a.nch = (int)geo.nch;
     a.group = geo.group;
-    if (geo.group > 0) {
-        a.out = out;
-        const int64_t threads = n_rows * geo.group;
-        const dim3 grid((unsigned)((threads + kBlock - 1) / kBlock));
-        if (vec) hipLaunchKernelGGL((row_dot_wave_kernel<T, NT, true>), grid, dim3(kBlock), 0, s, a);
-        else hipLaunchKernelGGL((row_dot_wave_kernel<T, NT, false>), grid, dim3(kBlock), 0, s, a);
-        return check_launch();
-    }
     a.out = geo.nch == 1 ? out : ws;                 // one chunk per row: the chunk sums are the results, [NT, B]
-    const dim3 grid((unsigned)(n_rows * geo.nch));
-    if (vec) hipLaunchKernelGGL((row_dot_chunk_kernel<T, NT, true>), grid, dim3(kBlock), 0, s, a);
-    else hipLaunchKernelGGL((row_dot_chunk_kernel<T, NT, false>), grid, dim3(kBlock), 0, s, a);
-    const int e = check_launch();
+    const int e = row_bool(vec, [&](auto v) {
+        constexpr bool VEC = decltype(v)::value;
+        if (geo.group > 0) {
+            const dim3 grid((unsigned)((n_rows * geo.group + kBlock - 1) / kBlock));
+            hipLaunchKernelGGL((row_dot_wave_kernel<T, NT, VEC>), grid, dim3(kBlock), 0, s, a);
+        } else {
+            hipLaunchKernelGGL((row_dot_chunk_kernel<T, NT, VEC>), dim3((unsigned)(n_rows * geo.nch)), dim3(kBlock), 0, s, a);
+        }
+        return check_launch();
+    });
     if (e || geo.nch == 1) return e;
     RowDotFinalizeArgs f;
     f.part = ws;
@@ -642,18 +562,6 @@ int row_dot_n(const void* g, const void* const* x, int64_t n_rows, int64_t row_l
     return check_launch();
 }
 
-template <typename T>
-int row_dot_dispatch(const void* g, const void* const* x, int nt, int64_t n_rows, int64_t row_len, double* out,
-                     double* ws, hipStream_t s) {
-    switch (nt) {
-#define TDEQ_CASE(N) case N: return row_dot_n<T, N>(g, x, n_rows, row_len, out, ws, s);
-        TDEQ_CASE(1) TDEQ_CASE(2) TDEQ_CASE(3) TDEQ_CASE(4) TDEQ_CASE(5) TDEQ_CASE(6) TDEQ_CASE(7)
-        TDEQ_CASE(8) TDEQ_CASE(9) TDEQ_CASE(10) TDEQ_CASE(11) TDEQ_CASE(12) TDEQ_CASE(13) TDEQ_CASE(14)
-#undef TDEQ_CASE
-    }
-    return TDEQ_EINVAL;
-}
-
 }  // namespace
 
 int tdeq_row_scale_many(void* const* outs, int n_out, const void* g, const void* w, int64_t n_rows, int64_t row_len,
@@ -663,8 +571,9 @@ int tdeq_row_scale_many(void* const* outs, int n_out, const void* g, const void*
     for (int j = 0; j < n_out; ++j) if (!outs[j]) return TDEQ_EINVAL;
     if (n_rows == 0 || row_len == 0) return 0;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    return dtype == TDEQ_F32 ? row_scale_dispatch<float>(outs, n_out, g, w, n_rows, row_len, s)
-                             : row_scale_dispatch<double>(outs, n_out, g, w, n_rows, row_len, s);
+    return row_dtype_terms<1>(dtype, n_out, [&](auto t, auto n) {
+        return row_scale_n<decltype(t), decltype(n)::value>(outs, g, w, n_rows, row_len, s);
+    });
 }
 
 size_t tdeq_row_dots_workspace_bytes(int64_t n_rows, int64_t row_len, int n_x, int dtype) {
@@ -685,104 +594,37 @@ int tdeq_row_multi_dot(const void* g, const void* const* x, int n_x, int64_t n_r
     if (need > 0 && (!workspace || workspace_bytes < need)) return TDEQ_EWORKSPACE;
     if (n_rows * row_geom(row_len, dtype).nch > 0x7fffffffLL) return TDEQ_EINVAL;
     double* ws = static_cast<double*>(workspace);
-    return dtype == TDEQ_F32 ? row_dot_dispatch<float>(g, x, n_x, n_rows, row_len, out, ws, s)
-                             : row_dot_dispatch<double>(g, x, n_x, n_rows, row_len, out, ws, s);
+    return row_dtype_terms<1>(dtype, n_x, [&](auto t, auto n) {
+        return row_dot_n<decltype(t), decltype(n)::value>(g, x, n_rows, row_len, out, ws, s);
+    });
 }
 
 // ---- per-row terminal events: tdeq_row_event_detect / tdeq_row_event_fit / tdeq_row_event_eval, and the two of a
 // ---- compacted event solve: tdeq_row_event_fit_mapped / tdeq_row_event_eval_mapped -----------------------------------
 namespace {
 
-template <typename T, int NT>
-int row_event_fit_n(void* q, const int32_t* fired_now, const void* y0, const void* y1, const void* f0, const void* f1,
-                    const void* const* k, const double* coef, const void* dts, int64_t n_rows, int64_t row_len,
-                    hipStream_t s) {
-    RowEventFitArgs<T, NT> a;
+// tdeq_row_event_fit and (MAPPED: row_map, q_rows) tdeq_row_event_fit_mapped
+template <typename T, int NT, bool MAPPED>
+int row_event_fit_n(void* q, const int32_t* row_map, int64_t q_rows, const int32_t* fired_now, const void* y0,
+                    const void* y1, const void* f0, const void* f1, const void* const* k, const double* coef,
+                    const void* dts, int64_t n_rows, int64_t row_len, hipStream_t s) {
+    typename std::conditional<MAPPED, RowEventFitMappedArgs<T, NT>, RowEventFitArgs<T, NT>>::type a;
     a.q = static_cast<T*>(q);
-    a.y0 = static_cast<const T*>(y0);
-    a.y1 = static_cast<const T*>(y1);
-    a.f0 = static_cast<const T*>(f0);
-    a.f1 = static_cast<const T*>(f1);
-    for (int j = 0; j < NT; ++j) {
-        a.k[j] = static_cast<const T*>(k[j]);
-        a.c[j] = (T)coef[j];
-    }
-    a.dts = static_cast<const T*>(dts);
+    const bool aligned = row_quartic_args<T, NT>(a, q, y0, y1, f0, f1, k, coef, dts);
     a.fired_now = fired_now;
     a.n = n_rows * row_len;
-    const int lv = row_lanes(row_len, std::is_same<T, float>::value ? TDEQ_F32 : TDEQ_F64);
-    bool vec = lv > 1 && aligned16(q) && aligned16(y0) && aligned16(y1) && aligned16(f0) && aligned16(f1);
-    for (int j = 0; j < NT; ++j) vec = vec && aligned16(k[j]);
-    if (vec) {
-        a.row_len = row_len / lv;
-        hipLaunchKernelGGL((row_event_fit_kernel<T, NT, true>), dim3(stream_grid(a.n / lv, kBlock)), dim3(kBlock), 0, s, a);
-    } else {
-        a.row_len = row_len;
-        hipLaunchKernelGGL((row_event_fit_kernel<T, NT, false>), dim3(stream_grid(a.n, kBlock)), dim3(kBlock), 0, s, a);
+    if constexpr (MAPPED) {
+        a.row_map = row_map;
+        a.q_plane = q_rows * row_len;
     }
-    return check_launch();
-}
-
-template <typename T>
-int row_event_fit_dispatch(void* q, const int32_t* fired_now, const void* y0, const void* y1, const void* f0,
-                           const void* f1, const void* const* k, const double* coef, int nt, const void* dts,
-                           int64_t n_rows, int64_t row_len, hipStream_t s) {
-    switch (nt) {
-#define TDEQ_CASE(N) case N: return row_event_fit_n<T, N>(q, fired_now, y0, y1, f0, f1, k, coef, dts, n_rows, row_len, s);
-        TDEQ_CASE(1) TDEQ_CASE(2) TDEQ_CASE(3) TDEQ_CASE(4) TDEQ_CASE(5) TDEQ_CASE(6) TDEQ_CASE(7)
-        TDEQ_CASE(8) TDEQ_CASE(9) TDEQ_CASE(10) TDEQ_CASE(11) TDEQ_CASE(12) TDEQ_CASE(13) TDEQ_CASE(14)
-#undef TDEQ_CASE
-    }
-    return TDEQ_EINVAL;
-}
-
-template <typename T, int NT>
-int row_event_fit_mapped_n(void* q, const int32_t* row_map, int64_t q_rows, const int32_t* fired_now, const void* y0,
-                           const void* y1, const void* f0, const void* f1, const void* const* k, const double* coef,
-                           const void* dts, int64_t n_rows, int64_t row_len, hipStream_t s) {
-    RowEventFitMappedArgs<T, NT> a;
-    a.q = static_cast<T*>(q);
-    a.y0 = static_cast<const T*>(y0);
-    a.y1 = static_cast<const T*>(y1);
-    a.f0 = static_cast<const T*>(f0);
-    a.f1 = static_cast<const T*>(f1);
-    for (int j = 0; j < NT; ++j) {
-        a.k[j] = static_cast<const T*>(k[j]);
-        a.c[j] = (T)coef[j];
-    }
-    a.dts = static_cast<const T*>(dts);
-    a.fired_now = fired_now;
-    a.n = n_rows * row_len;
-    a.row_map = row_map;
-    a.q_plane = q_rows * row_len;
     // (16-byte elements: row_len is a whole number of them, so every row start and every plane of q is aligned as q is)
-    const int lv = row_lanes(row_len, std::is_same<T, float>::value ? TDEQ_F32 : TDEQ_F64);
-    bool vec = lv > 1 && aligned16(q) && aligned16(y0) && aligned16(y1) && aligned16(f0) && aligned16(f1);
-    for (int j = 0; j < NT; ++j) vec = vec && aligned16(k[j]);
-    if (vec) {
-        a.row_len = row_len / lv;
-        hipLaunchKernelGGL((row_event_fit_mapped_kernel<T, NT, true>), dim3(stream_grid(a.n / lv, kBlock)), dim3(kBlock), 0,
-                           s, a);
-    } else {
-        a.row_len = row_len;
-        hipLaunchKernelGGL((row_event_fit_mapped_kernel<T, NT, false>), dim3(stream_grid(a.n, kBlock)), dim3(kBlock), 0, s,
-                           a);
-    }
-    return check_launch();
-}
-
-template <typename T>
-int row_event_fit_mapped_dispatch(void* q, const int32_t* row_map, int64_t q_rows, const int32_t* fired_now,
-                                  const void* y0, const void* y1, const void* f0, const void* f1, const void* const* k,
-                                  const double* coef, int nt, const void* dts, int64_t n_rows, int64_t row_len,
-                                  hipStream_t s) {
-    switch (nt) {
-#define TDEQ_CASE(N) case N: return row_event_fit_mapped_n<T, N>(q, row_map, q_rows, fired_now, y0, y1, f0, f1, k, coef, dts, n_rows, row_len, s);
-        TDEQ_CASE(1) TDEQ_CASE(2) TDEQ_CASE(3) TDEQ_CASE(4) TDEQ_CASE(5) TDEQ_CASE(6) TDEQ_CASE(7)
-        TDEQ_CASE(8) TDEQ_CASE(9) TDEQ_CASE(10) TDEQ_CASE(11) TDEQ_CASE(12) TDEQ_CASE(13) TDEQ_CASE(14)
-#undef TDEQ_CASE
-    }
-    return TDEQ_EINVAL;
+    return row_vec<T>(row_len, aligned, a.row_len, [&](auto vec) {
+        constexpr bool VEC = decltype(vec)::value;
+        const dim3 grid(stream_grid(n_rows * a.row_len, kBlock));
+        if constexpr (MAPPED) hipLaunchKernelGGL((row_event_fit_mapped_kernel<T, NT, VEC>), grid, dim3(kBlock), 0, s, a);
+        else hipLaunchKernelGGL((row_event_fit_kernel<T, NT, VEC>), grid, dim3(kBlock), 0, s, a);
+        return check_launch();
+    });
 }
 
 template <typename T>
@@ -794,21 +636,11 @@ int row_event_eval_launch(void* out, const void* q, const void* x, const int32_t
     a.x = static_cast<const T*>(x);
     a.mask = mask;
     a.n = n_rows * row_len;
-    const int lv = row_lanes(row_len, std::is_same<T, float>::value ? TDEQ_F32 : TDEQ_F64);
-    if (lv > 1 && aligned16(out) && aligned16(q)) {
-        a.row_len = row_len / lv;
-        hipLaunchKernelGGL((row_event_eval_kernel<T, true>), dim3(stream_grid(a.n / lv, kBlock)), dim3(kBlock), 0, s, a);
-    } else {
-        a.row_len = row_len;
-        hipLaunchKernelGGL((row_event_eval_kernel<T, false>), dim3(stream_grid(a.n, kBlock)), dim3(kBlock), 0, s, a);
-    }
-    return check_launch();
-}
-
-template <typename T, bool VEC, bool DST>
-int row_event_eval_mapped_go(const RowEventEvalMappedArgs<T>& a, hipStream_t s) {
-    hipLaunchKernelGGL((row_event_eval_mapped_kernel<T, VEC, DST>), dim3(stream_grid(a.ne, kBlock)), dim3(kBlock), 0, s, a);
-    return check_launch();
+    return row_vec<T>(row_len, row_aligned(out, q), a.row_len, [&](auto vec) {
+        hipLaunchKernelGGL((row_event_eval_kernel<T, decltype(vec)::value>), dim3(stream_grid(n_rows * a.row_len, kBlock)),
+                           dim3(kBlock), 0, s, a);
+        return check_launch();
+    });
 }
 
 template <typename T>
@@ -821,15 +653,14 @@ int row_event_eval_mapped_launch(void* out, const int32_t* dst_map, const void* 
     a.src_map = src_map;
     a.dst_map = dst_map;
     a.q_plane = q_rows * row_len;
-    const int lv = row_lanes(row_len, std::is_same<T, float>::value ? TDEQ_F32 : TDEQ_F64);
-    if (lv > 1 && aligned16(out) && aligned16(q)) {
-        a.row_len = row_len / lv;
+    return row_vec<T>(row_len, row_aligned(out, q), a.row_len, [&](auto vec) {
         a.ne = n_idx * a.row_len;
-        return dst_map ? row_event_eval_mapped_go<T, true, true>(a, s) : row_event_eval_mapped_go<T, true, false>(a, s);
-    }
-    a.row_len = row_len;
-    a.ne = n_idx * row_len;
-    return dst_map ? row_event_eval_mapped_go<T, false, true>(a, s) : row_event_eval_mapped_go<T, false, false>(a, s);
+        return row_bool(dst_map != nullptr, [&](auto dst) {
+            hipLaunchKernelGGL((row_event_eval_mapped_kernel<T, decltype(vec)::value, decltype(dst)::value>),
+                               dim3(stream_grid(a.ne, kBlock)), dim3(kBlock), 0, s, a);
+            return check_launch();
+        });
+    });
 }
 
 }  // namespace
@@ -861,9 +692,10 @@ int tdeq_row_event_detect(const void* g1, const int32_t* sign0, const tdeq_step_
     a.hi = hi;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const dim3 grid((unsigned)((a.n_rows + kBlock - 1) / kBlock));
-    if (dtype == TDEQ_F32) hipLaunchKernelGGL((row_event_detect_kernel<float>), grid, dim3(kBlock), 0, s, a);
-    else hipLaunchKernelGGL((row_event_detect_kernel<double>), grid, dim3(kBlock), 0, s, a);
-    return check_launch();
+    return row_dtype(dtype, [&](auto t) {
+        hipLaunchKernelGGL((row_event_detect_kernel<decltype(t)>), grid, dim3(kBlock), 0, s, a);
+        return check_launch();
+    });
 }
 
 int tdeq_row_event_fit(void* q, const int32_t* fired_now, const void* y0, const void* y1, const void* f0, const void* f1,
@@ -874,9 +706,10 @@ int tdeq_row_event_fit(void* q, const int32_t* fired_now, const void* y0, const 
     for (int j = 0; j < n_terms; ++j) if (!k[j]) return TDEQ_EINVAL;
     if (n_rows == 0) return 0;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    return dtype == TDEQ_F32
-               ? row_event_fit_dispatch<float>(q, fired_now, y0, y1, f0, f1, k, coef, n_terms, dts, n_rows, row_len, s)
-               : row_event_fit_dispatch<double>(q, fired_now, y0, y1, f0, f1, k, coef, n_terms, dts, n_rows, row_len, s);
+    return row_dtype_terms<1>(dtype, n_terms, [&](auto t, auto n) {
+        return row_event_fit_n<decltype(t), decltype(n)::value, false>(q, nullptr, 0, fired_now, y0, y1, f0, f1, k, coef,
+                                                                        dts, n_rows, row_len, s);
+    });
 }
 
 int tdeq_row_event_eval(void* out, const void* q, const void* x, const int32_t* mask, int64_t n_rows, int64_t row_len,
@@ -884,8 +717,9 @@ int tdeq_row_event_eval(void* out, const void* q, const void* x, const int32_t* 
     if (!out || !q || !x || !mask || n_rows < 0 || row_len < 1 || !row_dtype_ok(dtype)) return TDEQ_EINVAL;
     if (n_rows == 0) return 0;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    return dtype == TDEQ_F32 ? row_event_eval_launch<float>(out, q, x, mask, n_rows, row_len, s)
-                             : row_event_eval_launch<double>(out, q, x, mask, n_rows, row_len, s);
+    return row_dtype(dtype, [&](auto t) {
+        return row_event_eval_launch<decltype(t)>(out, q, x, mask, n_rows, row_len, s);
+    });
 }
 
 int tdeq_row_event_fit_mapped(void* q, const int32_t* row_map, int64_t q_rows, const int32_t* fired_now, const void* y0,
@@ -898,11 +732,10 @@ int tdeq_row_event_fit_mapped(void* q, const int32_t* row_map, int64_t q_rows, c
     if (n_rows == 0) return 0;
     if (q_rows < n_rows) return TDEQ_EINVAL;          // (row_map names n_rows different rows of q)
     hipStream_t s = static_cast<hipStream_t>(stream);
-    return dtype == TDEQ_F32
-               ? row_event_fit_mapped_dispatch<float>(q, row_map, q_rows, fired_now, y0, y1, f0, f1, k, coef, n_terms, dts,
-                                                      n_rows, row_len, s)
-               : row_event_fit_mapped_dispatch<double>(q, row_map, q_rows, fired_now, y0, y1, f0, f1, k, coef, n_terms, dts,
-                                                       n_rows, row_len, s);
+    return row_dtype_terms<1>(dtype, n_terms, [&](auto t, auto n) {
+        return row_event_fit_n<decltype(t), decltype(n)::value, true>(q, row_map, q_rows, fired_now, y0, y1, f0, f1, k, coef,
+                                                                       dts, n_rows, row_len, s);
+    });
 }
 
 int tdeq_row_event_eval_mapped(void* out, const int32_t* dst_map, int64_t out_rows, const void* q, const int32_t* src_map,
@@ -912,22 +745,12 @@ int tdeq_row_event_eval_mapped(void* out, const int32_t* dst_map, int64_t out_ro
     if (n_idx == 0) return 0;
     if (q_rows < 1 || out_rows < 1 || (!dst_map && out_rows < n_idx)) return TDEQ_EINVAL;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    return dtype == TDEQ_F32
-               ? row_event_eval_mapped_launch<float>(out, dst_map, q, src_map, q_rows, x, n_idx, row_len, s)
-               : row_event_eval_mapped_launch<double>(out, dst_map, q, src_map, q_rows, x, n_idx, row_len, s);
+    return row_dtype(dtype, [&](auto t) {
+        return row_event_eval_mapped_launch<decltype(t)>(out, dst_map, q, src_map, q_rows, x, n_idx, row_len, s);
+    });
 }
 
 // ---- per-row dense output: tdeq_row_dense_slots / tdeq_row_dense_pack / tdeq_row_dense_search -------------------------
-namespace {
-
-template <typename E>
-int row_dense_pack_launch(const RowDensePackArgs& a, hipStream_t s) {
-    hipLaunchKernelGGL((row_dense_pack_kernel<E>), dim3(stream_grid(a.ne, kBlock)), dim3(kBlock), 0, s, a);
-    return check_launch();
-}
-
-}  // namespace
-
 int tdeq_row_dense_slots(const tdeq_row_state* st, const int32_t* row_map, int64_t cap, int32_t* counter, int32_t* slot_row,
                          int32_t* slot_ord, double* slot_ta, double* slot_tb, int32_t* slot, int32_t* mask, void* stream) {
     if (!st || !counter || !slot_row || !slot_ord || !slot_ta || !slot_tb || !slot || !mask) return TDEQ_EINVAL;
@@ -968,17 +791,14 @@ int tdeq_row_dense_pack(void* dst, int64_t dst_rows, const void* src, int64_t sr
     a.dest = dest;
     hipStream_t s = static_cast<hipStream_t>(stream);
     // (16-byte elements: row_len is a whole number of them, so every row start and every plane is aligned as its base is)
-    const int lv = row_lanes(row_len, dtype);
-    const bool vec = lv > 1 && aligned16(dst) && aligned16(src);
-    a.row_len = vec ? row_len / lv : row_len;
-    a.ne = n_used * a.row_len;
-    a.dst_plane = dst_rows * a.row_len;
-    a.src_plane = src_rows * a.row_len;
-    if (vec) {
-        return dtype == TDEQ_F32 ? row_dense_pack_launch<VecOf<float>::type>(a, s)
-                                 : row_dense_pack_launch<VecOf<double>::type>(a, s);
-    }
-    return dtype == TDEQ_F32 ? row_dense_pack_launch<float>(a, s) : row_dense_pack_launch<double>(a, s);
+    return row_elem(dtype, row_len, row_aligned(dst, src), [&](auto e, int64_t row_len_e) {
+        a.row_len = row_len_e;
+        a.ne = n_used * row_len_e;
+        a.dst_plane = dst_rows * row_len_e;
+        a.src_plane = src_rows * row_len_e;
+        hipLaunchKernelGGL((row_dense_pack_kernel<decltype(e)>), dim3(stream_grid(a.ne, kBlock)), dim3(kBlock), 0, s, a);
+        return check_launch();
+    });
 }
 
 int tdeq_row_dense_search(const double* tq, int64_t n_q, const int64_t* offsets, const double* seg_ta, const double* seg_tb,
@@ -1005,9 +825,10 @@ int tdeq_row_dense_search(const double* tq, int64_t n_q, const int64_t* offsets,
     a.status = status;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const dim3 grid((unsigned)((a.n + kBlock - 1) / kBlock));
-    if (dtype == TDEQ_F32) hipLaunchKernelGGL((row_dense_search_kernel<float>), grid, dim3(kBlock), 0, s, a);
-    else hipLaunchKernelGGL((row_dense_search_kernel<double>), grid, dim3(kBlock), 0, s, a);
-    return check_launch();
+    return row_dtype(dtype, [&](auto t) {
+        hipLaunchKernelGGL((row_dense_search_kernel<decltype(t)>), grid, dim3(kBlock), 0, s, a);
+        return check_launch();
+    });
 }
 
 // ---- calculus on the record: tdeq_row_dense_prefix / tdeq_row_dense_calc ----------------------------------------------
@@ -1024,27 +845,12 @@ int row_dense_prefix_launch(double* prefix, const void* coeffs, const int64_t* o
     a.seg_tb = seg_tb;
     a.n_seg = n_seg;
     a.q_plane = n_seg * row_len;
-    const int lv = row_lanes(row_len, std::is_same<T, float>::value ? TDEQ_F32 : TDEQ_F64);
-    if (lv > 1 && aligned16(prefix) && aligned16(coeffs)) {
-        a.row_len = row_len / lv;
+    return row_vec<T>(row_len, row_aligned(prefix, coeffs), a.row_len, [&](auto vec) {
         a.ne = n_rows * a.row_len;
-        hipLaunchKernelGGL((row_dense_prefix_kernel<T, true>), dim3(stream_grid(a.ne, kBlock)), dim3(kBlock), 0, s, a);
-    } else {
-        a.row_len = row_len;
-        a.ne = n_rows * row_len;
-        hipLaunchKernelGGL((row_dense_prefix_kernel<T, false>), dim3(stream_grid(a.ne, kBlock)), dim3(kBlock), 0, s, a);
-    }
-    return check_launch();
-}
-
-template <typename T, bool VEC>
-int row_dense_calc_go(const RowDenseCalcArgs<T>& a, int mode, hipStream_t s) {
-    const dim3 grid(stream_grid(a.ne, kBlock)), block(kBlock);
-    if (mode == kDenseDerivative) hipLaunchKernelGGL((row_dense_calc_kernel<T, VEC, kDenseDerivative>), grid, block, 0, s, a);
-    else if (mode == kDenseAntiderivative)
-        hipLaunchKernelGGL((row_dense_calc_kernel<T, VEC, kDenseAntiderivative>), grid, block, 0, s, a);
-    else hipLaunchKernelGGL((row_dense_calc_kernel<T, VEC, kDenseIntegral>), grid, block, 0, s, a);
-    return check_launch();
+        hipLaunchKernelGGL((row_dense_prefix_kernel<T, decltype(vec)::value>), dim3(stream_grid(a.ne, kBlock)), dim3(kBlock),
+                           0, s, a);
+        return check_launch();
+    });
 }
 
 template <typename T>
@@ -1066,15 +872,16 @@ int row_dense_calc_launch(void* out, int mode, const void* coeffs, int64_t n_seg
     a.x2 = static_cast<const T*>(x2);
     a.tq2 = tq2;
     a.q_plane = n_seg * row_len;
-    const int lv = row_lanes(row_len, std::is_same<T, float>::value ? TDEQ_F32 : TDEQ_F64);
-    if (lv > 1 && aligned16(out) && aligned16(coeffs) && (!prefix || aligned16(prefix))) {
-        a.row_len = row_len / lv;
+    return row_vec<T>(row_len, row_aligned(out, coeffs, prefix), a.row_len, [&](auto vec) {
+        constexpr bool VEC = decltype(vec)::value;
         a.ne = n_idx * a.row_len;
-        return row_dense_calc_go<T, true>(a, mode, s);
-    }
-    a.row_len = row_len;
-    a.ne = n_idx * row_len;
-    return row_dense_calc_go<T, false>(a, mode, s);
+        const dim3 grid(stream_grid(a.ne, kBlock)), block(kBlock);
+        if (mode == kDenseDerivative) hipLaunchKernelGGL((row_dense_calc_kernel<T, VEC, kDenseDerivative>), grid, block, 0, s, a);
+        else if (mode == kDenseAntiderivative)
+            hipLaunchKernelGGL((row_dense_calc_kernel<T, VEC, kDenseAntiderivative>), grid, block, 0, s, a);
+        else hipLaunchKernelGGL((row_dense_calc_kernel<T, VEC, kDenseIntegral>), grid, block, 0, s, a);
+        return check_launch();
+    });
 }
 
 }  // namespace
@@ -1086,9 +893,9 @@ int tdeq_row_dense_prefix(double* prefix, const void* coeffs, const int64_t* off
     if (n_rows == 0 || n_seg == 0) return 0;
     if (n_seg > 0x7fffffffLL) return TDEQ_EINVAL;      // (a segment index is an int32 word everywhere else)
     hipStream_t s = static_cast<hipStream_t>(stream);
-    return dtype == TDEQ_F32
-               ? row_dense_prefix_launch<float>(prefix, coeffs, offsets, seg_ta, seg_tb, n_seg, n_rows, row_len, s)
-               : row_dense_prefix_launch<double>(prefix, coeffs, offsets, seg_ta, seg_tb, n_seg, n_rows, row_len, s);
+    return row_dtype(dtype, [&](auto t) {
+        return row_dense_prefix_launch<decltype(t)>(prefix, coeffs, offsets, seg_ta, seg_tb, n_seg, n_rows, row_len, s);
+    });
 }
 
 int tdeq_row_dense_calc(void* out, int mode, const void* coeffs, int64_t n_seg, const double* seg_ta, const double* seg_tb,
@@ -1104,9 +911,8 @@ int tdeq_row_dense_calc(void* out, int mode, const void* coeffs, int64_t n_seg, 
     if (n_idx == 0) return 0;
     if (n_seg < 1 || n_seg > 0x7fffffffLL) return TDEQ_EINVAL;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    return dtype == TDEQ_F32
-               ? row_dense_calc_launch<float>(out, mode, coeffs, n_seg, seg_ta, seg_tb, prefix, time_sign, seg, x, tq, seg2,
-                                              x2, tq2, n_idx, row_len, s)
-               : row_dense_calc_launch<double>(out, mode, coeffs, n_seg, seg_ta, seg_tb, prefix, time_sign, seg, x, tq, seg2,
-                                               x2, tq2, n_idx, row_len, s);
+    return row_dtype(dtype, [&](auto t) {
+        return row_dense_calc_launch<decltype(t)>(out, mode, coeffs, n_seg, seg_ta, seg_tb, prefix, time_sign, seg, x, tq,
+                                                  seg2, x2, tq2, n_idx, row_len, s);
+    });
 }
