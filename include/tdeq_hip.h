@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define TDEQ_ABI_VERSION 31
+#define TDEQ_ABI_VERSION 32
 #define TDEQ_F32 0
 #define TDEQ_F64 1
 /* interleaved (re, im) complex states — accepted by the NORM entry points only (tdeq_error_norm, tdeq_error_norm_partial[_ctrl],
@@ -785,6 +785,63 @@ int tdeq_row_dense_calc(void* out, int mode, const void* coeffs, int64_t n_seg, 
                         const double* prefix, double time_sign, const int32_t* seg, const void* x, const double* tq,
                         const int32_t* seg2, const void* x2, const double* tq2, int64_t n_idx, int64_t row_len, int dtype,
                         void* stream);
+
+/*
+ * ---- Extrema of the per-row dense record over a time window (ABI 32; `RowDenseOutput.maximum` / `.minimum`) ----
+ * tdeq_row_dense_extremum  for i < n_idx and every element of the row: the largest (TDEQ_DENSE_MAXIMUM) or smallest
+ *                          (TDEQ_DENSE_MINIMUM) value of the piecewise quartic on the closed window between the queries tq[i]
+ *                          and tq2[i], and the time at which that element attains it.  (seg, x, tq) and (seg2, x2, tq2) are
+ *                          what tdeq_row_dense_search wrote for the two ends (both of one row of the record); their order
+ *                          does not matter.  `values` [n_idx, row_len] of the state type T, `times` [n_idx, row_len] double in
+ *                          TRUE time.  The extremum is over the left-continuous record on the window together with the RIGHT
+ *                          limits at the breakpoints p with lo <= p < hi (lo, hi the window's ends in solver time): the walk
+ *                          below enters the segment that starts at p at x = 0, so a state impulse at p inside the window or at
+ *                          its near end counts, one at its far end does not, and the time reported for a right limit is p.
+ *                          THE ARITHMETIC IS THE CONTRACT.  Everything is fp64, one rounded operation per written operation,
+ *                          nothing contracted; only + - * /, comparisons and fabs (no sqrt, no transcendental).  Per element:
+ *                          Ends.    (segA, tqa), (segB, tqb) = the two ends, swapped if tq2[i] < tq[i], so tqa <= tqb.  If x[i]
+ *                                   or x2[i] is NaN (an out-of-range end): values = NaN, times = NaN.
+ *                          Walk.    s = segA .. segB in order; ta_s = seg_ta[s], tb_s = seg_tb[s], h_s = tb_s - ta_s,
+ *                                   xlo = (s == segA) ? (tqa - ta_s) / h_s : 0.0,  xhi = (s == segB) ? (tqb - ta_s) / h_s : 1.0
+ *                                   (the fractions of the antiderivative, not rounded to T).
+ *                          Polynomials, the coefficients converted T -> double (exact):
+ *                                   p(x)  = e + x*(d + x*(c + x*(b + x*a)))
+ *                                   g(x)  = d + x*((c+c) + x*(3*b + x*(4*a)))
+ *                                   g1(x) = (c+c) + x*(6*b + x*(12*a))
+ *                                   x1 = (-b) / (4*a), the root of g1', when a != 0.
+ *                          bisect(phi, lo, hi), with neg(v) = (v < 0): if phi(lo) == 0 or phi(hi) == 0 (that end is a
+ *                                   candidate already) or neg(phi(lo)) == neg(phi(hi)) there is no root.  Otherwise at most 64
+ *                                   rounds of: mid = 0.5 * (lo + hi); stop if mid == lo || mid == hi; if phi(mid) == 0 the root
+ *                                   is mid; else mid replaces the end whose neg it shares.  After the rounds the root is lo if
+ *                                   fabs(phi(lo)) <= fabs(phi(hi)), else hi.  (An exact zero is treated alike for phi and -phi:
+ *                                   the minimum of a record is minus the maximum of the record with negated coefficients, at
+ *                                   the same time, bit for bit but for the sign of a zero value.)
+ *                          Isolation.  The pieces of g1 are bounded by [xlo, x1, xhi], x1 only if xlo < x1 < xhi; bisect g1 on
+ *                                   each piece (at most 2 roots).  The pieces of g are bounded by xlo, those roots and xhi;
+ *                                   bisect g on each piece (at most 3 roots).  Every bound of a piece of g and every root of g
+ *                                   is a candidate: at most 7 evaluations of p per segment.
+ *                          Selection.  Candidates are visited in increasing x, segments in order; the first candidate sets the
+ *                                   best, a later one replaces it only if strictly greater (maximum) / strictly smaller
+ *                                   (minimum): a tie goes to the candidate met first in the direction of the solve.  A NaN
+ *                                   candidate value makes values and times NaN.  values = T(best): one rounding.
+ *                          Time of a candidate x of segment s:  tqa if s == segA and x == xlo;  else tqb if s == segB and
+ *                                   x == xhi;  else ta_s if x == 0;  else tb_s if x == 1 (the stored bits);  else ta_s + x * h_s.
+ *                                   times = time_sign * that.
+ *                          (Equal x give equal p(x), so a repeated candidate never replaces anything and an implementation may
+ *                          visit repeats or skip them.)
+ *                          One lane per (query, 16-byte element) walks its segments serially; no workspace, nothing cached.
+ *                          0 <= seg[i] , seg2[i] < n_seg (the walk is clamped to the record).  16-byte elements when row_len
+ *                          is a multiple of 16 / sizeof(T) and `values`, `times` and `coeffs` are 16-byte aligned, scalar
+ *                          elements otherwise.  A NULL pointer, `which` or time_sign other than those named, a negative
+ *                          size, n_seg > INT32_MAX or a dtype other than TDEQ_F32 / TDEQ_F64: TDEQ_EINVAL before any launch.
+ *                          n_idx == 0 or row_len == 0: no-op.
+ */
+#define TDEQ_DENSE_MAXIMUM 0
+#define TDEQ_DENSE_MINIMUM 1
+int tdeq_row_dense_extremum(void* values, double* times, int which, const void* coeffs, int64_t n_seg, const double* seg_ta,
+                            const double* seg_tb, double time_sign, const int32_t* seg, const void* x, const double* tq,
+                            const int32_t* seg2, const void* x2, const double* tq2, int64_t n_idx, int64_t row_len, int dtype,
+                            void* stream);
 
 /*
  * ---- Per-row step options (ABI 29; `min_step`, `max_step`, `step_t`, `jump_t` of the rowwise family) ----

@@ -18,7 +18,7 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-TDEQ_ABI_VERSION = 31
+TDEQ_ABI_VERSION = 32
 TDEQ_F32, TDEQ_F64 = 0, 1
 TDEQ_C64, TDEQ_C128 = 2, 3        # interleaved complex: the norm entry points only (include/tdeq_hip.h)
 TDEQ_BF16, TDEQ_F16 = 4, 5        # reduced-precision states: the entry points of the host-driven step (LowPrecisionHipKernels)
@@ -292,6 +292,11 @@ ABI_SIGNATURES = {
                                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double, ctypes.c_void_p,
                                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                            ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p]),
+    # extrema of the per-row dense record over a time window (ABI 32, `RowDenseOutput.maximum` / `.minimum`)
+    "tdeq_row_dense_extremum": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int64,
+                                               ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double, ctypes.c_void_p,
+                                               ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                               ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p]),
     # per-row step options (ABI 29, `min_step` / `max_step` / `step_t` / `jump_t` of the rowwise family)
     "tdeq_row_control_points": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(StepCtrl),
                                                ctypes.POINTER(RowState), ctypes.POINTER(RowPoints), ctypes.c_void_p,
@@ -1191,6 +1196,36 @@ class HipKernels:
                                             x.data_ptr(), ptr(tq, mode != 0), ptr(seg2, mode == 2), ptr(x2, mode == 2),
                                             ptr(tq2, mode == 2), n_idx, L, dtype_code(out.dtype), self._stream()),
                "tdeq_row_dense_calc")
+
+    def row_dense_extremum(self, values, times, which: int, coeffs, seg_ta, seg_tb, sign: float, seg, x, tq, seg2, x2,
+                           tq2) -> None:
+        """tdeq_row_dense_extremum: per element the maximum (`which` 0) or minimum (1) of the record on the window between
+        the queries (seg[i], x[i], tq[i]) and (seg2[i], x2[i], tq2[i]) of `row_dense_search`, and its time.  `values`
+        [n_idx, L] and `x`, `x2` [n_idx] of the dtype of `coeffs` [5, n_seg, L], `times` fp64 [n_idx, L] (true time), `seg`,
+        `seg2` int32 [n_idx], `tq`, `tq2` fp64 with n_idx elements in solver time, `sign` +1.0 or -1.0."""
+        n_idx = seg.numel()
+        if n_idx == 0:
+            return
+        n_seg = seg_ta.numel()
+        if coeffs.dim() != 3 or coeffs.shape[:2] != (5, n_seg) or coeffs.dtype != values.dtype or not coeffs.is_contiguous():
+            raise ValueError("row_dense_extremum: coeffs must be a contiguous [5, n_seg, L] tensor of values' dtype")
+        L = coeffs.shape[2]
+        if which not in (0, 1):
+            raise ValueError("row_dense_extremum: which 0 (maximum) or 1 (minimum)")
+        for name, t, dtype, shape in (("values", values, values.dtype, (n_idx, L)), ("times", times, torch.float64, (n_idx, L)),
+                                      ("seg_ta", seg_ta, torch.float64, (n_seg,)), ("seg_tb", seg_tb, torch.float64, (n_seg,)),
+                                      ("seg", seg, torch.int32, (n_idx,)), ("x", x, values.dtype, (n_idx,)),
+                                      ("tq", tq.view(-1), torch.float64, (n_idx,)), ("seg2", seg2, torch.int32, (n_idx,)),
+                                      ("x2", x2, values.dtype, (n_idx,)), ("tq2", tq2.view(-1), torch.float64, (n_idx,))):
+            if tuple(t.shape) != shape or t.dtype != dtype or not t.is_contiguous():
+                raise ValueError(f"row_dense_extremum: {name} must be a contiguous {dtype} {list(shape)} tensor")
+        if not tq.is_contiguous() or not tq2.is_contiguous():
+            raise ValueError("row_dense_extremum: tq and tq2 must be contiguous")
+        _check(self.lib.tdeq_row_dense_extremum(values.data_ptr(), times.data_ptr(), which, coeffs.data_ptr(), n_seg,
+                                                seg_ta.data_ptr(), seg_tb.data_ptr(), float(sign), seg.data_ptr(),
+                                                x.data_ptr(), tq.data_ptr(), seg2.data_ptr(), x2.data_ptr(), tq2.data_ptr(),
+                                                n_idx, L, dtype_code(values.dtype), self._stream()),
+               "tdeq_row_dense_extremum")
 
 
 class ComplexHipKernels:

@@ -916,3 +916,56 @@ int tdeq_row_dense_calc(void* out, int mode, const void* coeffs, int64_t n_seg, 
                                                   seg2, x2, tq2, n_idx, row_len, s);
     });
 }
+
+// ---- extrema of the record over a time window: tdeq_row_dense_extremum --------------------------------------------------
+namespace {
+
+template <typename T>
+int row_dense_extremum_launch(void* values, double* times, int which, const void* coeffs, int64_t n_seg, const double* seg_ta,
+                              const double* seg_tb, double time_sign, const int32_t* seg, const void* x, const double* tq,
+                              const int32_t* seg2, const void* x2, const double* tq2, int64_t n_idx, int64_t row_len,
+                              hipStream_t s) {
+    RowDenseExtremumArgs<T> a;
+    a.values = static_cast<T*>(values);
+    a.times = times;
+    a.q = static_cast<const T*>(coeffs);
+    a.seg_ta = seg_ta;
+    a.seg_tb = seg_tb;
+    a.sign = time_sign;
+    a.seg = seg;
+    a.x = static_cast<const T*>(x);
+    a.tq = tq;
+    a.seg2 = seg2;
+    a.x2 = static_cast<const T*>(x2);
+    a.tq2 = tq2;
+    a.n_seg = n_seg;
+    a.q_plane = n_seg * row_len;
+    return row_vec<T>(row_len, row_aligned(values, times, coeffs), a.row_len, [&](auto vec) {
+        constexpr bool VEC = decltype(vec)::value;
+        a.ne = n_idx * a.row_len;
+        const dim3 grid(stream_grid(a.ne, kBlock)), block(kBlock);
+        if (which == kDenseMaximum) hipLaunchKernelGGL((row_dense_extremum_kernel<T, VEC, true>), grid, block, 0, s, a);
+        else hipLaunchKernelGGL((row_dense_extremum_kernel<T, VEC, false>), grid, block, 0, s, a);
+        return check_launch();
+    });
+}
+
+}  // namespace
+
+int tdeq_row_dense_extremum(void* values, double* times, int which, const void* coeffs, int64_t n_seg, const double* seg_ta,
+                            const double* seg_tb, double time_sign, const int32_t* seg, const void* x, const double* tq,
+                            const int32_t* seg2, const void* x2, const double* tq2, int64_t n_idx, int64_t row_len, int dtype,
+                            void* stream) {
+    if (!values || !times || !coeffs || !seg_ta || !seg_tb || !seg || !x || !tq || !seg2 || !x2 || !tq2 || !row_dtype_ok(dtype))
+        return TDEQ_EINVAL;
+    if (which != TDEQ_DENSE_MAXIMUM && which != TDEQ_DENSE_MINIMUM) return TDEQ_EINVAL;
+    if (!(time_sign == 1.0 || time_sign == -1.0)) return TDEQ_EINVAL;
+    if (n_idx < 0 || n_seg < 0 || row_len < 0) return TDEQ_EINVAL;
+    if (n_idx == 0 || row_len == 0) return 0;
+    if (n_seg < 1 || n_seg > 0x7fffffffLL) return TDEQ_EINVAL;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return row_dtype(dtype, [&](auto t) {
+        return row_dense_extremum_launch<decltype(t)>(values, times, which, coeffs, n_seg, seg_ta, seg_tb, time_sign, seg, x,
+                                                      tq, seg2, x2, tq2, n_idx, row_len, s);
+    });
+}

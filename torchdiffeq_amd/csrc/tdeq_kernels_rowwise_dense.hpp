@@ -14,7 +14,8 @@
 //   row_dense_search   one lane per query: the segment of the row that holds the query time (bisection over the row's
 //                      segment ends) and the fraction x of that step, in the arithmetic of row_dense_commit
 // followed by row_event_eval_mapped on (coeffs, seg, x).  No LDS; plain vector loads and stores; 64-bit element offsets.
-// The derivative, antiderivative and integral of the record (row_dense_prefix, row_dense_calc) are at the end of the file.
+// The derivative, antiderivative and integral of the record (row_dense_prefix, row_dense_calc) and its extrema over a time
+// window (row_dense_extremum) are at the end of the file.
 #pragma once
 
 #include "tdeq_kernels_rowwise.hpp"
@@ -313,6 +314,174 @@ __global__ __launch_bounds__(kBlock) void row_dense_calc_kernel(const RowDenseCa
             __builtin_memcpy(&w, o, sizeof(E));
             reinterpret_cast<E*>(a.out)[i] = w;
         }
+    }
+}
+
+// ---- extrema of the record over a time window (ABI 32): RowDenseOutput.maximum / .minimum -----------------------------
+//   row_dense_extremum   the shape of row_dense_calc with a walk: one lane per (query, 16-byte element) goes through the
+//                        segments segA .. segB of its window serially and keeps, per element, the best candidate value and
+//                        its time.  The arithmetic — fp64, + - * /, comparisons and fabs only — is stated in
+//                        include/tdeq_hip.h and is the contract; the host model (rowwise.py quartic_extrema) has its bits.
+// On a segment where the element is monotone the lane evaluates g1 twice (three times with x1 inside), g twice and p twice
+// and takes no loop.  A bisection is at most 64 dependent rounds of one Horner form (4 to 6 fp64 operations and a compare);
+// lanes of a wave that need none wait for those that do.  No LDS, no atomics, no workspace.
+
+// modes of row_dense_extremum (== TDEQ_DENSE_MAXIMUM / _MINIMUM)
+constexpr int kDenseMaximum = 0;
+constexpr int kDenseMinimum = 1;
+
+template <typename T>
+struct RowDenseExtremumArgs {
+    T* values;                        // [n_idx, L]
+    double* times;                    // [n_idx, L] true time
+    const T* q;                       // [5, n_seg, L]
+    const double* seg_ta;             // [n_seg]
+    const double* seg_tb;             // [n_seg]
+    double sign;
+    const int32_t* seg;               // [n_idx] one end of each window (row_dense_search)
+    const T* x;                       // [n_idx] NaN marks an out-of-range end
+    const double* tq;                 // [n_idx] solver time
+    const int32_t* seg2;              // the other end
+    const T* x2;
+    const double* tq2;
+    int64_t n_seg;
+    int64_t row_len;                  // E units
+    int64_t ne;                       // n_idx * row_len
+    int64_t q_plane;                  // n_seg * L elements of T
+};
+
+// c0 + x*(c1 + x*(c2 + x*c3)): g with (d, c+c, 3b, 4a); g1 with (c+c, 6b, 12a, 0) skips the last term
+struct QuarticSlope {
+    double c0, c1, c2, c3;
+    __device__ __forceinline__ double operator()(double x) const { return c0 + x * (c1 + x * (c2 + x * c3)); }
+};
+struct QuarticCurvature {
+    double c0, c1, c2;
+    __device__ __forceinline__ double operator()(double x) const { return c0 + x * (c1 + x * c2); }
+};
+
+// bisect(phi, lo, hi) of the header -> a root was found (in `root`)
+template <typename F>
+__device__ __forceinline__ bool quartic_bisect(const F& phi, double lo, double hi, double& root) {
+    double flo = phi(lo), fhi = phi(hi);
+    const bool nlo = flo < 0.0;
+    if (flo == 0.0 || fhi == 0.0 || nlo == (fhi < 0.0)) return false;
+    for (int k = 0; k < 64; ++k) {
+        const double mid = 0.5 * (lo + hi);
+        if (mid == lo || mid == hi) break;
+        const double fm = phi(mid);
+        if (fm == 0.0) {
+            root = mid;
+            return true;
+        }
+        if ((fm < 0.0) == nlo) {
+            lo = mid;
+            flo = fm;
+        } else {
+            hi = mid;
+            fhi = fm;
+        }
+    }
+    root = __builtin_fabs(flo) <= __builtin_fabs(fhi) ? lo : hi;
+    return true;
+}
+
+template <typename T, bool VEC, bool MAX>
+__global__ __launch_bounds__(kBlock) void row_dense_extremum_kernel(const RowDenseExtremumArgs<T> a) {
+    using E = typename std::conditional<VEC, typename VecOf<T>::type, T>::type;
+    constexpr int LV = VEC ? VecOf<T>::L : 1;
+    const int64_t stride = (int64_t)gridDim.x * kBlock;
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < a.ne; i += stride) {
+        const int64_t r = i / a.row_len;
+        const int64_t el = i - r * a.row_len;
+        int64_t sA = a.seg[r], sB = a.seg2[r];
+        double tqa = a.tq[r], tqb = a.tq2[r];
+        const T xa = a.x[r], xb = a.x2[r];
+        if (tqb < tqa) {
+            const int64_t s = sA;
+            sA = sB;
+            sB = s;
+            const double t = tqa;
+            tqa = tqb;
+            tqb = t;
+        }
+        if (sA < 0) sA = 0;                                           // (nothing is read outside the record)
+        if (sB > a.n_seg - 1) sB = a.n_seg - 1;
+        const bool bad = xa != xa || xb != xb || sA > sB;             // (sA > sB: only from ends the search did not write)
+        double best[LV], when[LV];
+        bool nanv[LV];
+#pragma unroll
+        for (int c = 0; c < LV; ++c) {
+            best[c] = when[c] = 0.0;
+            nanv[c] = bad;
+        }
+        bool first = true;
+        for (int64_t s = bad ? sB + 1 : sA; s <= sB; ++s) {           // serial: segments in order
+            const int64_t at = s * a.row_len + el;
+            T qe[LV], qd[LV], qc[LV], qb[LV], qa[LV];
+            load_lanes<T, E, LV>(a.q, at, qe);
+            load_lanes<T, E, LV>(a.q + a.q_plane, at, qd);
+            load_lanes<T, E, LV>(a.q + 2 * a.q_plane, at, qc);
+            load_lanes<T, E, LV>(a.q + 3 * a.q_plane, at, qb);
+            load_lanes<T, E, LV>(a.q + 4 * a.q_plane, at, qa);
+            const double ta = a.seg_ta[s], tb = a.seg_tb[s];
+            const double h = tb - ta;
+            const bool atA = s == sA, atB = s == sB;
+            const double xlo = atA ? (tqa - ta) / h : 0.0;
+            const double xhi = atB ? (tqb - ta) / h : 1.0;
+#pragma unroll
+            for (int c = 0; c < LV; ++c) {
+                const double e = (double)qe[c], d = (double)qd[c], cc = (double)qc[c], b = (double)qb[c], aa = (double)qa[c];
+                const double c2 = cc + cc, a4 = 4.0 * aa;
+                const QuarticSlope g{d, c2, 3.0 * b, a4};
+                const QuarticCurvature g1{c2, 6.0 * b, 12.0 * aa};
+                double bst = best[c], whn = when[c];
+                bool have = !first;
+                auto consider = [&](double x) {
+                    const double v = e + x * (d + x * (cc + x * (b + x * aa)));
+                    if (v != v) nanv[c] = true;
+                    if (!have || (MAX ? v > bst : v < bst)) {
+                        have = true;
+                        bst = v;
+                        whn = (atA && x == xlo) ? tqa : (atB && x == xhi) ? tqb : x == 0.0 ? ta : x == 1.0 ? tb : ta + x * h;
+                    }
+                };
+                // the roots of g1 bound the pieces of g; a piece without a root passes its lower bound on
+                double xm = xlo;
+                if (aa != 0.0) {
+                    const double x1 = (-b) / a4;
+                    if (xlo < x1 && x1 < xhi) xm = x1;
+                }
+                double r0 = xlo, r1, z;
+                if (xm > xlo) quartic_bisect(g1, xlo, xm, r0);
+                r1 = r0;
+                quartic_bisect(g1, xm, xhi, r1);
+                consider(xlo);
+                if (r0 > xlo) {
+                    if (quartic_bisect(g, xlo, r0, z)) consider(z);
+                    consider(r0);
+                }
+                if (r1 > r0) {
+                    if (quartic_bisect(g, r0, r1, z)) consider(z);
+                    consider(r1);
+                }
+                if (quartic_bisect(g, r1, xhi, z)) consider(z);
+                consider(xhi);
+                best[c] = bst;
+                when[c] = whn;
+            }
+            first = false;
+        }
+        T o[LV];
+#pragma unroll
+        for (int c = 0; c < LV; ++c) {
+            o[c] = nanv[c] ? (T)__builtin_nan("") : (T)best[c];
+            when[c] = nanv[c] ? __builtin_nan("") : a.sign * when[c];
+        }
+        E w;
+        __builtin_memcpy(&w, o, sizeof(E));
+        reinterpret_cast<E*>(a.values)[i] = w;
+        store_doubles<LV>(a.times + i * LV, when);
     }
 }
 

@@ -903,6 +903,93 @@ class HostRowKernels:
             total = sign * (prefix.numpy()[s] + HostRowKernels._quartic_integral(*planes, x64, h[:, None]))
         return torch.from_numpy(total)
 
+    # -- extrema of a dense record over a window (the arithmetic of tdeq_row_dense_extremum, include/tdeq_hip.h) ----------
+    @staticmethod
+    def _bisect(phi, lo, hi, on):
+        """bisect(phi, lo, hi) of the header on fp64 arrays, where `on` -> (a root was found, the root): every round moves all
+        the elements that still bisect."""
+        lo, hi = lo.copy(), hi.copy()
+        flo, fhi = phi(lo), phi(hi)
+        nlo = flo < 0
+        found = on & (flo != 0) & (fhi != 0) & (nlo != (fhi < 0))
+        live = found.copy()
+        for _ in range(64):
+            if not live.any():
+                break
+            mid = 0.5 * (lo + hi)
+            live &= (mid != lo) & (mid != hi)
+            fm = phi(mid)
+            hit = live & (fm == 0)                           # an exact zero is the root: both ends move onto it
+            left = live & (hit | ((fm < 0) == nlo))
+            right = live & (hit | ~left)
+            lo, flo = np.where(left, mid, lo), np.where(left, fm, flo)
+            hi, fhi = np.where(right, mid, hi), np.where(right, fm, fhi)
+            live &= ~hit
+        return found, np.where(np.abs(flo) <= np.abs(fhi), lo, hi)
+
+    @staticmethod
+    def quartic_extrema(q, ta, tb, sign: float, src, x, tq, src2, x2, tq2, maximum: bool):
+        """The maximum (or minimum) of the record `q` [5, n_seg, L] on the windows between the queries (src, x, tq) and (src2,
+        x2, tq2) of the search, per element, and its time -> (values [n, L] in the state's type, times fp64 [n, L] in true
+        time).  Step k of every window's walk at once; the bisection rounds run under masks."""
+        H = HostRowKernels
+        planes, start, end = q.numpy(), ta.numpy(), tb.numpy()
+        sa, sb = src.numpy().astype(np.int64), src2.numpy().astype(np.int64)
+        qa, qb = tq.numpy().reshape(-1), tq2.numpy().reshape(-1)
+        swap = qb < qa
+        sa, sb = np.where(swap, sb, sa), np.where(swap, sa, sb)
+        qa, qb = np.where(swap, qb, qa), np.where(swap, qa, qb)
+        bad = np.isnan(x.numpy()) | np.isnan(x2.numpy()) | (sa > sb)
+        n, L = sa.size, planes.shape[2]
+        best, when = np.zeros((n, L)), np.zeros((n, L))
+        have, nan = np.zeros((n, L), dtype=bool), np.repeat(bad[:, None], L, axis=1)
+        count = np.where(bad, 0, sb - sa + 1)
+        with np.errstate(all="ignore"):
+            for k in range(int(count.max()) if n else 0):
+                idx = np.flatnonzero(count > k)
+                s = sa[idx] + k
+                e, d, c, b, a = (planes[p, s].astype(np.float64) for p in range(5))
+                t_a, t_b = start[s][:, None], end[s][:, None]
+                h = t_b - t_a
+                atA, atB = np.full((idx.size, 1), k == 0), (s == sb[idx])[:, None]
+                t_lo, t_hi = qa[idx][:, None], qb[idx][:, None]
+                xlo = np.broadcast_to(np.where(atA, (t_lo - t_a) / h, 0.0), e.shape)
+                xhi = np.broadcast_to(np.where(atB, (t_hi - t_a) / h, 1.0), e.shape)
+                c2, a4 = c + c, 4.0 * a
+                b3, b6, a12 = 3.0 * b, 6.0 * b, 12.0 * a
+                g = lambda v: d + v * (c2 + v * (b3 + v * a4))           # noqa: E731
+                g1 = lambda v: c2 + v * (b6 + v * a12)                   # noqa: E731
+                bst, whn, hv, nn = best[idx], when[idx], have[idx], nan[idx]
+
+                def consider(v, on):
+                    nonlocal bst, whn, hv, nn
+                    p = e + v * (d + v * (c + v * (b + v * a)))
+                    nn = nn | (on & np.isnan(p))
+                    take = on & (~hv | ((p > bst) if maximum else (p < bst)))
+                    t = np.where(atA & (v == xlo), t_lo, np.where(atB & (v == xhi), t_hi, np.where(
+                        v == 0.0, t_a, np.where(v == 1.0, t_b, t_a + v * h))))
+                    bst, whn, hv = np.where(take, p, bst), np.where(take, t, whn), hv | on
+
+                every = np.ones(e.shape, dtype=bool)
+                x1 = (-b) / a4
+                xm = np.where((a != 0.0) & (xlo < x1) & (x1 < xhi), x1, xlo)
+                f0, root = H._bisect(g1, xlo, xm, xm > xlo)
+                r0 = np.where(f0, root, xlo)
+                f1, root = H._bisect(g1, xm, xhi, every)
+                r1 = np.where(f1, root, r0)
+                consider(xlo, every)
+                for lo, hi in ((xlo, r0), (r0, r1)):
+                    fz, z = H._bisect(g, lo, hi, hi > lo)
+                    consider(z, fz)
+                    consider(hi, hi > lo)
+                fz, z = H._bisect(g, r1, xhi, every)
+                consider(z, fz)
+                consider(xhi, every)
+                best[idx], when[idx], have[idx], nan[idx] = bst, whn, hv, nn
+            values = np.where(nan, np.nan, best).astype(planes.dtype)
+            times = np.where(nan, np.nan, sign * when)
+        return torch.from_numpy(values), torch.from_numpy(times)
+
     def event_eval_mapped(self, out, dst, q, src, x) -> None:
         """out[dst[i] (None: i), :] = the quartic q[:, src[i]] at x[i], for the index lists `dst`, `src`."""
         if src.numel() == 0:

@@ -16,9 +16,13 @@ host keeps an upper bound of the slots taken (a step accepts at most `n_active` 
 one word — only when that bound leaves no room.  An evaluation is `tdeq_row_dense_search` (per query: the row's segment
 and the fraction of the step) followed by `tdeq_row_event_eval_mapped`.  The derivative, antiderivative and integral of the
 record are the same search followed by `tdeq_row_dense_calc`; the two integrals read a per-row prefix of whole-step
-integrals that `tdeq_row_dense_prefix` builds on first use.  CPU states run the same steps as torch / numpy ops.
+integrals that `tdeq_row_dense_prefix` builds on first use.  The maximum and minimum over a time window are the search of both ends followed
+by `tdeq_row_dense_extremum`, which walks the window's segments and builds nothing.  CPU states run the same steps as
+torch / numpy ops.
 """
 from __future__ import annotations
+
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -27,7 +31,7 @@ from . import rowwise
 from ._native import device_guard
 from .rowwise import _Problem
 
-__all__ = ["odeint_rowwise_dense", "RowDenseOutput"]
+__all__ = ["odeint_rowwise_dense", "RowDenseOutput", "RowDenseExtremum"]
 
 # the default chunk: CHUNK_ROWS_PER_ROW slots per row of the batch, at most CHUNK_BYTES of coefficients, never fewer than B
 CHUNK_ROWS_PER_ROW = 4
@@ -158,9 +162,17 @@ class RowDenseStore:
         return offsets, seg_ta, seg_tb, coeffs
 
 
+class RowDenseExtremum(NamedTuple):
+    """`RowDenseOutput.maximum` / `.minimum`: per element the extreme value (the state's dtype) and the true time (fp64) at
+    which that element attains it."""
+    values: torch.Tensor
+    times: torch.Tensor
+
+
 class RowDenseOutput:
     """The piecewise quartic of a rowwise solve; `dense(t)` evaluates it, `derivative(t)`, `antiderivative(t)` and
-    `integral(ta, tb)` give its time derivative and its integrals in closed form (see `odeint_rowwise_dense`).
+    `integral(ta, tb)` give its time derivative and its integrals in closed form, `maximum(ta, tb)` and `minimum(ta, tb)` its
+    extrema over a time window and their times (see `odeint_rowwise_dense`).
 
     Attributes (the wire format, all on the state's device): `t0`, `t1` `[B]` fp64 in true time; `offsets` `[B + 1]` int64;
     `seg_start`, `seg_end` `[n_seg]` fp64 in true time, row r's segments — its accepted steps — contiguous and in step
@@ -281,15 +293,8 @@ class RowDenseOutput:
     def _calculus(self, what: str, mode: int, names, ts, check: bool) -> torch.Tensor:
         """`derivative` (mode 0), `antiderivative` (1), `integral` (2) of the query lists `ts`, in the steps of `dense(t)`:
         the search per list, one evaluation, one read of the status words (with `check`)."""
-        parsed = [self._queries(t) for t in ts]
-        single = all(one for _, one in parsed)
-        tqs = [tq for tq, _ in parsed]
+        tqs, single = self._query_lists(what, names, ts)
         B = self._shape[0]
-        if len(tqs) == 2 and tqs[0].shape[0] != tqs[1].shape[0]:
-            Qa, Qb = tqs[0].shape[0], tqs[1].shape[0]
-            if 1 not in (Qa, Qb):
-                raise ValueError(f"{what}: {names[0]} and {names[1]} hold {Qa} and {Qb} times; they do not broadcast")
-            tqs = [tq.expand(Qa * Qb, B).contiguous() for tq in tqs]      # (one of them is 1: Qa * Qb is the other)
         Q = tqs[0].shape[0]
         L, dev, dtype = self.coeffs.shape[2], self.coeffs.device, self.coeffs.dtype
         out = torch.empty(Q * B, L, dtype=dtype, device=dev)
@@ -325,13 +330,30 @@ class RowDenseOutput:
                     if check:
                         firsts = status.tolist()                          # the one read
         if check:
-            for name, tq, first in zip(names, tqs, firsts):
-                if first != _NONE:
-                    j, r = divmod(first, B)
-                    raise ValueError("{}: query {} of row {} ({} = {}) is outside the row's interval [t0, t1] = [{}, {}]".format(
-                        what, j, r, name, float(tq[j, r]) * self._sign, float(self.t0[r]), float(self.t1[r])))
+            self._raise_out_of_range(what, names, tqs, firsts)
         out = out.view(Q, *self._shape)
         return out[0] if single else out
+
+    def _query_lists(self, what: str, names, ts):
+        """One or two query lists -> ([fp64 [Q, B] in solver time, ...] broadcast against each other, all were single)."""
+        parsed = [self._queries(t) for t in ts]
+        single = all(one for _, one in parsed)
+        tqs = [tq for tq, _ in parsed]
+        if len(tqs) == 2 and tqs[0].shape[0] != tqs[1].shape[0]:
+            Qa, Qb = tqs[0].shape[0], tqs[1].shape[0]
+            if 1 not in (Qa, Qb):
+                raise ValueError(f"{what}: {names[0]} and {names[1]} hold {Qa} and {Qb} times; they do not broadcast")
+            tqs = [tq.expand(Qa * Qb, self._shape[0]).contiguous() for tq in tqs]      # (one of them is 1: Qa * Qb is the other)
+        return tqs, single
+
+    def _raise_out_of_range(self, what: str, names, tqs, firsts) -> None:
+        """ValueError for the first list that has an out-of-range query (`firsts`: the status word of each list)."""
+        B = self._shape[0]
+        for name, tq, first in zip(names, tqs, firsts):
+            if first != _NONE:
+                j, r = divmod(first, B)
+                raise ValueError("{}: query {} of row {} ({} = {}) is outside the row's interval [t0, t1] = [{}, {}]".format(
+                    what, j, r, name, float(tq[j, r]) * self._sign, float(self.t0[r]), float(self.t1[r])))
 
     def derivative(self, t, check: bool = True) -> torch.Tensor:
         """`dy_r/dt` of the interpolant at `t`, with respect to TRUE time (also for a descending solve), in the query forms
@@ -353,6 +375,63 @@ class RowDenseOutput:
         `tb` each take the query forms of `dense(t)` and broadcast against each other; both must lie inside `[t0[r], t1[r]]`
         (`check=True` names the offending query of `ta` first, then of `tb`; `check=False` gives NaN rows)."""
         return self._calculus("dense.integral(ta, tb)", 2, ("ta", "tb"), (ta, tb), check)
+
+    # -- extrema over a time window: every segment's quartic between the window's ends -------------------------------------
+    def _extremum(self, what: str, which: int, ta, tb, check: bool) -> RowDenseExtremum:
+        """`maximum` (which 0) / `minimum` (1) in the steps of `integral`: the search per end, one launch, one read of the
+        status words (with `check`).  Nothing is built or kept."""
+        names = ("ta", "tb")
+        tqs, single = self._query_lists(what, names, (ta, tb))
+        Q, B = tqs[0].shape
+        if self._k is not None and Q * B >= _NONE:
+            raise ValueError(f"{what}: {Q * B} queries in one call; the query index is a 32-bit word")
+        L, dev, dtype = self.coeffs.shape[2], self.coeffs.device, self.coeffs.dtype
+        values = torch.empty(Q * B, L, dtype=dtype, device=dev)
+        times = torch.empty(Q * B, L, dtype=torch.float64, device=dev)
+        firsts = [_NONE, _NONE]
+        if Q > 0:
+            with torch.no_grad(), device_guard(dev):
+                if self._k is None:
+                    found = [self._search_host(tq) for tq in tqs]
+                    firsts = [first for _, _, first in found]
+                    lists = [v for (seg, x, _), tq in zip(found, tqs) for v in (seg, x, tq)]
+                    v, t = rowwise.HostRowKernels.quartic_extrema(self.coeffs, self._ta, self._tb, self._sign, *lists, which == 0)
+                    values.copy_(v)
+                    times.copy_(t)
+                else:
+                    status = torch.full((2,), _NONE, dtype=torch.int32, device=dev)
+                    lists = []
+                    for i, tq in enumerate(tqs):
+                        seg = torch.empty(Q * B, dtype=torch.int32, device=dev)
+                        x = torch.empty(Q * B, dtype=dtype, device=dev)
+                        self._k.row_dense_search(tq, self.offsets, self._ta, self._tb, self._t0, self._t1, seg, x,
+                                                 status[i:i + 1])
+                        lists += [seg, x, tq]
+                    self._k.row_dense_extremum(values, times, which, self.coeffs, self._ta, self._tb, self._sign, *lists)
+                    if check:
+                        firsts = status.tolist()                          # the one read
+        if check:
+            self._raise_out_of_range(what, names, tqs, firsts)
+        values, times = values.view(Q, *self._shape), times.view(Q, *self._shape)
+        return RowDenseExtremum(values[0], times[0]) if single else RowDenseExtremum(values, times)
+
+    def maximum(self, ta, tb, check: bool = True) -> RowDenseExtremum:
+        """The largest value every ELEMENT of `y_r` takes on the closed window between `ta` and `tb` (true time, in either
+        order: `maximum(a, b)` and `maximum(b, a)` have the same bits) and the time at which it takes it -> `RowDenseExtremum(
+        values, times)`: `values` in the state's dtype, `times` fp64, both `[Q, B, *row_shape]` (`[B, *row_shape]` for two
+        single times); elements of a row peak at different times.  `ta` and `tb` take the query forms of `integral` and
+        broadcast against each other; both must lie inside `[t0[r], t1[r]]` (`check=True` names the offending query of `ta`
+        first, then of `tb`; `check=False` gives NaN rows in both outputs and reads nothing).  Exact on the record: per step the
+        quartic's stationary points are isolated by bisection (see `odeint_rowwise_dense`).  The window holds the
+        left-continuous `dense(t)` and the RIGHT limits at the breakpoints `p` with `lo <= p < hi` (`lo`, `hi` the window's
+        ends in the direction of the solve): a `jump_dy` dose at `p` inside the window or at its near end counts with the
+        impulse, reported at time `p`; one at its far end does not.  Ties go to the earlier candidate in the direction of the
+        solve.  Builds and caches nothing."""
+        return self._extremum("dense.maximum(ta, tb)", 0, ta, tb, check)
+
+    def minimum(self, ta, tb, check: bool = True) -> RowDenseExtremum:
+        """The smallest value of every element on the window and its time: `maximum` with the comparison reversed."""
+        return self._extremum("dense.minimum(ta, tb)", 1, ta, tb, check)
 
 
 def odeint_rowwise_dense(func, y0, t0, t1, *, rtol=1e-7, atol=1e-9, method="dopri5", options=None, compact=None,
@@ -396,6 +475,20 @@ def odeint_rowwise_dense(func, y0, t0, t1, *, rtol=1e-7, atol=1e-9, method="dopr
     must be in range (`check=True` names the offending query of `ta` first, then of `tb`).  A ROCm state runs them on HIP
     kernels (`tdeq_row_dense_prefix`, `tdeq_row_dense_calc`, ABI 31), a CPU state as numpy / torch ops with the same bits.
 
+    Extrema on the record: `dense.maximum(ta, tb)` and `dense.minimum(ta, tb)` -> `RowDenseExtremum(values, times)`, per
+    ELEMENT the extreme value over the closed window between the two times (either order, the query forms and `check` of
+    `integral`) and the fp64 true time at which the element attains it — Cmax / Tmax and Cmin of a dosing solve.  The window
+    is walked step by step in fp64: on each step the candidates are the ends (clipped to the window) and the stationary
+    points of the quartic, isolated by nested bisection (the roots of y'' bound the pieces on which y' is monotone; only
+    `+ - * /`, comparisons and `fabs`, at most 64 rounds per root) — the exact operation order is stated in
+    include/tdeq_hip.h and is the contract: the HIP kernel (`tdeq_row_dense_extremum`, ABI 32) and the numpy path of a CPU
+    state have the same bits.  `values` is the best candidate rounded once to the state's dtype.  The segment that starts at a
+    breakpoint `p` is entered at its start, so the RIGHT limit at `p` counts for `lo <= p < hi`: a `jump_dy` dose inside the
+    window or at its near end contributes the state with the impulse at time `p`, one at the far end does not; `maximum(p, p)`
+    is `dense(p)` (the fp64 Horner form rounded once).  Ties go to the earlier candidate in the direction of the solve.  One
+    launch after the two searches; cost grows with the steps inside the window (one lane per element walks them); nothing is
+    built or cached.
+
     Returns `dense`; with `return_stats=True`, `(dense, stats)`: the stats of `odeint_rowwise` (`n_accepted`,
     `n_rejected`, `nfe`; with `compact` also `row_evals`, `n_repacks`) plus `n_segments` and `n_chunks`.
 
@@ -407,7 +500,7 @@ def odeint_rowwise_dense(func, y0, t0, t1, *, rtol=1e-7, atol=1e-9, method="dopr
     `8 * L * n_seg` bytes (fp64 `[n_seg, L]`: 40 % on top of an fp32 record), built by the first such call, kept on the object
     and released by `dense.drop_integral_cache()`; `dense(t)` and `derivative` never build it.
 
-    Out of scope (raises or is not offered): gradients through the solve, through `dense(t)` or through the three methods
+    Out of scope (raises or is not offered): gradients through the solve, through `dense(t)` or through the methods
     above (with grad mode on and
     `y0`, `t0`, `t1`, a query tensor or a parameter of `func` requiring grad: NotImplementedError; there is no
     `differentiable` argument), events combined with dense output, 16-bit / complex / tuple states (ValueError), captured
