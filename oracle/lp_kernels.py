@@ -16,6 +16,7 @@ inputs (tests/golden/make_golden_lowp.py -> tests/golden/lowp_kernels.npz).
 """
 from __future__ import annotations
 
+import math
 from typing import List, Sequence, Tuple
 
 import torch
@@ -147,3 +148,94 @@ def weighted_sum(xs, ws):
     for x, w in zip(xs[1:], ws[1:]):
         acc = acc + x * _t(w, x.dtype)
     return acc
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The step controller in the state's type, and the look-ahead first stage it selects (the parity oracle of the 16-bit
+# branches of norm_finalize_ctrl_kernel in csrc/tdeq_kernels.hpp and of lp::sel_kernel).  Pinned to the reference by
+# tests/test_lowp_oracle.py against tests/golden/lowp_controller.npz.
+# ---------------------------------------------------------------------------------------------------------------------
+def stage_combine_sel(y_acc, f_acc, y_rej, f_rej, coef, accept, dt_T):
+    """The first stage of the NEXT trial step, y + f * (beta_00 * dt) (rk_common.py:79 with one term), on the pair the
+    controller kept: (y1, f1) after an accepted step, (y0, f0) after a rejected one (rk_common.py:338-357).  `dt_T` is
+    the signed step size as a 0-dim tensor of the state's type holds it (rk_common.py:64)."""
+    y, f = (y_acc, f_acc) if accept else (y_rej, f_rej)
+    return y + f * (_t(coef, y.dtype) * _t(dt_T, y.dtype))
+
+
+def segment_norm(q, leading_abs: bool = False) -> float:
+    """`q.abs().pow(2).mean().sqrt()` (misc.py:22-23) of one segment, from the fp64 sum of the rounded squares the norm
+    kernels report: ATen's mean of a reduced-precision tensor is a float32 sum divided by a float32 count, rounded ONCE
+    to the type, and the `sqrt` is rounded again.  A one-element segment is |x|, squared in the type — the same
+    expression — and with `leading_abs` |x| itself (the adjoint norms take their time component as `t.abs()`,
+    adjoint.py:250, 273)."""
+    a = q.abs()
+    if leading_abs and q.numel() == 1:
+        return float(a.reshape(()))
+    total = a.pow(2).double().sum()
+    mean = (total.to(torch.float32) / torch.tensor(float(q.numel()), dtype=torch.float32)).to(q.dtype)
+    return float(mean.sqrt())
+
+
+def _nan_max(values) -> float:
+    """`max(...)` over 0-dim tensors as the controller needs it: a NaN wins wherever it stands."""
+    out = 0.0
+    for v in values:
+        if math.isnan(v) or math.isnan(out):
+            out = math.nan
+        else:
+            out = max(out, v)
+    return out
+
+
+def step_controller(norms, t0, dt, ctrl, dtype):
+    """One pass of rk_common.py:323-360 after the norms, and the stage times of the trial step that follows
+    (rk_common.py:61-78, 268-273, through misc.py:180-197).
+
+    `norms`: the per-segment values (`segment_norm`); `t0`, `dt`: the trial step just taken, fp64 host numbers, dt > 0;
+    `ctrl`: anything with the fields of `tdeq_step_ctrl` (safety, ifactor, dfactor, exponent = 1 / order, min_step,
+    max_step, time_sign, alpha — already rounded to the state's type — alpha_is_one, n_times, n_norm_seg).
+
+    -> (accept, dt_next, ratio, t0_next, T(dt') * sign, stage_times[T]) where dt_next is `_optimal_step_size` with a
+    fp64 `last_step` (misc.py:85-95) clamped (rk_common.py:359) and dt' is what the next `_adaptive_step` makes of it
+    (rk_common.py:269-271: a non-finite step size becomes min_step)."""
+    f64 = lambda x: torch.tensor(float(x), dtype=torch.float64)
+    ratio = _nan_max([float(v) for v in list(norms)[:ctrl.n_norm_seg]])                  # misc.py:30-33
+    t0_, dt_ = f64(t0), f64(dt)
+    lo, hi = f64(ctrl.min_step), f64(ctrl.max_step)
+    accept = bool(f64(ratio) <= 1)                                                       # rk_common.py:324
+    if dt_ > hi:
+        accept = False
+    if dt_ <= lo:
+        accept = True
+    error_ratio = f64(ratio)                                                             # misc.py:92 `.type_as(last_step)`
+    if error_ratio == 0:                                                                 # misc.py:88-95
+        dt_next = dt_ * f64(ctrl.ifactor)
+    else:
+        dfactor = f64(1.0) if error_ratio < 1 else f64(ctrl.dfactor)
+        factor = torch.min(f64(ctrl.ifactor), torch.max(f64(ctrl.safety) / error_ratio ** f64(ctrl.exponent), dfactor))
+        dt_next = dt_ * factor
+    dt_next = dt_next.clamp(lo, hi)                                                      # rk_common.py:359
+    t0_next = t0_ + dt_ if accept else t0_                                               # rk_common.py:340 / 355
+    dt_new = dt_next if bool(torch.isfinite(dt_next)) else lo                            # rk_common.py:269-271
+    dt_new = dt_new.clamp(lo, hi)
+    dt_signed = float(dt_new.to(dtype) * torch.tensor(float(ctrl.time_sign), dtype=dtype))
+    return (accept, float(dt_next), ratio, float(t0_next), dt_signed, stage_times(float(t0_next), float(dt_new), ctrl, dtype))
+
+
+def stage_times(t0, dt, ctrl, dtype):
+    """The times `func` sees during the trial step (t0, dt) — fp64 host numbers — of a state of `dtype`
+    (rk_common.py:61-78 through misc.py:180-197): t0, dt and t1 = t0 + dt are each cast from fp64, `t0 + alpha_i * dt` is
+    arithmetic on 0-dim tensors of the type, a stage at alpha == 1 sits at nextafter(t1, t1 - 1), and a solve in
+    decreasing time negates the result (misc.py:165, exact)."""
+    f64 = lambda x: torch.tensor(float(x), dtype=torch.float64)
+    t0T, dtT, t1T = f64(t0).to(dtype), f64(dt).to(dtype), (f64(t0) + f64(dt)).to(dtype)  # rk_common.py:63-65, 273
+    sign = torch.tensor(float(ctrl.time_sign), dtype=dtype)
+    times = []
+    for i in range(ctrl.n_times):
+        if (ctrl.alpha_is_one >> i) & 1:                                                 # rk_common.py:72-75, misc.py:193
+            ti = torch.nextafter(t1T, t1T - 1)
+        else:
+            ti = t0T + torch.tensor(float(ctrl.alpha[i]), dtype=dtype) * dtT             # rk_common.py:77
+        times.append(sign * ti)
+    return torch.stack(times)

@@ -3,8 +3,12 @@ tensors (CPU), stored as float32 (exact for both types).
 
     PYTHONDONTWRITEBYTECODE=1 python tests/golden/make_golden_lowp.py      (build container only: /root/reference)
 
--> tests/golden/lowp_kernels.npz.  Pins oracle/lp_kernels.py (tests/test_lowp_oracle.py), which in turn is what the HIP
-kernels of csrc/tdeq_kernels_lp.hpp are compared with bit for bit on the GPU (tests/test_lowp_gpu.py).
+-> tests/golden/lowp_kernels.npz (`main`) and tests/golden/lowp_controller.npz (`main_controller`: error ratios of
+crafted error rows, the step sizes that follow them and the stage times of the next trial step).  Pins
+oracle/lp_kernels.py (tests/test_lowp_oracle.py), which in turn is what the HIP kernels of csrc/tdeq_kernels_lp.hpp are
+compared with bit for bit on the GPU (tests/test_lowp_gpu.py, tests/test_lowp_kernels_gpu.py).
+
+    ... make_golden_lowp.py controller        writes lowp_controller.npz only (lowp_kernels.npz stays as it is)
 """
 import os
 import sys
@@ -113,5 +117,102 @@ def main():
     print("lowp_kernels.npz", len(out), "arrays")
 
 
+RATIO_CASES = ("zero", "small", "one", "one_up", "large", "inf", "nan")
+
+
+def crafted_rows(dtype, n, rtol, atol):
+    """(y1_error, y0, y1) rows [7, n] whose error ratios are 0, about 1e-3, exactly 1, one unit in the last place above
+    1, about 30, inf and NaN.  The exact ones have y0 = y1 = 0, so that the quotient is error / T(atol)."""
+    aT = torch.tensor(atol, dtype=torch.float64).to(dtype)
+    zero = torch.zeros(n, dtype=dtype)
+    signs = torch.where(rand(n, seed=70, dtype=dtype) < 0, -torch.ones(n, dtype=dtype), torch.ones(n, dtype=dtype))
+    y0, y1 = rand(n, seed=71, dtype=dtype), rand(n, seed=72, dtype=dtype)
+    tol = (atol + rtol * torch.max(y0.abs(), y1.abs()).double())
+    noise = rand(n, seed=73, dtype=torch.float64)
+    big = noise.clone().to(dtype)
+    big[n // 2] = torch.finfo(dtype).max                      # / T(atol) overflows the type
+    bad = noise.clone().to(dtype)
+    bad[n - 1] = float("nan")
+    rows = [(zero, zero, zero),
+            ((1e-3 * tol * noise).to(dtype), y0, y1),
+            (signs * aT, zero, zero),
+            (signs * torch.nextafter(aT, aT + 1), zero, zero),
+            ((30 * tol * noise).to(dtype), y0, y1),
+            (big, zero, zero),
+            (bad, y0, y1)]
+    return [torch.stack([r[j] for r in rows]) for j in range(3)]
+
+
+class SeenTimes:
+    """The innermost `func`: records the time it is called with, returns zeros."""
+
+    def __init__(self):
+        self.seen = []
+
+    def __call__(self, t, y):
+        self.seen.append(t.clone())
+        return torch.zeros_like(y)
+
+
+def main_controller():
+    arrays = {}
+    n = 33
+    f32 = lambda t: t.to(torch.float32)
+    rtol, atol = 1e-2, 1e-3
+    # (name, reversed, solver-side t0, dt, min_step, max_step): the second one also exercises both clamps
+    directions = [("fwd", False, 0.3, 0.0371, 0.0, float("inf")), ("rev", True, -2.0, 0.0371, 1e-3, 0.05)]
+    for dname, dtype in [("bf16", torch.bfloat16), ("f16", torch.float16)]:
+        err, y0s, y1s = crafted_rows(dtype, n, rtol, atol)
+        for mname, solver_cls in [("dopri5", dopri5.Dopri5Solver), ("dopri8", dopri8.Dopri8Solver),
+                                  ("tsit5", tsit5.Tsit5Solver), ("bosh3", bosh3.Bosh3Solver)]:
+            key = f"{mname}_{dname}"
+            solver = solver_cls(func=None, y0=y0s[0], rtol=rtol, atol=atol, norm=misc._rms_norm)
+            ratios = [misc._compute_error_ratio(e, solver.rtol, solver.atol, a, b, misc._rms_norm)
+                      for e, a, b in zip(err, y0s, y1s)]
+            assert all(r.dtype == dtype for r in ratios)
+            one_up = float(torch.nextafter(torch.ones((), dtype=dtype), torch.full((), 2.0, dtype=dtype)))
+            assert [float(r) for r in ratios[:1] + ratios[2:4] + ratios[5:6]] == [0.0, 1.0, one_up, float("inf")]
+            assert 3e-4 < float(ratios[1]) < 3e-3 and 10 < float(ratios[4]) < 90 and bool(torch.isnan(ratios[6]))
+            arrays[f"{key}_err"], arrays[f"{key}_y0"], arrays[f"{key}_y1"] = f32(err), f32(y0s), f32(y1s)
+            arrays[f"{key}_rtol_atol"] = torch.tensor([rtol, atol], dtype=torch.float64)
+            arrays[f"{key}_ratio"] = torch.stack(ratios).to(torch.float64)
+            arrays[f"{key}_order"] = torch.tensor(solver.order)
+            for d, rev, t0, dt, lo, hi in directions:
+                t0, dt = torch.tensor(t0, dtype=torch.float64), torch.tensor(dt, dtype=torch.float64)
+                lo, hi = torch.tensor(lo, dtype=torch.float64), torch.tensor(hi, dtype=torch.float64)
+                dt_opt, dt_next, accepts, t_next, times = [], [], [], [], []
+                for ratio in ratios:
+                    h = misc._optimal_step_size(dt, ratio, solver.safety, solver.ifactor, solver.dfactor, solver.order)
+                    assert h.dtype == torch.float64
+                    dt_opt.append(h)
+                    dt_next.append(h.clamp(lo, hi))
+                    accept = bool(ratio <= 1)
+                    accept = False if dt > hi else accept
+                    accept = True if dt <= lo else accept
+                    accepts.append(accept)
+                    t_next.append(t0 + dt if accept else t0)
+                    # the trial step that follows: its size as the solver would take it, its stage times as `func` sees them
+                    h = dt_next[-1] if torch.isfinite(dt_next[-1]) else lo
+                    h = h.clamp(lo, hi)
+                    inner = SeenTimes()
+                    func = misc._PerturbFunc(misc._ReverseFunc(inner, mul=-1.0) if rev else inner)
+                    rk_common._runge_kutta_step(func, y0s[0], y0s[0], t_next[-1], h, t_next[-1] + h, solver.tableau)
+                    assert all(t.dtype == dtype for t in inner.seen) and len(inner.seen) == len(solver.tableau.alpha)
+                    times.append(torch.stack(inner.seen))
+                arrays[f"{key}_{d}_step"] = torch.stack([t0, dt, lo, hi, torch.tensor(-1.0 if rev else 1.0, dtype=torch.float64)])
+                arrays[f"{key}_{d}_dt_opt"] = torch.stack(dt_opt)
+                arrays[f"{key}_{d}_dt_next"] = torch.stack(dt_next)
+                arrays[f"{key}_{d}_accept"] = torch.tensor(accepts)
+                arrays[f"{key}_{d}_t0_next"] = torch.stack(t_next)
+                arrays[f"{key}_{d}_times"] = f32(torch.stack(times))
+    out = {k: v.detach().cpu().numpy() for k, v in arrays.items()}
+    np.savez_compressed(os.path.join(HERE, "lowp_controller.npz"), **out)
+    print("lowp_controller.npz", len(out), "arrays")
+
+
 if __name__ == "__main__":
-    main()
+    if sys.argv[1:] == ["controller"]:
+        main_controller()
+    else:
+        main()
+        main_controller()

@@ -7,7 +7,11 @@ reference's arithmetic up to the order of a row's float32 accumulation".
 Where the oracle and the reference can differ: a tableau row summed over its non-zero weights left to right vs ATen's
 own order over the dense row — float32 accumulation of <= 14 products that carry 8 (bf16) / 11 (fp16) significand bits,
 i.e. exact in almost every element; the bound below is one unit in the last place of the storage type on a small
-fraction of the elements, and identical everywhere else."""
+fraction of the elements, and identical everywhere else.
+
+The controller half of the oracle (`segment_norm`, `step_controller`, `stage_times`: what the 16-bit device controller is
+compared with in tests/test_lowp_kernels_gpu.py) has no row sums: it is pinned exactly, to lowp_controller.npz and to
+ATen's literal rms expression."""
 import os
 import sys
 
@@ -18,6 +22,7 @@ import torch
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
 from oracle import lp_kernels as olp  # noqa: E402
+from _lowp_kernels import COEFS  # noqa: E402  (the weights tests/test_lowp_gpu.py uses)
 from torchdiffeq_amd import _fallback, tableaus as tb  # noqa: E402
 
 Z = np.load(os.path.join(HERE, "golden", "lowp_kernels.npz"))
@@ -95,6 +100,71 @@ def test_fixed_grid_pieces_equal_the_reference_bit_for_bit(low):
     yy, f0 = T(Z[f"init_{low}_y0_f0"], dtype)
     q0, q1 = olp.init_quotients(0, yy.reshape(-1), f0.reshape(-1), yy.reshape(-1), 1e-2, 1e-3)
     assert torch.equal(q0, T(Z[f"init_{low}_q0"], dtype).reshape(-1)) and torch.equal(q1, T(Z[f"init_{low}_q1"], dtype).reshape(-1))
+
+
+ZC = np.load(os.path.join(HERE, "golden", "lowp_controller.npz"))
+RATIO_CASES = ("zero", "small", "one", "one_up", "large", "inf", "nan")
+
+
+def controller_fields(tab, order, dtype, sign=1.0, min_step=0.0, max_step=float("inf"), n_norm_seg=1):
+    """The fields of `tdeq_step_ctrl` as solvers/adaptive.py fills them for a state of `dtype`: abscissae rounded to the
+    state's type (rk_common.py:201), `alpha == 1` decided before the rounding."""
+    import types
+    alpha = [float(torch.tensor(float(a), dtype=torch.float64).to(dtype)) for a in tab.alpha]
+    return types.SimpleNamespace(safety=0.9, ifactor=10.0, dfactor=0.2, exponent=1.0 / order, min_step=min_step,
+                                 max_step=max_step, time_sign=sign, alpha=alpha, n_times=len(alpha), n_norm_seg=n_norm_seg,
+                                 alpha_is_one=sum(1 << i for i, a in enumerate(tab.alpha) if a == 1.0), leading_abs=0)
+
+
+@pytest.mark.parametrize("low", ["bf16", "f16"])
+@pytest.mark.parametrize("method", list(TABS))
+def test_step_controller_equals_the_reference(method, low):
+    """`segment_norm` + `step_controller` against what the reference's `_compute_error_ratio`, `_optimal_step_size` and
+    `_PerturbFunc` gave for crafted error rows (ratios 0, ~1e-3, 1, 1 + ulp, ~30, inf, NaN), forwards and in decreasing
+    time (the latter with both step bounds active): accept, ratio, t0' and the stage times bit for bit, the step size
+    equal (libm's pow on both sides)."""
+    dtype, tab, key = DT[low], TABS[method], f"{method}_{low}"
+    rtol, atol = (float(v) for v in ZC[key + "_rtol_atol"])
+    order = int(ZC[key + "_order"])
+    for d in ("fwd", "rev"):
+        t0, dt, lo, hi, sign = (float(v) for v in ZC[f"{key}_{d}_step"])
+        c = controller_fields(tab, order, dtype, sign, lo, hi)
+        for i, case in enumerate(RATIO_CASES):
+            e, y0, y1 = (T(ZC[f"{key}_{name}"][i], dtype) for name in ("err", "y0", "y1"))
+            q = olp.error_quotient(y0, y1, [e], (1.0,), 1.0, rtol, atol)       # (one term, weight 1, dt 1: the row itself)
+            accept, dt_next, ratio, t0_next, dt_signed, times = olp.step_controller([olp.segment_norm(q)], t0, dt, c, dtype)
+            where = (d, case)
+            assert np.array_equal(ratio, ZC[key + "_ratio"][i], equal_nan=True), where
+            assert accept == bool(ZC[f"{key}_{d}_accept"][i]), where
+            assert t0_next == float(ZC[f"{key}_{d}_t0_next"][i]), where
+            assert np.array_equal(dt_next, ZC[f"{key}_{d}_dt_next"][i], equal_nan=True), where
+            if lo == 0.0 and hi == float("inf"):
+                assert np.array_equal(dt_next, ZC[f"{key}_{d}_dt_opt"][i], equal_nan=True), where
+            ref_times = T(ZC[f"{key}_{d}_times"][i], dtype)
+            assert times.dtype == dtype and torch.equal(times.view(torch.int16), ref_times.view(torch.int16)), where
+            # the signed step size the device keeps for the kernels: T(dt') * sign
+            h = dt_next if np.isfinite(dt_next) else lo
+            assert dt_signed == sign * float(torch.tensor(min(max(h, lo), hi), dtype=torch.float64).to(dtype)), where
+
+
+NORM_GRID_N = (1, 2, 7, 8, 9, 15, 16, 17, 255, 256, 257, 1023, 1024, 1025, 2047, 2048, 2049, 3072, 4099, 5000, 8195)
+
+
+def test_segment_norm_equals_atens_literal_expression():
+    """`segment_norm` (fp64 sum of the rounded squares -> float32 / n -> the type -> sqrt) == ATen's own
+    `q.abs().pow(2).mean().sqrt()` on every input of the grid — a condition, not a tolerance: the GPU tests compare
+    `plan.rms0` and the device controller's ratio with `segment_norm`."""
+    cases = differ = 0
+    for dtype in DT.values():
+        for n in NORM_GRID_N:
+            for seed in range(8):
+                for scale in (1, 30, 1e-2):
+                    g = torch.Generator().manual_seed(1000 * seed + n)
+                    y0, y1, *ks = [(scale * torch.randn(n, generator=g, dtype=torch.float64)).to(dtype) for _ in range(9)]
+                    q = olp.error_quotient(y0, y1, ks[:7], COEFS[:7], 0.0371, 1e-2, 1e-3)
+                    cases += 1
+                    differ += olp.segment_norm(q) != float(q.abs().pow(2).mean().sqrt())
+    assert cases == 1008 and differ == 0, (cases, differ)
 
 
 _KernelOrderLow = _fallback.KernelOrderLowHostKernels

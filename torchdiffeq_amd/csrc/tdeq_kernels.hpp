@@ -891,10 +891,16 @@ __device__ __forceinline__ float ctl_rnd16(float x, int tkind) {
         if ((u & 0x7fffffffu) > 0x7f800000u) return x;
         return __uint_as_float((u + 0x7fffu + ((u >> 16) & 1u)) & 0xffff0000u);
     }
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm("" : "+v"(x));      // (keeps `(_Float16)(a * b)` from becoming v_fma_mixlo_f16(a, b, +0), which turns a -0 product into +0)
+#endif
     return (float)(_Float16)x;
 }
 __device__ __forceinline__ uint16_t ctl_bits16(float x, int tkind) {     // x already rounded
     if (tkind == 2) return (uint16_t)(__float_as_uint(x) >> 16);
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm("" : "+v"(x));      // (as in ctl_rnd16: `time_sign * 0` keeps its sign)
+#endif
     const _Float16 h = (_Float16)x;
     uint16_t b;
     __builtin_memcpy(&b, &h, 2);

@@ -92,7 +92,16 @@ struct F16 {
         __builtin_memcpy(&b, &v, 2);
         return b;
     }
-    __host__ __device__ static __forceinline__ float rnd(float f) { return (float)(_Float16)f; }
+    // On the device the value goes through an empty asm first: the compiler selects `(_Float16)(a * b)` as
+    // v_fma_mixlo_f16(a, b, +0), and (-0) + (+0) is +0 — a product that is -0 lost its sign, so that y = -0, k = -0 gave
+    // +0 where ATen's (-0) + (-0) is -0 (tests/test_lowp_kernels_gpu.py).  Behind the barrier the product is a v_mul_f32
+    // and the conversion a v_cvt_f16_f32, which keeps the sign.
+    __host__ __device__ static __forceinline__ float rnd(float f) {
+#if defined(__HIP_DEVICE_COMPILE__)
+        asm("" : "+v"(f));
+#endif
+        return (float)(_Float16)f;
+    }
     __device__ static __forceinline__ void unpack2(uint32_t w, float& lo, float& hi) {
         lo = ld(w & 0xffffu);
         hi = ld(w >> 16);
@@ -477,7 +486,10 @@ __global__ __launch_bounds__(kBlock) void error_norm_kernel(const ErrArgs<NT> a)
     // `single` = the segment is ONE element: only ever true in the scalar tail (such a segment has no 8-element group)
     auto elem = [&](const float* kk, float y0, float y1, bool single) -> float {
         const float e = row_sum<S, NT>(kk, cc);
-        const float tol = S::rnd(S::rnd(__builtin_fmaxf(__builtin_fabsf(y0), __builtin_fabsf(y1)) * rtol) + atol);
+        // torch.max hands on a NaN of either operand (misc.py:81); fmaxf alone would return the other one
+        const float a0 = __builtin_fabsf(y0), a1 = __builtin_fabsf(y1);
+        const float amax = __builtin_isunordered(a0, a1) ? a0 + a1 : __builtin_fmaxf(a0, a1);
+        const float tol = S::rnd(S::rnd(amax * rtol) + atol);
         const float r = S::rnd(e / tol);
         acc += norm_term<S>(r, single);
         n_bad += (__builtin_isfinite(y0) && __builtin_isfinite(y1)) ? 0u : 1u;
