@@ -297,6 +297,62 @@ class OracleKernels:
         import torch as _torch
         dst.copy_(_torch.tensor(list(vals), dtype=_torch.float64).to(dst.dtype))
 
+    # -- fixed-grid captured step: the step data kept on the device (include/tdeq_hip.h, tdeq_grid_advance ...) ---------
+    # Restated from the header's text in numpy scalars of the grid type G and the state type T, one rounded operation
+    # at a time; pinned to the reference's own stage times by tests/test_fixed_grid_oracle.py.
+    RK4_38_TIMES = ((0.0, 2), (1 / 3, 0), (2 / 3, 0), (0.0, 1 | 4))      # t0 (NEXT), t0 + dt/3, t0 + 2dt/3, t1 (PREV)
+
+    @staticmethod
+    def perturb_next(tt):
+        """Perturb.NEXT of a numpy scalar: np.nextafter(tt, tt + 1) in its own type."""
+        with np.errstate(all="ignore"):
+            return np.nextafter(tt, tt + type(tt)(1))
+
+    @staticmethod
+    def perturb_prev(tt):
+        """Perturb.PREV of a numpy scalar: np.nextafter(tt, tt - 1) in its own type."""
+        with np.errstate(all="ignore"):
+            return np.nextafter(tt, tt - type(tt)(1))
+
+    def grid_advance_stages(self, grid, counter, perturb, sign, fracs, modes, times_out, dt_out) -> None:
+        assert grid.device.type == "cpu" and counter.dtype == torch.int64 and dt_out.dtype == torch.float64
+        assert 1 <= len(fracs) == len(modes) <= 4 and grid.numel() >= 2
+        G, T = self._np_type(grid.dtype), self._np_type(times_out.dtype)
+        c = int(counter) + 1
+        counter.fill_(c)
+        if c + 1 >= grid.numel():
+            return                                          # past the last interval: nothing else is written
+        g, times = grid.numpy(), times_out.numpy()
+        t0, t1 = G(g[c]), G(g[c + 1])
+        with np.errstate(all="ignore"):
+            dt = t1 - t0
+            for i, (frac, mode) in enumerate(zip(fracs, modes)):
+                tg = t1 if mode & 1 else (t0 if frac == 0.0 else t0 + dt * G(frac))
+                tt = T(tg)
+                if perturb and mode & 2:
+                    tt = self.perturb_next(tt)
+                if perturb and mode & 4:
+                    tt = self.perturb_prev(tt)
+                times[i] = T(sign) * tt
+            dt_out.numpy()[0] = np.float64(dt) * np.float64(sign)
+
+    def grid_advance(self, grid, counter, perturb, sign, times_out, dt_out) -> None:
+        fracs, modes = zip(*self.RK4_38_TIMES)
+        self.grid_advance_stages(grid, counter, perturb, sign, fracs, modes, times_out, dt_out)
+
+    def grid_commit(self, solution, y_cur, y_new, counter) -> None:
+        n = y_cur.numel()
+        row = int(counter) + 1
+        assert 0 <= row < solution.shape[0] and solution.stride(0) >= n
+        solution[row, :n].copy_(y_new)
+        y_cur.copy_(y_new)
+
+    def fixed_stage_dev(self, mode, out, y0, ks, ws, dt_dev) -> None:
+        self.fixed_stage(mode, out, y0, ks, ws, float(dt_dev[0]))
+
+    def rk4_stage_dev(self, stage, out, y0, k1, k2, k3, k4, dt_dev) -> None:
+        self.rk4_stage(stage, out, y0, k1, k2, k3, k4, float(dt_dev[0]))
+
     # -- per-row step control: the row interface of HipKernels, row by row ------------------------------------------------
     # The contract (csrc/tdeq_kernels_rowwise.hpp): every element of row r is what the whole-batch operation gives for
     # that row alone with dt = float(dts[r]).  So each method below loops over the rows and calls the whole-batch oracle
