@@ -67,7 +67,12 @@ def load() -> ctypes.CDLL:
                                       V, V, I],
         "oracle_error_norm_partial_ctrl": [V, V, V, _c_void_pp, _c_double_p, I, D, ctypes.POINTER(Segment), I, I64, I64,
                                            V, V, V, V, V, V, I],
-        "oracle_step_controller": [ctypes.POINTER(Segment), I, V, V, V, V, V, I],
+        "oracle_step_controller": [ctypes.POINTER(Segment), I, V, V, V, V, V, I, I],
+        "oracle_error_norm_vec": [V, V, V, _c_void_pp, _c_double_p, I, D, V, D, V, D, ctypes.POINTER(Segment), I, I64,
+                                  V, V, I],
+        "oracle_error_norm_vec_ctrl": [V, V, V, _c_void_pp, _c_double_p, I, D, V, D, V, D, ctypes.POINTER(Segment), I, I64,
+                                       V, V, V, V, V, V, V, I, I],
+        "oracle_init_norms_vec": [I, V, V, V, V, D, V, D, ctypes.POINTER(Segment), I, I64, V, V, I],
         "oracle_stage_combine_sel": [V, V, V, V, V, D, V, I64, I],
         "oracle_pack_segments": [V, _c_void_pp, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64),
                                  _c_double_p, I, I64, I64, I],
@@ -108,6 +113,10 @@ class OraclePlan:
         self.bad_ptr = self.out_ptr + 16 * self.n_seg
         self.ctrl_ptr = self.out_ptr + 24 * self.n_seg
         self.ctrl_dev = torch.zeros(2, dtype=torch.float64)
+        # {accept, sign * T(dt'), t0', dt'}: the product's four device-resident controller words (NormPlan.ctrl_dev), kept
+        # apart from the two-word `ctrl_dev` above, whose shape existing callers rely on.  error_norm_vec_ctrl reads its
+        # trial step from here under `state_in_dev` and rewrites all four; `ctrl_dev` receives the first two.
+        self.ctrl_state = torch.zeros(4, dtype=torch.float64)
 
 
 class OracleKernels:
@@ -203,13 +212,58 @@ class OracleKernels:
                                                     plan.ctrl_dev.data_ptr(), next_times.data_ptr(), _code(y0.dtype)),
             "oracle_error_norm_partial_ctrl")
 
-    def step_controller(self, plan, sumsq, ctrl, next_times, dtype):
-        """The controller alone on given per-segment sums -> (out_ctrl[4], ctrl_dev[2]) as lists."""
+    def step_controller(self, plan, sumsq, ctrl, next_times, dtype, ratio_dtype=None):
+        """The controller alone on given per-segment sums -> (out_ctrl[4], ctrl_dev[2]) as lists.  `ratio_dtype`: the type
+        the error ratio is rounded to — `dtype` unless given (per-element tolerances: torch.float64 for either state type)."""
         ss = (ctypes.c_double * plan.n_seg)(*sumsq)
         _ok(self.lib.oracle_step_controller(plan.segs, plan.n_seg, ctypes.addressof(ss), ctypes.addressof(ctrl),
                                             plan.ctrl_ptr, plan.ctrl_dev.data_ptr(), next_times.data_ptr(),
-                                            _code(dtype)), "oracle_step_controller")
+                                            _code(dtype), _code(dtype if ratio_dtype is None else ratio_dtype)),
+            "oracle_step_controller")
         return plan.out.tolist()[3 * plan.n_seg:], plan.ctrl_dev.tolist()
+
+    # -- per-element tolerances (twins of HipKernels.error_norm_vec / error_norm_vec_ctrl / init_norms_vec) ---------------
+    vec_partial = True          # `partial=` continues the error row of stage_combine_err
+    vec_ctrl_in_graph = True    # `state_in_dev` is honoured (the trial step is read from plan.ctrl_state)
+
+    @staticmethod
+    def _tol(tol):
+        """(vector pointer or None, scalar) of one tolerance: an fp64 vector over the flat padded state, or a host float."""
+        if isinstance(tol, torch.Tensor):
+            assert tol.device.type == "cpu" and tol.dtype == torch.float64 and tol.is_contiguous()
+            return tol.data_ptr(), 0.0
+        return None, float(tol)
+
+    @staticmethod
+    def _rest(ks, coefs):
+        n = len(ks)
+        for k in ks:
+            assert k.device.type == "cpu" and k.is_contiguous()
+        return (ctypes.c_void_p * max(n, 1))(*[k.data_ptr() for k in ks]), (ctypes.c_double * max(n, 1))(*coefs), n
+
+    def error_norm_vec(self, plan, y0, y1, ks, coefs, dt, rtol, atol, partial=None):
+        ptrs, cf, n = self._rest(ks, coefs)
+        (rv, rs), (av, as_) = self._tol(rtol), self._tol(atol)
+        _ok(self.lib.oracle_error_norm_vec(None if partial is None else partial.data_ptr(), y0.data_ptr(), y1.data_ptr(),
+                                           ptrs, cf, n, dt, rv, rs, av, as_, plan.segs, plan.n_seg, plan.chunk,
+                                           plan.out_ptr, plan.bad_ptr, _code(y0.dtype)), "oracle_error_norm_vec")
+
+    def error_norm_vec_ctrl(self, plan, y0, y1, ks, coefs, dt, rtol, atol, ctrl, next_times, partial=None,
+                            state_in_dev=False):
+        ptrs, cf, n = self._rest(ks, coefs)
+        (rv, rs), (av, as_) = self._tol(rtol), self._tol(atol)
+        _ok(self.lib.oracle_error_norm_vec_ctrl(None if partial is None else partial.data_ptr(), y0.data_ptr(),
+                                                y1.data_ptr(), ptrs, cf, n, dt, rv, rs, av, as_, plan.segs, plan.n_seg,
+                                                plan.chunk, plan.out_ptr, plan.bad_ptr, ctypes.addressof(ctrl),
+                                                plan.ctrl_ptr, plan.ctrl_dev.data_ptr(), plan.ctrl_state.data_ptr(),
+                                                next_times.data_ptr(), 1 if state_in_dev else 0, _code(y0.dtype)),
+            "oracle_error_norm_vec_ctrl")
+
+    def init_norms_vec(self, plan, mode, a, b, yscale, rtol, atol):
+        (rv, rs), (av, as_) = self._tol(rtol), self._tol(atol)
+        _ok(self.lib.oracle_init_norms_vec(mode, a.data_ptr(), b.data_ptr(), yscale.data_ptr(), rv, rs, av, as_, plan.segs,
+                                           plan.n_seg, plan.chunk, plan.out_ptr, plan.bad_ptr, _code(yscale.dtype)),
+            "oracle_init_norms_vec")
 
     def read_ctrl(self, plan):
         v = plan.out.tolist()

@@ -12,6 +12,7 @@
  * `beta_i * dt` on a tableau already cast to T (rk_common.py:79, 201-205).  Reductions accumulate in
  * fp64 over fixed-size chunks (deterministic for any thread count); the reference accumulates in T
  * with ATen's blocked order, which differs from the exact value by a few ulp_T — see DESIGN.md.
+ * (The per-element-tolerance twins, oracle_*_vec, accumulate a segment in long double in index order instead.)
  *
  * Pinning: tests/test_oracle_golden.py checks every function here against vectors produced by the
  * imported reference itself (tests/golden/make_golden.py -> tests/golden/ npz files).
@@ -581,14 +582,19 @@ static double o_clamp(double x, double lo, double hi) {
     return m < hi ? m : hi;
 }
 
+/* is_f32: the type T of the step size and the stage times.  ratio_is_f32: the type the error ratio is formed in — T for
+ * scalar tolerances (every existing caller passes the same value twice); fp64 = 0 for per-element tolerances, where the
+ * reference's quotient and norm promote to the tolerance tensors' type (misc.py:80-82).
+ * state4 (may be null): the device-resident words {accept, sign * T(dt'), t0', dt'} of a captured step. */
 static void controller(const oracle_step_ctrl* c, const oracle_segment* segs, int n_seg, const double* sumsq,
-                       int is_f32, double* out_ctrl, double* ctrl_dev, void* next_times) {
+                       int is_f32, int ratio_is_f32, double* out_ctrl, double* ctrl_dev, void* next_times,
+                       double* state4) {
     double val = 0.0;
     for (int s = 0; s < c->n_norm_seg && s < n_seg; ++s) {
         if (segs[s].numel == 0) continue;
         val = o_nan_max(val, sqrt(sumsq[s] / (double)segs[s].numel));
     }
-    const double ratio = is_f32 ? (double)(float)val : val;
+    const double ratio = ratio_is_f32 ? (double)(float)val : val;
     int accept = ratio <= 1.0;
     if (c->dt > c->max_step) accept = 0;
     if (c->dt <= c->min_step) accept = 1;
@@ -627,6 +633,12 @@ static void controller(const oracle_step_ctrl* c, const oracle_segment* segs, in
         ctrl_dev[1] = dtn * c->time_sign;
     }
     ctrl_dev[0] = accept ? 1.0 : 0.0;
+    if (state4) {
+        state4[0] = ctrl_dev[0];
+        state4[1] = ctrl_dev[1];
+        state4[2] = t0n;
+        state4[3] = dtn;
+    }
     out_ctrl[0] = accept ? 1.0 : 0.0;
     out_ctrl[1] = dt_next;
     out_ctrl[2] = ratio;
@@ -643,15 +655,17 @@ int oracle_error_norm_partial_ctrl(const void* err_partial, const void* y0, cons
     const int e = oracle_error_norm_partial(err_partial, y0, y1, k, coef, n_terms, dt, segs, n_seg, chunk, n_chunks,
                                             out_sumsq, out_nonfinite, dtype);
     if (e) return e;
-    controller(ctrl, segs, n_seg, out_sumsq, dtype == ORACLE_F32, out_ctrl, ctrl_dev, next_times);
+    controller(ctrl, segs, n_seg, out_sumsq, dtype == ORACLE_F32, dtype == ORACLE_F32, out_ctrl, ctrl_dev, next_times, NULL);
     return 0;
 }
 
-/* The controller alone on given per-segment sums (kernel-parity tests feed it the device's sums). */
+/* The controller alone on given per-segment sums (kernel-parity tests feed it the device's sums).  ratio_dtype: the type
+ * the error ratio is rounded to (= dtype for scalar tolerances, ORACLE_F64 for per-element ones). */
 int oracle_step_controller(const oracle_segment* segs, int n_seg, const double* sumsq, const oracle_step_ctrl* ctrl,
-                           double* out_ctrl, double* ctrl_dev, void* next_times, int dtype) {
+                           double* out_ctrl, double* ctrl_dev, void* next_times, int dtype, int ratio_dtype) {
     if (!segs || !sumsq || !ctrl || !out_ctrl || !ctrl_dev || !next_times) return -1;
-    controller(ctrl, segs, n_seg, sumsq, dtype == ORACLE_F32, out_ctrl, ctrl_dev, next_times);
+    if ((dtype != ORACLE_F32 && dtype != ORACLE_F64) || (ratio_dtype != ORACLE_F32 && ratio_dtype != ORACLE_F64)) return -1;
+    controller(ctrl, segs, n_seg, sumsq, dtype == ORACLE_F32, ratio_dtype == ORACLE_F32, out_ctrl, ctrl_dev, next_times, NULL);
     return 0;
 }
 
@@ -664,6 +678,145 @@ int oracle_stage_combine_sel(void* out, const void* y_acc, const void* f_acc, co
     const void* f = accept ? f_acc : f_rej;
     const void* ks[1] = {f};
     return oracle_stage_combine(out, y, ks, &coef, 1, ctrl_dev[1], n, dtype);
+}
+
+/* ---------------------------------------------------------------------------------------------------
+ * Per-element tolerances (CPU twins of tdeq_error_norm_vec / tdeq_error_norm_vec_ctrl / tdeq_init_norms_vec):
+ * `rtol` / `atol` tensors of the time type W = fp64 that broadcast against the state, misc.py:80-82 and :50-56, 68.
+ * ATen's type promotion decides every operation (a dimensioned fp64 tensor promotes, a 0-dim one does not):
+ *   err            left to right in T: [partial +] fl_T(fl_T(coef_j) * T(dt)) * k_j, each coefficient formed once
+ *   m              max(|y0|, |y1|) in T                       (|y| for the initial-step norms)
+ *   rtol * m       fp64 for a vector rtol; T (rtol cast to T), then widened, for a 0-dim rtol
+ *   atol + ..., err / tol, the square and the norm            fp64
+ * The vectors are indexed like the state: by the PADDED flat index chunk_start * chunk + t.
+ * A segment's sum is accumulated in long double in index order — no chunks, no lanes: this is the high-precision
+ * reference the kernels' blocked fp64 sums are compared with.
+ * ------------------------------------------------------------------------------------------------- */
+#define DEF_ERROR_VEC(NAME, T, ABS, MAX)                                                              \
+    static void NAME(const T* partial, const T* y0, const T* y1, const T* const* k, const double* coef,\
+                     int nt, double dt, const double* rtol_v, double rtol_s, const double* atol_v,    \
+                     double atol_s, const oracle_segment* segs, int n_seg, int64_t chunk,             \
+                     double* out_sumsq, double* out_bad) {                                            \
+        T c[ORACLE_MAX_TERMS];                                                                        \
+        const T dtT = (T)dt;                                                                          \
+        for (int j = 0; j < nt; ++j) c[j] = (T)coef[j] * dtT;                                         \
+        const T rtolT = (T)rtol_s;                                                                    \
+        for (int s = 0; s < n_seg; ++s) {                                                             \
+            const int64_t base = segs[s].chunk_start * chunk;                                         \
+            long double acc = 0.0L;                                                                   \
+            double bad = 0.0;                                                                         \
+            for (int64_t t = 0; t < segs[s].numel; ++t) {                                             \
+                const int64_t i = base + t;                                                           \
+                T e = partial ? partial[i] : k[0][i] * c[0];                                          \
+                for (int j = partial ? 0 : 1; j < nt; ++j) e = e + k[j][i] * c[j];                    \
+                const T m = MAX(ABS(y0[i]), ABS(y1[i]));                                              \
+                const double prod = rtol_v ? rtol_v[i] * (double)m : (double)(rtolT * m);             \
+                const double tol = (atol_v ? atol_v[i] : atol_s) + prod;                              \
+                const double r = (double)e / tol;                                                     \
+                acc += (long double)(r * r);                                                          \
+                if (!isfinite((double)y0[i]) || !isfinite((double)y1[i])) bad += 1.0;                 \
+            }                                                                                         \
+            out_sumsq[s] = (double)acc;                                                               \
+            out_bad[s] = bad;                                                                         \
+        }                                                                                             \
+    }
+DEF_ERROR_VEC(error_vec_f32, float, fabsf, fmaxf)
+DEF_ERROR_VEC(error_vec_f64, double, fabs, fmax)
+
+int oracle_error_norm_vec(const void* err_partial, const void* y0, const void* y1, const void* const* k, const double* coef,
+                          int n_terms, double dt, const double* rtol_vec, double rtol_scalar, const double* atol_vec,
+                          double atol_scalar, const oracle_segment* segs, int n_seg, int64_t chunk, double* out_sumsq,
+                          double* out_nonfinite, int dtype) {
+    if (!y0 || !y1 || !segs || !out_sumsq || !out_nonfinite || n_seg < 1) return -1;
+    if (!rtol_vec && !atol_vec) return -1;      /* two 0-dim tolerances: oracle_error_norm (a different promotion) */
+    if (n_terms < (err_partial ? 0 : 1) || n_terms > ORACLE_MAX_TERMS || (n_terms > 0 && (!k || !coef))) return -1;
+    for (int j = 0; j < n_terms; ++j) if (!k[j]) return -1;
+    if (dtype == ORACLE_F32)
+        error_vec_f32((const float*)err_partial, (const float*)y0, (const float*)y1, (const float* const*)k, coef, n_terms,
+                      dt, rtol_vec, rtol_scalar, atol_vec, atol_scalar, segs, n_seg, chunk, out_sumsq, out_nonfinite);
+    else if (dtype == ORACLE_F64)
+        error_vec_f64((const double*)err_partial, (const double*)y0, (const double*)y1, (const double* const*)k, coef,
+                      n_terms, dt, rtol_vec, rtol_scalar, atol_vec, atol_scalar, segs, n_seg, chunk, out_sumsq,
+                      out_nonfinite);
+    else return -1;
+    return 0;
+}
+
+/* The same launch with the step controller behind it: the ratio stays fp64 (the promoted type) for either T, the step size
+ * and the stage times are rounded to T.  state_in_dev (captured steps): `dt` and ctrl->t0 / ctrl->dt are ignored — the
+ * norm's step size is T(state4[1]) (= sign * T(dt), as the previous controller left it) and the trial step is
+ * (t0, dt) = state4[2..3].  state4 = {accept, sign * T(dt'), t0', dt'} is rewritten; ctrl_dev receives its first two words. */
+int oracle_error_norm_vec_ctrl(const void* err_partial, const void* y0, const void* y1, const void* const* k,
+                               const double* coef, int n_terms, double dt, const double* rtol_vec, double rtol_scalar,
+                               const double* atol_vec, double atol_scalar, const oracle_segment* segs, int n_seg,
+                               int64_t chunk, double* out_sumsq, double* out_nonfinite, const oracle_step_ctrl* ctrl,
+                               double* out_ctrl, double* ctrl_dev, double* state4, void* next_times, int state_in_dev,
+                               int dtype) {
+    if (!ctrl || !out_ctrl || !ctrl_dev || !state4 || !next_times) return -1;
+    if (ctrl->n_times < 1 || ctrl->n_times > ORACLE_MAX_STAGE_TIMES || ctrl->n_norm_seg < 0 || ctrl->n_norm_seg > n_seg)
+        return -1;
+    oracle_step_ctrl c = *ctrl;
+    if (state_in_dev) {
+        dt = state4[1];
+        c.t0 = state4[2];
+        c.dt = state4[3];
+    }
+    const int e = oracle_error_norm_vec(err_partial, y0, y1, k, coef, n_terms, dt, rtol_vec, rtol_scalar, atol_vec,
+                                        atol_scalar, segs, n_seg, chunk, out_sumsq, out_nonfinite, dtype);
+    if (e) return e;
+    controller(&c, segs, n_seg, out_sumsq, dtype == ORACLE_F32, 0, out_ctrl, ctrl_dev, next_times, state4);
+    return 0;
+}
+
+/* scale = atol + |y| * rtol                                        misc.py:50 (promoted as above)
+ *   mode 0: sum (a/scale)^2 and sum (b/scale)^2                   misc.py:55-56
+ *   mode 1: sum ((a-b)/scale)^2, a - b formed in T                misc.py:68 */
+#define DEF_INIT_VEC(NAME, T, ABS)                                                                    \
+    static void NAME(int mode, const T* a, const T* b, const T* y, const double* rtol_v,              \
+                     double rtol_s, const double* atol_v, double atol_s, const oracle_segment* segs,  \
+                     int n_seg, int64_t chunk, double* out_sumsq, double* out_bad) {                  \
+        const T rtolT = (T)rtol_s;                                                                    \
+        for (int s = 0; s < n_seg; ++s) {                                                             \
+            const int64_t base = segs[s].chunk_start * chunk;                                         \
+            long double s0 = 0.0L, s1 = 0.0L;                                                         \
+            double bad = 0.0;                                                                         \
+            for (int64_t t = 0; t < segs[s].numel; ++t) {                                             \
+                const int64_t i = base + t;                                                           \
+                const T m = ABS(y[i]);                                                                \
+                const double prod = rtol_v ? (double)m * rtol_v[i] : (double)(m * rtolT);             \
+                const double scale = (atol_v ? atol_v[i] : atol_s) + prod;                            \
+                if (mode == 0) {                                                                      \
+                    const double r0 = (double)a[i] / scale, r1 = (double)b[i] / scale;                \
+                    s0 += (long double)(r0 * r0);                                                     \
+                    s1 += (long double)(r1 * r1);                                                     \
+                } else {                                                                              \
+                    const T d = a[i] - b[i];                                                          \
+                    const double r0 = (double)d / scale;                                              \
+                    s0 += (long double)(r0 * r0);                                                     \
+                }                                                                                     \
+                if (!isfinite((double)y[i])) bad += 1.0;                                              \
+            }                                                                                         \
+            out_sumsq[s] = (double)s0;                                                                \
+            if (mode == 0) out_sumsq[n_seg + s] = (double)s1;                                         \
+            out_bad[s] = bad;                                                                         \
+        }                                                                                             \
+    }
+DEF_INIT_VEC(init_vec_f32, float, fabsf)
+DEF_INIT_VEC(init_vec_f64, double, fabs)
+
+int oracle_init_norms_vec(int mode, const void* a, const void* b, const void* yscale, const double* rtol_vec,
+                          double rtol_scalar, const double* atol_vec, double atol_scalar, const oracle_segment* segs,
+                          int n_seg, int64_t chunk, double* out_sumsq, double* out_nonfinite, int dtype) {
+    if ((mode != 0 && mode != 1) || !a || !b || !yscale || !segs || !out_sumsq || !out_nonfinite || n_seg < 1) return -1;
+    if (!rtol_vec && !atol_vec) return -1;
+    if (dtype == ORACLE_F32)
+        init_vec_f32(mode, (const float*)a, (const float*)b, (const float*)yscale, rtol_vec, rtol_scalar, atol_vec,
+                     atol_scalar, segs, n_seg, chunk, out_sumsq, out_nonfinite);
+    else if (dtype == ORACLE_F64)
+        init_vec_f64(mode, (const double*)a, (const double*)b, (const double*)yscale, rtol_vec, rtol_scalar, atol_vec,
+                     atol_scalar, segs, n_seg, chunk, out_sumsq, out_nonfinite);
+    else return -1;
+    return 0;
 }
 
 /* ---------------------------------------------------------------------------------------------------

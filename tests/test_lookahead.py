@@ -156,19 +156,7 @@ def test_lookahead_tuple_state_and_adjoint(dev, monkeypatch):
 # ---------------------------------------------------------------------------------------------------------------
 # kernel parity on the GPU
 # ---------------------------------------------------------------------------------------------------------------
-def _ctrl(t0, dt, order, tab, sign=1.0, min_step=0.0, max_step=math.inf, n_norm_seg=1, np_dtype=np.float64):
-    c = _native.StepCtrl()
-    c.t0, c.dt = t0, dt
-    c.safety, c.ifactor, c.dfactor = 0.9, 10.0, 0.2
-    c.exponent = 1.0 / order
-    c.min_step, c.max_step, c.time_sign = min_step, max_step, sign
-    mask = 0
-    for i, a in enumerate(tab.alpha):
-        c.alpha[i] = float(np_dtype(a))
-        if a == 1.0:
-            mask |= 1 << i
-    c.alpha_is_one, c.n_times, c.n_norm_seg = mask, len(tab.alpha), n_norm_seg
-    return c
+from _vec_tol_cases import step_ctrl as _ctrl  # noqa: E402  (shared with the per-element-tolerance kernel tests)
 
 
 @pytest.mark.gpu
