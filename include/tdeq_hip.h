@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define TDEQ_ABI_VERSION 32
+#define TDEQ_ABI_VERSION 33
 #define TDEQ_F32 0
 #define TDEQ_F64 1
 /* interleaved (re, im) complex states — accepted by the NORM entry points only (tdeq_error_norm, tdeq_error_norm_partial[_ctrl],
@@ -842,6 +842,61 @@ int tdeq_row_dense_extremum(void* values, double* times, int which, const void* 
                             const double* seg_tb, double time_sign, const int32_t* seg, const void* x, const double* tq,
                             const int32_t* seg2, const void* x2, const double* tq2, int64_t n_idx, int64_t row_len, int dtype,
                             void* stream);
+
+/*
+ * ---- Level crossings of the per-row dense record over a time window (ABI 33; `RowDenseOutput.crossings` / `.time_above`) ----
+ * tdeq_row_dense_level     for i < n_idx (a query of row i % n_rows; n_idx is a multiple of n_rows) and every element of the
+ *                          row: how often the piecewise quartic crosses `level[row, el]` (`level` [n_rows, row_len] of the state
+ *                          type T) on the window between the queries tq[i] and tq2[i], the times of the first and the last
+ *                          crossing, and for how long the element is ABOVE the level.  (seg, x, tq), (seg2, x2, tq2) as for
+ *                          tdeq_row_dense_extremum; their order does not matter.  `count` int32, `first`, `last`, `time_above`
+ *                          double, all [n_idx, row_len]; `first` and `last` in TRUE time, `time_above` a duration >= 0.
+ *                          THE ARITHMETIC IS THE CONTRACT.  Everything is fp64, one rounded operation per written operation,
+ *                          nothing contracted; only + - * /, comparisons and fabs.  Per element:
+ *                          Ends, Walk, xlo, xhi, Polynomials, bisect, Isolation: those of tdeq_row_dense_extremum, exactly.
+ *                                   The candidates of a segment are the extremum's — xlo, the roots of g1 that bound pieces,
+ *                                   the roots of g, xhi — in increasing x; between two neighbours the quartic is monotone up
+ *                                   to what the isolation leaves.  (A repeated candidate changes nothing.)
+ *                          Level function.  lev = double(level[row, el]);  phi(x) = (e + x*(d + x*(c + x*(b + x*a)))) - lev
+ *                                   (the extremum's p, then one subtraction);  above(x) = phi(x) > 0, strict: a value equal to
+ *                                   the level is not above.
+ *                          State machine.  Candidates are visited in increasing x, segments in order.  The first candidate of
+ *                                   the window (xlo of segA) sets state = above; if it is above, t_up = tqa.  Every later
+ *                                   candidate v — the first candidate of each later segment, which is the RIGHT limit at a
+ *                                   breakpoint, included — is compared with state; a difference is a crossing, after which
+ *                                   state = above(v).
+ *                          Location of a crossing.  Between two candidates u < v of one segment: z = u if phi(u) == 0, else
+ *                                   v if phi(v) == 0, else bisect(phi, u, v), which always finds a root there.  At the first
+ *                                   candidate of a later segment: that candidate, whose time is the breakpoint — a state
+ *                                   impulse at p that lifts the element over the level is a crossing at p.
+ *                          Time tz of a crossing z of segment s: the extremum's rule for a candidate — tqa if s == segA and
+ *                                   z == xlo;  else tqb if s == segB and z == xhi;  else ta_s if z == 0;  else tb_s if z == 1
+ *                                   (the stored bits);  else ta_s + z * h_s.
+ *                          Accumulation per crossing.  count += 1;  first is set by the first crossing, last by every one;  an
+ *                                   up-crossing (state becomes above) sets t_up = tz;  a down-crossing does
+ *                                   total = total + (tz - t_up).  After the last segment, if state: total = total + (tqb -
+ *                                   t_up).  Durations are added left to right in solver time; that order is the contract.
+ *                          Outputs.  first = time_sign * tz of the first crossing, last = time_sign * tz of the last one, NaN
+ *                                   when count == 0;  time_above = total (solver-time differences: the same number for an
+ *                                   ascending and a descending solve).  A NaN phi at any candidate (a NaN level included), or
+ *                                   an out-of-range end (x[i] or x2[i] NaN): count = -1, first = last = time_above = NaN.
+ *                          The answer is exact ON THE RECORD, and the record is discontinuous at rounding level at every
+ *                          breakpoint: p_s(1) and p_{s+1}(0) may differ in their last bits, and a level inside that gap is
+ *                          crossed once more at the breakpoint (and back on the way).  A value that touches the level without
+ *                          passing it (phi == 0 at a candidate, not above on both sides) is no crossing; one that comes down
+ *                          to the level exactly and rises again is two crossings at the same time.
+ *                          One lane per (query, 16-byte element) walks its segments serially; no workspace, nothing cached.
+ *                          0 <= seg[i], seg2[i] < n_seg (the walk is clamped to the record).  16-byte elements when row_len
+ *                          is a multiple of 16 / sizeof(T), `coeffs`, `level`, `first`, `last` and `time_above` are 16-byte
+ *                          aligned and `count` is aligned to its word of 16 / sizeof(T) int32; scalar elements otherwise, with
+ *                          the same bits.  A NULL pointer, n_rows <= 0 with n_idx > 0, n_idx no multiple of n_rows, a
+ *                          negative size, n_seg > INT32_MAX, a time_sign other than +1 / -1 or a dtype other than TDEQ_F32 /
+ *                          TDEQ_F64: TDEQ_EINVAL before any launch.  n_idx == 0 or row_len == 0: no-op.
+ */
+int tdeq_row_dense_level(int32_t* count, double* first, double* last, double* time_above, const void* level, int64_t n_rows,
+                         const void* coeffs, int64_t n_seg, const double* seg_ta, const double* seg_tb, double time_sign,
+                         const int32_t* seg, const void* x, const double* tq, const int32_t* seg2, const void* x2,
+                         const double* tq2, int64_t n_idx, int64_t row_len, int dtype, void* stream);
 
 /*
  * ---- Per-row step options (ABI 29; `min_step`, `max_step`, `step_t`, `jump_t` of the rowwise family) ----

@@ -14,8 +14,8 @@
 //   row_dense_search   one lane per query: the segment of the row that holds the query time (bisection over the row's
 //                      segment ends) and the fraction x of that step, in the arithmetic of row_dense_commit
 // followed by row_event_eval_mapped on (coeffs, seg, x).  No LDS; plain vector loads and stores; 64-bit element offsets.
-// The derivative, antiderivative and integral of the record (row_dense_prefix, row_dense_calc) and its extrema over a time
-// window (row_dense_extremum) are at the end of the file.
+// The derivative, antiderivative and integral of the record (row_dense_prefix, row_dense_calc), its extrema over a time
+// window (row_dense_extremum) and its crossings of a level (row_dense_level) are at the end of the file.
 #pragma once
 
 #include "tdeq_kernels_rowwise.hpp"
@@ -386,6 +386,33 @@ __device__ __forceinline__ bool quartic_bisect(const F& phi, double lo, double h
     return true;
 }
 
+// the candidates of one element on one segment (Isolation of the header), visited in increasing x; repeats are not skipped
+template <typename V>
+__device__ __forceinline__ void quartic_candidates(const QuarticSlope& g, const QuarticCurvature& g1, double b, double aa,
+                                                   double a4, double xlo, double xhi, V&& visit) {
+    // the roots of g1 bound the pieces of g; a piece without a root passes its lower bound on
+    double xm = xlo;
+    if (aa != 0.0) {
+        const double x1 = (-b) / a4;
+        if (xlo < x1 && x1 < xhi) xm = x1;
+    }
+    double r0 = xlo, r1, z;
+    if (xm > xlo) quartic_bisect(g1, xlo, xm, r0);
+    r1 = r0;
+    quartic_bisect(g1, xm, xhi, r1);
+    visit(xlo);
+    if (r0 > xlo) {
+        if (quartic_bisect(g, xlo, r0, z)) visit(z);
+        visit(r0);
+    }
+    if (r1 > r0) {
+        if (quartic_bisect(g, r0, r1, z)) visit(z);
+        visit(r1);
+    }
+    if (quartic_bisect(g, r1, xhi, z)) visit(z);
+    visit(xhi);
+}
+
 template <typename T, bool VEC, bool MAX>
 __global__ __launch_bounds__(kBlock) void row_dense_extremum_kernel(const RowDenseExtremumArgs<T> a) {
     using E = typename std::conditional<VEC, typename VecOf<T>::type, T>::type;
@@ -446,27 +473,7 @@ __global__ __launch_bounds__(kBlock) void row_dense_extremum_kernel(const RowDen
                         whn = (atA && x == xlo) ? tqa : (atB && x == xhi) ? tqb : x == 0.0 ? ta : x == 1.0 ? tb : ta + x * h;
                     }
                 };
-                // the roots of g1 bound the pieces of g; a piece without a root passes its lower bound on
-                double xm = xlo;
-                if (aa != 0.0) {
-                    const double x1 = (-b) / a4;
-                    if (xlo < x1 && x1 < xhi) xm = x1;
-                }
-                double r0 = xlo, r1, z;
-                if (xm > xlo) quartic_bisect(g1, xlo, xm, r0);
-                r1 = r0;
-                quartic_bisect(g1, xm, xhi, r1);
-                consider(xlo);
-                if (r0 > xlo) {
-                    if (quartic_bisect(g, xlo, r0, z)) consider(z);
-                    consider(r0);
-                }
-                if (r1 > r0) {
-                    if (quartic_bisect(g, r0, r1, z)) consider(z);
-                    consider(r1);
-                }
-                if (quartic_bisect(g, r1, xhi, z)) consider(z);
-                consider(xhi);
+                quartic_candidates(g, g1, b, aa, a4, xlo, xhi, consider);
                 best[c] = bst;
                 when[c] = whn;
             }
@@ -482,6 +489,163 @@ __global__ __launch_bounds__(kBlock) void row_dense_extremum_kernel(const RowDen
         __builtin_memcpy(&w, o, sizeof(E));
         reinterpret_cast<E*>(a.values)[i] = w;
         store_doubles<LV>(a.times + i * LV, when);
+    }
+}
+
+// ---- level crossings of the record over a time window (ABI 33): RowDenseOutput.crossings / .time_above ------------------
+//   row_dense_level   the walk of row_dense_extremum with a state machine in place of the selection: between two
+//                     neighbouring candidates the quartic is monotone, so phi = p - level has at most one root there, found
+//                     by one more bisection.  Per element the lane keeps above / t_up / total / count / first / last.  The
+//                     arithmetic is stated in include/tdeq_hip.h; the host model is rowwise.py quartic_levels.
+// A segment without a crossing costs the isolation of the extremum walk and at most 7 evaluations of phi.  No LDS, no
+// atomics, no workspace.
+
+template <typename T>
+struct RowDenseLevelArgs {
+    int32_t* count;                   // [n_idx, L]
+    double* first;                    // [n_idx, L] true time
+    double* last;                     // [n_idx, L] true time
+    double* total;                    // [n_idx, L] duration
+    const T* level;                   // [n_rows, L]
+    const T* q;                       // [5, n_seg, L]
+    const double* seg_ta;             // [n_seg]
+    const double* seg_tb;             // [n_seg]
+    double sign;
+    const int32_t* seg;               // [n_idx] one end of each window (row_dense_search)
+    const T* x;                       // [n_idx] NaN marks an out-of-range end
+    const double* tq;                 // [n_idx] solver time
+    const int32_t* seg2;              // the other end
+    const T* x2;
+    const double* tq2;
+    int64_t n_rows;                   // query i belongs to row i % n_rows
+    int64_t n_seg;
+    int64_t row_len;                  // E units
+    int64_t ne;                       // n_idx * row_len
+    int64_t q_plane;                  // n_seg * L elements of T
+};
+
+// phi of the header: the extremum's p, then one subtraction
+struct QuarticLevel {
+    double e, d, c, b, a, lev;
+    __device__ __forceinline__ double operator()(double x) const { return (e + x * (d + x * (c + x * (b + x * a)))) - lev; }
+};
+
+template <int LV>
+__device__ __forceinline__ void store_ints(int32_t* p, const int32_t (&v)[LV]) {
+    if constexpr (LV == 1) {
+        p[0] = v[0];
+    } else {
+        typedef int32_t W __attribute__((ext_vector_type(LV)));
+        W w;
+#pragma unroll
+        for (int c = 0; c < LV; ++c) w[c] = v[c];
+        *reinterpret_cast<W*>(p) = w;
+    }
+}
+
+template <typename T, bool VEC>
+__global__ __launch_bounds__(kBlock) void row_dense_level_kernel(const RowDenseLevelArgs<T> a) {
+    using E = typename std::conditional<VEC, typename VecOf<T>::type, T>::type;
+    constexpr int LV = VEC ? VecOf<T>::L : 1;
+    const int64_t stride = (int64_t)gridDim.x * kBlock;
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < a.ne; i += stride) {
+        const int64_t r = i / a.row_len;
+        const int64_t el = i - r * a.row_len;
+        int64_t sA = a.seg[r], sB = a.seg2[r];
+        double tqa = a.tq[r], tqb = a.tq2[r];
+        const T xa = a.x[r], xb = a.x2[r];
+        if (tqb < tqa) {
+            const int64_t s = sA;
+            sA = sB;
+            sB = s;
+            const double t = tqa;
+            tqa = tqb;
+            tqb = t;
+        }
+        if (sA < 0) sA = 0;                                           // (nothing is read outside the record)
+        if (sB > a.n_seg - 1) sB = a.n_seg - 1;
+        const bool bad = xa != xa || xb != xb || sA > sB;             // (sA > sB: only from ends the search did not write)
+        T lev[LV];
+        load_lanes<T, E, LV>(a.level, (r % a.n_rows) * a.row_len + el, lev);
+        double t_up[LV], total[LV], tfirst[LV], tlast[LV];
+        int32_t count[LV];
+        bool above[LV], nanv[LV];
+#pragma unroll
+        for (int c = 0; c < LV; ++c) {
+            t_up[c] = total[c] = tfirst[c] = tlast[c] = 0.0;
+            count[c] = 0;
+            above[c] = false;
+            nanv[c] = bad;
+        }
+        for (int64_t s = bad ? sB + 1 : sA; s <= sB; ++s) {           // serial: segments in order
+            const int64_t at = s * a.row_len + el;
+            T qe[LV], qd[LV], qc[LV], qb[LV], qa[LV];
+            load_lanes<T, E, LV>(a.q, at, qe);
+            load_lanes<T, E, LV>(a.q + a.q_plane, at, qd);
+            load_lanes<T, E, LV>(a.q + 2 * a.q_plane, at, qc);
+            load_lanes<T, E, LV>(a.q + 3 * a.q_plane, at, qb);
+            load_lanes<T, E, LV>(a.q + 4 * a.q_plane, at, qa);
+            const double ta = a.seg_ta[s], tb = a.seg_tb[s];
+            const double h = tb - ta;
+            const bool atA = s == sA, atB = s == sB;
+            const double xlo = atA ? (tqa - ta) / h : 0.0;
+            const double xhi = atB ? (tqb - ta) / h : 1.0;
+#pragma unroll
+            for (int c = 0; c < LV; ++c) {
+                const double b = (double)qb[c], aa = (double)qa[c];
+                const QuarticLevel phi{(double)qe[c], (double)qd[c], (double)qc[c], b, aa, (double)lev[c]};
+                const double c2 = phi.c + phi.c, a4 = 4.0 * aa;
+                const QuarticSlope g{phi.d, c2, 3.0 * b, a4};
+                const QuarticCurvature g1{c2, 6.0 * b, 12.0 * aa};
+                bool st = above[c], entry = true;                     // entry: the segment's first candidate comes next
+                double up = t_up[c], sum = total[c], u = xlo, fu = 0.0;
+                auto visit = [&](double x) {
+                    const double v = phi(x);
+                    if (v != v) nanv[c] = true;
+                    const bool ab = v > 0.0;
+                    if (entry && atA) {                               // the window's first candidate sets the state
+                        st = ab;
+                        up = tqa;
+                    } else if (ab != st) {
+                        double z = x;                                 // (a later segment's first candidate: the breakpoint)
+                        if (!entry) {
+                            if (fu == 0.0) z = u;
+                            else if (v != 0.0) quartic_bisect(phi, u, x, z);
+                        }
+                        const double tz =
+                            (atA && z == xlo) ? tqa : (atB && z == xhi) ? tqb : z == 0.0 ? ta : z == 1.0 ? tb : ta + z * h;
+                        if (count[c] == 0) tfirst[c] = tz;
+                        tlast[c] = tz;
+                        ++count[c];
+                        if (ab) up = tz;
+                        else sum = sum + (tz - up);
+                        st = ab;
+                    }
+                    entry = false;
+                    u = x;
+                    fu = v;
+                };
+                quartic_candidates(g, g1, b, aa, a4, xlo, xhi, visit);
+                above[c] = st;
+                t_up[c] = up;
+                total[c] = sum;
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < LV; ++c) {
+            if (above[c]) total[c] = total[c] + (tqb - t_up[c]);
+            const bool none = count[c] == 0;
+            tfirst[c] = (nanv[c] || none) ? __builtin_nan("") : a.sign * tfirst[c];
+            tlast[c] = (nanv[c] || none) ? __builtin_nan("") : a.sign * tlast[c];
+            if (nanv[c]) {
+                total[c] = __builtin_nan("");
+                count[c] = -1;
+            }
+        }
+        store_ints<LV>(a.count + i * LV, count);
+        store_doubles<LV>(a.first + i * LV, tfirst);
+        store_doubles<LV>(a.last + i * LV, tlast);
+        store_doubles<LV>(a.total + i * LV, total);
     }
 }
 

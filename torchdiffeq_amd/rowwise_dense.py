@@ -17,8 +17,9 @@ one word — only when that bound leaves no room.  An evaluation is `tdeq_row_de
 and the fraction of the step) followed by `tdeq_row_event_eval_mapped`.  The derivative, antiderivative and integral of the
 record are the same search followed by `tdeq_row_dense_calc`; the two integrals read a per-row prefix of whole-step
 integrals that `tdeq_row_dense_prefix` builds on first use.  The maximum and minimum over a time window are the search of both ends followed
-by `tdeq_row_dense_extremum`, which walks the window's segments and builds nothing.  CPU states run the same steps as
-torch / numpy ops.
+by `tdeq_row_dense_extremum`, which walks the window's segments and builds nothing; the crossings of a level and the time
+above it are the same two searches followed by `tdeq_row_dense_level`, the same walk with a state machine.  CPU states run
+the same steps as torch / numpy ops.
 """
 from __future__ import annotations
 
@@ -31,7 +32,7 @@ from . import rowwise
 from ._native import device_guard
 from .rowwise import _Problem
 
-__all__ = ["odeint_rowwise_dense", "RowDenseOutput", "RowDenseExtremum"]
+__all__ = ["odeint_rowwise_dense", "RowDenseOutput", "RowDenseExtremum", "RowDenseCrossings"]
 
 # the default chunk: CHUNK_ROWS_PER_ROW slots per row of the batch, at most CHUNK_BYTES of coefficients, never fewer than B
 CHUNK_ROWS_PER_ROW = 4
@@ -169,10 +170,21 @@ class RowDenseExtremum(NamedTuple):
     times: torch.Tensor
 
 
+class RowDenseCrossings(NamedTuple):
+    """`RowDenseOutput.crossings`: per element the number of crossings of the level inside the window (int32; -1 where the
+    answer is NaN), the fp64 true times of the first and the last crossing met in the direction of the solve (NaN if `count
+    <= 0`) and the total true-time duration (fp64, >= 0) with `y > level` inside the window."""
+    count: torch.Tensor
+    first: torch.Tensor
+    last: torch.Tensor
+    time_above: torch.Tensor
+
+
 class RowDenseOutput:
     """The piecewise quartic of a rowwise solve; `dense(t)` evaluates it, `derivative(t)`, `antiderivative(t)` and
     `integral(ta, tb)` give its time derivative and its integrals in closed form, `maximum(ta, tb)` and `minimum(ta, tb)` its
-    extrema over a time window and their times (see `odeint_rowwise_dense`).
+    extrema over a time window and their times, `crossings(level, ta, tb)` and `time_above(level, ta, tb)` its crossings of a
+    level and the time spent above it (see `odeint_rowwise_dense`).
 
     Attributes (the wire format, all on the state's device): `t0`, `t1` `[B]` fp64 in true time; `offsets` `[B + 1]` int64;
     `seg_start`, `seg_end` `[n_seg]` fp64 in true time, row r's segments — its accepted steps — contiguous and in step
@@ -433,6 +445,86 @@ class RowDenseOutput:
         """The smallest value of every element on the window and its time: `maximum` with the comparison reversed."""
         return self._extremum("dense.minimum(ta, tb)", 1, ta, tb, check)
 
+    # -- crossings of a level over a time window: the walk of the extrema with a state machine ------------------------------
+    def _level(self, what: str, level) -> torch.Tensor:
+        """level -> a contiguous `[B, L]` tensor of the state's dtype on the state's device."""
+        B, L = self._shape[0], self.coeffs.shape[2]
+        dev, dtype = self.coeffs.device, self.coeffs.dtype
+        if isinstance(level, torch.Tensor):
+            if level.requires_grad and torch.is_grad_enabled():
+                raise NotImplementedError("odeint_rowwise_dense: the dense output does not propagate gradients (level "
+                                          "requires grad); detach it or evaluate under torch.no_grad()")
+            if level.is_complex() or level.dtype == torch.bool:
+                raise ValueError(f"{what}: level must be a real number or tensor, got a {level.dtype} tensor")
+            lev = level.detach().to(device=dev, dtype=dtype)
+        elif isinstance(level, (int, float)) and not isinstance(level, bool):
+            lev = torch.tensor(float(level), dtype=dtype, device=dev)
+        else:
+            raise ValueError(f"{what}: level must be a number or a tensor, got {type(level).__name__}")
+        try:
+            lev = lev.expand(self._shape)
+        except RuntimeError:
+            raise ValueError(f"{what}: level of shape {tuple(lev.shape)} does not broadcast to [B, *row_shape] = "
+                             f"{list(self._shape)}") from None
+        return lev.reshape(B, L).contiguous()
+
+    def crossings(self, level, ta, tb, check: bool = True) -> RowDenseCrossings:
+        """Where every ELEMENT of `y_r` crosses `level` on the window between `ta` and `tb` (true time, in either order: the
+        same bits) and for how long it is above it -> `RowDenseCrossings(count, first, last, time_above)`, all `[Q, B,
+        *row_shape]` (`[B, *row_shape]` for two single times): `count` int32, the crossings inside the window; `first` and
+        `last` fp64, the true times of the first and the last crossing met in the direction of the solve (NaN without one);
+        `time_above` fp64, the total duration (>= 0) with `y > level`, strictly.  `level` is a number or a real tensor that
+        broadcasts to `[B, *row_shape]` (one for all, one per element, or one per row as `[B, 1, ...]`), rounded once to
+        the state's dtype; it does not vary per query, and a NaN level gives `count = -1` and NaN for that element alone.
+        `ta` and `tb` take the query forms of `integral` and broadcast against each other; both must lie inside `[t0[r],
+        t1[r]]` (`check=True` names the offending query of `ta` first, then of `tb`; `check=False` gives `count = -1` and NaN
+        for the whole row of such a query and reads nothing).  Exact on the record: between two neighbouring candidates of
+        the walk of `maximum` the quartic is monotone, and a crossing there is found by bisection (see
+        `odeint_rowwise_dense`).  The segment that starts at a breakpoint `p` is entered at its start: a `jump_dy` dose at `p`
+        inside the window or at its near end that lifts the element over the level is a crossing at time `p`; one at the far
+        end is not seen.  Builds and caches nothing."""
+        what = "dense.crossings(level, ta, tb)"
+        names = ("ta", "tb")
+        lev = self._level(what, level)
+        tqs, single = self._query_lists(what, names, (ta, tb))
+        Q, B = tqs[0].shape
+        if self._k is not None and Q * B >= _NONE:
+            raise ValueError(f"{what}: {Q * B} queries in one call; the query index is a 32-bit word")
+        L, dev, dtype = self.coeffs.shape[2], self.coeffs.device, self.coeffs.dtype
+        count = torch.empty(Q * B, L, dtype=torch.int32, device=dev)
+        first, last, above = (torch.empty(Q * B, L, dtype=torch.float64, device=dev) for _ in range(3))
+        firsts = [_NONE, _NONE]
+        if Q > 0:
+            with torch.no_grad(), device_guard(dev):
+                if self._k is None:
+                    found = [self._search_host(tq) for tq in tqs]
+                    firsts = [bad for _, _, bad in found]
+                    lists = [v for (seg, x, _), tq in zip(found, tqs) for v in (seg, x, tq)]
+                    outs = rowwise.HostRowKernels.quartic_levels(self.coeffs, lev, self._ta, self._tb, self._sign, *lists)
+                    for dst, src in zip((count, first, last, above), outs):
+                        dst.copy_(src)
+                else:
+                    status = torch.full((2,), _NONE, dtype=torch.int32, device=dev)
+                    lists = []
+                    for i, tq in enumerate(tqs):
+                        seg = torch.empty(Q * B, dtype=torch.int32, device=dev)
+                        x = torch.empty(Q * B, dtype=dtype, device=dev)
+                        self._k.row_dense_search(tq, self.offsets, self._ta, self._tb, self._t0, self._t1, seg, x,
+                                                 status[i:i + 1])
+                        lists += [seg, x, tq]
+                    self._k.row_dense_level(count, first, last, above, lev, self.coeffs, self._ta, self._tb, self._sign, *lists)
+                    if check:
+                        firsts = status.tolist()                          # the one read
+        if check:
+            self._raise_out_of_range(what, names, tqs, firsts)
+        outs = RowDenseCrossings(*(v.view(Q, *self._shape) for v in (count, first, last, above)))
+        return RowDenseCrossings(*(v[0] for v in outs)) if single else outs
+
+    def time_above(self, level, ta, tb, check: bool = True) -> torch.Tensor:
+        """The total true-time duration every element spends strictly above `level` on the window: `crossings(level, ta, tb,
+        check).time_above`, the same launch."""
+        return self.crossings(level, ta, tb, check).time_above
+
 
 def odeint_rowwise_dense(func, y0, t0, t1, *, rtol=1e-7, atol=1e-9, method="dopri5", options=None, compact=None,
                          return_stats=False):
@@ -488,6 +580,26 @@ def odeint_rowwise_dense(func, y0, t0, t1, *, rtol=1e-7, atol=1e-9, method="dopr
     is `dense(p)` (the fp64 Horner form rounded once).  Ties go to the earlier candidate in the direction of the solve.  One
     launch after the two searches; cost grows with the steps inside the window (one lane per element walks them); nothing is
     built or cached.
+
+    Level crossings on the record: `dense.crossings(level, ta, tb)` -> `RowDenseCrossings(count, first, last, time_above)`
+    and `dense.time_above(level, ta, tb)` (the last field alone, the same launch) answer, per ELEMENT and over the window
+    between the two times (either order, the query forms and `check` of `integral`): how often the element crosses `level`
+    (int32), the fp64 true times of the first and the last crossing met in the direction of the solve (NaN without one), and
+    the total true-time duration with `y > level`, strictly — T > MIC, onset and offset of a dosing solve.  `level` is a
+    number or a real tensor that broadcasts to `[B, *row_shape]` (one for all, one per element, one per row as `[B, 1, ...]`),
+    rounded once to the state's dtype; it does not vary per query; a NaN level gives `count = -1` and NaN for that element,
+    an out-of-range query with `check=False` for its whole row.  The walk is that of `maximum`: between two neighbouring
+    candidates of a step (its clipped ends, the roots of y'' that bound pieces, the stationary points) the quartic is
+    monotone, so `y - level` has at most one root there, which one more bisection in fp64 finds (`+ - * /`, comparisons and
+    `fabs` only).  A state machine over the candidates in solver-time order counts the crossings and adds the durations left
+    to right; include/tdeq_hip.h states the operation order, which is the contract: the HIP kernel (`tdeq_row_dense_level`,
+    ABI 33) and the numpy path of a CPU state have the same bits, and a window gives the same bits in either order of its
+    ends.  The first candidate of every later step is the RIGHT limit at the breakpoint: a `jump_dy` dose at `p` that lifts an
+    element over the level is a crossing at time `p` exactly, for `lo <= p < hi`; a window that ends at `p` does not see
+    it, and `time_above(level, p, p)` is 0.  The answer is exact ON THE RECORD, and the record is discontinuous at
+    rounding level at every breakpoint (the end of one step's quartic and the start of the next may differ in their last
+    bits): a level inside such a gap is crossed there once more than the continuous solution would be.  A value that only
+    touches the level from below is no crossing.  One launch after the two searches; nothing is built or cached.
 
     Returns `dense`; with `return_stats=True`, `(dense, stats)`: the stats of `odeint_rowwise` (`n_accepted`,
     `n_rejected`, `nfe`; with `compact` also `row_evals`, `n_repacks`) plus `n_segments` and `n_chunks`.
