@@ -15,9 +15,10 @@ torch expressions on CPU tensors of the state's type, pinned to the reference by
 Every elementwise comparison runs on randn inputs and on an edge tensor (`_lowp_kernels.draw_edge`: the float16 subnormal
 range, products that overflow the type, +-0, +-inf, NaN): finite and infinite results bit for bit, NaN for NaN.
 
-Out of scope: bfloat16 subnormals (they are float32 subnormals), and the grid-stride branch of lp::sel_kernel past the
-grid cap, which needs more than 10^8 elements.  No state here has more than 3 * 2048 + 17 elements (a layout of S segments
-occupies S reduction chunks at least, whatever its segments hold)."""
+Out of scope: bfloat16 subnormals (they are float32 subnormals).  The grid-stride branches of lp::map_kernel and
+lp::sel_kernel past the grid cap, which need more than 10^8 elements, are in tests/test_grid_stride_gpu.py.  No state here
+has more than 3 * 2048 + 17 elements (a layout of S segments occupies S reduction chunks at least, whatever its segments
+hold)."""
 import math
 
 import numpy as np
