@@ -4,6 +4,7 @@
 #include <hip/hip_ext.h>
 
 #include <cstdlib>
+#include <type_traits>
 
 #include "tdeq_kernels.hpp"
 #include "tdeq_kernels_complex.hpp"
@@ -33,6 +34,133 @@ inline int check_launch() {
     return (int)e;
 }
 
+// ---- the run-time choices of a launch, each written once: every helper calls f with a tag and returns its status -----
+// (shared by the three host files: this one, tdeq_abi_lp.hpp, tdeq_abi_rowwise.hpp)
+inline bool real_dtype_ok(int dtype) { return dtype == TDEQ_F32 || dtype == TDEQ_F64; }
+// bfloat16 / float16 states: the entry points of the host-driven step (tdeq_kernels_lp.hpp; include/tdeq_hip.h lists them)
+inline bool lp_dtype(int dtype) { return dtype == TDEQ_BF16 || dtype == TDEQ_F16; }
+inline bool state_dtype_ok(int dtype) { return real_dtype_ok(dtype) || lp_dtype(dtype); }
+// the norm entry points also take interleaved complex states (TDEQ_C64 / TDEQ_C128: tdeq_kernels_complex.hpp)
+inline bool cplx_dtype(int dtype) { return dtype == TDEQ_C64 || dtype == TDEQ_C128; }
+
+template <typename T>
+constexpr bool is_lp = std::is_same_v<T, lp::BF16> || std::is_same_v<T, lp::F16>;
+
+// f(T{}), T = float or double
+template <typename F>
+int real_dtype(int dtype, F f) {
+    return dtype == TDEQ_F32 ? f(float{}) : f(double{});
+}
+
+// f(T{}) or, for a 16-bit state, f(S{}) with S = lp::BF16 or lp::F16 (is_lp<S>)
+template <typename F>
+int state_dtype(int dtype, F f) {
+    if (dtype == TDEQ_BF16) return f(lp::BF16{});
+    if (dtype == TDEQ_F16) return f(lp::F16{});
+    return real_dtype(dtype, f);
+}
+
+// the norm entry points: f(tag, std::bool_constant<CPLX>{}) — a complex state comes as its real type with CPLX set
+template <typename F>
+int norm_dtype(int dtype, F f) {
+    if (dtype == TDEQ_C64) return f(float{}, std::true_type{});
+    if (dtype == TDEQ_C128) return f(double{}, std::true_type{});
+    return state_dtype(dtype, [&](auto t) { return f(t, std::false_type{}); });
+}
+
+// f(std::true_type{}) or f(std::false_type{}): one bool template argument of a kernel; flags: two of them
+template <typename F>
+int flag(bool b, F f) {
+    return b ? f(std::true_type{}) : f(std::false_type{});
+}
+
+template <typename F>
+int flags(bool b0, bool b1, F f) {
+    return flag(b0, [&](auto t0) { return flag(b1, [&](auto t1) { return f(t0, t1); }); });
+}
+
+// f(std::integral_constant<int, N>{}) for LO <= N = nt <= HI: the only switch over a term (or stage) count
+template <int LO, int HI = TDEQ_MAX_TERMS, typename F>
+int terms(int nt, F f) {
+    static_assert(LO >= 0 && HI <= TDEQ_MAX_TERMS);
+    switch (nt) {
+#define TDEQ_CASE(N) case N: if constexpr (N >= LO && N <= HI) return f(std::integral_constant<int, N>{}); break;
+        TDEQ_CASE(0) TDEQ_CASE(1) TDEQ_CASE(2) TDEQ_CASE(3) TDEQ_CASE(4) TDEQ_CASE(5) TDEQ_CASE(6) TDEQ_CASE(7)
+        TDEQ_CASE(8) TDEQ_CASE(9) TDEQ_CASE(10) TDEQ_CASE(11) TDEQ_CASE(12) TDEQ_CASE(13) TDEQ_CASE(14)
+#undef TDEQ_CASE
+    }
+    return TDEQ_EINVAL;
+}
+
+// f(T{}, std::integral_constant<int, N>{}): what a term-templated entry point launches through
+template <int LO, int HI = TDEQ_MAX_TERMS, typename F>
+int real_dtype_terms(int dtype, int nt, F f) {
+    return real_dtype(dtype, [&](auto t) { return terms<LO, HI>(nt, [&](auto n) { return f(t, n); }); });
+}
+
+template <int LO, int HI = TDEQ_MAX_TERMS, typename F>
+int state_dtype_terms(int dtype, int nt, F f) {
+    return state_dtype(dtype, [&](auto t) { return terms<LO, HI>(nt, [&](auto n) { return f(t, n); }); });
+}
+
+struct Ptrs {                         // an array of n pointers: k[], outs[], x[]
+    const void* const* p;
+    int n;
+};
+
+inline bool aligned16(Ptrs a) {
+    for (int j = 0; j < a.n; ++j) if (!aligned16(a.p[j])) return false;
+    return true;
+}
+
+// are all of these pointers (and every pointer of these arrays) 16-byte aligned; so is a null pointer: an absent input
+template <typename... P>
+bool all_aligned(P... p) {
+    return (aligned16(p) && ...);
+}
+
+// A streaming launch over n elements of T: 16-byte elements when `vec`; f(std::bool_constant<VEC>{}, grid) launches.
+template <typename T, typename F>
+int stream_launch(bool vec, int64_t n, F f) {
+    const dim3 g(stream_grid(vec ? n / VecOf<T>::L : n, kBlock));
+    return flag(vec, [&](auto v) {
+        f(v, g);
+        return check_launch();
+    });
+}
+
+// The terms of a launch: a.k[j] and the coefficients as the reference rounds them, c_j = fl_T(fl_T(coef_j) * fl_T(dt)) —
+// rk_common.py:79,201-205 (a stage row), :89 (dt * c_error, the second row `e` of the fused error), :365-366 (dt * c_mid).
+// With dt in device memory (`dev_dt`: captured steps) c_j = fl_T(coef_j) and the kernel multiplies.  The zero-term forms
+// keep one unused slot.  Returns whether every k[j] is 16-byte aligned.
+template <typename T, int NT, int M>
+bool fill_terms(const T* (&ak)[M], T (&ac)[M], const void* const* k, const double* coef, double dt, bool dev_dt,
+                T (*ae)[M] = nullptr, const double* err_coef = nullptr) {
+    static_assert(NT <= M);
+    const T dtT = (T)dt;
+    if (NT == 0) {
+        ak[0] = nullptr;
+        ac[0] = (T)0;
+    }
+    for (int j = 0; j < NT; ++j) {
+        ak[j] = static_cast<const T*>(k[j]);
+        ac[j] = dev_dt ? (T)coef[j] : (T)coef[j] * dtT;
+        if (ae) (*ae)[j] = dev_dt ? (T)err_coef[j] : (T)err_coef[j] * dtT;
+    }
+    return all_aligned(Ptrs{k, NT});
+}
+
+// out = y0 + sum_j c_j k_j: the argument block of every stage combine; returns the 16-byte decision of its pointers
+template <typename T, int NT>
+bool fill_combine(CombineArgs<T, NT>& a, void* out, const void* y0, const void* const* k, const double* coef, double dt,
+                  int64_t n, bool dev_dt = false, T (*e)[NT] = nullptr, const double* err_coef = nullptr) {
+    a.out = static_cast<T*>(out);
+    a.y0 = static_cast<const T*>(y0);
+    a.n = n;
+    const bool k_aligned = fill_terms<T, NT>(a.k, a.c, k, coef, dt, dev_dt, e, err_coef);
+    return all_aligned(out, y0) && k_aligned;
+}
+
 // Cache policy of a streaming launch (bit 0: non-temporal loads, bit 1: non-temporal stores), chosen from the bytes
 // its streams touch.  Measured on the MI355X (tools/stream_count.hip, profiles/r05_stream_count.json): with every byte
 // coming from DRAM, 5 read + 2 write streams run at 5.4 TB/s with the default policy and at 6.0 TB/s with both hints
@@ -58,127 +186,81 @@ inline int stream_policy(int64_t stream_bytes) {
     return stream_bytes > threshold ? kNtPolicy : 0;
 }
 
+// f(std::integral_constant<int, POLICY>{}) with the policy of a launch that touches stream_bytes
+template <typename F>
+int with_policy(int64_t stream_bytes, F f) {
+    switch (stream_policy(stream_bytes)) {
+        case 1: return f(std::integral_constant<int, 1>{});
+        case 2: return f(std::integral_constant<int, 2>{});
+        case 3: return f(std::integral_constant<int, 3>{});
+    }
+    return f(std::integral_constant<int, 0>{});
+}
+
 // ---- stage_combine --------------------------------------------------------------------------------
 template <typename T, int NT>
 int launch_combine(void* out, const void* y0, const void* const* k, const double* coef, double dt,
                    int64_t n, hipStream_t s, hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr) {
     CombineArgs<T, NT> a;
-    a.out = static_cast<T*>(out);
-    a.y0 = static_cast<const T*>(y0);
-    bool vec = aligned16(out) && aligned16(y0);
-    const T dtT = (T)dt;
-    for (int j = 0; j < NT; ++j) {
-        a.k[j] = static_cast<const T*>(k[j]);
-        a.c[j] = (T)coef[j] * dtT;   // fl_T(fl_T(coef)*fl_T(dt)) — rk_common.py:79,201-205
-        vec = vec && aligned16(k[j]);
-    }
-    a.n = n;
+    const bool vec = fill_combine(a, out, y0, k, coef, dt, n);
     constexpr int L = VecOf<T>::L;
     constexpr int U = 1;
-    if (vec && ev_start && ev_stop) {
-        // measurement hook (tdeq_stage_combine_timed): the events carry the dispatch's own begin / end timestamps
-        const unsigned g = stream_grid(n / L, kBlock * U);
-        hipExtLaunchKernelGGL((stage_combine_kernel<T, NT, U, true, 0>), dim3(g), dim3(kBlock), 0, s, ev_start, ev_stop, 0, a);
-    } else if (vec) {
-        const unsigned g = stream_grid(n / L, kBlock * U);
-        switch (stream_policy((int64_t)(NT + 2) * n * (int64_t)sizeof(T))) {   // see stream_policy()
-            case 1: hipLaunchKernelGGL((stage_combine_kernel<T, NT, U, true, 1>), dim3(g), dim3(kBlock), 0, s, a); break;
-            case 2: hipLaunchKernelGGL((stage_combine_kernel<T, NT, U, true, 2>), dim3(g), dim3(kBlock), 0, s, a); break;
-            case 3: hipLaunchKernelGGL((stage_combine_kernel<T, NT, U, true, 3>), dim3(g), dim3(kBlock), 0, s, a); break;
-            default:
-                if ((int64_t)g * kBlock * U >= n / L)
-                    hipLaunchKernelGGL((stage_combine_kernel<T, NT, U, true, 0, true>), dim3(g), dim3(kBlock), 0, s, a);
-                else hipLaunchKernelGGL((stage_combine_kernel<T, NT, U, true, 0>), dim3(g), dim3(kBlock), 0, s, a);
-        }
-    } else {
-        const unsigned g = stream_grid(n, kBlock * U);
-        hipLaunchKernelGGL((stage_combine_kernel<T, NT, U, false>), dim3(g), dim3(kBlock), 0, s, a);
+    const dim3 b(kBlock);
+    if (!vec) {
+        hipLaunchKernelGGL((stage_combine_kernel<T, NT, U, false>), dim3(stream_grid(n, kBlock * U)), b, 0, s, a);
+        return check_launch();
     }
-    return check_launch();
+    const dim3 g(stream_grid(n / L, kBlock * U));
+    if (ev_start && ev_stop) {
+        // measurement hook (tdeq_stage_combine_timed): the events carry the dispatch's own begin / end timestamps
+        hipExtLaunchKernelGGL((stage_combine_kernel<T, NT, U, true, 0>), g, b, 0, s, ev_start, ev_stop, 0, a);
+        return check_launch();
+    }
+    return with_policy((int64_t)(NT + 2) * n * (int64_t)sizeof(T), [&](auto p) {      // see stream_policy()
+        constexpr int P = decltype(p)::value;
+        if (P == 0 && (int64_t)g.x * kBlock * U >= n / L)      // the default policy in one pass
+            hipLaunchKernelGGL((stage_combine_kernel<T, NT, U, true, 0, true>), g, b, 0, s, a);
+        else hipLaunchKernelGGL((stage_combine_kernel<T, NT, U, true, P>), g, b, 0, s, a);
+        return check_launch();
+    });
 }
 
 template <typename T, int NT>
 int launch_combine_fill(void* out, const void* y0, const void* const* k, const double* coef, double dt, int64_t n,
                         void* fill_dst, const double* fill_vals, int n_fill, hipStream_t s) {
     CombineArgs<T, NT> a;
-    a.out = static_cast<T*>(out);
-    a.y0 = static_cast<const T*>(y0);
-    bool vec = aligned16(out) && aligned16(y0);
-    const T dtT = (T)dt;
-    for (int j = 0; j < NT; ++j) {
-        a.k[j] = static_cast<const T*>(k[j]);
-        a.c[j] = (T)coef[j] * dtT;
-        vec = vec && aligned16(k[j]);
-    }
-    a.n = n;
+    const bool vec = fill_combine(a, out, y0, k, coef, dt, n);
     SideFill<T> f;
     f.dst = static_cast<T*>(fill_dst);
     for (int i = 0; i < 16; ++i) f.v[i] = i < n_fill ? (T)fill_vals[i] : (T)0;
     f.n = n_fill;
-    constexpr int L = VecOf<T>::L;
-    if (vec) hipLaunchKernelGGL((stage_combine_fill_kernel<T, NT, true>), dim3(stream_grid(n / L, kBlock)), dim3(kBlock), 0, s, a, f);
-    else hipLaunchKernelGGL((stage_combine_fill_kernel<T, NT, false>), dim3(stream_grid(n, kBlock)), dim3(kBlock), 0, s, a, f);
-    return check_launch();
+    return stream_launch<T>(vec, n, [&](auto v, dim3 g) {
+        hipLaunchKernelGGL((stage_combine_fill_kernel<T, NT, decltype(v)::value>), g, dim3(kBlock), 0, s, a, f);
+    });
 }
 
 template <typename T, int NT>
 int launch_combine_err(void* out, void* err_out, const void* y0, const void* const* k, const double* coef,
                        const double* err_coef, double dt, int64_t n, hipStream_t s) {
     CombineErrArgs<T, NT> a;
-    a.c.out = static_cast<T*>(out);
-    a.c.y0 = static_cast<const T*>(y0);
     a.err_out = static_cast<T*>(err_out);
-    bool vec = aligned16(out) && aligned16(y0) && aligned16(err_out);
-    const T dtT = (T)dt;
-    for (int j = 0; j < NT; ++j) {
-        a.c.k[j] = static_cast<const T*>(k[j]);
-        a.c.c[j] = (T)coef[j] * dtT;
-        a.e[j] = (T)err_coef[j] * dtT;      // dt * c_error_j — rk_common.py:89
-        vec = vec && aligned16(k[j]);
-    }
-    a.c.n = n;
+    const bool vec = fill_combine(a.c, out, y0, k, coef, dt, n, false, &a.e, err_coef) && aligned16(err_out);
     constexpr int L = VecOf<T>::L;
-    if (vec) {
-        const dim3 g(stream_grid(n / L, kBlock)), b(kBlock);
-        // (r05, tried: non-temporal loads for the k streams of THIS launch only — their last use in a dopri5 step — with the
-        //  default policy elsewhere: 0.3357 vs 0.3336 ms per cfg2 step, loads + stores 0.3323: noise; not kept)
-        switch (stream_policy((int64_t)(NT + 3) * n * (int64_t)sizeof(T))) {
-            case 1: hipLaunchKernelGGL((stage_combine_err_kernel<T, NT, true, 1>), g, b, 0, s, a); break;
-            case 2: hipLaunchKernelGGL((stage_combine_err_kernel<T, NT, true, 2>), g, b, 0, s, a); break;
-            case 3: hipLaunchKernelGGL((stage_combine_err_kernel<T, NT, true, 3>), g, b, 0, s, a); break;
-            default:
-                if ((int64_t)g.x * kBlock >= n / L)
-                    hipLaunchKernelGGL((stage_combine_err_kernel<T, NT, true, 0, true>), g, b, 0, s, a);
-                else hipLaunchKernelGGL((stage_combine_err_kernel<T, NT, true, 0>), g, b, 0, s, a);
-        }
-    } else {
-        hipLaunchKernelGGL((stage_combine_err_kernel<T, NT, false>), dim3(stream_grid(n, kBlock)), dim3(kBlock), 0, s, a);
+    const dim3 b(kBlock);
+    if (!vec) {
+        hipLaunchKernelGGL((stage_combine_err_kernel<T, NT, false>), dim3(stream_grid(n, kBlock)), b, 0, s, a);
+        return check_launch();
     }
-    return check_launch();
-}
-
-template <typename T>
-int dispatch_combine_err(void* out, void* err_out, const void* y0, const void* const* k, const double* coef,
-                         const double* err_coef, int nt, double dt, int64_t n, hipStream_t s) {
-    switch (nt) {
-#define TDEQ_CASE(N) case N: return launch_combine_err<T, N>(out, err_out, y0, k, coef, err_coef, dt, n, s);
-        TDEQ_CASE(1) TDEQ_CASE(2) TDEQ_CASE(3) TDEQ_CASE(4) TDEQ_CASE(5) TDEQ_CASE(6) TDEQ_CASE(7)
-        TDEQ_CASE(8) TDEQ_CASE(9) TDEQ_CASE(10) TDEQ_CASE(11) TDEQ_CASE(12) TDEQ_CASE(13) TDEQ_CASE(14)
-#undef TDEQ_CASE
-    }
-    return TDEQ_EINVAL;
-}
-
-template <typename T>
-int dispatch_combine(void* out, const void* y0, const void* const* k, const double* coef, int nt,
-                     double dt, int64_t n, hipStream_t s, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr) {
-    switch (nt) {
-#define TDEQ_CASE(N) case N: return launch_combine<T, N>(out, y0, k, coef, dt, n, s, e0, e1);
-        TDEQ_CASE(1) TDEQ_CASE(2) TDEQ_CASE(3) TDEQ_CASE(4) TDEQ_CASE(5) TDEQ_CASE(6) TDEQ_CASE(7)
-        TDEQ_CASE(8) TDEQ_CASE(9) TDEQ_CASE(10) TDEQ_CASE(11) TDEQ_CASE(12) TDEQ_CASE(13) TDEQ_CASE(14)
-#undef TDEQ_CASE
-    }
-    return TDEQ_EINVAL;
+    const dim3 g(stream_grid(n / L, kBlock));
+    // (r05, tried: non-temporal loads for the k streams of THIS launch only — their last use in a dopri5 step — with the
+    //  default policy elsewhere: 0.3357 vs 0.3336 ms per cfg2 step, loads + stores 0.3323: noise; not kept)
+    return with_policy((int64_t)(NT + 3) * n * (int64_t)sizeof(T), [&](auto p) {
+        constexpr int P = decltype(p)::value;
+        if (P == 0 && (int64_t)g.x * kBlock >= n / L)
+            hipLaunchKernelGGL((stage_combine_err_kernel<T, NT, true, 0, true>), g, b, 0, s, a);
+        else hipLaunchKernelGGL((stage_combine_err_kernel<T, NT, true, P>), g, b, 0, s, a);
+        return check_launch();
+    });
 }
 
 // ---- stage_combine_multi (carried partial sums) ---------------------------------------------------------
@@ -190,74 +272,49 @@ int launch_combine_multi(const tdeq_multi_out* outs, int n_out, const void* y0, 
     a.dt_dev = dt_dev;
     a.y0 = static_cast<const T*>(y0);
     a.acc_in = static_cast<const T*>(acc_in);
-    bool vec = aligned16(y0) && aligned16(acc_in);
+    for (int j = 0; j < NT; ++j) a.k[j] = static_cast<const T*>(k[j]);
+    bool vec = all_aligned(y0, acc_in, Ptrs{k, NT});
     const T dtT = (T)dt;
-    for (int j = 0; j < NT; ++j) {
-        a.k[j] = static_cast<const T*>(k[j]);
-        vec = vec && aligned16(k[j]);
-    }
     a.add_y0 = 0;
     for (int o = 0; o < kMaxMultiOut; ++o) {
         const bool live = o < n_out;
         a.out[o] = live ? static_cast<T*>(outs[o].out) : nullptr;
         a.mask[o] = live ? outs[o].mask : 0u;
         if (live && outs[o].add_y0) a.add_y0 |= 1u << o;
-        for (int j = 0; j < NT; ++j)      // rk_common.py:79,201-205 (dt from device memory: the kernel multiplies)
+        for (int j = 0; j < NT; ++j)      // the rounding of fill_terms, one row per output; a dead output's row is zero
             a.c[o][j] = !live ? (T)0 : (dt_dev ? (T)outs[o].coef[j] : (T)outs[o].coef[j] * dtT);
         if (live) vec = vec && aligned16(outs[o].out);
     }
     a.n_out = n_out;
     a.n = n;
     constexpr int L = VecOf<T>::L;
-    if (vec) {
-        const dim3 g(stream_grid(n / L, kBlock)), b(kBlock);
-        const bool timed = ev_start && ev_stop;      // measurement hook (tdeq_stage_combine_multi_timed)
-        const int64_t streams = NT + 1 + (acc_in ? 1 : 0) + n_out;
-#define TDEQ_MULTI(P)                                                                                                   \
-    if (timed) hipExtLaunchKernelGGL((stage_combine_multi_kernel<T, NT, true, P>), g, b, 0, s, ev_start, ev_stop, 0, a); \
-    else hipLaunchKernelGGL((stage_combine_multi_kernel<T, NT, true, P>), g, b, 0, s, a);
-        const bool one_pass = (int64_t)g.x * kBlock >= n / L;      // exact cover (always, up to 2^24 16-byte elements)
-#define TDEQ_MULTI_LAUNCH(...)                                                                                                \
-    if (timed) hipExtLaunchKernelGGL((stage_combine_multi_kernel<T, NT, true, 0, __VA_ARGS__>), g, b, 0, s, ev_start, ev_stop, 0, a); \
-    else hipLaunchKernelGGL((stage_combine_multi_kernel<T, NT, true, 0, __VA_ARGS__>), g, b, 0, s, a);
-        // (output count, prefix continuation, dt from device memory — captured steps —, one pass)
-#define TDEQ_MULTI_SHAPE(NO, AC)                                       \
-    if (!one_pass) { TDEQ_MULTI_LAUNCH(NO, AC) }                       \
-    else if (dt_dev) { TDEQ_MULTI_LAUNCH(NO, AC, true, true) }         \
-    else { TDEQ_MULTI_LAUNCH(NO, AC, false, true) }
-        switch (stream_policy(streams * n * (int64_t)sizeof(T))) {
-            case 1: TDEQ_MULTI(1) break;
-            case 2: TDEQ_MULTI(2) break;
-            case 3: TDEQ_MULTI(3) break;
-            default:
-                // the in-cache regime (every dopri5 launch at cfg2): output count and prefix continuation as compile-time
-                // constants for the one- and two-output launches (tdeq_kernels.hpp multi_elem)
-                if (n_out == 1 && acc_in) { TDEQ_MULTI_SHAPE(1, 1) }
-                else if (n_out == 1) { TDEQ_MULTI_SHAPE(1, 0) }
-                else if (n_out == 2 && acc_in) { TDEQ_MULTI_SHAPE(2, 1) }
-                else if (n_out == 2) { TDEQ_MULTI_SHAPE(2, 0) }
-                else { TDEQ_MULTI(0) }
-        }
-#undef TDEQ_MULTI_SHAPE
-#undef TDEQ_MULTI_LAUNCH
-#undef TDEQ_MULTI
-    } else {
-        hipLaunchKernelGGL((stage_combine_multi_kernel<T, NT, false>), dim3(stream_grid(n, kBlock)), dim3(kBlock), 0, s, a);
+    const dim3 b(kBlock);
+    if (!vec) {
+        hipLaunchKernelGGL((stage_combine_multi_kernel<T, NT, false>), dim3(stream_grid(n, kBlock)), b, 0, s, a);
+        return check_launch();
     }
-    return check_launch();
-}
-
-template <typename T>
-int dispatch_combine_multi(const tdeq_multi_out* outs, int n_out, const void* y0, const void* acc_in,
-                           const void* const* k, int nt, double dt, int64_t n, hipStream_t s, hipEvent_t e0 = nullptr,
-                           hipEvent_t e1 = nullptr, const double* dt_dev = nullptr) {
-    switch (nt) {
-#define TDEQ_CASE(N) case N: return launch_combine_multi<T, N>(outs, n_out, y0, acc_in, k, dt, n, s, e0, e1, dt_dev);
-        TDEQ_CASE(1) TDEQ_CASE(2) TDEQ_CASE(3) TDEQ_CASE(4) TDEQ_CASE(5) TDEQ_CASE(6) TDEQ_CASE(7)
-        TDEQ_CASE(8) TDEQ_CASE(9) TDEQ_CASE(10) TDEQ_CASE(11) TDEQ_CASE(12) TDEQ_CASE(13) TDEQ_CASE(14)
-#undef TDEQ_CASE
-    }
-    return TDEQ_EINVAL;
+    const dim3 g(stream_grid(n / L, kBlock));
+    const bool timed = ev_start && ev_stop;      // measurement hook (tdeq_stage_combine_multi_timed)
+    auto launch = [&](void (*kernel)(const MultiArgs<T, NT>)) {
+        if (timed) hipExtLaunchKernelGGL(kernel, g, b, 0, s, ev_start, ev_stop, 0, a);
+        else hipLaunchKernelGGL(kernel, g, b, 0, s, a);
+        return check_launch();
+    };
+    const bool one_pass = (int64_t)g.x * kBlock >= n / L;      // exact cover (always, up to 2^24 16-byte elements)
+    const int64_t streams = NT + 1 + (acc_in ? 1 : 0) + n_out;
+    return with_policy(streams * n * (int64_t)sizeof(T), [&](auto p) {
+        constexpr int P = decltype(p)::value;
+        if (P != 0 || n_out > 2) return launch(stage_combine_multi_kernel<T, NT, true, P>);
+        // the in-cache regime (every dopri5 launch at cfg2): output count and prefix continuation as compile-time
+        // constants for the one- and two-output launches (tdeq_kernels.hpp multi_elem), then dt from device memory —
+        // captured steps — and one pass
+        return flags(n_out == 2, acc_in != nullptr, [&](auto two, auto acc) {
+            constexpr int NO = decltype(two)::value ? 2 : 1, AC = decltype(acc)::value ? 1 : 0;
+            if (!one_pass) return launch(stage_combine_multi_kernel<T, NT, true, 0, NO, AC>);
+            if (dt_dev) return launch(stage_combine_multi_kernel<T, NT, true, 0, NO, AC, true, true>);
+            return launch(stage_combine_multi_kernel<T, NT, true, 0, NO, AC, false, true>);
+        });
+    });
 }
 
 // ---- segment table / workspace ---------------------------------------------------------------------
@@ -279,6 +336,24 @@ int fill_segtable(SegTable& st, const tdeq_segment* segs, const void* segs_dev, 
     return 0;
 }
 
+// What a norm launch works on: the segment table, the partial-sum workspace [3][n_chunks] and the stream.
+struct NormSetup {
+    SegTable st;
+    double* ws;
+    hipStream_t s;
+};
+
+// The prologue of the norm entry points: the segment table first, then the size of the workspace.
+int norm_setup(NormSetup& ns, const tdeq_segment* segs, const void* segs_dev, int n_seg, int64_t chunk, int64_t n_chunks,
+               void* workspace, size_t workspace_bytes, void* stream) {
+    const int e = fill_segtable(ns.st, segs, segs_dev, n_seg, chunk, n_chunks);
+    if (e) return e;
+    if (workspace_bytes < tdeq_workspace_bytes(n_chunks)) return TDEQ_EWORKSPACE;
+    ns.ws = static_cast<double*>(workspace);
+    ns.s = static_cast<hipStream_t>(stream);
+    return 0;
+}
+
 int launch_finalize(const SegTable& st, double* ws, int n_sum, double* out_sumsq, double* out_bad,
                     hipStream_t s) {
     FinalizeArgs f;
@@ -293,39 +368,7 @@ int launch_finalize(const SegTable& st, double* ws, int n_sum, double* out_sumsq
     return check_launch();
 }
 
-// ---- error_norm ------------------------------------------------------------------------------------
-template <typename T, int NT>
-int launch_error(void* scaled, const void* y0, const void* y1, const void* const* k, const double* coef,
-                 double dt, const SegTable& st, double* out_sumsq, double* out_bad, double* ws,
-                 hipStream_t s) {
-    ErrArgs<T, NT> a;
-    a.scaled = static_cast<T*>(scaled);
-    a.y0 = static_cast<const T*>(y0);
-    a.y1 = static_cast<const T*>(y1);
-    bool vec = aligned16(y0) && aligned16(y1);
-    const T dtT = (T)dt;
-    for (int j = 0; j < NT; ++j) {
-        a.k[j] = static_cast<const T*>(k[j]);
-        a.c[j] = (T)coef[j] * dtT;   // dt * c_error — rk_common.py:89
-        vec = vec && aligned16(k[j]);
-    }
-    a.st = st;
-    a.part_sumsq = ws;
-    a.part_bad = ws + 2 * st.n_chunks;
-    const dim3 g((unsigned)st.n_chunks), b(kBlock);
-    if (scaled) {
-        vec = vec && aligned16(scaled);
-        if (vec) hipLaunchKernelGGL((error_norm_kernel<T, NT, true, true>), g, b, 0, s, a);
-        else hipLaunchKernelGGL((error_norm_kernel<T, NT, false, true>), g, b, 0, s, a);
-    } else {
-        if (vec) hipLaunchKernelGGL((error_norm_kernel<T, NT, true, false>), g, b, 0, s, a);
-        else hipLaunchKernelGGL((error_norm_kernel<T, NT, false, false>), g, b, 0, s, a);
-    }
-    const int e = check_launch();
-    if (e) return e;
-    return launch_finalize(st, ws, 1, out_sumsq, out_bad, s);
-}
-
+// Optional controller bundle of the *_ctrl entry points (null => plain finalize).
 struct CtrlBundle {
     const tdeq_step_ctrl* ctrl;
     double* out_ctrl;
@@ -333,77 +376,21 @@ struct CtrlBundle {
     void* next_times;
     int state_in_dev;     // hipGraph mode: (t0, dt) of the trial step and the kernels' dt live in ctrl_dev
 };
-int launch_finalize_ctrl(const SegTable& st, double* ws, double* out_sumsq, double* out_bad, const CtrlBundle& cb,
-                         int tkind, hipStream_t s, int ratio_kind);
 
-template <typename T, int NT>
-int launch_error_vec(const void* partial, const void* y0, const void* y1, const void* const* k, const double* coef, double dt,
-                     const double* rtol_v, double rtol_s, const double* atol_v, double atol_s, const SegTable& st,
-                     double* out_sumsq, double* out_bad, double* ws, hipStream_t s, const CtrlBundle* cb = nullptr) {
-    ErrVecArgs<T, NT> a;
-    a.y0 = static_cast<const T*>(y0);
-    a.y1 = static_cast<const T*>(y1);
-    a.partial = static_cast<const T*>(partial);
-    a.k[0] = nullptr;
-    a.c[0] = (T)0;
-    const bool dev_dt = cb && cb->state_in_dev;      // hipGraph mode: dt = ctrl_dev[1] on the device
-    const T dtT = (T)dt;
-    for (int j = 0; j < NT; ++j) {
-        a.k[j] = static_cast<const T*>(k[j]);
-        a.c[j] = dev_dt ? (T)coef[j] : (T)coef[j] * dtT;
-    }
-    a.dt_dev = dev_dt ? cb->ctrl_dev + 1 : nullptr;
-    a.rtol_v = rtol_v;
-    a.atol_v = atol_v;
-    a.rtol_s = rtol_s;
-    a.atol_s = atol_s;
-    a.st = st;
-    a.part_sumsq = ws;
-    a.part_bad = ws + 2 * st.n_chunks;
-    const dim3 g((unsigned)st.n_chunks), b(kBlock);
-    if (dev_dt) {
-        if (partial) hipLaunchKernelGGL((error_norm_vec_kernel<T, NT, true, true>), g, b, 0, s, a);
-        else if constexpr (NT > 0) hipLaunchKernelGGL((error_norm_vec_kernel<T, NT, false, true>), g, b, 0, s, a);
-        else return TDEQ_EINVAL;
-    } else if (partial) hipLaunchKernelGGL((error_norm_vec_kernel<T, NT, true>), g, b, 0, s, a);
-    else if constexpr (NT > 0) hipLaunchKernelGGL((error_norm_vec_kernel<T, NT, false>), g, b, 0, s, a);
-    else return TDEQ_EINVAL;
-    const int e = check_launch();
-    if (e) return e;
-    // with a controller bundle: the ratio in fp64 (the promoted type), the step size and the stage times in T
-    if (cb) return launch_finalize_ctrl(st, ws, out_sumsq, out_bad, *cb, sizeof(T) == 4 ? 1 : 0, s, 0);
-    return launch_finalize(st, ws, 1, out_sumsq, out_bad, s);
+// The prologue of the *_ctrl entry points: every pointer of the bundle, then the counts of the controller's constants.
+int make_ctrl(CtrlBundle& cb, const tdeq_step_ctrl* ctrl, double* out_ctrl, double* ctrl_dev, void* next_times,
+              int state_in_dev, int n_seg) {
+    if (!ctrl || !out_ctrl || !ctrl_dev || !next_times) return TDEQ_EINVAL;
+    if (ctrl->n_times < 1 || ctrl->n_times > TDEQ_MAX_STAGE_TIMES || ctrl->n_norm_seg < 0 || ctrl->n_norm_seg > n_seg)
+        return TDEQ_EINVAL;
+    cb = CtrlBundle{ctrl, out_ctrl, ctrl_dev, next_times, state_in_dev ? 1 : 0};
+    return 0;
 }
 
+// the state's real type as the controller kernel names it: 0 fp64, 1 fp32, 2 bfloat16, 3 float16
 template <typename T>
-int dispatch_error_vec(const void* partial, const void* y0, const void* y1, const void* const* k, const double* coef, int nt,
-                       double dt, const double* rtol_v, double rtol_s, const double* atol_v, double atol_s, const SegTable& st,
-                       double* out_sumsq, double* out_bad, double* ws, hipStream_t s, const CtrlBundle* cb = nullptr) {
-    switch (nt) {
-#define TDEQ_CASE(N) case N: return launch_error_vec<T, N>(partial, y0, y1, k, coef, dt, rtol_v, rtol_s, atol_v, atol_s, st, out_sumsq, out_bad, ws, s, cb);
-        TDEQ_CASE(0) TDEQ_CASE(1) TDEQ_CASE(2) TDEQ_CASE(3) TDEQ_CASE(4) TDEQ_CASE(5) TDEQ_CASE(6) TDEQ_CASE(7)
-        TDEQ_CASE(8) TDEQ_CASE(9) TDEQ_CASE(10) TDEQ_CASE(11) TDEQ_CASE(12) TDEQ_CASE(13) TDEQ_CASE(14)
-#undef TDEQ_CASE
-    }
-    return TDEQ_EINVAL;
-}
+constexpr int kTkind = std::is_same_v<T, lp::BF16> ? 2 : std::is_same_v<T, lp::F16> ? 3 : sizeof(T) == 4 ? 1 : 0;
 
-template <typename T>
-int dispatch_error(void* scaled, const void* y0, const void* y1, const void* const* k, const double* coef,
-                   int nt, double dt, const SegTable& st, double* out_sumsq, double* out_bad, double* ws,
-                   hipStream_t s) {
-    switch (nt) {
-#define TDEQ_CASE(N) case N: return launch_error<T, N>(scaled, y0, y1, k, coef, dt, st, out_sumsq, out_bad, ws, s);
-        TDEQ_CASE(1) TDEQ_CASE(2) TDEQ_CASE(3) TDEQ_CASE(4) TDEQ_CASE(5) TDEQ_CASE(6) TDEQ_CASE(7)
-        TDEQ_CASE(8) TDEQ_CASE(9) TDEQ_CASE(10) TDEQ_CASE(11) TDEQ_CASE(12) TDEQ_CASE(13) TDEQ_CASE(14)
-#undef TDEQ_CASE
-    }
-    return TDEQ_EINVAL;
-}
-
-// Optional controller bundle of the *_ctrl entry point (null ctrl => plain finalize).
-
-// tkind: the state's real type — 0 fp64, 1 fp32 (callers pass `sizeof(T) == 4`), 2 bfloat16, 3 float16
 int launch_finalize_ctrl(const SegTable& st, double* ws, double* out_sumsq, double* out_bad, const CtrlBundle& cb,
                          int tkind, hipStream_t s, int ratio_kind) {
     CtrlArgs a;
@@ -436,30 +423,86 @@ int launch_finalize_ctrl(const SegTable& st, double* ws, double* out_sumsq, doub
     return check_launch();
 }
 
+// The tail of every norm launch: the status of the launch just made, then the per-segment sums — with a controller
+// bundle the step controller too (ratio_kind -1: the ratio in the state's type; 0: in fp64, the promoted type).
+int finish_norm(const NormSetup& ns, int n_sum, double* out_sumsq, double* out_bad, const CtrlBundle* cb = nullptr,
+                int tkind = 0, int ratio_kind = -1) {
+    const int e = check_launch();
+    if (e) return e;
+    if (cb) return launch_finalize_ctrl(ns.st, ns.ws, out_sumsq, out_bad, *cb, tkind, ns.s, ratio_kind);
+    return launch_finalize(ns.st, ns.ws, n_sum, out_sumsq, out_bad, ns.s);
+}
+
+// ---- error_norm ------------------------------------------------------------------------------------
+template <typename T, int NT>
+int launch_error(void* scaled, const void* y0, const void* y1, const void* const* k, const double* coef,
+                 double dt, const NormSetup& ns, double* out_sumsq, double* out_bad) {
+    ErrArgs<T, NT> a;
+    a.scaled = static_cast<T*>(scaled);
+    a.y0 = static_cast<const T*>(y0);
+    a.y1 = static_cast<const T*>(y1);
+    const bool vec = fill_terms<T, NT>(a.k, a.c, k, coef, dt, false) && all_aligned(y0, y1, scaled);
+    a.st = ns.st;
+    a.part_sumsq = ns.ws;
+    a.part_bad = ns.ws + 2 * ns.st.n_chunks;
+    const dim3 g((unsigned)ns.st.n_chunks), b(kBlock);
+    flags(vec, scaled != nullptr, [&](auto v, auto sc) {
+        hipLaunchKernelGGL((error_norm_kernel<T, NT, decltype(v)::value, decltype(sc)::value>), g, b, 0, ns.s, a);
+        return 0;
+    });
+    return finish_norm(ns, 1, out_sumsq, out_bad);
+}
+
+template <typename T, int NT>
+int launch_error_vec(const void* partial, const void* y0, const void* y1, const void* const* k, const double* coef, double dt,
+                     const double* rtol_v, double rtol_s, const double* atol_v, double atol_s, const NormSetup& ns,
+                     double* out_sumsq, double* out_bad, const CtrlBundle* cb = nullptr) {
+    if (NT == 0 && !partial) return TDEQ_EINVAL;
+    ErrVecArgs<T, NT> a;
+    a.y0 = static_cast<const T*>(y0);
+    a.y1 = static_cast<const T*>(y1);
+    a.partial = static_cast<const T*>(partial);
+    const bool dev_dt = cb && cb->state_in_dev;      // hipGraph mode: dt = ctrl_dev[1] on the device
+    fill_terms<T, NT>(a.k, a.c, k, coef, dt, dev_dt);
+    a.dt_dev = dev_dt ? cb->ctrl_dev + 1 : nullptr;
+    a.rtol_v = rtol_v;
+    a.atol_v = atol_v;
+    a.rtol_s = rtol_s;
+    a.atol_s = atol_s;
+    a.st = ns.st;
+    a.part_sumsq = ns.ws;
+    a.part_bad = ns.ws + 2 * ns.st.n_chunks;
+    const dim3 g((unsigned)ns.st.n_chunks), b(kBlock);
+    flags(partial != nullptr, dev_dt, [&](auto pt, auto dd) {
+        constexpr bool PARTIAL = decltype(pt)::value, DEVDT = decltype(dd)::value;
+        if constexpr (PARTIAL || NT > 0) {
+            if constexpr (DEVDT) hipLaunchKernelGGL((error_norm_vec_kernel<T, NT, PARTIAL, true>), g, b, 0, ns.s, a);
+            else hipLaunchKernelGGL((error_norm_vec_kernel<T, NT, PARTIAL>), g, b, 0, ns.s, a);
+        }
+        return 0;
+    });
+    // with a controller bundle: the ratio in fp64 (the promoted type), the step size and the stage times in T
+    return finish_norm(ns, 1, out_sumsq, out_bad, cb, kTkind<T>, 0);
+}
+
 template <typename T, int NT>
 int launch_error_partial(const void* partial, const void* y0, const void* y1, const void* const* k,
-                         const double* coef, double dt, const SegTable& st, double* out_sumsq, double* out_bad,
-                         double* ws, const CtrlBundle* cb, hipStream_t s, void* copy_last = nullptr) {
+                         const double* coef, double dt, const NormSetup& ns, double* out_sumsq, double* out_bad,
+                         const CtrlBundle* cb, void* copy_last = nullptr) {
     ErrPartialArgs<T, NT> a;
     a.copy_out = static_cast<T*>(copy_last);
     if (copy_last && NT == 0) return TDEQ_EINVAL;        // nothing to copy: the error row ended with the last combine
     a.partial = static_cast<const T*>(partial);
     a.y0 = static_cast<const T*>(y0);
     a.y1 = static_cast<const T*>(y1);
-    bool vec = aligned16(partial) && aligned16(y0) && aligned16(y1);
     const bool dev_dt = cb && cb->state_in_dev;      // hipGraph mode: dt = ctrl_dev[1] on the device
-    const T dtT = (T)dt;
-    a.k[0] = nullptr;
-    a.c[0] = (T)0;
-    for (int j = 0; j < NT; ++j) {
-        a.k[j] = static_cast<const T*>(k[j]);
-        a.c[j] = dev_dt ? (T)coef[j] : (T)coef[j] * dtT;
-        vec = vec && aligned16(k[j]);
-    }
+    const bool vec = fill_terms<T, NT>(a.k, a.c, k, coef, dt, dev_dt) && all_aligned(partial, y0, y1);
     a.dt_dev = dev_dt ? cb->ctrl_dev + 1 : nullptr;
+    const SegTable& st = ns.st;
+    hipStream_t s = ns.s;
     a.st = st;
-    a.part_sumsq = ws;
-    a.part_bad = ws + 2 * st.n_chunks;
+    a.part_sumsq = ns.ws;
+    a.part_bad = ns.ws + 2 * st.n_chunks;
     const dim3 g((unsigned)st.n_chunks), b(kBlock);
     // the common shape — one segment whose chunk_start is 0, dt folded by the host — has its own lean instantiation
     const bool single = st.n_seg == 1 && st.inl[0].chunk_start == 0, lean = single && !dev_dt;
@@ -477,50 +520,23 @@ int launch_error_partial(const void* partial, const void* y0, const void* y1, co
     else if (vec && single) hipLaunchKernelGGL((error_norm_partial_kernel<T, NT, true, 0, true, true>), g, b, 0, s, a);
     else if (vec) hipLaunchKernelGGL((error_norm_partial_kernel<T, NT, true, 0>), g, b, 0, s, a);
     else hipLaunchKernelGGL((error_norm_partial_kernel<T, NT, false>), g, b, 0, s, a);
-    const int e = check_launch();
-    if (e) return e;
-    if (cb) return launch_finalize_ctrl(st, ws, out_sumsq, out_bad, *cb, sizeof(T) == 4 ? 1 : 0, s, -1);
-    return launch_finalize(st, ws, 1, out_sumsq, out_bad, s);
-}
-
-template <typename T>
-int dispatch_error_partial(const void* partial, const void* y0, const void* y1, const void* const* k,
-                           const double* coef, int nt, double dt, const SegTable& st, double* out_sumsq,
-                           double* out_bad, double* ws, const CtrlBundle* cb, hipStream_t s, void* copy_last = nullptr) {
-    switch (nt) {
-        case 0: return launch_error_partial<T, 0>(partial, y0, y1, k, coef, dt, st, out_sumsq, out_bad, ws, cb, s, copy_last);
-        case 1: return launch_error_partial<T, 1>(partial, y0, y1, k, coef, dt, st, out_sumsq, out_bad, ws, cb, s, copy_last);
-        case 2: return launch_error_partial<T, 2>(partial, y0, y1, k, coef, dt, st, out_sumsq, out_bad, ws, cb, s, copy_last);
-    }
-    return TDEQ_EINVAL;
+    return finish_norm(ns, 1, out_sumsq, out_bad, cb, kTkind<T>);
 }
 
 template <typename T, int NT>
 int launch_combine_devdt(void* out, void* err_out, const void* y0, const void* const* k, const double* coef,
                          const double* err_coef, const double* dt_dev, int64_t n, hipStream_t s) {
     CombineDevTArgs<T, NT> a;
-    a.c.out = static_cast<T*>(out);
-    a.c.y0 = static_cast<const T*>(y0);
     a.err_out = static_cast<T*>(err_out);
-    bool vec = aligned16(out) && aligned16(y0) && aligned16(err_out);
-    for (int j = 0; j < NT; ++j) {
-        a.c.k[j] = static_cast<const T*>(k[j]);
-        a.c.c[j] = (T)coef[j];
-        a.e[j] = err_out ? (T)err_coef[j] : (T)0;
-        vec = vec && aligned16(k[j]);
-    }
-    a.c.n = n;
+    const bool vec = fill_combine(a.c, out, y0, k, coef, 0.0, n, true, err_out ? &a.e : nullptr, err_coef) && aligned16(err_out);
+    if (!err_out) for (int j = 0; j < NT; ++j) a.e[j] = (T)0;
     a.dt_dev = dt_dev;
-    constexpr int L = VecOf<T>::L;
-    const dim3 g(vec ? stream_grid(n / L, kBlock) : stream_grid(n, kBlock)), b(kBlock);
-    if (err_out) {
-        if (vec) hipLaunchKernelGGL((combine_devdt_kernel<T, NT, true, true>), g, b, 0, s, a);
-        else hipLaunchKernelGGL((combine_devdt_kernel<T, NT, false, true>), g, b, 0, s, a);
-    } else {
-        if (vec) hipLaunchKernelGGL((combine_devdt_kernel<T, NT, true, false>), g, b, 0, s, a);
-        else hipLaunchKernelGGL((combine_devdt_kernel<T, NT, false, false>), g, b, 0, s, a);
-    }
-    return check_launch();
+    return stream_launch<T>(vec, n, [&](auto v, dim3 g) {
+        flag(err_out != nullptr, [&](auto err) {
+            hipLaunchKernelGGL((combine_devdt_kernel<T, NT, decltype(v)::value, decltype(err)::value>), g, dim3(kBlock), 0, s, a);
+            return 0;
+        });
+    });
 }
 
 // States below this size are launch-latency-bound: the run-time-term-count kernel (one instantiation, smallest code)
@@ -530,15 +546,10 @@ constexpr int64_t kDevCombineTunedFrom = 1 << 17;
 template <typename T>
 int launch_combine_dev(void* out, void* err_out, const void* y0, const void* const* k, const double* coef,
                        const double* err_coef, int nt, const double* dt_dev, int64_t n, hipStream_t s) {
-    if (n >= kDevCombineTunedFrom) {
-        switch (nt) {
-#define TDEQ_CASE(N) case N: return launch_combine_devdt<T, N>(out, err_out, y0, k, coef, err_coef, dt_dev, n, s);
-            TDEQ_CASE(1) TDEQ_CASE(2) TDEQ_CASE(3) TDEQ_CASE(4) TDEQ_CASE(5) TDEQ_CASE(6) TDEQ_CASE(7)
-            TDEQ_CASE(8) TDEQ_CASE(9) TDEQ_CASE(10) TDEQ_CASE(11) TDEQ_CASE(12) TDEQ_CASE(13) TDEQ_CASE(14)
-#undef TDEQ_CASE
-        }
-        return TDEQ_EINVAL;
-    }
+    if (n >= kDevCombineTunedFrom)
+        return terms<1>(nt, [&](auto t) {
+            return launch_combine_devdt<T, decltype(t)::value>(out, err_out, y0, k, coef, err_coef, dt_dev, n, s);
+        });
     CombineDevArgs<T> a;
     a.out = static_cast<T*>(out);
     a.err_out = static_cast<T*>(err_out);
@@ -567,12 +578,9 @@ int launch_commit(void* y_prev, void* f_prev, void* y_cur, void* f_cur, const vo
     a.f1 = static_cast<const T*>(f1);
     a.ctrl_dev = ctrl_dev;
     a.n = n;
-    const bool vec = aligned16(y_prev) && aligned16(f_prev) && aligned16(y_cur) && aligned16(f_cur) && aligned16(y1) &&
-                     aligned16(f1);
-    constexpr int L = VecOf<T>::L;
-    if (vec) hipLaunchKernelGGL((step_commit_kernel<T, true>), dim3(stream_grid(n / L, kBlock)), dim3(kBlock), 0, s, a);
-    else hipLaunchKernelGGL((step_commit_kernel<T, false>), dim3(stream_grid(n, kBlock)), dim3(kBlock), 0, s, a);
-    return check_launch();
+    return stream_launch<T>(all_aligned(y_prev, f_prev, y_cur, f_cur, y1, f1), n, [&](auto v, dim3 g) {
+        hipLaunchKernelGGL((step_commit_kernel<T, decltype(v)::value>), g, dim3(kBlock), 0, s, a);
+    });
 }
 
 template <typename T>
@@ -587,53 +595,42 @@ int launch_combine_sel(void* out, const void* y_acc, const void* f_acc, const vo
     a.coef = (T)coef;
     a.ctrl_dev = ctrl_dev;
     a.n = n;
-    constexpr int L = VecOf<T>::L;
-    const bool vec = aligned16(out) && aligned16(y_acc) && aligned16(f_acc) && aligned16(y_rej) && aligned16(f_rej);
-    if (vec) {
-        const dim3 g(stream_grid(n / L, kBlock)), b(kBlock);
-        // (reads 2 of the 4 inputs; the k tensors of the step just finished are the cache's other tenants)
-        switch (stream_policy((int64_t)3 * n * (int64_t)sizeof(T))) {
-            case 1: hipLaunchKernelGGL((stage_combine_sel_kernel<T, true, 1>), g, b, 0, s, a); break;
-            case 2: hipLaunchKernelGGL((stage_combine_sel_kernel<T, true, 2>), g, b, 0, s, a); break;
-            case 3: hipLaunchKernelGGL((stage_combine_sel_kernel<T, true, 3>), g, b, 0, s, a); break;
-            default: hipLaunchKernelGGL((stage_combine_sel_kernel<T, true, 0>), g, b, 0, s, a);
-        }
-    } else {
-        hipLaunchKernelGGL((stage_combine_sel_kernel<T, false>), dim3(stream_grid(n, kBlock)), dim3(kBlock), 0, s, a);
+    const dim3 b(kBlock);
+    if (!all_aligned(out, y_acc, f_acc, y_rej, f_rej)) {
+        hipLaunchKernelGGL((stage_combine_sel_kernel<T, false>), dim3(stream_grid(n, kBlock)), b, 0, s, a);
+        return check_launch();
     }
-    return check_launch();
+    const dim3 g(stream_grid(n / VecOf<T>::L, kBlock));
+    // (reads 2 of the 4 inputs; the k tensors of the step just finished are the cache's other tenants)
+    return with_policy((int64_t)3 * n * (int64_t)sizeof(T), [&](auto p) {
+        hipLaunchKernelGGL((stage_combine_sel_kernel<T, true, decltype(p)::value>), g, b, 0, s, a);
+        return check_launch();
+    });
 }
 
 // ---- init norms ------------------------------------------------------------------------------------
 template <typename T>
-int launch_init(int mode, const void* a_, const void* b_, const void* y_, const SegTable& st,
-                double* out_sumsq, double* out_bad, double* ws, hipStream_t s) {
+int launch_init(int mode, const void* a_, const void* b_, const void* y_, const NormSetup& ns, double* out_sumsq,
+                double* out_bad) {
     InitArgs<T> a;
     a.a = static_cast<const T*>(a_);
     a.b = static_cast<const T*>(b_);
     a.y = static_cast<const T*>(y_);
-    a.st = st;
-    a.part0 = ws;
-    a.part1 = ws + st.n_chunks;
-    a.part_bad = ws + 2 * st.n_chunks;
-    const bool vec = aligned16(a_) && aligned16(b_) && aligned16(y_);
-    const dim3 g((unsigned)st.n_chunks), b(kBlock);
-    if (mode == 0) {
-        if (vec) hipLaunchKernelGGL((init_norms_kernel<T, 0, true>), g, b, 0, s, a);
-        else hipLaunchKernelGGL((init_norms_kernel<T, 0, false>), g, b, 0, s, a);
-    } else {
-        if (vec) hipLaunchKernelGGL((init_norms_kernel<T, 1, true>), g, b, 0, s, a);
-        else hipLaunchKernelGGL((init_norms_kernel<T, 1, false>), g, b, 0, s, a);
-    }
-    const int e = check_launch();
-    if (e) return e;
-    return launch_finalize(st, ws, mode == 0 ? 2 : 1, out_sumsq, out_bad, s);
+    a.st = ns.st;
+    a.part0 = ns.ws;
+    a.part1 = ns.ws + ns.st.n_chunks;
+    a.part_bad = ns.ws + 2 * ns.st.n_chunks;
+    const dim3 g((unsigned)ns.st.n_chunks), b(kBlock);
+    flags(mode != 0, all_aligned(a_, b_, y_), [&](auto m, auto v) {
+        hipLaunchKernelGGL((init_norms_kernel<T, decltype(m)::value ? 1 : 0, decltype(v)::value>), g, b, 0, ns.s, a);
+        return 0;
+    });
+    return finish_norm(ns, mode == 0 ? 2 : 1, out_sumsq, out_bad);
 }
 
 template <typename T>
 int launch_init_vec(int mode, const void* a_, const void* b_, const void* y_, const double* rtol_v, double rtol_s,
-                    const double* atol_v, double atol_s, const SegTable& st, double* out_sumsq, double* out_bad, double* ws,
-                    hipStream_t s) {
+                    const double* atol_v, double atol_s, const NormSetup& ns, double* out_sumsq, double* out_bad) {
     InitVecArgs<T> a;
     a.a = static_cast<const T*>(a_);
     a.b = static_cast<const T*>(b_);
@@ -642,150 +639,92 @@ int launch_init_vec(int mode, const void* a_, const void* b_, const void* y_, co
     a.atol_v = atol_v;
     a.rtol_s = rtol_s;
     a.atol_s = atol_s;
-    a.st = st;
-    a.part0 = ws;
-    a.part1 = ws + st.n_chunks;
-    a.part_bad = ws + 2 * st.n_chunks;
-    const dim3 g((unsigned)st.n_chunks), b(kBlock);
-    if (mode == 0) hipLaunchKernelGGL((init_norms_vec_kernel<T, 0>), g, b, 0, s, a);
-    else hipLaunchKernelGGL((init_norms_vec_kernel<T, 1>), g, b, 0, s, a);
-    const int e = check_launch();
-    if (e) return e;
-    return launch_finalize(st, ws, mode == 0 ? 2 : 1, out_sumsq, out_bad, s);
+    a.st = ns.st;
+    a.part0 = ns.ws;
+    a.part1 = ns.ws + ns.st.n_chunks;
+    a.part_bad = ns.ws + 2 * ns.st.n_chunks;
+    const dim3 g((unsigned)ns.st.n_chunks), b(kBlock);
+    flag(mode != 0, [&](auto m) {
+        hipLaunchKernelGGL((init_norms_vec_kernel<T, decltype(m)::value ? 1 : 0>), g, b, 0, ns.s, a);
+        return 0;
+    });
+    return finish_norm(ns, mode == 0 ? 2 : 1, out_sumsq, out_bad);
 }
 
 // ---- complex states: the norm launches (tdeq_kernels_complex.hpp); T = the real type -------------------------------
 template <typename T, int NT, bool PARTIAL>
 int launch_cplx_error(const void* partial, void* scaled, const void* y0, const void* y1, const void* const* k,
-                      const double* coef, double dt, const SegTable& st, double* out_sumsq, double* out_bad, double* ws,
-                      const CtrlBundle* cb, hipStream_t s) {
+                      const double* coef, double dt, const NormSetup& ns, double* out_sumsq, double* out_bad,
+                      const CtrlBundle* cb) {
     CplxErrArgs<T, NT> a;
     a.partial = static_cast<const T*>(partial);
     a.scaled = static_cast<T*>(scaled);
     a.y0 = static_cast<const T*>(y0);
     a.y1 = static_cast<const T*>(y1);
-    bool vec = aligned16(y0) && aligned16(y1) && (!PARTIAL || aligned16(partial)) && (!scaled || aligned16(scaled));
     const bool dev_dt = cb && cb->state_in_dev;
-    const T dtT = (T)dt;
-    a.k[0] = nullptr;
-    a.c[0] = (T)0;
-    for (int j = 0; j < NT; ++j) {
-        a.k[j] = static_cast<const T*>(k[j]);
-        a.c[j] = dev_dt ? (T)coef[j] : (T)coef[j] * dtT;
-        vec = vec && aligned16(k[j]);
-    }
+    const bool vec = fill_terms<T, NT>(a.k, a.c, k, coef, dt, dev_dt) && all_aligned(y0, y1, scaled) &&
+                     (!PARTIAL || aligned16(partial));
     a.dt_dev = dev_dt ? cb->ctrl_dev + 1 : nullptr;
-    a.st = st;
-    a.part_sumsq = ws;
-    a.part_bad = ws + 2 * st.n_chunks;
-    const dim3 g((unsigned)st.n_chunks), b(kBlock);
-    if (scaled) {
-        if (vec) hipLaunchKernelGGL((cplx_error_norm_kernel<T, NT, true, PARTIAL, true>), g, b, 0, s, a);
-        else hipLaunchKernelGGL((cplx_error_norm_kernel<T, NT, false, PARTIAL, true>), g, b, 0, s, a);
-    } else {
-        if (vec) hipLaunchKernelGGL((cplx_error_norm_kernel<T, NT, true, PARTIAL, false>), g, b, 0, s, a);
-        else hipLaunchKernelGGL((cplx_error_norm_kernel<T, NT, false, PARTIAL, false>), g, b, 0, s, a);
-    }
-    const int e = check_launch();
-    if (e) return e;
-    if (cb) return launch_finalize_ctrl(st, ws, out_sumsq, out_bad, *cb, sizeof(T) == 4 ? 1 : 0, s, -1);
-    return launch_finalize(st, ws, 1, out_sumsq, out_bad, s);
+    a.st = ns.st;
+    a.part_sumsq = ns.ws;
+    a.part_bad = ns.ws + 2 * ns.st.n_chunks;
+    const dim3 g((unsigned)ns.st.n_chunks), b(kBlock);
+    flags(vec, scaled != nullptr, [&](auto v, auto sc) {
+        hipLaunchKernelGGL((cplx_error_norm_kernel<T, NT, decltype(v)::value, PARTIAL, decltype(sc)::value>), g, b, 0, ns.s, a);
+        return 0;
+    });
+    return finish_norm(ns, 1, out_sumsq, out_bad, cb, kTkind<T>);
 }
 
+// mode 0 / 1; out0 given: the quotients are stored (tdeq_init_scaled: no workspace, no sums), else their sums
+// (tdeq_init_norms)
 template <typename T>
-int dispatch_cplx_error(void* scaled, const void* y0, const void* y1, const void* const* k, const double* coef, int nt,
-                        double dt, const SegTable& st, double* out_sumsq, double* out_bad, double* ws, hipStream_t s) {
-    switch (nt) {
-#define TDEQ_CASE(N) case N: return launch_cplx_error<T, N, false>(nullptr, scaled, y0, y1, k, coef, dt, st, out_sumsq, out_bad, ws, nullptr, s);
-        TDEQ_CASE(1) TDEQ_CASE(2) TDEQ_CASE(3) TDEQ_CASE(4) TDEQ_CASE(5) TDEQ_CASE(6) TDEQ_CASE(7)
-        TDEQ_CASE(8) TDEQ_CASE(9) TDEQ_CASE(10) TDEQ_CASE(11) TDEQ_CASE(12) TDEQ_CASE(13) TDEQ_CASE(14)
-#undef TDEQ_CASE
-    }
-    return TDEQ_EINVAL;
-}
-
-template <typename T>
-int dispatch_cplx_error_partial(const void* partial, const void* y0, const void* y1, const void* const* k,
-                                const double* coef, int nt, double dt, const SegTable& st, double* out_sumsq,
-                                double* out_bad, double* ws, const CtrlBundle* cb, hipStream_t s) {
-    switch (nt) {
-        case 0: return launch_cplx_error<T, 0, true>(partial, nullptr, y0, y1, k, coef, dt, st, out_sumsq, out_bad, ws, cb, s);
-        case 1: return launch_cplx_error<T, 1, true>(partial, nullptr, y0, y1, k, coef, dt, st, out_sumsq, out_bad, ws, cb, s);
-        case 2: return launch_cplx_error<T, 2, true>(partial, nullptr, y0, y1, k, coef, dt, st, out_sumsq, out_bad, ws, cb, s);
-    }
-    return TDEQ_EINVAL;
-}
-
-// mode 0 / 1; out0 given: the quotients are stored (tdeq_init_scaled), else their sums (tdeq_init_norms)
-template <typename T>
-int launch_cplx_init(int mode, const void* a_, const void* b_, const void* y_, const SegTable& st, double* out_sumsq,
-                     double* out_bad, double* ws, void* out0, void* out1, hipStream_t s) {
+int launch_cplx_init(int mode, const void* a_, const void* b_, const void* y_, const NormSetup& ns, double* out_sumsq,
+                     double* out_bad, void* out0, void* out1) {
     CplxInitArgs<T> a;
     a.a = static_cast<const T*>(a_);
     a.b = static_cast<const T*>(b_);
     a.y = static_cast<const T*>(y_);
-    a.st = st;
-    a.part0 = ws;
-    a.part1 = ws ? ws + st.n_chunks : nullptr;
-    a.part_bad = ws ? ws + 2 * st.n_chunks : nullptr;
+    a.st = ns.st;
+    a.part0 = ns.ws;
+    a.part1 = ns.ws ? ns.ws + ns.st.n_chunks : nullptr;
+    a.part_bad = ns.ws ? ns.ws + 2 * ns.st.n_chunks : nullptr;
     a.out0 = static_cast<T*>(out0);
     a.out1 = static_cast<T*>(out1);
-    const dim3 g((unsigned)st.n_chunks), b(kBlock);
-    if (out0) {
-        if (mode == 0) hipLaunchKernelGGL((cplx_init_norms_kernel<T, 0, true>), g, b, 0, s, a);
-        else hipLaunchKernelGGL((cplx_init_norms_kernel<T, 1, true>), g, b, 0, s, a);
-        return check_launch();
-    }
-    if (mode == 0) hipLaunchKernelGGL((cplx_init_norms_kernel<T, 0, false>), g, b, 0, s, a);
-    else hipLaunchKernelGGL((cplx_init_norms_kernel<T, 1, false>), g, b, 0, s, a);
-    const int e = check_launch();
-    if (e) return e;
-    return launch_finalize(st, ws, mode == 0 ? 2 : 1, out_sumsq, out_bad, s);
+    const dim3 g((unsigned)ns.st.n_chunks), b(kBlock);
+    flags(mode != 0, out0 != nullptr, [&](auto m, auto o) {
+        hipLaunchKernelGGL((cplx_init_norms_kernel<T, decltype(m)::value ? 1 : 0, decltype(o)::value>), g, b, 0, ns.s, a);
+        return 0;
+    });
+    if (out0) return check_launch();
+    return finish_norm(ns, mode == 0 ? 2 : 1, out_sumsq, out_bad);
 }
 
 // ---- dense output ----------------------------------------------------------------------------------
-template <typename T, int NT, bool FIT_ONLY>
-int launch_dense(void* out, const void* y0, const void* y1, const void* f0, const void* f1,
-                 const void* const* k, const double* coef, double dt, double x, int64_t n, hipStream_t s) {
-    DenseArgs<T, NT> a;
+// the argument block of the dense-output kernels (c_j = dt * c_mid_j); returns the 16-byte decision of its pointers
+template <typename T, int NT>
+bool fill_dense(DenseArgs<T, NT>& a, void* out, const void* y0, const void* y1, const void* f0, const void* f1,
+                const void* const* k, const double* coef, double dt, double x, int64_t n) {
     a.out = static_cast<T*>(out);
     a.y0 = static_cast<const T*>(y0);
     a.y1 = static_cast<const T*>(y1);
     a.f0 = static_cast<const T*>(f0);
     a.f1 = static_cast<const T*>(f1);
-    bool vec = aligned16(out) && aligned16(y0) && aligned16(y1) && aligned16(f0) && aligned16(f1);
-    const T dtT = (T)dt;
-    for (int j = 0; j < NT; ++j) {
-        a.k[j] = static_cast<const T*>(k[j]);
-        a.c[j] = (T)coef[j] * dtT;   // dt * mid — rk_common.py:365-366
-        vec = vec && aligned16(k[j]);
-    }
-    a.dt = dtT;
+    a.dt = (T)dt;
     a.x = (T)x;
     a.n = n;
-    constexpr int L = VecOf<T>::L;
-    if (FIT_ONLY) vec = vec && (n % L == 0);   // the 5 coefficient planes must stay 16-byte aligned
-    if (vec) {
-        const unsigned g = stream_grid(n / L, kBlock);
-        hipLaunchKernelGGL((dense_kernel<T, NT, FIT_ONLY, true>), dim3(g), dim3(kBlock), 0, s, a);
-    } else {
-        const unsigned g = stream_grid(n, kBlock);
-        hipLaunchKernelGGL((dense_kernel<T, NT, FIT_ONLY, false>), dim3(g), dim3(kBlock), 0, s, a);
-    }
-    return check_launch();
+    return fill_terms<T, NT>(a.k, a.c, k, coef, dt, false) && all_aligned(out, y0, y1, f0, f1);
 }
 
-template <typename T, bool FIT_ONLY>
-int dispatch_dense(void* out, const void* y0, const void* y1, const void* f0, const void* f1,
-                   const void* const* k, const double* coef, int nt, double dt, double x, int64_t n,
-                   hipStream_t s) {
-    switch (nt) {
-#define TDEQ_CASE(N) case N: return launch_dense<T, N, FIT_ONLY>(out, y0, y1, f0, f1, k, coef, dt, x, n, s);
-        TDEQ_CASE(1) TDEQ_CASE(2) TDEQ_CASE(3) TDEQ_CASE(4) TDEQ_CASE(5) TDEQ_CASE(6) TDEQ_CASE(7)
-        TDEQ_CASE(8) TDEQ_CASE(9) TDEQ_CASE(10) TDEQ_CASE(11) TDEQ_CASE(12) TDEQ_CASE(13) TDEQ_CASE(14)
-#undef TDEQ_CASE
-    }
-    return TDEQ_EINVAL;
+template <typename T, int NT, bool FIT_ONLY>
+int launch_dense(void* out, const void* y0, const void* y1, const void* f0, const void* f1,
+                 const void* const* k, const double* coef, double dt, double x, int64_t n, hipStream_t s) {
+    DenseArgs<T, NT> a;
+    bool vec = fill_dense(a, out, y0, y1, f0, f1, k, coef, dt, x, n);
+    if (FIT_ONLY) vec = vec && (n % VecOf<T>::L == 0);   // the 5 coefficient planes must stay 16-byte aligned
+    return stream_launch<T>(vec, n, [&](auto v, dim3 g) {
+        hipLaunchKernelGGL((dense_kernel<T, NT, FIT_ONLY, decltype(v)::value>), g, dim3(kBlock), 0, s, a);
+    });
 }
 
 template <typename T, int NT>
@@ -793,82 +732,35 @@ int launch_dense_multi(void* out, int64_t out_stride, const void* y0, const void
                        const void* const* k, const double* coef, double dt, const double* x, int n_x, int64_t n,
                        hipStream_t s) {
     DenseMultiArgs<T, NT> a;
-    a.d.out = static_cast<T*>(out);
-    a.d.y0 = static_cast<const T*>(y0);
-    a.d.y1 = static_cast<const T*>(y1);
-    a.d.f0 = static_cast<const T*>(f0);
-    a.d.f1 = static_cast<const T*>(f1);
-    bool vec = aligned16(out) && aligned16(y0) && aligned16(y1) && aligned16(f0) && aligned16(f1);
-    const T dtT = (T)dt;
-    for (int j = 0; j < NT; ++j) {
-        a.d.k[j] = static_cast<const T*>(k[j]);
-        a.d.c[j] = (T)coef[j] * dtT;
-        vec = vec && aligned16(k[j]);
-    }
-    a.d.dt = dtT;
-    a.d.x = (T)0;
-    a.d.n = n;
+    bool vec = fill_dense(a.d, out, y0, y1, f0, f1, k, coef, dt, 0.0, n);
     for (int r = 0; r < kMaxDenseOutputs; ++r) a.xs[r] = r < n_x ? (T)x[r] : (T)0;
     a.m = n_x;
     a.out_stride = out_stride;
     vec = vec && (n_x == 1 || (out_stride * (int64_t)sizeof(T)) % 16 == 0);   // every output row 16-byte aligned
-    constexpr int L = VecOf<T>::L;
-    if (vec) hipLaunchKernelGGL((dense_multi_kernel<T, NT, true>), dim3(stream_grid(n / L, kBlock)), dim3(kBlock), 0, s, a);
-    else hipLaunchKernelGGL((dense_multi_kernel<T, NT, false>), dim3(stream_grid(n, kBlock)), dim3(kBlock), 0, s, a);
-    return check_launch();
-}
-
-template <typename T>
-int dispatch_dense_multi(void* out, int64_t out_stride, const void* y0, const void* y1, const void* f0,
-                         const void* f1, const void* const* k, const double* coef, int nt, double dt,
-                         const double* x, int n_x, int64_t n, hipStream_t s) {
-    switch (nt) {
-#define TDEQ_CASE(N) case N: return launch_dense_multi<T, N>(out, out_stride, y0, y1, f0, f1, k, coef, dt, x, n_x, n, s);
-        TDEQ_CASE(1) TDEQ_CASE(2) TDEQ_CASE(3) TDEQ_CASE(4) TDEQ_CASE(5) TDEQ_CASE(6) TDEQ_CASE(7)
-        TDEQ_CASE(8) TDEQ_CASE(9) TDEQ_CASE(10) TDEQ_CASE(11) TDEQ_CASE(12) TDEQ_CASE(13) TDEQ_CASE(14)
-#undef TDEQ_CASE
-    }
-    return TDEQ_EINVAL;
+    return stream_launch<T>(vec, n, [&](auto v, dim3 g) {
+        hipLaunchKernelGGL((dense_multi_kernel<T, NT, decltype(v)::value>), g, dim3(kBlock), 0, s, a);
+    });
 }
 
 // ---- rk4 / lerp ------------------------------------------------------------------------------------
+// (a stage reads k1..k<STAGE>: the entry points have checked those)
 template <typename T, int STAGE>
-int launch_rk4(void* out, const void* y0, const void* k1, const void* k2, const void* k3,
-               const void* k4, double dt, int64_t n, hipStream_t s, const double* dt_dev = nullptr) {
+int launch_rk4(void* out, const void* y0, const void* const (&ks)[4], double dt, int64_t n, hipStream_t s,
+               const double* dt_dev = nullptr) {
     Rk4Args<T> a;
     a.dt_dev = dt_dev;
     a.out = static_cast<T*>(out);
     a.y0 = static_cast<const T*>(y0);
-    a.k1 = static_cast<const T*>(k1);
-    a.k2 = static_cast<const T*>(k2);
-    a.k3 = static_cast<const T*>(k3);
-    a.k4 = static_cast<const T*>(k4);
+    a.k1 = static_cast<const T*>(ks[0]);
+    a.k2 = static_cast<const T*>(ks[1]);
+    a.k3 = static_cast<const T*>(ks[2]);
+    a.k4 = static_cast<const T*>(ks[3]);
     a.dt = (T)dt;
     a.third = (T)(1.0 / 3.0);   // `_one_third` rounded to T — rk_common.py:94,114-115
     a.n = n;
-    bool vec = aligned16(out) && aligned16(y0) && aligned16(k1);
-    if (STAGE >= 2) vec = vec && aligned16(k2);
-    if (STAGE >= 3) vec = vec && aligned16(k3);
-    if (STAGE >= 4) vec = vec && aligned16(k4);
-    constexpr int L = VecOf<T>::L;
-    if (vec) {
-        hipLaunchKernelGGL((rk4_kernel<T, STAGE, true>), dim3(stream_grid(n / L, kBlock)), dim3(kBlock), 0, s, a);
-    } else {
-        hipLaunchKernelGGL((rk4_kernel<T, STAGE, false>), dim3(stream_grid(n, kBlock)), dim3(kBlock), 0, s, a);
-    }
-    return check_launch();
-}
-
-template <typename T>
-int dispatch_rk4(int stage, void* out, const void* y0, const void* k1, const void* k2, const void* k3,
-                 const void* k4, double dt, int64_t n, hipStream_t s, const double* dt_dev = nullptr) {
-    switch (stage) {
-        case 1: return k1 ? launch_rk4<T, 1>(out, y0, k1, k2, k3, k4, dt, n, s, dt_dev) : TDEQ_EINVAL;
-        case 2: return (k1 && k2) ? launch_rk4<T, 2>(out, y0, k1, k2, k3, k4, dt, n, s, dt_dev) : TDEQ_EINVAL;
-        case 3: return (k1 && k2 && k3) ? launch_rk4<T, 3>(out, y0, k1, k2, k3, k4, dt, n, s, dt_dev) : TDEQ_EINVAL;
-        case 4: return (k1 && k2 && k3 && k4) ? launch_rk4<T, 4>(out, y0, k1, k2, k3, k4, dt, n, s, dt_dev) : TDEQ_EINVAL;
-    }
-    return TDEQ_EINVAL;
+    return stream_launch<T>(all_aligned(out, y0, Ptrs{ks, STAGE}), n, [&](auto v, dim3 g) {
+        hipLaunchKernelGGL((rk4_kernel<T, STAGE, decltype(v)::value>), g, dim3(kBlock), 0, s, a);
+    });
 }
 
 template <typename T>
@@ -893,12 +785,9 @@ int launch_lerp(void* out, const void* y0, const void* y1, double slope, int64_t
     a.y1 = static_cast<const T*>(y1);
     a.slope = (T)slope;
     a.n = n;
-    constexpr int L = VecOf<T>::L;
-    if (aligned16(out) && aligned16(y0) && aligned16(y1))
-        hipLaunchKernelGGL((lerp_kernel<T, true>), dim3(stream_grid(n / L, kBlock)), dim3(kBlock), 0, s, a);
-    else
-        hipLaunchKernelGGL((lerp_kernel<T, false>), dim3(stream_grid(n, kBlock)), dim3(kBlock), 0, s, a);
-    return check_launch();
+    return stream_launch<T>(all_aligned(out, y0, y1), n, [&](auto v, dim3 g) {
+        hipLaunchKernelGGL((lerp_kernel<T, decltype(v)::value>), g, dim3(kBlock), 0, s, a);
+    });
 }
 
 // ---- low-order fixed-grid stages / weighted sums -----------------------------------------------------
@@ -909,33 +798,16 @@ int launch_fixed(void* out, const void* y0, const void* const* k, const double* 
     a.dt_dev = dt_dev;
     a.out = static_cast<T*>(out);
     a.y0 = static_cast<const T*>(y0);
-    bool vec = aligned16(out) && (MODE == 2 || aligned16(y0));
     for (int j = 0; j < NT; ++j) {
         a.k[j] = static_cast<const T*>(k[j]);
         a.w[j] = (T)w[j];   // Python-float weights meet a T tensor: rounded to T (rk_common.py:139-157)
-        vec = vec && aligned16(k[j]);
     }
     a.dt = (T)dt;
     a.n = n;
-    constexpr int L = VecOf<T>::L;
-    if (vec) hipLaunchKernelGGL((fixed_stage_kernel<T, NT, MODE, true>), dim3(stream_grid(n / L, kBlock)), dim3(kBlock), 0, s, a);
-    else hipLaunchKernelGGL((fixed_stage_kernel<T, NT, MODE, false>), dim3(stream_grid(n, kBlock)), dim3(kBlock), 0, s, a);
-    return check_launch();
-}
-
-template <typename T, int MODE>
-int dispatch_fixed(void* out, const void* y0, const void* const* k, const double* w, int nt, double dt,
-                   int64_t n, hipStream_t s, const double* dt_dev = nullptr) {
-    switch (nt) {
-#define TDEQ_CASE(N) case N: return launch_fixed<T, N, MODE>(out, y0, k, w, dt, n, s, dt_dev);
-        TDEQ_CASE(1) TDEQ_CASE(2) TDEQ_CASE(3) TDEQ_CASE(4)
-        case 5: if (MODE == 2) return launch_fixed<T, 5, MODE>(out, y0, k, w, dt, n, s); break;
-        case 6: if (MODE == 2) return launch_fixed<T, 6, MODE>(out, y0, k, w, dt, n, s); break;
-        case 7: if (MODE == 2) return launch_fixed<T, 7, MODE>(out, y0, k, w, dt, n, s); break;
-        case 8: if (MODE == 2) return launch_fixed<T, 8, MODE>(out, y0, k, w, dt, n, s); break;
-#undef TDEQ_CASE
-    }
-    return TDEQ_EINVAL;
+    const bool vec = all_aligned(out, Ptrs{k, NT}) && (MODE == 2 || aligned16(y0));
+    return stream_launch<T>(vec, n, [&](auto v, dim3 g) {
+        hipLaunchKernelGGL((fixed_stage_kernel<T, NT, MODE, decltype(v)::value>), g, dim3(kBlock), 0, s, a);
+    });
 }
 
 // ---- backward helpers: scale_many / multi_dot ------------------------------------------------------------
@@ -943,28 +815,14 @@ template <typename T, int NT>
 int launch_scale(void* const* outs, const void* g, const double* w, int64_t n, hipStream_t s) {
     ScaleArgs<T, NT> a;
     a.g = static_cast<const T*>(g);
-    bool vec = aligned16(g);
     for (int j = 0; j < NT; ++j) {
         a.out[j] = static_cast<T*>(outs[j]);
         a.w[j] = (T)w[j];
-        vec = vec && aligned16(outs[j]);
     }
     a.n = n;
-    constexpr int L = VecOf<T>::L;
-    if (vec) hipLaunchKernelGGL((scale_many_kernel<T, NT, true>), dim3(stream_grid(n / L, kBlock)), dim3(kBlock), 0, s, a);
-    else hipLaunchKernelGGL((scale_many_kernel<T, NT, false>), dim3(stream_grid(n, kBlock)), dim3(kBlock), 0, s, a);
-    return check_launch();
-}
-
-template <typename T>
-int dispatch_scale(void* const* outs, const void* g, const double* w, int nt, int64_t n, hipStream_t s) {
-    switch (nt) {
-#define TDEQ_CASE(N) case N: return launch_scale<T, N>(outs, g, w, n, s);
-        TDEQ_CASE(1) TDEQ_CASE(2) TDEQ_CASE(3) TDEQ_CASE(4) TDEQ_CASE(5) TDEQ_CASE(6) TDEQ_CASE(7)
-        TDEQ_CASE(8) TDEQ_CASE(9) TDEQ_CASE(10) TDEQ_CASE(11) TDEQ_CASE(12) TDEQ_CASE(13) TDEQ_CASE(14)
-#undef TDEQ_CASE
-    }
-    return TDEQ_EINVAL;
+    return stream_launch<T>(all_aligned(g, Ptrs{outs, NT}), n, [&](auto v, dim3 grid) {
+        hipLaunchKernelGGL((scale_many_kernel<T, NT, decltype(v)::value>), grid, dim3(kBlock), 0, s, a);
+    });
 }
 
 constexpr int64_t kDotChunk = 4096;
@@ -973,20 +831,17 @@ template <typename T, int NT>
 int launch_dots(const void* g, const void* const* x, int64_t n, double* out, double* ws, hipStream_t s) {
     DotArgs<T, NT> a;
     a.g = static_cast<const T*>(g);
-    bool vec = aligned16(g);
-    for (int j = 0; j < NT; ++j) {
-        a.x[j] = static_cast<const T*>(x[j]);
-        vec = vec && aligned16(x[j]);
-    }
+    for (int j = 0; j < NT; ++j) a.x[j] = static_cast<const T*>(x[j]);
     a.n = n;
     a.chunk = kDotChunk;
     a.n_chunks = (n + kDotChunk - 1) / kDotChunk;
     if (a.n_chunks < 1) a.n_chunks = 1;
     a.part = ws;
     const dim3 grid((unsigned)a.n_chunks), blk(kBlock);
-    if (vec) hipLaunchKernelGGL((multi_dot_kernel<T, NT, true>), grid, blk, 0, s, a);
-    else hipLaunchKernelGGL((multi_dot_kernel<T, NT, false>), grid, blk, 0, s, a);
-    const int e = check_launch();
+    const int e = flag(all_aligned(g, Ptrs{x, NT}), [&](auto v) {
+        hipLaunchKernelGGL((multi_dot_kernel<T, NT, decltype(v)::value>), grid, blk, 0, s, a);
+        return check_launch();
+    });
     if (e) return e;
     DotFinalizeArgs f;
     f.part = ws;
@@ -994,17 +849,6 @@ int launch_dots(const void* g, const void* const* x, int64_t n, double* out, dou
     f.out = out;
     hipLaunchKernelGGL(dot_finalize_kernel, dim3(NT), dim3(kBlock), 0, s, f);
     return check_launch();
-}
-
-template <typename T>
-int dispatch_dots(const void* g, const void* const* x, int nt, int64_t n, double* out, double* ws, hipStream_t s) {
-    switch (nt) {
-#define TDEQ_CASE(N) case N: return launch_dots<T, N>(g, x, n, out, ws, s);
-        TDEQ_CASE(1) TDEQ_CASE(2) TDEQ_CASE(3) TDEQ_CASE(4) TDEQ_CASE(5) TDEQ_CASE(6) TDEQ_CASE(7)
-        TDEQ_CASE(8) TDEQ_CASE(9) TDEQ_CASE(10) TDEQ_CASE(11) TDEQ_CASE(12) TDEQ_CASE(13) TDEQ_CASE(14)
-#undef TDEQ_CASE
-    }
-    return TDEQ_EINVAL;
 }
 
 template <typename T>
@@ -1032,43 +876,25 @@ int launch_adams_predict(void* y_out, void* dy_out, void* delta_out, const void*
     a.dy_out = static_cast<T*>(dy_out);
     a.delta_out = static_cast<T*>(delta_out);
     a.y0 = static_cast<const T*>(y0);
-    bool vec = aligned16(y_out) && aligned16(y0) && aligned16(dy_out) && aligned16(delta_out);
     for (int j = 0; j < NT; ++j) {
         a.f[j] = static_cast<const T*>(f[j]);
         a.cb[j] = (T)cb[j];
         a.cm[j] = implicit ? (T)cm[j] : (T)0;
-        vec = vec && aligned16(f[j]);
     }
     a.dt = (T)dt;
     a.n = n;
-    constexpr int L = VecOf<T>::L;
-    const dim3 g(vec ? stream_grid(n / L, kBlock) : stream_grid(n, kBlock)), b(kBlock);
-    if (implicit) {
-        if (vec) hipLaunchKernelGGL((adams_predict_kernel<T, NT, true, true>), g, b, 0, s, a);
-        else hipLaunchKernelGGL((adams_predict_kernel<T, NT, true, false>), g, b, 0, s, a);
-    } else {
-        if (vec) hipLaunchKernelGGL((adams_predict_kernel<T, NT, false, true>), g, b, 0, s, a);
-        else hipLaunchKernelGGL((adams_predict_kernel<T, NT, false, false>), g, b, 0, s, a);
-    }
-    return check_launch();
-}
-
-template <typename T>
-int dispatch_adams_predict(void* y_out, void* dy_out, void* delta_out, const void* y0, const void* const* f,
-                           const double* cb, const double* cm, int nt, double dt, int64_t n, hipStream_t s) {
-    switch (nt) {
-#define TDEQ_CASE(N) case N: return launch_adams_predict<T, N>(y_out, dy_out, delta_out, y0, f, cb, cm, dt, n, s);
-        TDEQ_CASE(1) TDEQ_CASE(2) TDEQ_CASE(3) TDEQ_CASE(4) TDEQ_CASE(5) TDEQ_CASE(6) TDEQ_CASE(7)
-        TDEQ_CASE(8) TDEQ_CASE(9) TDEQ_CASE(10) TDEQ_CASE(11) TDEQ_CASE(12) TDEQ_CASE(13) TDEQ_CASE(14)
-#undef TDEQ_CASE
-    }
-    return TDEQ_EINVAL;
+    return stream_launch<T>(all_aligned(y_out, y0, dy_out, delta_out, Ptrs{f, NT}), n, [&](auto v, dim3 g) {
+        flag(implicit, [&](auto im) {
+            hipLaunchKernelGGL((adams_predict_kernel<T, NT, decltype(im)::value, decltype(v)::value>), g, dim3(kBlock), 0, s, a);
+            return 0;
+        });
+    });
 }
 
 template <typename T>
 int launch_adams_correct(void* y_out, void* dy_out, const void* f, const void* delta, const void* dy_old,
-                         const void* y0, double c, bool compute, const SegTable& st, int64_t n, double* out_count,
-                         double* out_bad, double* ws, hipStream_t s) {
+                         const void* y0, double c, bool compute, const NormSetup& ns, int64_t n, double* out_count,
+                         double* out_bad) {
     AdamsCorrectArgs<T> a;
     a.y_out = static_cast<T*>(y_out);
     a.dy_out = static_cast<T*>(dy_out);
@@ -1078,31 +904,26 @@ int launch_adams_correct(void* y_out, void* dy_out, const void* f, const void* d
     a.y0 = static_cast<const T*>(y0);
     a.c = (T)c;
     a.n = n;
-    a.st = st;
-    a.part_count = ws;
-    a.part_bad = ws + 2 * st.n_chunks;
-    const bool vec = aligned16(y_out) && aligned16(dy_out) && aligned16(f) && aligned16(delta) && aligned16(dy_old) &&
-                     aligned16(y0);
-    const dim3 g((unsigned)st.n_chunks), b(kBlock);
-    if (compute) {
-        if (vec) hipLaunchKernelGGL((adams_correct_kernel<T, true, true>), g, b, 0, s, a);
-        else hipLaunchKernelGGL((adams_correct_kernel<T, true, false>), g, b, 0, s, a);
-    } else {
-        if (vec) hipLaunchKernelGGL((adams_correct_kernel<T, false, true>), g, b, 0, s, a);
-        else hipLaunchKernelGGL((adams_correct_kernel<T, false, false>), g, b, 0, s, a);
-    }
-    const int e = check_launch();
-    if (e) return e;
-    return launch_finalize(st, ws, 1, out_count, out_bad, s);
+    a.st = ns.st;
+    a.part_count = ns.ws;
+    a.part_bad = ns.ws + 2 * ns.st.n_chunks;
+    const dim3 g((unsigned)ns.st.n_chunks), b(kBlock);
+    flags(compute, all_aligned(y_out, dy_out, f, delta, dy_old, y0), [&](auto cp, auto v) {
+        hipLaunchKernelGGL((adams_correct_kernel<T, decltype(cp)::value, decltype(v)::value>), g, b, 0, ns.s, a);
+        return 0;
+    });
+    return finish_norm(ns, 1, out_count, out_bad);
 }
 
-inline bool bad_dtype(int dtype) { return dtype != TDEQ_F32 && dtype != TDEQ_F64; }
-// bfloat16 / float16 states: the entry points of the host-driven step (tdeq_kernels_lp.hpp; include/tdeq_hip.h lists them)
-inline bool lp_dtype(int dtype) { return dtype == TDEQ_BF16 || dtype == TDEQ_F16; }
-
 #include "tdeq_abi_lp.hpp"
-// the norm entry points also take interleaved complex states (TDEQ_C64 / TDEQ_C128: tdeq_kernels_complex.hpp)
-inline bool bad_norm_dtype(int dtype) { return bad_dtype(dtype) && dtype != TDEQ_C64 && dtype != TDEQ_C128; }
+
+// ---- what the entry points check before anything else -----------------------------------------------------------------
+// n_terms in [lo, hi] and every pointer of the array non-null
+inline int check_terms(const void* const* k, int n_terms, int lo, int hi = TDEQ_MAX_TERMS) {
+    if (n_terms < lo || n_terms > hi || (n_terms > 0 && !k)) return TDEQ_EINVAL;
+    for (int j = 0; j < n_terms; ++j) if (!k[j]) return TDEQ_EINVAL;
+    return 0;
+}
 
 }  // namespace
 
@@ -1117,42 +938,43 @@ size_t tdeq_workspace_bytes(int64_t n_chunks) {
 
 int tdeq_stage_combine(void* out, const void* y0, const void* const* k, const double* coef, int n_terms,
                        double dt, int64_t n, int dtype, void* stream) {
-    if (!out || !y0 || !k || !coef || n < 0 || (bad_dtype(dtype) && !lp_dtype(dtype))) return TDEQ_EINVAL;
-    if (n_terms < 1 || n_terms > TDEQ_MAX_TERMS) return TDEQ_EINVAL;
-    for (int j = 0; j < n_terms; ++j) if (!k[j]) return TDEQ_EINVAL;
+    if (!out || !y0 || !k || !coef || n < 0 || !state_dtype_ok(dtype)) return TDEQ_EINVAL;
+    if (const int e = check_terms(k, n_terms, 1)) return e;
     if (n == 0) return 0;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (dtype == TDEQ_BF16) return lp_dispatch_combine<lp::BF16, 1>(out, nullptr, y0, k, coef, nullptr, n_terms, dt, n, nullptr, nullptr, 0, s);
-    if (dtype == TDEQ_F16) return lp_dispatch_combine<lp::F16, 1>(out, nullptr, y0, k, coef, nullptr, n_terms, dt, n, nullptr, nullptr, 0, s);
-    return dtype == TDEQ_F32 ? dispatch_combine<float>(out, y0, k, coef, n_terms, dt, n, s)
-                             : dispatch_combine<double>(out, y0, k, coef, n_terms, dt, n, s);
+    return state_dtype_terms<1>(dtype, n_terms, [&](auto t, auto nt) {
+        using T = decltype(t);
+        constexpr int NT = decltype(nt)::value;
+        if constexpr (is_lp<T>) return lp_launch_combine<T, NT, 1>(out, nullptr, y0, k, coef, nullptr, dt, n, s);
+        else return launch_combine<T, NT>(out, y0, k, coef, dt, n, s);
+    });
 }
 
 int tdeq_stage_combine_timed(void* out, const void* y0, const void* const* k, const double* coef, int n_terms,
                              double dt, int64_t n, int dtype, void* stream, void* start_event, void* stop_event) {
-    if (!out || !y0 || !k || !coef || n < 1 || bad_dtype(dtype) || !start_event || !stop_event) return TDEQ_EINVAL;
-    if (n_terms < 1 || n_terms > TDEQ_MAX_TERMS) return TDEQ_EINVAL;
-    for (int j = 0; j < n_terms; ++j) if (!k[j]) return TDEQ_EINVAL;
+    if (!out || !y0 || !k || !coef || n < 1 || !real_dtype_ok(dtype) || !start_event || !stop_event) return TDEQ_EINVAL;
+    if (const int e = check_terms(k, n_terms, 1)) return e;
     hipStream_t s = static_cast<hipStream_t>(stream);
     hipEvent_t e0 = static_cast<hipEvent_t>(start_event), e1 = static_cast<hipEvent_t>(stop_event);
-    return dtype == TDEQ_F32 ? dispatch_combine<float>(out, y0, k, coef, n_terms, dt, n, s, e0, e1)
-                             : dispatch_combine<double>(out, y0, k, coef, n_terms, dt, n, s, e0, e1);
+    return real_dtype_terms<1>(dtype, n_terms, [&](auto t, auto nt) {
+        return launch_combine<decltype(t), decltype(nt)::value>(out, y0, k, coef, dt, n, s, e0, e1);
+    });
 }
 
 int tdeq_stage_combine_fill(void* out, const void* y0, const void* const* k, const double* coef, int n_terms,
                             double dt, int64_t n, int dtype, void* fill_dst, const double* fill_vals, int n_fill,
                             void* stream) {
-    if (!out || !y0 || !k || !coef || n < 1 || (bad_dtype(dtype) && !lp_dtype(dtype))) return TDEQ_EINVAL;
-    if (n_terms < 1 || n_terms > 2 || !k[0] || (n_terms == 2 && !k[1])) return TDEQ_EINVAL;
+    if (!out || !y0 || !k || !coef || n < 1 || !state_dtype_ok(dtype)) return TDEQ_EINVAL;
+    if (const int e = check_terms(k, n_terms, 1, 2)) return e;
     if (!fill_dst || !fill_vals || n_fill < 1 || n_fill > 16) return TDEQ_EINVAL;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (dtype == TDEQ_BF16) return lp_dispatch_combine<lp::BF16, 1>(out, nullptr, y0, k, coef, nullptr, n_terms, dt, n, fill_dst, fill_vals, n_fill, s);
-    if (dtype == TDEQ_F16) return lp_dispatch_combine<lp::F16, 1>(out, nullptr, y0, k, coef, nullptr, n_terms, dt, n, fill_dst, fill_vals, n_fill, s);
-    if (dtype == TDEQ_F32)
-        return n_terms == 1 ? launch_combine_fill<float, 1>(out, y0, k, coef, dt, n, fill_dst, fill_vals, n_fill, s)
-                            : launch_combine_fill<float, 2>(out, y0, k, coef, dt, n, fill_dst, fill_vals, n_fill, s);
-    return n_terms == 1 ? launch_combine_fill<double, 1>(out, y0, k, coef, dt, n, fill_dst, fill_vals, n_fill, s)
-                        : launch_combine_fill<double, 2>(out, y0, k, coef, dt, n, fill_dst, fill_vals, n_fill, s);
+    return state_dtype_terms<1, 2>(dtype, n_terms, [&](auto t, auto nt) {
+        using T = decltype(t);
+        constexpr int NT = decltype(nt)::value;
+        if constexpr (is_lp<T>)
+            return lp_launch_combine<T, NT, 1>(out, nullptr, y0, k, coef, nullptr, dt, n, s, nullptr, fill_dst, fill_vals, n_fill);
+        else return launch_combine_fill<T, NT>(out, y0, k, coef, dt, n, fill_dst, fill_vals, n_fill, s);
+    });
 }
 
 int tdeq_error_norm(void* scaled_out, const void* y0, const void* y1, const void* const* k,
@@ -1160,28 +982,39 @@ int tdeq_error_norm(void* scaled_out, const void* y0, const void* y1, const void
                     const void* segs_dev, int n_seg, int64_t chunk, int64_t n_chunks, double* out_sumsq,
                     double* out_nonfinite, void* workspace, size_t workspace_bytes, int dtype,
                     void* stream) {
-    if (!y0 || !y1 || !k || !coef || !out_sumsq || !out_nonfinite || !workspace || (bad_norm_dtype(dtype) && !lp_dtype(dtype)))
+    if (!y0 || !y1 || !k || !coef || !out_sumsq || !out_nonfinite || !workspace || !(state_dtype_ok(dtype) || cplx_dtype(dtype)))
         return TDEQ_EINVAL;
-    if (n_terms < 1 || n_terms > TDEQ_MAX_TERMS) return TDEQ_EINVAL;
-    for (int j = 0; j < n_terms; ++j) if (!k[j]) return TDEQ_EINVAL;
-    SegTable st;
-    const int e = fill_segtable(st, segs, segs_dev, n_seg, chunk, n_chunks);
-    if (e) return e;
-    if (workspace_bytes < tdeq_workspace_bytes(n_chunks)) return TDEQ_EWORKSPACE;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    double* ws = static_cast<double*>(workspace);
+    if (const int e = check_terms(k, n_terms, 1)) return e;
+    NormSetup ns;
+    if (const int e = norm_setup(ns, segs, segs_dev, n_seg, chunk, n_chunks, workspace, workspace_bytes, stream)) return e;
     // bf16 / fp16: out_sumsq[s] = sum of fl(|r|^2) — |r| itself for a one-element segment (tdeq_kernels_lp.hpp norm_term)
-    if (dtype == TDEQ_BF16)
-        return lp_dispatch_error<lp::BF16>(scaled_out, y0, y1, k, coef, n_terms, dt, st, out_sumsq, out_nonfinite, ws, s);
-    if (dtype == TDEQ_F16)
-        return lp_dispatch_error<lp::F16>(scaled_out, y0, y1, k, coef, n_terms, dt, st, out_sumsq, out_nonfinite, ws, s);
-    if (dtype == TDEQ_C64)
-        return dispatch_cplx_error<float>(scaled_out, y0, y1, k, coef, n_terms, dt, st, out_sumsq, out_nonfinite, ws, s);
-    if (dtype == TDEQ_C128)
-        return dispatch_cplx_error<double>(scaled_out, y0, y1, k, coef, n_terms, dt, st, out_sumsq, out_nonfinite, ws, s);
-    return dtype == TDEQ_F32
-               ? dispatch_error<float>(scaled_out, y0, y1, k, coef, n_terms, dt, st, out_sumsq, out_nonfinite, ws, s)
-               : dispatch_error<double>(scaled_out, y0, y1, k, coef, n_terms, dt, st, out_sumsq, out_nonfinite, ws, s);
+    return norm_dtype(dtype, [&](auto t, auto cplx) {
+        return terms<1>(n_terms, [&](auto nt) {
+            using T = decltype(t);
+            constexpr int NT = decltype(nt)::value;
+            if constexpr (is_lp<T>) return lp_launch_error<T, NT>(scaled_out, y0, y1, k, coef, dt, ns, out_sumsq, out_nonfinite);
+            else if constexpr (decltype(cplx)::value)
+                return launch_cplx_error<T, NT, false>(nullptr, scaled_out, y0, y1, k, coef, dt, ns, out_sumsq, out_nonfinite, nullptr);
+            else return launch_error<T, NT>(scaled_out, y0, y1, k, coef, dt, ns, out_sumsq, out_nonfinite);
+        });
+    });
+}
+
+// tdeq_error_norm_vec with an optional controller bundle (ctrl == nullptr: none)
+static int error_norm_vec_checked(const void* err_partial, const void* y0, const void* y1, const void* const* k,
+                                  const double* coef, int n_terms, double dt, const double* rtol_vec, double rtol_scalar,
+                                  const double* atol_vec, double atol_scalar, const tdeq_segment* segs, const void* segs_dev,
+                                  int n_seg, int64_t chunk, int64_t n_chunks, double* out_sumsq, double* out_nonfinite,
+                                  const CtrlBundle* cb, void* workspace, size_t workspace_bytes, int dtype, void* stream) {
+    if (!y0 || !y1 || !out_sumsq || !out_nonfinite || !workspace || !real_dtype_ok(dtype)) return TDEQ_EINVAL;
+    if (!rtol_vec && !atol_vec) return TDEQ_EINVAL;      // two 0-dim tolerances: tdeq_error_norm (a different promotion)
+    if ((n_terms > 0 && !coef) || check_terms(k, n_terms, err_partial ? 0 : 1)) return TDEQ_EINVAL;
+    NormSetup ns;
+    if (const int e = norm_setup(ns, segs, segs_dev, n_seg, chunk, n_chunks, workspace, workspace_bytes, stream)) return e;
+    return real_dtype_terms<0>(dtype, n_terms, [&](auto t, auto nt) {
+        return launch_error_vec<decltype(t), decltype(nt)::value>(err_partial, y0, y1, k, coef, dt, rtol_vec, rtol_scalar,
+                                                                  atol_vec, atol_scalar, ns, out_sumsq, out_nonfinite, cb);
+    });
 }
 
 int tdeq_error_norm_vec(const void* err_partial, const void* y0, const void* y1, const void* const* k, const double* coef,
@@ -1189,21 +1022,9 @@ int tdeq_error_norm_vec(const void* err_partial, const void* y0, const void* y1,
                         const tdeq_segment* segs, const void* segs_dev, int n_seg, int64_t chunk, int64_t n_chunks,
                         double* out_sumsq, double* out_nonfinite, void* workspace, size_t workspace_bytes, int dtype,
                         void* stream) {
-    if (!y0 || !y1 || !out_sumsq || !out_nonfinite || !workspace || bad_dtype(dtype)) return TDEQ_EINVAL;
-    if (!rtol_vec && !atol_vec) return TDEQ_EINVAL;      // two 0-dim tolerances: tdeq_error_norm (a different promotion)
-    if (n_terms < (err_partial ? 0 : 1) || n_terms > TDEQ_MAX_TERMS || (n_terms > 0 && (!k || !coef))) return TDEQ_EINVAL;
-    for (int j = 0; j < n_terms; ++j) if (!k[j]) return TDEQ_EINVAL;
-    SegTable st;
-    const int e = fill_segtable(st, segs, segs_dev, n_seg, chunk, n_chunks);
-    if (e) return e;
-    if (workspace_bytes < tdeq_workspace_bytes(n_chunks)) return TDEQ_EWORKSPACE;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    double* ws = static_cast<double*>(workspace);
-    return dtype == TDEQ_F32
-               ? dispatch_error_vec<float>(err_partial, y0, y1, k, coef, n_terms, dt, rtol_vec, rtol_scalar, atol_vec, atol_scalar, st,
-                                           out_sumsq, out_nonfinite, ws, s)
-               : dispatch_error_vec<double>(err_partial, y0, y1, k, coef, n_terms, dt, rtol_vec, rtol_scalar, atol_vec, atol_scalar, st,
-                                            out_sumsq, out_nonfinite, ws, s);
+    return error_norm_vec_checked(err_partial, y0, y1, k, coef, n_terms, dt, rtol_vec, rtol_scalar, atol_vec, atol_scalar, segs,
+                                  segs_dev, n_seg, chunk, n_chunks, out_sumsq, out_nonfinite, nullptr, workspace,
+                                  workspace_bytes, dtype, stream);
 }
 
 int tdeq_error_norm_vec_ctrl(const void* err_partial, const void* y0, const void* y1, const void* const* k,
@@ -1212,54 +1033,43 @@ int tdeq_error_norm_vec_ctrl(const void* err_partial, const void* y0, const void
                              double* out_sumsq, double* out_nonfinite, const tdeq_step_ctrl* ctrl, double* out_ctrl,
                              double* ctrl_dev, void* next_times, int state_in_dev, void* workspace, size_t workspace_bytes,
                              int dtype, void* stream) {
-    if (!y0 || !y1 || !out_sumsq || !out_nonfinite || !workspace || bad_dtype(dtype)) return TDEQ_EINVAL;
-    if ((!rtol_vec && !atol_vec) || !ctrl || !out_ctrl || !ctrl_dev || !next_times) return TDEQ_EINVAL;
-    if (n_terms < (err_partial ? 0 : 1) || n_terms > TDEQ_MAX_TERMS || (n_terms > 0 && (!k || !coef))) return TDEQ_EINVAL;
-    for (int j = 0; j < n_terms; ++j) if (!k[j]) return TDEQ_EINVAL;
-    if (ctrl->n_times < 1 || ctrl->n_times > TDEQ_MAX_STAGE_TIMES || ctrl->n_norm_seg < 0 || ctrl->n_norm_seg > n_seg)
-        return TDEQ_EINVAL;
-    SegTable st;
-    const int e = fill_segtable(st, segs, segs_dev, n_seg, chunk, n_chunks);
-    if (e) return e;
-    if (workspace_bytes < tdeq_workspace_bytes(n_chunks)) return TDEQ_EWORKSPACE;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    double* ws = static_cast<double*>(workspace);
-    const CtrlBundle cb{ctrl, out_ctrl, ctrl_dev, next_times, state_in_dev ? 1 : 0};
-    return dtype == TDEQ_F32
-               ? dispatch_error_vec<float>(err_partial, y0, y1, k, coef, n_terms, dt, rtol_vec, rtol_scalar, atol_vec, atol_scalar, st,
-                                           out_sumsq, out_nonfinite, ws, s, &cb)
-               : dispatch_error_vec<double>(err_partial, y0, y1, k, coef, n_terms, dt, rtol_vec, rtol_scalar, atol_vec, atol_scalar, st,
-                                            out_sumsq, out_nonfinite, ws, s, &cb);
+    CtrlBundle cb;
+    if (const int e = make_ctrl(cb, ctrl, out_ctrl, ctrl_dev, next_times, state_in_dev, n_seg)) return e;
+    return error_norm_vec_checked(err_partial, y0, y1, k, coef, n_terms, dt, rtol_vec, rtol_scalar, atol_vec, atol_scalar, segs,
+                                  segs_dev, n_seg, chunk, n_chunks, out_sumsq, out_nonfinite, &cb, workspace, workspace_bytes,
+                                  dtype, stream);
 }
 
 int tdeq_stage_combine_err(void* out, void* err_out, const void* y0, const void* const* k, const double* coef,
                            const double* err_coef, int n_terms, double dt, int64_t n, int dtype, void* stream) {
-    if (!out || !err_out || !y0 || !k || !coef || !err_coef || n < 0 || (bad_dtype(dtype) && !lp_dtype(dtype))) return TDEQ_EINVAL;
-    if (n_terms < 1 || n_terms > TDEQ_MAX_TERMS) return TDEQ_EINVAL;
-    for (int j = 0; j < n_terms; ++j) if (!k[j]) return TDEQ_EINVAL;
+    if (!out || !err_out || !y0 || !k || !coef || !err_coef || n < 0 || !state_dtype_ok(dtype)) return TDEQ_EINVAL;
+    if (const int e = check_terms(k, n_terms, 1)) return e;
     if (n == 0) return 0;
     hipStream_t s = static_cast<hipStream_t>(stream);
     // (bf16 / fp16: err_out is the row sum over THESE stages rounded once — a caller that continues it rounds twice)
-    if (dtype == TDEQ_BF16) return lp_dispatch_combine<lp::BF16, 2>(out, err_out, y0, k, coef, err_coef, n_terms, dt, n, nullptr, nullptr, 0, s);
-    if (dtype == TDEQ_F16) return lp_dispatch_combine<lp::F16, 2>(out, err_out, y0, k, coef, err_coef, n_terms, dt, n, nullptr, nullptr, 0, s);
-    return dtype == TDEQ_F32 ? dispatch_combine_err<float>(out, err_out, y0, k, coef, err_coef, n_terms, dt, n, s)
-                             : dispatch_combine_err<double>(out, err_out, y0, k, coef, err_coef, n_terms, dt, n, s);
+    return state_dtype_terms<1>(dtype, n_terms, [&](auto t, auto nt) {
+        using T = decltype(t);
+        constexpr int NT = decltype(nt)::value;
+        if constexpr (is_lp<T>) return lp_launch_combine<T, NT, 2>(out, err_out, y0, k, coef, err_coef, dt, n, s);
+        else return launch_combine_err<T, NT>(out, err_out, y0, k, coef, err_coef, dt, n, s);
+    });
 }
 
 static int combine_multi_checked(const tdeq_multi_out* outs, int n_out, const void* y0, const void* acc_in,
                                  const void* const* k, int n_terms, double dt, int64_t n, int dtype, void* stream,
                                  void* e0, void* e1, const double* dt_dev = nullptr) {
-    if (!outs || !y0 || !k || n < 0 || bad_dtype(dtype)) return TDEQ_EINVAL;
-    if (n_terms < 1 || n_terms > TDEQ_MAX_TERMS || n_out < 1 || n_out > TDEQ_MAX_MULTI_OUT) return TDEQ_EINVAL;
-    for (int j = 0; j < n_terms; ++j) if (!k[j]) return TDEQ_EINVAL;
+    if (!outs || !y0 || !k || n < 0 || !real_dtype_ok(dtype)) return TDEQ_EINVAL;
+    if (check_terms(k, n_terms, 1) || n_out < 1 || n_out > TDEQ_MAX_MULTI_OUT) return TDEQ_EINVAL;
     for (int o = 0; o < n_out; ++o) {
         if (!outs[o].out || outs[o].mask == 0u) return TDEQ_EINVAL;
         if (n_terms < 32 && (outs[o].mask >> n_terms) != 0u) return TDEQ_EINVAL;
     }
     if (n == 0) return 0;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    return dtype == TDEQ_F32 ? dispatch_combine_multi<float>(outs, n_out, y0, acc_in, k, n_terms, dt, n, s, static_cast<hipEvent_t>(e0), static_cast<hipEvent_t>(e1), dt_dev)
-                             : dispatch_combine_multi<double>(outs, n_out, y0, acc_in, k, n_terms, dt, n, s, static_cast<hipEvent_t>(e0), static_cast<hipEvent_t>(e1), dt_dev);
+    return real_dtype_terms<1>(dtype, n_terms, [&](auto t, auto nt) {
+        return launch_combine_multi<decltype(t), decltype(nt)::value>(outs, n_out, y0, acc_in, k, dt, n, s, static_cast<hipEvent_t>(e0),
+                                                                      static_cast<hipEvent_t>(e1), dt_dev);
+    });
 }
 
 int tdeq_stage_combine_multi(const tdeq_multi_out* outs, int n_out, const void* y0, const void* acc_in,
@@ -1281,28 +1091,46 @@ int tdeq_stage_combine_multi_timed(const tdeq_multi_out* outs, int n_out, const 
     return combine_multi_checked(outs, n_out, y0, acc_in, k, n_terms, dt, n, dtype, stream, start_event, stop_event);
 }
 
+// tdeq_error_norm_partial with an optional controller bundle.  fp32 / fp64 / complex continue err_partial with 0..2
+// terms.  bf16 / fp16 (with a bundle only): the WHOLE error row in one launch — a row is rounded once, so there is no
+// partial sum to continue: err_partial must be NULL and there is at least one term — then finalize + controller in the
+// state's type.
+static int error_norm_partial_checked(const void* err_partial, const void* y0, const void* y1, const void* const* k,
+                                      const double* coef, int n_terms, double dt, const tdeq_segment* segs,
+                                      const void* segs_dev, int n_seg, int64_t chunk, int64_t n_chunks, double* out_sumsq,
+                                      double* out_nonfinite, const CtrlBundle* cb, void* copy_last_k, void* workspace,
+                                      size_t workspace_bytes, int dtype, void* stream) {
+    const bool low = cb && lp_dtype(dtype);
+    if (copy_last_k && (low || cplx_dtype(dtype) || n_terms < 1)) return TDEQ_EINVAL;
+    if (!y0 || !y1 || !out_sumsq || !out_nonfinite || !workspace || !(low || real_dtype_ok(dtype) || cplx_dtype(dtype)))
+        return TDEQ_EINVAL;
+    if (low ? err_partial != nullptr : !err_partial) return TDEQ_EINVAL;
+    if ((n_terms > 0 && !coef) || check_terms(k, n_terms, low ? 1 : 0, low ? TDEQ_MAX_TERMS : 2)) return TDEQ_EINVAL;
+    NormSetup ns;
+    if (const int e = norm_setup(ns, segs, segs_dev, n_seg, chunk, n_chunks, workspace, workspace_bytes, stream)) return e;
+    return norm_dtype(dtype, [&](auto t, auto cplx) {
+        using T = decltype(t);
+        if constexpr (is_lp<T>)
+            return terms<1>(n_terms, [&](auto nt) {
+                return lp_launch_error<T, decltype(nt)::value>(nullptr, y0, y1, k, coef, dt, ns, out_sumsq, out_nonfinite, cb);
+            });
+        else
+            return terms<0, 2>(n_terms, [&](auto nt) {
+                constexpr int NT = decltype(nt)::value;
+                if constexpr (decltype(cplx)::value)
+                    return launch_cplx_error<T, NT, true>(err_partial, nullptr, y0, y1, k, coef, dt, ns, out_sumsq, out_nonfinite, cb);
+                else return launch_error_partial<T, NT>(err_partial, y0, y1, k, coef, dt, ns, out_sumsq, out_nonfinite, cb, copy_last_k);
+            });
+    });
+}
+
 int tdeq_error_norm_partial(const void* err_partial, const void* y0, const void* y1, const void* const* k,
                             const double* coef, int n_terms, double dt, const tdeq_segment* segs,
                             const void* segs_dev, int n_seg, int64_t chunk, int64_t n_chunks, double* out_sumsq,
                             double* out_nonfinite, void* workspace, size_t workspace_bytes, int dtype,
                             void* stream) {
-    if (!err_partial || !y0 || !y1 || !out_sumsq || !out_nonfinite || !workspace || bad_norm_dtype(dtype))
-        return TDEQ_EINVAL;
-    if (n_terms < 0 || n_terms > 2 || (n_terms > 0 && (!k || !coef))) return TDEQ_EINVAL;
-    for (int j = 0; j < n_terms; ++j) if (!k[j]) return TDEQ_EINVAL;
-    SegTable st;
-    const int e = fill_segtable(st, segs, segs_dev, n_seg, chunk, n_chunks);
-    if (e) return e;
-    if (workspace_bytes < tdeq_workspace_bytes(n_chunks)) return TDEQ_EWORKSPACE;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    double* ws = static_cast<double*>(workspace);
-    if (dtype == TDEQ_C64)
-        return dispatch_cplx_error_partial<float>(err_partial, y0, y1, k, coef, n_terms, dt, st, out_sumsq, out_nonfinite, ws, nullptr, s);
-    if (dtype == TDEQ_C128)
-        return dispatch_cplx_error_partial<double>(err_partial, y0, y1, k, coef, n_terms, dt, st, out_sumsq, out_nonfinite, ws, nullptr, s);
-    return dtype == TDEQ_F32
-               ? dispatch_error_partial<float>(err_partial, y0, y1, k, coef, n_terms, dt, st, out_sumsq, out_nonfinite, ws, nullptr, s)
-               : dispatch_error_partial<double>(err_partial, y0, y1, k, coef, n_terms, dt, st, out_sumsq, out_nonfinite, ws, nullptr, s);
+    return error_norm_partial_checked(err_partial, y0, y1, k, coef, n_terms, dt, segs, segs_dev, n_seg, chunk, n_chunks,
+                                      out_sumsq, out_nonfinite, nullptr, nullptr, workspace, workspace_bytes, dtype, stream);
 }
 
 int tdeq_error_norm_partial_ctrl(const void* err_partial, const void* y0, const void* y1, const void* const* k,
@@ -1311,58 +1139,19 @@ int tdeq_error_norm_partial_ctrl(const void* err_partial, const void* y0, const 
                                  double* out_nonfinite, const tdeq_step_ctrl* ctrl, double* out_ctrl, double* ctrl_dev,
                                  void* next_times, int state_in_dev, void* copy_last_k, void* workspace,
                                  size_t workspace_bytes, int dtype, void* stream) {
-    if (copy_last_k && (lp_dtype(dtype) || dtype == TDEQ_C64 || dtype == TDEQ_C128 || n_terms < 1)) return TDEQ_EINVAL;
-    if (lp_dtype(dtype)) {
-        // bf16 / fp16: the WHOLE error row in one launch (a row is rounded once: no partial sum to continue — err_partial
-        // must be NULL), then finalize + controller in the state's type
-        if (err_partial || !y0 || !y1 || !k || !coef || !out_sumsq || !out_nonfinite || !workspace) return TDEQ_EINVAL;
-        if (!ctrl || !out_ctrl || !ctrl_dev || !next_times || n_terms < 1 || n_terms > TDEQ_MAX_TERMS) return TDEQ_EINVAL;
-        for (int j = 0; j < n_terms; ++j) if (!k[j]) return TDEQ_EINVAL;
-        if (ctrl->n_times < 1 || ctrl->n_times > TDEQ_MAX_STAGE_TIMES || ctrl->n_norm_seg < 0 || ctrl->n_norm_seg > n_seg)
-            return TDEQ_EINVAL;
-        SegTable st;
-        const int e = fill_segtable(st, segs, segs_dev, n_seg, chunk, n_chunks);
-        if (e) return e;
-        if (workspace_bytes < tdeq_workspace_bytes(n_chunks)) return TDEQ_EWORKSPACE;
-        hipStream_t s = static_cast<hipStream_t>(stream);
-        double* ws = static_cast<double*>(workspace);
-        const CtrlBundle cb{ctrl, out_ctrl, ctrl_dev, next_times, state_in_dev ? 1 : 0};
-        return dtype == TDEQ_BF16
-                   ? lp_dispatch_error<lp::BF16>(nullptr, y0, y1, k, coef, n_terms, dt, st, out_sumsq, out_nonfinite, ws, s, &cb)
-                   : lp_dispatch_error<lp::F16>(nullptr, y0, y1, k, coef, n_terms, dt, st, out_sumsq, out_nonfinite, ws, s, &cb);
-    }
-    if (!err_partial || !y0 || !y1 || !out_sumsq || !out_nonfinite || !workspace || bad_norm_dtype(dtype))
-        return TDEQ_EINVAL;
-    if (!ctrl || !out_ctrl || !ctrl_dev || !next_times) return TDEQ_EINVAL;
-    if (n_terms < 0 || n_terms > 2 || (n_terms > 0 && (!k || !coef))) return TDEQ_EINVAL;
-    for (int j = 0; j < n_terms; ++j) if (!k[j]) return TDEQ_EINVAL;
-    if (ctrl->n_times < 1 || ctrl->n_times > TDEQ_MAX_STAGE_TIMES || ctrl->n_norm_seg < 0 || ctrl->n_norm_seg > n_seg)
-        return TDEQ_EINVAL;
-    SegTable st;
-    const int e = fill_segtable(st, segs, segs_dev, n_seg, chunk, n_chunks);
-    if (e) return e;
-    if (workspace_bytes < tdeq_workspace_bytes(n_chunks)) return TDEQ_EWORKSPACE;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    double* ws = static_cast<double*>(workspace);
-    const CtrlBundle cb{ctrl, out_ctrl, ctrl_dev, next_times, state_in_dev ? 1 : 0};
-    if (dtype == TDEQ_C64)
-        return dispatch_cplx_error_partial<float>(err_partial, y0, y1, k, coef, n_terms, dt, st, out_sumsq, out_nonfinite, ws, &cb, s);
-    if (dtype == TDEQ_C128)
-        return dispatch_cplx_error_partial<double>(err_partial, y0, y1, k, coef, n_terms, dt, st, out_sumsq, out_nonfinite, ws, &cb, s);
-    return dtype == TDEQ_F32
-               ? dispatch_error_partial<float>(err_partial, y0, y1, k, coef, n_terms, dt, st, out_sumsq, out_nonfinite, ws, &cb, s, copy_last_k)
-               : dispatch_error_partial<double>(err_partial, y0, y1, k, coef, n_terms, dt, st, out_sumsq, out_nonfinite, ws, &cb, s, copy_last_k);
+    CtrlBundle cb;
+    if (const int e = make_ctrl(cb, ctrl, out_ctrl, ctrl_dev, next_times, state_in_dev, n_seg)) return e;
+    return error_norm_partial_checked(err_partial, y0, y1, k, coef, n_terms, dt, segs, segs_dev, n_seg, chunk, n_chunks,
+                                      out_sumsq, out_nonfinite, &cb, copy_last_k, workspace, workspace_bytes, dtype, stream);
 }
 
 int tdeq_step_controller(const double* sums, const double* nonfinite, const tdeq_segment* segs, const void* segs_dev,
                          int n_seg, double* out_sumsq, double* out_nonfinite, const tdeq_step_ctrl* ctrl,
                          double* out_ctrl, double* ctrl_dev, void* next_times, int state_in_dev, int dtype,
                          void* stream) {
-    if (!sums || !nonfinite || !segs || !out_sumsq || !out_nonfinite || !ctrl || !out_ctrl || !ctrl_dev ||
-        !next_times || bad_dtype(dtype))
-        return TDEQ_EINVAL;
-    if (ctrl->n_times < 1 || ctrl->n_times > TDEQ_MAX_STAGE_TIMES || ctrl->n_norm_seg < 0 || ctrl->n_norm_seg > n_seg)
-        return TDEQ_EINVAL;
+    if (!sums || !nonfinite || !segs || !out_sumsq || !out_nonfinite || !real_dtype_ok(dtype)) return TDEQ_EINVAL;
+    CtrlBundle cb;
+    if (const int e = make_ctrl(cb, ctrl, out_ctrl, ctrl_dev, next_times, state_in_dev, n_seg)) return e;
     SegTable st;
     const int e = fill_segtable(st, segs, segs_dev, n_seg, TDEQ_CHUNK_QUANTUM, 1);   // only numel is read
     if (e) return e;
@@ -1378,7 +1167,7 @@ int tdeq_step_controller(const double* sums, const double* nonfinite, const tdeq
     a.out_ctrl = out_ctrl;
     a.ctrl_dev = ctrl_dev;
     a.next_times = next_times;
-    a.state_in_dev = state_in_dev ? 1 : 0;
+    a.state_in_dev = cb.state_in_dev;
     a.presummed = 1;
     a.in_sumsq = sums;
     a.in_bad = nonfinite;
@@ -1389,40 +1178,42 @@ int tdeq_step_controller(const double* sums, const double* nonfinite, const tdeq
 int tdeq_stage_combine_dev(void* out, void* err_out, const void* y0, const void* const* k, const double* coef,
                            const double* err_coef, int n_terms, const double* ctrl_dev, int64_t n, int dtype,
                            void* stream) {
-    if (!out || !y0 || !k || !coef || !ctrl_dev || n < 0 || (bad_dtype(dtype) && !lp_dtype(dtype))) return TDEQ_EINVAL;
-    if (n_terms < 1 || n_terms > TDEQ_MAX_TERMS || (err_out && !err_coef)) return TDEQ_EINVAL;
-    for (int j = 0; j < n_terms; ++j) if (!k[j]) return TDEQ_EINVAL;
+    if (!out || !y0 || !k || !coef || !ctrl_dev || n < 0 || !state_dtype_ok(dtype)) return TDEQ_EINVAL;
+    if (check_terms(k, n_terms, 1) || (err_out && !err_coef)) return TDEQ_EINVAL;
     if (lp_dtype(dtype) && err_out) return TDEQ_EINVAL;      // a 16-bit row is rounded once: no partial error to continue
     if (n == 0) return 0;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (dtype == TDEQ_BF16)
-        return lp_dispatch_combine<lp::BF16, 1>(out, nullptr, y0, k, coef, nullptr, n_terms, 0.0, n, nullptr, nullptr, 0, s, ctrl_dev);
-    if (dtype == TDEQ_F16)
-        return lp_dispatch_combine<lp::F16, 1>(out, nullptr, y0, k, coef, nullptr, n_terms, 0.0, n, nullptr, nullptr, 0, s, ctrl_dev);
-    return dtype == TDEQ_F32
-               ? launch_combine_dev<float>(out, err_out, y0, k, coef, err_coef, n_terms, ctrl_dev + 1, n, s)
-               : launch_combine_dev<double>(out, err_out, y0, k, coef, err_coef, n_terms, ctrl_dev + 1, n, s);
+    return state_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        if constexpr (is_lp<T>)
+            return terms<1>(n_terms, [&](auto nt) {
+                return lp_launch_combine<T, decltype(nt)::value, 1>(out, nullptr, y0, k, coef, nullptr, 0.0, n, s, ctrl_dev);
+            });
+        else return launch_combine_dev<T>(out, err_out, y0, k, coef, err_coef, n_terms, ctrl_dev + 1, n, s);
+    });
 }
 
 int tdeq_step_commit(void* y_prev, void* f_prev, void* y_cur, void* f_cur, const void* y1, const void* f1,
                      const double* ctrl_dev, int64_t n, int dtype, void* stream) {
-    if (!y_prev || !f_prev || !y_cur || !f_cur || !y1 || !f1 || !ctrl_dev || n < 0 || bad_dtype(dtype))
+    if (!y_prev || !f_prev || !y_cur || !f_cur || !y1 || !f1 || !ctrl_dev || n < 0 || !real_dtype_ok(dtype))
         return TDEQ_EINVAL;
     if (n == 0) return 0;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    return dtype == TDEQ_F32 ? launch_commit<float>(y_prev, f_prev, y_cur, f_cur, y1, f1, ctrl_dev, n, s)
-                             : launch_commit<double>(y_prev, f_prev, y_cur, f_cur, y1, f1, ctrl_dev, n, s);
+    return real_dtype(dtype, [&](auto t) {
+        return launch_commit<decltype(t)>(y_prev, f_prev, y_cur, f_cur, y1, f1, ctrl_dev, n, s);
+    });
 }
 
 int tdeq_stage_combine_sel(void* out, const void* y_acc, const void* f_acc, const void* y_rej, const void* f_rej,
                            double coef, const double* ctrl_dev, int64_t n, int dtype, void* stream) {
-    if (!out || !y_acc || !f_acc || !y_rej || !f_rej || !ctrl_dev || n < 0 || (bad_dtype(dtype) && !lp_dtype(dtype))) return TDEQ_EINVAL;
+    if (!out || !y_acc || !f_acc || !y_rej || !f_rej || !ctrl_dev || n < 0 || !state_dtype_ok(dtype)) return TDEQ_EINVAL;
     if (n == 0) return 0;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (dtype == TDEQ_BF16) return lp_launch_sel<lp::BF16>(out, y_acc, f_acc, y_rej, f_rej, coef, ctrl_dev, n, s);
-    if (dtype == TDEQ_F16) return lp_launch_sel<lp::F16>(out, y_acc, f_acc, y_rej, f_rej, coef, ctrl_dev, n, s);
-    return dtype == TDEQ_F32 ? launch_combine_sel<float>(out, y_acc, f_acc, y_rej, f_rej, coef, ctrl_dev, n, s)
-                             : launch_combine_sel<double>(out, y_acc, f_acc, y_rej, f_rej, coef, ctrl_dev, n, s);
+    return state_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        if constexpr (is_lp<T>) return lp_launch_sel<T>(out, y_acc, f_acc, y_rej, f_rej, coef, ctrl_dev, n, s);
+        else return launch_combine_sel<T>(out, y_acc, f_acc, y_rej, f_rej, coef, ctrl_dev, n, s);
+    });
 }
 
 int tdeq_init_norms(int mode, const void* a, const void* b, const void* yscale, const tdeq_segment* segs,
@@ -1430,142 +1221,139 @@ int tdeq_init_norms(int mode, const void* a, const void* b, const void* yscale, 
                     double* out_nonfinite, void* workspace, size_t workspace_bytes, int dtype,
                     void* stream) {
     if ((mode != 0 && mode != 1) || !a || !b || !yscale || !out_sumsq || !out_nonfinite || !workspace ||
-        (bad_norm_dtype(dtype) && !lp_dtype(dtype)))
+        !(state_dtype_ok(dtype) || cplx_dtype(dtype)))
         return TDEQ_EINVAL;
-    SegTable st;
-    const int e = fill_segtable(st, segs, segs_dev, n_seg, chunk, n_chunks);
-    if (e) return e;
-    if (workspace_bytes < tdeq_workspace_bytes(n_chunks)) return TDEQ_EWORKSPACE;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    double* ws = static_cast<double*>(workspace);
-    if (dtype == TDEQ_BF16) return lp_launch_init<lp::BF16>(mode, a, b, yscale, st, out_sumsq, out_nonfinite, ws, nullptr, nullptr, s);
-    if (dtype == TDEQ_F16) return lp_launch_init<lp::F16>(mode, a, b, yscale, st, out_sumsq, out_nonfinite, ws, nullptr, nullptr, s);
-    if (dtype == TDEQ_C64) return launch_cplx_init<float>(mode, a, b, yscale, st, out_sumsq, out_nonfinite, ws, nullptr, nullptr, s);
-    if (dtype == TDEQ_C128) return launch_cplx_init<double>(mode, a, b, yscale, st, out_sumsq, out_nonfinite, ws, nullptr, nullptr, s);
-    return dtype == TDEQ_F32 ? launch_init<float>(mode, a, b, yscale, st, out_sumsq, out_nonfinite, ws, s)
-                             : launch_init<double>(mode, a, b, yscale, st, out_sumsq, out_nonfinite, ws, s);
+    NormSetup ns;
+    if (const int e = norm_setup(ns, segs, segs_dev, n_seg, chunk, n_chunks, workspace, workspace_bytes, stream)) return e;
+    return norm_dtype(dtype, [&](auto t, auto cplx) {
+        using T = decltype(t);
+        if constexpr (is_lp<T>) return lp_launch_init<T>(mode, a, b, yscale, ns, out_sumsq, out_nonfinite, nullptr, nullptr);
+        else if constexpr (decltype(cplx)::value)
+            return launch_cplx_init<T>(mode, a, b, yscale, ns, out_sumsq, out_nonfinite, nullptr, nullptr);
+        else return launch_init<T>(mode, a, b, yscale, ns, out_sumsq, out_nonfinite);
+    });
 }
 
 int tdeq_init_norms_vec(int mode, const void* a, const void* b, const void* yscale, const double* rtol_vec,
                         double rtol_scalar, const double* atol_vec, double atol_scalar, const tdeq_segment* segs,
                         const void* segs_dev, int n_seg, int64_t chunk, int64_t n_chunks, double* out_sumsq,
                         double* out_nonfinite, void* workspace, size_t workspace_bytes, int dtype, void* stream) {
-    if ((mode != 0 && mode != 1) || !a || !b || !yscale || !out_sumsq || !out_nonfinite || !workspace || bad_dtype(dtype))
+    if ((mode != 0 && mode != 1) || !a || !b || !yscale || !out_sumsq || !out_nonfinite || !workspace || !real_dtype_ok(dtype))
         return TDEQ_EINVAL;
     if (!rtol_vec && !atol_vec) return TDEQ_EINVAL;      // two 0-dim tolerances: tdeq_init_norms (a different promotion)
-    SegTable st;
-    const int e = fill_segtable(st, segs, segs_dev, n_seg, chunk, n_chunks);
-    if (e) return e;
-    if (workspace_bytes < tdeq_workspace_bytes(n_chunks)) return TDEQ_EWORKSPACE;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    double* ws = static_cast<double*>(workspace);
-    return dtype == TDEQ_F32
-               ? launch_init_vec<float>(mode, a, b, yscale, rtol_vec, rtol_scalar, atol_vec, atol_scalar, st, out_sumsq,
-                                        out_nonfinite, ws, s)
-               : launch_init_vec<double>(mode, a, b, yscale, rtol_vec, rtol_scalar, atol_vec, atol_scalar, st, out_sumsq,
-                                         out_nonfinite, ws, s);
+    NormSetup ns;
+    if (const int e = norm_setup(ns, segs, segs_dev, n_seg, chunk, n_chunks, workspace, workspace_bytes, stream)) return e;
+    return real_dtype(dtype, [&](auto t) {
+        return launch_init_vec<decltype(t)>(mode, a, b, yscale, rtol_vec, rtol_scalar, atol_vec, atol_scalar, ns, out_sumsq,
+                                            out_nonfinite);
+    });
 }
 
 int tdeq_init_scaled(int mode, const void* a, const void* b, const void* yscale, const tdeq_segment* segs,
                      const void* segs_dev, int n_seg, int64_t chunk, int64_t n_chunks, void* out0, void* out1,
                      int dtype, void* stream) {
     if ((mode != 0 && mode != 1) || !a || !b || !yscale || !out0 || (mode == 0 && !out1) ||
-        (bad_norm_dtype(dtype) && !lp_dtype(dtype)))
+        !(state_dtype_ok(dtype) || cplx_dtype(dtype)))
         return TDEQ_EINVAL;
-    SegTable st;
-    const int e = fill_segtable(st, segs, segs_dev, n_seg, chunk, n_chunks);
+    NormSetup ns{{}, nullptr, static_cast<hipStream_t>(stream)};      // no sums: no workspace
+    const int e = fill_segtable(ns.st, segs, segs_dev, n_seg, chunk, n_chunks);
     if (e) return e;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (dtype == TDEQ_BF16) return lp_launch_init<lp::BF16>(mode, a, b, yscale, st, nullptr, nullptr, nullptr, out0, out1, s);
-    if (dtype == TDEQ_F16) return lp_launch_init<lp::F16>(mode, a, b, yscale, st, nullptr, nullptr, nullptr, out0, out1, s);
-    if (dtype == TDEQ_C64) return launch_cplx_init<float>(mode, a, b, yscale, st, nullptr, nullptr, nullptr, out0, out1, s);
-    if (dtype == TDEQ_C128) return launch_cplx_init<double>(mode, a, b, yscale, st, nullptr, nullptr, nullptr, out0, out1, s);
-    const dim3 g((unsigned)st.n_chunks), blk(kBlock);
-    if (dtype == TDEQ_F32) {
-        InitScaledArgs<float> x{static_cast<const float*>(a), static_cast<const float*>(b),
-                                static_cast<const float*>(yscale), st, static_cast<float*>(out0),
-                                static_cast<float*>(out1)};
-        if (mode == 0) hipLaunchKernelGGL((init_scaled_kernel<float, 0>), g, blk, 0, s, x);
-        else hipLaunchKernelGGL((init_scaled_kernel<float, 1>), g, blk, 0, s, x);
-    } else {
-        InitScaledArgs<double> x{static_cast<const double*>(a), static_cast<const double*>(b),
-                                 static_cast<const double*>(yscale), st, static_cast<double*>(out0),
-                                 static_cast<double*>(out1)};
-        if (mode == 0) hipLaunchKernelGGL((init_scaled_kernel<double, 0>), g, blk, 0, s, x);
-        else hipLaunchKernelGGL((init_scaled_kernel<double, 1>), g, blk, 0, s, x);
-    }
-    return check_launch();
+    return norm_dtype(dtype, [&](auto t, auto cplx) {
+        using T = decltype(t);
+        if constexpr (is_lp<T>) return lp_launch_init<T>(mode, a, b, yscale, ns, nullptr, nullptr, out0, out1);
+        else if constexpr (decltype(cplx)::value) return launch_cplx_init<T>(mode, a, b, yscale, ns, nullptr, nullptr, out0, out1);
+        else {
+            InitScaledArgs<T> x{static_cast<const T*>(a), static_cast<const T*>(b), static_cast<const T*>(yscale), ns.st,
+                                static_cast<T*>(out0), static_cast<T*>(out1)};
+            return flag(mode != 0, [&](auto m) {
+                hipLaunchKernelGGL((init_scaled_kernel<T, decltype(m)::value ? 1 : 0>), dim3((unsigned)ns.st.n_chunks), dim3(kBlock),
+                                   0, ns.s, x);
+                return check_launch();
+            });
+        }
+    });
 }
 
 int tdeq_dense_eval(void* out, const void* y0, const void* y1, const void* f0, const void* f1,
                     const void* const* k, const double* coef, int n_terms, double dt, double x, int64_t n,
                     int dtype, void* stream) {
-    if (!out || !y0 || !y1 || !f0 || !f1 || !k || !coef || n < 0 || (bad_dtype(dtype) && !lp_dtype(dtype))) return TDEQ_EINVAL;
-    if (n_terms < 1 || n_terms > TDEQ_MAX_TERMS) return TDEQ_EINVAL;
-    for (int j = 0; j < n_terms; ++j) if (!k[j]) return TDEQ_EINVAL;
+    if (!out || !y0 || !y1 || !f0 || !f1 || !k || !coef || n < 0 || !state_dtype_ok(dtype)) return TDEQ_EINVAL;
+    if (const int e = check_terms(k, n_terms, 1)) return e;
     if (n == 0) return 0;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (dtype == TDEQ_BF16) return lp_dense_eval<lp::BF16>(out, n, y0, y1, f0, f1, k, coef, n_terms, dt, &x, 1, n, s);
-    if (dtype == TDEQ_F16) return lp_dense_eval<lp::F16>(out, n, y0, y1, f0, f1, k, coef, n_terms, dt, &x, 1, n, s);
-    return dtype == TDEQ_F32
-               ? dispatch_dense<float, false>(out, y0, y1, f0, f1, k, coef, n_terms, dt, x, n, s)
-               : dispatch_dense<double, false>(out, y0, y1, f0, f1, k, coef, n_terms, dt, x, n, s);
+    return state_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        if constexpr (is_lp<T>) return lp_dense_eval<T>(out, n, y0, y1, f0, f1, k, coef, n_terms, dt, &x, 1, n, s);
+        else
+            return terms<1>(n_terms, [&](auto nt) {
+                return launch_dense<T, decltype(nt)::value, false>(out, y0, y1, f0, f1, k, coef, dt, x, n, s);
+            });
+    });
 }
 
 int tdeq_dense_eval_multi(void* out, int64_t out_stride, const void* y0, const void* y1, const void* f0,
                           const void* f1, const void* const* k, const double* coef, int n_terms, double dt,
                           const double* x, int n_x, int64_t n, int dtype, void* stream) {
-    if (!out || !y0 || !y1 || !f0 || !f1 || !k || !coef || !x || n < 0 || (bad_dtype(dtype) && !lp_dtype(dtype))) return TDEQ_EINVAL;
-    if (n_terms < 1 || n_terms > TDEQ_MAX_TERMS || n_x < 1 || n_x > TDEQ_MAX_DENSE_OUTPUTS) return TDEQ_EINVAL;
+    if (!out || !y0 || !y1 || !f0 || !f1 || !k || !coef || !x || n < 0 || !state_dtype_ok(dtype)) return TDEQ_EINVAL;
+    if (check_terms(k, n_terms, 1) || n_x < 1 || n_x > TDEQ_MAX_DENSE_OUTPUTS) return TDEQ_EINVAL;
     if (n_x > 1 && out_stride < n) return TDEQ_EINVAL;
-    for (int j = 0; j < n_terms; ++j) if (!k[j]) return TDEQ_EINVAL;
     if (n == 0) return 0;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (dtype == TDEQ_BF16) return lp_dense_eval<lp::BF16>(out, out_stride, y0, y1, f0, f1, k, coef, n_terms, dt, x, n_x, n, s);
-    if (dtype == TDEQ_F16) return lp_dense_eval<lp::F16>(out, out_stride, y0, y1, f0, f1, k, coef, n_terms, dt, x, n_x, n, s);
-    return dtype == TDEQ_F32
-               ? dispatch_dense_multi<float>(out, out_stride, y0, y1, f0, f1, k, coef, n_terms, dt, x, n_x, n, s)
-               : dispatch_dense_multi<double>(out, out_stride, y0, y1, f0, f1, k, coef, n_terms, dt, x, n_x, n, s);
+    return state_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        if constexpr (is_lp<T>) return lp_dense_eval<T>(out, out_stride, y0, y1, f0, f1, k, coef, n_terms, dt, x, n_x, n, s);
+        else
+            return terms<1>(n_terms, [&](auto nt) {
+                return launch_dense_multi<T, decltype(nt)::value>(out, out_stride, y0, y1, f0, f1, k, coef, dt, x, n_x, n, s);
+            });
+    });
 }
 
 int tdeq_interp_fit(void* coeffs, const void* y0, const void* y1, const void* f0, const void* f1,
                     const void* const* k, const double* coef, int n_terms, double dt, int64_t n, int dtype,
                     void* stream) {
-    if (!coeffs || !y0 || !y1 || !f0 || !f1 || !k || !coef || n < 0 || (bad_dtype(dtype) && !lp_dtype(dtype))) return TDEQ_EINVAL;
-    if (n_terms < 1 || n_terms > TDEQ_MAX_TERMS) return TDEQ_EINVAL;
-    for (int j = 0; j < n_terms; ++j) if (!k[j]) return TDEQ_EINVAL;
+    if (!coeffs || !y0 || !y1 || !f0 || !f1 || !k || !coef || n < 0 || !state_dtype_ok(dtype)) return TDEQ_EINVAL;
+    if (const int e = check_terms(k, n_terms, 1)) return e;
     if (n == 0) return 0;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (dtype == TDEQ_BF16) return lp_dispatch_fit<lp::BF16>(coeffs, y0, y1, f0, f1, k, coef, n_terms, dt, n, s);
-    if (dtype == TDEQ_F16) return lp_dispatch_fit<lp::F16>(coeffs, y0, y1, f0, f1, k, coef, n_terms, dt, n, s);
-    return dtype == TDEQ_F32
-               ? dispatch_dense<float, true>(coeffs, y0, y1, f0, f1, k, coef, n_terms, dt, 0.0, n, s)
-               : dispatch_dense<double, true>(coeffs, y0, y1, f0, f1, k, coef, n_terms, dt, 0.0, n, s);
+    return state_dtype_terms<1>(dtype, n_terms, [&](auto t, auto nt) {
+        using T = decltype(t);
+        constexpr int NT = decltype(nt)::value;
+        if constexpr (is_lp<T>) return lp_launch_fit<T, NT>(coeffs, y0, y1, f0, f1, k, coef, dt, n, s);
+        else return launch_dense<T, NT, true>(coeffs, y0, y1, f0, f1, k, coef, dt, 0.0, n, s);
+    });
+}
+
+// tdeq_rk4_38_stage with the step size from the host (dt) or from device memory (dt_dev: fp32 / fp64 only)
+static int rk4_stage_checked(int stage, void* out, const void* y0, const void* const (&ks)[4], double dt,
+                             const double* dt_dev, int64_t n, int dtype, void* stream) {
+    if (!out || !y0 || n < 0 || !(dt_dev ? real_dtype_ok(dtype) : state_dtype_ok(dtype))) return TDEQ_EINVAL;
+    if (n == 0) return (stage >= 1 && stage <= 4) ? 0 : TDEQ_EINVAL;
+    if (const int e = check_terms(ks, stage, 1, 4)) return e;      // stage 1..4 with its k1..k<stage>
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return state_dtype(dtype, [&](auto t) {
+        return terms<1, 4>(stage, [&](auto st) {
+            using T = decltype(t);
+            if constexpr (is_lp<T>) return lp_launch_rk4<T, decltype(st)::value>(out, y0, ks, dt, n, s);
+            else return launch_rk4<T, decltype(st)::value>(out, y0, ks, dt, n, s, dt_dev);
+        });
+    });
 }
 
 int tdeq_rk4_38_stage(int stage, void* out, const void* y0, const void* k1, const void* k2, const void* k3,
                       const void* k4, double dt, int64_t n, int dtype, void* stream) {
-    if (!out || !y0 || n < 0 || (bad_dtype(dtype) && !lp_dtype(dtype))) return TDEQ_EINVAL;
-    if (n == 0) return (stage >= 1 && stage <= 4) ? 0 : TDEQ_EINVAL;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (dtype == TDEQ_BF16) return lp_dispatch_rk4<lp::BF16>(stage, out, y0, k1, k2, k3, k4, dt, n, s);
-    if (dtype == TDEQ_F16) return lp_dispatch_rk4<lp::F16>(stage, out, y0, k1, k2, k3, k4, dt, n, s);
-    return dtype == TDEQ_F32 ? dispatch_rk4<float>(stage, out, y0, k1, k2, k3, k4, dt, n, s)
-                             : dispatch_rk4<double>(stage, out, y0, k1, k2, k3, k4, dt, n, s);
+    return rk4_stage_checked(stage, out, y0, {k1, k2, k3, k4}, dt, nullptr, n, dtype, stream);
 }
 
 int tdeq_rk4_38_stage_dev(int stage, void* out, const void* y0, const void* k1, const void* k2, const void* k3,
                           const void* k4, const double* dt_dev, int64_t n, int dtype, void* stream) {
-    if (!out || !y0 || !dt_dev || n < 0 || bad_dtype(dtype)) return TDEQ_EINVAL;
-    if (n == 0) return (stage >= 1 && stage <= 4) ? 0 : TDEQ_EINVAL;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    return dtype == TDEQ_F32 ? dispatch_rk4<float>(stage, out, y0, k1, k2, k3, k4, 0.0, n, s, dt_dev)
-                             : dispatch_rk4<double>(stage, out, y0, k1, k2, k3, k4, 0.0, n, s, dt_dev);
+    if (!dt_dev) return TDEQ_EINVAL;
+    return rk4_stage_checked(stage, out, y0, {k1, k2, k3, k4}, 0.0, dt_dev, n, dtype, stream);
 }
 
 int tdeq_grid_advance(const void* grid, int grid_dtype, int64_t n_grid, int64_t* counter, int perturb, double sign,
                       void* times_out, double* dt_out, int state_dtype, void* stream) {
-    if (!grid || !counter || !times_out || !dt_out || n_grid < 2 || bad_dtype(grid_dtype) || bad_dtype(state_dtype))
+    if (!grid || !counter || !times_out || !dt_out || n_grid < 2 || !real_dtype_ok(grid_dtype) || !real_dtype_ok(state_dtype))
         return TDEQ_EINVAL;
     GridAdvanceArgs a;
     a.grid = grid;
@@ -1584,8 +1372,8 @@ int tdeq_grid_advance(const void* grid, int grid_dtype, int64_t n_grid, int64_t*
 int tdeq_grid_advance_stages(const void* grid, int grid_dtype, int64_t n_grid, int64_t* counter, int perturb, double sign,
                              const double* frac, const int* mode, int n_times, void* times_out, double* dt_out,
                              int state_dtype, void* stream) {
-    if (!grid || !counter || !times_out || !dt_out || !frac || !mode || n_grid < 2 || bad_dtype(grid_dtype) ||
-        bad_dtype(state_dtype) || n_times < 1 || n_times > kMaxGridStages)
+    if (!grid || !counter || !times_out || !dt_out || !frac || !mode || n_grid < 2 || !real_dtype_ok(grid_dtype) ||
+        !real_dtype_ok(state_dtype) || n_times < 1 || n_times > kMaxGridStages)
         return TDEQ_EINVAL;
     GridStagesArgs a;
     a.base.grid = grid;
@@ -1608,75 +1396,79 @@ int tdeq_grid_advance_stages(const void* grid, int grid_dtype, int64_t n_grid, i
 
 int tdeq_grid_commit(void* solution, int64_t row_stride, void* y_cur, const void* y_new, const int64_t* counter,
                      int64_t n, int dtype, void* stream) {
-    if (!solution || !y_cur || !y_new || !counter || n < 0 || row_stride < n || bad_dtype(dtype)) return TDEQ_EINVAL;
+    if (!solution || !y_cur || !y_new || !counter || n < 0 || row_stride < n || !real_dtype_ok(dtype)) return TDEQ_EINVAL;
     if (n == 0) return 0;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    return dtype == TDEQ_F32 ? launch_grid_commit<float>(solution, row_stride, y_cur, y_new, counter, n, s)
-                             : launch_grid_commit<double>(solution, row_stride, y_cur, y_new, counter, n, s);
+    return real_dtype(dtype, [&](auto t) {
+        return launch_grid_commit<decltype(t)>(solution, row_stride, y_cur, y_new, counter, n, s);
+    });
 }
 
 int tdeq_lerp(void* out, const void* y0, const void* y1, double slope, int64_t n, int dtype, void* stream) {
-    if (!out || !y0 || !y1 || n < 0 || (bad_dtype(dtype) && !lp_dtype(dtype))) return TDEQ_EINVAL;
+    if (!out || !y0 || !y1 || n < 0 || !state_dtype_ok(dtype)) return TDEQ_EINVAL;
     if (n == 0) return 0;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (dtype == TDEQ_BF16) return lp_launch_lerp<lp::BF16>(out, y0, y1, slope, n, s);
-    if (dtype == TDEQ_F16) return lp_launch_lerp<lp::F16>(out, y0, y1, slope, n, s);
-    return dtype == TDEQ_F32 ? launch_lerp<float>(out, y0, y1, slope, n, s)
-                             : launch_lerp<double>(out, y0, y1, slope, n, s);
+    return state_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        if constexpr (is_lp<T>) return lp_launch_lerp<T>(out, y0, y1, slope, n, s);
+        else return launch_lerp<T>(out, y0, y1, slope, n, s);
+    });
+}
+
+// tdeq_fixed_stage with the step size from the host (dt) or from device memory (dt_dev: fp32 / fp64 only)
+static int fixed_stage_checked(int mode, void* out, const void* y0, const void* const* k, const double* w, int n_terms,
+                               double dt, const double* dt_dev, int64_t n, int dtype, void* stream) {
+    if (!out || !y0 || !k || !w || n < 0 || !(dt_dev ? real_dtype_ok(dtype) : state_dtype_ok(dtype))) return TDEQ_EINVAL;
+    if ((mode != 0 && mode != 1) || (mode == 1 && n_terms != 1)) return TDEQ_EINVAL;
+    if (const int e = check_terms(k, n_terms, 1, 4)) return e;
+    if (n == 0) return 0;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return state_dtype(dtype, [&](auto t) {
+        auto launch = [&](auto nt, auto m) {
+            using T = decltype(t);
+            constexpr int NT = decltype(nt)::value, MODE = decltype(m)::value;
+            if constexpr (is_lp<T>) return lp_launch_fixed<T, NT, MODE>(out, y0, k, w, dt, n, s);
+            else return launch_fixed<T, NT, MODE>(out, y0, k, w, dt, n, s, dt_dev);
+        };
+        if (mode == 1) return launch(std::integral_constant<int, 1>{}, std::integral_constant<int, 1>{});
+        return terms<1, 4>(n_terms, [&](auto nt) { return launch(nt, std::integral_constant<int, 0>{}); });
+    });
 }
 
 int tdeq_fixed_stage(int mode, void* out, const void* y0, const void* const* k, const double* w, int n_terms,
                      double dt, int64_t n, int dtype, void* stream) {
-    if (!out || !y0 || !k || !w || n < 0 || (bad_dtype(dtype) && !lp_dtype(dtype))) return TDEQ_EINVAL;
-    if ((mode != 0 && mode != 1) || n_terms < 1 || n_terms > 4 || (mode == 1 && n_terms != 1)) return TDEQ_EINVAL;
-    for (int j = 0; j < n_terms; ++j) if (!k[j]) return TDEQ_EINVAL;
-    if (n == 0) return 0;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (dtype == TDEQ_BF16) return lp_dispatch_fixed<lp::BF16>(mode, out, y0, k, w, n_terms, dt, n, s);
-    if (dtype == TDEQ_F16) return lp_dispatch_fixed<lp::F16>(mode, out, y0, k, w, n_terms, dt, n, s);
-    if (dtype == TDEQ_F32)
-        return mode == 0 ? dispatch_fixed<float, 0>(out, y0, k, w, n_terms, dt, n, s)
-                         : dispatch_fixed<float, 1>(out, y0, k, w, n_terms, dt, n, s);
-    return mode == 0 ? dispatch_fixed<double, 0>(out, y0, k, w, n_terms, dt, n, s)
-                     : dispatch_fixed<double, 1>(out, y0, k, w, n_terms, dt, n, s);
+    return fixed_stage_checked(mode, out, y0, k, w, n_terms, dt, nullptr, n, dtype, stream);
 }
 
 int tdeq_fixed_stage_dev(int mode, void* out, const void* y0, const void* const* k, const double* w, int n_terms,
                          const double* dt_dev, int64_t n, int dtype, void* stream) {
-    if (!out || !y0 || !k || !w || !dt_dev || n < 0 || bad_dtype(dtype)) return TDEQ_EINVAL;
-    if ((mode != 0 && mode != 1) || n_terms < 1 || n_terms > 4 || (mode == 1 && n_terms != 1)) return TDEQ_EINVAL;
-    for (int j = 0; j < n_terms; ++j) if (!k[j]) return TDEQ_EINVAL;
-    if (n == 0) return 0;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (dtype == TDEQ_F32)
-        return mode == 0 ? dispatch_fixed<float, 0>(out, y0, k, w, n_terms, 0.0, n, s, dt_dev)
-                         : dispatch_fixed<float, 1>(out, y0, k, w, n_terms, 0.0, n, s, dt_dev);
-    return mode == 0 ? dispatch_fixed<double, 0>(out, y0, k, w, n_terms, 0.0, n, s, dt_dev)
-                     : dispatch_fixed<double, 1>(out, y0, k, w, n_terms, 0.0, n, s, dt_dev);
+    if (!dt_dev) return TDEQ_EINVAL;
+    return fixed_stage_checked(mode, out, y0, k, w, n_terms, 0.0, dt_dev, n, dtype, stream);
 }
 
 int tdeq_weighted_sum(void* out, const void* const* x, const double* w, int n_terms, int64_t n, int dtype,
                       void* stream) {
-    if (!out || !x || !w || n < 0 || (bad_dtype(dtype) && !lp_dtype(dtype))) return TDEQ_EINVAL;
-    if (n_terms < 1 || n_terms > TDEQ_MAX_SUM_TERMS) return TDEQ_EINVAL;
-    for (int j = 0; j < n_terms; ++j) if (!x[j]) return TDEQ_EINVAL;
+    if (!out || !x || !w || n < 0 || !state_dtype_ok(dtype)) return TDEQ_EINVAL;
+    if (const int e = check_terms(x, n_terms, 1, TDEQ_MAX_SUM_TERMS)) return e;
     if (n == 0) return 0;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (dtype == TDEQ_BF16) return lp_dispatch_weighted<lp::BF16>(out, x, w, n_terms, n, s);
-    if (dtype == TDEQ_F16) return lp_dispatch_weighted<lp::F16>(out, x, w, n_terms, n, s);
-    return dtype == TDEQ_F32 ? dispatch_fixed<float, 2>(out, nullptr, x, w, n_terms, 0.0, n, s)
-                             : dispatch_fixed<double, 2>(out, nullptr, x, w, n_terms, 0.0, n, s);
+    return state_dtype_terms<1, TDEQ_MAX_SUM_TERMS>(dtype, n_terms, [&](auto t, auto nt) {
+        using T = decltype(t);
+        constexpr int NT = decltype(nt)::value;
+        if constexpr (is_lp<T>) return lp_launch_weighted<T, NT>(out, x, w, n, s);
+        else return launch_fixed<T, NT, 2>(out, nullptr, x, w, 0.0, n, s);
+    });
 }
 
 int tdeq_scale_many(void* const* outs, const void* g, const double* w, int n_out, int64_t n, int dtype,
                     void* stream) {
-    if (!outs || !g || !w || n < 0 || bad_dtype(dtype)) return TDEQ_EINVAL;
-    if (n_out < 1 || n_out > TDEQ_MAX_TERMS) return TDEQ_EINVAL;
-    for (int j = 0; j < n_out; ++j) if (!outs[j]) return TDEQ_EINVAL;
+    if (!outs || !g || !w || n < 0 || !real_dtype_ok(dtype)) return TDEQ_EINVAL;
+    if (const int e = check_terms(outs, n_out, 1)) return e;
     if (n == 0) return 0;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    return dtype == TDEQ_F32 ? dispatch_scale<float>(outs, g, w, n_out, n, s)
-                             : dispatch_scale<double>(outs, g, w, n_out, n, s);
+    return real_dtype_terms<1>(dtype, n_out, [&](auto t, auto nt) {
+        return launch_scale<decltype(t), decltype(nt)::value>(outs, g, w, n, s);
+    });
 }
 
 size_t tdeq_dots_workspace_bytes(int64_t n, int n_x) {
@@ -1688,19 +1480,19 @@ size_t tdeq_dots_workspace_bytes(int64_t n, int n_x) {
 
 int tdeq_multi_dot(const void* g, const void* const* x, int n_x, int64_t n, double* out, void* workspace,
                    size_t workspace_bytes, int dtype, void* stream) {
-    if (!g || !x || !out || !workspace || n < 0 || bad_dtype(dtype)) return TDEQ_EINVAL;
-    if (n_x < 1 || n_x > TDEQ_MAX_TERMS) return TDEQ_EINVAL;
-    for (int j = 0; j < n_x; ++j) if (!x[j]) return TDEQ_EINVAL;
+    if (!g || !x || !out || !workspace || n < 0 || !real_dtype_ok(dtype)) return TDEQ_EINVAL;
+    if (const int e = check_terms(x, n_x, 1)) return e;
     if (workspace_bytes < tdeq_dots_workspace_bytes(n, n_x)) return TDEQ_EWORKSPACE;
     hipStream_t s = static_cast<hipStream_t>(stream);
     double* ws = static_cast<double*>(workspace);
-    return dtype == TDEQ_F32 ? dispatch_dots<float>(g, x, n_x, n, out, ws, s)
-                             : dispatch_dots<double>(g, x, n_x, n, out, ws, s);
+    return real_dtype_terms<1>(dtype, n_x, [&](auto t, auto nt) {
+        return launch_dots<decltype(t), decltype(nt)::value>(g, x, n, out, ws, s);
+    });
 }
 
 int tdeq_pack_segments(void* out, const void* const* src, const int64_t* chunk_start, const int64_t* numel,
                        const double* scale, int n_seg, int64_t chunk, int64_t n_chunks, int dtype, void* stream) {
-    if (!out || !src || !chunk_start || !numel || !scale || bad_dtype(dtype)) return TDEQ_EINVAL;
+    if (!out || !src || !chunk_start || !numel || !scale || !real_dtype_ok(dtype)) return TDEQ_EINVAL;
     if (n_seg < 1 || n_seg > TDEQ_INLINE_SEGMENTS) return TDEQ_EINVAL;
     if (chunk < TDEQ_CHUNK_QUANTUM || chunk % TDEQ_CHUNK_QUANTUM != 0 || n_chunks < 1 || n_chunks > 0x7fffffffLL)
         return TDEQ_EINVAL;
@@ -1712,12 +1504,13 @@ int tdeq_pack_segments(void* out, const void* const* src, const int64_t* chunk_s
         if (numel[q] > (end - chunk_start[q]) * chunk) return TDEQ_EINVAL;
     }
     hipStream_t s = static_cast<hipStream_t>(stream);
-    return dtype == TDEQ_F32 ? launch_pack<float>(out, src, chunk_start, numel, scale, n_seg, chunk, n_chunks, s)
-                             : launch_pack<double>(out, src, chunk_start, numel, scale, n_seg, chunk, n_chunks, s);
+    return real_dtype(dtype, [&](auto t) {
+        return launch_pack<decltype(t)>(out, src, chunk_start, numel, scale, n_seg, chunk, n_chunks, s);
+    });
 }
 
 int tdeq_fill_scalars(void* dst, const double* vals, int n_vals, int dtype, void* stream) {
-    if (!dst || !vals || n_vals < 1 || n_vals > 16 || bad_dtype(dtype)) return TDEQ_EINVAL;
+    if (!dst || !vals || n_vals < 1 || n_vals > 16 || !real_dtype_ok(dtype)) return TDEQ_EINVAL;
     FillArgs a;
     a.dst = dst;
     for (int i = 0; i < 16; ++i) a.v[i] = i < n_vals ? vals[i] : 0.0;
@@ -1730,33 +1523,30 @@ int tdeq_fill_scalars(void* dst, const double* vals, int n_vals, int dtype, void
 int tdeq_adams_predict(void* y_out, void* dy_out, void* delta_out, const void* y0, const void* const* f_hist,
                        const double* cb, const double* cm, int n_terms, double dt, int64_t n, int dtype,
                        void* stream) {
-    if (!y_out || !y0 || !f_hist || !cb || n < 0 || bad_dtype(dtype)) return TDEQ_EINVAL;
+    if (!y_out || !y0 || !f_hist || !cb || n < 0 || !real_dtype_ok(dtype)) return TDEQ_EINVAL;
     if ((dy_out == nullptr) != (delta_out == nullptr)) return TDEQ_EINVAL;
     if (dy_out && !cm) return TDEQ_EINVAL;
-    if (n_terms < 1 || n_terms > TDEQ_MAX_TERMS) return TDEQ_EINVAL;
-    for (int j = 0; j < n_terms; ++j) if (!f_hist[j]) return TDEQ_EINVAL;
+    if (const int e = check_terms(f_hist, n_terms, 1)) return e;
     if (n == 0) return 0;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    return dtype == TDEQ_F32 ? dispatch_adams_predict<float>(y_out, dy_out, delta_out, y0, f_hist, cb, cm, n_terms, dt, n, s)
-                             : dispatch_adams_predict<double>(y_out, dy_out, delta_out, y0, f_hist, cb, cm, n_terms, dt, n, s);
+    return real_dtype_terms<1>(dtype, n_terms, [&](auto t, auto nt) {
+        return launch_adams_predict<decltype(t), decltype(nt)::value>(y_out, dy_out, delta_out, y0, f_hist, cb, cm, dt, n, s);
+    });
 }
 
 int tdeq_adams_correct(void* y_out, void* dy_out, const void* f, const void* delta, const void* dy_old,
                        const void* y0, double c, int compute, const tdeq_segment* segs, const void* segs_dev,
                        int n_seg, int64_t chunk, int64_t n_chunks, int64_t n, double* out_count,
                        double* out_nonfinite, void* workspace, size_t workspace_bytes, int dtype, void* stream) {
-    if (!dy_out || !dy_old || !out_count || !out_nonfinite || !workspace || n < 0 || bad_dtype(dtype))
+    if (!dy_out || !dy_old || !out_count || !out_nonfinite || !workspace || n < 0 || !real_dtype_ok(dtype))
         return TDEQ_EINVAL;
     if (compute && (!y_out || !f || !delta || !y0)) return TDEQ_EINVAL;
-    SegTable st;
-    const int e = fill_segtable(st, segs, segs_dev, n_seg, chunk, n_chunks);
-    if (e) return e;
-    if (workspace_bytes < tdeq_workspace_bytes(n_chunks)) return TDEQ_EWORKSPACE;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    double* ws = static_cast<double*>(workspace);
-    return dtype == TDEQ_F32
-               ? launch_adams_correct<float>(y_out, dy_out, f, delta, dy_old, y0, c, compute != 0, st, n, out_count, out_nonfinite, ws, s)
-               : launch_adams_correct<double>(y_out, dy_out, f, delta, dy_old, y0, c, compute != 0, st, n, out_count, out_nonfinite, ws, s);
+    NormSetup ns;
+    if (const int e = norm_setup(ns, segs, segs_dev, n_seg, chunk, n_chunks, workspace, workspace_bytes, stream)) return e;
+    return real_dtype(dtype, [&](auto t) {
+        return launch_adams_correct<decltype(t)>(y_out, dy_out, f, delta, dy_old, y0, c, compute != 0, ns, n, out_count,
+                                                 out_nonfinite);
+    });
 }
 
 }  // extern "C"

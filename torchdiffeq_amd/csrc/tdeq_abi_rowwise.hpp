@@ -1,6 +1,6 @@
 // tdeq_abi_rowwise.hpp — extern "C" entry points of the per-row step control (tdeq_kernels_rowwise.hpp, declared in
-// include/tdeq_hip.h).  Included by tdeq_abi.hip after its anonymous namespace: host-side validation, launch geometry,
-// template dispatch.  No allocation, no synchronisation.
+// include/tdeq_hip.h).  Included by tdeq_abi.hip after its anonymous namespace, whose dispatch helpers it shares: host-side
+// validation, launch geometry, template dispatch.  No allocation, no synchronisation.
 #pragma once
 
 #include "tdeq_kernels_rowwise.hpp"
@@ -10,61 +10,14 @@
 namespace {
 using namespace tdeq;
 
-// ---- the run-time choices of a launch, each written once: every helper calls f with a tag and returns its status -----
-inline bool row_dtype_ok(int dtype) { return dtype == TDEQ_F32 || dtype == TDEQ_F64; }
-
-// f(T{}), T = float or double
-template <typename F>
-int row_dtype(int dtype, F f) {
-    return dtype == TDEQ_F32 ? f(float{}) : f(double{});
-}
-
-// f(std::true_type{}) or f(std::false_type{}): one bool template argument of a kernel
-template <typename F>
-int row_bool(bool b, F f) {
-    return b ? f(std::true_type{}) : f(std::false_type{});
-}
-
-// f(std::integral_constant<int, N>{}) for LO <= N = nt <= 14: the only switch over the term count
-template <int LO, typename F>
-int row_terms(int nt, F f) {
-    switch (nt) {
-#define TDEQ_CASE(N) case N: if constexpr (N >= LO) return f(std::integral_constant<int, N>{}); break;
-        TDEQ_CASE(0) TDEQ_CASE(1) TDEQ_CASE(2) TDEQ_CASE(3) TDEQ_CASE(4) TDEQ_CASE(5) TDEQ_CASE(6) TDEQ_CASE(7)
-        TDEQ_CASE(8) TDEQ_CASE(9) TDEQ_CASE(10) TDEQ_CASE(11) TDEQ_CASE(12) TDEQ_CASE(13) TDEQ_CASE(14)
-#undef TDEQ_CASE
-    }
-    return TDEQ_EINVAL;
-}
-
-// f(T{}, std::integral_constant<int, N>{}): what a term-templated entry point launches through
-template <int LO, typename F>
-int row_dtype_terms(int dtype, int nt, F f) {
-    return row_dtype(dtype, [&](auto t) { return row_terms<LO>(nt, [&](auto n) { return f(t, n); }); });
-}
+// (the run-time choices of a launch — real_dtype, flag, terms, real_dtype_terms — and all_aligned / Ptrs are those of
+//  tdeq_abi.hip: every helper calls f with a tag and returns its status)
 
 // ---- the 16-byte decision ---------------------------------------------------------------------------------------------
 // 16-byte elements when a row is a whole number of them (an element then never straddles two rows)
 template <typename T>
 int row_lanes(int64_t row_len) {
     return row_len % VecOf<T>::L == 0 ? VecOf<T>::L : 1;
-}
-
-struct RowPtrs {                      // an array of n pointers: k[], outs[], x[]
-    const void* const* p;
-    int n;
-};
-
-inline bool row_aligned16(const void* p) { return aligned16(p); }      // (so is a null pointer: an input that is absent)
-inline bool row_aligned16(RowPtrs a) {
-    for (int j = 0; j < a.n; ++j) if (!aligned16(a.p[j])) return false;
-    return true;
-}
-
-// are all of these pointers (and every pointer of these arrays) 16-byte aligned
-template <typename... P>
-bool row_aligned(P... p) {
-    return (row_aligned16(p) && ...);
 }
 
 // A launch takes 16-byte elements when the row is a whole number of them and every pointer is `aligned`: row_len_e
@@ -74,14 +27,14 @@ int row_vec(int64_t row_len, bool aligned, int64_t& row_len_e, F f) {
     const int lv = row_lanes<T>(row_len);
     const bool vec = lv > 1 && aligned;
     row_len_e = vec ? row_len / lv : row_len;
-    return row_bool(vec, f);
+    return flag(vec, f);
 }
 
 // The same decision for the copy-style kernels, which are templated on the element alone: f(E{}, row_len_e) with
 // E = T or VecOf<T>::type.
 template <typename F>
 int row_elem(int dtype, int64_t row_len, bool aligned, F f) {
-    return row_dtype(dtype, [&](auto t) {
+    return real_dtype(dtype, [&](auto t) {
         using T = decltype(t);
         const int lv = row_lanes<T>(row_len);
         return lv > 1 && aligned ? f(typename VecOf<T>::type{}, row_len / lv) : f(t, row_len);
@@ -129,7 +82,7 @@ int row_combine_n(const tdeq_multi_out* outs, int n_out, const void* y0, const v
     a.acc_in = static_cast<const T*>(acc_in);
     for (int j = 0; j < NT; ++j) a.k[j] = static_cast<const T*>(k[j]);
     a.add_y0 = 0;
-    bool aligned = row_aligned(y0, acc_in, RowPtrs{k, NT});
+    bool aligned = all_aligned(y0, acc_in, Ptrs{k, NT});
     for (int o = 0; o < kMaxMultiOut; ++o) {
         const bool live = o < n_out;
         a.out[o] = live ? static_cast<T*>(outs[o].out) : nullptr;
@@ -151,7 +104,7 @@ int row_combine_n(const tdeq_multi_out* outs, int n_out, const void* y0, const v
 
 template <typename T, int NT, int MODE, bool PARTIAL, bool ROWTOL>
 int row_reduce_launch(RowRedArgsOf<T, NT, ROWTOL>& a, const RowGeom& g, bool vec, hipStream_t s) {
-    return row_bool(vec, [&](auto v) {
+    return flag(vec, [&](auto v) {
         constexpr bool VEC = decltype(v)::value;
         if (g.group > 0) {            // short row; a long row of one chunk (1024 < nv <= 2048) takes the chunk kernel,
             const int64_t threads = a.n_rows * g.group;  // whose part[q * B + r] is what the lane-per-row controller reads
@@ -207,7 +160,7 @@ int row_reduce_n(int mode, const void* y0, const void* y1, const void* partial, 
     a.nch = (int)g.nch;
     a.group = g.group;
     a.part = part;
-    const bool vec = g.lv > 1 && row_aligned(y0, y1, partial, RowPtrs{k, NT});
+    const bool vec = g.lv > 1 && all_aligned(y0, y1, partial, Ptrs{k, NT});
     if (g.lv > 1 && !vec) return TDEQ_EINVAL;      // (the geometry, hence the sums, must not depend on alignment)
     if constexpr (NT == 0) {
         if (mode == 1) return row_reduce_launch<T, NT, 1, false, ROWTOL>(a, g, vec, s);
@@ -225,7 +178,7 @@ template <bool ROWTOL>
 int row_reduce_entry(int mode, const void* y0, const void* y1, const void* partial, const void* const* k,
                      const double* coef, int n_terms, const void* dts, const int32_t* active, const RowTols& tol,
                      int64_t n_rows, int64_t row_len, double* part, size_t part_bytes, int dtype, void* stream) {
-    if (!y0 || !y1 || !part || n_rows < 0 || row_len < 1 || !row_dtype_ok(dtype)) return TDEQ_EINVAL;
+    if (!y0 || !y1 || !part || n_rows < 0 || row_len < 1 || !real_dtype_ok(dtype)) return TDEQ_EINVAL;
     if (mode < 0 || mode > 2 || n_terms < 0 || n_terms > TDEQ_MAX_TERMS) return TDEQ_EINVAL;
     if (mode == 0 && (n_terms < 1 || !k || !coef || !dts || !active)) return TDEQ_EINVAL;
     if (mode != 0 && (n_terms != 0 || !partial)) return TDEQ_EINVAL;
@@ -234,7 +187,7 @@ int row_reduce_entry(int mode, const void* y0, const void* y1, const void* parti
     if (part_bytes < (size_t)(3 * n_rows * nch) * sizeof(double)) return TDEQ_EWORKSPACE;
     if (n_rows == 0) return 0;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    return row_dtype_terms<0>(dtype, n_terms, [&](auto t, auto n) {
+    return real_dtype_terms<0>(dtype, n_terms, [&](auto t, auto n) {
         return row_reduce_n<decltype(t), decltype(n)::value, ROWTOL>(mode, y0, y1, partial, k, coef, dts, active, tol,
                                                                      n_rows, row_len, part, s);
     });
@@ -267,7 +220,7 @@ bool row_quartic_args(A& a, const void* out, P* y0, const void* y1, P* f0, const
         a.c[j] = (T)coef[j];
     }
     a.dts = static_cast<const T*>(dts);
-    return row_aligned(out, y0, y1, f0, f1, RowPtrs{k, NT});
+    return all_aligned(out, y0, y1, f0, f1, Ptrs{k, NT});
 }
 
 // tdeq_row_dense_commit and (MAPPED: row_map, sol_rows) tdeq_row_dense_commit_mapped
@@ -328,14 +281,14 @@ int row_gather_dispatch(void* const* dst, const void* const* src, int n_src, con
 }  // namespace
 
 int64_t tdeq_row_partials(int64_t row_len, int dtype) {
-    if (row_len < 1 || !row_dtype_ok(dtype)) return TDEQ_EINVAL;
+    if (row_len < 1 || !real_dtype_ok(dtype)) return TDEQ_EINVAL;
     return row_geom(row_len, dtype).nch;
 }
 
 int tdeq_row_combine(const tdeq_multi_out* outs, int n_out, const void* y0, const void* acc_in, const void* const* k,
                      int n_terms, const void* dts, const int32_t* active, int64_t n_rows, int64_t row_len, int dtype,
                      void* stream) {
-    if (!outs || !y0 || !k || !dts || !active || n_rows < 0 || row_len < 1 || !row_dtype_ok(dtype)) return TDEQ_EINVAL;
+    if (!outs || !y0 || !k || !dts || !active || n_rows < 0 || row_len < 1 || !real_dtype_ok(dtype)) return TDEQ_EINVAL;
     if (n_terms < 1 || n_terms > TDEQ_MAX_TERMS || n_out < 1 || n_out > TDEQ_MAX_MULTI_OUT) return TDEQ_EINVAL;
     for (int j = 0; j < n_terms; ++j) if (!k[j]) return TDEQ_EINVAL;
     for (int o = 0; o < n_out; ++o) {
@@ -343,7 +296,7 @@ int tdeq_row_combine(const tdeq_multi_out* outs, int n_out, const void* y0, cons
     }
     if (n_rows == 0) return 0;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    return row_dtype_terms<1>(dtype, n_terms, [&](auto t, auto n) {
+    return real_dtype_terms<1>(dtype, n_terms, [&](auto t, auto n) {
         return row_combine_n<decltype(t), decltype(n)::value>(outs, n_out, y0, acc_in, k, dts, active, n_rows, row_len, s);
     });
 }
@@ -370,7 +323,7 @@ namespace {
 int row_control_args(RowCtrlArgs& a, int mode, const double* part, const tdeq_step_ctrl* ctrl, const tdeq_row_state* st,
                      void* dts_out, void* times_out, int dtype, int n_status, hipStream_t s, bool& launch) {
     launch = false;
-    if (!part || !ctrl || !st || !row_dtype_ok(dtype) || mode < 0 || mode > 3) return TDEQ_EINVAL;
+    if (!part || !ctrl || !st || !real_dtype_ok(dtype) || mode < 0 || mode > 3) return TDEQ_EINVAL;
     if (st->n_rows < 0 || st->row_len < 1 || st->n_out < 1 || !st->status) return TDEQ_EINVAL;
     if (ctrl->n_times < 1 || ctrl->n_times > TDEQ_MAX_STAGE_TIMES) return TDEQ_EINVAL;
     if (!dts_out || !times_out) return TDEQ_EINVAL;
@@ -402,7 +355,7 @@ int tdeq_row_control(int mode, const double* part, const tdeq_step_ctrl* ctrl, c
     bool launch;
     const int e = row_control_args(a, mode, part, ctrl, st, dts_out, times_out, dtype, 2, s, launch);
     if (e || !launch) return e;
-    return row_dtype(dtype, [&](auto t) { return row_control_launch<decltype(t), false, false>(a, s); });
+    return real_dtype(dtype, [&](auto t) { return row_control_launch<decltype(t), false, false>(a, s); });
 }
 
 // ---- per-row step options: tdeq_row_control_points / tdeq_row_select / tdeq_row_impulse -------------------------------
@@ -418,7 +371,7 @@ int tdeq_row_control_points(int mode, const double* part, const tdeq_step_ctrl* 
     const int e = row_control_args(a, mode, part, ctrl, st, dts_out, times_out, dtype, 3, s, launch);
     if (e || !launch) return e;
     a.pts = *pts;
-    return row_dtype(dtype, [&](auto t) {                // a solve with impulses: the closed rule for the jump table
+    return real_dtype(dtype, [&](auto t) {                // a solve with impulses: the closed rule for the jump table
         return pts->jump_hit ? row_control_launch<decltype(t), true, true>(a, s)
                              : row_control_launch<decltype(t), true, false>(a, s);
     });
@@ -426,14 +379,14 @@ int tdeq_row_control_points(int mode, const double* part, const tdeq_step_ctrl* 
 
 int tdeq_row_select(void* dst, const void* src, const int32_t* mask, int64_t n_rows, int64_t row_len, int dtype,
                     void* stream) {
-    if (!dst || !src || !mask || n_rows < 0 || row_len < 1 || !row_dtype_ok(dtype)) return TDEQ_EINVAL;
+    if (!dst || !src || !mask || n_rows < 0 || row_len < 1 || !real_dtype_ok(dtype)) return TDEQ_EINVAL;
     if (n_rows == 0) return 0;
     hipStream_t s = static_cast<hipStream_t>(stream);
     RowSelectArgs a;
     a.dst = dst;
     a.src = src;
     a.mask = mask;
-    return row_elem(dtype, row_len, row_aligned(dst, src), [&](auto e, int64_t row_len_e) {
+    return row_elem(dtype, row_len, all_aligned(dst, src), [&](auto e, int64_t row_len_e) {
         a.row_len = row_len_e;
         a.ne = n_rows * row_len_e;
         hipLaunchKernelGGL((row_select_kernel<decltype(e)>), dim3(stream_grid(a.ne, kBlock)), dim3(kBlock), 0, s, a);
@@ -444,7 +397,7 @@ int tdeq_row_select(void* dst, const void* src, const int32_t* mask, int64_t n_r
 int tdeq_row_impulse(void* y, const void* dy, int64_t dy_rows, const int32_t* dy_index, int64_t n_orig,
                      const int32_t* jump_hit, const int32_t* jumped, const int32_t* row_map, int64_t n_rows, int64_t row_len,
                      int dtype, void* stream) {
-    if (!y || !dy || !dy_index || !jump_hit || !jumped || n_rows < 0 || row_len < 1 || !row_dtype_ok(dtype)) return TDEQ_EINVAL;
+    if (!y || !dy || !dy_index || !jump_hit || !jumped || n_rows < 0 || row_len < 1 || !real_dtype_ok(dtype)) return TDEQ_EINVAL;
     if (n_orig < 1 || (dy_rows != 1 && dy_rows != n_orig)) return TDEQ_EINVAL;
     if (n_rows == 0) return 0;
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -457,7 +410,7 @@ int tdeq_row_impulse(void* y, const void* dy, int64_t dy_rows, const int32_t* dy
     a.row_map = row_map;
     a.dy_rows = dy_rows;
     a.n_orig = n_orig;
-    return row_elem(dtype, row_len, row_aligned(y, dy), [&](auto e, int64_t row_len_e) {
+    return row_elem(dtype, row_len, all_aligned(y, dy), [&](auto e, int64_t row_len_e) {
         a.row_len = row_len_e;
         a.ne = n_rows * row_len_e;
         hipLaunchKernelGGL((row_impulse_kernel<decltype(e)>), dim3(stream_grid(a.ne, kBlock)), dim3(kBlock), 0, s, a);
@@ -468,12 +421,12 @@ int tdeq_row_impulse(void* y, const void* dy, int64_t dy_rows, const int32_t* dy
 int tdeq_row_dense_commit(void* sol, void* y0, const void* y1, void* f0, const void* f1, const void* const* k,
                           const double* coef, int n_terms, const void* dts, const tdeq_row_state* st, int dtype,
                           void* stream) {
-    if (!sol || !y0 || !y1 || !f0 || !f1 || !k || !coef || !dts || !st || !row_dtype_ok(dtype)) return TDEQ_EINVAL;
+    if (!sol || !y0 || !y1 || !f0 || !f1 || !k || !coef || !dts || !st || !real_dtype_ok(dtype)) return TDEQ_EINVAL;
     if (n_terms < 1 || n_terms > TDEQ_MAX_TERMS || st->n_rows < 0 || st->row_len < 1) return TDEQ_EINVAL;
     for (int j = 0; j < n_terms; ++j) if (!k[j]) return TDEQ_EINVAL;
     if (st->n_rows == 0) return 0;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    return row_dtype_terms<1>(dtype, n_terms, [&](auto t, auto n) {
+    return real_dtype_terms<1>(dtype, n_terms, [&](auto t, auto n) {
         return row_dense_n<decltype(t), decltype(n)::value, false>(sol, nullptr, 0, y0, y1, f0, f1, k, coef, dts, st, s);
     });
 }
@@ -481,12 +434,12 @@ int tdeq_row_dense_commit(void* sol, void* y0, const void* y1, void* f0, const v
 // ---- compaction of a rowwise batch: tdeq_row_gather / tdeq_row_dense_commit_mapped ------------------------------------
 int tdeq_row_gather(void* const* dst, const void* const* src, int n_src, const int32_t* idx, int64_t n_idx,
                     int64_t row_len, int dtype, void* stream) {
-    if (!dst || !src || !idx || n_src < 1 || n_src > kMaxGather || n_idx < 0 || row_len < 1 || !row_dtype_ok(dtype))
+    if (!dst || !src || !idx || n_src < 1 || n_src > kMaxGather || n_idx < 0 || row_len < 1 || !real_dtype_ok(dtype))
         return TDEQ_EINVAL;
     for (int m = 0; m < n_src; ++m) if (!dst[m] || !src[m]) return TDEQ_EINVAL;
     if (n_idx == 0) return 0;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const bool aligned = row_aligned(RowPtrs{dst, n_src}, RowPtrs{src, n_src});
+    const bool aligned = all_aligned(Ptrs{dst, n_src}, Ptrs{src, n_src});
     return row_elem(dtype, row_len, aligned, [&](auto e, int64_t row_len_e) {
         return row_gather_dispatch<decltype(e)>(dst, src, n_src, idx, n_idx, row_len_e, s);
     });
@@ -495,13 +448,13 @@ int tdeq_row_gather(void* const* dst, const void* const* src, int n_src, const i
 int tdeq_row_dense_commit_mapped(void* sol, const int32_t* row_map, int64_t sol_rows, void* y0, const void* y1, void* f0,
                                  const void* f1, const void* const* k, const double* coef, int n_terms, const void* dts,
                                  const tdeq_row_state* st, int dtype, void* stream) {
-    if (!sol || !row_map || !y0 || !y1 || !f0 || !f1 || !k || !coef || !dts || !st || !row_dtype_ok(dtype)) return TDEQ_EINVAL;
+    if (!sol || !row_map || !y0 || !y1 || !f0 || !f1 || !k || !coef || !dts || !st || !real_dtype_ok(dtype)) return TDEQ_EINVAL;
     if (n_terms < 1 || n_terms > TDEQ_MAX_TERMS || st->n_rows < 0 || st->row_len < 1) return TDEQ_EINVAL;
     if (sol_rows < 1 || sol_rows < st->n_rows) return TDEQ_EINVAL;
     for (int j = 0; j < n_terms; ++j) if (!k[j]) return TDEQ_EINVAL;
     if (st->n_rows == 0) return 0;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    return row_dtype_terms<1>(dtype, n_terms, [&](auto t, auto n) {
+    return real_dtype_terms<1>(dtype, n_terms, [&](auto t, auto n) {
         return row_dense_n<decltype(t), decltype(n)::value, true>(sol, row_map, sol_rows, y0, y1, f0, f1, k, coef, dts, st,
                                                                    s);
     });
@@ -518,7 +471,7 @@ int row_scale_n(void* const* outs, const void* g, const void* w, int64_t n_rows,
     a.n_rows = n_rows;
     a.n = n_rows * row_len;
     for (int j = 0; j < NT; ++j) a.out[j] = static_cast<T*>(outs[j]);
-    return row_vec<T>(row_len, row_aligned(g, RowPtrs{outs, NT}), a.row_len, [&](auto vec) {
+    return row_vec<T>(row_len, all_aligned(g, Ptrs{outs, NT}), a.row_len, [&](auto vec) {
         hipLaunchKernelGGL((row_scale_many_kernel<T, NT, decltype(vec)::value>),
                            dim3(stream_grid(n_rows * a.row_len, kBlock)), dim3(kBlock), 0, s, a);
         return check_launch();
@@ -532,7 +485,7 @@ int row_dot_n(const void* g, const void* const* x, int64_t n_rows, int64_t row_l
     RowDotArgs<T, NT> a;
     a.g = static_cast<const T*>(g);
     for (int j = 0; j < NT; ++j) a.x[j] = static_cast<const T*>(x[j]);
-    const bool vec = geo.lv > 1 && row_aligned(g, RowPtrs{x, NT});
+    const bool vec = geo.lv > 1 && all_aligned(g, Ptrs{x, NT});
     if (geo.lv > 1 && !vec) return TDEQ_EINVAL;      // (the geometry, hence the sums, must not depend on alignment)
     a.row_len = geo.nv;
     a.n_rows = n_rows;
@@ -540,7 +493,7 @@ int row_dot_n(const void* g, const void* const* x, int64_t n_rows, int64_t row_l
     a.nch = (int)geo.nch;
     a.group = geo.group;
     a.out = geo.nch == 1 ? out : ws;                 // one chunk per row: the chunk sums are the results, [NT, B]
-    const int e = row_bool(vec, [&](auto v) {
+    const int e = flag(vec, [&](auto v) {
         constexpr bool VEC = decltype(v)::value;
         if (geo.group > 0) {
             const dim3 grid((unsigned)((n_rows * geo.group + kBlock - 1) / kBlock));
@@ -566,25 +519,25 @@ int row_dot_n(const void* g, const void* const* x, int64_t n_rows, int64_t row_l
 
 int tdeq_row_scale_many(void* const* outs, int n_out, const void* g, const void* w, int64_t n_rows, int64_t row_len,
                         int dtype, void* stream) {
-    if (!outs || !g || !w || n_rows < 0 || row_len < 0 || !row_dtype_ok(dtype)) return TDEQ_EINVAL;
+    if (!outs || !g || !w || n_rows < 0 || row_len < 0 || !real_dtype_ok(dtype)) return TDEQ_EINVAL;
     if (n_out < 1 || n_out > TDEQ_MAX_TERMS) return TDEQ_EINVAL;
     for (int j = 0; j < n_out; ++j) if (!outs[j]) return TDEQ_EINVAL;
     if (n_rows == 0 || row_len == 0) return 0;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    return row_dtype_terms<1>(dtype, n_out, [&](auto t, auto n) {
+    return real_dtype_terms<1>(dtype, n_out, [&](auto t, auto n) {
         return row_scale_n<decltype(t), decltype(n)::value>(outs, g, w, n_rows, row_len, s);
     });
 }
 
 size_t tdeq_row_dots_workspace_bytes(int64_t n_rows, int64_t row_len, int n_x, int dtype) {
-    if (n_rows < 1 || row_len < 1 || n_x < 1 || !row_dtype_ok(dtype)) return 0;
+    if (n_rows < 1 || row_len < 1 || n_x < 1 || !real_dtype_ok(dtype)) return 0;
     const int64_t nch = row_geom(row_len, dtype).nch;
     return nch == 1 ? 0 : (size_t)n_x * (size_t)n_rows * (size_t)nch * sizeof(double);
 }
 
 int tdeq_row_multi_dot(const void* g, const void* const* x, int n_x, int64_t n_rows, int64_t row_len, double* out,
                        void* workspace, size_t workspace_bytes, int dtype, void* stream) {
-    if (!g || !x || !out || n_rows < 0 || row_len < 0 || !row_dtype_ok(dtype)) return TDEQ_EINVAL;
+    if (!g || !x || !out || n_rows < 0 || row_len < 0 || !real_dtype_ok(dtype)) return TDEQ_EINVAL;
     if (n_x < 1 || n_x > TDEQ_MAX_TERMS) return TDEQ_EINVAL;
     for (int j = 0; j < n_x; ++j) if (!x[j]) return TDEQ_EINVAL;
     if (n_rows == 0) return 0;
@@ -594,7 +547,7 @@ int tdeq_row_multi_dot(const void* g, const void* const* x, int n_x, int64_t n_r
     if (need > 0 && (!workspace || workspace_bytes < need)) return TDEQ_EWORKSPACE;
     if (n_rows * row_geom(row_len, dtype).nch > 0x7fffffffLL) return TDEQ_EINVAL;
     double* ws = static_cast<double*>(workspace);
-    return row_dtype_terms<1>(dtype, n_x, [&](auto t, auto n) {
+    return real_dtype_terms<1>(dtype, n_x, [&](auto t, auto n) {
         return row_dot_n<decltype(t), decltype(n)::value>(g, x, n_rows, row_len, out, ws, s);
     });
 }
@@ -636,7 +589,7 @@ int row_event_eval_launch(void* out, const void* q, const void* x, const int32_t
     a.x = static_cast<const T*>(x);
     a.mask = mask;
     a.n = n_rows * row_len;
-    return row_vec<T>(row_len, row_aligned(out, q), a.row_len, [&](auto vec) {
+    return row_vec<T>(row_len, all_aligned(out, q), a.row_len, [&](auto vec) {
         hipLaunchKernelGGL((row_event_eval_kernel<T, decltype(vec)::value>), dim3(stream_grid(n_rows * a.row_len, kBlock)),
                            dim3(kBlock), 0, s, a);
         return check_launch();
@@ -653,9 +606,9 @@ int row_event_eval_mapped_launch(void* out, const int32_t* dst_map, const void* 
     a.src_map = src_map;
     a.dst_map = dst_map;
     a.q_plane = q_rows * row_len;
-    return row_vec<T>(row_len, row_aligned(out, q), a.row_len, [&](auto vec) {
+    return row_vec<T>(row_len, all_aligned(out, q), a.row_len, [&](auto vec) {
         a.ne = n_idx * a.row_len;
-        return row_bool(dst_map != nullptr, [&](auto dst) {
+        return flag(dst_map != nullptr, [&](auto dst) {
             hipLaunchKernelGGL((row_event_eval_mapped_kernel<T, decltype(vec)::value, decltype(dst)::value>),
                                dim3(stream_grid(a.ne, kBlock)), dim3(kBlock), 0, s, a);
             return check_launch();
@@ -668,7 +621,7 @@ int row_event_eval_mapped_launch(void* out, const int32_t* dst_map, const void* 
 int tdeq_row_event_detect(const void* g1, const int32_t* sign0, const tdeq_step_ctrl* ctrl, const tdeq_row_state* st,
                           void* dts, void* times, int32_t* fired, int32_t* fired_now, double* lo, double* hi, int dtype,
                           void* stream) {
-    if (!g1 || !sign0 || !ctrl || !st || !dts || !times || !fired || !fired_now || !lo || !hi || !row_dtype_ok(dtype))
+    if (!g1 || !sign0 || !ctrl || !st || !dts || !times || !fired || !fired_now || !lo || !hi || !real_dtype_ok(dtype))
         return TDEQ_EINVAL;
     if (st->n_rows < 0 || !st->accepted || !st->tprev || !st->t0 || !st->active || !st->status) return TDEQ_EINVAL;
     if (ctrl->n_times < 1 || ctrl->n_times > TDEQ_MAX_STAGE_TIMES) return TDEQ_EINVAL;
@@ -692,7 +645,7 @@ int tdeq_row_event_detect(const void* g1, const int32_t* sign0, const tdeq_step_
     a.hi = hi;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const dim3 grid((unsigned)((a.n_rows + kBlock - 1) / kBlock));
-    return row_dtype(dtype, [&](auto t) {
+    return real_dtype(dtype, [&](auto t) {
         hipLaunchKernelGGL((row_event_detect_kernel<decltype(t)>), grid, dim3(kBlock), 0, s, a);
         return check_launch();
     });
@@ -701,12 +654,12 @@ int tdeq_row_event_detect(const void* g1, const int32_t* sign0, const tdeq_step_
 int tdeq_row_event_fit(void* q, const int32_t* fired_now, const void* y0, const void* y1, const void* f0, const void* f1,
                        const void* const* k, const double* coef, int n_terms, const void* dts, int64_t n_rows,
                        int64_t row_len, int dtype, void* stream) {
-    if (!q || !fired_now || !y0 || !y1 || !f0 || !f1 || !k || !coef || !dts || !row_dtype_ok(dtype)) return TDEQ_EINVAL;
+    if (!q || !fired_now || !y0 || !y1 || !f0 || !f1 || !k || !coef || !dts || !real_dtype_ok(dtype)) return TDEQ_EINVAL;
     if (n_terms < 1 || n_terms > TDEQ_MAX_TERMS || n_rows < 0 || row_len < 1) return TDEQ_EINVAL;
     for (int j = 0; j < n_terms; ++j) if (!k[j]) return TDEQ_EINVAL;
     if (n_rows == 0) return 0;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    return row_dtype_terms<1>(dtype, n_terms, [&](auto t, auto n) {
+    return real_dtype_terms<1>(dtype, n_terms, [&](auto t, auto n) {
         return row_event_fit_n<decltype(t), decltype(n)::value, false>(q, nullptr, 0, fired_now, y0, y1, f0, f1, k, coef,
                                                                         dts, n_rows, row_len, s);
     });
@@ -714,10 +667,10 @@ int tdeq_row_event_fit(void* q, const int32_t* fired_now, const void* y0, const 
 
 int tdeq_row_event_eval(void* out, const void* q, const void* x, const int32_t* mask, int64_t n_rows, int64_t row_len,
                         int dtype, void* stream) {
-    if (!out || !q || !x || !mask || n_rows < 0 || row_len < 1 || !row_dtype_ok(dtype)) return TDEQ_EINVAL;
+    if (!out || !q || !x || !mask || n_rows < 0 || row_len < 1 || !real_dtype_ok(dtype)) return TDEQ_EINVAL;
     if (n_rows == 0) return 0;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    return row_dtype(dtype, [&](auto t) {
+    return real_dtype(dtype, [&](auto t) {
         return row_event_eval_launch<decltype(t)>(out, q, x, mask, n_rows, row_len, s);
     });
 }
@@ -725,14 +678,14 @@ int tdeq_row_event_eval(void* out, const void* q, const void* x, const int32_t* 
 int tdeq_row_event_fit_mapped(void* q, const int32_t* row_map, int64_t q_rows, const int32_t* fired_now, const void* y0,
                               const void* y1, const void* f0, const void* f1, const void* const* k, const double* coef,
                               int n_terms, const void* dts, int64_t n_rows, int64_t row_len, int dtype, void* stream) {
-    if (!q || !row_map || !fired_now || !y0 || !y1 || !f0 || !f1 || !k || !coef || !dts || !row_dtype_ok(dtype))
+    if (!q || !row_map || !fired_now || !y0 || !y1 || !f0 || !f1 || !k || !coef || !dts || !real_dtype_ok(dtype))
         return TDEQ_EINVAL;
     if (n_terms < 1 || n_terms > TDEQ_MAX_TERMS || n_rows < 0 || q_rows < 0 || row_len < 1) return TDEQ_EINVAL;
     for (int j = 0; j < n_terms; ++j) if (!k[j]) return TDEQ_EINVAL;
     if (n_rows == 0) return 0;
     if (q_rows < n_rows) return TDEQ_EINVAL;          // (row_map names n_rows different rows of q)
     hipStream_t s = static_cast<hipStream_t>(stream);
-    return row_dtype_terms<1>(dtype, n_terms, [&](auto t, auto n) {
+    return real_dtype_terms<1>(dtype, n_terms, [&](auto t, auto n) {
         return row_event_fit_n<decltype(t), decltype(n)::value, true>(q, row_map, q_rows, fired_now, y0, y1, f0, f1, k, coef,
                                                                        dts, n_rows, row_len, s);
     });
@@ -740,12 +693,12 @@ int tdeq_row_event_fit_mapped(void* q, const int32_t* row_map, int64_t q_rows, c
 
 int tdeq_row_event_eval_mapped(void* out, const int32_t* dst_map, int64_t out_rows, const void* q, const int32_t* src_map,
                                int64_t q_rows, const void* x, int64_t n_idx, int64_t row_len, int dtype, void* stream) {
-    if (!out || !q || !src_map || !x || !row_dtype_ok(dtype)) return TDEQ_EINVAL;
+    if (!out || !q || !src_map || !x || !real_dtype_ok(dtype)) return TDEQ_EINVAL;
     if (n_idx < 0 || out_rows < 0 || q_rows < 0 || row_len < 1) return TDEQ_EINVAL;
     if (n_idx == 0) return 0;
     if (q_rows < 1 || out_rows < 1 || (!dst_map && out_rows < n_idx)) return TDEQ_EINVAL;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    return row_dtype(dtype, [&](auto t) {
+    return real_dtype(dtype, [&](auto t) {
         return row_event_eval_mapped_launch<decltype(t)>(out, dst_map, q, src_map, q_rows, x, n_idx, row_len, s);
     });
 }
@@ -781,7 +734,7 @@ int tdeq_row_dense_slots(const tdeq_row_state* st, const int32_t* row_map, int64
 
 int tdeq_row_dense_pack(void* dst, int64_t dst_rows, const void* src, int64_t src_rows, const int64_t* dest, int64_t n_used,
                         int64_t row_len, int dtype, void* stream) {
-    if (!dst || !src || !dest || !row_dtype_ok(dtype)) return TDEQ_EINVAL;
+    if (!dst || !src || !dest || !real_dtype_ok(dtype)) return TDEQ_EINVAL;
     if (dst_rows < 0 || src_rows < 0 || n_used < 0 || row_len < 1 || n_used > src_rows) return TDEQ_EINVAL;
     if (n_used == 0) return 0;
     if (dst_rows < 1) return TDEQ_EINVAL;
@@ -791,7 +744,7 @@ int tdeq_row_dense_pack(void* dst, int64_t dst_rows, const void* src, int64_t sr
     a.dest = dest;
     hipStream_t s = static_cast<hipStream_t>(stream);
     // (16-byte elements: row_len is a whole number of them, so every row start and every plane is aligned as its base is)
-    return row_elem(dtype, row_len, row_aligned(dst, src), [&](auto e, int64_t row_len_e) {
+    return row_elem(dtype, row_len, all_aligned(dst, src), [&](auto e, int64_t row_len_e) {
         a.row_len = row_len_e;
         a.ne = n_used * row_len_e;
         a.dst_plane = dst_rows * row_len_e;
@@ -804,7 +757,7 @@ int tdeq_row_dense_pack(void* dst, int64_t dst_rows, const void* src, int64_t sr
 int tdeq_row_dense_search(const double* tq, int64_t n_q, const int64_t* offsets, const double* seg_ta, const double* seg_tb,
                           int64_t n_seg, const double* t0, const double* t1, int64_t n_rows, int32_t* seg, void* x,
                           int32_t* status, int dtype, void* stream) {
-    if (!tq || !offsets || !seg_ta || !seg_tb || !t0 || !t1 || !seg || !x || !status || !row_dtype_ok(dtype))
+    if (!tq || !offsets || !seg_ta || !seg_tb || !t0 || !t1 || !seg || !x || !status || !real_dtype_ok(dtype))
         return TDEQ_EINVAL;
     if (n_q < 0 || n_rows < 0 || n_seg < 0) return TDEQ_EINVAL;
     if (n_q == 0 || n_rows == 0) return 0;
@@ -825,7 +778,7 @@ int tdeq_row_dense_search(const double* tq, int64_t n_q, const int64_t* offsets,
     a.status = status;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const dim3 grid((unsigned)((a.n + kBlock - 1) / kBlock));
-    return row_dtype(dtype, [&](auto t) {
+    return real_dtype(dtype, [&](auto t) {
         hipLaunchKernelGGL((row_dense_search_kernel<decltype(t)>), grid, dim3(kBlock), 0, s, a);
         return check_launch();
     });
@@ -845,7 +798,7 @@ int row_dense_prefix_launch(double* prefix, const void* coeffs, const int64_t* o
     a.seg_tb = seg_tb;
     a.n_seg = n_seg;
     a.q_plane = n_seg * row_len;
-    return row_vec<T>(row_len, row_aligned(prefix, coeffs), a.row_len, [&](auto vec) {
+    return row_vec<T>(row_len, all_aligned(prefix, coeffs), a.row_len, [&](auto vec) {
         a.ne = n_rows * a.row_len;
         hipLaunchKernelGGL((row_dense_prefix_kernel<T, decltype(vec)::value>), dim3(stream_grid(a.ne, kBlock)), dim3(kBlock),
                            0, s, a);
@@ -872,7 +825,7 @@ int row_dense_calc_launch(void* out, int mode, const void* coeffs, int64_t n_seg
     a.x2 = static_cast<const T*>(x2);
     a.tq2 = tq2;
     a.q_plane = n_seg * row_len;
-    return row_vec<T>(row_len, row_aligned(out, coeffs, prefix), a.row_len, [&](auto vec) {
+    return row_vec<T>(row_len, all_aligned(out, coeffs, prefix), a.row_len, [&](auto vec) {
         constexpr bool VEC = decltype(vec)::value;
         a.ne = n_idx * a.row_len;
         const dim3 grid(stream_grid(a.ne, kBlock)), block(kBlock);
@@ -888,12 +841,12 @@ int row_dense_calc_launch(void* out, int mode, const void* coeffs, int64_t n_seg
 
 int tdeq_row_dense_prefix(double* prefix, const void* coeffs, const int64_t* offsets, const double* seg_ta,
                           const double* seg_tb, int64_t n_seg, int64_t n_rows, int64_t row_len, int dtype, void* stream) {
-    if (!prefix || !coeffs || !offsets || !seg_ta || !seg_tb || !row_dtype_ok(dtype)) return TDEQ_EINVAL;
+    if (!prefix || !coeffs || !offsets || !seg_ta || !seg_tb || !real_dtype_ok(dtype)) return TDEQ_EINVAL;
     if (n_seg < 0 || n_rows < 0 || row_len < 1) return TDEQ_EINVAL;
     if (n_rows == 0 || n_seg == 0) return 0;
     if (n_seg > 0x7fffffffLL) return TDEQ_EINVAL;      // (a segment index is an int32 word everywhere else)
     hipStream_t s = static_cast<hipStream_t>(stream);
-    return row_dtype(dtype, [&](auto t) {
+    return real_dtype(dtype, [&](auto t) {
         return row_dense_prefix_launch<decltype(t)>(prefix, coeffs, offsets, seg_ta, seg_tb, n_seg, n_rows, row_len, s);
     });
 }
@@ -902,7 +855,7 @@ int tdeq_row_dense_calc(void* out, int mode, const void* coeffs, int64_t n_seg, 
                         const double* prefix, double time_sign, const int32_t* seg, const void* x, const double* tq,
                         const int32_t* seg2, const void* x2, const double* tq2, int64_t n_idx, int64_t row_len, int dtype,
                         void* stream) {
-    if (!out || !coeffs || !seg_ta || !seg_tb || !seg || !x || !row_dtype_ok(dtype)) return TDEQ_EINVAL;
+    if (!out || !coeffs || !seg_ta || !seg_tb || !seg || !x || !real_dtype_ok(dtype)) return TDEQ_EINVAL;
     if (mode != TDEQ_DENSE_DERIVATIVE && mode != TDEQ_DENSE_ANTIDERIVATIVE && mode != TDEQ_DENSE_INTEGRAL) return TDEQ_EINVAL;
     if (mode != TDEQ_DENSE_DERIVATIVE && (!prefix || !tq)) return TDEQ_EINVAL;
     if (mode == TDEQ_DENSE_INTEGRAL && (!seg2 || !x2 || !tq2)) return TDEQ_EINVAL;
@@ -911,7 +864,7 @@ int tdeq_row_dense_calc(void* out, int mode, const void* coeffs, int64_t n_seg, 
     if (n_idx == 0) return 0;
     if (n_seg < 1 || n_seg > 0x7fffffffLL) return TDEQ_EINVAL;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    return row_dtype(dtype, [&](auto t) {
+    return real_dtype(dtype, [&](auto t) {
         return row_dense_calc_launch<decltype(t)>(out, mode, coeffs, n_seg, seg_ta, seg_tb, prefix, time_sign, seg, x, tq,
                                                   seg2, x2, tq2, n_idx, row_len, s);
     });
@@ -940,7 +893,7 @@ int row_dense_extremum_launch(void* values, double* times, int which, const void
     a.tq2 = tq2;
     a.n_seg = n_seg;
     a.q_plane = n_seg * row_len;
-    return row_vec<T>(row_len, row_aligned(values, times, coeffs), a.row_len, [&](auto vec) {
+    return row_vec<T>(row_len, all_aligned(values, times, coeffs), a.row_len, [&](auto vec) {
         constexpr bool VEC = decltype(vec)::value;
         a.ne = n_idx * a.row_len;
         const dim3 grid(stream_grid(a.ne, kBlock)), block(kBlock);
@@ -956,7 +909,7 @@ int tdeq_row_dense_extremum(void* values, double* times, int which, const void* 
                             const double* seg_tb, double time_sign, const int32_t* seg, const void* x, const double* tq,
                             const int32_t* seg2, const void* x2, const double* tq2, int64_t n_idx, int64_t row_len, int dtype,
                             void* stream) {
-    if (!values || !times || !coeffs || !seg_ta || !seg_tb || !seg || !x || !tq || !seg2 || !x2 || !tq2 || !row_dtype_ok(dtype))
+    if (!values || !times || !coeffs || !seg_ta || !seg_tb || !seg || !x || !tq || !seg2 || !x2 || !tq2 || !real_dtype_ok(dtype))
         return TDEQ_EINVAL;
     if (which != TDEQ_DENSE_MAXIMUM && which != TDEQ_DENSE_MINIMUM) return TDEQ_EINVAL;
     if (!(time_sign == 1.0 || time_sign == -1.0)) return TDEQ_EINVAL;
@@ -964,7 +917,7 @@ int tdeq_row_dense_extremum(void* values, double* times, int which, const void* 
     if (n_idx == 0 || row_len == 0) return 0;
     if (n_seg < 1 || n_seg > 0x7fffffffLL) return TDEQ_EINVAL;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    return row_dtype(dtype, [&](auto t) {
+    return real_dtype(dtype, [&](auto t) {
         return row_dense_extremum_launch<decltype(t)>(values, times, which, coeffs, n_seg, seg_ta, seg_tb, time_sign, seg, x,
                                                       tq, seg2, x2, tq2, n_idx, row_len, s);
     });
@@ -999,7 +952,7 @@ int row_dense_level_launch(int32_t* count, double* first, double* last, double* 
     a.q_plane = n_seg * row_len;
     // `count` is stored as one word of 16 / sizeof(T) int32: 16 bytes for float, 8 for double
     const bool count_ok = reinterpret_cast<uintptr_t>(count) % (sizeof(int32_t) * (16 / sizeof(T))) == 0;
-    return row_vec<T>(row_len, count_ok && row_aligned(first, last, time_above, level, coeffs), a.row_len, [&](auto vec) {
+    return row_vec<T>(row_len, count_ok && all_aligned(first, last, time_above, level, coeffs), a.row_len, [&](auto vec) {
         constexpr bool VEC = decltype(vec)::value;
         a.ne = n_idx * a.row_len;
         hipLaunchKernelGGL((row_dense_level_kernel<T, VEC>), dim3(stream_grid(a.ne, kBlock)), dim3(kBlock), 0, s, a);
@@ -1014,7 +967,7 @@ int tdeq_row_dense_level(int32_t* count, double* first, double* last, double* ti
                          const int32_t* seg, const void* x, const double* tq, const int32_t* seg2, const void* x2,
                          const double* tq2, int64_t n_idx, int64_t row_len, int dtype, void* stream) {
     if (!count || !first || !last || !time_above || !level || !coeffs || !seg_ta || !seg_tb || !seg || !x || !tq || !seg2 ||
-        !x2 || !tq2 || !row_dtype_ok(dtype))
+        !x2 || !tq2 || !real_dtype_ok(dtype))
         return TDEQ_EINVAL;
     if (!(time_sign == 1.0 || time_sign == -1.0)) return TDEQ_EINVAL;
     if (n_idx < 0 || n_seg < 0 || row_len < 0 || n_rows < 0) return TDEQ_EINVAL;
@@ -1022,7 +975,7 @@ int tdeq_row_dense_level(int32_t* count, double* first, double* last, double* ti
     if (n_idx == 0 || row_len == 0) return 0;
     if (n_seg < 1 || n_seg > 0x7fffffffLL) return TDEQ_EINVAL;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    return row_dtype(dtype, [&](auto t) {
+    return real_dtype(dtype, [&](auto t) {
         return row_dense_level_launch<decltype(t)>(count, first, last, time_above, level, n_rows, coeffs, n_seg, seg_ta, seg_tb,
                                                    time_sign, seg, x, tq, seg2, x2, tq2, n_idx, row_len, s);
     });
