@@ -32,6 +32,8 @@ from typing import Callable, List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
+from ._scalars import operand
+
 Scalar = Optional[torch.Tensor]          # shadow of a time-like scalar (0-dim, requires grad) or None
 
 
@@ -213,7 +215,9 @@ class Ops:
             self.k.fixed_stage(mode, out, y0, ks, ws, dt)
             return out
         T = self.T
-        wT = [float(T(v)) for v in ws]
+        # the weights are SECOND operands: the kernels take them in the state's type for fp32 / fp64 and at float32 next
+        # to a 16-bit state (`_scalars.operand`, as `_fallback.HostKernels.fixed_stage` and csrc/tdeq_kernels_lp.hpp do)
+        wT = [operand(T, v) for v in ws]
         w = [1.0] + [float(T(dt)) * v for v in wT]
         return self._record(lambda o: self.k.fixed_stage(mode, o, y0, ks, ws, dt), [y0, *ks], w,
                             [(dt_shadow, [0.0] + wT)])
@@ -226,7 +230,9 @@ class Ops:
                 out = torch.empty_like(y0)
             self.k.rk4_stage(stage, out, y0, k1, k2, k3, k4, dt)
             return out
-        dtT, third = float(self.T(dt)), float(self.T(1.0 / 3.0))
+        # `* _one_third` and the increment's `* dt` are SECOND operands (`_scalars.operand`: float32 next to a 16-bit state)
+        third = operand(self.T, 1.0 / 3.0)
+        dtT = operand(self.T, dt) if stage == 4 else float(self.T(dt))
         pattern = {1: [third], 2: [-third, 1.0], 3: [1.0, -1.0, 1.0], 4: [0.125, 0.375, 0.375, 0.125]}[stage]
         w = [1.0] + [dtT * p for p in pattern]
         return self._record(lambda o: self.k.rk4_stage(stage, o, y0, k1, k2, k3, k4, dt), [y0] + ks, w,
