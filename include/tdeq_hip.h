@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define TDEQ_ABI_VERSION 33
+#define TDEQ_ABI_VERSION 34
 #define TDEQ_F32 0
 #define TDEQ_F64 1
 /* interleaved (re, im) complex states — accepted by the NORM entry points only (tdeq_error_norm, tdeq_error_norm_partial[_ctrl],
@@ -897,6 +897,52 @@ int tdeq_row_dense_level(int32_t* count, double* first, double* last, double* ti
                          const void* coeffs, int64_t n_seg, const double* seg_ta, const double* seg_tb, double time_sign,
                          const int32_t* seg, const void* x, const double* tq, const int32_t* seg2, const void* x2,
                          const double* tq2, int64_t n_idx, int64_t row_len, int dtype, void* stream);
+
+/*
+ * ---- Area above and below a level over a time window (ABI 34; `RowDenseOutput.exposure` / `.area_above` / `.area_below`) ----
+ * tdeq_row_dense_exposure  for i < n_idx (a query of row i % n_rows; n_idx is a multiple of n_rows) and every element of the
+ *                          row: the integral of max(y - level, 0) and of max(level - y, 0) of the piecewise quartic over the
+ *                          window between the queries tq[i] and tq2[i], and for how long the element is ABOVE the level.
+ *                          `level` [n_rows, row_len] of the state type T; (seg, x, tq), (seg2, x2, tq2) as for
+ *                          tdeq_row_dense_extremum; their order does not matter.  `area_above`, `area_below` of T,
+ *                          `time_above` double, all [n_idx, row_len]; the areas are durations times state units, >= 0.
+ *                          THE ARITHMETIC IS THE CONTRACT.  Everything is fp64, one rounded operation per written operation,
+ *                          nothing contracted; only + - * /, comparisons and fabs.  Per element:
+ *                          Ends, Walk, xlo, xhi, Polynomials, bisect, Isolation, Level function, State machine, Location and
+ *                                   Time of a crossing: those of tdeq_row_dense_level, exactly, so `time_above` is that
+ *                                   function's `time_above`, bit for bit (its `total`, t_up and tz).
+ *                          Area function.  el = e - lev, one subtraction;
+ *                                       K(x) = (((((a*0.2)*x + b*0.25)*x + c*(1.0/3.0))*x + d*0.5)*x + el) * x * h_s
+ *                                   — J_s of tdeq_row_dense_prefix with e replaced by el: the integral of y - level from the
+ *                                   segment's start to x, in solver time.
+ *                          Accumulation.  A_up = A_dn = 0.  A piece q is added under a state st:  A_up = A_up + q if st is
+ *                                   above, else A_dn = A_dn - q.  For every candidate v that is not the first of its segment,
+ *                                   with u the previous candidate of that segment:  without a crossing between them, add
+ *                                   K(v) - K(u) under the current state;  with a crossing at z (the z of Location above, u or v
+ *                                   themselves included), add K(z) - K(u) under the old state, then K(v) - K(z) under the new
+ *                                   one.  The first candidate of a later segment (the right limit at a breakpoint) adds
+ *                                   nothing: a state impulse flips the state there with zero width.  The window's first
+ *                                   candidate adds nothing either.  Pieces are added in the order of the walk; that order is
+ *                                   the contract.  (K(u) may be carried over from the previous visit: the same expression.)
+ *                          Outputs.  area_above = T(A_up < 0 ? 0 : A_up), area_below = T(A_dn < 0 ? 0 : A_dn): one rounding
+ *                                   each (a piece next to a crossing may carry the wrong sign at rounding level);  time_above =
+ *                                   total.  All three are sums of solver-time pieces: the same numbers for an ascending and a
+ *                                   descending solve, and `time_sign` changes nothing.  A NaN phi at any candidate (a NaN level
+ *                                   included), or an out-of-range end (x[i] or x2[i] NaN): all three outputs NaN.
+ *                          area_above - area_below is the integral of y - level over the window up to rounding; like the
+ *                          crossings the answer is exact ON THE RECORD.  One lane per (query, 16-byte element) walks its
+ *                          segments serially; no workspace, nothing cached.  0 <= seg[i], seg2[i] < n_seg (the walk is
+ *                          clamped to the record).  16-byte elements when row_len is a multiple of 16 / sizeof(T) and `coeffs`,
+ *                          `level`, `area_above`, `area_below` and `time_above` are 16-byte aligned; scalar elements otherwise,
+ *                          with the same bits.  Refusals and no-ops are those of tdeq_row_dense_level: a NULL pointer,
+ *                          n_rows <= 0 with n_idx > 0, n_idx no multiple of n_rows, a negative size, n_seg > INT32_MAX, a
+ *                          time_sign other than +1 / -1 or a dtype other than TDEQ_F32 / TDEQ_F64: TDEQ_EINVAL before any
+ *                          launch.  n_idx == 0 or row_len == 0: no-op.
+ */
+int tdeq_row_dense_exposure(void* area_above, void* area_below, double* time_above, const void* level, int64_t n_rows,
+                            const void* coeffs, int64_t n_seg, const double* seg_ta, const double* seg_tb, double time_sign,
+                            const int32_t* seg, const void* x, const double* tq, const int32_t* seg2, const void* x2,
+                            const double* tq2, int64_t n_idx, int64_t row_len, int dtype, void* stream);
 
 /*
  * ---- Per-row step options (ABI 29; `min_step`, `max_step`, `step_t`, `jump_t` of the rowwise family) ----

@@ -18,7 +18,7 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-TDEQ_ABI_VERSION = 33
+TDEQ_ABI_VERSION = 34
 TDEQ_F32, TDEQ_F64 = 0, 1
 TDEQ_C64, TDEQ_C128 = 2, 3        # interleaved complex: the norm entry points only (include/tdeq_hip.h)
 TDEQ_BF16, TDEQ_F16 = 4, 5        # reduced-precision states: the entry points of the host-driven step (LowPrecisionHipKernels)
@@ -303,6 +303,12 @@ ABI_SIGNATURES = {
                                             ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                             ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int,
                                             ctypes.c_void_p]),
+    # area above and below a level over a time window (ABI 34, `RowDenseOutput.exposure` / `.area_above` / `.area_below`)
+    "tdeq_row_dense_exposure": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                               ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
+                                               ctypes.c_void_p, ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p,
+                                               ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                               ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p]),
     # per-row step options (ABI 29, `min_step` / `max_step` / `step_t` / `jump_t` of the rowwise family)
     "tdeq_row_control_points": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(StepCtrl),
                                                ctypes.POINTER(RowState), ctypes.POINTER(RowPoints), ctypes.c_void_p,
@@ -1267,6 +1273,40 @@ class HipKernels:
                                              seg2.data_ptr(), x2.data_ptr(), tq2.data_ptr(), n_idx, L, dtype_code(T),
                                              self._stream()),
                "tdeq_row_dense_level")
+
+    def row_dense_exposure(self, area_above, area_below, time_above, level, coeffs, seg_ta, seg_tb, sign: float, seg, x, tq,
+                           seg2, x2, tq2) -> None:
+        """tdeq_row_dense_exposure: per element the area between the record and `level` [n_rows, L] above and below it on the
+        window between the queries (seg[i], x[i], tq[i]) and (seg2[i], x2[i], tq2[i]) of `row_dense_search` (query i of row
+        i % n_rows), and the time above it.  `area_above`, `area_below` [n_idx, L], `level` and `x`, `x2` [n_idx] of the dtype
+        of `coeffs` [5, n_seg, L]; `time_above` fp64 [n_idx, L]; `seg`, `seg2` int32 [n_idx]; `tq`, `tq2` fp64 with n_idx
+        elements in solver time; `sign` +1.0 or -1.0."""
+        n_idx = seg.numel()
+        if n_idx == 0:
+            return
+        n_seg = seg_ta.numel()
+        if coeffs.dim() != 3 or coeffs.shape[:2] != (5, n_seg) or not coeffs.is_contiguous():
+            raise ValueError("row_dense_exposure: coeffs must be a contiguous [5, n_seg, L] tensor")
+        L, T = coeffs.shape[2], coeffs.dtype
+        if level.dim() != 2 or level.shape[1] != L or level.shape[0] == 0 or n_idx % level.shape[0] != 0:
+            raise ValueError(f"row_dense_exposure: level must be [n_rows, {L}] with n_rows dividing the {n_idx} queries")
+        n_rows = level.shape[0]
+        for name, t, dtype, shape in (("area_above", area_above, T, (n_idx, L)), ("area_below", area_below, T, (n_idx, L)),
+                                      ("time_above", time_above, torch.float64, (n_idx, L)), ("level", level, T, (n_rows, L)),
+                                      ("seg_ta", seg_ta, torch.float64, (n_seg,)), ("seg_tb", seg_tb, torch.float64, (n_seg,)),
+                                      ("seg", seg, torch.int32, (n_idx,)), ("x", x, T, (n_idx,)),
+                                      ("tq", tq.view(-1), torch.float64, (n_idx,)), ("seg2", seg2, torch.int32, (n_idx,)),
+                                      ("x2", x2, T, (n_idx,)), ("tq2", tq2.view(-1), torch.float64, (n_idx,))):
+            if tuple(t.shape) != shape or t.dtype != dtype or not t.is_contiguous():
+                raise ValueError(f"row_dense_exposure: {name} must be a contiguous {dtype} {list(shape)} tensor")
+        if not tq.is_contiguous() or not tq2.is_contiguous():
+            raise ValueError("row_dense_exposure: tq and tq2 must be contiguous")
+        _check(self.lib.tdeq_row_dense_exposure(area_above.data_ptr(), area_below.data_ptr(), time_above.data_ptr(),
+                                                level.data_ptr(), n_rows, coeffs.data_ptr(), n_seg, seg_ta.data_ptr(),
+                                                seg_tb.data_ptr(), float(sign), seg.data_ptr(), x.data_ptr(), tq.data_ptr(),
+                                                seg2.data_ptr(), x2.data_ptr(), tq2.data_ptr(), n_idx, L, dtype_code(T),
+                                                self._stream()),
+               "tdeq_row_dense_exposure")
 
 
 class ComplexHipKernels:

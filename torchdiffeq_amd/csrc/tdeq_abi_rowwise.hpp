@@ -980,3 +980,58 @@ int tdeq_row_dense_level(int32_t* count, double* first, double* last, double* ti
                                                    time_sign, seg, x, tq, seg2, x2, tq2, n_idx, row_len, s);
     });
 }
+
+// ---- area above and below a level over a time window: tdeq_row_dense_exposure ---------------------------------------------
+namespace {
+
+template <typename T>
+int row_dense_exposure_launch(void* area_above, void* area_below, double* time_above, const void* level, int64_t n_rows,
+                              const void* coeffs, int64_t n_seg, const double* seg_ta, const double* seg_tb, const int32_t* seg,
+                              const void* x, const double* tq, const int32_t* seg2, const void* x2, const double* tq2,
+                              int64_t n_idx, int64_t row_len, hipStream_t s) {
+    RowDenseExposureArgs<T> a;
+    a.area_above = static_cast<T*>(area_above);
+    a.area_below = static_cast<T*>(area_below);
+    a.total = time_above;
+    a.level = static_cast<const T*>(level);
+    a.q = static_cast<const T*>(coeffs);
+    a.seg_ta = seg_ta;
+    a.seg_tb = seg_tb;
+    a.seg = seg;
+    a.x = static_cast<const T*>(x);
+    a.tq = tq;
+    a.seg2 = seg2;
+    a.x2 = static_cast<const T*>(x2);
+    a.tq2 = tq2;
+    a.n_rows = n_rows;
+    a.n_seg = n_seg;
+    a.q_plane = n_seg * row_len;
+    return row_vec<T>(row_len, all_aligned(area_above, area_below, time_above, level, coeffs), a.row_len, [&](auto vec) {
+        constexpr bool VEC = decltype(vec)::value;
+        a.ne = n_idx * a.row_len;
+        hipLaunchKernelGGL((row_dense_exposure_kernel<T, VEC>), dim3(stream_grid(a.ne, kBlock)), dim3(kBlock), 0, s, a);
+        return check_launch();
+    });
+}
+
+}  // namespace
+
+// (the areas and the time above are durations: `time_sign` is checked and not used)
+int tdeq_row_dense_exposure(void* area_above, void* area_below, double* time_above, const void* level, int64_t n_rows,
+                            const void* coeffs, int64_t n_seg, const double* seg_ta, const double* seg_tb, double time_sign,
+                            const int32_t* seg, const void* x, const double* tq, const int32_t* seg2, const void* x2,
+                            const double* tq2, int64_t n_idx, int64_t row_len, int dtype, void* stream) {
+    if (!area_above || !area_below || !time_above || !level || !coeffs || !seg_ta || !seg_tb || !seg || !x || !tq || !seg2 ||
+        !x2 || !tq2 || !real_dtype_ok(dtype))
+        return TDEQ_EINVAL;
+    if (!(time_sign == 1.0 || time_sign == -1.0)) return TDEQ_EINVAL;
+    if (n_idx < 0 || n_seg < 0 || row_len < 0 || n_rows < 0) return TDEQ_EINVAL;
+    if (n_idx > 0 && (n_rows == 0 || n_idx % n_rows != 0)) return TDEQ_EINVAL;
+    if (n_idx == 0 || row_len == 0) return 0;
+    if (n_seg < 1 || n_seg > 0x7fffffffLL) return TDEQ_EINVAL;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return real_dtype(dtype, [&](auto t) {
+        return row_dense_exposure_launch<decltype(t)>(area_above, area_below, time_above, level, n_rows, coeffs, n_seg, seg_ta,
+                                                      seg_tb, seg, x, tq, seg2, x2, tq2, n_idx, row_len, s);
+    });
+}

@@ -15,7 +15,8 @@
 //                      segment ends) and the fraction x of that step, in the arithmetic of row_dense_commit
 // followed by row_event_eval_mapped on (coeffs, seg, x).  No LDS; plain vector loads and stores; 64-bit element offsets.
 // The derivative, antiderivative and integral of the record (row_dense_prefix, row_dense_calc), its extrema over a time
-// window (row_dense_extremum) and its crossings of a level (row_dense_level) are at the end of the file.
+// window (row_dense_extremum), its crossings of a level (row_dense_level) and its area above and below a level
+// (row_dense_exposure) are at the end of the file.
 #pragma once
 
 #include "tdeq_kernels_rowwise.hpp"
@@ -645,6 +646,160 @@ __global__ __launch_bounds__(kBlock) void row_dense_level_kernel(const RowDenseL
         store_ints<LV>(a.count + i * LV, count);
         store_doubles<LV>(a.first + i * LV, tfirst);
         store_doubles<LV>(a.last + i * LV, tlast);
+        store_doubles<LV>(a.total + i * LV, total);
+    }
+}
+
+// ---- area above and below a level over a time window (ABI 34): RowDenseOutput.exposure / .area_above / .area_below --------
+//   row_dense_exposure   the walk and state machine of row_dense_level, which also integrates y - level piece by piece: K is
+//                        J_s of row_dense_prefix with e - level in place of e, a piece between two neighbouring candidates
+//                        adds K(v) - K(u) to the area above or takes it from the area below by the state, and a crossing at z
+//                        splits its piece there.  Per element the lane keeps above / t_up / total / A_up / A_dn and, inside
+//                        a segment, K of the previous candidate.  The arithmetic is stated in include/tdeq_hip.h; the host
+//                        model is rowwise.py quartic_exposure.
+// A segment without a crossing costs what it costs row_dense_level plus at most 7 evaluations of K.  No LDS, no atomics, no
+// workspace.
+
+template <typename T>
+struct RowDenseExposureArgs {
+    T* area_above;                    // [n_idx, L]
+    T* area_below;                    // [n_idx, L]
+    double* total;                    // [n_idx, L] duration above
+    const T* level;                   // [n_rows, L]
+    const T* q;                       // [5, n_seg, L]
+    const double* seg_ta;             // [n_seg]
+    const double* seg_tb;             // [n_seg]
+    const int32_t* seg;               // [n_idx] one end of each window (row_dense_search)
+    const T* x;                       // [n_idx] NaN marks an out-of-range end
+    const double* tq;                 // [n_idx] solver time
+    const int32_t* seg2;              // the other end
+    const T* x2;
+    const double* tq2;
+    int64_t n_rows;                   // query i belongs to row i % n_rows
+    int64_t n_seg;
+    int64_t row_len;                  // E units
+    int64_t ne;                       // n_idx * row_len
+    int64_t q_plane;                  // n_seg * L elements of T
+};
+
+// K of the header: quartic_integral_one with el in place of e (the coefficients are those the lane holds for phi)
+struct QuarticArea {
+    const QuarticLevel& p;
+    double el, h;
+    __device__ __forceinline__ double operator()(double x) const { return quartic_integral_one(el, p.d, p.c, p.b, p.a, x, h); }
+};
+
+template <typename T, bool VEC>
+__global__ __launch_bounds__(kBlock) void row_dense_exposure_kernel(const RowDenseExposureArgs<T> a) {
+    using E = typename std::conditional<VEC, typename VecOf<T>::type, T>::type;
+    constexpr int LV = VEC ? VecOf<T>::L : 1;
+    const int64_t stride = (int64_t)gridDim.x * kBlock;
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < a.ne; i += stride) {
+        const int64_t r = i / a.row_len;
+        const int64_t el = i - r * a.row_len;
+        int64_t sA = a.seg[r], sB = a.seg2[r];
+        double tqa = a.tq[r], tqb = a.tq2[r];
+        const T xa = a.x[r], xb = a.x2[r];
+        if (tqb < tqa) {
+            const int64_t s = sA;
+            sA = sB;
+            sB = s;
+            const double t = tqa;
+            tqa = tqb;
+            tqb = t;
+        }
+        if (sA < 0) sA = 0;                                           // (nothing is read outside the record)
+        if (sB > a.n_seg - 1) sB = a.n_seg - 1;
+        const bool bad = xa != xa || xb != xb || sA > sB;             // (sA > sB: only from ends the search did not write)
+        T lev[LV];
+        load_lanes<T, E, LV>(a.level, (r % a.n_rows) * a.row_len + el, lev);
+        double t_up[LV], total[LV], a_up[LV], a_dn[LV];
+        bool above[LV], nanv[LV];
+#pragma unroll
+        for (int c = 0; c < LV; ++c) {
+            t_up[c] = total[c] = a_up[c] = a_dn[c] = 0.0;
+            above[c] = false;
+            nanv[c] = bad;
+        }
+        for (int64_t s = bad ? sB + 1 : sA; s <= sB; ++s) {           // serial: segments in order
+            const int64_t at = s * a.row_len + el;
+            T qe[LV], qd[LV], qc[LV], qb[LV], qa[LV];
+            load_lanes<T, E, LV>(a.q, at, qe);
+            load_lanes<T, E, LV>(a.q + a.q_plane, at, qd);
+            load_lanes<T, E, LV>(a.q + 2 * a.q_plane, at, qc);
+            load_lanes<T, E, LV>(a.q + 3 * a.q_plane, at, qb);
+            load_lanes<T, E, LV>(a.q + 4 * a.q_plane, at, qa);
+            const double ta = a.seg_ta[s], tb = a.seg_tb[s];
+            const double h = tb - ta;
+            const bool atA = s == sA, atB = s == sB;
+            const double xlo = atA ? (tqa - ta) / h : 0.0;
+            const double xhi = atB ? (tqb - ta) / h : 1.0;
+#pragma unroll
+            for (int c = 0; c < LV; ++c) {
+                const double b = (double)qb[c], aa = (double)qa[c];
+                const QuarticLevel phi{(double)qe[c], (double)qd[c], (double)qc[c], b, aa, (double)lev[c]};
+                const double c2 = phi.c + phi.c, a4 = 4.0 * aa;
+                const QuarticSlope g{phi.d, c2, 3.0 * b, a4};
+                const QuarticCurvature g1{c2, 6.0 * b, 12.0 * aa};
+                const QuarticArea K{phi, phi.e - phi.lev, h};
+                bool st = above[c], entry = true;                     // entry: the segment's first candidate comes next
+                double up = t_up[c], sum = total[c], aup = a_up[c], adn = a_dn[c], u = xlo, fu = 0.0, ku = 0.0;
+                auto add = [&](double q, bool over) {
+                    if (over) aup = aup + q;
+                    else adn = adn - q;
+                };
+                auto visit = [&](double x) {
+                    const double v = phi(x);
+                    if (v != v) nanv[c] = true;
+                    const bool ab = v > 0.0;
+                    const double kx = K(x);
+                    if (entry && atA) {                               // the window's first candidate sets the state
+                        st = ab;
+                        up = tqa;
+                    } else {
+                        double kz = ku;                               // (no crossing: one piece, K(x) - K(u))
+                        if (ab != st) {
+                            double z = x;                             // (a later segment's first candidate: the breakpoint)
+                            if (!entry) {
+                                if (fu == 0.0) z = u;
+                                else if (v != 0.0) quartic_bisect(phi, u, x, z);
+                                kz = K(z);
+                                add(kz - ku, st);
+                            }
+                            const double tz =
+                                (atA && z == xlo) ? tqa : (atB && z == xhi) ? tqb : z == 0.0 ? ta : z == 1.0 ? tb : ta + z * h;
+                            if (ab) up = tz;
+                            else sum = sum + (tz - up);
+                            st = ab;
+                        }
+                        if (!entry) add(kx - kz, st);
+                    }
+                    entry = false;
+                    u = x;
+                    fu = v;
+                    ku = kx;
+                };
+                quartic_candidates(g, g1, b, aa, a4, xlo, xhi, visit);
+                above[c] = st;
+                t_up[c] = up;
+                total[c] = sum;
+                a_up[c] = aup;
+                a_dn[c] = adn;
+            }
+        }
+        T oa[LV], ob[LV];
+#pragma unroll
+        for (int c = 0; c < LV; ++c) {
+            if (above[c]) total[c] = total[c] + (tqb - t_up[c]);
+            oa[c] = nanv[c] ? (T)__builtin_nan("") : (T)(a_up[c] < 0.0 ? 0.0 : a_up[c]);
+            ob[c] = nanv[c] ? (T)__builtin_nan("") : (T)(a_dn[c] < 0.0 ? 0.0 : a_dn[c]);
+            if (nanv[c]) total[c] = __builtin_nan("");
+        }
+        E w;
+        __builtin_memcpy(&w, oa, sizeof(E));
+        reinterpret_cast<E*>(a.area_above)[i] = w;
+        __builtin_memcpy(&w, ob, sizeof(E));
+        reinterpret_cast<E*>(a.area_below)[i] = w;
         store_doubles<LV>(a.total + i * LV, total);
     }
 }

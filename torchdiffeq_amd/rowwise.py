@@ -1074,6 +1074,95 @@ class HostRowKernels:
             total = np.where(nan, np.nan, total)
         return tuple(torch.from_numpy(np.ascontiguousarray(v)) for v in (count, first, last, total))
 
+    # -- area above and below a level over a window (the arithmetic of tdeq_row_dense_exposure, include/tdeq_hip.h) ----------
+    @staticmethod
+    def quartic_exposure(q, level, ta, tb, sign: float, src, x, tq, src2, x2, tq2):
+        """The area between the record `q` [5, n_seg, L] and `level` [n_rows, L] (query i belongs to row i % n_rows) above and
+        below the level on the windows between the queries (src, x, tq) and (src2, x2, tq2) of the search, per element ->
+        (area_above, area_below in the state's type, time_above fp64), all [n, L].  The walk and the state machine of
+        `quartic_levels`; every piece between two candidates adds its K(v) - K(u) under a mask, split at a crossing.  `sign`
+        changes nothing (durations)."""
+        H = HostRowKernels
+        planes, start, end = q.numpy(), ta.numpy(), tb.numpy()
+        sa, sb = src.numpy().astype(np.int64), src2.numpy().astype(np.int64)
+        qa, qb = tq.numpy().reshape(-1), tq2.numpy().reshape(-1)
+        swap = qb < qa
+        sa, sb = np.where(swap, sb, sa), np.where(swap, sa, sb)
+        qa, qb = np.where(swap, qb, qa), np.where(swap, qa, qb)
+        bad = np.isnan(x.numpy()) | np.isnan(x2.numpy()) | (sa > sb)
+        n, L = sa.size, planes.shape[2]
+        levels = level.numpy().astype(np.float64)[np.arange(n) % level.shape[0]]
+        state, nan = np.zeros((n, L), dtype=bool), np.repeat(bad[:, None], L, axis=1)
+        t_up, total, a_up, a_dn = (np.zeros((n, L)) for _ in range(4))
+        steps = np.where(bad, 0, sb - sa + 1)
+        with np.errstate(all="ignore"):
+            for k in range(int(steps.max()) if n else 0):
+                idx = np.flatnonzero(steps > k)
+                s = sa[idx] + k
+                e, d, c, b, a = (planes[p, s].astype(np.float64) for p in range(5))
+                lev = levels[idx]
+                t_a, t_b = start[s][:, None], end[s][:, None]
+                h = t_b - t_a
+                atA, atB = np.full((idx.size, 1), k == 0), (s == sb[idx])[:, None]
+                t_lo, t_hi = qa[idx][:, None], qb[idx][:, None]
+                xlo = np.broadcast_to(np.where(atA, (t_lo - t_a) / h, 0.0), e.shape)
+                xhi = np.broadcast_to(np.where(atB, (t_hi - t_a) / h, 1.0), e.shape)
+                c2, a4 = c + c, 4.0 * a
+                b3, b6, a12 = 3.0 * b, 6.0 * b, 12.0 * a
+                g = lambda v: d + v * (c2 + v * (b3 + v * a4))           # noqa: E731
+                g1 = lambda v: c2 + v * (b6 + v * a12)                   # noqa: E731
+                phi = lambda v: (e + v * (d + v * (c + v * (b + v * a)))) - lev      # noqa: E731
+                el = e - lev
+                K = lambda v: H._quartic_integral(el, d, c, b, a, v, h)  # noqa: E731
+                st, up, tot, aup, adn, nn = state[idx], t_up[idx], total[idx], a_up[idx], a_dn[idx], nan[idx]
+                entry = np.ones(e.shape, dtype=bool)                     # the segment's first candidate comes next
+                u, fu, ku = xlo, np.zeros(e.shape), np.zeros(e.shape)
+
+                def visit(v, on):
+                    nonlocal st, up, tot, aup, adn, nn, entry, u, fu, ku
+                    fv, kv = phi(v), K(v)
+                    nn = nn | (on & np.isnan(fv))
+                    ab = fv > 0
+                    opening = on & entry & atA                           # the window's first candidate sets the state
+                    cross = on & ~opening & (ab != st)
+                    inside = cross & ~entry                              # (else: a later segment's first candidate)
+                    found, root = H._bisect(phi, u, v, inside & (fu != 0) & (fv != 0))
+                    z = np.where(inside & (fu == 0), u, np.where(found, root, v))
+                    tz = np.where(atA & (z == xlo), t_lo, np.where(atB & (z == xhi), t_hi, np.where(
+                        z == 0.0, t_a, np.where(z == 1.0, t_b, t_a + z * h))))
+                    piece = on & ~entry                                  # u -> v, or u -> z under the old state and z -> v
+                    kz = np.where(inside, K(z), ku)
+                    head = kz - ku
+                    aup, adn = np.where(inside & st, aup + head, aup), np.where(inside & ~st, adn - head, adn)
+                    tail = kv - kz
+                    aup, adn = np.where(piece & ab, aup + tail, aup), np.where(piece & ~ab, adn - tail, adn)
+                    tot = np.where(cross & ~ab, tot + (tz - up), tot)
+                    up = np.where(opening, t_lo, np.where(cross & ab, tz, up))
+                    st = np.where(opening | cross, ab, st)
+                    entry, u, fu, ku = entry & ~on, np.where(on, v, u), np.where(on, fv, fu), np.where(on, kv, ku)
+
+                every = np.ones(e.shape, dtype=bool)
+                x1 = (-b) / a4
+                xm = np.where((a != 0.0) & (xlo < x1) & (x1 < xhi), x1, xlo)
+                f0, root = H._bisect(g1, xlo, xm, xm > xlo)
+                r0 = np.where(f0, root, xlo)
+                f1, root = H._bisect(g1, xm, xhi, every)
+                r1 = np.where(f1, root, r0)
+                visit(xlo, every)
+                for lo, hi in ((xlo, r0), (r0, r1)):
+                    fz, z = H._bisect(g, lo, hi, hi > lo)
+                    visit(z, fz)
+                    visit(hi, hi > lo)
+                fz, z = H._bisect(g, r1, xhi, every)
+                visit(z, fz)
+                visit(xhi, every)
+                state[idx], t_up[idx], total[idx], a_up[idx], a_dn[idx], nan[idx] = st, up, tot, aup, adn, nn
+            total = np.where(state, total + (qb[:, None] - t_up), total)
+            above = np.where(nan, np.nan, np.where(a_up < 0, 0.0, a_up)).astype(planes.dtype)
+            below = np.where(nan, np.nan, np.where(a_dn < 0, 0.0, a_dn)).astype(planes.dtype)
+            total = np.where(nan, np.nan, total)
+        return tuple(torch.from_numpy(np.ascontiguousarray(v)) for v in (above, below, total))
+
     def event_eval_mapped(self, out, dst, q, src, x) -> None:
         """out[dst[i] (None: i), :] = the quartic q[:, src[i]] at x[i], for the index lists `dst`, `src`."""
         if src.numel() == 0:

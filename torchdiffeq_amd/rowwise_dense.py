@@ -18,8 +18,9 @@ and the fraction of the step) followed by `tdeq_row_event_eval_mapped`.  The der
 record are the same search followed by `tdeq_row_dense_calc`; the two integrals read a per-row prefix of whole-step
 integrals that `tdeq_row_dense_prefix` builds on first use.  The maximum and minimum over a time window are the search of both ends followed
 by `tdeq_row_dense_extremum`, which walks the window's segments and builds nothing; the crossings of a level and the time
-above it are the same two searches followed by `tdeq_row_dense_level`, the same walk with a state machine.  CPU states run
-the same steps as torch / numpy ops.
+above it are the same two searches followed by `tdeq_row_dense_level`, the same walk with a state machine; the area between
+the record and a level, above and below it, is the same again with `tdeq_row_dense_exposure`, which integrates `y - level`
+piece by piece while it walks.  CPU states run the same steps as torch / numpy ops.
 """
 from __future__ import annotations
 
@@ -32,7 +33,7 @@ from . import rowwise
 from ._native import device_guard
 from .rowwise import _Problem
 
-__all__ = ["odeint_rowwise_dense", "RowDenseOutput", "RowDenseExtremum", "RowDenseCrossings"]
+__all__ = ["odeint_rowwise_dense", "RowDenseOutput", "RowDenseExtremum", "RowDenseCrossings", "RowDenseExposure"]
 
 # the default chunk: CHUNK_ROWS_PER_ROW slots per row of the batch, at most CHUNK_BYTES of coefficients, never fewer than B
 CHUNK_ROWS_PER_ROW = 4
@@ -180,11 +181,21 @@ class RowDenseCrossings(NamedTuple):
     time_above: torch.Tensor
 
 
+class RowDenseExposure(NamedTuple):
+    """`RowDenseOutput.exposure`: per element the integral of `max(y - level, 0)` and of `max(level - y, 0)` over the window (the
+    state's dtype, >= 0, true-time durations times state units) and the total true-time duration (fp64, >= 0) with `y >
+    level` inside the window, which is `RowDenseCrossings.time_above` bit for bit."""
+    area_above: torch.Tensor
+    area_below: torch.Tensor
+    time_above: torch.Tensor
+
+
 class RowDenseOutput:
     """The piecewise quartic of a rowwise solve; `dense(t)` evaluates it, `derivative(t)`, `antiderivative(t)` and
     `integral(ta, tb)` give its time derivative and its integrals in closed form, `maximum(ta, tb)` and `minimum(ta, tb)` its
     extrema over a time window and their times, `crossings(level, ta, tb)` and `time_above(level, ta, tb)` its crossings of a
-    level and the time spent above it (see `odeint_rowwise_dense`).
+    level and the time spent above it, `exposure(level, ta, tb)`, `area_above(level, ta, tb)` and `area_below(level, ta, tb)`
+    the area between it and a level (see `odeint_rowwise_dense`).
 
     Attributes (the wire format, all on the state's device): `t0`, `t1` `[B]` fp64 in true time; `offsets` `[B + 1]` int64;
     `seg_start`, `seg_end` `[n_seg]` fp64 in true time, row r's segments — its accepted steps — contiguous and in step
@@ -468,6 +479,44 @@ class RowDenseOutput:
                              f"{list(self._shape)}") from None
         return lev.reshape(B, L).contiguous()
 
+    def _level_walk(self, what: str, level, ta, tb, check: bool, host: str, launch: str, dtypes):
+        """The steps of `crossings` and `exposure`: the level, the search per end, one launch (`launch` of the device kernels,
+        `host` of `HostRowKernels` for a CPU state) that fills outputs of `dtypes`, one read of the status words (with `check`)
+        -> (the outputs as `[Q, B, *row_shape]`, both times were single).  Nothing is built or kept."""
+        names = ("ta", "tb")
+        lev = self._level(what, level)
+        tqs, single = self._query_lists(what, names, (ta, tb))
+        Q, B = tqs[0].shape
+        if self._k is not None and Q * B >= _NONE:
+            raise ValueError(f"{what}: {Q * B} queries in one call; the query index is a 32-bit word")
+        L, dev, dtype = self.coeffs.shape[2], self.coeffs.device, self.coeffs.dtype
+        outs = [torch.empty(Q * B, L, dtype=t, device=dev) for t in dtypes]
+        firsts = [_NONE, _NONE]
+        if Q > 0:
+            with torch.no_grad(), device_guard(dev):
+                if self._k is None:
+                    found = [self._search_host(tq) for tq in tqs]
+                    firsts = [bad for _, _, bad in found]
+                    lists = [v for (seg, x, _), tq in zip(found, tqs) for v in (seg, x, tq)]
+                    walked = getattr(rowwise.HostRowKernels, host)(self.coeffs, lev, self._ta, self._tb, self._sign, *lists)
+                    for dst, src in zip(outs, walked):
+                        dst.copy_(src)
+                else:
+                    status = torch.full((2,), _NONE, dtype=torch.int32, device=dev)
+                    lists = []
+                    for i, tq in enumerate(tqs):
+                        seg = torch.empty(Q * B, dtype=torch.int32, device=dev)
+                        x = torch.empty(Q * B, dtype=dtype, device=dev)
+                        self._k.row_dense_search(tq, self.offsets, self._ta, self._tb, self._t0, self._t1, seg, x,
+                                                 status[i:i + 1])
+                        lists += [seg, x, tq]
+                    getattr(self._k, launch)(*outs, lev, self.coeffs, self._ta, self._tb, self._sign, *lists)
+                    if check:
+                        firsts = status.tolist()                          # the one read
+        if check:
+            self._raise_out_of_range(what, names, tqs, firsts)
+        return [v.view(Q, *self._shape) for v in outs], single
+
     def crossings(self, level, ta, tb, check: bool = True) -> RowDenseCrossings:
         """Where every ELEMENT of `y_r` crosses `level` on the window between `ta` and `tb` (true time, in either order: the
         same bits) and for how long it is above it -> `RowDenseCrossings(count, first, last, time_above)`, all `[Q, B,
@@ -483,47 +532,42 @@ class RowDenseOutput:
         `odeint_rowwise_dense`).  The segment that starts at a breakpoint `p` is entered at its start: a `jump_dy` dose at `p`
         inside the window or at its near end that lifts the element over the level is a crossing at time `p`; one at the far
         end is not seen.  Builds and caches nothing."""
-        what = "dense.crossings(level, ta, tb)"
-        names = ("ta", "tb")
-        lev = self._level(what, level)
-        tqs, single = self._query_lists(what, names, (ta, tb))
-        Q, B = tqs[0].shape
-        if self._k is not None and Q * B >= _NONE:
-            raise ValueError(f"{what}: {Q * B} queries in one call; the query index is a 32-bit word")
-        L, dev, dtype = self.coeffs.shape[2], self.coeffs.device, self.coeffs.dtype
-        count = torch.empty(Q * B, L, dtype=torch.int32, device=dev)
-        first, last, above = (torch.empty(Q * B, L, dtype=torch.float64, device=dev) for _ in range(3))
-        firsts = [_NONE, _NONE]
-        if Q > 0:
-            with torch.no_grad(), device_guard(dev):
-                if self._k is None:
-                    found = [self._search_host(tq) for tq in tqs]
-                    firsts = [bad for _, _, bad in found]
-                    lists = [v for (seg, x, _), tq in zip(found, tqs) for v in (seg, x, tq)]
-                    outs = rowwise.HostRowKernels.quartic_levels(self.coeffs, lev, self._ta, self._tb, self._sign, *lists)
-                    for dst, src in zip((count, first, last, above), outs):
-                        dst.copy_(src)
-                else:
-                    status = torch.full((2,), _NONE, dtype=torch.int32, device=dev)
-                    lists = []
-                    for i, tq in enumerate(tqs):
-                        seg = torch.empty(Q * B, dtype=torch.int32, device=dev)
-                        x = torch.empty(Q * B, dtype=dtype, device=dev)
-                        self._k.row_dense_search(tq, self.offsets, self._ta, self._tb, self._t0, self._t1, seg, x,
-                                                 status[i:i + 1])
-                        lists += [seg, x, tq]
-                    self._k.row_dense_level(count, first, last, above, lev, self.coeffs, self._ta, self._tb, self._sign, *lists)
-                    if check:
-                        firsts = status.tolist()                          # the one read
-        if check:
-            self._raise_out_of_range(what, names, tqs, firsts)
-        outs = RowDenseCrossings(*(v.view(Q, *self._shape) for v in (count, first, last, above)))
-        return RowDenseCrossings(*(v[0] for v in outs)) if single else outs
+        outs, single = self._level_walk("dense.crossings(level, ta, tb)", level, ta, tb, check, "quartic_levels",
+                                        "row_dense_level", (torch.int32, torch.float64, torch.float64, torch.float64))
+        return RowDenseCrossings(*(v[0] for v in outs)) if single else RowDenseCrossings(*outs)
 
     def time_above(self, level, ta, tb, check: bool = True) -> torch.Tensor:
         """The total true-time duration every element spends strictly above `level` on the window: `crossings(level, ta, tb,
         check).time_above`, the same launch."""
         return self.crossings(level, ta, tb, check).time_above
+
+    # -- area above and below a level over a time window: the walk of the crossings, integrating as it goes --------------------
+    def exposure(self, level, ta, tb, check: bool = True) -> RowDenseExposure:
+        """The area between every ELEMENT of `y_r` and `level` on the window between `ta` and `tb` (true time, in either order:
+        the same bits) -> `RowDenseExposure(area_above, area_below, time_above)`, all `[Q, B, *row_shape]` (`[B, *row_shape]`
+        for two single times): `area_above` = the integral of `max(y - level, 0)` and `area_below` = the integral of
+        `max(level - y, 0)`, both >= 0 and in the state's dtype (AUC above a threshold, the deficit below a target);
+        `time_above` fp64, the `time_above` of `crossings`, bit for bit.  `level`, `ta`, `tb` and `check` are those of
+        `crossings`: a NaN level gives NaN for that element alone, an out-of-range query with `check=False` NaN in all three
+        fields for its whole row, and nothing is read.  Exact on the record: the walk of `crossings` splits the window at every
+        crossing it finds and adds the closed-form integral of `y - level` over each piece, in fp64, left to right in solver
+        time (see `odeint_rowwise_dense`); `area_above - area_below` is `integral(ta, tb) - level * (tb - ta)` for ascending
+        ends, up to rounding.  A `jump_dy` dose at `p` switches sides at `p` with zero width, for `lo <= p < hi`; a window that
+        ends at `p` does not see it, and `exposure(level, p, p)` is all zeros.  Builds and caches nothing."""
+        T = self.coeffs.dtype
+        outs, single = self._level_walk("dense.exposure(level, ta, tb)", level, ta, tb, check, "quartic_exposure",
+                                        "row_dense_exposure", (T, T, torch.float64))
+        return RowDenseExposure(*(v[0] for v in outs)) if single else RowDenseExposure(*outs)
+
+    def area_above(self, level, ta, tb, check: bool = True) -> torch.Tensor:
+        """The integral of `max(y - level, 0)` over the window, per element: `exposure(level, ta, tb, check).area_above`, the
+        same launch."""
+        return self.exposure(level, ta, tb, check).area_above
+
+    def area_below(self, level, ta, tb, check: bool = True) -> torch.Tensor:
+        """The integral of `max(level - y, 0)` over the window, per element: `exposure(level, ta, tb, check).area_below`, the
+        same launch."""
+        return self.exposure(level, ta, tb, check).area_below
 
 
 def odeint_rowwise_dense(func, y0, t0, t1, *, rtol=1e-7, atol=1e-9, method="dopri5", options=None, compact=None,
@@ -600,6 +644,22 @@ def odeint_rowwise_dense(func, y0, t0, t1, *, rtol=1e-7, atol=1e-9, method="dopr
     rounding level at every breakpoint (the end of one step's quartic and the start of the next may differ in their last
     bits): a level inside such a gap is crossed there once more than the continuous solution would be.  A value that only
     touches the level from below is no crossing.  One launch after the two searches; nothing is built or cached.
+
+    Exposure against a level: `dense.exposure(level, ta, tb)` -> `RowDenseExposure(area_above, area_below, time_above)`, and
+    `dense.area_above(level, ta, tb)` / `dense.area_below(level, ta, tb)` (one field each, the same launch), with the `level`,
+    the query forms and the `check` of `crossings`: per ELEMENT the integral of `max(y - level, 0)` and of `max(level - y, 0)`
+    over the window, in the state's dtype and >= 0 — AUC above MIC, exposure above a toxic level, the deficit below a target
+    trough — and the `time_above` of `crossings`, bit for bit.  No `relu(y - level)` quadrature variable is needed in the
+    state, so `y` keeps its bits, and no sampling grid has to hit the dose times.  The walk, the state machine and the root
+    location are those of `crossings`; between two neighbouring candidates of a step the element stays on one side of the
+    level, so the piece's area is the difference of the closed-form fp64 antiderivative `K` of `y - level` (the `J_s` of
+    `integral` with `e - level` in place of `e`) at its ends, and a piece that holds a crossing is split at the located root.
+    The pieces above are added to one fp64 sum and the pieces below subtracted from another, left to right in solver time;
+    each sum is clamped at 0 and rounded once.  include/tdeq_hip.h states the operation order, which is the contract: the HIP
+    kernel (`tdeq_row_dense_exposure`, ABI 34) and the numpy path of a CPU state have the same bits, a window gives the same
+    bits in either order of its ends, and an ascending and a descending solve of the same record give the same numbers.  A
+    `jump_dy` dose at `p` flips the side at `p` with zero width for `lo <= p < hi`; `exposure(level, p, p)` is all zeros.  One
+    launch after the two searches; nothing is built or cached.
 
     Returns `dense`; with `return_stats=True`, `(dense, stats)`: the stats of `odeint_rowwise` (`n_accepted`,
     `n_rejected`, `nfe`; with `compact` also `row_evals`, `n_repacks`) plus `n_segments` and `n_chunks`.
