@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define TDEQ_ABI_VERSION 34
+#define TDEQ_ABI_VERSION 35
 #define TDEQ_F32 0
 #define TDEQ_F64 1
 /* interleaved (re, im) complex states — accepted by the NORM entry points only (tdeq_error_norm, tdeq_error_norm_partial[_ctrl],
@@ -943,6 +943,46 @@ int tdeq_row_dense_exposure(void* area_above, void* area_below, double* time_abo
                             const void* coeffs, int64_t n_seg, const double* seg_ta, const double* seg_tb, double time_sign,
                             const int32_t* seg, const void* x, const double* tq, const int32_t* seg2, const void* x2,
                             const double* tq2, int64_t n_idx, int64_t row_len, int dtype, void* stream);
+
+/*
+ * ---- The times of all crossings of a level over a time window (ABI 35; `RowDenseOutput.crossing_times`) ----
+ * tdeq_row_dense_level_times  for i < n_idx (a query of row i % n_rows; n_idx is a multiple of n_rows) and every element of
+ *                          the row: the times of the first K = max_count RISING and of the first K FALLING crossings of
+ *                          `level[row, el]` on the window between the queries tq[i] and tq2[i], and how many crossings of
+ *                          each direction the window holds.  `level` [n_rows, row_len] of the state type T; (seg, x, tq),
+ *                          (seg2, x2, tq2) as for tdeq_row_dense_extremum; their order does not matter.  `n_rising`,
+ *                          `n_falling` int32 [n_idx, row_len]; `rising`, `falling` double [K, n_idx, row_len] in TRUE time.
+ *                          THE ARITHMETIC IS THE CONTRACT.  Per element:
+ *                          Ends, Walk, xlo, xhi, Polynomials, bisect, Isolation, Level function, State machine, Location and
+ *                                   Time of a crossing: those of tdeq_row_dense_level, exactly: the crossings are that
+ *                                   function's crossings, in its order, with its tz.
+ *                          Direction.  Rising is defined in TRUE time: y goes from <= level to > level as true time
+ *                                   increases.  The walk runs in solver time, so a crossing after which the state is above is
+ *                                   rising when time_sign > 0 and falling when time_sign < 0:
+ *                                   rising = (state becomes above) == (time_sign > 0).
+ *                          Lists.  Each direction has a counter n, 0 at the start.  A crossing at tz of that direction:  if
+ *                                   n < K, list[n, i, el] = time_sign * tz;  then n += 1.  So a list holds the first K
+ *                                   crossings of its direction in the order of the walk — the direction of the solve:
+ *                                   decreasing true time when time_sign < 0 — and the counting continues past K.  After the
+ *                                   walk the slots min(n, K) .. K - 1 of both lists are NaN and n_rising, n_falling are the
+ *                                   two counters; n_rising + n_falling is the `count` of tdeq_row_dense_level.
+ *                          NaN.  A NaN phi at any candidate (a NaN level included), or an out-of-range end (x[i] or x2[i]
+ *                                   NaN): n_rising = n_falling = -1 and all K slots of both lists NaN.
+ *                          Every slot of the four outputs is written and nothing else.  The remarks of tdeq_row_dense_level
+ *                          on the record (the rounding-level gap at a breakpoint, a touch, a state impulse) hold unchanged.
+ *                          One lane per (query, 16-byte element) walks its segments serially and stores a located time at
+ *                          once, as one 8-byte store; no workspace, nothing cached.  0 <= seg[i], seg2[i] < n_seg (the walk is
+ *                          clamped to the record).  16-byte elements when row_len is a multiple of 16 / sizeof(T), `coeffs`
+ *                          and `level` are 16-byte aligned and `n_rising`, `n_falling` are aligned to their word of
+ *                          16 / sizeof(T) int32; scalar elements otherwise, with the same bits.  `rising` and `falling` put no
+ *                          condition on the form.  Refusals and no-ops are those of tdeq_row_dense_level, plus max_count < 1 or
+ *                          max_count > 65535: TDEQ_EINVAL before any launch.
+ */
+int tdeq_row_dense_level_times(int32_t* n_rising, int32_t* n_falling, double* rising, double* falling, int64_t max_count,
+                               const void* level, int64_t n_rows, const void* coeffs, int64_t n_seg, const double* seg_ta,
+                               const double* seg_tb, double time_sign, const int32_t* seg, const void* x, const double* tq,
+                               const int32_t* seg2, const void* x2, const double* tq2, int64_t n_idx, int64_t row_len,
+                               int dtype, void* stream);
 
 /*
  * ---- Per-row step options (ABI 29; `min_step`, `max_step`, `step_t`, `jump_t` of the rowwise family) ----

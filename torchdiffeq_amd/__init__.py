@@ -12,8 +12,9 @@ from .solvers import clear_graph_cache
 from ._fallback import HostPathWarning
 from .rowwise import odeint_rowwise
 from .rowwise_event import odeint_rowwise_event
-from .rowwise_dense import RowDenseCrossings, RowDenseExposure, odeint_rowwise_dense
+from .rowwise_dense import RowDenseCrossings, RowDenseCrossingTimes, RowDenseExposure, odeint_rowwise_dense
 
 __version__ = "0.1.0"
 __all__ = ["odeint", "odeint_adjoint", "odeint_rowwise", "odeint_rowwise_event", "odeint_rowwise_dense", "odeint_event", "odeint_dense",
-           "SOLVERS", "clear_graph_cache", "HostPathWarning", "RowDenseCrossings", "RowDenseExposure"]
+           "SOLVERS", "clear_graph_cache", "HostPathWarning", "RowDenseCrossings", "RowDenseCrossingTimes",
+           "RowDenseExposure"]

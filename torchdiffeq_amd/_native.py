@@ -18,7 +18,7 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-TDEQ_ABI_VERSION = 34
+TDEQ_ABI_VERSION = 35
 TDEQ_F32, TDEQ_F64 = 0, 1
 TDEQ_C64, TDEQ_C128 = 2, 3        # interleaved complex: the norm entry points only (include/tdeq_hip.h)
 TDEQ_BF16, TDEQ_F16 = 4, 5        # reduced-precision states: the entry points of the host-driven step (LowPrecisionHipKernels)
@@ -309,6 +309,13 @@ ABI_SIGNATURES = {
                                                ctypes.c_void_p, ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p,
                                                ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                                ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p]),
+    # the times of all crossings of a level over a time window (ABI 35, `RowDenseOutput.crossing_times`)
+    "tdeq_row_dense_level_times": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                  ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
+                                                  ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double,
+                                                  ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                  ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
+                                                  ctypes.c_int, ctypes.c_void_p]),
     # per-row step options (ABI 29, `min_step` / `max_step` / `step_t` / `jump_t` of the rowwise family)
     "tdeq_row_control_points": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(StepCtrl),
                                                ctypes.POINTER(RowState), ctypes.POINTER(RowPoints), ctypes.c_void_p,
@@ -1307,6 +1314,47 @@ class HipKernels:
                                                 seg2.data_ptr(), x2.data_ptr(), tq2.data_ptr(), n_idx, L, dtype_code(T),
                                                 self._stream()),
                "tdeq_row_dense_exposure")
+
+
+    def row_dense_level_times(self, n_rising, n_falling, rising, falling, level, coeffs, seg_ta, seg_tb, sign: float, seg, x,
+                              tq, seg2, x2, tq2) -> None:
+        """tdeq_row_dense_level_times: per element the true times of the first K rising and the first K falling crossings of
+        `level` [n_rows, L] on the window between the queries (seg[i], x[i], tq[i]) and (seg2[i], x2[i], tq2[i]) of
+        `row_dense_search` (query i of row i % n_rows), and the number of crossings of each direction.  `n_rising`,
+        `n_falling` int32 [n_idx, L]; `rising`, `falling` fp64 [K, n_idx, L] with K = rising.shape[0]; `level` and `x`, `x2`
+        [n_idx] of the dtype of `coeffs` [5, n_seg, L]; `seg`, `seg2` int32 [n_idx]; `tq`, `tq2` fp64 with n_idx elements in
+        solver time; `sign` +1.0 or -1.0."""
+        n_idx = seg.numel()
+        if n_idx == 0:
+            return
+        n_seg = seg_ta.numel()
+        if coeffs.dim() != 3 or coeffs.shape[:2] != (5, n_seg) or not coeffs.is_contiguous():
+            raise ValueError("row_dense_level_times: coeffs must be a contiguous [5, n_seg, L] tensor")
+        L, T = coeffs.shape[2], coeffs.dtype
+        if level.dim() != 2 or level.shape[1] != L or level.shape[0] == 0 or n_idx % level.shape[0] != 0:
+            raise ValueError(f"row_dense_level_times: level must be [n_rows, {L}] with n_rows dividing the {n_idx} queries")
+        n_rows = level.shape[0]
+        if rising.dim() != 3:
+            raise ValueError("row_dense_level_times: rising must be a [K, n_idx, L] tensor")
+        K = rising.shape[0]
+        for name, t, dtype, shape in (("n_rising", n_rising, torch.int32, (n_idx, L)),
+                                      ("n_falling", n_falling, torch.int32, (n_idx, L)),
+                                      ("rising", rising, torch.float64, (K, n_idx, L)),
+                                      ("falling", falling, torch.float64, (K, n_idx, L)), ("level", level, T, (n_rows, L)),
+                                      ("seg_ta", seg_ta, torch.float64, (n_seg,)), ("seg_tb", seg_tb, torch.float64, (n_seg,)),
+                                      ("seg", seg, torch.int32, (n_idx,)), ("x", x, T, (n_idx,)),
+                                      ("tq", tq.view(-1), torch.float64, (n_idx,)), ("seg2", seg2, torch.int32, (n_idx,)),
+                                      ("x2", x2, T, (n_idx,)), ("tq2", tq2.view(-1), torch.float64, (n_idx,))):
+            if tuple(t.shape) != shape or t.dtype != dtype or not t.is_contiguous():
+                raise ValueError(f"row_dense_level_times: {name} must be a contiguous {dtype} {list(shape)} tensor")
+        if not tq.is_contiguous() or not tq2.is_contiguous():
+            raise ValueError("row_dense_level_times: tq and tq2 must be contiguous")
+        _check(self.lib.tdeq_row_dense_level_times(n_rising.data_ptr(), n_falling.data_ptr(), rising.data_ptr(),
+                                                   falling.data_ptr(), K, level.data_ptr(), n_rows, coeffs.data_ptr(), n_seg,
+                                                   seg_ta.data_ptr(), seg_tb.data_ptr(), float(sign), seg.data_ptr(),
+                                                   x.data_ptr(), tq.data_ptr(), seg2.data_ptr(), x2.data_ptr(), tq2.data_ptr(),
+                                                   n_idx, L, dtype_code(T), self._stream()),
+               "tdeq_row_dense_level_times")
 
 
 class ComplexHipKernels:

@@ -981,6 +981,74 @@ int tdeq_row_dense_level(int32_t* count, double* first, double* last, double* ti
     });
 }
 
+// ---- the times of all crossings of a level over a time window: tdeq_row_dense_level_times ---------------------------------
+namespace {
+
+template <typename T>
+int row_dense_level_times_launch(int32_t* n_rising, int32_t* n_falling, double* rising, double* falling, int64_t max_count,
+                                 const void* level, int64_t n_rows, const void* coeffs, int64_t n_seg, const double* seg_ta,
+                                 const double* seg_tb, double time_sign, const int32_t* seg, const void* x, const double* tq,
+                                 const int32_t* seg2, const void* x2, const double* tq2, int64_t n_idx, int64_t row_len,
+                                 hipStream_t s) {
+    RowDenseLevelTimesArgs<T> a;
+    // rising is meant in true time: rising = (the state becomes above) == (time_sign > 0)
+    const bool up_rises = time_sign > 0.0;
+    a.n_up = up_rises ? n_rising : n_falling;
+    a.n_dn = up_rises ? n_falling : n_rising;
+    a.ups = up_rises ? rising : falling;
+    a.dns = up_rises ? falling : rising;
+    a.k = static_cast<int32_t>(max_count);
+    a.level = static_cast<const T*>(level);
+    a.q = static_cast<const T*>(coeffs);
+    a.seg_ta = seg_ta;
+    a.seg_tb = seg_tb;
+    a.sign = time_sign;
+    a.seg = seg;
+    a.x = static_cast<const T*>(x);
+    a.tq = tq;
+    a.seg2 = seg2;
+    a.x2 = static_cast<const T*>(x2);
+    a.tq2 = tq2;
+    a.n_rows = n_rows;
+    a.n_seg = n_seg;
+    a.q_plane = n_seg * row_len;
+    a.t_plane = n_idx * row_len;
+    // the counters are stored as one word of 16 / sizeof(T) int32 each; the lists take 8-byte stores in either form
+    const uintptr_t word = sizeof(int32_t) * (16 / sizeof(T));
+    const bool counters_ok =
+        reinterpret_cast<uintptr_t>(n_rising) % word == 0 && reinterpret_cast<uintptr_t>(n_falling) % word == 0;
+    return row_vec<T>(row_len, counters_ok && all_aligned(level, coeffs), a.row_len, [&](auto vec) {
+        constexpr bool VEC = decltype(vec)::value;
+        a.ne = n_idx * a.row_len;
+        hipLaunchKernelGGL((row_dense_level_times_kernel<T, VEC>), dim3(stream_grid(a.ne, kBlock)), dim3(kBlock), 0, s, a);
+        return check_launch();
+    });
+}
+
+}  // namespace
+
+int tdeq_row_dense_level_times(int32_t* n_rising, int32_t* n_falling, double* rising, double* falling, int64_t max_count,
+                               const void* level, int64_t n_rows, const void* coeffs, int64_t n_seg, const double* seg_ta,
+                               const double* seg_tb, double time_sign, const int32_t* seg, const void* x, const double* tq,
+                               const int32_t* seg2, const void* x2, const double* tq2, int64_t n_idx, int64_t row_len,
+                               int dtype, void* stream) {
+    if (!n_rising || !n_falling || !rising || !falling || !level || !coeffs || !seg_ta || !seg_tb || !seg || !x || !tq ||
+        !seg2 || !x2 || !tq2 || !real_dtype_ok(dtype))
+        return TDEQ_EINVAL;
+    if (max_count < 1 || max_count > 65535) return TDEQ_EINVAL;
+    if (!(time_sign == 1.0 || time_sign == -1.0)) return TDEQ_EINVAL;
+    if (n_idx < 0 || n_seg < 0 || row_len < 0 || n_rows < 0) return TDEQ_EINVAL;
+    if (n_idx > 0 && (n_rows == 0 || n_idx % n_rows != 0)) return TDEQ_EINVAL;
+    if (n_idx == 0 || row_len == 0) return 0;
+    if (n_seg < 1 || n_seg > 0x7fffffffLL) return TDEQ_EINVAL;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return real_dtype(dtype, [&](auto t) {
+        return row_dense_level_times_launch<decltype(t)>(n_rising, n_falling, rising, falling, max_count, level, n_rows,
+                                                         coeffs, n_seg, seg_ta, seg_tb, time_sign, seg, x, tq, seg2, x2,
+                                                         tq2, n_idx, row_len, s);
+    });
+}
+
 // ---- area above and below a level over a time window: tdeq_row_dense_exposure ---------------------------------------------
 namespace {
 

@@ -15,8 +15,8 @@
 //                      segment ends) and the fraction x of that step, in the arithmetic of row_dense_commit
 // followed by row_event_eval_mapped on (coeffs, seg, x).  No LDS; plain vector loads and stores; 64-bit element offsets.
 // The derivative, antiderivative and integral of the record (row_dense_prefix, row_dense_calc), its extrema over a time
-// window (row_dense_extremum), its crossings of a level (row_dense_level) and its area above and below a level
-// (row_dense_exposure) are at the end of the file.
+// window (row_dense_extremum), its crossings of a level (row_dense_level), its area above and below a level
+// (row_dense_exposure) and the times of all its crossings of a level (row_dense_level_times) are at the end of the file.
 #pragma once
 
 #include "tdeq_kernels_rowwise.hpp"
@@ -801,6 +801,144 @@ __global__ __launch_bounds__(kBlock) void row_dense_exposure_kernel(const RowDen
         __builtin_memcpy(&w, ob, sizeof(E));
         reinterpret_cast<E*>(a.area_below)[i] = w;
         store_doubles<LV>(a.total + i * LV, total);
+    }
+}
+
+// ---- the times of all crossings of a level over a time window (ABI 35): RowDenseOutput.crossing_times ---------------------
+//   row_dense_level_times   the walk, state machine and root location of row_dense_level; what is kept differs.  Per element
+//                           the lane keeps above and one int32 counter per direction, and a crossing located at tz goes
+//                           straight to global memory: slot n of its direction's list while n < K, as one 8-byte store; the
+//                           counter runs on.  Rising is defined in true time: the state becomes above and time_sign > 0, or
+//                           it becomes not above and time_sign < 0; the launcher hands the two directions over as `ups` and
+//                           `dns` accordingly.  After the walk the free slots are filled with NaN, so
+//                           every slot of the four outputs is written.  The list index is an offset in global memory, never
+//                           an index into a per-lane array.  The arithmetic is stated in include/tdeq_hip.h; the host model
+//                           is rowwise.py quartic_crossing_times.
+// No LDS, no atomics, no workspace.
+
+template <typename T>
+struct RowDenseLevelTimesArgs {
+    int32_t* n_up;                    // [n_idx, L] crossings after which the state is above: n_rising if sign > 0, else
+    int32_t* n_dn;                    // n_falling; and those after which it is not (the launcher maps the directions)
+    double* ups;                      // [K, n_idx, L] true time: rising if sign > 0, else falling
+    double* dns;                      // [K, n_idx, L]
+    int32_t k;                        // K: slots per list
+    const T* level;                   // [n_rows, L]
+    const T* q;                       // [5, n_seg, L]
+    const double* seg_ta;             // [n_seg]
+    const double* seg_tb;             // [n_seg]
+    double sign;
+    const int32_t* seg;               // [n_idx] one end of each window (row_dense_search)
+    const T* x;                       // [n_idx] NaN marks an out-of-range end
+    const double* tq;                 // [n_idx] solver time
+    const int32_t* seg2;              // the other end
+    const T* x2;
+    const double* tq2;
+    int64_t n_rows;                   // query i belongs to row i % n_rows
+    int64_t n_seg;
+    int64_t row_len;                  // E units
+    int64_t ne;                       // n_idx * row_len
+    int64_t q_plane;                  // n_seg * L elements of T
+    int64_t t_plane;                  // n_idx * L doubles: one slot of a list
+};
+
+template <typename T, bool VEC>
+__global__ __launch_bounds__(kBlock) void row_dense_level_times_kernel(const RowDenseLevelTimesArgs<T> a) {
+    using E = typename std::conditional<VEC, typename VecOf<T>::type, T>::type;
+    constexpr int LV = VEC ? VecOf<T>::L : 1;
+    const int64_t stride = (int64_t)gridDim.x * kBlock;
+    const int32_t K = a.k;
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < a.ne; i += stride) {
+        const int64_t r = i / a.row_len;
+        const int64_t el = i - r * a.row_len;
+        int64_t sA = a.seg[r], sB = a.seg2[r];
+        double tqa = a.tq[r], tqb = a.tq2[r];
+        const T xa = a.x[r], xb = a.x2[r];
+        if (tqb < tqa) {
+            const int64_t s = sA;
+            sA = sB;
+            sB = s;
+            const double t = tqa;
+            tqa = tqb;
+            tqb = t;
+        }
+        if (sA < 0) sA = 0;                                           // (nothing is read outside the record)
+        if (sB > a.n_seg - 1) sB = a.n_seg - 1;
+        const bool bad = xa != xa || xb != xb || sA > sB;             // (sA > sB: only from ends the search did not write)
+        T lev[LV];
+        load_lanes<T, E, LV>(a.level, (r % a.n_rows) * a.row_len + el, lev);
+        int32_t n_up[LV], n_dn[LV];                                   // crossings of the walk: to above, to not above
+        bool above[LV], nanv[LV];
+#pragma unroll
+        for (int c = 0; c < LV; ++c) {
+            n_up[c] = n_dn[c] = 0;
+            above[c] = false;
+            nanv[c] = bad;
+        }
+        double* const ups = a.ups + i * LV;                           // slot 0 of this lane's elements
+        double* const dns = a.dns + i * LV;
+        for (int64_t s = bad ? sB + 1 : sA; s <= sB; ++s) {           // serial: segments in order
+            const int64_t at = s * a.row_len + el;
+            T qe[LV], qd[LV], qc[LV], qb[LV], qa[LV];
+            load_lanes<T, E, LV>(a.q, at, qe);
+            load_lanes<T, E, LV>(a.q + a.q_plane, at, qd);
+            load_lanes<T, E, LV>(a.q + 2 * a.q_plane, at, qc);
+            load_lanes<T, E, LV>(a.q + 3 * a.q_plane, at, qb);
+            load_lanes<T, E, LV>(a.q + 4 * a.q_plane, at, qa);
+            const double ta = a.seg_ta[s], tb = a.seg_tb[s];
+            const double h = tb - ta;
+            const bool atA = s == sA, atB = s == sB;
+            const double xlo = atA ? (tqa - ta) / h : 0.0;
+            const double xhi = atB ? (tqb - ta) / h : 1.0;
+#pragma unroll
+            for (int c = 0; c < LV; ++c) {
+                const double b = (double)qb[c], aa = (double)qa[c];
+                const QuarticLevel phi{(double)qe[c], (double)qd[c], (double)qc[c], b, aa, (double)lev[c]};
+                const double c2 = phi.c + phi.c, a4 = 4.0 * aa;
+                const QuarticSlope g{phi.d, c2, 3.0 * b, a4};
+                const QuarticCurvature g1{c2, 6.0 * b, 12.0 * aa};
+                bool st = above[c], entry = true;                     // entry: the segment's first candidate comes next
+                int32_t nu = n_up[c], nd = n_dn[c];
+                double u = xlo, fu = 0.0;
+                auto visit = [&](double x) {
+                    const double v = phi(x);
+                    if (v != v) nanv[c] = true;
+                    const bool ab = v > 0.0;
+                    if (entry && atA) {                               // the window's first candidate sets the state
+                        st = ab;
+                    } else if (ab != st) {
+                        double z = x;                                 // (a later segment's first candidate: the breakpoint)
+                        if (!entry) {
+                            if (fu == 0.0) z = u;
+                            else if (v != 0.0) quartic_bisect(phi, u, x, z);
+                        }
+                        const double tz =
+                            (atA && z == xlo) ? tqa : (atB && z == xhi) ? tqb : z == 0.0 ? ta : z == 1.0 ? tb : ta + z * h;
+                        const int32_t n = ab ? nu : nd;
+                        if (n < K) (ab ? ups : dns)[(int64_t)n * a.t_plane + c] = a.sign * tz;
+                        nu += ab ? 1 : 0;                             // (both counters by value: no pointer to either)
+                        nd += ab ? 0 : 1;
+                        st = ab;
+                    }
+                    entry = false;
+                    u = x;
+                    fu = v;
+                };
+                quartic_candidates(g, g1, b, aa, a4, xlo, xhi, visit);
+                above[c] = st;
+                n_up[c] = nu;
+                n_dn[c] = nd;
+            }
+        }
+        const double nan = __builtin_nan("");
+#pragma unroll
+        for (int c = 0; c < LV; ++c) {
+            for (int32_t n = nanv[c] ? 0 : n_up[c]; n < K; ++n) ups[(int64_t)n * a.t_plane + c] = nan;
+            for (int32_t n = nanv[c] ? 0 : n_dn[c]; n < K; ++n) dns[(int64_t)n * a.t_plane + c] = nan;
+            if (nanv[c]) n_up[c] = n_dn[c] = -1;
+        }
+        store_ints<LV>(a.n_up + i * LV, n_up);
+        store_ints<LV>(a.n_dn + i * LV, n_dn);
     }
 }
 

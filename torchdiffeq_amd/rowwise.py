@@ -1074,6 +1074,92 @@ class HostRowKernels:
             total = np.where(nan, np.nan, total)
         return tuple(torch.from_numpy(np.ascontiguousarray(v)) for v in (count, first, last, total))
 
+    # -- the times of all crossings of a level over a window (the arithmetic of tdeq_row_dense_level_times, include/tdeq_hip.h)
+    @staticmethod
+    def quartic_crossing_times(q, level, ta, tb, sign: float, max_count: int, src, x, tq, src2, x2, tq2):
+        """The true times of the first `max_count` rising and falling crossings of `level` [n_rows, L] (query i belongs to row
+        i % n_rows) by the record `q` [5, n_seg, L] on the windows between the queries (src, x, tq) and (src2, x2, tq2) of the
+        search, per element, and the number of crossings of each direction -> (n_rising, n_falling int32 [n, L], rising,
+        falling fp64 [max_count, n, L]).  `quartic_levels` with the lists filled under masks: a crossing of the walk goes to
+        slot n of its direction's list while n < max_count, and the counter runs on; rising is meant in true time, so the two
+        directions of the walk swap for `sign` < 0."""
+        H = HostRowKernels
+        planes, start, end = q.numpy(), ta.numpy(), tb.numpy()
+        sa, sb = src.numpy().astype(np.int64), src2.numpy().astype(np.int64)
+        qa, qb = tq.numpy().reshape(-1), tq2.numpy().reshape(-1)
+        swap = qb < qa
+        sa, sb = np.where(swap, sb, sa), np.where(swap, sa, sb)
+        qa, qb = np.where(swap, qb, qa), np.where(swap, qa, qb)
+        bad = np.isnan(x.numpy()) | np.isnan(x2.numpy()) | (sa > sb)
+        n, L, K = sa.size, planes.shape[2], int(max_count)
+        levels = level.numpy().astype(np.float64)[np.arange(n) % level.shape[0]]
+        state, nan = np.zeros((n, L), dtype=bool), np.repeat(bad[:, None], L, axis=1)
+        n_up, n_dn = (np.zeros((n, L), dtype=np.int32) for _ in range(2))   # crossings of the walk: to above, to not above
+        ups, dns = (np.full((K, n, L), np.nan) for _ in range(2))
+        steps = np.where(bad, 0, sb - sa + 1)
+        with np.errstate(all="ignore"):
+            for k in range(int(steps.max()) if n else 0):
+                idx = np.flatnonzero(steps > k)
+                s = sa[idx] + k
+                e, d, c, b, a = (planes[p, s].astype(np.float64) for p in range(5))
+                lev = levels[idx]
+                t_a, t_b = start[s][:, None], end[s][:, None]
+                h = t_b - t_a
+                atA, atB = np.full((idx.size, 1), k == 0), (s == sb[idx])[:, None]
+                t_lo, t_hi = qa[idx][:, None], qb[idx][:, None]
+                xlo = np.broadcast_to(np.where(atA, (t_lo - t_a) / h, 0.0), e.shape)
+                xhi = np.broadcast_to(np.where(atB, (t_hi - t_a) / h, 1.0), e.shape)
+                c2, a4 = c + c, 4.0 * a
+                b3, b6, a12 = 3.0 * b, 6.0 * b, 12.0 * a
+                g = lambda v: d + v * (c2 + v * (b3 + v * a4))           # noqa: E731
+                g1 = lambda v: c2 + v * (b6 + v * a12)                   # noqa: E731
+                phi = lambda v: (e + v * (d + v * (c + v * (b + v * a)))) - lev      # noqa: E731
+                st, nu, nd, nn = state[idx], n_up[idx], n_dn[idx], nan[idx]
+                entry = np.ones(e.shape, dtype=bool)                     # the segment's first candidate comes next
+                u, fu = xlo, np.zeros(e.shape)
+                window = np.broadcast_to(idx[:, None], e.shape)
+                column = np.broadcast_to(np.arange(L)[None, :], e.shape)
+
+                def visit(v, on):
+                    nonlocal st, nu, nd, nn, entry, u, fu
+                    fv = phi(v)
+                    nn = nn | (on & np.isnan(fv))
+                    ab = fv > 0
+                    opening = on & entry & atA                           # the window's first candidate sets the state
+                    cross = on & ~opening & (ab != st)
+                    inside = cross & ~entry                              # (else: a later segment's first candidate)
+                    found, root = H._bisect(phi, u, v, inside & (fu != 0) & (fv != 0))
+                    z = np.where(inside & (fu == 0), u, np.where(found, root, v))
+                    tz = np.where(atA & (z == xlo), t_lo, np.where(atB & (z == xhi), t_hi, np.where(
+                        z == 0.0, t_a, np.where(z == 1.0, t_b, t_a + z * h))))
+                    for lst, cnt, to in ((ups, nu, cross & ab), (dns, nd, cross & ~ab)):
+                        keep = to & (cnt < K)
+                        lst[cnt[keep], window[keep], column[keep]] = sign * tz[keep]
+                    nu, nd = nu + (cross & ab).astype(np.int32), nd + (cross & ~ab).astype(np.int32)
+                    st = np.where(opening | cross, ab, st)
+                    entry, u, fu = entry & ~on, np.where(on, v, u), np.where(on, fv, fu)
+
+                every = np.ones(e.shape, dtype=bool)
+                x1 = (-b) / a4
+                xm = np.where((a != 0.0) & (xlo < x1) & (x1 < xhi), x1, xlo)
+                f0, root = H._bisect(g1, xlo, xm, xm > xlo)
+                r0 = np.where(f0, root, xlo)
+                f1, root = H._bisect(g1, xm, xhi, every)
+                r1 = np.where(f1, root, r0)
+                visit(xlo, every)
+                for lo, hi in ((xlo, r0), (r0, r1)):
+                    fz, z = H._bisect(g, lo, hi, hi > lo)
+                    visit(z, fz)
+                    visit(hi, hi > lo)
+                fz, z = H._bisect(g, r1, xhi, every)
+                visit(z, fz)
+                visit(xhi, every)
+                state[idx], n_up[idx], n_dn[idx], nan[idx] = st, nu, nd, nn
+            n_up, n_dn = np.where(nan, np.int32(-1), n_up).astype(np.int32), np.where(nan, np.int32(-1), n_dn).astype(np.int32)
+            ups, dns = np.where(nan[None], np.nan, ups), np.where(nan[None], np.nan, dns)
+        outs = (n_up, n_dn, ups, dns) if sign > 0 else (n_dn, n_up, dns, ups)
+        return tuple(torch.from_numpy(np.ascontiguousarray(v)) for v in outs)
+
     # -- area above and below a level over a window (the arithmetic of tdeq_row_dense_exposure, include/tdeq_hip.h) ----------
     @staticmethod
     def quartic_exposure(q, level, ta, tb, sign: float, src, x, tq, src2, x2, tq2):

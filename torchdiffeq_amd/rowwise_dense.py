@@ -20,7 +20,8 @@ integrals that `tdeq_row_dense_prefix` builds on first use.  The maximum and min
 by `tdeq_row_dense_extremum`, which walks the window's segments and builds nothing; the crossings of a level and the time
 above it are the same two searches followed by `tdeq_row_dense_level`, the same walk with a state machine; the area between
 the record and a level, above and below it, is the same again with `tdeq_row_dense_exposure`, which integrates `y - level`
-piece by piece while it walks.  CPU states run the same steps as torch / numpy ops.
+piece by piece while it walks; the times of ALL crossings, by direction, are the same walk with `tdeq_row_dense_level_times`,
+which stores every located time at once.  CPU states run the same steps as torch / numpy ops.
 """
 from __future__ import annotations
 
@@ -33,7 +34,8 @@ from . import rowwise
 from ._native import device_guard
 from .rowwise import _Problem
 
-__all__ = ["odeint_rowwise_dense", "RowDenseOutput", "RowDenseExtremum", "RowDenseCrossings", "RowDenseExposure"]
+__all__ = ["odeint_rowwise_dense", "RowDenseOutput", "RowDenseExtremum", "RowDenseCrossings", "RowDenseCrossingTimes",
+           "RowDenseExposure"]
 
 # the default chunk: CHUNK_ROWS_PER_ROW slots per row of the batch, at most CHUNK_BYTES of coefficients, never fewer than B
 CHUNK_ROWS_PER_ROW = 4
@@ -181,6 +183,17 @@ class RowDenseCrossings(NamedTuple):
     time_above: torch.Tensor
 
 
+class RowDenseCrossingTimes(NamedTuple):
+    """`RowDenseOutput.crossing_times`: per element the number of rising and of falling crossings of the level inside the
+    window (int32, ALL of them; -1 where the answer is NaN) and the fp64 true times of the first `max_count` crossings of each
+    direction in the order the walk meets them — the direction of the solve — as `[max_count, ...]` lists padded with NaN from
+    index `min(n, max_count)` on.  Rising is meant in true time: `y` goes from `<= level` to `> level` as true time increases."""
+    n_rising: torch.Tensor
+    n_falling: torch.Tensor
+    rising: torch.Tensor
+    falling: torch.Tensor
+
+
 class RowDenseExposure(NamedTuple):
     """`RowDenseOutput.exposure`: per element the integral of `max(y - level, 0)` and of `max(level - y, 0)` over the window (the
     state's dtype, >= 0, true-time durations times state units) and the total true-time duration (fp64, >= 0) with `y >
@@ -194,8 +207,9 @@ class RowDenseOutput:
     """The piecewise quartic of a rowwise solve; `dense(t)` evaluates it, `derivative(t)`, `antiderivative(t)` and
     `integral(ta, tb)` give its time derivative and its integrals in closed form, `maximum(ta, tb)` and `minimum(ta, tb)` its
     extrema over a time window and their times, `crossings(level, ta, tb)` and `time_above(level, ta, tb)` its crossings of a
-    level and the time spent above it, `exposure(level, ta, tb)`, `area_above(level, ta, tb)` and `area_below(level, ta, tb)`
-    the area between it and a level (see `odeint_rowwise_dense`).
+    level and the time spent above it, `crossing_times(level, ta, tb, max_count)` the times of all its crossings by direction,
+    `exposure(level, ta, tb)`, `area_above(level, ta, tb)` and `area_below(level, ta, tb)` the area between it and a level (see
+    `odeint_rowwise_dense`).
 
     Attributes (the wire format, all on the state's device): `t0`, `t1` `[B]` fp64 in true time; `offsets` `[B + 1]` int64;
     `seg_start`, `seg_end` `[n_seg]` fp64 in true time, row r's segments — its accepted steps — contiguous and in step
@@ -479,10 +493,13 @@ class RowDenseOutput:
                              f"{list(self._shape)}") from None
         return lev.reshape(B, L).contiguous()
 
-    def _level_walk(self, what: str, level, ta, tb, check: bool, host: str, launch: str, dtypes):
-        """The steps of `crossings` and `exposure`: the level, the search per end, one launch (`launch` of the device kernels,
-        `host` of `HostRowKernels` for a CPU state) that fills outputs of `dtypes`, one read of the status words (with `check`)
-        -> (the outputs as `[Q, B, *row_shape]`, both times were single).  Nothing is built or kept."""
+    def _level_walk(self, what: str, level, ta, tb, check: bool, host: str, launch: str, dtypes, max_count: int = 0,
+                    listed: int = 0):
+        """The steps of `crossings`, `exposure` and `crossing_times`: the level, the search per end, one launch (`launch` of the
+        device kernels, `host` of `HostRowKernels` for a CPU state) that fills outputs of `dtypes`, one read of the status
+        words (with `check`) -> (the outputs as `[Q, B, *row_shape]`, both times were single).  The last `listed` outputs are
+        lists with a leading dimension: `[max_count, Q, B, *row_shape]`, and the host function takes `max_count` after the
+        sign.  Nothing is built or kept."""
         names = ("ta", "tb")
         lev = self._level(what, level)
         tqs, single = self._query_lists(what, names, (ta, tb))
@@ -490,7 +507,8 @@ class RowDenseOutput:
         if self._k is not None and Q * B >= _NONE:
             raise ValueError(f"{what}: {Q * B} queries in one call; the query index is a 32-bit word")
         L, dev, dtype = self.coeffs.shape[2], self.coeffs.device, self.coeffs.dtype
-        outs = [torch.empty(Q * B, L, dtype=t, device=dev) for t in dtypes]
+        plain = len(dtypes) - listed
+        outs = [torch.empty(*((max_count,) if i >= plain else ()), Q * B, L, dtype=t, device=dev) for i, t in enumerate(dtypes)]
         firsts = [_NONE, _NONE]
         if Q > 0:
             with torch.no_grad(), device_guard(dev):
@@ -498,7 +516,8 @@ class RowDenseOutput:
                     found = [self._search_host(tq) for tq in tqs]
                     firsts = [bad for _, _, bad in found]
                     lists = [v for (seg, x, _), tq in zip(found, tqs) for v in (seg, x, tq)]
-                    walked = getattr(rowwise.HostRowKernels, host)(self.coeffs, lev, self._ta, self._tb, self._sign, *lists)
+                    walked = getattr(rowwise.HostRowKernels, host)(self.coeffs, lev, self._ta, self._tb, self._sign,
+                                                                   *((max_count,) if listed else ()), *lists)
                     for dst, src in zip(outs, walked):
                         dst.copy_(src)
                 else:
@@ -515,7 +534,7 @@ class RowDenseOutput:
                         firsts = status.tolist()                          # the one read
         if check:
             self._raise_out_of_range(what, names, tqs, firsts)
-        return [v.view(Q, *self._shape) for v in outs], single
+        return [v.view(*v.shape[:-2], Q, *self._shape) for v in outs], single
 
     def crossings(self, level, ta, tb, check: bool = True) -> RowDenseCrossings:
         """Where every ELEMENT of `y_r` crosses `level` on the window between `ta` and `tb` (true time, in either order: the
@@ -540,6 +559,32 @@ class RowDenseOutput:
         """The total true-time duration every element spends strictly above `level` on the window: `crossings(level, ta, tb,
         check).time_above`, the same launch."""
         return self.crossings(level, ta, tb, check).time_above
+
+    def crossing_times(self, level, ta, tb, max_count: int = 4, check: bool = True) -> RowDenseCrossingTimes:
+        """EVERY crossing of `level` by every ELEMENT of `y_r` on the window between `ta` and `tb` (true time, in either order:
+        the same bits), by direction -> `RowDenseCrossingTimes(n_rising, n_falling, rising, falling)`: `n_rising` and
+        `n_falling` int32 `[Q, B, *row_shape]` (`[B, *row_shape]` for two single times), ALL the crossings of each direction
+        inside the window, those beyond `max_count` included; `rising` and `falling` fp64 `[max_count, Q, B, *row_shape]`
+        (`[max_count, B, *row_shape]`), the true times of the first `max_count` crossings of each direction in the order the
+        walk meets them — the direction of the solve, as for `first` and `last` of `crossings`: decreasing true time for a
+        descending solve — padded with NaN from index `min(n, max_count)` on.  Rising is meant in TRUE time: `y` goes from
+        `<= level` to `> level` as true time increases (above is strict), so an up-crossing of a descending solve's walk is a
+        falling crossing.  `n_rising + n_falling` is the `count` of `crossings`, and the earlier of `rising[0]`, `falling[0]`
+        its `first`.  `level`, `ta`, `tb` and `check` are those of `crossings`: both counters are -1 and both lists all NaN
+        where `count` is -1 (a NaN level for that element alone; an out-of-range query with `check=False` for its whole row,
+        and nothing is read).  `max_count` is an `int` in `[1, 65535]`.  Memory: `16 * max_count` bytes per element and
+        window, 537 MB for one whole-row window at 65536 x 128 with the default.  Everything `crossings` says about the
+        record holds here: a `jump_dy` dose at a breakpoint inside the window or at its near end is a crossing at the stored
+        dose time, the rounding-level gap at a step boundary can add a pair of crossings, a value that touches the level
+        exactly and turns back is two crossings at the same time, and nothing is built or cached."""
+        what = "dense.crossing_times(level, ta, tb)"
+        if not isinstance(max_count, int) or isinstance(max_count, bool) or not 1 <= max_count <= 65535:
+            raise ValueError(f"{what}: max_count must be an int in [1, 65535], got {max_count!r}")
+        outs, single = self._level_walk(what, level, ta, tb, check, "quartic_crossing_times", "row_dense_level_times",
+                                        (torch.int32, torch.int32, torch.float64, torch.float64), max_count, listed=2)
+        if single:
+            outs = [outs[0][0], outs[1][0], outs[2][:, 0], outs[3][:, 0]]
+        return RowDenseCrossingTimes(*outs)
 
     # -- area above and below a level over a time window: the walk of the crossings, integrating as it goes --------------------
     def exposure(self, level, ta, tb, check: bool = True) -> RowDenseExposure:
@@ -644,6 +689,18 @@ def odeint_rowwise_dense(func, y0, t0, t1, *, rtol=1e-7, atol=1e-9, method="dopr
     rounding level at every breakpoint (the end of one step's quartic and the start of the next may differ in their last
     bits): a level inside such a gap is crossed there once more than the continuous solution would be.  A value that only
     touches the level from below is no crossing.  One launch after the two searches; nothing is built or cached.
+
+    Every crossing of a level: `dense.crossing_times(level, ta, tb, max_count=4)` -> `RowDenseCrossingTimes(n_rising,
+    n_falling, rising, falling)`, with the `level`, the query forms and the `check` of `crossings`: per ELEMENT the number of
+    rising and of falling crossings inside the window (int32, all of them) and the fp64 true times of the first `max_count` of
+    each direction as `[max_count, ...]` lists in the order the walk meets them (the direction of the solve), padded with NaN —
+    onset and offset of every dosing interval, spike times, periods, Poincare sections.  Rising is meant in TRUE time (`y` goes
+    from `<= level` to `> level` as true time increases), so the two directions of the walk swap for a descending solve.  The
+    walk, the state machine, the root location and the time rule are those of `crossings`, so `n_rising + n_falling` is its
+    `count` and the lists hold its `first` and, where they fit, its `last`; the HIP kernel (`tdeq_row_dense_level_times`, ABI
+    35) stores each located time at once and keeps only the state and two counters per element, and the numpy path of a CPU
+    state has the same bits.  `16 * max_count` bytes per element and window.  One launch after the two searches; nothing is
+    built or cached.
 
     Exposure against a level: `dense.exposure(level, ta, tb)` -> `RowDenseExposure(area_above, area_below, time_above)`, and
     `dense.area_above(level, ta, tb)` / `dense.area_below(level, ta, tb)` (one field each, the same launch), with the `level`,
