@@ -1216,145 +1216,100 @@ class HipKernels:
                                             ptr(tq2, mode == 2), n_idx, L, dtype_code(out.dtype), self._stream()),
                "tdeq_row_dense_calc")
 
-    def row_dense_extremum(self, values, times, which: int, coeffs, seg_ta, seg_tb, sign: float, seg, x, tq, seg2, x2,
-                           tq2) -> None:
-        """tdeq_row_dense_extremum: per element the maximum (`which` 0) or minimum (1) of the record on the window between
-        the queries (seg[i], x[i], tq[i]) and (seg2[i], x2[i], tq2[i]) of `row_dense_search`, and its time.  `values`
-        [n_idx, L] and `x`, `x2` [n_idx] of the dtype of `coeffs` [5, n_seg, L], `times` fp64 [n_idx, L] (true time), `seg`,
-        `seg2` int32 [n_idx], `tq`, `tq2` fp64 with n_idx elements in solver time, `sign` +1.0 or -1.0."""
+    # -- queries over a time window of the record (RowDenseOutput.maximum / crossings / exposure / crossing_times) -----------
+    def _row_dense_window(self, name: str, outs, coeffs, seg_ta, seg_tb, sign: float, seg, x, tq, seg2, x2, tq2, level=None,
+                          like=None, refuse=None):
+        """What the bindings of the four window kernels share.  The windows lie between the queries (seg[i], x[i], tq[i]) and
+        (seg2[i], x2[i], tq2[i]) of `row_dense_search`: `seg`, `seg2` int32 [n_idx], `x`, `x2` [n_idx] of the dtype of `coeffs`
+        [5, n_seg, L], `tq`, `tq2` fp64 with n_idx elements in solver time, `sign` +1.0 or -1.0; with a `level` [n_rows, L] of
+        that dtype query i belongs to row i % n_rows.  `outs`: the binding's outputs as (name, tensor, dtype or None for that
+        of `coeffs`, leading dimensions), each [*leading, n_idx, L].  Validated in this order: `coeffs` (of the dtype of the
+        tensor `like` = (name, tensor), when given), `level`, `refuse` (the binding's own complaint, or None), then every
+        output, `level` and the shared tensors -> the arguments of the entry point from `level` (or `coeffs`) on, or None
+        for no queries."""
         n_idx = seg.numel()
         if n_idx == 0:
-            return
+            return None
         n_seg = seg_ta.numel()
-        if coeffs.dim() != 3 or coeffs.shape[:2] != (5, n_seg) or coeffs.dtype != values.dtype or not coeffs.is_contiguous():
-            raise ValueError("row_dense_extremum: coeffs must be a contiguous [5, n_seg, L] tensor of values' dtype")
-        L = coeffs.shape[2]
-        if which not in (0, 1):
-            raise ValueError("row_dense_extremum: which 0 (maximum) or 1 (minimum)")
-        for name, t, dtype, shape in (("values", values, values.dtype, (n_idx, L)), ("times", times, torch.float64, (n_idx, L)),
-                                      ("seg_ta", seg_ta, torch.float64, (n_seg,)), ("seg_tb", seg_tb, torch.float64, (n_seg,)),
-                                      ("seg", seg, torch.int32, (n_idx,)), ("x", x, values.dtype, (n_idx,)),
-                                      ("tq", tq.view(-1), torch.float64, (n_idx,)), ("seg2", seg2, torch.int32, (n_idx,)),
-                                      ("x2", x2, values.dtype, (n_idx,)), ("tq2", tq2.view(-1), torch.float64, (n_idx,))):
+        if coeffs.dim() != 3 or coeffs.shape[:2] != (5, n_seg) or not coeffs.is_contiguous() \
+                or (like is not None and coeffs.dtype != like[1].dtype):
+            raise ValueError(f"{name}: coeffs must be a contiguous [5, n_seg, L] tensor" +
+                             (f" of {like[0]}' dtype" if like is not None else ""))
+        L, T = coeffs.shape[2], coeffs.dtype
+        table, head = [(n, t, dtype or T, (*lead, n_idx, L)) for n, t, dtype, lead in outs], ()
+        if level is not None:
+            if level.dim() != 2 or level.shape[1] != L or level.shape[0] == 0 or n_idx % level.shape[0] != 0:
+                raise ValueError(f"{name}: level must be [n_rows, {L}] with n_rows dividing the {n_idx} queries")
+            table.append(("level", level, T, (level.shape[0], L)))
+            head = (level.data_ptr(), level.shape[0])
+        if refuse is not None:
+            raise ValueError(f"{name}: {refuse}")
+        table += [("seg_ta", seg_ta, torch.float64, (n_seg,)), ("seg_tb", seg_tb, torch.float64, (n_seg,)),
+                  ("seg", seg, torch.int32, (n_idx,)), ("x", x, T, (n_idx,)), ("tq", tq.view(-1), torch.float64, (n_idx,)),
+                  ("seg2", seg2, torch.int32, (n_idx,)), ("x2", x2, T, (n_idx,)),
+                  ("tq2", tq2.view(-1), torch.float64, (n_idx,))]
+        for n, t, dtype, shape in table:
             if tuple(t.shape) != shape or t.dtype != dtype or not t.is_contiguous():
-                raise ValueError(f"row_dense_extremum: {name} must be a contiguous {dtype} {list(shape)} tensor")
+                raise ValueError(f"{name}: {n} must be a contiguous {dtype} {list(shape)} tensor")
         if not tq.is_contiguous() or not tq2.is_contiguous():
-            raise ValueError("row_dense_extremum: tq and tq2 must be contiguous")
-        _check(self.lib.tdeq_row_dense_extremum(values.data_ptr(), times.data_ptr(), which, coeffs.data_ptr(), n_seg,
-                                                seg_ta.data_ptr(), seg_tb.data_ptr(), float(sign), seg.data_ptr(),
-                                                x.data_ptr(), tq.data_ptr(), seg2.data_ptr(), x2.data_ptr(), tq2.data_ptr(),
-                                                n_idx, L, dtype_code(values.dtype), self._stream()),
-               "tdeq_row_dense_extremum")
+            raise ValueError(f"{name}: tq and tq2 must be contiguous")
+        return (*head, coeffs.data_ptr(), n_seg, seg_ta.data_ptr(), seg_tb.data_ptr(), float(sign), seg.data_ptr(),
+                x.data_ptr(), tq.data_ptr(), seg2.data_ptr(), x2.data_ptr(), tq2.data_ptr(), n_idx, L, dtype_code(T),
+                self._stream())
+
+    def row_dense_extremum(self, values, times, which: int, coeffs, seg_ta, seg_tb, sign: float, seg, x, tq, seg2, x2,
+                           tq2) -> None:
+        """tdeq_row_dense_extremum: per element the maximum (`which` 0) or minimum (1) of the record on each window, and its
+        time.  `values` [n_idx, L] of the dtype of `coeffs`, `times` fp64 [n_idx, L] (true time); the record and the two query
+        lists as `_row_dense_window` describes them."""
+        tail = self._row_dense_window("row_dense_extremum", (("values", values, None, ()), ("times", times, torch.float64, ())),
+                                      coeffs, seg_ta, seg_tb, sign, seg, x, tq, seg2, x2, tq2, like=("values", values),
+                                      refuse=None if which in (0, 1) else "which 0 (maximum) or 1 (minimum)")
+        if tail is not None:
+            _check(self.lib.tdeq_row_dense_extremum(values.data_ptr(), times.data_ptr(), which, *tail),
+                   "tdeq_row_dense_extremum")
 
     def row_dense_level(self, count, first, last, time_above, level, coeffs, seg_ta, seg_tb, sign: float, seg, x, tq, seg2, x2,
                         tq2) -> None:
-        """tdeq_row_dense_level: per element the crossings of `level` [n_rows, L] on the window between the queries (seg[i],
-        x[i], tq[i]) and (seg2[i], x2[i], tq2[i]) of `row_dense_search` (query i of row i % n_rows), and the time above it.
-        `count` int32, `first`, `last` (true time) and `time_above` fp64, all [n_idx, L]; `level` and `x`, `x2` [n_idx] of the
-        dtype of `coeffs` [5, n_seg, L]; `seg`, `seg2` int32 [n_idx]; `tq`, `tq2` fp64 with n_idx elements in solver time;
-        `sign` +1.0 or -1.0."""
-        n_idx = seg.numel()
-        if n_idx == 0:
-            return
-        n_seg = seg_ta.numel()
-        if coeffs.dim() != 3 or coeffs.shape[:2] != (5, n_seg) or not coeffs.is_contiguous():
-            raise ValueError("row_dense_level: coeffs must be a contiguous [5, n_seg, L] tensor")
-        L, T = coeffs.shape[2], coeffs.dtype
-        if level.dim() != 2 or level.shape[1] != L or level.shape[0] == 0 or n_idx % level.shape[0] != 0:
-            raise ValueError(f"row_dense_level: level must be [n_rows, {L}] with n_rows dividing the {n_idx} queries")
-        n_rows = level.shape[0]
-        for name, t, dtype, shape in (("count", count, torch.int32, (n_idx, L)), ("first", first, torch.float64, (n_idx, L)),
-                                      ("last", last, torch.float64, (n_idx, L)),
-                                      ("time_above", time_above, torch.float64, (n_idx, L)), ("level", level, T, (n_rows, L)),
-                                      ("seg_ta", seg_ta, torch.float64, (n_seg,)), ("seg_tb", seg_tb, torch.float64, (n_seg,)),
-                                      ("seg", seg, torch.int32, (n_idx,)), ("x", x, T, (n_idx,)),
-                                      ("tq", tq.view(-1), torch.float64, (n_idx,)), ("seg2", seg2, torch.int32, (n_idx,)),
-                                      ("x2", x2, T, (n_idx,)), ("tq2", tq2.view(-1), torch.float64, (n_idx,))):
-            if tuple(t.shape) != shape or t.dtype != dtype or not t.is_contiguous():
-                raise ValueError(f"row_dense_level: {name} must be a contiguous {dtype} {list(shape)} tensor")
-        if not tq.is_contiguous() or not tq2.is_contiguous():
-            raise ValueError("row_dense_level: tq and tq2 must be contiguous")
-        _check(self.lib.tdeq_row_dense_level(count.data_ptr(), first.data_ptr(), last.data_ptr(), time_above.data_ptr(),
-                                             level.data_ptr(), n_rows, coeffs.data_ptr(), n_seg, seg_ta.data_ptr(),
-                                             seg_tb.data_ptr(), float(sign), seg.data_ptr(), x.data_ptr(), tq.data_ptr(),
-                                             seg2.data_ptr(), x2.data_ptr(), tq2.data_ptr(), n_idx, L, dtype_code(T),
-                                             self._stream()),
-               "tdeq_row_dense_level")
+        """tdeq_row_dense_level: per element the crossings of `level` [n_rows, L] on each window, and the time above it.
+        `count` int32, `first`, `last` (true time) and `time_above` fp64, all [n_idx, L]; the record and the two query lists as
+        `_row_dense_window` describes them."""
+        f64 = torch.float64
+        tail = self._row_dense_window("row_dense_level", (("count", count, torch.int32, ()), ("first", first, f64, ()),
+                                                          ("last", last, f64, ()), ("time_above", time_above, f64, ())),
+                                      coeffs, seg_ta, seg_tb, sign, seg, x, tq, seg2, x2, tq2, level=level)
+        if tail is not None:
+            _check(self.lib.tdeq_row_dense_level(count.data_ptr(), first.data_ptr(), last.data_ptr(), time_above.data_ptr(),
+                                                 *tail), "tdeq_row_dense_level")
 
     def row_dense_exposure(self, area_above, area_below, time_above, level, coeffs, seg_ta, seg_tb, sign: float, seg, x, tq,
                            seg2, x2, tq2) -> None:
-        """tdeq_row_dense_exposure: per element the area between the record and `level` [n_rows, L] above and below it on the
-        window between the queries (seg[i], x[i], tq[i]) and (seg2[i], x2[i], tq2[i]) of `row_dense_search` (query i of row
-        i % n_rows), and the time above it.  `area_above`, `area_below` [n_idx, L], `level` and `x`, `x2` [n_idx] of the dtype
-        of `coeffs` [5, n_seg, L]; `time_above` fp64 [n_idx, L]; `seg`, `seg2` int32 [n_idx]; `tq`, `tq2` fp64 with n_idx
-        elements in solver time; `sign` +1.0 or -1.0."""
-        n_idx = seg.numel()
-        if n_idx == 0:
-            return
-        n_seg = seg_ta.numel()
-        if coeffs.dim() != 3 or coeffs.shape[:2] != (5, n_seg) or not coeffs.is_contiguous():
-            raise ValueError("row_dense_exposure: coeffs must be a contiguous [5, n_seg, L] tensor")
-        L, T = coeffs.shape[2], coeffs.dtype
-        if level.dim() != 2 or level.shape[1] != L or level.shape[0] == 0 or n_idx % level.shape[0] != 0:
-            raise ValueError(f"row_dense_exposure: level must be [n_rows, {L}] with n_rows dividing the {n_idx} queries")
-        n_rows = level.shape[0]
-        for name, t, dtype, shape in (("area_above", area_above, T, (n_idx, L)), ("area_below", area_below, T, (n_idx, L)),
-                                      ("time_above", time_above, torch.float64, (n_idx, L)), ("level", level, T, (n_rows, L)),
-                                      ("seg_ta", seg_ta, torch.float64, (n_seg,)), ("seg_tb", seg_tb, torch.float64, (n_seg,)),
-                                      ("seg", seg, torch.int32, (n_idx,)), ("x", x, T, (n_idx,)),
-                                      ("tq", tq.view(-1), torch.float64, (n_idx,)), ("seg2", seg2, torch.int32, (n_idx,)),
-                                      ("x2", x2, T, (n_idx,)), ("tq2", tq2.view(-1), torch.float64, (n_idx,))):
-            if tuple(t.shape) != shape or t.dtype != dtype or not t.is_contiguous():
-                raise ValueError(f"row_dense_exposure: {name} must be a contiguous {dtype} {list(shape)} tensor")
-        if not tq.is_contiguous() or not tq2.is_contiguous():
-            raise ValueError("row_dense_exposure: tq and tq2 must be contiguous")
-        _check(self.lib.tdeq_row_dense_exposure(area_above.data_ptr(), area_below.data_ptr(), time_above.data_ptr(),
-                                                level.data_ptr(), n_rows, coeffs.data_ptr(), n_seg, seg_ta.data_ptr(),
-                                                seg_tb.data_ptr(), float(sign), seg.data_ptr(), x.data_ptr(), tq.data_ptr(),
-                                                seg2.data_ptr(), x2.data_ptr(), tq2.data_ptr(), n_idx, L, dtype_code(T),
-                                                self._stream()),
-               "tdeq_row_dense_exposure")
-
+        """tdeq_row_dense_exposure: per element the area between the record and `level` [n_rows, L] above and below it on each
+        window, and the time above it.  `area_above`, `area_below` [n_idx, L] of the dtype of `coeffs`, `time_above` fp64
+        [n_idx, L]; the record and the two query lists as `_row_dense_window` describes them."""
+        tail = self._row_dense_window("row_dense_exposure", (("area_above", area_above, None, ()),
+                                                             ("area_below", area_below, None, ()),
+                                                             ("time_above", time_above, torch.float64, ())),
+                                      coeffs, seg_ta, seg_tb, sign, seg, x, tq, seg2, x2, tq2, level=level)
+        if tail is not None:
+            _check(self.lib.tdeq_row_dense_exposure(area_above.data_ptr(), area_below.data_ptr(), time_above.data_ptr(), *tail),
+                   "tdeq_row_dense_exposure")
 
     def row_dense_level_times(self, n_rising, n_falling, rising, falling, level, coeffs, seg_ta, seg_tb, sign: float, seg, x,
                               tq, seg2, x2, tq2) -> None:
         """tdeq_row_dense_level_times: per element the true times of the first K rising and the first K falling crossings of
-        `level` [n_rows, L] on the window between the queries (seg[i], x[i], tq[i]) and (seg2[i], x2[i], tq2[i]) of
-        `row_dense_search` (query i of row i % n_rows), and the number of crossings of each direction.  `n_rising`,
-        `n_falling` int32 [n_idx, L]; `rising`, `falling` fp64 [K, n_idx, L] with K = rising.shape[0]; `level` and `x`, `x2`
-        [n_idx] of the dtype of `coeffs` [5, n_seg, L]; `seg`, `seg2` int32 [n_idx]; `tq`, `tq2` fp64 with n_idx elements in
-        solver time; `sign` +1.0 or -1.0."""
-        n_idx = seg.numel()
-        if n_idx == 0:
-            return
-        n_seg = seg_ta.numel()
-        if coeffs.dim() != 3 or coeffs.shape[:2] != (5, n_seg) or not coeffs.is_contiguous():
-            raise ValueError("row_dense_level_times: coeffs must be a contiguous [5, n_seg, L] tensor")
-        L, T = coeffs.shape[2], coeffs.dtype
-        if level.dim() != 2 or level.shape[1] != L or level.shape[0] == 0 or n_idx % level.shape[0] != 0:
-            raise ValueError(f"row_dense_level_times: level must be [n_rows, {L}] with n_rows dividing the {n_idx} queries")
-        n_rows = level.shape[0]
-        if rising.dim() != 3:
-            raise ValueError("row_dense_level_times: rising must be a [K, n_idx, L] tensor")
-        K = rising.shape[0]
-        for name, t, dtype, shape in (("n_rising", n_rising, torch.int32, (n_idx, L)),
-                                      ("n_falling", n_falling, torch.int32, (n_idx, L)),
-                                      ("rising", rising, torch.float64, (K, n_idx, L)),
-                                      ("falling", falling, torch.float64, (K, n_idx, L)), ("level", level, T, (n_rows, L)),
-                                      ("seg_ta", seg_ta, torch.float64, (n_seg,)), ("seg_tb", seg_tb, torch.float64, (n_seg,)),
-                                      ("seg", seg, torch.int32, (n_idx,)), ("x", x, T, (n_idx,)),
-                                      ("tq", tq.view(-1), torch.float64, (n_idx,)), ("seg2", seg2, torch.int32, (n_idx,)),
-                                      ("x2", x2, T, (n_idx,)), ("tq2", tq2.view(-1), torch.float64, (n_idx,))):
-            if tuple(t.shape) != shape or t.dtype != dtype or not t.is_contiguous():
-                raise ValueError(f"row_dense_level_times: {name} must be a contiguous {dtype} {list(shape)} tensor")
-        if not tq.is_contiguous() or not tq2.is_contiguous():
-            raise ValueError("row_dense_level_times: tq and tq2 must be contiguous")
-        _check(self.lib.tdeq_row_dense_level_times(n_rising.data_ptr(), n_falling.data_ptr(), rising.data_ptr(),
-                                                   falling.data_ptr(), K, level.data_ptr(), n_rows, coeffs.data_ptr(), n_seg,
-                                                   seg_ta.data_ptr(), seg_tb.data_ptr(), float(sign), seg.data_ptr(),
-                                                   x.data_ptr(), tq.data_ptr(), seg2.data_ptr(), x2.data_ptr(), tq2.data_ptr(),
-                                                   n_idx, L, dtype_code(T), self._stream()),
-               "tdeq_row_dense_level_times")
+        `level` [n_rows, L] on each window, and the number of crossings of each direction.  `n_rising`, `n_falling` int32
+        [n_idx, L]; `rising`, `falling` fp64 [K, n_idx, L] with K = rising.shape[0]; the record and the two query lists as
+        `_row_dense_window` describes them."""
+        K = rising.shape[0] if rising.dim() == 3 else None
+        tail = self._row_dense_window("row_dense_level_times",
+                                      (("n_rising", n_rising, torch.int32, ()), ("n_falling", n_falling, torch.int32, ()),
+                                       ("rising", rising, torch.float64, (K,)), ("falling", falling, torch.float64, (K,))),
+                                      coeffs, seg_ta, seg_tb, sign, seg, x, tq, seg2, x2, tq2, level=level,
+                                      refuse=None if K is not None else "rising must be a [K, n_idx, L] tensor")
+        if tail is not None:
+            _check(self.lib.tdeq_row_dense_level_times(n_rising.data_ptr(), n_falling.data_ptr(), rising.data_ptr(),
+                                                       falling.data_ptr(), K, *tail), "tdeq_row_dense_level_times")
 
 
 class ComplexHipKernels:

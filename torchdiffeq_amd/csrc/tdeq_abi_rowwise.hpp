@@ -870,35 +870,139 @@ int tdeq_row_dense_calc(void* out, int mode, const void* coeffs, int64_t n_seg, 
     });
 }
 
-// ---- extrema of the record over a time window: tdeq_row_dense_extremum --------------------------------------------------
+// ---- queries over a time window: tdeq_row_dense_extremum / _level / _level_times / _exposure ------------------------------
 namespace {
 
+// what the four entry points share, as it arrives (`level`, `n_rows`: the level family; NULL and 0 for the extrema)
+struct RowDenseWindowIn {
+    const void* level;
+    int64_t n_rows;
+    const void* coeffs;
+    int64_t n_seg;
+    const double* seg_ta;
+    const double* seg_tb;
+    double time_sign;
+    const int32_t* seg;
+    const void* x;
+    const double* tq;
+    const int32_t* seg2;
+    const void* x2;
+    const double* tq2;
+    int64_t n_idx;
+    int64_t row_len;
+};
+
+// The shared checks, after those of an entry point's own arguments (`outputs`: none of its outputs is NULL) ->
+// TDEQ_EINVAL, 0 (nothing to do) or 1 (launch).
+int row_dense_window_check(bool outputs, bool leveled, const RowDenseWindowIn& w, int dtype) {
+    if (!outputs || (leveled && !w.level) || !w.coeffs || !w.seg_ta || !w.seg_tb || !w.seg || !w.x || !w.tq || !w.seg2 ||
+        !w.x2 || !w.tq2 || !real_dtype_ok(dtype))
+        return TDEQ_EINVAL;
+    if (!(w.time_sign == 1.0 || w.time_sign == -1.0)) return TDEQ_EINVAL;
+    if (w.n_idx < 0 || w.n_seg < 0 || w.row_len < 0 || w.n_rows < 0) return TDEQ_EINVAL;
+    if (leveled && w.n_idx > 0 && (w.n_rows == 0 || w.n_idx % w.n_rows != 0)) return TDEQ_EINVAL;
+    if (w.n_idx == 0 || w.row_len == 0) return 0;
+    if (w.n_seg < 1 || w.n_seg > 0x7fffffffLL) return TDEQ_EINVAL;
+    return 1;
+}
+
+// (row_len and ne follow the 16-byte decision of the launch)
 template <typename T>
-int row_dense_extremum_launch(void* values, double* times, int which, const void* coeffs, int64_t n_seg, const double* seg_ta,
-                              const double* seg_tb, double time_sign, const int32_t* seg, const void* x, const double* tq,
-                              const int32_t* seg2, const void* x2, const double* tq2, int64_t n_idx, int64_t row_len,
-                              hipStream_t s) {
+void row_dense_window_fill(RowDenseWindowArgs<T>& a, const RowDenseWindowIn& w) {
+    a.q = static_cast<const T*>(w.coeffs);
+    a.seg_ta = w.seg_ta;
+    a.seg_tb = w.seg_tb;
+    a.sign = w.time_sign;
+    a.seg = w.seg;
+    a.x = static_cast<const T*>(w.x);
+    a.tq = w.tq;
+    a.seg2 = w.seg2;
+    a.x2 = static_cast<const T*>(w.x2);
+    a.tq2 = w.tq2;
+    a.n_rows = w.n_rows;
+    a.n_seg = w.n_seg;
+    a.q_plane = w.n_seg * w.row_len;
+}
+
+// int32 outputs are stored as one word of 16 / sizeof(T) int32: 16 bytes for float, 8 for double
+template <typename T>
+bool int_word_aligned(const int32_t* p) {
+    return reinterpret_cast<uintptr_t>(p) % (sizeof(int32_t) * (16 / sizeof(T))) == 0;
+}
+
+template <typename T>
+int row_dense_extremum_launch(void* values, double* times, int which, const RowDenseWindowIn& w, hipStream_t s) {
     RowDenseExtremumArgs<T> a;
+    row_dense_window_fill<T>(a, w);
     a.values = static_cast<T*>(values);
     a.times = times;
-    a.q = static_cast<const T*>(coeffs);
-    a.seg_ta = seg_ta;
-    a.seg_tb = seg_tb;
-    a.sign = time_sign;
-    a.seg = seg;
-    a.x = static_cast<const T*>(x);
-    a.tq = tq;
-    a.seg2 = seg2;
-    a.x2 = static_cast<const T*>(x2);
-    a.tq2 = tq2;
-    a.n_seg = n_seg;
-    a.q_plane = n_seg * row_len;
-    return row_vec<T>(row_len, all_aligned(values, times, coeffs), a.row_len, [&](auto vec) {
+    return row_vec<T>(w.row_len, all_aligned(values, times, w.coeffs), a.row_len, [&](auto vec) {
         constexpr bool VEC = decltype(vec)::value;
-        a.ne = n_idx * a.row_len;
+        a.ne = w.n_idx * a.row_len;
         const dim3 grid(stream_grid(a.ne, kBlock)), block(kBlock);
         if (which == kDenseMaximum) hipLaunchKernelGGL((row_dense_extremum_kernel<T, VEC, true>), grid, block, 0, s, a);
         else hipLaunchKernelGGL((row_dense_extremum_kernel<T, VEC, false>), grid, block, 0, s, a);
+        return check_launch();
+    });
+}
+
+template <typename T>
+int row_dense_level_launch(int32_t* count, double* first, double* last, double* time_above, const RowDenseWindowIn& w,
+                           hipStream_t s) {
+    RowDenseLevelArgs<T> a;
+    row_dense_window_fill<T>(a, w);
+    a.count = count;
+    a.first = first;
+    a.last = last;
+    a.total = time_above;
+    a.level = static_cast<const T*>(w.level);
+    const bool aligned = int_word_aligned<T>(count) && all_aligned(first, last, time_above, w.level, w.coeffs);
+    return row_vec<T>(w.row_len, aligned, a.row_len, [&](auto vec) {
+        constexpr bool VEC = decltype(vec)::value;
+        a.ne = w.n_idx * a.row_len;
+        hipLaunchKernelGGL((row_dense_level_kernel<T, VEC>), dim3(stream_grid(a.ne, kBlock)), dim3(kBlock), 0, s, a);
+        return check_launch();
+    });
+}
+
+template <typename T>
+int row_dense_level_times_launch(int32_t* n_rising, int32_t* n_falling, double* rising, double* falling, int64_t max_count,
+                                 const RowDenseWindowIn& w, hipStream_t s) {
+    RowDenseLevelTimesArgs<T> a;
+    row_dense_window_fill<T>(a, w);
+    // rising is meant in true time: rising = (the state becomes above) == (time_sign > 0)
+    const bool up_rises = w.time_sign > 0.0;
+    a.n_up = up_rises ? n_rising : n_falling;
+    a.n_dn = up_rises ? n_falling : n_rising;
+    a.ups = up_rises ? rising : falling;
+    a.dns = up_rises ? falling : rising;
+    a.k = static_cast<int32_t>(max_count);
+    a.level = static_cast<const T*>(w.level);
+    a.t_plane = w.n_idx * w.row_len;
+    // (the lists take 8-byte stores in either form)
+    const bool aligned = int_word_aligned<T>(n_rising) && int_word_aligned<T>(n_falling) && all_aligned(w.level, w.coeffs);
+    return row_vec<T>(w.row_len, aligned, a.row_len, [&](auto vec) {
+        constexpr bool VEC = decltype(vec)::value;
+        a.ne = w.n_idx * a.row_len;
+        hipLaunchKernelGGL((row_dense_level_times_kernel<T, VEC>), dim3(stream_grid(a.ne, kBlock)), dim3(kBlock), 0, s, a);
+        return check_launch();
+    });
+}
+
+template <typename T>
+int row_dense_exposure_launch(void* area_above, void* area_below, double* time_above, const RowDenseWindowIn& w,
+                              hipStream_t s) {
+    RowDenseExposureArgs<T> a;
+    row_dense_window_fill<T>(a, w);
+    a.area_above = static_cast<T*>(area_above);
+    a.area_below = static_cast<T*>(area_below);
+    a.total = time_above;
+    a.level = static_cast<const T*>(w.level);
+    const bool aligned = all_aligned(area_above, area_below, time_above, w.level, w.coeffs);
+    return row_vec<T>(w.row_len, aligned, a.row_len, [&](auto vec) {
+        constexpr bool VEC = decltype(vec)::value;
+        a.ne = w.n_idx * a.row_len;
+        hipLaunchKernelGGL((row_dense_exposure_kernel<T, VEC>), dim3(stream_grid(a.ne, kBlock)), dim3(kBlock), 0, s, a);
         return check_launch();
     });
 }
@@ -909,197 +1013,52 @@ int tdeq_row_dense_extremum(void* values, double* times, int which, const void* 
                             const double* seg_tb, double time_sign, const int32_t* seg, const void* x, const double* tq,
                             const int32_t* seg2, const void* x2, const double* tq2, int64_t n_idx, int64_t row_len, int dtype,
                             void* stream) {
-    if (!values || !times || !coeffs || !seg_ta || !seg_tb || !seg || !x || !tq || !seg2 || !x2 || !tq2 || !real_dtype_ok(dtype))
-        return TDEQ_EINVAL;
+    const RowDenseWindowIn w{nullptr, 0, coeffs, n_seg, seg_ta, seg_tb, time_sign, seg, x, tq, seg2, x2, tq2, n_idx, row_len};
     if (which != TDEQ_DENSE_MAXIMUM && which != TDEQ_DENSE_MINIMUM) return TDEQ_EINVAL;
-    if (!(time_sign == 1.0 || time_sign == -1.0)) return TDEQ_EINVAL;
-    if (n_idx < 0 || n_seg < 0 || row_len < 0) return TDEQ_EINVAL;
-    if (n_idx == 0 || row_len == 0) return 0;
-    if (n_seg < 1 || n_seg > 0x7fffffffLL) return TDEQ_EINVAL;
+    const int go = row_dense_window_check(values && times, false, w, dtype);
+    if (go != 1) return go;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    return real_dtype(dtype, [&](auto t) {
-        return row_dense_extremum_launch<decltype(t)>(values, times, which, coeffs, n_seg, seg_ta, seg_tb, time_sign, seg, x,
-                                                      tq, seg2, x2, tq2, n_idx, row_len, s);
-    });
+    return real_dtype(dtype, [&](auto t) { return row_dense_extremum_launch<decltype(t)>(values, times, which, w, s); });
 }
-
-// ---- level crossings of the record over a time window: tdeq_row_dense_level --------------------------------------------------
-namespace {
-
-template <typename T>
-int row_dense_level_launch(int32_t* count, double* first, double* last, double* time_above, const void* level, int64_t n_rows,
-                           const void* coeffs, int64_t n_seg, const double* seg_ta, const double* seg_tb, double time_sign,
-                           const int32_t* seg, const void* x, const double* tq, const int32_t* seg2, const void* x2,
-                           const double* tq2, int64_t n_idx, int64_t row_len, hipStream_t s) {
-    RowDenseLevelArgs<T> a;
-    a.count = count;
-    a.first = first;
-    a.last = last;
-    a.total = time_above;
-    a.level = static_cast<const T*>(level);
-    a.q = static_cast<const T*>(coeffs);
-    a.seg_ta = seg_ta;
-    a.seg_tb = seg_tb;
-    a.sign = time_sign;
-    a.seg = seg;
-    a.x = static_cast<const T*>(x);
-    a.tq = tq;
-    a.seg2 = seg2;
-    a.x2 = static_cast<const T*>(x2);
-    a.tq2 = tq2;
-    a.n_rows = n_rows;
-    a.n_seg = n_seg;
-    a.q_plane = n_seg * row_len;
-    // `count` is stored as one word of 16 / sizeof(T) int32: 16 bytes for float, 8 for double
-    const bool count_ok = reinterpret_cast<uintptr_t>(count) % (sizeof(int32_t) * (16 / sizeof(T))) == 0;
-    return row_vec<T>(row_len, count_ok && all_aligned(first, last, time_above, level, coeffs), a.row_len, [&](auto vec) {
-        constexpr bool VEC = decltype(vec)::value;
-        a.ne = n_idx * a.row_len;
-        hipLaunchKernelGGL((row_dense_level_kernel<T, VEC>), dim3(stream_grid(a.ne, kBlock)), dim3(kBlock), 0, s, a);
-        return check_launch();
-    });
-}
-
-}  // namespace
 
 int tdeq_row_dense_level(int32_t* count, double* first, double* last, double* time_above, const void* level, int64_t n_rows,
                          const void* coeffs, int64_t n_seg, const double* seg_ta, const double* seg_tb, double time_sign,
                          const int32_t* seg, const void* x, const double* tq, const int32_t* seg2, const void* x2,
                          const double* tq2, int64_t n_idx, int64_t row_len, int dtype, void* stream) {
-    if (!count || !first || !last || !time_above || !level || !coeffs || !seg_ta || !seg_tb || !seg || !x || !tq || !seg2 ||
-        !x2 || !tq2 || !real_dtype_ok(dtype))
-        return TDEQ_EINVAL;
-    if (!(time_sign == 1.0 || time_sign == -1.0)) return TDEQ_EINVAL;
-    if (n_idx < 0 || n_seg < 0 || row_len < 0 || n_rows < 0) return TDEQ_EINVAL;
-    if (n_idx > 0 && (n_rows == 0 || n_idx % n_rows != 0)) return TDEQ_EINVAL;
-    if (n_idx == 0 || row_len == 0) return 0;
-    if (n_seg < 1 || n_seg > 0x7fffffffLL) return TDEQ_EINVAL;
+    const RowDenseWindowIn w{level, n_rows, coeffs, n_seg, seg_ta, seg_tb, time_sign, seg, x, tq, seg2, x2, tq2, n_idx, row_len};
+    const int go = row_dense_window_check(count && first && last && time_above, true, w, dtype);
+    if (go != 1) return go;
     hipStream_t s = static_cast<hipStream_t>(stream);
     return real_dtype(dtype, [&](auto t) {
-        return row_dense_level_launch<decltype(t)>(count, first, last, time_above, level, n_rows, coeffs, n_seg, seg_ta, seg_tb,
-                                                   time_sign, seg, x, tq, seg2, x2, tq2, n_idx, row_len, s);
+        return row_dense_level_launch<decltype(t)>(count, first, last, time_above, w, s);
     });
 }
-
-// ---- the times of all crossings of a level over a time window: tdeq_row_dense_level_times ---------------------------------
-namespace {
-
-template <typename T>
-int row_dense_level_times_launch(int32_t* n_rising, int32_t* n_falling, double* rising, double* falling, int64_t max_count,
-                                 const void* level, int64_t n_rows, const void* coeffs, int64_t n_seg, const double* seg_ta,
-                                 const double* seg_tb, double time_sign, const int32_t* seg, const void* x, const double* tq,
-                                 const int32_t* seg2, const void* x2, const double* tq2, int64_t n_idx, int64_t row_len,
-                                 hipStream_t s) {
-    RowDenseLevelTimesArgs<T> a;
-    // rising is meant in true time: rising = (the state becomes above) == (time_sign > 0)
-    const bool up_rises = time_sign > 0.0;
-    a.n_up = up_rises ? n_rising : n_falling;
-    a.n_dn = up_rises ? n_falling : n_rising;
-    a.ups = up_rises ? rising : falling;
-    a.dns = up_rises ? falling : rising;
-    a.k = static_cast<int32_t>(max_count);
-    a.level = static_cast<const T*>(level);
-    a.q = static_cast<const T*>(coeffs);
-    a.seg_ta = seg_ta;
-    a.seg_tb = seg_tb;
-    a.sign = time_sign;
-    a.seg = seg;
-    a.x = static_cast<const T*>(x);
-    a.tq = tq;
-    a.seg2 = seg2;
-    a.x2 = static_cast<const T*>(x2);
-    a.tq2 = tq2;
-    a.n_rows = n_rows;
-    a.n_seg = n_seg;
-    a.q_plane = n_seg * row_len;
-    a.t_plane = n_idx * row_len;
-    // the counters are stored as one word of 16 / sizeof(T) int32 each; the lists take 8-byte stores in either form
-    const uintptr_t word = sizeof(int32_t) * (16 / sizeof(T));
-    const bool counters_ok =
-        reinterpret_cast<uintptr_t>(n_rising) % word == 0 && reinterpret_cast<uintptr_t>(n_falling) % word == 0;
-    return row_vec<T>(row_len, counters_ok && all_aligned(level, coeffs), a.row_len, [&](auto vec) {
-        constexpr bool VEC = decltype(vec)::value;
-        a.ne = n_idx * a.row_len;
-        hipLaunchKernelGGL((row_dense_level_times_kernel<T, VEC>), dim3(stream_grid(a.ne, kBlock)), dim3(kBlock), 0, s, a);
-        return check_launch();
-    });
-}
-
-}  // namespace
 
 int tdeq_row_dense_level_times(int32_t* n_rising, int32_t* n_falling, double* rising, double* falling, int64_t max_count,
                                const void* level, int64_t n_rows, const void* coeffs, int64_t n_seg, const double* seg_ta,
                                const double* seg_tb, double time_sign, const int32_t* seg, const void* x, const double* tq,
                                const int32_t* seg2, const void* x2, const double* tq2, int64_t n_idx, int64_t row_len,
                                int dtype, void* stream) {
-    if (!n_rising || !n_falling || !rising || !falling || !level || !coeffs || !seg_ta || !seg_tb || !seg || !x || !tq ||
-        !seg2 || !x2 || !tq2 || !real_dtype_ok(dtype))
-        return TDEQ_EINVAL;
+    const RowDenseWindowIn w{level, n_rows, coeffs, n_seg, seg_ta, seg_tb, time_sign, seg, x, tq, seg2, x2, tq2, n_idx, row_len};
     if (max_count < 1 || max_count > 65535) return TDEQ_EINVAL;
-    if (!(time_sign == 1.0 || time_sign == -1.0)) return TDEQ_EINVAL;
-    if (n_idx < 0 || n_seg < 0 || row_len < 0 || n_rows < 0) return TDEQ_EINVAL;
-    if (n_idx > 0 && (n_rows == 0 || n_idx % n_rows != 0)) return TDEQ_EINVAL;
-    if (n_idx == 0 || row_len == 0) return 0;
-    if (n_seg < 1 || n_seg > 0x7fffffffLL) return TDEQ_EINVAL;
+    const int go = row_dense_window_check(n_rising && n_falling && rising && falling, true, w, dtype);
+    if (go != 1) return go;
     hipStream_t s = static_cast<hipStream_t>(stream);
     return real_dtype(dtype, [&](auto t) {
-        return row_dense_level_times_launch<decltype(t)>(n_rising, n_falling, rising, falling, max_count, level, n_rows,
-                                                         coeffs, n_seg, seg_ta, seg_tb, time_sign, seg, x, tq, seg2, x2,
-                                                         tq2, n_idx, row_len, s);
+        return row_dense_level_times_launch<decltype(t)>(n_rising, n_falling, rising, falling, max_count, w, s);
     });
 }
-
-// ---- area above and below a level over a time window: tdeq_row_dense_exposure ---------------------------------------------
-namespace {
-
-template <typename T>
-int row_dense_exposure_launch(void* area_above, void* area_below, double* time_above, const void* level, int64_t n_rows,
-                              const void* coeffs, int64_t n_seg, const double* seg_ta, const double* seg_tb, const int32_t* seg,
-                              const void* x, const double* tq, const int32_t* seg2, const void* x2, const double* tq2,
-                              int64_t n_idx, int64_t row_len, hipStream_t s) {
-    RowDenseExposureArgs<T> a;
-    a.area_above = static_cast<T*>(area_above);
-    a.area_below = static_cast<T*>(area_below);
-    a.total = time_above;
-    a.level = static_cast<const T*>(level);
-    a.q = static_cast<const T*>(coeffs);
-    a.seg_ta = seg_ta;
-    a.seg_tb = seg_tb;
-    a.seg = seg;
-    a.x = static_cast<const T*>(x);
-    a.tq = tq;
-    a.seg2 = seg2;
-    a.x2 = static_cast<const T*>(x2);
-    a.tq2 = tq2;
-    a.n_rows = n_rows;
-    a.n_seg = n_seg;
-    a.q_plane = n_seg * row_len;
-    return row_vec<T>(row_len, all_aligned(area_above, area_below, time_above, level, coeffs), a.row_len, [&](auto vec) {
-        constexpr bool VEC = decltype(vec)::value;
-        a.ne = n_idx * a.row_len;
-        hipLaunchKernelGGL((row_dense_exposure_kernel<T, VEC>), dim3(stream_grid(a.ne, kBlock)), dim3(kBlock), 0, s, a);
-        return check_launch();
-    });
-}
-
-}  // namespace
 
 // (the areas and the time above are durations: `time_sign` is checked and not used)
 int tdeq_row_dense_exposure(void* area_above, void* area_below, double* time_above, const void* level, int64_t n_rows,
                             const void* coeffs, int64_t n_seg, const double* seg_ta, const double* seg_tb, double time_sign,
                             const int32_t* seg, const void* x, const double* tq, const int32_t* seg2, const void* x2,
                             const double* tq2, int64_t n_idx, int64_t row_len, int dtype, void* stream) {
-    if (!area_above || !area_below || !time_above || !level || !coeffs || !seg_ta || !seg_tb || !seg || !x || !tq || !seg2 ||
-        !x2 || !tq2 || !real_dtype_ok(dtype))
-        return TDEQ_EINVAL;
-    if (!(time_sign == 1.0 || time_sign == -1.0)) return TDEQ_EINVAL;
-    if (n_idx < 0 || n_seg < 0 || row_len < 0 || n_rows < 0) return TDEQ_EINVAL;
-    if (n_idx > 0 && (n_rows == 0 || n_idx % n_rows != 0)) return TDEQ_EINVAL;
-    if (n_idx == 0 || row_len == 0) return 0;
-    if (n_seg < 1 || n_seg > 0x7fffffffLL) return TDEQ_EINVAL;
+    const RowDenseWindowIn w{level, n_rows, coeffs, n_seg, seg_ta, seg_tb, time_sign, seg, x, tq, seg2, x2, tq2, n_idx, row_len};
+    const int go = row_dense_window_check(area_above && area_below && time_above, true, w, dtype);
+    if (go != 1) return go;
     hipStream_t s = static_cast<hipStream_t>(stream);
     return real_dtype(dtype, [&](auto t) {
-        return row_dense_exposure_launch<decltype(t)>(area_above, area_below, time_above, level, n_rows, coeffs, n_seg, seg_ta,
-                                                      seg_tb, seg, x, tq, seg2, x2, tq2, n_idx, row_len, s);
+        return row_dense_exposure_launch<decltype(t)>(area_above, area_below, time_above, w, s);
     });
 }

@@ -14,9 +14,10 @@
 //   row_dense_search   one lane per query: the segment of the row that holds the query time (bisection over the row's
 //                      segment ends) and the fraction x of that step, in the arithmetic of row_dense_commit
 // followed by row_event_eval_mapped on (coeffs, seg, x).  No LDS; plain vector loads and stores; 64-bit element offsets.
-// The derivative, antiderivative and integral of the record (row_dense_prefix, row_dense_calc), its extrema over a time
-// window (row_dense_extremum), its crossings of a level (row_dense_level), its area above and below a level
-// (row_dense_exposure) and the times of all its crossings of a level (row_dense_level_times) are at the end of the file.
+// The derivative, antiderivative and integral of the record (row_dense_prefix, row_dense_calc) follow, and at the end of the
+// file the queries over a time window: one walk over the window's segments (row_dense_walk) and one level machine on it
+// (row_dense_level_walk) carry the extrema (row_dense_extremum), the crossings of a level (row_dense_level), the area above
+// and below a level (row_dense_exposure) and the times of all crossings of a level (row_dense_level_times).
 #pragma once
 
 #include "tdeq_kernels_rowwise.hpp"
@@ -155,6 +156,17 @@ __device__ __forceinline__ void load_lanes(const T* base, int64_t at, T (&v)[LV]
     __builtin_memcpy(v, &w, sizeof(E));
 }
 
+// the five planes e, d, c, b, a of a record `q` at element offset `at`
+template <typename T, typename E, int LV>
+__device__ __forceinline__ void load_planes(const T* q, int64_t q_plane, int64_t at, T (&qe)[LV], T (&qd)[LV], T (&qc)[LV],
+                                            T (&qb)[LV], T (&qa)[LV]) {
+    load_lanes<T, E, LV>(q, at, qe);
+    load_lanes<T, E, LV>(q + q_plane, at, qd);
+    load_lanes<T, E, LV>(q + 2 * q_plane, at, qc);
+    load_lanes<T, E, LV>(q + 3 * q_plane, at, qb);
+    load_lanes<T, E, LV>(q + 4 * q_plane, at, qa);
+}
+
 template <int LV>
 __device__ __forceinline__ void store_doubles(double* p, const double (&v)[LV]) {
     if constexpr (LV == 1) {
@@ -214,11 +226,7 @@ __global__ __launch_bounds__(kBlock) void row_dense_prefix_kernel(const RowDense
         for (; s < end; ++s) {                                        // serial by construction: the order is the contract
             const int64_t at = s * a.row_len + el;
             T qe[LV], qd[LV], qc[LV], qb[LV], qa[LV];
-            load_lanes<T, E, LV>(a.q, at, qe);
-            load_lanes<T, E, LV>(a.q + a.q_plane, at, qd);
-            load_lanes<T, E, LV>(a.q + 2 * a.q_plane, at, qc);
-            load_lanes<T, E, LV>(a.q + 3 * a.q_plane, at, qb);
-            load_lanes<T, E, LV>(a.q + 4 * a.q_plane, at, qa);
+            load_planes<T, E, LV>(a.q, a.q_plane, at, qe, qd, qc, qb, qa);
             const double h = a.seg_tb[s] - a.seg_ta[s];
             store_doubles<LV>(a.prefix + at * LV, acc);
 #pragma unroll
@@ -262,11 +270,7 @@ __device__ __forceinline__ void row_dense_antiderivative_one(const RowDenseCalcA
     const double x64 = xT != xT ? __builtin_nan("") : (tq - ta) / h;
     const int64_t at = s * a.row_len + el;
     T qe[LV], qd[LV], qc[LV], qb[LV], qa[LV];
-    load_lanes<T, E, LV>(a.q, at, qe);
-    load_lanes<T, E, LV>(a.q + a.q_plane, at, qd);
-    load_lanes<T, E, LV>(a.q + 2 * a.q_plane, at, qc);
-    load_lanes<T, E, LV>(a.q + 3 * a.q_plane, at, qb);
-    load_lanes<T, E, LV>(a.q + 4 * a.q_plane, at, qa);
+    load_planes<T, E, LV>(a.q, a.q_plane, at, qe, qd, qc, qb, qa);
     double p[LV];
     load_doubles<LV>(a.prefix + at * LV, p);
 #pragma unroll
@@ -318,33 +322,53 @@ __global__ __launch_bounds__(kBlock) void row_dense_calc_kernel(const RowDenseCa
     }
 }
 
-// ---- extrema of the record over a time window (ABI 32): RowDenseOutput.maximum / .minimum -----------------------------
-//   row_dense_extremum   the shape of row_dense_calc with a walk: one lane per (query, 16-byte element) goes through the
-//                        segments segA .. segB of its window serially and keeps, per element, the best candidate value and
-//                        its time.  The arithmetic — fp64, + - * /, comparisons and fabs only — is stated in
-//                        include/tdeq_hip.h and is the contract; the host model (rowwise.py quartic_extrema) has its bits.
+// ---- queries over a time window (ABI 32 to 35): extrema, level crossings, exposure, crossing times -----------------------
+// Four kernels in the shape of row_dense_calc, one lane per (query, 16-byte element), on ONE walk and ONE level machine:
+//   row_dense_walk         the window's prologue (both ends, in solver-time order, clamped to the record), the serial loop over
+//                          its segments segA .. segB, the five planes of each, and per element a WindowQuartic: the
+//                          coefficients as doubles, y' and y'', the segment clipped to the window, the candidates of the
+//                          isolation in increasing x and the time of a candidate
+//   row_dense_level_walk   the walk with a state machine over the candidates of phi = y - level: between two neighbouring
+//                          candidates the quartic is monotone, so phi has at most one root there, found by one more bisection.
+//                          It keeps above / nan per element and tells its caller of the window's opening, of every crossing
+//                          (tz, above after it) and, for the exposure alone, of every piece K(v) - K(u)
+// and what each kernel keeps:
+//   row_dense_extremum     (RowDenseOutput.maximum / .minimum) the best candidate value and its time
+//   row_dense_level        (.crossings / .time_above) count / first / last and the time above
+//   row_dense_exposure     (.exposure / .area_above / .area_below) the time above and the two areas: K is J_s of
+//                          row_dense_prefix with e - level in place of e; a piece adds to the area above or takes from the
+//                          area below by the state, and a crossing at z splits its piece there
+//   row_dense_level_times  (.crossing_times) one int32 counter per direction; a crossing located at tz goes straight to global
+//                          memory: slot n of its direction's list while n < K, as one 8-byte store; the counter runs on.
+//                          Rising is defined in true time: the state becomes above and time_sign > 0, or it becomes not above
+//                          and time_sign < 0; the launcher hands the two directions over as `ups` and `dns` accordingly.  After
+//                          the walk the free slots are filled with NaN, so every slot of the four outputs is written.  The list
+//                          index is an offset in global memory, never an index into a per-lane array
+// The arithmetic — fp64, + - * /, comparisons and fabs only — is stated in include/tdeq_hip.h and is the contract; the host
+// model (rowwise.py: _window_walk, _level_walk and quartic_extrema / _levels / _exposure / _crossing_times) has its bits.
 // On a segment where the element is monotone the lane evaluates g1 twice (three times with x1 inside), g twice and p twice
-// and takes no loop.  A bisection is at most 64 dependent rounds of one Horner form (4 to 6 fp64 operations and a compare);
-// lanes of a wave that need none wait for those that do.  No LDS, no atomics, no workspace.
+// and takes no loop; the level machine adds at most 7 evaluations of phi, the exposure as many of K.  A bisection is at most 64
+// dependent rounds of one Horner form (4 to 6 fp64 operations and a compare); lanes of a wave that need none wait for those
+// that do.  Per-lane state is named scalars and arrays indexed by the unrolled element only.  No LDS, no atomics, no workspace.
 
 // modes of row_dense_extremum (== TDEQ_DENSE_MAXIMUM / _MINIMUM)
 constexpr int kDenseMaximum = 0;
 constexpr int kDenseMinimum = 1;
 
+// what the four kernels share: the record and the two query lists of row_dense_search
 template <typename T>
-struct RowDenseExtremumArgs {
-    T* values;                        // [n_idx, L]
-    double* times;                    // [n_idx, L] true time
+struct RowDenseWindowArgs {
     const T* q;                       // [5, n_seg, L]
     const double* seg_ta;             // [n_seg]
     const double* seg_tb;             // [n_seg]
-    double sign;
-    const int32_t* seg;               // [n_idx] one end of each window (row_dense_search)
+    double sign;                      // (the exposure keeps durations only and does not read it)
+    const int32_t* seg;               // [n_idx] one end of each window
     const T* x;                       // [n_idx] NaN marks an out-of-range end
     const double* tq;                 // [n_idx] solver time
     const int32_t* seg2;              // the other end
     const T* x2;
     const double* tq2;
+    int64_t n_rows;                   // query i belongs to row i % n_rows (read with a level only)
     int64_t n_seg;
     int64_t row_len;                  // E units
     int64_t ne;                       // n_idx * row_len
@@ -414,121 +438,148 @@ __device__ __forceinline__ void quartic_candidates(const QuarticSlope& g, const 
     visit(xhi);
 }
 
-template <typename T, bool VEC, bool MAX>
-__global__ __launch_bounds__(kBlock) void row_dense_extremum_kernel(const RowDenseExtremumArgs<T> a) {
-    using E = typename std::conditional<VEC, typename VecOf<T>::type, T>::type;
-    constexpr int LV = VEC ? VecOf<T>::L : 1;
-    const int64_t stride = (int64_t)gridDim.x * kBlock;
-    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < a.ne; i += stride) {
-        const int64_t r = i / a.row_len;
-        const int64_t el = i - r * a.row_len;
-        int64_t sA = a.seg[r], sB = a.seg2[r];
-        double tqa = a.tq[r], tqb = a.tq2[r];
-        const T xa = a.x[r], xb = a.x2[r];
-        if (tqb < tqa) {
-            const int64_t s = sA;
-            sA = sB;
-            sB = s;
-            const double t = tqa;
-            tqa = tqb;
-            tqb = t;
-        }
-        if (sA < 0) sA = 0;                                           // (nothing is read outside the record)
-        if (sB > a.n_seg - 1) sB = a.n_seg - 1;
-        const bool bad = xa != xa || xb != xb || sA > sB;             // (sA > sB: only from ends the search did not write)
-        double best[LV], when[LV];
-        bool nanv[LV];
-#pragma unroll
-        for (int c = 0; c < LV; ++c) {
-            best[c] = when[c] = 0.0;
-            nanv[c] = bad;
-        }
-        bool first = true;
-        for (int64_t s = bad ? sB + 1 : sA; s <= sB; ++s) {           // serial: segments in order
-            const int64_t at = s * a.row_len + el;
-            T qe[LV], qd[LV], qc[LV], qb[LV], qa[LV];
-            load_lanes<T, E, LV>(a.q, at, qe);
-            load_lanes<T, E, LV>(a.q + a.q_plane, at, qd);
-            load_lanes<T, E, LV>(a.q + 2 * a.q_plane, at, qc);
-            load_lanes<T, E, LV>(a.q + 3 * a.q_plane, at, qb);
-            load_lanes<T, E, LV>(a.q + 4 * a.q_plane, at, qa);
-            const double ta = a.seg_ta[s], tb = a.seg_tb[s];
-            const double h = tb - ta;
-            const bool atA = s == sA, atB = s == sB;
-            const double xlo = atA ? (tqa - ta) / h : 0.0;
-            const double xhi = atB ? (tqb - ta) / h : 1.0;
-#pragma unroll
-            for (int c = 0; c < LV; ++c) {
-                const double e = (double)qe[c], d = (double)qd[c], cc = (double)qc[c], b = (double)qb[c], aa = (double)qa[c];
-                const double c2 = cc + cc, a4 = 4.0 * aa;
-                const QuarticSlope g{d, c2, 3.0 * b, a4};
-                const QuarticCurvature g1{c2, 6.0 * b, 12.0 * aa};
-                double bst = best[c], whn = when[c];
-                bool have = !first;
-                auto consider = [&](double x) {
-                    const double v = e + x * (d + x * (cc + x * (b + x * aa)));
-                    if (v != v) nanv[c] = true;
-                    if (!have || (MAX ? v > bst : v < bst)) {
-                        have = true;
-                        bst = v;
-                        whn = (atA && x == xlo) ? tqa : (atB && x == xhi) ? tqb : x == 0.0 ? ta : x == 1.0 ? tb : ta + x * h;
-                    }
-                };
-                quartic_candidates(g, g1, b, aa, a4, xlo, xhi, consider);
-                best[c] = bst;
-                when[c] = whn;
-            }
-            first = false;
-        }
-        T o[LV];
-#pragma unroll
-        for (int c = 0; c < LV; ++c) {
-            o[c] = nanv[c] ? (T)__builtin_nan("") : (T)best[c];
-            when[c] = nanv[c] ? __builtin_nan("") : a.sign * when[c];
-        }
-        E w;
-        __builtin_memcpy(&w, o, sizeof(E));
-        reinterpret_cast<E*>(a.values)[i] = w;
-        store_doubles<LV>(a.times + i * LV, when);
+// one element on one segment of its window, as the walk hands it over; operator() is p of the header
+struct WindowQuartic {
+    double e, d, c, b, a;             // the element's coefficients
+    QuarticSlope g;                   // y'
+    QuarticCurvature g1;              // y''
+    double ta, tb, h;                 // the segment
+    double tqa, tqb;                  // the window's ends, tqa <= tqb
+    bool atA, atB;                    // this is the window's first / last segment
+    double xlo, xhi;                  // the segment clipped to the window
+    __device__ __forceinline__ double operator()(double x) const { return e + x * (d + x * (c + x * (b + x * a))); }
+    template <typename V>
+    __device__ __forceinline__ void candidates(V&& visit) const {
+        quartic_candidates(g, g1, b, a, g.c3, xlo, xhi, visit);
     }
-}
-
-// ---- level crossings of the record over a time window (ABI 33): RowDenseOutput.crossings / .time_above ------------------
-//   row_dense_level   the walk of row_dense_extremum with a state machine in place of the selection: between two
-//                     neighbouring candidates the quartic is monotone, so phi = p - level has at most one root there, found
-//                     by one more bisection.  Per element the lane keeps above / t_up / total / count / first / last.  The
-//                     arithmetic is stated in include/tdeq_hip.h; the host model is rowwise.py quartic_levels.
-// A segment without a crossing costs the isolation of the extremum walk and at most 7 evaluations of phi.  No LDS, no
-// atomics, no workspace.
-
-template <typename T>
-struct RowDenseLevelArgs {
-    int32_t* count;                   // [n_idx, L]
-    double* first;                    // [n_idx, L] true time
-    double* last;                     // [n_idx, L] true time
-    double* total;                    // [n_idx, L] duration
-    const T* level;                   // [n_rows, L]
-    const T* q;                       // [5, n_seg, L]
-    const double* seg_ta;             // [n_seg]
-    const double* seg_tb;             // [n_seg]
-    double sign;
-    const int32_t* seg;               // [n_idx] one end of each window (row_dense_search)
-    const T* x;                       // [n_idx] NaN marks an out-of-range end
-    const double* tq;                 // [n_idx] solver time
-    const int32_t* seg2;              // the other end
-    const T* x2;
-    const double* tq2;
-    int64_t n_rows;                   // query i belongs to row i % n_rows
-    int64_t n_seg;
-    int64_t row_len;                  // E units
-    int64_t ne;                       // n_idx * row_len
-    int64_t q_plane;                  // n_seg * L elements of T
+    // the time of a candidate: a window's end and a breakpoint are the stored words, not ta + x * h
+    __device__ __forceinline__ double time_of(double z) const {
+        return (atA && z == xlo) ? tqa : (atB && z == xhi) ? tqb : z == 0.0 ? ta : z == 1.0 ? tb : ta + z * h;
+    }
 };
 
-// phi of the header: the extremum's p, then one subtraction
-struct QuarticLevel {
-    double e, d, c, b, a, lev;
-    __device__ __forceinline__ double operator()(double x) const { return (e + x * (d + x * (c + x * (b + x * a)))) - lev; }
+struct RowDenseWindow {
+    double tqb;                       // the window's later end
+    bool bad;                         // an end is out of range: no segment was walked
+};
+
+// The walk of window r for the LV elements at `el`: each(c, WindowQuartic) for every segment in order and, inside it, every
+// element c.  Serial by construction.
+template <typename T, typename E, int LV, typename F>
+__device__ __forceinline__ RowDenseWindow row_dense_walk(const RowDenseWindowArgs<T>& a, int64_t r, int64_t el, F&& each) {
+    int64_t sA = a.seg[r], sB = a.seg2[r];
+    double tqa = a.tq[r], tqb = a.tq2[r];
+    const T xa = a.x[r], xb = a.x2[r];
+    if (tqb < tqa) {
+        const int64_t s = sA;
+        sA = sB;
+        sB = s;
+        const double t = tqa;
+        tqa = tqb;
+        tqb = t;
+    }
+    if (sA < 0) sA = 0;                                               // (nothing is read outside the record)
+    if (sB > a.n_seg - 1) sB = a.n_seg - 1;
+    const bool bad = xa != xa || xb != xb || sA > sB;                 // (sA > sB: only from ends the search did not write)
+    for (int64_t s = bad ? sB + 1 : sA; s <= sB; ++s) {               // serial: segments in order
+        T qe[LV], qd[LV], qc[LV], qb[LV], qa[LV];
+        load_planes<T, E, LV>(a.q, a.q_plane, s * a.row_len + el, qe, qd, qc, qb, qa);
+        const double ta = a.seg_ta[s], tb = a.seg_tb[s];
+        const double h = tb - ta;
+        const bool atA = s == sA, atB = s == sB;
+        const double xlo = atA ? (tqa - ta) / h : 0.0;
+        const double xhi = atB ? (tqb - ta) / h : 1.0;
+#pragma unroll
+        for (int c = 0; c < LV; ++c) {
+            const double e = (double)qe[c], d = (double)qd[c], cc = (double)qc[c], b = (double)qb[c], aa = (double)qa[c];
+            const double c2 = cc + cc, a4 = 4.0 * aa;
+            each(c, WindowQuartic{e, d, cc, b, aa, {d, c2, 3.0 * b, a4}, {c2, 6.0 * b, 12.0 * aa}, ta, tb, h, tqa, tqb, atA, atB,
+                                  xlo, xhi});
+        }
+    }
+    return {tqb, bad};
+}
+
+template <int LV>
+struct RowDenseLevelWalk {
+    double tqb;                       // the window's later end
+    bool above[LV];                   // the state at the window's end
+    bool nan[LV];                     // the element's answer is NaN: a bad window, or phi was NaN at a candidate
+};
+
+struct NoPieces {
+    __device__ __forceinline__ void operator()(int, double, bool) const {}
+};
+
+// The level machine on the walk, for `level` [n_rows, L].  Its caller hears open(c, tqa) at the window's first candidate,
+// cross(c, tz, ab) at every crossing (tz in solver time; ab: above after it) and, with AREA, piece(c, q, over) for every
+// piece between two candidates of a segment, split at a crossing: q = K(v) - K(u), over: the state on it.  K is evaluated
+// with AREA only.
+template <typename T, typename E, int LV, bool AREA, typename Open, typename Cross, typename Piece>
+__device__ __forceinline__ RowDenseLevelWalk<LV> row_dense_level_walk(const RowDenseWindowArgs<T>& a, const T* level, int64_t r,
+                                                                      int64_t el, Open&& open, Cross&& cross, Piece&& piece) {
+    T lev[LV];
+    load_lanes<T, E, LV>(level, (r % a.n_rows) * a.row_len + el, lev);
+    RowDenseLevelWalk<LV> m;
+#pragma unroll
+    for (int c = 0; c < LV; ++c) m.above[c] = m.nan[c] = false;
+    const RowDenseWindow w = row_dense_walk<T, E, LV>(a, r, el, [&](int c, const WindowQuartic& s) {
+        const double lv = (double)lev[c], el0 = s.e - lv;
+        auto phi = [&](double x) { return s(x) - lv; };               // phi of the header: p, then one subtraction
+        auto K = [&](double x) { return quartic_integral_one(el0, s.d, s.c, s.b, s.a, x, s.h); };
+        bool st = m.above[c], entry = true;                           // entry: the segment's first candidate comes next
+        double u = s.xlo, fu = 0.0, ku = 0.0;
+        s.candidates([&](double x) {
+            const double v = phi(x);
+            if (v != v) m.nan[c] = true;
+            const bool ab = v > 0.0;
+            double kx = 0.0;
+            if constexpr (AREA) kx = K(x);
+            if (entry && s.atA) {                                     // the window's first candidate sets the state
+                st = ab;
+                open(c, s.tqa);
+            } else {
+                double kz = ku;                                       // (no crossing: one piece, K(x) - K(u))
+                if (ab != st) {
+                    double z = x;                                     // (a later segment's first candidate: the breakpoint)
+                    if (!entry) {
+                        if (fu == 0.0) z = u;
+                        else if (v != 0.0) quartic_bisect(phi, u, x, z);
+                        if constexpr (AREA) {
+                            kz = K(z);
+                            piece(c, kz - ku, st);
+                        }
+                    }
+                    cross(c, s.time_of(z), ab);
+                    st = ab;
+                }
+                if constexpr (AREA) {
+                    if (!entry) piece(c, kx - kz, st);
+                }
+            }
+            entry = false;
+            u = x;
+            fu = v;
+            ku = kx;
+        });
+        m.above[c] = st;
+    });
+    m.tqb = w.tqb;
+#pragma unroll
+    for (int c = 0; c < LV; ++c) m.nan[c] = m.nan[c] || w.bad;
+    return m;
+}
+
+// the time above the level, as row_dense_level and row_dense_exposure keep it: the start of the current stay and the sum of
+// the finished ones, left to right
+struct TimeAbove {
+    double up = 0.0, sum = 0.0;
+    __device__ __forceinline__ void open(double tqa) { up = tqa; }
+    __device__ __forceinline__ void cross(double tz, bool ab) {
+        if (ab) up = tz;
+        else sum = sum + (tz - up);
+    }
+    __device__ __forceinline__ double close(bool above, double tqb) const { return above ? sum + (tqb - up) : sum; }
 };
 
 template <int LV>
@@ -544,6 +595,69 @@ __device__ __forceinline__ void store_ints(int32_t* p, const int32_t (&v)[LV]) {
     }
 }
 
+template <typename T, typename E, int LV>
+__device__ __forceinline__ void store_lanes(T* base, int64_t at, const T (&v)[LV]) {
+    E w;
+    __builtin_memcpy(&w, v, sizeof(E));
+    reinterpret_cast<E*>(base)[at] = w;
+}
+
+template <typename T>
+struct RowDenseExtremumArgs : RowDenseWindowArgs<T> {
+    T* values;                        // [n_idx, L]
+    double* times;                    // [n_idx, L] true time
+};
+
+template <typename T, bool VEC, bool MAX>
+__global__ __launch_bounds__(kBlock) void row_dense_extremum_kernel(const RowDenseExtremumArgs<T> a) {
+    using E = typename std::conditional<VEC, typename VecOf<T>::type, T>::type;
+    constexpr int LV = VEC ? VecOf<T>::L : 1;
+    const int64_t stride = (int64_t)gridDim.x * kBlock;
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < a.ne; i += stride) {
+        const int64_t r = i / a.row_len;
+        double best[LV], when[LV];
+        bool nanv[LV];
+#pragma unroll
+        for (int c = 0; c < LV; ++c) {
+            best[c] = when[c] = 0.0;
+            nanv[c] = false;
+        }
+        const RowDenseWindow w = row_dense_walk<T, E, LV>(a, r, i - r * a.row_len, [&](int c, const WindowQuartic& s) {
+            double bst = best[c], whn = when[c];
+            bool have = !s.atA;                                       // (the window's first candidate is taken as it is)
+            s.candidates([&](double x) {
+                const double v = s(x);
+                if (v != v) nanv[c] = true;
+                if (!have || (MAX ? v > bst : v < bst)) {
+                    have = true;
+                    bst = v;
+                    whn = s.time_of(x);
+                }
+            });
+            best[c] = bst;
+            when[c] = whn;
+        });
+        T o[LV];
+#pragma unroll
+        for (int c = 0; c < LV; ++c) {
+            const bool nan = w.bad || nanv[c];
+            o[c] = nan ? (T)__builtin_nan("") : (T)best[c];
+            when[c] = nan ? __builtin_nan("") : a.sign * when[c];
+        }
+        store_lanes<T, E, LV>(a.values, i, o);
+        store_doubles<LV>(a.times + i * LV, when);
+    }
+}
+
+template <typename T>
+struct RowDenseLevelArgs : RowDenseWindowArgs<T> {
+    int32_t* count;                   // [n_idx, L]
+    double* first;                    // [n_idx, L] true time
+    double* last;                     // [n_idx, L] true time
+    double* total;                    // [n_idx, L] duration
+    const T* level;                   // [n_rows, L]
+};
+
 template <typename T, bool VEC>
 __global__ __launch_bounds__(kBlock) void row_dense_level_kernel(const RowDenseLevelArgs<T> a) {
     using E = typename std::conditional<VEC, typename VecOf<T>::type, T>::type;
@@ -551,94 +665,30 @@ __global__ __launch_bounds__(kBlock) void row_dense_level_kernel(const RowDenseL
     const int64_t stride = (int64_t)gridDim.x * kBlock;
     for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < a.ne; i += stride) {
         const int64_t r = i / a.row_len;
-        const int64_t el = i - r * a.row_len;
-        int64_t sA = a.seg[r], sB = a.seg2[r];
-        double tqa = a.tq[r], tqb = a.tq2[r];
-        const T xa = a.x[r], xb = a.x2[r];
-        if (tqb < tqa) {
-            const int64_t s = sA;
-            sA = sB;
-            sB = s;
-            const double t = tqa;
-            tqa = tqb;
-            tqb = t;
-        }
-        if (sA < 0) sA = 0;                                           // (nothing is read outside the record)
-        if (sB > a.n_seg - 1) sB = a.n_seg - 1;
-        const bool bad = xa != xa || xb != xb || sA > sB;             // (sA > sB: only from ends the search did not write)
-        T lev[LV];
-        load_lanes<T, E, LV>(a.level, (r % a.n_rows) * a.row_len + el, lev);
-        double t_up[LV], total[LV], tfirst[LV], tlast[LV];
+        TimeAbove dur[LV];
+        double tfirst[LV], tlast[LV], total[LV];
         int32_t count[LV];
-        bool above[LV], nanv[LV];
 #pragma unroll
         for (int c = 0; c < LV; ++c) {
-            t_up[c] = total[c] = tfirst[c] = tlast[c] = 0.0;
+            tfirst[c] = tlast[c] = 0.0;
             count[c] = 0;
-            above[c] = false;
-            nanv[c] = bad;
         }
-        for (int64_t s = bad ? sB + 1 : sA; s <= sB; ++s) {           // serial: segments in order
-            const int64_t at = s * a.row_len + el;
-            T qe[LV], qd[LV], qc[LV], qb[LV], qa[LV];
-            load_lanes<T, E, LV>(a.q, at, qe);
-            load_lanes<T, E, LV>(a.q + a.q_plane, at, qd);
-            load_lanes<T, E, LV>(a.q + 2 * a.q_plane, at, qc);
-            load_lanes<T, E, LV>(a.q + 3 * a.q_plane, at, qb);
-            load_lanes<T, E, LV>(a.q + 4 * a.q_plane, at, qa);
-            const double ta = a.seg_ta[s], tb = a.seg_tb[s];
-            const double h = tb - ta;
-            const bool atA = s == sA, atB = s == sB;
-            const double xlo = atA ? (tqa - ta) / h : 0.0;
-            const double xhi = atB ? (tqb - ta) / h : 1.0;
-#pragma unroll
-            for (int c = 0; c < LV; ++c) {
-                const double b = (double)qb[c], aa = (double)qa[c];
-                const QuarticLevel phi{(double)qe[c], (double)qd[c], (double)qc[c], b, aa, (double)lev[c]};
-                const double c2 = phi.c + phi.c, a4 = 4.0 * aa;
-                const QuarticSlope g{phi.d, c2, 3.0 * b, a4};
-                const QuarticCurvature g1{c2, 6.0 * b, 12.0 * aa};
-                bool st = above[c], entry = true;                     // entry: the segment's first candidate comes next
-                double up = t_up[c], sum = total[c], u = xlo, fu = 0.0;
-                auto visit = [&](double x) {
-                    const double v = phi(x);
-                    if (v != v) nanv[c] = true;
-                    const bool ab = v > 0.0;
-                    if (entry && atA) {                               // the window's first candidate sets the state
-                        st = ab;
-                        up = tqa;
-                    } else if (ab != st) {
-                        double z = x;                                 // (a later segment's first candidate: the breakpoint)
-                        if (!entry) {
-                            if (fu == 0.0) z = u;
-                            else if (v != 0.0) quartic_bisect(phi, u, x, z);
-                        }
-                        const double tz =
-                            (atA && z == xlo) ? tqa : (atB && z == xhi) ? tqb : z == 0.0 ? ta : z == 1.0 ? tb : ta + z * h;
-                        if (count[c] == 0) tfirst[c] = tz;
-                        tlast[c] = tz;
-                        ++count[c];
-                        if (ab) up = tz;
-                        else sum = sum + (tz - up);
-                        st = ab;
-                    }
-                    entry = false;
-                    u = x;
-                    fu = v;
-                };
-                quartic_candidates(g, g1, b, aa, a4, xlo, xhi, visit);
-                above[c] = st;
-                t_up[c] = up;
-                total[c] = sum;
-            }
-        }
+        const RowDenseLevelWalk<LV> m = row_dense_level_walk<T, E, LV, false>(
+            a, a.level, r, i - r * a.row_len, [&](int c, double tqa) { dur[c].open(tqa); },
+            [&](int c, double tz, bool ab) {
+                if (count[c] == 0) tfirst[c] = tz;
+                tlast[c] = tz;
+                ++count[c];
+                dur[c].cross(tz, ab);
+            },
+            NoPieces{});
 #pragma unroll
         for (int c = 0; c < LV; ++c) {
-            if (above[c]) total[c] = total[c] + (tqb - t_up[c]);
+            total[c] = dur[c].close(m.above[c], m.tqb);
             const bool none = count[c] == 0;
-            tfirst[c] = (nanv[c] || none) ? __builtin_nan("") : a.sign * tfirst[c];
-            tlast[c] = (nanv[c] || none) ? __builtin_nan("") : a.sign * tlast[c];
-            if (nanv[c]) {
+            tfirst[c] = (m.nan[c] || none) ? __builtin_nan("") : a.sign * tfirst[c];
+            tlast[c] = (m.nan[c] || none) ? __builtin_nan("") : a.sign * tlast[c];
+            if (m.nan[c]) {
                 total[c] = __builtin_nan("");
                 count[c] = -1;
             }
@@ -650,43 +700,12 @@ __global__ __launch_bounds__(kBlock) void row_dense_level_kernel(const RowDenseL
     }
 }
 
-// ---- area above and below a level over a time window (ABI 34): RowDenseOutput.exposure / .area_above / .area_below --------
-//   row_dense_exposure   the walk and state machine of row_dense_level, which also integrates y - level piece by piece: K is
-//                        J_s of row_dense_prefix with e - level in place of e, a piece between two neighbouring candidates
-//                        adds K(v) - K(u) to the area above or takes it from the area below by the state, and a crossing at z
-//                        splits its piece there.  Per element the lane keeps above / t_up / total / A_up / A_dn and, inside
-//                        a segment, K of the previous candidate.  The arithmetic is stated in include/tdeq_hip.h; the host
-//                        model is rowwise.py quartic_exposure.
-// A segment without a crossing costs what it costs row_dense_level plus at most 7 evaluations of K.  No LDS, no atomics, no
-// workspace.
-
 template <typename T>
-struct RowDenseExposureArgs {
+struct RowDenseExposureArgs : RowDenseWindowArgs<T> {
     T* area_above;                    // [n_idx, L]
     T* area_below;                    // [n_idx, L]
     double* total;                    // [n_idx, L] duration above
     const T* level;                   // [n_rows, L]
-    const T* q;                       // [5, n_seg, L]
-    const double* seg_ta;             // [n_seg]
-    const double* seg_tb;             // [n_seg]
-    const int32_t* seg;               // [n_idx] one end of each window (row_dense_search)
-    const T* x;                       // [n_idx] NaN marks an out-of-range end
-    const double* tq;                 // [n_idx] solver time
-    const int32_t* seg2;              // the other end
-    const T* x2;
-    const double* tq2;
-    int64_t n_rows;                   // query i belongs to row i % n_rows
-    int64_t n_seg;
-    int64_t row_len;                  // E units
-    int64_t ne;                       // n_idx * row_len
-    int64_t q_plane;                  // n_seg * L elements of T
-};
-
-// K of the header: quartic_integral_one with el in place of e (the coefficients are those the lane holds for phi)
-struct QuarticArea {
-    const QuarticLevel& p;
-    double el, h;
-    __device__ __forceinline__ double operator()(double x) const { return quartic_integral_one(el, p.d, p.c, p.b, p.a, x, h); }
 };
 
 template <typename T, bool VEC>
@@ -696,149 +715,38 @@ __global__ __launch_bounds__(kBlock) void row_dense_exposure_kernel(const RowDen
     const int64_t stride = (int64_t)gridDim.x * kBlock;
     for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < a.ne; i += stride) {
         const int64_t r = i / a.row_len;
-        const int64_t el = i - r * a.row_len;
-        int64_t sA = a.seg[r], sB = a.seg2[r];
-        double tqa = a.tq[r], tqb = a.tq2[r];
-        const T xa = a.x[r], xb = a.x2[r];
-        if (tqb < tqa) {
-            const int64_t s = sA;
-            sA = sB;
-            sB = s;
-            const double t = tqa;
-            tqa = tqb;
-            tqb = t;
-        }
-        if (sA < 0) sA = 0;                                           // (nothing is read outside the record)
-        if (sB > a.n_seg - 1) sB = a.n_seg - 1;
-        const bool bad = xa != xa || xb != xb || sA > sB;             // (sA > sB: only from ends the search did not write)
-        T lev[LV];
-        load_lanes<T, E, LV>(a.level, (r % a.n_rows) * a.row_len + el, lev);
-        double t_up[LV], total[LV], a_up[LV], a_dn[LV];
-        bool above[LV], nanv[LV];
+        TimeAbove dur[LV];
+        double a_up[LV], a_dn[LV], total[LV];
 #pragma unroll
-        for (int c = 0; c < LV; ++c) {
-            t_up[c] = total[c] = a_up[c] = a_dn[c] = 0.0;
-            above[c] = false;
-            nanv[c] = bad;
-        }
-        for (int64_t s = bad ? sB + 1 : sA; s <= sB; ++s) {           // serial: segments in order
-            const int64_t at = s * a.row_len + el;
-            T qe[LV], qd[LV], qc[LV], qb[LV], qa[LV];
-            load_lanes<T, E, LV>(a.q, at, qe);
-            load_lanes<T, E, LV>(a.q + a.q_plane, at, qd);
-            load_lanes<T, E, LV>(a.q + 2 * a.q_plane, at, qc);
-            load_lanes<T, E, LV>(a.q + 3 * a.q_plane, at, qb);
-            load_lanes<T, E, LV>(a.q + 4 * a.q_plane, at, qa);
-            const double ta = a.seg_ta[s], tb = a.seg_tb[s];
-            const double h = tb - ta;
-            const bool atA = s == sA, atB = s == sB;
-            const double xlo = atA ? (tqa - ta) / h : 0.0;
-            const double xhi = atB ? (tqb - ta) / h : 1.0;
-#pragma unroll
-            for (int c = 0; c < LV; ++c) {
-                const double b = (double)qb[c], aa = (double)qa[c];
-                const QuarticLevel phi{(double)qe[c], (double)qd[c], (double)qc[c], b, aa, (double)lev[c]};
-                const double c2 = phi.c + phi.c, a4 = 4.0 * aa;
-                const QuarticSlope g{phi.d, c2, 3.0 * b, a4};
-                const QuarticCurvature g1{c2, 6.0 * b, 12.0 * aa};
-                const QuarticArea K{phi, phi.e - phi.lev, h};
-                bool st = above[c], entry = true;                     // entry: the segment's first candidate comes next
-                double up = t_up[c], sum = total[c], aup = a_up[c], adn = a_dn[c], u = xlo, fu = 0.0, ku = 0.0;
-                auto add = [&](double q, bool over) {
-                    if (over) aup = aup + q;
-                    else adn = adn - q;
-                };
-                auto visit = [&](double x) {
-                    const double v = phi(x);
-                    if (v != v) nanv[c] = true;
-                    const bool ab = v > 0.0;
-                    const double kx = K(x);
-                    if (entry && atA) {                               // the window's first candidate sets the state
-                        st = ab;
-                        up = tqa;
-                    } else {
-                        double kz = ku;                               // (no crossing: one piece, K(x) - K(u))
-                        if (ab != st) {
-                            double z = x;                             // (a later segment's first candidate: the breakpoint)
-                            if (!entry) {
-                                if (fu == 0.0) z = u;
-                                else if (v != 0.0) quartic_bisect(phi, u, x, z);
-                                kz = K(z);
-                                add(kz - ku, st);
-                            }
-                            const double tz =
-                                (atA && z == xlo) ? tqa : (atB && z == xhi) ? tqb : z == 0.0 ? ta : z == 1.0 ? tb : ta + z * h;
-                            if (ab) up = tz;
-                            else sum = sum + (tz - up);
-                            st = ab;
-                        }
-                        if (!entry) add(kx - kz, st);
-                    }
-                    entry = false;
-                    u = x;
-                    fu = v;
-                    ku = kx;
-                };
-                quartic_candidates(g, g1, b, aa, a4, xlo, xhi, visit);
-                above[c] = st;
-                t_up[c] = up;
-                total[c] = sum;
-                a_up[c] = aup;
-                a_dn[c] = adn;
-            }
-        }
+        for (int c = 0; c < LV; ++c) a_up[c] = a_dn[c] = 0.0;
+        const RowDenseLevelWalk<LV> m = row_dense_level_walk<T, E, LV, true>(
+            a, a.level, r, i - r * a.row_len, [&](int c, double tqa) { dur[c].open(tqa); },
+            [&](int c, double tz, bool ab) { dur[c].cross(tz, ab); },
+            [&](int c, double q, bool over) {
+                if (over) a_up[c] = a_up[c] + q;
+                else a_dn[c] = a_dn[c] - q;
+            });
         T oa[LV], ob[LV];
 #pragma unroll
         for (int c = 0; c < LV; ++c) {
-            if (above[c]) total[c] = total[c] + (tqb - t_up[c]);
-            oa[c] = nanv[c] ? (T)__builtin_nan("") : (T)(a_up[c] < 0.0 ? 0.0 : a_up[c]);
-            ob[c] = nanv[c] ? (T)__builtin_nan("") : (T)(a_dn[c] < 0.0 ? 0.0 : a_dn[c]);
-            if (nanv[c]) total[c] = __builtin_nan("");
+            total[c] = m.nan[c] ? __builtin_nan("") : dur[c].close(m.above[c], m.tqb);
+            oa[c] = m.nan[c] ? (T)__builtin_nan("") : (T)(a_up[c] < 0.0 ? 0.0 : a_up[c]);
+            ob[c] = m.nan[c] ? (T)__builtin_nan("") : (T)(a_dn[c] < 0.0 ? 0.0 : a_dn[c]);
         }
-        E w;
-        __builtin_memcpy(&w, oa, sizeof(E));
-        reinterpret_cast<E*>(a.area_above)[i] = w;
-        __builtin_memcpy(&w, ob, sizeof(E));
-        reinterpret_cast<E*>(a.area_below)[i] = w;
+        store_lanes<T, E, LV>(a.area_above, i, oa);
+        store_lanes<T, E, LV>(a.area_below, i, ob);
         store_doubles<LV>(a.total + i * LV, total);
     }
 }
 
-// ---- the times of all crossings of a level over a time window (ABI 35): RowDenseOutput.crossing_times ---------------------
-//   row_dense_level_times   the walk, state machine and root location of row_dense_level; what is kept differs.  Per element
-//                           the lane keeps above and one int32 counter per direction, and a crossing located at tz goes
-//                           straight to global memory: slot n of its direction's list while n < K, as one 8-byte store; the
-//                           counter runs on.  Rising is defined in true time: the state becomes above and time_sign > 0, or
-//                           it becomes not above and time_sign < 0; the launcher hands the two directions over as `ups` and
-//                           `dns` accordingly.  After the walk the free slots are filled with NaN, so
-//                           every slot of the four outputs is written.  The list index is an offset in global memory, never
-//                           an index into a per-lane array.  The arithmetic is stated in include/tdeq_hip.h; the host model
-//                           is rowwise.py quartic_crossing_times.
-// No LDS, no atomics, no workspace.
-
 template <typename T>
-struct RowDenseLevelTimesArgs {
+struct RowDenseLevelTimesArgs : RowDenseWindowArgs<T> {
     int32_t* n_up;                    // [n_idx, L] crossings after which the state is above: n_rising if sign > 0, else
     int32_t* n_dn;                    // n_falling; and those after which it is not (the launcher maps the directions)
     double* ups;                      // [K, n_idx, L] true time: rising if sign > 0, else falling
     double* dns;                      // [K, n_idx, L]
     int32_t k;                        // K: slots per list
     const T* level;                   // [n_rows, L]
-    const T* q;                       // [5, n_seg, L]
-    const double* seg_ta;             // [n_seg]
-    const double* seg_tb;             // [n_seg]
-    double sign;
-    const int32_t* seg;               // [n_idx] one end of each window (row_dense_search)
-    const T* x;                       // [n_idx] NaN marks an out-of-range end
-    const double* tq;                 // [n_idx] solver time
-    const int32_t* seg2;              // the other end
-    const T* x2;
-    const double* tq2;
-    int64_t n_rows;                   // query i belongs to row i % n_rows
-    int64_t n_seg;
-    int64_t row_len;                  // E units
-    int64_t ne;                       // n_idx * row_len
-    int64_t q_plane;                  // n_seg * L elements of T
     int64_t t_plane;                  // n_idx * L doubles: one slot of a list
 };
 
@@ -850,92 +758,26 @@ __global__ __launch_bounds__(kBlock) void row_dense_level_times_kernel(const Row
     const int32_t K = a.k;
     for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < a.ne; i += stride) {
         const int64_t r = i / a.row_len;
-        const int64_t el = i - r * a.row_len;
-        int64_t sA = a.seg[r], sB = a.seg2[r];
-        double tqa = a.tq[r], tqb = a.tq2[r];
-        const T xa = a.x[r], xb = a.x2[r];
-        if (tqb < tqa) {
-            const int64_t s = sA;
-            sA = sB;
-            sB = s;
-            const double t = tqa;
-            tqa = tqb;
-            tqb = t;
-        }
-        if (sA < 0) sA = 0;                                           // (nothing is read outside the record)
-        if (sB > a.n_seg - 1) sB = a.n_seg - 1;
-        const bool bad = xa != xa || xb != xb || sA > sB;             // (sA > sB: only from ends the search did not write)
-        T lev[LV];
-        load_lanes<T, E, LV>(a.level, (r % a.n_rows) * a.row_len + el, lev);
         int32_t n_up[LV], n_dn[LV];                                   // crossings of the walk: to above, to not above
-        bool above[LV], nanv[LV];
 #pragma unroll
-        for (int c = 0; c < LV; ++c) {
-            n_up[c] = n_dn[c] = 0;
-            above[c] = false;
-            nanv[c] = bad;
-        }
+        for (int c = 0; c < LV; ++c) n_up[c] = n_dn[c] = 0;
         double* const ups = a.ups + i * LV;                           // slot 0 of this lane's elements
         double* const dns = a.dns + i * LV;
-        for (int64_t s = bad ? sB + 1 : sA; s <= sB; ++s) {           // serial: segments in order
-            const int64_t at = s * a.row_len + el;
-            T qe[LV], qd[LV], qc[LV], qb[LV], qa[LV];
-            load_lanes<T, E, LV>(a.q, at, qe);
-            load_lanes<T, E, LV>(a.q + a.q_plane, at, qd);
-            load_lanes<T, E, LV>(a.q + 2 * a.q_plane, at, qc);
-            load_lanes<T, E, LV>(a.q + 3 * a.q_plane, at, qb);
-            load_lanes<T, E, LV>(a.q + 4 * a.q_plane, at, qa);
-            const double ta = a.seg_ta[s], tb = a.seg_tb[s];
-            const double h = tb - ta;
-            const bool atA = s == sA, atB = s == sB;
-            const double xlo = atA ? (tqa - ta) / h : 0.0;
-            const double xhi = atB ? (tqb - ta) / h : 1.0;
-#pragma unroll
-            for (int c = 0; c < LV; ++c) {
-                const double b = (double)qb[c], aa = (double)qa[c];
-                const QuarticLevel phi{(double)qe[c], (double)qd[c], (double)qc[c], b, aa, (double)lev[c]};
-                const double c2 = phi.c + phi.c, a4 = 4.0 * aa;
-                const QuarticSlope g{phi.d, c2, 3.0 * b, a4};
-                const QuarticCurvature g1{c2, 6.0 * b, 12.0 * aa};
-                bool st = above[c], entry = true;                     // entry: the segment's first candidate comes next
-                int32_t nu = n_up[c], nd = n_dn[c];
-                double u = xlo, fu = 0.0;
-                auto visit = [&](double x) {
-                    const double v = phi(x);
-                    if (v != v) nanv[c] = true;
-                    const bool ab = v > 0.0;
-                    if (entry && atA) {                               // the window's first candidate sets the state
-                        st = ab;
-                    } else if (ab != st) {
-                        double z = x;                                 // (a later segment's first candidate: the breakpoint)
-                        if (!entry) {
-                            if (fu == 0.0) z = u;
-                            else if (v != 0.0) quartic_bisect(phi, u, x, z);
-                        }
-                        const double tz =
-                            (atA && z == xlo) ? tqa : (atB && z == xhi) ? tqb : z == 0.0 ? ta : z == 1.0 ? tb : ta + z * h;
-                        const int32_t n = ab ? nu : nd;
-                        if (n < K) (ab ? ups : dns)[(int64_t)n * a.t_plane + c] = a.sign * tz;
-                        nu += ab ? 1 : 0;                             // (both counters by value: no pointer to either)
-                        nd += ab ? 0 : 1;
-                        st = ab;
-                    }
-                    entry = false;
-                    u = x;
-                    fu = v;
-                };
-                quartic_candidates(g, g1, b, aa, a4, xlo, xhi, visit);
-                above[c] = st;
-                n_up[c] = nu;
-                n_dn[c] = nd;
-            }
-        }
+        const RowDenseLevelWalk<LV> m = row_dense_level_walk<T, E, LV, false>(
+            a, a.level, r, i - r * a.row_len, [](int, double) {},
+            [&](int c, double tz, bool ab) {
+                const int32_t n = ab ? n_up[c] : n_dn[c];
+                if (n < K) (ab ? ups : dns)[(int64_t)n * a.t_plane + c] = a.sign * tz;
+                n_up[c] += ab ? 1 : 0;                                // (both counters by value: no pointer to either)
+                n_dn[c] += ab ? 0 : 1;
+            },
+            NoPieces{});
         const double nan = __builtin_nan("");
 #pragma unroll
         for (int c = 0; c < LV; ++c) {
-            for (int32_t n = nanv[c] ? 0 : n_up[c]; n < K; ++n) ups[(int64_t)n * a.t_plane + c] = nan;
-            for (int32_t n = nanv[c] ? 0 : n_dn[c]; n < K; ++n) dns[(int64_t)n * a.t_plane + c] = nan;
-            if (nanv[c]) n_up[c] = n_dn[c] = -1;
+            for (int32_t n = m.nan[c] ? 0 : n_up[c]; n < K; ++n) ups[(int64_t)n * a.t_plane + c] = nan;
+            for (int32_t n = m.nan[c] ? 0 : n_dn[c]; n < K; ++n) dns[(int64_t)n * a.t_plane + c] = nan;
+            if (m.nan[c]) n_up[c] = n_dn[c] = -1;
         }
         store_ints<LV>(a.n_up + i * LV, n_up);
         store_ints<LV>(a.n_dn + i * LV, n_dn);

@@ -903,7 +903,7 @@ class HostRowKernels:
             total = sign * (prefix.numpy()[s] + HostRowKernels._quartic_integral(*planes, x64, h[:, None]))
         return torch.from_numpy(total)
 
-    # -- extrema of a dense record over a window (the arithmetic of tdeq_row_dense_extremum, include/tdeq_hip.h) ----------
+    # -- the walk over a window of a dense record and the level machine on it, once for the four queries below --------------
     @staticmethod
     def _bisect(phi, lo, hi, on):
         """bisect(phi, lo, hi) of the header on fp64 arrays, where `on` -> (a root was found, the root): every round moves all
@@ -927,12 +927,52 @@ class HostRowKernels:
             live &= ~hit
         return found, np.where(np.abs(flo) <= np.abs(fhi), lo, hi)
 
+    class _WindowStep:
+        """Step k of the walk of every window that has one (WindowQuartic of the kernels): the windows `idx` on their k-th
+        segment.  Coefficients, `xlo` and `xhi` are fp64 [len(idx), L]; the segment `t_a`, `t_b`, `h`, the window's ends
+        `t_lo`, `t_hi` and `atA`, `atB` (this is the window's first / last segment) are [len(idx), 1]."""
+
+        def __init__(self, idx, planes, t_a, t_b, atA, atB, t_lo, t_hi):
+            self.idx, self.t_a, self.t_b, self.atA, self.atB, self.t_lo, self.t_hi = idx, t_a, t_b, atA, atB, t_lo, t_hi
+            self.e, self.d, self.c, self.b, self.a = e, d, c, b, a = planes
+            self.h = h = t_b - t_a
+            self.xlo = np.broadcast_to(np.where(atA, (t_lo - t_a) / h, 0.0), e.shape)
+            self.xhi = np.broadcast_to(np.where(atB, (t_hi - t_a) / h, 1.0), e.shape)
+            c2, self.a4 = c + c, 4.0 * a
+            b3, b6, a12, a4 = 3.0 * b, 6.0 * b, 12.0 * a, self.a4
+            self.p = lambda v: e + v * (d + v * (c + v * (b + v * a)))
+            self.g = lambda v: d + v * (c2 + v * (b3 + v * a4))
+            self.g1 = lambda v: c2 + v * (b6 + v * a12)
+
+        def time_of(self, z):
+            """The time of the candidates `z`: a window's end and a breakpoint are the stored words."""
+            return np.where(self.atA & (z == self.xlo), self.t_lo, np.where(self.atB & (z == self.xhi), self.t_hi, np.where(
+                z == 0.0, self.t_a, np.where(z == 1.0, self.t_b, self.t_a + z * self.h))))
+
+        def run(self, visit):
+            """The isolation: `visit(v, on)` for the candidates in increasing x, `on` the elements that have this one."""
+            bisect, xlo, xhi, g, g1 = HostRowKernels._bisect, self.xlo, self.xhi, self.g, self.g1
+            every = np.ones(xlo.shape, dtype=bool)
+            x1 = (-self.b) / self.a4
+            xm = np.where((self.a != 0.0) & (xlo < x1) & (x1 < xhi), x1, xlo)
+            f0, root = bisect(g1, xlo, xm, xm > xlo)
+            r0 = np.where(f0, root, xlo)
+            f1, root = bisect(g1, xm, xhi, every)
+            r1 = np.where(f1, root, r0)
+            visit(xlo, every)
+            for lo, hi in ((xlo, r0), (r0, r1)):
+                fz, z = bisect(g, lo, hi, hi > lo)
+                visit(z, fz)
+                visit(hi, hi > lo)
+            fz, z = bisect(g, r1, xhi, every)
+            visit(z, fz)
+            visit(xhi, every)
+
     @staticmethod
-    def quartic_extrema(q, ta, tb, sign: float, src, x, tq, src2, x2, tq2, maximum: bool):
-        """The maximum (or minimum) of the record `q` [5, n_seg, L] on the windows between the queries (src, x, tq) and (src2,
-        x2, tq2) of the search, per element, and its time -> (values [n, L] in the state's type, times fp64 [n, L] in true
-        time).  Step k of every window's walk at once; the bisection rounds run under masks."""
-        H = HostRowKernels
+    def _window_walk(q, ta, tb, src, x, tq, src2, x2, tq2):
+        """The walk of the windows between the queries (src, x, tq) and (src2, x2, tq2) of the search over the record `q`
+        [5, n_seg, L] (row_dense_walk of the kernels) -> (nan bool [n, L]: the windows with an out-of-range end, which are not
+        walked; the later end of every window, fp64 [n, 1]; the `_WindowStep`s: step k of every window's walk at once)."""
         planes, start, end = q.numpy(), ta.numpy(), tb.numpy()
         sa, sb = src.numpy().astype(np.int64), src2.numpy().astype(np.int64)
         qa, qb = tq.numpy().reshape(-1), tq2.numpy().reshape(-1)
@@ -940,141 +980,120 @@ class HostRowKernels:
         sa, sb = np.where(swap, sb, sa), np.where(swap, sa, sb)
         qa, qb = np.where(swap, qb, qa), np.where(swap, qa, qb)
         bad = np.isnan(x.numpy()) | np.isnan(x2.numpy()) | (sa > sb)
-        n, L = sa.size, planes.shape[2]
-        best, when = np.zeros((n, L)), np.zeros((n, L))
-        have, nan = np.zeros((n, L), dtype=bool), np.repeat(bad[:, None], L, axis=1)
         count = np.where(bad, 0, sb - sa + 1)
+
+        def steps():
+            with np.errstate(all="ignore"):
+                for k in range(int(count.max()) if sa.size else 0):
+                    idx = np.flatnonzero(count > k)
+                    s = sa[idx] + k
+                    yield HostRowKernels._WindowStep(
+                        idx, [planes[p, s].astype(np.float64) for p in range(5)], start[s][:, None], end[s][:, None],
+                        np.full((idx.size, 1), k == 0), (s == sb[idx])[:, None], qa[idx][:, None], qb[idx][:, None])
+        return np.repeat(bad[:, None], planes.shape[2], axis=1), qb[:, None], steps()
+
+    @staticmethod
+    def _level_walk(q, level, window, cross=None, piece=None, timed=False):
+        """The level machine on the walk of `window` (the arguments of `_window_walk` after `q`), for `level` [n_rows, L]
+        (query i belongs to row i % n_rows), run under masks (row_dense_level_walk of the kernels) -> (nan bool [n, L]; with
+        `timed` the time above the level, fp64 [n, L], else None).  `cross(s, on, tz, ab)`: the elements `on` of step `s` cross at the
+        solver times `tz` and are above after it where `ab`.  `piece(s, on, area, over)`: a piece between two candidates,
+        split at a crossing, adds `area` = K(v) - K(u) for the elements `on`, above the level where `over`; K is evaluated
+        with a `piece` only."""
+        H = HostRowKernels
+        nan, t_hi, steps = H._window_walk(q, *window)
+        n, L = nan.shape
+        levels = level.numpy().astype(np.float64)[np.arange(n) % level.shape[0]]
+        state, t_up, total = np.zeros((n, L), dtype=bool), np.zeros((n, L)), np.zeros((n, L))
         with np.errstate(all="ignore"):
-            for k in range(int(count.max()) if n else 0):
-                idx = np.flatnonzero(count > k)
-                s = sa[idx] + k
-                e, d, c, b, a = (planes[p, s].astype(np.float64) for p in range(5))
-                t_a, t_b = start[s][:, None], end[s][:, None]
-                h = t_b - t_a
-                atA, atB = np.full((idx.size, 1), k == 0), (s == sb[idx])[:, None]
-                t_lo, t_hi = qa[idx][:, None], qb[idx][:, None]
-                xlo = np.broadcast_to(np.where(atA, (t_lo - t_a) / h, 0.0), e.shape)
-                xhi = np.broadcast_to(np.where(atB, (t_hi - t_a) / h, 1.0), e.shape)
-                c2, a4 = c + c, 4.0 * a
-                b3, b6, a12 = 3.0 * b, 6.0 * b, 12.0 * a
-                g = lambda v: d + v * (c2 + v * (b3 + v * a4))           # noqa: E731
-                g1 = lambda v: c2 + v * (b6 + v * a12)                   # noqa: E731
+            for s in steps:
+                idx = s.idx
+                lev = levels[idx]
+                el = s.e - lev
+                phi = lambda v: s.p(v) - lev                             # noqa: E731
+                K = lambda v: H._quartic_integral(el, s.d, s.c, s.b, s.a, v, s.h)    # noqa: E731
+                st, up, tot, nn = state[idx], t_up[idx], total[idx], nan[idx]
+                entry = np.ones(st.shape, dtype=bool)                    # the segment's first candidate comes next
+                u, fu, ku = s.xlo, np.zeros(st.shape), np.zeros(st.shape)
+
+                def visit(v, on):
+                    nonlocal st, up, tot, nn, entry, u, fu, ku
+                    fv = phi(v)
+                    nn = nn | (on & np.isnan(fv))
+                    ab = fv > 0
+                    opening = on & entry & s.atA                         # the window's first candidate sets the state
+                    crossing = on & ~opening & (ab != st)
+                    inside = crossing & ~entry                           # (else: a later segment's first candidate)
+                    found, root = H._bisect(phi, u, v, inside & (fu != 0) & (fv != 0))
+                    z = np.where(inside & (fu == 0), u, np.where(found, root, v))
+                    tz = s.time_of(z)
+                    if piece is not None:                                # u -> v, or u -> z under the old state and z -> v
+                        kv = K(v)
+                        kz = np.where(inside, K(z), ku)
+                        piece(s, inside, kz - ku, st)
+                        piece(s, on & ~entry, kv - kz, ab)
+                        ku = np.where(on, kv, ku)
+                    if cross is not None:
+                        cross(s, crossing, tz, ab)
+                    if timed:
+                        tot = np.where(crossing & ~ab, tot + (tz - up), tot)
+                        up = np.where(opening, s.t_lo, np.where(crossing & ab, tz, up))
+                    st = np.where(opening | crossing, ab, st)
+                    entry, u, fu = entry & ~on, np.where(on, v, u), np.where(on, fv, fu)
+
+                s.run(visit)
+                state[idx], t_up[idx], total[idx], nan[idx] = st, up, tot, nn
+            return nan, np.where(state, total + (t_hi - t_up), total) if timed else None
+
+    # -- queries over a window of a dense record (the arithmetic of tdeq_row_dense_extremum / _level / _level_times /
+    #    _exposure, include/tdeq_hip.h) ---------------------------------------------------------------------------------------
+    @staticmethod
+    def quartic_extrema(q, ta, tb, sign: float, src, x, tq, src2, x2, tq2, maximum: bool):
+        """The maximum (or minimum) of the record `q` [5, n_seg, L] on the windows between the queries (src, x, tq) and (src2,
+        x2, tq2) of the search, per element, and its time -> (values [n, L] in the state's type, times fp64 [n, L] in true
+        time).  Step k of every window's walk at once; the bisection rounds run under masks."""
+        nan, _, steps = HostRowKernels._window_walk(q, ta, tb, src, x, tq, src2, x2, tq2)
+        best, when, have = np.zeros(nan.shape), np.zeros(nan.shape), np.zeros(nan.shape, dtype=bool)
+        with np.errstate(all="ignore"):
+            for s in steps:
+                idx = s.idx
                 bst, whn, hv, nn = best[idx], when[idx], have[idx], nan[idx]
 
                 def consider(v, on):
                     nonlocal bst, whn, hv, nn
-                    p = e + v * (d + v * (c + v * (b + v * a)))
+                    p = s.p(v)
                     nn = nn | (on & np.isnan(p))
                     take = on & (~hv | ((p > bst) if maximum else (p < bst)))
-                    t = np.where(atA & (v == xlo), t_lo, np.where(atB & (v == xhi), t_hi, np.where(
-                        v == 0.0, t_a, np.where(v == 1.0, t_b, t_a + v * h))))
-                    bst, whn, hv = np.where(take, p, bst), np.where(take, t, whn), hv | on
+                    bst, whn, hv = np.where(take, p, bst), np.where(take, s.time_of(v), whn), hv | on
 
-                every = np.ones(e.shape, dtype=bool)
-                x1 = (-b) / a4
-                xm = np.where((a != 0.0) & (xlo < x1) & (x1 < xhi), x1, xlo)
-                f0, root = H._bisect(g1, xlo, xm, xm > xlo)
-                r0 = np.where(f0, root, xlo)
-                f1, root = H._bisect(g1, xm, xhi, every)
-                r1 = np.where(f1, root, r0)
-                consider(xlo, every)
-                for lo, hi in ((xlo, r0), (r0, r1)):
-                    fz, z = H._bisect(g, lo, hi, hi > lo)
-                    consider(z, fz)
-                    consider(hi, hi > lo)
-                fz, z = H._bisect(g, r1, xhi, every)
-                consider(z, fz)
-                consider(xhi, every)
+                s.run(consider)
                 best[idx], when[idx], have[idx], nan[idx] = bst, whn, hv, nn
-            values = np.where(nan, np.nan, best).astype(planes.dtype)
+            values = np.where(nan, np.nan, best).astype(q.numpy().dtype)
             times = np.where(nan, np.nan, sign * when)
         return torch.from_numpy(values), torch.from_numpy(times)
 
-    # -- level crossings of a dense record over a window (the arithmetic of tdeq_row_dense_level, include/tdeq_hip.h) --------
     @staticmethod
     def quartic_levels(q, level, ta, tb, sign: float, src, x, tq, src2, x2, tq2):
         """The crossings of `level` [n_rows, L] (query i belongs to row i % n_rows) by the record `q` [5, n_seg, L] on the
         windows between the queries (src, x, tq) and (src2, x2, tq2) of the search, per element -> (count int32, first, last
         fp64 in true time, time_above fp64), all [n, L].  Step k of every window's walk at once; the candidates are those of
         `quartic_extrema`, the state machine and the bisection rounds run under masks."""
-        H = HostRowKernels
-        planes, start, end = q.numpy(), ta.numpy(), tb.numpy()
-        sa, sb = src.numpy().astype(np.int64), src2.numpy().astype(np.int64)
-        qa, qb = tq.numpy().reshape(-1), tq2.numpy().reshape(-1)
-        swap = qb < qa
-        sa, sb = np.where(swap, sb, sa), np.where(swap, sa, sb)
-        qa, qb = np.where(swap, qb, qa), np.where(swap, qa, qb)
-        bad = np.isnan(x.numpy()) | np.isnan(x2.numpy()) | (sa > sb)
-        n, L = sa.size, planes.shape[2]
-        levels = level.numpy().astype(np.float64)[np.arange(n) % level.shape[0]]
-        state, nan = np.zeros((n, L), dtype=bool), np.repeat(bad[:, None], L, axis=1)
-        t_up, total, first, last = (np.zeros((n, L)) for _ in range(4))
-        count = np.zeros((n, L), dtype=np.int32)
-        steps = np.where(bad, 0, sb - sa + 1)
+        shape = (src.numel(), q.shape[2])
+        first, last, count = np.zeros(shape), np.zeros(shape), np.zeros(shape, dtype=np.int32)
+
+        def cross(s, on, tz, ab):
+            i = s.idx
+            first[i], last[i] = np.where(on & (count[i] == 0), tz, first[i]), np.where(on, tz, last[i])
+            count[i] = count[i] + on.astype(np.int32)
+
+        nan, total = HostRowKernels._level_walk(q, level, (ta, tb, src, x, tq, src2, x2, tq2), cross, timed=True)
         with np.errstate(all="ignore"):
-            for k in range(int(steps.max()) if n else 0):
-                idx = np.flatnonzero(steps > k)
-                s = sa[idx] + k
-                e, d, c, b, a = (planes[p, s].astype(np.float64) for p in range(5))
-                lev = levels[idx]
-                t_a, t_b = start[s][:, None], end[s][:, None]
-                h = t_b - t_a
-                atA, atB = np.full((idx.size, 1), k == 0), (s == sb[idx])[:, None]
-                t_lo, t_hi = qa[idx][:, None], qb[idx][:, None]
-                xlo = np.broadcast_to(np.where(atA, (t_lo - t_a) / h, 0.0), e.shape)
-                xhi = np.broadcast_to(np.where(atB, (t_hi - t_a) / h, 1.0), e.shape)
-                c2, a4 = c + c, 4.0 * a
-                b3, b6, a12 = 3.0 * b, 6.0 * b, 12.0 * a
-                g = lambda v: d + v * (c2 + v * (b3 + v * a4))           # noqa: E731
-                g1 = lambda v: c2 + v * (b6 + v * a12)                   # noqa: E731
-                phi = lambda v: (e + v * (d + v * (c + v * (b + v * a)))) - lev      # noqa: E731
-                st, up, tot, cnt, tf, tl, nn = state[idx], t_up[idx], total[idx], count[idx], first[idx], last[idx], nan[idx]
-                entry = np.ones(e.shape, dtype=bool)                     # the segment's first candidate comes next
-                u, fu = xlo, np.zeros(e.shape)
-
-                def visit(v, on):
-                    nonlocal st, up, tot, cnt, tf, tl, nn, entry, u, fu
-                    fv = phi(v)
-                    nn = nn | (on & np.isnan(fv))
-                    ab = fv > 0
-                    opening = on & entry & atA                           # the window's first candidate sets the state
-                    cross = on & ~opening & (ab != st)
-                    inside = cross & ~entry                              # (else: a later segment's first candidate)
-                    found, root = H._bisect(phi, u, v, inside & (fu != 0) & (fv != 0))
-                    z = np.where(inside & (fu == 0), u, np.where(found, root, v))
-                    tz = np.where(atA & (z == xlo), t_lo, np.where(atB & (z == xhi), t_hi, np.where(
-                        z == 0.0, t_a, np.where(z == 1.0, t_b, t_a + z * h))))
-                    tf, tl = np.where(cross & (cnt == 0), tz, tf), np.where(cross, tz, tl)
-                    cnt = cnt + cross.astype(np.int32)
-                    tot = np.where(cross & ~ab, tot + (tz - up), tot)
-                    up = np.where(opening, t_lo, np.where(cross & ab, tz, up))
-                    st = np.where(opening | cross, ab, st)
-                    entry, u, fu = entry & ~on, np.where(on, v, u), np.where(on, fv, fu)
-
-                every = np.ones(e.shape, dtype=bool)
-                x1 = (-b) / a4
-                xm = np.where((a != 0.0) & (xlo < x1) & (x1 < xhi), x1, xlo)
-                f0, root = H._bisect(g1, xlo, xm, xm > xlo)
-                r0 = np.where(f0, root, xlo)
-                f1, root = H._bisect(g1, xm, xhi, every)
-                r1 = np.where(f1, root, r0)
-                visit(xlo, every)
-                for lo, hi in ((xlo, r0), (r0, r1)):
-                    fz, z = H._bisect(g, lo, hi, hi > lo)
-                    visit(z, fz)
-                    visit(hi, hi > lo)
-                fz, z = H._bisect(g, r1, xhi, every)
-                visit(z, fz)
-                visit(xhi, every)
-                state[idx], t_up[idx], total[idx], count[idx], first[idx], last[idx], nan[idx] = st, up, tot, cnt, tf, tl, nn
-            total = np.where(state, total + (qb[:, None] - t_up), total)
             none = nan | (count == 0)
             count = np.where(nan, np.int32(-1), count).astype(np.int32)
             first, last = np.where(none, np.nan, sign * first), np.where(none, np.nan, sign * last)
             total = np.where(nan, np.nan, total)
         return tuple(torch.from_numpy(np.ascontiguousarray(v)) for v in (count, first, last, total))
 
-    # -- the times of all crossings of a level over a window (the arithmetic of tdeq_row_dense_level_times, include/tdeq_hip.h)
     @staticmethod
     def quartic_crossing_times(q, level, ta, tb, sign: float, max_count: int, src, x, tq, src2, x2, tq2):
         """The true times of the first `max_count` rising and falling crossings of `level` [n_rows, L] (query i belongs to row
@@ -1083,84 +1102,25 @@ class HostRowKernels:
         falling fp64 [max_count, n, L]).  `quartic_levels` with the lists filled under masks: a crossing of the walk goes to
         slot n of its direction's list while n < max_count, and the counter runs on; rising is meant in true time, so the two
         directions of the walk swap for `sign` < 0."""
-        H = HostRowKernels
-        planes, start, end = q.numpy(), ta.numpy(), tb.numpy()
-        sa, sb = src.numpy().astype(np.int64), src2.numpy().astype(np.int64)
-        qa, qb = tq.numpy().reshape(-1), tq2.numpy().reshape(-1)
-        swap = qb < qa
-        sa, sb = np.where(swap, sb, sa), np.where(swap, sa, sb)
-        qa, qb = np.where(swap, qb, qa), np.where(swap, qa, qb)
-        bad = np.isnan(x.numpy()) | np.isnan(x2.numpy()) | (sa > sb)
-        n, L, K = sa.size, planes.shape[2], int(max_count)
-        levels = level.numpy().astype(np.float64)[np.arange(n) % level.shape[0]]
-        state, nan = np.zeros((n, L), dtype=bool), np.repeat(bad[:, None], L, axis=1)
+        n, L, K = src.numel(), q.shape[2], int(max_count)
         n_up, n_dn = (np.zeros((n, L), dtype=np.int32) for _ in range(2))   # crossings of the walk: to above, to not above
         ups, dns = (np.full((K, n, L), np.nan) for _ in range(2))
-        steps = np.where(bad, 0, sb - sa + 1)
-        with np.errstate(all="ignore"):
-            for k in range(int(steps.max()) if n else 0):
-                idx = np.flatnonzero(steps > k)
-                s = sa[idx] + k
-                e, d, c, b, a = (planes[p, s].astype(np.float64) for p in range(5))
-                lev = levels[idx]
-                t_a, t_b = start[s][:, None], end[s][:, None]
-                h = t_b - t_a
-                atA, atB = np.full((idx.size, 1), k == 0), (s == sb[idx])[:, None]
-                t_lo, t_hi = qa[idx][:, None], qb[idx][:, None]
-                xlo = np.broadcast_to(np.where(atA, (t_lo - t_a) / h, 0.0), e.shape)
-                xhi = np.broadcast_to(np.where(atB, (t_hi - t_a) / h, 1.0), e.shape)
-                c2, a4 = c + c, 4.0 * a
-                b3, b6, a12 = 3.0 * b, 6.0 * b, 12.0 * a
-                g = lambda v: d + v * (c2 + v * (b3 + v * a4))           # noqa: E731
-                g1 = lambda v: c2 + v * (b6 + v * a12)                   # noqa: E731
-                phi = lambda v: (e + v * (d + v * (c + v * (b + v * a)))) - lev      # noqa: E731
-                st, nu, nd, nn = state[idx], n_up[idx], n_dn[idx], nan[idx]
-                entry = np.ones(e.shape, dtype=bool)                     # the segment's first candidate comes next
-                u, fu = xlo, np.zeros(e.shape)
-                window = np.broadcast_to(idx[:, None], e.shape)
-                column = np.broadcast_to(np.arange(L)[None, :], e.shape)
 
-                def visit(v, on):
-                    nonlocal st, nu, nd, nn, entry, u, fu
-                    fv = phi(v)
-                    nn = nn | (on & np.isnan(fv))
-                    ab = fv > 0
-                    opening = on & entry & atA                           # the window's first candidate sets the state
-                    cross = on & ~opening & (ab != st)
-                    inside = cross & ~entry                              # (else: a later segment's first candidate)
-                    found, root = H._bisect(phi, u, v, inside & (fu != 0) & (fv != 0))
-                    z = np.where(inside & (fu == 0), u, np.where(found, root, v))
-                    tz = np.where(atA & (z == xlo), t_lo, np.where(atB & (z == xhi), t_hi, np.where(
-                        z == 0.0, t_a, np.where(z == 1.0, t_b, t_a + z * h))))
-                    for lst, cnt, to in ((ups, nu, cross & ab), (dns, nd, cross & ~ab)):
-                        keep = to & (cnt < K)
-                        lst[cnt[keep], window[keep], column[keep]] = sign * tz[keep]
-                    nu, nd = nu + (cross & ab).astype(np.int32), nd + (cross & ~ab).astype(np.int32)
-                    st = np.where(opening | cross, ab, st)
-                    entry, u, fu = entry & ~on, np.where(on, v, u), np.where(on, fv, fu)
+        def cross(s, on, tz, ab):
+            window = np.broadcast_to(s.idx[:, None], on.shape)
+            column = np.broadcast_to(np.arange(L)[None, :], on.shape)
+            for lst, total, to in ((ups, n_up, on & ab), (dns, n_dn, on & ~ab)):
+                cnt = total[s.idx]
+                keep = to & (cnt < K)
+                lst[cnt[keep], window[keep], column[keep]] = sign * tz[keep]
+                total[s.idx] = cnt + to.astype(np.int32)
 
-                every = np.ones(e.shape, dtype=bool)
-                x1 = (-b) / a4
-                xm = np.where((a != 0.0) & (xlo < x1) & (x1 < xhi), x1, xlo)
-                f0, root = H._bisect(g1, xlo, xm, xm > xlo)
-                r0 = np.where(f0, root, xlo)
-                f1, root = H._bisect(g1, xm, xhi, every)
-                r1 = np.where(f1, root, r0)
-                visit(xlo, every)
-                for lo, hi in ((xlo, r0), (r0, r1)):
-                    fz, z = H._bisect(g, lo, hi, hi > lo)
-                    visit(z, fz)
-                    visit(hi, hi > lo)
-                fz, z = H._bisect(g, r1, xhi, every)
-                visit(z, fz)
-                visit(xhi, every)
-                state[idx], n_up[idx], n_dn[idx], nan[idx] = st, nu, nd, nn
-            n_up, n_dn = np.where(nan, np.int32(-1), n_up).astype(np.int32), np.where(nan, np.int32(-1), n_dn).astype(np.int32)
-            ups, dns = np.where(nan[None], np.nan, ups), np.where(nan[None], np.nan, dns)
+        nan, _ = HostRowKernels._level_walk(q, level, (ta, tb, src, x, tq, src2, x2, tq2), cross)
+        n_up, n_dn = np.where(nan, np.int32(-1), n_up).astype(np.int32), np.where(nan, np.int32(-1), n_dn).astype(np.int32)
+        ups, dns = np.where(nan[None], np.nan, ups), np.where(nan[None], np.nan, dns)
         outs = (n_up, n_dn, ups, dns) if sign > 0 else (n_dn, n_up, dns, ups)
         return tuple(torch.from_numpy(np.ascontiguousarray(v)) for v in outs)
 
-    # -- area above and below a level over a window (the arithmetic of tdeq_row_dense_exposure, include/tdeq_hip.h) ----------
     @staticmethod
     def quartic_exposure(q, level, ta, tb, sign: float, src, x, tq, src2, x2, tq2):
         """The area between the record `q` [5, n_seg, L] and `level` [n_rows, L] (query i belongs to row i % n_rows) above and
@@ -1168,84 +1128,16 @@ class HostRowKernels:
         (area_above, area_below in the state's type, time_above fp64), all [n, L].  The walk and the state machine of
         `quartic_levels`; every piece between two candidates adds its K(v) - K(u) under a mask, split at a crossing.  `sign`
         changes nothing (durations)."""
-        H = HostRowKernels
-        planes, start, end = q.numpy(), ta.numpy(), tb.numpy()
-        sa, sb = src.numpy().astype(np.int64), src2.numpy().astype(np.int64)
-        qa, qb = tq.numpy().reshape(-1), tq2.numpy().reshape(-1)
-        swap = qb < qa
-        sa, sb = np.where(swap, sb, sa), np.where(swap, sa, sb)
-        qa, qb = np.where(swap, qb, qa), np.where(swap, qa, qb)
-        bad = np.isnan(x.numpy()) | np.isnan(x2.numpy()) | (sa > sb)
-        n, L = sa.size, planes.shape[2]
-        levels = level.numpy().astype(np.float64)[np.arange(n) % level.shape[0]]
-        state, nan = np.zeros((n, L), dtype=bool), np.repeat(bad[:, None], L, axis=1)
-        t_up, total, a_up, a_dn = (np.zeros((n, L)) for _ in range(4))
-        steps = np.where(bad, 0, sb - sa + 1)
+        a_up, a_dn = (np.zeros((src.numel(), q.shape[2])) for _ in range(2))
+
+        def piece(s, on, area, over):
+            i = s.idx
+            a_up[i], a_dn[i] = np.where(on & over, a_up[i] + area, a_up[i]), np.where(on & ~over, a_dn[i] - area, a_dn[i])
+
+        nan, total = HostRowKernels._level_walk(q, level, (ta, tb, src, x, tq, src2, x2, tq2), piece=piece, timed=True)
         with np.errstate(all="ignore"):
-            for k in range(int(steps.max()) if n else 0):
-                idx = np.flatnonzero(steps > k)
-                s = sa[idx] + k
-                e, d, c, b, a = (planes[p, s].astype(np.float64) for p in range(5))
-                lev = levels[idx]
-                t_a, t_b = start[s][:, None], end[s][:, None]
-                h = t_b - t_a
-                atA, atB = np.full((idx.size, 1), k == 0), (s == sb[idx])[:, None]
-                t_lo, t_hi = qa[idx][:, None], qb[idx][:, None]
-                xlo = np.broadcast_to(np.where(atA, (t_lo - t_a) / h, 0.0), e.shape)
-                xhi = np.broadcast_to(np.where(atB, (t_hi - t_a) / h, 1.0), e.shape)
-                c2, a4 = c + c, 4.0 * a
-                b3, b6, a12 = 3.0 * b, 6.0 * b, 12.0 * a
-                g = lambda v: d + v * (c2 + v * (b3 + v * a4))           # noqa: E731
-                g1 = lambda v: c2 + v * (b6 + v * a12)                   # noqa: E731
-                phi = lambda v: (e + v * (d + v * (c + v * (b + v * a)))) - lev      # noqa: E731
-                el = e - lev
-                K = lambda v: H._quartic_integral(el, d, c, b, a, v, h)  # noqa: E731
-                st, up, tot, aup, adn, nn = state[idx], t_up[idx], total[idx], a_up[idx], a_dn[idx], nan[idx]
-                entry = np.ones(e.shape, dtype=bool)                     # the segment's first candidate comes next
-                u, fu, ku = xlo, np.zeros(e.shape), np.zeros(e.shape)
-
-                def visit(v, on):
-                    nonlocal st, up, tot, aup, adn, nn, entry, u, fu, ku
-                    fv, kv = phi(v), K(v)
-                    nn = nn | (on & np.isnan(fv))
-                    ab = fv > 0
-                    opening = on & entry & atA                           # the window's first candidate sets the state
-                    cross = on & ~opening & (ab != st)
-                    inside = cross & ~entry                              # (else: a later segment's first candidate)
-                    found, root = H._bisect(phi, u, v, inside & (fu != 0) & (fv != 0))
-                    z = np.where(inside & (fu == 0), u, np.where(found, root, v))
-                    tz = np.where(atA & (z == xlo), t_lo, np.where(atB & (z == xhi), t_hi, np.where(
-                        z == 0.0, t_a, np.where(z == 1.0, t_b, t_a + z * h))))
-                    piece = on & ~entry                                  # u -> v, or u -> z under the old state and z -> v
-                    kz = np.where(inside, K(z), ku)
-                    head = kz - ku
-                    aup, adn = np.where(inside & st, aup + head, aup), np.where(inside & ~st, adn - head, adn)
-                    tail = kv - kz
-                    aup, adn = np.where(piece & ab, aup + tail, aup), np.where(piece & ~ab, adn - tail, adn)
-                    tot = np.where(cross & ~ab, tot + (tz - up), tot)
-                    up = np.where(opening, t_lo, np.where(cross & ab, tz, up))
-                    st = np.where(opening | cross, ab, st)
-                    entry, u, fu, ku = entry & ~on, np.where(on, v, u), np.where(on, fv, fu), np.where(on, kv, ku)
-
-                every = np.ones(e.shape, dtype=bool)
-                x1 = (-b) / a4
-                xm = np.where((a != 0.0) & (xlo < x1) & (x1 < xhi), x1, xlo)
-                f0, root = H._bisect(g1, xlo, xm, xm > xlo)
-                r0 = np.where(f0, root, xlo)
-                f1, root = H._bisect(g1, xm, xhi, every)
-                r1 = np.where(f1, root, r0)
-                visit(xlo, every)
-                for lo, hi in ((xlo, r0), (r0, r1)):
-                    fz, z = H._bisect(g, lo, hi, hi > lo)
-                    visit(z, fz)
-                    visit(hi, hi > lo)
-                fz, z = H._bisect(g, r1, xhi, every)
-                visit(z, fz)
-                visit(xhi, every)
-                state[idx], t_up[idx], total[idx], a_up[idx], a_dn[idx], nan[idx] = st, up, tot, aup, adn, nn
-            total = np.where(state, total + (qb[:, None] - t_up), total)
-            above = np.where(nan, np.nan, np.where(a_up < 0, 0.0, a_up)).astype(planes.dtype)
-            below = np.where(nan, np.nan, np.where(a_dn < 0, 0.0, a_dn)).astype(planes.dtype)
+            above = np.where(nan, np.nan, np.where(a_up < 0, 0.0, a_up)).astype(q.numpy().dtype)
+            below = np.where(nan, np.nan, np.where(a_dn < 0, 0.0, a_dn)).astype(q.numpy().dtype)
             total = np.where(nan, np.nan, total)
         return tuple(torch.from_numpy(np.ascontiguousarray(v)) for v in (above, below, total))
 

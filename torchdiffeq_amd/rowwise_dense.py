@@ -270,45 +270,63 @@ class RowDenseOutput:
         first = int(bad[0]) if bad.size else _NONE
         return torch.from_numpy(seg.reshape(-1).astype(np.int32)), torch.from_numpy(x.reshape(-1).astype(T)), first
 
-    def search(self, tq: torch.Tensor):
-        """The segment lookup alone, on the device kernels: `tq` fp64 `[Q, B]` in SOLVER time, contiguous, on the state's
-        device -> (seg int32 [Q * B], x [Q * B] in the state's dtype, status int32 [1]: the smallest out-of-range query
-        index, 0x7FFFFFFF for none — still on the device, not read)."""
+    def _search_device(self, tq: torch.Tensor, status: torch.Tensor):
+        """`search` with the status word given: int32 [1], preset to 0x7FFFFFFF -> (seg, x)."""
         dev = self.coeffs.device
         n = tq.numel()
         seg = torch.empty(n, dtype=torch.int32, device=dev)
         x = torch.empty(n, dtype=self.coeffs.dtype, device=dev)
-        status = torch.full((1,), _NONE, dtype=torch.int32, device=dev)
         self._k.row_dense_search(tq, self.offsets, self._ta, self._tb, self._t0, self._t1, seg, x, status)
-        return seg, x, status
+        return seg, x
+
+    def search(self, tq: torch.Tensor):
+        """The segment lookup alone, on the device kernels: `tq` fp64 `[Q, B]` in SOLVER time, contiguous, on the state's
+        device -> (seg int32 [Q * B], x [Q * B] in the state's dtype, status int32 [1]: the smallest out-of-range query
+        index, 0x7FFFFFFF for none — still on the device, not read)."""
+        status = torch.full((1,), _NONE, dtype=torch.int32, device=self.coeffs.device)
+        return (*self._search_device(tq, status), status)
+
+    def _ask(self, what: str, names, ts, check: bool, spec, host, device, prefix: bool = False):
+        """The steps every query method shares.  The query lists `ts` (called `names` in messages) are parsed and broadcast
+        against each other; the outputs are allocated from `spec`, one (dtype, leading dimensions) each, as `[*leading, Q * B,
+        L]`; every list is searched; then the one evaluation: for a CPU state `host(lists)` gives the outputs' values, else
+        `device(outs, lists)` launches into them, with `lists` = [seg, x, tq] of every list in turn, `tq` in solver time, and
+        with `prefix` the prefix store as one more argument.  With `check` the status words of the searches are read once and
+        the first out-of-range query raises -> the outputs as `[*leading, Q, B, *row_shape]`, without the Q of single times."""
+        tqs, single = self._query_lists(what, names, ts)
+        Q, B = tqs[0].shape
+        if self._k is not None and Q * B >= _NONE:
+            raise ValueError(f"{what}: {Q * B} queries in one call; the query index is a 32-bit word")
+        L, dev = self.coeffs.shape[2], self.coeffs.device
+        outs = [torch.empty(*lead, Q * B, L, dtype=dtype, device=dev) for dtype, lead in spec]
+        firsts = [_NONE] * len(tqs)
+        if Q > 0:
+            with torch.no_grad(), device_guard(dev):
+                more = (self._integral_prefix(),) if prefix else ()
+                if self._k is None:
+                    found = [self._search_host(tq) for tq in tqs]
+                    firsts = [first for _, _, first in found]
+                    lists = [v for (seg, x, _), tq in zip(found, tqs) for v in (seg, x, tq)]
+                    for dst, src in zip(outs, host(lists, *more)):
+                        dst.copy_(src)
+                else:
+                    status = torch.full((len(tqs),), _NONE, dtype=torch.int32, device=dev)
+                    lists = [v for i, tq in enumerate(tqs) for v in (*self._search_device(tq, status[i:i + 1]), tq)]
+                    device(outs, lists, *more)
+                    if check:
+                        firsts = status.tolist()                          # the one read
+        if check:
+            self._raise_out_of_range(what, names, tqs, firsts)
+        outs = [v.view(*v.shape[:-2], Q, *self._shape) for v in outs]
+        return [v.select(len(lead), 0) for v, (_, lead) in zip(outs, spec)] if single else outs
 
     def __call__(self, t, check: bool = True) -> torch.Tensor:
         """Row r at `t`: a number or 0-dim tensor -> `[B, *row_shape]`; `[Q]` (the same times for every row) or `[Q, B]` (times
         per row) -> `[Q, B, *row_shape]`.  A query outside `[t0[r], t1[r]]` (a NaN included) raises ValueError naming the
         first such query — or, with `check=False`, gives an all-NaN row without any host read."""
-        tq, single = self._queries(t)
-        Q, B = tq.shape
-        L, dev = self.coeffs.shape[2], self.coeffs.device
-        out = torch.empty(Q * B, L, dtype=self.coeffs.dtype, device=dev)
-        first = _NONE
-        if Q > 0:
-            with torch.no_grad(), device_guard(dev):
-                if self._k is None:
-                    seg, x, first = self._search_host(tq)
-                    out.copy_(rowwise.HostRowKernels.eval_quartics(self.coeffs, seg, x))
-                else:
-                    if Q * B >= _NONE:
-                        raise ValueError(f"dense(t): {Q * B} queries in one call; the query index is a 32-bit word")
-                    seg, x, status = self.search(tq)
-                    self._k.row_event_eval_mapped(out, None, self.coeffs, seg, x)
-                    if check:
-                        first = int(status)
-        if check and first != _NONE:
-            j, r = divmod(first, B)
-            raise ValueError("dense(t): query {} of row {} (t = {}) is outside the row's interval [t0, t1] = [{}, {}]".format(
-                j, r, float(tq[j, r]) * self._sign, float(self.t0[r]), float(self.t1[r])))
-        out = out.view(Q, *self._shape)
-        return out[0] if single else out
+        return self._ask("dense(t)", ("t",), (t,), check, [(self.coeffs.dtype, ())],
+                         lambda lists: [rowwise.HostRowKernels.eval_quartics(self.coeffs, *lists[:2])],
+                         lambda outs, lists: self._k.row_event_eval_mapped(outs[0], None, self.coeffs, *lists[:2]))[0]
 
     # -- calculus on the record: closed forms of every segment's quartic ---------------------------------------------------
     def _integral_prefix(self) -> torch.Tensor:
@@ -328,48 +346,21 @@ class RowDenseOutput:
         self._prefix = None
 
     def _calculus(self, what: str, mode: int, names, ts, check: bool) -> torch.Tensor:
-        """`derivative` (mode 0), `antiderivative` (1), `integral` (2) of the query lists `ts`, in the steps of `dense(t)`:
-        the search per list, one evaluation, one read of the status words (with `check`)."""
-        tqs, single = self._query_lists(what, names, ts)
-        B = self._shape[0]
-        Q = tqs[0].shape[0]
-        L, dev, dtype = self.coeffs.shape[2], self.coeffs.device, self.coeffs.dtype
-        out = torch.empty(Q * B, L, dtype=dtype, device=dev)
-        firsts = [_NONE] * len(tqs)
-        if Q > 0:
-            with torch.no_grad(), device_guard(dev):
-                prefix = self._integral_prefix() if mode else None
-                if self._k is None:
-                    H = rowwise.HostRowKernels
-                    found = [self._search_host(tq) for tq in tqs]
-                    firsts = [first for _, _, first in found]
-                    if mode == 0:
-                        seg, x, _ = found[0]
-                        s = seg.numpy().astype(np.int64)
-                        w = (self._sign * (self._tb.numpy()[s] - self._ta.numpy()[s])).astype(x.numpy().dtype)
-                        out.copy_(H.quartic_derivatives(self.coeffs, seg, x, torch.from_numpy(w)))
-                    else:
-                        F = [H.quartic_antiderivatives(self.coeffs, prefix, self._ta, self._tb, self._sign, seg, x, tq)
-                             for (seg, x, _), tq in zip(found, tqs)]
-                        out.copy_((F[0] if mode == 1 else F[1] - F[0]).to(dtype))
-                else:
-                    if Q * B >= _NONE:
-                        raise ValueError(f"{what}: {Q * B} queries in one call; the query index is a 32-bit word")
-                    status = torch.full((len(tqs),), _NONE, dtype=torch.int32, device=dev)
-                    lists = []
-                    for i, tq in enumerate(tqs):
-                        seg = torch.empty(Q * B, dtype=torch.int32, device=dev)
-                        x = torch.empty(Q * B, dtype=dtype, device=dev)
-                        self._k.row_dense_search(tq, self.offsets, self._ta, self._tb, self._t0, self._t1, seg, x,
-                                                 status[i:i + 1])
-                        lists += [seg, x, tq]
-                    self._k.row_dense_calc(out, mode, self.coeffs, self._ta, self._tb, prefix, self._sign, *lists)
-                    if check:
-                        firsts = status.tolist()                          # the one read
-        if check:
-            self._raise_out_of_range(what, names, tqs, firsts)
-        out = out.view(Q, *self._shape)
-        return out[0] if single else out
+        """`derivative` (mode 0), `antiderivative` (1), `integral` (2) of the query lists `ts`, in the steps of `dense(t)`."""
+        def host(lists, prefix=None):
+            H = rowwise.HostRowKernels
+            if mode == 0:
+                seg, x, _ = lists
+                s = seg.numpy().astype(np.int64)
+                w = (self._sign * (self._tb.numpy()[s] - self._ta.numpy()[s])).astype(x.numpy().dtype)
+                return [H.quartic_derivatives(self.coeffs, seg, x, torch.from_numpy(w))]
+            F = [H.quartic_antiderivatives(self.coeffs, prefix, self._ta, self._tb, self._sign, *lists[i:i + 3])
+                 for i in range(0, len(lists), 3)]
+            return [(F[0] if mode == 1 else F[1] - F[0]).to(self.coeffs.dtype)]
+
+        def device(outs, lists, prefix=None):
+            self._k.row_dense_calc(outs[0], mode, self.coeffs, self._ta, self._tb, prefix, self._sign, *lists)
+        return self._ask(what, names, ts, check, [(self.coeffs.dtype, ())], host, device, prefix=mode != 0)[0]
 
     def _query_lists(self, what: str, names, ts):
         """One or two query lists -> ([fp64 [Q, B] in solver time, ...] broadcast against each other, all were single)."""
@@ -415,42 +406,12 @@ class RowDenseOutput:
 
     # -- extrema over a time window: every segment's quartic between the window's ends -------------------------------------
     def _extremum(self, what: str, which: int, ta, tb, check: bool) -> RowDenseExtremum:
-        """`maximum` (which 0) / `minimum` (1) in the steps of `integral`: the search per end, one launch, one read of the
-        status words (with `check`).  Nothing is built or kept."""
-        names = ("ta", "tb")
-        tqs, single = self._query_lists(what, names, (ta, tb))
-        Q, B = tqs[0].shape
-        if self._k is not None and Q * B >= _NONE:
-            raise ValueError(f"{what}: {Q * B} queries in one call; the query index is a 32-bit word")
-        L, dev, dtype = self.coeffs.shape[2], self.coeffs.device, self.coeffs.dtype
-        values = torch.empty(Q * B, L, dtype=dtype, device=dev)
-        times = torch.empty(Q * B, L, dtype=torch.float64, device=dev)
-        firsts = [_NONE, _NONE]
-        if Q > 0:
-            with torch.no_grad(), device_guard(dev):
-                if self._k is None:
-                    found = [self._search_host(tq) for tq in tqs]
-                    firsts = [first for _, _, first in found]
-                    lists = [v for (seg, x, _), tq in zip(found, tqs) for v in (seg, x, tq)]
-                    v, t = rowwise.HostRowKernels.quartic_extrema(self.coeffs, self._ta, self._tb, self._sign, *lists, which == 0)
-                    values.copy_(v)
-                    times.copy_(t)
-                else:
-                    status = torch.full((2,), _NONE, dtype=torch.int32, device=dev)
-                    lists = []
-                    for i, tq in enumerate(tqs):
-                        seg = torch.empty(Q * B, dtype=torch.int32, device=dev)
-                        x = torch.empty(Q * B, dtype=dtype, device=dev)
-                        self._k.row_dense_search(tq, self.offsets, self._ta, self._tb, self._t0, self._t1, seg, x,
-                                                 status[i:i + 1])
-                        lists += [seg, x, tq]
-                    self._k.row_dense_extremum(values, times, which, self.coeffs, self._ta, self._tb, self._sign, *lists)
-                    if check:
-                        firsts = status.tolist()                          # the one read
-        if check:
-            self._raise_out_of_range(what, names, tqs, firsts)
-        values, times = values.view(Q, *self._shape), times.view(Q, *self._shape)
-        return RowDenseExtremum(values[0], times[0]) if single else RowDenseExtremum(values, times)
+        """`maximum` (which 0) / `minimum` (1) in the steps of `integral`.  Nothing is built or kept."""
+        record = (self.coeffs, self._ta, self._tb, self._sign)
+        return RowDenseExtremum(*self._ask(
+            what, ("ta", "tb"), (ta, tb), check, [(self.coeffs.dtype, ()), (torch.float64, ())],
+            lambda lists: rowwise.HostRowKernels.quartic_extrema(*record, *lists, which == 0),
+            lambda outs, lists: self._k.row_dense_extremum(*outs, which, *record, *lists)))
 
     def maximum(self, ta, tb, check: bool = True) -> RowDenseExtremum:
         """The largest value every ELEMENT of `y_r` takes on the closed window between `ta` and `tb` (true time, in either
@@ -493,48 +454,16 @@ class RowDenseOutput:
                              f"{list(self._shape)}") from None
         return lev.reshape(B, L).contiguous()
 
-    def _level_walk(self, what: str, level, ta, tb, check: bool, host: str, launch: str, dtypes, max_count: int = 0,
-                    listed: int = 0):
-        """The steps of `crossings`, `exposure` and `crossing_times`: the level, the search per end, one launch (`launch` of the
-        device kernels, `host` of `HostRowKernels` for a CPU state) that fills outputs of `dtypes`, one read of the status
-        words (with `check`) -> (the outputs as `[Q, B, *row_shape]`, both times were single).  The last `listed` outputs are
-        lists with a leading dimension: `[max_count, Q, B, *row_shape]`, and the host function takes `max_count` after the
-        sign.  Nothing is built or kept."""
-        names = ("ta", "tb")
+    def _level_walk(self, what: str, level, ta, tb, check: bool, host: str, launch: str, spec, *count):
+        """The steps of `crossings`, `exposure` and `crossing_times`: the level, then those of `maximum` with `launch` of the
+        device kernels, or `host` of `HostRowKernels` for a CPU state (it takes `count`, the `max_count` of the lists, after
+        the sign), filling outputs of `spec` (see `_ask`).  Nothing is built or kept."""
         lev = self._level(what, level)
-        tqs, single = self._query_lists(what, names, (ta, tb))
-        Q, B = tqs[0].shape
-        if self._k is not None and Q * B >= _NONE:
-            raise ValueError(f"{what}: {Q * B} queries in one call; the query index is a 32-bit word")
-        L, dev, dtype = self.coeffs.shape[2], self.coeffs.device, self.coeffs.dtype
-        plain = len(dtypes) - listed
-        outs = [torch.empty(*((max_count,) if i >= plain else ()), Q * B, L, dtype=t, device=dev) for i, t in enumerate(dtypes)]
-        firsts = [_NONE, _NONE]
-        if Q > 0:
-            with torch.no_grad(), device_guard(dev):
-                if self._k is None:
-                    found = [self._search_host(tq) for tq in tqs]
-                    firsts = [bad for _, _, bad in found]
-                    lists = [v for (seg, x, _), tq in zip(found, tqs) for v in (seg, x, tq)]
-                    walked = getattr(rowwise.HostRowKernels, host)(self.coeffs, lev, self._ta, self._tb, self._sign,
-                                                                   *((max_count,) if listed else ()), *lists)
-                    for dst, src in zip(outs, walked):
-                        dst.copy_(src)
-                else:
-                    status = torch.full((2,), _NONE, dtype=torch.int32, device=dev)
-                    lists = []
-                    for i, tq in enumerate(tqs):
-                        seg = torch.empty(Q * B, dtype=torch.int32, device=dev)
-                        x = torch.empty(Q * B, dtype=dtype, device=dev)
-                        self._k.row_dense_search(tq, self.offsets, self._ta, self._tb, self._t0, self._t1, seg, x,
-                                                 status[i:i + 1])
-                        lists += [seg, x, tq]
-                    getattr(self._k, launch)(*outs, lev, self.coeffs, self._ta, self._tb, self._sign, *lists)
-                    if check:
-                        firsts = status.tolist()                          # the one read
-        if check:
-            self._raise_out_of_range(what, names, tqs, firsts)
-        return [v.view(*v.shape[:-2], Q, *self._shape) for v in outs], single
+        record = (self.coeffs, self._ta, self._tb, self._sign)
+        return self._ask(
+            what, ("ta", "tb"), (ta, tb), check, spec,
+            lambda lists: getattr(rowwise.HostRowKernels, host)(self.coeffs, lev, *record[1:], *count, *lists),
+            lambda outs, lists: getattr(self._k, launch)(*outs, lev, *record, *lists))
 
     def crossings(self, level, ta, tb, check: bool = True) -> RowDenseCrossings:
         """Where every ELEMENT of `y_r` crosses `level` on the window between `ta` and `tb` (true time, in either order: the
@@ -551,9 +480,9 @@ class RowDenseOutput:
         `odeint_rowwise_dense`).  The segment that starts at a breakpoint `p` is entered at its start: a `jump_dy` dose at `p`
         inside the window or at its near end that lifts the element over the level is a crossing at time `p`; one at the far
         end is not seen.  Builds and caches nothing."""
-        outs, single = self._level_walk("dense.crossings(level, ta, tb)", level, ta, tb, check, "quartic_levels",
-                                        "row_dense_level", (torch.int32, torch.float64, torch.float64, torch.float64))
-        return RowDenseCrossings(*(v[0] for v in outs)) if single else RowDenseCrossings(*outs)
+        f64 = torch.float64
+        return RowDenseCrossings(*self._level_walk("dense.crossings(level, ta, tb)", level, ta, tb, check, "quartic_levels",
+                                                   "row_dense_level", [(torch.int32, ()), (f64, ()), (f64, ()), (f64, ())]))
 
     def time_above(self, level, ta, tb, check: bool = True) -> torch.Tensor:
         """The total true-time duration every element spends strictly above `level` on the window: `crossings(level, ta, tb,
@@ -580,11 +509,9 @@ class RowDenseOutput:
         what = "dense.crossing_times(level, ta, tb)"
         if not isinstance(max_count, int) or isinstance(max_count, bool) or not 1 <= max_count <= 65535:
             raise ValueError(f"{what}: max_count must be an int in [1, 65535], got {max_count!r}")
-        outs, single = self._level_walk(what, level, ta, tb, check, "quartic_crossing_times", "row_dense_level_times",
-                                        (torch.int32, torch.int32, torch.float64, torch.float64), max_count, listed=2)
-        if single:
-            outs = [outs[0][0], outs[1][0], outs[2][:, 0], outs[3][:, 0]]
-        return RowDenseCrossingTimes(*outs)
+        counts, times = (torch.int32, ()), (torch.float64, (max_count,))
+        return RowDenseCrossingTimes(*self._level_walk(what, level, ta, tb, check, "quartic_crossing_times",
+                                                       "row_dense_level_times", [counts, counts, times, times], max_count))
 
     # -- area above and below a level over a time window: the walk of the crossings, integrating as it goes --------------------
     def exposure(self, level, ta, tb, check: bool = True) -> RowDenseExposure:
@@ -600,9 +527,8 @@ class RowDenseOutput:
         ends, up to rounding.  A `jump_dy` dose at `p` switches sides at `p` with zero width, for `lo <= p < hi`; a window that
         ends at `p` does not see it, and `exposure(level, p, p)` is all zeros.  Builds and caches nothing."""
         T = self.coeffs.dtype
-        outs, single = self._level_walk("dense.exposure(level, ta, tb)", level, ta, tb, check, "quartic_exposure",
-                                        "row_dense_exposure", (T, T, torch.float64))
-        return RowDenseExposure(*(v[0] for v in outs)) if single else RowDenseExposure(*outs)
+        return RowDenseExposure(*self._level_walk("dense.exposure(level, ta, tb)", level, ta, tb, check, "quartic_exposure",
+                                                  "row_dense_exposure", [(T, ()), (T, ()), (torch.float64, ())]))
 
     def area_above(self, level, ta, tb, check: bool = True) -> torch.Tensor:
         """The integral of `max(y - level, 0)` over the window, per element: `exposure(level, ta, tb, check).area_above`, the
