@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define TDEQ_ABI_VERSION 35
+#define TDEQ_ABI_VERSION 36
 #define TDEQ_F32 0
 #define TDEQ_F64 1
 /* interleaved (re, im) complex states — accepted by the NORM entry points only (tdeq_error_norm, tdeq_error_norm_partial[_ctrl],
@@ -69,6 +69,8 @@ extern "C" {
 #define TDEQ_MAX_SEGMENTS 4096
 #define TDEQ_INLINE_SEGMENTS 16  /* segment tables up to this size travel in the kernel arguments */
 #define TDEQ_CHUNK_QUANTUM 1024
+#define TDEQ_ROW_QUANTILES_MAX_RANKS 16   /* tdeq_row_dense_quantiles */
+#define TDEQ_ROW_QUANTILES_SLAB_ROWS 1024  /* rows of one workgroup of its counting pass */
 
 #define TDEQ_EINVAL (-1)       /* bad argument (null pointer, n_terms out of range, bad dtype ...) */
 #define TDEQ_EWORKSPACE (-2)   /* workspace too small */
@@ -983,6 +985,47 @@ int tdeq_row_dense_level_times(int32_t* n_rising, int32_t* n_falling, double* ri
                                const double* seg_tb, double time_sign, const int32_t* seg, const void* x, const double* tq,
                                const int32_t* seg2, const void* x2, const double* tq2, int64_t n_idx, int64_t row_len,
                                int dtype, void* stream);
+
+/*
+ * ---- Order statistics across rows (ABI 36; `RowDenseOutput.quantiles`) ----
+ * tdeq_row_dense_quantiles  for p < n_ranks, j < n_q and every element el of the row: out[p, j, el] = the value of rank
+ *                          ranks[p] (0 = the smallest) among the n_rows values v[r] = the quartic coeffs[:, seg[j * n_rows + r],
+ *                          el] at x[j * n_rows + r], r < n_rows, which are the values tdeq_row_event_eval_mapped gives those
+ *                          queries, bit for bit (eval_one, nothing contracted).  `out` [n_ranks, n_q, row_len] of the state
+ *                          type T; `ranks` DEVICE int32 [n_ranks], 0 <= ranks[p] < n_rows, duplicates allowed, NOT checked
+ *                          (a rank outside the rows gives an unspecified value and touches no memory outside the buffers);
+ *                          `coeffs` [5, n_seg, row_len]; `seg` int32 and `x` of T, both [n_q * n_rows]: what
+ *                          tdeq_row_dense_search wrote for tq [n_q, n_rows].
+ *                          Order.  Values are ordered by their key, an unsigned integer of the width of T: with u the bits of
+ *                                   v, key = all ones for a NaN, else u with the sign bit set for a clear sign bit, else ~u.
+ *                                   So -inf < ... < -0.0 < +0.0 < ... < +inf < NaN: -0.0 sorts before +0.0, every NaN last.
+ *                                   out is the inverse image of the selected key: the bits of one of the n_rows values, and
+ *                                   the canonical quiet NaN (0x7fc00000 / 0x7ff8000000000000) for a NaN of any payload.  A
+ *                                   query the search found out of range has x = NaN, hence v = NaN: it takes a top rank.
+ *                          Method.  A radix select, most significant byte first: sizeof(T) passes, each of which evaluates
+ *                                   every (query, row, element) again and counts one byte of the keys that share the bytes
+ *                                   selected so far, in 256 x 64 histograms in LDS that are added to global ones with integer
+ *                                   atomics, followed by one lane per (rank, query, element) that picks the byte.  Counts are
+ *                                   integers, so the result depends neither on the grid nor on the order of the rows; nothing
+ *                                   of size n_q * n_rows * row_len is written.  1 + 2 * sizeof(T) launches: 9 for TDEQ_F32,
+ *                                   17 for TDEQ_F64.  A workgroup of the counting pass takes TDEQ_ROW_QUANTILES_SLAB_ROWS
+ *                                   rows of one query and 64 elements; for every n_rows the rows are split in that way.
+ *                          `workspace`: 16-byte aligned device memory of at least
+ *                          tdeq_row_dense_quantiles_workspace_bytes(n_ranks, n_q, row_len, dtype) =
+ *                          (n_ranks + 1) * n_q * ceil(row_len / 64) * 65536 + 12 * n_ranks * n_q * row_len bytes (0 for
+ *                          arguments the entry point refuses); its content before and after the call means nothing.
+ *                          16-byte loads when row_len is a multiple of 16 / sizeof(T) and `coeffs` is 16-byte aligned, scalar
+ *                          loads otherwise, with the same bits.  A NULL pointer, a negative size, n_ranks outside 1 ..
+ *                          TDEQ_ROW_QUANTILES_MAX_RANKS, n_seg < 1, n_q * n_rows >= INT32_MAX, a workspace that is not 16-byte
+ *                          aligned, n_q * ceil(row_len / 64) > INT32_MAX (the workspace size is then 0: no byte count of the
+ *                          call can overflow), more than INT32_MAX workgroups in a pass, or a dtype other than TDEQ_F32 /
+ *                          TDEQ_F64: TDEQ_EINVAL before any launch.  workspace_bytes too small: TDEQ_EWORKSPACE.  n_q == 0, n_rows == 0
+ *                          or row_len == 0: no-op.
+ */
+size_t tdeq_row_dense_quantiles_workspace_bytes(int n_ranks, int64_t n_q, int64_t row_len, int dtype);
+int tdeq_row_dense_quantiles(void* out, const int32_t* ranks, int n_ranks, const void* coeffs, int64_t n_seg,
+                             const int32_t* seg, const void* x, int64_t n_q, int64_t n_rows, int64_t row_len, void* workspace,
+                             size_t workspace_bytes, int dtype, void* stream);
 
 /*
  * ---- Per-row step options (ABI 29; `min_step`, `max_step`, `step_t`, `jump_t` of the rowwise family) ----

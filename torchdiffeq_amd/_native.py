@@ -18,7 +18,9 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-TDEQ_ABI_VERSION = 35
+TDEQ_ABI_VERSION = 36
+TDEQ_ROW_QUANTILES_MAX_RANKS = 16       # include/tdeq_hip.h
+TDEQ_ROW_QUANTILES_SLAB_ROWS = 1024     # rows of one workgroup of the counting pass of tdeq_row_dense_quantiles
 TDEQ_F32, TDEQ_F64 = 0, 1
 TDEQ_C64, TDEQ_C128 = 2, 3        # interleaved complex: the norm entry points only (include/tdeq_hip.h)
 TDEQ_BF16, TDEQ_F16 = 4, 5        # reduced-precision states: the entry points of the host-driven step (LowPrecisionHipKernels)
@@ -316,6 +318,12 @@ ABI_SIGNATURES = {
                                                   ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                                   ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
                                                   ctypes.c_int, ctypes.c_void_p]),
+    # order statistics across rows (ABI 36, `RowDenseOutput.quantiles`)
+    "tdeq_row_dense_quantiles_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int]),
+    "tdeq_row_dense_quantiles": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int64,
+                                                ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
+                                                ctypes.c_int64, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int,
+                                                ctypes.c_void_p]),
     # per-row step options (ABI 29, `min_step` / `max_step` / `step_t` / `jump_t` of the rowwise family)
     "tdeq_row_control_points": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(StepCtrl),
                                                ctypes.POINTER(RowState), ctypes.POINTER(RowPoints), ctypes.c_void_p,
@@ -1310,6 +1318,41 @@ class HipKernels:
         if tail is not None:
             _check(self.lib.tdeq_row_dense_level_times(n_rising.data_ptr(), n_falling.data_ptr(), rising.data_ptr(),
                                                        falling.data_ptr(), K, *tail), "tdeq_row_dense_level_times")
+
+    # -- order statistics across rows of the record (RowDenseOutput.quantiles) ------------------------------------------------
+    def row_dense_quantiles_workspace_bytes(self, n_ranks: int, n_q: int, row_len: int, dtype) -> int:
+        """tdeq_row_dense_quantiles_workspace_bytes: the workspace of `row_dense_quantiles` for that many ranks and query times."""
+        return int(self.lib.tdeq_row_dense_quantiles_workspace_bytes(n_ranks, n_q, row_len, dtype_code(dtype)))
+
+    def row_dense_quantiles(self, out, ranks, coeffs, seg, x, workspace) -> None:
+        """tdeq_row_dense_quantiles: out[p, j, :] = per element the value of rank ranks[p] among the n_rows values of query
+        time j, the queries (seg[j * n_rows + r], x[j * n_rows + r]) of `row_dense_search`.  `out` [P, Q, L] of the dtype of
+        `coeffs` [5, n_seg, L], `ranks` int32 [P] on the device with 0 <= ranks < n_rows (not checked here: they are not
+        read), `seg` int32 and `x` [Q * n_rows], `workspace` a contiguous uint8 tensor of at least
+        `row_dense_quantiles_workspace_bytes(P, Q, L, dtype)` bytes."""
+        if out.dim() != 3 or ranks.dim() != 1 or out.shape[0] != ranks.numel() or not out.is_contiguous():
+            raise ValueError("row_dense_quantiles: out must be a contiguous [P, Q, L] tensor for ranks [P]")
+        P, Q, L = out.shape
+        if not 1 <= P <= TDEQ_ROW_QUANTILES_MAX_RANKS:
+            raise ValueError(f"row_dense_quantiles: 1 to {TDEQ_ROW_QUANTILES_MAX_RANKS} ranks, got {P}")
+        if Q == 0 or L == 0:
+            return
+        if coeffs.dim() != 3 or coeffs.shape[0] != 5 or coeffs.shape[1] < 1 or coeffs.shape[2] != L \
+                or coeffs.dtype != out.dtype or not coeffs.is_contiguous():
+            raise ValueError("row_dense_quantiles: coeffs must be a contiguous [5, n_seg >= 1, L] tensor of out's dtype")
+        n_idx = seg.numel()
+        if n_idx == 0 or n_idx % Q != 0:
+            raise ValueError(f"row_dense_quantiles: seg must hold n_rows >= 1 queries for each of the {Q} times")
+        for name, t, dtype, shape in (("ranks", ranks, torch.int32, (P,)), ("seg", seg, torch.int32, (n_idx,)),
+                                      ("x", x, out.dtype, (n_idx,))):
+            if tuple(t.shape) != shape or t.dtype != dtype or not t.is_contiguous():
+                raise ValueError(f"row_dense_quantiles: {name} must be a contiguous {dtype} {list(shape)} tensor")
+        if workspace.dtype != torch.uint8 or workspace.dim() != 1 or not workspace.is_contiguous():
+            raise ValueError("row_dense_quantiles: workspace must be a contiguous uint8 vector")
+        _check(self.lib.tdeq_row_dense_quantiles(out.data_ptr(), ranks.data_ptr(), P, coeffs.data_ptr(), coeffs.shape[1],
+                                                 seg.data_ptr(), x.data_ptr(), Q, n_idx // Q, L, workspace.data_ptr(),
+                                                 workspace.numel(), dtype_code(out.dtype), self._stream()),
+               "tdeq_row_dense_quantiles")
 
 
 class ComplexHipKernels:

@@ -1062,3 +1062,95 @@ int tdeq_row_dense_exposure(void* area_above, void* area_below, double* time_abo
         return row_dense_exposure_launch<decltype(t)>(area_above, area_below, time_above, w, s);
     });
 }
+
+// ---- order statistics across rows: tdeq_row_dense_quantiles -----------------------------------------------------------------
+namespace {
+
+// the three parts of the workspace, in bytes: the global histograms (first: they are cleared in 16-byte words), the prefixes,
+// the remaining ranks
+struct RowDenseQuantSpace {
+    size_t hist, prefix, rem;
+};
+
+inline RowDenseQuantSpace row_dense_quant_space(int n_ranks, int64_t n_q, int64_t row_len) {
+    const size_t tiles = (size_t)((row_len + kQuantTile - 1) / kQuantTile), cells = (size_t)n_ranks * n_q * row_len;
+    return {(size_t)(n_ranks + 1) * n_q * tiles * kQuantBins * kQuantTile * sizeof(uint32_t), cells * sizeof(uint64_t),
+            cells * sizeof(uint32_t)};
+}
+
+// (n_q * tiles <= INT32_MAX, tested without overflow: the byte counts of row_dense_quant_space then fit a size_t)
+inline bool row_dense_quant_sizes_ok(int n_ranks, int64_t n_q, int64_t row_len, int dtype) {
+    if (n_ranks < 1 || n_ranks > TDEQ_ROW_QUANTILES_MAX_RANKS || n_q < 0 || row_len < 0 || !real_dtype_ok(dtype)) return false;
+    if (n_q > 0x7fffffffLL || row_len > 0x7fffffffLL * kQuantTile) return false;
+    const int64_t tiles = (row_len + kQuantTile - 1) / kQuantTile;
+    return tiles == 0 || n_q <= 0x7fffffffLL / tiles;
+}
+
+template <typename T>
+int row_dense_quant_launch(RowDenseQuantArgs<T>& a, bool aligned, hipStream_t s) {
+    const int64_t per_pass = a.slabs * a.tiles * a.n_q;               // workgroups of pass 0; n_ranks times that later
+    if (per_pass * a.n_ranks > 0x7fffffffLL) return TDEQ_EINVAL;
+    RowDenseQuantClearArgs c;
+    c.hist = reinterpret_cast<u32x4*>(a.hist);
+    c.n = (int64_t)(a.n_ranks + 1) * a.n_q * a.tiles * kQuantBins * kQuantTile / 4;
+    hipLaunchKernelGGL(row_dense_quant_clear_kernel, dim3(stream_grid(c.n, kBlock)), dim3(kBlock), 0, s, c);
+    int64_t unused;
+    return row_vec<T>(a.row_len, aligned, unused, [&](auto vec) {
+        constexpr bool VEC = decltype(vec)::value;
+        const dim3 block(kBlock), pick(stream_grid(a.n_ranks * a.n_q * a.row_len, kBlock));
+        for (a.pass = 0; a.pass < (int)sizeof(T); ++a.pass) {
+            if (a.pass == 0) {
+                hipLaunchKernelGGL((row_dense_quant_count_kernel<T, VEC, true>), dim3((unsigned)per_pass), block, 0, s, a);
+                hipLaunchKernelGGL((row_dense_quant_select_kernel<T, true>), pick, block, 0, s, a);
+            } else {
+                hipLaunchKernelGGL((row_dense_quant_count_kernel<T, VEC, false>), dim3((unsigned)(per_pass * a.n_ranks)), block,
+                                   0, s, a);
+                hipLaunchKernelGGL((row_dense_quant_select_kernel<T, false>), pick, block, 0, s, a);
+            }
+        }
+        return check_launch();
+    });
+}
+
+}  // namespace
+
+size_t tdeq_row_dense_quantiles_workspace_bytes(int n_ranks, int64_t n_q, int64_t row_len, int dtype) {
+    if (!row_dense_quant_sizes_ok(n_ranks, n_q, row_len, dtype)) return 0;
+    const RowDenseQuantSpace w = row_dense_quant_space(n_ranks, n_q, row_len);
+    return w.hist + w.prefix + w.rem;
+}
+
+int tdeq_row_dense_quantiles(void* out, const int32_t* ranks, int n_ranks, const void* coeffs, int64_t n_seg,
+                             const int32_t* seg, const void* x, int64_t n_q, int64_t n_rows, int64_t row_len, void* workspace,
+                             size_t workspace_bytes, int dtype, void* stream) {
+    if (!out || !ranks || !coeffs || !seg || !x || !workspace || !row_dense_quant_sizes_ok(n_ranks, n_q, row_len, dtype))
+        return TDEQ_EINVAL;
+    if (n_rows < 0 || n_seg < 1 || !aligned16(workspace)) return TDEQ_EINVAL;
+    if (n_rows > 0 && n_q > 0x7ffffffeLL / n_rows) return TDEQ_EINVAL;      // n_q * n_rows >= INT32_MAX
+    const RowDenseQuantSpace w = row_dense_quant_space(n_ranks, n_q, row_len);
+    if (workspace_bytes < w.hist + w.prefix + w.rem) return TDEQ_EWORKSPACE;
+    if (n_q == 0 || n_rows == 0 || row_len == 0) return 0;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return real_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        RowDenseQuantArgs<T> a;
+        a.q = static_cast<const T*>(coeffs);
+        a.seg = seg;
+        a.x = static_cast<const T*>(x);
+        a.ranks = ranks;
+        a.out = static_cast<T*>(out);
+        a.hist = static_cast<uint32_t*>(workspace);
+        a.prefix = reinterpret_cast<uint64_t*>(static_cast<char*>(workspace) + w.hist);
+        a.rem = reinterpret_cast<uint32_t*>(static_cast<char*>(workspace) + w.hist + w.prefix);
+        a.n_rows = n_rows;
+        a.n_seg = n_seg;
+        a.row_len = row_len;
+        a.q_plane = n_seg * row_len;
+        a.n_q = n_q;
+        a.tiles = (row_len + kQuantTile - 1) / kQuantTile;
+        a.slabs = (n_rows + kQuantSlabRows - 1) / kQuantSlabRows;
+        a.n_ranks = n_ranks;
+        a.pass = 0;
+        return row_dense_quant_launch<T>(a, aligned16(coeffs), s);
+    });
+}

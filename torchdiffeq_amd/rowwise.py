@@ -858,6 +858,24 @@ class HostRowKernels:
         total = total + a * x4
         return total
 
+    @staticmethod
+    def quartic_quantiles(q, src, x, ranks, Q: int, B: int) -> torch.Tensor:
+        """The values of rank `ranks[p]` (0 = the smallest) among the B rows of each of the Q query times, per element: the
+        queries (src, x) [Q * B] of the search on the record `q` [5, n_seg, L] -> [P, Q, L].  The model of
+        tdeq_row_dense_quantiles: `eval_quartics`, then a sort along B of the key of that kernel as a SIGNED integer of the
+        width of the type (the bits of v >= +0 as they are, every bit but the sign flipped for v <= -0, the largest integer
+        for a NaN), so -0.0 sorts before +0.0 and every NaN last, and the inverse image of the key at each rank: the bits of
+        one of the B values, the canonical quiet NaN for a NaN."""
+        v = HostRowKernels.eval_quartics(q, src, x).view(Q, B, -1)
+        I = torch.int32 if v.dtype == torch.float32 else torch.int64
+        top = torch.iinfo(I).max
+        bits = v.contiguous().view(I)
+        key = torch.where(bits < 0, bits ^ top, bits)
+        key = torch.where(torch.isnan(v), torch.full_like(key, top), key)
+        picked = torch.sort(key, dim=1).values[:, torch.as_tensor(ranks, dtype=torch.int64)].transpose(0, 1).contiguous()
+        back = torch.where(picked < 0, picked ^ top, picked).view(v.dtype)
+        return torch.where(picked == top, torch.full_like(back, float("nan")), back)
+
     # -- calculus on a dense record (rowwise_dense.py; the arithmetic of tdeq_row_dense_prefix / tdeq_row_dense_calc) -----
     @staticmethod
     def _quartic_integral(e, d, c, b, a, x, h):

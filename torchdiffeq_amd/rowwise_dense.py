@@ -21,17 +21,21 @@ by `tdeq_row_dense_extremum`, which walks the window's segments and builds nothi
 above it are the same two searches followed by `tdeq_row_dense_level`, the same walk with a state machine; the area between
 the record and a level, above and below it, is the same again with `tdeq_row_dense_exposure`, which integrates `y - level`
 piece by piece while it walks; the times of ALL crossings, by direction, are the same walk with `tdeq_row_dense_level_times`,
-which stores every located time at once.  CPU states run the same steps as torch / numpy ops.
+which stores every located time at once; the order statistics across rows are one search followed by
+`tdeq_row_dense_quantiles`, a radix select that evaluates the record in every pass.  CPU states run the same steps as torch /
+numpy ops.
 """
 from __future__ import annotations
 
+import math
+import numbers
 from typing import NamedTuple
 
 import numpy as np
 import torch
 
 from . import rowwise
-from ._native import device_guard
+from ._native import TDEQ_ROW_QUANTILES_MAX_RANKS, device_guard
 from .rowwise import _Problem
 
 __all__ = ["odeint_rowwise_dense", "RowDenseOutput", "RowDenseExtremum", "RowDenseCrossings", "RowDenseCrossingTimes",
@@ -40,6 +44,7 @@ __all__ = ["odeint_rowwise_dense", "RowDenseOutput", "RowDenseExtremum", "RowDen
 # the default chunk: CHUNK_ROWS_PER_ROW slots per row of the batch, at most CHUNK_BYTES of coefficients, never fewer than B
 CHUNK_ROWS_PER_ROW = 4
 CHUNK_BYTES = 256 << 20
+QUANTILES_WORKSPACE_BYTES = 256 << 20                        # `quantiles` slices its query times to keep its workspace below
 _NONE = 0x7FFFFFFF                                           # the search's status word: no query out of range
 
 
@@ -208,8 +213,8 @@ class RowDenseOutput:
     `integral(ta, tb)` give its time derivative and its integrals in closed form, `maximum(ta, tb)` and `minimum(ta, tb)` its
     extrema over a time window and their times, `crossings(level, ta, tb)` and `time_above(level, ta, tb)` its crossings of a
     level and the time spent above it, `crossing_times(level, ta, tb, max_count)` the times of all its crossings by direction,
-    `exposure(level, ta, tb)`, `area_above(level, ta, tb)` and `area_below(level, ta, tb)` the area between it and a level (see
-    `odeint_rowwise_dense`).
+    `exposure(level, ta, tb)`, `area_above(level, ta, tb)` and `area_below(level, ta, tb)` the area between it and a level,
+    `quantiles(t, probs)` its order statistics across the rows (see `odeint_rowwise_dense`).
 
     Attributes (the wire format, all on the state's device): `t0`, `t1` `[B]` fp64 in true time; `offsets` `[B + 1]` int64;
     `seg_start`, `seg_end` `[n_seg]` fp64 in true time, row r's segments — its accepted steps — contiguous and in step
@@ -540,6 +545,82 @@ class RowDenseOutput:
         same launch."""
         return self.exposure(level, ta, tb, check).area_below
 
+    # -- order statistics across rows: a radix select on the record, nothing of size [Q, B, L] is built ----------------------
+    def _quantile_ranks(self, what: str, probs, ranks) -> list:
+        """`probs` or `ranks` -> the P ranks as Python ints in [0, B - 1]."""
+        B = self._shape[0]
+        if (probs is None) == (ranks is None):
+            raise ValueError(f"{what}: give exactly one of probs and ranks")
+        name, given = ("probs", probs) if ranks is None else ("ranks", ranks)
+        if isinstance(given, (str, bytes)) or not hasattr(given, "__iter__"):
+            raise ValueError(f"{what}: {name} must be a sequence of numbers, got {type(given).__name__}")
+        given = given.tolist() if isinstance(given, (torch.Tensor, np.ndarray)) else list(given)
+        if not 1 <= len(given) <= TDEQ_ROW_QUANTILES_MAX_RANKS:
+            raise ValueError(f"{what}: {name} must hold 1 to {TDEQ_ROW_QUANTILES_MAX_RANKS} entries, got {len(given)}")
+        out = []
+        for v in given:
+            if ranks is None:
+                if isinstance(v, bool) or not isinstance(v, numbers.Real) or not 0.0 <= v <= 1.0:      # (a NaN fails both)
+                    raise ValueError(f"{what}: probs must be numbers in [0, 1], got {v!r}")
+                out.append(int(math.floor(float(v) * (B - 1))))                                      # the "lower" rule
+            else:
+                if isinstance(v, bool) or not isinstance(v, numbers.Integral) or not 0 <= v <= B - 1:
+                    raise ValueError(f"{what}: ranks must be integers in [0, B - 1] = [0, {B - 1}], got {v!r}")
+                out.append(int(v))
+        return out
+
+    def quantiles(self, t, probs=None, *, ranks=None, check: bool = True) -> torch.Tensor:
+        """Order statistics ACROSS the B rows: per time and per ELEMENT of the row, the value of rank `k_p` (0 = the smallest)
+        among the B values `dense(t)[q, :, ...]` -> `[P, Q, *row_shape]` in the state's dtype (`[P, *row_shape]` for a single
+        time) — the 5 % / 50 % / 95 % bands of a population of simulated patients, the envelope of an ensemble.  `t` takes the
+        query forms of `dense(t)`.  Exactly one of `ranks`, a sequence of P integers in `[0, B - 1]`, and `probs`, a sequence of
+        P numbers in `[0, 1]` mapped in Python doubles to `k = floor(p * (B - 1))` (the "lower" rule: `p = 1` is the largest
+        value), with `1 <= P <= 16`; duplicates are allowed; anything else is a ValueError.  There is no interpolation between
+        ranks: ask for two and combine them.  Every returned value is one of the B evaluated values with the bits `dense(t)`
+        gives that row, except that among equal values `-0.0` sorts before `+0.0`; a NaN sorts last and comes back as the
+        canonical quiet NaN.  `check=True` raises for the first out-of-range query like `dense(t)`, after one read of the
+        status word; with `check=False` nothing is read and an out-of-range row counts as a NaN of that time's population, so
+        it takes a top rank.  A ROCm state runs a radix select on HIP kernels (`tdeq_row_dense_quantiles`, ABI 36) that
+        evaluates the record again in each of its `sizeof(dtype)` passes and never builds the `[Q, B, *row_shape]` values: next
+        to the outputs the call allocates the search's `[Q, B]` lists and a workspace of at most 256 MiB (or that of one
+        query time), and runs the times in slices that fit it.  A CPU state sorts the same integer keys with torch ops: the
+        same bits.  Counts are integers, so the result does not depend on the order of the rows.  Row subsets, weights, means
+        and gradients are out of scope."""
+        what = "dense.quantiles(t)"
+        ks = self._quantile_ranks(what, probs, ranks)
+        tqs, single = self._query_lists(what, ("t",), (t,))
+        tq = tqs[0]
+        Q, B = tq.shape
+        if self._k is not None and Q * B >= _NONE:
+            raise ValueError(f"{what}: {Q * B} queries in one call; the query index is a 32-bit word")
+        P, L, dev, T = len(ks), self.coeffs.shape[2], self.coeffs.device, self.coeffs.dtype
+        out = torch.empty(P, Q, L, dtype=T, device=dev)
+        first = _NONE
+        if Q > 0:
+            with torch.no_grad(), device_guard(dev):
+                if self._k is None:
+                    seg, x, first = self._search_host(tq)
+                    out.copy_(rowwise.HostRowKernels.quartic_quantiles(self.coeffs, seg, x, ks, Q, B))
+                else:
+                    status = torch.full((1,), _NONE, dtype=torch.int32, device=dev)
+                    seg, x = self._search_device(tq, status)
+                    on_dev = torch.tensor(ks, dtype=torch.int32, device=dev)
+                    per_time = self._k.row_dense_quantiles_workspace_bytes(P, 1, L, T)        # (linear in the times)
+                    step = min(Q, max(1, QUANTILES_WORKSPACE_BYTES // max(per_time, 1)))
+                    work = torch.empty(step * per_time, dtype=torch.uint8, device=dev)
+                    for q0 in range(0, Q, step):
+                        q1 = min(q0 + step, Q)
+                        part = out if q1 - q0 == Q else torch.empty(P, q1 - q0, L, dtype=T, device=dev)
+                        self._k.row_dense_quantiles(part, on_dev, self.coeffs, seg[q0 * B:q1 * B], x[q0 * B:q1 * B], work)
+                        if part is not out:
+                            out[:, q0:q1] = part
+                    if check:
+                        first = int(status)                                                    # the one read
+        if check:
+            self._raise_out_of_range(what, ("t",), tqs, [first])
+        out = out.view(P, Q, *self._shape[1:])
+        return out.select(1, 0) if single else out
+
 
 def odeint_rowwise_dense(func, y0, t0, t1, *, rtol=1e-7, atol=1e-9, method="dopri5", options=None, compact=None,
                          return_stats=False):
@@ -643,6 +724,15 @@ def odeint_rowwise_dense(func, y0, t0, t1, *, rtol=1e-7, atol=1e-9, method="dopr
     bits in either order of its ends, and an ascending and a descending solve of the same record give the same numbers.  A
     `jump_dy` dose at `p` flips the side at `p` with zero width for `lo <= p < hi`; `exposure(level, p, p)` is all zeros.  One
     launch after the two searches; nothing is built or cached.
+
+    Order statistics across rows: `dense.quantiles(t, probs)` or `dense.quantiles(t, ranks=...)` -> `[P, Q, *row_shape]`, per
+    time and ELEMENT the value of rank `k_p` among the B rows' `dense(t)` (`probs` by the "lower" rule `k = floor(p * (B - 1))`,
+    at most 16 ranks) — the percentile bands of a population, the envelope of an ensemble.  A most-significant-byte-first radix
+    select on the ordered integer image of the value (`-0.0` before `+0.0`, NaN last and canonical): the HIP kernels
+    (`tdeq_row_dense_quantiles`, ABI 36) evaluate the record again in each of `sizeof(dtype)` counting passes, with the
+    histograms in LDS, and never build `[Q, B, *row_shape]`; the counts are integers, so the answer depends neither on the grid
+    nor on the order of the rows, and the torch path of a CPU state has the same bits.  `check` as for `dense(t)`; with
+    `check=False` an out-of-range row is a NaN of its time's population.  A workspace of at most 256 MiB; nothing is cached.
 
     Returns `dense`; with `return_stats=True`, `(dense, stats)`: the stats of `odeint_rowwise` (`n_accepted`,
     `n_rejected`, `nfe`; with `compact` also `row_evals`, `n_repacks`) plus `n_segments` and `n_chunks`.
