@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define TDEQ_ABI_VERSION 36
+#define TDEQ_ABI_VERSION 37
 #define TDEQ_F32 0
 #define TDEQ_F64 1
 /* interleaved (re, im) complex states — accepted by the NORM entry points only (tdeq_error_norm, tdeq_error_norm_partial[_ctrl],
@@ -71,6 +71,8 @@ extern "C" {
 #define TDEQ_CHUNK_QUANTUM 1024
 #define TDEQ_ROW_QUANTILES_MAX_RANKS 16   /* tdeq_row_dense_quantiles */
 #define TDEQ_ROW_QUANTILES_SLAB_ROWS 1024  /* rows of one workgroup of its counting pass */
+#define TDEQ_ROW_MOMENTS_SLAB_ROWS 1024    /* tdeq_row_dense_moments: rows of one workgroup of its sum passes */
+#define TDEQ_ROW_MOMENTS_MAX_COV_LEN 1024  /* the longest row it takes with a covariance */
 
 #define TDEQ_EINVAL (-1)       /* bad argument (null pointer, n_terms out of range, bad dtype ...) */
 #define TDEQ_EWORKSPACE (-2)   /* workspace too small */
@@ -1026,6 +1028,51 @@ size_t tdeq_row_dense_quantiles_workspace_bytes(int n_ranks, int64_t n_q, int64_
 int tdeq_row_dense_quantiles(void* out, const int32_t* ranks, int n_ranks, const void* coeffs, int64_t n_seg,
                              const int32_t* seg, const void* x, int64_t n_q, int64_t n_rows, int64_t row_len, void* workspace,
                              size_t workspace_bytes, int dtype, void* stream);
+
+/*
+ * ---- Moments across rows (ABI 37; `RowDenseOutput.moments`) ----
+ * tdeq_row_dense_moments   for j < n_q and every element el of the row, over the POPULATION of time j = the rows r < n_rows
+ *                          with x[j * n_rows + r] == x[j * n_rows + r] (the search writes x = NaN for a query out of range)
+ *                          and the values v[r][el] tdeq_row_event_eval_mapped gives those queries, bit for bit, as doubles:
+ *                          count[j] = the rows of the population; mean[j, el] = sum_r v / count (NaN for count == 0);
+ *                          variance[j, el] = sum_r (v - mean)^2 / div with div = count - correction, and 0 where that is
+ *                          not positive (NaN or inf by IEEE division); with `covariance` not NULL also
+ *                          covariance[j, a, b] = sum_r (v[r][a] - mean[a]) (v[r][b] - mean[b]) / div, a, b < row_len.
+ *                          `count` int64 [n_q]; `mean`, `variance` double [n_q, row_len]; `covariance` double [n_q,
+ *                          row_len, row_len] or NULL; `correction` 0 or 1; `coeffs` [5, n_seg, row_len] of T; `seg` int32
+ *                          and `x` of T, both [n_q * n_rows]: what tdeq_row_dense_search wrote for tq [n_q, n_rows].
+ *                          Method.  Two passes in fp64, the mean first, then sums centred on the stored fp64 mean; every
+ *                                   pass evaluates the record again and nothing of size n_q * n_rows * row_len is written.
+ *                          Partition and merge order (the contract of run-to-run reproducibility; no floating-point
+ *                                   atomics).  Sums: the rows are split into slabs of TDEQ_ROW_MOMENTS_SLAB_ROWS, a single
+ *                                   slab included; a workgroup of 4 waves takes one time, 64 elements and one slab, a lane
+ *                                   adds the rows g, g + G, g + 2 G, .. of the slab in that order (g < G = 4 row groups, 16 /
+ *                                   8 in the 16-byte form of TDEQ_F32 / TDEQ_F64), the G sums of an element are added in the
+ *                                   order of g, the slabs in index order.  Covariance: v_mfma_f64_16x16x4_f64 on 64 x 64
+ *                                   blocks of pairs of 64-element tiles; slabs = min(ceil(n_rows / 1024), max(1, 1024 /
+ *                                   pairs)), pairs = tiles (tiles + 1) / 2, rows per slab rounded up to a multiple of 16 and
+ *                                   the slab count taken again from that; inside a slab the rows enter in index order, 4 per
+ *                                   matrix instruction; the slabs are added in index order.  Both splits are functions of
+ *                                   (n_rows, row_len) alone: slicing the times of a call changes no bit.  With `covariance`
+ *                                   the lower triangle is a copy of the upper and `variance` is its diagonal, bit for bit
+ *                                   (no centred sum pass runs).  5 launches (covariance: 4).
+ *                          `workspace`: 16-byte aligned device memory of at least
+ *                          tdeq_row_dense_moments_workspace_bytes(covariance != NULL, n_q, n_rows, row_len, dtype) =
+ *                          8 * n_q * (slabs * (1 + row_len) + (covariance ? gram_slabs * pairs * 4096 : 0)) bytes, rounded up
+ *                          to a multiple of 16 (0 for arguments the entry point refuses); its content before and after the
+ *                          call means nothing.
+ *                          16-byte loads when row_len is a multiple of 16 / sizeof(T) and `coeffs` is 16-byte aligned, scalar
+ *                          loads otherwise.  A NULL pointer (but `covariance`), a negative size, n_seg < 1, correction other
+ *                          than 0 or 1, n_q * n_rows >= INT32_MAX, n_q * ceil(row_len / 64) > INT32_MAX, row_len >
+ *                          TDEQ_ROW_MOMENTS_MAX_COV_LEN with a covariance, a workspace that is not 16-byte aligned, more
+ *                          than INT32_MAX workgroups in a pass, or a dtype other than TDEQ_F32 / TDEQ_F64: TDEQ_EINVAL
+ *                          before any launch.  workspace_bytes too small: TDEQ_EWORKSPACE.  n_q == 0, n_rows == 0 or
+ *                          row_len == 0: no-op.
+ */
+size_t tdeq_row_dense_moments_workspace_bytes(int covariance, int64_t n_q, int64_t n_rows, int64_t row_len, int dtype);
+int tdeq_row_dense_moments(int64_t* count, double* mean, double* variance, double* covariance_or_null, int correction,
+                           const void* coeffs, int64_t n_seg, const int32_t* seg, const void* x, int64_t n_q, int64_t n_rows,
+                           int64_t row_len, void* workspace, size_t workspace_bytes, int dtype, void* stream);
 
 /*
  * ---- Per-row step options (ABI 29; `min_step`, `max_step`, `step_t`, `jump_t` of the rowwise family) ----

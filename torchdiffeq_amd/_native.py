@@ -18,9 +18,11 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-TDEQ_ABI_VERSION = 36
+TDEQ_ABI_VERSION = 37
 TDEQ_ROW_QUANTILES_MAX_RANKS = 16       # include/tdeq_hip.h
 TDEQ_ROW_QUANTILES_SLAB_ROWS = 1024     # rows of one workgroup of the counting pass of tdeq_row_dense_quantiles
+TDEQ_ROW_MOMENTS_SLAB_ROWS = 1024       # rows of one workgroup of the sum passes of tdeq_row_dense_moments
+TDEQ_ROW_MOMENTS_MAX_COV_LEN = 1024     # the longest row tdeq_row_dense_moments takes with a covariance
 TDEQ_F32, TDEQ_F64 = 0, 1
 TDEQ_C64, TDEQ_C128 = 2, 3        # interleaved complex: the norm entry points only (include/tdeq_hip.h)
 TDEQ_BF16, TDEQ_F16 = 4, 5        # reduced-precision states: the entry points of the host-driven step (LowPrecisionHipKernels)
@@ -324,6 +326,13 @@ ABI_SIGNATURES = {
                                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
                                                 ctypes.c_int64, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int,
                                                 ctypes.c_void_p]),
+    # moments across rows (ABI 37, `RowDenseOutput.moments`)
+    "tdeq_row_dense_moments_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
+                                                                 ctypes.c_int]),
+    "tdeq_row_dense_moments": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+                                              ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
+                                              ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int,
+                                              ctypes.c_void_p]),
     # per-row step options (ABI 29, `min_step` / `max_step` / `step_t` / `jump_t` of the rowwise family)
     "tdeq_row_control_points": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(StepCtrl),
                                                ctypes.POINTER(RowState), ctypes.POINTER(RowPoints), ctypes.c_void_p,
@@ -1353,6 +1362,50 @@ class HipKernels:
                                                  seg.data_ptr(), x.data_ptr(), Q, n_idx // Q, L, workspace.data_ptr(),
                                                  workspace.numel(), dtype_code(out.dtype), self._stream()),
                "tdeq_row_dense_quantiles")
+
+    # -- moments across rows of the record (RowDenseOutput.moments) ----------------------------------------------------------
+    def row_dense_moments_workspace_bytes(self, covariance: bool, n_q: int, n_rows: int, row_len: int, dtype) -> int:
+        """tdeq_row_dense_moments_workspace_bytes: the workspace of `row_dense_moments` for that many query times and rows."""
+        return int(self.lib.tdeq_row_dense_moments_workspace_bytes(int(bool(covariance)), n_q, n_rows, row_len,
+                                                                   dtype_code(dtype)))
+
+    def row_dense_moments(self, count, mean, variance, covariance, correction: int, coeffs, seg, x, workspace) -> None:
+        """tdeq_row_dense_moments: per query time j the number of rows with x == x (`count` int64 [Q]), per element their
+        mean and variance (fp64 [Q, L], the variance divided by max(count - correction, 0)) and, unless `covariance` is None,
+        their covariance (fp64 [Q, L, L], L <= TDEQ_ROW_MOMENTS_MAX_COV_LEN), of the queries (seg[j * n_rows + r], x[j * n_rows
+        + r]) of `row_dense_search` on `coeffs` [5, n_seg, L].  `workspace`: a contiguous uint8 tensor of at least
+        `row_dense_moments_workspace_bytes(covariance is not None, Q, n_rows, L, dtype)` bytes."""
+        if mean.dim() != 2 or not mean.is_contiguous() or mean.dtype != torch.float64:
+            raise ValueError("row_dense_moments: mean must be a contiguous float64 [Q, L] tensor")
+        Q, L = mean.shape
+        if correction not in (0, 1) or isinstance(correction, bool):
+            raise ValueError(f"row_dense_moments: correction must be 0 or 1, got {correction!r}")
+        if covariance is not None and L > TDEQ_ROW_MOMENTS_MAX_COV_LEN:
+            raise ValueError(f"row_dense_moments: a covariance takes rows of at most {TDEQ_ROW_MOMENTS_MAX_COV_LEN} elements, "
+                             f"got {L}")
+        if Q == 0 or L == 0:
+            return
+        if coeffs.dim() != 3 or coeffs.shape[0] != 5 or coeffs.shape[1] < 1 or coeffs.shape[2] != L \
+                or coeffs.dtype not in (torch.float32, torch.float64) or not coeffs.is_contiguous():
+            raise ValueError("row_dense_moments: coeffs must be a contiguous float32 / float64 [5, n_seg >= 1, L] tensor")
+        n_idx = seg.numel()
+        if n_idx == 0 or n_idx % Q != 0:
+            raise ValueError(f"row_dense_moments: seg must hold n_rows >= 1 queries for each of the {Q} times")
+        checks = [("count", count, torch.int64, (Q,)), ("variance", variance, torch.float64, (Q, L)),
+                  ("seg", seg, torch.int32, (n_idx,)), ("x", x, coeffs.dtype, (n_idx,))]
+        if covariance is not None:
+            checks.append(("covariance", covariance, torch.float64, (Q, L, L)))
+        for name, t, dtype, shape in checks:
+            if tuple(t.shape) != shape or t.dtype != dtype or not t.is_contiguous():
+                raise ValueError(f"row_dense_moments: {name} must be a contiguous {dtype} {list(shape)} tensor")
+        if workspace.dtype != torch.uint8 or workspace.dim() != 1 or not workspace.is_contiguous():
+            raise ValueError("row_dense_moments: workspace must be a contiguous uint8 vector")
+        _check(self.lib.tdeq_row_dense_moments(count.data_ptr(), mean.data_ptr(), variance.data_ptr(),
+                                               None if covariance is None else covariance.data_ptr(), correction,
+                                               coeffs.data_ptr(), coeffs.shape[1], seg.data_ptr(), x.data_ptr(), Q, n_idx // Q,
+                                               L, workspace.data_ptr(), workspace.numel(), dtype_code(coeffs.dtype),
+                                               self._stream()),
+               "tdeq_row_dense_moments")
 
 
 class ComplexHipKernels:

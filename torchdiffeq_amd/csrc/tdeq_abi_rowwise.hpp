@@ -1154,3 +1154,118 @@ int tdeq_row_dense_quantiles(void* out, const int32_t* ranks, int n_ranks, const
         return row_dense_quant_launch<T>(a, aligned16(coeffs), s);
     });
 }
+
+// ---- moments across rows: tdeq_row_dense_moments --------------------------------------------------------------------------
+// Partition and merge order (tdeq_kernels_rowwise_dense.hpp, row_moments_split): sums in slabs of TDEQ_ROW_MOMENTS_SLAB_ROWS
+// rows, the Gram blocks in at most max(1, 1024 / pairs) slabs of whole 16-row chunks; inside a workgroup a fixed order through
+// LDS (sums) or the order of the rows (matrix instructions); the slabs in index order by the finish kernels.  No atomics.
+namespace {
+
+// the parts of the workspace, in bytes: the slabs' counts, the partial sums, the partial Gram blocks
+struct RowDenseMomSpace {
+    size_t counts, sums, gram;
+};
+
+inline RowDenseMomSpace row_dense_mom_space(bool covariance, int64_t n_q, const RowMomentsSplit& sp, int64_t row_len) {
+    return {(size_t)n_q * sp.slabs * sizeof(int64_t), (size_t)n_q * sp.slabs * row_len * sizeof(double),
+            covariance ? (size_t)n_q * sp.gram_slabs * sp.pairs * kMomBlock * sizeof(double) : 0};
+}
+
+// (n_q * n_rows < INT32_MAX and n_q * tiles <= INT32_MAX, tested without overflow: n_q * slabs * row_len * 8 < 2^62 and, with
+//  row_len <= 1024, n_q * gram_slabs * pairs * 32768 < 2^57 then fit a size_t)
+inline bool row_dense_mom_sizes_ok(bool covariance, int64_t n_q, int64_t n_rows, int64_t row_len, int dtype) {
+    if (n_q < 0 || n_rows < 0 || row_len < 0 || !real_dtype_ok(dtype)) return false;
+    if (n_q > 0x7fffffffLL || row_len > 0x7fffffffLL * kMomTile) return false;
+    if (covariance && row_len > TDEQ_ROW_MOMENTS_MAX_COV_LEN) return false;
+    if (n_rows > 0 && n_q > 0x7ffffffeLL / n_rows) return false;            // n_q * n_rows >= INT32_MAX
+    const int64_t tiles = (row_len + kMomTile - 1) / kMomTile;
+    return tiles == 0 || n_q <= 0x7fffffffLL / tiles;
+}
+
+template <typename T>
+int row_dense_mom_launch(RowDenseMomArgs<T> a, RowDenseMomFinishArgs f, const RowMomentsSplit& sp, const RowDenseMomSpace& w,
+                         double* variance, double* covariance, bool aligned, hipStream_t s) {
+    const int64_t sum_groups = a.n_q * sp.tiles * sp.slabs, gram_groups = a.n_q * sp.gram_slabs * sp.pairs;
+    if (sum_groups > 0x7fffffffLL || (covariance && gram_groups > 0x7fffffffLL)) return TDEQ_EINVAL;
+    double* const sums = a.partial;
+    int64_t unused;
+    return row_vec<T>(a.row_len, aligned, unused, [&](auto vec) {
+        constexpr bool VEC = decltype(vec)::value;
+        const dim3 block(kBlock), cells(stream_grid(a.n_q * a.row_len, kBlock));
+        a.slabs = f.slabs = sp.slabs;
+        a.slab_rows = kMomSlabRows;
+        hipLaunchKernelGGL((row_dense_moments_sum_kernel<T, VEC, false>), dim3((unsigned)sum_groups), block, 0, s, a);
+        hipLaunchKernelGGL(row_dense_moments_finish_kernel<false>, cells, block, 0, s, f);   // mean and count
+        if (covariance) {
+            a.partial = reinterpret_cast<double*>(reinterpret_cast<char*>(sums) + w.sums);
+            a.slabs = f.slabs = sp.gram_slabs;
+            a.slab_rows = sp.gram_rows;
+            f.partial = a.partial;
+            f.out = covariance;
+            f.variance = variance;
+            hipLaunchKernelGGL((row_dense_moments_gram_kernel<T, VEC>), dim3((unsigned)gram_groups), block, 0, s, a);
+            hipLaunchKernelGGL(row_dense_moments_gram_finish_kernel, dim3(stream_grid(a.n_q * sp.pairs * kMomBlock, kBlock)),
+                               block, 0, s, f);
+        } else {
+            f.out = variance;
+            hipLaunchKernelGGL((row_dense_moments_sum_kernel<T, VEC, true>), dim3((unsigned)sum_groups), block, 0, s, a);
+            hipLaunchKernelGGL(row_dense_moments_finish_kernel<true>, cells, block, 0, s, f);
+        }
+        return check_launch();
+    });
+}
+
+}  // namespace
+
+size_t tdeq_row_dense_moments_workspace_bytes(int covariance, int64_t n_q, int64_t n_rows, int64_t row_len, int dtype) {
+    if (!row_dense_mom_sizes_ok(covariance != 0, n_q, n_rows, row_len, dtype)) return 0;
+    const RowDenseMomSpace w = row_dense_mom_space(covariance != 0, n_q, row_moments_split(n_rows, row_len), row_len);
+    return (w.counts + w.sums + w.gram + 15) / 16 * 16;
+}
+
+int tdeq_row_dense_moments(int64_t* count, double* mean, double* variance, double* covariance_or_null, int correction,
+                           const void* coeffs, int64_t n_seg, const int32_t* seg, const void* x, int64_t n_q, int64_t n_rows,
+                           int64_t row_len, void* workspace, size_t workspace_bytes, int dtype, void* stream) {
+    const bool cov = covariance_or_null != nullptr;
+    if (!count || !mean || !variance || !coeffs || !seg || !x || !workspace ||
+        !row_dense_mom_sizes_ok(cov, n_q, n_rows, row_len, dtype))
+        return TDEQ_EINVAL;
+    if (n_seg < 1 || (correction != 0 && correction != 1) || !aligned16(workspace)) return TDEQ_EINVAL;
+    const RowMomentsSplit sp = row_moments_split(n_rows, row_len);
+    const RowDenseMomSpace w = row_dense_mom_space(cov, n_q, sp, row_len);
+    if (workspace_bytes < w.counts + w.sums + w.gram) return TDEQ_EWORKSPACE;
+    if (n_q == 0 || n_rows == 0 || row_len == 0) return 0;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return real_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        RowDenseMomArgs<T> a;
+        a.q = static_cast<const T*>(coeffs);
+        a.seg = seg;
+        a.x = static_cast<const T*>(x);
+        a.mean = mean;
+        a.slab_count = static_cast<int64_t*>(workspace);
+        a.partial = reinterpret_cast<double*>(static_cast<char*>(workspace) + w.counts);
+        a.n_rows = n_rows;
+        a.n_seg = n_seg;
+        a.row_len = row_len;
+        a.q_plane = n_seg * row_len;
+        a.n_q = n_q;
+        a.tiles = sp.tiles;
+        a.pairs = sp.pairs;
+        a.slabs = sp.slabs;
+        a.slab_rows = kMomSlabRows;
+        RowDenseMomFinishArgs f;
+        f.partial = a.partial;
+        f.slab_count = a.slab_count;
+        f.count = count;
+        f.out = mean;
+        f.variance = variance;
+        f.n_q = n_q;
+        f.row_len = row_len;
+        f.tiles = sp.tiles;
+        f.pairs = sp.pairs;
+        f.slabs = sp.slabs;
+        f.correction = correction;
+        return row_dense_mom_launch<T>(a, f, sp, w, variance, covariance_or_null, aligned16(coeffs), s);
+    });
+}

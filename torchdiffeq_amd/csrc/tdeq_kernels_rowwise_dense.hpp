@@ -975,4 +975,326 @@ __global__ __launch_bounds__(kBlock) void row_dense_quant_select_kernel(const Ro
     }
 }
 
+// ---- moments across rows (ABI 37): count, mean, variance and covariance of the B rows, per query time -------------------
+// The POPULATION of a time is the set of rows whose query is in range (x == x; the search writes x = NaN otherwise).  Two
+// passes, the mean first and then centred sums, all in fp64; nothing of size [n_q, n_rows, L] is written: every pass
+// evaluates the quartics again (quant_value: eval_one, the bits of row_event_eval_mapped).  No floating-point atomics: the
+// rows are split into slabs by a rule of (n_rows, row_len) alone, a workgroup adds its slab in a fixed order and stores a
+// partial, and a finish kernel adds the partials in slab order.  So a result is reproducible from run to run and does not
+// depend on n_q (the times may be sliced); it is NOT the host path's bit for bit (another summation order).
+//   row_dense_moments_sum      the work split of row_dense_quant_count: a workgroup owns one time, one tile of 64 contiguous
+//                              elements and one slab of kMomSlabRows rows; its four waves take different rows, the lanes run
+//                              along the tile (16-byte form: a lane holds LV neighbouring elements, the wave covers LV rows
+//                              per step).  A lane adds double(v), or (double(v) - mean)^2 when CENTRED, in row order; the 4 *
+//                              LV per-lane sums of a column are then added through LDS in the order (wave, row group).  The
+//                              workgroup of tile 0 also stores the number of rows of its slab that took part.
+//   row_dense_moments_finish   one lane per (time, element): partials added in slab order, divided by count (the mean; the
+//                              lane of element 0 also stores count) or by max(count - correction, 0) (the variance).
+//   row_dense_moments_gram     the covariance as a Gram matrix of deviations on v_mfma_f64_16x16x4_f64.  A workgroup owns
+//                              one time, one slab of rows and one pair (I, J), I <= J, of 64-element tiles: a 64 x 64 block
+//                              of sum_r dev[r][i] dev[r][j].  It walks the slab in chunks of kMomChunk = 16 rows: all 256
+//                              threads evaluate the chunk's 16 x 64 values of tile I (and of tile J when J != I) with
+//                              coalesced plane loads, subtract the fp64 mean and write the deviations to an LDS stage — zero
+//                              for a row outside the population or past the slab's end and for an element >= L.  The stage
+//                              is double-buffered: the loads and the arithmetic of chunk c + 1 are issued before the matrix
+//                              work on chunk c, one barrier per chunk.  Wave w owns rows 16 w .. 16 w + 15 of the block and
+//                              all 64 columns: four 16 x 16 accumulators, 16 doubles per lane; per chunk 4 k-steps of one A
+//                              fragment, four B fragments and four matrix instructions.  Operands: lane l supplies A[i = l %
+//                              16][k = l / 16] and B[k = l / 16][j = l % 16], so it reads dev[k0 + l / 16][i0 + l % 16], and
+//                              holds D[4 v + l / 16][l % 16], v < 4.  The stage's row stride is kMomStride = 80 doubles: the 16
+//                              consecutive doubles a row of the fragment reads cover 32 four-byte banks, and 80 doubles = 160
+//                              words = 32 mod 64, so two neighbouring rows k and k + 1 — one half-wave of an 8-byte read —
+//                              cover all 64 banks once; a stride of 64 would put all four rows on the same 32 banks.  The
+//                              block is stored to partial[time, slab, pair] with plain vector stores.
+//   row_dense_moments_gram_finish   one lane per (time, pair, i, j) of the upper triangle: blocks added in slab order, divided
+//                              by max(count - correction, 0), stored to out[i][j] and its mirror out[j][i]; the diagonal
+//                              is also the variance, bit for bit.
+// The evaluating kernels carry TDEQ_NO_PACKED_FP32 for the reason given at the counting kernel, clamp seg as it does, use
+// 64-bit offsets and no scratch.
+constexpr int kMomTile = 64;
+constexpr int kMomSlabRows = TDEQ_ROW_MOMENTS_SLAB_ROWS;
+constexpr int kMomChunk = 16;                                         // rows of one stage of the Gram kernel: 4 k-steps
+constexpr int kMomStride = kMomTile + 16;                             // doubles between two rows of the stage (see above)
+constexpr int kMomBlock = kMomTile * kMomTile;                        // doubles of one block of the Gram matrix
+static_assert(kMomTile == kWave && kBlock == 4 * kWave && kMomSlabRows % kMomChunk == 0, "four waves of 16 block rows each");
+
+// THE slab rule, a function of (n_rows, row_len) only.  Sums: slabs of kMomSlabRows rows, a single slab included.  Gram: at
+// most max(1, 1024 / pairs) slabs, so that the partial blocks of a time stay near 1024 * 32 KB; whole chunks per slab.
+struct RowMomentsSplit {
+    int64_t tiles, pairs;             // ceil(L / 64); tiles (tiles + 1) / 2
+    int64_t slabs;                    // of the sum kernels
+    int64_t gram_slabs, gram_rows;    // of the Gram kernel: slabs and rows per slab
+};
+
+inline RowMomentsSplit row_moments_split(int64_t n_rows, int64_t row_len) {
+    RowMomentsSplit s;
+    s.tiles = (row_len + kMomTile - 1) / kMomTile;
+    s.pairs = s.tiles * (s.tiles + 1) / 2;
+    s.slabs = (n_rows + kMomSlabRows - 1) / kMomSlabRows;
+    const int64_t cap = s.pairs > 0 && 1024 / s.pairs > 1 ? 1024 / s.pairs : 1;
+    const int64_t want = s.slabs < cap ? (s.slabs > 0 ? s.slabs : 1) : cap;
+    s.gram_rows = ((n_rows + want - 1) / want + kMomChunk - 1) / kMomChunk * kMomChunk;
+    s.gram_slabs = s.gram_rows > 0 ? (n_rows + s.gram_rows - 1) / s.gram_rows : 0;
+    return s;
+}
+
+template <typename T>
+struct RowDenseMomArgs {
+    const T* q;                       // [5, n_seg, L]
+    const int32_t* seg;               // [n_q * n_rows]
+    const T* x;                       // [n_q * n_rows]
+    const double* mean;               // [n_q, L] (the centred sums and the Gram kernel)
+    double* partial;                  // sums: [n_q, slabs, L]; Gram: [n_q, gram_slabs, pairs, 64, 64]
+    int64_t* slab_count;              // [n_q, slabs] rows of the slab that took part
+    int64_t n_rows;
+    int64_t n_seg;
+    int64_t row_len;                  // T units
+    int64_t q_plane;                  // n_seg * L
+    int64_t n_q;
+    int64_t tiles;
+    int64_t pairs;
+    int64_t slabs;                    // of THIS launch (sums: slabs, Gram: gram_slabs)
+    int64_t slab_rows;                // of THIS launch
+};
+
+struct RowDenseMomFinishArgs {
+    const double* partial;            // as above
+    const int64_t* slab_count;        // [n_q, slabs] (the mean)
+    int64_t* count;                   // [n_q] written with the mean, read afterwards
+    double* out;                      // mean / variance [n_q, L]; covariance [n_q, L, L]
+    double* variance;                 // [n_q, L] (the Gram finish: the diagonal)
+    int64_t n_q;
+    int64_t row_len;
+    int64_t tiles;
+    int64_t pairs;
+    int64_t slabs;
+    int32_t correction;
+};
+
+template <typename T, bool VEC, bool CENTRED>
+__global__ __launch_bounds__(kBlock) TDEQ_NO_PACKED_FP32 void row_dense_moments_sum_kernel(const RowDenseMomArgs<T> a) {
+    using E = typename std::conditional<VEC, typename VecOf<T>::type, T>::type;
+    constexpr int LV = VEC ? VecOf<T>::L : 1;                         // elements per lane = rows per wave step
+    constexpr int kLanesPerRow = kMomTile / LV;
+    constexpr int kGroups = (kBlock / kWave) * LV;                    // per-lane sums of one column
+    __shared__ double red[kGroups * kMomTile];
+    __shared__ int32_t cnt[kGroups];
+
+    int64_t b = blockIdx.x;
+    const int64_t slab = b % a.slabs;
+    b /= a.slabs;
+    const int64_t tile = b % a.tiles;
+    const int64_t q = b / a.tiles;
+    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+    const int col = (lane % kLanesPerRow) * LV;                       // the lane's first element inside the tile
+    const int group = wave * LV + lane / kLanesPerRow;
+    const int64_t el = tile * kMomTile + col;
+
+    double acc[LV], mean[LV];
+    int32_t n = 0;
+#pragma unroll
+    for (int c = 0; c < LV; ++c) acc[c] = 0.0, mean[c] = 0.0;
+    if (el < a.row_len) {                                             // (VEC: L is a whole number of lanes' elements)
+        if constexpr (CENTRED) {
+#pragma unroll
+            for (int c = 0; c < LV; ++c) mean[c] = a.mean[q * a.row_len + el + c];
+        }
+        const int64_t r_end = (slab + 1) * a.slab_rows < a.n_rows ? (slab + 1) * a.slab_rows : a.n_rows;
+        for (int64_t r = slab * a.slab_rows + group; r < r_end; r += kGroups) {
+            const int64_t i = q * a.n_rows + r;
+            const T x = a.x[i];
+            if (x != x) continue;                                     // the row has left this time's population
+            int64_t s = a.seg[i];
+            s = s < 0 ? 0 : (s < a.n_seg ? s : a.n_seg - 1);          // (the search writes 0 <= seg < n_seg)
+            T qe[LV], qd[LV], qc[LV], qb[LV], qa[LV];
+            load_planes<T, E, LV>(a.q, a.q_plane, (s * a.row_len + el) / LV, qe, qd, qc, qb, qa);
+            ++n;
+#pragma unroll
+            for (int c = 0; c < LV; ++c) {
+                const double v = (double)quant_value<T>(qe[c], qd[c], qc[c], qb[c], qa[c], x);
+                if constexpr (CENTRED) {
+                    const double d = v - mean[c];
+                    acc[c] = acc[c] + d * d;
+                } else {
+                    acc[c] = acc[c] + v;
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < LV; ++c) red[group * kMomTile + col + c] = acc[c];
+    if (col == 0) cnt[group] = n;                                     // (element 0 of a tile exists in tile 0)
+    __syncthreads();
+    if (threadIdx.x < kMomTile && tile * kMomTile + threadIdx.x < a.row_len) {
+        double total = red[threadIdx.x];
+        for (int g = 1; g < kGroups; ++g) total = total + red[g * kMomTile + threadIdx.x];
+        a.partial[(q * a.slabs + slab) * a.row_len + tile * kMomTile + threadIdx.x] = total;
+    }
+    if (!CENTRED && tile == 0 && threadIdx.x == 0) {
+        int64_t total = 0;
+        for (int g = 0; g < kGroups; ++g) total += cnt[g];
+        a.slab_count[q * a.slabs + slab] = total;
+    }
+}
+
+// the divisor of the centred sums: count - correction, and 0 (NaN or inf by IEEE division) where that is not positive
+__device__ __forceinline__ double moments_divisor(int64_t count, int32_t correction) {
+    return count > correction ? (double)(count - correction) : 0.0;
+}
+
+template <bool CENTRED>
+__global__ __launch_bounds__(kBlock) void row_dense_moments_finish_kernel(const RowDenseMomFinishArgs a) {
+    const int64_t n = a.n_q * a.row_len, stride = (int64_t)gridDim.x * kBlock;
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
+        const int64_t q = i / a.row_len, el = i - q * a.row_len;
+        double total = 0.0;
+        for (int64_t s = 0; s < a.slabs; ++s) total = total + a.partial[(q * a.slabs + s) * a.row_len + el];
+        if constexpr (CENTRED) {
+            a.out[i] = total / moments_divisor(a.count[q], a.correction);
+        } else {
+            int64_t count = 0;
+            for (int64_t s = 0; s < a.slabs; ++s) count += a.slab_count[q * a.slabs + s];
+            a.out[i] = total / (double)count;
+            if (el == 0) a.count[q] = count;
+        }
+    }
+}
+
+typedef double mom_f64x4 __attribute__((ext_vector_type(4)));
+
+// D += A B of v_mfma_f64_16x16x4_f64 (the host pass does not know the builtin and never calls this)
+__device__ __forceinline__ mom_f64x4 moments_mfma(double a, double b, mom_f64x4 d) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, d, 0, 0, 0);
+#else
+    return d;
+#endif
+}
+
+template <typename T, bool VEC>
+__global__ __launch_bounds__(kBlock) TDEQ_NO_PACKED_FP32 void row_dense_moments_gram_kernel(const RowDenseMomArgs<T> a) {
+    using E = typename std::conditional<VEC, typename VecOf<T>::type, T>::type;
+    constexpr int LV = VEC ? VecOf<T>::L : 1;
+    constexpr int kLanesPerRow = kMomTile / LV;
+    constexpr int kRowsPerStep = kBlock / kLanesPerRow;               // rows of the chunk the 256 threads cover at once
+    constexpr int kSteps = kMomChunk / kRowsPerStep;                  // 4 (scalar), 1 (fp32 16-byte), 2 (fp64 16-byte)
+    static_assert(kSteps * kRowsPerStep == kMomChunk, "a chunk is whole steps");
+    __shared__ double stage[2][2][kMomChunk * kMomStride];            // [buffer][tile I, tile J][row][element], 40 KB
+
+    int64_t b = blockIdx.x;
+    const int64_t pair = b % a.pairs;
+    b /= a.pairs;
+    const int64_t slab = b % a.slabs;
+    const int64_t q = b / a.slabs;
+    int64_t I = 0, J = pair;                                          // pairs in the order (0,0) (0,1) .. (1,1) (1,2) ..
+    while (J >= a.tiles - I) {
+        J -= a.tiles - I;
+        ++I;
+    }
+    J += I;
+    const int n_t = I == J ? 1 : 2;                                   // tiles to stage
+    const int col = ((int)threadIdx.x % kLanesPerRow) * LV, row0 = (int)threadIdx.x / kLanesPerRow;
+    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+
+    int64_t el[2];
+    double mean[2][LV];
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+        el[t] = (t == 0 ? I : J) * kMomTile + col;
+#pragma unroll
+        for (int c = 0; c < LV; ++c) mean[t][c] = el[t] < a.row_len ? a.mean[q * a.row_len + el[t] + c] : 0.0;
+    }
+    const int64_t r_begin = slab * a.slab_rows;
+    const int64_t r_end = r_begin + a.slab_rows < a.n_rows ? r_begin + a.slab_rows : a.n_rows;
+    const int64_t n_chunks = (r_end - r_begin + kMomChunk - 1) / kMomChunk;
+
+    double dev[2][kSteps][LV];
+    // the deviations of chunk c of the thread's cells, in registers
+    auto evaluate = [&](int64_t c) __attribute__((always_inline)) {
+#pragma unroll
+        for (int k = 0; k < kSteps; ++k) {
+            const int64_t r = r_begin + c * kMomChunk + k * kRowsPerStep + row0;
+            const bool row_ok = r < r_end;
+            const int64_t i = q * a.n_rows + (row_ok ? r : r_begin);  // (r_begin < n_rows: the slab is not empty)
+            const T x = a.x[i];
+            int64_t s = a.seg[i];
+            s = s < 0 ? 0 : (s < a.n_seg ? s : a.n_seg - 1);
+            const bool in = row_ok && x == x;
+#pragma unroll
+            for (int t = 0; t < 2; ++t) {
+#pragma unroll
+                for (int cc = 0; cc < LV; ++cc) dev[t][k][cc] = 0.0;
+                if (t < n_t && in && el[t] < a.row_len) {
+                    T qe[LV], qd[LV], qc[LV], qb[LV], qa[LV];
+                    load_planes<T, E, LV>(a.q, a.q_plane, (s * a.row_len + el[t]) / LV, qe, qd, qc, qb, qa);
+#pragma unroll
+                    for (int cc = 0; cc < LV; ++cc)
+                        dev[t][k][cc] = (double)quant_value<T>(qe[cc], qd[cc], qc[cc], qb[cc], qa[cc], x) - mean[t][cc];
+                }
+            }
+        }
+    };
+    auto publish = [&](int buf) __attribute__((always_inline)) {
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+            if (t >= n_t) continue;
+#pragma unroll
+            for (int k = 0; k < kSteps; ++k) {
+#pragma unroll
+                for (int cc = 0; cc < LV; ++cc) stage[buf][t][(k * kRowsPerStep + row0) * kMomStride + col + cc] = dev[t][k][cc];
+            }
+        }
+    };
+
+    mom_f64x4 acc[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[j] = mom_f64x4{0.0, 0.0, 0.0, 0.0};
+    if (n_chunks > 0) {
+        evaluate(0);
+        publish(0);
+    }
+    __syncthreads();
+    for (int64_t c = 0; c < n_chunks; ++c) {
+        const int buf = (int)(c & 1);
+        if (c + 1 < n_chunks) evaluate(c + 1);                        // its loads are in flight during the matrix work
+        const double* const sa = stage[buf][0] + (lane / 16) * kMomStride + wave * 16 + lane % 16;
+        const double* const sb = stage[buf][n_t - 1] + (lane / 16) * kMomStride + lane % 16;
+#pragma unroll
+        for (int k0 = 0; k0 < kMomChunk; k0 += 4) {
+            const double fa = sa[k0 * kMomStride];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc[j] = moments_mfma(fa, sb[k0 * kMomStride + 16 * j], acc[j]);
+        }
+        if (c + 1 < n_chunks) publish(buf ^ 1);                       // (last read before the barrier of chunk c - 1)
+        __syncthreads();
+    }
+    double* const g = a.partial + ((q * a.slabs + slab) * a.pairs + pair) * kMomBlock;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+#pragma unroll
+        for (int v = 0; v < 4; ++v) g[(wave * 16 + 4 * v + lane / 16) * kMomTile + 16 * j + lane % 16] = acc[j][v];
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void row_dense_moments_gram_finish_kernel(const RowDenseMomFinishArgs a) {
+    const int64_t n = a.n_q * a.pairs * kMomBlock, stride = (int64_t)gridDim.x * kBlock;
+    for (int64_t at = (int64_t)blockIdx.x * kBlock + threadIdx.x; at < n; at += stride) {
+        const int64_t cell = at % kMomBlock, pair = at / kMomBlock % a.pairs, q = at / kMomBlock / a.pairs;
+        int64_t I = 0, J = pair;
+        while (J >= a.tiles - I) {
+            J -= a.tiles - I;
+            ++I;
+        }
+        J += I;
+        const int64_t i = I * kMomTile + cell / kMomTile, j = J * kMomTile + cell % kMomTile;
+        if (i > j || j >= a.row_len) continue;                        // (i <= j < L; the lower triangle is the mirror)
+        double total = 0.0;
+        for (int64_t s = 0; s < a.slabs; ++s) total = total + a.partial[((q * a.slabs + s) * a.pairs + pair) * kMomBlock + cell];
+        const double v = total / moments_divisor(a.count[q], a.correction);
+        a.out[(q * a.row_len + i) * a.row_len + j] = v;
+        a.out[(q * a.row_len + j) * a.row_len + i] = v;
+        if (i == j) a.variance[q * a.row_len + i] = v;
+    }
+}
+
 }  // namespace tdeq

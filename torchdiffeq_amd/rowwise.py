@@ -876,6 +876,26 @@ class HostRowKernels:
         back = torch.where(picked < 0, picked ^ top, picked).view(v.dtype)
         return torch.where(picked == top, torch.full_like(back, float("nan")), back)
 
+    @staticmethod
+    def quartic_moments(q, src, x, Q: int, B: int, covariance: bool, correction: int):
+        """Count, mean, variance and (or None) covariance across the rows of each of the Q query times that are in range (`x
+        == x`): the queries (src, x) [Q * B] of the search on the record `q` [5, n_seg, L] -> (int64 [Q], fp64 [Q, L], fp64
+        [Q, L], fp64 [Q, L, L] or None).  The definition of tdeq_row_dense_moments in plain fp64 torch ops: `eval_quartics`,
+        the mean, then sums centred on it, divided by `max(count - correction, 0)`; the covariance is `dev.T @ dev` per time
+        with the lower triangle copied from the upper, and the variance is then its diagonal.  The order of the sums is
+        torch's, not the kernels': the same error bound, other last bits."""
+        v = HostRowKernels.eval_quartics(q, src, x).view(Q, B, -1).double()
+        took_part = (x == x).view(Q, B, 1)
+        count = took_part.sum(dim=(1, 2))
+        mean = torch.where(took_part, v, torch.zeros_like(v)).sum(dim=1) / count.double()[:, None]
+        dev = torch.where(took_part, v - mean[:, None, :], torch.zeros_like(v))
+        div = (count - correction).clamp_min(0).double()
+        if not covariance:
+            return count, mean, (dev * dev).sum(dim=1) / div[:, None], None
+        upper = torch.triu(dev.transpose(1, 2) @ dev / div[:, None, None])
+        cov = upper + torch.triu(upper, 1).transpose(1, 2)
+        return count, mean, torch.diagonal(cov, dim1=1, dim2=2).clone(), cov
+
     # -- calculus on a dense record (rowwise_dense.py; the arithmetic of tdeq_row_dense_prefix / tdeq_row_dense_calc) -----
     @staticmethod
     def _quartic_integral(e, d, c, b, a, x, h):

@@ -22,8 +22,10 @@ above it are the same two searches followed by `tdeq_row_dense_level`, the same 
 the record and a level, above and below it, is the same again with `tdeq_row_dense_exposure`, which integrates `y - level`
 piece by piece while it walks; the times of ALL crossings, by direction, are the same walk with `tdeq_row_dense_level_times`,
 which stores every located time at once; the order statistics across rows are one search followed by
-`tdeq_row_dense_quantiles`, a radix select that evaluates the record in every pass.  CPU states run the same steps as torch /
-numpy ops.
+`tdeq_row_dense_quantiles`, a radix select that evaluates the record in every pass; the mean, variance and covariance across
+rows are one search followed by `tdeq_row_dense_moments`, two passes of fp64 sums over slabs of rows merged in a fixed order,
+the covariance as a Gram matrix of deviations on the fp64 matrix instructions.  CPU states run the same steps as torch / numpy
+ops.
 """
 from __future__ import annotations
 
@@ -35,17 +37,18 @@ import numpy as np
 import torch
 
 from . import rowwise
-from ._native import TDEQ_ROW_QUANTILES_MAX_RANKS, device_guard
+from ._native import TDEQ_ROW_MOMENTS_MAX_COV_LEN, TDEQ_ROW_QUANTILES_MAX_RANKS, device_guard
 from .rowwise import _Problem
 
 __all__ = ["odeint_rowwise_dense", "RowDenseOutput", "RowDenseExtremum", "RowDenseCrossings", "RowDenseCrossingTimes",
-           "RowDenseExposure"]
+           "RowDenseExposure", "RowDenseMoments"]
 
 # the default chunk: CHUNK_ROWS_PER_ROW slots per row of the batch, at most CHUNK_BYTES of coefficients, never fewer than B
 CHUNK_ROWS_PER_ROW = 4
 CHUNK_BYTES = 256 << 20
 QUANTILES_WORKSPACE_BYTES = 256 << 20                        # `quantiles` slices its query times to keep its workspace below
-_NONE = 0x7FFFFFFF                                           # the search's status word: no query out of range
+MOMENTS_WORKSPACE_BYTES = 256 << 20                          # and so does `moments`
+_NONE = 0x7FFFFFFF                                          # the search's status word: no query out of range
 
 
 def _dense_time(name: str, v, B: int) -> torch.Tensor:
@@ -208,13 +211,24 @@ class RowDenseExposure(NamedTuple):
     time_above: torch.Tensor
 
 
+class RowDenseMoments(NamedTuple):
+    """`RowDenseOutput.moments`: per time the number of rows that took part (int64 `[Q]`), per element their mean and their
+    variance (fp64 `[Q, *row_shape]`) and, with `covariance=True`, the covariance between the elements of the row (fp64 `[Q,
+    L, L]`, exactly symmetric, its diagonal is `variance`), else None."""
+    count: torch.Tensor
+    mean: torch.Tensor
+    variance: torch.Tensor
+    covariance: torch.Tensor | None
+
+
 class RowDenseOutput:
     """The piecewise quartic of a rowwise solve; `dense(t)` evaluates it, `derivative(t)`, `antiderivative(t)` and
     `integral(ta, tb)` give its time derivative and its integrals in closed form, `maximum(ta, tb)` and `minimum(ta, tb)` its
     extrema over a time window and their times, `crossings(level, ta, tb)` and `time_above(level, ta, tb)` its crossings of a
     level and the time spent above it, `crossing_times(level, ta, tb, max_count)` the times of all its crossings by direction,
     `exposure(level, ta, tb)`, `area_above(level, ta, tb)` and `area_below(level, ta, tb)` the area between it and a level,
-    `quantiles(t, probs)` its order statistics across the rows (see `odeint_rowwise_dense`).
+    `quantiles(t, probs)` its order statistics across the rows, `moments(t)` their mean, variance and covariance (see
+    `odeint_rowwise_dense`).
 
     Attributes (the wire format, all on the state's device): `t0`, `t1` `[B]` fp64 in true time; `offsets` `[B + 1]` int64;
     `seg_start`, `seg_end` `[n_seg]` fp64 in true time, row r's segments — its accepted steps — contiguous and in step
@@ -584,8 +598,8 @@ class RowDenseOutput:
         evaluates the record again in each of its `sizeof(dtype)` passes and never builds the `[Q, B, *row_shape]` values: next
         to the outputs the call allocates the search's `[Q, B]` lists and a workspace of at most 256 MiB (or that of one
         query time), and runs the times in slices that fit it.  A CPU state sorts the same integer keys with torch ops: the
-        same bits.  Counts are integers, so the result does not depend on the order of the rows.  Row subsets, weights, means
-        and gradients are out of scope."""
+        same bits.  Counts are integers, so the result does not depend on the order of the rows.  Means, variances and
+        covariances across the rows are `moments(t)`; row subsets, weights and gradients are out of scope."""
         what = "dense.quantiles(t)"
         ks = self._quantile_ranks(what, probs, ranks)
         tqs, single = self._query_lists(what, ("t",), (t,))
@@ -620,6 +634,74 @@ class RowDenseOutput:
             self._raise_out_of_range(what, ("t",), tqs, [first])
         out = out.view(P, Q, *self._shape[1:])
         return out.select(1, 0) if single else out
+
+    # -- moments across rows: two passes over the record in fp64, nothing of size [Q, B, L] is built ---------------------------
+    def moments(self, t, *, covariance: bool = False, correction: int = 1, check: bool = True) -> RowDenseMoments:
+        """Mean, variance and covariance ACROSS the rows, per time: the ensemble mean ± SD of a population of solves and the
+        covariance between its state components -> `RowDenseMoments(count, mean, variance, covariance)`, all fp64 for both
+        state dtypes (`count` int64), without the `Q` dimension for a single time.  `t` takes the query forms of `dense(t)`.
+        The POPULATION of a time is the set of rows whose query is in range: `check=True` raises for the first out-of-range
+        query like `dense(t)`, after one read of the status word; with `check=False` nothing is read and an out-of-range row
+        has left that time's population.  `count` `[Q]`: the rows that took part.  `mean` `[Q, *row_shape]`: the fp64 sum of
+        their `dense(t)` values over `count` (NaN for `count == 0`).  `variance` `[Q, *row_shape]`: the fp64 sum of `(y -
+        mean)^2`, with that fp64 mean, over `count - correction` (`correction` is the int 0 or 1) — two passes, never `E[x^2] -
+        E[x]^2`; a divisor that is not positive counts as zero, so a population too small gives NaN (or inf) by IEEE
+        division.  `covariance=True` also gives `covariance` `[Q, L, L]`, `L = prod(row_shape) <= 1024`: the sum of `(y_i -
+        mean_i) (y_j - mean_j)` over the same divisor, exactly symmetric (the lower triangle is a copy of the upper), and
+        `variance` is then its diagonal bit for bit; otherwise `covariance` is None.  A non-finite value inside the record
+        propagates by IEEE rules.  A ROCm state runs HIP kernels (`tdeq_row_dense_moments`, ABI 37) that evaluate the record
+        again in each pass and never build the `[Q, B, *row_shape]` values; the covariance is a Gram matrix of deviations on
+        the fp64 matrix instructions.  Next to the outputs the call allocates the search's `[Q, B]` lists and a workspace of
+        at most 256 MiB (or that of one query time), and runs the times in slices that fit it; the rows are split by a rule of
+        `(B, L)` alone and merged in a fixed order without atomics, so the result is the same from run to run and does not
+        depend on the slicing.  A CPU state runs the same definition as plain torch ops in fp64: the same error bound, not the
+        same last bits (another order of the sums).  Weights, row subsets, higher moments, correlation matrices (divide by the
+        SDs), cross-time covariance and gradients are out of scope."""
+        what = "dense.moments(t)"
+        if isinstance(correction, bool) or not isinstance(correction, int) or correction not in (0, 1):
+            raise ValueError(f"{what}: correction must be the int 0 or 1, got {correction!r}")
+        if not isinstance(covariance, bool):
+            raise ValueError(f"{what}: covariance must be a bool, got {covariance!r}")
+        L, dev, T = self.coeffs.shape[2], self.coeffs.device, self.coeffs.dtype
+        if covariance and L > TDEQ_ROW_MOMENTS_MAX_COV_LEN:
+            raise ValueError(f"{what}: covariance=True takes rows of at most {TDEQ_ROW_MOMENTS_MAX_COV_LEN} elements, this "
+                             f"row has {L}")
+        tqs, single = self._query_lists(what, ("t",), (t,))
+        tq = tqs[0]
+        Q, B = tq.shape
+        if self._k is not None and Q * B >= _NONE:
+            raise ValueError(f"{what}: {Q * B} queries in one call; the query index is a 32-bit word")
+        count = torch.empty(Q, dtype=torch.int64, device=dev)
+        mean, var = (torch.empty(Q, L, dtype=torch.float64, device=dev) for _ in range(2))
+        cov = torch.empty(Q, L, L, dtype=torch.float64, device=dev) if covariance else None
+        first = _NONE
+        if Q > 0:
+            with torch.no_grad(), device_guard(dev):
+                if self._k is None:
+                    seg, x, first = self._search_host(tq)
+                    got = rowwise.HostRowKernels.quartic_moments(self.coeffs, seg, x, Q, B, covariance, correction)
+                    for dst, src in zip((count, mean, var, cov), got):
+                        if dst is not None:
+                            dst.copy_(src)
+                else:
+                    status = torch.full((1,), _NONE, dtype=torch.int32, device=dev)
+                    seg, x = self._search_device(tq, status)
+                    per_time = self._k.row_dense_moments_workspace_bytes(covariance, 1, B, L, T)    # (linear in the times)
+                    step = min(Q, max(1, MOMENTS_WORKSPACE_BYTES // max(per_time, 1)))
+                    work = torch.empty(self._k.row_dense_moments_workspace_bytes(covariance, step, B, L, T), dtype=torch.uint8,
+                                       device=dev)
+                    for q0 in range(0, Q, step):
+                        q1 = min(q0 + step, Q)
+                        self._k.row_dense_moments(count[q0:q1], mean[q0:q1], var[q0:q1], None if cov is None else cov[q0:q1],
+                                                  correction, self.coeffs, seg[q0 * B:q1 * B], x[q0 * B:q1 * B], work)
+                    if check:
+                        first = int(status)                                                    # the one read
+        if check:
+            self._raise_out_of_range(what, ("t",), tqs, [first])
+        mean, var = (v.view(Q, *self._shape[1:]) for v in (mean, var))
+        if single:
+            return RowDenseMoments(count[0], mean[0], var[0], None if cov is None else cov[0])
+        return RowDenseMoments(count, mean, var, cov)
 
 
 def odeint_rowwise_dense(func, y0, t0, t1, *, rtol=1e-7, atol=1e-9, method="dopri5", options=None, compact=None,
@@ -733,6 +815,17 @@ def odeint_rowwise_dense(func, y0, t0, t1, *, rtol=1e-7, atol=1e-9, method="dopr
     histograms in LDS, and never build `[Q, B, *row_shape]`; the counts are integers, so the answer depends neither on the grid
     nor on the order of the rows, and the torch path of a CPU state has the same bits.  `check` as for `dense(t)`; with
     `check=False` an out-of-range row is a NaN of its time's population.  A workspace of at most 256 MiB; nothing is cached.
+
+    Moments across rows: `dense.moments(t, covariance=False, correction=1)` -> `RowDenseMoments(count, mean, variance,
+    covariance)`, per time the number of rows in range, per element their mean and variance and, on request, the `[L, L]`
+    covariance between the elements (`L <= 1024`) — mean ± SD of a population, the forecast covariance of an ensemble; all
+    fp64.  Two passes in fp64, the mean and then sums centred on it, divided by `count - correction`; with `check=False` an
+    out-of-range row has left its time's population.  The HIP kernels (`tdeq_row_dense_moments`, ABI 37) evaluate the record
+    again in each pass and never build `[Q, B, *row_shape]`: slabs of 1024 rows are added in a fixed order through LDS and merged
+    in slab order, the covariance is a Gram matrix of deviations on `v_mfma_f64_16x16x4_f64` (64 x 64 blocks per pair of
+    element tiles, the upper triangle mirrored; `variance` is then its diagonal).  No atomics: the same bits from run to run and
+    for any slicing of the times; the torch path of a CPU state has the same error bound, not the same last bits.  A workspace
+    of at most 256 MiB; nothing is cached.
 
     Returns `dense`; with `return_stats=True`, `(dense, stats)`: the stats of `odeint_rowwise` (`n_accepted`,
     `n_rejected`, `nfe`; with `compact` also `row_evals`, `n_repacks`) plus `n_segments` and `n_chunks`.
