@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define TDEQ_ABI_VERSION 37
+#define TDEQ_ABI_VERSION 38
 #define TDEQ_F32 0
 #define TDEQ_F64 1
 /* interleaved (re, im) complex states — accepted by the NORM entry points only (tdeq_error_norm, tdeq_error_norm_partial[_ctrl],
@@ -73,6 +73,7 @@ extern "C" {
 #define TDEQ_ROW_QUANTILES_SLAB_ROWS 1024  /* rows of one workgroup of its counting pass */
 #define TDEQ_ROW_MOMENTS_SLAB_ROWS 1024    /* tdeq_row_dense_moments: rows of one workgroup of its sum passes */
 #define TDEQ_ROW_MOMENTS_MAX_COV_LEN 1024  /* the longest row it takes with a covariance */
+#define TDEQ_ROW_CROSS_MAX_BLOCKS 1024     /* tdeq_row_dense_cross: ceil(row_len / 64) * ceil(n_cols / W) at most */
 
 #define TDEQ_EINVAL (-1)       /* bad argument (null pointer, n_terms out of range, bad dtype ...) */
 #define TDEQ_EWORKSPACE (-2)   /* workspace too small */
@@ -1073,6 +1074,52 @@ size_t tdeq_row_dense_moments_workspace_bytes(int covariance, int64_t n_q, int64
 int tdeq_row_dense_moments(int64_t* count, double* mean, double* variance, double* covariance_or_null, int correction,
                            const void* coeffs, int64_t n_seg, const int32_t* seg, const void* x, int64_t n_q, int64_t n_rows,
                            int64_t row_len, void* workspace, size_t workspace_bytes, int dtype, void* stream);
+
+/*
+ * ---- Cross-covariance with per-row covariates (ABI 38; `RowDenseOutput.cross_covariance`) ----
+ * tdeq_row_dense_cross     for j < n_q, over the population of time j and the values v[r][el] of tdeq_row_dense_moments, and
+ *                          with z = `other`, double [n_rows, n_cols] (one row of n_cols covariates per row of the batch):
+ *                          count[j] and ybar[j, el]: `count` and `mean` of tdeq_row_dense_moments, bit for bit;
+ *                          zbar[m] = sum_r z[r][m] / count over the population;
+ *                          out[j, el, m] = sum_r (v[r][el] - ybar[el]) (z[r][m] - zbar[m]) / div, div = count - correction
+ *                          and 0 where that is not positive (NaN or inf by IEEE division).  `out` double [n_q, row_len,
+ *                          n_cols]; `count` int64 [n_q]; `ybar` double [n_q, row_len]; `correction` 0 or 1; `coeffs`, `seg`,
+ *                          `x` as for tdeq_row_dense_moments.  A row outside the population contributes exact zeros: its
+ *                          entries of `other` are selected away, not multiplied, so a NaN there does not leak; a non-finite
+ *                          entry of a row inside the population propagates by IEEE rules.
+ *                          Method.  Two passes in fp64, never E[yz] - E[y] E[z]; nothing of size n_q * n_rows * row_len is
+ *                                   written.
+ *                          Operation order (the contract of run-to-run reproducibility; no floating-point atomics).
+ *                                   1. ybar, count: the sum and finish kernels of tdeq_row_dense_moments, unchanged.
+ *                                   2. zbar: slabs of TDEQ_ROW_MOMENTS_SLAB_ROWS rows; a workgroup of 4 waves takes one time,
+ *                                      64 columns and one slab; wave w adds the rows w, w + 4, .. of the slab that are in
+ *                                      the population, in that order; the four sums of a column are added in wave order, the
+ *                                      slabs in index order, then the division by count.
+ *                                   3. v_mfma_f64_16x16x4_f64 on blocks of 64 elements x W columns, W = 16 for n_cols <= 16
+ *                                      and 64 otherwise; blocks = ceil(row_len / 64) * ceil(n_cols / W), all computed;
+ *                                      slabs = min(ceil(n_rows / 1024), max(1, 1024 / blocks)), rows per slab rounded up to a
+ *                                      multiple of 16 and the slab count taken again from that; inside a slab the rows
+ *                                      enter in index order, 4 per matrix instruction.
+ *                                   4. the slabs are added in index order, then the division by div.
+ *                                   Every split is a function of (n_rows, row_len, n_cols) alone: slicing the times of a
+ *                                   call changes no bit.  6 launches.
+ *                          `workspace`: 16-byte aligned device memory of at least
+ *                          tdeq_row_dense_cross_workspace_bytes(n_q, n_rows, row_len, n_cols, dtype) =
+ *                          8 * n_q * (sum_slabs * (1 + row_len + n_cols) + n_cols + slabs * blocks * 64 * W) bytes, rounded
+ *                          up to a multiple of 16 (0 for arguments the entry point refuses); its content before and after
+ *                          the call means nothing.
+ *                          16-byte loads of `coeffs` when row_len is a multiple of 16 / sizeof(T) and `coeffs` is 16-byte
+ *                          aligned, scalar loads otherwise.  A NULL pointer, a negative size, n_cols < 1, n_seg < 1,
+ *                          blocks > TDEQ_ROW_CROSS_MAX_BLOCKS (the bound under which the slab rule keeps the partial blocks
+ *                          of a time near 32 MB), correction other than 0 or 1, n_q * n_rows >= INT32_MAX, a workspace
+ *                          that is not 16-byte aligned, more than INT32_MAX workgroups in a pass, or a dtype other than
+ *                          TDEQ_F32 / TDEQ_F64: TDEQ_EINVAL before any launch.  workspace_bytes too small:
+ *                          TDEQ_EWORKSPACE.  n_q == 0, n_rows == 0 or row_len == 0: no-op.
+ */
+size_t tdeq_row_dense_cross_workspace_bytes(int64_t n_q, int64_t n_rows, int64_t row_len, int64_t n_cols, int dtype);
+int tdeq_row_dense_cross(double* out, int64_t* count, double* ybar, const double* other, int64_t n_cols, int correction,
+                         const void* coeffs, int64_t n_seg, const int32_t* seg, const void* x, int64_t n_q, int64_t n_rows,
+                         int64_t row_len, void* workspace, size_t workspace_bytes, int dtype, void* stream);
 
 /*
  * ---- Per-row step options (ABI 29; `min_step`, `max_step`, `step_t`, `jump_t` of the rowwise family) ----

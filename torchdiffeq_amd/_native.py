@@ -18,11 +18,12 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-TDEQ_ABI_VERSION = 37
+TDEQ_ABI_VERSION = 38
 TDEQ_ROW_QUANTILES_MAX_RANKS = 16       # include/tdeq_hip.h
 TDEQ_ROW_QUANTILES_SLAB_ROWS = 1024     # rows of one workgroup of the counting pass of tdeq_row_dense_quantiles
 TDEQ_ROW_MOMENTS_SLAB_ROWS = 1024       # rows of one workgroup of the sum passes of tdeq_row_dense_moments
 TDEQ_ROW_MOMENTS_MAX_COV_LEN = 1024     # the longest row tdeq_row_dense_moments takes with a covariance
+TDEQ_ROW_CROSS_MAX_BLOCKS = 1024        # tdeq_row_dense_cross: ceil(L / 64) * ceil(M / W) blocks at most, W = 16 (M <= 16) or 64
 TDEQ_F32, TDEQ_F64 = 0, 1
 TDEQ_C64, TDEQ_C128 = 2, 3        # interleaved complex: the norm entry points only (include/tdeq_hip.h)
 TDEQ_BF16, TDEQ_F16 = 4, 5        # reduced-precision states: the entry points of the host-driven step (LowPrecisionHipKernels)
@@ -333,6 +334,13 @@ ABI_SIGNATURES = {
                                               ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
                                               ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int,
                                               ctypes.c_void_p]),
+    # cross-covariance with per-row covariates (ABI 38, `RowDenseOutput.cross_covariance`)
+    "tdeq_row_dense_cross_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
+                                                               ctypes.c_int]),
+    "tdeq_row_dense_cross": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
+                                            ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
+                                            ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_size_t,
+                                            ctypes.c_int, ctypes.c_void_p]),
     # per-row step options (ABI 29, `min_step` / `max_step` / `step_t` / `jump_t` of the rowwise family)
     "tdeq_row_control_points": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(StepCtrl),
                                                ctypes.POINTER(RowState), ctypes.POINTER(RowPoints), ctypes.c_void_p,
@@ -1406,6 +1414,42 @@ class HipKernels:
                                                L, workspace.data_ptr(), workspace.numel(), dtype_code(coeffs.dtype),
                                                self._stream()),
                "tdeq_row_dense_moments")
+
+    # -- cross-covariance of the record's rows with per-row covariates (RowDenseOutput.cross_covariance) -----------------------
+    def row_dense_cross_workspace_bytes(self, n_q: int, n_rows: int, row_len: int, n_cols: int, dtype) -> int:
+        """tdeq_row_dense_cross_workspace_bytes: the workspace of `row_dense_cross` for that many times, rows and covariates."""
+        return int(self.lib.tdeq_row_dense_cross_workspace_bytes(n_q, n_rows, row_len, n_cols, dtype_code(dtype)))
+
+    def row_dense_cross(self, out, count, ybar, other, correction: int, coeffs, seg, x, workspace) -> None:
+        """tdeq_row_dense_cross: per query time j the covariance of the L elements with the M columns of `other` (fp64
+        [n_rows, M]) across the rows with x == x: `out` fp64 [Q, L, M] = sum of (y - ybar) (z - zbar) over max(count -
+        correction, 0); `count` int64 [Q] and `ybar` fp64 [Q, L] are those of `row_dense_moments`, bit for bit.  The queries
+        are (seg[j * n_rows + r], x[j * n_rows + r]) of `row_dense_search` on `coeffs` [5, n_seg, L].  `workspace`: a
+        contiguous uint8 tensor of at least `row_dense_cross_workspace_bytes(Q, n_rows, L, M, dtype)` bytes."""
+        if out.dim() != 3 or not out.is_contiguous() or out.dtype != torch.float64 or out.shape[2] < 1:
+            raise ValueError("row_dense_cross: out must be a contiguous float64 [Q, L, M >= 1] tensor")
+        Q, L, M = out.shape
+        if correction not in (0, 1) or isinstance(correction, bool):
+            raise ValueError(f"row_dense_cross: correction must be 0 or 1, got {correction!r}")
+        if Q == 0 or L == 0:
+            return
+        if coeffs.dim() != 3 or coeffs.shape[0] != 5 or coeffs.shape[1] < 1 or coeffs.shape[2] != L \
+                or coeffs.dtype not in (torch.float32, torch.float64) or not coeffs.is_contiguous():
+            raise ValueError("row_dense_cross: coeffs must be a contiguous float32 / float64 [5, n_seg >= 1, L] tensor")
+        n_idx = seg.numel()
+        if n_idx == 0 or n_idx % Q != 0:
+            raise ValueError(f"row_dense_cross: seg must hold n_rows >= 1 queries for each of the {Q} times")
+        for name, t, dtype, shape in [("count", count, torch.int64, (Q,)), ("ybar", ybar, torch.float64, (Q, L)),
+                                      ("other", other, torch.float64, (n_idx // Q, M)), ("seg", seg, torch.int32, (n_idx,)),
+                                      ("x", x, coeffs.dtype, (n_idx,))]:
+            if tuple(t.shape) != shape or t.dtype != dtype or not t.is_contiguous():
+                raise ValueError(f"row_dense_cross: {name} must be a contiguous {dtype} {list(shape)} tensor")
+        if workspace.dtype != torch.uint8 or workspace.dim() != 1 or not workspace.is_contiguous():
+            raise ValueError("row_dense_cross: workspace must be a contiguous uint8 vector")
+        _check(self.lib.tdeq_row_dense_cross(out.data_ptr(), count.data_ptr(), ybar.data_ptr(), other.data_ptr(), M, correction,
+                                             coeffs.data_ptr(), coeffs.shape[1], seg.data_ptr(), x.data_ptr(), Q, n_idx // Q, L,
+                                             workspace.data_ptr(), workspace.numel(), dtype_code(coeffs.dtype), self._stream()),
+               "tdeq_row_dense_cross")
 
 
 class ComplexHipKernels:

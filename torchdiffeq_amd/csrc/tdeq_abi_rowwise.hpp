@@ -1269,3 +1269,154 @@ int tdeq_row_dense_moments(int64_t* count, double* mean, double* variance, doubl
         return row_dense_mom_launch<T>(a, f, sp, w, variance, covariance_or_null, aligned16(coeffs), s);
     });
 }
+
+// ---- cross-covariance with per-row covariates: tdeq_row_dense_cross ----------------------------------------------------------
+// Partition and merge order (tdeq_kernels_rowwise_dense.hpp, row_cross_split): the sums of y and z in slabs of
+// TDEQ_ROW_MOMENTS_SLAB_ROWS rows, the rectangular Gram blocks in at most max(1, 1024 / blocks) slabs of whole 16-row chunks;
+// the slabs in index order by the finish kernels.  No atomics.
+namespace {
+
+// the parts of the workspace, in bytes: the slabs' counts, the partial sums of y and of z, zbar, the partial Gram blocks
+struct RowDenseCrossSpace {
+    size_t counts, ysums, zsums, zbar, gram;
+    size_t total() const { return counts + ysums + zsums + zbar + gram; }
+};
+
+inline RowDenseCrossSpace row_dense_cross_space(int64_t n_q, const RowCrossSplit& sp, int64_t row_len, int64_t n_cols) {
+    return {(size_t)n_q * sp.slabs * sizeof(int64_t), (size_t)n_q * sp.slabs * row_len * sizeof(double),
+            (size_t)n_q * sp.slabs * n_cols * sizeof(double), (size_t)n_q * n_cols * sizeof(double),
+            (size_t)n_q * sp.gram_slabs * sp.blocks * kMomTile * 16 * sp.nb * sizeof(double)};
+}
+
+// (the block bound keeps row_len <= 64 * 1024 and n_cols <= 64 * 1024; with n_q * n_rows < INT32_MAX every product of
+//  row_dense_cross_space is below 2^31 * 2^17 * 8 or 2^31 * 1024 * 4096 * 8 and fits a size_t)
+inline bool row_dense_cross_sizes_ok(int64_t n_q, int64_t n_rows, int64_t row_len, int64_t n_cols, int dtype) {
+    if (n_q < 0 || n_rows < 0 || row_len < 0 || n_cols < 1 || !real_dtype_ok(dtype)) return false;
+    if (n_q > 0x7fffffffLL || row_len > (int64_t)TDEQ_ROW_CROSS_MAX_BLOCKS * kMomTile ||
+        n_cols > (int64_t)TDEQ_ROW_CROSS_MAX_BLOCKS * kMomTile)
+        return false;
+    if (n_rows > 0 && n_q > 0x7ffffffeLL / n_rows) return false;            // n_q * n_rows >= INT32_MAX
+    return row_cross_split(n_rows, row_len, n_cols).blocks <= TDEQ_ROW_CROSS_MAX_BLOCKS;
+}
+
+template <typename T, bool VEC>
+void row_dense_cross_gram_launch(int nb, unsigned groups, hipStream_t s, const RowDenseCrossArgs<T>& a) {
+    if (nb == 1)
+        hipLaunchKernelGGL((row_dense_cross_gram_kernel<T, VEC, 1>), dim3(groups), dim3(kBlock), 0, s, a);
+    else
+        hipLaunchKernelGGL((row_dense_cross_gram_kernel<T, VEC, 4>), dim3(groups), dim3(kBlock), 0, s, a);
+}
+
+}  // namespace
+
+size_t tdeq_row_dense_cross_workspace_bytes(int64_t n_q, int64_t n_rows, int64_t row_len, int64_t n_cols, int dtype) {
+    if (!row_dense_cross_sizes_ok(n_q, n_rows, row_len, n_cols, dtype)) return 0;
+    return (row_dense_cross_space(n_q, row_cross_split(n_rows, row_len, n_cols), row_len, n_cols).total() + 15) / 16 * 16;
+}
+
+int tdeq_row_dense_cross(double* out, int64_t* count, double* ybar, const double* other, int64_t n_cols, int correction,
+                         const void* coeffs, int64_t n_seg, const int32_t* seg, const void* x, int64_t n_q, int64_t n_rows,
+                         int64_t row_len, void* workspace, size_t workspace_bytes, int dtype, void* stream) {
+    if (!out || !count || !ybar || !other || !coeffs || !seg || !x || !workspace ||
+        !row_dense_cross_sizes_ok(n_q, n_rows, row_len, n_cols, dtype))
+        return TDEQ_EINVAL;
+    if (n_seg < 1 || (correction != 0 && correction != 1) || !aligned16(workspace)) return TDEQ_EINVAL;
+    const RowCrossSplit sp = row_cross_split(n_rows, row_len, n_cols);
+    const RowDenseCrossSpace w = row_dense_cross_space(n_q, sp, row_len, n_cols);
+    if (workspace_bytes < w.total()) return TDEQ_EWORKSPACE;
+    const int64_t z_tiles = (n_cols + kMomTile - 1) / kMomTile;
+    const int64_t ysum_groups = n_q * sp.tiles * sp.slabs, zsum_groups = n_q * z_tiles * sp.slabs,
+                  gram_groups = n_q * sp.gram_slabs * sp.blocks;
+    if (ysum_groups > 0x7fffffffLL || zsum_groups > 0x7fffffffLL || gram_groups > 0x7fffffffLL) return TDEQ_EINVAL;
+    if (n_q == 0 || n_rows == 0 || row_len == 0) return 0;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    char* const base = static_cast<char*>(workspace);
+    double* const ysums = reinterpret_cast<double*>(base + w.counts);
+    double* const zsums = reinterpret_cast<double*>(base + w.counts + w.ysums);
+    double* const zbar = reinterpret_cast<double*>(base + w.counts + w.ysums + w.zsums);
+    double* const gram = reinterpret_cast<double*>(base + w.counts + w.ysums + w.zsums + w.zbar);
+    return real_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        // 1. ybar and count: the kernels and the arguments of tdeq_row_dense_moments, so its bits
+        RowDenseMomArgs<T> ya;
+        ya.q = static_cast<const T*>(coeffs);
+        ya.seg = seg;
+        ya.x = static_cast<const T*>(x);
+        ya.mean = ybar;
+        ya.slab_count = reinterpret_cast<int64_t*>(base);
+        ya.partial = ysums;
+        ya.n_rows = n_rows;
+        ya.n_seg = n_seg;
+        ya.row_len = row_len;
+        ya.q_plane = n_seg * row_len;
+        ya.n_q = n_q;
+        ya.tiles = sp.tiles;
+        ya.pairs = 0;
+        ya.slabs = sp.slabs;
+        ya.slab_rows = kMomSlabRows;
+        RowDenseMomFinishArgs f;
+        f.partial = ysums;
+        f.slab_count = ya.slab_count;
+        f.count = count;
+        f.out = ybar;
+        f.variance = nullptr;
+        f.n_q = n_q;
+        f.row_len = row_len;
+        f.tiles = sp.tiles;
+        f.pairs = 0;
+        f.slabs = sp.slabs;
+        f.correction = 0;
+        // 2. zbar: the column sums of `other` per slab, then the finish kernel's division by the count of step 1
+        RowDenseCrossArgs<T> a;
+        a.q = ya.q;
+        a.seg = seg;
+        a.x = ya.x;
+        a.other = other;
+        a.ybar = ybar;
+        a.zbar = zbar;
+        a.partial = zsums;
+        a.n_rows = n_rows;
+        a.n_seg = n_seg;
+        a.row_len = row_len;
+        a.q_plane = ya.q_plane;
+        a.n_cols = n_cols;
+        a.col_tiles = z_tiles;
+        a.blocks = sp.blocks;
+        a.slabs = sp.slabs;
+        a.slab_rows = kMomSlabRows;
+        RowDenseMomFinishArgs zf = f;
+        zf.partial = zsums;
+        zf.out = zbar;
+        zf.row_len = n_cols;
+        // 4. the blocks in slab order, the division
+        RowDenseCrossFinishArgs cf;
+        cf.partial = gram;
+        cf.count = count;
+        cf.out = out;
+        cf.n_q = n_q;
+        cf.row_len = row_len;
+        cf.n_cols = n_cols;
+        cf.col_tiles = sp.col_tiles;
+        cf.blocks = sp.blocks;
+        cf.slabs = sp.gram_slabs;
+        cf.width = 16 * sp.nb;
+        cf.correction = correction;
+        int64_t unused;
+        return row_vec<T>(row_len, aligned16(coeffs), unused, [&](auto vec) {
+            constexpr bool VEC = decltype(vec)::value;
+            const dim3 block(kBlock);
+            hipLaunchKernelGGL((row_dense_moments_sum_kernel<T, VEC, false>), dim3((unsigned)ysum_groups), block, 0, s, ya);
+            hipLaunchKernelGGL(row_dense_moments_finish_kernel<false>, dim3(stream_grid(n_q * row_len, kBlock)), block, 0, s, f);
+            hipLaunchKernelGGL(row_dense_cross_zsum_kernel<T>, dim3((unsigned)zsum_groups), block, 0, s, a);
+            hipLaunchKernelGGL(row_dense_moments_finish_kernel<true>, dim3(stream_grid(n_q * n_cols, kBlock)), block, 0, s, zf);
+            // 3. the rectangular Gram blocks
+            a.partial = gram;
+            a.col_tiles = sp.col_tiles;
+            a.slabs = sp.gram_slabs;
+            a.slab_rows = sp.gram_rows;
+            row_dense_cross_gram_launch<T, VEC>(sp.nb, (unsigned)gram_groups, s, a);
+            hipLaunchKernelGGL(row_dense_cross_finish_kernel, dim3(stream_grid(n_q * row_len * n_cols, kBlock)), block, 0, s, cf);
+            return check_launch();
+        });
+    });
+}

@@ -1297,4 +1297,244 @@ __global__ __launch_bounds__(kBlock) void row_dense_moments_gram_finish_kernel(c
     }
 }
 
+// ---- cross-covariance with per-row covariates (ABI 38): cov(y(t), z) of the B rows, per query time ---------------------------
+// `other` = z [n_rows, M] fp64 holds M covariates per row (sampled parameters, or dense(t_ref) for a cross-time covariance).
+// out[q, i, m] = sum_r (y_ri - ybar_i) (z_rm - zbar_m) / max(count - correction, 0) over the population of time q, two passes
+// in fp64 with the contract of the moments above: no floating-point atomics, the rows split by a rule of the shapes alone, the
+// partials merged in slab order.  ybar and count come from row_dense_moments_sum / _finish, launched unchanged.
+//   row_dense_cross_zsum     the work split of row_dense_moments_sum on `other`: a workgroup owns one time, one tile of 64
+//                            columns and one slab of kMomSlabRows rows; lanes run along the columns (coalesced fp64 loads),
+//                            wave w adds the rows w, w + 4, .. of the slab that are in the population, in that order; the four
+//                            per-wave sums of a column are added through LDS in wave order.  row_dense_moments_finish<true>
+//                            with correction 0 then divides by the count that already exists: zbar [n_q, M].
+//   row_dense_cross_gram     the RECTANGULAR Gram kernel on v_mfma_f64_16x16x4_f64.  A workgroup owns one time, one slab of
+//                            rows and one block (I, J): element tile I of 64 state elements times covariate tile J of W = 16 NB
+//                            columns; all tiles * col_tiles blocks are computed.  NB = 1 for M <= 16 (a 64 x 16 block: one
+//                            accumulator per wave, 8 AGPRs, a 16-column stage for z), NB = 4 otherwise (64 x 64) — the typical M
+//                            is 3 .. 10, where the square kernel would waste three of four accumulators and 48 of 64 staged
+//                            columns.  It walks the slab in chunks of kMomChunk = 16 rows: all 256 threads evaluate the
+//                            chunk's 16 x 64 values of tile I, subtract ybar and write the deviations to the y stage; the
+//                            threads that have a cell of the 16 x W tile of z (all of them: 4 cells each for NB = 4, one for NB
+//                            = 1) load it, subtract zbar and write the z stage — zero (selected, not multiplied: a NaN of such a
+//                            z entry does not leak) for a row outside the population or past the slab's end, an element >= L
+//                            or a column >= M.  Both stages are double-buffered as in row_dense_moments_gram: the loads of
+//                            chunk c + 1 are issued before the matrix work of chunk c, one barrier per chunk.  Wave w owns block
+//                            rows 16 w .. 16 w + 15: per 4-row k-step one A fragment (y), NB B fragments (z) and NB matrix
+//                            instructions, operands as documented at moments_mfma's first user above (lane l: A[l % 16][l /
+//                            16], B[l / 16][l % 16], D[4 v + l / 16][l % 16]).  Stage strides: a fragment read is 8 bytes per
+//                            lane, served a half-wave at a time: lanes 0 .. 31 read rows k and k + 1 of the stage, 16
+//                            consecutive doubles = 32 four-byte banks each, so the two rows are disjoint iff the stride is 32
+//                            words mod 64 = 16 doubles mod 32.  64 columns: 64 = 0 mod 32 conflicts, hence kMomStride = 80.  16
+//                            columns: the dense stride 16 = 16 mod 32 already satisfies it — rows k and k + 1 are 32
+//                            consecutive doubles, all 64 banks once — so kCrossStride16 = 16, no padding.  LDS: 20 KB (y) +
+//                            20 KB / 4 KB (z).  The block goes to partial[time, slab, block][64][W] with plain vector stores.
+//   row_dense_cross_finish   one lane per (time, i < L, m < M): blocks added in slab order, divided by moments_divisor.
+constexpr int kCrossStride16 = 16;                                    // doubles between two rows of the 16-column z stage
+
+// THE slab rule of the cross-covariance: that of the Gram kernel above with `pairs` replaced by the block count.
+struct RowCrossSplit {
+    int nb;                           // 16-column accumulators per wave: 1 (n_cols <= 16) or 4
+    int64_t tiles, col_tiles, blocks; // ceil(L / 64), ceil(M / (16 nb)), their product
+    int64_t slabs;                    // of the sum kernels (y and z)
+    int64_t gram_slabs, gram_rows;    // of the Gram kernel: slabs and rows per slab
+};
+
+inline RowCrossSplit row_cross_split(int64_t n_rows, int64_t row_len, int64_t n_cols) {
+    RowCrossSplit s;
+    s.nb = n_cols <= 16 ? 1 : 4;
+    s.tiles = (row_len + kMomTile - 1) / kMomTile;
+    s.col_tiles = (n_cols + 16 * s.nb - 1) / (16 * s.nb);
+    s.blocks = s.tiles * s.col_tiles;
+    s.slabs = (n_rows + kMomSlabRows - 1) / kMomSlabRows;
+    const int64_t cap = s.blocks > 0 && 1024 / s.blocks > 1 ? 1024 / s.blocks : 1;
+    const int64_t want = s.slabs < cap ? (s.slabs > 0 ? s.slabs : 1) : cap;
+    s.gram_rows = ((n_rows + want - 1) / want + kMomChunk - 1) / kMomChunk * kMomChunk;
+    s.gram_slabs = s.gram_rows > 0 ? (n_rows + s.gram_rows - 1) / s.gram_rows : 0;
+    return s;
+}
+
+template <typename T>
+struct RowDenseCrossArgs {
+    const T* q;                       // [5, n_seg, L]
+    const int32_t* seg;               // [n_q * n_rows]
+    const T* x;                       // [n_q * n_rows]
+    const double* other;              // z [n_rows, M]
+    const double* ybar;               // [n_q, L]
+    const double* zbar;               // [n_q, M]
+    double* partial;                  // zsum: [n_q, slabs, M]; Gram: [n_q, gram_slabs, blocks, 64, W]
+    int64_t n_rows;
+    int64_t n_seg;
+    int64_t row_len;                  // L, T units
+    int64_t q_plane;                  // n_seg * L
+    int64_t n_cols;                   // M
+    int64_t col_tiles;                // zsum: ceil(M / 64); Gram: ceil(M / W)
+    int64_t blocks;
+    int64_t slabs;                    // of THIS launch
+    int64_t slab_rows;                // of THIS launch
+};
+
+struct RowDenseCrossFinishArgs {
+    const double* partial;            // [n_q, gram_slabs, blocks, 64, W]
+    const int64_t* count;             // [n_q]
+    double* out;                      // [n_q, L, M]
+    int64_t n_q;
+    int64_t row_len;
+    int64_t n_cols;
+    int64_t col_tiles;
+    int64_t blocks;
+    int64_t slabs;
+    int32_t width;                    // W
+    int32_t correction;
+};
+
+template <typename T>
+__global__ __launch_bounds__(kBlock) void row_dense_cross_zsum_kernel(const RowDenseCrossArgs<T> a) {
+    constexpr int kWaves = kBlock / kWave;
+    __shared__ double red[kWaves * kMomTile];
+
+    int64_t b = blockIdx.x;
+    const int64_t slab = b % a.slabs;
+    b /= a.slabs;
+    const int64_t tile = b % a.col_tiles;
+    const int64_t q = b / a.col_tiles;
+    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+    const int64_t m = tile * kMomTile + lane;
+
+    double acc = 0.0;
+    if (m < a.n_cols) {
+        const int64_t r_end = (slab + 1) * a.slab_rows < a.n_rows ? (slab + 1) * a.slab_rows : a.n_rows;
+        for (int64_t r = slab * a.slab_rows + wave; r < r_end; r += kWaves) {
+            const T x = a.x[q * a.n_rows + r];
+            if (x != x) continue;                                     // the row has left this time's population
+            acc = acc + a.other[r * a.n_cols + m];
+        }
+    }
+    red[wave * kMomTile + lane] = acc;
+    __syncthreads();
+    if (wave == 0 && m < a.n_cols) {
+        double total = red[lane];
+        for (int w = 1; w < kWaves; ++w) total = total + red[w * kMomTile + lane];
+        a.partial[(q * a.slabs + slab) * a.n_cols + m] = total;
+    }
+}
+
+template <typename T, bool VEC, int NB>
+__global__ __launch_bounds__(kBlock) TDEQ_NO_PACKED_FP32 void row_dense_cross_gram_kernel(const RowDenseCrossArgs<T> a) {
+    using E = typename std::conditional<VEC, typename VecOf<T>::type, T>::type;
+    constexpr int LV = VEC ? VecOf<T>::L : 1;
+    constexpr int kLanesPerRow = kMomTile / LV;
+    constexpr int kRowsPerStep = kBlock / kLanesPerRow;               // rows of the chunk the 256 threads cover at once (y)
+    constexpr int kSteps = kMomChunk / kRowsPerStep;                  // 4 (scalar), 1 (fp32 16-byte), 2 (fp64 16-byte)
+    constexpr int W = 16 * NB;                                        // columns of the block
+    constexpr int kZStride = NB == 1 ? kCrossStride16 : kMomStride;
+    constexpr int kZRowsPerStep = kBlock / W;                         // 16 (NB = 1), 4 (NB = 4)
+    constexpr int kZSteps = kMomChunk / kZRowsPerStep;                // cells of z per thread: 1, 4
+    static_assert(kSteps * kRowsPerStep == kMomChunk && kZSteps * kZRowsPerStep == kMomChunk && (NB == 1 || NB == 4),
+                  "a chunk is whole steps");
+    __shared__ double stage_y[2][kMomChunk * kMomStride];             // [buffer][row][element], 20 KB
+    __shared__ double stage_z[2][kMomChunk * kZStride];               // [buffer][row][column], 4 / 20 KB
+
+    int64_t b = blockIdx.x;
+    const int64_t block = b % a.blocks;
+    b /= a.blocks;
+    const int64_t slab = b % a.slabs;
+    const int64_t q = b / a.slabs;
+    const int64_t I = block / a.col_tiles, J = block % a.col_tiles;
+    const int col = ((int)threadIdx.x % kLanesPerRow) * LV, row0 = (int)threadIdx.x / kLanesPerRow;
+    const int zcol = (int)threadIdx.x % W, zrow0 = (int)threadIdx.x / W;
+    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+
+    const int64_t el = I * kMomTile + col, m = J * W + zcol;
+    const bool el_ok = el < a.row_len, m_ok = m < a.n_cols;           // (VEC: L is a whole number of lanes' elements)
+    double ybar[LV];
+#pragma unroll
+    for (int c = 0; c < LV; ++c) ybar[c] = el_ok ? a.ybar[q * a.row_len + el + c] : 0.0;
+    const double zbar = m_ok ? a.zbar[q * a.n_cols + m] : 0.0;
+    const int64_t r_begin = slab * a.slab_rows;
+    const int64_t r_end = r_begin + a.slab_rows < a.n_rows ? r_begin + a.slab_rows : a.n_rows;
+    const int64_t n_chunks = (r_end - r_begin + kMomChunk - 1) / kMomChunk;
+
+    double dy[kSteps][LV], dz[kZSteps];
+    // the deviations of chunk c of the thread's cells, in registers
+    auto evaluate = [&](int64_t c) __attribute__((always_inline)) {
+#pragma unroll
+        for (int k = 0; k < kSteps; ++k) {
+            const int64_t r = r_begin + c * kMomChunk + k * kRowsPerStep + row0;
+            const bool row_ok = r < r_end;
+            const int64_t i = q * a.n_rows + (row_ok ? r : r_begin);  // (r_begin < n_rows: the slab is not empty)
+            const T x = a.x[i];
+            int64_t s = a.seg[i];
+            s = s < 0 ? 0 : (s < a.n_seg ? s : a.n_seg - 1);
+#pragma unroll
+            for (int cc = 0; cc < LV; ++cc) dy[k][cc] = 0.0;
+            if (row_ok && x == x && el_ok) {
+                T qe[LV], qd[LV], qc[LV], qb[LV], qa[LV];
+                load_planes<T, E, LV>(a.q, a.q_plane, (s * a.row_len + el) / LV, qe, qd, qc, qb, qa);
+#pragma unroll
+                for (int cc = 0; cc < LV; ++cc)
+                    dy[k][cc] = (double)quant_value<T>(qe[cc], qd[cc], qc[cc], qb[cc], qa[cc], x) - ybar[cc];
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < kZSteps; ++k) {
+            const int64_t r = r_begin + c * kMomChunk + k * kZRowsPerStep + zrow0;
+            const bool row_ok = r < r_end;
+            const T x = a.x[q * a.n_rows + (row_ok ? r : r_begin)];
+            dz[k] = 0.0;
+            if (row_ok && x == x && m_ok) dz[k] = a.other[r * a.n_cols + m] - zbar;
+        }
+    };
+    auto publish = [&](int buf) __attribute__((always_inline)) {
+#pragma unroll
+        for (int k = 0; k < kSteps; ++k) {
+#pragma unroll
+            for (int cc = 0; cc < LV; ++cc) stage_y[buf][(k * kRowsPerStep + row0) * kMomStride + col + cc] = dy[k][cc];
+        }
+#pragma unroll
+        for (int k = 0; k < kZSteps; ++k) stage_z[buf][(k * kZRowsPerStep + zrow0) * kZStride + zcol] = dz[k];
+    };
+
+    mom_f64x4 acc[NB];
+#pragma unroll
+    for (int j = 0; j < NB; ++j) acc[j] = mom_f64x4{0.0, 0.0, 0.0, 0.0};
+    if (n_chunks > 0) {
+        evaluate(0);
+        publish(0);
+    }
+    __syncthreads();
+    for (int64_t c = 0; c < n_chunks; ++c) {
+        const int buf = (int)(c & 1);
+        if (c + 1 < n_chunks) evaluate(c + 1);                        // its loads are in flight during the matrix work
+        const double* const sa = stage_y[buf] + (lane / 16) * kMomStride + wave * 16 + lane % 16;
+        const double* const sb = stage_z[buf] + (lane / 16) * kZStride + lane % 16;
+#pragma unroll
+        for (int k0 = 0; k0 < kMomChunk; k0 += 4) {
+            const double fa = sa[k0 * kMomStride];
+#pragma unroll
+            for (int j = 0; j < NB; ++j) acc[j] = moments_mfma(fa, sb[k0 * kZStride + 16 * j], acc[j]);
+        }
+        if (c + 1 < n_chunks) publish(buf ^ 1);                       // (last read before the barrier of chunk c - 1)
+        __syncthreads();
+    }
+    double* const g = a.partial + ((q * a.slabs + slab) * a.blocks + block) * (kMomTile * W);
+#pragma unroll
+    for (int j = 0; j < NB; ++j) {
+#pragma unroll
+        for (int v = 0; v < 4; ++v) g[(wave * 16 + 4 * v + lane / 16) * W + 16 * j + lane % 16] = acc[j][v];
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void row_dense_cross_finish_kernel(const RowDenseCrossFinishArgs a) {
+    const int64_t n = a.n_q * a.row_len * a.n_cols, stride = (int64_t)gridDim.x * kBlock;
+    const int64_t cells = (int64_t)kMomTile * a.width;
+    for (int64_t at = (int64_t)blockIdx.x * kBlock + threadIdx.x; at < n; at += stride) {
+        const int64_t m = at % a.n_cols, i = at / a.n_cols % a.row_len, q = at / a.n_cols / a.row_len;
+        const int64_t block = i / kMomTile * a.col_tiles + m / a.width;
+        const int64_t cell = i % kMomTile * a.width + m % a.width;
+        double total = 0.0;
+        for (int64_t s = 0; s < a.slabs; ++s) total = total + a.partial[((q * a.slabs + s) * a.blocks + block) * cells + cell];
+        a.out[at] = total / moments_divisor(a.count[q], a.correction);
+    }
+}
+
 }  // namespace tdeq

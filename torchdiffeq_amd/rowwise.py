@@ -896,6 +896,23 @@ class HostRowKernels:
         cov = upper + torch.triu(upper, 1).transpose(1, 2)
         return count, mean, torch.diagonal(cov, dim1=1, dim2=2).clone(), cov
 
+    @staticmethod
+    def quartic_cross_covariance(q, src, x, other, Q: int, B: int, correction: int):
+        """Covariance across the rows of each of the Q query times that are in range (`x == x`) between the L elements and the
+        M columns of `other` (fp64 [B, M]): the queries (src, x) [Q * B] of the search on the record `q` [5, n_seg, L] -> fp64
+        [Q, L, M].  The definition of tdeq_row_dense_cross in plain fp64 torch ops: deviations from the population's means of
+        both, selected to zero for a row that has left (a NaN of its `other` entries does not leak), `dev_y.T @ dev_z` per time
+        over `max(count - correction, 0)`.  The order of the sums is torch's: the same error bound, other last bits."""
+        v = HostRowKernels.eval_quartics(q, src, x).view(Q, B, -1).double()
+        took_part = (x == x).view(Q, B, 1)
+        count = took_part.sum(dim=(1, 2)).double()
+        z = other.expand(Q, B, -1)
+        ybar = torch.where(took_part, v, torch.zeros_like(v)).sum(dim=1) / count[:, None]
+        zbar = torch.where(took_part, z, torch.zeros_like(z)).sum(dim=1) / count[:, None]
+        dev_y = torch.where(took_part, v - ybar[:, None, :], torch.zeros_like(v))
+        dev_z = torch.where(took_part, z - zbar[:, None, :], torch.zeros_like(z))
+        return dev_y.transpose(1, 2) @ dev_z / (count - correction).clamp_min(0)[:, None, None]
+
     # -- calculus on a dense record (rowwise_dense.py; the arithmetic of tdeq_row_dense_prefix / tdeq_row_dense_calc) -----
     @staticmethod
     def _quartic_integral(e, d, c, b, a, x, h):

@@ -24,8 +24,9 @@ piece by piece while it walks; the times of ALL crossings, by direction, are the
 which stores every located time at once; the order statistics across rows are one search followed by
 `tdeq_row_dense_quantiles`, a radix select that evaluates the record in every pass; the mean, variance and covariance across
 rows are one search followed by `tdeq_row_dense_moments`, two passes of fp64 sums over slabs of rows merged in a fixed order,
-the covariance as a Gram matrix of deviations on the fp64 matrix instructions.  CPU states run the same steps as torch / numpy
-ops.
+the covariance as a Gram matrix of deviations on the fp64 matrix instructions; the covariance with per-row covariates is one
+search followed by `tdeq_row_dense_cross`, the same mean pass and a rectangular Gram kernel.  CPU states run the same steps as
+torch / numpy ops.
 """
 from __future__ import annotations
 
@@ -37,7 +38,7 @@ import numpy as np
 import torch
 
 from . import rowwise
-from ._native import TDEQ_ROW_MOMENTS_MAX_COV_LEN, TDEQ_ROW_QUANTILES_MAX_RANKS, device_guard
+from ._native import TDEQ_ROW_CROSS_MAX_BLOCKS, TDEQ_ROW_MOMENTS_MAX_COV_LEN, TDEQ_ROW_QUANTILES_MAX_RANKS, device_guard
 from .rowwise import _Problem
 
 __all__ = ["odeint_rowwise_dense", "RowDenseOutput", "RowDenseExtremum", "RowDenseCrossings", "RowDenseCrossingTimes",
@@ -227,8 +228,8 @@ class RowDenseOutput:
     extrema over a time window and their times, `crossings(level, ta, tb)` and `time_above(level, ta, tb)` its crossings of a
     level and the time spent above it, `crossing_times(level, ta, tb, max_count)` the times of all its crossings by direction,
     `exposure(level, ta, tb)`, `area_above(level, ta, tb)` and `area_below(level, ta, tb)` the area between it and a level,
-    `quantiles(t, probs)` its order statistics across the rows, `moments(t)` their mean, variance and covariance (see
-    `odeint_rowwise_dense`).
+    `quantiles(t, probs)` its order statistics across the rows, `moments(t)` their mean, variance and covariance,
+    `cross_covariance(t, other)` their covariance with per-row covariates (see `odeint_rowwise_dense`).
 
     Attributes (the wire format, all on the state's device): `t0`, `t1` `[B]` fp64 in true time; `offsets` `[B + 1]` int64;
     `seg_start`, `seg_end` `[n_seg]` fp64 in true time, row r's segments — its accepted steps — contiguous and in step
@@ -655,8 +656,9 @@ class RowDenseOutput:
         at most 256 MiB (or that of one query time), and runs the times in slices that fit it; the rows are split by a rule of
         `(B, L)` alone and merged in a fixed order without atomics, so the result is the same from run to run and does not
         depend on the slicing.  A CPU state runs the same definition as plain torch ops in fp64: the same error bound, not the
-        same last bits (another order of the sums).  Weights, row subsets, higher moments, correlation matrices (divide by the
-        SDs), cross-time covariance and gradients are out of scope."""
+        same last bits (another order of the sums).  The covariance with a second per-row quantity — sampled parameters, or
+        the state at another time (cross-time covariance) — is `cross_covariance(t, other)`.  Weights, row subsets, higher
+        moments, correlation matrices (divide by the SDs) and gradients are out of scope."""
         what = "dense.moments(t)"
         if isinstance(correction, bool) or not isinstance(correction, int) or correction not in (0, 1):
             raise ValueError(f"{what}: correction must be the int 0 or 1, got {correction!r}")
@@ -702,6 +704,75 @@ class RowDenseOutput:
         if single:
             return RowDenseMoments(count[0], mean[0], var[0], None if cov is None else cov[0])
         return RowDenseMoments(count, mean, var, cov)
+
+    # -- covariance with a second per-row quantity: the mean pass of `moments`, then a rectangular Gram matrix -----------------
+    def cross_covariance(self, t, other, *, correction: int = 1, check: bool = True) -> torch.Tensor:
+        """Covariance ACROSS the rows between the state and per-row covariates, per time: `C_y,theta(t)` of an ensemble Kalman
+        or smoother update, the regression-based sensitivity of every component to every sampled input (divide by the SDs),
+        the covariate-effect screen of a population run -> fp64 `[Q, L, M]`, `L = prod(row_shape)`; `[L, M]` for a single
+        time.  `t` and `check` as for `moments(t)`: the population of a time is the set of rows whose query is in range.
+        `other`: a real tensor `[B]` (`M = 1`) or `[B, M]`, `M >= 1`, of a floating or integer dtype on any device, taken as
+        contiguous fp64 on the record's device.  With `n` the population's size, `ybar` the mean of `moments` and `zbar_m =
+        sum_r other_rm / n` over the same population, `out[q, i, m] = sum_r (y_ri - ybar_i) (other_rm - zbar_m) / max(n -
+        correction, 0)` in fp64 (`correction` is the int 0 or 1; a zero divisor: IEEE division) — two passes, never `E[yz] -
+        E[y] E[z]`.  A row outside the population contributes exact zeros, so a NaN in its `other` entries does not leak; a
+        non-finite entry of a row inside it propagates by IEEE rules.  Cross-time covariance is the same call: `other =
+        dense(t_ref).reshape(B, L)` gives `cov(y(t), y(t_ref))` for all `t`.  A ROCm state runs HIP kernels
+        (`tdeq_row_dense_cross`, ABI 38): the mean and count kernels of `moments` (the same bits), the column sums of `other`,
+        and a rectangular Gram kernel on the fp64 matrix instructions with blocks of 64 elements by 16 covariates for `M <=
+        16` and 64 by 64 otherwise; `ceil(L / 64) * ceil(M / W)` must be at most 1024 blocks.  No atomics, the split is a
+        rule of `(B, L, M)` alone: the same bits from run to run and for any slicing of the times; the workspace stays under
+        256 MiB (or that of one time).  A CPU state runs the definition as plain fp64 torch ops: the same error bound, not
+        the same last bits.  Weights, row subsets and gradients are out of scope."""
+        what = "dense.cross_covariance(t, other)"
+        if isinstance(correction, bool) or not isinstance(correction, int) or correction not in (0, 1):
+            raise ValueError(f"{what}: correction must be the int 0 or 1, got {correction!r}")
+        L, dev, T = self.coeffs.shape[2], self.coeffs.device, self.coeffs.dtype
+        B = self._shape[0]
+        if not isinstance(other, torch.Tensor):
+            raise ValueError(f"{what}: other must be a tensor, got {type(other).__name__}")
+        if other.is_complex() or other.dtype == torch.bool or other.dim() not in (1, 2) or other.shape[0] != B \
+                or (other.dim() == 2 and other.shape[1] == 0):
+            raise ValueError(f"{what}: other must be a real tensor [B] or [B, M >= 1] with B = {B}, got a {other.dtype} "
+                             f"tensor of shape {tuple(other.shape)}")
+        if other.requires_grad and torch.is_grad_enabled():
+            raise NotImplementedError("odeint_rowwise_dense: the dense output does not propagate gradients (other requires "
+                                      "grad); detach it or evaluate under torch.no_grad()")
+        M = 1 if other.dim() == 1 else other.shape[1]
+        W = 16 if M <= 16 else 64
+        if -(-L // 64) * -(-M // W) > TDEQ_ROW_CROSS_MAX_BLOCKS:
+            raise ValueError(f"{what}: {-(-L // 64)} x {-(-M // W)} blocks of 64 elements x {W} covariates; at most "
+                             f"{TDEQ_ROW_CROSS_MAX_BLOCKS} are taken")
+        tqs, single = self._query_lists(what, ("t",), (t,))
+        tq = tqs[0]
+        Q = tq.shape[0]
+        if self._k is not None and Q * B >= _NONE:
+            raise ValueError(f"{what}: {Q * B} queries in one call; the query index is a 32-bit word")
+        out = torch.empty(Q, L, M, dtype=torch.float64, device=dev)
+        first = _NONE
+        if Q > 0:
+            with torch.no_grad(), device_guard(dev):
+                z = other.detach().to(device=dev, dtype=torch.float64).reshape(B, M).contiguous()
+                if self._k is None:
+                    seg, x, first = self._search_host(tq)
+                    out.copy_(rowwise.HostRowKernels.quartic_cross_covariance(self.coeffs, seg, x, z, Q, B, correction))
+                else:
+                    status = torch.full((1,), _NONE, dtype=torch.int32, device=dev)
+                    seg, x = self._search_device(tq, status)
+                    per_time = self._k.row_dense_cross_workspace_bytes(1, B, L, M, T)               # (linear in the times)
+                    step = min(Q, max(1, MOMENTS_WORKSPACE_BYTES // max(per_time, 1)))
+                    work = torch.empty(self._k.row_dense_cross_workspace_bytes(step, B, L, M, T), dtype=torch.uint8, device=dev)
+                    count = torch.empty(Q, dtype=torch.int64, device=dev)
+                    ybar = torch.empty(Q, L, dtype=torch.float64, device=dev)
+                    for q0 in range(0, Q, step):
+                        q1 = min(q0 + step, Q)
+                        self._k.row_dense_cross(out[q0:q1], count[q0:q1], ybar[q0:q1], z, correction, self.coeffs,
+                                                seg[q0 * B:q1 * B], x[q0 * B:q1 * B], work)
+                    if check:
+                        first = int(status)                                                    # the one read
+        if check:
+            self._raise_out_of_range(what, ("t",), tqs, [first])
+        return out[0] if single else out
 
 
 def odeint_rowwise_dense(func, y0, t0, t1, *, rtol=1e-7, atol=1e-9, method="dopri5", options=None, compact=None,
@@ -826,6 +897,15 @@ def odeint_rowwise_dense(func, y0, t0, t1, *, rtol=1e-7, atol=1e-9, method="dopr
     element tiles, the upper triangle mirrored; `variance` is then its diagonal).  No atomics: the same bits from run to run and
     for any slicing of the times; the torch path of a CPU state has the same error bound, not the same last bits.  A workspace
     of at most 256 MiB; nothing is cached.
+
+    Covariance with per-row covariates: `dense.cross_covariance(t, other, correction=1)` -> fp64 `[Q, L, M]`, per time the
+    covariance across the rows in range between each of the `L` elements and each of the `M` columns of `other` (`[B]` or `[B,
+    M]`: the sampled parameters of the ensemble members, or `dense(t_ref).reshape(B, L)` for a cross-time covariance) — the
+    `C_y,theta(t)` of an ensemble Kalman or smoother update and, divided by the SDs, a regression-based global sensitivity.  Two
+    passes in fp64 over the same population and divisor as `moments`; a row out of range contributes exact zeros.  The HIP
+    kernels (`tdeq_row_dense_cross`, ABI 38) reuse the mean and count kernels of `moments`, add the columns of `other` in slabs
+    of 1024 rows, and compute a rectangular Gram matrix on `v_mfma_f64_16x16x4_f64` in blocks of 64 elements by 16 covariates
+    (`M <= 16`) or 64 by 64, at most 1024 blocks.  No atomics: the same bits from run to run and for any slicing of the times.
 
     Returns `dense`; with `return_stats=True`, `(dense, stats)`: the stats of `odeint_rowwise` (`n_accepted`,
     `n_rejected`, `nfe`; with `compact` also `row_evals`, `n_repacks`) plus `n_segments` and `n_chunks`.
