@@ -1122,6 +1122,50 @@ int tdeq_row_dense_cross(double* out, int64_t* count, double* ybar, const double
                          int64_t row_len, void* workspace, size_t workspace_bytes, int dtype, void* stream);
 
 /*
+ * ---- Weighted moments and cross-covariance (additive symbols within ABI 38: TDEQ_ABI_VERSION is unchanged and a client of
+ *      ABI 38 that does not call them is unaffected; `weights=` of `RowDenseOutput.moments` / `.cross_covariance`) ----
+ * tdeq_row_dense_moments_weighted   tdeq_row_dense_moments with reliability weights.  `weights` double, w[j][r] =
+ *                          weights[j * w_stride + r]: w_stride == 0 is one set [n_rows] for all times, w_stride == n_rows one
+ *                          set per time [n_q, n_rows].  Over the population of time j (the rows with x == x):
+ *                          count[j] = the rows of the population, whatever their weights; W1 = sum_r w, W2 = sum_r w^2;
+ *                          mean[j, el] = sum_r w v / W1; D = W1 - correction * W2 / W1, and 0 where that is not positive or
+ *                          is NaN (NaN or inf by IEEE division); variance[j, el] = sum_r w (v - mean)^2 / D;
+ *                          covariance[j, a, b] = sum_r w (v[r][a] - mean[a]) (v[r][b] - mean[b]) / D: the reliability weights
+ *                          of numpy.cov(aweights = w, ddof = correction).  A row outside the population contributes selected
+ *                          zeros to every sum, W1 and W2 included: its weight is not multiplied, so a NaN there does not
+ *                          leak.  The weights' values are not inspected: a negative or non-finite weight of a row inside the
+ *                          population propagates by IEEE arithmetic.
+ *                          Method, partition and merge order: those of tdeq_row_dense_moments, on kernels of their own that
+ *                          load one weight per row.  Sums: a lane adds w * v, or (w * d) * d; the workgroup of the first
+ *                          64-element tile also adds n, w and w * w of its slab in the order of the row groups.  Covariance:
+ *                          the A operand of v_mfma_f64_16x16x4_f64 is staged as w * d of tile I, the B operand as d of tile
+ *                          J.  BITS: with every weight 1.0 each output has the bits tdeq_row_dense_moments gives; a weight
+ *                          of exactly 0 leaves every output but `count` as if the row were outside the population.  5
+ *                          launches (covariance: 4).
+ *                          `workspace`: 16-byte aligned, at least tdeq_row_dense_moments_weighted_workspace_bytes(...) =
+ *                          the bytes of tdeq_row_dense_moments_workspace_bytes + 16 * n_q * (slabs + 1) before rounding.
+ *                          Refusals, their order and the no-ops: those of tdeq_row_dense_moments; also TDEQ_EINVAL for a
+ *                          NULL `weights` and for a w_stride other than 0 or n_rows.
+ * tdeq_row_dense_cross_weighted     tdeq_row_dense_cross with the same weights: count, ybar, W1 and D as above (ybar and
+ *                          count with the bits of tdeq_row_dense_moments_weighted), zbar[m] = sum_r w z[r][m] / W1,
+ *                          out[j, el, m] = sum_r w (v[r][el] - ybar[el]) (z[r][m] - zbar[m]) / D.  The operation order of
+ *                          tdeq_row_dense_cross; the weight is multiplied into the staged z - zbar side.  With every weight
+ *                          1.0 the bits of tdeq_row_dense_cross.  6 launches.  `workspace`: the bytes of
+ *                          tdeq_row_dense_cross_workspace_bytes + 16 * n_q * (sum_slabs + 1) before rounding.  Refusals as
+ *                          for tdeq_row_dense_cross, and those of `weights` and `w_stride` above.
+ */
+size_t tdeq_row_dense_moments_weighted_workspace_bytes(int covariance, int64_t n_q, int64_t n_rows, int64_t row_len, int dtype);
+int tdeq_row_dense_moments_weighted(int64_t* count, double* mean, double* variance, double* covariance_or_null, int correction,
+                                    const void* coeffs, int64_t n_seg, const int32_t* seg, const void* x, int64_t n_q,
+                                    int64_t n_rows, int64_t row_len, void* workspace, size_t workspace_bytes, int dtype,
+                                    void* stream, const double* weights, int64_t w_stride);
+size_t tdeq_row_dense_cross_weighted_workspace_bytes(int64_t n_q, int64_t n_rows, int64_t row_len, int64_t n_cols, int dtype);
+int tdeq_row_dense_cross_weighted(double* out, int64_t* count, double* ybar, const double* other, int64_t n_cols, int correction,
+                                  const void* coeffs, int64_t n_seg, const int32_t* seg, const void* x, int64_t n_q,
+                                  int64_t n_rows, int64_t row_len, void* workspace, size_t workspace_bytes, int dtype,
+                                  void* stream, const double* weights, int64_t w_stride);
+
+/*
  * ---- Per-row step options (ABI 29; `min_step`, `max_step`, `step_t`, `jump_t` of the rowwise family) ----
  * tdeq_row_control_points  tdeq_row_control with step bounds per row and with points per row: `step_t` (times a step of
  *                          the row must end on) and `jump_t` (times where func is discontinuous), rk_common.py:223-241,

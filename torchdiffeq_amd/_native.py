@@ -341,6 +341,22 @@ ABI_SIGNATURES = {
                                             ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
                                             ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_size_t,
                                             ctypes.c_int, ctypes.c_void_p]),
+    # the same two with reliability weights (additive symbols within ABI 38, `weights=` of the two methods): the twin's
+    # arguments, then `weights` and `w_stride`
+    "tdeq_row_dense_moments_weighted_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int64, ctypes.c_int64,
+                                                                          ctypes.c_int64, ctypes.c_int]),
+    "tdeq_row_dense_moments_weighted": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                       ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
+                                                       ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
+                                                       ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_void_p,
+                                                       ctypes.c_void_p, ctypes.c_int64]),
+    "tdeq_row_dense_cross_weighted_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
+                                                                        ctypes.c_int64, ctypes.c_int]),
+    "tdeq_row_dense_cross_weighted": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                     ctypes.c_int64, ctypes.c_int, ctypes.c_void_p, ctypes.c_int64,
+                                                     ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
+                                                     ctypes.c_int64, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int,
+                                                     ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64]),
     # per-row step options (ABI 29, `min_step` / `max_step` / `step_t` / `jump_t` of the rowwise family)
     "tdeq_row_control_points": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(StepCtrl),
                                                ctypes.POINTER(RowState), ctypes.POINTER(RowPoints), ctypes.c_void_p,
@@ -1450,6 +1466,83 @@ class HipKernels:
                                              coeffs.data_ptr(), coeffs.shape[1], seg.data_ptr(), x.data_ptr(), Q, n_idx // Q, L,
                                              workspace.data_ptr(), workspace.numel(), dtype_code(coeffs.dtype), self._stream()),
                "tdeq_row_dense_cross")
+
+    # -- the same two with reliability weights (`weights=` of RowDenseOutput.moments / .cross_covariance) ----------------------
+    @staticmethod
+    def _row_dense_weighted_checks(what: str, Q: int, L: int, correction, coeffs, seg, x, weights, workspace, outputs) -> int:
+        """The argument checks the two weighted calls share -> n_rows.  `weights`: contiguous fp64 [n_rows] or [Q, n_rows]."""
+        if correction not in (0, 1) or isinstance(correction, bool):
+            raise ValueError(f"{what}: correction must be 0 or 1, got {correction!r}")
+        if coeffs.dim() != 3 or coeffs.shape[0] != 5 or coeffs.shape[1] < 1 or coeffs.shape[2] != L \
+                or coeffs.dtype not in (torch.float32, torch.float64) or not coeffs.is_contiguous():
+            raise ValueError(f"{what}: coeffs must be a contiguous float32 / float64 [5, n_seg >= 1, L] tensor")
+        n_idx = seg.numel()
+        if n_idx == 0 or n_idx % Q != 0:
+            raise ValueError(f"{what}: seg must hold n_rows >= 1 queries for each of the {Q} times")
+        B = n_idx // Q
+        if weights.dtype != torch.float64 or not weights.is_contiguous() or tuple(weights.shape) not in ((B,), (Q, B)):
+            raise ValueError(f"{what}: weights must be a contiguous float64 [{B}] or [{Q}, {B}] tensor")
+        for name, t, dtype, shape in outputs + [("seg", seg, torch.int32, (n_idx,)), ("x", x, coeffs.dtype, (n_idx,))]:
+            if tuple(t.shape) != tuple(d if d is not None else B for d in shape) or t.dtype != dtype or not t.is_contiguous():
+                raise ValueError(f"{what}: {name} must be a contiguous {dtype} {list(shape)} tensor")
+        if workspace.dtype != torch.uint8 or workspace.dim() != 1 or not workspace.is_contiguous():
+            raise ValueError(f"{what}: workspace must be a contiguous uint8 vector")
+        return B
+
+    def row_dense_moments_weighted_workspace_bytes(self, covariance: bool, n_q: int, n_rows: int, row_len: int, dtype) -> int:
+        """tdeq_row_dense_moments_weighted_workspace_bytes: the workspace of `row_dense_moments_weighted`."""
+        return int(self.lib.tdeq_row_dense_moments_weighted_workspace_bytes(int(bool(covariance)), n_q, n_rows, row_len,
+                                                                            dtype_code(dtype)))
+
+    def row_dense_moments_weighted(self, count, mean, variance, covariance, correction: int, coeffs, seg, x, workspace,
+                                   weights) -> None:
+        """tdeq_row_dense_moments_weighted: `row_dense_moments` with reliability weights, fp64 [n_rows] (one set for all
+        times) or [Q, n_rows]: `count` still counts the rows with x == x; the mean is sum w v / W1 and the centred sums are
+        divided by max(W1 - correction * W2 / W1, 0), W1 = sum w, W2 = sum w^2 over those rows.  With every weight 1.0 the
+        bits of `row_dense_moments`.  `workspace`: at least `row_dense_moments_weighted_workspace_bytes(...)` bytes."""
+        what = "row_dense_moments_weighted"
+        if mean.dim() != 2 or not mean.is_contiguous() or mean.dtype != torch.float64:
+            raise ValueError(f"{what}: mean must be a contiguous float64 [Q, L] tensor")
+        Q, L = mean.shape
+        if covariance is not None and L > TDEQ_ROW_MOMENTS_MAX_COV_LEN:
+            raise ValueError(f"{what}: a covariance takes rows of at most {TDEQ_ROW_MOMENTS_MAX_COV_LEN} elements, got {L}")
+        if Q == 0 or L == 0:
+            return
+        outputs = [("count", count, torch.int64, (Q,)), ("variance", variance, torch.float64, (Q, L))]
+        if covariance is not None:
+            outputs.append(("covariance", covariance, torch.float64, (Q, L, L)))
+        B = self._row_dense_weighted_checks(what, Q, L, correction, coeffs, seg, x, weights, workspace, outputs)
+        _check(self.lib.tdeq_row_dense_moments_weighted(count.data_ptr(), mean.data_ptr(), variance.data_ptr(),
+                                                        None if covariance is None else covariance.data_ptr(), correction,
+                                                        coeffs.data_ptr(), coeffs.shape[1], seg.data_ptr(), x.data_ptr(), Q, B,
+                                                        L, workspace.data_ptr(), workspace.numel(), dtype_code(coeffs.dtype),
+                                                        self._stream(), weights.data_ptr(), 0 if weights.dim() == 1 else B),
+               "tdeq_row_dense_moments_weighted")
+
+    def row_dense_cross_weighted_workspace_bytes(self, n_q: int, n_rows: int, row_len: int, n_cols: int, dtype) -> int:
+        """tdeq_row_dense_cross_weighted_workspace_bytes: the workspace of `row_dense_cross_weighted`."""
+        return int(self.lib.tdeq_row_dense_cross_weighted_workspace_bytes(n_q, n_rows, row_len, n_cols, dtype_code(dtype)))
+
+    def row_dense_cross_weighted(self, out, count, ybar, other, correction: int, coeffs, seg, x, workspace, weights) -> None:
+        """tdeq_row_dense_cross_weighted: `row_dense_cross` with the weights of `row_dense_moments_weighted`: `count` and
+        `ybar` with its bits, zbar = sum w z / W1, `out` = sum w (y - ybar) (z - zbar) / max(W1 - correction * W2 / W1, 0).
+        With every weight 1.0 the bits of `row_dense_cross`.  `workspace`: at least
+        `row_dense_cross_weighted_workspace_bytes(Q, n_rows, L, M, dtype)` bytes."""
+        what = "row_dense_cross_weighted"
+        if out.dim() != 3 or not out.is_contiguous() or out.dtype != torch.float64 or out.shape[2] < 1:
+            raise ValueError(f"{what}: out must be a contiguous float64 [Q, L, M >= 1] tensor")
+        Q, L, M = out.shape
+        if Q == 0 or L == 0:
+            return
+        outputs = [("count", count, torch.int64, (Q,)), ("ybar", ybar, torch.float64, (Q, L)),
+                   ("other", other, torch.float64, (None, M))]                      # (None: n_rows)
+        B = self._row_dense_weighted_checks(what, Q, L, correction, coeffs, seg, x, weights, workspace, outputs)
+        _check(self.lib.tdeq_row_dense_cross_weighted(out.data_ptr(), count.data_ptr(), ybar.data_ptr(), other.data_ptr(), M,
+                                                      correction, coeffs.data_ptr(), coeffs.shape[1], seg.data_ptr(),
+                                                      x.data_ptr(), Q, B, L, workspace.data_ptr(), workspace.numel(),
+                                                      dtype_code(coeffs.dtype), self._stream(), weights.data_ptr(),
+                                                      0 if weights.dim() == 1 else B),
+               "tdeq_row_dense_cross_weighted")
 
 
 class ComplexHipKernels:

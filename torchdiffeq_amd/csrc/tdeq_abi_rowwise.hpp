@@ -1420,3 +1420,220 @@ int tdeq_row_dense_cross(double* out, int64_t* count, double* ybar, const double
         });
     });
 }
+
+// ---- weighted moments and cross-covariance: tdeq_row_dense_moments_weighted, tdeq_row_dense_cross_weighted ------------------
+// Additive symbols within ABI 38.  The splits, the merge order and the checks are those of the unweighted twins above; the
+// kernels are the row_dense_w* family (tdeq_kernels_rowwise_dense.hpp), which gives the twins' bits for weights of 1.0.  The
+// workspace grows by the slabs' (W1, W2) and by (W1, D) per time.
+namespace {
+
+// the statistics in front of the twin's workspace, in bytes: the slabs' counts, the slabs' (W1, W2), (W1, D) per time
+struct RowDenseWStatSpace {
+    size_t counts, slab_w, stat;
+    size_t total() const { return counts + slab_w + stat; }
+};
+
+inline RowDenseWStatSpace row_dense_wstat_space(int64_t n_q, int64_t slabs) {
+    return {(size_t)n_q * slabs * sizeof(int64_t), (size_t)n_q * slabs * 2 * sizeof(double), (size_t)n_q * 2 * sizeof(double)};
+}
+
+template <typename T, bool VEC>
+void row_dense_wcross_gram_launch(int nb, unsigned groups, hipStream_t s, const RowDenseWCrossArgs<T>& a) {
+    if (nb == 1)
+        hipLaunchKernelGGL((row_dense_wcross_gram_kernel<T, VEC, 1>), dim3(groups), dim3(kBlock), 0, s, a);
+    else
+        hipLaunchKernelGGL((row_dense_wcross_gram_kernel<T, VEC, 4>), dim3(groups), dim3(kBlock), 0, s, a);
+}
+
+// the arguments of the weighted sum pass over y and of its finish, shared by the two entry points
+template <typename T>
+void row_dense_wmean_args(RowDenseWMomArgs<T>& a, RowDenseWMomFinishArgs& f, const void* coeffs, const int32_t* seg, const void* x,
+                          const double* weights, int64_t w_stride, int64_t* count, double* mean, int correction, char* base,
+                          const RowDenseWStatSpace& st, int64_t n_q, int64_t n_rows, int64_t n_seg, int64_t row_len,
+                          int64_t tiles, int64_t pairs, int64_t slabs) {
+    a.q = static_cast<const T*>(coeffs);
+    a.seg = seg;
+    a.x = static_cast<const T*>(x);
+    a.mean = mean;
+    a.slab_count = reinterpret_cast<int64_t*>(base);
+    a.slab_w = reinterpret_cast<double*>(base + st.counts);
+    a.partial = reinterpret_cast<double*>(base + st.total());
+    a.w = weights;
+    a.w_stride = w_stride;
+    a.n_rows = n_rows;
+    a.n_seg = n_seg;
+    a.row_len = row_len;
+    a.q_plane = n_seg * row_len;
+    a.n_q = n_q;
+    a.tiles = tiles;
+    a.pairs = pairs;
+    a.slabs = slabs;
+    a.slab_rows = kMomSlabRows;
+    f.partial = a.partial;
+    f.slab_count = a.slab_count;
+    f.slab_w = a.slab_w;
+    f.stat = reinterpret_cast<double*>(base + st.counts + st.slab_w);
+    f.divisor = f.stat + 1;                                                  // D
+    f.count = count;
+    f.out = mean;
+    f.variance = nullptr;
+    f.n_q = n_q;
+    f.row_len = row_len;
+    f.tiles = tiles;
+    f.pairs = pairs;
+    f.slabs = slabs;
+    f.correction = correction;
+}
+
+}  // namespace
+
+size_t tdeq_row_dense_moments_weighted_workspace_bytes(int covariance, int64_t n_q, int64_t n_rows, int64_t row_len, int dtype) {
+    if (!row_dense_mom_sizes_ok(covariance != 0, n_q, n_rows, row_len, dtype)) return 0;
+    const RowMomentsSplit sp = row_moments_split(n_rows, row_len);
+    const RowDenseMomSpace w = row_dense_mom_space(covariance != 0, n_q, sp, row_len);
+    return (row_dense_wstat_space(n_q, sp.slabs).total() + w.sums + w.gram + 15) / 16 * 16;
+}
+
+int tdeq_row_dense_moments_weighted(int64_t* count, double* mean, double* variance, double* covariance_or_null, int correction,
+                                    const void* coeffs, int64_t n_seg, const int32_t* seg, const void* x, int64_t n_q,
+                                    int64_t n_rows, int64_t row_len, void* workspace, size_t workspace_bytes, int dtype,
+                                    void* stream, const double* weights, int64_t w_stride) {
+    const bool cov = covariance_or_null != nullptr;
+    if (!count || !mean || !variance || !coeffs || !seg || !x || !workspace || !weights ||
+        !row_dense_mom_sizes_ok(cov, n_q, n_rows, row_len, dtype) || (w_stride != 0 && w_stride != n_rows))
+        return TDEQ_EINVAL;
+    if (n_seg < 1 || (correction != 0 && correction != 1) || !aligned16(workspace)) return TDEQ_EINVAL;
+    const RowMomentsSplit sp = row_moments_split(n_rows, row_len);
+    const RowDenseMomSpace w = row_dense_mom_space(cov, n_q, sp, row_len);
+    const RowDenseWStatSpace st = row_dense_wstat_space(n_q, sp.slabs);
+    if (workspace_bytes < st.total() + w.sums + w.gram) return TDEQ_EWORKSPACE;
+    if (n_q == 0 || n_rows == 0 || row_len == 0) return 0;
+    const int64_t sum_groups = n_q * sp.tiles * sp.slabs, gram_groups = n_q * sp.gram_slabs * sp.pairs;
+    if (sum_groups > 0x7fffffffLL || (cov && gram_groups > 0x7fffffffLL)) return TDEQ_EINVAL;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    char* const base = static_cast<char*>(workspace);
+    return real_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        RowDenseWMomArgs<T> a;
+        RowDenseWMomFinishArgs f;
+        row_dense_wmean_args<T>(a, f, coeffs, seg, x, weights, w_stride, count, mean, correction, base, st, n_q, n_rows, n_seg,
+                                row_len, sp.tiles, sp.pairs, sp.slabs);
+        int64_t unused;
+        return row_vec<T>(row_len, aligned16(coeffs), unused, [&](auto vec) {
+            constexpr bool VEC = decltype(vec)::value;
+            const dim3 block(kBlock), cells(stream_grid(n_q * row_len, kBlock));
+            hipLaunchKernelGGL((row_dense_wmoments_sum_kernel<T, VEC, false>), dim3((unsigned)sum_groups), block, 0, s, a);
+            hipLaunchKernelGGL(row_dense_wmoments_finish_kernel<false>, cells, block, 0, s, f);   // mean, count, W1 and D
+            if (cov) {
+                f.partial = a.partial = reinterpret_cast<double*>(base + st.total() + w.sums);
+                a.slabs = f.slabs = sp.gram_slabs;
+                a.slab_rows = sp.gram_rows;
+                f.out = covariance_or_null;
+                f.variance = variance;
+                hipLaunchKernelGGL((row_dense_wmoments_gram_kernel<T, VEC>), dim3((unsigned)gram_groups), block, 0, s, a);
+                hipLaunchKernelGGL(row_dense_wmoments_gram_finish_kernel, dim3(stream_grid(n_q * sp.pairs * kMomBlock, kBlock)),
+                                   block, 0, s, f);
+            } else {
+                f.out = variance;
+                hipLaunchKernelGGL((row_dense_wmoments_sum_kernel<T, VEC, true>), dim3((unsigned)sum_groups), block, 0, s, a);
+                hipLaunchKernelGGL(row_dense_wmoments_finish_kernel<true>, cells, block, 0, s, f);
+            }
+            return check_launch();
+        });
+    });
+}
+
+size_t tdeq_row_dense_cross_weighted_workspace_bytes(int64_t n_q, int64_t n_rows, int64_t row_len, int64_t n_cols, int dtype) {
+    if (!row_dense_cross_sizes_ok(n_q, n_rows, row_len, n_cols, dtype)) return 0;
+    const RowCrossSplit sp = row_cross_split(n_rows, row_len, n_cols);
+    const RowDenseCrossSpace w = row_dense_cross_space(n_q, sp, row_len, n_cols);
+    return (row_dense_wstat_space(n_q, sp.slabs).total() + w.total() - w.counts + 15) / 16 * 16;
+}
+
+int tdeq_row_dense_cross_weighted(double* out, int64_t* count, double* ybar, const double* other, int64_t n_cols, int correction,
+                                  const void* coeffs, int64_t n_seg, const int32_t* seg, const void* x, int64_t n_q,
+                                  int64_t n_rows, int64_t row_len, void* workspace, size_t workspace_bytes, int dtype,
+                                  void* stream, const double* weights, int64_t w_stride) {
+    if (!out || !count || !ybar || !other || !coeffs || !seg || !x || !workspace || !weights ||
+        !row_dense_cross_sizes_ok(n_q, n_rows, row_len, n_cols, dtype) || (w_stride != 0 && w_stride != n_rows))
+        return TDEQ_EINVAL;
+    if (n_seg < 1 || (correction != 0 && correction != 1) || !aligned16(workspace)) return TDEQ_EINVAL;
+    const RowCrossSplit sp = row_cross_split(n_rows, row_len, n_cols);
+    const RowDenseCrossSpace w = row_dense_cross_space(n_q, sp, row_len, n_cols);
+    const RowDenseWStatSpace st = row_dense_wstat_space(n_q, sp.slabs);
+    if (workspace_bytes < st.total() + w.total() - w.counts) return TDEQ_EWORKSPACE;
+    const int64_t z_tiles = (n_cols + kMomTile - 1) / kMomTile;
+    const int64_t ysum_groups = n_q * sp.tiles * sp.slabs, zsum_groups = n_q * z_tiles * sp.slabs,
+                  gram_groups = n_q * sp.gram_slabs * sp.blocks;
+    if (ysum_groups > 0x7fffffffLL || zsum_groups > 0x7fffffffLL || gram_groups > 0x7fffffffLL) return TDEQ_EINVAL;
+    if (n_q == 0 || n_rows == 0 || row_len == 0) return 0;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    char* const base = static_cast<char*>(workspace);
+    double* const zsums = reinterpret_cast<double*>(base + st.total() + w.ysums);
+    double* const zbar = reinterpret_cast<double*>(base + st.total() + w.ysums + w.zsums);
+    double* const gram = reinterpret_cast<double*>(base + st.total() + w.ysums + w.zsums + w.zbar);
+    return real_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        // 1. ybar, count, W1 and D: the kernels and the arguments of tdeq_row_dense_moments_weighted, so its bits
+        RowDenseWMomArgs<T> ya;
+        RowDenseWMomFinishArgs f;
+        row_dense_wmean_args<T>(ya, f, coeffs, seg, x, weights, w_stride, count, ybar, correction, base, st, n_q, n_rows, n_seg,
+                                row_len, sp.tiles, 0, sp.slabs);
+        // 2. zbar: the weighted column sums of `other` per slab, then the division by W1
+        RowDenseWCrossArgs<T> a;
+        a.q = ya.q;
+        a.seg = seg;
+        a.x = ya.x;
+        a.other = other;
+        a.ybar = ybar;
+        a.zbar = zbar;
+        a.partial = zsums;
+        a.w = weights;
+        a.w_stride = w_stride;
+        a.n_rows = n_rows;
+        a.n_seg = n_seg;
+        a.row_len = row_len;
+        a.q_plane = ya.q_plane;
+        a.n_cols = n_cols;
+        a.col_tiles = z_tiles;
+        a.blocks = sp.blocks;
+        a.slabs = sp.slabs;
+        a.slab_rows = kMomSlabRows;
+        RowDenseWMomFinishArgs zf = f;
+        zf.partial = zsums;
+        zf.out = zbar;
+        zf.row_len = n_cols;
+        zf.divisor = f.stat;                                                 // W1
+        // 4. the blocks in slab order, the division by D
+        RowDenseWCrossFinishArgs cf;
+        cf.partial = gram;
+        cf.count = count;
+        cf.divisor = f.stat + 1;
+        cf.out = out;
+        cf.n_q = n_q;
+        cf.row_len = row_len;
+        cf.n_cols = n_cols;
+        cf.col_tiles = sp.col_tiles;
+        cf.blocks = sp.blocks;
+        cf.slabs = sp.gram_slabs;
+        cf.width = 16 * sp.nb;
+        cf.correction = correction;
+        int64_t unused;
+        return row_vec<T>(row_len, aligned16(coeffs), unused, [&](auto vec) {
+            constexpr bool VEC = decltype(vec)::value;
+            const dim3 block(kBlock);
+            hipLaunchKernelGGL((row_dense_wmoments_sum_kernel<T, VEC, false>), dim3((unsigned)ysum_groups), block, 0, s, ya);
+            hipLaunchKernelGGL(row_dense_wmoments_finish_kernel<false>, dim3(stream_grid(n_q * row_len, kBlock)), block, 0, s, f);
+            hipLaunchKernelGGL(row_dense_wcross_zsum_kernel<T>, dim3((unsigned)zsum_groups), block, 0, s, a);
+            hipLaunchKernelGGL(row_dense_wmoments_finish_kernel<true>, dim3(stream_grid(n_q * n_cols, kBlock)), block, 0, s, zf);
+            // 3. the rectangular Gram blocks
+            a.partial = gram;
+            a.col_tiles = sp.col_tiles;
+            a.slabs = sp.gram_slabs;
+            a.slab_rows = sp.gram_rows;
+            row_dense_wcross_gram_launch<T, VEC>(sp.nb, (unsigned)gram_groups, s, a);
+            hipLaunchKernelGGL(row_dense_wcross_finish_kernel, dim3(stream_grid(n_q * row_len * n_cols, kBlock)), block, 0, s, cf);
+            return check_launch();
+        });
+    });
+}

@@ -1537,4 +1537,451 @@ __global__ __launch_bounds__(kBlock) void row_dense_cross_finish_kernel(const Ro
     }
 }
 
+// ---- weighted moments and cross-covariance (additive within ABI 38): reliability weights w_r >= 0 per row and time -----------
+// Per time q over the population of the moments above, with w = weights[q * w_stride + r] (w_stride = 0: one set for all
+// times; n_rows: one set per time): n = rows in range, W1 = sum w, W2 = sum w^2, mean_i = sum w y_i / W1, D = W1 - correction
+// W2 / W1 (0 where that is not positive or NaN), cov_ij = sum w (y_i - mean_i) (y_j - mean_j) / D, and for the cross-
+// covariance zbar_m = sum w z_m / W1 and out_im = sum w (y_i - mean_i) (z_m - zbar_m) / D: numpy.cov(aweights = w, ddof =
+// correction).  The contract of the family holds: fp64, two passes, no floating-point atomics, the splits of row_moments_split
+// / row_cross_split, partials merged in slab order, 64-bit offsets, no scratch.  A row out of range contributes SELECTED zeros
+// to every sum, W1 and W2 included: its weight is never multiplied, so a NaN there does not leak.  The weights' values are not
+// inspected: a negative or non-finite weight of a row in range propagates by IEEE arithmetic.
+// THE PROPERTY THAT PINS THE DESIGN: with every weight 1.0 each output carries the bits of the unweighted kernels.  The work
+// split, the order of the rows inside a lane, the order through LDS and the order of the slabs are those kernels'; w * v and w *
+// d are exact for w = 1; W1 = n, W2 / W1 = 1 and D = n - correction are exact; and the library is compiled with contraction off
+// (-ffp-contract=off), so `acc + d * d` there is v_mul_f64 then v_add_f64 and `acc + (w * d) * d` here rounds at the same two
+// places.  For the same reason a weight of exactly 0 leaves every sum as if the row had left (acc + 0 = acc, 0 * d = 0 in the
+// matrix instruction), `count` apart.
+//   row_dense_wmoments_sum     row_dense_moments_sum with one more load per row: a lane adds w * v, or (w * d) * d when
+//                              CENTRED.  In the non-centred pass the lanes of column 0 also add n, w and w * w over their rows,
+//                              and the workgroup of tile 0 stores the slab's n, W1, W2, added in the order (wave, row group).
+//   row_dense_wmoments_finish  the mean: slabs in index order, divided by W1; the lane of element 0 stores count[q] and stat[q] =
+//                              (W1, D).  CENTRED: slabs in order, divided by divisor[2 q] — D for the variance, W1 for zbar.
+//   row_dense_wmoments_gram    row_dense_moments_gram with TWO operands: the A fragments come from a stage of w * dev of tile
+//                              I, the B fragments from a stage of dev of tile J.  Both stages are written for every pair, I == J
+//                              included (tile I is evaluated once and published twice), so LDS stays at 40 KB; the blocking,
+//                              the 16-row double-buffered stage of stride 80 and the one barrier per chunk are unchanged.
+//   row_dense_wmoments_gram_finish   row_dense_moments_gram_finish with the divisor D.
+//   row_dense_wcross_zsum      row_dense_cross_zsum adding w * z.
+//   row_dense_wcross_gram      row_dense_cross_gram<T, VEC, NB> with the weight multiplied into the staged z - zbar side (W
+//                              columns, usually narrower than the 64 elements).
+//   row_dense_wcross_finish    row_dense_cross_finish with the divisor D.
+template <typename T>
+struct RowDenseWMomArgs : RowDenseMomArgs<T> {
+    const double* w;                  // [n_rows] (w_stride 0) or [n_q, n_rows] (w_stride n_rows)
+    int64_t w_stride;
+    double* slab_w;                   // [n_q, slabs, 2] W1 and W2 of the slab
+};
+
+struct RowDenseWMomFinishArgs : RowDenseMomFinishArgs {
+    const double* slab_w;             // as above (the mean)
+    double* stat;                     // [n_q, 2] W1 and D, written with the mean
+    const double* divisor;            // stat or stat + 1, read at [2 q] (the centred sums, the Gram finish)
+};
+
+// D of the definition above; W2 / W1 is 1.0 exactly for equal weights of 1
+__device__ __forceinline__ double wmoments_divisor(double w1, double w2, int32_t correction) {
+    const double d = correction != 0 ? w1 - (double)correction * (w2 / w1) : w1;
+    return d > 0.0 ? d : 0.0;                                          // (a NaN is not > 0)
+}
+
+template <typename T, bool VEC, bool CENTRED>
+__global__ __launch_bounds__(kBlock) TDEQ_NO_PACKED_FP32 void row_dense_wmoments_sum_kernel(const RowDenseWMomArgs<T> a) {
+    using E = typename std::conditional<VEC, typename VecOf<T>::type, T>::type;
+    constexpr int LV = VEC ? VecOf<T>::L : 1;                         // elements per lane = rows per wave step
+    constexpr int kLanesPerRow = kMomTile / LV;
+    constexpr int kGroups = (kBlock / kWave) * LV;                    // per-lane sums of one column
+    __shared__ double red[kGroups * kMomTile];
+    __shared__ double wsum[kGroups * 2];
+    __shared__ int32_t cnt[kGroups];
+
+    int64_t b = blockIdx.x;
+    const int64_t slab = b % a.slabs;
+    b /= a.slabs;
+    const int64_t tile = b % a.tiles;
+    const int64_t q = b / a.tiles;
+    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+    const int col = (lane % kLanesPerRow) * LV;                       // the lane's first element inside the tile
+    const int group = wave * LV + lane / kLanesPerRow;
+    const int64_t el = tile * kMomTile + col;
+
+    double acc[LV], mean[LV], w1 = 0.0, w2 = 0.0;
+    int32_t n = 0;
+#pragma unroll
+    for (int c = 0; c < LV; ++c) acc[c] = 0.0, mean[c] = 0.0;
+    if (el < a.row_len) {                                             // (VEC: L is a whole number of lanes' elements)
+        if constexpr (CENTRED) {
+#pragma unroll
+            for (int c = 0; c < LV; ++c) mean[c] = a.mean[q * a.row_len + el + c];
+        }
+        const int64_t r_end = (slab + 1) * a.slab_rows < a.n_rows ? (slab + 1) * a.slab_rows : a.n_rows;
+        for (int64_t r = slab * a.slab_rows + group; r < r_end; r += kGroups) {
+            const int64_t i = q * a.n_rows + r;
+            const T x = a.x[i];
+            if (x != x) continue;                                     // the row has left: its weight is not read
+            int64_t s = a.seg[i];
+            s = s < 0 ? 0 : (s < a.n_seg ? s : a.n_seg - 1);          // (the search writes 0 <= seg < n_seg)
+            const double w = a.w[q * a.w_stride + r];
+            T qe[LV], qd[LV], qc[LV], qb[LV], qa[LV];
+            load_planes<T, E, LV>(a.q, a.q_plane, (s * a.row_len + el) / LV, qe, qd, qc, qb, qa);
+            ++n;
+            if constexpr (!CENTRED) {
+                w1 = w1 + w;
+                w2 = w2 + w * w;
+            }
+#pragma unroll
+            for (int c = 0; c < LV; ++c) {
+                const double v = (double)quant_value<T>(qe[c], qd[c], qc[c], qb[c], qa[c], x);
+                if constexpr (CENTRED) {
+                    const double d = v - mean[c];
+                    acc[c] = acc[c] + (w * d) * d;
+                } else {
+                    acc[c] = acc[c] + w * v;
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < LV; ++c) red[group * kMomTile + col + c] = acc[c];
+    if (col == 0) {                                                   // (element 0 of a tile exists in tile 0)
+        cnt[group] = n;
+        wsum[group * 2] = w1;
+        wsum[group * 2 + 1] = w2;
+    }
+    __syncthreads();
+    if (threadIdx.x < kMomTile && tile * kMomTile + threadIdx.x < a.row_len) {
+        double total = red[threadIdx.x];
+        for (int g = 1; g < kGroups; ++g) total = total + red[g * kMomTile + threadIdx.x];
+        a.partial[(q * a.slabs + slab) * a.row_len + tile * kMomTile + threadIdx.x] = total;
+    }
+    if (!CENTRED && tile == 0 && threadIdx.x < 3) {                   // lane 0: n, lane 1: W1, lane 2: W2
+        if (threadIdx.x == 0) {
+            int64_t total = 0;
+            for (int g = 0; g < kGroups; ++g) total += cnt[g];
+            a.slab_count[q * a.slabs + slab] = total;
+        } else {
+            const int k = (int)threadIdx.x - 1;
+            double total = wsum[k];
+            for (int g = 1; g < kGroups; ++g) total = total + wsum[g * 2 + k];
+            a.slab_w[(q * a.slabs + slab) * 2 + k] = total;
+        }
+    }
+}
+
+template <bool CENTRED>
+__global__ __launch_bounds__(kBlock) void row_dense_wmoments_finish_kernel(const RowDenseWMomFinishArgs a) {
+    const int64_t n = a.n_q * a.row_len, stride = (int64_t)gridDim.x * kBlock;
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
+        const int64_t q = i / a.row_len, el = i - q * a.row_len;
+        double total = 0.0;
+        for (int64_t s = 0; s < a.slabs; ++s) total = total + a.partial[(q * a.slabs + s) * a.row_len + el];
+        if constexpr (CENTRED) {
+            a.out[i] = total / a.divisor[2 * q];
+        } else {
+            int64_t count = 0;
+            double w1 = 0.0, w2 = 0.0;
+            for (int64_t s = 0; s < a.slabs; ++s) {
+                count += a.slab_count[q * a.slabs + s];
+                w1 = w1 + a.slab_w[(q * a.slabs + s) * 2];
+                w2 = w2 + a.slab_w[(q * a.slabs + s) * 2 + 1];
+            }
+            a.out[i] = total / w1;
+            if (el == 0) {
+                a.count[q] = count;
+                a.stat[2 * q] = w1;
+                a.stat[2 * q + 1] = wmoments_divisor(w1, w2, a.correction);
+            }
+        }
+    }
+}
+
+template <typename T, bool VEC>
+__global__ __launch_bounds__(kBlock) TDEQ_NO_PACKED_FP32 void row_dense_wmoments_gram_kernel(const RowDenseWMomArgs<T> a) {
+    using E = typename std::conditional<VEC, typename VecOf<T>::type, T>::type;
+    constexpr int LV = VEC ? VecOf<T>::L : 1;
+    constexpr int kLanesPerRow = kMomTile / LV;
+    constexpr int kRowsPerStep = kBlock / kLanesPerRow;               // rows of the chunk the 256 threads cover at once
+    constexpr int kSteps = kMomChunk / kRowsPerStep;                  // 4 (scalar), 1 (fp32 16-byte), 2 (fp64 16-byte)
+    static_assert(kSteps * kRowsPerStep == kMomChunk, "a chunk is whole steps");
+    __shared__ double stage[2][2][kMomChunk * kMomStride];            // [buffer][w dev of I, dev of J][row][element], 40 KB
+
+    int64_t b = blockIdx.x;
+    const int64_t pair = b % a.pairs;
+    b /= a.pairs;
+    const int64_t slab = b % a.slabs;
+    const int64_t q = b / a.slabs;
+    int64_t I = 0, J = pair;                                          // pairs in the order (0,0) (0,1) .. (1,1) (1,2) ..
+    while (J >= a.tiles - I) {
+        J -= a.tiles - I;
+        ++I;
+    }
+    J += I;
+    const int n_t = I == J ? 1 : 2;                                   // tiles to evaluate
+    const int col = ((int)threadIdx.x % kLanesPerRow) * LV, row0 = (int)threadIdx.x / kLanesPerRow;
+    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+
+    int64_t el[2];
+    double mean[2][LV];
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+        el[t] = (t == 0 ? I : J) * kMomTile + col;
+#pragma unroll
+        for (int c = 0; c < LV; ++c) mean[t][c] = el[t] < a.row_len ? a.mean[q * a.row_len + el[t] + c] : 0.0;
+    }
+    const int64_t r_begin = slab * a.slab_rows;
+    const int64_t r_end = r_begin + a.slab_rows < a.n_rows ? r_begin + a.slab_rows : a.n_rows;
+    const int64_t n_chunks = (r_end - r_begin + kMomChunk - 1) / kMomChunk;
+
+    double dev[2][kSteps][LV], wk[kSteps];
+    // the deviations and the weights of chunk c of the thread's cells, in registers
+    auto evaluate = [&](int64_t c) __attribute__((always_inline)) {
+#pragma unroll
+        for (int k = 0; k < kSteps; ++k) {
+            const int64_t r = r_begin + c * kMomChunk + k * kRowsPerStep + row0;
+            const bool row_ok = r < r_end;
+            const int64_t rr = row_ok ? r : r_begin;                  // (r_begin < n_rows: the slab is not empty)
+            const int64_t i = q * a.n_rows + rr;
+            const T x = a.x[i];
+            int64_t s = a.seg[i];
+            s = s < 0 ? 0 : (s < a.n_seg ? s : a.n_seg - 1);
+            const bool in = row_ok && x == x;
+            const double w = a.w[q * a.w_stride + rr];
+            wk[k] = in ? w : 0.0;                                     // selected: the weight of a row that has left is dropped
+#pragma unroll
+            for (int t = 0; t < 2; ++t) {
+#pragma unroll
+                for (int cc = 0; cc < LV; ++cc) dev[t][k][cc] = 0.0;
+                if (t < n_t && in && el[t] < a.row_len) {
+                    T qe[LV], qd[LV], qc[LV], qb[LV], qa[LV];
+                    load_planes<T, E, LV>(a.q, a.q_plane, (s * a.row_len + el[t]) / LV, qe, qd, qc, qb, qa);
+#pragma unroll
+                    for (int cc = 0; cc < LV; ++cc)
+                        dev[t][k][cc] = (double)quant_value<T>(qe[cc], qd[cc], qc[cc], qb[cc], qa[cc], x) - mean[t][cc];
+                }
+            }
+        }
+    };
+    auto publish = [&](int buf) __attribute__((always_inline)) {
+#pragma unroll
+        for (int k = 0; k < kSteps; ++k) {
+            const int at = (k * kRowsPerStep + row0) * kMomStride + col;
+#pragma unroll
+            for (int cc = 0; cc < LV; ++cc) {
+                stage[buf][0][at + cc] = wk[k] * dev[0][k][cc];
+                stage[buf][1][at + cc] = dev[n_t - 1][k][cc];
+            }
+        }
+    };
+
+    mom_f64x4 acc[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[j] = mom_f64x4{0.0, 0.0, 0.0, 0.0};
+    if (n_chunks > 0) {
+        evaluate(0);
+        publish(0);
+    }
+    __syncthreads();
+    for (int64_t c = 0; c < n_chunks; ++c) {
+        const int buf = (int)(c & 1);
+        if (c + 1 < n_chunks) evaluate(c + 1);                        // its loads are in flight during the matrix work
+        const double* const sa = stage[buf][0] + (lane / 16) * kMomStride + wave * 16 + lane % 16;
+        const double* const sb = stage[buf][1] + (lane / 16) * kMomStride + lane % 16;
+#pragma unroll
+        for (int k0 = 0; k0 < kMomChunk; k0 += 4) {
+            const double fa = sa[k0 * kMomStride];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc[j] = moments_mfma(fa, sb[k0 * kMomStride + 16 * j], acc[j]);
+        }
+        if (c + 1 < n_chunks) publish(buf ^ 1);                       // (last read before the barrier of chunk c - 1)
+        __syncthreads();
+    }
+    double* const g = a.partial + ((q * a.slabs + slab) * a.pairs + pair) * kMomBlock;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+#pragma unroll
+        for (int v = 0; v < 4; ++v) g[(wave * 16 + 4 * v + lane / 16) * kMomTile + 16 * j + lane % 16] = acc[j][v];
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void row_dense_wmoments_gram_finish_kernel(const RowDenseWMomFinishArgs a) {
+    const int64_t n = a.n_q * a.pairs * kMomBlock, stride = (int64_t)gridDim.x * kBlock;
+    for (int64_t at = (int64_t)blockIdx.x * kBlock + threadIdx.x; at < n; at += stride) {
+        const int64_t cell = at % kMomBlock, pair = at / kMomBlock % a.pairs, q = at / kMomBlock / a.pairs;
+        int64_t I = 0, J = pair;
+        while (J >= a.tiles - I) {
+            J -= a.tiles - I;
+            ++I;
+        }
+        J += I;
+        const int64_t i = I * kMomTile + cell / kMomTile, j = J * kMomTile + cell % kMomTile;
+        if (i > j || j >= a.row_len) continue;                        // (i <= j < L; the lower triangle is the mirror)
+        double total = 0.0;
+        for (int64_t s = 0; s < a.slabs; ++s) total = total + a.partial[((q * a.slabs + s) * a.pairs + pair) * kMomBlock + cell];
+        const double v = total / a.divisor[2 * q];
+        a.out[(q * a.row_len + i) * a.row_len + j] = v;
+        a.out[(q * a.row_len + j) * a.row_len + i] = v;
+        if (i == j) a.variance[q * a.row_len + i] = v;
+    }
+}
+
+template <typename T>
+struct RowDenseWCrossArgs : RowDenseCrossArgs<T> {
+    const double* w;                  // as in RowDenseWMomArgs
+    int64_t w_stride;
+};
+
+struct RowDenseWCrossFinishArgs : RowDenseCrossFinishArgs {
+    const double* divisor;            // stat + 1, read at [2 q]
+};
+
+template <typename T>
+__global__ __launch_bounds__(kBlock) void row_dense_wcross_zsum_kernel(const RowDenseWCrossArgs<T> a) {
+    constexpr int kWaves = kBlock / kWave;
+    __shared__ double red[kWaves * kMomTile];
+
+    int64_t b = blockIdx.x;
+    const int64_t slab = b % a.slabs;
+    b /= a.slabs;
+    const int64_t tile = b % a.col_tiles;
+    const int64_t q = b / a.col_tiles;
+    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+    const int64_t m = tile * kMomTile + lane;
+
+    double acc = 0.0;
+    if (m < a.n_cols) {
+        const int64_t r_end = (slab + 1) * a.slab_rows < a.n_rows ? (slab + 1) * a.slab_rows : a.n_rows;
+        for (int64_t r = slab * a.slab_rows + wave; r < r_end; r += kWaves) {
+            const T x = a.x[q * a.n_rows + r];
+            if (x != x) continue;                                     // the row has left this time's population
+            acc = acc + a.w[q * a.w_stride + r] * a.other[r * a.n_cols + m];
+        }
+    }
+    red[wave * kMomTile + lane] = acc;
+    __syncthreads();
+    if (wave == 0 && m < a.n_cols) {
+        double total = red[lane];
+        for (int w = 1; w < kWaves; ++w) total = total + red[w * kMomTile + lane];
+        a.partial[(q * a.slabs + slab) * a.n_cols + m] = total;
+    }
+}
+
+template <typename T, bool VEC, int NB>
+__global__ __launch_bounds__(kBlock) TDEQ_NO_PACKED_FP32 void row_dense_wcross_gram_kernel(const RowDenseWCrossArgs<T> a) {
+    using E = typename std::conditional<VEC, typename VecOf<T>::type, T>::type;
+    constexpr int LV = VEC ? VecOf<T>::L : 1;
+    constexpr int kLanesPerRow = kMomTile / LV;
+    constexpr int kRowsPerStep = kBlock / kLanesPerRow;               // rows of the chunk the 256 threads cover at once (y)
+    constexpr int kSteps = kMomChunk / kRowsPerStep;                  // 4 (scalar), 1 (fp32 16-byte), 2 (fp64 16-byte)
+    constexpr int W = 16 * NB;                                        // columns of the block
+    constexpr int kZStride = NB == 1 ? kCrossStride16 : kMomStride;
+    constexpr int kZRowsPerStep = kBlock / W;                         // 16 (NB = 1), 4 (NB = 4)
+    constexpr int kZSteps = kMomChunk / kZRowsPerStep;                // cells of z per thread: 1, 4
+    static_assert(kSteps * kRowsPerStep == kMomChunk && kZSteps * kZRowsPerStep == kMomChunk && (NB == 1 || NB == 4),
+                  "a chunk is whole steps");
+    __shared__ double stage_y[2][kMomChunk * kMomStride];             // [buffer][row][element], 20 KB
+    __shared__ double stage_z[2][kMomChunk * kZStride];               // [buffer][row][column], 4 / 20 KB: w (z - zbar)
+
+    int64_t b = blockIdx.x;
+    const int64_t block = b % a.blocks;
+    b /= a.blocks;
+    const int64_t slab = b % a.slabs;
+    const int64_t q = b / a.slabs;
+    const int64_t I = block / a.col_tiles, J = block % a.col_tiles;
+    const int col = ((int)threadIdx.x % kLanesPerRow) * LV, row0 = (int)threadIdx.x / kLanesPerRow;
+    const int zcol = (int)threadIdx.x % W, zrow0 = (int)threadIdx.x / W;
+    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+
+    const int64_t el = I * kMomTile + col, m = J * W + zcol;
+    const bool el_ok = el < a.row_len, m_ok = m < a.n_cols;           // (VEC: L is a whole number of lanes' elements)
+    double ybar[LV];
+#pragma unroll
+    for (int c = 0; c < LV; ++c) ybar[c] = el_ok ? a.ybar[q * a.row_len + el + c] : 0.0;
+    const double zbar = m_ok ? a.zbar[q * a.n_cols + m] : 0.0;
+    const int64_t r_begin = slab * a.slab_rows;
+    const int64_t r_end = r_begin + a.slab_rows < a.n_rows ? r_begin + a.slab_rows : a.n_rows;
+    const int64_t n_chunks = (r_end - r_begin + kMomChunk - 1) / kMomChunk;
+
+    double dy[kSteps][LV], dz[kZSteps];
+    // the deviations of chunk c of the thread's cells, in registers; the weight goes into the z side
+    auto evaluate = [&](int64_t c) __attribute__((always_inline)) {
+#pragma unroll
+        for (int k = 0; k < kSteps; ++k) {
+            const int64_t r = r_begin + c * kMomChunk + k * kRowsPerStep + row0;
+            const bool row_ok = r < r_end;
+            const int64_t i = q * a.n_rows + (row_ok ? r : r_begin);  // (r_begin < n_rows: the slab is not empty)
+            const T x = a.x[i];
+            int64_t s = a.seg[i];
+            s = s < 0 ? 0 : (s < a.n_seg ? s : a.n_seg - 1);
+#pragma unroll
+            for (int cc = 0; cc < LV; ++cc) dy[k][cc] = 0.0;
+            if (row_ok && x == x && el_ok) {
+                T qe[LV], qd[LV], qc[LV], qb[LV], qa[LV];
+                load_planes<T, E, LV>(a.q, a.q_plane, (s * a.row_len + el) / LV, qe, qd, qc, qb, qa);
+#pragma unroll
+                for (int cc = 0; cc < LV; ++cc)
+                    dy[k][cc] = (double)quant_value<T>(qe[cc], qd[cc], qc[cc], qb[cc], qa[cc], x) - ybar[cc];
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < kZSteps; ++k) {
+            const int64_t r = r_begin + c * kMomChunk + k * kZRowsPerStep + zrow0;
+            const bool row_ok = r < r_end;
+            const T x = a.x[q * a.n_rows + (row_ok ? r : r_begin)];
+            dz[k] = 0.0;
+            if (row_ok && x == x && m_ok) dz[k] = a.w[q * a.w_stride + r] * (a.other[r * a.n_cols + m] - zbar);
+        }
+    };
+    auto publish = [&](int buf) __attribute__((always_inline)) {
+#pragma unroll
+        for (int k = 0; k < kSteps; ++k) {
+#pragma unroll
+            for (int cc = 0; cc < LV; ++cc) stage_y[buf][(k * kRowsPerStep + row0) * kMomStride + col + cc] = dy[k][cc];
+        }
+#pragma unroll
+        for (int k = 0; k < kZSteps; ++k) stage_z[buf][(k * kZRowsPerStep + zrow0) * kZStride + zcol] = dz[k];
+    };
+
+    mom_f64x4 acc[NB];
+#pragma unroll
+    for (int j = 0; j < NB; ++j) acc[j] = mom_f64x4{0.0, 0.0, 0.0, 0.0};
+    if (n_chunks > 0) {
+        evaluate(0);
+        publish(0);
+    }
+    __syncthreads();
+    for (int64_t c = 0; c < n_chunks; ++c) {
+        const int buf = (int)(c & 1);
+        if (c + 1 < n_chunks) evaluate(c + 1);                        // its loads are in flight during the matrix work
+        const double* const sa = stage_y[buf] + (lane / 16) * kMomStride + wave * 16 + lane % 16;
+        const double* const sb = stage_z[buf] + (lane / 16) * kZStride + lane % 16;
+#pragma unroll
+        for (int k0 = 0; k0 < kMomChunk; k0 += 4) {
+            const double fa = sa[k0 * kMomStride];
+#pragma unroll
+            for (int j = 0; j < NB; ++j) acc[j] = moments_mfma(fa, sb[k0 * kZStride + 16 * j], acc[j]);
+        }
+        if (c + 1 < n_chunks) publish(buf ^ 1);                       // (last read before the barrier of chunk c - 1)
+        __syncthreads();
+    }
+    double* const g = a.partial + ((q * a.slabs + slab) * a.blocks + block) * (kMomTile * W);
+#pragma unroll
+    for (int j = 0; j < NB; ++j) {
+#pragma unroll
+        for (int v = 0; v < 4; ++v) g[(wave * 16 + 4 * v + lane / 16) * W + 16 * j + lane % 16] = acc[j][v];
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void row_dense_wcross_finish_kernel(const RowDenseWCrossFinishArgs a) {
+    const int64_t n = a.n_q * a.row_len * a.n_cols, stride = (int64_t)gridDim.x * kBlock;
+    const int64_t cells = (int64_t)kMomTile * a.width;
+    for (int64_t at = (int64_t)blockIdx.x * kBlock + threadIdx.x; at < n; at += stride) {
+        const int64_t m = at % a.n_cols, i = at / a.n_cols % a.row_len, q = at / a.n_cols / a.row_len;
+        const int64_t block = i / kMomTile * a.col_tiles + m / a.width;
+        const int64_t cell = i % kMomTile * a.width + m % a.width;
+        double total = 0.0;
+        for (int64_t s = 0; s < a.slabs; ++s) total = total + a.partial[((q * a.slabs + s) * a.blocks + block) * cells + cell];
+        a.out[at] = total / a.divisor[2 * q];
+    }
+}
+
 }  // namespace tdeq

@@ -913,6 +913,48 @@ class HostRowKernels:
         dev_z = torch.where(took_part, z - zbar[:, None, :], torch.zeros_like(z))
         return dev_y.transpose(1, 2) @ dev_z / (count - correction).clamp_min(0)[:, None, None]
 
+    @staticmethod
+    def _weighted_population(q, src, x, weights, Q: int, B: int, correction: int):
+        """What the two weighted definitions share -> (count int64 [Q], took part [Q, B, 1], values [Q, B, L] fp64 with zeros
+        for a row that has left, w [Q, B, 1] likewise, W1 [Q], D [Q]).  `weights` fp64 [B] or [Q, B]; D = W1 - correction * W2
+        / W1, and 0 where that is not positive or is NaN."""
+        v = HostRowKernels.eval_quartics(q, src, x).view(Q, B, -1).double()
+        took_part = (x == x).view(Q, B, 1)
+        w = weights.expand(Q, B)[:, :, None]
+        w = torch.where(took_part, w, torch.zeros_like(w))            # selected: a NaN weight of a row that has left is dropped
+        W1 = w.sum(dim=(1, 2))
+        D = W1 - (w * w).sum(dim=(1, 2)) / W1 if correction else W1
+        D = torch.where(D > 0, D, torch.zeros_like(D))
+        return took_part.sum(dim=(1, 2)), took_part, torch.where(took_part, v, torch.zeros_like(v)), w, W1, D
+
+    @staticmethod
+    def quartic_moments_weighted(q, src, x, weights, Q: int, B: int, covariance: bool, correction: int):
+        """`quartic_moments` with reliability weights (fp64 [B] or [Q, B]): the definition of tdeq_row_dense_moments_weighted
+        in plain fp64 torch ops — `count` the rows in range, mean = sum w v / W1, the centred sums over D (see
+        `_weighted_population`), the covariance `(w dev).T @ dev` with the lower triangle copied from the upper.  Torch's
+        order of the sums: the same error bound, other last bits."""
+        count, took_part, v, w, W1, D = HostRowKernels._weighted_population(q, src, x, weights, Q, B, correction)
+        mean = (w * v).sum(dim=1) / W1[:, None]
+        dev = torch.where(took_part, v - mean[:, None, :], torch.zeros_like(v))
+        if not covariance:
+            return count, mean, (w * dev * dev).sum(dim=1) / D[:, None], None
+        upper = torch.triu((w * dev).transpose(1, 2) @ dev / D[:, None, None])
+        cov = upper + torch.triu(upper, 1).transpose(1, 2)
+        return count, mean, torch.diagonal(cov, dim1=1, dim2=2).clone(), cov
+
+    @staticmethod
+    def quartic_cross_covariance_weighted(q, src, x, other, weights, Q: int, B: int, correction: int):
+        """`quartic_cross_covariance` with the weights of `quartic_moments_weighted`: the definition of
+        tdeq_row_dense_cross_weighted in plain fp64 torch ops, `dev_y.T @ (w dev_z) / D` with both means weighted."""
+        _, took_part, v, w, W1, D = HostRowKernels._weighted_population(q, src, x, weights, Q, B, correction)
+        z = other.expand(Q, B, -1)
+        z = torch.where(took_part, z, torch.zeros_like(z))
+        ybar = (w * v).sum(dim=1) / W1[:, None]
+        zbar = (w * z).sum(dim=1) / W1[:, None]
+        dev_y = torch.where(took_part, v - ybar[:, None, :], torch.zeros_like(v))
+        dev_z = torch.where(took_part, z - zbar[:, None, :], torch.zeros_like(z))
+        return dev_y.transpose(1, 2) @ (w * dev_z) / D[:, None, None]
+
     # -- calculus on a dense record (rowwise_dense.py; the arithmetic of tdeq_row_dense_prefix / tdeq_row_dense_calc) -----
     @staticmethod
     def _quartic_integral(e, d, c, b, a, x, h):

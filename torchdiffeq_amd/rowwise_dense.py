@@ -636,8 +636,22 @@ class RowDenseOutput:
         out = out.view(P, Q, *self._shape[1:])
         return out.select(1, 0) if single else out
 
+    def _weights_arg(self, what: str, weights, Q: int) -> torch.Tensor:
+        """`weights=` of `moments` / `cross_covariance` -> contiguous fp64 `[B]` or `[Q, B]` on the record's device.  The
+        values are not inspected."""
+        B = self._shape[0]
+        if not isinstance(weights, torch.Tensor):
+            raise ValueError(f"{what}: weights must be a tensor, got {type(weights).__name__}")
+        if weights.is_complex() or weights.dtype == torch.bool or tuple(weights.shape) not in ((B,), (Q, B)):
+            raise ValueError(f"{what}: weights must be a real tensor [B] or [Q, B] with Q = {Q}, B = {B}, got a "
+                             f"{weights.dtype} tensor of shape {tuple(weights.shape)}")
+        if weights.requires_grad and torch.is_grad_enabled():
+            raise NotImplementedError("odeint_rowwise_dense: the dense output does not propagate gradients (weights requires "
+                                      "grad); detach it or evaluate under torch.no_grad()")
+        return weights.detach().to(device=self.coeffs.device, dtype=torch.float64).contiguous()
+
     # -- moments across rows: two passes over the record in fp64, nothing of size [Q, B, L] is built ---------------------------
-    def moments(self, t, *, covariance: bool = False, correction: int = 1, check: bool = True) -> RowDenseMoments:
+    def moments(self, t, *, covariance: bool = False, correction: int = 1, weights=None, check: bool = True) -> RowDenseMoments:
         """Mean, variance and covariance ACROSS the rows, per time: the ensemble mean ± SD of a population of solves and the
         covariance between its state components -> `RowDenseMoments(count, mean, variance, covariance)`, all fp64 for both
         state dtypes (`count` int64), without the `Q` dimension for a single time.  `t` takes the query forms of `dense(t)`.
@@ -657,8 +671,20 @@ class RowDenseOutput:
         `(B, L)` alone and merged in a fixed order without atomics, so the result is the same from run to run and does not
         depend on the slicing.  A CPU state runs the same definition as plain torch ops in fp64: the same error bound, not the
         same last bits (another order of the sums).  The covariance with a second per-row quantity — sampled parameters, or
-        the state at another time (cross-time covariance) — is `cross_covariance(t, other)`.  Weights, row subsets, higher
-        moments, correlation matrices (divide by the SDs) and gradients are out of scope."""
+        the state at another time (cross-time covariance) — is `cross_covariance(t, other)`.  `weights`: None, or a real
+        tensor `[B]` (one set for all times) or `[Q, B]` (one set per time: the importance weights of a particle filter; a
+        single time takes `[B]` or `[1, B]`) of a floating or integer dtype on any device, taken as contiguous fp64 on the
+        record's device — the reliability weights of `numpy.cov(aweights=weights, ddof=correction)`.  With `W1 = sum_r w_r`
+        and `W2 = sum_r w_r^2` over the population, `mean_i = sum_r w_r y_ri / W1` and the centred sums `sum_r w_r (y_ri -
+        mean_i) (y_rj - mean_j)` are divided by `D = W1 - correction * W2 / W1` (a `D` that is not positive or is NaN counts
+        as zero); `count` still counts the rows in range, whatever their weights.  A row out of range contributes selected
+        zeros to every sum, `W1` and `W2` included, so a NaN in its weight does not leak; 0/1 weights select a subgroup.  The
+        weights' values are not inspected and the call makes no extra device read: a negative or non-finite weight of a row
+        in range propagates by IEEE arithmetic.  On a ROCm state the weighted call runs kernels of its own
+        (`tdeq_row_dense_moments_weighted`); with every weight 1.0 they give the bits of the unweighted call, and a weight
+        of exactly 0 gives every field but `count` the bits it has when that row is out of range.  Higher moments,
+        correlation matrices (divide by the SDs), the effective sample size, weighted quantiles and gradients are out of
+        scope."""
         what = "dense.moments(t)"
         if isinstance(correction, bool) or not isinstance(correction, int) or correction not in (0, 1):
             raise ValueError(f"{what}: correction must be the int 0 or 1, got {correction!r}")
@@ -673,6 +699,7 @@ class RowDenseOutput:
         Q, B = tq.shape
         if self._k is not None and Q * B >= _NONE:
             raise ValueError(f"{what}: {Q * B} queries in one call; the query index is a 32-bit word")
+        w = None if weights is None else self._weights_arg(what, weights, Q)
         count = torch.empty(Q, dtype=torch.int64, device=dev)
         mean, var = (torch.empty(Q, L, dtype=torch.float64, device=dev) for _ in range(2))
         cov = torch.empty(Q, L, L, dtype=torch.float64, device=dev) if covariance else None
@@ -681,21 +708,30 @@ class RowDenseOutput:
             with torch.no_grad(), device_guard(dev):
                 if self._k is None:
                     seg, x, first = self._search_host(tq)
-                    got = rowwise.HostRowKernels.quartic_moments(self.coeffs, seg, x, Q, B, covariance, correction)
+                    if w is None:
+                        got = rowwise.HostRowKernels.quartic_moments(self.coeffs, seg, x, Q, B, covariance, correction)
+                    else:
+                        got = rowwise.HostRowKernels.quartic_moments_weighted(self.coeffs, seg, x, w, Q, B, covariance,
+                                                                              correction)
                     for dst, src in zip((count, mean, var, cov), got):
                         if dst is not None:
                             dst.copy_(src)
                 else:
                     status = torch.full((1,), _NONE, dtype=torch.int32, device=dev)
                     seg, x = self._search_device(tq, status)
-                    per_time = self._k.row_dense_moments_workspace_bytes(covariance, 1, B, L, T)    # (linear in the times)
+                    space = self._k.row_dense_moments_workspace_bytes if w is None \
+                        else self._k.row_dense_moments_weighted_workspace_bytes
+                    per_time = space(covariance, 1, B, L, T)                                        # (linear in the times)
                     step = min(Q, max(1, MOMENTS_WORKSPACE_BYTES // max(per_time, 1)))
-                    work = torch.empty(self._k.row_dense_moments_workspace_bytes(covariance, step, B, L, T), dtype=torch.uint8,
-                                       device=dev)
+                    work = torch.empty(space(covariance, step, B, L, T), dtype=torch.uint8, device=dev)
                     for q0 in range(0, Q, step):
                         q1 = min(q0 + step, Q)
-                        self._k.row_dense_moments(count[q0:q1], mean[q0:q1], var[q0:q1], None if cov is None else cov[q0:q1],
-                                                  correction, self.coeffs, seg[q0 * B:q1 * B], x[q0 * B:q1 * B], work)
+                        outs = (count[q0:q1], mean[q0:q1], var[q0:q1], None if cov is None else cov[q0:q1])
+                        if w is None:
+                            self._k.row_dense_moments(*outs, correction, self.coeffs, seg[q0 * B:q1 * B], x[q0 * B:q1 * B], work)
+                        else:
+                            self._k.row_dense_moments_weighted(*outs, correction, self.coeffs, seg[q0 * B:q1 * B],
+                                                               x[q0 * B:q1 * B], work, w if w.dim() == 1 else w[q0:q1])
                     if check:
                         first = int(status)                                                    # the one read
         if check:
@@ -706,7 +742,7 @@ class RowDenseOutput:
         return RowDenseMoments(count, mean, var, cov)
 
     # -- covariance with a second per-row quantity: the mean pass of `moments`, then a rectangular Gram matrix -----------------
-    def cross_covariance(self, t, other, *, correction: int = 1, check: bool = True) -> torch.Tensor:
+    def cross_covariance(self, t, other, *, correction: int = 1, weights=None, check: bool = True) -> torch.Tensor:
         """Covariance ACROSS the rows between the state and per-row covariates, per time: `C_y,theta(t)` of an ensemble Kalman
         or smoother update, the regression-based sensitivity of every component to every sampled input (divide by the SDs),
         the covariate-effect screen of a population run -> fp64 `[Q, L, M]`, `L = prod(row_shape)`; `[L, M]` for a single
@@ -723,7 +759,13 @@ class RowDenseOutput:
         16` and 64 by 64 otherwise; `ceil(L / 64) * ceil(M / W)` must be at most 1024 blocks.  No atomics, the split is a
         rule of `(B, L, M)` alone: the same bits from run to run and for any slicing of the times; the workspace stays under
         256 MiB (or that of one time).  A CPU state runs the definition as plain fp64 torch ops: the same error bound, not
-        the same last bits.  Weights, row subsets and gradients are out of scope."""
+        the same last bits.  `weights`: None, or the `[B]` / `[Q, B]` reliability weights of `moments(t, weights=...)`, taken
+        the same way: `ybar` is the weighted mean of `moments`, `zbar_m = sum_r w_r other_rm / W1`, and `out[q, i, m] = sum_r
+        w_r (y_ri - ybar_i) (other_rm - zbar_m) / D` with `D = W1 - correction * W2 / W1` (not positive or NaN: zero).  A row
+        out of range contributes selected zeros, its weight included; the weights' values are not inspected, so a negative
+        or non-finite weight of a row in range propagates by IEEE arithmetic.  On a ROCm state the weighted call runs
+        kernels of its own (`tdeq_row_dense_cross_weighted`), which give the bits of the unweighted call for weights of
+        1.0.  Weighted quantiles and gradients are out of scope."""
         what = "dense.cross_covariance(t, other)"
         if isinstance(correction, bool) or not isinstance(correction, int) or correction not in (0, 1):
             raise ValueError(f"{what}: correction must be the int 0 or 1, got {correction!r}")
@@ -748,6 +790,7 @@ class RowDenseOutput:
         Q = tq.shape[0]
         if self._k is not None and Q * B >= _NONE:
             raise ValueError(f"{what}: {Q * B} queries in one call; the query index is a 32-bit word")
+        w = None if weights is None else self._weights_arg(what, weights, Q)
         out = torch.empty(Q, L, M, dtype=torch.float64, device=dev)
         first = _NONE
         if Q > 0:
@@ -755,19 +798,29 @@ class RowDenseOutput:
                 z = other.detach().to(device=dev, dtype=torch.float64).reshape(B, M).contiguous()
                 if self._k is None:
                     seg, x, first = self._search_host(tq)
-                    out.copy_(rowwise.HostRowKernels.quartic_cross_covariance(self.coeffs, seg, x, z, Q, B, correction))
+                    if w is None:
+                        out.copy_(rowwise.HostRowKernels.quartic_cross_covariance(self.coeffs, seg, x, z, Q, B, correction))
+                    else:
+                        out.copy_(rowwise.HostRowKernels.quartic_cross_covariance_weighted(self.coeffs, seg, x, z, w, Q, B,
+                                                                                           correction))
                 else:
                     status = torch.full((1,), _NONE, dtype=torch.int32, device=dev)
                     seg, x = self._search_device(tq, status)
-                    per_time = self._k.row_dense_cross_workspace_bytes(1, B, L, M, T)               # (linear in the times)
+                    space = self._k.row_dense_cross_workspace_bytes if w is None \
+                        else self._k.row_dense_cross_weighted_workspace_bytes
+                    per_time = space(1, B, L, M, T)                                                 # (linear in the times)
                     step = min(Q, max(1, MOMENTS_WORKSPACE_BYTES // max(per_time, 1)))
-                    work = torch.empty(self._k.row_dense_cross_workspace_bytes(step, B, L, M, T), dtype=torch.uint8, device=dev)
+                    work = torch.empty(space(step, B, L, M, T), dtype=torch.uint8, device=dev)
                     count = torch.empty(Q, dtype=torch.int64, device=dev)
                     ybar = torch.empty(Q, L, dtype=torch.float64, device=dev)
                     for q0 in range(0, Q, step):
                         q1 = min(q0 + step, Q)
-                        self._k.row_dense_cross(out[q0:q1], count[q0:q1], ybar[q0:q1], z, correction, self.coeffs,
-                                                seg[q0 * B:q1 * B], x[q0 * B:q1 * B], work)
+                        args = (out[q0:q1], count[q0:q1], ybar[q0:q1], z, correction, self.coeffs, seg[q0 * B:q1 * B],
+                                x[q0 * B:q1 * B], work)
+                        if w is None:
+                            self._k.row_dense_cross(*args)
+                        else:
+                            self._k.row_dense_cross_weighted(*args, w if w.dim() == 1 else w[q0:q1])
                     if check:
                         first = int(status)                                                    # the one read
         if check:
