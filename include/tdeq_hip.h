@@ -1166,6 +1166,51 @@ int tdeq_row_dense_cross_weighted(double* out, int64_t* count, double* ybar, con
                                   void* stream, const double* weights, int64_t w_stride);
 
 /*
+ * ---- Weighted order statistics across rows (additive symbols within ABI 38; `weights=` of `RowDenseOutput.quantiles`) ----
+ * tdeq_row_dense_quantiles_weighted   for p < n_ranks, j < n_q and every element el: out[p, j, el] = the weighted quantile
+ *                          probs[p] of the values v[r][el] of tdeq_row_dense_quantiles under w[j][r] = weights[j * w_stride +
+ *                          r] (w_stride 0 or n_rows, as for tdeq_row_dense_moments_weighted).  `probs` DEVICE double
+ *                          [n_ranks], numbers in [0, 1], duplicates allowed, NOT checked.
+ *                          Population.  The rows with x == x.  The weight of a row outside it counts as 0 and is not inspected
+ *                                   (it may be NaN): unlike tdeq_row_dense_quantiles, where such a row is a NaN VALUE.
+ *                          Validity.  Every weight of the population must be finite and >= 0 (-0.0 is 0).  If one is not, or
+ *                                   the population is empty, or its largest weight is 0, out[:, j, :] is the canonical quiet
+ *                                   NaN; other times are unaffected.  Nothing is reported to the host.
+ *                          Units.   wmax = f * 2^E, 0.5 <= f < 1, the largest weight of the population (frexp); S = 62 -
+ *                                   bit_length(n_rows); m[r] = llrint(ldexp(w[r], S - E)), ties to even, so m[r] <= 2^S and W
+ *                                   = sum_r m[r] < 2^62 is exact in integers: the weight resolution is 2^-S of the largest
+ *                                   weight (2^-45 at 65536 rows).
+ *                          Target.  K = min(max(ceil(probs[p] * (double)W), 1), W), the conversion and the product in IEEE
+ *                                   fp64, round to nearest even.
+ *                          Answer.  The smallest key k with C(k) >= K, C(k) = the sum of m[r] over the rows whose key is <= k;
+ *                                   keys, order and the canonical NaN are those of tdeq_row_dense_quantiles, and out carries
+ *                                   the bits of one of the evaluated values.  numpy.quantile(v, p, weights = w, method =
+ *                                   "inverted_cdf") wherever the weights are dyadic.  Equal weights of a power of two give
+ *                                   rank max(ceil(p * n) - 1, 0) of the n rows of the population; a weight of exactly 0 gives
+ *                                   the bits of the record without that row; scaling every weight by a power of two changes no
+ *                                   bit.
+ *                          Method.  The clear kernel (histograms, and wmax, W and flag per time); a scale kernel (the maximum
+ *                                   of the weights' unsigned 64-bit images: wave shuffles, one 64-bit atomicMax per workgroup;
+ *                                   an invalid weight: one atomicOr); a units kernel (m as uint64 [n_q, n_rows], one 64-bit
+ *                                   atomicAdd per workgroup into W); then the sizeof(T) passes of the radix select with 64-bit
+ *                                   counters in 256 x 32 histograms (64 KB of LDS; a wave covers two rows of 32 elements),
+ *                                   which skip a row with m == 0 before its coefficients are loaded, and a select kernel with
+ *                                   a 64-bit remainder.  Integer atomics only: the result depends neither on the grid nor on
+ *                                   the order of the rows.  3 + 2 * sizeof(T) launches: 11 for TDEQ_F32, 19 for TDEQ_F64.
+ *                          `workspace`: 16-byte aligned, at least tdeq_row_dense_quantiles_weighted_workspace_bytes(n_ranks,
+ *                          n_q, n_rows, row_len, dtype) = (n_ranks + 1) * n_q * ceil(row_len / 32) * 65536 + 32 * n_q + 16 *
+ *                          n_ranks * n_q * row_len + 8 * n_q * n_rows bytes (0 for arguments the entry point refuses).
+ *                          Refusals, their order and the no-ops: those of tdeq_row_dense_quantiles, with tiles of 32 elements
+ *                          in the size rule and n_q * n_rows >= INT32_MAX tested with it; also TDEQ_EINVAL for a NULL `probs`
+ *                          or `weights` and for a w_stride other than 0 or n_rows.
+ */
+size_t tdeq_row_dense_quantiles_weighted_workspace_bytes(int n_ranks, int64_t n_q, int64_t n_rows, int64_t row_len, int dtype);
+int tdeq_row_dense_quantiles_weighted(void* out, const double* probs, int n_ranks, const void* coeffs, int64_t n_seg,
+                                      const int32_t* seg, const void* x, int64_t n_q, int64_t n_rows, int64_t row_len,
+                                      void* workspace, size_t workspace_bytes, int dtype, void* stream, const double* weights,
+                                      int64_t w_stride);
+
+/*
  * ---- Per-row step options (ABI 29; `min_step`, `max_step`, `step_t`, `jump_t` of the rowwise family) ----
  * tdeq_row_control_points  tdeq_row_control with step bounds per row and with points per row: `step_t` (times a step of
  *                          the row must end on) and `jump_t` (times where func is discontinuous), rk_common.py:223-241,

@@ -357,6 +357,14 @@ ABI_SIGNATURES = {
                                                      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
                                                      ctypes.c_int64, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int,
                                                      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64]),
+    # weighted order statistics (additive symbols within ABI 38, `weights=` of `RowDenseOutput.quantiles`): the arguments of
+    # tdeq_row_dense_quantiles with `probs` (double) for `ranks`, then `weights` and `w_stride`
+    "tdeq_row_dense_quantiles_weighted_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int64, ctypes.c_int64,
+                                                                            ctypes.c_int64, ctypes.c_int]),
+    "tdeq_row_dense_quantiles_weighted": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
+                                                         ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
+                                                         ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_size_t,
+                                                         ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64]),
     # per-row step options (ABI 29, `min_step` / `max_step` / `step_t` / `jump_t` of the rowwise family)
     "tdeq_row_control_points": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(StepCtrl),
                                                ctypes.POINTER(RowState), ctypes.POINTER(RowPoints), ctypes.c_void_p,
@@ -1543,6 +1551,33 @@ class HipKernels:
                                                       dtype_code(coeffs.dtype), self._stream(), weights.data_ptr(),
                                                       0 if weights.dim() == 1 else B),
                "tdeq_row_dense_cross_weighted")
+
+    # -- weighted order statistics (`weights=` of RowDenseOutput.quantiles) -----------------------------------------------------
+    def row_dense_quantiles_weighted_workspace_bytes(self, n_ranks: int, n_q: int, n_rows: int, row_len: int, dtype) -> int:
+        """tdeq_row_dense_quantiles_weighted_workspace_bytes: the workspace of `row_dense_quantiles_weighted`."""
+        return int(self.lib.tdeq_row_dense_quantiles_weighted_workspace_bytes(n_ranks, n_q, n_rows, row_len, dtype_code(dtype)))
+
+    def row_dense_quantiles_weighted(self, out, probs, coeffs, seg, x, workspace, weights) -> None:
+        """tdeq_row_dense_quantiles_weighted: out[p, j, :] = per element the weighted quantile probs[p] of the n_rows values
+        of query time j under `weights`, fp64 [n_rows] (one set for all times) or [Q, n_rows]: the smallest value whose
+        cumulative fixed-point weight reaches ceil(probs[p] * W).  `out` [P, Q, L] of the dtype of `coeffs`, `probs` fp64 [P]
+        on the device with values in [0, 1] (not checked here: they are not read), `seg`, `x` and `workspace` as for
+        `row_dense_quantiles`, with `row_dense_quantiles_weighted_workspace_bytes(P, Q, n_rows, L, dtype)` bytes."""
+        what = "row_dense_quantiles_weighted"
+        if out.dim() != 3 or probs.dim() != 1 or out.shape[0] != probs.numel() or not out.is_contiguous():
+            raise ValueError(f"{what}: out must be a contiguous [P, Q, L] tensor for probs [P]")
+        P, Q, L = out.shape
+        if not 1 <= P <= TDEQ_ROW_QUANTILES_MAX_RANKS:
+            raise ValueError(f"{what}: 1 to {TDEQ_ROW_QUANTILES_MAX_RANKS} probs, got {P}")
+        if Q == 0 or L == 0:
+            return
+        outputs = [("out", out, coeffs.dtype, (P, Q, L)), ("probs", probs, torch.float64, (P,))]
+        B = self._row_dense_weighted_checks(what, Q, L, 0, coeffs, seg, x, weights, workspace, outputs)
+        _check(self.lib.tdeq_row_dense_quantiles_weighted(out.data_ptr(), probs.data_ptr(), P, coeffs.data_ptr(), coeffs.shape[1],
+                                                          seg.data_ptr(), x.data_ptr(), Q, B, L, workspace.data_ptr(),
+                                                          workspace.numel(), dtype_code(coeffs.dtype), self._stream(),
+                                                          weights.data_ptr(), 0 if weights.dim() == 1 else B),
+               "tdeq_row_dense_quantiles_weighted")
 
 
 class ComplexHipKernels:

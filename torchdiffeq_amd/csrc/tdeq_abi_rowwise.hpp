@@ -1637,3 +1637,112 @@ int tdeq_row_dense_cross_weighted(double* out, int64_t* count, double* ybar, con
         });
     });
 }
+
+// ---- weighted order statistics across rows: tdeq_row_dense_quantiles_weighted ------------------------------------------------
+// Additive symbols within ABI 38.  The kernels are the row_dense_wquant family (tdeq_kernels_rowwise_dense.hpp): a scale and
+// a units kernel, then the counting and the select pass per byte of the key: 2 + 2 * sizeof(T) launches after the clear.
+namespace {
+
+// the parts of the workspace, in bytes: the global histograms and behind them wmax_bits, W and flag per time (together cleared
+// in 16-byte words), the prefixes, the remainders, the units
+struct RowDenseWQuantSpace {
+    size_t hist, stat, prefix, rem, units;
+    size_t total() const { return hist + stat + prefix + rem + units; }
+};
+
+inline RowDenseWQuantSpace row_dense_wquant_space(int n_ranks, int64_t n_q, int64_t n_rows, int64_t row_len) {
+    const size_t tiles = (size_t)((row_len + kWQuantTile - 1) / kWQuantTile), cells = (size_t)n_ranks * n_q * row_len;
+    return {(size_t)(n_ranks + 1) * n_q * tiles * kQuantBins * kWQuantTile * sizeof(WQuantU), (size_t)n_q * 32,
+            cells * sizeof(WQuantU), cells * sizeof(WQuantU), (size_t)n_q * n_rows * sizeof(WQuantU)};
+}
+
+// (n_q * tiles <= INT32_MAX and n_q * n_rows < INT32_MAX, tested without overflow: the byte counts then fit a size_t)
+inline bool row_dense_wquant_sizes_ok(int n_ranks, int64_t n_q, int64_t n_rows, int64_t row_len, int dtype) {
+    if (n_ranks < 1 || n_ranks > TDEQ_ROW_QUANTILES_MAX_RANKS || n_q < 0 || n_rows < 0 || row_len < 0 || !real_dtype_ok(dtype))
+        return false;
+    if (n_q > 0x7fffffffLL || row_len > 0x7fffffffLL * kWQuantTile) return false;
+    if (n_rows > 0 && n_q > 0x7ffffffeLL / n_rows) return false;
+    const int64_t tiles = (row_len + kWQuantTile - 1) / kWQuantTile;
+    return tiles == 0 || n_q <= 0x7fffffffLL / tiles;
+}
+
+template <typename T>
+int row_dense_wquant_launch(RowDenseWQuantArgs<T>& a, size_t cleared_bytes, bool aligned, hipStream_t s) {
+    const int64_t rows = a.slabs * a.n_q, per_pass = rows * a.tiles;  // workgroups of pass 0; n_ranks times that later
+    if (per_pass * a.n_ranks > 0x7fffffffLL) return TDEQ_EINVAL;
+    RowDenseQuantClearArgs c;
+    c.hist = reinterpret_cast<u32x4*>(a.hist);
+    c.n = (int64_t)(cleared_bytes / 16);
+    const dim3 block(kBlock);
+    hipLaunchKernelGGL(row_dense_quant_clear_kernel, dim3(stream_grid(c.n, kBlock)), block, 0, s, c);
+    hipLaunchKernelGGL(row_dense_wquant_scale_kernel<T>, dim3((unsigned)rows), block, 0, s, a);
+    hipLaunchKernelGGL(row_dense_wquant_units_kernel<T>, dim3((unsigned)rows), block, 0, s, a);
+    int64_t unused;
+    return row_vec<T>(a.row_len, aligned, unused, [&](auto vec) {
+        constexpr bool VEC = decltype(vec)::value;
+        const dim3 pick(stream_grid(a.n_ranks * a.n_q * a.row_len, kBlock));
+        for (a.pass = 0; a.pass < (int)sizeof(T); ++a.pass) {
+            if (a.pass == 0) {
+                hipLaunchKernelGGL((row_dense_wquant_count_kernel<T, VEC, true>), dim3((unsigned)per_pass), block, 0, s, a);
+                hipLaunchKernelGGL((row_dense_wquant_select_kernel<T, true>), pick, block, 0, s, a);
+            } else {
+                hipLaunchKernelGGL((row_dense_wquant_count_kernel<T, VEC, false>), dim3((unsigned)(per_pass * a.n_ranks)), block,
+                                   0, s, a);
+                hipLaunchKernelGGL((row_dense_wquant_select_kernel<T, false>), pick, block, 0, s, a);
+            }
+        }
+        return check_launch();
+    });
+}
+
+}  // namespace
+
+size_t tdeq_row_dense_quantiles_weighted_workspace_bytes(int n_ranks, int64_t n_q, int64_t n_rows, int64_t row_len, int dtype) {
+    if (!row_dense_wquant_sizes_ok(n_ranks, n_q, n_rows, row_len, dtype)) return 0;
+    return row_dense_wquant_space(n_ranks, n_q, n_rows, row_len).total();
+}
+
+int tdeq_row_dense_quantiles_weighted(void* out, const double* probs, int n_ranks, const void* coeffs, int64_t n_seg,
+                                      const int32_t* seg, const void* x, int64_t n_q, int64_t n_rows, int64_t row_len,
+                                      void* workspace, size_t workspace_bytes, int dtype, void* stream, const double* weights,
+                                      int64_t w_stride) {
+    if (!out || !probs || !coeffs || !seg || !x || !workspace || !weights ||
+        !row_dense_wquant_sizes_ok(n_ranks, n_q, n_rows, row_len, dtype) || (w_stride != 0 && w_stride != n_rows))
+        return TDEQ_EINVAL;
+    if (n_seg < 1 || !aligned16(workspace)) return TDEQ_EINVAL;
+    const RowDenseWQuantSpace w = row_dense_wquant_space(n_ranks, n_q, n_rows, row_len);
+    if (workspace_bytes < w.total()) return TDEQ_EWORKSPACE;
+    if (n_q == 0 || n_rows == 0 || row_len == 0) return 0;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    char* const base = static_cast<char*>(workspace);
+    return real_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        RowDenseWQuantArgs<T> a;
+        a.q = static_cast<const T*>(coeffs);
+        a.seg = seg;
+        a.x = static_cast<const T*>(x);
+        a.probs = probs;
+        a.w = weights;
+        a.w_stride = w_stride;
+        a.out = static_cast<T*>(out);
+        a.hist = reinterpret_cast<WQuantU*>(base);
+        a.wmax_bits = reinterpret_cast<WQuantU*>(base + w.hist);                 // per time 32 bytes: 8 n_q, 8 n_q, 4 n_q, unused
+        a.total = a.wmax_bits + n_q;
+        a.flag = reinterpret_cast<uint32_t*>(a.total + n_q);
+        a.prefix = reinterpret_cast<WQuantU*>(base + w.hist + w.stat);
+        a.rem = reinterpret_cast<WQuantU*>(base + w.hist + w.stat + w.prefix);
+        a.units = reinterpret_cast<WQuantU*>(base + w.hist + w.stat + w.prefix + w.rem);
+        a.n_rows = n_rows;
+        a.n_seg = n_seg;
+        a.row_len = row_len;
+        a.q_plane = n_seg * row_len;
+        a.n_q = n_q;
+        a.tiles = (row_len + kWQuantTile - 1) / kWQuantTile;
+        a.slabs = (n_rows + kQuantSlabRows - 1) / kQuantSlabRows;
+        a.n_ranks = n_ranks;
+        a.pass = 0;
+        a.scale = 62;                                                            // S = 62 - bit_length(n_rows)
+        for (int64_t v = n_rows; v > 0; v >>= 1) --a.scale;
+        return row_dense_wquant_launch<T>(a, w.hist + w.stat, aligned16(coeffs), s);
+    });
+}

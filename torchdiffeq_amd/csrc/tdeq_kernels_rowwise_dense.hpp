@@ -1984,4 +1984,239 @@ __global__ __launch_bounds__(kBlock) void row_dense_wcross_finish_kernel(const R
     }
 }
 
+// ---- weighted order statistics across rows (additive within ABI 38): the radix select above on fixed-point weights -------
+// Per time q, with w = weights[q * w_stride + r].  POPULATION: the rows in range (x == x); the weight of a row that has left
+// is not inspected and counts as 0.  VALID: every weight of the population is finite and >= 0 (-0.0 is 0); otherwise, or when
+// the population is empty or its largest weight is 0, every output of that time is the canonical quiet NaN.  UNITS: with wmax
+// = f * 2^E (0.5 <= f < 1) the largest weight and S = 62 - bit_length(n_rows), m_r = llrint(ldexp(w_r, S - E)), ties to even:
+// m_r <= 2^S, so W = sum_r m_r < 2^62 is an exact integer in any order.  TARGET: K_p = min(max(ceil(p * double(W)), 1), W), the
+// product and the conversion in IEEE fp64.  ANSWER, per element: the smallest key v with sum of m_r over keys <= v >= K_p; the
+// keys and the canonical NaN are those of the unweighted select.  Integer sums throughout, so the result depends neither on
+// the grid nor on the order of the rows, and the host path (sort, int64 cumulative sum) gives the same bits.  Per call:
+//   row_dense_quant_clear    (as above) zeroes the global histograms and, behind them, wmax_bits, W and flag of every time
+//   row_dense_wquant_scale   a workgroup owns one time and one slab of kQuantSlabRows rows.  A non-negative double orders as
+//                            its unsigned 64-bit image: the lanes take the maximum of the images of the valid weights in
+//                            range, the wave reduces with shuffles, the four waves through LDS, and ONE 64-bit integer
+//                            atomicMax per workgroup reaches wmax_bits[q]; an invalid weight is one atomicOr into flag[q].
+//   row_dense_wquant_units   the same split: writes m[q, r] (0 for a row that has left or whose weight is invalid) and adds
+//                            the slab's sum to W[q] with one 64-bit integer atomicAdd.  The later passes read m alone.
+//   then for d = 0 .. NB - 1:
+//   row_dense_wquant_count   the work split of row_dense_quant_count with 64-bit counters, hence a tile of kWQuantTile = 32
+//                            elements: hist[256][32] of uint64 is 64 KB of LDS, two workgroups per CU of 160 KB as before.
+//                            A wave covers TWO rows per step, lanes 0 - 31 on one and 32 - 63 on the next (128 B per plane
+//                            load in fp32, 256 B in fp64); 16-byte form: a lane holds LV neighbouring elements and the wave
+//                            covers 2 LV rows.  In the scalar form the lanes of a half-wave never meet on a counter; the two
+//                            halves and the four waves do (64-bit LDS atomicAdd of m).  A row with m == 0 is skipped BEFORE
+//                            seg, x and its planes are loaded: a 0/1 selection pays for the subgroup.  The nonzero counters
+//                            go to the global histogram of (set, query, tile) with 64-bit integer atomicAdd.
+//   row_dense_wquant_select  row_dense_quant_select with a 64-bit k: pass 0 forms K_p from probs[p] and W[q] and starts from
+//                            k = K_p - 1; the last pass stores the canonical NaN where flag[q] is set or W[q] == 0.
+// No floating-point atomics; quant_value unchanged and TDEQ_NO_PACKED_FP32 on the counting kernel; 64-bit offsets; no scratch.
+constexpr int kWQuantTile = 32;
+static_assert(kWave == 2 * kWQuantTile && kQuantSlabRows % ((kBlock / kWave) * 2 * 4) == 0 && kQuantSlabRows % kBlock == 0,
+              "a slab is whole wave steps");
+
+typedef unsigned long long WQuantU;                                   // the type of the 64-bit integer atomics
+
+template <typename T>
+struct RowDenseWQuantArgs {
+    const T* q;                       // [5, n_seg, L]
+    const int32_t* seg;               // [n_q * n_rows]
+    const T* x;                       // [n_q * n_rows]
+    const double* probs;              // [n_ranks]
+    const double* w;                  // [n_rows] (w_stride 0) or [n_q, n_rows] (w_stride n_rows)
+    int64_t w_stride;
+    T* out;                           // [n_ranks, n_q, L]
+    WQuantU* hist;                    // [n_ranks + 1, n_q, tiles, 256, 32]
+    WQuantU* wmax_bits;               // [n_q] the image of the largest valid weight in range
+    WQuantU* total;                   // [n_q] W
+    uint32_t* flag;                   // [n_q] nonzero: an invalid weight in range
+    WQuantU* prefix;                  // [n_ranks, n_q, L] the bytes of the key selected so far, in place
+    WQuantU* rem;                     // [n_ranks, n_q, L] the units still to pass among the rows that share the prefix
+    WQuantU* units;                   // [n_q, n_rows] m
+    int64_t n_rows;
+    int64_t n_seg;
+    int64_t row_len;                  // T units
+    int64_t q_plane;                  // n_seg * L
+    int64_t n_q;
+    int64_t tiles;                    // ceil(L / 32)
+    int64_t slabs;                    // ceil(n_rows / kQuantSlabRows)
+    int32_t n_ranks;
+    int32_t pass;                     // d
+    int32_t scale;                    // S
+};
+
+// is w a weight the definition takes, and its ordered image (-0.0 is 0)
+__device__ __forceinline__ bool wquant_valid(double w) { return w >= 0.0 && w < __builtin_inf(); }      // (a NaN fails both)
+__device__ __forceinline__ WQuantU wquant_image(double w) { return w == 0.0 ? 0ull : (WQuantU)__double_as_longlong(w); }
+
+// E of frexp from the image of a positive finite double: normal 1.m * 2^(e - 1023) = 0.1m * 2^(e - 1022); a subnormal is its
+// significand times 2^-1074
+__device__ __forceinline__ int wquant_exponent(WQuantU image) {
+    const int biased = (int)(image >> 52);
+    return biased ? biased - 1022 : (image ? 64 - __clzll((long long)image) : 0) - 1074;
+}
+
+template <typename T>
+__global__ __launch_bounds__(kBlock) void row_dense_wquant_scale_kernel(const RowDenseWQuantArgs<T> a) {
+    __shared__ WQuantU top[kBlock / kWave];
+    __shared__ uint32_t bad[kBlock / kWave];
+    const int64_t slab = blockIdx.x % a.slabs, q = blockIdx.x / a.slabs;
+    const int64_t r_end = (slab + 1) * kQuantSlabRows < a.n_rows ? (slab + 1) * kQuantSlabRows : a.n_rows;
+    WQuantU best = 0ull;
+    uint32_t invalid = 0u;
+    for (int64_t r = slab * kQuantSlabRows + threadIdx.x; r < r_end; r += kBlock) {
+        const T x = a.x[q * a.n_rows + r];
+        if (x != x) continue;                                         // the row has left: its weight is not read
+        const double w = a.w[q * a.w_stride + r];
+        if (wquant_valid(w)) {
+            const WQuantU u = wquant_image(w);
+            best = u > best ? u : best;
+        } else {
+            invalid = 1u;
+        }
+    }
+    for (int off = kWave / 2; off > 0; off >>= 1) {
+        const WQuantU other = __shfl_xor(best, off, kWave);
+        best = other > best ? other : best;
+        invalid |= __shfl_xor(invalid, off, kWave);
+    }
+    if ((threadIdx.x & (kWave - 1)) == 0) {
+        top[threadIdx.x / kWave] = best;
+        bad[threadIdx.x / kWave] = invalid;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int v = 1; v < kBlock / kWave; ++v) {
+            best = top[v] > best ? top[v] : best;
+            invalid |= bad[v];
+        }
+        atomicMax(a.wmax_bits + q, best);
+        if (invalid) atomicOr(a.flag + q, 1u);
+    }
+}
+
+template <typename T>
+__global__ __launch_bounds__(kBlock) void row_dense_wquant_units_kernel(const RowDenseWQuantArgs<T> a) {
+    __shared__ WQuantU part[kBlock / kWave];
+    const int64_t slab = blockIdx.x % a.slabs, q = blockIdx.x / a.slabs;
+    const int64_t r_end = (slab + 1) * kQuantSlabRows < a.n_rows ? (slab + 1) * kQuantSlabRows : a.n_rows;
+    const int shift = a.scale - wquant_exponent(a.wmax_bits[q]);      // (can exceed 1023: ldexp, never a product with 2^k)
+    WQuantU sum = 0ull;
+    for (int64_t r = slab * kQuantSlabRows + threadIdx.x; r < r_end; r += kBlock) {
+        const int64_t i = q * a.n_rows + r;
+        const T x = a.x[i];
+        WQuantU m = 0ull;
+        if (x == x) {
+            const double w = a.w[q * a.w_stride + r];
+            if (wquant_valid(w)) m = (WQuantU)llrint(ldexp(w, shift));                    // <= 2^S: w <= wmax < 2^E
+        }
+        a.units[i] = m;
+        sum += m;
+    }
+    for (int off = kWave / 2; off > 0; off >>= 1) sum += __shfl_xor(sum, off, kWave);
+    if ((threadIdx.x & (kWave - 1)) == 0) part[threadIdx.x / kWave] = sum;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int v = 1; v < kBlock / kWave; ++v) sum += part[v];
+        if (sum) atomicAdd(a.total + q, sum);
+    }
+}
+
+template <typename T, bool VEC, bool FIRST>
+__global__ __launch_bounds__(kBlock) TDEQ_NO_PACKED_FP32 void row_dense_wquant_count_kernel(const RowDenseWQuantArgs<T> a) {
+    using E = typename std::conditional<VEC, typename VecOf<T>::type, T>::type;
+    using U = typename QuantKey<T>::U;
+    constexpr int LV = VEC ? VecOf<T>::L : 1;                         // elements per lane
+    constexpr int kLanesPerRow = kWQuantTile / LV;
+    constexpr int kRowsPerWave = kWave / kLanesPerRow;                // 2 LV rows per wave step
+    __shared__ WQuantU hist[kQuantBins * kWQuantTile];
+    for (int j = threadIdx.x; j < kQuantBins * kWQuantTile; j += kBlock) hist[j] = 0ull;
+    __syncthreads();
+
+    int64_t b = blockIdx.x;
+    const int64_t slab = b % a.slabs;
+    b /= a.slabs;
+    const int64_t tile = b % a.tiles;
+    b /= a.tiles;
+    const int64_t q = b % a.n_q;
+    const int64_t p = b / a.n_q;                                      // (FIRST: one set, p == 0)
+    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+    const int col = (lane % kLanesPerRow) * LV;                       // the lane's first element inside the tile
+    const int64_t el = tile * kWQuantTile + col;
+    const int shift = 8 * ((int)sizeof(T) - 1 - a.pass);
+
+    if (el < a.row_len) {                                             // (VEC: L is a whole number of lanes' elements)
+        U want[LV];
+#pragma unroll
+        for (int c = 0; c < LV; ++c) want[c] = FIRST ? (U)0 : (U)(a.prefix[(p * a.n_q + q) * a.row_len + el + c] >> (shift + 8));
+        const int64_t r_end = (slab + 1) * kQuantSlabRows < a.n_rows ? (slab + 1) * kQuantSlabRows : a.n_rows;
+        for (int64_t r = slab * kQuantSlabRows + wave * kRowsPerWave + lane / kLanesPerRow; r < r_end;
+             r += (kBlock / kWave) * kRowsPerWave) {
+            const int64_t i = q * a.n_rows + r;
+            const WQuantU m = a.units[i];
+            if (m == 0ull) continue;                                  // no weight, or the row has left: nothing is loaded
+            int64_t s = a.seg[i];
+            s = s < 0 ? 0 : (s < a.n_seg ? s : a.n_seg - 1);          // (the search writes 0 <= seg < n_seg)
+            const T x = a.x[i];
+            T qe[LV], qd[LV], qc[LV], qb[LV], qa[LV];
+            load_planes<T, E, LV>(a.q, a.q_plane, (s * a.row_len + el) / LV, qe, qd, qc, qb, qa);
+#pragma unroll
+            for (int c = 0; c < LV; ++c) {
+                const U key = quant_key<T>(quant_value<T>(qe[c], qd[c], qc[c], qb[c], qa[c], x));
+                bool mine = true;
+                if constexpr (!FIRST) mine = (key >> (shift + 8)) == want[c];
+                if (mine) atomicAdd(&hist[(int)((key >> shift) & 0xff) * kWQuantTile + col + c], m);
+            }
+        }
+    }
+    __syncthreads();
+    WQuantU* const g = a.hist + ((((FIRST ? 0 : 1 + p) * a.n_q + q) * a.tiles + tile) * kQuantBins) * kWQuantTile;
+    for (int j = threadIdx.x; j < kQuantBins * kWQuantTile; j += kBlock) {
+        const WQuantU n = hist[j];
+        if (n) atomicAdd(g + j, n);
+    }
+}
+
+template <typename T, bool FIRST>
+__global__ __launch_bounds__(kBlock) void row_dense_wquant_select_kernel(const RowDenseWQuantArgs<T> a) {
+    using U = typename QuantKey<T>::U;
+    const int64_t per_rank = a.n_q * a.row_len, n = a.n_ranks * per_rank;
+    const int64_t stride = (int64_t)gridDim.x * kBlock;
+    const int shift = 8 * ((int)sizeof(T) - 1 - a.pass);
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
+        const int64_t p = i / per_rank, at = i - p * per_rank;
+        const int64_t q = at / a.row_len, el = at - q * a.row_len;
+        WQuantU* const h = a.hist + ((((FIRST ? 0 : 1 + p) * a.n_q + q) * a.tiles + el / kWQuantTile) * kQuantBins) * kWQuantTile
+                           + el % kWQuantTile;
+        const WQuantU total = a.total[q];
+        WQuantU k;
+        if constexpr (FIRST) {
+            WQuantU target = (WQuantU)ceil(a.probs[p] * (double)total);                   // K_p: < 2^62, exact
+            target = target < 1ull ? 1ull : target;
+            target = target > total ? total : target;
+            k = target ? target - 1ull : 0ull;                        // (W == 0: the NaN below)
+        } else {
+            k = a.rem[i];
+        }
+        int bin = kQuantBins - 1;
+        bool found = false;
+        for (int j = 0; j < kQuantBins; ++j) {
+            const WQuantU c = h[j * kWQuantTile];
+            if constexpr (!FIRST) h[j * kWQuantTile] = 0ull;          // for the next pass of this rank
+            const bool here = !found && k < c;
+            bin = here ? j : bin;
+            found = found || here;
+            k = found ? k : k - c;
+        }
+        const U key = (FIRST ? (U)0 : (U)a.prefix[i]) | ((U)bin << shift);
+        if (shift == 0) {
+            a.out[i] = (a.flag[q] != 0u || total == 0ull) ? QuantKey<T>::value(QuantKey<T>::kQuietNan) : quant_unkey<T>(key);
+        } else {
+            a.prefix[i] = key;
+            a.rem[i] = k;
+        }
+    }
+}
+
 }  // namespace tdeq

@@ -877,6 +877,40 @@ class HostRowKernels:
         return torch.where(picked == top, torch.full_like(back, float("nan")), back)
 
     @staticmethod
+    def quartic_quantiles_weighted(q, src, x, probs, weights, Q: int, B: int) -> torch.Tensor:
+        """The weighted quantiles `probs[p]` (Python floats in [0, 1]) across the B rows of each of the Q query times, per
+        element, under `weights` (fp64 [B] or [Q, B]) -> [P, Q, L].  The model of tdeq_row_dense_quantiles_weighted, bit for
+        bit: the population is the rows with `x == x`; with wmax = f * 2^E its largest weight (frexp) and S = 62 -
+        bit_length(B), m_r = rint(ldexp(w_r, S - E)) as an integer, 0 for a row that has left; W = sum_r m_r; K_p =
+        min(max(ceil(p * float(W)), 1), W); the answer is the key of `quartic_quantiles` at the first place of the sorted
+        rows where the int64 cumulative sum of m reaches K_p.  A time with a negative or non-finite weight in range, or with W
+        == 0, is all NaN."""
+        v = HostRowKernels.eval_quartics(q, src, x).view(Q, B, -1)
+        I = torch.int32 if v.dtype == torch.float32 else torch.int64
+        top = torch.iinfo(I).max
+        bits = v.contiguous().view(I)
+        key = torch.where(bits < 0, bits ^ top, bits)
+        key = torch.where(torch.isnan(v), torch.full_like(key, top), key).transpose(1, 2)           # [Q, L, B]
+        took_part = (x == x).view(Q, B).numpy()
+        w = weights.expand(Q, B).numpy()
+        with np.errstate(invalid="ignore"):
+            valid = took_part & (w >= 0) & (w < np.inf)
+        bad = (took_part & ~valid).any(axis=1)
+        w = np.where(valid, w, 0.0)                                   # (-0.0 is 0 under frexp and rint alike)
+        E = np.frexp(w.max(axis=1))[1]
+        units = np.rint(np.ldexp(w, ((62 - int(B).bit_length()) - E)[:, None])).astype(np.int64)   # a true ldexp: S - E > 1023
+        totals = [int(t) for t in units.sum(axis=1)]
+        targets = [[min(max(math.ceil(float(p) * float(W)), 1), W) for p in probs] for W in totals]
+        key, order = torch.sort(key, dim=2)
+        cum = torch.from_numpy(units)[:, None, :].expand_as(order).gather(2, order).cumsum(dim=2)
+        K = torch.tensor(targets, dtype=torch.int64)[:, None, :].expand(Q, key.shape[1], len(probs)).contiguous()
+        at = torch.searchsorted(cum, K).clamp_max(B - 1)
+        picked = key.gather(2, at).permute(2, 0, 1).contiguous()                                   # [P, Q, L]
+        back = torch.where(picked < 0, picked ^ top, picked).view(v.dtype)
+        nan = (picked == top) | torch.tensor([b or W == 0 for b, W in zip(bad, totals)])[None, :, None]
+        return torch.where(nan, torch.full_like(back, float("nan")), back)
+
+    @staticmethod
     def quartic_moments(q, src, x, Q: int, B: int, covariance: bool, correction: int):
         """Count, mean, variance and (or None) covariance across the rows of each of the Q query times that are in range (`x
         == x`): the queries (src, x) [Q * B] of the search on the record `q` [5, n_seg, L] -> (int64 [Q], fp64 [Q, L], fp64

@@ -561,8 +561,8 @@ class RowDenseOutput:
         return self.exposure(level, ta, tb, check).area_below
 
     # -- order statistics across rows: a radix select on the record, nothing of size [Q, B, L] is built ----------------------
-    def _quantile_ranks(self, what: str, probs, ranks) -> list:
-        """`probs` or `ranks` -> the P ranks as Python ints in [0, B - 1]."""
+    def _quantile_ranks(self, what: str, probs, ranks, as_probs: bool = False) -> list:
+        """`probs` or `ranks` -> the P ranks as Python ints in [0, B - 1]; `as_probs`: the checked probs as Python floats."""
         B = self._shape[0]
         if (probs is None) == (ranks is None):
             raise ValueError(f"{what}: give exactly one of probs and ranks")
@@ -577,14 +577,14 @@ class RowDenseOutput:
             if ranks is None:
                 if isinstance(v, bool) or not isinstance(v, numbers.Real) or not 0.0 <= v <= 1.0:      # (a NaN fails both)
                     raise ValueError(f"{what}: probs must be numbers in [0, 1], got {v!r}")
-                out.append(int(math.floor(float(v) * (B - 1))))                                      # the "lower" rule
+                out.append(float(v) if as_probs else int(math.floor(float(v) * (B - 1))))            # the "lower" rule
             else:
                 if isinstance(v, bool) or not isinstance(v, numbers.Integral) or not 0 <= v <= B - 1:
                     raise ValueError(f"{what}: ranks must be integers in [0, B - 1] = [0, {B - 1}], got {v!r}")
                 out.append(int(v))
         return out
 
-    def quantiles(self, t, probs=None, *, ranks=None, check: bool = True) -> torch.Tensor:
+    def quantiles(self, t, probs=None, *, ranks=None, weights=None, check: bool = True) -> torch.Tensor:
         """Order statistics ACROSS the B rows: per time and per ELEMENT of the row, the value of rank `k_p` (0 = the smallest)
         among the B values `dense(t)[q, :, ...]` -> `[P, Q, *row_shape]` in the state's dtype (`[P, *row_shape]` for a single
         time) — the 5 % / 50 % / 95 % bands of a population of simulated patients, the envelope of an ensemble.  `t` takes the
@@ -600,14 +600,42 @@ class RowDenseOutput:
         to the outputs the call allocates the search's `[Q, B]` lists and a workspace of at most 256 MiB (or that of one
         query time), and runs the times in slices that fit it.  A CPU state sorts the same integer keys with torch ops: the
         same bits.  Counts are integers, so the result does not depend on the order of the rows.  Means, variances and
-        covariances across the rows are `moments(t)`; row subsets, weights and gradients are out of scope."""
+        covariances across the rows are `moments(t)`; gradients are out of scope.
+
+        `weights`: None, or the `[B]` / `[Q, B]` weights of `moments(t, weights=...)`, taken the same way (a real tensor of a
+        floating or integer dtype on any device, as contiguous fp64; a single time takes `[B]` or `[1, B]`): WEIGHTED order
+        statistics, the credible band of weighted particles, the band of a 0/1 subgroup.  `probs` is then required and
+        `ranks=` is a ValueError (an integer rank has no meaning under real weights).  The definition is exact, independent
+        of the order of the rows, and the same bits on both paths.  Population: the rows whose query is in range; with
+        `check=False` an out-of-range row has LEFT the population and its weight counts as 0, as in `moments` — its weight
+        may be NaN without effect — which differs from the unweighted call, where such a row counts as a NaN value.
+        Validity: every weight of a row in range must be finite and `>= 0` (`-0.0` is 0); if one is not, or the population
+        is empty, or its largest weight is 0, every output of that time is NaN, the other times are unaffected, and nothing
+        is read or raised.  Fixed-point weights: with `wmax = f * 2^E`, `0.5 <= f < 1`, the largest weight of the population
+        and `S = 62 - B.bit_length()`, `m_r = rint(ldexp(w_r, S - E))` (ties to even) as an integer, so `W = sum_r m_r <
+        2^62` is exact in any order; the weight resolution is `2^-S` of the largest weight, 2^-45 at B = 65536.  Target: `K_p
+        = min(max(ceil(p * float(W)), 1), W)` in IEEE fp64.  Answer, per element: the smallest value `v` whose cumulative
+        weight `sum of m_r over the rows with value <= v` reaches `K_p`, in the order and with the bits of the unweighted
+        call — `numpy.quantile(dense(t), p, axis=..., weights=w, method="inverted_cdf")` wherever the weights are dyadic.
+        Three identities follow.  Weights that are all 1.0, or all the same power of two, give rank `max(ceil(p * n) - 1,
+        0)` of the `n` rows in range (`p * n` a Python double product): NOT the `floor(p * (B - 1))` of the unweighted
+        `probs`; the unweighted call that matches is `quantiles(t, ranks=[...])`.  Other equal weights, such as 3.7, can
+        differ from that by one rank where `p * n` is an integer: a rounding of `p * W`, not a defect.  A weight of exactly
+        0 gives the bits of the same record without that row.  Scaling all weights by a power of two changes no bit.  A
+        ROCm state runs kernels of its own (`tdeq_row_dense_quantiles_weighted`): the largest weight by integer `atomicMax`
+        on the weights' bit images, the units `m` as uint64 `[Q, B]` in the workspace, then the radix select with 64-bit
+        counters, which skips a row of weight 0 before it loads its coefficients, so a subgroup costs what the subgroup
+        costs.  Integer atomics only; the times are sliced as above."""
         what = "dense.quantiles(t)"
-        ks = self._quantile_ranks(what, probs, ranks)
+        if weights is not None and ranks is not None:
+            raise ValueError(f"{what}: ranks has no meaning under weights; give probs")
+        ks = self._quantile_ranks(what, probs, ranks, as_probs=weights is not None)
         tqs, single = self._query_lists(what, ("t",), (t,))
         tq = tqs[0]
         Q, B = tq.shape
         if self._k is not None and Q * B >= _NONE:
             raise ValueError(f"{what}: {Q * B} queries in one call; the query index is a 32-bit word")
+        w = None if weights is None else self._weights_arg(what, weights, Q)
         P, L, dev, T = len(ks), self.coeffs.shape[2], self.coeffs.device, self.coeffs.dtype
         out = torch.empty(P, Q, L, dtype=T, device=dev)
         first = _NONE
@@ -615,18 +643,26 @@ class RowDenseOutput:
             with torch.no_grad(), device_guard(dev):
                 if self._k is None:
                     seg, x, first = self._search_host(tq)
-                    out.copy_(rowwise.HostRowKernels.quartic_quantiles(self.coeffs, seg, x, ks, Q, B))
+                    if w is None:
+                        out.copy_(rowwise.HostRowKernels.quartic_quantiles(self.coeffs, seg, x, ks, Q, B))
+                    else:
+                        out.copy_(rowwise.HostRowKernels.quartic_quantiles_weighted(self.coeffs, seg, x, ks, w, Q, B))
                 else:
                     status = torch.full((1,), _NONE, dtype=torch.int32, device=dev)
                     seg, x = self._search_device(tq, status)
-                    on_dev = torch.tensor(ks, dtype=torch.int32, device=dev)
-                    per_time = self._k.row_dense_quantiles_workspace_bytes(P, 1, L, T)        # (linear in the times)
+                    on_dev = torch.tensor(ks, dtype=torch.int32 if w is None else torch.float64, device=dev)
+                    per_time = self._k.row_dense_quantiles_workspace_bytes(P, 1, L, T) if w is None \
+                        else self._k.row_dense_quantiles_weighted_workspace_bytes(P, 1, B, L, T)  # (linear in the times)
                     step = min(Q, max(1, QUANTILES_WORKSPACE_BYTES // max(per_time, 1)))
                     work = torch.empty(step * per_time, dtype=torch.uint8, device=dev)
                     for q0 in range(0, Q, step):
                         q1 = min(q0 + step, Q)
                         part = out if q1 - q0 == Q else torch.empty(P, q1 - q0, L, dtype=T, device=dev)
-                        self._k.row_dense_quantiles(part, on_dev, self.coeffs, seg[q0 * B:q1 * B], x[q0 * B:q1 * B], work)
+                        if w is None:
+                            self._k.row_dense_quantiles(part, on_dev, self.coeffs, seg[q0 * B:q1 * B], x[q0 * B:q1 * B], work)
+                        else:
+                            self._k.row_dense_quantiles_weighted(part, on_dev, self.coeffs, seg[q0 * B:q1 * B], x[q0 * B:q1 * B],
+                                                                 work, w if w.dim() == 1 else w[q0:q1])
                         if part is not out:
                             out[:, q0:q1] = part
                     if check:
@@ -683,8 +719,8 @@ class RowDenseOutput:
         in range propagates by IEEE arithmetic.  On a ROCm state the weighted call runs kernels of its own
         (`tdeq_row_dense_moments_weighted`); with every weight 1.0 they give the bits of the unweighted call, and a weight
         of exactly 0 gives every field but `count` the bits it has when that row is out of range.  Higher moments,
-        correlation matrices (divide by the SDs), the effective sample size, weighted quantiles and gradients are out of
-        scope."""
+        correlation matrices (divide by the SDs), the effective sample size and gradients are out of scope; weighted
+        quantiles are `quantiles(t, probs, weights=...)`."""
         what = "dense.moments(t)"
         if isinstance(correction, bool) or not isinstance(correction, int) or correction not in (0, 1):
             raise ValueError(f"{what}: correction must be the int 0 or 1, got {correction!r}")
@@ -765,7 +801,7 @@ class RowDenseOutput:
         out of range contributes selected zeros, its weight included; the weights' values are not inspected, so a negative
         or non-finite weight of a row in range propagates by IEEE arithmetic.  On a ROCm state the weighted call runs
         kernels of its own (`tdeq_row_dense_cross_weighted`), which give the bits of the unweighted call for weights of
-        1.0.  Weighted quantiles and gradients are out of scope."""
+        1.0.  Weighted quantiles are `quantiles(t, probs, weights=...)`; gradients are out of scope."""
         what = "dense.cross_covariance(t, other)"
         if isinstance(correction, bool) or not isinstance(correction, int) or correction not in (0, 1):
             raise ValueError(f"{what}: correction must be the int 0 or 1, got {correction!r}")
@@ -939,6 +975,9 @@ def odeint_rowwise_dense(func, y0, t0, t1, *, rtol=1e-7, atol=1e-9, method="dopr
     histograms in LDS, and never build `[Q, B, *row_shape]`; the counts are integers, so the answer depends neither on the grid
     nor on the order of the rows, and the torch path of a CPU state has the same bits.  `check` as for `dense(t)`; with
     `check=False` an out-of-range row is a NaN of its time's population.  A workspace of at most 256 MiB; nothing is cached.
+    `dense.quantiles(t, probs, weights=w)` gives WEIGHTED order statistics for `[B]` or `[Q, B]` weights: the weights become
+    integers of a fixed-point scale set by the largest one, and the same select runs with 64-bit counters
+    (`tdeq_row_dense_quantiles_weighted`); a row out of range has then left the population.
 
     Moments across rows: `dense.moments(t, covariance=False, correction=1)` -> `RowDenseMoments(count, mean, variance,
     covariance)`, per time the number of rows in range, per element their mean and variance and, on request, the `[L, L]`
