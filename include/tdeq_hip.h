@@ -71,6 +71,8 @@ extern "C" {
 #define TDEQ_CHUNK_QUANTUM 1024
 #define TDEQ_ROW_QUANTILES_MAX_RANKS 16   /* tdeq_row_dense_quantiles */
 #define TDEQ_ROW_QUANTILES_SLAB_ROWS 1024  /* rows of one workgroup of its counting pass */
+#define TDEQ_ROW_RANKS_MAX_VALUES 16      /* tdeq_row_dense_ranks: thresholds of one call */
+#define TDEQ_ROW_RANKS_GROUP_VALUES 4     /* thresholds one workgroup of its counting kernel holds in registers */
 #define TDEQ_ROW_MOMENTS_SLAB_ROWS 1024    /* tdeq_row_dense_moments: rows of one workgroup of its sum passes */
 #define TDEQ_ROW_MOMENTS_MAX_COV_LEN 1024  /* the longest row it takes with a covariance */
 #define TDEQ_ROW_CROSS_MAX_BLOCKS 1024     /* tdeq_row_dense_cross: ceil(row_len / 64) * ceil(n_cols / W) at most */
@@ -1209,6 +1211,54 @@ int tdeq_row_dense_quantiles_weighted(void* out, const double* probs, int n_rank
                                       const int32_t* seg, const void* x, int64_t n_q, int64_t n_rows, int64_t row_len,
                                       void* workspace, size_t workspace_bytes, int dtype, void* stream, const double* weights,
                                       int64_t w_stride);
+
+/*
+ * ---- Population ranks of given values (additive symbols within ABI 38; `RowDenseOutput.ranks` / `cdf`) ----
+ * tdeq_row_dense_ranks     the inverse of tdeq_row_dense_quantiles: for v < n_values, j < n_q and every element el, with the
+ *                          n_rows values y[r][el] of tdeq_row_dense_quantiles (same record, seg and x; the bits of
+ *                          tdeq_row_event_eval_mapped) and the threshold values[v, j, el]:
+ *                              below[v, j, el] = the number of rows r with key(y[r][el]) <  key(values[v, j, el])
+ *                              equal[v, j, el] = the number of rows r with key(y[r][el]) == key(values[v, j, el])
+ *                          Order.   The key of tdeq_row_dense_quantiles: -inf < ... < -0.0 < +0.0 < ... < +inf < NaN, every NaN
+ *                                   the one largest key.  A threshold may be NaN or infinite.
+ *                          Population.  All n_rows rows: a query the search found out of range has x = NaN, hence the value
+ *                                   NaN.  For every rank k < n_rows and v = the value tdeq_row_dense_quantiles selects for it:
+ *                                   below(v) <= k < below(v) + equal(v).
+ *                          `below`, `equal` int64 [n_values, n_q, row_len]; `values` [n_values, n_q, row_len] of the state type
+ *                          T, 1 <= n_values <= TDEQ_ROW_RANKS_MAX_VALUES.
+ *                          Method.  A clear launch, then ONE counting pass over the record: a workgroup takes one query, 64
+ *                                   elements, TDEQ_ROW_QUANTILES_SLAB_ROWS rows and TDEQ_ROW_RANKS_GROUP_VALUES thresholds,
+ *                                   counts in registers and adds its nonzero counts with 64-bit integer atomics.  Integer sums:
+ *                                   the result depends neither on the grid nor on the order of the rows.  No workspace.
+ *                          16-byte loads when row_len is a multiple of 16 / sizeof(T) and `coeffs` is 16-byte aligned, scalar
+ *                          loads otherwise, with the same result.  A NULL pointer, a negative size, n_values out of range,
+ *                          n_seg < 1, n_q * n_rows >= INT32_MAX, n_q * ceil(row_len / 64) > INT32_MAX, more than INT32_MAX
+ *                          workgroups, or a dtype other than TDEQ_F32 / TDEQ_F64: TDEQ_EINVAL before any launch.  n_q == 0,
+ *                          n_rows == 0 or row_len == 0: no-op.
+ * tdeq_row_dense_ranks_weighted   the same under w[j][r] = weights[j * w_stride + r] (w_stride 0 or n_rows), with the population,
+ *                          validity rule and fixed-point units m[r] of tdeq_row_dense_quantiles_weighted (S = 62 -
+ *                          bit_length(n_rows), scale set by the largest weight of the rows with x == x; the weight of a row
+ *                          outside them is not inspected): below and equal are the sums of m[r] over those rows, total[j]
+ *                          (int64 [n_q]) = W = sum_r m[r].  An invalid time (a negative or non-finite weight in range, an empty
+ *                          population, a largest weight of 0) has below = equal = 0 and total = 0; other times are unaffected
+ *                          and nothing is reported to the host.  Scaling every weight by a power of two changes no bit.
+ *                          Method.  The clear launch (also wmax_bits, W and flag per time), the scale and the units kernel of
+ *                                   tdeq_row_dense_quantiles_weighted, the counting pass with 64-bit counters, which skips a
+ *                                   row with m == 0 before its coefficients are loaded, and a launch that writes total.
+ *                          `workspace`: 16-byte aligned, at least tdeq_row_dense_ranks_weighted_workspace_bytes(n_q, n_rows)
+ *                          = 32 * n_q + 8 * n_q * n_rows bytes (0 for sizes the entry point refuses).  Refusals and no-ops:
+ *                          those of tdeq_row_dense_ranks; also TDEQ_EINVAL for a NULL `total`, `weights` or `workspace`, a
+ *                          workspace that is not 16-byte aligned and a w_stride other than 0 or n_rows; TDEQ_EWORKSPACE for a
+ *                          workspace that is too small.
+ */
+int tdeq_row_dense_ranks(int64_t* below, int64_t* equal, const void* values, int n_values, const void* coeffs, int64_t n_seg,
+                         const int32_t* seg, const void* x, int64_t n_q, int64_t n_rows, int64_t row_len, int dtype,
+                         void* stream);
+size_t tdeq_row_dense_ranks_weighted_workspace_bytes(int64_t n_q, int64_t n_rows);
+int tdeq_row_dense_ranks_weighted(int64_t* below, int64_t* equal, int64_t* total, const void* values, int n_values,
+                                  const void* coeffs, int64_t n_seg, const int32_t* seg, const void* x, int64_t n_q,
+                                  int64_t n_rows, int64_t row_len, void* workspace, size_t workspace_bytes, int dtype,
+                                  void* stream, const double* weights, int64_t w_stride);
 
 /*
  * ---- Per-row step options (ABI 29; `min_step`, `max_step`, `step_t`, `jump_t` of the rowwise family) ----

@@ -21,6 +21,8 @@ import torch
 TDEQ_ABI_VERSION = 38
 TDEQ_ROW_QUANTILES_MAX_RANKS = 16       # include/tdeq_hip.h
 TDEQ_ROW_QUANTILES_SLAB_ROWS = 1024     # rows of one workgroup of the counting pass of tdeq_row_dense_quantiles
+TDEQ_ROW_RANKS_MAX_VALUES = 16          # thresholds of one call of tdeq_row_dense_ranks
+TDEQ_ROW_RANKS_GROUP_VALUES = 4         # thresholds one workgroup of its counting kernel holds in registers
 TDEQ_ROW_MOMENTS_SLAB_ROWS = 1024       # rows of one workgroup of the sum passes of tdeq_row_dense_moments
 TDEQ_ROW_MOMENTS_MAX_COV_LEN = 1024     # the longest row tdeq_row_dense_moments takes with a covariance
 TDEQ_ROW_CROSS_MAX_BLOCKS = 1024        # tdeq_row_dense_cross: ceil(L / 64) * ceil(M / W) blocks at most, W = 16 (M <= 16) or 64
@@ -365,7 +367,17 @@ ABI_SIGNATURES = {
                                                          ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
                                                          ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_size_t,
                                                          ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64]),
-    # per-row step options (ABI 29, `min_step` / `max_step` / `step_t` / `jump_t` of the rowwise family)
+    # population ranks of given values (additive symbols within ABI 38, `RowDenseOutput.ranks` / `cdf`)
+    "tdeq_row_dense_ranks": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
+                                            ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
+                                            ctypes.c_int64, ctypes.c_int, ctypes.c_void_p]),
+    "tdeq_row_dense_ranks_weighted_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int64]),
+    "tdeq_row_dense_ranks_weighted": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                     ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
+                                                     ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
+                                                     ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_void_p,
+                                                     ctypes.c_void_p, ctypes.c_int64]),
+    # per-row step options (ABI 29,`min_step` / `max_step` / `step_t` / `jump_t` of the rowwise family)
     "tdeq_row_control_points": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(StepCtrl),
                                                ctypes.POINTER(RowState), ctypes.POINTER(RowPoints), ctypes.c_void_p,
                                                ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
@@ -1478,7 +1490,8 @@ class HipKernels:
     # -- the same two with reliability weights (`weights=` of RowDenseOutput.moments / .cross_covariance) ----------------------
     @staticmethod
     def _row_dense_weighted_checks(what: str, Q: int, L: int, correction, coeffs, seg, x, weights, workspace, outputs) -> int:
-        """The argument checks the two weighted calls share -> n_rows.  `weights`: contiguous fp64 [n_rows] or [Q, n_rows]."""
+        """The argument checks the weighted calls share -> n_rows.  `weights`: contiguous fp64 [n_rows] or [Q, n_rows]
+        (`row_dense_ranks`: None, and no workspace)."""
         if correction not in (0, 1) or isinstance(correction, bool):
             raise ValueError(f"{what}: correction must be 0 or 1, got {correction!r}")
         if coeffs.dim() != 3 or coeffs.shape[0] != 5 or coeffs.shape[1] < 1 or coeffs.shape[2] != L \
@@ -1488,12 +1501,13 @@ class HipKernels:
         if n_idx == 0 or n_idx % Q != 0:
             raise ValueError(f"{what}: seg must hold n_rows >= 1 queries for each of the {Q} times")
         B = n_idx // Q
-        if weights.dtype != torch.float64 or not weights.is_contiguous() or tuple(weights.shape) not in ((B,), (Q, B)):
+        if weights is not None and (weights.dtype != torch.float64 or not weights.is_contiguous()
+                                    or tuple(weights.shape) not in ((B,), (Q, B))):
             raise ValueError(f"{what}: weights must be a contiguous float64 [{B}] or [{Q}, {B}] tensor")
         for name, t, dtype, shape in outputs + [("seg", seg, torch.int32, (n_idx,)), ("x", x, coeffs.dtype, (n_idx,))]:
             if tuple(t.shape) != tuple(d if d is not None else B for d in shape) or t.dtype != dtype or not t.is_contiguous():
                 raise ValueError(f"{what}: {name} must be a contiguous {dtype} {list(shape)} tensor")
-        if workspace.dtype != torch.uint8 or workspace.dim() != 1 or not workspace.is_contiguous():
+        if weights is not None and (workspace.dtype != torch.uint8 or workspace.dim() != 1 or not workspace.is_contiguous()):
             raise ValueError(f"{what}: workspace must be a contiguous uint8 vector")
         return B
 
@@ -1578,6 +1592,53 @@ class HipKernels:
                                                           workspace.numel(), dtype_code(coeffs.dtype), self._stream(),
                                                           weights.data_ptr(), 0 if weights.dim() == 1 else B),
                "tdeq_row_dense_quantiles_weighted")
+
+    # -- population ranks of given values (RowDenseOutput.ranks / .cdf) ---------------------------------------------------------
+    def row_dense_ranks(self, below, equal, values, coeffs, seg, x) -> None:
+        """tdeq_row_dense_ranks: below[v, j, :] / equal[v, j, :] = per element the number of the n_rows values of query time j
+        whose key is < / == the key of the threshold values[v, j, :], the queries (seg[j * n_rows + r], x[j * n_rows + r]) of
+        `row_dense_search`.  `below`, `equal` int64 [V, Q, L]; `values` [V, Q, L] of the dtype of `coeffs` [5, n_seg, L]; `seg`
+        int32 and `x` [Q * n_rows].  No workspace."""
+        what = "row_dense_ranks"
+        V, Q, L = self._row_dense_ranks_outputs(what, below, equal)
+        if Q == 0 or L == 0:
+            return
+        B = self._row_dense_weighted_checks(what, Q, L, 0, coeffs, seg, x, None, None,
+                                            [("values", values, coeffs.dtype, (V, Q, L))])
+        _check(self.lib.tdeq_row_dense_ranks(below.data_ptr(), equal.data_ptr(), values.data_ptr(), V, coeffs.data_ptr(),
+                                             coeffs.shape[1], seg.data_ptr(), x.data_ptr(), Q, B, L, dtype_code(coeffs.dtype),
+                                             self._stream()), "tdeq_row_dense_ranks")
+
+    def row_dense_ranks_weighted_workspace_bytes(self, n_q: int, n_rows: int) -> int:
+        """tdeq_row_dense_ranks_weighted_workspace_bytes: the workspace of `row_dense_ranks_weighted`."""
+        return int(self.lib.tdeq_row_dense_ranks_weighted_workspace_bytes(n_q, n_rows))
+
+    def row_dense_ranks_weighted(self, below, equal, total, values, coeffs, seg, x, workspace, weights) -> None:
+        """tdeq_row_dense_ranks_weighted: `row_dense_ranks` under `weights`, fp64 [n_rows] (one set for all times) or [Q,
+        n_rows]: `below` and `equal` are sums of the fixed-point units of `row_dense_quantiles_weighted` over the rows in
+        range, `total` int64 [Q] their sum over all of them; all three are 0 for a time with an invalid weight.  `workspace`:
+        a contiguous uint8 tensor of at least `row_dense_ranks_weighted_workspace_bytes(Q, n_rows)` bytes."""
+        what = "row_dense_ranks_weighted"
+        V, Q, L = self._row_dense_ranks_outputs(what, below, equal)
+        if Q == 0 or L == 0:
+            return
+        outputs = [("values", values, coeffs.dtype, (V, Q, L)), ("total", total, torch.int64, (Q,))]
+        B = self._row_dense_weighted_checks(what, Q, L, 0, coeffs, seg, x, weights, workspace, outputs)
+        _check(self.lib.tdeq_row_dense_ranks_weighted(below.data_ptr(), equal.data_ptr(), total.data_ptr(), values.data_ptr(), V,
+                                                      coeffs.data_ptr(), coeffs.shape[1], seg.data_ptr(), x.data_ptr(), Q, B, L,
+                                                      workspace.data_ptr(), workspace.numel(), dtype_code(coeffs.dtype),
+                                                      self._stream(), weights.data_ptr(), 0 if weights.dim() == 1 else B),
+               "tdeq_row_dense_ranks_weighted")
+
+    @staticmethod
+    def _row_dense_ranks_outputs(what: str, below, equal):
+        """The two int64 [V, Q, L] outputs of the rank calls -> (V, Q, L)."""
+        for name, t in (("below", below), ("equal", equal)):
+            if t.dim() != 3 or t.dtype != torch.int64 or not t.is_contiguous() or t.shape != below.shape:
+                raise ValueError(f"{what}: {name} must be a contiguous int64 [V, Q, L] tensor")
+        if not 1 <= below.shape[0] <= TDEQ_ROW_RANKS_MAX_VALUES:
+            raise ValueError(f"{what}: 1 to {TDEQ_ROW_RANKS_MAX_VALUES} values, got {below.shape[0]}")
+        return tuple(below.shape)
 
 
 class ComplexHipKernels:

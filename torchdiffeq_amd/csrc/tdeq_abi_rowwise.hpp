@@ -1746,3 +1746,136 @@ int tdeq_row_dense_quantiles_weighted(void* out, const double* probs, int n_rank
         return row_dense_wquant_launch<T>(a, w.hist + w.stat, aligned16(coeffs), s);
     });
 }
+
+// ---- population ranks of given values: tdeq_row_dense_ranks, tdeq_row_dense_ranks_weighted ---------------------------------
+// Additive symbols within ABI 38.  The kernels are the row_dense_ranks family (tdeq_kernels_rowwise_dense.hpp): a clear and
+// ONE counting launch; weighted: the scale and units kernels of the weighted select in between and a finish launch.
+namespace {
+
+// (n_q * tiles <= INT32_MAX and n_q * n_rows < INT32_MAX, tested without overflow)
+inline bool row_dense_ranks_sizes_ok(int n_values, int64_t n_q, int64_t n_rows, int64_t row_len, int dtype) {
+    if (n_values < 1 || n_values > TDEQ_ROW_RANKS_MAX_VALUES || n_q < 0 || n_rows < 0 || row_len < 0 || !real_dtype_ok(dtype))
+        return false;
+    if (n_q > 0x7fffffffLL || row_len > 0x7fffffffLL * kQuantTile) return false;
+    if (n_rows > 0 && n_q > 0x7ffffffeLL / n_rows) return false;
+    const int64_t tiles = (row_len + kQuantTile - 1) / kQuantTile;
+    return tiles == 0 || n_q <= 0x7fffffffLL / tiles;
+}
+
+// the weighted workspace: wmax_bits, W and flag per time (32 bytes each, cleared), then the units
+inline size_t row_dense_ranks_stat_bytes(int64_t n_q) { return (size_t)n_q * 32; }
+
+// weights == NULL: the unweighted call (no workspace, no total)
+template <typename T>
+int row_dense_ranks_launch(RowDenseRanksArgs<T>& a, int64_t* total, const double* weights, int64_t w_stride, void* workspace,
+                           bool aligned, hipStream_t s) {
+    const int64_t rows = a.slabs * a.n_q, groups = (a.n_values + kRanksGroup - 1) / kRanksGroup;
+    const int64_t grid = rows * a.tiles * groups;                     // (rows * tiles < 2^52: n_q * tiles <= INT32_MAX)
+    if (grid > 0x7fffffffLL) return TDEQ_EINVAL;
+    const dim3 block(kBlock);
+    RowDenseRanksClearArgs c;
+    c.below = a.below;
+    c.equal = a.equal;
+    c.n = (int64_t)a.n_values * a.n_q * a.row_len;
+    c.stat = static_cast<WQuantU*>(workspace);
+    c.n_stat = weights ? (int64_t)(row_dense_ranks_stat_bytes(a.n_q) / sizeof(WQuantU)) : 0;
+    hipLaunchKernelGGL(row_dense_ranks_clear_kernel, dim3(stream_grid(c.n > c.n_stat ? c.n : c.n_stat, kBlock)), block, 0, s, c);
+    RowDenseWQuantArgs<T> w = {};
+    if (weights) {
+        w.x = a.x;
+        w.w = weights;
+        w.w_stride = w_stride;
+        w.wmax_bits = c.stat;                                         // per time 32 bytes: 8 n_q, 8 n_q, 4 n_q, unused
+        w.total = w.wmax_bits + a.n_q;
+        w.flag = reinterpret_cast<uint32_t*>(w.total + a.n_q);
+        w.units = reinterpret_cast<WQuantU*>(static_cast<char*>(workspace) + row_dense_ranks_stat_bytes(a.n_q));
+        w.n_rows = a.n_rows;
+        w.n_q = a.n_q;
+        w.slabs = a.slabs;
+        w.scale = 62;                                                 // S = 62 - bit_length(n_rows)
+        for (int64_t v = a.n_rows; v > 0; v >>= 1) --w.scale;
+        hipLaunchKernelGGL(row_dense_wquant_scale_kernel<T>, dim3((unsigned)rows), block, 0, s, w);
+        hipLaunchKernelGGL(row_dense_wquant_units_kernel<T>, dim3((unsigned)rows), block, 0, s, w);
+        a.units = w.units;
+        a.flag = w.flag;
+    }
+    int64_t unused;
+    return row_vec<T>(a.row_len, aligned, unused, [&](auto vec) {
+        constexpr bool VEC = decltype(vec)::value;
+        if (weights) {
+            hipLaunchKernelGGL((row_dense_ranks_count_kernel<T, VEC, true>), dim3((unsigned)grid), block, 0, s, a);
+            RowDenseRanksFinishArgs f;
+            f.out = reinterpret_cast<WQuantU*>(total);
+            f.total = w.total;
+            f.flag = w.flag;
+            f.n_q = a.n_q;
+            hipLaunchKernelGGL(row_dense_ranks_finish_kernel, dim3(stream_grid(a.n_q, kBlock)), block, 0, s, f);
+        } else {
+            hipLaunchKernelGGL((row_dense_ranks_count_kernel<T, VEC, false>), dim3((unsigned)grid), block, 0, s, a);
+        }
+        return check_launch();
+    });
+}
+
+template <typename T>
+RowDenseRanksArgs<T> row_dense_ranks_args(int64_t* below, int64_t* equal, const void* values, int n_values, const void* coeffs,
+                                          int64_t n_seg, const int32_t* seg, const void* x, int64_t n_q, int64_t n_rows,
+                                          int64_t row_len) {
+    RowDenseRanksArgs<T> a;
+    a.q = static_cast<const T*>(coeffs);
+    a.seg = seg;
+    a.x = static_cast<const T*>(x);
+    a.values = static_cast<const T*>(values);
+    a.below = reinterpret_cast<WQuantU*>(below);
+    a.equal = reinterpret_cast<WQuantU*>(equal);
+    a.units = nullptr;
+    a.flag = nullptr;
+    a.n_rows = n_rows;
+    a.n_seg = n_seg;
+    a.row_len = row_len;
+    a.q_plane = n_seg * row_len;
+    a.n_q = n_q;
+    a.tiles = (row_len + kQuantTile - 1) / kQuantTile;
+    a.slabs = (n_rows + kQuantSlabRows - 1) / kQuantSlabRows;
+    a.n_values = n_values;
+    return a;
+}
+
+}  // namespace
+
+int tdeq_row_dense_ranks(int64_t* below, int64_t* equal, const void* values, int n_values, const void* coeffs, int64_t n_seg,
+                         const int32_t* seg, const void* x, int64_t n_q, int64_t n_rows, int64_t row_len, int dtype,
+                         void* stream) {
+    if (!below || !equal || !values || !coeffs || !seg || !x || !row_dense_ranks_sizes_ok(n_values, n_q, n_rows, row_len, dtype))
+        return TDEQ_EINVAL;
+    if (n_seg < 1) return TDEQ_EINVAL;
+    if (n_q == 0 || n_rows == 0 || row_len == 0) return 0;
+    return real_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        RowDenseRanksArgs<T> a = row_dense_ranks_args<T>(below, equal, values, n_values, coeffs, n_seg, seg, x, n_q, n_rows, row_len);
+        return row_dense_ranks_launch<T>(a, nullptr, nullptr, 0, nullptr, aligned16(coeffs), static_cast<hipStream_t>(stream));
+    });
+}
+
+size_t tdeq_row_dense_ranks_weighted_workspace_bytes(int64_t n_q, int64_t n_rows) {
+    if (!row_dense_ranks_sizes_ok(1, n_q, n_rows, 0, TDEQ_F64)) return 0;
+    return row_dense_ranks_stat_bytes(n_q) + (size_t)n_q * n_rows * sizeof(WQuantU);
+}
+
+int tdeq_row_dense_ranks_weighted(int64_t* below, int64_t* equal, int64_t* total, const void* values, int n_values,
+                                  const void* coeffs, int64_t n_seg, const int32_t* seg, const void* x, int64_t n_q,
+                                  int64_t n_rows, int64_t row_len, void* workspace, size_t workspace_bytes, int dtype,
+                                  void* stream, const double* weights, int64_t w_stride) {
+    if (!below || !equal || !total || !values || !coeffs || !seg || !x || !workspace || !weights ||
+        !row_dense_ranks_sizes_ok(n_values, n_q, n_rows, row_len, dtype) || (w_stride != 0 && w_stride != n_rows))
+        return TDEQ_EINVAL;
+    if (n_seg < 1 || !aligned16(workspace)) return TDEQ_EINVAL;
+    if (workspace_bytes < tdeq_row_dense_ranks_weighted_workspace_bytes(n_q, n_rows)) return TDEQ_EWORKSPACE;
+    if (n_q == 0 || n_rows == 0 || row_len == 0) return 0;
+    return real_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        RowDenseRanksArgs<T> a = row_dense_ranks_args<T>(below, equal, values, n_values, coeffs, n_seg, seg, x, n_q, n_rows, row_len);
+        return row_dense_ranks_launch<T>(a, total, weights, w_stride, workspace, aligned16(coeffs),
+                                         static_cast<hipStream_t>(stream));
+    });
+}

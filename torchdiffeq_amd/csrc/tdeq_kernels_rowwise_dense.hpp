@@ -2219,4 +2219,180 @@ __global__ __launch_bounds__(kBlock) void row_dense_wquant_select_kernel(const R
     }
 }
 
+// ---- population ranks of given values across rows (additive within ABI 38): the inverse of the select above --------------
+// For threshold v, time q and element el: below = the number of rows whose key (quant_key of quant_value, the bits of
+// row_event_eval_mapped) is < the key of values[v, q, el], equal = the number whose key is == it.  ONE pass over the record,
+// where the select needs sizeof(T); every result is an integer sum, so it depends neither on the grid nor on row order.
+//   row_dense_ranks_clear    zeroes below, equal and (weighted) the per-time words wmax_bits, W and flag
+//   (weighted) row_dense_wquant_scale and row_dense_wquant_units, unchanged: the units m [n_q, n_rows], W and flag
+//   row_dense_ranks_count    a workgroup owns one time, one tile of kQuantTile = 64 contiguous elements, one slab of
+//                            kQuantSlabRows rows and one group of G = kRanksGroup thresholds.  The lanes of a wave run along
+//                            the elements, so the five plane loads of a row coalesce; the four waves take different rows
+//                            (16-byte form: a lane holds LV neighbouring elements and the wave covers LV rows at once).  The
+//                            keys of the G thresholds of the lane's elements are formed once and stay in registers with the
+//                            2 G LV counters (uint32 unweighted: a lane sees at most a slab of rows; uint64 sums of m
+//                            weighted); every loop over them is unrolled at compile time, so nothing is indexed at run time
+//                            and nothing goes to scratch.  A comparison does not scatter: the hot loop has no atomics and
+//                            touches no LDS.  Weighted: a row with m == 0 is skipped BEFORE seg, x and its planes are loaded,
+//                            and a workgroup of a flagged time returns at once.  Merge: the LV row groups of a wave by
+//                            shuffles (16-byte form), the four waves through 2 G x 64 counters each in LDS (4 KB unweighted,
+//                            16 KB weighted), then ONE 64-bit integer atomicAdd per nonzero (threshold, time, element).
+//   (weighted) row_dense_ranks_finish   total[q] = flag[q] ? 0 : W[q]
+// G = 4, from the compiler's resource report for gfx950 (VGPRs / waves per SIMD; no kernel has scratch, LDS as above):
+//                    fp32 scalar   fp32 16-byte   fp64 scalar   fp64 16-byte
+//   G = 4 unweighted    41 / 8        94 / 5         52 / 8        70 / 7
+//   G = 4 weighted      51 / 8       123 / 4         62 / 8       100 / 4
+//   G = 8 unweighted    54 / 8       138 / 3         64 / 8       118 / 4
+//   G = 8 weighted      86 / 5       248 / 2         96 / 5       138 / 3
+// The 16-byte forms are what a long row takes: G = 8 leaves them 2 to 4 waves per SIMD to hide five plane loads per row, G = 4
+// keeps 4 to 7, so 16 thresholds run as ceil(16 / 4) = 4 threshold groups in the grid, each of which reads the record again.
+// (An occupancy from the compiler's report is not a time: tools/rowwise_ranks_bench.py measures V = 3 against V = 16.)
+// 64-bit offsets; integer atomics only; TDEQ_NO_PACKED_FP32 on the counting kernel for the reason given above.
+constexpr int kRanksGroup = TDEQ_ROW_RANKS_GROUP_VALUES;
+static_assert(TDEQ_ROW_RANKS_MAX_VALUES % kRanksGroup == 0 && (2 * kRanksGroup * kQuantTile) % kBlock == 0,
+              "whole groups; the merge is whole workgroup steps");
+
+template <typename T>
+struct RowDenseRanksArgs {
+    const T* q;                       // [5, n_seg, L]
+    const int32_t* seg;               // [n_q * n_rows]
+    const T* x;                       // [n_q * n_rows]
+    const T* values;                  // [n_values, n_q, L] the thresholds
+    WQuantU* below;                   // [n_values, n_q, L] (the int64 outputs: the sums stay below 2^62)
+    WQuantU* equal;                   // [n_values, n_q, L]
+    const WQuantU* units;             // weighted: [n_q, n_rows] m
+    const uint32_t* flag;             // weighted: [n_q] nonzero: an invalid weight in range
+    int64_t n_rows;
+    int64_t n_seg;
+    int64_t row_len;                  // T units
+    int64_t q_plane;                  // n_seg * L
+    int64_t n_q;
+    int64_t tiles;                    // ceil(L / 64)
+    int64_t slabs;                    // ceil(n_rows / kQuantSlabRows)
+    int32_t n_values;
+};
+
+struct RowDenseRanksClearArgs {
+    WQuantU* below;
+    WQuantU* equal;
+    int64_t n;                        // words of each output
+    WQuantU* stat;                    // weighted: wmax_bits, W, flag (and the unused word) of every time; else NULL
+    int64_t n_stat;                   // 64-bit words
+};
+
+__global__ __launch_bounds__(kBlock) void row_dense_ranks_clear_kernel(const RowDenseRanksClearArgs a) {
+    const int64_t stride = (int64_t)gridDim.x * kBlock;
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < a.n; i += stride) {
+        a.below[i] = 0ull;
+        a.equal[i] = 0ull;
+    }
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < a.n_stat; i += stride) a.stat[i] = 0ull;
+}
+
+template <typename T, bool VEC, bool WEIGHTED>
+__global__ __launch_bounds__(kBlock) TDEQ_NO_PACKED_FP32 void row_dense_ranks_count_kernel(const RowDenseRanksArgs<T> a) {
+    using E = typename std::conditional<VEC, typename VecOf<T>::type, T>::type;
+    using U = typename QuantKey<T>::U;
+    using C = typename std::conditional<WEIGHTED, WQuantU, uint32_t>::type;     // a lane's counter
+    constexpr int G = kRanksGroup;
+    constexpr int LV = VEC ? VecOf<T>::L : 1;                         // elements per lane = rows per wave step
+    constexpr int kLanesPerRow = kQuantTile / LV;
+    constexpr int kWaves = kBlock / kWave;
+    __shared__ C part[kWaves][2 * G][kQuantTile];                     // [wave][below 0 .. G - 1, equal 0 .. G - 1][element]
+
+    int64_t b = blockIdx.x;
+    const int64_t slab = b % a.slabs;
+    b /= a.slabs;
+    const int64_t tile = b % a.tiles;
+    b /= a.tiles;
+    const int64_t q = b % a.n_q;
+    const int64_t v0 = (b / a.n_q) * G;                               // the group's first threshold
+    if constexpr (WEIGHTED) {
+        if (a.flag[q] != 0u) return;                                  // (the whole workgroup) the time's outputs stay zero
+    }
+    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+    const int col = (lane % kLanesPerRow) * LV;                       // the lane's first element inside the tile
+    const int64_t el = tile * kQuantTile + col;
+
+    U level[G][LV];
+    C below[G][LV], equal[G][LV];
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+#pragma unroll
+        for (int c = 0; c < LV; ++c) {
+            level[g][c] = (U)0;
+            below[g][c] = (C)0;
+            equal[g][c] = (C)0;
+        }
+    }
+    if (el < a.row_len) {                                             // (VEC: L is a whole number of lanes' elements)
+#pragma unroll
+        for (int g = 0; g < G; ++g) {                                 // (past the last threshold: a copy of it, never stored)
+            const int64_t v = v0 + g < a.n_values ? v0 + g : a.n_values - 1;
+#pragma unroll
+            for (int c = 0; c < LV; ++c) level[g][c] = quant_key<T>(a.values[(v * a.n_q + q) * a.row_len + el + c]);
+        }
+        const int64_t r_end = (slab + 1) * kQuantSlabRows < a.n_rows ? (slab + 1) * kQuantSlabRows : a.n_rows;
+        for (int64_t r = slab * kQuantSlabRows + wave * LV + lane / kLanesPerRow; r < r_end; r += kWaves * LV) {
+            const int64_t i = q * a.n_rows + r;
+            C m = (C)1;
+            if constexpr (WEIGHTED) {
+                m = a.units[i];
+                if (m == 0ull) continue;                              // no weight, or the row has left: nothing is loaded
+            }
+            int64_t s = a.seg[i];
+            s = s < 0 ? 0 : (s < a.n_seg ? s : a.n_seg - 1);          // (the search writes 0 <= seg < n_seg)
+            const T x = a.x[i];
+            T qe[LV], qd[LV], qc[LV], qb[LV], qa[LV];
+            load_planes<T, E, LV>(a.q, a.q_plane, (s * a.row_len + el) / LV, qe, qd, qc, qb, qa);
+#pragma unroll
+            for (int c = 0; c < LV; ++c) {
+                const U key = quant_key<T>(quant_value<T>(qe[c], qd[c], qc[c], qb[c], qa[c], x));
+#pragma unroll
+                for (int g = 0; g < G; ++g) {
+                    below[g][c] += key < level[g][c] ? m : (C)0;
+                    equal[g][c] += key == level[g][c] ? m : (C)0;
+                }
+            }
+        }
+    }
+    // the rows a wave covers at once: the lanes with the same elements are kLanesPerRow apart (every lane takes part)
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+#pragma unroll
+        for (int c = 0; c < LV; ++c) {
+#pragma unroll
+            for (int off = kLanesPerRow; off < kWave; off <<= 1) {
+                below[g][c] += __shfl_xor(below[g][c], off, kWave);
+                equal[g][c] += __shfl_xor(equal[g][c], off, kWave);
+            }
+            if (lane < kLanesPerRow) {
+                part[wave][g][col + c] = below[g][c];
+                part[wave][G + g][col + c] = equal[g][c];
+            }
+        }
+    }
+    __syncthreads();
+    for (int j = threadIdx.x; j < 2 * G * kQuantTile; j += kBlock) {
+        const int k = j / kQuantTile, e = j % kQuantTile;
+        WQuantU n = 0ull;
+#pragma unroll
+        for (int w = 0; w < kWaves; ++w) n += part[w][k][e];
+        const int64_t v = v0 + (k < G ? k : k - G), at = tile * kQuantTile + e;
+        if (n && v < a.n_values && at < a.row_len) atomicAdd((k < G ? a.below : a.equal) + (v * a.n_q + q) * a.row_len + at, n);
+    }
+}
+
+struct RowDenseRanksFinishArgs {
+    WQuantU* out;                     // [n_q] total
+    const WQuantU* total;             // [n_q] W
+    const uint32_t* flag;             // [n_q]
+    int64_t n_q;
+};
+
+__global__ __launch_bounds__(kBlock) void row_dense_ranks_finish_kernel(const RowDenseRanksFinishArgs a) {
+    const int64_t stride = (int64_t)gridDim.x * kBlock;
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < a.n_q; i += stride) a.out[i] = a.flag[i] ? 0ull : a.total[i];
+}
+
 }  // namespace tdeq

@@ -891,14 +891,7 @@ class HostRowKernels:
         bits = v.contiguous().view(I)
         key = torch.where(bits < 0, bits ^ top, bits)
         key = torch.where(torch.isnan(v), torch.full_like(key, top), key).transpose(1, 2)           # [Q, L, B]
-        took_part = (x == x).view(Q, B).numpy()
-        w = weights.expand(Q, B).numpy()
-        with np.errstate(invalid="ignore"):
-            valid = took_part & (w >= 0) & (w < np.inf)
-        bad = (took_part & ~valid).any(axis=1)
-        w = np.where(valid, w, 0.0)                                   # (-0.0 is 0 under frexp and rint alike)
-        E = np.frexp(w.max(axis=1))[1]
-        units = np.rint(np.ldexp(w, ((62 - int(B).bit_length()) - E)[:, None])).astype(np.int64)   # a true ldexp: S - E > 1023
+        units, bad = HostRowKernels._weight_units(x, weights, Q, B)
         totals = [int(t) for t in units.sum(axis=1)]
         targets = [[min(max(math.ceil(float(p) * float(W)), 1), W) for p in probs] for W in totals]
         key, order = torch.sort(key, dim=2)
@@ -909,6 +902,50 @@ class HostRowKernels:
         back = torch.where(picked < 0, picked ^ top, picked).view(v.dtype)
         nan = (picked == top) | torch.tensor([b or W == 0 for b, W in zip(bad, totals)])[None, :, None]
         return torch.where(nan, torch.full_like(back, float("nan")), back)
+
+    @staticmethod
+    def _weight_units(x, weights, Q: int, B: int):
+        """The fixed-point units of the weighted order statistics -> (m int64 numpy [Q, B], 0 for a row that has left or whose
+        weight is invalid; bool numpy [Q]: the time has a negative or non-finite weight in range)."""
+        took_part = (x == x).view(Q, B).numpy()
+        w = weights.expand(Q, B).numpy()
+        with np.errstate(invalid="ignore"):
+            valid = took_part & (w >= 0) & (w < np.inf)
+        bad = (took_part & ~valid).any(axis=1)
+        w = np.where(valid, w, 0.0)                                   # (-0.0 is 0 under frexp and rint alike)
+        E = np.frexp(w.max(axis=1))[1]
+        units = np.rint(np.ldexp(w, ((62 - int(B).bit_length()) - E)[:, None])).astype(np.int64)   # a true ldexp: S - E > 1023
+        return units, bad
+
+    @staticmethod
+    def _order_keys(v) -> torch.Tensor:
+        """The key of `quartic_quantiles` as a signed integer of the width of `v`: -0.0 before +0.0, every NaN the largest."""
+        I = torch.int32 if v.dtype == torch.float32 else torch.int64
+        top = torch.iinfo(I).max
+        bits = v.contiguous().view(I)
+        return torch.where(torch.isnan(v), torch.full_like(bits, top), torch.where(bits < 0, bits ^ top, bits))
+
+    @staticmethod
+    def quartic_ranks(q, src, x, values, Q: int, B: int):
+        """Per threshold `values[v]` ([V, Q, L] of the record's dtype), time and element the number of the B rows whose value
+        has a key below, and equal to, the threshold's key -> (below, equal), int64 [V, Q, L].  The model of
+        tdeq_row_dense_ranks: `eval_quartics`, the integer keys of `quartic_quantiles`, compared in torch and summed in int64;
+        a row out of range is a NaN value."""
+        key = HostRowKernels._order_keys(HostRowKernels.eval_quartics(q, src, x).view(1, Q, B, -1))
+        level = HostRowKernels._order_keys(values)[:, :, None, :]                                  # [V, Q, 1, L]
+        return (key < level).sum(dim=2), (key == level).sum(dim=2)
+
+    @staticmethod
+    def quartic_ranks_weighted(q, src, x, values, weights, Q: int, B: int):
+        """`quartic_ranks` under `weights` (fp64 [B] or [Q, B]) -> (below, equal, total): the sums of the units m_r of
+        `quartic_quantiles_weighted` over the rows in range on either side of the comparison, and int64 [Q] their sum W.  A
+        time with a negative or non-finite weight in range is all zeros, `total` included.  The model of
+        tdeq_row_dense_ranks_weighted, bit for bit."""
+        units, bad = HostRowKernels._weight_units(x, weights, Q, B)
+        m = torch.from_numpy(np.where(bad[:, None], 0, units))[None, :, :, None]                   # [1, Q, B, 1]
+        key = HostRowKernels._order_keys(HostRowKernels.eval_quartics(q, src, x).view(1, Q, B, -1))
+        level = HostRowKernels._order_keys(values)[:, :, None, :]
+        return ((key < level) * m).sum(dim=2), ((key == level) * m).sum(dim=2), m.sum(dim=(0, 2, 3))
 
     @staticmethod
     def quartic_moments(q, src, x, Q: int, B: int, covariance: bool, correction: int):

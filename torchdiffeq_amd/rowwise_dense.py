@@ -25,8 +25,9 @@ which stores every located time at once; the order statistics across rows are on
 `tdeq_row_dense_quantiles`, a radix select that evaluates the record in every pass; the mean, variance and covariance across
 rows are one search followed by `tdeq_row_dense_moments`, two passes of fp64 sums over slabs of rows merged in a fixed order,
 the covariance as a Gram matrix of deviations on the fp64 matrix instructions; the covariance with per-row covariates is one
-search followed by `tdeq_row_dense_cross`, the same mean pass and a rectangular Gram kernel.  CPU states run the same steps as
-torch / numpy ops.
+search followed by `tdeq_row_dense_cross`, the same mean pass and a rectangular Gram kernel; the population ranks of given
+values, the inverse of the order statistics, are one search followed by `tdeq_row_dense_ranks`, one counting pass with the
+counters in registers.  CPU states run the same steps as torch / numpy ops.
 """
 from __future__ import annotations
 
@@ -38,11 +39,12 @@ import numpy as np
 import torch
 
 from . import rowwise
-from ._native import TDEQ_ROW_CROSS_MAX_BLOCKS, TDEQ_ROW_MOMENTS_MAX_COV_LEN, TDEQ_ROW_QUANTILES_MAX_RANKS, device_guard
+from ._native import TDEQ_ROW_CROSS_MAX_BLOCKS, TDEQ_ROW_MOMENTS_MAX_COV_LEN, TDEQ_ROW_QUANTILES_MAX_RANKS, \
+    TDEQ_ROW_RANKS_MAX_VALUES, device_guard
 from .rowwise import _Problem
 
 __all__ = ["odeint_rowwise_dense", "RowDenseOutput", "RowDenseExtremum", "RowDenseCrossings", "RowDenseCrossingTimes",
-           "RowDenseExposure", "RowDenseMoments"]
+           "RowDenseExposure", "RowDenseMoments", "RowDenseRanks"]
 
 # the default chunk: CHUNK_ROWS_PER_ROW slots per row of the batch, at most CHUNK_BYTES of coefficients, never fewer than B
 CHUNK_ROWS_PER_ROW = 4
@@ -222,6 +224,15 @@ class RowDenseMoments(NamedTuple):
     covariance: torch.Tensor | None
 
 
+class RowDenseRanks(NamedTuple):
+    """`RowDenseOutput.ranks`: per threshold, time and element the number of rows of the population whose value sorts below
+    the threshold and the number that equal it (int64 `[V, Q, *row_shape]`), and per time the size of the population (int64
+    `[Q]`); under `weights=` all three count the fixed-point units of the weights."""
+    below: torch.Tensor
+    equal: torch.Tensor
+    total: torch.Tensor
+
+
 class RowDenseOutput:
     """The piecewise quartic of a rowwise solve; `dense(t)` evaluates it, `derivative(t)`, `antiderivative(t)` and
     `integral(ta, tb)` give its time derivative and its integrals in closed form, `maximum(ta, tb)` and `minimum(ta, tb)` its
@@ -229,7 +240,8 @@ class RowDenseOutput:
     level and the time spent above it, `crossing_times(level, ta, tb, max_count)` the times of all its crossings by direction,
     `exposure(level, ta, tb)`, `area_above(level, ta, tb)` and `area_below(level, ta, tb)` the area between it and a level,
     `quantiles(t, probs)` its order statistics across the rows, `moments(t)` their mean, variance and covariance,
-    `cross_covariance(t, other)` their covariance with per-row covariates (see `odeint_rowwise_dense`).
+    `cross_covariance(t, other)` their covariance with per-row covariates, `ranks(t, values)` and `cdf(t, values)` where given
+    values stand among the rows (see `odeint_rowwise_dense`).
 
     Attributes (the wire format, all on the state's device): `t0`, `t1` `[B]` fp64 in true time; `offsets` `[B + 1]` int64;
     `seg_start`, `seg_end` `[n_seg]` fp64 in true time, row r's segments — its accepted steps — contiguous and in step
@@ -672,6 +684,123 @@ class RowDenseOutput:
         out = out.view(P, Q, *self._shape[1:])
         return out.select(1, 0) if single else out
 
+    # -- population ranks of given values: one counting pass over the record, the inverse of `quantiles` ---------------------
+    def _rank_values(self, what: str, values, Q: int) -> torch.Tensor:
+        """`values` of `ranks` -> the thresholds as a contiguous `[V, Q, L]` tensor of the state's dtype on its device."""
+        row_shape, dev, T = self._shape[1:], self.coeffs.device, self.coeffs.dtype
+        if isinstance(values, torch.Tensor):
+            if values.requires_grad and torch.is_grad_enabled():
+                raise NotImplementedError("odeint_rowwise_dense: the dense output does not propagate gradients (values requires "
+                                          "grad); detach it or evaluate under torch.no_grad()")
+            if values.is_complex() or values.dtype == torch.bool:
+                raise ValueError(f"{what}: values must be a real number or tensor, got a {values.dtype} tensor")
+            vals = values.detach().to(device=dev, dtype=T)                                # rounded once to the state's dtype
+        elif isinstance(values, (int, float)) and not isinstance(values, bool):
+            vals = torch.tensor(float(values), dtype=T, device=dev)
+        else:
+            raise ValueError(f"{what}: values must be a number or a tensor, got {type(values).__name__}")
+        shape, n = tuple(vals.shape), len(row_shape)
+        if vals.dim() <= 1:
+            vals = vals.reshape(-1, 1, *([1] * n))                                        # a number or [V]
+        elif vals.dim() == 1 + n:
+            vals = vals.unsqueeze(1)                                                      # [V, *row_shape]
+        V = vals.shape[0]
+        try:
+            if vals.dim() != 2 + n:
+                raise RuntimeError
+            vals = vals.expand(V, Q, *row_shape)
+        except RuntimeError:
+            raise ValueError(f"{what}: values of shape {shape} is none of [V], [V, *row_shape] and [V, Q, *row_shape] with Q = "
+                             f"{Q}, row_shape = {list(row_shape)}") from None
+        if not 1 <= V <= TDEQ_ROW_RANKS_MAX_VALUES:
+            raise ValueError(f"{what}: values must hold 1 to {TDEQ_ROW_RANKS_MAX_VALUES} thresholds, got {V}")
+        return vals.reshape(V, Q, self.coeffs.shape[2]).contiguous()
+
+    def ranks(self, t, values, *, weights=None, check: bool = True) -> RowDenseRanks:
+        """Where given values stand in the population of the B rows, per time and per ELEMENT of the row: the inverse of
+        `quantiles` -> `RowDenseRanks(below, equal, total)`.  `below` and `equal`, int64 `[V, Q, *row_shape]` (`[V, *row_shape]`
+        for a single time), count the rows whose `dense(t)` value sorts below threshold v, and equals it; `total`, int64 `[Q]`,
+        is the size of the population — the empirical CDF of an observation among simulated patients (NPDE, PIT), the fraction
+        of them above a target, the rank of an observation in an ensemble.  `t` takes the query forms of `quantiles(t, ...)`.
+        `values`: a number or a real tensor on any device (floating or integer; not bool, not complex, not requiring grad),
+        rounded once to the state's dtype; a number or `[V]` gives the same thresholds to every time and element, `[V,
+        *row_shape]` one set per element, `[V, Q, *row_shape]` one per time and element; size-1 dimensions broadcast inside
+        each form and `1 <= V <= 16`; anything else is a ValueError.  The order is that of `quantiles`, on the ordered integer
+        image of the bits `dense(t)` gives: `-0.0` sorts before `+0.0` (so `-0.0` does not EQUAL `+0.0`), every NaN is the one
+        largest value, and a threshold may be NaN or infinite.  The population is all B rows, `total == B`; `check` as for
+        `quantiles`: with `check=False` an out-of-range row is a NaN value of its time.  Hence for every rank `k` and `v =
+        quantiles(t, ranks=[k])`: `below(v) <= k < below(v) + equal(v)`, element by element.
+
+        `weights`: the `[B]` / `[Q, B]` weights of `quantiles(t, probs, weights=...)`, with its population (a row out of
+        range has left; its weight is not inspected), validity rule and fixed-point units `m_r = rint(ldexp(w_r, S - E))`, `S =
+        62 - B.bit_length()`, `E` from the largest weight in range.  `below` and `equal` are then sums of `m_r` and `total` is
+        `W = sum_r m_r`; a time with a negative or non-finite weight in range, an empty population or a largest weight of 0
+        has `below = equal = 0` and `total = 0`, and nothing is read or raised.  Scaling all weights by a power of two changes
+        no bit.  All results are integer sums: exact, and independent of the order of the rows.  A ROCm state runs one
+        counting pass on a HIP kernel (`tdeq_row_dense_ranks`, `tdeq_row_dense_ranks_weighted`) that keeps the thresholds' keys
+        and its counters in registers and never builds `[Q, B, *row_shape]`; the weighted call keeps the units `[Q, B]` in a
+        workspace and runs the times in slices that hold it under 256 MiB.  A CPU state compares the same keys with torch ops:
+        the same bits.  The mid-rank PIT, histograms over bin edges (differences of `cdf`), thresholds per row and gradients
+        are out of scope."""
+        what = "dense.ranks(t)"
+        tqs, single = self._query_lists(what, ("t",), (t,))
+        tq = tqs[0]
+        Q, B = tq.shape
+        if self._k is not None and Q * B >= _NONE:
+            raise ValueError(f"{what}: {Q * B} queries in one call; the query index is a 32-bit word")
+        w = None if weights is None else self._weights_arg(what, weights, Q)
+        vals = self._rank_values(what, values, Q)
+        V, L, dev = vals.shape[0], self.coeffs.shape[2], self.coeffs.device
+        below, equal = (torch.empty(V, Q, L, dtype=torch.int64, device=dev) for _ in range(2))
+        total = torch.full((Q,), B, dtype=torch.int64, device=dev)
+        first = _NONE
+        if Q > 0:
+            with torch.no_grad(), device_guard(dev):
+                if self._k is None:
+                    seg, x, first = self._search_host(tq)
+                    if w is None:
+                        got = rowwise.HostRowKernels.quartic_ranks(self.coeffs, seg, x, vals, Q, B)
+                    else:
+                        got = rowwise.HostRowKernels.quartic_ranks_weighted(self.coeffs, seg, x, vals, w, Q, B)
+                    for dst, src in zip((below, equal, total), got):
+                        dst.copy_(src)
+                else:
+                    status = torch.full((1,), _NONE, dtype=torch.int32, device=dev)
+                    seg, x = self._search_device(tq, status)
+                    if w is None:
+                        self._k.row_dense_ranks(below, equal, vals, self.coeffs, seg, x)
+                    else:
+                        per_time = self._k.row_dense_ranks_weighted_workspace_bytes(1, B)     # (linear in the times)
+                        step = min(Q, max(1, QUANTILES_WORKSPACE_BYTES // max(per_time, 1)))
+                        work = torch.empty(step * per_time, dtype=torch.uint8, device=dev)
+                        for q0 in range(0, Q, step):
+                            q1 = min(q0 + step, Q)
+                            whole = q1 - q0 == Q
+                            part = (below, equal) if whole else tuple(torch.empty(V, q1 - q0, L, dtype=torch.int64, device=dev)
+                                                                      for _ in range(2))
+                            self._k.row_dense_ranks_weighted(*part, total[q0:q1], vals if whole else vals[:, q0:q1].contiguous(),
+                                                             self.coeffs, seg[q0 * B:q1 * B], x[q0 * B:q1 * B], work,
+                                                             w if w.dim() == 1 else w[q0:q1])
+                            if not whole:
+                                below[:, q0:q1], equal[:, q0:q1] = part
+                    if check:
+                        first = int(status)                                                    # the one read
+        if check:
+            self._raise_out_of_range(what, ("t",), tqs, [first])
+        below, equal = (v.view(V, Q, *self._shape[1:]) for v in (below, equal))
+        return RowDenseRanks(below.select(1, 0), equal.select(1, 0), total) if single else RowDenseRanks(below, equal, total)
+
+    def cdf(self, t, values, *, weights=None, check: bool = True) -> torch.Tensor:
+        """The empirical `P(Y <= v)` of the population at time `t`: `(below + equal) / total` of `ranks(t, values, ...)`, fp64
+        `[V, Q, *row_shape]` (`[V, *row_shape]` for a single time), formed with torch ops from the integer counts on either
+        device: the same bits.  `0 / 0`, a time without a valid population under `weights=`, is NaN.  `1 - cdf` is the
+        fraction above a target; differences of `cdf` at bin edges give a histogram."""
+        r = self.ranks(t, values, weights=weights, check=check)
+        total = r.total.double()
+        if r.below.dim() == len(self._shape) + 1:                                           # [V, Q, *row_shape]
+            return (r.below + r.equal).double() / total.view(-1, *([1] * (len(self._shape) - 1)))
+        return (r.below + r.equal).double() / total[0]
+
     def _weights_arg(self, what: str, weights, Q: int) -> torch.Tensor:
         """`weights=` of `moments` / `cross_covariance` -> contiguous fp64 `[B]` or `[Q, B]` on the record's device.  The
         values are not inspected."""
@@ -978,6 +1107,9 @@ def odeint_rowwise_dense(func, y0, t0, t1, *, rtol=1e-7, atol=1e-9, method="dopr
     `dense.quantiles(t, probs, weights=w)` gives WEIGHTED order statistics for `[B]` or `[Q, B]` weights: the weights become
     integers of a fixed-point scale set by the largest one, and the same select runs with 64-bit counters
     (`tdeq_row_dense_quantiles_weighted`); a row out of range has then left the population.
+    `dense.ranks(t, values, weights=None)` -> `RowDenseRanks(below, equal, total)` is the inverse: per threshold, time and
+    element the number of rows below a given value and equal to it in the same order, in ONE counting pass with the counters in
+    registers (`tdeq_row_dense_ranks`); `dense.cdf(t, values)` is `(below + equal) / total`.
 
     Moments across rows: `dense.moments(t, covariance=False, correction=1)` -> `RowDenseMoments(count, mean, variance,
     covariance)`, per time the number of rows in range, per element their mean and variance and, on request, the `[L, L]`
