@@ -76,6 +76,7 @@ extern "C" {
 #define TDEQ_ROW_MOMENTS_SLAB_ROWS 1024    /* tdeq_row_dense_moments: rows of one workgroup of its sum passes */
 #define TDEQ_ROW_MOMENTS_MAX_COV_LEN 1024  /* the longest row it takes with a covariance */
 #define TDEQ_ROW_CROSS_MAX_BLOCKS 1024     /* tdeq_row_dense_cross: ceil(row_len / 64) * ceil(n_cols / W) at most */
+#define TDEQ_ROW_TIME_MOMENTS_MAX_COV_LEN 256  /* tdeq_row_dense_time_gram: the longest row it takes */
 
 #define TDEQ_EINVAL (-1)       /* bad argument (null pointer, n_terms out of range, bad dtype ...) */
 #define TDEQ_EWORKSPACE (-2)   /* workspace too small */
@@ -950,6 +951,68 @@ int tdeq_row_dense_exposure(void* area_above, void* area_below, double* time_abo
                             const void* coeffs, int64_t n_seg, const double* seg_ta, const double* seg_tb, double time_sign,
                             const int32_t* seg, const void* x, const double* tq, const int32_t* seg2, const void* x2,
                             const double* tq2, int64_t n_idx, int64_t row_len, int dtype, void* stream);
+
+/*
+ * ---- Second moments along time over a window (additive symbols within ABI 38: TDEQ_ABI_VERSION is unchanged;
+ *      `RowDenseOutput.time_moments`) ----
+ * tdeq_row_dense_time_moments  for i < n_idx and every element of the row: the duration T of the window between the queries
+ *                          tq[i] and tq2[i], the time mean (1/T) int y dt of the piecewise quartic over it and the variance
+ *                          (1/T) int (y - mean)^2 dt around that mean.  (seg, x, tq), (seg2, x2, tq2) as for
+ *                          tdeq_row_dense_extremum; their order does not matter.  `duration` [n_idx], `mean` and `variance`
+ *                          [n_idx, row_len], all double for both state types.  Everything is fp64, one rounded operation per
+ *                          written operation, nothing contracted; the coefficients convert T -> double exactly.  Per element:
+ *                          Ends, Walk, xlo, xhi and p(x): those of tdeq_row_dense_extremum, exactly.
+ *                          Rule.    The 5-point Gauss-Legendre rule on [-1, 1], g = 0 .. 4 in increasing x: xi = {-TDEQ_GL5_X2,
+ *                                   -TDEQ_GL5_X1, 0, TDEQ_GL5_X1, TDEQ_GL5_X2}, omega = {TDEQ_GL5_W2, TDEQ_GL5_W1,
+ *                                   TDEQ_GL5_W0, TDEQ_GL5_W1, TDEQ_GL5_W2}; n_g = 0.5 + 0.5 * xi_g and w_g = 0.5 * omega_g are
+ *                                   constants (each one rounded fp64 operation per written operation).  It integrates a
+ *                                   polynomial of degree <= 9 exactly, a product of two quartics has degree 8: the answers are
+ *                                   exact ON THE RECORD up to rounding.
+ *                          Nodes.   Per segment s of the walk: u = xhi - xlo,  x_g = xlo + u * n_g,  W_g = (h_s * u) * w_g.
+ *                                   h_s > 0 and u >= 0, so every W_g >= 0.
+ *                          First walk.   S = S + W_g * p(x_g) and Tsum = Tsum + W_g, from 0, segments in order and g = 0 .. 4
+ *                                   inside a segment: that order is the contract of the mean.  mean = S / Tsum.
+ *                          Second walk.  v = p(x_g) - mean;  C = C + (W_g * v) * v in the same order.  variance = C / Tsum: a
+ *                                   sum of non-negative terms, never E[y^2] - E[y]^2.
+ *                          Outputs.  duration = tqb - tqa (solver-time ends, >= 0: the same number for either order of the
+ *                                   ends and either direction of the solve).  A zero-length window (tqa == tqb): duration = 0,
+ *                                   mean = p(xlo) of its segment, variance = 0 (selected).  An out-of-range end (x[i] or x2[i]
+ *                                   NaN): all three NaN, nothing read.  A non-finite coefficient propagates by IEEE rules.
+ *                                   Breakpoints and state impulses have measure zero and add nothing.
+ *                          One lane per (query, 16-byte element) walks its segments twice and keeps the mean in registers; no
+ *                          workspace, no atomics.  16-byte elements when row_len is a multiple of 16 / sizeof(T) and `mean`,
+ *                          `variance` and `coeffs` are 16-byte aligned, scalar elements otherwise, with the same bits.
+ * tdeq_row_dense_time_gram  for i < n_idx the covariance along time between the elements of the row: covariance[i][a][b] =
+ *                          (1/T) int (y_a - mean_a)(y_b - mean_b) dt, `covariance` [n_idx, row_len, row_len] double (8 *
+ *                          n_idx * row_len^2 bytes), exactly symmetric — the upper triangle is computed and the lower is its
+ *                          copy — and `variance` [n_idx, row_len] double, its diagonal bit for bit.  row_len <=
+ *                          TDEQ_ROW_TIME_MOMENTS_MAX_COV_LEN.  Nodes, W_g, S, Tsum and mean as above, with the same bits (it
+ *                          forms the means itself; it writes neither `mean` nor `duration`).  Second walk: C_ab = sum over
+ *                          segments and g of (W_g * v_a) * v_b, the products summed on v_mfma_f64_16x16x4_f64 in the
+ *                          kernel's own order; result C_ab / Tsum.  So against the definition evaluated in any other order
+ *                          the contract is an ERROR BOUND, as for tdeq_row_dense_moments, not last bits; two runs of the
+ *                          same call give the same bits (a workgroup walks a window serially; no atomics, no workspace, no
+ *                          merge), and a window's bits do not depend on which other windows share the call.  A zero-length
+ *                          window: exact zeros.  An out-of-range end: NaN.  A workgroup owns one window and one pair of
+ *                          64-element blocks, or four windows when row_len <= 16.
+ * Both: a NULL pointer, a negative size, n_seg > INT32_MAX, a time_sign other than +1 / -1 (checked, not used: every output
+ * is a solver-time quantity) or a dtype other than TDEQ_F32 / TDEQ_F64, and for tdeq_row_dense_time_gram row_len >
+ * TDEQ_ROW_TIME_MOMENTS_MAX_COV_LEN or more than INT32_MAX workgroups: TDEQ_EINVAL before any launch.  n_idx == 0 or
+ * row_len == 0: no-op.
+ */
+#define TDEQ_GL5_X1 0.53846931010568309   /* (1/3) sqrt(5 - 2 sqrt(10/7)) */
+#define TDEQ_GL5_X2 0.90617984593866399   /* (1/3) sqrt(5 + 2 sqrt(10/7)) */
+#define TDEQ_GL5_W0 0.56888888888888889   /* 128 / 225 */
+#define TDEQ_GL5_W1 0.47862867049936647   /* (322 + 13 sqrt(70)) / 900 */
+#define TDEQ_GL5_W2 0.23692688505618909   /* (322 - 13 sqrt(70)) / 900 */
+int tdeq_row_dense_time_moments(double* duration, double* mean, double* variance, const void* coeffs, int64_t n_seg,
+                                const double* seg_ta, const double* seg_tb, double time_sign, const int32_t* seg, const void* x,
+                                const double* tq, const int32_t* seg2, const void* x2, const double* tq2, int64_t n_idx,
+                                int64_t row_len, int dtype, void* stream);
+int tdeq_row_dense_time_gram(double* covariance, double* variance, const void* coeffs, int64_t n_seg, const double* seg_ta,
+                             const double* seg_tb, double time_sign, const int32_t* seg, const void* x, const double* tq,
+                             const int32_t* seg2, const void* x2, const double* tq2, int64_t n_idx, int64_t row_len, int dtype,
+                             void* stream);
 
 /*
  * ---- The times of all crossings of a level over a time window (ABI 35; `RowDenseOutput.crossing_times`) ----

@@ -13,9 +13,9 @@ from ._fallback import HostPathWarning
 from .rowwise import odeint_rowwise
 from .rowwise_event import odeint_rowwise_event
 from .rowwise_dense import (RowDenseCrossings, RowDenseCrossingTimes, RowDenseExposure, RowDenseMoments, RowDenseRanks,
-                            odeint_rowwise_dense)
+                            RowDenseTimeMoments, odeint_rowwise_dense)
 
 __version__ = "0.1.0"
 __all__ = ["odeint", "odeint_adjoint", "odeint_rowwise", "odeint_rowwise_event", "odeint_rowwise_dense", "odeint_event", "odeint_dense",
            "SOLVERS", "clear_graph_cache", "HostPathWarning", "RowDenseCrossings", "RowDenseCrossingTimes",
-           "RowDenseExposure", "RowDenseMoments", "RowDenseRanks"]
+           "RowDenseExposure", "RowDenseMoments", "RowDenseRanks", "RowDenseTimeMoments"]

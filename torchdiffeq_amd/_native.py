@@ -26,6 +26,9 @@ TDEQ_ROW_RANKS_GROUP_VALUES = 4         # thresholds one workgroup of its counti
 TDEQ_ROW_MOMENTS_SLAB_ROWS = 1024       # rows of one workgroup of the sum passes of tdeq_row_dense_moments
 TDEQ_ROW_MOMENTS_MAX_COV_LEN = 1024     # the longest row tdeq_row_dense_moments takes with a covariance
 TDEQ_ROW_CROSS_MAX_BLOCKS = 1024        # tdeq_row_dense_cross: ceil(L / 64) * ceil(M / W) blocks at most, W = 16 (M <= 16) or 64
+TDEQ_ROW_TIME_MOMENTS_MAX_COV_LEN = 256  # the longest row tdeq_row_dense_time_gram takes
+TDEQ_GL5_X1, TDEQ_GL5_X2 = 0.53846931010568309, 0.90617984593866399            # the 5-point Gauss-Legendre rule of
+TDEQ_GL5_W0, TDEQ_GL5_W1, TDEQ_GL5_W2 = 0.56888888888888889, 0.47862867049936647, 0.23692688505618909   # time_moments
 TDEQ_F32, TDEQ_F64 = 0, 1
 TDEQ_C64, TDEQ_C128 = 2, 3        # interleaved complex: the norm entry points only (include/tdeq_hip.h)
 TDEQ_BF16, TDEQ_F16 = 4, 5        # reduced-precision states: the entry points of the host-driven step (LowPrecisionHipKernels)
@@ -377,6 +380,17 @@ ABI_SIGNATURES = {
                                                      ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
                                                      ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_void_p,
                                                      ctypes.c_void_p, ctypes.c_int64]),
+    # second moments along time over a window (additive symbols within ABI 38, `RowDenseOutput.time_moments`)
+    "tdeq_row_dense_time_moments": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                   ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double,
+                                                   ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                   ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
+                                                   ctypes.c_int, ctypes.c_void_p]),
+    "tdeq_row_dense_time_gram": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
+                                                ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double, ctypes.c_void_p,
+                                                ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int,
+                                                ctypes.c_void_p]),
     # per-row step options (ABI 29,`min_step` / `max_step` / `step_t` / `jump_t` of the rowwise family)
     "tdeq_row_control_points": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(StepCtrl),
                                                ctypes.POINTER(RowState), ctypes.POINTER(RowPoints), ctypes.c_void_p,
@@ -1355,6 +1369,36 @@ class HipKernels:
         if tail is not None:
             _check(self.lib.tdeq_row_dense_exposure(area_above.data_ptr(), area_below.data_ptr(), time_above.data_ptr(), *tail),
                    "tdeq_row_dense_exposure")
+
+    def row_dense_time_moments(self, duration, mean, variance, coeffs, seg_ta, seg_tb, sign: float, seg, x, tq, seg2, x2,
+                               tq2) -> None:
+        """tdeq_row_dense_time_moments: per window its duration (fp64 [n_idx]) and per element the time mean of the record and
+        its variance around that mean (fp64 [n_idx, L]); the record and the two query lists as `_row_dense_window` describes
+        them."""
+        f64, n_idx = torch.float64, seg.numel()
+        ok = tuple(duration.shape) == (n_idx,) and duration.dtype == f64 and duration.is_contiguous()
+        tail = self._row_dense_window("row_dense_time_moments", (("mean", mean, f64, ()), ("variance", variance, f64, ())),
+                                      coeffs, seg_ta, seg_tb, sign, seg, x, tq, seg2, x2, tq2,
+                                      refuse=None if ok else f"duration must be a contiguous {f64} [{n_idx}] tensor")
+        if tail is not None:
+            _check(self.lib.tdeq_row_dense_time_moments(duration.data_ptr(), mean.data_ptr(), variance.data_ptr(), *tail),
+                   "tdeq_row_dense_time_moments")
+
+    def row_dense_time_gram(self, covariance, variance, coeffs, seg_ta, seg_tb, sign: float, seg, x, tq, seg2, x2, tq2) -> None:
+        """tdeq_row_dense_time_gram: per window the covariance along time between the elements of the row (fp64 [n_idx, L, L],
+        L <= TDEQ_ROW_TIME_MOMENTS_MAX_COV_LEN, exactly symmetric) and its diagonal (`variance` fp64 [n_idx, L]); the record
+        and the two query lists as `_row_dense_window` describes them."""
+        f64, n_idx, L = torch.float64, seg.numel(), coeffs.shape[-1]
+        refuse = None
+        if L > TDEQ_ROW_TIME_MOMENTS_MAX_COV_LEN:
+            refuse = f"a covariance takes rows of at most {TDEQ_ROW_TIME_MOMENTS_MAX_COV_LEN} elements, got {L}"
+        elif tuple(covariance.shape) != (n_idx, L, L) or covariance.dtype != f64 or not covariance.is_contiguous():
+            refuse = f"covariance must be a contiguous {f64} [{n_idx}, {L}, {L}] tensor"
+        tail = self._row_dense_window("row_dense_time_gram", (("variance", variance, f64, ()),), coeffs, seg_ta, seg_tb, sign,
+                                      seg, x, tq, seg2, x2, tq2, refuse=refuse)
+        if tail is not None:
+            _check(self.lib.tdeq_row_dense_time_gram(covariance.data_ptr(), variance.data_ptr(), *tail),
+                   "tdeq_row_dense_time_gram")
 
     def row_dense_level_times(self, n_rising, n_falling, rising, falling, level, coeffs, seg_ta, seg_tb, sign: float, seg, x,
                               tq, seg2, x2, tq2) -> None:

@@ -1063,6 +1063,73 @@ int tdeq_row_dense_exposure(void* area_above, void* area_below, double* time_abo
     });
 }
 
+// ---- second moments along time over a window: tdeq_row_dense_time_moments / _time_gram -------------------------------------
+namespace {
+
+template <typename T>
+int row_dense_time_moments_launch(double* duration, double* mean, double* variance, const RowDenseWindowIn& w, hipStream_t s) {
+    RowDenseTimeMomentsArgs<T> a;
+    row_dense_window_fill<T>(a, w);
+    a.duration = duration;
+    a.mean = mean;
+    a.variance = variance;
+    return row_vec<T>(w.row_len, all_aligned(mean, variance, w.coeffs), a.row_len, [&](auto vec) {
+        constexpr bool VEC = decltype(vec)::value;
+        a.ne = w.n_idx * a.row_len;
+        hipLaunchKernelGGL((row_dense_time_moments_kernel<T, VEC>), dim3(stream_grid(a.ne, kBlock)), dim3(kBlock), 0, s, a);
+        return check_launch();
+    });
+}
+
+// (a workgroup per (window, block pair), or per 4 windows for a row of at most 16 elements: the grid is not a stream grid)
+template <typename T>
+int row_dense_time_gram_launch(double* covariance, double* variance, const RowDenseWindowIn& w, hipStream_t s) {
+    RowDenseTimeGramArgs<T> a;
+    row_dense_window_fill<T>(a, w);
+    a.covariance = covariance;
+    a.variance = variance;
+    a.row_len = w.row_len;
+    a.ne = 0;
+    a.n_idx = w.n_idx;
+    if (w.row_len <= 16) {
+        a.tiles = a.pairs = 1;
+        const int64_t groups = (w.n_idx + 3) / 4;
+        hipLaunchKernelGGL((row_dense_time_gram_kernel<T, 16>), dim3((unsigned)groups), dim3(kBlock), 0, s, a);
+    } else {
+        a.tiles = (w.row_len + kMomTile - 1) / kMomTile;
+        a.pairs = a.tiles * (a.tiles + 1) / 2;
+        if (w.n_idx > 0x7fffffffLL / a.pairs) return TDEQ_EINVAL;
+        hipLaunchKernelGGL((row_dense_time_gram_kernel<T, kMomTile>), dim3((unsigned)(w.n_idx * a.pairs)), dim3(kBlock), 0, s, a);
+    }
+    return check_launch();
+}
+
+}  // namespace
+
+// (`duration`, `mean` and `variance` are sums of solver-time pieces: `time_sign` is checked and not used)
+int tdeq_row_dense_time_moments(double* duration, double* mean, double* variance, const void* coeffs, int64_t n_seg,
+                                const double* seg_ta, const double* seg_tb, double time_sign, const int32_t* seg, const void* x,
+                                const double* tq, const int32_t* seg2, const void* x2, const double* tq2, int64_t n_idx,
+                                int64_t row_len, int dtype, void* stream) {
+    const RowDenseWindowIn w{nullptr, 0, coeffs, n_seg, seg_ta, seg_tb, time_sign, seg, x, tq, seg2, x2, tq2, n_idx, row_len};
+    const int go = row_dense_window_check(duration && mean && variance, false, w, dtype);
+    if (go != 1) return go;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return real_dtype(dtype, [&](auto t) { return row_dense_time_moments_launch<decltype(t)>(duration, mean, variance, w, s); });
+}
+
+int tdeq_row_dense_time_gram(double* covariance, double* variance, const void* coeffs, int64_t n_seg, const double* seg_ta,
+                             const double* seg_tb, double time_sign, const int32_t* seg, const void* x, const double* tq,
+                             const int32_t* seg2, const void* x2, const double* tq2, int64_t n_idx, int64_t row_len, int dtype,
+                             void* stream) {
+    const RowDenseWindowIn w{nullptr, 0, coeffs, n_seg, seg_ta, seg_tb, time_sign, seg, x, tq, seg2, x2, tq2, n_idx, row_len};
+    if (row_len > TDEQ_ROW_TIME_MOMENTS_MAX_COV_LEN) return TDEQ_EINVAL;
+    const int go = row_dense_window_check(covariance && variance, false, w, dtype);
+    if (go != 1) return go;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return real_dtype(dtype, [&](auto t) { return row_dense_time_gram_launch<decltype(t)>(covariance, variance, w, s); });
+}
+
 // ---- order statistics across rows: tdeq_row_dense_quantiles -----------------------------------------------------------------
 namespace {
 

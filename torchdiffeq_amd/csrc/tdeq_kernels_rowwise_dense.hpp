@@ -2395,4 +2395,266 @@ __global__ __launch_bounds__(kBlock) void row_dense_ranks_finish_kernel(const Ro
     for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < a.n_q; i += stride) a.out[i] = a.flag[i] ? 0ull : a.total[i];
 }
 
+// ---- second moments ALONG TIME, inside one row (additive within ABI 38): `RowDenseOutput.time_moments` ----------------------
+// Per window and element the time mean (1/T) int y dt, the variance (1/T) int (y - mean)^2 dt and, on request, the [L, L]
+// covariance (1/T) int (y_i - mean_i)(y_j - mean_j) dt.  A segment is a quartic in x, a product of two deviations has degree
+// 8, and the 5-point Gauss-Legendre rule is exact to degree 9: per clipped segment [xlo, xhi] of the walk, u = xhi - xlo, the
+// nodes are x_g = xlo + u * kTimeNode[g] and the weights W_g = (h * u) * kTimeWeight[g] >= 0 (include/tdeq_hip.h states the
+// arithmetic).  Two walks, the second centred on the fp64 mean of the first; no E[y^2] - E[y]^2, so no variance is negative.
+//   row_dense_time_moments   the shape of row_dense_exposure: one lane per (window, 16-byte element) on row_dense_walk, twice.
+//                            S, T and the mean stay in registers between the walks; the lane of element 0 stores the
+//                            duration.  No LDS, no workspace, no atomics; the scalar and the 16-byte form have the same bits.
+//   row_dense_time_gram      the covariance as a weighted Gram matrix of the [5 * segments, L] node deviations on
+//                            v_mfma_f64_16x16x4_f64 (moments_mfma).  TW = 64: a workgroup owns one window and one pair (I, J),
+//                            I <= J, of 64-element blocks; TW = 16 (L <= 16): a wave owns a whole window, four windows per
+//                            workgroup, columns >= L zero.  Either way a GROUP of 4 TW threads owns a window and walks its
+//                            segments serially in stages of kTimeStage = 4 segments = 20 nodes = 5 k-steps: thread u of the
+//                            group takes segment u / TW of the stage and element u % TW of block I (and of block J), so a
+//                            wave reads 64 (16) neighbouring elements of one segment's five planes — coalesced along L — and
+//                            evaluates its 5 nodes by Horner in fp64.  Stage rows k = 5 * (u / TW) + g of two LDS tiles with
+//                            row stride TW + 16 (kMomStride; 16 for TW = 16, see kCrossStride16): tile A holds W_g * v of block I,
+//                            tile B holds v of block J; rows of a segment past the window's end, and columns >= L, are selected
+//                            zeros (zero weights).  First walk, mean = 0 and tile B weighted like A: the 20 rows W_g p(x_g) of
+//                            a column are added in row order — the walk order of the walk kernel, so its bits — by the first
+//                            TW (2 TW off the diagonal) threads of the group, the 20 weights by every thread; the means go to
+//                            LDS.  Second walk: wave w of the group accumulates rows 16 w .. 16 w + 15 of the block against
+//                            all TW columns, TW / 16 accumulators, per stage 5 k-steps of one A fragment and TW / 16 B
+//                            fragments (lane l: A[k0 + l / 16][16 w + l % 16], B[k0 + l / 16][16 j + l % 16], D[4 v + l /
+//                            16][l % 16]).  Two barriers per stage, none inside divergent control flow: the windows of a
+//                            workgroup run to the LONGEST stage count among them, the shorter ones on zero weights.  Epilogue:
+//                            divide by T, store out[i][j] and its mirror for i <= j < L; the diagonal is also the variance.
+//                            No workspace, no atomics, no merge across workgroups: deterministic by construction.
+// From the compiler's resource report for gfx950 (VGPRs + AGPRs / waves per SIMD / LDS bytes per workgroup; no kernel has
+// scratch), the same for fp32 and fp64 records where one figure is given:
+//   row_dense_time_moments   scalar 90 + 0 / 5 / 0      16-byte fp32 146 + 0 / 3 / 0      16-byte fp64 112 + 0 / 4 / 0
+//   row_dense_time_gram      TW = 16: 106 + 8 / 4 / 22160                TW = 64: 119 + 32 / 3 / 26792
+// (An occupancy from the compiler's report is not a time: tools/rowwise_time_moments_bench.py measures.)
+constexpr int kTimeNodes = 5;
+constexpr int kTimeStage = 4;                                         // segments of one stage
+constexpr int kTimeRows = kTimeStage * kTimeNodes;                    // 20 rows = 5 k-steps of 4
+static_assert(kTimeRows % 4 == 0, "whole k-steps");
+
+// 0.5 + 0.5 * xi_g and 0.5 * omega_g of the 5-point Gauss-Legendre rule on [-1, 1], g in increasing x (TDEQ_GL5_* of
+// include/tdeq_hip.h); a compile-time g only, so nothing is indexed at run time
+__host__ __device__ constexpr double time_node(int g) {
+    return g == 0 ? 0.5 + 0.5 * -TDEQ_GL5_X2 : g == 1 ? 0.5 + 0.5 * -TDEQ_GL5_X1 : g == 2 ? 0.5 :
+           g == 3 ? 0.5 + 0.5 * TDEQ_GL5_X1 : 0.5 + 0.5 * TDEQ_GL5_X2;
+}
+__host__ __device__ constexpr double time_weight(int g) {
+    return g == 2 ? 0.5 * TDEQ_GL5_W0 : (g == 1 || g == 3) ? 0.5 * TDEQ_GL5_W1 : 0.5 * TDEQ_GL5_W2;
+}
+
+template <typename T>
+struct RowDenseTimeMomentsArgs : RowDenseWindowArgs<T> {
+    double* duration;                 // [n_idx]
+    double* mean;                     // [n_idx, L]
+    double* variance;                 // [n_idx, L]
+};
+
+template <typename T, bool VEC>
+__global__ __launch_bounds__(kBlock) void row_dense_time_moments_kernel(const RowDenseTimeMomentsArgs<T> a) {
+    using E = typename std::conditional<VEC, typename VecOf<T>::type, T>::type;
+    constexpr int LV = VEC ? VecOf<T>::L : 1;
+    const int64_t stride = (int64_t)gridDim.x * kBlock;
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < a.ne; i += stride) {
+        const int64_t r = i / a.row_len, el = i - r * a.row_len;
+        double sum[LV], first[LV], mean[LV], var[LV], total = 0.0;
+#pragma unroll
+        for (int c = 0; c < LV; ++c) sum[c] = first[c] = var[c] = 0.0;
+        const RowDenseWindow w = row_dense_walk<T, E, LV>(a, r, el, [&](int c, const WindowQuartic& s) {
+            const double u = s.xhi - s.xlo, hu = s.h * u;
+            if (s.atA) first[c] = s(s.xlo);
+#pragma unroll
+            for (int g = 0; g < kTimeNodes; ++g) {
+                const double wg = hu * time_weight(g);
+                sum[c] = sum[c] + wg * s(s.xlo + u * time_node(g));
+                if (c == 0) total = total + wg;
+            }
+        });
+        const double t1 = a.tq[r], t2 = a.tq2[r];
+        const bool empty = t1 == t2;                                  // a zero-length window: the record's value, no spread
+#pragma unroll
+        for (int c = 0; c < LV; ++c) mean[c] = empty ? first[c] : sum[c] / total;
+        row_dense_walk<T, E, LV>(a, r, el, [&](int c, const WindowQuartic& s) {
+            const double u = s.xhi - s.xlo, hu = s.h * u;
+#pragma unroll
+            for (int g = 0; g < kTimeNodes; ++g) {
+                const double v = s(s.xlo + u * time_node(g)) - mean[c];
+                var[c] = var[c] + ((hu * time_weight(g)) * v) * v;
+            }
+        });
+        const double nan = __builtin_nan("");
+#pragma unroll
+        for (int c = 0; c < LV; ++c) {
+            mean[c] = w.bad ? nan : mean[c];
+            var[c] = w.bad ? nan : empty ? 0.0 : var[c] / total;
+        }
+        store_doubles<LV>(a.mean + i * LV, mean);
+        store_doubles<LV>(a.variance + i * LV, var);
+        if (el == 0) a.duration[r] = w.bad ? nan : (t2 < t1 ? t1 - t2 : t2 - t1);
+    }
+}
+
+template <typename T>
+struct RowDenseTimeGramArgs : RowDenseWindowArgs<T> {     // (row_len in T units; ne is not used)
+    double* covariance;               // [n_idx, L, L]
+    double* variance;                 // [n_idx, L] the diagonal
+    int64_t n_idx;
+    int64_t tiles;                    // ceil(L / TW)
+    int64_t pairs;                    // tiles (tiles + 1) / 2
+};
+
+template <typename T, int TW>
+__global__ __launch_bounds__(kBlock) void row_dense_time_gram_kernel(const RowDenseTimeGramArgs<T> a) {
+    constexpr int kGroup = 4 * TW;                                    // threads that own one window
+    constexpr int kWindows = kBlock / kGroup;                         // windows of a workgroup: 1 or 4
+    constexpr int NJ = TW / 16;                                       // accumulators of a wave
+    constexpr int kStride = TW == 64 ? kMomStride : kCrossStride16;
+    static_assert((TW == 64 || TW == 16) && kGroup % kWave == 0 && kTimeStage * TW == kGroup, "a wave per 16 block rows");
+    __shared__ double tile_a[kWindows][kTimeRows * kStride];          // W v of block I ([row][element]); TW = 64: 12.5 KB
+    __shared__ double tile_b[kWindows][kTimeRows * kStride];          // v of block J (first walk: W v)
+    __shared__ double weights[kWindows][kTimeRows];
+    __shared__ double means[kWindows][2][TW];
+    __shared__ int32_t stages[kWindows];
+
+    const int grp = (int)threadIdx.x / kGroup, u = (int)threadIdx.x % kGroup;
+    const int slot = u / TW, col = u % TW;                            // the thread's segment of a stage and its element
+    const int lane = threadIdx.x & (kWave - 1), wave = u / kWave;     // (wave: inside the group)
+    int64_t r, I = 0, J = 0;
+    if constexpr (TW == 64) {
+        r = (int64_t)blockIdx.x / a.pairs;
+        J = (int64_t)blockIdx.x % a.pairs;                            // pairs in the order (0,0) (0,1) .. (1,1) (1,2) ..
+        while (J >= a.tiles - I) {
+            J -= a.tiles - I;
+            ++I;
+        }
+        J += I;
+    } else {
+        r = (int64_t)blockIdx.x * kWindows + grp;
+    }
+    const bool diag = I == J, exists = r < a.n_idx;
+
+    // Ends of the header (row_dense_walk's prologue), the same for every thread of the group
+    int64_t sA = 0, sB = -1;
+    double tqa = 0.0, tqb = 0.0;
+    bool bad = true;
+    if (exists) {
+        sA = a.seg[r], sB = a.seg2[r];
+        tqa = a.tq[r], tqb = a.tq2[r];
+        const T xa = a.x[r], xb = a.x2[r];
+        if (tqb < tqa) {
+            const int64_t s = sA;
+            sA = sB;
+            sB = s;
+            const double t = tqa;
+            tqa = tqb;
+            tqb = t;
+        }
+        if (sA < 0) sA = 0;                                           // (nothing is read outside the record)
+        if (sB > a.n_seg - 1) sB = a.n_seg - 1;
+        bad = xa != xa || xb != xb || sA > sB;
+    }
+    const bool empty = tqa == tqb;                                    // a zero-length window: exact zeros, nothing walked
+    const int64_t n_stage = bad || empty ? 0 : (sB - sA + kTimeStage) / kTimeStage;
+    if (u == 0) stages[grp] = (int32_t)(n_stage < 0x7fffffffLL ? n_stage : 0x7fffffffLL);
+    __syncthreads();
+    int32_t n_loop = 0;                                               // the longest walk of the workgroup: uniform barriers
+#pragma unroll
+    for (int g = 0; g < kWindows; ++g) n_loop = stages[g] > n_loop ? stages[g] : n_loop;
+
+    const int64_t el_a = I * TW + col, el_b = J * TW + col;
+    const bool in_a = el_a < a.row_len, in_b = el_b < a.row_len;
+    double* const ta_ = tile_a[grp] + col;
+    double* const tb_ = tile_b[grp] + col;
+    double mean_a = 0.0, mean_b = 0.0;
+
+    // stage `at` of the walk: rows 5 slot .. 5 slot + 4 of both tiles and of the weights
+    auto stage = [&](int64_t at, auto first_walk) __attribute__((always_inline)) {
+        constexpr bool FIRST = decltype(first_walk)::value;
+        const int64_t s = sA + at * kTimeStage + slot;
+        const bool live = at < n_stage && s <= sB;
+        double e[2] = {0.0, 0.0}, d[2] = {0.0, 0.0}, c[2] = {0.0, 0.0}, b[2] = {0.0, 0.0}, q4[2] = {0.0, 0.0};
+        double xlo = 0.0, span = 0.0, hu = 0.0;
+        if (live) {
+            const double ta = a.seg_ta[s], tb = a.seg_tb[s];
+            const double h = tb - ta;
+            xlo = s == sA ? (tqa - ta) / h : 0.0;
+            span = (s == sB ? (tqb - ta) / h : 1.0) - xlo;
+            hu = h * span;
+#pragma unroll
+            for (int t = 0; t < 2; ++t) {
+                if (t == 1 && diag) continue;
+                if (!(t == 0 ? in_a : in_b)) continue;
+                const T* const p = a.q + s * a.row_len + (t == 0 ? el_a : el_b);
+                e[t] = (double)p[0];
+                d[t] = (double)p[a.q_plane];
+                c[t] = (double)p[2 * a.q_plane];
+                b[t] = (double)p[3 * a.q_plane];
+                q4[t] = (double)p[4 * a.q_plane];
+            }
+        }
+#pragma unroll
+        for (int g = 0; g < kTimeNodes; ++g) {
+            const double x = xlo + span * time_node(g), wg = hu * time_weight(g);
+            const int row = (slot * kTimeNodes + g) * kStride;
+            const double va = (e[0] + x * (d[0] + x * (c[0] + x * (b[0] + x * q4[0])))) - mean_a;
+            const double vb = diag ? va : (e[1] + x * (d[1] + x * (c[1] + x * (b[1] + x * q4[1])))) - mean_b;
+            ta_[row] = live && in_a ? wg * va : 0.0;
+            tb_[row] = live && in_b ? (FIRST ? wg * vb : vb) : 0.0;
+            if (col == 0) weights[grp][slot * kTimeNodes + g] = live ? wg : 0.0;
+        }
+    };
+
+    // first walk: the column sums S and T in row order, then the means
+    double sum = 0.0, total = 0.0;
+    const bool summing = u < TW || (!diag && u < 2 * TW);             // the threads that own a column of tile A, of tile B
+    const double* const column = (u < TW ? tile_a[grp] : tile_b[grp]) + (summing ? u % TW : 0);
+    for (int32_t at = 0; at < n_loop; ++at) {
+        stage(at, std::true_type{});
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < kTimeRows; ++k) {
+            if (summing) sum = sum + column[k * kStride];
+            total = total + weights[grp][k];
+        }
+        __syncthreads();
+    }
+    if (summing) means[grp][u / TW][u % TW] = sum / total;
+    __syncthreads();
+    mean_a = means[grp][0][col];
+    mean_b = means[grp][diag ? 0 : 1][col];
+
+    // second walk: the Gram matrix of the deviations
+    mom_f64x4 acc[NJ];
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) acc[j] = mom_f64x4{0.0, 0.0, 0.0, 0.0};
+    const double* const sa = tile_a[grp] + (lane / 16) * kStride + wave * 16 + lane % 16;
+    const double* const sb = tile_b[grp] + (lane / 16) * kStride + lane % 16;
+    for (int32_t at = 0; at < n_loop; ++at) {
+        stage(at, std::false_type{});
+        __syncthreads();
+#pragma unroll
+        for (int k0 = 0; k0 < kTimeRows; k0 += 4) {
+            const double fa = sa[k0 * kStride];
+#pragma unroll
+            for (int j = 0; j < NJ; ++j) acc[j] = moments_mfma(fa, sb[k0 * kStride + 16 * j], acc[j]);
+        }
+        __syncthreads();
+    }
+    if (!exists) return;
+    double* const out = a.covariance + r * a.row_len * a.row_len;
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+            const int64_t i0 = I * TW + wave * 16 + 4 * v + lane / 16, j0 = J * TW + 16 * j + lane % 16;
+            if (i0 > j0 || j0 >= a.row_len) continue;                 // (i0 <= j0 < L; the lower triangle is the mirror)
+            const double val = bad ? __builtin_nan("") : empty ? 0.0 : acc[j][v] / total;
+            out[i0 * a.row_len + j0] = val;
+            out[j0 * a.row_len + i0] = val;
+            if (i0 == j0) a.variance[r * a.row_len + i0] = val;
+        }
+    }
+}
+
 }  // namespace tdeq

@@ -1309,6 +1309,59 @@ class HostRowKernels:
             total = np.where(nan, np.nan, total)
         return tuple(torch.from_numpy(np.ascontiguousarray(v)) for v in (above, below, total))
 
+    # n_g = 0.5 + 0.5 xi_g and w_g = 0.5 omega_g of the 5-point Gauss-Legendre rule, g in increasing x (include/tdeq_hip.h)
+    _TIME_RULE = tuple((0.5 + 0.5 * xi, 0.5 * omega) for xi, omega in (
+        (-_native.TDEQ_GL5_X2, _native.TDEQ_GL5_W2), (-_native.TDEQ_GL5_X1, _native.TDEQ_GL5_W1), (0.0, _native.TDEQ_GL5_W0),
+        (_native.TDEQ_GL5_X1, _native.TDEQ_GL5_W1), (_native.TDEQ_GL5_X2, _native.TDEQ_GL5_W2)))
+
+    @staticmethod
+    def quartic_time_moments(q, ta, tb, sign: float, covariance: bool, src, x, tq, src2, x2, tq2):
+        """The time mean of the record `q` [5, n_seg, L] on the windows between the queries (src, x, tq) and (src2, x2, tq2) of
+        the search, per element, its variance around that mean and, with `covariance`, the covariance between the elements ->
+        (duration fp64 [n], mean, variance fp64 [n, L], covariance fp64 [n, L, L] or None).  The definition of
+        tdeq_row_dense_time_moments (include/tdeq_hip.h) as numpy ops in fp64, step k of every window's walk at once: two
+        walks over the Gauss-Legendre nodes of every clipped segment, the second centred on the mean of the first; the
+        covariance takes the upper triangle of sum (W v_i) v_j and mirrors it.  `sign` changes nothing (durations)."""
+        H, window = HostRowKernels, (ta, tb, src, x, tq, src2, x2, tq2)
+        nan, _, steps = H._window_walk(q, *window)
+        n, L = nan.shape
+        bad = nan[:, :1] if L else np.zeros((n, 1), dtype=bool)
+        total, S, first = np.zeros((n, 1)), np.zeros((n, L)), np.zeros((n, L))
+
+        def nodes(s):
+            u = s.xhi - s.xlo
+            hu = s.h * u
+            for ng, wg in H._TIME_RULE:
+                yield hu * wg, s.p(s.xlo + u * ng)
+
+        with np.errstate(all="ignore"):
+            for s in steps:
+                i = s.idx
+                if bool(s.atA.all()):
+                    first[i] = s.p(s.xlo)
+                for w, y in nodes(s):
+                    S[i], total[i] = S[i] + w * y, total[i] + w[:, :1]
+            duration = np.abs(tq2.numpy().reshape(-1) - tq.numpy().reshape(-1))
+            empty = (duration == 0.0)[:, None]
+            mean = np.where(empty, first, S / total)
+            var = np.zeros((n, L))
+            cov = np.zeros((n, L, L)) if covariance else None
+            for s in H._window_walk(q, *window)[2]:
+                i = s.idx
+                for w, y in nodes(s):
+                    v = y - mean[i]
+                    wv = w * v
+                    var[i] = var[i] + wv * v
+                    if covariance:
+                        cov[i] = cov[i] + wv[:, :, None] * v[:, None, :]
+            mean = np.where(bad, np.nan, mean)
+            var = np.where(bad, np.nan, np.where(empty, 0.0, var / total))
+            duration = np.where(bad[:, 0], np.nan, duration)
+            if covariance:
+                cov = np.triu(cov) + np.triu(cov, 1).transpose(0, 2, 1)
+                cov = np.where(bad[:, :, None], np.nan, np.where(empty[:, :, None], 0.0, cov / total[:, :, None]))
+        return tuple(None if v is None else torch.from_numpy(np.ascontiguousarray(v)) for v in (duration, mean, var, cov))
+
     def event_eval_mapped(self, out, dst, q, src, x) -> None:
         """out[dst[i] (None: i), :] = the quartic q[:, src[i]] at x[i], for the index lists `dst`, `src`."""
         if src.numel() == 0:

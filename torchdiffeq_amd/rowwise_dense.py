@@ -21,7 +21,10 @@ by `tdeq_row_dense_extremum`, which walks the window's segments and builds nothi
 above it are the same two searches followed by `tdeq_row_dense_level`, the same walk with a state machine; the area between
 the record and a level, above and below it, is the same again with `tdeq_row_dense_exposure`, which integrates `y - level`
 piece by piece while it walks; the times of ALL crossings, by direction, are the same walk with `tdeq_row_dense_level_times`,
-which stores every located time at once; the order statistics across rows are one search followed by
+which stores every located time at once; the mean, variance and covariance ALONG TIME inside a row are the same two searches
+followed by `tdeq_row_dense_time_moments`, two walks over the Gauss-Legendre nodes of the window's steps, and for the
+covariance `tdeq_row_dense_time_gram`, a weighted Gram matrix of the node values on the fp64 matrix instructions; the order
+statistics across rows are one search followed by
 `tdeq_row_dense_quantiles`, a radix select that evaluates the record in every pass; the mean, variance and covariance across
 rows are one search followed by `tdeq_row_dense_moments`, two passes of fp64 sums over slabs of rows merged in a fixed order,
 the covariance as a Gram matrix of deviations on the fp64 matrix instructions; the covariance with per-row covariates is one
@@ -40,11 +43,11 @@ import torch
 
 from . import rowwise
 from ._native import TDEQ_ROW_CROSS_MAX_BLOCKS, TDEQ_ROW_MOMENTS_MAX_COV_LEN, TDEQ_ROW_QUANTILES_MAX_RANKS, \
-    TDEQ_ROW_RANKS_MAX_VALUES, device_guard
+    TDEQ_ROW_RANKS_MAX_VALUES, TDEQ_ROW_TIME_MOMENTS_MAX_COV_LEN, device_guard
 from .rowwise import _Problem
 
 __all__ = ["odeint_rowwise_dense", "RowDenseOutput", "RowDenseExtremum", "RowDenseCrossings", "RowDenseCrossingTimes",
-           "RowDenseExposure", "RowDenseMoments", "RowDenseRanks"]
+           "RowDenseExposure", "RowDenseMoments", "RowDenseRanks", "RowDenseTimeMoments"]
 
 # the default chunk: CHUNK_ROWS_PER_ROW slots per row of the batch, at most CHUNK_BYTES of coefficients, never fewer than B
 CHUNK_ROWS_PER_ROW = 4
@@ -233,12 +236,24 @@ class RowDenseRanks(NamedTuple):
     total: torch.Tensor
 
 
+class RowDenseTimeMoments(NamedTuple):
+    """`RowDenseOutput.time_moments`: per window its true-time duration `T` (fp64 `[Q, B]`), per element the time mean `(1/T)
+    int y dt` and the variance `(1/T) int (y - mean)^2 dt` around it (fp64 `[Q, B, *row_shape]`) and, with `covariance=True`,
+    the covariance along time between the elements of the row (fp64 `[Q, B, L, L]`, exactly symmetric, its diagonal is
+    `variance`), else None."""
+    duration: torch.Tensor
+    mean: torch.Tensor
+    variance: torch.Tensor
+    covariance: torch.Tensor | None
+
+
 class RowDenseOutput:
     """The piecewise quartic of a rowwise solve; `dense(t)` evaluates it, `derivative(t)`, `antiderivative(t)` and
     `integral(ta, tb)` give its time derivative and its integrals in closed form, `maximum(ta, tb)` and `minimum(ta, tb)` its
     extrema over a time window and their times, `crossings(level, ta, tb)` and `time_above(level, ta, tb)` its crossings of a
     level and the time spent above it, `crossing_times(level, ta, tb, max_count)` the times of all its crossings by direction,
     `exposure(level, ta, tb)`, `area_above(level, ta, tb)` and `area_below(level, ta, tb)` the area between it and a level,
+    `time_moments(ta, tb)` its mean, variance and covariance along time inside each row,
     `quantiles(t, probs)` its order statistics across the rows, `moments(t)` their mean, variance and covariance,
     `cross_covariance(t, other)` their covariance with per-row covariates, `ranks(t, values)` and `cdf(t, values)` where given
     values stand among the rows (see `odeint_rowwise_dense`).
@@ -571,6 +586,68 @@ class RowDenseOutput:
         """The integral of `max(level - y, 0)` over the window, per element: `exposure(level, ta, tb, check).area_below`, the
         same launch."""
         return self.exposure(level, ta, tb, check).area_below
+
+    # -- second moments along time: two walks over the Gauss-Legendre nodes of the window's segments -----------------------------
+    def time_moments(self, ta, tb, *, covariance: bool = False, check: bool = True) -> RowDenseTimeMoments:
+        """Mean, variance and covariance ALONG TIME, inside each row, over the window between `ta` and `tb` (true time, in
+        either order: the same bits) -> `RowDenseTimeMoments(duration, mean, variance, covariance)`, all fp64 for both state
+        dtypes, without the `Q` dimension for two single times — time-averaged second moments of a long or chaotic solve, the
+        RMS amplitude of an oscillation (`sqrt(variance + mean^2)`), the L2 distance to a set point.  `duration` `[Q, B]`: `T =
+        |tb - ta|`.  `mean` `[Q, B, *row_shape]`: `(1/T) int y dt`.  `variance` `[Q, B, *row_shape]`: `(1/T) int (y - mean)^2
+        dt`, centred on that fp64 mean in a second walk — never `E[y^2] - E[y]^2`, and a sum of non-negative terms, so it is
+        never negative.  `covariance=True` also gives `covariance` `[Q, B, L, L]`, `L = prod(row_shape) <= 256`: `(1/T) int
+        (y_i - mean_i) (y_j - mean_j) dt`, exactly symmetric (the lower triangle is a copy of the upper), and `variance` is
+        then its diagonal bit for bit, the rule of `moments`; that output holds `8 * Q * B * L^2` bytes (1 GiB for 65536 rows
+        of 45 elements and one window), so reduce the rows or the windows of a call to what fits.  `ta` and `tb` take the
+        query forms of `integral` and broadcast against each other; both must lie inside `[t0[r], t1[r]]` (`check=True` names
+        the offending query of `ta` first, then of `tb`; `check=False` gives NaN in every field for the row of such a query
+        and reads nothing).  Exact on the record up to rounding: every step is a quartic in the step fraction, a product of
+        two deviations has degree 8, and the 5-point Gauss-Legendre rule on each step clipped to the window integrates that
+        exactly (see `odeint_rowwise_dense`).  `mean * duration` is `integral(ta, tb)` for ascending ends, up to rounding.  A
+        zero-length window gives `duration = 0`, `mean` = the record's value at that time in fp64 and exact zeros for the
+        variance and covariance.  Breakpoints and `jump_dy` impulses have measure zero and add nothing; a non-finite
+        coefficient propagates by IEEE rules.  A ROCm state runs HIP kernels: `tdeq_row_dense_time_moments`, one lane per
+        window and element walking the steps twice with the mean in registers, and for the covariance
+        `tdeq_row_dense_time_gram`, a weighted Gram matrix of the node values on the fp64 matrix instructions, one workgroup
+        per window and pair of 64-element blocks (four windows per workgroup for `L <= 16`) walking the steps serially — no
+        workspace, no atomics, the same bits from run to run; the windows of a call are launched in slices whose covariance
+        stays under 256 MiB, and the result does not depend on the slicing.  A CPU state runs the same definition as numpy
+        ops in fp64: the same bits for `duration`, `mean` and the variance without a covariance; for the covariance the same
+        error bound, not the same last bits.  Builds and caches nothing.  Correlation matrices (divide by the SDs), moments
+        pooled over rows and time, weights in time, higher moments and gradients are out of scope."""
+        what = "dense.time_moments(ta, tb)"
+        if not isinstance(covariance, bool):
+            raise ValueError(f"{what}: covariance must be a bool, got {covariance!r}")
+        B, L, dev, f64 = self._shape[0], self.coeffs.shape[2], self.coeffs.device, torch.float64
+        if covariance and L > TDEQ_ROW_TIME_MOMENTS_MAX_COV_LEN:
+            raise ValueError(f"{what}: covariance=True takes rows of at most {TDEQ_ROW_TIME_MOMENTS_MAX_COV_LEN} elements, "
+                             f"this row has {L}")
+        record = (self.coeffs, self._ta, self._tb, self._sign)
+        duration, cov = torch.empty(0, dtype=f64, device=dev), torch.empty(0, L, L, dtype=f64, device=dev)
+
+        def host(lists):
+            nonlocal duration, cov
+            duration, mean, var, cov = rowwise.HostRowKernels.quartic_time_moments(*record, covariance, *lists)
+            return mean, var
+
+        def device(outs, lists):
+            nonlocal duration, cov
+            n = lists[0].numel()
+            duration = torch.empty(n, dtype=f64, device=dev)
+            self._k.row_dense_time_moments(duration, *outs, *record, *lists)
+            if covariance:
+                cov = torch.empty(n, L, L, dtype=f64, device=dev)
+                step = B * max(1, MOMENTS_WORKSPACE_BYTES // max(8 * B * L * L, 1))       # whole query times per launch
+                for i in range(0, n, step):
+                    self._k.row_dense_time_gram(cov[i:i + step], outs[1][i:i + step], *record,
+                                                *(v.view(-1)[i:i + step] for v in lists))
+
+        mean, var = self._ask(what, ("ta", "tb"), (ta, tb), check, [(f64, ()), (f64, ())], host, device)
+        single = mean.dim() == len(self._shape)
+        duration = duration.view(B) if single else duration.view(-1, B)
+        if not covariance:
+            return RowDenseTimeMoments(duration, mean, var, None)
+        return RowDenseTimeMoments(duration, mean, var, cov.view(B, L, L) if single else cov.view(-1, B, L, L))
 
     # -- order statistics across rows: a radix select on the record, nothing of size [Q, B, L] is built ----------------------
     def _quantile_ranks(self, what: str, probs, ranks, as_probs: bool = False) -> list:
@@ -1095,6 +1172,22 @@ def odeint_rowwise_dense(func, y0, t0, t1, *, rtol=1e-7, atol=1e-9, method="dopr
     bits in either order of its ends, and an ascending and a descending solve of the same record give the same numbers.  A
     `jump_dy` dose at `p` flips the side at `p` with zero width for `lo <= p < hi`; `exposure(level, p, p)` is all zeros.  One
     launch after the two searches; nothing is built or cached.
+
+    Second moments along time: `dense.time_moments(ta, tb, covariance=False)` -> `RowDenseTimeMoments(duration, mean,
+    variance, covariance)`, with the query forms and the `check` of `integral`: per window its duration `T`, per ELEMENT the
+    time mean `(1/T) int y dt` and the variance `(1/T) int (y - mean)^2 dt` and, on request, the `[L, L]` covariance along time
+    between the elements of the row (`L <= 256`; `8 * Q * B * L^2` bytes) — the RMS and the variance of a component of a long
+    or chaotic solve, oscillation amplitudes, the correlation of two components along one trajectory; all fp64.  Exact on
+    the record up to rounding without sampling: a product of two deviations is a polynomial of degree 8 in the step fraction,
+    which the 5-point Gauss-Legendre rule on each step clipped to the window integrates exactly.  Two walks in fp64, the
+    second centred on the mean of the first; the quadrature weights are non-negative, so no variance is negative.
+    include/tdeq_hip.h states the nodes and the order of the sums: the walk kernel (`tdeq_row_dense_time_moments`, one lane
+    per window and element, the mean in registers between the walks) and the numpy path of a CPU state have the same bits;
+    the covariance (`tdeq_row_dense_time_gram`) is a weighted Gram matrix of the `[5 * steps, L]` node deviations on
+    `v_mfma_f64_16x16x4_f64`, one workgroup per window and pair of 64-element blocks (four windows per workgroup for `L <=
+    16`) that walks the steps serially in stages of 4 steps = 20 nodes through LDS: no workspace, no atomics, the same bits
+    from run to run, an error bound against the CPU path; `variance` is then its diagonal.  A zero-length window gives the
+    record's value and exact zeros; breakpoints and `jump_dy` impulses add nothing.  Nothing is built or cached.
 
     Order statistics across rows: `dense.quantiles(t, probs)` or `dense.quantiles(t, ranks=...)` -> `[P, Q, *row_shape]`, per
     time and ELEMENT the value of rank `k_p` among the B rows' `dense(t)` (`probs` by the "lower" rule `k = floor(p * (B - 1))`,
