@@ -1015,6 +1015,69 @@ int tdeq_row_dense_time_gram(double* covariance, double* variance, const void* c
                              void* stream);
 
 /*
+ * ---- Lagged second moments along time over a window (additive symbols within ABI 38: TDEQ_ABI_VERSION is unchanged;
+ *      `RowDenseOutput.autocovariance`) ----
+ * tdeq_row_dense_time_lagged  for k < n_lags, i < n_idx (entry n = k * n_idx + i of every [n_lags, n_idx] list) and every element
+ *                          of the row: autocovariance[n][el] = (1 / Wsum) int_lo^hi (y(t) - m)(y(t + tau) - m) dt with tau =
+ *                          lag[n] >= 0, [lo, hi + tau] the window between the queries tq[i] and tq2[i] and m = mean[i][el], an
+ *                          INPUT: the `mean` of tdeq_row_dense_time_moments on the same windows.  (seg, x, tq), (seg2, x2, tq2)
+ *                          as for tdeq_row_dense_extremum, their order does not matter; seg3[n] is the segment
+ *                          tdeq_row_dense_search finds for min(tqa + tau, tqb), tqa <= tqb — a third query list, per lag.
+ *                          `autocovariance` [n_lags, n_idx, row_len], `mean` [n_idx, row_len], `lag` [n_lags, n_idx], all
+ *                          double for both state types.  Everything is solver time and fp64, one rounded operation per written
+ *                          operation, nothing contracted.  Per entry:
+ *                          Ends.    Those of tdeq_row_dense_extremum: tqa <= tqb, segA <= segB.  segL = seg3[n] clamped to
+ *                                   [segA, segB].
+ *                          Lag.     Valid iff tau == 0 or 0 < tau < tqb - tqa.  lo = tqa, hi = tqb - tau.  An invalid lag (a
+ *                                   negative or NaN one included) or an out-of-range end: NaN, nothing read.  Valid and not
+ *                                   hi > lo (tau == 0 on a zero-length window): exact zeros (selected), nothing walked.
+ *                          Pieces.  Two cursors, sb = segA (base) and sl = segL (lead), at = lo.  Repeat: eb = seg_tb[sb],
+ *                                   el = seg_tb[sl] - tau, end = min(eb, el, hi), last = not (end < hi), end = max(end, at);
+ *                                   the piece is [at, end] on base segment sb and lead segment sl; unless last, sb advances if
+ *                                   eb <= end and sb < segB, sl advances if el <= end and sl < segB (both when the breakpoints
+ *                                   coincide: one piece, not two); at = end; stop after the last piece or when neither
+ *                                   advanced.  A piece of length zero (a lead breakpoint that rounds onto `at`) has zero
+ *                                   weights and adds exact zeros.
+ *                          Nodes.   Per piece [p_lo, p_hi], width = p_hi - p_lo: base h = seg_tb[sb] - seg_ta[sb], xlo = (p_lo
+ *                                   - seg_ta[sb]) / h, span = width / h; lead h' likewise, xlo' = ((p_lo + tau) - seg_ta[sl]) /
+ *                                   h', span' = width / h'.  x_g = xlo + span * n_g, x'_g = xlo' + span' * n_g, W_g = width *
+ *                                   w_g >= 0, with n_g, w_g of tdeq_row_dense_time_moments.
+ *                          Sum.     v = p_sb(x_g) - m, v' = p_sl(x'_g) - m (Horner as p(x) of tdeq_row_dense_extremum); C = C +
+ *                                   (W_g * v) * v' and Wsum = Wsum + W_g, from 0, pieces in order and g = 0 .. 4 inside a
+ *                                   piece: that order is the contract.  autocovariance = C / Wsum.
+ *                          Both factors on a piece are quartics in t, so the rule is exact ON THE RECORD up to rounding.
+ *                          Breakpoints and state impulses have measure zero.  `time_sign` is checked and not used: a product
+ *                          of one element with itself is the same integral in either time direction.  One lane per (lag,
+ *                          query, 16-byte element) walks the pieces once; no workspace, no atomics.  16-byte elements when
+ *                          row_len is a multiple of 16 / sizeof(T) and `autocovariance`, `mean` and `coeffs` are 16-byte
+ *                          aligned, scalar elements otherwise, with the same bits.
+ * tdeq_row_dense_time_lagged_gram  the matrix: covariance[n][a][b] = (1 / Wsum) int (y_a(t) - m_a)(y_b(t + tau) - m_b) dt in
+ *                          TRUE time, `covariance` [n_lags, n_idx, row_len, row_len] double, not symmetric for tau > 0, and
+ *                          `autocovariance` [n_lags, n_idx, row_len], its diagonal bit for bit.  row_len <=
+ *                          TDEQ_ROW_TIME_MOMENTS_MAX_COV_LEN.  Ends, Lag, Pieces, Nodes and Wsum as above, with the same bits.
+ *                          In solver time the base factor is element a for time_sign = +1 and element b for time_sign = -1
+ *                          (true time runs backwards there, so the factor that leads in true time trails in solver time); the
+ *                          kernel swaps the roles of its two operand tiles once in its prologue.  The products (W_g * v_a) *
+ *                          v'_b (time_sign = -1: (W_g * v'_a) * v_b) are summed on v_mfma_f64_16x16x4_f64 in the kernel's own
+ *                          order: against the definition in any other order the contract is an ERROR BOUND, as for
+ *                          tdeq_row_dense_time_gram; two runs of the same call give the same bits and an entry's bits do not
+ *                          depend on which other entries share the call (no atomics, no workspace, no merge).  A workgroup
+ *                          owns one entry and one ORDERED pair of 64-element blocks, or four entries when row_len <= 16.
+ * Both: a NULL pointer, a negative size, n_seg > INT32_MAX, a time_sign other than +1 / -1 or a dtype other than TDEQ_F32 /
+ * TDEQ_F64, and for tdeq_row_dense_time_lagged_gram row_len > TDEQ_ROW_TIME_MOMENTS_MAX_COV_LEN or more than INT32_MAX
+ * workgroups: TDEQ_EINVAL before any launch.  n_lags == 0, n_idx == 0 or row_len == 0: no-op.
+ */
+int tdeq_row_dense_time_lagged(double* autocovariance, const double* mean, const double* lag, const int32_t* seg3,
+                               int64_t n_lags, const void* coeffs, int64_t n_seg, const double* seg_ta, const double* seg_tb,
+                               double time_sign, const int32_t* seg, const void* x, const double* tq, const int32_t* seg2,
+                               const void* x2, const double* tq2, int64_t n_idx, int64_t row_len, int dtype, void* stream);
+int tdeq_row_dense_time_lagged_gram(double* covariance, double* autocovariance, const double* mean, const double* lag,
+                                    const int32_t* seg3, int64_t n_lags, const void* coeffs, int64_t n_seg,
+                                    const double* seg_ta, const double* seg_tb, double time_sign, const int32_t* seg,
+                                    const void* x, const double* tq, const int32_t* seg2, const void* x2, const double* tq2,
+                                    int64_t n_idx, int64_t row_len, int dtype, void* stream);
+
+/*
  * ---- The times of all crossings of a level over a time window (ABI 35; `RowDenseOutput.crossing_times`) ----
  * tdeq_row_dense_level_times  for i < n_idx (a query of row i % n_rows; n_idx is a multiple of n_rows) and every element of
  *                          the row: the times of the first K = max_count RISING and of the first K FALLING crossings of

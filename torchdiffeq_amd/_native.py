@@ -391,6 +391,18 @@ ABI_SIGNATURES = {
                                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                                 ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int,
                                                 ctypes.c_void_p]),
+    # lagged second moments along time over a window (additive symbols within ABI 38, `RowDenseOutput.autocovariance`)
+    "tdeq_row_dense_time_lagged": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                  ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
+                                                  ctypes.c_void_p, ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p,
+                                                  ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                  ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p]),
+    "tdeq_row_dense_time_lagged_gram": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                       ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64,
+                                                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double, ctypes.c_void_p,
+                                                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                       ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int,
+                                                       ctypes.c_void_p]),
     # per-row step options (ABI 29,`min_step` / `max_step` / `step_t` / `jump_t` of the rowwise family)
     "tdeq_row_control_points": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(StepCtrl),
                                                ctypes.POINTER(RowState), ctypes.POINTER(RowPoints), ctypes.c_void_p,
@@ -1399,6 +1411,46 @@ class HipKernels:
         if tail is not None:
             _check(self.lib.tdeq_row_dense_time_gram(covariance.data_ptr(), variance.data_ptr(), *tail),
                    "tdeq_row_dense_time_gram")
+
+    def _row_dense_lag(self, name: str, autocovariance, mean, lag, seg3, covariance, coeffs, seg_ta, seg_tb, sign, seg, x, tq,
+                       seg2, x2, tq2):
+        """The arguments tdeq_row_dense_time_lagged and _time_lagged_gram share, validated: `autocovariance` fp64 [K, n_idx,
+        L], `mean` fp64 [n_idx, L], `lag` fp64 and `seg3` int32 [K, n_idx] and, for the gram, `covariance` fp64 [K, n_idx, L,
+        L] -> the arguments of the entry point from `autocovariance` on, or None for nothing to do."""
+        f64, n_idx, L, K = torch.float64, seg.numel(), coeffs.shape[-1], lag.shape[0] if lag.dim() == 2 else -1
+        refuse = None
+        for what, t, dtype, shape in (("lag", lag, f64, (K, n_idx)), ("seg3", seg3, torch.int32, (K, n_idx)),
+                                      ("covariance", covariance, f64, (K, n_idx, L, L))):
+            if t is not None and (K < 0 or tuple(t.shape) != shape or t.dtype != dtype or not t.is_contiguous()):
+                refuse = refuse or f"{what} must be a contiguous {dtype} [K, {n_idx}{', L, L' if t is covariance else ''}] tensor"
+        if covariance is not None and L > TDEQ_ROW_TIME_MOMENTS_MAX_COV_LEN:
+            refuse = f"a covariance takes rows of at most {TDEQ_ROW_TIME_MOMENTS_MAX_COV_LEN} elements, got {L}"
+        tail = self._row_dense_window(name, (("autocovariance", autocovariance, f64, (max(K, 0),)), ("mean", mean, f64, ())),
+                                      coeffs, seg_ta, seg_tb, sign, seg, x, tq, seg2, x2, tq2, refuse=refuse)
+        if tail is None or K == 0:
+            return None
+        return (autocovariance.data_ptr(), mean.data_ptr(), lag.data_ptr(), seg3.data_ptr(), K, *tail)
+
+    def row_dense_time_lagged(self, autocovariance, mean, lag, seg3, coeffs, seg_ta, seg_tb, sign: float, seg, x, tq, seg2, x2,
+                              tq2) -> None:
+        """tdeq_row_dense_time_lagged: per lag, window and element the autocovariance along time around `mean` (fp64 [n_idx,
+        L], that of `row_dense_time_moments` on the same windows) -> `autocovariance` fp64 [K, n_idx, L].  `lag` fp64 [K,
+        n_idx] in solver time, `seg3` int32 [K, n_idx] the segment the search finds for min(lo + lag, hi) of each window [lo,
+        hi]; the record and the two query lists as `_row_dense_window` describes them."""
+        args = self._row_dense_lag("row_dense_time_lagged", autocovariance, mean, lag, seg3, None, coeffs, seg_ta, seg_tb, sign,
+                                   seg, x, tq, seg2, x2, tq2)
+        if args is not None:
+            _check(self.lib.tdeq_row_dense_time_lagged(*args), "tdeq_row_dense_time_lagged")
+
+    def row_dense_time_lagged_gram(self, covariance, autocovariance, mean, lag, seg3, coeffs, seg_ta, seg_tb, sign: float, seg,
+                                   x, tq, seg2, x2, tq2) -> None:
+        """tdeq_row_dense_time_lagged_gram: per lag and window the lagged covariance between the elements of the row (fp64 [K,
+        n_idx, L, L], L <= TDEQ_ROW_TIME_MOMENTS_MAX_COV_LEN, entry [i, j]: i at t, j at t + lag in true time) and its
+        diagonal (`autocovariance` fp64 [K, n_idx, L]); the other arguments as `row_dense_time_lagged`."""
+        args = self._row_dense_lag("row_dense_time_lagged_gram", autocovariance, mean, lag, seg3, covariance, coeffs, seg_ta,
+                                   seg_tb, sign, seg, x, tq, seg2, x2, tq2)
+        if args is not None:
+            _check(self.lib.tdeq_row_dense_time_lagged_gram(covariance.data_ptr(), *args), "tdeq_row_dense_time_lagged_gram")
 
     def row_dense_level_times(self, n_rising, n_falling, rising, falling, level, coeffs, seg_ta, seg_tb, sign: float, seg, x,
                               tq, seg2, x2, tq2) -> None:

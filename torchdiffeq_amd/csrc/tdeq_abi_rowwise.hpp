@@ -1130,6 +1130,104 @@ int tdeq_row_dense_time_gram(double* covariance, double* variance, const void* c
     return real_dtype(dtype, [&](auto t) { return row_dense_time_gram_launch<decltype(t)>(covariance, variance, w, s); });
 }
 
+// ---- lagged second moments along time over a window: tdeq_row_dense_time_lagged / _time_lagged_gram ------------------------
+namespace {
+
+// what the two entry points add to the window: the [n_lags, n_idx] lists and the means
+struct RowDenseLagIn {
+    double* autocovariance;
+    const double* mean;
+    const double* lag;
+    const int32_t* seg3;
+    int64_t n_lags;
+};
+
+// the checks of both entry points, in the order of row_dense_window_check -> TDEQ_EINVAL, 0 (nothing to do) or 1 (launch)
+int row_dense_lag_check(bool outputs, const RowDenseLagIn& g, const RowDenseWindowIn& w, int dtype) {
+    if (!g.mean || !g.lag || !g.seg3 || g.n_lags < 0) return TDEQ_EINVAL;
+    const int go = row_dense_window_check(outputs && g.autocovariance, false, w, dtype);
+    if (go != 1) return go;
+    return g.n_lags == 0 ? 0 : 1;
+}
+
+template <typename T>
+void row_dense_lag_fill(RowDenseTimeLaggedArgs<T>& a, const RowDenseLagIn& g, const RowDenseWindowIn& w) {
+    row_dense_window_fill<T>(a, w);
+    a.out = g.autocovariance;
+    a.covariance = nullptr;
+    a.mean = g.mean;
+    a.lag = g.lag;
+    a.seg3 = g.seg3;
+    a.n_idx = w.n_idx;
+    a.n_win = g.n_lags * w.n_idx;
+    a.tiles = 1;
+}
+
+template <typename T>
+int row_dense_time_lagged_launch(const RowDenseLagIn& g, const RowDenseWindowIn& w, hipStream_t s) {
+    RowDenseTimeLaggedArgs<T> a;
+    row_dense_lag_fill<T>(a, g, w);
+    return row_vec<T>(w.row_len, all_aligned(g.autocovariance, g.mean, w.coeffs), a.row_len, [&](auto vec) {
+        constexpr bool VEC = decltype(vec)::value;
+        a.ne = a.n_win * a.row_len;
+        hipLaunchKernelGGL((row_dense_time_lagged_kernel<T, VEC>), dim3(stream_grid(a.ne, kBlock)), dim3(kBlock), 0, s, a);
+        return check_launch();
+    });
+}
+
+// (a workgroup per (lag, window, ordered block pair), or per 4 (lag, window) for a row of at most 16 elements)
+template <typename T>
+int row_dense_time_lagged_gram_launch(double* covariance, const RowDenseLagIn& g, const RowDenseWindowIn& w, hipStream_t s) {
+    RowDenseTimeLaggedArgs<T> a;
+    row_dense_lag_fill<T>(a, g, w);
+    a.covariance = covariance;
+    a.row_len = w.row_len;
+    a.ne = 0;
+    if (w.row_len <= 16) {
+        const int64_t groups = (a.n_win + 3) / 4;
+        if (groups > 0x7fffffffLL) return TDEQ_EINVAL;
+        hipLaunchKernelGGL((row_dense_time_lagged_gram_kernel<T, 16>), dim3((unsigned)groups), dim3(kBlock), 0, s, a);
+    } else {
+        a.tiles = (w.row_len + kMomTile - 1) / kMomTile;
+        const int64_t pairs = a.tiles * a.tiles;
+        if (a.n_win > 0x7fffffffLL / pairs) return TDEQ_EINVAL;
+        hipLaunchKernelGGL((row_dense_time_lagged_gram_kernel<T, kMomTile>), dim3((unsigned)(a.n_win * pairs)), dim3(kBlock), 0,
+                           s, a);
+    }
+    return check_launch();
+}
+
+}  // namespace
+
+// (an element against itself is the same integral in either time direction: `time_sign` is checked and not used)
+int tdeq_row_dense_time_lagged(double* autocovariance, const double* mean, const double* lag, const int32_t* seg3,
+                               int64_t n_lags, const void* coeffs, int64_t n_seg, const double* seg_ta, const double* seg_tb,
+                               double time_sign, const int32_t* seg, const void* x, const double* tq, const int32_t* seg2,
+                               const void* x2, const double* tq2, int64_t n_idx, int64_t row_len, int dtype, void* stream) {
+    const RowDenseWindowIn w{nullptr, 0, coeffs, n_seg, seg_ta, seg_tb, time_sign, seg, x, tq, seg2, x2, tq2, n_idx, row_len};
+    const RowDenseLagIn g{autocovariance, mean, lag, seg3, n_lags};
+    const int go = row_dense_lag_check(true, g, w, dtype);
+    if (go != 1) return go;
+    if (n_lags > 0x7fffffffffffffffLL / n_idx / row_len) return TDEQ_EINVAL;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return real_dtype(dtype, [&](auto t) { return row_dense_time_lagged_launch<decltype(t)>(g, w, s); });
+}
+
+int tdeq_row_dense_time_lagged_gram(double* covariance, double* autocovariance, const double* mean, const double* lag,
+                                    const int32_t* seg3, int64_t n_lags, const void* coeffs, int64_t n_seg,
+                                    const double* seg_ta, const double* seg_tb, double time_sign, const int32_t* seg,
+                                    const void* x, const double* tq, const int32_t* seg2, const void* x2, const double* tq2,
+                                    int64_t n_idx, int64_t row_len, int dtype, void* stream) {
+    const RowDenseWindowIn w{nullptr, 0, coeffs, n_seg, seg_ta, seg_tb, time_sign, seg, x, tq, seg2, x2, tq2, n_idx, row_len};
+    const RowDenseLagIn g{autocovariance, mean, lag, seg3, n_lags};
+    if (row_len > TDEQ_ROW_TIME_MOMENTS_MAX_COV_LEN) return TDEQ_EINVAL;
+    const int go = row_dense_lag_check(covariance != nullptr, g, w, dtype);
+    if (go != 1) return go;
+    if (n_lags > 0x7fffffffLL / n_idx) return TDEQ_EINVAL;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return real_dtype(dtype, [&](auto t) { return row_dense_time_lagged_gram_launch<decltype(t)>(covariance, g, w, s); });
+}
+
 // ---- order statistics across rows: tdeq_row_dense_quantiles -----------------------------------------------------------------
 namespace {
 

@@ -2657,4 +2657,293 @@ __global__ __launch_bounds__(kBlock) void row_dense_time_gram_kernel(const RowDe
     }
 }
 
+// ---- LAGGED second moments along time (additive within ABI 38): `RowDenseOutput.autocovariance` -----------------------------
+// Per lag tau >= 0, window [lo, hi + tau] and element the autocovariance (1 / (hi - lo)) int_lo^hi (y_i(t) - m_i)(y_i(t + tau)
+// - m_i) dt and, on request, the [L, L] matrix with y_j(t + tau) as the second factor, m the whole-window mean of
+// row_dense_time_moments (an INPUT here).  The two factors live on different steps of the record, so the overlap [lo, hi] is cut
+// at the union of the breakpoints of the BASE steps and of the LEAD steps shifted by -tau: on a piece both factors are quartics
+// in t, their product has degree 8, and the rule of row_dense_time_moments is exact on it.  include/tdeq_hip.h states the
+// arithmetic.
+//   LagCursor                the merge of the two step lists: two cursors and next(), one piece per call, at most one advance of
+//                            each cursor; the only walk here that follows two lists
+//   row_dense_lag_walk       the prologue (ends in solver-time order, the lag's validity, the lead cursor at seg3 = the search
+//                            of lo + tau) and the serial loop over the pieces: per piece the five planes of both steps and per
+//                            element a LagQuartics for the visitor
+//   row_dense_time_lagged    the shape of row_dense_time_moments: one lane per (lag, window, 16-byte element) on
+//                            row_dense_lag_walk, once.  Mean, sum and weight total stay in registers.  No LDS, no workspace, no
+//                            atomics; the scalar and the 16-byte form have the same bits.
+//   row_dense_time_lagged_gram   the matrix as a NON-symmetric weighted Gram product on v_mfma_f64_16x16x4_f64, in the frame of
+//                            row_dense_time_gram (groups of 4 TW threads, stages of kTimeStage PIECES = 20 rows = 5 k-steps, the
+//                            same two LDS tiles and strides, fragments and barriers) with four differences.  (1) The grid is
+//                            (lag, window) x ALL tiles^2 ordered block pairs (I, J): no I <= J, no diagonal shortcut, no mirror
+//                            store.  (2) Tile A holds W_g (y_I(t_g) - m_I) on the piece's BASE step, tile B y_J(t_g + tau) - m_J
+//                            on its LEAD step.  For a descending solve true time runs against solver time and the factor that
+//                            leads in true time trails in solver time: the prologue swaps the roles of the two tiles once
+//                            (`swap`), nothing else changes and the store stays out[i][j].  (3) Every thread replays its
+//                            group's merge: once dry, to count the pieces (the stage count must be known before the first
+//                            barrier), then one cursor kept across the stages, at most kTimeStage next() per stage, thread
+//                            `slot` keeping the piece it stops at.  A workgroup of TW = 64 owns one (lag, window), so its seg_tb
+//                            loads are uniform.  (4) One walk: the means are read from global memory once.
+//                            The weight total is summed by every thread from the `weights` tile in row order.  Epilogue:
+//                            divide, store out[i][j] for i, j < L, the diagonal also to `autocovariance`.  Deterministic: no
+//                            atomics, no workspace, no merge across workgroups.
+// From the compiler's resource report for gfx950 (VGPRs + AGPRs / waves per SIMD / LDS bytes per workgroup; no kernel has
+// scratch):
+//   row_dense_time_lagged        scalar 78 + 0 / 6 / 0 (fp64: 74)    16-byte fp32 130 + 0 / 3 / 0    16-byte fp64 124 + 0 / 4 / 0
+//   row_dense_time_lagged_gram   TW = 16: 98 + 8 / 4 / 21136                TW = 64: 116 + 32 / 3 / 25768
+// (tools/rowwise_autocovariance_bench.py measures.)
+template <typename T>
+struct RowDenseTimeLaggedArgs : RowDenseWindowArgs<T> {   // (the gram: row_len in T units, ne not used)
+    double* out;                      // [n_lags, n_idx, L] the autocovariance
+    double* covariance;               // [n_lags, n_idx, L, L] (the gram only)
+    const double* mean;               // [n_idx, L] of row_dense_time_moments
+    const double* lag;                // [n_lags, n_idx] tau
+    const int32_t* seg3;              // [n_lags, n_idx] the segment of min(lo + tau, the window's far end) (row_dense_search)
+    int64_t n_idx;
+    int64_t n_win;                    // n_lags * n_idx
+    int64_t tiles;                    // ceil(L / TW) (the gram only)
+};
+
+struct LagPiece {
+    int64_t sb, sl;                   // the base and the lead segment
+    double lo, hi;                    // the piece in base time, lo <= hi
+};
+
+// Pieces of the header.  `done` before the first next(): nothing to walk.
+struct LagCursor {
+    const double* seg_tb;
+    int64_t sb, sl, sB;               // the cursors, and the segment neither passes
+    double at, hi, tau;               // the start of the next piece, the end of the overlap
+    bool done;
+    __device__ __forceinline__ LagPiece next() {
+        const double eb = seg_tb[sb], el = seg_tb[sl] - tau;
+        double end = eb < el ? eb : el;
+        end = end < hi ? end : hi;
+        const bool last = !(end < hi);
+        if (end < at) end = at;                                       // (a rounded lead breakpoint just before `at`)
+        const LagPiece p{sb, sl, at, end};
+        const bool step_b = !last && eb <= end && sb < sB, step_l = !last && el <= end && sl < sB;
+        sb += step_b ? 1 : 0;
+        sl += step_l ? 1 : 0;
+        at = end;
+        done = !(step_b || step_l);                                   // the last piece (or a record that is not one)
+        return p;
+    }
+};
+
+struct LagWindow {
+    LagCursor cur;
+    int64_t r;                        // the window of this (lag, window)
+    bool bad, empty;                  // NaN (an end out of range, an invalid lag); exact zeros (no overlap)
+};
+
+// Ends and Lag of the header for entry n of the [n_lags, n_idx] list
+template <typename T>
+__device__ __forceinline__ LagWindow row_dense_lag_open(const RowDenseTimeLaggedArgs<T>& a, int64_t n) {
+    const int64_t r = n % a.n_idx;
+    int64_t sA = a.seg[r], sB = a.seg2[r], sL = a.seg3[n];
+    double tqa = a.tq[r], tqb = a.tq2[r];
+    const T xa = a.x[r], xb = a.x2[r];
+    const double tau = a.lag[n];
+    if (tqb < tqa) {
+        const int64_t s = sA;
+        sA = sB;
+        sB = s;
+        const double t = tqa;
+        tqa = tqb;
+        tqb = t;
+    }
+    if (sA < 0) sA = 0;                                               // (nothing is read outside the record)
+    if (sB > a.n_seg - 1) sB = a.n_seg - 1;
+    if (sL < sA) sL = sA;
+    if (sL > sB) sL = sB;
+    const bool valid = tau == 0.0 || (tau > 0.0 && tau < tqb - tqa);  // (a NaN lag fails every comparison)
+    const bool bad = xa != xa || xb != xb || sA > sB || !valid;
+    const double hi = tqb - tau;
+    const bool empty = !(hi > tqa);
+    return {{a.seg_tb, sA, sL, sB, tqa, hi, tau, bad || empty}, r, bad, empty};
+}
+
+// one element on one piece, as the walk hands it over: both quartics, their fractions at the piece's start, their spans and
+// the piece's length
+struct LagQuartics {
+    double e, d, c, b, a;             // the base step's coefficients
+    double e2, d2, c2, b2, a2;        // the lead step's
+    double xlo, span, xlo2, span2, width;
+    __device__ __forceinline__ double base(double x) const { return e + x * (d + x * (c + x * (b + x * a))); }
+    __device__ __forceinline__ double lead(double x) const { return e2 + x * (d2 + x * (c2 + x * (b2 + x * a2))); }
+};
+
+// The two-cursor walk of entry `w` for the LV elements at `el`: each(c, LagQuartics) for every piece in order and, inside it,
+// every element c.  Serial by construction.
+template <typename T, typename E, int LV, typename F>
+__device__ __forceinline__ void row_dense_lag_walk(const RowDenseTimeLaggedArgs<T>& a, LagCursor cur, int64_t el, F&& each) {
+    while (!cur.done) {
+        const LagPiece p = cur.next();
+        T qe[LV], qd[LV], qc[LV], qb[LV], qa[LV], le[LV], ld[LV], lc[LV], lb[LV], la[LV];
+        load_planes<T, E, LV>(a.q, a.q_plane, p.sb * a.row_len + el, qe, qd, qc, qb, qa);
+        load_planes<T, E, LV>(a.q, a.q_plane, p.sl * a.row_len + el, le, ld, lc, lb, la);
+        const double ta = a.seg_ta[p.sb], h = a.seg_tb[p.sb] - ta;
+        const double ta2 = a.seg_ta[p.sl], h2 = a.seg_tb[p.sl] - ta2;
+        const double width = p.hi - p.lo;
+        const double xlo = (p.lo - ta) / h, span = width / h;
+        const double xlo2 = ((p.lo + cur.tau) - ta2) / h2, span2 = width / h2;
+#pragma unroll
+        for (int c = 0; c < LV; ++c)
+            each(c, LagQuartics{(double)qe[c], (double)qd[c], (double)qc[c], (double)qb[c], (double)qa[c], (double)le[c],
+                                (double)ld[c], (double)lc[c], (double)lb[c], (double)la[c], xlo, span, xlo2, span2, width});
+    }
+}
+
+template <typename T, bool VEC>
+__global__ __launch_bounds__(kBlock) void row_dense_time_lagged_kernel(const RowDenseTimeLaggedArgs<T> a) {
+    using E = typename std::conditional<VEC, typename VecOf<T>::type, T>::type;
+    constexpr int LV = VEC ? VecOf<T>::L : 1;
+    const int64_t stride = (int64_t)gridDim.x * kBlock;
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < a.ne; i += stride) {
+        const int64_t n = i / a.row_len, el = i - n * a.row_len;
+        const LagWindow w = row_dense_lag_open<T>(a, n);
+        double mean[LV], acc[LV], total = 0.0;
+        load_doubles<LV>(a.mean + (w.r * a.row_len + el) * LV, mean);
+#pragma unroll
+        for (int c = 0; c < LV; ++c) acc[c] = 0.0;
+        row_dense_lag_walk<T, E, LV>(a, w.cur, el, [&](int c, const LagQuartics& s) {
+#pragma unroll
+            for (int g = 0; g < kTimeNodes; ++g) {
+                const double wg = s.width * time_weight(g);
+                const double v = s.base(s.xlo + s.span * time_node(g)) - mean[c];
+                const double v2 = s.lead(s.xlo2 + s.span2 * time_node(g)) - mean[c];
+                acc[c] = acc[c] + (wg * v) * v2;
+                if (c == 0) total = total + wg;
+            }
+        });
+#pragma unroll
+        for (int c = 0; c < LV; ++c) acc[c] = w.bad ? __builtin_nan("") : w.empty ? 0.0 : acc[c] / total;
+        store_doubles<LV>(a.out + i * LV, acc);
+    }
+}
+
+template <typename T, int TW>
+__global__ __launch_bounds__(kBlock) void row_dense_time_lagged_gram_kernel(const RowDenseTimeLaggedArgs<T> a) {
+    constexpr int kGroup = 4 * TW;                                    // threads that own one (lag, window)
+    constexpr int kWindows = kBlock / kGroup;                         // entries of a workgroup: 1 or 4
+    constexpr int NJ = TW / 16;                                       // accumulators of a wave
+    constexpr int kStride = TW == 64 ? kMomStride : kCrossStride16;
+    static_assert((TW == 64 || TW == 16) && kGroup % kWave == 0 && kTimeStage * TW == kGroup, "a wave per 16 block rows");
+    __shared__ double tile_a[kWindows][kTimeRows * kStride];          // W v of block I ([row][element])
+    __shared__ double tile_b[kWindows][kTimeRows * kStride];          // v of block J
+    __shared__ double weights[kWindows][kTimeRows];
+    __shared__ int32_t stages[kWindows];
+
+    const int grp = (int)threadIdx.x / kGroup, u = (int)threadIdx.x % kGroup;
+    const int slot = u / TW, col = u % TW;                            // the thread's piece of a stage and its element
+    const int lane = threadIdx.x & (kWave - 1), wave = u / kWave;     // (wave: inside the group)
+    int64_t n, I = 0, J = 0;
+    if constexpr (TW == 64) {
+        const int64_t pairs = a.tiles * a.tiles;
+        n = (int64_t)blockIdx.x / pairs;
+        I = ((int64_t)blockIdx.x % pairs) / a.tiles;
+        J = (int64_t)blockIdx.x % a.tiles;
+    } else {
+        n = (int64_t)blockIdx.x * kWindows + grp;
+    }
+    const bool exists = n < a.n_win;
+    LagWindow w{{a.seg_tb, 0, 0, 0, 0.0, 0.0, 0.0, true}, 0, true, false};
+    if (exists) w = row_dense_lag_open<T>(a, n);
+    LagCursor cur = w.cur;
+    const double tau = cur.tau;
+    const bool swap = a.sign < 0.0;                                   // tile A takes the lead step, tile B the base step
+
+    int64_t pieces = 0;                                               // the dry replay
+    for (LagCursor dry = cur; !dry.done; ++pieces) dry.next();
+    const int64_t n_stage = (pieces + kTimeStage - 1) / kTimeStage;
+    if (u == 0) stages[grp] = (int32_t)(n_stage < 0x7fffffffLL ? n_stage : 0x7fffffffLL);
+    __syncthreads();
+    int32_t n_loop = 0;                                               // the longest walk of the workgroup: uniform barriers
+#pragma unroll
+    for (int g = 0; g < kWindows; ++g) n_loop = stages[g] > n_loop ? stages[g] : n_loop;
+
+    const int64_t el_a = I * TW + col, el_b = J * TW + col;
+    const bool in_a = el_a < a.row_len, in_b = el_b < a.row_len;
+    double* const ta_ = tile_a[grp] + col;
+    double* const tb_ = tile_b[grp] + col;
+    const double mean_a = exists && in_a ? a.mean[w.r * a.row_len + el_a] : 0.0;
+    const double mean_b = exists && in_b ? a.mean[w.r * a.row_len + el_b] : 0.0;
+
+    mom_f64x4 acc[NJ];
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) acc[j] = mom_f64x4{0.0, 0.0, 0.0, 0.0};
+    const double* const sa = tile_a[grp] + (lane / 16) * kStride + wave * 16 + lane % 16;
+    const double* const sb = tile_b[grp] + (lane / 16) * kStride + lane % 16;
+    double total = 0.0;
+    for (int32_t at = 0; at < n_loop; ++at) {
+        // the stage's pieces: rows 5 slot .. 5 slot + 4 of both tiles and of the weights
+        LagPiece mine{0, 0, 0.0, 0.0};
+        bool live = false;
+#pragma unroll
+        for (int k = 0; k < kTimeStage; ++k) {
+            if (cur.done) continue;
+            const LagPiece p = cur.next();
+            if (k == slot) {
+                mine = p;
+                live = true;
+            }
+        }
+        double e[2] = {0.0, 0.0}, d[2] = {0.0, 0.0}, c[2] = {0.0, 0.0}, b[2] = {0.0, 0.0}, q4[2] = {0.0, 0.0};
+        double xlo[2] = {0.0, 0.0}, span[2] = {0.0, 0.0}, width = 0.0;
+        if (live) {
+            width = mine.hi - mine.lo;
+#pragma unroll
+            for (int t = 0; t < 2; ++t) {
+                const bool lead = (t == 1) != swap;
+                const int64_t s = lead ? mine.sl : mine.sb;
+                const double ta = a.seg_ta[s], h = a.seg_tb[s] - ta;
+                xlo[t] = ((lead ? mine.lo + tau : mine.lo) - ta) / h;
+                span[t] = width / h;
+                if (!(t == 0 ? in_a : in_b)) continue;
+                const T* const p = a.q + s * a.row_len + (t == 0 ? el_a : el_b);
+                e[t] = (double)p[0];
+                d[t] = (double)p[a.q_plane];
+                c[t] = (double)p[2 * a.q_plane];
+                b[t] = (double)p[3 * a.q_plane];
+                q4[t] = (double)p[4 * a.q_plane];
+            }
+        }
+#pragma unroll
+        for (int g = 0; g < kTimeNodes; ++g) {
+            const double x = xlo[0] + span[0] * time_node(g), x2 = xlo[1] + span[1] * time_node(g);
+            const double wg = width * time_weight(g);
+            const int row = (slot * kTimeNodes + g) * kStride;
+            const double va = (e[0] + x * (d[0] + x * (c[0] + x * (b[0] + x * q4[0])))) - mean_a;
+            const double vb = (e[1] + x2 * (d[1] + x2 * (c[1] + x2 * (b[1] + x2 * q4[1])))) - mean_b;
+            ta_[row] = live && in_a ? wg * va : 0.0;
+            tb_[row] = live && in_b ? vb : 0.0;
+            if (col == 0) weights[grp][slot * kTimeNodes + g] = live ? wg : 0.0;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < kTimeRows; ++k) total = total + weights[grp][k];
+#pragma unroll
+        for (int k0 = 0; k0 < kTimeRows; k0 += 4) {
+            const double fa = sa[k0 * kStride];
+#pragma unroll
+            for (int j = 0; j < NJ; ++j) acc[j] = moments_mfma(fa, sb[k0 * kStride + 16 * j], acc[j]);
+        }
+        __syncthreads();
+    }
+    if (!exists) return;
+    double* const out = a.covariance + n * a.row_len * a.row_len;
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+            const int64_t i0 = I * TW + wave * 16 + 4 * v + lane / 16, j0 = J * TW + 16 * j + lane % 16;
+            if (i0 >= a.row_len || j0 >= a.row_len) continue;
+            const double val = w.bad ? __builtin_nan("") : w.empty ? 0.0 : acc[j][v] / total;
+            out[i0 * a.row_len + j0] = val;
+            if (i0 == j0) a.out[n * a.row_len + i0] = val;
+        }
+    }
+}
+
 }  // namespace tdeq

@@ -1362,6 +1362,79 @@ class HostRowKernels:
                 cov = np.where(bad[:, :, None], np.nan, np.where(empty[:, :, None], 0.0, cov / total[:, :, None]))
         return tuple(None if v is None else torch.from_numpy(np.ascontiguousarray(v)) for v in (duration, mean, var, cov))
 
+    @staticmethod
+    def _lag_pieces(tb, sb: int, sl: int, sB: int, lo: float, hi: float, tau: float):
+        """Pieces of tdeq_row_dense_time_lagged (include/tdeq_hip.h): the merge of the base steps from `sb` and of the lead
+        steps from `sl`, shifted by -tau, over [lo, hi] -> (base segment, lead segment, p_lo, p_hi) of every piece in order."""
+        at, done = np.float64(lo), False
+        while not done:
+            eb, el = tb[sb], tb[sl] - tau
+            end = eb if eb < el else el
+            end = end if end < hi else hi
+            last = not end < hi
+            if end < at:
+                end = at
+            yield sb, sl, at, end
+            step_b, step_l = not last and eb <= end and sb < sB, not last and el <= end and sl < sB
+            sb, sl, at, done = sb + step_b, sl + step_l, end, not (step_b or step_l)
+
+    @staticmethod
+    def quartic_time_lagged(q, ta, tb, sign: float, covariance: bool, mean, lag, src3, src, x, tq, src2, x2, tq2):
+        """The lagged covariance along time of the record `q` [5, n_seg, L] around `mean` fp64 [n, L] on the windows between the
+        queries (src, x, tq) and (src2, x2, tq2) of the search, per lag `lag` fp64 [K, n] (solver time; `src3` int32 [K, n]:
+        the segment of min(lo + lag, hi) of the window [lo, hi]) -> (autocovariance fp64 [K, n, L], covariance fp64 [K, n, L,
+        L] or None).  The definition of tdeq_row_dense_time_lagged (include/tdeq_hip.h) as numpy ops in fp64, one (lag, window)
+        after the other, the elements of a row at once: the same pieces, nodes and order of the sums, so the autocovariance
+        has the kernel's bits; the covariance sums (W v_i) v'_j in piece order (the kernel's matrix instruction has its own
+        order) with i on the base step for `sign` > 0 and on the lead step for `sign` < 0, and its diagonal is the
+        autocovariance returned with it."""
+        H, co = HostRowKernels, q.numpy().astype(np.float64)
+        sta, stb, m, tau_all = ta.numpy(), tb.numpy(), mean.numpy(), lag.numpy()
+        t1, t2, xa, xb = tq.numpy().reshape(-1), tq2.numpy().reshape(-1), x.numpy(), x2.numpy()
+        s1, s2, s3 = src.numpy().astype(np.int64), src2.numpy().astype(np.int64), src3.numpy().astype(np.int64)
+        (K, n), L = tau_all.shape, co.shape[2]
+        auto = np.zeros((K, n, L))
+        cov = np.zeros((K, n, L, L)) if covariance else None
+
+        def value(c, xs):
+            return c[0] + xs * (c[1] + xs * (c[2] + xs * (c[3] + xs * c[4])))
+
+        with np.errstate(all="ignore"):
+            for k in range(K):
+                for r in range(n):
+                    (tqa, sA), (tqb, sB) = ((t2[r], s2[r]), (t1[r], s1[r])) if t2[r] < t1[r] else ((t1[r], s1[r]), (t2[r], s2[r]))
+                    tau = tau_all[k, r]
+                    valid = tau == 0.0 or (tau > 0.0 and tau < tqb - tqa)
+                    if np.isnan(xa[r]) or np.isnan(xb[r]) or sA > sB or not valid:
+                        auto[k, r] = np.nan
+                        if covariance:
+                            cov[k, r] = np.nan
+                        continue
+                    hi = tqb - tau
+                    if not hi > tqa:
+                        continue                                         # exact zeros
+                    C, total = np.zeros((L, L)) if covariance else np.zeros(L), np.float64(0.0)
+                    for sb, sl, p_lo, p_hi in H._lag_pieces(stb, sA, min(max(s3[k, r], sA), sB), sB, tqa, hi, tau):
+                        h, h2, width = stb[sb] - sta[sb], stb[sl] - sta[sl], p_hi - p_lo
+                        xlo, span = (p_lo - sta[sb]) / h, width / h
+                        xlo2, span2 = ((p_lo + tau) - sta[sl]) / h2, width / h2
+                        for ng, wg in H._TIME_RULE:
+                            w = width * wg
+                            v, v2 = value(co[:, sb], xlo + span * ng) - m[r], value(co[:, sl], xlo2 + span2 * ng) - m[r]
+                            if not covariance:
+                                C = C + (w * v) * v2
+                            elif sign > 0:
+                                C = C + (w * v)[:, None] * v2[None, :]
+                            else:
+                                C = C + (w * v2)[:, None] * v[None, :]
+                            total = total + w
+                    if covariance:
+                        cov[k, r] = C / total
+                        auto[k, r] = np.diagonal(cov[k, r])
+                    else:
+                        auto[k, r] = C / total
+        return torch.from_numpy(auto), None if cov is None else torch.from_numpy(cov)
+
     def event_eval_mapped(self, out, dst, q, src, x) -> None:
         """out[dst[i] (None: i), :] = the quartic q[:, src[i]] at x[i], for the index lists `dst`, `src`."""
         if src.numel() == 0:

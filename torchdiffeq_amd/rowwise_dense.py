@@ -23,7 +23,9 @@ the record and a level, above and below it, is the same again with `tdeq_row_den
 piece by piece while it walks; the times of ALL crossings, by direction, are the same walk with `tdeq_row_dense_level_times`,
 which stores every located time at once; the mean, variance and covariance ALONG TIME inside a row are the same two searches
 followed by `tdeq_row_dense_time_moments`, two walks over the Gauss-Legendre nodes of the window's steps, and for the
-covariance `tdeq_row_dense_time_gram`, a weighted Gram matrix of the node values on the fp64 matrix instructions; the order
+covariance `tdeq_row_dense_time_gram`, a weighted Gram matrix of the node values on the fp64 matrix instructions; the LAGGED
+covariance along time is those, a third search per lag and `tdeq_row_dense_time_lagged`, one walk with two cursors over the
+merged breakpoints of `t` and `t + lag`, or `tdeq_row_dense_time_lagged_gram`, its non-symmetric Gram product; the order
 statistics across rows are one search followed by
 `tdeq_row_dense_quantiles`, a radix select that evaluates the record in every pass; the mean, variance and covariance across
 rows are one search followed by `tdeq_row_dense_moments`, two passes of fp64 sums over slabs of rows merged in a fixed order,
@@ -47,7 +49,7 @@ from ._native import TDEQ_ROW_CROSS_MAX_BLOCKS, TDEQ_ROW_MOMENTS_MAX_COV_LEN, TD
 from .rowwise import _Problem
 
 __all__ = ["odeint_rowwise_dense", "RowDenseOutput", "RowDenseExtremum", "RowDenseCrossings", "RowDenseCrossingTimes",
-           "RowDenseExposure", "RowDenseMoments", "RowDenseRanks", "RowDenseTimeMoments"]
+           "RowDenseExposure", "RowDenseMoments", "RowDenseRanks", "RowDenseTimeMoments", "RowDenseAutocovariance"]
 
 # the default chunk: CHUNK_ROWS_PER_ROW slots per row of the batch, at most CHUNK_BYTES of coefficients, never fewer than B
 CHUNK_ROWS_PER_ROW = 4
@@ -247,6 +249,18 @@ class RowDenseTimeMoments(NamedTuple):
     covariance: torch.Tensor | None
 
 
+class RowDenseAutocovariance(NamedTuple):
+    """`RowDenseOutput.autocovariance`: per window its true-time duration `T` and per element the time mean (fp64 `[Q, B]` and
+    `[Q, B, *row_shape]`: those of `time_moments`, bit for bit), per lag and element the autocovariance `C_ii(tau)` around that
+    mean (fp64 `[K, Q, B, *row_shape]`) and, with `covariance=True`, the lagged covariance `C_ij(tau)` between the elements of
+    the row (fp64 `[K, Q, B, L, L]`, `i` at `t` and `j` at `t + tau`, not symmetric; its diagonal is `autocovariance`), else
+    None."""
+    duration: torch.Tensor
+    mean: torch.Tensor
+    autocovariance: torch.Tensor
+    covariance: torch.Tensor | None
+
+
 class RowDenseOutput:
     """The piecewise quartic of a rowwise solve; `dense(t)` evaluates it, `derivative(t)`, `antiderivative(t)` and
     `integral(ta, tb)` give its time derivative and its integrals in closed form, `maximum(ta, tb)` and `minimum(ta, tb)` its
@@ -333,13 +347,15 @@ class RowDenseOutput:
         status = torch.full((1,), _NONE, dtype=torch.int32, device=self.coeffs.device)
         return (*self._search_device(tq, status), status)
 
-    def _ask(self, what: str, names, ts, check: bool, spec, host, device, prefix: bool = False):
+    def _ask(self, what: str, names, ts, check: bool, spec, host, device, prefix: bool = False, flags: list | None = None):
         """The steps every query method shares.  The query lists `ts` (called `names` in messages) are parsed and broadcast
         against each other; the outputs are allocated from `spec`, one (dtype, leading dimensions) each, as `[*leading, Q * B,
         L]`; every list is searched; then the one evaluation: for a CPU state `host(lists)` gives the outputs' values, else
         `device(outs, lists)` launches into them, with `lists` = [seg, x, tq] of every list in turn, `tq` in solver time, and
         with `prefix` the prefix store as one more argument.  With `check` the status words of the searches are read once and
-        the first out-of-range query raises -> the outputs as `[*leading, Q, B, *row_shape]`, without the Q of single times."""
+        the first out-of-range query raises -> the outputs as `[*leading, Q, B, *row_shape]`, without the Q of single times.
+        `flags`: a list of further status words of the caller's own; `device` gets them as one more int32 tensor to fill, and
+        with `check` their values come back in the list from the same read (`host` fills the list itself)."""
         tqs, single = self._query_lists(what, names, ts)
         Q, B = tqs[0].shape
         if self._k is not None and Q * B >= _NONE:
@@ -357,11 +373,13 @@ class RowDenseOutput:
                     for dst, src in zip(outs, host(lists, *more)):
                         dst.copy_(src)
                 else:
-                    status = torch.full((len(tqs),), _NONE, dtype=torch.int32, device=dev)
+                    status = torch.full((len(tqs) + len(flags or ()),), _NONE, dtype=torch.int32, device=dev)
                     lists = [v for i, tq in enumerate(tqs) for v in (*self._search_device(tq, status[i:i + 1]), tq)]
-                    device(outs, lists, *more)
+                    device(outs, lists, *more, *((status[len(tqs):],) if flags else ()))
                     if check:
                         firsts = status.tolist()                          # the one read
+                        if flags:
+                            firsts, flags[:] = firsts[:len(tqs)], firsts[len(tqs):]
         if check:
             self._raise_out_of_range(what, names, tqs, firsts)
         outs = [v.view(*v.shape[:-2], Q, *self._shape) for v in outs]
@@ -648,6 +666,140 @@ class RowDenseOutput:
         if not covariance:
             return RowDenseTimeMoments(duration, mean, var, None)
         return RowDenseTimeMoments(duration, mean, var, cov.view(B, L, L) if single else cov.view(-1, B, L, L))
+
+    # -- lagged second moments along time: one walk with two cursors over the merged breakpoints of t and t + lag ---------------
+    def _lags(self, what: str, lags):
+        """lags -> (fp64 `[K, B]` on the state's device, lags was a single number).  Lags that live on the host are checked
+        here; those on a device by the flag of `autocovariance`."""
+        B, dev = self._shape[0], self.coeffs.device
+        if isinstance(lags, torch.Tensor):
+            if lags.requires_grad and torch.is_grad_enabled():
+                raise NotImplementedError("odeint_rowwise_dense: the dense output does not propagate gradients (lags requires "
+                                          "grad); detach it or evaluate under torch.no_grad()")
+            if lags.is_complex() or lags.dtype == torch.bool or lags.dim() > 2 or (lags.dim() == 2 and lags.shape[1] != B) \
+                    or (lags.dim() > 0 and lags.shape[0] == 0):
+                raise ValueError(f"{what}: lags must be a number, a 0-dim tensor, [K] or [K, B] = [K, {B}] with K >= 1, got a "
+                                 f"{lags.dtype} tensor of shape {tuple(lags.shape)}")
+            lag = lags.detach().to(torch.float64)
+        elif isinstance(lags, (int, float)) and not isinstance(lags, bool):
+            lag = torch.tensor(float(lags), dtype=torch.float64)
+        else:
+            raise ValueError(f"{what}: lags must be a number or a tensor, got {type(lags).__name__}")
+        if lag.device.type == "cpu" and not bool((lag >= 0).all()):
+            raise ValueError(f"{what}: lags must be >= 0 and not NaN (C(-lag) is the transpose of C(lag)), got "
+                             f"{lag[~(lag >= 0)].reshape(-1)[0].item()}")
+        single = lag.dim() == 0
+        if lag.dim() < 2:
+            lag = lag.reshape(-1, 1).expand(-1, B)
+        return lag.to(dev).contiguous(), single
+
+    def autocovariance(self, ta, tb, lags, *, covariance: bool = False, check: bool = True) -> RowDenseAutocovariance:
+        """The lagged second moment ALONG TIME, inside each row, over the window `[a, b]` between `ta` and `tb` (true time, in
+        either order: the same bits), `T = b - a` -> `RowDenseAutocovariance(duration, mean, autocovariance, covariance)`, all
+        fp64, without the `Q` dimension for two single times and without the `K` dimension for a single lag — the
+        autocorrelation function of a long, oscillatory or chaotic solve and what is built on it: decorrelation times, the
+        period of a limit cycle (the first maximum of `C_ii`), phase lags between components (the peak of `C_ij`), Green-Kubo
+        integrals, the power spectrum.  `autocovariance` `[K, Q, B, *row_shape]`: `C_ii(tau) = 1 / (T - tau) int_a^(b - tau)
+        (y_i(t) - m_i) (y_i(t + tau) - m_i) dt`, centred on the WHOLE-window mean `m` and divided by the overlap length.
+        `covariance=True` also gives `covariance` `[K, Q, B, L, L]`, `L = prod(row_shape) <= 256`, entry `[i, j] = C_ij(tau)`
+        with `i` at `t` and `j` at `t + tau`: not symmetric for `tau > 0`, and `autocovariance` is then its diagonal bit for
+        bit; it holds `8 * K * Q * B * L^2` bytes.  `duration` `[Q, B]` and `mean` `[Q, B, *row_shape]` are those of
+        `time_moments(ta, tb)` bit for bit: the same kernel runs first and its mean is an input of the lagged kernels.
+        `lags`: a number, `[K]` (the same lags for every row) or `[K, B]` (lags per row), real, on any device, taken as fp64,
+        `K >= 1`; a lag is a true-time offset `tau >= 0`.  Negative lags are refused: `C(-tau)` is the transpose of `C(tau)`.
+        A lag is valid for a window if `tau == 0` or `0 < tau < T`; `tau == 0` on a zero-length window gives exact zeros, as
+        `time_moments` does.  `check=True` raises ValueError naming the first invalid (lag, query, row) — after the
+        out-of-range queries of `ta`, then `tb`, which behave as in `time_moments` — from the one read of the search's status
+        words; `check=False` gives NaN for that (lag, window) alone and reads nothing.  Exact on the record up to rounding:
+        the overlap is cut at the union of the breakpoints of the steps under `t` and of the steps under `t + tau` shifted by
+        `-tau`; on every piece both factors are quartics in `t`, and the 5-point Gauss-Legendre rule of `time_moments`
+        integrates their product exactly (include/tdeq_hip.h states the pieces, the nodes and the order of the sums).  At
+        `tau = 0` `covariance` equals `time_moments(...).covariance` within the error bound, not in its last bits: another
+        kernel, which stores no mirror.  A `jump_dy` impulse has measure zero.  A descending solve is handled in true time:
+        in solver time the factor at `t + tau` is the EARLIER one, so the two factors swap roles; the matrix kernel does that
+        once in its prologue (the per-element kernel has nothing to swap).  A ROCm state runs HIP kernels:
+        `tdeq_row_dense_time_lagged`, one lane per lag, window and 16-byte element on a walk with two cursors, and for the
+        matrix `tdeq_row_dense_time_lagged_gram`, a non-symmetric weighted Gram product on the fp64 matrix instructions, one
+        workgroup per lag, window and ordered pair of 64-element blocks (four (lag, window) per workgroup for `L <= 16`) — no
+        workspace, no atomics, the same bits from run to run; the matrix is launched in slices that stay under 256 MiB and
+        does not depend on the slicing.  A CPU state runs the same definition as numpy ops in fp64: the same bits for
+        `autocovariance` without a covariance, the same error bound for the covariance.  Builds and caches nothing.
+        Gradients, normalisation to correlations (divide by `C_ii(0)`) and lags pooled over rows are out of scope."""
+        what = "dense.autocovariance(ta, tb, lags)"
+        if not isinstance(covariance, bool):
+            raise ValueError(f"{what}: covariance must be a bool, got {covariance!r}")
+        B, L, dev, f64 = self._shape[0], self.coeffs.shape[2], self.coeffs.device, torch.float64
+        if covariance and L > TDEQ_ROW_TIME_MOMENTS_MAX_COV_LEN:
+            raise ValueError(f"{what}: covariance=True takes rows of at most {TDEQ_ROW_TIME_MOMENTS_MAX_COV_LEN} elements, "
+                             f"this row has {L}")
+        lag, one_lag = self._lags(what, lags)
+        K = lag.shape[0]
+        record = (self.coeffs, self._ta, self._tb, self._sign)
+        duration, cov = torch.empty(0, dtype=f64, device=dev), torch.empty(K, 0, L, L, dtype=f64, device=dev)
+        flags, ends = [_NONE], []
+
+        def third_list(lists):
+            """-> (tau [K, Q * B], the first invalid (lag, query, row) as a 0-dim tensor, the lead cursor's queries [K * Q, B])."""
+            tq, tq2 = lists[2], lists[5]
+            ends[:] = [tq, tq2]
+            Q = tq.shape[0]
+            if K * Q * B >= _NONE:
+                raise ValueError(f"{what}: {K * Q * B} (lag, query, row) in one call; their index is a 32-bit word")
+            lo, hi = torch.minimum(tq, tq2), torch.maximum(tq, tq2)
+            tau = lag[:, None, :].expand(K, Q, B).contiguous()
+            valid = (tau == 0) | ((tau > 0) & (tau < hi - lo))
+            invalid = ~valid.view(-1)
+            first = torch.where(invalid.any(), invalid.to(torch.uint8).argmax(), _NONE)
+            t3 = torch.where(valid, torch.minimum(lo + tau, hi), lo.expand(K, Q, B))
+            return tau.view(K, Q * B), first, t3.view(K * Q, B).contiguous()
+
+        def host(lists):
+            nonlocal duration, cov
+            H = rowwise.HostRowKernels
+            tau, first, t3 = third_list(lists)
+            flags[0] = int(first)
+            duration, mean, _, _ = H.quartic_time_moments(*record, False, *lists)
+            seg3 = self._search_host(t3)[0].view(K, -1)
+            auto, cov = H.quartic_time_lagged(*record, covariance, mean, tau, seg3, *lists)
+            return mean, auto
+
+        def device(outs, lists, status):
+            nonlocal duration, cov
+            n = lists[0].numel()
+            mean, auto = outs
+            duration = torch.empty(n, dtype=f64, device=dev)
+            self._k.row_dense_time_moments(duration, mean, torch.empty(n, L, dtype=f64, device=dev), *record, *lists)
+            tau, first, t3 = third_list(lists)
+            if check:
+                status.copy_(first)
+            # (a valid lag's query lies inside the window and an invalid one's at its start: this status word says nothing new)
+            seg3 = self._search_device(t3, torch.full((1,), _NONE, dtype=torch.int32, device=dev))[0].view(K, n)
+            if not covariance:
+                self._k.row_dense_time_lagged(auto, mean, tau, seg3, *record, *lists)
+                return
+            cov = torch.empty(K, n, L, L, dtype=f64, device=dev)
+            per = max(1, MOMENTS_WORKSPACE_BYTES // max(8 * B * L * L, 1))        # whole query times per launch
+            if K * (n // B) <= per:
+                self._k.row_dense_time_lagged_gram(cov, auto, mean, tau, seg3, *record, *lists)
+                return
+            for k in range(K):
+                for i in range(0, n, B * per):
+                    j = i + B * per
+                    self._k.row_dense_time_lagged_gram(cov[k:k + 1, i:j], auto[k:k + 1, i:j], mean[i:j], tau[k:k + 1, i:j],
+                                                       seg3[k:k + 1, i:j], *record, *(v.view(-1)[i:j] for v in lists))
+
+        mean, auto = self._ask(what, ("ta", "tb"), (ta, tb), check, [(f64, ()), (f64, (K,))], host, device, flags=flags)
+        if check and flags[0] != _NONE:
+            Q = ends[0].shape[0]
+            k, j, r = flags[0] // (Q * B), flags[0] // B % Q, flags[0] % B
+            raise ValueError("{}: lag {} of query {} of row {} (lag = {}) is neither 0 nor inside (0, T) of its window, T = {}"
+                             .format(what, k, j, r, float(lag[k, r]), abs(float(ends[1][j, r]) - float(ends[0][j, r]))))
+        single = mean.dim() == len(self._shape)
+        duration = duration.view(B) if single else duration.view(-1, B)
+        cov = (cov.view(K, B, L, L) if single else cov.view(K, -1, B, L, L)) if covariance else None
+        if one_lag:
+            auto, cov = auto[0], None if cov is None else cov[0]
+        return RowDenseAutocovariance(duration, mean, auto, cov)
 
     # -- order statistics across rows: a radix select on the record, nothing of size [Q, B, L] is built ----------------------
     def _quantile_ranks(self, what: str, probs, ranks, as_probs: bool = False) -> list:
@@ -1188,6 +1340,19 @@ def odeint_rowwise_dense(func, y0, t0, t1, *, rtol=1e-7, atol=1e-9, method="dopr
     16`) that walks the steps serially in stages of 4 steps = 20 nodes through LDS: no workspace, no atomics, the same bits
     from run to run, an error bound against the CPU path; `variance` is then its diagonal.  A zero-length window gives the
     record's value and exact zeros; breakpoints and `jump_dy` impulses add nothing.  Nothing is built or cached.
+
+    Lagged second moments along time: `dense.autocovariance(ta, tb, lags, covariance=False)` -> `RowDenseAutocovariance(
+    duration, mean, autocovariance, covariance)`: per lag `tau >= 0` (a number, `[K]` or `[K, B]`) and ELEMENT `C_ii(tau) = 1 /
+    (T - tau) int_a^(b - tau) (y_i(t) - m_i)(y_i(t + tau) - m_i) dt` around the whole-window mean of `time_moments` and, on
+    request, the `[L, L]` matrix `C_ij(tau)` with `i` at `t` and `j` at `t + tau` — the autocorrelation function of a long or
+    chaotic solve, the period of a limit cycle, phase lags between components; all fp64.  Exact on the record up to rounding,
+    across step boundaries too: the overlap is cut at the breakpoints of the steps under `t` and of the steps under `t + tau`
+    shifted back, both factors are quartics on every piece, and the rule of `time_moments` integrates their product exactly.
+    `tdeq_row_dense_time_moments` runs first and its mean is an input; a third search per lag places the second cursor;
+    `tdeq_row_dense_time_lagged` (one lane per lag, window and element on a walk with two cursors) and the numpy path of a CPU
+    state have the same bits; the matrix (`tdeq_row_dense_time_lagged_gram`) is a non-symmetric Gram product on
+    `v_mfma_f64_16x16x4_f64` over all ordered pairs of 64-element blocks: no workspace, no atomics, an error bound against the
+    CPU path.  Nothing is built or cached.
 
     Order statistics across rows: `dense.quantiles(t, probs)` or `dense.quantiles(t, ranks=...)` -> `[P, Q, *row_shape]`, per
     time and ELEMENT the value of rank `k_p` among the B rows' `dense(t)` (`probs` by the "lower" rule `k = floor(p * (B - 1))`,
